@@ -14,7 +14,7 @@ it is already running under a launcher (RANK in the environment).  Frames shard 
 scaling); the only collective on the path is the one-time RCCL broadcast of the packed weight blobs, HBM to HBM,
 inside libpadel_hip.so (pa_engine_bcast_weights) — executed at N=1 too.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4] [--batch 64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4] [--batch 64] [--dump-outputs DIR]
 
 Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline`, `cpu_baseline` and `parity`
 (`parity.low_noise_heads`: the same graphs with well-conditioned heads, where the literal 1e-3 px bar is checked).
@@ -84,6 +84,9 @@ def parse():
     ap.add_argument("--no-compare", action="store_true", help="skip the fp32-MFMA comparison leg of engine_only (profiling runs)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="frames of the CPU baseline sample (0 = auto)")
     ap.add_argument("--dump-ops", default="", help="write the per-op profile (CSV) of the roofline pass here")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed path returned for its last step as DIR/<tracker>.npy (float64, rank 0; "
+                         "at most 64 MB in all: larger outputs are cut to a seeded sample of rows)")
     ap.add_argument("--no-host-frames", action="store_true",
                     help="skip the end-to-end-from-host leg (clip in page-locked host memory: sequential = one upload per "
                          "tracker like the reference, fan-out = one upload per batch — PCIe-inclusive rates)")
@@ -110,6 +113,8 @@ def parse():
                     help="f32: the parity path (the reference runs half=False) — the headline; f16: fp16 activations / "
                          "weights with fp32 accumulation (BASELINE configs[4]), reports its own L-inf vs the fp32 oracle")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps: at least one timed step")
     if a.fake_engine:
         a.quick = a.no_roofline = True
     if a.quick:
@@ -381,6 +386,50 @@ def build_trackers(names, frames, rank, B, H, W, eng, tmp, half=False, frac=0.01
     return trackers, flops
 
 
+# --dump-outputs: under 64 MB in all, .npy headers included, whether MB means 10^6 or 2^20 bytes
+DUMP_LIMIT_BYTES = 60 << 20
+
+
+def runner_outputs(trackers, frames_idx):
+    """What TrackingRunner.run() left its caller for the frames `frames_idx`, one float64 table per tracker with the frame
+    index in column 0: players = x1, y1, x2, y2, confidence, class id, track id (-1: none) per player; pose = x, y (source
+    pixels) of every keypoint per person; ball = x, y, visibility per frame."""
+    out = {}
+    for name, t in trackers.items():
+        preds, rows = t.results.predictions, []
+        for f in frames_idx:
+            if name == "players":
+                rows += [[f, *p.xyxy, p.confidence, p.class_id, -1 if p.id is None else p.id] for p in preds[f].players]
+            elif name == "pose":
+                rows += [[f, *(v for k in person.player_keypoints for v in k.xy)] for person in preds[f].players_keypoints]
+            else:
+                rows.append([f, *preds[f].xy, preds[f].visibility])
+        width = {"players": 8, "ball": 4}.get(name) or 1 + 2 * TRACKERS[name]["kpt"][0]
+        out[name] = np.asarray(rows, np.float64).reshape(-1, width)
+    return out
+
+
+def engine_outputs(last):
+    """What pa_yolo_infer returned in the last engine-only step, one float64 table per tracker with one row per detection:
+    frame, x1, y1, x2, y2, confidence, class id, then x, y, confidence of every keypoint on pose models."""
+    out = {}
+    for name, (boxes, kpts, counts) in last.items():
+        out[name] = np.concatenate([np.concatenate([np.full((c, 1), i), boxes[i, :c]] + ([] if kpts is None else [kpts[i, :c]]), 1)
+                                    for i, c in enumerate(counts.tolist())]).astype(np.float64)
+    return out
+
+
+def write_outputs(d, tables):
+    """DIR/<name>.npy.  Beyond DUMP_LIMIT_BYTES in all, every table keeps the same fraction of its rows, a sample drawn with
+    a fixed seed (the frame column says where each kept row came from)."""
+    keep = min(1.0, DUMP_LIMIT_BYTES / max(sum(x.nbytes for x in tables.values()), 1))
+    Path(d).mkdir(parents=True, exist_ok=True)
+    for name, x in tables.items():
+        if keep < 1.0:
+            x = x[np.sort(np.random.default_rng(0).choice(len(x), int(len(x) * keep), replace=False))]
+        np.save(Path(d) / f"{name}.npy", x)
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "RANK" not in os.environ:
@@ -456,6 +505,8 @@ def main():
         dt = time.perf_counter() - t0
         return eng.allreduce_max(dt), runner
 
+    last_infer = {}          # the arrays of the latest engine_step (--dump-outputs --engine-only)
+
     def engine_step():
         tot = 0
         for name in names:
@@ -465,6 +516,7 @@ def main():
                 max_det=1 if name == "ball" else 300,
                 pre_mode=E.PRE_PIL_STRETCH if cfg["pre"] == "pil" else E.PRE_LETTERBOX, channel_reverse=cfg["rev"],
                 reuse_outputs=True)
+            last_infer[name] = (boxes, kpts, counts)
             tot += int(counts.sum())
         return tot
 
@@ -529,6 +581,8 @@ def main():
         dt_e = eng.allreduce_max(time.perf_counter() - t0)
         out["engine_only"] = {"value": round(world * B * K / dt_e, 2), "unit": "frames/s", "ms_per_step": round(1e3 * dt_e / K, 3),
                               "what": "the same K steps calling pa_yolo_infer directly: no Detections / PolygonZone / ByteTrack / objects"}
+        if a.dump_outputs and a.engine_only and rank == 0:
+            write_outputs(a.dump_outputs, engine_outputs(last_infer))
         if a.dtype == "f32" and a.impl == "bx3" and not a.no_compare:
             out["engine_only"]["fp32_mfma_kernels"] = fp32_mfma_leg()
         out["config"]["detections_per_step_rank0"] = ndet
@@ -565,6 +619,9 @@ def main():
                 out["ms_per_step"] = round(1e3 * dt / K, 3)
                 out["config"]["timed_path_n_gpus"] = "TrackingRunner(distributed=True), ONE clip of world x K x B frames: shards, packed gather to rank 0"
                 out["config"]["runner_seconds_per_tracker_rank0"] = {k: round(v["seconds"], 4) for k, v in runner.timings.items()}
+            if a.dump_outputs and rank == 0:
+                # the last step = the last B frames of every rank's shard (at N > 1 rank 0 holds the merged results of all shards)
+                write_outputs(a.dump_outputs, runner_outputs(trackers, [r * K * B + (K - 1) * B + i for r in range(world) for i in range(B)]))
             kept = sum(len(p) for p in trackers["players"].results.predictions) if "players" in trackers else 0
             out["config"]["tracked_players_rank0"] = kept
             out["config"]["frames_with_results_rank0"] = {n_: len(t_.results) for n_, t_ in trackers.items()}

@@ -10,6 +10,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
+
 ROOT = Path(__file__).resolve().parents[1]
 
 
@@ -65,3 +67,46 @@ def test_bench_main_world2_gloo_fake_engine(tmp_path):
     assert r1["weight_checksums"] == r0["weight_checksums"] and all(v != 0 for v in r0["weight_checksums"].values())
     # the sharded runner's device stage goes through the two-call form (submit_sample / collect_sample -> yolo_submit / yolo_wait)
     assert "submit" in r0["log"] and "submit" in r1["log"]
+
+
+def _fake_bench_world1(tmp_path, *args):
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--warmup", "1", "--fake-engine", "--batch", "4", "--height", "72",
+           "--width", "128", "--scales", "players=n,ball=n,pose=n", *args]
+    p = subprocess.run(cmd, cwd=tmp_path, env=dict(os.environ, OMP_NUM_THREADS="2"), capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    return json.loads(p.stdout)
+
+
+def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):
+    """``--dump-outputs DIR``: float64 tables of what the timed runner returned for its last step — frames (K - 1) B .. K B - 1
+    in column 0 — identical from run to run; ``--steps`` sets the number of timed steps.  ``--engine-only``: the arrays of the
+    last engine-only step (frames 0 .. B - 1 of the batch)."""
+    B, K = 4, 3
+    for run in ("a", "b"):
+        d = _fake_bench_world1(tmp_path, "--steps", str(K), "--dump-outputs", str(tmp_path / run))
+        assert d["steps"] == K and d["config"]["frames_with_results_rank0"] == {"players": K * B, "ball": K * B, "pose": K * B}
+    for name, width in (("players", 8), ("ball", 4), ("pose", 1 + 13 * 2)):
+        x = np.load(tmp_path / "a" / f"{name}.npy")
+        assert x.dtype == np.float64 and x.shape[1:] == (width,) and len(x) > 0, (name, x.dtype, x.shape)
+        assert set(x[:, 0].tolist()) <= set(range((K - 1) * B, K * B)), name
+        np.testing.assert_array_equal(x, np.load(tmp_path / "b" / f"{name}.npy"))
+    assert np.load(tmp_path / "a" / "ball.npy")[:, 0].tolist() == list(range((K - 1) * B, K * B))      # one row per frame
+    _fake_bench_world1(tmp_path, "--steps", str(K), "--engine-only", "--dump-outputs", str(tmp_path / "e"))
+    for name, width in (("players", 7), ("ball", 7), ("pose", 7 + 13 * 3)):
+        x = np.load(tmp_path / "e" / f"{name}.npy")
+        assert x.dtype == np.float64 and x.shape[1:] == (width,) and len(x) > 0, (name, x.dtype, x.shape)
+        assert set(x[:, 0].tolist()) <= set(range(B)), name
+
+
+def test_dump_outputs_seeded_sample_under_the_limit(tmp_path, monkeypatch):
+    """Tables larger than the limit in all keep the same fraction of their rows, the same rows every time, in order."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 6400)
+    tables = {"a": np.arange(800.0).reshape(100, 8), "b": np.arange(400.0).reshape(100, 4)}
+    bench.write_outputs(tmp_path / "x", tables)
+    bench.write_outputs(tmp_path / "y", tables)
+    a, b = np.load(tmp_path / "x" / "a.npy"), np.load(tmp_path / "x" / "b.npy")
+    assert a.nbytes + b.nbytes <= 6400 and len(a) == len(b) == 66
+    assert (np.diff(a[:, 0]) > 0).all() and np.isin(a, tables["a"]).all() and (a[:, 0] % 8 == 0).all()
+    np.testing.assert_array_equal(a, np.load(tmp_path / "y" / "a.npy"))
+    np.testing.assert_array_equal(b, np.load(tmp_path / "y" / "b.npy"))
