@@ -14,10 +14,14 @@ it is already running under a launcher (RANK in the environment).  Frames shard 
 scaling); the only collective on the path is the one-time RCCL broadcast of the packed weight blobs, HBM to HBM,
 inside libpadel_hip.so (pa_engine_bcast_weights) — executed at N=1 too.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4] [--batch 64] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4] [--batch 64] [--dump-outputs DIR] [--full]
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus `roofline`, `cpu_baseline` and `parity`
-(`parity.low_noise_heads`: the same graphs with well-conditioned heads, where the literal 1e-3 px bar is checked).
+A plain run does what the headline needs and nothing else: set-up, W warm-up steps, the K timed steps, the outputs of
+`--dump-outputs`, and ONE JSON line (rank 0) with the driver's contract fields.  `--full` adds every other leg to that
+line: `engine_only` (and the strict-fp32 kernels beside it), `objects_materialised`, `value_lazy_objects`,
+`value_eager_objects`, `host_frames`, `reference_default`, `roofline` (per-op profile, PMC traffic passes), `cpu_baseline`
+and `parity` (`parity.low_noise_heads`: the same graphs with well-conditioned heads, where the literal 1e-3 px bar is
+checked), at N > 1 `replica_runners`; the `--no-*` options and `--quick` drop legs of a `--full` run.
 """
 from __future__ import annotations
 
@@ -77,6 +81,9 @@ def parse():
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--scales", default="", help="override scales, e.g. players=n,pose=n")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: engine-only, lazy / eager result objects, host frames, the reference's "
+                         "default trackers, roofline, CPU baseline and parity (minutes; a plain run times the headline alone)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU oracle leg (cpu_baseline and parity)")
     ap.add_argument("--no-fp64", action="store_true", help="parity leg: skip the fp64 oracle (noise floor)")
     ap.add_argument("--no-roofline", action="store_true")
@@ -115,6 +122,10 @@ def parse():
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps: at least one timed step")
+    if a.dump_ops and not a.full:
+        ap.error("--dump-ops: the per-op profile belongs to the roofline leg, which runs with --full")
+    if not a.full:
+        a.quick = a.no_roofline = True
     if a.fake_engine:
         a.quick = a.no_roofline = True
     if a.quick:
@@ -175,13 +186,17 @@ def conv1x1_roofline(c1, fl1, ms1, peak1, a):
     return out
 
 
-def make_state_dict(name, cfg, frames, frac=0.01, seed_offset=0):
+def make_state_dict(name, cfg, frames, frac=0.01, seed_offset=0, calib_dtype="f32"):
     """Setup (untimed): seeded synthetic checkpoint with data-calibrated BatchNorm statistics
     (oracle/synth_weights.py — weight synthesis, not part of the measured path).  1280-input models
-    are calibrated on a 640x640 centre crop of the network input (same statistics, 4x cheaper)."""
+    are calibrated on a 640x640 centre crop of the network input (same statistics, 4x cheaper).
+    ``calib_dtype="f64"``: the calibration pass in double precision, which makes the checkpoint independent of torch's thread count
+    (synth_weights.calibrated_state_dict).  The benchmark's own checkpoints are and stay made with the fp32 pass, so their weights
+    follow the host's thread count too: figures of two hosts are figures on slightly different weights."""
     import zlib
     # (the fingerprint of the calibration frames is part of the key: tests build the same tracker for different clips)
-    key = (name, cfg["scale"], cfg["nc"], cfg["kpt"], cfg["imgsz"], frac, seed_offset, zlib.crc32(np.ascontiguousarray(frames[:2]).tobytes()))
+    key = (name, cfg["scale"], cfg["nc"], cfg["kpt"], cfg["imgsz"], frac, seed_offset, zlib.crc32(np.ascontiguousarray(frames[:2]).tobytes())) + \
+        ((calib_dtype,) if calib_dtype != "f32" else ())
     if key in _SD_CACHE:
         return _SD_CACHE[key]
     # the PMC passes of the roofline section re-run this script under rocprofv3: they find the checkpoints of the parent here
@@ -192,6 +207,7 @@ def make_state_dict(name, cfg, frames, frac=0.01, seed_offset=0):
             sd = {k: z[k] for k in z.files}
         _SD_CACHE[key] = sd
         return sd
+    import torch
     from oracle import synth_weights, yolov8_ref as ref
     srcs = source_for_oracle(cfg, frames[:2])
     im = ref.preprocess(srcs, cfg["imgsz"])
@@ -199,7 +215,8 @@ def make_state_dict(name, cfg, frames, frac=0.01, seed_offset=0):
         o = (im.shape[2] - 640) // 2
         im = im[:, :, o:o + 640, o:o + 640].contiguous()
     sd = synth_weights.calibrated_state_dict(cfg["scale"], cfg["nc"], cfg["kpt"], im, cfg["conf"],
-                                             seed=sum(map(ord, name)) + seed_offset, frac=frac)
+                                             seed=sum(map(ord, name)) + seed_offset, frac=frac,
+                                             dtype={"f32": torch.float32, "f64": torch.float64}[calib_dtype])
     _SD_CACHE[key] = sd
     if cfile is not None:
         np.savez(cfile, **{k: np.asarray(v) for k, v in sd.items()})
@@ -481,7 +498,9 @@ def main():
     frames = synth.synthetic_frames(B, H, W, seed=1000 + rank)          # each rank its own shard
     clip = video.DeviceClip(eng, frames, repeat=max(K, Wm, 1))           # resident in HBM before timing
     tmp = tempfile.mkdtemp(prefix="padel_bench_")
-    os.environ.setdefault("PADEL_BENCH_SD_CACHE", tmp)      # calibrated checkpoints on disk: the PMC sub-runs (measure_traffic) reuse them
+    # (only a run that will start them: a plain run writes no checkpoint files)
+    if a.traffic == "live" and not a.no_roofline:
+        os.environ.setdefault("PADEL_BENCH_SD_CACHE", tmp)      # calibrated checkpoints on disk: the PMC sub-runs (measure_traffic) reuse them
     with contextlib.redirect_stdout(sys.stderr):
         trackers, flops_per_frame = build_trackers(names, frames, rank, B, H, W, eng, tmp, half=a.dtype == "f16", replay=a.replay)
 
@@ -570,23 +589,29 @@ def main():
 
     with contextlib.redirect_stdout(sys.stderr):
         # ---- engine-only: K steps straight through the C-ABI (round 1's `value`)
-        ndet = 0
-        for _ in range(max(Wm, 1)):
-            ndet = engine_step()
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(K):
+        # (a leg of --full; with --engine-only these ARE the timed steps)
+        if a.full or a.engine_only:
+            ndet = 0
+            for _ in range(max(Wm, 1)):
+                ndet = engine_step()
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(K):
+                engine_step()
+            fence()
+            dt_e = eng.allreduce_max(time.perf_counter() - t0)
+            out["engine_only"] = {"value": round(world * B * K / dt_e, 2), "unit": "frames/s", "ms_per_step": round(1e3 * dt_e / K, 3),
+                                  "what": "the same K steps calling pa_yolo_infer directly: no Detections / PolygonZone / ByteTrack / objects"}
+            if a.dump_outputs and a.engine_only and rank == 0:
+                write_outputs(a.dump_outputs, engine_outputs(last_infer))
+            if a.dtype == "f32" and a.impl == "bx3" and not a.no_compare:
+                out["engine_only"]["fp32_mfma_kernels"] = fp32_mfma_leg()
+            out["config"]["detections_per_step_rank0"] = ndet
+            out["config"]["engine_only_frames_per_s"] = out["engine_only"]["value"]
+        elif Wm == 0:
+            # --warmup 0 has never meant a cold first timed step: one untimed pass through every model (arena, captured op lists,
+            # page-locked result sets) precedes the runner, as the engine-only leg did when it ran in every run
             engine_step()
-        fence()
-        dt_e = eng.allreduce_max(time.perf_counter() - t0)
-        out["engine_only"] = {"value": round(world * B * K / dt_e, 2), "unit": "frames/s", "ms_per_step": round(1e3 * dt_e / K, 3),
-                              "what": "the same K steps calling pa_yolo_infer directly: no Detections / PolygonZone / ByteTrack / objects"}
-        if a.dump_outputs and a.engine_only and rank == 0:
-            write_outputs(a.dump_outputs, engine_outputs(last_infer))
-        if a.dtype == "f32" and a.impl == "bx3" and not a.no_compare:
-            out["engine_only"]["fp32_mfma_kernels"] = fp32_mfma_leg()
-        out["config"]["detections_per_step_rank0"] = ndet
-        out["config"]["engine_only_frames_per_s"] = out["engine_only"]["value"]
         # ---- through the runner (the metric's path).  Round 5: `value` is the run with the result objects built where the
         # reference builds them — every Player / PlayerKeypoints object inside predict_sample (players_tracker.py:371-378,
         # players_keypoints_tracker.py:303-320; trackers.set_eager_objects(True): array-backed objects, ~0.5 us each); the run
@@ -594,13 +619,14 @@ def main():
         from padel_analytics_amd import trackers as T
         if not a.engine_only:
             T.set_eager_objects(True)
-            if Wm > 0:
-                run_runner(clip, Wm)
-            dt, runner = run_runner(clip, K)
-            out["value"] = round(world * B * K / dt, 2)
-            out["ms_per_step"] = round(1e3 * dt / K, 3)
-            out["config"]["runner_seconds_per_tracker_rank0"] = {k: round(v["seconds"], 4) for k, v in runner.timings.items()}
-            out["config"]["runner_host_tail_seconds_rank0"] = {k: round(v["host_tail_seconds"], 4) for k, v in runner.timings.items() if "host_tail_seconds" in v}
+            if world == 1 or a.full:          # at N > 1 the replica runners are a leg of --full: `value` is the sharded runner below
+                if Wm > 0:
+                    run_runner(clip, Wm)
+                dt, runner = run_runner(clip, K)
+                out["value"] = round(world * B * K / dt, 2)
+                out["ms_per_step"] = round(1e3 * dt / K, 3)
+                out["config"]["runner_seconds_per_tracker_rank0"] = {k: round(v["seconds"], 4) for k, v in runner.timings.items()}
+                out["config"]["runner_host_tail_seconds_rank0"] = {k: round(v["host_tail_seconds"], 4) for k, v in runner.timings.items() if "host_tail_seconds" in v}
             if world > 1:
                 # N > 1: the path BASELINE configs[3] names (reference trackers/runner.py:185-236 over ONE clip): a single clip
                 # of world x K x B frames, TrackingRunner(distributed=True) — every rank runs the stateless part of each tracker
@@ -609,8 +635,9 @@ def main():
                 # over ranks with the gathers and rank 0's sequential stages inside.  THIS is `value` at N > 1; the
                 # independent-replica figure above (each rank its own runner over its own clip: an upper bound that omits the
                 # gather and the rank-0 stage) stays beside it.
-                out["replica_runners"] = {"value": out["value"], "ms_per_step": out["ms_per_step"],
-                                          "what": "N independent TrackingRunner.run() over N private clips: no gather, ByteTrack per rank"}
+                if a.full:
+                    out["replica_runners"] = {"value": out["value"], "ms_per_step": out["ms_per_step"],
+                                              "what": "N independent TrackingRunner.run() over N private clips: no gather, ByteTrack per rank"}
                 gclip = clip.alias(world * max(K, Wm, 1))       # rank r only ever reads frames [r K B, (r + 1) K B): its own
                 if Wm > 0:
                     run_runner(gclip, world * Wm, distributed=True)
@@ -627,10 +654,11 @@ def main():
             out["config"]["frames_with_results_rank0"] = {n_: len(t_.results) for n_, t_ in trackers.items()}
         else:
             out["value"], out["ms_per_step"] = out["engine_only"]["value"], out["engine_only"]["ms_per_step"]
+        T.set_eager_objects(False)          # (read by the containers' constructors alone: the count below is not affected)
         # how many result OBJECTS the timed run created (`Players` / `PlayersKeypoints` can keep the detector's arrays and build
         # their `Player` / `PlayerKeypoints` objects on first access; the reference — and `value` — build them eagerly,
         # players_tracker.py:371-378): count what the timed region materialised
-        if not a.engine_only:
+        if a.full and not a.engine_only:
             om = {}
             for nm_, t_ in trackers.items():
                 preds = t_.results.predictions
@@ -645,7 +673,6 @@ def main():
                 om[nm_] = {"containers": len(preds), "array_backed": True, "objects_built_inside_timed_region": inside,
                            "objects_total": total, "build_all_ms": round(1e3 * (time.perf_counter() - t1_), 2)}
             out["objects_materialised"] = om
-            T.set_eager_objects(False)
             if world == 1:
                 run_runner(clip, 1)
                 dt_lz, _ = run_runner(clip, K)

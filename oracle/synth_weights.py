@@ -29,7 +29,7 @@ class _Calibrator(ref.YoloV8Ref):
     """Walks the graph like the oracle but sets BN running stats from the data before fusing."""
 
     def _conv(self, x, prefix, k, s):
-        w = ref._t(self.sd, f"{prefix}.conv.weight").float()
+        w = ref._t(self.sd, f"{prefix}.conv.weight").float().to(x.dtype)
         y = F.conv2d(x, w, None, stride=s, padding=k // 2)
         mu = y.mean(dim=(0, 2, 3))
         var = y.var(dim=(0, 2, 3), unbiased=False).clamp_min(1e-4)
@@ -41,11 +41,18 @@ class _Calibrator(ref.YoloV8Ref):
 
 @torch.no_grad()
 def calibrated_state_dict(scale: str, nc: int, kpt_shape: Optional[tuple], calib_input: torch.Tensor,
-                          conf: float, seed: int = 0, frac: float = 0.01, target_class: int = 0):
-    """calib_input: (B,3,H,W) fp32 network input (already preprocessed)."""
+                          conf: float, seed: int = 0, frac: float = 0.01, target_class: int = 0, dtype=torch.float32):
+    """calib_input: (B,3,H,W) fp32 network input (already preprocessed).
+
+    ``dtype``: what the calibration pass is evaluated in.  Every statistic is rounded to an fp16 number, one flipped rounding changes
+    every layer after it, and these networks amplify a perturbation layer by layer.  In fp32 the order in which torch sums a
+    convolution or a mean, which follows its thread count, is enough to flip some: 1, 8-16 and 32 or more threads give three
+    different checkpoints for one seed.  In ``torch.float64`` the checkpoint no longer depends on the thread count (measured on two
+    kinds of host at 1 to 64 threads).  It is still not the same on every CPU: two hosts whose BLAS kernels differ agreed up to
+    model.4 and then differed by one fp16 step in one mean, and from there on everywhere."""
     sd = yolo_arch.synth_state_dict(scale, nc, kpt_shape, seed, cls_bias=0.0, gain=2.0)
-    cal = _Calibrator(sd, nc, kpt_shape)
-    det, _ = cal.head_raw(cal.features(calib_input))
+    cal = _Calibrator(sd, nc, kpt_shape, dtype=dtype)
+    det, _ = cal.head_raw(cal.features(calib_input.to(dtype)))
     # make `target_class` the arg-max on most anchors that pass (reference filters classes=[0])
     logit_t = torch.cat([d[:, 64 + target_class].reshape(-1) for d in det]).numpy()
     target = float(np.log(conf / (1 - conf)))

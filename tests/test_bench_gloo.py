@@ -2,7 +2,8 @@
 tests/fake_engine.py, started exactly the way the driver starts it (one process per rank, RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_* in the environment).  Checked: ONE JSON line, from rank 0 only; ``n_gpus``, ``steps``, ``warmup`` echo the
 command line; ``value`` = world x B x K / (the max-over-ranks time the line reports as ms_per_step); ranks != 0 build
-their models EMPTY and end up with rank 0's weights through the broadcast hook alone."""
+their models EMPTY and end up with rank 0's weights through the broadcast hook alone.  A plain run carries the headline alone;
+the legs beside it (``engine_only``, ``replica_runners``, ...) come with ``--full``."""
 import json
 import os
 import socket
@@ -25,7 +26,7 @@ def test_bench_main_world2_gloo_fake_engine(tmp_path):
     world, B, K, Wm = 2, 4, 2, 1
     port = str(_free_port())
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--steps", str(K), "--warmup", str(Wm), "--fake-engine",
-           "--batch", str(B), "--height", "72", "--width", "128", "--scales", "players=n,ball=n,pose=n"]
+           "--full", "--batch", str(B), "--height", "72", "--width", "128", "--scales", "players=n,ball=n,pose=n"]
     procs = []
     for r in range(world):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=port,
@@ -75,6 +76,71 @@ def _fake_bench_world1(tmp_path, *args):
     p = subprocess.run(cmd, cwd=tmp_path, env=dict(os.environ, OMP_NUM_THREADS="2"), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     return json.loads(p.stdout)
+
+
+FULL_LEGS = ("engine_only", "objects_materialised", "value_lazy_objects", "value_eager_objects", "host_frames", "reference_default",
+             "roofline", "cpu_baseline", "parity", "replica_runners")
+
+
+def test_plain_run_times_the_headline_alone(tmp_path):
+    """Without ``--full`` the line carries the contract fields and none of the other legs; ``--full`` brings them back (under the
+    fake engine, which implies ``--quick``: the engine-only, object-count and lazy-object legs)."""
+    B, K = 4, 2
+    d = _fake_bench_world1(tmp_path, "--steps", str(K))
+    assert not [k for k in FULL_LEGS if k in d], [k for k in FULL_LEGS if k in d]
+    assert d["metric"].startswith("frames/sec") and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"]
+    assert d["steps"] == K and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert abs(d["value"] - B * K / (d["ms_per_step"] * K / 1e3)) <= 0.02 * d["value"]
+    assert d["config"]["frames_with_results_rank0"] == {"players": K * B, "ball": K * B, "pose": K * B}
+    assert d["config"]["engine_only_frames_per_s"] is None
+    f = _fake_bench_world1(tmp_path, "--steps", str(K), "--full")
+    assert {"engine_only", "objects_materialised", "value_lazy_objects"} <= set(f)
+    assert f["config"]["engine_only_frames_per_s"] == f["engine_only"]["value"]
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "n_gpus"):
+        assert f[k] == d[k], k
+
+
+def test_plain_run_without_warmup(tmp_path):
+    """``--warmup 0``: one untimed pass through every model (one ``yolo_infer`` each) stands in for the engine-only leg that used
+    to precede the runner; the line and the results are those of K timed steps."""
+    B, K = 4, 2
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "0", "--fake-engine", "--batch", str(B),
+           "--height", "72", "--width", "128", "--scales", "players=n,ball=n,pose=n"]
+    p = subprocess.run(cmd, cwd=tmp_path, env=dict(os.environ, OMP_NUM_THREADS="2"), capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads(p.stdout)
+    assert d["steps"] == K and d["warmup"] == 0 and not [k for k in FULL_LEGS if k in d]
+    assert abs(d["value"] - B * K / (d["ms_per_step"] * K / 1e3)) <= 0.02 * d["value"]
+    assert d["config"]["frames_with_results_rank0"] == {"players": K * B, "ball": K * B, "pose": K * B}
+    log = d["ranks"][0]["log"]
+    # the priming pass comes before the runner's first submit
+    assert "submit" in log and any("infer" in x for x in log[:log.index("submit")]), log
+
+
+def test_plain_run_world2_is_the_sharded_runner_alone(tmp_path):
+    """N > 1 without ``--full``: no replica runners in front, ``value`` is the sharded runner, rank 0 holds all shards."""
+    world, B, K = 2, 4, 2
+    port = str(_free_port())
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--steps", str(K), "--warmup", "1", "--fake-engine",
+           "--batch", str(B), "--height", "72", "--width", "128", "--scales", "players=n,ball=n,pose=n"]
+    procs = [subprocess.Popen(cmd, cwd=tmp_path, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                              env=dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1",
+                                       MASTER_PORT=port, OMP_NUM_THREADS="2")) for r in range(world)]
+    outs = [p.communicate(timeout=900) for p in procs]
+    for r, (p, (so, se)) in enumerate(zip(procs, outs)):
+        assert p.returncode == 0, f"rank {r} failed:\n{se[-3000:]}"
+    assert outs[1][0].strip() == ""
+    d = json.loads(outs[0][0])
+    assert not [k for k in FULL_LEGS if k in d], [k for k in FULL_LEGS if k in d]
+    assert d["n_gpus"] == world and "distributed=True" in d["config"]["timed_path_n_gpus"]
+    assert abs(d["value"] - world * B * K / (d["ms_per_step"] * K / 1e3)) <= 0.02 * d["value"]
+    assert d["config"]["frames_with_results_rank0"] == {"players": world * K * B, "ball": world * K * B, "pose": world * K * B}
+
+
+def test_dump_ops_needs_full(tmp_path):
+    p = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--fake-engine", "--dump-ops", str(tmp_path / "ops.csv")], cwd=tmp_path,
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 2 and "--full" in p.stderr and p.stdout == ""
 
 
 def test_bench_dump_outputs_is_the_last_timed_step(tmp_path):

@@ -126,7 +126,10 @@ def test_fp16_graph_vs_emulation_and_fp32_oracle(gpu_engine, scale, nc, kpt, hw,
         srcs = [f[..., ::-1] for f in frames]
     import bench
     cfg = dict(scale=scale, nc=nc, kpt=kpt, imgsz=S, conf=conf, pre="pil" if pre == "pil" else "letterbox")
-    sd = bench.make_state_dict(f"fp16-{scale}-{nc}-{S}", cfg, frames)
+    # (calibrated in fp64: in fp32 the checkpoint follows torch's thread count — 1, 16 and 64 threads give three different
+    #  networks for this seed, with 72, 73 and 74 oracle detections and 51, 50 and 53 matches on the m / nc 80 case — and the
+    #  test would check a different case with every setting of the host.  In fp64: 51 of 72 at 1, 16 and 64 threads)
+    sd = bench.make_state_dict(f"fp16-{scale}-{nc}-{S}", cfg, frames, calib_dtype="f64")
     g16 = G.build_yolov8(sd, nc, kpt, dtype="f16")
     m = E.Model(gpu_engine, g16)
     m.set_max_batch(2)

@@ -13,16 +13,18 @@
 #   pmc_nms       instruction mix / wait breakdown of nms_kernel and decode_kernel (tools/pmc_nms.sh)
 #   tiles         tools/conv_bench.py --dtype h2 --tiles $TILES (default auto,T323,T303) on $SWEEP_ARGS shapes
 #   tests_sel     python -m pytest $PYTEST_SEL -m gpu (any selection)
-#   bench_c2q / bench_c4q   the other configs with --quick --steps 5 (runner + engine-only + roofline only)
+#   bench_c2q / bench_c4q   the other configs with --full --quick --steps 5 (runner + engine-only + roofline only)
 #   bench_c2d / bench_c4d   the same with the driver's --steps 20 --warmup 5
 #   tests_post    ball / known-answer (decode, NMS) / runner / bench-config suites
-#   bench_driver  the driver's command line: python bench.py --gpus 1 --steps 20 --warmup 5
+#   bench_driver  the driver's command line: python bench.py --gpus 1 --steps 20 --warmup 5 (the headline alone)
 #   tests_f16     the fp16 kernel tests + BASELINE configs[0] / [3] / [4] tests
 #   replay        engine-only c3 with 16 / 32 frames per pass over the op list (MALL residency experiment)
-#   bench         python bench.py --dump-ops (default command line: c3)
-#   bench_short   python bench.py --steps 5 --warmup 2 --dump-ops, engine-only extras skipped where the flag exists
+#   bench         python bench.py --full --dump-ops (every leg, default workload: c3)
+#   bench_short   python bench.py --full --quick --steps 5 --warmup 2 --dump-ops
 #   bench_c2 / bench_c4   the other single-GPU configs
 #   stats         rocprofv3 --kernel-trace --stats of the bench command (summary copied to gpurun_out/<tag>/)
+#                 (a plain run: the runner steps alone; the committed r6*_c3_kernel_stats.csv also hold the engine-only leg
+#                  and the roofline step, which `--full --quick` still traces: launch counts compare only like with like)
 #   pmc           tools/pmc_h2.sh (MFMA busy / wait breakdown / LDS conflicts / L2 hit rate of the h2 conv kernels; three --pmc passes)
 set -u
 TAG=$1; shift
@@ -56,31 +58,31 @@ for stage in "$@"; do
       PADEL_LIB=tools/ab/libpadel_hip_probes.so timeout 300 python tools/timeline_probe.py --kernel h2q --cin 96 --cout 96 --hw 96x160 --out "$OUT/timeline_h2q_96.txt" > /dev/null 2>"$OUT/timeline_96.err"; note "timeline:96" $?
       head -60 "$OUT/timeline_h2q_192.txt"; head -20 "$OUT/timeline_h2q_96.txt"; grep -A3 'epilogue' "$OUT/timeline_h2q_96.txt" | head -5 ;;
     bench)
-      timeout 1200 python bench.py --dump-ops "$OUT/ops_c3.csv" > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"; note $stage $?
+      timeout 1200 python bench.py --full --dump-ops "$OUT/ops_c3.csv" > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"; note $stage $?
       python tools/bench_summary.py "$OUT/bench_c3.json" ;;
     bench_short)
-      timeout 900 python bench.py --steps 5 --warmup 2 --quick --dump-ops "$OUT/ops_c3.csv" > "$OUT/bench_c3_short.json" 2> "$OUT/bench_c3_short.err"; note $stage $?
+      timeout 900 python bench.py --full --steps 5 --warmup 2 --quick --dump-ops "$OUT/ops_c3.csv" > "$OUT/bench_c3_short.json" 2> "$OUT/bench_c3_short.err"; note $stage $?
       python tools/bench_summary.py "$OUT/bench_c3_short.json" ;;
     bench_c2)
-      timeout 900 python bench.py --workload c2 --dump-ops "$OUT/ops_c2.csv" > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"; note $stage $?
+      timeout 900 python bench.py --full --workload c2 --dump-ops "$OUT/ops_c2.csv" > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"; note $stage $?
       python tools/bench_summary.py "$OUT/bench_c2.json" ;;
     bench_c4)
-      timeout 900 python bench.py --workload c4 --dump-ops "$OUT/ops_c4.csv" > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"; note $stage $?
+      timeout 900 python bench.py --full --workload c4 --dump-ops "$OUT/ops_c4.csv" > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"; note $stage $?
       python tools/bench_summary.py "$OUT/bench_c4.json" ;;
     tests_sel)
       timeout 1200 python -m pytest ${PYTEST_SEL:-tests} -m gpu -q --maxfail=5 > "$OUT/pytest_sel.txt" 2>&1; note $stage $?
       grep -E "passed|failed|FAILED|Error" "$OUT/pytest_sel.txt" | tail -12 ;;
     bench_c2d)
-      timeout 600 python bench.py --workload c2 --steps 20 --warmup 5 --quick --dump-ops "$OUT/ops_c2.csv" > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"; note $stage $?
+      timeout 600 python bench.py --full --workload c2 --steps 20 --warmup 5 --quick --dump-ops "$OUT/ops_c2.csv" > "$OUT/bench_c2.json" 2> "$OUT/bench_c2.err"; note $stage $?
       python tools/bench_summary.py "$OUT/bench_c2.json" ;;
     bench_c4d)
-      timeout 600 python bench.py --workload c4 --steps 20 --warmup 5 --quick --dump-ops "$OUT/ops_c4.csv" > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"; note $stage $?
+      timeout 600 python bench.py --full --workload c4 --steps 20 --warmup 5 --quick --dump-ops "$OUT/ops_c4.csv" > "$OUT/bench_c4.json" 2> "$OUT/bench_c4.err"; note $stage $?
       python tools/bench_summary.py "$OUT/bench_c4.json" ;;
     bench_c2q)
-      timeout 600 python bench.py --workload c2 --steps 5 --warmup 2 --quick > "$OUT/bench_c2_quick.json" 2> "$OUT/bench_c2_quick.err"; note $stage $?
+      timeout 600 python bench.py --full --workload c2 --steps 5 --warmup 2 --quick > "$OUT/bench_c2_quick.json" 2> "$OUT/bench_c2_quick.err"; note $stage $?
       python tools/bench_summary.py "$OUT/bench_c2_quick.json" ;;
     bench_c4q)
-      timeout 600 python bench.py --workload c4 --steps 5 --warmup 2 --quick > "$OUT/bench_c4_quick.json" 2> "$OUT/bench_c4_quick.err"; note $stage $?
+      timeout 600 python bench.py --full --workload c4 --steps 5 --warmup 2 --quick > "$OUT/bench_c4_quick.json" 2> "$OUT/bench_c4_quick.err"; note $stage $?
       python tools/bench_summary.py "$OUT/bench_c4_quick.json" ;;
     pmc_nms)
       timeout 900 bash tools/pmc_nms.sh "$GRAFT_REPO_ROOT/$OUT/pmc_nms" > "$OUT/pmc_nms.txt" 2>&1; note $stage $?
