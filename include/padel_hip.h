@@ -292,8 +292,10 @@ int pa_bytetrack_update_batch(pa_bytetrack* b, const float* boxes, const int32_t
  * engine's stream.  kinds/ms/flops are host arrays of capacity cap; returns the number of records. */
 int pa_engine_set_profiling(pa_engine* eng, int enable);
 int pa_model_last_profile(pa_model* m, int cap, int32_t* kinds, float* ms, double* flops, int32_t* ksizes);
-/* same records as CSV text: kind,ksize,M,cout,cin,stride,mf,nf,ms,flops,res per line (mf, nf: the workgroup tile's pixels and
- * channels; res: 1 if the conv adds a residual input it has to read); returns bytes written */
+/* same records as CSV text: kind,ksize,M,cout,cin,stride,mf,nf,ms,flops,res,tile,family per line (mf, nf: the REQUESTED workgroup
+ * tile's pixels and channels; res: 1 if the conv adds a residual input it has to read; tile, family: the tile id the conv
+ * dispatcher launched after every fall-through and the tag of the kernel family that ran — h2t, h2d, h2s, h2s3, h2p, h2q, h2r,
+ * h2v, h2w | bx3t, bx3p | tap | tap16, tap16d, p16, p16q; -1 and empty for ops that are not convs); returns bytes written */
 int pa_model_profile_text(pa_model* m, char* buf, size_t cap);
 
 #ifdef __cplusplus

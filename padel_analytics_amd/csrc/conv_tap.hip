@@ -488,19 +488,19 @@ bool conv_variant_shape(int variant, int* bm, int* bn) {
 }
 
 // hipErrorNotSupported when the layer or the tile is not covered
-hipError_t launch_conv_tap(const ConvArgs& a, int variant, hipStream_t s) {
+hipError_t launch_conv_tap(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
     if ((a.ksize != 3 && a.ksize != 1) || (a.cin & 15) || a.cin < 16) return hipErrorNotSupported;
     switch (variant) {
-        case 6: return launch_t<2, 2, 2, 4>(a, s);    //  64 x 128
-        case 7: return launch_t<2, 2, 2, 3>(a, s);    //  64 x  96
-        case 9: return launch_t<4, 1, 2, 4>(a, s);    // 128 x  64
-        case 10: return launch_t<2, 2, 4, 2>(a, s);   // 128 x  64 (2x2 waves)
-        case 11: return launch_t<4, 1, 2, 2>(a, s);   // 128 x  32
-        case 12: return launch_t<4, 1, 2, 1>(a, s);   // 128 x  16
-        case 13: return launch_t<4, 2, 2, 3>(a, s);   // 128 x  96,  8 waves
-        case 14: return launch_t<4, 2, 2, 4>(a, s);   // 128 x 128,  8 waves
-        case 15: return launch_t<4, 2, 2, 2>(a, s);   // 128 x  64,  8 waves
-        case 20: return launch_t<4, 1, 2, 3>(a, s);   // 128 x  48
+        case 6: return conv_ran(ran, 6, "tap", launch_t<2, 2, 2, 4>(a, s));    //  64 x 128
+        case 7: return conv_ran(ran, 7, "tap", launch_t<2, 2, 2, 3>(a, s));    //  64 x  96
+        case 9: return conv_ran(ran, 9, "tap", launch_t<4, 1, 2, 4>(a, s));    // 128 x  64
+        case 10: return conv_ran(ran, 10, "tap", launch_t<2, 2, 4, 2>(a, s));   // 128 x  64 (2x2 waves)
+        case 11: return conv_ran(ran, 11, "tap", launch_t<4, 1, 2, 2>(a, s));   // 128 x  32
+        case 12: return conv_ran(ran, 12, "tap", launch_t<4, 1, 2, 1>(a, s));   // 128 x  16
+        case 13: return conv_ran(ran, 13, "tap", launch_t<4, 2, 2, 3>(a, s));   // 128 x  96,  8 waves
+        case 14: return conv_ran(ran, 14, "tap", launch_t<4, 2, 2, 4>(a, s));   // 128 x 128,  8 waves
+        case 15: return conv_ran(ran, 15, "tap", launch_t<4, 2, 2, 2>(a, s));   // 128 x  64,  8 waves
+        case 20: return conv_ran(ran, 20, "tap", launch_t<4, 1, 2, 3>(a, s));   // 128 x  48
     }
     return hipErrorNotSupported;
 }

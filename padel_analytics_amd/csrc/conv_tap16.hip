@@ -559,32 +559,32 @@ static hipError_t launch_t16(const ConvArgs& a_in, hipStream_t s) {
 }
 
 // tile ids: the fp32 id space (conv_variant_shape) + 30.. for the larger per-wave tiles only the fp16 path has
-hipError_t launch_conv_tap16(const ConvArgs& a, int variant, hipStream_t s) {
+hipError_t launch_conv_tap16(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
     if ((a.ksize != 3 && a.ksize != 1) || (a.cin & 31) || a.cin < 32) return hipErrorNotSupported;
     if (variant >= 300 && variant < 400) {           // fp16 patch kernel (conv_patch16.hip), or a tap tile where it does not apply
         const int nf = variant - 300;
-        if (conv_p16_supported(a)) return launch_conv_p16(a, nf, s);
+        if (conv_p16_supported(a)) return conv_ran(ran, variant, nf >= 20 ? "p16q" : "p16", launch_conv_p16(a, nf, s));
         variant = nf == 3 ? 20 : nf == 4 ? 9 : 31;
     }
     switch (variant) {
-        case 6: return launch_t16<2, 2, 2, 4>(a, s);    //  64 x 128
-        case 7: return launch_t16<2, 2, 2, 3>(a, s);    //  64 x  96
-        case 9: return launch_t16<4, 1, 2, 4>(a, s);    // 128 x  64
-        case 11: return launch_t16<4, 1, 2, 2>(a, s);   // 128 x  32
-        case 12: return launch_t16<4, 1, 2, 1>(a, s);   // 128 x  16
-        case 20: return launch_t16<4, 1, 2, 3>(a, s);   // 128 x  48
-        case 30: return launch_t16<2, 2, 4, 4>(a, s);   // 128 x 128, 4 waves of 64 x 64
-        case 31: return launch_t16<2, 2, 4, 3>(a, s);   // 128 x  96
-        case 32: return launch_t16<2, 2, 4, 2>(a, s);   // 128 x  64
+        case 6: return conv_ran(ran, 6, "tap16", launch_t16<2, 2, 2, 4>(a, s));    //  64 x 128
+        case 7: return conv_ran(ran, 7, "tap16", launch_t16<2, 2, 2, 3>(a, s));    //  64 x  96
+        case 9: return conv_ran(ran, 9, "tap16", launch_t16<4, 1, 2, 4>(a, s));    // 128 x  64
+        case 11: return conv_ran(ran, 11, "tap16", launch_t16<4, 1, 2, 2>(a, s));   // 128 x  32
+        case 12: return conv_ran(ran, 12, "tap16", launch_t16<4, 1, 2, 1>(a, s));   // 128 x  16
+        case 20: return conv_ran(ran, 20, "tap16", launch_t16<4, 1, 2, 3>(a, s));   // 128 x  48
+        case 30: return conv_ran(ran, 30, "tap16", launch_t16<2, 2, 4, 4>(a, s));   // 128 x 128, 4 waves of 64 x 64
+        case 31: return conv_ran(ran, 31, "tap16", launch_t16<2, 2, 4, 3>(a, s));   // 128 x  96
+        case 32: return conv_ran(ran, 32, "tap16", launch_t16<2, 2, 4, 2>(a, s));   // 128 x  64
         // + 40: the same tile with 64-channel (double) k-steps
-        case 46: return launch_t16d<2, 2, 2, 4>(a, s);  //  64 x 128
-        case 47: return launch_t16d<2, 2, 2, 3>(a, s);  //  64 x  96
-        case 49: return launch_t16d<4, 1, 2, 4>(a, s);  // 128 x  64
-        case 51: return launch_t16d<4, 1, 2, 2>(a, s);  // 128 x  32
-        case 60: return launch_t16d<4, 1, 2, 3>(a, s);  // 128 x  48
-        case 70: return launch_t16d<2, 2, 4, 4>(a, s);  // 128 x 128
-        case 71: return launch_t16d<2, 2, 4, 3>(a, s);  // 128 x  96
-        case 72: return launch_t16d<2, 2, 4, 2>(a, s);  // 128 x  64
+        case 46: return conv_ran(ran, 46, "tap16d", launch_t16d<2, 2, 2, 4>(a, s));  //  64 x 128
+        case 47: return conv_ran(ran, 47, "tap16d", launch_t16d<2, 2, 2, 3>(a, s));  //  64 x  96
+        case 49: return conv_ran(ran, 49, "tap16d", launch_t16d<4, 1, 2, 4>(a, s));  // 128 x  64
+        case 51: return conv_ran(ran, 51, "tap16d", launch_t16d<4, 1, 2, 2>(a, s));  // 128 x  32
+        case 60: return conv_ran(ran, 60, "tap16d", launch_t16d<4, 1, 2, 3>(a, s));  // 128 x  48
+        case 70: return conv_ran(ran, 70, "tap16d", launch_t16d<2, 2, 4, 4>(a, s));  // 128 x 128
+        case 71: return conv_ran(ran, 71, "tap16d", launch_t16d<2, 2, 4, 3>(a, s));  // 128 x  96
+        case 72: return conv_ran(ran, 72, "tap16d", launch_t16d<2, 2, 4, 2>(a, s));  // 128 x  64
     }
     return hipErrorNotSupported;
 }

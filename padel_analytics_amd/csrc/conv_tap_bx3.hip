@@ -450,40 +450,40 @@ static hipError_t launch_b3u(const ConvArgs& a_in, hipStream_t s) {
 }
 
 // tile ids of the fp32 id space (conv_variant_shape); the ring holds 2 BM + 3 BN rows per stage
-hipError_t launch_conv_bx3(const ConvArgs& a, int variant, hipStream_t s) {
+hipError_t launch_conv_bx3(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
     if ((a.ksize != 3 && a.ksize != 1) || (a.cin & 15) || a.cin < 16 || !a.w3) return hipErrorNotSupported;
     if (a.in2 && a.ksize == 3) {                                // absorbed upsample in front of a 3x3: the patch kernel only
         if (variant < 300 || variant >= 400 || !conv_bx3p_supported(a)) return hipErrorNotSupported;
-        return launch_conv_bx3p(a, variant - 300, s);
+        return conv_ran(ran, variant, "bx3p", launch_conv_bx3p(a, variant - 300, s));
     }
     if (a.in2) {                                                // absorbed upsample in front of a 1x1: the three tiles instantiated for it
         if (a.ksize != 1) return hipErrorNotSupported;
-        if (variant == 209 || variant == 9 || variant == 304) return launch_b3u<4, 1, 2, 4>(a, s);
-        if (variant == 213 || variant == 13 || variant == 14 || variant == 306 || variant == 206 || variant == 6) return launch_b3u<4, 1, 2, 6>(a, s);
-        return launch_b3u<4, 1, 2, 3>(a, s);
+        if (variant == 209 || variant == 9 || variant == 304) return conv_ran(ran, 209, "bx3t", launch_b3u<4, 1, 2, 4>(a, s));
+        if (variant == 213 || variant == 13 || variant == 14 || variant == 306 || variant == 206 || variant == 6) return conv_ran(ran, 213, "bx3t", launch_b3u<4, 1, 2, 6>(a, s));
+        return conv_ran(ran, 220, "bx3t", launch_b3u<4, 1, 2, 3>(a, s));
     }
     if (variant >= 300 && variant < 400) {                      // patch kernel, or its tap-kernel sibling where it does not apply
         const int nf = variant - 300;
-        if (conv_bx3p_supported(a)) return launch_conv_bx3p(a, nf, s);
+        if (conv_bx3p_supported(a)) return conv_ran(ran, variant, "bx3p", launch_conv_bx3p(a, nf, s));
         variant = nf == 3 ? 220 : nf == 4 ? 209 : 206;
     }
     switch (variant) {
-        case 7: return launch_b3<2, 2, 2, 3>(a, s);    //  64 x  96
-        case 6: return launch_b3<2, 2, 2, 4>(a, s);    //  64 x 128
-        case 9: return launch_b3<4, 1, 2, 4>(a, s);    // 128 x  64
-        case 20: return launch_b3<4, 1, 2, 3>(a, s);   // 128 x  48
-        case 11: return launch_b3<4, 1, 2, 2>(a, s);   // 128 x  32
-        case 12: return launch_b3<4, 1, 2, 1>(a, s);   // 128 x  16
-        case 13: return launch_b3<4, 2, 2, 3>(a, s);   // 128 x  96, 8 waves
-        case 14: return launch_b3<4, 2, 2, 4>(a, s);   // 128 x 128, 8 waves
+        case 7: return conv_ran(ran, 7, "bx3t", launch_b3<2, 2, 2, 3>(a, s));    //  64 x  96
+        case 6: return conv_ran(ran, 6, "bx3t", launch_b3<2, 2, 2, 4>(a, s));    //  64 x 128
+        case 9: return conv_ran(ran, 9, "bx3t", launch_b3<4, 1, 2, 4>(a, s));    // 128 x  64
+        case 20: return conv_ran(ran, 20, "bx3t", launch_b3<4, 1, 2, 3>(a, s));   // 128 x  48
+        case 11: return conv_ran(ran, 11, "bx3t", launch_b3<4, 1, 2, 2>(a, s));   // 128 x  32
+        case 12: return conv_ran(ran, 12, "bx3t", launch_b3<4, 1, 2, 1>(a, s));   // 128 x  16
+        case 13: return conv_ran(ran, 13, "bx3t", launch_b3<4, 2, 2, 3>(a, s));   // 128 x  96, 8 waves
+        case 14: return conv_ran(ran, 14, "bx3t", launch_b3<4, 2, 2, 4>(a, s));   // 128 x 128, 8 waves
         // + 200: 2-stage ring (prefetch distance 1, 3 workgroups per CU)
-        case 207: return launch_b3<2, 2, 2, 3, 2>(a, s);
-        case 220: return launch_b3<4, 1, 2, 3, 2>(a, s);
-        case 206: return launch_b3<2, 2, 2, 4, 2>(a, s);
-        case 209: return launch_b3<4, 1, 2, 4, 2>(a, s);
-        case 211: return launch_b3<4, 1, 2, 2, 2>(a, s);
-        case 225: return launch_b3<4, 1, 1, 5, 2>(a, s);
-        case 213: return launch_b3<4, 1, 2, 6, 2>(a, s);   // 128 x 96 with 4 waves (2 x 6 fragments each), 2 workgroups per CU
+        case 207: return conv_ran(ran, 207, "bx3t", launch_b3<2, 2, 2, 3, 2>(a, s));
+        case 220: return conv_ran(ran, 220, "bx3t", launch_b3<4, 1, 2, 3, 2>(a, s));
+        case 206: return conv_ran(ran, 206, "bx3t", launch_b3<2, 2, 2, 4, 2>(a, s));
+        case 209: return conv_ran(ran, 209, "bx3t", launch_b3<4, 1, 2, 4, 2>(a, s));
+        case 211: return conv_ran(ran, 211, "bx3t", launch_b3<4, 1, 2, 2, 2>(a, s));
+        case 225: return conv_ran(ran, 225, "bx3t", launch_b3<4, 1, 1, 5, 2>(a, s));
+        case 213: return conv_ran(ran, 213, "bx3t", launch_b3<4, 1, 2, 6, 2>(a, s));   // 128 x 96 with 4 waves (2 x 6 fragments each), 2 workgroups per CU
 #ifdef PADEL_BX3_PROBES      // ceiling probes of tile 220 (WRONG results; tools/conv_bench.py only), DBG bits: 1 no split VALU, 2 one of the 6 MFMA groups, 4 / 8 no activation / weight requests
         case 420: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 1>(a, s) : hipErrorNotSupported;
         case 520: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 2>(a, s) : hipErrorNotSupported;
@@ -494,7 +494,7 @@ hipError_t launch_conv_bx3(const ConvArgs& a, int variant, hipStream_t s) {
         case 1020: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 13>(a, s) : hipErrorNotSupported;  // LDS reads + 6 MFMA groups + barriers only
         case 1120: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 5>(a, s) : hipErrorNotSupported;   // no split, no activation requests
 #endif
-        case 25: return launch_b3<4, 1, 1, 5>(a, s);   //  64 x  80, 4 waves of 16 x 80: the 19-fragment (304-channel) fused pose heads
+        case 25: return conv_ran(ran, 25, "bx3t", launch_b3<4, 1, 1, 5>(a, s));   //  64 x  80, 4 waves of 16 x 80: the 19-fragment (304-channel) fused pose heads
     }
     return hipErrorNotSupported;
 }

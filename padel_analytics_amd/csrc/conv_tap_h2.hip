@@ -213,62 +213,62 @@ static hipError_t launch_h2t(const ConvArgs& a_in, hipStream_t s) {
 
 // tile ids follow the bf16x3 ids (conv_variant_shape + 200); 30x = the patch kernel (conv_patch_h2.hip) or, where it does
 // not apply, its tap sibling
-hipError_t launch_conv_h2(const ConvArgs& a, int variant, hipStream_t s) {
+hipError_t launch_conv_h2(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
     if ((a.ksize != 3 && a.ksize != 1) || (a.cin & 15) || a.cin < 16 || !a.w || !a.oscale || !a.ovf_flag) return hipErrorNotSupported;
     if (variant >= 341 && variant <= 343) {  // the wide patch kernel for 16 / 32 / 48 input channels (conv_patch_h2w.hip), 1..3 channel fragments
         if (!(a.tune & 8) && conv_h2v_supported(a)) {      // its register-weights form (conv_patch_h2v.hip; tuning bit 3: the round-3 kernel)
             const hipError_t e = launch_conv_h2v(a, variant - 340, s);
-            if (e != hipErrorNotSupported) return e;
+            if (e != hipErrorNotSupported) return conv_ran(ran, variant, "h2v", e);
         }
-        if (conv_h2w_supported(a)) return launch_conv_h2w(a, variant - 340, s);
+        if (conv_h2w_supported(a)) return conv_ran(ran, variant, "h2w", launch_conv_h2w(a, variant - 340, s));
         variant = 303;
     }
     if (variant == 324 || variant == 325) {   // the register-weights quad kernels (conv_patch_h2r.hip): 324 = 96-channel tiles (two-product layers),
         if (conv_h2r_supported(a)) {           // 325 = 64-channel tiles (two or three products); elsewhere the quad kernel / the 64-channel patch tile
             const hipError_t e = launch_conv_h2r(a, variant == 324 ? 3 : 2, s);
-            if (e != hipErrorNotSupported) return e;
+            if (e != hipErrorNotSupported) return conv_ran(ran, variant, "h2r", e);
         }
         variant = variant == 324 ? 323 : 304;
     }
     if (variant == 323) {                  // the quad patch kernel (conv_patch_h2q.hip); where it does not apply, the 48-channel patch tile
-        if (conv_h2q_supported(a)) return launch_conv_h2q(a, s);
+        if (conv_h2q_supported(a)) return conv_ran(ran, 323, "h2q", launch_conv_h2q(a, s));
         variant = 303;
     }
     if (variant >= 300 && variant < 400) {
         const int nf = variant - 300;
-        if (conv_h2p_supported(a)) return launch_conv_h2p(a, nf, s);
+        if (conv_h2p_supported(a)) return conv_ran(ran, variant, "h2p", launch_conv_h2p(a, nf, s));
         if (a.in2 && a.ksize == 3) return hipErrorNotSupported;      // an absorbed upsample in front of a 3x3: the patch kernel only
         variant = (nf == 3 || nf == 13) ? 220 : (nf == 4 || nf == 14) ? 209 : 213;      // where the patch kernel does not apply: its tap sibling
     }
     if (a.in2 && a.ksize == 3) return hipErrorNotSupported;
     if (variant == 248) {                  // ... as 64 x 192 tiles of four waves
-        if (conv_h2s3_supported(a)) return launch_conv_h2s3(a, s, true);
+        if (conv_h2s3_supported(a)) return conv_ran(ran, 248, "h2s3", launch_conv_h2s3(a, s, true));
         variant = 213;
     }
     if (variant == 246) {                  // stride-2 3x3 on the register-weights ring machine (conv_1x1_h2s.hip: 128 x 192); elsewhere the 128 x 96 tap tile
-        if (conv_h2s3_supported(a)) return launch_conv_h2s3(a, s);
+        if (conv_h2s3_supported(a)) return conv_ran(ran, 246, "h2s3", launch_conv_h2s3(a, s));
         variant = 213;
     }
     if (variant == 247) {                  // 64 x 192 tiles of the 1x1 register-weights kernel (four waves, two workgroups per CU)
-        if (conv_h2s_supported(a)) return launch_conv_h2s(a, true, s, true);
+        if (conv_h2s_supported(a)) return conv_ran(ran, 247, "h2s", launch_conv_h2s(a, true, s, true));
         variant = 243;
     }
     if (variant == 244 || variant == 245) {   // 1x1 with register weights and a deep activation ring (conv_1x1_h2s.hip): 128 x 96 / 128 x 192; elsewhere the deep-ring tile
-        if (conv_h2s_supported(a)) return launch_conv_h2s(a, variant == 245, s);
+        if (conv_h2s_supported(a)) return conv_ran(ran, variant, "h2s", launch_conv_h2s(a, variant == 245, s));
         variant = 243;
     }
     if (variant == 243 || variant == 239) {   // 1x1 with the three-stage activation ring (conv_h2_1p_kernel); other kernel sizes: the plain tile
         const hipError_t e = launch_conv_h2_deep(a, variant, s);
-        if (e != hipErrorNotSupported) return e;
+        if (e != hipErrorNotSupported) return conv_ran(ran, variant, "h2d", e);
         variant -= 30;
     }
     switch (variant) {
-        case 207: return launch_h2t<2, 2, 2, 3>(a, s);    //  64 x  96
-        case 220: return launch_h2t<4, 1, 2, 3>(a, s);    // 128 x  48
-        case 209: return launch_h2t<4, 1, 2, 4>(a, s);    // 128 x  64
-        case 211: return launch_h2t<4, 1, 2, 2>(a, s);    // 128 x  32
-        case 213: return launch_h2t<4, 1, 2, 6>(a, s);    // 128 x  96, 4 waves of 2 x 6 fragments
-        case 225: return launch_h2t<4, 1, 1, 5>(a, s);    //  64 x  80: the 19-fragment (304-channel) fused pose heads
+        case 207: return conv_ran(ran, 207, "h2t", launch_h2t<2, 2, 2, 3>(a, s));    //  64 x  96
+        case 220: return conv_ran(ran, 220, "h2t", launch_h2t<4, 1, 2, 3>(a, s));    // 128 x  48
+        case 209: return conv_ran(ran, 209, "h2t", launch_h2t<4, 1, 2, 4>(a, s));    // 128 x  64
+        case 211: return conv_ran(ran, 211, "h2t", launch_h2t<4, 1, 2, 2>(a, s));    // 128 x  32
+        case 213: return conv_ran(ran, 213, "h2t", launch_h2t<4, 1, 2, 6>(a, s));    // 128 x  96, 4 waves of 2 x 6 fragments
+        case 225: return conv_ran(ran, 225, "h2t", launch_h2t<4, 1, 1, 5>(a, s));    //  64 x  80: the 19-fragment (304-channel) fused pose heads
         // (the eight-wave tiles 230 = 128 x 192 and 231 = 256 x 96 of round 4 were timed at the start of round 5 and removed:
         //  8-25 % slower than 128 x 96 on the K >= 576 1x1 and the stride-2 3x3 layers, 20-70 % on the P2 layers —
         //  profiles/r5a_tiles_230_231.txt; eight waves in lock step behind one barrier leave one workgroup per CU)

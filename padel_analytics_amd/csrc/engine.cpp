@@ -74,7 +74,7 @@ static int env_int(const char* k, int dflt) { const char* v = getenv(k); return 
         }                                                                                  \
     } while (0)
 
-struct ProfRec { int kind; int ksize; double flops; hipEvent_t e0, e1; float ms; int M, cout, cin, stride, mf, nf, res; };
+struct ProfRec { int kind; int ksize; double flops; hipEvent_t e0, e1; float ms; int M, cout, cin, stride, mf, nf, res; int tile; const char* family; };      // tile, family: what the conv dispatcher launched (ConvLaunched; -1 / "" for other ops)
 
 struct pa_model {
     pa_engine* e = nullptr;
@@ -690,6 +690,7 @@ static ProfRec* prof_begin(pa_model* m, size_t idx, int kind, int ksize, double 
     ProfRec* r = &m->prof[idx];
     r->kind = kind; r->ksize = ksize; r->flops = flops; r->ms = 0.f;
     r->M = r->cout = r->cin = r->stride = r->mf = r->nf = r->res = 0;
+    r->tile = -1; r->family = "";
     hipEventRecord(r->e0, m->e->stream);
     return r;
 }
@@ -807,15 +808,17 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
                 else dbg_dev = nullptr;
                 a.dbg = dbg_dev;
             }
+            ConvLaunched ran{-1, ""};
             if (h2) {
-                r = launch_conv_h2(a, lv, s);
+                r = launch_conv_h2(a, lv, s, &ran);
             } else if (f16) {
-                r = launch_conv_tap16(a, lv, s);
+                r = launch_conv_tap16(a, lv, s, &ran);
             } else if (use_bx3) {
-                r = launch_conv_bx3(a, lv, s);
+                r = launch_conv_bx3(a, lv, s, &ran);
             } else {
-                r = launch_conv_tap(a, lv, s);
+                r = launch_conv_tap(a, lv, s, &ran);
             }
+            if (pr) { pr->tile = ran.tile; pr->family = ran.family; }
             if (dbg_dev) {
                 (void)hipStreamSynchronize(s);
                 std::vector<unsigned long long> host(dbg_bytes / 8);
@@ -1587,8 +1590,8 @@ int pa_model_profile_text(pa_model* m, char* buf, size_t cap) {
     size_t off = 0;
     for (size_t i = 0; i < m->n_prof && i < m->prof.size(); ++i) {
         const ProfRec& r = m->prof[i];
-        int n = snprintf(buf + off, off < cap ? cap - off : 0, "%d,%d,%d,%d,%d,%d,%d,%d,%.5f,%.0f,%d\n", r.kind, r.ksize, r.M, r.cout,
-                         r.cin, r.stride, r.mf, r.nf, r.ms, r.flops, r.res);
+        int n = snprintf(buf + off, off < cap ? cap - off : 0, "%d,%d,%d,%d,%d,%d,%d,%d,%.5f,%.0f,%d,%d,%s\n", r.kind, r.ksize, r.M, r.cout,
+                         r.cin, r.stride, r.mf, r.nf, r.ms, r.flops, r.res, r.tile, r.family ? r.family : "");
         if (n < 0 || off + n >= cap) break;
         off += n;
     }

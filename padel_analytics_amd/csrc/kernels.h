@@ -62,13 +62,22 @@ constexpr int kConvDbgWords = 8 + 4 * kConvDbgSteps * 5;   // u64 words per work
 // TFLOP/s (profiles/r5e_f32_tap_vs_lds.txt) — and three more retired generations live in tools/legacy_conv/ and are not
 // built.  Tile variants of every family share one id space (conv_variant_shape).
 bool conv_variant_shape(int variant, int* bm, int* bn);                         // false: unknown id
+// What a conv dispatcher (launch_conv_tap / _bx3 / _h2 / _tap16) launched: the tile id AFTER every fall-through (a tile that does
+// not cover the layer hands it to a sibling) and a tag for the kernel template family — tap | bx3t, bx3p | h2t (two-stage tap
+// ring), h2d (deep ring), h2s, h2s3, h2p, h2q, h2r, h2v, h2w | tap16, tap16d (64-channel k-steps), p16, p16q.  Filled on success
+// when the caller passes one (profile rows, pa_model_profile_text columns 12 / 13): one host-side store per launch.
+struct ConvLaunched { int tile; const char* family; };
+inline hipError_t conv_ran(ConvLaunched* ran, int tile, const char* family, hipError_t e) {
+    if (ran && e == hipSuccess) { ran->tile = tile; ran->family = family; }
+    return e;
+}
 // conv_tap.hip reads up to 128 B past the last chunk of a pixel / weight row, so every buffer a conv reads is
 // allocated with kConvReadSlack extra bytes; hipErrorNotSupported when the layer or the tile is not covered
-hipError_t launch_conv_tap(const ConvArgs& a, int variant, hipStream_t s);      // ids 6,7,9..15,20
+hipError_t launch_conv_tap(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran = nullptr);      // ids 6,7,9..15,20
 constexpr size_t kConvReadSlack = 512;
 int choose_conv_tap_variant(int M, int n16);
 // fp32 convolutions on the bf16 matrix pipe (conv_tap_bx3.hip): exact 3-way bf16 split, 6 products, fp32 accumulate
-hipError_t launch_conv_bx3(const ConvArgs& a, int variant, hipStream_t s);      // ids 6,7,9,11,12,13,14,20,25 (3-stage ring), 206..225 (2-stage), 303/304/306 (patch kernel)
+hipError_t launch_conv_bx3(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran = nullptr);      // ids 6,7,9,11,12,13,14,20,25 (3-stage ring), 206..225 (2-stage), 303/304/306 (patch kernel)
 int choose_conv_bx3_variant(const ConvArgs& a);      // per-layer tile heuristic (ids + 200: 2-stage ring, 30x: patch kernel)
 // stride-1 3x3, cin % 32 == 0: 8 x 16-pixel patch kernel (conv_patch_bx3.hip), the input patch is split once per chunk;
 // nf = channel fragments per workgroup (3, 4, 6); reached through launch_conv_bx3 ids 303 / 304 / 306
@@ -77,7 +86,7 @@ hipError_t launch_conv_bx3p(const ConvArgs& a, int nf, hipStream_t s);
 // h2 path (conv_tap_h2.hip, conv_patch_h2.hip; h2_common.h): activations are fp16 PAIRS (x ~ h + m / 2048) in 16-channel
 // groups of 64 bytes [h x 16 | m x 16], 4 bytes per channel like fp32 (cs / choff count channels); weights `w` are the
 // pre-split planes [Npad][k-step][h | m][32 fp16], `oscale` the inverse row scales; three f16 MFMAs per operand pair
-hipError_t launch_conv_h2(const ConvArgs& a, int variant, hipStream_t s);        // tap tiles 207..225, patch tiles 303 / 304 / 306
+hipError_t launch_conv_h2(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran = nullptr);        // tap tiles 207..225, patch tiles 303 / 304 / 306
 int choose_conv_h2_variant(const ConvArgs& a);
 bool conv_h2p_supported(const ConvArgs& a);
 hipError_t launch_conv_h2p(const ConvArgs& a, int nf, hipStream_t s);
@@ -100,7 +109,7 @@ bool conv_h2v_supported(const ConvArgs& a);            // conv_patch_h2v.hip (ro
 hipError_t launch_conv_h2v(const ConvArgs& a, int nf, hipStream_t s);
 // fp16 path (conv_tap16.hip): in / w / res / out are _Float16 arrays behind the float pointers of ConvArgs (cs and
 // choff count elements); cin % 32 == 0; weights packed [Npad][Ktot] with K order (64-channel chunk, tap, 32-channel half)
-hipError_t launch_conv_tap16(const ConvArgs& a, int variant, hipStream_t s);
+hipError_t launch_conv_tap16(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran = nullptr);
 int choose_conv_tap16_variant(const ConvArgs& a);
 bool conv_tap16_variant_shape(int variant, int* bm, int* bn);
 // fp16 stride-1 3x3 patch kernel (conv_patch16.hip), ids 303 / 304 / 306 of launch_conv_tap16

@@ -608,12 +608,7 @@ class Model:
         """Per-op records of the last profiled inference: dicts with shape, tile and milliseconds."""
         buf = C.create_string_buffer(1 << 20)
         self.engine.lib.pa_model_profile_text(self.handle, buf, len(buf))
-        rows = []
-        for line in buf.value.decode().splitlines():
-            k, ks, M, co, ci, st, mf, nf, ms, fl, res = (line.split(",") + ["0"])[:11]
-            rows.append(dict(kind=int(k), ksize=int(ks), M=int(M), cout=int(co), cin=int(ci), stride=int(st),
-                             mf=int(mf), nf=int(nf), ms=float(ms), flops=float(fl), res=int(res)))
-        return rows
+        return parse_profile_text(buf.value.decode())
 
     def close(self):
         """Drain first, unpin second: pa_model_destroy synchronizes the engine's stream, so tickets still queued (the
@@ -623,6 +618,21 @@ class Model:
             self.engine.lib.pa_model_destroy(self.handle)
             self.handle = None
             self._free_rings()
+
+
+def parse_profile_text(text: str):
+    """``pa_model_profile_text`` lines -> dicts.  Columns 1-11: kind, ksize, M, cout, cin, stride, mf, nf (the REQUESTED tile's
+    pixels and channels), ms, flops, res; 12 and 13 (convs): ``tile`` — the tile id the dispatcher launched after every
+    fall-through — and ``family`` — the tag of the kernel template that ran (csrc/kernels.h ConvLaunched).  Lines of older
+    libraries have 10 or 11 columns: res 0, tile -1, family ""."""
+    rows = []
+    for line in text.splitlines():
+        f = line.split(",")
+        k, ks, M, co, ci, st, mf, nf, ms, fl, res = (f + ["0"])[:11]
+        rows.append(dict(kind=int(k), ksize=int(ks), M=int(M), cout=int(co), cin=int(ci), stride=int(st),
+                         mf=int(mf), nf=int(nf), ms=float(ms), flops=float(fl), res=int(res),
+                         tile=int(f[11]) if len(f) > 11 and f[11] else -1, family=f[12] if len(f) > 12 else ""))
+    return rows
 
 
 class NativeByteTrack:

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from padel_analytics_amd import engine as E, graph as G
+from tests import tile_support as TS
 
 pytestmark = pytest.mark.gpu
 
@@ -30,14 +31,34 @@ CASES = [
     (2, 20, 24, 64, 192, 3, 1, G.ACT_SILU, True),     # two full 96-channel tiles (quad patch kernel: both channel halves), partial patches in y and x
     (1, 20, 27, 688, 96, 1, 1, G.ACT_SILU, False),    # 1x1 with long K: 21 full chunks + a 16-channel tail = three accumulation blocks (9 + 9 + 4), M tail
     (3, 18, 22, 96, 208, 3, 2, G.ACT_SILU, True),     # stride 2 to an odd map (9 x 11 outputs: M tail, every border), 13 fragments = two 192-channel tiles, residual
+    # added with tests/tile_support.py (tests/test_tile_coverage.py says which (tile, class) cells each of these fills)
+    (2, 16, 16, 64, 80, 3, 1, G.ACT_LEAKY, False),    # LeakyReLU (InpaintNet's activation); 512 pixels x 80 channels: whole 64 x 80 tiles (25 / 225), partial 96- and 64-channel tiles
+    (1, 16, 32, 32, 384, 3, 1, G.ACT_RELU, False),    # whole tiles for every tile shape but 64 x 80 (384 = 3 x 128 = 4 x 96 = 8 x 48), whole 8 x 16 and 16 x 16 patches
+    (1, 18, 20, 64, 39, 3, 1, G.ACT_NONE, True),      # cout % 16 != 0: a partial channel FRAGMENT (element-wise stores), residual, no activation
 ]
+ACT_FN = {G.ACT_SILU: F.silu, G.ACT_RELU: F.relu, G.ACT_SIGMOID: torch.sigmoid, G.ACT_NONE: lambda t: t, G.ACT_LEAKY: lambda t: F.leaky_relu(t, 0.01)}
 
 TAP_VARIANTS = (6, 7, 9, 10, 11, 12, 13, 14, 15, 20)
 BX3_VARIANTS = (6, 7, 9, 11, 12, 13, 14, 20, 25, 206, 207, 209, 211, 220, 225, 213, 303, 304, 306)      # bf16x3 kernels (conv_tap_bx3.hip): fp32 accuracy, own rounding
 
 
-def _run(eng, case, x, w, b, wr):
-    """Graph: [op0: 1x1 conv (stride s, no act) x -> residual buffer]  op1: the conv under test (+ residual)."""
+def _launched(m, which=-1):
+    """(family, tile) the engine reports for a conv of the op list (default: the last one, the conv under test), from the profile rows."""
+    r = [r for r in m.profile_rows() if r["kind"] == G.OP_CONV][which]
+    return r["family"], r["tile"]
+
+
+def _check_launched(path, case, requested, got, w_single=False):
+    """The forced runs of one case against tests/tile_support.py, both directions; prints the (requested -> launched) table."""
+    print(f"case {case}{' two-product' if w_single else ''}: " + "  ".join(f"{t} -> {f}/{v}" for t, (f, v) in got.items()))
+    for t, fv in got.items():
+        want = TS.expected(path, t, case, w_single)
+        assert fv == want, f"requested {t}, launched {fv[0]}/{fv[1]}; tests/tile_support.py says {want[0]}/{want[1]}"
+    assert set(got) == {t for t, _ in requested}
+
+def _run(eng, case, x, w, b, wr, ran=None):
+    """Graph: [op0: 1x1 conv (stride s, no act) x -> residual buffer]  op1: the conv under test (+ residual).
+    ``ran``: a dict -> profiling on for this run, ``ran["launched"]`` = (family, tile) of the conv under test."""
     B, H, W, cin, cout, k, s, act, use_res = case
     g = G.Graph(task=G.TASK_TRACKNET)
     b0 = g.buf(0, cin)
@@ -52,7 +73,15 @@ def _run(eng, case, x, w, b, wr):
     g.head_buf = (b1, -1, -1)
     m = E.Model(eng, g)
     m.set_max_batch(B)
-    y = m.tracknet_infer(x)[..., :cout]
+    if ran is not None:
+        eng.set_profiling(True)
+    try:
+        y = m.tracknet_infer(x)[..., :cout]
+        if ran is not None:
+            ran["launched"] = _launched(m)
+    finally:
+        if ran is not None:
+            eng.set_profiling(False)
     m.close()
     return y
 
@@ -67,17 +96,20 @@ def test_conv_variants(gpu_engine, case):
     wr = rng.normal(0, (1.0 / cin) ** 0.5, (cout, cin, 1, 1)).astype(np.float32)
     xt = torch.from_numpy(x).permute(0, 3, 1, 2)
     want = F.conv2d(xt.double(), torch.from_numpy(w).double(), torch.from_numpy(b).double(), stride=s, padding=k // 2)
-    want = {G.ACT_SILU: F.silu, G.ACT_RELU: F.relu, G.ACT_SIGMOID: torch.sigmoid, G.ACT_NONE: lambda t: t}[act](want)
+    want = ACT_FN[act](want)
     if use_res:
         want = want + F.conv2d(xt.double(), torch.from_numpy(wr).double(), stride=s)
     want = want.permute(0, 2, 3, 1).numpy()
     scale = max(1.0, float(np.abs(want).max()))
     outs = {}
+    runs, got = TS.plan("tap", TAP_VARIANTS, case), {}
     try:
-        for v in TAP_VARIANTS:                            # LDS-DMA ring: twice, a DMA / barrier race is not deterministic
+        for v, _ in runs:                                 # LDS-DMA ring: twice, a DMA / barrier race is not deterministic
             gpu_engine.set_tuning(impl=0, variant=v)
             for rep in range(2):
-                outs[f"T{v}.{rep}"] = _run(gpu_engine, case, x, w, b, wr)
+                ran = {}
+                outs[f"T{v}.{rep}"] = _run(gpu_engine, case, x, w, b, wr, ran=ran)
+                got[v] = ran["launched"]
         gpu_engine.set_tuning(impl=0, variant=7, tap_pd=3)   # 1x1 tap kernel with prefetch distance 3
         outs["T7.pd3"] = _run(gpu_engine, case, x, w, b, wr)
         gpu_engine.set_tuning(impl=0, variant=-1, tap_pd=2)
@@ -88,6 +120,7 @@ def test_conv_variants(gpu_engine, case):
         outs["auto.noalias"] = _run(gpu_engine, case, x, w, b, wr)
     finally:
         gpu_engine.set_tuning(impl=2, variant=-1, tap_pd=2, graph=0, alias=1)
+    _check_launched("tap", case, runs, got)
     ref_name, ref = next(iter(outs.items()))
     for name, y in outs.items():
         assert y.shape == want.shape
@@ -97,15 +130,19 @@ def test_conv_variants(gpu_engine, case):
     # ---- bf16x3: same accuracy bar against fp64, bitwise equal among its own tiles, and its RMS error not worse
     # than the fp32 MFMA kernels' (the admission criterion for making it the default)
     outs3 = {}
+    runs3, got3 = TS.plan("bx3", BX3_VARIANTS, case), {}      # (the 30x ids on a conv the patch kernel does not take are duplicates of 220 / 209 / 206)
     try:
-        for v in BX3_VARIANTS:
+        for v, _ in runs3:
             gpu_engine.set_tuning(impl=2, variant=v)
             for rep in range(2):
-                outs3[f"B{v}.{rep}"] = _run(gpu_engine, case, x, w, b, wr)
+                ran = {}
+                outs3[f"B{v}.{rep}"] = _run(gpu_engine, case, x, w, b, wr, ran=ran)
+                got3[v] = ran["launched"]
         gpu_engine.set_tuning(impl=2, variant=-1)
         outs3["B.auto"] = _run(gpu_engine, case, x, w, b, wr)
     finally:
         gpu_engine.set_tuning(impl=2, variant=-1)
+    _check_launched("bx3", case, runs3, got3)
     n3, r3 = next(iter(outs3.items()))
     for name, y in outs3.items():
         err = float(np.abs(y - want).max()) / scale
@@ -115,6 +152,128 @@ def test_conv_variants(gpu_engine, case):
     rms3 = float(np.sqrt(np.mean((r3 - want) ** 2)))
     print(f"case {case}: RMS error vs fp64  fp32-MFMA {rms32:.3e}  bf16x3 {rms3:.3e}")
     assert rms3 <= 1.25 * rms32 + 1e-9, (rms3, rms32)
+
+
+# ---- channel slices (real graphs read C2f halves at a channel offset and write into slices of concat buffers; the sweeps above
+# only ever use offset 0).  Shared with the fp16 path (tests/test_gpu_fp16.py); the h2 path has its own, tests/test_gpu_h2_epilogue.py.
+SLICE_BASES = [(1, 16, 16, 64, 3, 1), (1, 16, 16, 64, 1, 1), (1, 32, 32, 64, 3, 2)]      # (B, H, W, cin, k, stride)
+SLICE_WIDTH = 160
+BIG = 3.0e4                                                                              # what the neighbours of an input / residual slice hold
+
+
+def slice_sentinel(n):
+    return (-100.0 - 0.25 * np.arange(n)).astype(np.float32)          # fp16 numbers
+
+
+def slice_graph(dtype, base, cout, d, use_res, out_choff=0, in_choff=None, res_choff=0):
+    """[1x1 -> residual slice], sentinel fill of the SLICE_WIDTH-wide buffer S (1x1, zero weights, bias = sentinel), the conv under
+    test -> S[out_choff : out_choff + cout]; fp32 graphs read S back as the head, fp16 graphs through an identity 1x1.  ``in_choff``
+    (not None): the input through an identity copy into channel ``in_choff`` of a wider buffer whose other channels hold BIG;
+    ``res_choff``: the residual at that channel of a wider buffer.  Returns (graph, index of the conv under test among the convs)."""
+    B, H, W, cin, k, s = base
+    z = lambda *shape: np.zeros(shape, np.float32)
+    g = G.Graph(task=G.TASK_TRACKNET, dtype=dtype)
+    b0 = g.buf(0, cin)
+    lvl = 1 if s == 2 else 0
+    src = (b0, 0, cin)
+    if in_choff is not None:
+        bi = g.buf(0, in_choff + cin + (16 if in_choff else 0))
+        if in_choff:
+            g.conv((b0, 0, cin), (bi, 0), z(in_choff, cin, 1, 1), np.full(in_choff, BIG, np.float32), 1, 1, G.ACT_NONE)
+            g.conv((b0, 0, cin), (bi, in_choff + cin), z(16, cin, 1, 1), np.full(16, BIG, np.float32), 1, 1, G.ACT_NONE)
+        g.conv((b0, 0, cin), (bi, in_choff), np.eye(cin, dtype=np.float32)[:, :, None, None], z(cin), 1, 1, G.ACT_NONE)
+        src = (bi, in_choff, cin)
+    res = None
+    if use_res:
+        rw = (res_choff + cout + 15) // 16 * 16
+        rb = g.buf(lvl, rw)
+        if res_choff:
+            g.conv((b0, 0, cin), (rb, 0), z(res_choff, cin, 1, 1), np.full(res_choff, BIG, np.float32), 1, s, G.ACT_NONE)
+        g.conv((b0, 0, cin), (rb, res_choff), d["wr"], z(cout), 1, s, G.ACT_NONE)
+        res = (rb, res_choff)
+    S = g.buf(lvl, SLICE_WIDTH)
+    g.conv((b0, 0, cin), (S, 0), z(SLICE_WIDTH, cin, 1, 1), slice_sentinel(SLICE_WIDTH), 1, s, G.ACT_NONE)
+    g.conv(src, (S, out_choff), d["w"], d["b"], k, s, G.ACT_SILU, res=res)
+    if dtype == G.DTYPE_F16:
+        hd = g.buf(lvl, SLICE_WIDTH)
+        g.conv((S, 0, SLICE_WIDTH), (hd, 0), np.eye(SLICE_WIDTH, dtype=np.float32)[:, :, None, None], z(SLICE_WIDTH), 1, 1, G.ACT_NONE)
+        g.head_buf = (hd, -1, -1)
+        return g, -2
+    g.head_buf = (S, -1, -1)
+    return g, -1
+
+
+def slice_data(base, cout, f16=False):
+    B, H, W, cin, k, s = base
+    rng = np.random.default_rng(cin * 7 + cout * 5 + k + s)
+    r = (lambda a: a.astype(np.float16).astype(np.float32)) if f16 else (lambda a: a.astype(np.float32))
+    x = rng.normal(0, 1, (B, H, W, cin))
+    return dict(x=x.astype(np.float16) if f16 else x.astype(np.float32), w=r(rng.normal(0, (2.0 / (cin * k * k)) ** 0.5, (cout, cin, k, k))),
+                b=rng.normal(0, 0.5, cout).astype(np.float32), wr=r(rng.normal(0, (1.0 / cin) ** 0.5, (cout, cin, 1, 1))))
+
+
+def slice_run(eng, path, dtype, base, cout, d, use_res, tile, **kw):
+    """One forced run of a slice graph; what launched is checked against tests/tile_support.py.  Returns S as fp32 (B, Ho, Wo, SLICE_WIDTH)."""
+    g, which = slice_graph(dtype, base, cout, d, use_res, **kw)
+    B, H, W, cin, k, s = base
+    case = (B, H, W, cin, cout, k, s, G.ACT_SILU, use_res)
+    eng.set_tuning(variant=tile)
+    eng.set_profiling(True)
+    m = E.Model(eng, g)
+    try:
+        m.set_max_batch(B)
+        y = m.tracknet_infer(d["x"])
+        got = _launched(m, which)
+    finally:
+        eng.set_profiling(False)
+        m.close()
+    want = TS.expected(path, tile, case)
+    assert got == want, f"requested {tile}, launched {got[0]}/{got[1]}; tests/tile_support.py says {want[0]}/{want[1]}"
+    return y
+
+
+def check_slices(eng, path, dtype, tiles, base, out_slices, res_offsets):
+    """The three slice statements on every native tile of ``tiles``: (1) cout channels written at out_choff are the bits of the
+    offset-0 run and every other channel of S keeps its sentinel — also under a 96- / 128-channel tile that overhangs the slice;
+    (2) an input slice at channel 32 between channels that hold BIG, (3) a residual at ``res_offsets``: bitwise the offset-0 runs.
+    The offsets include one that misses the vector alignment the fast epilogues test (4 floats / 8 halves): element-wise path."""
+    B, H, W, cin, k, s = base
+    f16 = dtype == G.DTYPE_F16
+    sent = slice_sentinel(SLICE_WIDTH)
+    nat = lambda cout, res: [t for t in tiles if TS.native(path, t, (B, H, W, cin, cout, k, s, G.ACT_SILU, res))]
+    for choff, cout, res in out_slices:
+        d = slice_data(base, cout, f16)
+        for t in nat(cout, res):
+            ref = slice_run(eng, path, dtype, base, cout, d, res, t)
+            y = slice_run(eng, path, dtype, base, cout, d, res, t, out_choff=choff)
+            name = f"{path} tile {t}, {cout} channels at {choff}"
+            assert np.array_equal(y[..., choff:choff + cout], ref[..., :cout]), f"{name}: differs from the offset-0 run"
+            rest = np.concatenate([y[..., :choff], y[..., choff + cout:]], -1)
+            bad = rest != np.broadcast_to(np.concatenate([sent[:choff], sent[choff + cout:]]), rest.shape)
+            assert not bad.any(), f"{name}: {int(bad.sum())} values outside the slice changed"
+            assert np.array_equal(ref[..., cout:], np.broadcast_to(sent[cout:], ref[..., cout:].shape)), f"{name}: the offset-0 run wrote beyond its channels"
+    for cout in (96, 40):
+        d = slice_data(base, cout, f16)
+        for t in nat(cout, True):
+            ref = slice_run(eng, path, dtype, base, cout, d, True, t, in_choff=0)
+            y = slice_run(eng, path, dtype, base, cout, d, True, t, in_choff=32)
+            assert np.array_equal(y, ref), f"{path} tile {t}, cout {cout}: input slice at channel 32 differs from offset 0 (max {np.abs(y - ref).max():.3e})"
+            ref = slice_run(eng, path, dtype, base, cout, d, True, t)
+            for rc in res_offsets:
+                y = slice_run(eng, path, dtype, base, cout, d, True, t, res_choff=rc)
+                assert np.array_equal(y, ref), f"{path} tile {t}, cout {cout}: residual at channel {rc} differs from offset 0 (max {np.abs(y - ref).max():.3e})"
+
+
+@pytest.mark.parametrize("base", SLICE_BASES, ids=["3x3", "1x1", "s2"])
+@pytest.mark.parametrize("path", ["tap", "bx3"])
+def test_conv_slices(gpu_engine, path, base):
+    """fp32 storage (tap_epilogue / bx3_common.h): the vector path needs choff % 4 == 0 and cs % 4 == 0; 6 is the offset that misses it."""
+    try:
+        gpu_engine.set_tuning(impl=0 if path == "tap" else 2)
+        check_slices(gpu_engine, path, G.DTYPE_F32, TAP_VARIANTS if path == "tap" else BX3_VARIANTS, base,
+                     [(16, 32, False), (48, 80, True), (16, 96, True), (6, 26, True)], (16, 6))
+    finally:
+        gpu_engine.set_tuning(impl=2, variant=-1)
 
 
 @pytest.mark.parametrize("shape", [(2, 24, 40, 64, 32, 80, 1), (1, 18, 28, 32, 48, 96, 1), (3, 16, 16, 96, 16, 48, 1),

@@ -19,7 +19,8 @@ import torch.nn.functional as F
 from oracle import yolov8_ref as ref
 from padel_analytics_amd import engine as E, graph as G
 from tests import synth
-from tests import graph_interp, parity
+from tests import graph_interp, parity, tile_support as TS
+from tests.test_gpu_conv import ACT_FN, SLICE_BASES, _check_launched, _launched, check_slices
 from tests.test_gpu_yolo_parity import _calib
 
 pytestmark = pytest.mark.gpu
@@ -36,6 +37,10 @@ CASES = [
     (3, 17, 23, 160, 96, 3, 1, G.ACT_SILU, True),     # two chunks + tail, odd spatial size
     (2, 16, 16, 64, 39, 1, 1, G.ACT_NONE, False),     # cout not a multiple of 4: element-wise epilogue
     (2, 20, 40, 64, 192, 3, 1, G.ACT_SILU, True),     # two 96-channel tiles, 16-row tiles with a partial last row block (quad patch kernel)
+    # added with tests/tile_support.py (tests/test_tile_coverage.py says which (tile, class) cells each of these fills)
+    (1, 16, 32, 32, 384, 3, 1, G.ACT_RELU, False),    # whole tiles for every tile shape (384 = 3 x 128 = 4 x 96 = 8 x 48), whole 8 x 16 and 16 x 16 patches
+    (1, 18, 20, 64, 39, 3, 1, G.ACT_NONE, True),      # the patch kernels' element-wise epilogue (cout % 16 != 0), residual, no activation
+    (2, 16, 16, 64, 80, 3, 1, G.ACT_LEAKY, False),    # LeakyReLU
 ]
 VARIANTS = (6, 7, 9, 11, 12, 20, 30, 31, 32, 46, 47, 49, 51, 60, 70, 71, 72)
 # fp16 patch kernel (csrc/conv_patch16.hip; stride-1 3x3 only, elsewhere these ids fall back to tap tiles): it walks K as
@@ -44,7 +49,7 @@ VARIANTS = (6, 7, 9, 11, 12, 20, 30, 31, 32, 46, 47, 49, 51, 60, 70, 71, 72)
 PATCH_VARIANTS = (303, 304, 306, 323, 324, 326)       # 32x: the quad kernel (16 x 16 pixels per workgroup)
 
 
-def _run(eng, case, x16, w, b, wr):
+def _run(eng, case, x16, w, b, wr, ran=None):
     B, H, W, cin, cout, k, s, act, use_res = case
     g = G.Graph(task=G.TASK_TRACKNET, dtype=G.DTYPE_F16)
     b0 = g.buf(0, cin)
@@ -62,7 +67,15 @@ def _run(eng, case, x16, w, b, wr):
     g.head_buf = (hd, -1, -1)
     m = E.Model(eng, g)
     m.set_max_batch(B)
-    y = m.tracknet_infer(x16)[..., :cout]
+    if ran is not None:                                   # ran["launched"] = (family, tile) of the conv under test: the one before the identity
+        eng.set_profiling(True)
+    try:
+        y = m.tracknet_infer(x16)[..., :cout]
+        if ran is not None:
+            ran["launched"] = _launched(m, -2)
+    finally:
+        if ran is not None:
+            eng.set_profiling(False)
     m.close()
     return y
 
@@ -77,30 +90,29 @@ def test_conv16_variants(gpu_engine, case):
     wr = rng.normal(0, (1.0 / cin) ** 0.5, (cout, cin, 1, 1)).astype(np.float16).astype(np.float32)
     xt = torch.from_numpy(x16.astype(np.float32)).permute(0, 3, 1, 2).double()
     want = F.conv2d(xt, torch.from_numpy(w).double(), torch.from_numpy(b).double(), stride=s, padding=k // 2)
-    want = {G.ACT_SILU: F.silu, G.ACT_RELU: F.relu, G.ACT_SIGMOID: torch.sigmoid, G.ACT_NONE: lambda t: t}[act](want)
+    want = ACT_FN[act](want)
     if use_res:
         want = want + F.conv2d(xt, torch.from_numpy(wr).double(), stride=s).half().double()    # the residual is stored as fp16
     want = want.permute(0, 2, 3, 1).numpy()
     scale = max(1.0, float(np.abs(want).max()))
-    outs = {}
+    outs, outs_p = {}, {}
+    # what launched is checked against tests/tile_support.py; a patch id on a conv the patch kernels do not take resolves to a tap
+    # tile this sweep runs under its own id (20 / 9 / 31): a duplicate run, not repeated
+    runs, got = TS.plan("f16", VARIANTS + PATCH_VARIANTS, case), {}
     try:
-        for v in VARIANTS:
+        for v, _ in runs:
             gpu_engine.set_tuning(variant=v)
             for rep in range(2):
-                outs[f"H{v}.{rep}"] = _run(gpu_engine, case, x16, w, b, wr)
-        outs_p = {}
-        for v in PATCH_VARIANTS:
-            gpu_engine.set_tuning(variant=v)
-            for rep in range(2):
-                outs_p[f"P{v}.{rep}"] = _run(gpu_engine, case, x16, w, b, wr)
+                ran = {}
+                y = _run(gpu_engine, case, x16, w, b, wr, ran=ran)
+                got[v] = ran["launched"]
+                # bitwise groups by the REPORTED kernel: the patch kernels (p16 / p16q) walk K in another order than the tap kernels
+                (outs_p if got[v][0] in ("p16", "p16q") else outs)[f"{got[v][0]}{v}.{rep}"] = y
         gpu_engine.set_tuning(variant=-1)
         auto = _run(gpu_engine, case, x16, w, b, wr)
     finally:
         gpu_engine.set_tuning(variant=-1)
-    patch_case = k == 3 and s == 1
-    if not patch_case:
-        outs.update(outs_p)                      # the ids fell back to tap tiles: same family
-        outs_p = {}
+    _check_launched("f16", case, runs, got)
     for fam in (outs, outs_p):
         if not fam:
             continue
@@ -111,6 +123,17 @@ def test_conv16_variants(gpu_engine, case):
             assert err < 1.5e-3, f"{name}: rel err {err:.2e} vs fp64 conv2d of the fp16 operands (fp16 output rounding is 4.9e-4)"
             assert np.array_equal(y, r0), f"{name} differs bitwise from {ref_name} (max {np.abs(y - r0).max():.3e})"
     assert any(np.array_equal(auto, next(iter(fam.values()))) for fam in (outs, outs_p) if fam), "auto matches neither family"
+
+
+@pytest.mark.parametrize("base", SLICE_BASES, ids=["3x3", "1x1", "s2"])
+def test_conv16_slices(gpu_engine, base):
+    """fp16 storage (f16_epilogue.h): the 16-byte path needs choff % 8 == 0 and cs % 8 == 0; 4 is the offset that misses it.  The three
+    slice statements of tests/test_gpu_conv.py::check_slices on every native fp16 tile, read back through an identity 1x1."""
+    try:
+        check_slices(gpu_engine, "f16", G.DTYPE_F16, VARIANTS + PATCH_VARIANTS, base,
+                     [(16, 32, False), (48, 80, True), (16, 96, True), (4, 28, True)], (16, 4))
+    finally:
+        gpu_engine.set_tuning(variant=-1)
 
 
 @pytest.mark.parametrize("scale,nc,kpt,hw,S,pre", [("n", 80, None, (720, 1280), 640, "lb"), ("m", 80, None, (720, 1280), 640, "lb"),

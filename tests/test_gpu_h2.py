@@ -6,6 +6,9 @@ producer, three f16 MFMA products per operand pair, correction products in their
   and the admission criterion (RMS error <= 1.25 x the fp32-MFMA kernels') are the ones the bf16x3 kernels were
   admitted under, and they include what the 22-23-bit operand representation costs;
 * bitwise equality among the tiles that share the accumulation scheme;
+* every forced-tile run is verified: the engine reports which kernel family and tile id it launched after all fall-throughs
+  (profile rows) and the sweeps compare that with tests/tile_support.py; the pair-store paths of the epilogue and channel
+  slices have their own file, tests/test_gpu_h2_epilogue.py;
 * values far below the fp16 normal range (the MFMA must not flush fp16 subnormals), the overflow flag, the absorbed
   upsample, the helper kernels (SPPF pools, MaxPool2d(2, 2), upsample) — exact on pairs."""
 import numpy as np
@@ -14,12 +17,40 @@ import torch
 import torch.nn.functional as F
 
 from padel_analytics_amd import engine as E, graph as G
-from tests.test_gpu_conv import CASES
+from tests import tile_support as TS
+from tests.test_gpu_conv import ACT_FN, CASES, _check_launched, _launched
 
 pytestmark = pytest.mark.gpu
 
 H2_TILES = (207, 209, 211, 213, 220, 225, 239, 243, 244, 245, 246, 247, 248, 303, 304, 313, 323, 324, 325, 341, 342, 343)      # 324 / 325: the register-weights quad kernels (round 6; 96-channel tiles, two-product layers only / 64-channel tiles, two or three products); 239 / 243: tap tiles with the three-stage activation ring (conv_tap_h2p.hip); 31x: software-pipelined patch schedule; 323: the quad patch kernel; 34x: the wide patch kernel (cin 16 / 32 / 48)
 H2_SINGLE_LEVEL = ()            # (the 6-fragment patch tile 306 — main product accumulated in ONE level — was removed in round 5)
+
+# More h2 cases (the fp32 sweeps of tests/test_gpu_conv.py do not need them): with CASES they fill every (tile, class) cell of
+# tests/tile_support.py — the CPU test tests/test_tile_coverage.py checks that from the table alone.
+H2_EXTRA = [
+    (1, 16, 24, 128, 192, 1, 1, G.ACT_RELU, True),     # 1x1, 384 pixels x 192 channels: whole 128 x 192 / 64 x 192 / 128 x 64 tiles, residual
+    (1, 18, 20, 48, 39, 3, 1, G.ACT_SIGMOID, False),   # wide patch kernel (cin 48) with a partial channel fragment
+    (1, 12, 20, 96, 39, 1, 1, G.ACT_SIGMOID, False),   # 1x1 with a partial channel fragment
+    (1, 16, 24, 64, 39, 3, 2, G.ACT_NONE, False),      # stride 2 with a partial channel fragment, no residual, no activation
+    (2, 32, 32, 32, 192, 3, 2, G.ACT_RELU, False),     # stride 2, 512 pixels x 192 channels: whole 128 x 192 / 64 x 192 tiles
+    (1, 16, 16, 16, 48, 3, 1, G.ACT_LEAKY, True),      # wide patch kernel (cin 16): one whole 16 x 16 patch, whole 16- / 48-channel tiles, residual
+    (1, 10, 12, 48, 32, 3, 1, G.ACT_NONE, False),      # wide patch kernel, no activation
+    (1, 16, 16, 32, 32, 3, 2, G.ACT_SIGMOID, True),    # stride 2 with a sigmoid
+    (1, 12, 16, 64, 48, 3, 2, G.ACT_LEAKY, False),     # stride 2 with LeakyReLU
+    (1, 8, 16, 64, 64, 1, 1, G.ACT_LEAKY, False),      # 1x1 with LeakyReLU, one whole 128 x 64 tile
+    (1, 8, 16, 64, 192, 3, 1, G.ACT_RELU, True),       # one whole 8 x 16 patch x 192 channels (whole 96-, 64- and 48-channel tiles of the quad / patch kernels), residual
+]
+H2_CASES = CASES + H2_EXTRA
+# two-product (PA_CONV_W_SINGLE) sweep only: the shapes that take the register-weights kernels through their K loops and partial tiles
+W_ONLY = [
+    (1, 12, 20, 96, 144, 3, 1, G.ACT_SILU, False),     # partial 96- and 64-channel tiles of the quad kernels 324 / 325
+    (1, 20, 27, 704, 96, 1, 1, G.ACT_SILU, False),     # 1x1, 22 WHOLE chunks = three accumulation blocks, M tail (688 has a 16-channel tail: not their shape)
+    (1, 16, 24, 128, 200, 1, 1, G.ACT_SILU, False),    # 1x1, a partial 192-channel tile
+    (1, 18, 22, 128, 80, 3, 2, G.ACT_SILU, True),      # stride 2 to an odd 9 x 11 map, residual
+]
+W_SINGLE_CASES = H2_CASES + W_ONLY
+_W_IDS = {0: "3x3", 1: "3x3-tail-res", 3: "1x1", 5: "1x1-res", 7: "s2-res", 8: "odd-size", 11: "quad-192", 12: "1x1-long-K", 13: "s2-odd-13-fragments"}
+
 
 def _graph(case, w, b, wr, dtype):
     B, H, W, cin, cout, k, s, act, use_res = case
@@ -37,10 +68,19 @@ def _graph(case, w, b, wr, dtype):
     return g
 
 
-def _run(eng, case, x, w, b, wr, dtype=G.DTYPE_H2, want_flag=False):
+def _run(eng, case, x, w, b, wr, dtype=G.DTYPE_H2, want_flag=False, ran=None):
+    """``ran``: a dict -> profiling on for this run, ``ran["launched"]`` = (family, tile) of the conv under test."""
     m = E.Model(eng, _graph(case, w, b, wr, dtype))
     m.set_max_batch(case[0])
-    y = m.tracknet_infer(x)[..., :case[4]]
+    if ran is not None:
+        eng.set_profiling(True)
+    try:
+        y = m.tracknet_infer(x)[..., :case[4]]
+        if ran is not None:
+            ran["launched"] = _launched(m)
+    finally:
+        if ran is not None:
+            eng.set_profiling(False)
     flag = m.take_overflow()
     m.close()
     return (y, flag) if want_flag else y
@@ -60,23 +100,29 @@ def _want(case, x, w, b, wr):
     B, H, W, cin, cout, k, s, act, use_res = case
     xt = torch.from_numpy(x).permute(0, 3, 1, 2).double()
     want = F.conv2d(xt, torch.from_numpy(w).double(), torch.from_numpy(b).double(), stride=s, padding=k // 2)
-    want = {G.ACT_SILU: F.silu, G.ACT_RELU: F.relu, G.ACT_SIGMOID: torch.sigmoid, G.ACT_NONE: lambda t: t}[act](want)
+    want = ACT_FN[act](want)
     if use_res:
         want = want + F.conv2d(xt, torch.from_numpy(wr).double(), stride=s)
     return want.permute(0, 2, 3, 1).numpy()
 
 
-@pytest.mark.parametrize("case", CASES, ids=[f"c{i}" for i in range(len(CASES))])
+@pytest.mark.parametrize("case", H2_CASES, ids=[f"c{i}" for i in range(len(H2_CASES))])
 def test_h2_conv_variants(gpu_engine, case):
+    """Every forced tile must launch what tests/tile_support.py says (family and tile id, from the engine's profile rows); a tile
+    that resolves to a sibling this sweep runs under its own id on the same case is a duplicate run and is not repeated."""
     x, w, b, wr = _data(case)
     want = _want(case, x, w, b, wr)
     scale = max(1.0, float(np.abs(want).max()))
     outs = {}
+    runs, got = TS.plan("h2", H2_TILES, case), {}
+    assert any(t == 220 for t, _ in runs)
     try:
-        for v in H2_TILES:
+        for v, _ in runs:
             gpu_engine.set_tuning(variant=v)
             for rep in range(2):                       # LDS-DMA ring: a DMA / barrier race is not deterministic
-                outs[f"H{v}.{rep}"] = _run(gpu_engine, case, x, w, b, wr)
+                ran = {}
+                outs[f"H{v}.{rep}"] = _run(gpu_engine, case, x, w, b, wr, ran=ran)
+                got[v] = ran["launched"]
         gpu_engine.set_tuning(variant=-1)
         outs["H.auto"] = _run(gpu_engine, case, x, w, b, wr)
         gpu_engine.set_tuning(alias=0)
@@ -87,6 +133,7 @@ def test_h2_conv_variants(gpu_engine, case):
         y3 = _run(gpu_engine, case, x, w, b, wr, dtype=G.DTYPE_F32)            # bf16x3
     finally:
         gpu_engine.set_tuning(impl=2, variant=-1, alias=1)
+    _check_launched("h2", case, runs, got)
     k, cin = case[5], case[3]
     patch_applies = k == 3 and case[6] == 1
     ref_name, ref = "H220.0", outs["H220.0"]
@@ -102,8 +149,7 @@ def test_h2_conv_variants(gpu_engine, case):
     assert rms(ref) <= 1.25 * rms(y32) + 1e-9, (rms(ref), rms(y32))
 
 
-@pytest.mark.parametrize("case", [CASES[0], CASES[1], CASES[3], CASES[5], CASES[7], CASES[8], CASES[11], CASES[12], CASES[13]],
-                         ids=["3x3", "3x3-tail-res", "1x1", "1x1-res", "s2-res", "odd-size", "quad-192", "1x1-long-K", "s2-odd-13-fragments"])
+@pytest.mark.parametrize("case", W_SINGLE_CASES, ids=[_W_IDS.get(i, f"c{i}" if i < len(H2_CASES) else f"w{i - len(H2_CASES)}") for i in range(len(W_SINGLE_CASES))])
 def test_h2_two_product_mode_on_fp16_weights(gpu_engine, case):
     """Round 5: a checkpoint's conv weights are fp16 numbers (Ultralytics stores ``model.half()``); with BatchNorm's scale kept
     in the conv's per-channel OUTPUT scale instead of multiplied into them (``Graph.conv(out_scale=)``), the packed weights'
@@ -111,7 +157,9 @@ def test_h2_two_product_mode_on_fp16_weights(gpu_engine, case):
     (wh x ah and wh x am; the skipped wm x ah is exactly zero).  Checked on every tile: the flag is set by the packer; the
     two-product kernels give BITWISE the results of the three-product kernels on the same blob (tuning ``w_single=0``); against
     fp64 conv2d with the exact weights w x scale the error stays inside the h2 bound (3e-6) and the RMS inside the admission
-    criterion against the fp32-input MFMA kernels run on the FOLDED fp32 weights (what the reference's fused model holds)."""
+    criterion against the fp32-input MFMA kernels run on the FOLDED fp32 weights (what the reference's fused model holds).
+    Runs on every case of the three-product sweep plus W_ONLY: the register-weights kernels (324, 244 .. 248) exist for two-product
+    layers only, so this is the sweep that reaches them — what launched is checked against tests/tile_support.py in both modes."""
     B, H, W, cin, cout, k, s, act, use_res = case
     rng = np.random.default_rng(cin * 17 + cout + k)
     x = rng.normal(0, 1, (B, H, W, cin)).astype(np.float32)
@@ -123,7 +171,7 @@ def test_h2_two_product_mode_on_fp16_weights(gpu_engine, case):
     xt = torch.from_numpy(x).permute(0, 3, 1, 2).double()
     w_exact = torch.from_numpy(w).double() * torch.from_numpy(scale).double()[:, None, None, None]
     want = F.conv2d(xt, w_exact, torch.from_numpy(b).double(), stride=s, padding=k // 2)
-    want = {G.ACT_SILU: F.silu, G.ACT_RELU: F.relu, G.ACT_SIGMOID: torch.sigmoid, G.ACT_NONE: lambda t: t}[act](want)
+    want = ACT_FN[act](want)
     if use_res:
         want = want + F.conv2d(xt, torch.from_numpy(wr).double(), stride=s)
     want = want.permute(0, 2, 3, 1).numpy()
@@ -143,10 +191,18 @@ def test_h2_two_product_mode_on_fp16_weights(gpu_engine, case):
         g.head_buf = (b1, -1, -1)
         return g
 
-    def run(g):
+    def run(g, ran=None):
         m = E.Model(gpu_engine, g)
         m.set_max_batch(B)
-        y = m.tracknet_infer(x)[..., :cout]
+        if ran is not None:
+            gpu_engine.set_profiling(True)
+        try:
+            y = m.tracknet_infer(x)[..., :cout]
+            if ran is not None:
+                ran["launched"] = _launched(m)
+        finally:
+            if ran is not None:
+                gpu_engine.set_profiling(False)
         assert not m.take_overflow()
         m.close()
         return y
@@ -156,18 +212,30 @@ def test_h2_two_product_mode_on_fp16_weights(gpu_engine, case):
     g3 = graph(G.DTYPE_H2, w_fold, None)
     assert not (g3.ops[-1]["flags"] & G.FLAG_W_SINGLE), "folded weights are not fp16 numbers"
     outs = {}
+    runs2, runs3, got2, got3 = TS.plan("h2", H2_TILES, case, True), TS.plan("h2", H2_TILES, case, False), {}, {}
     try:
-        for v in H2_TILES + (-1,):
+        for v, _ in runs2:
             gpu_engine.set_tuning(variant=v, w_single=1)
-            outs[f"two-product H{v}"] = run(g2)
+            ran = {}
+            outs[f"two-product H{v}"] = run(g2, ran)
+            got2[v] = ran["launched"]
+        for v, _ in runs3:
             gpu_engine.set_tuning(variant=v, w_single=0)
-            outs[f"three-product kernels, same blob H{v}"] = run(g2)
+            ran = {}
+            outs[f"three-product kernels, same blob H{v}"] = run(g2, ran)
+            got3[v] = ran["launched"]
+        gpu_engine.set_tuning(variant=-1, w_single=1)
+        outs["two-product H-1"] = run(g2)
+        gpu_engine.set_tuning(variant=-1, w_single=0)
+        outs["three-product kernels, same blob H-1"] = run(g2)
         gpu_engine.set_tuning(variant=-1, w_single=1)
         y_fold = run(g3)                                                                  # the round-4 path: folded weights, 3 products
         gpu_engine.set_tuning(impl=0, variant=-1)
         y32 = run(graph(G.DTYPE_F32, w_fold, None))                                       # fp32-input MFMA kernels on the folded weights
     finally:
         gpu_engine.set_tuning(impl=2, variant=-1, w_single=1)
+    _check_launched("h2", case, runs2, got2, True)
+    _check_launched("h2", case, runs3, got3, False)
     ref_name, ref = next(iter(outs.items()))
     for name, y in outs.items():
         err = float(np.abs(y - want).max()) / sc
