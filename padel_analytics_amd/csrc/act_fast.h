@@ -7,8 +7,9 @@ namespace {
 
 // SiLU / sigmoid for the epilogues: e^-x through v_exp_f32 on a compensated argument (the product x * log2(e) carried as
 // hi + lo), the quotient through v_rcp_f32 + one Newton step on the remainder.  11 VALU instead of the 28 of
-// expf() + IEEE division, at the accuracy of the fp32 formula itself (max 2.7 ulp / mean 0.37 ulp against 2.4 / 0.35 for
-// correctly rounded exp + division, measured over 2.5 M arguments in [-90, 90]; profiles/h2_silu_accuracy_r3.txt).
+// expf() + IEEE division, at the accuracy of the fp32 formula itself: over 2.2 M arguments in [-80, 80] SiLU max 2.9 / mean 0.33 ulp,
+// sigmoid 3.1 / 0.36, against 3.4 / 0.37 and 3.3 / 0.40 for the formula in float32 with libm's exp (profiles/act_ulp_sweep.txt,
+// asserted by tests/test_gpu_helpers.py; the round-3 tool's figures: profiles/h2_silu_accuracy_r3.txt).
 __device__ __forceinline__ float fast_exp_neg(float x) {           // e^-x, finite for every finite x (clamped at 2^126)
     const float t = -x * 1.4426950216293335f;
     float tl = fmaf(-x, 1.4426950216293335f, -t);

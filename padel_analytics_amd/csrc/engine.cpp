@@ -284,6 +284,11 @@ static int validate_desc(pa_engine* e, const pa_model_desc* d, size_t n_floats) 
     for (int i = 0; i < d->n_ops; ++i) {
         const pa_op_desc& o = d->ops[i];
         if (!okslice(o.out_buf, o.out_choff, o.cout)) PA_FAIL(e, "op %d: bad output slice", i);
+        // fp16 pools / upsample move 16-byte vectors at pixel x width halves (pool5_kernel<f16x8>, maxpool2_kernel<f16x8>,
+        // upsample2x_kernel<f16x8>): a width of 8k + 4 halves would misalign every second pixel
+        if (f16 && (o.kind == PA_OP_SPPF_POOL || o.kind == PA_OP_UPSAMPLE2X || o.kind == PA_OP_MAXPOOL2) &&
+            ((d->bufs[o.out_buf].channels & 7) || (o.in_buf >= 0 && o.in_buf < d->n_bufs && (d->bufs[o.in_buf].channels & 7))))
+            PA_FAIL(e, "op %d: fp16 pool / upsample buffers must be a multiple of 8 channels wide", i);
         if (h2 && o.kind != PA_OP_STEM && (((o.in_choff | o.cin) & 15) || (!is_head_buf(o.out_buf) && (o.out_choff & 3))))
             PA_FAIL(e, "op %d: h2 slices must start on a 16-channel group", i);
         if (o.kind != PA_OP_STEM && !okslice(o.in_buf, o.in_choff, o.cin)) PA_FAIL(e, "op %d: bad input slice", i);

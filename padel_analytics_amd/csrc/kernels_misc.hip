@@ -488,20 +488,20 @@ __global__ void __launch_bounds__(NT) sppf_f16_kernel(_Float16* buf, int cs, int
     for (int level = 1; level <= 3; ++level) {
         for (int p = threadIdx.x; p < HW; p += NT) {
             const int y = (int)(((float)p + 0.5f) * inv_w), x = p - y * W;
-            f16x8 m = X[p];
+            // walked from d = -2 like pool5_kernel's window (vmax keeps its second argument between equal values): the zero that wins
+            // a tie of +0 and -0 is the one the three launches pick, so the maps agree in every bit
+            f16x8 m = X[y * W + max(x - 2, 0)];
 #pragma unroll
-            for (int d = -2; d <= 2; ++d)
-                if (d) m = vmax(m, X[y * W + min(max(x + d, 0), W - 1)]);
+            for (int d = -1; d <= 2; ++d) m = vmax(m, X[y * W + min(max(x + d, 0), W - 1)]);
             T[p] = m;
         }
         __syncthreads();
         _Float16* ob = base + level * c;
         for (int p = threadIdx.x; p < HW; p += NT) {
             const int y = (int)(((float)p + 0.5f) * inv_w), x = p - y * W;
-            f16x8 m = T[p];
+            f16x8 m = T[max(y - 2, 0) * W + x];
 #pragma unroll
-            for (int d = -2; d <= 2; ++d)
-                if (d) m = vmax(m, T[min(max(y + d, 0), H - 1) * W + x]);
+            for (int d = -1; d <= 2; ++d) m = vmax(m, T[min(max(y + d, 0), H - 1) * W + x]);
             X[p] = m;
             *reinterpret_cast<f16x8*>(ob + (long long)p * cs) = m;
         }
