@@ -39,7 +39,16 @@ enum pa_op_kind {
     PA_OP_CONV = 2,       /* Conv kxk (k in 1,3; stride 1,2) + bias + act (+ residual)           */
     PA_OP_SPPF_POOL = 3,  /* three chained MaxPool2d(5,1,2): slice c -> slices c+1..c+3          */
     PA_OP_UPSAMPLE2X = 4, /* nearest x2 of a slice into a slice of a buffer one level finer      */
-    PA_OP_MAXPOOL2 = 5    /* MaxPool2d(2,2) into a buffer one level coarser                      */
+    PA_OP_MAXPOOL2 = 5,   /* MaxPool2d(2,2) into a buffer one level coarser                      */
+    /* ResNet-50 (the court-keypoint regressor, trackers/keypoints_tracker/keypoints_tracker.py:158-168): */
+    PA_OP_STEM7 = 6,      /* conv1: Conv 7x7 s2 p3, 3 -> 64 (cout = 64) + bias + ReLU straight from the u8 network input of
+                             pa_resnet_infer; w_off: [148][64] fp32, row (ky * 7 + kx) * 3 + c, row 147 zero; `reserved`: offset of
+                             the [3][256] fp32 table byte -> normalised value (ToTensor + Normalize; padding is zero in THAT space) */
+    PA_OP_MAXPOOL3S2 = 7, /* MaxPool2d(3, 2, 1) into a buffer one level coarser (padding = -inf); fp32 and h2 storage          */
+    PA_OP_GAP_FC = 8      /* mean over the map of the cin-channel input slice (fp32), then cout <= 64 outputs of a linear layer
+                             (w_off: [cout][cin], b_off: [cout], fp32 FMA) and their sigmoid (act = PA_ACT_SIGMOID): cout logits and
+                             cout probabilities per image, kept by the model (pa_resnet_infer / pa_resnet_read_fc), not in a buffer:
+                             out_buf = in_buf.  One per graph                                                                   */
 };
 
 enum pa_act { PA_ACT_NONE = 0, PA_ACT_SILU = 1, PA_ACT_RELU = 2, PA_ACT_SIGMOID = 3, PA_ACT_LEAKY = 4 /* nn.LeakyReLU(0.01): InpaintNet, reference trackers/ball_tracker/models.py:83-93 */ };
@@ -55,7 +64,7 @@ typedef struct pa_op_desc {
     int32_t in_buf, in_choff, cin;      /* slice read  (cin multiple of 16 for PA_OP_CONV)          */
     int32_t out_buf, out_choff, cout;   /* slice written (cout = real channels)                     */
     int32_t ksize, stride, act;
-    int32_t res_buf, res_choff;         /* residual slice added after the activation; res_buf < 0: none */
+    int32_t res_buf, res_choff;         /* residual slice added after the activation (before it: PA_CONV_RES_PREACT); res_buf < 0: none */
     int32_t npad;                       /* PA_OP_CONV: rows of the packed weight matrix (multiple of 16) */
     int32_t reserved;                   /* PA_OP_CONV, fp32 models: offset (in floats, > 0) of the same weights pre-split
                                            into three bf16 planes for the bf16x3 kernels, [npad][k-step][hi|mid|lo][32];
@@ -66,12 +75,17 @@ typedef struct pa_op_desc {
                                            weights is all zero — the weights are fp16 numbers (what an Ultralytics checkpoint stores)
                                            times the row's power of two, BatchNorm's scale travels in the per-channel output scale
                                            instead — so the kernels skip the wm x ah product: TWO MFMAs per operand pair, not three.
-                                           Results do not depend on the flag (the skipped product is exactly zero).  ABI v4 */
+                                           Results do not depend on the flag (the skipped product is exactly zero).  ABI v4
+                                           PA_CONV_RES_PREACT (any PA_OP_CONV with a residual slice): out = act(conv + bias + residual)
+                                           instead of act(conv + bias) + residual — the join of a ResNet bottleneck.  Implemented by the
+                                           h2 and the bf16x3 kernels; fp16 models are refused at pa_model_create, the fp32-MFMA tap
+                                           kernels (tuning impl = 0) fail the inference call: nobody applies the other order silently */
     int32_t pad_;
 } pa_op_desc;
 #define PA_CONV_W_SINGLE 1
+#define PA_CONV_RES_PREACT 4
 
-enum pa_task { PA_TASK_DETECT = 0, PA_TASK_POSE = 1, PA_TASK_TRACKNET = 2 };
+enum pa_task { PA_TASK_DETECT = 0, PA_TASK_POSE = 1, PA_TASK_TRACKNET = 2, PA_TASK_RESNET = 3 /* pa_resnet_infer; head_buf[0] optional (tests) */ };
 
 /* PA_DTYPE_F32: the parity path (fp32 storage, fp32 MFMA: what the reference computes with half=False).
  * PA_DTYPE_F16 (detect / pose only; BASELINE configs[4]): activations and conv weights are fp16, accumulation fp32
@@ -215,6 +229,25 @@ int pa_yolo_read_netin(pa_model* m, int n, uint8_t* out);
  * contents of buffer head_buf[0]: n x (H>>level) x (W>>level) x channels fp32 */
 int pa_tracknet_infer(pa_model* m, const float* x, int n, int h, int w, int x_on_device, float* out,
                       int out_on_device);
+
+/* ---- court keypoints: torchvision ResNet-50 regressor (trackers/keypoints_tracker/keypoints_tracker.py:264-312) ----
+ * frames: n x h x w x 3 uint8 BGR.  Each is turned to RGB, resized to 224 x 224 as transforms.Resize does on a PIL image (Pillow
+ * BILINEAR: horizontal pass, then vertical, 22-bit fixed point), normalised inside the stem and run through the graph of a
+ * PA_TASK_RESNET model.  out_xy: n x cout sigmoid outputs of the graph's PA_OP_GAP_FC (24 = 12 keypoints x (x, y) as fractions of
+ * the frame size); out_logits (optional): the same before the sigmoid.  A graph without that op (unit tests) takes out_xy = NULL. */
+int pa_resnet_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, int frames_on_device, float* out_xy, float* out_logits);
+/* the u8 network input (n x 224 x 224 x 4: R, G, B, 0) the last pa_resnet_infer call built from its first n frames */
+int pa_resnet_read_netin(pa_model* m, int n, uint8_t* out);
+/* results of the PA_OP_GAP_FC op of the last replay of ANY graph that has one (n x cout each, either may be NULL) */
+int pa_resnet_read_fc(pa_model* m, int n, float* out_xy, float* out_logits);
+/* tests: contents of buffer head_buf[0] of a PA_TASK_RESNET model after the last pa_resnet_infer call, n x H x W x channels fp32 */
+int pa_resnet_read_head(pa_model* m, int n, float* out);
+
+/* host only (no GPU needed; tests): the coefficient tables of one Pillow resample pass in_size -> out_size as the device kernels
+ * use them — filter 0 = BICUBIC (a = -0.5), 1 = BILINEAR; 22-bit fixed point.  *ksize = taps per output; bounds: out_size x 2
+ * {first input index, taps used}; coefs: out_size x ksize (coefs_cap = its capacity in elements).  bounds = coefs = NULL: only
+ * *ksize is returned.                                                                                                       */
+int pa_pil_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* coefs, int coefs_cap, int* ksize);
 
 /* ---- ball path: streaming TrackNet session (trackers/ball_tracker/ball_tracker.py:373-523) ----
  * Frames are fed in stream order; every frame is Pillow-bicubic-resized to 512x288 on the device once

@@ -180,6 +180,28 @@ def load_checkpoint(path) -> Checkpoint:
     raise ValueError(f"{path}: unrecognised checkpoint layout")
 
 
+def load_state_dict(path) -> "OrderedDict[str, np.ndarray]":
+    """A bare ``torch.save(model.state_dict())`` file (what the reference hands ``torch.load`` for the court ResNet-50,
+    ``keypoints_tracker.py:165``) -> name -> fp32 ndarray, through the same two unpicklers as :func:`load_checkpoint` (torch's
+    safe one, then the allow-listed stub: a crafted file cannot run code).  ``FileNotFoundError`` / ``OSError`` for a file that
+    cannot be opened, ``ValueError`` for one that does not hold a flat dict of tensors."""
+    with open(str(path), "rb"):
+        pass
+    try:
+        obj = torch.load(str(path), map_location="cpu", weights_only=True)
+    except Exception:
+        try:
+            obj = torch.load(str(path), map_location="cpu", weights_only=False, pickle_module=_StubPickleModule)
+        except Exception as err:
+            raise ValueError(f"{path}: not a torch checkpoint ({type(err).__name__}: {err})") from err
+    if isinstance(obj, dict) and obj.get("padel_format") == 1:
+        obj = obj["state_dict"]
+    if not isinstance(obj, dict) or not obj or not all(isinstance(k, str) and (torch.is_tensor(v) or isinstance(v, np.ndarray))
+                                                       for k, v in obj.items()):
+        raise ValueError(f"{path}: not a flat state_dict of tensors")
+    return OrderedDict((k, _to_np(v)) for k, v in obj.items())
+
+
 def make_synthetic_yolo(path, scale, nc, kpt_shape=None, seed=0, cls_bias=-4.0, names=None) -> None:
     """Seeded synthetic YOLOv8 detect/pose checkpoint (SURVEY.md §8(d) weight recipe)."""
     sd = yolo_arch.synth_state_dict(scale, nc, kpt_shape, seed, cls_bias)

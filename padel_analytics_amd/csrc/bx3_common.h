@@ -63,6 +63,15 @@ constexpr int min_waves3(int frags) { return frags <= 6 ? 2 : 1; }
 
 }  // namespace
 
+template <int ACT>
+__device__ __forceinline__ float bx3_act(float x) {
+    if (ACT == ACT_SILU) return x / (1.0f + expf(-x));
+    if (ACT == ACT_RELU) return x > 0.0f ? x : 0.0f;
+    if (ACT == ACT_SIGMOID) return 1.0f / (1.0f + expf(-x));
+    if (ACT == ACT_LEAKY) return x >= 0.0f ? x : 0.01f * x;
+    return x;
+}
+
 template <int MF, int NF, int ACT, bool RES, bool FAST>
 __device__ __forceinline__ void bx3_epilogue_case(const ConvArgs& a, const f32x4 (&acc)[MF][NF], const int (&mpix)[MF], int fw, int lq) {
 #pragma unroll
@@ -78,16 +87,19 @@ __device__ __forceinline__ void bx3_epilogue_case(const ConvArgs& a, const f32x4
         for (int f = 0; f < MF; ++f) {
             const int m = mpix[f];
             if (!FAST && m < 0) continue;
+            if (RES && a.res_pre) {          // PA_CONV_RES_PREACT: act(conv + bias + residual), element by element (the fallback path of a fallback)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int co = co0 + r;
+                    if (!FAST && co >= a.cout) continue;
+                    const float rv = a.res[(long long)m * a.res_cs + a.res_choff + co];
+                    a.out[(long long)m * a.out_cs + a.out_choff + co] = bx3_act<ACT>((acc[f][j][r] + b[r]) + rv);
+                }
+                continue;
+            }
             f32x4 v;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float x = acc[f][j][r] + b[r];
-                if (ACT == ACT_SILU) x = x / (1.0f + expf(-x));
-                else if (ACT == ACT_RELU) x = x > 0.0f ? x : 0.0f;
-                else if (ACT == ACT_SIGMOID) x = 1.0f / (1.0f + expf(-x));
-                else if (ACT == ACT_LEAKY) x = x >= 0.0f ? x : 0.01f * x;
-                v[r] = x;
-            }
+            for (int r = 0; r < 4; ++r) v[r] = bx3_act<ACT>(acc[f][j][r] + b[r]);
             if (FAST) {
                 if (RES) {
                     const f32x4 rv = *reinterpret_cast<const f32x4*>(a.res + (long long)m * a.res_cs + a.res_choff + co0);

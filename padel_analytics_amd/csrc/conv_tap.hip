@@ -490,6 +490,7 @@ bool conv_variant_shape(int variant, int* bm, int* bn) {
 // hipErrorNotSupported when the layer or the tile is not covered
 hipError_t launch_conv_tap(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
     if ((a.ksize != 3 && a.ksize != 1) || (a.cin & 15) || a.cin < 16) return hipErrorNotSupported;
+    if (a.res_pre) return hipErrorNotSupported;      // PA_CONV_RES_PREACT: h2 and bf16x3 epilogues only (the engine refuses with a message)
     switch (variant) {
         case 6: return conv_ran(ran, 6, "tap", launch_t<2, 2, 2, 4>(a, s));    //  64 x 128
         case 7: return conv_ran(ran, 7, "tap", launch_t<2, 2, 2, 3>(a, s));    //  64 x  96

@@ -561,6 +561,7 @@ static hipError_t launch_t16(const ConvArgs& a_in, hipStream_t s) {
 // tile ids: the fp32 id space (conv_variant_shape) + 30.. for the larger per-wave tiles only the fp16 path has
 hipError_t launch_conv_tap16(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
     if ((a.ksize != 3 && a.ksize != 1) || (a.cin & 31) || a.cin < 32) return hipErrorNotSupported;
+    if (a.res_pre) return hipErrorNotSupported;      // PA_CONV_RES_PREACT: h2 and bf16x3 epilogues only
     if (variant >= 300 && variant < 400) {           // fp16 patch kernel (conv_patch16.hip), or a tap tile where it does not apply
         const int nf = variant - 300;
         if (conv_p16_supported(a)) return conv_ran(ran, variant, nf >= 20 ? "p16q" : "p16", launch_conv_p16(a, nf, s));

@@ -92,6 +92,8 @@ struct pa_model {
     bool wr_valid = false;
     unsigned* d_ovf = nullptr;             // h2 models: sticky "a value did not fit fp16" flag (pa_model_take_overflow)
     float* d_stage = nullptr; size_t stage_cap = 0;   // h2 generic graphs: fp32 input staged here before it is encoded
+    float* d_fc = nullptr;                 // graphs with a PA_OP_GAP_FC op: [max_batch][kGapFcMaxOut] logits, then as many probabilities (plan_buffers)
+    int fc_nout = 0;                       // outputs of that op (0: the graph has none)
     int max_batch = 64;
 
     // plan
@@ -283,15 +285,17 @@ static int validate_desc(pa_engine* e, const pa_model_desc* d, size_t n_floats) 
             if (!is_head_buf(i) && (d->bufs[i].channels & 15)) PA_FAIL(e, "model desc: h2 buffer %d has %d channels", i, d->bufs[i].channels);
     for (int i = 0; i < d->n_ops; ++i) {
         const pa_op_desc& o = d->ops[i];
-        if (!okslice(o.out_buf, o.out_choff, o.cout)) PA_FAIL(e, "op %d: bad output slice", i);
+        // (the pooled linear head writes no buffer: its cout counts outputs kept by the model, checked with the op below)
+        if (o.kind != PA_OP_GAP_FC && !okslice(o.out_buf, o.out_choff, o.cout)) PA_FAIL(e, "op %d: bad output slice", i);
         // fp16 pools / upsample move 16-byte vectors at pixel x width halves (pool5_kernel<f16x8>, maxpool2_kernel<f16x8>,
         // upsample2x_kernel<f16x8>): a width of 8k + 4 halves would misalign every second pixel
         if (f16 && (o.kind == PA_OP_SPPF_POOL || o.kind == PA_OP_UPSAMPLE2X || o.kind == PA_OP_MAXPOOL2) &&
             ((d->bufs[o.out_buf].channels & 7) || (o.in_buf >= 0 && o.in_buf < d->n_bufs && (d->bufs[o.in_buf].channels & 7))))
             PA_FAIL(e, "op %d: fp16 pool / upsample buffers must be a multiple of 8 channels wide", i);
-        if (h2 && o.kind != PA_OP_STEM && (((o.in_choff | o.cin) & 15) || (!is_head_buf(o.out_buf) && (o.out_choff & 3))))
+        const bool from_netin = o.kind == PA_OP_STEM || o.kind == PA_OP_STEM7;      // reads the u8 network input, not a buffer
+        if (h2 && !from_netin && (((o.in_choff | o.cin) & 15) || (!is_head_buf(o.out_buf) && (o.out_choff & 3))))
             PA_FAIL(e, "op %d: h2 slices must start on a 16-channel group", i);
-        if (o.kind != PA_OP_STEM && !okslice(o.in_buf, o.in_choff, o.cin)) PA_FAIL(e, "op %d: bad input slice", i);
+        if (!from_netin && !okslice(o.in_buf, o.in_choff, o.cin)) PA_FAIL(e, "op %d: bad input slice", i);
         if (o.kind == PA_OP_CONV) {
             if ((o.cin & kalign) || (o.in_choff & valign) || (o.ksize != 1 && o.ksize != 3) || (o.stride != 1 && o.stride != 2))
                 PA_FAIL(e, "op %d: unsupported conv (cin %d choff %d k %d s %d)", i, o.cin, o.in_choff, o.ksize, o.stride);
@@ -302,6 +306,10 @@ static int validate_desc(pa_engine* e, const pa_model_desc* d, size_t n_floats) 
                 (size_t)o.b_off + o.npad > n_floats)
                 PA_FAIL(e, "op %d: weights outside the blob", i);
             if (o.res_buf >= 0 && !okslice(o.res_buf, o.res_choff, o.cout)) PA_FAIL(e, "op %d: bad residual slice", i);
+            if (o.flags & PA_CONV_RES_PREACT) {
+                if (o.res_buf < 0) PA_FAIL(e, "op %d: PA_CONV_RES_PREACT without a residual slice", i);
+                if (f16) PA_FAIL(e, "op %d: PA_CONV_RES_PREACT is not implemented for fp16 storage (h2 and fp32 / bf16x3 models only)", i);
+            }
             if (h2) {
                 if (o.reserved <= 0 || (o.reserved & 3) || (size_t)o.reserved + o.npad > n_floats) PA_FAIL(e, "op %d: h2 row scales outside the blob", i);
                 if (o.res_buf >= 0 && (o.res_choff & 3)) PA_FAIL(e, "op %d: h2 residual slice alignment", i);
@@ -322,6 +330,23 @@ static int validate_desc(pa_engine* e, const pa_model_desc* d, size_t n_floats) 
         } else if (o.kind == PA_OP_MAXPOOL2) {
             if (d->bufs[o.out_buf].level != d->bufs[o.in_buf].level + 1 || o.cin != o.cout || ((o.cin | o.in_choff | o.out_choff) & valign))
                 PA_FAIL(e, "op %d: bad maxpool", i);
+        } else if (o.kind == PA_OP_MAXPOOL3S2) {
+            if (f16) PA_FAIL(e, "op %d: MaxPool2d(3, 2, 1) is not implemented for fp16 storage", i);
+            if (d->bufs[o.out_buf].level != d->bufs[o.in_buf].level + 1 || o.cin != o.cout || ((o.cin | o.in_choff | o.out_choff) & 3))
+                PA_FAIL(e, "op %d: bad 3x3 stride-2 maxpool", i);
+        } else if (o.kind == PA_OP_STEM7) {
+            if (f16) PA_FAIL(e, "op %d: the 7x7 stem is not implemented for fp16 storage", i);
+            if (o.cout != 64 || o.w_off < 0 || (o.w_off & 3) || (size_t)o.w_off + 148 * 64 > n_floats || o.b_off < 0 || (o.b_off & 3) ||
+                (size_t)o.b_off + 64 > n_floats || o.reserved <= 0 || (size_t)o.reserved + 768 > n_floats || (o.out_choff & (h2 ? 15 : 3)) ||
+                (o.act != PA_ACT_RELU && o.act != PA_ACT_NONE))
+                PA_FAIL(e, "op %d: bad 7x7 stem", i);
+            if (d->bufs[o.out_buf].level != 1) PA_FAIL(e, "op %d: stem output must be level 1", i);
+        } else if (o.kind == PA_OP_GAP_FC) {
+            if (f16) PA_FAIL(e, "op %d: the pooled linear head is not implemented for fp16 storage", i);
+            if (o.out_buf != o.in_buf || (o.cin & 3) || (o.in_choff & 3) || o.cin > kGapFcMaxC || o.cout < 1 || o.cout > kGapFcMaxOut || o.w_off < 0 ||
+                (size_t)o.w_off + (size_t)o.cout * o.cin > n_floats || o.b_off < 0 || (size_t)o.b_off + o.cout > n_floats || o.act != PA_ACT_SIGMOID)
+                PA_FAIL(e, "op %d: bad pooled linear head", i);
+            for (int k = 0; k < i; ++k) if (d->ops[k].kind == PA_OP_GAP_FC) PA_FAIL(e, "op %d: a graph has one pooled linear head", i);
         } else {
             PA_FAIL(e, "op %d: unknown kind %d", i, o.kind);
         }
@@ -375,8 +400,9 @@ static void free_plan(pa_model* m) {
     m->arena = nullptr;
     m->bptr.clear();
     void* ptrs[] = {m->d_netin, m->d_tmp, m->d_xtab, m->d_ytab, m->d_hb, m->d_hk, m->d_vb, m->d_vk, m->d_cand,
-                    m->d_cidx, m->d_ccnt, m->d_keys, m->d_order, m->d_supp, m->d_oboxes, m->d_okpts, m->d_ocnt};
+                    m->d_cidx, m->d_ccnt, m->d_keys, m->d_order, m->d_supp, m->d_oboxes, m->d_okpts, m->d_ocnt, m->d_fc};
     for (void* p : ptrs) if (p) hipFree(p);
+    m->d_fc = nullptr;
     m->d_netin = m->d_tmp = nullptr;
     m->d_xtab = m->d_ytab = m->d_hb = m->d_hk = m->d_vb = m->d_vk = nullptr;
     m->d_cand = nullptr; m->d_cidx = m->d_ccnt = nullptr; m->d_keys = nullptr; m->d_order = nullptr; m->d_supp = nullptr;
@@ -455,10 +481,15 @@ static double pil_bicubic(double x) {
     if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
     return 0.0;
 }
-static int pil_coeffs(int in_size, int out_size, std::vector<int32_t>& bounds, std::vector<int32_t>& kk) {
+static double pil_bilinear(double x) {          // Pillow's triangle filter (Image.BILINEAR), support 1
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+enum { PIL_BICUBIC = 0, PIL_BILINEAR = 1 };
+static int pil_coeffs(int in_size, int out_size, std::vector<int32_t>& bounds, std::vector<int32_t>& kk, int filter = PIL_BICUBIC) {
     const double scale = (double)in_size / out_size;
     double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * filterscale;
+    const double support = (filter == PIL_BILINEAR ? 1.0 : 2.0) * filterscale;
     const int ksize = (int)std::ceil(support) * 2 + 1;
     bounds.assign((size_t)out_size * 2, 0);
     kk.assign((size_t)out_size * ksize, 0);
@@ -472,7 +503,11 @@ static int pil_coeffs(int in_size, int out_size, std::vector<int32_t>& bounds, s
         if (xmax > in_size) xmax = in_size;
         xmax -= xmin;
         double ww = 0.0;
-        for (int x = 0; x < xmax; ++x) { k[x] = pil_bicubic((x + xmin - center + 0.5) * ss); ww += k[x]; }
+        for (int x = 0; x < xmax; ++x) {
+            const double arg = (x + xmin - center + 0.5) * ss;
+            k[x] = filter == PIL_BILINEAR ? pil_bilinear(arg) : pil_bicubic(arg);
+            ww += k[x];
+        }
         for (int x = 0; x < xmax; ++x) {
             double v = ww != 0.0 ? k[x] / ww : k[x];
             kk[(size_t)xx * ksize + x] = v < 0 ? (int)(-0.5 + v * (1 << 22)) : (int)(0.5 + v * (1 << 22));
@@ -525,7 +560,7 @@ static void find_upsample_folds(pa_model* m) {
                         (o.res_buf == u.out_buf && overlap(o.res_choff, o.cout, u.out_choff, u.cin));
             } else if (o.kind == PA_OP_SPPF_POOL) {
                 reads = o.in_buf == u.out_buf && overlap(o.in_choff, 4 * o.cin, u.out_choff, u.cin);
-            } else if (o.kind != PA_OP_STEM) {
+            } else if (o.kind != PA_OP_STEM && o.kind != PA_OP_STEM7) {
                 reads = o.in_buf == u.out_buf && overlap(o.in_choff, o.cin, u.out_choff, u.cin);
             }
             if (reads) { reader = k; ++readers; }
@@ -563,7 +598,7 @@ static int plan_buffers(pa_model* m, int batch) {
     auto touch = [&](int b, int i) { if (b >= 0 && b < nb) { first[b] = std::min(first[b], i); last[b] = std::max(last[b], i); } };
     for (int i = 0; i < nops; ++i) {
         const pa_op_desc& o = m->ops[i];
-        if (o.kind != PA_OP_STEM) touch(o.in_buf, i);
+        if (o.kind != PA_OP_STEM && o.kind != PA_OP_STEM7) touch(o.in_buf, i);
         touch(o.out_buf, i);
         if (o.kind == PA_OP_CONV && o.res_buf >= 0) touch(o.res_buf, i);
         if (o.kind == PA_OP_CONV && m->fold_src[i] >= 0) touch(m->ops[m->fold_src[i]].in_buf, i);   // an absorbed upsample's source
@@ -603,6 +638,12 @@ static int plan_buffers(pa_model* m, int batch) {
         }
     } else {
         for (int i = 0; i < nb; ++i) { off[i] = total; total += bytes[i]; }
+    }
+    m->fc_nout = 0;
+    for (const auto& o : m->ops) if (o.kind == PA_OP_GAP_FC) m->fc_nout = o.cout;
+    if (m->fc_nout) {
+        PA_HIP(e, hipMalloc((void**)&m->d_fc, (size_t)batch * 2 * kGapFcMaxOut * sizeof(float)));
+        PA_HIP(e, hipMemsetAsync(m->d_fc, 0, (size_t)batch * 2 * kGapFcMaxOut * sizeof(float), e->stream));
     }
     PA_HIP(e, hipMalloc(&m->arena, total + kConvReadSlack));
     PA_HIP(e, hipMemsetAsync(m->arena, 0, total + kConvReadSlack, e->stream));
@@ -715,6 +756,7 @@ static int conv_launch_args(const pa_model* m, size_t i, int n, ConvArgs& a) {
     a.out = m->bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
     a.res = o.res_buf >= 0 ? m->bptr[o.res_buf] : nullptr;
     a.res_cs = o.res_buf >= 0 ? m->bufs[o.res_buf].channels : 0; a.res_choff = o.res_choff;
+    a.res_pre = (o.res_buf >= 0 && (o.flags & PA_CONV_RES_PREACT)) ? 1 : 0;
     a.zeros = e->zeros;
     a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off;
     a.H = m->net_h >> ib.level; a.W = m->net_w >> ib.level; a.Ho = Ho; a.Wo = Wo;
@@ -814,6 +856,10 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
                 a.dbg = dbg_dev;
             }
             ConvLaunched ran{-1, ""};
+            // act(conv + bias + residual) exists in the h2 and bf16x3 epilogues; the other families refuse instead of applying the other order
+            if (a.res_pre && !h2 && !use_bx3)
+                PA_FAIL(e, "op %zu: PA_CONV_RES_PREACT needs the h2 or the bf16x3 kernels (tuning impl = 2, bf16x3 weights in the blob), not the %s family",
+                        i, f16 ? "fp16" : "fp32-MFMA tap");
             if (h2) {
                 r = launch_conv_h2(a, lv, s, &ran);
             } else if (f16) {
@@ -869,6 +915,30 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
             pr = prof_begin(m, (*pi)++, o.kind, 2, 0.0);
             r = launch_maxpool2(m->bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, m->bptr[o.out_buf],
                                 ob.channels, o.out_choff, o.cin, n, Ho * 2, Wo * 2, s, (int)m->d.dtype);
+        } else if (o.kind == PA_OP_MAXPOOL3S2) {
+            const int lin = m->bufs[o.in_buf].level;
+            pr = prof_begin(m, (*pi)++, o.kind, 3, 0.0);
+            r = launch_maxpool3s2(m->bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, m->bptr[o.out_buf], ob.channels, o.out_choff,
+                                  o.cin, n, m->net_h >> lin, m->net_w >> lin, Ho, Wo, s, m->d.dtype == PA_DTYPE_H2 ? 1 : 0);
+        } else if (o.kind == PA_OP_STEM7) {
+            if (!m->d_netin) PA_FAIL(e, "op %zu: the 7x7 stem reads the u8 network input of pa_resnet_infer", i);
+            const bool head = o.out_buf == m->d.head_buf[0] || o.out_buf == m->d.head_buf[1] || o.out_buf == m->d.head_buf[2];
+            Stem7Args a{};
+            a.in = m->d_netin; a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off; a.lut = m->d_w + o.reserved;
+            a.out = m->bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
+            a.H = m->net_h; a.W = m->net_w; a.Ho = Ho; a.Wo = Wo; a.B = n; a.act = o.act;
+            a.out_h2 = (m->d.dtype == PA_DTYPE_H2 && !head) ? 1 : 0;
+            a.ovf_flag = m->d_ovf;
+            pr = prof_begin(m, (*pi)++, o.kind, 7, 2.0 * n * Ho * Wo * 64.0 * 147.0);
+            if (pr) { pr->M = n * Ho * Wo; pr->cout = 64; pr->cin = 3; pr->stride = 2; }
+            r = launch_stem7(a, s);
+        } else if (o.kind == PA_OP_GAP_FC) {
+            const int lin = m->bufs[o.in_buf].level;
+            const int hw = (m->net_h >> lin) * (m->net_w >> lin);
+            pr = prof_begin(m, (*pi)++, o.kind, 0, 2.0 * n * (double)o.cout * o.cin);
+            if (pr) { pr->M = n; pr->cout = o.cout; pr->cin = o.cin; }
+            r = launch_gap_fc(m->bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, o.cin, n, hw, m->d_w + o.w_off, m->d_w + o.b_off,
+                              o.cout, m->d_fc, m->d_fc + (size_t)m->p_batch * kGapFcMaxOut, s, m->d.dtype == PA_DTYPE_H2 ? 1 : 0);
         }
         prof_end(m, pr);
         if (r != hipSuccess) PA_FAIL(e, "op %zu (kind %d) launch failed: %s", i, o.kind, hipGetErrorString(r));
@@ -1307,6 +1377,142 @@ int pa_tracknet_infer(pa_model* m, const float* x, int n, int h, int w, int x_on
     return 0;
 }
 
+// ---- court keypoints: the ResNet-50 regressor of trackers/keypoints_tracker (keypoints_tracker.py:264-312, iterable.py:10-39) ----
+// transforms.Resize((224, 224)) on a PIL image is Image.resize(..., BILINEAR): the separable 22-bit fixed-point passes of the
+// pose path with the triangle filter, horizontal first; ToTensor + Normalize happen inside the stem (its 3 x 256 table).
+static const int RESNET_S = 224;
+
+static int plan_resnet(pa_model* m, int h0, int w0) {
+    pa_engine* e = m->e;
+    PA_HIP(e, hipStreamSynchronize(e->stream));
+    free_plan(m);
+    const int S = RESNET_S;
+    m->net_h = m->net_w = S;
+    m->rw = m->rh = S; m->top = m->left = 0; m->lb_mode = 0;
+    std::vector<int32_t> b, k;
+    if (w0 != S) { m->hks = pil_coeffs(w0, S, b, k, PIL_BILINEAR); PA_HIP(e, upload(e, &m->d_hb, b)); PA_HIP(e, upload(e, &m->d_hk, k)); }
+    if (h0 != S) { m->vks = pil_coeffs(h0, S, b, k, PIL_BILINEAR); PA_HIP(e, upload(e, &m->d_vb, b)); PA_HIP(e, upload(e, &m->d_vk, k)); }
+    if (w0 != S && h0 != S) PA_HIP(e, hipMalloc((void**)&m->d_tmp, (size_t)m->max_batch * h0 * S * 3));
+    PA_HIP(e, hipMalloc((void**)&m->d_netin, (size_t)m->max_batch * S * S * 4));
+    if (plan_buffers(m, m->max_batch)) return 1;
+    PA_HIP(e, hipStreamSynchronize(e->stream));
+    m->p_h0 = h0; m->p_w0 = w0; m->p_imgsz = S; m->p_pre = PA_PRE_PIL_STRETCH; m->p_auto = 0;
+    m->planned = true;
+    return 0;
+}
+
+int pa_resnet_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, int frames_on_device, float* out_xy, float* out_logits) {
+    if (!m) return 1;
+    pa_engine* e = m->e;
+    if (m->d.task != PA_TASK_RESNET) PA_FAIL(e, "pa_resnet_infer on a model of another task");
+    if (!frames || n <= 0 || h <= 0 || w <= 0) PA_FAIL(e, "pa_resnet_infer: bad arguments");
+    PA_HIP(e, hipSetDevice(e->dev));
+    if (m->n_inflight) PA_FAIL(e, "pa_resnet_infer: tickets in flight");
+    if (!m->planned || m->p_h0 != h || m->p_w0 != w || m->p_batch != m->max_batch)
+        if (plan_resnet(m, h, w)) return 1;
+    if (m->fc_nout && !out_xy) PA_FAIL(e, "pa_resnet_infer: out_xy is NULL");
+    hipStream_t s = e->stream;
+    const int S = RESNET_S;
+    const size_t frame_bytes = (size_t)h * w * 3;
+    m->ovf_cached = false;               // this call's kernels may raise the flag: the host copy is stale
+    size_t pi = 0;
+    for (int c0 = 0; c0 < n; c0 += m->max_batch) {
+        const int nb = std::min(m->max_batch, n - c0);
+        const uint8_t* src = frames + (size_t)c0 * frame_bytes;
+        if (!frames_on_device) {
+            if (m->frames_cap < (size_t)nb * frame_bytes) {
+                if (m->d_frames) hipFree(m->d_frames);
+                m->frames_cap = (size_t)m->max_batch * frame_bytes;
+                PA_HIP(e, hipMalloc((void**)&m->d_frames, m->frames_cap));
+            }
+            PA_HIP(e, hipMemcpyAsync(m->d_frames, src, (size_t)nb * frame_bytes, hipMemcpyHostToDevice, s));
+            src = m->d_frames;
+        }
+        // ---- BGR frames -> RGB, Pillow bilinear to 224 x 224 (horizontal pass, then vertical), u8 NHWC4
+        ProfRec* pr = prof_begin(m, pi++, PROF_PRE, 0, 0.0);
+        hipError_t r = hipSuccess;
+        if (h == S && w == S) {
+            LetterboxArgs a{};
+            a.src = src; a.dst = m->d_netin; a.B = nb; a.h0 = h; a.w0 = w; a.rw = S; a.rh = S; a.nh = S; a.nw = S; a.mode = 0; a.reverse = 1;
+            r = launch_letterbox(a, s);
+        } else {
+            const uint8_t* cur = src; int cw = w;
+            if (w != S) {
+                ResamplePassArgs a{};
+                const bool last = (h == S);
+                a.in = cur; a.out = last ? m->d_netin : m->d_tmp; a.B = nb; a.in_h = h; a.in_w = w; a.in_c = 3;
+                a.out_h = h; a.out_w = S; a.out_c = last ? 4 : 3; a.vertical = 0; a.bounds = m->d_hb; a.coefs = m->d_hk;
+                a.ksize = m->hks; a.reverse = last ? 1 : 0;
+                r = launch_resample_pass(a, s);
+                cur = m->d_tmp; cw = S;
+            }
+            if (r == hipSuccess && h != S) {
+                ResamplePassArgs a{};
+                a.in = cur; a.out = m->d_netin; a.B = nb; a.in_h = h; a.in_w = cw; a.in_c = 3;
+                a.out_h = S; a.out_w = cw; a.out_c = 4; a.vertical = 1; a.bounds = m->d_vb; a.coefs = m->d_vk;
+                a.ksize = m->vks; a.reverse = 1;
+                r = launch_resample_pass(a, s);
+            }
+        }
+        prof_end(m, pr);
+        if (r != hipSuccess) PA_FAIL(e, "preprocess launch failed: %s", hipGetErrorString(r));
+        if (run_graph(m, nb, &pi)) return 1;
+        if (m->fc_nout) {
+            const size_t row = (size_t)m->fc_nout * sizeof(float);
+            PA_HIP(e, hipMemcpyAsync(out_xy + (size_t)c0 * m->fc_nout, m->d_fc + (size_t)m->p_batch * kGapFcMaxOut, nb * row, hipMemcpyDeviceToHost, s));
+            if (out_logits) PA_HIP(e, hipMemcpyAsync(out_logits + (size_t)c0 * m->fc_nout, m->d_fc, nb * row, hipMemcpyDeviceToHost, s));
+        }
+        PA_HIP(e, hipStreamSynchronize(s));
+        m->last_n = nb;
+    }
+    finish_profile(m, pi);
+    return 0;
+}
+
+int pa_pil_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_t* coefs, int coefs_cap, int* ksize) {
+    if (in_size < 1 || out_size < 1 || (filter != PIL_BICUBIC && filter != PIL_BILINEAR) || !ksize) return 1;
+    std::vector<int32_t> b, k;
+    *ksize = pil_coeffs(in_size, out_size, b, k, filter);
+    if (!bounds || !coefs) return 0;                       // size query
+    if ((size_t)coefs_cap < k.size()) return 1;
+    memcpy(bounds, b.data(), b.size() * sizeof(int32_t));
+    memcpy(coefs, k.data(), k.size() * sizeof(int32_t));
+    return 0;
+}
+
+int pa_resnet_read_netin(pa_model* m, int n, uint8_t* out) {
+    if (!m) return 1;
+    pa_engine* e = m->e;
+    if (m->d.task != PA_TASK_RESNET || !m->planned || !m->d_netin || n < 1 || n > m->last_n || !out) PA_FAIL(e, "pa_resnet_read_netin: no plan / bad n");
+    PA_HIP(e, hipSetDevice(e->dev));
+    PA_HIP(e, hipMemcpyAsync(out, m->d_netin, (size_t)n * RESNET_S * RESNET_S * 4, hipMemcpyDeviceToHost, e->stream));
+    PA_HIP(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+int pa_resnet_read_fc(pa_model* m, int n, float* out_xy, float* out_logits) {
+    if (!m) return 1;
+    pa_engine* e = m->e;
+    if (!m->planned || !m->fc_nout || !m->d_fc || n < 1 || n > m->p_batch) PA_FAIL(e, "pa_resnet_read_fc: no plan with a pooled linear head / bad n");
+    PA_HIP(e, hipSetDevice(e->dev));
+    const size_t bytes = (size_t)n * m->fc_nout * sizeof(float);
+    if (out_xy) PA_HIP(e, hipMemcpyAsync(out_xy, m->d_fc + (size_t)m->p_batch * kGapFcMaxOut, bytes, hipMemcpyDeviceToHost, e->stream));
+    if (out_logits) PA_HIP(e, hipMemcpyAsync(out_logits, m->d_fc, bytes, hipMemcpyDeviceToHost, e->stream));
+    PA_HIP(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+int pa_resnet_read_head(pa_model* m, int n, float* out) {
+    if (!m) return 1;
+    pa_engine* e = m->e;
+    const int b = m->d.head_buf[0];
+    if (m->d.task != PA_TASK_RESNET || !m->planned || b < 0 || n < 1 || n > m->last_n || !out) PA_FAIL(e, "pa_resnet_read_head: no plan / no head buffer / bad n");
+    PA_HIP(e, hipSetDevice(e->dev));
+    const size_t hw = (size_t)(m->net_h >> m->bufs[b].level) * (m->net_w >> m->bufs[b].level);
+    PA_HIP(e, hipMemcpyAsync(out, m->bptr[b], (size_t)n * hw * m->bufs[b].channels * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    PA_HIP(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
 
 // ------------------------------------------------------------------------------- ball session
 struct pa_ball {

@@ -103,8 +103,22 @@ typedef unsigned short h2_u16x2 __attribute__((ext_vector_type(2)));
 //     goes up when an h part IS the largest fp16 number, i.e. for |x| > 65488 (a shade earlier than |x| > 65504; NaN is
 //     clamped to -65504 by v_med3 and flagged too).
 // Arithmetic per value is unchanged (same operations in the same order): results are bitwise those of round 3.
+// a.res_pre (PA_CONV_RES_PREACT, ResNet's bottleneck join): the residual is added BEFORE the activation, act(conv + bias + res),
+// in all three paths (16-byte pair path, element-wise path; fp32 head maps carry no residual).
 // Needs whole fragments inside the tensor, choff % 16 == 0 and cs % 16 == 0 (pairs) or % 4 (fp32 out); everything else takes
 // h2_epilogue_slow.
+// what a conv computed for one output, before the activation: (main + cross / 2048) * (1 / row scale) + bias
+__device__ __forceinline__ float h2_conv_value(float cross, float mainacc, float sc, float b) {
+    return fmaf(fmaf(cross, kH2InvScale, mainacc), sc, b);
+}
+// a 16-byte residual piece as the pair path loads it -> this lane's four values (the inverse of the store's two swaps, then decode)
+__device__ __forceinline__ f32x4 h2_residual4(const h2_u32x4 rr) {
+    const h2_u32x2 s0 = __builtin_amdgcn_permlane16_swap(rr[0], rr[2], false, false);
+    const h2_u32x2 s1 = __builtin_amdgcn_permlane16_swap(rr[1], rr[3], false, false);
+    const h2_u32x2 hd = {s0[0], s1[0]}, md = {s0[1], s1[1]};
+    return h2_decode4(__builtin_bit_cast(h16x4, hd), __builtin_bit_cast(h16x4, md));
+}
+
 template <int MF, int NF, int ACT, bool RES, bool F32OUT>
 __device__ __forceinline__ void h2_epilogue_fast(const ConvArgs& a, const f32x4 (&mainacc)[MF][NF], const f32x4 (&cross)[MF][NF],
                                                  const int (&mpix)[MF], int fw, int lq, bool& bad) {
@@ -126,7 +140,7 @@ __device__ __forceinline__ void h2_epilogue_fast(const ConvArgs& a, const f32x4 
             for (int f = 0; f < MF; ++f) {
                 f32x4 v;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = h2_act<ACT>(fmaf(fmaf(cross[f][j][r], kH2InvScale, mainacc[f][j][r]), sc[j][r], b[j][r]));
+                for (int r = 0; r < 4; ++r) v[r] = h2_act<ACT>(h2_conv_value(cross[f][j][r], mainacc[f][j][r], sc[j][r], b[j][r]));
                 *reinterpret_cast<f32x4*>(op[f] + j * 16) = v;
             }
     } else {
@@ -149,14 +163,19 @@ __device__ __forceinline__ void h2_epilogue_fast(const ConvArgs& a, const f32x4 
             for (int f = 0; f < MF; ++f) {
                 f32x4 v;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = h2_act<ACT>(fmaf(fmaf(cross[f][j][r], kH2InvScale, mainacc[f][j][r]), sc[j][r], b[j][r]));
+                for (int r = 0; r < 4; ++r) v[r] = h2_conv_value(cross[f][j][r], mainacc[f][j][r], sc[j][r], b[j][r]);
                 if constexpr (RES) {
-                    const h2_u32x2 s0 = __builtin_amdgcn_permlane16_swap(rr[f][j][0], rr[f][j][2], false, false);
-                    const h2_u32x2 s1 = __builtin_amdgcn_permlane16_swap(rr[f][j][1], rr[f][j][3], false, false);
-                    const h2_u32x2 hd = {s0[0], s1[0]}, md = {s0[1], s1[1]};
-                    const f32x4 rv = h2_decode4(__builtin_bit_cast(h16x4, hd), __builtin_bit_cast(h16x4, md));
+                    const f32x4 rv = h2_residual4(rr[f][j]);
+                    if (a.res_pre) {          // PA_CONV_RES_PREACT: act(conv + bias + residual)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] += rv[r];
+                        for (int r = 0; r < 4; ++r) v[r] = h2_act<ACT>(v[r] + rv[r]);
+                    } else {                  // the default order: act(conv + bias) + residual
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = h2_act<ACT>(v[r]) + rv[r];
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = h2_act<ACT>(v[r]);
                 }
                 h2_u32x2 hd, md;
 #pragma unroll
@@ -198,11 +217,14 @@ __device__ __forceinline__ void h2_epilogue_slow(const ConvArgs& a, const f32x4 
             for (int r = 0; r < 4; ++r) {
                 const int co = co0 + r;
                 if (co >= a.cout) continue;
-                float x = h2_act<ACT>(fmaf(fmaf(cross[f][j][r], kH2InvScale, mainacc[f][j][r]), sc[r], b[r]));
+                float x = h2_conv_value(cross[f][j][r], mainacc[f][j][r], sc[r], b[r]);
                 if (RES) {
                     const int rc = a.res_choff + co;
                     const _Float16* rp = reinterpret_cast<const _Float16*>(resb + (long long)m * a.res_cs * 4 + (long long)(rc >> 4) * 64) + (rc & 15);
-                    x += fmaf((float)rp[16], kH2InvScale, (float)rp[0]);
+                    const float rv = fmaf((float)rp[16], kH2InvScale, (float)rp[0]);
+                    x = a.res_pre ? h2_act<ACT>(x + rv) : h2_act<ACT>(x) + rv;      // PA_CONV_RES_PREACT: the residual before the activation
+                } else {
+                    x = h2_act<ACT>(x);
                 }
                 if (a.out_f32) {
                     a.out[(long long)m * a.out_cs + a.out_choff + co] = x;

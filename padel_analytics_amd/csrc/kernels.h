@@ -16,7 +16,8 @@ struct ConvArgs {
     const float* w;       // packed weights [Npad][Ktot], K order = (c32 chunk, tap, c16 half)
     const void* w3;       // bf16x3 kernels: the same weights pre-split, [Npad][k-step][hi|mid|lo][32 bf16] (or nullptr)
     const float* bias;    // [Npad]
-    const float* res;     // optional residual buffer base (added AFTER the activation) or nullptr
+    const float* res;     // optional residual buffer base (added AFTER the activation, or before it: res_pre) or nullptr
+    int res_pre;          // 1 (PA_CONV_RES_PREACT): out = act(conv + bias + res) — ResNet's bottleneck join; h2 and bf16x3 kernels only
     const float* zeros;   // >= 64 bytes of zeros in HBM (source of padded taps)
     const float* in2;     // bf16x3 1x1 and patch kernels: channels [0, up_c) of the input are read from this buffer of HALF the
     int in2_cs, in2_choff, up_c;   // spatial size at [y >> 1][x >> 1] (an absorbed nn.Upsample(2)); nullptr: none; up_c % 32 == 0
@@ -145,6 +146,34 @@ hipError_t launch_h2_encode(const float* in, float* out, long long n_floats, uns
 // MaxPool2d(2,2)
 hipError_t launch_maxpool2(const float* in, int in_cs, int in_choff, float* out, int out_cs, int out_choff,
                            int c, int B, int H, int W, hipStream_t s, int f16 = 0);
+
+// ---- ResNet-50 court-keypoint regressor (resnet_ops.hip) ----------------------------------------------
+// conv1: Conv 7x7 stride 2 pad 3, 3 -> 64, + bias (BatchNorm folded) + ReLU straight from the u8 NHWC4 network input.  Every byte
+// goes through `lut` ([3][256] fp32: the normalised value of colour c, byte b) — the padding is zero in NORMALISED space, which is
+// why the normalisation cannot be folded into the weights.  w: [148][64] fp32, row k = (ky * 7 + kx) * 3 + c (row 147: zeros).
+struct Stem7Args {
+    const uint8_t* in;    // [B][H][W][4] u8
+    const float* w;       // [148][64]
+    const float* bias;    // [64]
+    const float* lut;     // [3][256]
+    float* out;           // fp32 or h2 pairs, pixel stride out_cs
+    int out_cs, out_choff;
+    int H, W, Ho, Wo, B;
+    int act;              // ACT_RELU | ACT_NONE
+    int out_h2;           // 1: h2 pairs
+    unsigned* ovf_flag;
+    unsigned howo_magic, howo_shift, wo_magic, wo_shift;   // filled by launch_stem7
+};
+hipError_t launch_stem7(const Stem7Args& a, hipStream_t s);
+// MaxPool2d(3, 2, 1) of an H x W map into an Ho x Wo one (padding = -inf: absent taps are skipped); h2 = 1: h2 pairs ordered like
+// every other h2 pool (value, then pair bits); c % 4 == 0 (fp32) / c, choff % 4 == 0 inside 16-channel groups (h2)
+hipError_t launch_maxpool3s2(const float* in, int in_cs, int in_choff, float* out, int out_cs, int out_choff,
+                             int c, int B, int H, int W, int Ho, int Wo, hipStream_t s, int h2);
+// global average pool over the HW pixels of c channels (fp32 sum in pixel order / HW), then nout <= 64 outputs of a linear layer
+// (w [nout][c], fp32 FMA chains, one wave per output) + bias -> logits [B][nout], and their sigmoid -> probs [B][nout]
+hipError_t launch_gap_fc(const float* in, int in_cs, int in_choff, int c, int B, int HW, const float* w, const float* bias, int nout,
+                         float* logits, float* probs, hipStream_t s, int h2);
+constexpr int kGapFcMaxC = 4096, kGapFcMaxOut = 64;
 
 // ---- preprocessing -----------------------------------------------------------------
 struct LetterboxArgs {

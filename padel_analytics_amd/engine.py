@@ -86,6 +86,7 @@ ABI_SYMBOLS = [
     "pa_bytetrack_create", "pa_bytetrack_destroy", "pa_bytetrack_reset", "pa_bytetrack_update_batch",
     "pa_model_take_overflow", "pa_yolo_postprocess", "pa_host_register", "pa_host_unregister",
     "pa_engine_bcast_weights_from", "pa_model_fill_arena", "pa_yolo_submit", "pa_yolo_wait",
+    "pa_resnet_infer", "pa_resnet_read_netin", "pa_resnet_read_fc", "pa_resnet_read_head", "pa_pil_coeffs",
 ]
 
 
@@ -127,6 +128,11 @@ def load_library():
     lib.pa_yolo_head_shape.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.pa_yolo_read_head.argtypes = [vp, i32, i32, vp]
     lib.pa_tracknet_infer.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
+    lib.pa_resnet_infer.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
+    lib.pa_resnet_read_netin.argtypes = [vp, i32, vp]
+    lib.pa_resnet_read_fc.argtypes = [vp, i32, vp, vp]
+    lib.pa_resnet_read_head.argtypes = [vp, i32, vp]
+    lib.pa_pil_coeffs.argtypes = [i32, i32, i32, vp, vp, i32, C.POINTER(i32)]
     lib.pa_engine_set_profiling.argtypes = [vp, i32]
     lib.pa_model_last_profile.argtypes = [vp, i32, vp, vp, vp, vp]
     lib.pa_model_profile_text.argtypes = [vp, C.c_char_p, sz]
@@ -168,6 +174,23 @@ def load_library():
         raise EngineUnavailable("libpadel_hip.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+PIL_BICUBIC, PIL_BILINEAR = 0, 1
+
+
+def pil_coeffs(in_size: int, out_size: int, filter: int = PIL_BICUBIC):
+    """(bounds (out, 2) int32 {first input index, taps}, coefs (out, ksize) int32, 22-bit fixed point) of one Pillow resample
+    pass as the device kernels use them (``pa_pil_coeffs``: host code, no GPU needed)."""
+    lib = load_library()
+    ks = C.c_int(0)
+    if lib.pa_pil_coeffs(in_size, out_size, filter, None, None, 0, C.byref(ks)) != 0:
+        raise EngineError("pa_pil_coeffs: bad arguments")
+    bounds = np.zeros((out_size, 2), np.int32)
+    coefs = np.zeros((out_size, ks.value), np.int32)
+    if lib.pa_pil_coeffs(in_size, out_size, filter, bounds.ctypes.data, coefs.ctypes.data, coefs.size, C.byref(ks)) != 0:
+        raise EngineError("pa_pil_coeffs failed")
+    return bounds, coefs
 
 
 def graph_dtype(mode: Optional[str] = None) -> str:
@@ -595,6 +618,47 @@ class Model:
         self.engine._check(self.engine.lib.pa_tracknet_infer(self.handle, x.ctypes.data, n, h, w, 0, out.ctypes.data, 0))
         return out
 
+    # ---- court keypoints (PA_TASK_RESNET graphs: graph.build_resnet50)
+    def resnet_infer(self, frames, n: int, h: int, w: int, *, want_logits: bool = False):
+        """frames: (n, h, w, 3) uint8 BGR ndarray, or a DeviceBuffer holding the same bytes -> (xy (n, c) fp32 sigmoid outputs,
+        logits (n, c) | None); c = outputs of the graph's pooled linear head (24).  A graph without one (unit tests) gives
+        (None, None): read its head buffer with ``resnet_read_head``."""
+        on_dev = isinstance(frames, DeviceBuffer)
+        if on_dev:
+            ptr = frames.ptr
+            assert frames.nbytes >= n * h * w * 3
+        else:
+            frames = np.ascontiguousarray(frames, np.uint8)
+            assert frames.shape == (n, h, w, 3), frames.shape
+            ptr = frames.ctypes.data
+        c = next((o["cout"] for o in self.graph.ops if o["kind"] == G.OP_GAP_FC), 0)
+        xy = np.zeros((n, c), np.float32) if c else None
+        logits = np.zeros((n, c), np.float32) if (c and want_logits) else None
+        self.engine._check(self.engine.lib.pa_resnet_infer(self.handle, ptr, n, h, w, int(on_dev),
+                                                           xy.ctypes.data if c else None,
+                                                           logits.ctypes.data if logits is not None else None))
+        return xy, logits
+
+    def resnet_read_netin(self, n: int) -> np.ndarray:
+        """u8 NHWC4 (R, G, B, 0) 224 x 224 network input of the first n frames of the last resnet_infer call."""
+        out = np.empty((n, G.RESNET_INPUT, G.RESNET_INPUT, 4), np.uint8)
+        self.engine._check(self.engine.lib.pa_resnet_read_netin(self.handle, n, out.ctypes.data))
+        return out
+
+    def read_fc(self, n: int):
+        """(xy, logits), each (n, c): what the pooled linear head of the graph wrote during the last replay."""
+        c = next(o["cout"] for o in self.graph.ops if o["kind"] == G.OP_GAP_FC)
+        xy, logits = np.empty((n, c), np.float32), np.empty((n, c), np.float32)
+        self.engine._check(self.engine.lib.pa_resnet_read_fc(self.handle, n, xy.ctypes.data, logits.ctypes.data))
+        return xy, logits
+
+    def resnet_read_head(self, n: int) -> np.ndarray:
+        """Tests: buffer head_buf[0] of a PA_TASK_RESNET graph after the last resnet_infer call, (n, H, W, channels) fp32."""
+        lvl, ch = self.graph.bufs[self.graph.head_buf[0]]
+        out = np.empty((n, G.RESNET_INPUT >> lvl, G.RESNET_INPUT >> lvl, ch), np.float32)
+        self.engine._check(self.engine.lib.pa_resnet_read_head(self.handle, n, out.ctypes.data))
+        return out
+
     def last_profile(self, cap: int = 4096):
         kinds = np.zeros(cap, np.int32)
         ms = np.zeros(cap, np.float32)
@@ -618,6 +682,10 @@ class Model:
             self.engine.lib.pa_model_destroy(self.handle)
             self.handle = None
             self._free_rings()
+
+
+# ``kind`` of the profile rows that are not ops of the graph (csrc/engine.cpp: PROF_PRE, PROF_DECODE, PROF_NMS)
+PROF_PRE, PROF_DECODE, PROF_NMS = 100, 101, 102
 
 
 def parse_profile_text(text: str):

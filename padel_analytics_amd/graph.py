@@ -26,8 +26,9 @@ from . import yolo_arch
 
 # mirror of include/padel_hip.h
 OP_STEM, OP_CONV, OP_SPPF_POOL, OP_UPSAMPLE2X, OP_MAXPOOL2 = 1, 2, 3, 4, 5
+OP_STEM7, OP_MAXPOOL3S2, OP_GAP_FC = 6, 7, 8            # ResNet-50: conv1 7x7 s2, MaxPool2d(3, 2, 1), avgpool + fc + sigmoid
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_SIGMOID, ACT_LEAKY = 0, 1, 2, 3, 4
-TASK_DETECT, TASK_POSE, TASK_TRACKNET = 0, 1, 2
+TASK_DETECT, TASK_POSE, TASK_TRACKNET, TASK_RESNET = 0, 1, 2, 3
 DTYPE_F32, DTYPE_F16, DTYPE_H2 = 0, 1, 2
 
 
@@ -267,12 +268,13 @@ class Graph:
         self.n_floats += arr.size + padn
         return off
 
-    def conv(self, src, dst, w, b, k, s, act, res=None, out_width=None, out_scale=None):
+    def conv(self, src, dst, w, b, k, s, act, res=None, out_width=None, out_scale=None, res_preact=False):
         """src = (buf, choff, width read), dst = (buf, choff).  ``w`` is (cout, cin, k, k) with the
         real channel counts; input channels are zero-padded up to the slice width, output channels up
         to ``out_width`` (those rows are zero, so the kernel writes act(0) there).
         ``out_scale`` (h2 graphs only): per-output-channel factor applied to the accumulated sum before the bias — BatchNorm's
-        scale kept out of the weights, so that a checkpoint's fp16 weights stay fp16 numbers (PA_CONV_W_SINGLE)."""
+        scale kept out of the weights, so that a checkpoint's fp16 weights stay fp16 numbers (PA_CONV_W_SINGLE).
+        ``res_preact``: the residual is added BEFORE the activation, act(conv + bias + res) (PA_CONV_RES_PREACT)."""
         sb, so, sw = src
         cout, cin = w.shape[:2]
         if sw % self.kalign:
@@ -309,10 +311,40 @@ class Graph:
             if self.bx3:            # the same weights pre-split for the bf16x3 kernels (engine tuning impl=2)
                 w3_off = self._add(np.ascontiguousarray(pack_conv_weight_bx3(wp)).view(np.float32))
         b_off = self._add(bp)
+        if res_preact:
+            assert res is not None and self.dtype != DTYPE_F16, "res_preact: a residual, h2 / fp32 graphs only"
+            flags |= FLAG_RES_PREACT
         self.ops.append(dict(kind=OP_CONV, in_buf=sb, in_choff=so, cin=sw, out_buf=dst[0], out_choff=dst[1],
                              cout=ow, ksize=k, stride=s, act=act, res_buf=-1 if res is None else res[0],
                              res_choff=0 if res is None else res[1], npad=npad, w_off=w_off, b_off=b_off, reserved=w3_off,
                              flags=flags))
+
+    # ---- the three ops of the ResNet-50 graph (csrc/resnet_ops.hip)
+    def stem7(self, w, b, dst, act=ACT_RELU):
+        """Conv 7x7 stride 2 pad 3, 3 -> 64 (``w`` (64, 3, 7, 7), BatchNorm folded) + bias + act from the u8 network input of
+        ``pa_resnet_infer`` into ``dst = (buf, choff)`` at level 1.  The blob gets the weights as [148][64] (row (ky * 7 + kx) * 3 + c,
+        row 147 zero), the bias and the [3][256] normalisation table (``resnet_norm_table``)."""
+        w = np.asarray(w, np.float32)
+        assert w.shape == (64, 3, 7, 7), w.shape
+        wp = np.zeros((148, 64), np.float32)
+        wp[:147] = np.ascontiguousarray(w.transpose(2, 3, 1, 0)).reshape(147, 64)
+        w_off, b_off, lut_off = self._add(wp), self._add(np.asarray(b, np.float32)), self._add(resnet_norm_table())
+        self.ops.append(dict(kind=OP_STEM7, in_buf=0, in_choff=0, cin=3, out_buf=dst[0], out_choff=dst[1], cout=64, ksize=7, stride=2,
+                             act=act, res_buf=-1, res_choff=0, npad=64, w_off=w_off, b_off=b_off, reserved=lut_off))
+
+    def maxpool3s2(self, src, dst):
+        """MaxPool2d(3, 2, 1) of ``src = (buf, choff, channels)`` into ``dst = (buf, choff)`` one level coarser."""
+        self.ops.append(dict(kind=OP_MAXPOOL3S2, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=dst[0], out_choff=dst[1], cout=src[2],
+                             ksize=3, stride=2, act=0, res_buf=-1, res_choff=0, npad=0, w_off=0, b_off=0))
+
+    def gap_fc(self, src, w, b):
+        """Mean over the map of ``src = (buf, choff, channels)``, linear layer ``w`` (nout, channels) + ``b``, sigmoid; the results
+        stay with the model (``Model.resnet_infer`` / ``read_fc``)."""
+        w = np.asarray(w, np.float32)
+        assert w.shape[1] == src[2] and len(b) == w.shape[0], (w.shape, src)
+        w_off, b_off = self._add(w), self._add(np.asarray(b, np.float32))
+        self.ops.append(dict(kind=OP_GAP_FC, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=src[0], out_choff=0, cout=w.shape[0],
+                             ksize=0, stride=0, act=ACT_SIGMOID, res_buf=-1, res_choff=0, npad=0, w_off=w_off, b_off=b_off))
 
     def blob(self) -> np.ndarray:
         return np.concatenate(self.chunks) if self.chunks else np.zeros(0, np.float32)
@@ -321,16 +353,17 @@ class Graph:
         """Real (unpadded would need the spec; this counts the op list as executed) 2*MAC per image."""
         total = 0.0
         for o in self.ops:
-            if o["kind"] not in (OP_CONV, OP_STEM):
+            if o["kind"] not in (OP_CONV, OP_STEM, OP_STEM7):
                 continue
             lvl = self.bufs[o["out_buf"]][0]
             hw = (net_h >> lvl) * (net_w >> lvl)
-            kk = 27 if o["kind"] == OP_STEM else o["cin"] * o["ksize"] ** 2
+            kk = 27 if o["kind"] == OP_STEM else 147 if o["kind"] == OP_STEM7 else o["cin"] * o["ksize"] ** 2
             total += 2.0 * hw * o["cout"] * kk
         return total
 
 
 FLAG_W_SINGLE = 1          # pa_op_desc.flags: PA_CONV_W_SINGLE (include/padel_hip.h)
+FLAG_RES_PREACT = 4        # pa_op_desc.flags: PA_CONV_RES_PREACT — act(conv + bias + residual)
 # tests / tuning (PADEL_UNFOLDED_BN=0): fold BatchNorm into the weights of h2 graphs even when the checkpoint's weights are fp16 numbers
 UNFOLDED_BN: bool = os.environ.get("PADEL_UNFOLDED_BN", "1") != "0"
 
@@ -619,4 +652,116 @@ def build_inpaintnet(sd, dtype: str = "f32") -> Graph:
     c1d("predictor", (u3, 0, 32), (out, 0), act=ACT_SIGMOID)
     g.head_buf = (out, -1, -1)
     g.out_channels = 2
+    return g
+
+
+# ---- torchvision ResNet-50 with a 24-way fc: the court-keypoint regressor (reference trackers/keypoints_tracker/
+# keypoints_tracker.py:158-168; forward :286-289; preprocessing iterable.py:16-25) --------------------------------------------
+RESNET_BN_EPS = 1e-5                 # nn.BatchNorm2d default
+RESNET_INPUT = 224
+RESNET_LAYERS = (3, 4, 6, 3)         # bottlenecks per stage, planes 64 / 128 / 256 / 512, expansion 4
+RESNET_OUT = 24                      # 12 keypoints x (x, y)
+# transforms.Normalize of the reference's KeypointsIterable.  The green mean 0.465 is the REFERENCE's value (iterable.py:21; the
+# usual ImageNet figure is 0.456): the checkpoint was trained behind it, so it is reproduced, not corrected.
+RESNET_MEAN = (0.485, 0.465, 0.406)
+RESNET_STD = (0.229, 0.224, 0.225)
+
+
+def resnet_norm_table() -> np.ndarray:
+    """[3][256] fp32: colour c, byte b -> ((b / 255) - mean[c]) / std[c] with exactly the fp32 operations of
+    ``ToTensor`` (``/ 255``) and ``Normalize`` (``sub_(mean).div_(std)`` on float32 tensors)."""
+    b = np.arange(256, dtype=np.float32) / np.float32(255)
+    return np.stack([(b - np.float32(RESNET_MEAN[c])) / np.float32(RESNET_STD[c]) for c in range(3)]).astype(np.float32)
+
+
+def resnet50_shapes(n_out: int = RESNET_OUT) -> dict:
+    """name -> shape of every parameter / buffer of a torchvision ResNet-50 (v1.5: the stride sits on conv2) whose fc has
+    ``n_out`` outputs; ``num_batches_tracked`` scalars are left out (a state_dict may carry them)."""
+    sh = {"conv1.weight": (64, 3, 7, 7)}
+
+    def bn(p, c):
+        for k in ("weight", "bias", "running_mean", "running_var"):
+            sh[f"{p}.{k}"] = (c,)
+    bn("bn1", 64)
+    cin = 64
+    for n, blocks in enumerate(RESNET_LAYERS, 1):
+        planes = 64 << (n - 1)
+        for i in range(blocks):
+            p = f"layer{n}.{i}"
+            sh[f"{p}.conv1.weight"] = (planes, cin, 1, 1); bn(f"{p}.bn1", planes)
+            sh[f"{p}.conv2.weight"] = (planes, planes, 3, 3); bn(f"{p}.bn2", planes)
+            sh[f"{p}.conv3.weight"] = (4 * planes, planes, 1, 1); bn(f"{p}.bn3", 4 * planes)
+            if i == 0:
+                sh[f"{p}.downsample.0.weight"] = (4 * planes, cin, 1, 1); bn(f"{p}.downsample.1", 4 * planes)
+            cin = 4 * planes
+    sh["fc.weight"] = (n_out, 2048)
+    sh["fc.bias"] = (n_out,)
+    return sh
+
+
+def check_resnet50_state_dict(sd) -> None:
+    """ValueError unless ``sd`` is exactly a torchvision ResNet-50 with a 24-way fc (resnet18 / 101, another head: refused)."""
+    want = resnet50_shapes()
+    try:
+        have = {k: tuple(np.shape(v)) for k, v in sd.items() if not k.endswith("num_batches_tracked")}
+    except AttributeError as err:
+        raise ValueError("not a state_dict") from err
+    if have != want:
+        missing = sorted(set(want) - set(have))[:3]
+        extra = sorted(set(have) - set(want))[:3]
+        wrong = sorted(k for k in set(want) & set(have) if want[k] != have[k])[:3]
+        raise ValueError(f"not a torchvision ResNet-50 with a {RESNET_OUT}-way fc (missing {missing}, unexpected {extra}, "
+                         f"other shapes {[(k, have[k]) for k in wrong]})")
+
+
+def build_resnet50(sd, dtype: str = "f32") -> Graph:
+    """The court-keypoint regressor over the engine's op set: conv1 (PA_OP_STEM7, level 1), MaxPool2d(3, 2, 1) and layer1 (level
+    2), layer2 .. layer4 (levels 3 .. 5; v1.5: the stride sits on conv2 of a stage's first block, the downsample branch is a 1x1
+    stride-2 conv), average pool + fc + sigmoid (PA_OP_GAP_FC).  BatchNorm (eps 1e-5) is folded like everywhere else; the join of a
+    bottleneck is relu(bn3(conv3) + identity): conv3 carries the residual with PA_CONV_RES_PREACT.  The weights are fp32, so an
+    h2 graph runs three products per operand pair, as TrackNetV3 does."""
+    check_resnet50_state_dict(sd)
+    g = Graph(task=TASK_RESNET, dtype={"f32": DTYPE_F32, "h2": DTYPE_H2}[dtype])
+    split_bn = g.dtype == DTYPE_H2 and UNFOLDED_BN
+
+    def parts(conv, bn):
+        """-> (weights to pack, bias, out_scale | None): fold_bn / fold_bn_split over this conv's and BatchNorm's tensors"""
+        view = {"x.conv.weight": sd[f"{conv}.weight"]}
+        view.update({f"x.bn.{k}": sd[f"{bn}.{k}"] for k in ("weight", "bias", "running_mean", "running_var")})
+        if split_bn:
+            w, sc, b = fold_bn_split(view, "x", RESNET_BN_EPS)
+            if fp16_exact(w):
+                return w, b, sc
+        w, b = fold_bn(view, "x", RESNET_BN_EPS)
+        return w, b, None
+
+    def cb(conv, bn, src, dst, k, s, act, res=None, res_preact=False):
+        w, b, sc = parts(conv, bn)
+        g.conv(src, dst, w, b, k, s, act, res, out_scale=sc, res_preact=res_preact)
+
+    # conv1 + bn1 + relu from the u8 network input: [148][64] weights (row (ky * 7 + kx) * 3 + c), bias, normalisation table
+    w0, b0 = fold_bn({"x.conv.weight": sd["conv1.weight"], **{f"x.bn.{k}": sd[f"bn1.{k}"] for k in
+                                                               ("weight", "bias", "running_mean", "running_var")}}, "x", RESNET_BN_EPS)
+    stem = g.buf(1, 64)
+    g.stem7(w0, b0, (stem, 0))
+    x = g.buf(2, 64)
+    g.maxpool3s2((stem, 0, 64), (x, 0))
+    cin, level = 64, 2
+    for n, blocks in enumerate(RESNET_LAYERS, 1):
+        planes = 64 << (n - 1)
+        for i in range(blocks):
+            p = f"layer{n}.{i}"
+            stride = 2 if (i == 0 and n > 1) else 1
+            lout = level + (stride == 2)
+            t1, t2, out = g.buf(level, planes), g.buf(lout, planes), g.buf(lout, 4 * planes)
+            cb(f"{p}.conv1", f"{p}.bn1", (x, 0, cin), (t1, 0), 1, 1, ACT_RELU)
+            cb(f"{p}.conv2", f"{p}.bn2", (t1, 0, planes), (t2, 0), 3, stride, ACT_RELU)
+            identity = x
+            if i == 0:
+                identity = g.buf(lout, 4 * planes)
+                cb(f"{p}.downsample.0", f"{p}.downsample.1", (x, 0, cin), (identity, 0), 1, stride, ACT_NONE)
+            cb(f"{p}.conv3", f"{p}.bn3", (t2, 0, planes), (out, 0), 1, 1, ACT_RELU, res=(identity, 0), res_preact=True)
+            x, cin, level = out, 4 * planes, lout
+    g.gap_fc((x, 0, cin), sd["fc.weight"], sd["fc.bias"])
+    g.out_channels = RESNET_OUT
     return g

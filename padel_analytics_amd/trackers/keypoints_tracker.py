@@ -4,8 +4,13 @@
 In the shipped configuration the reference never runs a model here: ``main.py:81-104,154-161`` always passes
 ``fixed_keypoints_detection`` and both predict methods short-circuit (:204-209, :266-271).  The "yolo" model
 type (:199-262) is just another YOLOv8-pose graph (K = 12 keypoints, ``max_det = 12``, conf .5, Pillow stretch
-to 640x640) and runs on the same HIP engine as the players keypoints tracker.  The "resnet" type (a
-torchvision ResNet-50 regressor, :158-168, :273-312) is outside the engine's op set and raises.
+to 640x640) and runs on the same HIP engine as the players keypoints tracker.  The "resnet" type — the constructor's
+default: a torchvision ResNet-50 whose 24 sigmoid outputs are the 12 keypoints as fractions of the frame (:158-168, :273-312,
+preprocessing ``iterable.py:10-39``) — runs on the engine too (``resnet.CourtResNet``: BGR -> RGB, Pillow bilinear resize to
+224 x 224, normalisation, network, sigmoid on the device); it consumes the frame stream in ``predict_frames`` in batches of
+``batch_size`` and its ``predict_sample`` raises ``NoPredictSample``, as in the reference.  Construction opens no file: the
+checkpoint is resolved by ``to`` / at the top of ``predict_frames``, where a file that is missing, unreadable or not a
+ResNet-50 with a 24-way ``fc`` raises ``NotImplementedError`` ("no court model this engine can run") chained from the cause.
 """
 from __future__ import annotations
 
@@ -14,7 +19,8 @@ from typing import Iterable, Optional, Type
 
 import numpy as np
 
-from .tracker import NoPredictFrames, Object, Tracker
+from .. import video
+from .tracker import NoPredictFrames, NoPredictSample, Object, Tracker, _sampler
 
 
 class Keypoint:
@@ -72,12 +78,21 @@ class KeypointsTracker(Tracker):
     @property
     def model(self):
         if self._model is None:
-            if self.model_type != "yolo":
-                raise NotImplementedError("the ResNet-50 court-keypoint regressor is outside this engine's op set; "
-                                          "use model_type='yolo' or fixed_keypoints_detection")
-            from ..yolo import YOLO
-            self._model = YOLO(self.model_path)
+            if self.model_type == "yolo":
+                from ..yolo import YOLO
+                self._model = YOLO(self.model_path)
+            else:
+                from ..resnet import CourtResNet
+                try:
+                    self._model = CourtResNet(self.model_path)
+                except (OSError, ValueError) as err:      # missing / unreadable file, not a ResNet-50 with a 24-way fc
+                    raise NotImplementedError(f"{self.model_path}: no court model this engine can run ({err})") from err
         return self._model
+
+    @property
+    def streams(self):
+        """The ResNet regressor consumes the stream in ``predict_frames`` (runner: no probing call, no file opened for it)."""
+        return True if (self.model_type == "resnet" and self.fixed_keypoints_detection is None) else None
 
     def video_info_post_init(self, video_info) -> "KeypointsTracker": return self
 
@@ -98,6 +113,8 @@ class KeypointsTracker(Tracker):
         if self.fixed_keypoints_detection is not None:
             print(f"{self.__str__()}: using fixed court keypoints")
             return [self.fixed_keypoints_detection for _ in sample]
+        if self.model_type != "yolo":
+            raise NoPredictSample()
         h_frame, w_frame = sample[0].shape[:2]
         ratio_x, ratio_y = w_frame / self.TRAIN_IMAGE_SIZE, h_frame / self.TRAIN_IMAGE_SIZE
         results = self.model.predict_frames(sample, self.CONF, self.IOU, self.TRAIN_IMAGE_SIZE, classes=None,
@@ -118,4 +135,27 @@ class KeypointsTracker(Tracker):
             return [self.fixed_keypoints_detection for _ in frame_generator]
         if self.model_type == "yolo":
             raise NoPredictFrames()
-        raise NotImplementedError("ResNet-50 court keypoints are not supported by this engine")
+        model = self.model                    # resolved before the generator is touched: an unusable checkpoint fails here
+        model.set_max_batch(self.batch_size)
+        predictions = []
+        for sample in _sampler(iter(frame_generator), self.batch_size):      # (an empty generator yields no batch)
+            dev = video.device_batch(sample)
+            if dev is not None:
+                buf, n, h_frame, w_frame = dev
+                outputs = model.infer(buf, n, h_frame, w_frame)
+            else:
+                frames = video.host_batch(sample)
+                h_frame, w_frame = frames.shape[1:3]
+                outputs = model.infer(frames)
+            predictions.extend(self.keypoints_from_outputs(outputs, w_frame, h_frame))
+        return predictions
+
+    @classmethod
+    def keypoints_from_outputs(cls, outputs: np.ndarray, w_frame: int, h_frame: int) -> list:
+        """(n, 24) float32 sigmoid outputs -> ``Keypoints`` per frame: ids 0..11 (``POINTS_MAPPER`` is the YOLO model's), xy =
+        (out[2i] * w_frame, out[2i + 1] * h_frame) as numpy computes float32 x int in the reference (:296-300)."""
+        out = []
+        for row in np.asarray(outputs, np.float32):
+            out.append(Keypoints([Keypoint(i, (float(kp[0] * w_frame), float(kp[1] * h_frame)))      # (the float32 product, as a JSON-able float)
+                                  for i, kp in enumerate(row.reshape(cls.NUMBER_KEYPOINTS, 2))]))
+        return out
