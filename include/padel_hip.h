@@ -45,10 +45,19 @@ enum pa_op_kind {
                              pa_resnet_infer; w_off: [148][64] fp32, row (ky * 7 + kx) * 3 + c, row 147 zero; `reserved`: offset of
                              the [3][256] fp32 table byte -> normalised value (ToTensor + Normalize; padding is zero in THAT space) */
     PA_OP_MAXPOOL3S2 = 7, /* MaxPool2d(3, 2, 1) into a buffer one level coarser (padding = -inf); fp32 and h2 storage          */
-    PA_OP_GAP_FC = 8      /* mean over the map of the cin-channel input slice (fp32), then cout <= 64 outputs of a linear layer
+    PA_OP_GAP_FC = 8,     /* mean over the map of the cin-channel input slice (fp32), then cout <= 64 outputs of a linear layer
                              (w_off: [cout][cin], b_off: [cout], fp32 FMA) and their sigmoid (act = PA_ACT_SIGMOID): cout logits and
                              cout probabilities per image, kept by the model (pa_resnet_infer / pa_resnet_read_fc), not in a buffer:
                              out_buf = in_buf.  One per graph                                                                   */
+    /* YOLO11 (ultralytics 8.3's default family: C3k2 / C2PSA backbone, depthwise class branch in the head): */
+    PA_OP_DWCONV3 = 9,    /* depthwise Conv 3x3 s1 p1 over a cin = cout channel slice (ksize 3, stride 1) + bias + act (NONE | SILU)
+                             (+ residual slice, added after the activation); w_off: [9][cin] fp32, tap ky * 3 + kx, BatchNorm folded;
+                             b_off: [cin]; npad = cin.  fp32 and h2 storage; the slices read and written must not overlap            */
+    PA_OP_PSA_ATTN = 10   /* C2PSA's spatial self-attention over the H * W tokens of one map: per image and head
+                             out = softmax_keys((q^T k) * kd^-1/2) applied to v.  stride = heads, ksize = kd (32), npad = hd (64): nothing
+                             else is implemented.  The input slice (cin = heads * (2 kd + hd)) holds [q of all heads | k of all heads |
+                             v of all heads], head h's q at in_choff + h * kd; the output slice has cout = heads * hd channels.  No
+                             weights.  fp32 and h2 storage                                                                            */
 };
 
 enum pa_act { PA_ACT_NONE = 0, PA_ACT_SILU = 1, PA_ACT_RELU = 2, PA_ACT_SIGMOID = 3, PA_ACT_LEAKY = 4 /* nn.LeakyReLU(0.01): InpaintNet, reference trackers/ball_tracker/models.py:83-93 */ };

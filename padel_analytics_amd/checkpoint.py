@@ -38,6 +38,7 @@ class Checkpoint:
     scale: Optional[str] = None
     names: dict = field(default_factory=dict)
     param_dict: dict = field(default_factory=dict)
+    family: str = "yolov8"                  # detect / pose: "yolov8" | "yolo11" (yolo_arch.infer_family)
 
 
 # ----------------------------------------------------------------------------- stub unpickle
@@ -127,14 +128,18 @@ def _to_np(t):
 # ----------------------------------------------------------------------------- public API
 
 def save_checkpoint(path, state_dict, task, nc=0, kpt_shape=None, scale=None, names=None,
-                    param_dict=None) -> None:
-    """Write a plain-dict checkpoint (synthetic weights)."""
+                    param_dict=None, family=None) -> None:
+    """Write a plain-dict checkpoint (synthetic weights).  ``family`` ("yolov8" | "yolo11", detect / pose only) is read off the
+    state_dict when not given; files written before the field existed load as YOLOv8."""
+    if family is None and task in ("detect", "pose"):
+        family = yolo_arch.infer_family(state_dict)
     sd = OrderedDict((k, torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray)
                       else torch.as_tensor(v)) for k, v in state_dict.items())
     torch.save({
         "padel_format": 1, "task": task, "nc": int(nc),
         "kpt_shape": tuple(kpt_shape) if kpt_shape else None, "scale": scale,
         "names": dict(names or {}), "param_dict": dict(param_dict or {}), "state_dict": sd,
+        "family": family or "yolov8",
     }, str(path))
 
 
@@ -150,7 +155,7 @@ def load_checkpoint(path) -> Checkpoint:
     if isinstance(obj, dict) and obj.get("padel_format") == 1:
         sd = OrderedDict((k, _to_np(v)) for k, v in obj["state_dict"].items())
         return Checkpoint(sd, obj["task"], obj.get("nc", 0), obj.get("kpt_shape"),
-                          obj.get("scale"), obj.get("names") or {}, obj.get("param_dict") or {})
+                          obj.get("scale"), obj.get("names") or {}, obj.get("param_dict") or {}, obj.get("family") or "yolov8")
     if isinstance(obj, dict) and "param_dict" in obj and "model" in obj and isinstance(obj["model"], dict):
         # TrackNetV3 release format (ball_tracker.py:253-265)
         sd = OrderedDict((k, _to_np(v)) for k, v in obj["model"].items())
@@ -163,7 +168,7 @@ def load_checkpoint(path) -> Checkpoint:
         if not tensors:
             raise ValueError(f"{path}: could not recover tensors from the pickled model")
         sd = OrderedDict((k, _to_np(v)) for k, v in tensors.items())
-        info = yolo_arch.infer_arch_from_state_dict(sd)
+        info = yolo_arch.infer_model(sd)          # the family first (C2PSA at model.10: YOLO11), then the scale inside it
         yaml = getattr(model, "yaml", None) or {}
         kpt_shape = yaml.get("kpt_shape") if isinstance(yaml, dict) else None
         if info["nk"] and not kpt_shape:
@@ -176,7 +181,7 @@ def load_checkpoint(path) -> Checkpoint:
             kpt_shape = (nk // 3, 3) if nk % 3 == 0 else (nk // 2, 2)
         names = getattr(model, "names", None) or {}
         return Checkpoint(sd, "pose" if info["nk"] else "detect", info["nc"],
-                          tuple(kpt_shape) if kpt_shape else None, info["scale"], dict(names))
+                          tuple(kpt_shape) if kpt_shape else None, info["scale"], dict(names), family=info["family"])
     raise ValueError(f"{path}: unrecognised checkpoint layout")
 
 
@@ -202,9 +207,10 @@ def load_state_dict(path) -> "OrderedDict[str, np.ndarray]":
     return OrderedDict((k, _to_np(v)) for k, v in obj.items())
 
 
-def make_synthetic_yolo(path, scale, nc, kpt_shape=None, seed=0, cls_bias=-4.0, names=None) -> None:
-    """Seeded synthetic YOLOv8 detect/pose checkpoint (SURVEY.md §8(d) weight recipe)."""
-    sd = yolo_arch.synth_state_dict(scale, nc, kpt_shape, seed, cls_bias)
+def make_synthetic_yolo(path, scale, nc, kpt_shape=None, seed=0, cls_bias=-4.0, names=None, family="yolov8") -> None:
+    """Seeded synthetic YOLOv8 (default) or YOLO11 detect/pose checkpoint (SURVEY.md §8(d) weight recipe)."""
+    synth = {"yolov8": yolo_arch.synth_state_dict, "yolo11": yolo_arch.synth_state_dict11}[family]
+    sd = synth(scale, nc, kpt_shape, seed, cls_bias)
     if names is None:
         names = {i: ("person" if i == 0 else f"class{i}") for i in range(nc)}
     save_checkpoint(path, sd, "pose" if kpt_shape else "detect", nc, kpt_shape, scale, names)

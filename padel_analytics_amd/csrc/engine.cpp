@@ -347,6 +347,30 @@ static int validate_desc(pa_engine* e, const pa_model_desc* d, size_t n_floats) 
                 (size_t)o.w_off + (size_t)o.cout * o.cin > n_floats || o.b_off < 0 || (size_t)o.b_off + o.cout > n_floats || o.act != PA_ACT_SIGMOID)
                 PA_FAIL(e, "op %d: bad pooled linear head", i);
             for (int k = 0; k < i; ++k) if (d->ops[k].kind == PA_OP_GAP_FC) PA_FAIL(e, "op %d: a graph has one pooled linear head", i);
+        } else if (o.kind == PA_OP_DWCONV3) {
+            if (f16) PA_FAIL(e, "op %d: the depthwise conv is not implemented for fp16 storage", i);
+            if (o.ksize != 3 || o.stride != 1 || o.cin != o.cout || ((o.cin | o.in_choff | o.out_choff) & 3) ||
+                d->bufs[o.out_buf].level != d->bufs[o.in_buf].level || (o.act != PA_ACT_NONE && o.act != PA_ACT_SILU))
+                PA_FAIL(e, "op %d: bad depthwise conv (3x3, stride 1, cin = cout, act none | SiLU)", i);
+            if (o.w_off < 0 || (o.w_off & 3) || (size_t)o.w_off + (size_t)9 * o.cin > n_floats || o.b_off < 0 || (o.b_off & 3) ||
+                (size_t)o.b_off + o.cin > n_floats)
+                PA_FAIL(e, "op %d: weights outside the blob", i);
+            if (h2 && is_head_buf(o.in_buf)) PA_FAIL(e, "op %d: a depthwise conv cannot read an fp32 head map of an h2 model", i);
+            if (o.in_buf == o.out_buf && o.in_choff < o.out_choff + o.cout && o.out_choff < o.in_choff + o.cin)
+                PA_FAIL(e, "op %d: a depthwise conv cannot write the slice it reads", i);
+            if (o.res_buf >= 0 && (!okslice(o.res_buf, o.res_choff, o.cout) || (o.res_choff & 3) || d->bufs[o.res_buf].level != d->bufs[o.out_buf].level ||
+                                   (h2 && is_head_buf(o.res_buf))))
+                PA_FAIL(e, "op %d: bad residual slice", i);
+        } else if (o.kind == PA_OP_PSA_ATTN) {
+            if (f16) PA_FAIL(e, "op %d: PSA attention is not implemented for fp16 storage", i);
+            if (o.ksize != 32 || o.npad != 64)
+                PA_FAIL(e, "op %d: PSA attention is implemented for key dim 32 and head dim 64 only (got kd %d, hd %d)", i, o.ksize, o.npad);
+            if (o.stride < 1 || o.cin != o.stride * 128 || o.cout != o.stride * 64 || ((o.in_choff | o.out_choff) & 3) ||
+                d->bufs[o.out_buf].level != d->bufs[o.in_buf].level)
+                PA_FAIL(e, "op %d: bad PSA attention (heads %d, cin %d, cout %d)", i, o.stride, o.cin, o.cout);
+            if (h2 && is_head_buf(o.in_buf)) PA_FAIL(e, "op %d: PSA attention cannot read an fp32 head map of an h2 model", i);
+            if (o.in_buf == o.out_buf && o.in_choff < o.out_choff + o.cout && o.out_choff < o.in_choff + o.cin)
+                PA_FAIL(e, "op %d: PSA attention cannot write the slice it reads", i);
         } else {
             PA_FAIL(e, "op %d: unknown kind %d", i, o.kind);
         }
@@ -558,6 +582,9 @@ static void find_upsample_folds(pa_model* m) {
             if (o.kind == PA_OP_CONV) {
                 reads = (o.in_buf == u.out_buf && overlap(o.in_choff, o.cin, u.out_choff, u.cin)) ||
                         (o.res_buf == u.out_buf && overlap(o.res_choff, o.cout, u.out_choff, u.cin));
+            } else if (o.kind == PA_OP_DWCONV3) {
+                reads = (o.in_buf == u.out_buf && overlap(o.in_choff, o.cin, u.out_choff, u.cin)) ||
+                        (o.res_buf >= 0 && o.res_buf == u.out_buf && overlap(o.res_choff, o.cout, u.out_choff, u.cin));
             } else if (o.kind == PA_OP_SPPF_POOL) {
                 reads = o.in_buf == u.out_buf && overlap(o.in_choff, 4 * o.cin, u.out_choff, u.cin);
             } else if (o.kind != PA_OP_STEM && o.kind != PA_OP_STEM7) {
@@ -600,7 +627,7 @@ static int plan_buffers(pa_model* m, int batch) {
         const pa_op_desc& o = m->ops[i];
         if (o.kind != PA_OP_STEM && o.kind != PA_OP_STEM7) touch(o.in_buf, i);
         touch(o.out_buf, i);
-        if (o.kind == PA_OP_CONV && o.res_buf >= 0) touch(o.res_buf, i);
+        if ((o.kind == PA_OP_CONV || o.kind == PA_OP_DWCONV3) && o.res_buf >= 0) touch(o.res_buf, i);
         if (o.kind == PA_OP_CONV && m->fold_src[i] >= 0) touch(m->ops[m->fold_src[i]].in_buf, i);   // an absorbed upsample's source
     }
     if (m->d.task == PA_TASK_TRACKNET) touch(0, -1);
@@ -806,7 +833,7 @@ static bool stem_fusable(const pa_model* m, size_t i) {
         if (k == i || k == i + 1) continue;
         const pa_op_desc& o = m->ops[k];
         if (o.kind != PA_OP_STEM && o.in_buf == st.out_buf) return false;
-        if (o.kind == PA_OP_CONV && o.res_buf == st.out_buf) return false;
+        if ((o.kind == PA_OP_CONV || o.kind == PA_OP_DWCONV3) && o.res_buf == st.out_buf) return false;
     }
     return true;
 }
@@ -939,6 +966,32 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
             if (pr) { pr->M = n; pr->cout = o.cout; pr->cin = o.cin; }
             r = launch_gap_fc(m->bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, o.cin, n, hw, m->d_w + o.w_off, m->d_w + o.b_off,
                               o.cout, m->d_fc, m->d_fc + (size_t)m->p_batch * kGapFcMaxOut, s, m->d.dtype == PA_DTYPE_H2 ? 1 : 0);
+        } else if (o.kind == PA_OP_DWCONV3) {
+            const bool h2 = m->d.dtype == PA_DTYPE_H2;
+            const bool head = o.out_buf == m->d.head_buf[0] || o.out_buf == m->d.head_buf[1] || o.out_buf == m->d.head_buf[2];
+            DwConvArgs a{};
+            a.in = m->bptr[o.in_buf]; a.in_cs = m->bufs[o.in_buf].channels; a.in_choff = o.in_choff;
+            a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off;
+            a.out = m->bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
+            if (o.res_buf >= 0) { a.res = m->bptr[o.res_buf]; a.res_cs = m->bufs[o.res_buf].channels; a.res_choff = o.res_choff; }
+            a.C = o.cin; a.B = n; a.H = Ho; a.W = Wo; a.act = o.act;
+            a.h2 = h2 ? 1 : 0; a.out_f32 = (h2 && head) ? 1 : 0; a.ovf_flag = m->d_ovf;
+            pr = prof_begin(m, (*pi)++, o.kind, 3, 2.0 * n * Ho * Wo * (double)o.cin * 9.0);
+            if (pr) { pr->M = n * Ho * Wo; pr->cout = o.cout; pr->cin = o.cin; pr->stride = 1; pr->res = o.res_buf >= 0; }
+            r = launch_dwconv3(a, s);
+        } else if (o.kind == PA_OP_PSA_ATTN) {
+            const bool h2 = m->d.dtype == PA_DTYPE_H2;
+            const bool head = o.out_buf == m->d.head_buf[0] || o.out_buf == m->d.head_buf[1] || o.out_buf == m->d.head_buf[2];
+            AttnArgs a{};
+            a.heads = o.stride; a.kd = o.ksize; a.hd = o.npad;
+            a.qkv = m->bptr[o.in_buf]; a.cs = m->bufs[o.in_buf].channels;
+            a.q_choff = o.in_choff; a.k_choff = o.in_choff + a.heads * a.kd; a.v_choff = o.in_choff + 2 * a.heads * a.kd;
+            a.out = m->bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
+            a.N = Ho * Wo; a.B = n; a.scale = (float)(1.0 / std::sqrt((double)a.kd));
+            a.h2 = h2 ? 1 : 0; a.out_f32 = (h2 && head) ? 1 : 0; a.ovf_flag = m->d_ovf;
+            pr = prof_begin(m, (*pi)++, o.kind, 0, 2.0 * n * (double)a.heads * a.N * (double)a.N * (a.kd + a.hd));
+            if (pr) { pr->M = n * a.N; pr->cout = o.cout; pr->cin = o.cin; pr->stride = a.heads; }
+            r = launch_psa_attn(a, s);
         }
         prof_end(m, pr);
         if (r != hipSuccess) PA_FAIL(e, "op %zu (kind %d) launch failed: %s", i, o.kind, hipGetErrorString(r));

@@ -175,6 +175,37 @@ hipError_t launch_gap_fc(const float* in, int in_cs, int in_choff, int c, int B,
                          float* logits, float* probs, hipStream_t s, int h2);
 constexpr int kGapFcMaxC = 4096, kGapFcMaxOut = 64;
 
+// ---- YOLO11 (yolo11_ops.hip) ---------------------------------------------------------------------------
+// depthwise Conv 3x3 stride 1 pad 1 over a C-channel slice (C, choffs, pixel strides % 4 == 0): w [9][C] fp32 (tap ky * 3 + kx,
+// BatchNorm folded), bias [C]; act ACT_NONE | ACT_SILU; res (optional): a slice added after the activation.  h2 = 1: in / res are
+// h2 pairs and so is out, unless out_f32 (a head map).  Absent taps are skipped, not read.
+struct DwConvArgs {
+    const float* in;
+    const float* w;
+    const float* bias;
+    const float* res;     // nullptr: none
+    float* out;
+    int in_cs, in_choff, out_cs, out_choff, res_cs, res_choff;
+    int C, B, H, W;
+    int act;
+    int h2, out_f32;
+    unsigned* ovf_flag;
+};
+hipError_t launch_dwconv3(const DwConvArgs& a, hipStream_t s);
+// PSA attention over the N = H * W tokens of one map: per image and head, out = softmax_keys((q^T k) * scale) applied to v.
+// qkv (pixel stride cs): q of head h at channels q_choff + h * kd, k at k_choff + h * kd, v at v_choff + h * hd; out: hd channels
+// per head at out_choff + h * hd.  kd = 32 and hd = 64 only (hipErrorNotSupported otherwise).
+struct AttnArgs {
+    const float* qkv;
+    float* out;
+    int cs, q_choff, k_choff, v_choff, out_cs, out_choff;
+    int heads, kd, hd, N, B;
+    float scale;
+    int h2, out_f32;
+    unsigned* ovf_flag;
+};
+hipError_t launch_psa_attn(const AttnArgs& a, hipStream_t s);
+
 // ---- preprocessing -----------------------------------------------------------------
 struct LetterboxArgs {
     const uint8_t* src;   // [B][h0][w0][3] u8

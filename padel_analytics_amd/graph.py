@@ -27,6 +27,7 @@ from . import yolo_arch
 # mirror of include/padel_hip.h
 OP_STEM, OP_CONV, OP_SPPF_POOL, OP_UPSAMPLE2X, OP_MAXPOOL2 = 1, 2, 3, 4, 5
 OP_STEM7, OP_MAXPOOL3S2, OP_GAP_FC = 6, 7, 8            # ResNet-50: conv1 7x7 s2, MaxPool2d(3, 2, 1), avgpool + fc + sigmoid
+OP_DWCONV3, OP_PSA_ATTN = 9, 10                         # YOLO11: depthwise 3x3, C2PSA's spatial self-attention
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_SIGMOID, ACT_LEAKY = 0, 1, 2, 3, 4
 TASK_DETECT, TASK_POSE, TASK_TRACKNET, TASK_RESNET = 0, 1, 2, 3
 DTYPE_F32, DTYPE_F16, DTYPE_H2 = 0, 1, 2
@@ -346,6 +347,33 @@ class Graph:
         self.ops.append(dict(kind=OP_GAP_FC, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=src[0], out_choff=0, cout=w.shape[0],
                              ksize=0, stride=0, act=ACT_SIGMOID, res_buf=-1, res_choff=0, npad=0, w_off=w_off, b_off=b_off))
 
+    # ---- the two ops YOLO11 adds (csrc/yolo11_ops.hip)
+    def dwconv3(self, src, dst, w, b, act, res=None):
+        """Depthwise Conv 3x3 stride 1 pad 1 of ``src = (buf, choff, width)`` into ``dst = (buf, choff)`` at the same level.  ``w`` is
+        (c, 1, 3, 3) with BatchNorm folded and c <= width: the channels up to ``width`` get zero weights and a zero bias (they read
+        the zeros a padded producer wrote there and write act(0) = 0).  The blob gets the weights as [9][width] (tap ky * 3 + kx).
+        ``res = (buf, choff)``: a slice added after the activation."""
+        sb, so, sw = src
+        w = np.asarray(w, np.float32)
+        c = w.shape[0]
+        assert w.shape == (c, 1, 3, 3) and c <= sw and sw % 4 == 0 and act in (ACT_NONE, ACT_SILU), (w.shape, sw, act)
+        assert self.dtype != DTYPE_F16, "depthwise conv: fp32 and h2 graphs only"
+        wp = np.zeros((9, sw), np.float32)
+        wp[:, :c] = w.reshape(c, 9).T
+        bp = np.zeros(sw, np.float32)
+        bp[:c] = b
+        w_off, b_off = self._add(wp), self._add(bp)
+        self.ops.append(dict(kind=OP_DWCONV3, in_buf=sb, in_choff=so, cin=sw, out_buf=dst[0], out_choff=dst[1], cout=sw, ksize=3, stride=1,
+                             act=act, res_buf=-1 if res is None else res[0], res_choff=0 if res is None else res[1], npad=sw,
+                             w_off=w_off, b_off=b_off))
+
+    def psa_attn(self, src, dst, heads: int, kd: int = yolo_arch.PSA_KEY_DIM, hd: int = yolo_arch.PSA_HEAD_DIM):
+        """C2PSA's attention: ``src = (buf, choff)`` holds [q of all heads | k of all heads | v of all heads] (heads * (2 kd + hd)
+        channels), ``dst = (buf, choff)`` receives heads * hd channels: softmax over the keys of (q^T k) * kd^-1/2, applied to v."""
+        assert self.dtype != DTYPE_F16, "PSA attention: fp32 and h2 graphs only"
+        self.ops.append(dict(kind=OP_PSA_ATTN, in_buf=src[0], in_choff=src[1], cin=heads * (2 * kd + hd), out_buf=dst[0], out_choff=dst[1],
+                             cout=heads * hd, ksize=kd, stride=heads, act=ACT_NONE, res_buf=-1, res_choff=0, npad=hd, w_off=0, b_off=0))
+
     def blob(self) -> np.ndarray:
         return np.concatenate(self.chunks) if self.chunks else np.zeros(0, np.float32)
 
@@ -353,11 +381,11 @@ class Graph:
         """Real (unpadded would need the spec; this counts the op list as executed) 2*MAC per image."""
         total = 0.0
         for o in self.ops:
-            if o["kind"] not in (OP_CONV, OP_STEM, OP_STEM7):
+            if o["kind"] not in (OP_CONV, OP_STEM, OP_STEM7, OP_DWCONV3):
                 continue
             lvl = self.bufs[o["out_buf"]][0]
             hw = (net_h >> lvl) * (net_w >> lvl)
-            kk = 27 if o["kind"] == OP_STEM else 147 if o["kind"] == OP_STEM7 else o["cin"] * o["ksize"] ** 2
+            kk = 27 if o["kind"] == OP_STEM else 147 if o["kind"] == OP_STEM7 else 9 if o["kind"] == OP_DWCONV3 else o["cin"] * o["ksize"] ** 2
             total += 2.0 * hw * o["cout"] * kk
         return total
 
@@ -536,6 +564,194 @@ def build_yolov8(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
         heads.append(hd)
     g.head_buf = tuple(heads)
     return g
+
+
+def build_yolo11(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f32") -> Graph:
+    """YOLO11 detect / pose graph (yolo_arch.yolo11_state_spec: layer table of the ultralytics 8.3 line) over the engine's op set.
+
+    Everything dense is ``Graph.conv``, wired the way ``build_yolov8`` wires it: chunk / cat are channel slices of concat buffers
+    (C3k2, C3k, C2PSA, SPPF, the FPN / PAN joins), a Bottleneck's shortcut is its second conv's residual slice, the two residuals
+    of a PSABlock ride on the ``proj`` and ``ffn.1`` convs (act none), nn.Upsample is an op its consumer may absorb.  New: the
+    depthwise 3x3 convs (the head's class branch, the attention's positional encoding) and the attention itself.  The rows of a
+    ``qkv`` conv are permuted from per-head [q | k | v] to [q of all heads | k of all heads | v of all heads]: v becomes one
+    contiguous slice in the channel order ``pe`` and the output reshape use.  h2 graphs keep fp16-number weights unfolded
+    (PA_CONV_W_SINGLE) exactly as ``build_yolov8`` does; fp16 storage is not implemented for the two new ops."""
+    if dtype == "f16":
+        raise ValueError("YOLO11 graphs: fp16 storage (half=True) is not implemented for the depthwise conv and the PSA attention")
+    info = yolo_arch.infer_arch11_from_state_dict(sd)
+    d = yolo_arch.arch11_dims(info["scale"])
+    assert info["nc"] == nc, (info, nc)
+    c2h, c3h, c4h, nk = yolo_arch.head_dims(d, nc, kpt_shape)
+    assert nk == info["nk"], (nk, info)
+    g = Graph(task=TASK_POSE if kpt_shape else TASK_DETECT, nc=nc, nk=nk, kpt_dim=int(kpt_shape[1]) if kpt_shape else 0,
+              dtype={"f32": DTYPE_F32, "h2": DTYPE_H2}[dtype])
+    eps = yolo_arch.BN_EPS
+    split_bn = g.dtype == DTYPE_H2 and UNFOLDED_BN
+
+    def parts(prefix, perm=None):
+        """-> (weights to pack, bias, out_scale | None); ``perm``: output-channel order (rows of the weights and of BatchNorm)"""
+        view, p = sd, prefix
+        if perm is not None:
+            view = {"x.conv.weight": np.asarray(sd[f"{prefix}.conv.weight"])[perm]}
+            view.update({f"x.bn.{k}": np.asarray(sd[f"{prefix}.bn.{k}"])[perm] for k in ("weight", "bias", "running_mean", "running_var")})
+            p = "x"
+        if split_bn:
+            w, sc, b = fold_bn_split(view, p, eps)
+            if fp16_exact(w):
+                return w, b, sc
+        w, b = fold_bn(view, p, eps)
+        return w, b, None
+
+    def cb(prefix, src, dst, k, s, act=ACT_SILU, res=None, out_width=None, perm=None):
+        w, b, sc = parts(prefix, perm)
+        g.conv(src, dst, w, b, k, s, act, res, out_width, out_scale=sc)
+
+    def dw(prefix, src, dst, act, res=None):
+        w, b = fold_bn(sd, prefix, eps)
+        g.dwconv3(src, dst, w, b, act, res)
+
+    def c3k2(i, src, cout, c3k, e, level, dst):
+        n = d.n
+        c = int(cout * e)
+        assert c % 16 == 0, (i, c)
+        p = f"model.{i}"
+        cat = g.buf(level, (2 + n) * c)
+        cb(f"{p}.cv1", src, (cat, 0), 1, 1)
+        for j in range(n):
+            x, y = (cat, (1 + j) * c, c), (cat, (2 + j) * c)
+            h = int(c * 0.5)
+            if c3k:         # C3k(c, c, 2): cv3(cat(m(cv1(x)), cv2(x))), m = two 3x3 / 3x3 bottlenecks with their shortcut
+                assert h % 16 == 0, (i, h)
+                cat3, y0, y1, t = g.buf(level, 2 * h), g.buf(level, h), g.buf(level, h), g.buf(level, h)
+                cb(f"{p}.m.{j}.cv1", x, (y0, 0), 1, 1)
+                cb(f"{p}.m.{j}.cv2", x, (cat3, h), 1, 1)
+                cb(f"{p}.m.{j}.m.0.cv1", (y0, 0, h), (t, 0), 3, 1)
+                cb(f"{p}.m.{j}.m.0.cv2", (t, 0, h), (y1, 0), 3, 1, res=(y0, 0))
+                cb(f"{p}.m.{j}.m.1.cv1", (y1, 0, h), (t, 0), 3, 1)
+                cb(f"{p}.m.{j}.m.1.cv2", (t, 0, h), (cat3, 0), 3, 1, res=(y1, 0))
+                cb(f"{p}.m.{j}.cv3", (cat3, 0, 2 * h), y, 1, 1)
+            else:           # Bottleneck(c, c, e = 0.5): x + cv2(cv1(x)); the hidden width (8 at the n scale) is written at k-step width
+                ht = g.padk(h)
+                t = g.buf(level, ht)
+                cb(f"{p}.m.{j}.cv1", x, (t, 0), 3, 1, out_width=ht if ht != h else None)
+                cb(f"{p}.m.{j}.cv2", (t, 0, ht), y, 3, 1, res=(x[0], x[1]))
+        cb(f"{p}.cv2", (cat, 0, (2 + n) * c), dst, 1, 1)
+
+    def upsample(src, dst):
+        g.ops.append(dict(kind=OP_UPSAMPLE2X, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=dst[0],
+                          out_choff=dst[1], cout=src[2], ksize=0, stride=0, act=0, res_buf=-1, res_choff=0, npad=0,
+                          w_off=0, b_off=0))
+
+    blk = {i: (cout, c3k, e) for i, _, cout, c3k, e in yolo_arch.c3k2_layers(d)}
+    c1, c2, c3, c4, c5 = d.c1, d.c2, d.c3, d.c4, d.c5
+    fuse = lambda p: fold_bn(sd, p, eps)
+    # stem: straight from the u8 network input
+    c1p = g.padk(c1)
+    b0 = g.buf(1, c1p)
+    w0, bias0 = fuse("model.0")
+    w0p = np.zeros((c1p, 27), np.float32)
+    w0p[:c1] = np.ascontiguousarray(w0.transpose(0, 2, 3, 1)).reshape(c1, 27)          # [cout][ky][kx][c]
+    b0p = np.zeros(c1p, np.float32)
+    b0p[:c1] = bias0
+    w_off = g._add(w0p)
+    b_off = g._add(b0p)
+    g.ops.append(dict(kind=OP_STEM, in_buf=0, in_choff=0, cin=3, out_buf=b0, out_choff=0, cout=c1p, ksize=3, stride=2,
+                      act=ACT_SILU, res_buf=-1, res_choff=0, npad=c1p, w_off=w_off, b_off=b_off))
+    b1 = g.buf(2, c2)
+    cb("model.1", (b0, 0, c1p), (b1, 0), 3, 2)
+    b2 = g.buf(2, c3)
+    c3k2(2, (b1, 0, c2), *blk[2], 2, (b2, 0))
+    b3 = g.buf(3, c3)
+    cb("model.3", (b2, 0, c3), (b3, 0), 3, 2)
+    cat15 = g.buf(3, c4 + c4)      # [upsample(model.13) | model.4]
+    c3k2(4, (b3, 0, c3), *blk[4], 3, (cat15, c4))
+    b5 = g.buf(4, c4)
+    cb("model.5", (cat15, c4, c4), (b5, 0), 3, 2)
+    cat12 = g.buf(4, c5 + c4)      # [upsample(model.10) | model.6]
+    c3k2(6, (b5, 0, c4), *blk[6], 4, (cat12, c5))
+    b7 = g.buf(5, c5)
+    cb("model.7", (cat12, c5, c4), (b7, 0), 3, 2)
+    b8 = g.buf(5, c5)
+    c3k2(8, (b7, 0, c5), *blk[8], 5, (b8, 0))
+    ch = c5 // 2
+    cat9 = g.buf(5, 4 * ch)
+    cb("model.9.cv1", (b8, 0, c5), (cat9, 0), 1, 1)
+    g.ops.append(dict(kind=OP_SPPF_POOL, in_buf=cat9, in_choff=0, cin=ch, out_buf=cat9, out_choff=ch, cout=3 * ch,
+                      ksize=5, stride=1, act=0, res_buf=-1, res_choff=0, npad=0, w_off=0, b_off=0))
+    b9 = g.buf(5, c5)
+    cb("model.9.cv2", (cat9, 0, 4 * ch), (b9, 0), 1, 1)
+
+    # C2PSA: a, b = split(cv1(x)); b = PSABlock^n(b); cv2(cat(a, b))
+    cat21 = g.buf(5, c4 + c5)      # [model.20 | model.10]
+    c = c5 // 2
+    kd, hd = yolo_arch.PSA_KEY_DIM, yolo_arch.PSA_HEAD_DIM
+    heads = c // hd
+    assert heads >= 1 and heads * hd == c, (c, heads)
+    per = 2 * kd + hd
+    perm = np.concatenate([np.arange(h * per + lo, h * per + hi) for (lo, hi) in ((0, kd), (kd, 2 * kd), (2 * kd, per)) for h in range(heads)])
+    catp = g.buf(5, 2 * c)
+    cb("model.10.cv1", (b9, 0, c5), (catp, 0), 1, 1)
+    x = (catp, c)
+    for j in range(d.n):
+        p = f"model.10.m.{j}"
+        qkv, att, pe, x1, f = g.buf(5, heads * per), g.buf(5, c), g.buf(5, c), g.buf(5, c), g.buf(5, 2 * c)
+        cb(f"{p}.attn.qkv", (x[0], x[1], c), (qkv, 0), 1, 1, act=ACT_NONE, perm=perm)
+        g.psa_attn((qkv, 0), (att, 0), heads, kd, hd)
+        dw(f"{p}.attn.pe", (qkv, 2 * heads * kd, c), (pe, 0), ACT_NONE, res=(att, 0))          # attention output + pe(v)
+        cb(f"{p}.attn.proj", (pe, 0, c), (x1, 0), 1, 1, act=ACT_NONE, res=x)                   # x + attn(x)
+        cb(f"{p}.ffn.0", (x1, 0, c), (f, 0), 1, 1)
+        y = (catp, c) if j == d.n - 1 else (g.buf(5, c), 0)
+        cb(f"{p}.ffn.1", (f, 0, 2 * c), y, 1, 1, act=ACT_NONE, res=(x1, 0))                    # x + ffn(x)
+        x = y
+    cb("model.10.cv2", (catp, 0, 2 * c), (cat21, c4), 1, 1)
+
+    upsample((cat21, c4, c5), (cat12, 0))
+    cat18 = g.buf(4, c3 + c4)      # [model.17 | model.13]
+    c3k2(13, (cat12, 0, c5 + c4), *blk[13], 4, (cat18, c3))
+    upsample((cat18, c3, c4), (cat15, 0))
+    b16 = g.buf(3, c3)
+    c3k2(16, (cat15, 0, c4 + c4), *blk[16], 3, (b16, 0))
+    cb("model.17", (b16, 0, c3), (cat18, 0), 3, 2)
+    b19 = g.buf(4, c4)
+    c3k2(19, (cat18, 0, c3 + c4), *blk[19], 4, (b19, 0))
+    cb("model.20", (b19, 0, c4), (cat21, 0), 3, 2)
+    b22 = g.buf(5, c5)
+    c3k2(22, (cat21, 0, c4 + c5), *blk[22], 5, (b22, 0))
+
+    # Detect / Pose head at model.23: box and keypoint branches as in YOLOv8 (3x3, 3x3, 1x1), the class branch
+    # [DWConv 3x3 -> Conv 1x1] x 2 -> Conv2d 1x1.  Every branch runs its own convs (nothing merged: not tuned)
+    head_cs = (64 + nc + nk + 3) // 4 * 4
+    heads_out = []
+    for l, (feat, chn, lvl) in enumerate(((b16, c3, 3), (b19, c4, 4), (b22, c5, 5))):
+        hdb = g.buf(lvl, head_cs)
+        for br, wd, hoff in [("cv2", c2h, 0)] + ([("cv4", c4h, 64 + nc)] if kpt_shape else []):
+            pw = g.padk(wd)
+            h0, h1 = g.buf(lvl, pw), g.buf(lvl, pw)
+            cb(f"model.23.{br}.{l}.0", (feat, 0, chn), (h0, 0), 3, 1, out_width=pw)
+            cb(f"model.23.{br}.{l}.1", (h0, 0, pw), (h1, 0), 3, 1, out_width=pw)
+            g.conv((h1, 0, pw), (hdb, hoff), np.asarray(sd[f"model.23.{br}.{l}.2.weight"], np.float32),
+                   np.asarray(sd[f"model.23.{br}.{l}.2.bias"], np.float32), 1, 1, ACT_NONE)
+        pw = g.padk(c3h)
+        d0, p0, d1, p1 = g.buf(lvl, chn), g.buf(lvl, pw), g.buf(lvl, pw), g.buf(lvl, pw)
+        dw(f"model.23.cv3.{l}.0.0", (feat, 0, chn), (d0, 0), ACT_SILU)
+        cb(f"model.23.cv3.{l}.0.1", (d0, 0, chn), (p0, 0), 1, 1, out_width=pw)
+        dw(f"model.23.cv3.{l}.1.0", (p0, 0, pw), (d1, 0), ACT_SILU)
+        cb(f"model.23.cv3.{l}.1.1", (d1, 0, pw), (p1, 0), 1, 1, out_width=pw)
+        g.conv((p1, 0, pw), (hdb, 64), np.asarray(sd[f"model.23.cv3.{l}.2.weight"], np.float32),
+               np.asarray(sd[f"model.23.cv3.{l}.2.bias"], np.float32), 1, 1, ACT_NONE)
+        heads_out.append(hdb)
+    g.head_buf = tuple(heads_out)
+    return g
+
+
+def build_yolo(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f32", family: Optional[str] = None) -> Graph:
+    """``build_yolov8`` or ``build_yolo11`` by the checkpoint's family (``yolo_arch.infer_family`` when not given)."""
+    family = family or yolo_arch.infer_family(sd)
+    if family == "yolo11":
+        return build_yolo11(sd, nc, kpt_shape, dtype)
+    if family != "yolov8":
+        raise ValueError(f"unknown YOLO family {family!r}")
+    return build_yolov8(sd, nc, kpt_shape, dtype)
 
 
 TRACKNET_BN_EPS = 1e-5      # nn.BatchNorm2d default (reference models.py:9)

@@ -76,13 +76,15 @@ class YOLO:
         object then keeps using."""
         self.ckpt = checkpoint.load_checkpoint(model_path)
         if self.ckpt.task not in ("detect", "pose"):
-            raise ValueError(f"{model_path}: not a YOLOv8 detect/pose checkpoint (task {self.ckpt.task})")
+            raise ValueError(f"{model_path}: not a YOLOv8 / YOLO11 detect/pose checkpoint (task {self.ckpt.task})")
         self.task = self.ckpt.task
         self.names = self.ckpt.names or {i: str(i) for i in range(self.ckpt.nc)}
         self.kpt_shape = self.ckpt.kpt_shape
         self.half = bool(half)
         self.fp32_mode = fp32_mode or E.fp32_mode()
-        self.graph = G.build_yolov8(self.ckpt.state_dict, self.ckpt.nc, self.kpt_shape, dtype=self._graph_dtype())
+        #: "yolov8" | "yolo11": which builder turns the state_dict into the engine's op list
+        self.family = self.ckpt.family
+        self.graph = self._build()
         self._engine = engine
         self._model: Optional[E.Model] = None
         self.max_batch = 64
@@ -93,15 +95,25 @@ class YOLO:
     def _graph_dtype(self) -> str:
         return "f16" if self.half else ("h2" if self.fp32_mode == "h2" else "f32")
 
+    def _build(self) -> G.Graph:
+        if self.half and self.family == "yolo11":
+            raise ValueError("half=True is not available for YOLO11 checkpoints: fp16 storage is not implemented for the depthwise "
+                             "conv and the PSA attention (use the default fp32-equivalent path)")
+        return G.build_yolo(self.ckpt.state_dict, self.ckpt.nc, self.kpt_shape, dtype=self._graph_dtype(), family=self.family)
+
     def _rebuild(self) -> None:
         self.close()
-        self.graph = G.build_yolov8(self.ckpt.state_dict, self.ckpt.nc, self.kpt_shape, dtype=self._graph_dtype())
+        self.graph = self._build()
 
     def set_half(self, half: bool) -> None:
         """Switch precision (rebuilds the packed graph; the HBM-resident model is re-created on next use)."""
         if bool(half) != self.half:
-            self.half = bool(half)
-            self._rebuild()
+            old, self.half = self.half, bool(half)
+            try:
+                self._rebuild()
+            except ValueError:
+                self.half = old
+                raise
 
     def set_fp32_mode(self, mode: str) -> None:
         if mode not in ("h2", "bx3"):
