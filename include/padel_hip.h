@@ -12,8 +12,8 @@
  *                                                                              -> pa_tracknet_infer()
  *
  * Conventions: plain pointers and sizes only; the caller owns every buffer and the
- * library never keeps a caller pointer past return; every call is synchronous at this boundary (the one
- * exception to both: the pa_yolo_submit / pa_yolo_wait pair below); one
+ * library never keeps a caller pointer past return; every call is synchronous at this boundary (the
+ * exceptions: the pa_yolo_submit / pa_yolo_wait pair and the stream-ordered pa_yuv420_to_bgr below); one
  * engine per GPU, not thread-safe; return 0 on success, non-zero on failure with the message in
  * pa_last_error().  The Python binding (`padel_analytics_amd/engine.py`, ctypes) is the only caller.
  */
@@ -148,6 +148,49 @@ int pa_upload(pa_engine* eng, void* dst_dev, const void* src_host, size_t nbytes
  * The caller keeps ownership and unregisters before freeing.                                                  */
 int pa_host_register(pa_engine* eng, void* ptr, size_t nbytes);
 int pa_host_unregister(pa_engine* eng, void* ptr);
+
+/* ---- frames from a decoder: 8-bit YUV 4:2:0 (NV12 / I420) -> the packed BGR bytes every other call consumes ----
+ * Nearest-neighbour chroma (each 2 x 2 block of pixels shares one U, V), 20-bit fixed point, all int32:
+ *     y = max(0, Y - y_off) * cy + (1 << 19)      u = U - 128      v = V - 128
+ *     R = clamp((y + cvr * v) >> 20, 0, 255)    G = clamp((y + cug * u + cvg * v) >> 20, 0, 255)    B = clamp((y + cub * u) >> 20, 0, 255)
+ * (>> arithmetic).  The named coefficient tables live in padel_analytics_amd/video.py (YUV_COEFFS).
+ * Offsets and pitches are bytes; offsets count from the start of a frame, frame i starts at src + i * frame_stride.  The source
+ * needs NO alignment (odd pitches, padded plane heights, frames that start anywhere): the launcher takes dword loads / stores
+ * when this call's pointers, pitches, offsets and stride allow it and w % 4 == 0, bytes otherwise.                       */
+enum pa_yuv_layout {
+    PA_YUV_NV12 = 0,      /* Y plane, then rows of interleaved U, V at off_u (off_v must be off_u + 1); pitch_c >= w */
+    PA_YUV_I420 = 1       /* Y plane, U plane at off_u, V plane at off_v; pitch_c >= w / 2                           */
+};
+typedef struct pa_yuv_desc {
+    int32_t layout;               /* enum pa_yuv_layout                      */
+    int32_t pitch_y, pitch_c;
+    int32_t off_u, off_v;
+    int32_t reserved;             /* 0                                        */
+    int64_t frame_stride;
+    int32_t y_off, cy, cvr, cug, cvg, cub;
+} pa_yuv_desc;
+/* n frames of h x w (both even, >= 2) -> dst_bgr_dev (HBM): n packed frames at dst + i * h * w * 3.  src: HBM (src_on_device = 1)
+ * or host memory.  Refused with an error, nothing launched: odd or too small w / h, n < 1, a pitch smaller than its row, planes
+ * that reach into the next frame (frame_stride too small), coefficients that could leave int32.
+ * ASYNCHRONOUS on the engine's compute stream — the second exception to "every call is synchronous".  A host src is first copied
+ * to an engine-owned staging buffer ON THAT SAME STREAM (grown on demand, freed with the engine), then converted; the caller keeps
+ * a page-locked src untouched until the stream has passed the copy (a pageable one is consumed before the call returns).
+ * INVARIANT: everything that later reads or overwrites dst, src in HBM, or the staging buffer is ordered behind this call by that
+ * one stream, as in pa_yolo_infer's own host path: a following pa_yolo_infer / pa_yolo_submit / pa_resnet_infer / pa_ball_feed on
+ * dst sees the converted frames, and the next conversion into the same dst waits for the readers queued before it.  That is what
+ * makes ONE staging buffer safe under the trackers' submit / collect pipelining.  Work on another stream (pa_upload's copy
+ * stream, another engine) is NOT ordered: pa_engine_synchronize first.                                                    */
+int pa_yuv420_to_bgr(pa_engine* eng, const uint8_t* src, int src_on_device, int n, int h, int w,
+                     const pa_yuv_desc* d, uint8_t* dst_bgr_dev);
+/* tests / tools: which instantiation the last successful pa_yuv420_to_bgr of this engine launched — 1 vector path, 2 byte path,
+ * 0 none yet                                                                                                          */
+int pa_yuv_last_path(pa_engine* eng);
+
+/* tools: device time of whatever is queued on the engine's compute stream between the two calls, from a pair of HIP events
+ * recorded on that stream (tools/yuv_bench.py times the asynchronous pa_yuv420_to_bgr with it).  pa_engine_timer_stop waits for
+ * its event and returns the milliseconds between the two.                                                              */
+int pa_engine_timer_start(pa_engine* eng);
+int pa_engine_timer_stop(pa_engine* eng, float* ms);
 
 /* tuning knobs (tests / tools only).  Defaults come from the environment ONCE at pa_engine_create
  * (PADEL_CONV_IMPL=tap|lds, PADEL_CONV_VARIANT, PADEL_CONV_TUNE, PADEL_CONV_TAP_PD, PADEL_GRAPH, PADEL_ALIAS).

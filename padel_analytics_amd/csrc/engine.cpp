@@ -53,6 +53,9 @@ struct pa_engine {
     int tuning_epoch = 0;     // bumped by pa_engine_set_tuning: captured graphs of an older epoch are discarded
     std::string timeline_path;
     pa_comm* comm = nullptr;  // RCCL communicator (pa_engine_comm_init), optional
+    uint8_t* yuv_stage = nullptr; size_t yuv_stage_cap = 0;   // pa_yuv420_to_bgr: raw YUV bytes of a host source, filled and read on `stream` only
+    int yuv_last_path = 0;    // 1 vector, 2 byte: what the last pa_yuv420_to_bgr launched (pa_yuv_last_path)
+    hipEvent_t timer_ev[2]{};  // pa_engine_timer_start / _stop, created on first use
 };
 
 static int env_int(const char* k, int dflt) { const char* v = getenv(k); return v ? atoi(v) : dflt; }
@@ -213,6 +216,8 @@ void pa_engine_destroy(pa_engine* e) {
     hipSetDevice(e->dev);
     pa_engine_comm_destroy(e);
     if (e->zeros) hipFree(e->zeros);
+    if (e->yuv_stage) { if (e->stream) hipStreamSynchronize(e->stream); hipFree(e->yuv_stage); }
+    for (hipEvent_t ev : e->timer_ev) if (ev) hipEventDestroy(ev);
     if (e->stream) hipStreamDestroy(e->stream);
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);
     delete e;
@@ -262,6 +267,82 @@ int pa_memcpy_d2h(pa_engine* e, void* dst, const void* src, size_t n) {
     PA_HIP(e, hipSetDevice(e->dev));
     PA_HIP(e, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, e->stream));
     PA_HIP(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// ------------------------------------------------------------------------------- YUV 4:2:0 -> BGR
+// Geometry checks of pa_yuv420_to_bgr (host only: no HIP call).  *span = bytes of src the kernel may read: the last frame's
+// start plus the extent of one frame's planes.
+static int yuv_validate(pa_engine* e, int n, int h, int w, const pa_yuv_desc* d, size_t* span) {
+    if (!d) PA_FAIL(e, "pa_yuv420_to_bgr: descriptor is NULL");
+    if (w < 2 || h < 2 || (w & 1) || (h & 1)) PA_FAIL(e, "pa_yuv420_to_bgr: %d x %d frames: 4:2:0 needs an even width and height of at least 2", w, h);
+    if (n < 1 || n > 65535) PA_FAIL(e, "pa_yuv420_to_bgr: n = %d frames outside [1, 65535]", n);
+    if (d->layout != PA_YUV_NV12 && d->layout != PA_YUV_I420) PA_FAIL(e, "pa_yuv420_to_bgr: unknown layout %d", d->layout);
+    const bool nv12 = d->layout == PA_YUV_NV12;
+    const int crow = nv12 ? w : w / 2;                    // bytes of one chroma row
+    if (d->pitch_y < w) PA_FAIL(e, "pa_yuv420_to_bgr: pitch_y %d is smaller than a luma row of %d bytes", d->pitch_y, w);
+    if (d->pitch_c < crow) PA_FAIL(e, "pa_yuv420_to_bgr: pitch_c %d is smaller than a chroma row of %d bytes", d->pitch_c, crow);
+    if (d->off_u < 0 || d->off_v < 0) PA_FAIL(e, "pa_yuv420_to_bgr: negative plane offset (off_u %d, off_v %d)", d->off_u, d->off_v);
+    if (nv12 && d->off_v != d->off_u + 1) PA_FAIL(e, "pa_yuv420_to_bgr: NV12 needs off_v == off_u + 1 (off_u %d, off_v %d)", d->off_u, d->off_v);
+    const long long y_end = (long long)(h - 1) * d->pitch_y + w;
+    const long long c_len = (long long)(h / 2 - 1) * d->pitch_c + crow;
+    const long long extent = std::max(y_end, std::max(d->off_u + c_len, nv12 ? 0ll : d->off_v + c_len));
+    if (extent > 0x7fffffffll) PA_FAIL(e, "pa_yuv420_to_bgr: a frame of %lld bytes is beyond 2 GiB", extent);
+    if (d->frame_stride < extent)
+        PA_FAIL(e, "pa_yuv420_to_bgr: frame_stride %lld is smaller than the %lld bytes the planes of one frame span (they would overlap the next frame)",
+                (long long)d->frame_stride, extent);
+    // the formula stays inside int32 for every byte value (the named tables reach 5.94e8)
+    const auto mag = [](int32_t c) { return (long long)(c < 0 ? -(long long)c : c); };
+    const long long worst = 255 * mag(d->cy) + (1 << 19) + 128 * std::max(mag(d->cvr), std::max(mag(d->cug) + mag(d->cvg), mag(d->cub)));
+    if (d->y_off < 0 || d->y_off > 255 || worst > 0x7fffffffll) PA_FAIL(e, "pa_yuv420_to_bgr: coefficients leave int32 (worst case %lld) or y_off %d outside [0, 255]", worst, d->y_off);
+    *span = (size_t)(n - 1) * (size_t)d->frame_stride + (size_t)extent;
+    return 0;
+}
+
+int pa_yuv420_to_bgr(pa_engine* e, const uint8_t* src, int src_on_device, int n, int h, int w, const pa_yuv_desc* d, uint8_t* dst) {
+    if (!e) return 1;
+    if (!src || !dst) PA_FAIL(e, "pa_yuv420_to_bgr: src or dst is NULL");
+    size_t span = 0;
+    if (yuv_validate(e, n, h, w, d, &span)) return 1;
+    PA_HIP(e, hipSetDevice(e->dev));
+    if (!src_on_device) {
+        if (e->yuv_stage_cap < span) {
+            PA_HIP(e, hipStreamSynchronize(e->stream));          // a conversion still queued reads the buffer about to go
+            if (e->yuv_stage) hipFree(e->yuv_stage);
+            e->yuv_stage = nullptr; e->yuv_stage_cap = 0;
+            PA_HIP(e, hipMalloc((void**)&e->yuv_stage, span));
+            e->yuv_stage_cap = span;
+        }
+        PA_HIP(e, hipMemcpyAsync(e->yuv_stage, src, span, hipMemcpyHostToDevice, e->stream));
+        src = e->yuv_stage;
+    }
+    YuvArgs a{};
+    a.src = src; a.dst = dst; a.n = n; a.h = h; a.w = w; a.nv12 = d->layout == PA_YUV_NV12;
+    a.pitch_y = d->pitch_y; a.pitch_c = d->pitch_c; a.off_u = d->off_u; a.off_v = d->off_v; a.frame_stride = d->frame_stride;
+    a.y_off = d->y_off; a.cy = d->cy; a.cvr = d->cvr; a.cug = d->cug; a.cvg = d->cvg; a.cub = d->cub;
+    int vec = 0;
+    const hipError_t r = launch_yuv420_to_bgr(a, e->stream, &vec);
+    if (r != hipSuccess) PA_FAIL(e, "yuv420_to_bgr launch failed: %s", hipGetErrorString(r));
+    e->yuv_last_path = vec ? 1 : 2;
+    return 0;
+}
+
+int pa_yuv_last_path(pa_engine* e) { return e ? e->yuv_last_path : 0; }
+
+int pa_engine_timer_start(pa_engine* e) {
+    if (!e) return 1;
+    PA_HIP(e, hipSetDevice(e->dev));
+    for (hipEvent_t& ev : e->timer_ev) if (!ev) PA_HIP(e, hipEventCreate(&ev));
+    PA_HIP(e, hipEventRecord(e->timer_ev[0], e->stream));
+    return 0;
+}
+int pa_engine_timer_stop(pa_engine* e, float* ms) {
+    if (!e || !ms) return 1;
+    if (!e->timer_ev[0] || !e->timer_ev[1]) PA_FAIL(e, "pa_engine_timer_stop without pa_engine_timer_start");
+    PA_HIP(e, hipSetDevice(e->dev));
+    PA_HIP(e, hipEventRecord(e->timer_ev[1], e->stream));
+    PA_HIP(e, hipEventSynchronize(e->timer_ev[1]));
+    PA_HIP(e, hipEventElapsedTime(ms, e->timer_ev[0], e->timer_ev[1]));
     return 0;
 }
 

@@ -221,6 +221,21 @@ struct LetterboxArgs {
 };
 hipError_t launch_letterbox(const LetterboxArgs& a, hipStream_t s);
 
+// YUV 4:2:0 -> packed BGR (yuv_convert.hip): n frames at src + i * frame_stride -> n packed frames at dst + i * h * w * 3.
+// The caller (pa_yuv420_to_bgr) has checked the geometry; the launcher only picks the vector or the byte instantiation.
+struct YuvArgs {
+    const uint8_t* src;   // HBM, no alignment guarantee
+    uint8_t* dst;
+    int n, h, w;          // h, w even
+    int nv12;             // 1: interleaved UV rows at off_u (off_v = off_u + 1), 0: I420 planes at off_u / off_v
+    int pitch_y, pitch_c; // bytes per luma / chroma row
+    int off_u, off_v;     // bytes from the start of a frame
+    long long frame_stride;
+    int y_off, cy, cvr, cug, cvg, cub;
+};
+bool yuv_vector_path_ok(const YuvArgs& a);              // every address of this launch allows dword / 16-bit accesses
+hipError_t launch_yuv420_to_bgr(const YuvArgs& a, hipStream_t s, int* vec_out = nullptr);      // *vec_out: 1 vector path, 0 byte path
+
 // Pillow-style separable resample pass over u8 images (coefficients precomputed on host):
 // out[b][y][x][c] = clip8((sum_k coef[o][k] * in[...lo[o]+k...] + (1<<21)) >> 22)
 struct ResamplePassArgs {

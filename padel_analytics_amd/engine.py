@@ -69,7 +69,17 @@ class pa_yolo_params(C.Structure):
                 ("frames_on_device", C.c_int32)]
 
 
+class pa_yuv_desc(C.Structure):
+    _fields_ = [("layout", C.c_int32), ("pitch_y", C.c_int32), ("pitch_c", C.c_int32), ("off_u", C.c_int32),
+                ("off_v", C.c_int32), ("reserved", C.c_int32), ("frame_stride", C.c_int64),
+                ("y_off", C.c_int32), ("cy", C.c_int32), ("cvr", C.c_int32), ("cug", C.c_int32), ("cvg", C.c_int32),
+                ("cub", C.c_int32)]
+
+
 PRE_LETTERBOX, PRE_PIL_STRETCH = 0, 1
+YUV_NV12, YUV_I420 = 0, 1
+#: ``Engine.yuv_last_path()``: which instantiation of the conversion kernel the launcher chose
+YUV_PATH_VECTOR, YUV_PATH_BYTE = 1, 2
 
 # every symbol include/padel_hip.h declares (tests check the .so exports all of them)
 ABI_SYMBOLS = [
@@ -87,6 +97,7 @@ ABI_SYMBOLS = [
     "pa_model_take_overflow", "pa_yolo_postprocess", "pa_host_register", "pa_host_unregister",
     "pa_engine_bcast_weights_from", "pa_model_fill_arena", "pa_yolo_submit", "pa_yolo_wait",
     "pa_resnet_infer", "pa_resnet_read_netin", "pa_resnet_read_fc", "pa_resnet_read_head", "pa_pil_coeffs",
+    "pa_yuv420_to_bgr", "pa_yuv_last_path", "pa_engine_timer_start", "pa_engine_timer_stop",
 ]
 
 
@@ -170,6 +181,10 @@ def load_library():
     lib.pa_host_unregister.argtypes = [vp, vp]
     lib.pa_model_take_overflow.argtypes = [vp, C.POINTER(i32)]
     lib.pa_yolo_postprocess.argtypes = [vp, C.POINTER(vp), i32, i32, i32, C.POINTER(pa_yolo_params), vp, vp, vp]
+    lib.pa_yuv420_to_bgr.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(pa_yuv_desc), vp]
+    lib.pa_yuv_last_path.argtypes = [vp]
+    lib.pa_engine_timer_start.argtypes = [vp]
+    lib.pa_engine_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
     if lib.pa_abi_version() != 5:
         raise EngineUnavailable("libpadel_hip.so ABI version mismatch")
     _lib = lib
@@ -196,6 +211,21 @@ def pil_coeffs(in_size: int, out_size: int, filter: int = PIL_BICUBIC):
 def graph_dtype(mode: Optional[str] = None) -> str:
     """graph.build_yolov8 / build_tracknet ``dtype`` of the fp32-equivalent path in arithmetic ``mode`` (default: fp32_mode())."""
     return {"h2": "h2", "bx3": "f32"}[mode or fp32_mode()]
+
+
+def yuv_span_bytes(n: int, h: int, w: int, d: "pa_yuv_desc") -> Optional[int]:
+    """Bytes of the source that ``n`` frames described by ``d`` reach (the last frame's start plus the extent of one frame's
+    planes); None where the geometry is one the library refuses anyway."""
+    if n < 1 or h < 2 or w < 2 or h % 2 or w % 2 or d.layout not in (YUV_NV12, YUV_I420):
+        return None
+    crow = w if d.layout == YUV_NV12 else w // 2
+    if d.pitch_y < w or d.pitch_c < crow or d.off_u < 0 or d.off_v < 0:
+        return None
+    c_len = (h // 2 - 1) * d.pitch_c + crow
+    extent = max((h - 1) * d.pitch_y + w, d.off_u + c_len, 0 if d.layout == YUV_NV12 else d.off_v + c_len)
+    if d.frame_stride < extent:
+        return None
+    return (n - 1) * d.frame_stride + extent
 
 
 class DeviceBuffer:
@@ -269,6 +299,40 @@ class Engine:
 
     def unpin(self, arr: np.ndarray) -> None:
         self._check(self.lib.pa_host_unregister(self.handle, arr.ctypes.data))
+
+    def yuv420_to_bgr(self, src, n: int, h: int, w: int, desc, dst: DeviceBuffer) -> None:
+        """``n`` frames of 8-bit YUV 4:2:0 -> packed BGR in ``dst`` (``pa_yuv420_to_bgr``).  ``src``: a 1-D uint8 ndarray of
+        raw bytes (copied to the engine's staging buffer on the compute stream first) or a ``DeviceBuffer``; ``desc``: a
+        ``pa_yuv_desc`` or a dict of its fields (``video.yuv_desc`` builds one).  Asynchronous: ordered with every later call
+        of this engine by its one compute stream.  Geometry the kernel cannot run is an ``EngineError``, nothing is launched."""
+        if not isinstance(desc, pa_yuv_desc):
+            desc = pa_yuv_desc(**{k: int(v) for k, v in desc.items()})
+        on_dev = isinstance(src, DeviceBuffer)
+        if on_dev:
+            ptr, have = src.ptr, src.nbytes
+        else:
+            if not (isinstance(src, np.ndarray) and src.dtype == np.uint8 and src.ndim == 1 and src.flags.c_contiguous):
+                raise TypeError("yuv420_to_bgr: src must be a contiguous 1-D uint8 array of raw bytes or a DeviceBuffer")
+            ptr, have = src.ctypes.data, src.nbytes
+        need = yuv_span_bytes(n, h, w, desc)
+        if need is not None and have < need:          # (geometry that has no span is refused by the library, with its reason)
+            raise EngineError(f"yuv420_to_bgr: {n} frames as described span {need} bytes, src holds {have}")
+        if n >= 1 and h >= 1 and w >= 1 and dst.nbytes < n * h * w * 3:
+            raise EngineError(f"yuv420_to_bgr: dst holds {dst.nbytes} bytes, {n} BGR frames need {n * h * w * 3}")
+        self._check(self.lib.pa_yuv420_to_bgr(self.handle, ptr, int(on_dev), int(n), int(h), int(w), C.byref(desc), dst.ptr))
+
+    def yuv_last_path(self) -> int:
+        """YUV_PATH_VECTOR / YUV_PATH_BYTE: what the last successful ``yuv420_to_bgr`` launched (0: none yet)."""
+        return int(self.lib.pa_yuv_last_path(self.handle))
+
+    def timer_start(self) -> None:
+        """Tools: mark the compute stream with a HIP event; ``timer_stop`` -> milliseconds of device time queued since."""
+        self._check(self.lib.pa_engine_timer_start(self.handle))
+
+    def timer_stop(self) -> float:
+        ms = C.c_float(0.0)
+        self._check(self.lib.pa_engine_timer_stop(self.handle, C.byref(ms)))
+        return float(ms.value)
 
     def set_tuning(self, **kv):
         """Tests / tools only: impl (2 bx3, 0 tap; 1 — the retired LDS kernel — is refused), variant (tile id, -1 auto), tune, tap_pd, graph, alias, fold_up, timeline."""

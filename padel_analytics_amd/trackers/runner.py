@@ -275,17 +275,22 @@ class TrackingRunner:
         from concurrent.futures import ThreadPoolExecutor
 
         def batches():
-            """Batches of frames resident in HBM: device clips pass through; host frames are uploaded once per
+            """Batches of frames resident in HBM: device clips and YUV clips pass through; host frames are uploaded once per
             batch into one of two staging clips, the next upload overlapping this batch's compute."""
             gen = self._frames()
             first = next(gen, None)
             if first is None:
                 return
-            if isinstance(first, video.DeviceFrame):
+            if isinstance(first, (video.DeviceFrame, video.YuvFrame)):
                 def chain():
                     yield first
                     yield from gen
-                yield from _sampler(chain(), bs)
+                for sample in _sampler(chain(), bs):
+                    # YUV clips: one conversion per batch into the clip's own BGR staging (no host_batch, no second staging
+                    # clip) — every tracker's device_batch over this batch or a part of it then finds the frames converted
+                    if isinstance(first, video.YuvFrame):
+                        video.device_batch(sample)
+                    yield sample
                 return
             from .. import engine as E
             eng = self.engine or E.default_engine()

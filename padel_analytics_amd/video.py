@@ -5,10 +5,16 @@ same two calls over (a) ``.npy`` frame stacks (N,H,W,3 uint8 BGR, memory-mapped)
 scheme somebody registered with ``register_source`` (the tests and the bench register ``synthetic://?n=64&h=720&w=1280&
 fps=30&seed=0``: tests/synth.py — generated frames are test infrastructure, not product) and (c) real video files when
 ``cv2`` happens to be importable, (d) ``DeviceClip`` objects: a clip already resident in HBM (the bench's device-resident mode; the
-runner's fan-out mode uploads each batch once and hands the same ``DeviceFrame`` handles to every tracker).
+runner's fan-out mode uploads each batch once and hands the same ``DeviceFrame`` handles to every tracker), (e) 8-bit YUV 4:2:0 —
+what decoders, capture cards and ``ffmpeg -f rawvideo`` actually emit, 1.5 bytes per pixel: ``YuvClip`` (NV12 / I420 bytes in host
+memory, any pitch / padded plane height / gap between frames), ``DeviceYuvClip`` (the same bytes resident in HBM: a hardware
+decoder's surfaces) and ``.y4m`` files by path (``YuvClip.from_y4m``: the one self-describing raw format, no codec).  Their
+frames are ``YuvFrame`` handles; ``device_batch`` converts a batch to BGR on the GPU (csrc/yuv_convert.hip), ``host_batch`` /
+``np.asarray(frame)`` on the host with the same integer formula (``yuv420_to_bgr_host``).
 Frames are HWC uint8 **BGR**, exactly what supervision yields."""
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 from typing import Iterator, Optional
 
@@ -47,12 +53,15 @@ class VideoInfo:
 
     @classmethod
     def from_video_path(cls, video_path) -> "VideoInfo":
-        if isinstance(video_path, (DeviceClip, ArrayClip)):
+        if isinstance(video_path, (DeviceClip, ArrayClip, _YuvSource)):
             return cls(video_path.w, video_path.h, video_path.fps, video_path.total_frames)
         p = str(video_path)
         src = _scheme(p)
         if src is not None:
             return src[0](p)
+        if p.endswith(".y4m"):
+            c = _open_y4m(p)
+            return cls(c.w, c.h, c.fps, c.total_frames)
         if p.endswith(".npy"):
             a = np.load(p, mmap_mode="r")
             return cls(int(a.shape[2]), int(a.shape[1]), 30, int(a.shape[0]))
@@ -179,11 +188,399 @@ class ArrayClip:
             yield self.array[i % self.n]
 
 
+# ---------------------------------------------------------------------------------------------- YUV 4:2:0 sources
+# name -> (y_off, CY, CVR, CUG, CVG, CUB): 20-bit fixed point, trunc(c * 2^20) of the 3-decimal coefficients (limited range) or of
+# the standard's own (full range).  The formula (include/padel_hip.h, pa_yuv_desc) is the specification; bt601_limited uses the
+# constants of OpenCV's COLOR_YUV2BGR_NV12 / _I420 as recalled — parity with cv2 is unpinned.
+YUV_COEFFS = {
+    "bt601_limited": (16, 1220542, 1673527, -409993, -852492, 2116026),
+    "bt709_limited": (16, 1220542, 1880096, -223346, -558891, 2214592),
+    "bt601_full": (0, 1048576, 1470103, -360852, -748825, 1858076),
+    "bt709_full": (0, 1048576, 1651297, -196423, -490863, 1945737),
+}
+YUV_LAYOUTS = {"nv12": 0, "i420": 1}          # enum pa_yuv_layout
+_DESC_FIELDS = ("layout", "pitch_y", "pitch_c", "off_u", "off_v", "frame_stride", "y_off", "cy", "cvr", "cug", "cvg", "cub")
+
+
+def yuv_desc(w: int, h: int, layout: str = "nv12", matrix: str = "bt601", range: str = "limited", pitch: Optional[int] = None,
+             pitch_c: Optional[int] = None, off_u: Optional[int] = None, off_v: Optional[int] = None,
+             frame_stride: Optional[int] = None, coeffs: Optional[tuple] = None) -> dict:
+    """The fields of ``pa_yuv_desc`` for ``h`` x ``w`` frames.  The defaults describe tightly packed frames: rows as long as
+    their pixels, chroma straight behind the last luma row, the next frame straight behind the last chroma row.  ``coeffs``:
+    six integers in place of the named table ``YUV_COEFFS[f"{matrix}_{range}"]``."""
+    if layout not in YUV_LAYOUTS:
+        raise ValueError(f"YUV layout {layout!r}: expected 'nv12' or 'i420'")
+    if coeffs is None:
+        name = f"{matrix}_{range}"
+        if name not in YUV_COEFFS:
+            raise ValueError(f"no YUV coefficient table {name!r} (video.YUV_COEFFS: {', '.join(YUV_COEFFS)})")
+        coeffs = YUV_COEFFS[name]
+    w, h = int(w), int(h)
+    nv12 = layout == "nv12"
+    pitch = w if pitch is None else int(pitch)
+    pitch_c = (w if nv12 else w // 2) if pitch_c is None else int(pitch_c)
+    off_u = h * pitch if off_u is None else int(off_u)
+    off_v = (off_u + 1 if nv12 else off_u + (h // 2) * pitch_c) if off_v is None else int(off_v)
+    if frame_stride is None:
+        frame_stride = (off_u if nv12 else max(off_u, off_v)) + (h // 2) * pitch_c
+    y_off, cy, cvr, cug, cvg, cub = (int(c) for c in coeffs)
+    return dict(layout=YUV_LAYOUTS[layout], pitch_y=pitch, pitch_c=pitch_c, off_u=off_u, off_v=off_v, frame_stride=int(frame_stride),
+                y_off=y_off, cy=cy, cvr=cvr, cug=cug, cvg=cvg, cub=cub)
+
+
+def _desc_dict(desc) -> dict:
+    return dict(desc) if isinstance(desc, dict) else {k: int(getattr(desc, k)) for k in _DESC_FIELDS}
+
+
+def yuv_span(n: int, h: int, w: int, desc) -> int:
+    """Bytes that ``n`` frames described by ``desc`` reach from the start of the first; ValueError for geometry that no
+    conversion accepts (the cases ``pa_yuv420_to_bgr`` refuses)."""
+    d = _desc_dict(desc)
+    if w < 2 or h < 2 or w % 2 or h % 2:
+        raise ValueError(f"{w} x {h} frames: 4:2:0 needs an even width and height of at least 2")
+    if n < 1:
+        raise ValueError(f"n = {n} frames")
+    nv12 = d["layout"] == YUV_LAYOUTS["nv12"]
+    crow = w if nv12 else w // 2
+    if d["pitch_y"] < w or d["pitch_c"] < crow:
+        raise ValueError(f"pitch smaller than its row (pitch_y {d['pitch_y']} for {w} bytes, pitch_c {d['pitch_c']} for {crow})")
+    if d["off_u"] < 0 or d["off_v"] < 0 or (nv12 and d["off_v"] != d["off_u"] + 1):
+        raise ValueError(f"bad plane offsets off_u {d['off_u']}, off_v {d['off_v']} (NV12: off_v = off_u + 1)")
+    c_len = (h // 2 - 1) * d["pitch_c"] + crow
+    extent = max((h - 1) * d["pitch_y"] + w, d["off_u"] + c_len, 0 if nv12 else d["off_v"] + c_len)
+    if d["frame_stride"] < extent:
+        raise ValueError(f"frame_stride {d['frame_stride']} is smaller than the {extent} bytes the planes of one frame span")
+    return (n - 1) * d["frame_stride"] + extent
+
+
+def yuv420_to_bgr_host(raw, n: int, h: int, w: int, desc) -> np.ndarray:
+    """(n, h, w, 3) uint8 BGR of ``n`` frames of 8-bit YUV 4:2:0 in the 1-D byte array ``raw``, geometry and coefficients as in
+    ``pa_yuv_desc`` (``yuv_desc``).  The CPU path and the readable twin of csrc/yuv_convert.hip — the same integers:
+    nearest-neighbour chroma, 20-bit fixed point in int32, ``>>`` arithmetic."""
+    d = _desc_dict(desc)
+    raw = np.asarray(raw)
+    if raw.dtype != np.uint8 or raw.ndim != 1:
+        raise ValueError("raw YUV bytes must be a 1-D uint8 array")
+    if yuv_span(n, h, w, d) > raw.size:
+        raise ValueError(f"{n} frames as described span {yuv_span(n, h, w, d)} bytes, the array holds {raw.size}")
+    nv12 = d["layout"] == YUV_LAYOUTS["nv12"]
+    strided = np.lib.stride_tricks.as_strided
+    cs = 2 if nv12 else 1                                   # NV12: U and V alternate inside a chroma row
+    out = np.empty((n, h, w, 3), np.uint8)
+    half = np.int32(1 << 19)
+    for i in range(n):
+        f = raw[i * d["frame_stride"]:]
+        Y = strided(f, (h, w), (d["pitch_y"], 1)).astype(np.int32)
+        U = strided(f[d["off_u"]:], (h // 2, w // 2), (d["pitch_c"], cs)).astype(np.int32)
+        V = strided(f[d["off_v"]:], (h // 2, w // 2), (d["pitch_c"], cs)).astype(np.int32)
+        u = (U - 128).repeat(2, axis=0).repeat(2, axis=1)     # each 2 x 2 block of pixels shares one (U, V)
+        v = (V - 128).repeat(2, axis=0).repeat(2, axis=1)
+        y = np.maximum(0, Y - np.int32(d["y_off"])) * np.int32(d["cy"]) + half
+        out[i, ..., 2] = np.clip((y + np.int32(d["cvr"]) * v) >> 20, 0, 255)
+        out[i, ..., 1] = np.clip((y + np.int32(d["cug"]) * u + np.int32(d["cvg"]) * v) >> 20, 0, 255)
+        out[i, ..., 0] = np.clip((y + np.int32(d["cub"]) * u) >> 20, 0, 255)
+    return out
+
+
+class YuvFrame:
+    """Handle of one frame of a YUV clip (stored frame ``index`` of ``clip``).  ``.shape`` is the BGR frame's; ``np.asarray(f)`` /
+    ``f.bgr()`` convert it on the host; a batch of them goes through ``device_batch`` / ``host_batch``."""
+    __slots__ = ("clip", "index")
+
+    def __init__(self, clip: "_YuvSource", index: int):
+        self.clip, self.index = clip, index
+
+    @property
+    def shape(self) -> tuple:
+        return (self.clip.h, self.clip.w, 3)
+
+    def bgr(self) -> np.ndarray:
+        return self.clip.host_bgr(self.index, 1)[0]
+
+    def __array__(self, dtype=None, copy=None):
+        a = self.bgr()
+        return a if dtype is None else a.astype(dtype)
+
+
+class _YuvSource:
+    """What ``YuvClip`` and ``DeviceYuvClip`` share: the geometry, the frame handles, the BGR staging buffer in HBM and the
+    memory of which stored range it holds."""
+
+    def _init_geometry(self, nbytes: int, w, h, layout, matrix, range, pitch, pitch_c, off_u, off_v, frame_stride, header_bytes, n,
+                       fps, repeat, coeffs=None) -> None:
+        self.w, self.h = int(w), int(h)
+        self.layout = layout
+        self.desc = yuv_desc(w, h, layout, matrix, range, pitch, pitch_c, off_u, off_v, frame_stride, coeffs)
+        self.header_bytes = int(header_bytes)
+        self.frame_stride = self.desc["frame_stride"]
+        self.extent = yuv_span(1, self.h, self.w, self.desc)
+        fit = (nbytes - self.header_bytes - self.extent) // self.frame_stride + 1 if nbytes - self.header_bytes >= self.extent else 0
+        self.n = fit if n is None else int(n)
+        if self.n < 1 or self.n > fit:
+            raise ValueError(f"{nbytes} bytes hold {fit} frame(s) of this geometry behind a {self.header_bytes}-byte header; n = {self.n}")
+        self.fps, self.repeat = int(fps), int(repeat)
+        self.frame_bytes = self.h * self.w * 3
+        self._bgr = None                 # DeviceBuffer: converted frames of the stored range _bgr_range = (first, count)
+        self._bgr_range = None
+        self._marker = None              # .y4m: the bytes every frame record starts with, checked when the frame is yielded
+
+    @property
+    def total_frames(self) -> int:
+        return self.n * self.repeat
+
+    def _offset(self, i: int) -> int:
+        return self.header_bytes + i * self.frame_stride
+
+    def frames(self, start: int = 0, end: Optional[int] = None, stride: int = 1) -> Iterator[YuvFrame]:
+        stop = self.total_frames if end is None else min(end, self.total_frames)
+        for i in range(start, stop, stride):
+            k = i % self.n
+            self._check_marker(k)
+            yield YuvFrame(self, k)
+
+    def _check_marker(self, k: int) -> None:
+        pass
+
+    def host_bgr(self, first: int, count: int) -> np.ndarray:
+        """(count, h, w, 3) uint8 BGR of stored frames [first, first + count), converted on the host."""
+        return yuv420_to_bgr_host(self._host_bytes(first, count), count, self.h, self.w, self.desc)
+
+    def _engine_or_default(self):
+        if self.engine is None:
+            from . import engine as E
+            self.engine = E.default_engine()
+        return self.engine
+
+    def invalidate(self) -> None:
+        """The clip's bytes were rewritten (a decoder's ring came round): forget which range the BGR staging holds."""
+        self._bgr_range = None
+
+    def device_view(self, first: int, count: int):
+        """(DeviceBuffer view over the BGR of stored frames [first, first + count), count, h, w): converted on the GPU into the
+        clip's staging buffer, on the engine's compute stream — the stream every later reader of the view and the next
+        conversion into it are queued on, which is what makes one staging buffer enough (include/padel_hip.h,
+        pa_yuv420_to_bgr).  A range the staging already holds converts nothing (fan-out: every tracker asks for the same batch)."""
+        assert 0 <= first and count >= 1 and first + count <= self.n, (first, count, self.n)
+        eng = self._engine_or_default()
+        if not hasattr(eng, "yuv420_to_bgr"):        # a stand-in engine without kernels (tests/fake_engine.py): host path
+            return None
+        held = self._bgr_range
+        if held is None or first < held[0] or first + count > held[0] + held[1]:
+            need = count * self.frame_bytes
+            if self._bgr is None or self._bgr.nbytes < need:
+                if self._bgr is not None:
+                    eng.synchronize()                # readers of the old staging may still be queued
+                    self._bgr.free()
+                self._bgr_range = None
+                self._bgr = eng.alloc(need)
+            self._bgr_range = None
+            eng.yuv420_to_bgr(self._device_source(first, count), count, self.h, self.w, self.desc, self._bgr)
+            held = self._bgr_range = (first, count)
+        return self._bgr.view((first - held[0]) * self.frame_bytes, count * self.frame_bytes), count, self.h, self.w
+
+    def free(self) -> None:
+        """Release the BGR staging buffer (and what else the clip owns in HBM)."""
+        if self._bgr is not None:
+            if self.engine is not None:
+                self.engine.synchronize()
+            self._bgr.free()
+        self._bgr, self._bgr_range = None, None
+
+
+class YuvClip(_YuvSource):
+    """Host-memory clip of 8-bit YUV 4:2:0 frames: ``data`` is a 1-D uint8 array (or ``np.memmap``) of raw bytes, frame i at
+    ``header_bytes + i * frame_stride``, planes inside a frame as ``yuv_desc`` describes (defaults: tightly packed).  Presented
+    as ``n * repeat`` frames.  ``on_device=True``: batches are uploaded raw — half the bytes of BGR — and converted on the GPU
+    of ``engine`` (default: the default engine, the one the trackers' models run on: the conversion is ordered with them by that
+    engine's stream); ``on_device=False``: converted on the host (boxes without a GPU)."""
+
+    def __init__(self, data, w: int, h: int, layout: str = "nv12", matrix: str = "bt601", range: str = "limited",
+                 pitch: Optional[int] = None, pitch_c: Optional[int] = None, off_u: Optional[int] = None, off_v: Optional[int] = None,
+                 frame_stride: Optional[int] = None, header_bytes: int = 0, n: Optional[int] = None, fps: int = 30, repeat: int = 1,
+                 on_device: bool = True, engine=None, coeffs: Optional[tuple] = None):
+        if not isinstance(data, np.ndarray) or data.dtype != np.uint8 or data.ndim != 1:
+            raise ValueError("YuvClip: data must be a 1-D uint8 array of raw bytes")
+        self.data = data
+        self.on_device, self.engine = bool(on_device), engine
+        self._pinned_by = None
+        self._init_geometry(data.size, w, h, layout, matrix, range, pitch, pitch_c, off_u, off_v, frame_stride, header_bytes, n, fps,
+                            repeat, coeffs)
+
+    # ---- .y4m: "YUV4MPEG2 W.. H.. F..:.. I. A..:.. C.. X..\n", then per frame "FRAME\n" + the planes of one I420 frame
+    @classmethod
+    def from_y4m(cls, path, matrix: Optional[str] = None, range: Optional[str] = None, **kw) -> "YuvClip":
+        """Memory-map a ``.y4m`` file (``ffmpeg -i rally.mp4 rally.y4m`` writes one).  8-bit 4:2:0 progressive only; ``matrix``
+        defaults to bt601, ``range`` to the file's ``XCOLORRANGE`` tag, else limited."""
+        path = str(path)
+        size = os.path.getsize(path)
+        with open(path, "rb") as fh:
+            head = fh.read(4096)
+        eol = head.find(b"\n")
+        if not head.startswith(b"YUV4MPEG2") or eol < 0:
+            raise ValueError(f"{path}: not a YUV4MPEG2 file (no 'YUV4MPEG2 ...' header line in the first 4096 bytes)")
+        w = h = None
+        fps, tag_range = 30, None
+        for tok in head[:eol].decode("ascii", "replace").split()[1:]:
+            key, val = tok[0], tok[1:]
+            if key == "W":
+                w = int(val)
+            elif key == "H":
+                h = int(val)
+            elif key == "F":
+                num, _, den = val.partition(":")
+                if int(num) > 0 and int(den or 1) > 0:
+                    fps = int(round(int(num) / int(den or 1)))
+            elif key == "I":
+                if val not in ("p", "?"):
+                    raise ValueError(f"{path}: interlacing I{val} is not supported (progressive frames only)")
+            elif key == "C":
+                if val not in ("420", "420jpeg", "420mpeg2", "420paldv"):
+                    raise ValueError(f"{path}: chroma format C{val} is not supported (8-bit 4:2:0 only)")
+            elif tok.startswith("XCOLORRANGE="):
+                tag_range = {"FULL": "full", "LIMITED": "limited"}.get(tok.split("=", 1)[1].upper())
+            # A (pixel aspect) and other X tags: ignored
+        if w is None or h is None:
+            raise ValueError(f"{path}: the header names no W / H")
+        if w < 2 or h < 2 or w % 2 or h % 2:
+            raise ValueError(f"{path}: odd or too small frame size W{w} H{h} (4:2:0 needs an even width and height)")
+        fb = w * h * 3 // 2
+        header = eol + 1
+        if (size - header) // (6 + fb) < 1:
+            raise ValueError(f"{path}: no whole frame behind the header ({size} bytes)")
+        data = np.memmap(path, np.uint8, "r")
+        clip = cls(data, w, h, layout="i420", matrix=matrix or "bt601", range=range or tag_range or "limited",
+                   frame_stride=6 + fb, header_bytes=header + 6, fps=kw.pop("fps", fps), **kw)
+        clip._marker = b"FRAME\n"
+        clip.path = path
+        return clip
+
+    def _check_marker(self, k: int) -> None:
+        if self._marker is not None:
+            at = self._offset(k) - len(self._marker)
+            if self.data[at:at + len(self._marker)].tobytes() != self._marker:
+                raise ValueError(f"{getattr(self, 'path', 'y4m')}: frame {k} does not start with 'FRAME\\n' at byte offset {at} "
+                                 f"(frame parameters or a damaged file)")
+
+    def pin(self, engine) -> "YuvClip":
+        """Page-lock the raw bytes (a decoder writing into pinned memory): batches then go up at PCIe speed.  The memory
+        must be writable (not a read-only mapping of a file)."""
+        if self._pinned_by is None:
+            engine.pin(self.data)
+            self._pinned_by = engine
+        elif self._pinned_by is not engine:
+            raise ValueError("YuvClip is page-locked through another engine: unpin() it first")
+        return self
+
+    def unpin(self) -> None:
+        if self._pinned_by is not None:
+            eng, self._pinned_by = self._pinned_by, None
+            eng.synchronize()                        # an upload from these pages may still be queued
+            eng.unpin(self.data)
+
+    def __enter__(self) -> "YuvClip":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.unpin()
+
+    def __del__(self):
+        try:
+            self.unpin()
+            self.free()
+        except Exception:
+            pass
+
+    def _host_bytes(self, first: int, count: int) -> np.ndarray:
+        o = self._offset(first)
+        return self.data[o:o + (count - 1) * self.frame_stride + self.extent]
+
+    _device_source = _host_bytes                     # the engine copies them to its raw staging buffer on the compute stream
+
+
+class DeviceYuvClip(_YuvSource):
+    """The raw YUV bytes resident in HBM — what a hardware decoder hands over.  ``data_or_buffer``: a 1-D uint8 array (uploaded
+    once, from ``header_bytes`` on, into a buffer the clip owns) or a ``DeviceBuffer`` that already holds the bytes (not owned:
+    ``free()`` leaves it alone).  Geometry arguments as for ``YuvClip``."""
+    on_device = True
+
+    def __init__(self, engine, data_or_buffer, w: int, h: int, layout: str = "nv12", matrix: str = "bt601", range: str = "limited",
+                 pitch: Optional[int] = None, pitch_c: Optional[int] = None, off_u: Optional[int] = None, off_v: Optional[int] = None,
+                 frame_stride: Optional[int] = None, header_bytes: int = 0, n: Optional[int] = None, fps: int = 30, repeat: int = 1,
+                 coeffs: Optional[tuple] = None):
+        self.engine = engine
+        host = isinstance(data_or_buffer, np.ndarray)
+        if host and (data_or_buffer.dtype != np.uint8 or data_or_buffer.ndim != 1):
+            raise ValueError("DeviceYuvClip: data must be a 1-D uint8 array of raw bytes or a DeviceBuffer")
+        nbytes = data_or_buffer.size if host else data_or_buffer.nbytes
+        self._init_geometry(nbytes, w, h, layout, matrix, range, pitch, pitch_c, off_u, off_v, frame_stride, header_bytes, n, fps,
+                            repeat, coeffs)
+        if host:
+            span = (self.n - 1) * self.frame_stride + self.extent
+            self.buffer = engine.alloc(span)
+            self.buffer.upload(np.ascontiguousarray(data_or_buffer[self.header_bytes:self.header_bytes + span]))
+            self.header_bytes = 0
+            self._owns = True
+        else:
+            self.buffer, self._owns = data_or_buffer, False
+
+    def upload(self, raw: np.ndarray, first: int = 0) -> None:
+        """Overwrite the bytes from stored frame ``first`` on (a decoder refilling its surfaces); forgets the converted range."""
+        raw = np.ascontiguousarray(raw, np.uint8).reshape(-1)
+        o = self._offset(first)
+        assert o + raw.size <= self.buffer.nbytes
+        self.engine.synchronize()                    # a conversion still queued reads the bytes about to change
+        self.buffer.view(o, raw.size).upload(raw)
+        self.invalidate()
+
+    def _device_source(self, first: int, count: int):
+        o = self._offset(first)
+        return self.buffer.view(o, (count - 1) * self.frame_stride + self.extent)
+
+    def _host_bytes(self, first: int, count: int) -> np.ndarray:
+        v = self._device_source(first, count)
+        return v.download(np.empty(v.nbytes, np.uint8))
+
+    def free(self) -> None:
+        super().free()
+        if self._owns and self.buffer is not None:
+            self.buffer.free()
+        self.buffer = None
+
+
+# .y4m files opened by path: one clip per file as it is on disk now (every read of the path — VideoInfo, each tracker's pass — shares
+# the mapping, the BGR staging and its memory of what it holds); a file that changed is opened afresh
+_Y4M_OPEN: dict = {}
+
+
+def _open_y4m(p: str) -> YuvClip:
+    st = os.stat(p)
+    key = (os.path.abspath(p), st.st_mtime_ns, st.st_size)
+    hit = _Y4M_OPEN.get(key[0])
+    if hit is None or hit[0] != key:
+        if hit is not None:
+            hit[1].free()
+        hit = _Y4M_OPEN[key[0]] = (key, YuvClip.from_y4m(p))
+    return hit[1]
+
+
 def device_batch(sample):
     """If ``sample`` is a list of DeviceFrame handles of ONE clip with consecutive stored indices, return
     (DeviceBuffer view over exactly those frames, n, h, w); None for host frames.  Anything else is an error: a
-    device batch must be one contiguous range (batch sizes that divide the stored clip length always are)."""
-    if isinstance(sample, np.ndarray) or not len(sample) or not isinstance(sample[0], DeviceFrame):
+    device batch must be one contiguous range (batch sizes that divide the stored clip length always are).
+    ``YuvFrame`` handles of a clip with ``on_device=True`` follow the same rule: the range is converted to BGR on the GPU
+    into the clip's staging buffer (once: asking for a range the staging already holds converts nothing) and the view over it
+    comes back; with ``on_device=False`` the answer is None and ``host_batch`` converts on the host."""
+    if isinstance(sample, np.ndarray) or not len(sample):
+        return None
+    if isinstance(sample[0], YuvFrame):
+        clip, i0 = sample[0].clip, sample[0].index
+        if not clip.on_device:
+            return None
+        for k, f in enumerate(sample):
+            if not isinstance(f, YuvFrame) or f.clip is not clip or f.index != i0 + k:
+                raise ValueError("a batch of device-converted YUV frames must be a contiguous range of one clip")
+        return clip.device_view(i0, len(sample))
+    if not isinstance(sample[0], DeviceFrame):
         return None
     clip, i0 = sample[0].clip, sample[0].index
     for k, f in enumerate(sample):
@@ -201,6 +598,10 @@ def host_batch(sample) -> np.ndarray:
         return sample
     sample = list(sample)
     f0 = sample[0]
+    if any(isinstance(f, YuvFrame) for f in sample):
+        if all(isinstance(f, YuvFrame) and f.clip is f0.clip and f.index == f0.index + k for k, f in enumerate(sample)):
+            return f0.clip.host_bgr(f0.index, len(sample))          # one pass over one contiguous range of raw bytes
+        return np.stack([np.asarray(f) for f in sample])
     if isinstance(f0, np.ndarray) and f0.flags.c_contiguous and f0.dtype == np.uint8 and f0.base is not None:
         fb, p0 = f0.nbytes, f0.ctypes.data
         root = f0.base
@@ -211,13 +612,16 @@ def host_batch(sample) -> np.ndarray:
 
 
 def get_video_frames_generator(source_path, stride: int = 1, start: int = 0, end: Optional[int] = None) -> Iterator[np.ndarray]:
-    if isinstance(source_path, (DeviceClip, ArrayClip)):
+    if isinstance(source_path, (DeviceClip, ArrayClip, _YuvSource)):
         yield from source_path.frames(start, end, stride)
         return
     p = str(source_path)
     src = _scheme(p)
     if src is not None:
         yield from src[1](p, start, end, stride)
+        return
+    if p.endswith(".y4m"):
+        yield from _open_y4m(p).frames(start, end, stride)
         return
     if p.endswith(".npy"):
         a = np.load(p, mmap_mode="r")
