@@ -27,6 +27,9 @@ fi
 if [ -z "${PADEL_ONLY:-}" ]; then
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c bytetrack.cpp -o "$BUILD/bytetrack.o" &
 pids+=($!)
+# which kernel runs a conv (tile table, resolver, choosers): no HIP runtime call, only the types of kernels.h
+g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include ${PADEL_EXTRA_FLAGS:-} -c conv_select.cpp -o "$BUILD/conv_select.o" &
+pids+=($!)
 fi
 for p in "${pids[@]}"; do wait "$p"; done
 hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$BUILD"/*.o -Wl,-rpath,/opt/rocm/lib

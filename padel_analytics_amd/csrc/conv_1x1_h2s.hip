@@ -421,13 +421,10 @@ __global__ void __launch_bounds__(256 * WR, 2) conv_h2s3_kernel(const ConvArgs a
     if (fw < a.n16) h2_epilogue<MF, NF>(a, acc, cross, mpix, fw, lq, fast);
 }
 
-bool conv_h2s3_supported(const ConvArgs& a) {
-    return a.w_single && a.wr && a.ksize == 3 && a.stride == 2 && (a.cin & 31) == 0 && a.cin >= 32 && a.w != nullptr && !a.in2 &&
-           a.Ho <= (a.H + 1) / 2 && a.Wo <= (a.W + 1) / 2 && (long long)4 * a.W * a.in_cs * 4 < 0x3FFFFFFFll;
-}
-
-hipError_t launch_conv_h2s3(const ConvArgs& a_in, hipStream_t s, bool m64) {
-    if (!conv_h2s3_supported(a_in)) return hipErrorNotSupported;
+// tile 246: 128 x 192 (8 waves), 248: 64 x 192 tiles of four waves
+hipError_t launch_conv_h2s3(const ConvArgs& a_in, int tile, hipStream_t s) {
+    if (tile != 246 && tile != 248) return hipErrorNotSupported;
+    const bool m64 = tile == 248;
     ConvArgs a = a_in;
     a.n_mtiles = m64 ? (a.M + 63) / 64 : (a.M + 127) / 128;
     a.n_ntiles = (a.n16 + 11) / 12;
@@ -442,13 +439,10 @@ hipError_t launch_conv_h2s3(const ConvArgs& a_in, hipStream_t s, bool m64) {
     return hipGetLastError();
 }
 
-bool conv_h2s_supported(const ConvArgs& a) {
-    return a.w_single && a.wr && a.ksize == 1 && a.stride == 1 && (a.cin & 31) == 0 && a.cin >= 64 && a.Ho == a.H && a.Wo == a.W && a.w != nullptr &&
-           !a.in2 && (long long)128 * a.in_cs * 4 < 0x7FFFFFFFll;
-}
-
-hipError_t launch_conv_h2s(const ConvArgs& a_in, bool nf12, hipStream_t s, bool m64) {
-    if (!conv_h2s_supported(a_in)) return hipErrorNotSupported;
+// tile 244: 128 x 96 (4 waves), 245: 128 x 192 (8 waves, one workgroup per CU), 247: 64 x 192 (four waves, two workgroups per CU)
+hipError_t launch_conv_h2s(const ConvArgs& a_in, int tile, hipStream_t s) {
+    if (tile != 244 && tile != 245 && tile != 247) return hipErrorNotSupported;
+    const bool nf12 = tile != 244, m64 = tile == 247;
     ConvArgs a = a_in;
     if (nf12 && m64) {                          // 64 x 192 tiles: four waves, two workgroups per CU
         a.n_mtiles = (a.M + 63) / 64;

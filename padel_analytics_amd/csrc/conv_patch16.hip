@@ -415,14 +415,9 @@ static hipError_t launch_p16(const ConvArgs& a_in, hipStream_t s) {
     return hipGetLastError();
 }
 
-bool conv_p16_supported(const ConvArgs& a) {
-    return a.ksize == 3 && a.stride == 1 && (a.cin & 31) == 0 && a.cin >= 32 && a.Ho == a.H && a.Wo == a.W;
-}
-
-// nf = channel fragments (of 16) per workgroup: 3, 4 (3 workgroups per CU) or 6; + 20: the quad kernel (16 x 16 pixels)
-hipError_t launch_conv_p16(const ConvArgs& a, int nf, hipStream_t s) {
-    if (!conv_p16_supported(a)) return hipErrorNotSupported;
-    switch (nf) {
+// tile - 300 = channel fragments (of 16) per workgroup: 3, 4 (3 workgroups per CU) or 6; + 20: the quad kernel (16 x 16 pixels)
+hipError_t launch_conv_p16(const ConvArgs& a, int tile, hipStream_t s) {
+    switch (tile - 300) {
         case 3: return launch_p16<3>(a, s);
         case 4: return launch_p16<4>(a, s);
         case 6: return launch_p16<6>(a, s);

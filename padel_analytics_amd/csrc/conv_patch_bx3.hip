@@ -365,22 +365,14 @@ static hipError_t launch_pt(const ConvArgs& a_in, hipStream_t s) {
 
 template <int NF>
 static hipError_t launch_p(const ConvArgs& a_in, hipStream_t s) {
-    if (a_in.in2) {                    // absorbed upsample: whole 32-channel chunks only, even map size
-        if ((a_in.cin & 31) || (a_in.up_c & 31) || a_in.up_c <= 0 || a_in.up_c > a_in.cin || ((a_in.H | a_in.W) & 1)) return hipErrorNotSupported;
-        return launch_pt<NF, false, true>(a_in, s);
-    }
+    if (a_in.in2) return launch_pt<NF, false, true>(a_in, s);      // absorbed upsample: whole 32-channel chunks only, even map size
     if (a_in.cin & 16) return launch_pt<NF, true, false>(a_in, s);
     return launch_pt<NF, false, false>(a_in, s);
 }
 
-bool conv_bx3p_supported(const ConvArgs& a) {
-    return a.ksize == 3 && a.stride == 1 && (a.cin & 15) == 0 && a.cin >= 16 && a.Ho == a.H && a.Wo == a.W && a.w3 != nullptr;
-}
-
-// nf = channel fragments (of 16) per workgroup: 3 (8x16 pixels x 48 channels, 3 workgroups per CU), 4, 6
-hipError_t launch_conv_bx3p(const ConvArgs& a, int nf, hipStream_t s) {
-    if (!conv_bx3p_supported(a)) return hipErrorNotSupported;
-    switch (nf) {
+// tile - 300 = channel fragments (of 16) per workgroup: 3 (8x16 pixels x 48 channels, 3 workgroups per CU), 4, 6
+hipError_t launch_conv_bx3p(const ConvArgs& a, int tile, hipStream_t s) {
+    switch (tile - 300) {
         case 3: return launch_p<3>(a, s);
         case 4: return launch_p<4>(a, s);
         case 6: return launch_p<6>(a, s);

@@ -490,22 +490,14 @@ static hipError_t launch_hpt(const ConvArgs& a_in, hipStream_t s) {
 
 template <int NF, bool PIPE>
 static hipError_t launch_hp(const ConvArgs& a_in, hipStream_t s) {
-    if (a_in.in2) {                    // absorbed upsample: whole 32-channel chunks only, even map size
-        if ((a_in.cin & 31) || (a_in.up_c & 31) || a_in.up_c <= 0 || a_in.up_c > a_in.cin || ((a_in.H | a_in.W) & 1)) return hipErrorNotSupported;
-        return launch_hpt<NF, false, true, PIPE>(a_in, s);
-    }
+    if (a_in.in2) return launch_hpt<NF, false, true, PIPE>(a_in, s);      // absorbed upsample: whole 32-channel chunks only, even map size
     if (a_in.cin & 16) return launch_hpt<NF, true, false, PIPE>(a_in, s);
     return launch_hpt<NF, false, false, PIPE>(a_in, s);
 }
 
-bool conv_h2p_supported(const ConvArgs& a) {
-    return a.ksize == 3 && a.stride == 1 && (a.cin & 15) == 0 && a.cin >= 16 && a.Ho == a.H && a.Wo == a.W && a.w != nullptr;
-}
-
-// nf = channel fragments (of 16) per workgroup: 3 (8x16 pixels x 48 channels), 4, 6; + 10: the software-pipelined schedule
-hipError_t launch_conv_h2p(const ConvArgs& a, int nf, hipStream_t s) {
-    if (!conv_h2p_supported(a)) return hipErrorNotSupported;
-    switch (nf) {
+// tile - 300 = channel fragments (of 16) per workgroup: 3 (8x16 pixels x 48 channels), 4; + 10: the software-pipelined schedule
+hipError_t launch_conv_h2p(const ConvArgs& a, int tile, hipStream_t s) {
+    switch (tile - 300) {
         case 3: return launch_hp<3, false>(a, s);
         case 4: return launch_hp<4, false>(a, s);
         case 13: return launch_hp<3, true>(a, s);
@@ -513,7 +505,7 @@ hipError_t launch_conv_h2p(const ConvArgs& a, int nf, hipStream_t s) {
         //  303 and 1.3-2 x its RMS error on long K, profiles/conv_h2_sweep_r3a.txt — and the software-pipelined 64-channel tile
         //  314 — 10-15 % slower than 304, profiles/conv_h2_sweep_r3f_pipe.txt — were never chosen automatically: removed)
 #ifdef PADEL_H2P_PROBES
-#define PADEL_HP_PROBE_CASE(P_) case 32 + (P_): if (a.in2 || (a.cin & 16)) return hipErrorNotSupported; return launch_hpt<3, false, false, false, (P_)>(a, s);
+#define PADEL_HP_PROBE_CASE(P_) case 32 + (P_): return launch_hpt<3, false, false, false, (P_)>(a, s);
         PADEL_HP_PROBE_CASE(1) PADEL_HP_PROBE_CASE(2) PADEL_HP_PROBE_CASE(3) PADEL_HP_PROBE_CASE(4) PADEL_HP_PROBE_CASE(5)
         PADEL_HP_PROBE_CASE(7) PADEL_HP_PROBE_CASE(8) PADEL_HP_PROBE_CASE(10) PADEL_HP_PROBE_CASE(15) PADEL_HP_PROBE_CASE(16)
         PADEL_HP_PROBE_CASE(17) PADEL_HP_PROBE_CASE(31)

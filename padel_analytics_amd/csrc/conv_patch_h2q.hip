@@ -61,8 +61,8 @@ __device__ __forceinline__ unsigned hq_off(int p, int q) { return (unsigned)(p *
 // DBG (tuning only, builds with -DPADEL_H2P_PROBES, pa_engine_set_tuning "timeline"): every wave stamps s_memtime at 5
 // points of every tap step (step top / own requests landed / barrier passed / operands in registers / last MFMA issued)
 // into an LDS ring of 32 steps, dumped to a.dbg at the end (tools/timeline_probe.py --kernel h2q)
-constexpr int kQDbgSteps = 32;
-constexpr int kQDbgWords = 8 + 4 * kQDbgSteps * 5;
+constexpr int kQDbgSteps = kPatchDbgSteps;      // kernels.h: the engine sizes the timeline buffer with the same constants
+constexpr int kQDbgWords = kPatchDbgWords;
 
 }  // namespace
 
@@ -306,12 +306,8 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
 #undef PADEL_HQ_STAMP
 }
 
-bool conv_h2q_supported(const ConvArgs& a) {
-    return a.ksize == 3 && a.stride == 1 && (a.cin & 31) == 0 && a.cin >= 32 && a.Ho == a.H && a.Wo == a.W && a.w != nullptr && !a.in2;
-}
-
-hipError_t launch_conv_h2q(const ConvArgs& a_in, hipStream_t s) {
-    if (!conv_h2q_supported(a_in)) return hipErrorNotSupported;
+hipError_t launch_conv_h2q(const ConvArgs& a_in, int tile, hipStream_t s) {
+    if (tile != 323) return hipErrorNotSupported;
     ConvArgs a = a_in;
     const int batch = a.M / (a.Ho * a.Wo);
     a.n_mtiles = batch * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);

@@ -49,8 +49,8 @@ typedef int hr_i32x4 __attribute__((ext_vector_type(4)));
 // wave stamps s_memtime at 5 points of every tap step into an LDS ring of 32 steps (tools/timeline_probe.py --kernel h2r):
 // 0 step top / 1 this tap's weights landed (counted wait passed) / 2 chunk barrier passed (tap 8; elsewhere = 1) / 3 the first
 // row's six products issued (its operands were in registers) / 4 last product issued
-constexpr int kRDbgSteps = 32;
-constexpr int kRDbgWords = 8 + 4 * kRDbgSteps * 5;
+constexpr int kRDbgSteps = kPatchDbgSteps;      // kernels.h: the engine sizes the timeline buffer with the same constants
+constexpr int kRDbgWords = kPatchDbgWords;
 constexpr int kRDbgTile = 3;                     // the tile of a persistent workgroup whose steps the ring keeps
 
 }  // namespace
@@ -499,11 +499,6 @@ hipError_t launch_h2_mplane_check(const float* w, long long rows_x_ksteps, unsig
     return hipGetLastError();
 }
 
-// k-steps of a stride-1 3x3 layer in the packed blob: 9 taps per whole 32-channel chunk + 5 tap pairs for a 16-channel tail
-// (1x1 layers: one k-step per 32 channels, a 16-channel tail half-filled)
-static int h2_ksteps(int cin, int ksize) { return ksize == 3 ? (cin >> 5) * 9 + ((cin & 16) ? 5 : 0) : (cin + 31) >> 5; }
-size_t conv_h2r_copy_bytes(int n16, int cin, int ksize) { return (size_t)n16 * (size_t)h2_ksteps(cin, ksize) * 2048; }
-
 hipError_t launch_h2r_repack(const float* w, void* wr, int n16, int cin, int ksize, hipStream_t s) {
     const int ksteps = h2_ksteps(cin, ksize);
     const long long n = (long long)n16 * ksteps * 128;
@@ -512,13 +507,10 @@ hipError_t launch_h2r_repack(const float* w, void* wr, int n16, int cin, int ksi
     return hipGetLastError();
 }
 
-bool conv_h2r_supported(const ConvArgs& a) {
-    return a.wr && a.ksize == 3 && a.stride == 1 && (a.cin & 31) == 0 && a.cin >= 64 && a.Ho == a.H && a.Wo == a.W && a.w != nullptr && !a.in2;
-}
-
-// nf = channel fragments per wave: 3 (96-channel tiles; two-product layers only) or 2 (64-channel tiles; two or three products)
-hipError_t launch_conv_h2r(const ConvArgs& a_in, int nf, hipStream_t s) {
-    if (!conv_h2r_supported(a_in) || (nf != 2 && nf != 3) || (nf == 3 && !a_in.w_single)) return hipErrorNotSupported;
+// nf = channel fragments per wave: 3 (tile 324, 96-channel tiles; two-product layers only) or 2 (tile 325, 64-channel tiles; two or three products)
+hipError_t launch_conv_h2r(const ConvArgs& a_in, int tile, hipStream_t s) {
+    if (tile != 324 && tile != 325) return hipErrorNotSupported;
+    const int nf = tile == 324 ? 3 : 2;
     ConvArgs a = a_in;
     const int batch = a.M / (a.Ho * a.Wo);
     a.n_mtiles = batch * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);

@@ -276,10 +276,6 @@ __global__ void __launch_bounds__(256, 2) conv_h2v_kernel(const ConvArgs a) {
     h2_epilogue<MF, NF>(a, acc, cross, mpix, f0, lq, fast);
 }
 
-bool conv_h2v_supported(const ConvArgs& a) {
-    return a.wr && a.ksize == 3 && a.stride == 1 && (a.cin == 16 || a.cin == 32 || a.cin == 48) && a.Ho == a.H && a.Wo == a.W && a.w != nullptr && !a.in2;
-}
-
 template <int NF, bool WS>
 static hipError_t launch_hv(const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a = a_in;
@@ -293,9 +289,9 @@ static hipError_t launch_hv(const ConvArgs& a_in, hipStream_t s) {
     return hipGetLastError();
 }
 
-// nf = channel fragments (of 16) per workgroup: 1, 2, 3 (3 with two products only)
-hipError_t launch_conv_h2v(const ConvArgs& a, int nf, hipStream_t s) {
-    if (!conv_h2v_supported(a)) return hipErrorNotSupported;
+// tile - 340 = channel fragments (of 16) per workgroup: 1, 2, 3 (3 with two products only)
+hipError_t launch_conv_h2v(const ConvArgs& a, int tile, hipStream_t s) {
+    const int nf = tile - 340;
     if (a.w_single) {
         switch (nf) {
             case 1: return launch_hv<1, true>(a, s);

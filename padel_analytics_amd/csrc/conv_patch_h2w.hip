@@ -274,10 +274,6 @@ __global__ void __launch_bounds__(256, 2) conv_h2w_kernel(const ConvArgs a) {
     h2_epilogue<MF, NF>(a, acc, cross, mpix, f0, lq, fast);
 }
 
-bool conv_h2w_supported(const ConvArgs& a) {
-    return a.ksize == 3 && a.stride == 1 && (a.cin == 16 || a.cin == 32 || a.cin == 48) && a.Ho == a.H && a.Wo == a.W && a.w != nullptr && !a.in2;
-}
-
 template <int NF>
 static hipError_t launch_hw(const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a = a_in;
@@ -295,10 +291,9 @@ static hipError_t launch_hw(const ConvArgs& a_in, hipStream_t s) {
     return hipGetLastError();
 }
 
-// nf = channel fragments (of 16) per workgroup: 1, 2, 3
-hipError_t launch_conv_h2w(const ConvArgs& a, int nf, hipStream_t s) {
-    if (!conv_h2w_supported(a)) return hipErrorNotSupported;
-    switch (nf) {
+// tile - 340 = channel fragments (of 16) per workgroup: 1, 2, 3
+hipError_t launch_conv_h2w(const ConvArgs& a, int tile, hipStream_t s) {
+    switch (tile - 340) {
         case 1: return launch_hw<1>(a, s);
         case 2: return launch_hw<2>(a, s);
         case 3: return launch_hw<3>(a, s);

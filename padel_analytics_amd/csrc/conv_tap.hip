@@ -457,75 +457,34 @@ static hipError_t launch_t(const ConvArgs& a_in, hipStream_t s) {
     return hipGetLastError();
 }
 
-// tile ids of the fp32 id space (shared by the tap, bf16x3 (+0), h2 (+200) and fp16 families): waves WM x WN, fragments MF x NF per wave
-struct TileShape { int id, wm, wn, mf, nf; };
-static const TileShape tile_shapes[] = {
-    {0, 2, 2, 4, 4},   // 128 x 128
-    {1, 2, 2, 4, 3},   // 128 x  96
-    {2, 4, 1, 4, 4},   // 256 x  64
-    {3, 4, 1, 4, 3},   // 256 x  48
-    {4, 4, 1, 4, 2},   // 256 x  32
-    {5, 4, 1, 4, 1},   // 256 x  16
-    {6, 2, 2, 2, 4},   //  64 x 128
-    {7, 2, 2, 2, 3},   //  64 x  96
-    {8, 4, 1, 2, 5},   // 128 x  80
-    {9, 4, 1, 2, 4},   // 128 x  64
-    {10, 2, 2, 4, 2},  // 128 x  64 (2x2 waves)
-    {11, 4, 1, 2, 2},  // 128 x  32
-    {12, 4, 1, 2, 1},  // 128 x  16
-    // tap kernel only (conv_tap.hip): 8 waves per workgroup / 128 x 48
-    {13, 4, 2, 2, 3},  // 128 x  96
-    {14, 4, 2, 2, 4},  // 128 x 128
-    {15, 4, 2, 2, 2},  // 128 x  64
-    {20, 4, 1, 2, 3},  // 128 x  48
-    {25, 4, 1, 1, 5},  //  64 x  80 (bf16x3 kernels only)
-};
-
-bool conv_variant_shape(int variant, int* bm, int* bn) {
-    for (const auto& v : tile_shapes)
-        if (v.id == variant) { *bm = v.wm * v.mf * 16; *bn = v.wn * v.nf * 16; return true; }
-    return false;
-}
-
-// hipErrorNotSupported when the layer or the tile is not covered
-hipError_t launch_conv_tap(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
-    if ((a.ksize != 3 && a.ksize != 1) || (a.cin & 15) || a.cin < 16) return hipErrorNotSupported;
-    if (a.res_pre) return hipErrorNotSupported;      // PA_CONV_RES_PREACT: h2 and bf16x3 epilogues only (the engine refuses with a message)
-    switch (variant) {
-        case 6: return conv_ran(ran, 6, "tap", launch_t<2, 2, 2, 4>(a, s));    //  64 x 128
-        case 7: return conv_ran(ran, 7, "tap", launch_t<2, 2, 2, 3>(a, s));    //  64 x  96
-        case 9: return conv_ran(ran, 9, "tap", launch_t<4, 1, 2, 4>(a, s));    // 128 x  64
-        case 10: return conv_ran(ran, 10, "tap", launch_t<2, 2, 4, 2>(a, s));   // 128 x  64 (2x2 waves)
-        case 11: return conv_ran(ran, 11, "tap", launch_t<4, 1, 2, 2>(a, s));   // 128 x  32
-        case 12: return conv_ran(ran, 12, "tap", launch_t<4, 1, 2, 1>(a, s));   // 128 x  16
-        case 13: return conv_ran(ran, 13, "tap", launch_t<4, 2, 2, 3>(a, s));   // 128 x  96,  8 waves
-        case 14: return conv_ran(ran, 14, "tap", launch_t<4, 2, 2, 4>(a, s));   // 128 x 128,  8 waves
-        case 15: return conv_ran(ran, 15, "tap", launch_t<4, 2, 2, 2>(a, s));   // 128 x  64,  8 waves
-        case 20: return conv_ran(ran, 20, "tap", launch_t<4, 1, 2, 3>(a, s));   // 128 x  48
+// waves WM x WN, fragments MF x NF per wave
+hipError_t launch_conv_tapt(const ConvArgs& a, int tile, hipStream_t s) {
+    switch (tile) {
+        case 6: return launch_t<2, 2, 2, 4>(a, s);    //  64 x 128
+        case 7: return launch_t<2, 2, 2, 3>(a, s);    //  64 x  96
+        case 9: return launch_t<4, 1, 2, 4>(a, s);    // 128 x  64
+        case 10: return launch_t<2, 2, 4, 2>(a, s);   // 128 x  64 (2x2 waves)
+        case 11: return launch_t<4, 1, 2, 2>(a, s);   // 128 x  32
+        case 12: return launch_t<4, 1, 2, 1>(a, s);   // 128 x  16
+        case 13: return launch_t<4, 2, 2, 3>(a, s);   // 128 x  96,  8 waves
+        case 14: return launch_t<4, 2, 2, 4>(a, s);   // 128 x 128,  8 waves
+        case 15: return launch_t<4, 2, 2, 2>(a, s);   // 128 x  64,  8 waves
+        case 20: return launch_t<4, 1, 2, 3>(a, s);   // 128 x  48
     }
     return hipErrorNotSupported;
 }
 
-// Tile choice for the tap kernels.  Measured on MI355X (profiles/conv_tap_sweep_r1.txt) every tile runs at
-// 113-121 TFLOP/s when its shape fits the layer exactly (128x16: ~0.8 of that), so the choice is about padding waste
-// (channel tile and pixel tile fill) and about the last, partly filled round of workgroups.
-int choose_conv_tap_variant(int M, int n16) {
-    struct V { int id, bm, nf; float speed; };
-    static const V vs[] = {{7, 64, 6, 1.00f},  {13, 128, 6, 0.99f}, {9, 128, 4, 0.99f}, {14, 128, 8, 1.00f}, {6, 64, 8, 0.98f},
-                           {20, 128, 3, 0.98f}, {11, 128, 2, 0.99f}, {12, 128, 1, 0.80f}};
-    float best = -1.f;
-    int bv = 7;
-    for (const V& v : vs) {
-        const int ntiles = (n16 + v.nf - 1) / v.nf;
-        const long long mtiles = (M + v.bm - 1) / v.bm;
-        const float fill = (float)n16 / (float)(ntiles * v.nf) * (float)M / (float)(mtiles * v.bm);
-        const long long blocks = mtiles * ntiles;
-        const long long per_cu = (blocks + 255) / 256;
-        const float occ = (float)blocks / (256.f * (float)per_cu);
-        const float sc = v.speed * fill * occ;
-        if (sc > best) { best = sc; bv = v.id; }
-    }
-    return bv;
+// The one conv entry point: which (tile, family) runs is resolve_conv's decision alone (conv_select.cpp); a launcher launches the tile it is given
+hipError_t launch_conv(int path, const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
+    static hipError_t (*const launchers[])(const ConvArgs&, int, hipStream_t) = {      // by ConvFamily
+        launch_conv_tapt, launch_conv_bx3t, launch_conv_bx3p, launch_conv_h2t, launch_conv_h2d, launch_conv_h2s, launch_conv_h2s3, launch_conv_h2p,
+        launch_conv_h2q,  launch_conv_h2r,  launch_conv_h2w,  launch_conv_h2v, launch_conv_t16, launch_conv_t16, launch_conv_p16,  launch_conv_p16};
+    ConvLaunched r;
+    ConvFamily f;
+    if (!resolve_conv(path, a, variant, &r, &f)) return hipErrorNotSupported;
+    const hipError_t e = launchers[f](a, r.tile, s);
+    if (ran && e == hipSuccess) *ran = r;
+    return e;
 }
 
 }  // namespace padel

@@ -558,103 +558,29 @@ static hipError_t launch_t16(const ConvArgs& a_in, hipStream_t s) {
     return hipGetLastError();
 }
 
-// tile ids: the fp32 id space (conv_variant_shape) + 30.. for the larger per-wave tiles only the fp16 path has
-hipError_t launch_conv_tap16(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
-    if ((a.ksize != 3 && a.ksize != 1) || (a.cin & 31) || a.cin < 32) return hipErrorNotSupported;
-    if (a.res_pre) return hipErrorNotSupported;      // PA_CONV_RES_PREACT: h2 and bf16x3 epilogues only
-    if (variant >= 300 && variant < 400) {           // fp16 patch kernel (conv_patch16.hip), or a tap tile where it does not apply
-        const int nf = variant - 300;
-        if (conv_p16_supported(a)) return conv_ran(ran, variant, nf >= 20 ? "p16q" : "p16", launch_conv_p16(a, nf, s));
-        variant = nf == 3 ? 20 : nf == 4 ? 9 : 31;
-    }
-    switch (variant) {
-        case 6: return conv_ran(ran, 6, "tap16", launch_t16<2, 2, 2, 4>(a, s));    //  64 x 128
-        case 7: return conv_ran(ran, 7, "tap16", launch_t16<2, 2, 2, 3>(a, s));    //  64 x  96
-        case 9: return conv_ran(ran, 9, "tap16", launch_t16<4, 1, 2, 4>(a, s));    // 128 x  64
-        case 11: return conv_ran(ran, 11, "tap16", launch_t16<4, 1, 2, 2>(a, s));   // 128 x  32
-        case 12: return conv_ran(ran, 12, "tap16", launch_t16<4, 1, 2, 1>(a, s));   // 128 x  16
-        case 20: return conv_ran(ran, 20, "tap16", launch_t16<4, 1, 2, 3>(a, s));   // 128 x  48
-        case 30: return conv_ran(ran, 30, "tap16", launch_t16<2, 2, 4, 4>(a, s));   // 128 x 128, 4 waves of 64 x 64
-        case 31: return conv_ran(ran, 31, "tap16", launch_t16<2, 2, 4, 3>(a, s));   // 128 x  96
-        case 32: return conv_ran(ran, 32, "tap16", launch_t16<2, 2, 4, 2>(a, s));   // 128 x  64
+// tile ids: the fp32 id space + 30.. for the larger per-wave tiles only the fp16 path has
+hipError_t launch_conv_t16(const ConvArgs& a, int tile, hipStream_t s) {
+    switch (tile) {
+        case 6: return launch_t16<2, 2, 2, 4>(a, s);    //  64 x 128
+        case 7: return launch_t16<2, 2, 2, 3>(a, s);    //  64 x  96
+        case 9: return launch_t16<4, 1, 2, 4>(a, s);    // 128 x  64
+        case 11: return launch_t16<4, 1, 2, 2>(a, s);   // 128 x  32
+        case 12: return launch_t16<4, 1, 2, 1>(a, s);   // 128 x  16
+        case 20: return launch_t16<4, 1, 2, 3>(a, s);   // 128 x  48
+        case 30: return launch_t16<2, 2, 4, 4>(a, s);   // 128 x 128, 4 waves of 64 x 64
+        case 31: return launch_t16<2, 2, 4, 3>(a, s);   // 128 x  96
+        case 32: return launch_t16<2, 2, 4, 2>(a, s);   // 128 x  64
         // + 40: the same tile with 64-channel (double) k-steps
-        case 46: return conv_ran(ran, 46, "tap16d", launch_t16d<2, 2, 2, 4>(a, s));  //  64 x 128
-        case 47: return conv_ran(ran, 47, "tap16d", launch_t16d<2, 2, 2, 3>(a, s));  //  64 x  96
-        case 49: return conv_ran(ran, 49, "tap16d", launch_t16d<4, 1, 2, 4>(a, s));  // 128 x  64
-        case 51: return conv_ran(ran, 51, "tap16d", launch_t16d<4, 1, 2, 2>(a, s));  // 128 x  32
-        case 60: return conv_ran(ran, 60, "tap16d", launch_t16d<4, 1, 2, 3>(a, s));  // 128 x  48
-        case 70: return conv_ran(ran, 70, "tap16d", launch_t16d<2, 2, 4, 4>(a, s));  // 128 x 128
-        case 71: return conv_ran(ran, 71, "tap16d", launch_t16d<2, 2, 4, 3>(a, s));  // 128 x  96
-        case 72: return conv_ran(ran, 72, "tap16d", launch_t16d<2, 2, 4, 2>(a, s));  // 128 x  64
+        case 46: return launch_t16d<2, 2, 2, 4>(a, s);  //  64 x 128
+        case 47: return launch_t16d<2, 2, 2, 3>(a, s);  //  64 x  96
+        case 49: return launch_t16d<4, 1, 2, 4>(a, s);  // 128 x  64
+        case 51: return launch_t16d<4, 1, 2, 2>(a, s);  // 128 x  32
+        case 60: return launch_t16d<4, 1, 2, 3>(a, s);  // 128 x  48
+        case 70: return launch_t16d<2, 2, 4, 4>(a, s);  // 128 x 128
+        case 71: return launch_t16d<2, 2, 4, 3>(a, s);  // 128 x  96
+        case 72: return launch_t16d<2, 2, 4, 2>(a, s);  // 128 x  64
     }
     return hipErrorNotSupported;
-}
-
-bool conv_tap16_variant_shape(int variant, int* bm, int* bn) {
-    static const int t[][3] = {{6, 64, 128}, {7, 64, 96}, {9, 128, 64}, {11, 128, 32}, {12, 128, 16}, {20, 128, 48},
-                               {30, 128, 128}, {31, 128, 96}, {32, 128, 64},
-                               {46, 64, 128}, {47, 64, 96}, {49, 128, 64}, {51, 128, 32}, {60, 128, 48}, {70, 128, 128}, {71, 128, 96}, {72, 128, 64}};
-    for (const auto& v : t)
-        if (v[0] == variant) { *bm = v[1]; *bn = v[2]; return true; }
-    return false;
-}
-
-// Tile choice: these kernels are issue- / HBM-bound, not MFMA-bound, so (a) the channel tile should cover all of
-// cout when it can (every extra channel tile re-reads the whole input from L2 / HBM), (b) bigger per-wave tiles
-// amortise the fixed per-k-step instruction cost, (c) the grid still has to fill 256 CUs.
-int choose_conv_tap16_variant(const ConvArgs& a) {
-    const int M = a.M, n16 = a.n16, ksize = a.ksize, cin = a.cin;
-    struct V { int id, bm, nf; float speed; bool dbl; };
-    // double-step tiles (ids + 40) win where K is a whole number of 64-channel steps and long enough to matter:
-    // 3x3 with cin % 64 == 0 (yolov8m 192 -> 192 / 304: 684-696 vs 626 TFLOP/s, profiles/conv_tap16_sweep_r2i.txt);
-    // with a 32-channel tail or on the short-K 1x1 layers the single-step tiles stay ahead
-    static const V vs[] = {{30, 128, 8, 1.30f, false}, {31, 128, 6, 1.25f, false}, {32, 128, 4, 1.10f, false}, {6, 64, 8, 1.05f, false},
-                           {7, 64, 6, 1.00f, false},   {9, 128, 4, 1.00f, false},  {20, 128, 3, 0.95f, false}, {11, 128, 2, 0.85f, false},
-                           {12, 128, 1, 0.60f, false}, {49, 128, 4, 1.40f, true},  {72, 128, 4, 1.40f, true}};
-    const bool dbl_ok = ksize == 3 && (cin & 63) == 0 && cin >= 128;
-    float best = -1.f;
-    int bv = 7;
-    for (const V& v : vs) {
-        if (v.dbl && !dbl_ok) continue;
-        const int ntiles = (n16 + v.nf - 1) / v.nf;
-        const long long mtiles = (M + v.bm - 1) / v.bm;
-        const float fill = (float)n16 / (float)(ntiles * v.nf) * (float)M / (float)(mtiles * v.bm);
-        const long long blocks = mtiles * ntiles;
-        const long long per_cu = (blocks + 255) / 256;
-        const float occ = (float)blocks / (256.f * (float)per_cu);
-        const float reread = 1.0f / (1.0f + 0.25f * (float)(ntiles - 1));        // input re-read per extra channel tile
-        const float sc = v.speed * fill * occ * (v.dbl ? 1.0f : reread);
-        if (sc > best) { best = sc; bv = v.id; }
-    }
-    // stride-1 3x3: the patch kernel (conv_patch16.hip) fetches the input once per chunk instead of once per tap:
-    // 806 vs 662 TFLOP/s on 192 -> 192, 875 vs 674 on the 256-channel heads, 558 vs 461 on 48(64) -> 64, about even on
-    // the short-K 96 -> 96 layers (profiles/conv_tap16_sweep_r2x_patch.txt) — hence the K-length factor
-    if (conv_p16_supported(a)) {
-        struct P { int nf; float sp; };
-        static const P ps[] = {{4, 1.70f}, {3, 1.55f}, {6, 1.45f}};
-        const int nch = cin >> 5;
-        const long long patches = (long long)(M / (a.Ho * a.Wo)) * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
-        for (const P& v : ps) {
-            const int ntiles = (n16 + v.nf - 1) / v.nf;
-            const float fill = (float)n16 / (float)(ntiles * v.nf) * (float)M / (float)(patches * 128);
-            const long long blocks = patches * ntiles;
-            const long long per_cu = (blocks + 255) / 256;
-            const float sc = v.sp * (float)nch / (float)(nch + 1) * fill * (float)blocks / (256.f * (float)per_cu);
-            if (sc > best) { best = sc; bv = 300 + v.nf; }
-        }
-        // the quad kernel (16 x 16 pixels x 96 channels per workgroup): 749-770 vs 656-682 TFLOP/s on 96 -> 96, 885 vs 857 on
-        // 192 -> 192; behind on partial channel tiles and on maps that do not fill 16-row tiles (profiles/r3s_sweep_p16q.txt)
-        {
-            const long long qpatches = (long long)(M / (a.Ho * a.Wo)) * ((a.Ho + 15) / 16) * ((a.Wo + 15) / 16);
-            const int ntiles = (n16 + 5) / 6;
-            const float fill = (float)n16 / (float)(ntiles * 6) * (float)M / (float)(qpatches * 256);
-            const long long blocks = qpatches * ntiles;
-            const long long per_cu = (blocks + 255) / 256;
-            const float sc = 1.78f * (float)nch / (float)(nch + 1) * fill * (float)blocks / (256.f * (float)per_cu);
-            if (sc > best) { best = sc; bv = 326; }
-        }
-    }
-    return bv;
 }
 
 }  // namespace padel

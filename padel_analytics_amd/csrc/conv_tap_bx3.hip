@@ -432,7 +432,6 @@ static hipError_t launch_b3(const ConvArgs& a_in, hipStream_t s) {
     a.n_ntiles = (a.n16 + WN * NF - 1) / (WN * NF);
     dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8) * (unsigned)a.n_ntiles, 1, 1);
     if (a.ksize == 3) hipLaunchKernelGGL((conv_bx3_kernel<WM, WN, MF, NF, NSTG, DBG>), grid, dim3(64 * WM * WN), 0, s, a);
-    else if (a.in2) return hipErrorNotSupported;                // absorbed upsample: launch_b3u tiles only
     else hipLaunchKernelGGL((conv_bx3_1_kernel<WM, WN, MF, NF, NSTG, false>), grid, dim3(64 * WM * WN), 0, s, a);
     return hipGetLastError();
 }
@@ -441,7 +440,6 @@ template <int WM, int WN, int MF, int NF>
 static hipError_t launch_b3u(const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a = a_in;
     constexpr int BM = WM * MF * 16;
-    if (a.ksize != 1 || a.stride != 1 || (a.up_c & 31) || a.up_c <= 0 || a.up_c > a.cin || ((a.H | a.W) & 1)) return hipErrorNotSupported;
     a.n_mtiles = (a.M + BM - 1) / BM;
     a.n_ntiles = (a.n16 + WN * NF - 1) / (WN * NF);
     dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8) * (unsigned)a.n_ntiles, 1, 1);
@@ -449,103 +447,46 @@ static hipError_t launch_b3u(const ConvArgs& a_in, hipStream_t s) {
     return hipGetLastError();
 }
 
-// tile ids of the fp32 id space (conv_variant_shape); the ring holds 2 BM + 3 BN rows per stage
-hipError_t launch_conv_bx3(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
-    if ((a.ksize != 3 && a.ksize != 1) || (a.cin & 15) || a.cin < 16 || !a.w3) return hipErrorNotSupported;
-    if (a.in2 && a.ksize == 3) {                                // absorbed upsample in front of a 3x3: the patch kernel only
-        if (variant < 300 || variant >= 400 || !conv_bx3p_supported(a)) return hipErrorNotSupported;
-        return conv_ran(ran, variant, "bx3p", launch_conv_bx3p(a, variant - 300, s));
-    }
+// the ring holds 2 BM + 3 BN rows per stage
+hipError_t launch_conv_bx3t(const ConvArgs& a, int tile, hipStream_t s) {
     if (a.in2) {                                                // absorbed upsample in front of a 1x1: the three tiles instantiated for it
-        if (a.ksize != 1) return hipErrorNotSupported;
-        if (variant == 209 || variant == 9 || variant == 304) return conv_ran(ran, 209, "bx3t", launch_b3u<4, 1, 2, 4>(a, s));
-        if (variant == 213 || variant == 13 || variant == 14 || variant == 306 || variant == 206 || variant == 6) return conv_ran(ran, 213, "bx3t", launch_b3u<4, 1, 2, 6>(a, s));
-        return conv_ran(ran, 220, "bx3t", launch_b3u<4, 1, 2, 3>(a, s));
+        switch (tile) {
+            case 209: return launch_b3u<4, 1, 2, 4>(a, s);
+            case 213: return launch_b3u<4, 1, 2, 6>(a, s);
+            case 220: return launch_b3u<4, 1, 2, 3>(a, s);
+        }
+        return hipErrorNotSupported;
     }
-    if (variant >= 300 && variant < 400) {                      // patch kernel, or its tap-kernel sibling where it does not apply
-        const int nf = variant - 300;
-        if (conv_bx3p_supported(a)) return conv_ran(ran, variant, "bx3p", launch_conv_bx3p(a, nf, s));
-        variant = nf == 3 ? 220 : nf == 4 ? 209 : 206;
-    }
-    switch (variant) {
-        case 7: return conv_ran(ran, 7, "bx3t", launch_b3<2, 2, 2, 3>(a, s));    //  64 x  96
-        case 6: return conv_ran(ran, 6, "bx3t", launch_b3<2, 2, 2, 4>(a, s));    //  64 x 128
-        case 9: return conv_ran(ran, 9, "bx3t", launch_b3<4, 1, 2, 4>(a, s));    // 128 x  64
-        case 20: return conv_ran(ran, 20, "bx3t", launch_b3<4, 1, 2, 3>(a, s));   // 128 x  48
-        case 11: return conv_ran(ran, 11, "bx3t", launch_b3<4, 1, 2, 2>(a, s));   // 128 x  32
-        case 12: return conv_ran(ran, 12, "bx3t", launch_b3<4, 1, 2, 1>(a, s));   // 128 x  16
-        case 13: return conv_ran(ran, 13, "bx3t", launch_b3<4, 2, 2, 3>(a, s));   // 128 x  96, 8 waves
-        case 14: return conv_ran(ran, 14, "bx3t", launch_b3<4, 2, 2, 4>(a, s));   // 128 x 128, 8 waves
+    switch (tile) {
+        case 7: return launch_b3<2, 2, 2, 3>(a, s);    //  64 x  96
+        case 6: return launch_b3<2, 2, 2, 4>(a, s);    //  64 x 128
+        case 9: return launch_b3<4, 1, 2, 4>(a, s);    // 128 x  64
+        case 20: return launch_b3<4, 1, 2, 3>(a, s);   // 128 x  48
+        case 11: return launch_b3<4, 1, 2, 2>(a, s);   // 128 x  32
+        case 12: return launch_b3<4, 1, 2, 1>(a, s);   // 128 x  16
+        case 13: return launch_b3<4, 2, 2, 3>(a, s);   // 128 x  96, 8 waves
+        case 14: return launch_b3<4, 2, 2, 4>(a, s);   // 128 x 128, 8 waves
         // + 200: 2-stage ring (prefetch distance 1, 3 workgroups per CU)
-        case 207: return conv_ran(ran, 207, "bx3t", launch_b3<2, 2, 2, 3, 2>(a, s));
-        case 220: return conv_ran(ran, 220, "bx3t", launch_b3<4, 1, 2, 3, 2>(a, s));
-        case 206: return conv_ran(ran, 206, "bx3t", launch_b3<2, 2, 2, 4, 2>(a, s));
-        case 209: return conv_ran(ran, 209, "bx3t", launch_b3<4, 1, 2, 4, 2>(a, s));
-        case 211: return conv_ran(ran, 211, "bx3t", launch_b3<4, 1, 2, 2, 2>(a, s));
-        case 225: return conv_ran(ran, 225, "bx3t", launch_b3<4, 1, 1, 5, 2>(a, s));
-        case 213: return conv_ran(ran, 213, "bx3t", launch_b3<4, 1, 2, 6, 2>(a, s));   // 128 x 96 with 4 waves (2 x 6 fragments each), 2 workgroups per CU
+        case 207: return launch_b3<2, 2, 2, 3, 2>(a, s);
+        case 220: return launch_b3<4, 1, 2, 3, 2>(a, s);
+        case 206: return launch_b3<2, 2, 2, 4, 2>(a, s);
+        case 209: return launch_b3<4, 1, 2, 4, 2>(a, s);
+        case 211: return launch_b3<4, 1, 2, 2, 2>(a, s);
+        case 225: return launch_b3<4, 1, 1, 5, 2>(a, s);
+        case 213: return launch_b3<4, 1, 2, 6, 2>(a, s);   // 128 x 96 with 4 waves (2 x 6 fragments each), 2 workgroups per CU
 #ifdef PADEL_BX3_PROBES      // ceiling probes of tile 220 (WRONG results; tools/conv_bench.py only), DBG bits: 1 no split VALU, 2 one of the 6 MFMA groups, 4 / 8 no activation / weight requests
-        case 420: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 1>(a, s) : hipErrorNotSupported;
-        case 520: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 2>(a, s) : hipErrorNotSupported;
-        case 620: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 3>(a, s) : hipErrorNotSupported;    // no split, 1 group: data movement only
-        case 720: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 4>(a, s) : hipErrorNotSupported;    // no activation requests
-        case 820: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 8>(a, s) : hipErrorNotSupported;    // no weight requests
-        case 920: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 12>(a, s) : hipErrorNotSupported;   // no requests at all
-        case 1020: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 13>(a, s) : hipErrorNotSupported;  // LDS reads + 6 MFMA groups + barriers only
-        case 1120: return a.ksize == 3 ? launch_b3<4, 1, 2, 3, 2, 5>(a, s) : hipErrorNotSupported;   // no split, no activation requests
+        case 420: return launch_b3<4, 1, 2, 3, 2, 1>(a, s);
+        case 520: return launch_b3<4, 1, 2, 3, 2, 2>(a, s);
+        case 620: return launch_b3<4, 1, 2, 3, 2, 3>(a, s);    // no split, 1 group: data movement only
+        case 720: return launch_b3<4, 1, 2, 3, 2, 4>(a, s);    // no activation requests
+        case 820: return launch_b3<4, 1, 2, 3, 2, 8>(a, s);    // no weight requests
+        case 920: return launch_b3<4, 1, 2, 3, 2, 12>(a, s);   // no requests at all
+        case 1020: return launch_b3<4, 1, 2, 3, 2, 13>(a, s);  // LDS reads + 6 MFMA groups + barriers only
+        case 1120: return launch_b3<4, 1, 2, 3, 2, 5>(a, s);   // no split, no activation requests
 #endif
-        case 25: return conv_ran(ran, 25, "bx3t", launch_b3<4, 1, 1, 5>(a, s));   //  64 x  80, 4 waves of 16 x 80: the 19-fragment (304-channel) fused pose heads
+        case 25: return launch_b3<4, 1, 1, 5>(a, s);   //  64 x  80, 4 waves of 16 x 80: the 19-fragment (304-channel) fused pose heads
     }
     return hipErrorNotSupported;
-}
-
-// Relative tile speeds measured on MI355X (profiles/conv_bx3_sweep_r2d.txt, ..._r2j.txt): 3x3 — 64x96 and 128x48 (4
-// waves, 2 workgroups per CU) lead at 173-189 TFLOP/s on the yolov8m bottlenecks, the 8-wave tiles follow at ~0.9;
-// 1x1 — since the channel tiles of a pixel tile run side by side on one XCD (the input is fetched from HBM once) the
-// same two tiles lead there too (147-169 on the wide C2f cv2 layers).  The rest is padding waste and the fill of the
-// last round of workgroups.
-int choose_conv_bx3_variant(const ConvArgs& a) {
-    const int M = a.M, n16 = a.n16, ksize = a.ksize;
-    struct V { int id, bm, nf; float s3, s1; };
-    // ids + 200 = the 2-stage ring: 51-53 KB of LDS instead of 77-80 -> 3 workgroups per CU, measured +5..12 % on every
-    // yolov8m 3x3 layer shape and +4..20 % on the 1x1 ones (profiles/conv_bx3_sweep_r2k.txt, ..._r2l.txt)
-    static const V vs[] = {{213, 128, 6, 1.07f, 1.08f},     // 128 x 96 with 4 waves of 2 x 6 fragments, 2 workgroups per CU (..._r2p.txt)
-                           {220, 128, 3, 1.00f, 1.00f}, {207, 64, 6, 0.98f, 0.95f}, {209, 128, 4, 1.00f, 1.00f}, {206, 64, 8, 0.90f, 0.70f},
-                           {211, 128, 2, 0.85f, 0.87f}, {225, 64, 5, 0.95f, 0.90f},
-                           {7, 64, 6, 0.93f, 0.84f},    {20, 128, 3, 0.93f, 0.87f}, {13, 128, 6, 0.85f, 0.82f}, {14, 128, 8, 0.83f, 0.85f},
-                           {25, 64, 5, 0.90f, 0.78f},
-                           {11, 128, 2, 0.80f, 0.61f},  {9, 128, 4, 0.65f, 0.70f},  {6, 64, 8, 0.50f, 0.49f},  {12, 128, 1, 0.45f, 0.26f}};
-    float best = -1.f;
-    int bv = 7;
-    for (const V& v : vs) {
-        const int ntiles = (n16 + v.nf - 1) / v.nf;
-        const long long mtiles = (M + v.bm - 1) / v.bm;
-        const float fill = (float)n16 / (float)(ntiles * v.nf) * (float)M / (float)(mtiles * v.bm);
-        const long long blocks = mtiles * ntiles;
-        const long long per_cu = (blocks + 255) / 256;
-        const float occ = (float)blocks / (256.f * (float)per_cu);
-        const float sp = ksize == 3 ? v.s3 : v.s1;
-        if (sp <= 0.0f) continue;
-        const float sc = sp * fill * occ;
-        if (sc > best) { best = sc; bv = v.id; }
-    }
-    // stride-1 3x3 layers with cin % 32 == 0: the patch kernel (conv_patch_bx3.hip) measured 1.18x (48-channel tiles,
-    // 3 workgroups per CU) / 1.15x (64-channel tiles) the best tap tile on full 8 x 16 patches
-    // (profiles/conv_bx3_sweep_r2n.txt); its fill counts the pixels of partial patches at the right / bottom edge
-    if (conv_bx3p_supported(a)) {
-        struct P { int nf; float sp; };
-        static const P ps[] = {{3, 1.17f}, {4, 1.14f}};
-        const long long patches = (long long)(M / (a.Ho * a.Wo)) * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
-        for (const P& v : ps) {
-            const int ntiles = (n16 + v.nf - 1) / v.nf;
-            const float fill = (float)n16 / (float)(ntiles * v.nf) * (float)M / (float)(patches * 128);
-            const long long blocks = patches * ntiles;
-            const long long per_cu = (blocks + 255) / 256;
-            const float sc = v.sp * fill * (float)blocks / (256.f * (float)per_cu);
-            if (sc > best) { best = sc; bv = 300 + v.nf; }
-        }
-    }
-    return bv;
 }
 
 }  // namespace padel

@@ -120,12 +120,10 @@ template <int WM, int WN, int MF, int NF>
 static hipError_t launch_h2t1p(const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a = a_in;
     constexpr int BM = WM * MF * 16;
-    if (a.ksize != 1) return hipErrorNotSupported;
     a.n_mtiles = (a.M + BM - 1) / BM;
     a.n_ntiles = (a.n16 + WN * NF - 1) / (WN * NF);
     dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8) * (unsigned)a.n_ntiles, 1, 1);
     if (a.in2) {
-        if (a.stride != 1 || (a.up_c & 31) || a.up_c <= 0 || a.up_c > a.cin || ((a.H | a.W) & 1)) return hipErrorNotSupported;
         if (a.w_single) hipLaunchKernelGGL((conv_h2_1p_kernel<WM, WN, MF, NF, true, true>), grid, dim3(64 * WM * WN), 0, s, a);
         else hipLaunchKernelGGL((conv_h2_1p_kernel<WM, WN, MF, NF, true>), grid, dim3(64 * WM * WN), 0, s, a);
     } else {
@@ -141,15 +139,13 @@ static hipError_t launch_h2t1p(const ConvArgs& a_in, hipStream_t s) {
 //  times, its activation requests hit the L2 and land inside a step already; removed again.)
 
 // tile ids = the 2-stage tile's id + 30 (243: 128 x 96, 239: 128 x 64)
-hipError_t launch_conv_h2_deep(const ConvArgs& a, int variant, hipStream_t s) {
-    if (a.ksize == 1) {
-        if (variant == 243) return launch_h2t1p<4, 1, 2, 6>(a, s);
-        if (variant == 239) return launch_h2t1p<4, 1, 2, 4>(a, s);
-        // (64 x 96 with the deep ring — 48 KB, three workgroups per CU — measured like its two-stage sibling 207: 10-18 % behind
-        //  128 x 96 on every 1x1 shape, profiles/r5o_tiles_237.txt; not kept)
-        // (128 x 96 as 2 x 2 waves of 4 x 3 fragments — 14 instead of 16 operand reads per 36 MFMAs — measured 1-2 % slower than
-        //  243's 4 x 1 waves of 2 x 6: profiles/r5h_tiles_1x1_wave_grid.txt; not kept)
-    }
+hipError_t launch_conv_h2d(const ConvArgs& a, int tile, hipStream_t s) {
+    if (tile == 243) return launch_h2t1p<4, 1, 2, 6>(a, s);
+    if (tile == 239) return launch_h2t1p<4, 1, 2, 4>(a, s);
+    // (64 x 96 with the deep ring — 48 KB, three workgroups per CU — measured like its two-stage sibling 207: 10-18 % behind
+    //  128 x 96 on every 1x1 shape, profiles/r5o_tiles_237.txt; not kept)
+    // (128 x 96 as 2 x 2 waves of 4 x 3 fragments — 14 instead of 16 operand reads per 36 MFMAs — measured 1-2 % slower than
+    //  243's 4 x 1 waves of 2 x 6: profiles/r5h_tiles_1x1_wave_grid.txt; not kept)
     return hipErrorNotSupported;
 }
 

@@ -381,7 +381,7 @@ static int validate_desc(pa_engine* e, const pa_model_desc* d, size_t n_floats) 
             if ((o.cin & kalign) || (o.in_choff & valign) || (o.ksize != 1 && o.ksize != 3) || (o.stride != 1 && o.stride != 2))
                 PA_FAIL(e, "op %d: unsupported conv (cin %d choff %d k %d s %d)", i, o.cin, o.in_choff, o.ksize, o.stride);
             if (o.npad < o.cout || (o.npad & 15)) PA_FAIL(e, "op %d: npad %d for cout %d", i, o.npad, o.cout);
-            const size_t ksteps3 = o.ksize == 3 ? (size_t)(o.cin / 32) * 9 + ((o.cin & 16) ? 5 : 0) : (size_t)(o.cin + 31) / 32;
+            const size_t ksteps3 = (size_t)h2_ksteps(o.cin, o.ksize);      // (the bf16x3 planes walk K in the same k-steps)
             const size_t wn = h2 ? (size_t)o.npad * ksteps3 * 32 : (size_t)o.npad * o.cin * o.ksize * o.ksize / (f16 ? 2 : 1);
             if (o.w_off < 0 || (o.w_off & 3) || (size_t)o.w_off + wn > n_floats || o.b_off < 0 ||
                 (size_t)o.b_off + o.npad > n_floats)
@@ -638,11 +638,12 @@ static hipError_t upload(pa_engine* e, int32_t** dptr, const std::vector<int32_t
 // live from before op 0, head buffers stay live past the last op (decode / NMS / pa_yolo_read_head read them).
 // Aliased bytes always hold finite fp32 activations, so a zero-weighted pad channel still contributes exactly 0.
 // nn.Upsample(scale_factor=2) + torch.cat is never materialised where the consumer allows it.  Upsample op j
-// (coarse slice S[so, so + c) -> fine slice X[xo, xo + c)) is absorbed by conv i when: i is a stride-1 conv with bf16x3
-// weights — 1x1 (YOLOv8's FPN joins) or 3x3 with cin % 32 == 0 (TrackNet's decoder blocks) — whose input slice starts
-// at X[xo] and covers the c channels (c % 32 == 0), nothing else reads those channels of X, and nothing overwrites the
-// source slice between j and i.  Whether the absorption is USED is decided per launch (fp32 model, impl bx3, tuning
-// fold_up, and for a 3x3 consumer the patch kernel being the tile chosen: conv_launch_args); the liveness plan keeps S
+// (coarse slice S[so, so + c) -> fine slice X[xo, xo + c)) is absorbed by conv i when: i is a stride-1 conv of an h2 model or
+// with bf16x3 weights — 1x1 (YOLOv8's FPN joins) or 3x3 with cin % 32 == 0 (TrackNet's decoder blocks) — whose input slice
+// starts at X[xo] and covers the c channels (c % 32 == 0), nothing else reads those channels of X, and nothing overwrites the
+// source slice between j and i.  Whether the absorption is USED is decided per launch in conv_launch_args (tuning fold_up; the
+// coarse map is attached and kept where resolve_conv names a kernel that reads it — the 1x1 tap tiles, and for a 3x3
+// consumer the patch kernel); the upsample op asks the same function, so both make one decision.  The liveness plan keeps S
 // alive until i either way.
 static void find_upsample_folds(pa_model* m) {
     const int nops = (int)m->ops.size();
@@ -850,11 +851,11 @@ static ProfRec* prof_begin(pa_model* m, size_t idx, int kind, int ksize, double 
 }
 static void prof_end(pa_model* m, ProfRec* r) { if (r) hipEventRecord(r->e1, m->e->stream); }
 
-// ConvArgs of conv op i for `n` images and the tile id it will be launched with (kernel choice: bf16x3 by default,
-// tap kernels / the LDS cross-check kernel by tuning, conv_tap16 for fp16 models; a forced variant picks the tile of
-// whichever kernel is selected).  An absorbed upsample (find_upsample_folds) is attached here: always for a 1x1
-// consumer, for a 3x3 consumer only when the tile chosen is the patch kernel's.
-static int conv_launch_args(const pa_model* m, size_t i, int n, ConvArgs& a) {
+// ConvArgs of conv op i for `n` images, its path (kernel choice: bf16x3 by default, tap kernels by tuning, conv_tap16 for fp16
+// models) and the tile id it will be requested with (a forced variant picks the tile of whichever path is selected).  An absorbed
+// upsample (find_upsample_folds) is attached here, where the requested tile resolves to a kernel that reads it: the 1x1 tap
+// tiles, and for a 3x3 consumer the patch kernel.
+static int conv_launch_args(const pa_model* m, size_t i, int n, ConvArgs& a, int* path_out = nullptr) {
     const pa_engine* e = m->e;
     const pa_op_desc& o = m->ops[i];
     const pa_buf_desc& ob = m->bufs[o.out_buf];
@@ -874,29 +875,26 @@ static int conv_launch_args(const pa_model* m, size_t i, int n, ConvArgs& a) {
     fill_fastdiv((unsigned)Wo, &a.wo_magic, &a.wo_shift);
     a.tune = e->t.tune; a.tap_pd = e->t.tap_pd;
     const bool f16 = m->d.dtype == PA_DTYPE_F16, h2 = m->d.dtype == PA_DTYPE_H2;
-    const bool use_tap = e->t.impl == 0 || f16;
     const bool use_bx3 = !f16 && !h2 && e->t.impl == 2 && o.reserved > 0;
     a.w3 = use_bx3 ? (const void*)(m->d_w + o.reserved) : nullptr;
     a.out_f32 = (f16 || h2) && (o.out_buf == m->d.head_buf[0] || o.out_buf == m->d.head_buf[1] || o.out_buf == m->d.head_buf[2]);
+    const int path = h2 ? CONV_PATH_H2 : f16 ? CONV_PATH_F16 : use_bx3 ? CONV_PATH_BX3 : CONV_PATH_TAP;
+    if (path_out) *path_out = path;
     if (h2) {
         a.oscale = m->d_w + o.reserved;
         a.ovf_flag = m->d_ovf;
         a.w_single = (o.flags & PA_CONV_W_SINGLE) && e->t.w_single ? 1 : 0;
         a.wr = (m->wr_valid && i < m->wr_off.size() && m->wr_off[i] >= 0) ? (const void*)(m->d_wr + m->wr_off[i]) : nullptr;
-        const int lv = e->t.variant >= 0 ? e->t.variant : choose_conv_h2_variant(a);
-        if (fold_active(m, (int)i) && (o.ksize == 1 || (lv >= 300 && lv < 400 && conv_h2p_supported(a)))) {
-            const pa_op_desc& u = m->ops[m->fold_src[i]];       // the first up_c channels come from the coarse map
-            a.in2 = m->bptr[u.in_buf]; a.in2_cs = m->bufs[u.in_buf].channels; a.in2_choff = u.in_choff; a.up_c = u.cin;
-        }
-        return lv;
     }
     const int lv = e->t.variant >= 0 ? e->t.variant
+                   : h2 ? choose_conv_h2_variant(a)
                    : f16 ? choose_conv_tap16_variant(a)
                    : use_bx3 ? choose_conv_bx3_variant(a)
                          : choose_conv_tap_variant(a.M, a.n16);
-    if (use_bx3 && fold_active(m, (int)i) && (o.ksize == 1 || (lv >= 300 && lv < 400 && conv_bx3p_supported(a)))) {
+    if ((h2 || use_bx3) && fold_active(m, (int)i)) {
         const pa_op_desc& u = m->ops[m->fold_src[i]];       // the first up_c channels come from the coarse map
         a.in2 = m->bptr[u.in_buf]; a.in2_cs = m->bufs[u.in_buf].channels; a.in2_choff = u.in_choff; a.up_c = u.cin;
+        if (!resolve_conv(path, a, lv, nullptr)) { a.in2 = nullptr; a.in2_cs = a.in2_choff = a.up_c = 0; }      // no kernel of this tile's chain reads it: the upsample runs
     }
     return lv;
 }
@@ -931,32 +929,21 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
         ProfRec* pr = nullptr;
         if (o.kind == PA_OP_CONV) {
             ConvArgs a{};
-            const int lv = conv_launch_args(m, i, n, a);
-            const bool f16 = m->d.dtype == PA_DTYPE_F16, h2 = m->d.dtype == PA_DTYPE_H2;
-            const bool use_tap = e->t.impl == 0 || f16;
-            const bool use_bx3 = a.w3 != nullptr;
+            int path = CONV_PATH_TAP;
+            const int lv = conv_launch_args(m, i, n, a, &path);
+            const bool f16 = path == CONV_PATH_F16, h2 = path == CONV_PATH_H2, use_bx3 = path == CONV_PATH_BX3;
             int bm = 0, bn = 0;
-            if (h2 && (lv == 323 || lv == 324)) { bm = 128; bn = 96; }
-            else if (h2 && lv == 325) { bm = 128; bn = 64; }
-            else if (h2 && lv == 244) { bm = 128; bn = 96; }
-            else if (h2 && (lv == 245 || lv == 246)) { bm = 128; bn = 192; }
-            else if (h2 && (lv == 247 || lv == 248)) { bm = 64; bn = 192; }
-            else if (h2 && lv >= 341 && lv <= 343) { bm = 256; bn = (lv - 340) * 16; }      // wide patch kernel: 16 x 16 pixels                       // quad patch kernel: 8 x 16 pixels x 96 channels
-            else if (h2 && (lv == 243 || lv == 239)) conv_variant_shape(lv - 230, &bm, &bn);      // deep-ring tap tiles: the shape of 213 / 209
-            else if ((f16 || h2) && lv >= 300) { bm = 128; bn = ((lv - 300) % 10) * 16; }
-            else if (f16) conv_tap16_variant_shape(lv, &bm, &bn);
-            else if (lv >= 300) { bm = 128; bn = (lv - 300) * 16; }          // patch kernel: 8 x 16 pixels x nf fragments
-            else conv_variant_shape(lv >= 200 ? lv - 200 : lv, &bm, &bn);   // profile rows carry BM, BN of the workgroup tile
+            conv_tile_shape(path, lv, &bm, &bn);            // profile rows carry BM, BN of the REQUESTED workgroup tile
             pr = prof_begin(m, (*pi)++, o.kind, o.ksize, 2.0 * a.M * (double)o.cout * o.cin * o.ksize * o.ksize);
             if (pr) { pr->M = a.M; pr->cout = o.cout; pr->cin = o.cin; pr->stride = o.stride; pr->mf = bm; pr->nf = bn; pr->res = a.res != nullptr; }
             // tuning only ("timeline"): collect the s_memtime timeline of this launch into timeline_path
             unsigned long long* dbg_dev = nullptr;
             size_t dbg_bytes = 0;
-            if (e->t.timeline && h2 && ((lv == 323 && conv_h2q_supported(a)) || (lv == 324 && conv_h2r_supported(a))) && !e->timeline_path.empty()) {
-                const size_t patches = (size_t)n * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);          // conv_patch_h2q.hip: one record per workgroup of its 1-D grid
-                dbg_bytes = 8 * ((patches + 7) / 8) * (size_t)((a.n16 + 5) / 6) * (8 + 4 * 32 * 5) * 8;          // kQDbgWords of conv_patch_h2q.hip (32-step ring)
-            } else if (e->t.timeline && !h2 && use_tap && lv == 7 && o.ksize == 3 && !e->timeline_path.empty()) {
-                dbg_bytes = (size_t)((a.M + 63) / 64) * ((o.npad + 95) / 96) * kConvDbgWords * 8;
+            ConvLaunched will{-1, ""};
+            if (e->t.timeline && !e->timeline_path.empty() && resolve_conv(path, a, lv, &will) && will.tile == lv) {
+                const size_t patches = (size_t)n * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);          // patch kernels: one record per workgroup of the 1-D grid
+                const size_t records = h2 ? 8 * ((patches + 7) / 8) * (size_t)((a.n16 + 5) / 6) : (size_t)((a.M + 63) / 64) * ((o.npad + 95) / 96);
+                dbg_bytes = records * conv_timeline_words(will, o.ksize) * 8;          // 0: this kernel has no timeline instantiation
             }
             if (dbg_bytes) {
                 if (hipMalloc(&dbg_dev, dbg_bytes) == hipSuccess) (void)hipMemsetAsync(dbg_dev, 0, dbg_bytes, s);
@@ -968,15 +955,7 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
             if (a.res_pre && !h2 && !use_bx3)
                 PA_FAIL(e, "op %zu: PA_CONV_RES_PREACT needs the h2 or the bf16x3 kernels (tuning impl = 2, bf16x3 weights in the blob), not the %s family",
                         i, f16 ? "fp16" : "fp32-MFMA tap");
-            if (h2) {
-                r = launch_conv_h2(a, lv, s, &ran);
-            } else if (f16) {
-                r = launch_conv_tap16(a, lv, s, &ran);
-            } else if (use_bx3) {
-                r = launch_conv_bx3(a, lv, s, &ran);
-            } else {
-                r = launch_conv_tap(a, lv, s, &ran);
-            }
+            r = launch_conv(path, a, lv, s, &ran);
             if (pr) { pr->tile = ran.tile; pr->family = ran.family; }
             if (dbg_dev) {
                 (void)hipStreamSynchronize(s);
@@ -1093,8 +1072,7 @@ static int ensure_operand_copies(pa_model* m) {
         for (size_t i = 0; i < m->ops.size(); ++i) {
             const pa_op_desc& o = m->ops[i];
             if (o.kind != PA_OP_CONV || !(o.flags & PA_CONV_W_SINGLE)) continue;
-            const long long ksteps = o.ksize == 3 ? (long long)(o.cin / 32) * 9 + ((o.cin & 16) ? 5 : 0) : (long long)(o.cin + 31) / 32 * o.ksize * o.ksize;
-            PA_HIP(e, launch_h2_mplane_check(m->d_w + o.w_off, (long long)o.npad * ksteps, m->d_ovf + 32, e->stream));
+            PA_HIP(e, launch_h2_mplane_check(m->d_w + o.w_off, (long long)o.npad * h2_ksteps(o.cin, o.ksize), m->d_ovf + 32, e->stream));
             any = true;
         }
         if (any) {
@@ -1105,26 +1083,19 @@ static int ensure_operand_copies(pa_model* m) {
         }
     }
     if (m->wr_off.empty()) {
-        m->wr_off.assign(m->ops.size(), -1);
+        std::vector<long long> off(m->ops.size(), -1);
         size_t total = 0;
         for (size_t i = 0; i < m->ops.size(); ++i) {
             const pa_op_desc& o = m->ops[i];
-            // conv_patch_h2r.hip: stride 1, whole chunks, at least two; conv_patch_h2v.hip: stride 1, 16 / 32 / 48 input channels;
-            // stem_l1_h2.hip: the stride-2 layer behind the stem (16 / 32 / 48 input channels)
-            // conv_1x1_h2s.hip: 1x1, stride 1, whole chunks, at least two
-            if (o.kind != PA_OP_CONV) continue;
-            const bool few = o.cin == 16 || o.cin == 32 || o.cin == 48;
-            const bool whole = o.stride == 1 && (o.cin & 31) == 0 && o.cin >= 64;
-            // conv_1x1_h2s.hip's stride-2 3x3 form: whole chunks, two products
-            const bool s2 = o.ksize == 3 && o.stride == 2 && (o.cin & 31) == 0 && o.cin >= 32 && (o.flags & PA_CONV_W_SINGLE);
-            if (!((o.ksize == 3 && (whole || few)) || s2 || (o.ksize == 1 && whole && (o.flags & PA_CONV_W_SINGLE)))) continue;
-            m->wr_off[i] = (long long)total;
+            if (o.kind != PA_OP_CONV || !conv_wants_operand_copy(o.ksize, o.stride, o.cin, (o.flags & PA_CONV_W_SINGLE) != 0)) continue;
+            off[i] = (long long)total;
             total += conv_h2r_copy_bytes(o.npad / 16, o.cin, o.ksize);
         }
         if (total) {
             PA_HIP(e, hipMalloc((void**)&m->d_wr, total + 8192));          // the last chunk's look-ahead reads run 4 KB past a fragment
             PA_HIP(e, hipMemsetAsync(m->d_wr + total, 0, 8192, e->stream));
         }
+        m->wr_off = std::move(off);        // only once the allocation stands: a failed call leaves no offsets into a null d_wr
     }
     for (size_t i = 0; i < m->ops.size(); ++i) {
         if (m->wr_off[i] < 0) continue;

@@ -55,67 +55,74 @@ inline void fill_fastdiv(unsigned d, unsigned* magic, unsigned* shift) {
     *magic = (unsigned)((((1ull << 32) * ((1ull << s) - d)) / d) + 1ull);
     *shift = s;
 }
-constexpr int kConvDbgSteps = 64;                       // k-steps kept per wave (ring)
-constexpr int kConvDbgWords = 8 + 4 * kConvDbgSteps * 5;   // u64 words per workgroup: header + 4 waves x steps x 5 stamps
+// tuning only ("timeline"): u64 words of one workgroup's s_memtime record — header + 4 waves x ring steps x 5 stamps
+constexpr int conv_dbg_words(int steps) { return 8 + 4 * steps * 5; }
+constexpr int kConvDbgSteps = 64;                       // k-steps kept per wave (ring): the fp32 tap kernel (conv_tap.hip)
+constexpr int kConvDbgWords = conv_dbg_words(kConvDbgSteps);
+constexpr int kPatchDbgSteps = 32;                      // ... the h2 quad patch kernels (conv_patch_h2q.hip, conv_patch_h2r.hip)
+constexpr int kPatchDbgWords = conv_dbg_words(kPatchDbgSteps);
 
+// ---- which kernel runs a conv (conv_select.cpp: host code only) -----------------------------------------------------
 // The implicit-GEMM conv on v_mfma_f32_16x16x4_f32 (strict fp32: the cross-check / no-argument leg) is the tap-unrolled LDS-DMA
 // ring of conv_tap.hip.  The register-staged LDS kernel of round 1 — its bitwise cross-check until round 5, 75-104 vs 109-124
 // TFLOP/s (profiles/r5e_f32_tap_vs_lds.txt) — and three more retired generations live in tools/legacy_conv/ and are not
-// built.  Tile variants of every family share one id space (conv_variant_shape).
-bool conv_variant_shape(int variant, int* bm, int* bn);                         // false: unknown id
-// What a conv dispatcher (launch_conv_tap / _bx3 / _h2 / _tap16) launched: the tile id AFTER every fall-through (a tile that does
-// not cover the layer hands it to a sibling) and a tag for the kernel template family — tap | bx3t, bx3p | h2t (two-stage tap
-// ring), h2d (deep ring), h2s, h2s3, h2p, h2q, h2r, h2v, h2w | tap16, tap16d (64-channel k-steps), p16, p16q.  Filled on success
-// when the caller passes one (profile rows, pa_model_profile_text columns 12 / 13): one host-side store per launch.
+// built.  Every path has its own table of tile ids:
+//   CONV_PATH_TAP  fp32 MFMA tap kernels (conv_tap.hip): ids 6, 7, 9..15, 20
+//   CONV_PATH_BX3  fp32 on the bf16 matrix pipe, exact 3-way bf16 split, 6 products, fp32 accumulate (conv_tap_bx3.hip: the tap ids
+//                  (3-stage ring) and + 200 (2-stage ring); conv_patch_bx3.hip: 303 / 304 / 306, stride-1 3x3 as 8 x 16-pixel patches)
+//   CONV_PATH_H2   activations are fp16 PAIRS (x ~ h + m / 2048) in 16-channel groups of 64 bytes [h x 16 | m x 16], 4 bytes per
+//                  channel like fp32 (cs / choff count channels); weights `w` are the pre-split planes [Npad][k-step][h | m][32 fp16],
+//                  `oscale` the inverse row scales; three f16 MFMAs per operand pair (h2_common.h)
+//   CONV_PATH_F16  in / w / res / out are _Float16 arrays behind the float pointers of ConvArgs (cs and choff count elements);
+//                  cin % 32 == 0; weights packed [Npad][Ktot] with K order (64-channel chunk, tap, 32-channel half)
+enum ConvPath : int { CONV_PATH_TAP = 0, CONV_PATH_BX3 = 1, CONV_PATH_H2 = 2, CONV_PATH_F16 = 3 };
+// workgroup tile of an id: bm output pixels (a patch tile's rows x cols) x bn channels; false: not a tile of this path
+bool conv_tile_shape(int path, int id, int* bm, int* bn);
+// What a requested tile id runs as on a layer: the tile id AFTER every fall-through (a tile that does not cover the layer hands it
+// to a sibling) and a tag for the kernel template family — tap | bx3t, bx3p | h2t (two-stage tap ring), h2d (deep ring), h2s,
+// h2s3, h2p, h2q, h2r, h2v, h2w | tap16, tap16d (64-channel k-steps), p16, p16q (profile rows, pa_model_profile_text columns 12 / 13)
 struct ConvLaunched { int tile; const char* family; };
-inline hipError_t conv_ran(ConvLaunched* ran, int tile, const char* family, hipError_t e) {
-    if (ran && e == hipSuccess) { ran->tile = tile; ran->family = family; }
-    return e;
-}
+enum ConvFamily : int { CONV_TAP, CONV_BX3T, CONV_BX3P, CONV_H2T, CONV_H2D, CONV_H2S, CONV_H2S3, CONV_H2P, CONV_H2Q, CONV_H2R, CONV_H2W, CONV_H2V,
+                        CONV_TAP16, CONV_TAP16D, CONV_P16, CONV_P16Q };      // the tags above, in this order (conv_family_name)
+const char* conv_family_name(ConvFamily f);
+// false: the layer or the tile is not covered.  With a.in2 set (an absorbed nn.Upsample(2); h2 and bf16x3) only kernels that read it resolve.
+bool resolve_conv(int path, const ConvArgs& a, int requested, ConvLaunched* out, ConvFamily* family = nullptr);
+int conv_timeline_words(const ConvLaunched& k, int ksize);      // u64 words per record of the timeline instantiation of kernel `k` on a ksize layer; 0: it has none
+// resolve_conv, then the launcher of the family it names (conv_tap.hip); hipErrorNotSupported: not resolved.  `ran` is filled on
+// success when the caller passes one: one host-side store per launch
+hipError_t launch_conv(int path, const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran = nullptr);
 // conv_tap.hip reads up to 128 B past the last chunk of a pixel / weight row, so every buffer a conv reads is
-// allocated with kConvReadSlack extra bytes; hipErrorNotSupported when the layer or the tile is not covered
-hipError_t launch_conv_tap(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran = nullptr);      // ids 6,7,9..15,20
+// allocated with kConvReadSlack extra bytes
 constexpr size_t kConvReadSlack = 512;
+// per-layer tile choice (no a.in2: the engine attaches an absorbed upsample after the choice)
 int choose_conv_tap_variant(int M, int n16);
-// fp32 convolutions on the bf16 matrix pipe (conv_tap_bx3.hip): exact 3-way bf16 split, 6 products, fp32 accumulate
-hipError_t launch_conv_bx3(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran = nullptr);      // ids 6,7,9,11,12,13,14,20,25 (3-stage ring), 206..225 (2-stage), 303/304/306 (patch kernel)
-int choose_conv_bx3_variant(const ConvArgs& a);      // per-layer tile heuristic (ids + 200: 2-stage ring, 30x: patch kernel)
-// stride-1 3x3, cin % 32 == 0: 8 x 16-pixel patch kernel (conv_patch_bx3.hip), the input patch is split once per chunk;
-// nf = channel fragments per workgroup (3, 4, 6); reached through launch_conv_bx3 ids 303 / 304 / 306
-bool conv_bx3p_supported(const ConvArgs& a);
-hipError_t launch_conv_bx3p(const ConvArgs& a, int nf, hipStream_t s);
-// h2 path (conv_tap_h2.hip, conv_patch_h2.hip; h2_common.h): activations are fp16 PAIRS (x ~ h + m / 2048) in 16-channel
-// groups of 64 bytes [h x 16 | m x 16], 4 bytes per channel like fp32 (cs / choff count channels); weights `w` are the
-// pre-split planes [Npad][k-step][h | m][32 fp16], `oscale` the inverse row scales; three f16 MFMAs per operand pair
-hipError_t launch_conv_h2(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran = nullptr);        // tap tiles 207..225, patch tiles 303 / 304 / 306
+int choose_conv_bx3_variant(const ConvArgs& a);
 int choose_conv_h2_variant(const ConvArgs& a);
-bool conv_h2p_supported(const ConvArgs& a);
-hipError_t launch_conv_h2p(const ConvArgs& a, int nf, hipStream_t s);
-bool conv_h2q_supported(const ConvArgs& a);            // conv_patch_h2q.hip: stride-1 3x3, cin % 32 == 0, no absorbed upsample
-hipError_t launch_conv_h2q(const ConvArgs& a, hipStream_t s);
-bool conv_h2r_supported(const ConvArgs& a);            // conv_patch_h2r.hip (round 6): the quad tile with the weights global -> registers, one barrier per chunk; PA_CONV_W_SINGLE layers only
-hipError_t launch_conv_h2r(const ConvArgs& a, int nf, hipStream_t s);      // nf 3: tile 324 (96 channels, two products), nf 2: tile 325 (64 channels, two or three products)
+int choose_conv_tap16_variant(const ConvArgs& a);
+// h2: does some kernel read this conv's weights in MFMA operand order (ConvArgs::wr)?  w_single: the op's PA_CONV_W_SINGLE flag
+bool conv_wants_operand_copy(int ksize, int stride, int cin, bool w_single);
+int h2_ksteps(int cin, int ksize);                                // k-steps (128-byte [h | m] records per weight row) of a layer in the packed h2 blob
 size_t conv_h2r_copy_bytes(int n16, int cin, int ksize);          // bytes of the operand-order copy of one conv's weights (both planes)
+
+// One launcher per family: launches exactly `tile` (an id of the family's rows in the table) — no fall-through.  A
+// hipErrorNotSupported for a tile resolve_conv named is a bug, not a refusal.
+hipError_t launch_conv_tapt(const ConvArgs& a, int tile, hipStream_t s);       // conv_tap.hip
+hipError_t launch_conv_bx3t(const ConvArgs& a, int tile, hipStream_t s);       // conv_tap_bx3.hip (a.in2: tiles 209 / 213 / 220 only)
+hipError_t launch_conv_bx3p(const ConvArgs& a, int tile, hipStream_t s);       // conv_patch_bx3.hip
+hipError_t launch_conv_h2t(const ConvArgs& a, int tile, hipStream_t s);        // conv_tap_h2.hip
+hipError_t launch_conv_h2d(const ConvArgs& a, int tile, hipStream_t s);        // conv_tap_h2p.hip: 239, 243
+hipError_t launch_conv_h2s(const ConvArgs& a, int tile, hipStream_t s);        // conv_1x1_h2s.hip: 244 (4 waves), 245 (8 waves, one workgroup per CU), 247 (four waves)
+hipError_t launch_conv_h2s3(const ConvArgs& a, int tile, hipStream_t s);       // ... 246 (8 waves), 248 (four waves)
+hipError_t launch_conv_h2p(const ConvArgs& a, int tile, hipStream_t s);        // conv_patch_h2.hip: 303, 304, 313
+hipError_t launch_conv_h2q(const ConvArgs& a, int tile, hipStream_t s);        // conv_patch_h2q.hip: 323
+hipError_t launch_conv_h2r(const ConvArgs& a, int tile, hipStream_t s);        // conv_patch_h2r.hip: 324 (a wave 4 rows x 3 fragments), 325 (x 2)
+hipError_t launch_conv_h2w(const ConvArgs& a, int tile, hipStream_t s);        // conv_patch_h2w.hip: 341..343
+hipError_t launch_conv_h2v(const ConvArgs& a, int tile, hipStream_t s);        // conv_patch_h2v.hip: 341..343
+hipError_t launch_conv_t16(const ConvArgs& a, int tile, hipStream_t s);        // conv_tap16.hip: families tap16 and tap16d
+hipError_t launch_conv_p16(const ConvArgs& a, int tile, hipStream_t s);        // conv_patch16.hip: families p16 (30x) and p16q (32x)
 hipError_t launch_h2r_repack(const float* w, void* wr, int n16, int cin, int ksize, hipStream_t s);
-bool conv_h2s_supported(const ConvArgs& a);            // conv_1x1_h2s.hip (round 6): 1x1, two products, register weights, one barrier per two k-steps
-hipError_t launch_conv_h2s(const ConvArgs& a, bool nf12, hipStream_t s, bool m64 = false);
-bool conv_h2s3_supported(const ConvArgs& a);           // the same machine for stride-2 3x3 layers (tile 246: 128 x 192, two products, whole chunks)
-hipError_t launch_conv_h2s3(const ConvArgs& a, hipStream_t s, bool m64 = false);   // m64: 64 x 192 tiles of four waves (tile 248)      // tile 244: 128 x 96 (4 waves), 245: 128 x 192 (8 waves, one workgroup per CU)
 // *flag |= 1 when any m-plane bit of `rows_x_ksteps` packed 128-byte k-step records is set (the PA_CONV_W_SINGLE promise, checked once per model)
 hipError_t launch_h2_mplane_check(const float* w, long long rows_x_ksteps, unsigned* flag, hipStream_t s);
-hipError_t launch_conv_h2_deep(const ConvArgs& a, int variant, hipStream_t s);     // conv_tap_h2p.hip: tap tiles with a 3-stage activation ring (239, 243); hipErrorNotSupported where they do not apply
-bool conv_h2w_supported(const ConvArgs& a);            // conv_patch_h2w.hip: stride-1 3x3 with 16 / 32 / 48 input channels
-hipError_t launch_conv_h2w(const ConvArgs& a, int nf, hipStream_t s);
-bool conv_h2v_supported(const ConvArgs& a);            // conv_patch_h2v.hip (round 6): the wide patch tile with the weights global -> registers, one barrier per workgroup
-hipError_t launch_conv_h2v(const ConvArgs& a, int nf, hipStream_t s);
-// fp16 path (conv_tap16.hip): in / w / res / out are _Float16 arrays behind the float pointers of ConvArgs (cs and
-// choff count elements); cin % 32 == 0; weights packed [Npad][Ktot] with K order (64-channel chunk, tap, 32-channel half)
-hipError_t launch_conv_tap16(const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran = nullptr);
-int choose_conv_tap16_variant(const ConvArgs& a);
-bool conv_tap16_variant_shape(int variant, int* bm, int* bn);
-// fp16 stride-1 3x3 patch kernel (conv_patch16.hip), ids 303 / 304 / 306 of launch_conv_tap16
-bool conv_p16_supported(const ConvArgs& a);
-hipError_t launch_conv_p16(const ConvArgs& a, int nf, hipStream_t s);
 
 struct StemArgs {
     const uint8_t* in;    // net input u8 NHWC4 [B][H][W][4]

@@ -323,11 +323,14 @@ def test_h2_upsample_absorbed(gpu_engine, shape):
         m = E.Model(gpu_engine, g)
         m.set_max_batch(B)
         y = m.tracknet_infer(x)[..., :cout]
-        n_up = sum(1 for r in m.profile_rows() if r["kind"] == G.OP_UPSAMPLE2X)
+        rows = m.profile_rows()
+        n_up = sum(1 for r in rows if r["kind"] == G.OP_UPSAMPLE2X)
+        consumer.update([r for r in rows if r["kind"] == G.OP_CONV][-1])
         m.close()
         gpu_engine.set_profiling(False)
         return y, n_up
 
+    consumer = {}                 # profile row of the conv behind the upsample, of the latest run
     absorbing = (220, 209, 213, 207, 243, 239) if k == 1 else (303, 304)
     keeping = () if k == 1 else (220,)
     try:
@@ -340,6 +343,15 @@ def test_h2_upsample_absorbed(gpu_engine, shape):
                 assert float(np.abs(y - ref).max()) < 2e-6 * max(1.0, float(np.abs(ref).max()))
             else:
                 assert np.array_equal(y, ref), f"variant {v}: absorbed upsample differs (max {np.abs(y - ref).max():.3e})"
+        # the auto choice: made before the coarse map is attached, so a 3x3 consumer's quad tile (no kernel of which reads the
+        # coarse map) resolves to the patch kernel — the upsample is absorbed whatever the chooser picked
+        y, n_up = run(variant=-1, fold_up=1)
+        assert n_up == 0, f"auto choice: {n_up} upsample launches (consumer ran as {consumer['family']} {consumer['tile']})"
+        assert k == 1 or consumer["family"] == "h2p", consumer
+        if consumer["tile"] in H2_SINGLE_LEVEL:
+            assert float(np.abs(y - ref).max()) < 2e-6 * max(1.0, float(np.abs(ref).max()))
+        else:
+            assert np.array_equal(y, ref), f"auto choice ({consumer['family']} {consumer['tile']}): absorbed upsample differs (max {np.abs(y - ref).max():.3e})"
     finally:
         gpu_engine.set_tuning(variant=-1, fold_up=1)
 
