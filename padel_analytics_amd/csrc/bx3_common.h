@@ -1,44 +1,16 @@
 // Shared pieces of the bf16x3 convolution kernels (conv_tap_bx3.hip: implicit-GEMM tap kernels; conv_patch_bx3.hip: the
-// stride-1 3x3 patch kernel): buffer descriptors, LDS-DMA requests, the exact fp32 -> 3 x bf16 split and the fused
-// bias / activation / residual epilogue.
+// stride-1 3x3 patch kernel): the exact fp32 -> 3 x bf16 split and the fused bias / activation / residual epilogue.
+// (Buffer descriptors, LDS-DMA requests, waits: conv_prims.h, shared with every other conv family.)
 #pragma once
 #include "kernels.h"
+#include "conv_prims.h"
 #include <cmath>
-#include <cstdint>
 
 namespace padel {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 
 namespace {
-
-__device__ __forceinline__ i32x4 make_rsrc3(const void* base) {
-    const unsigned long long b = (unsigned long long)(uintptr_t)base;
-    i32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    r[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xFFFFu));
-    r[2] = (int)0x80000000u;
-    r[3] = 0x00020000;
-    return r;
-}
-constexpr unsigned kOOR3 = 0xFFFFFFF0u;
-
-template <int LDS_IMM>
-__device__ __forceinline__ void dma3(unsigned voff, i32x4 rsrc, unsigned soff, unsigned lds_wave) {
-    asm volatile("s_add_u32 m0, %[lb], %[imm]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[vo], %[rs], %[so] offen lds"
-                 :
-                 : [lb] "s"(lds_wave), [imm] "n"(LDS_IMM), [vo] "v"(voff), [rs] "s"(rsrc), [so] "s"(soff)
-                 : "memory", "scc");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm3() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ int fastdiv3(int n, unsigned magic, unsigned shift) {
-    return (int)((__umulhi((unsigned)n, magic) + (unsigned)n) >> shift);
-}
 
 // 8 fp32 values (x0 = channels 4q..4q+3 of sub-row 0, x1 = of sub-row 1) -> exact bf16 triples, packed 2 per dword
 __device__ __forceinline__ void split8(const f32x4 x0, const f32x4 x1, bf8& hi, bf8& mid, bf8& lo) {

@@ -26,10 +26,6 @@ namespace padel {
 
 namespace {
 
-__device__ __forceinline__ unsigned hs_off(int p, int q) { return (unsigned)(p * 64 + ((q ^ (((p >> 2) & 1) << 1)) << 4)); }
-
-typedef int hs_i32x4 __attribute__((ext_vector_type(4)));
-
 }  // namespace
 
 // WC = waves along the channels: 2 (128 x 96 tile, 4 waves, 2 workgroups per CU, 5-stage ring) or 4 (128 x 192 tile, 8 waves, ONE
@@ -78,10 +74,9 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
     // XCD-aware 1-D tile map: the channel tiles of one pixel tile are neighbours on one XCD (they share its activations in the L2)
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;
     const int bid = blockIdx.x;
-    const int q8 = nmt >> 3, r8 = nmt & 7, xcd = bid & 7, idx = bid >> 3;
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;
-    if (mloc >= q8 + (xcd < r8 ? 1 : 0)) return;
-    const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);
+    if (xcd_slot_padding(slot)) return;
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;
     const int m0 = mt * (64 * WR);
     const int f0 = nt * WC * NF;
     const int nch = a.cin >> 5;                   // k-steps
@@ -92,7 +87,7 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
     // The descriptor starts at the tile's first pixel and ends with the tensor: the M tail reads zeros.
     const long long pix_b = (long long)a.in_cs * 4;
     const char* const in0 = reinterpret_cast<const char*>(a.in + a.in_choff) + (long long)m0 * pix_b;
-    i32x4 rsrcA = make_rsrc3(in0);
+    i32x4 rsrcA = make_rsrc(in0);
     {
         const long long left = ((long long)a.M - m0) * pix_b;
         rsrcA[2] = (int)(left > 0x7FFFFFFFll ? 0x7FFFFFFFll : left);
@@ -105,7 +100,7 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
     unsigned voL[2];                              // PROBE 4: whole 128-byte records, 8 pixels per request (wrong LDS layout)
 #pragma unroll
     for (int k = 0; k < 2; ++k) voL[k] = (unsigned)((wave * 16 + 8 * k + (lane >> 3)) * (unsigned)pix_b) + (unsigned)(lane & 7) * 16u;
-    hs_i32x4 sink[2] = {};                        // PROBE 6: the activation requests as plain register loads (no LDS-DMA)
+    i32x4 sink[2] = {};                        // PROBE 6: the activation requests as plain register loads (no LDS-DMA)
     unsigned voQ[2];                              // PROBE 5: the tile's bytes in address order — 16 KB contiguous per k-step (wrong data)
 #pragma unroll
     for (int k = 0; k < 2; ++k) voQ[k] = (unsigned)(wave * 2048 + k * 1024 + lane * 16);
@@ -119,15 +114,15 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
         const unsigned lb_ = lpw + (unsigned)(SB_);                                                               \
         i32x4 rs_ = rsrcA;                                                                                        \
         if ((int)(K_) >= nch) rs_[2] = 0;                                                                         \
-        if constexpr (PROBE == 4) { dma3<0>(voL[0], rs_, so_, lb_); dma3<kSPlaneB>(voL[1], rs_, so_, lb_); }      \
+        if constexpr (PROBE == 4) { lds_dma<0>(voL[0], rs_, so_, lb_); lds_dma<kSPlaneB>(voL[1], rs_, so_, lb_); } \
         else if constexpr (PROBE == 6) {                                                                          \
             asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(sink[0]) : "v"(voA[0]), "s"(rs_), "s"(so_) : "memory"); \
             asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(sink[1]) : "v"(voA[0]), "s"(rs_), "s"(so_ + 32u) : "memory"); \
         }                                                                                                         \
-        else if constexpr (PROBE == 5) { dma3<0>(voQ[0], rs_, so_ * 128u, lb_); dma3<kSPlaneB>(voQ[1], rs_, so_ * 128u, lb_); } \
+        else if constexpr (PROBE == 5) { lds_dma<0>(voQ[0], rs_, so_ * 128u, lb_); lds_dma<kSPlaneB>(voQ[1], rs_, so_ * 128u, lb_); } \
         else {                                                                                                    \
-        dma3<0>(voA[0], rs_, so_, lb_); if constexpr (WC == 2) dma3<4096>(voA[1], rs_, so_, lb_);                 \
-        dma3<kSPlaneB>(voA[0], rs_, so_ + 32u, lb_); if constexpr (WC == 2) dma3<kSPlaneB + 4096>(voA[1], rs_, so_ + 32u, lb_); \
+        lds_dma<0>(voA[0], rs_, so_, lb_); if constexpr (WC == 2) lds_dma<4096>(voA[1], rs_, so_, lb_);           \
+        lds_dma<kSPlaneB>(voA[0], rs_, so_ + 32u, lb_); if constexpr (WC == 2) lds_dma<kSPlaneB + 4096>(voA[1], rs_, so_ + 32u, lb_); \
         }                                                                                                         \
     }
 
@@ -138,9 +133,9 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
         const int frag = min(f0 + NF * wc + j, a.n16 - 1);   // fragments beyond the matrix: any valid rows (never stored)
-        rsrcW[j] = make_rsrc3(reinterpret_cast<const char*>(a.wr) + (long long)frag * fragb);
+        rsrcW[j] = make_rsrc(reinterpret_cast<const char*>(a.wr) + (long long)frag * fragb);
     }
-    hs_i32x4 w[NSET][NF];
+    i32x4 w[NSET][NF];
     // (k-steps beyond the last read the next fragment's first k-steps, or the slack behind the copy — never multiplied)
 #define PADEL_HS_LOADW(SET_, K_)                                                                                  \
     if constexpr (PROBE != 2 && PROBE < 4 || PROBE == 7) {                                                        \
@@ -152,9 +147,9 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
 #define PADEL_HS_WAITW(SET_, N_)                                                                                  \
     asm volatile("s_waitcnt vmcnt(%3)" : "+v"(w[SET_][0]), "+v"(w[SET_][1]), "+v"(w[SET_][2]) : "n"(PROBE == 2 || (PROBE >= 4 && PROBE != 7) ? ((N_) == 0 ? 0 : (PADEL_HS_AWIN) * NA) : PROBE == 3 ? (N_) * NF / (NF + NA) : (N_)) : "memory")
 
-    // ---- operand reads: pixel fragment f of the wave = pixels 64 wr + 16 f + lr: hs_off's swizzle depends on lr only, everything
+    // ---- operand reads: pixel fragment f of the wave = pixels 64 wr + 16 f + lr: swz_off's swizzle depends on lr only, everything
     // else is the stage's offset (scalar, walks the ring) and an immediate
-    const unsigned abase = hs_off(64 * wr + lr, lq);
+    const unsigned abase = swz_off(64 * wr + lr, lq);
     f32x4 acc[MF][NF], part[MF][NF], cross[MF][NF];
 #pragma unroll
     for (int f = 0; f < MF; ++f)
@@ -269,10 +264,9 @@ __global__ void __launch_bounds__(256 * WR, 2) conv_h2s3_kernel(const ConvArgs a
 
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;
     const int bid = blockIdx.x;
-    const int q8 = nmt >> 3, r8 = nmt & 7, xcd = bid & 7, idx = bid >> 3;
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;
-    if (mloc >= q8 + (xcd < r8 ? 1 : 0)) return;
-    const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);
+    if (xcd_slot_padding(slot)) return;
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;
     const int m0 = mt * (64 * WR);
     const int f0 = nt * WC * NF;
     const int nch = a.cin >> 5;
@@ -283,12 +277,12 @@ __global__ void __launch_bounds__(256 * WR, 2) conv_h2s3_kernel(const ConvArgs a
     const long long pix_b = (long long)a.in_cs * 4;
     long long lin0;
     {
-        const int n = fastdiv3(m0, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(m0, a.howo_magic, a.howo_shift);
         const int rem = m0 - n * HoWo;
-        const int oy = fastdiv3(rem, a.wo_magic, a.wo_shift), ox = rem - oy * a.Wo;
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift), ox = rem - oy * a.Wo;
         lin0 = ((long long)n * a.H + (2 * oy - 1)) * a.W + (2 * ox - 1);
     }
-    const i32x4 rsrcA = make_rsrc3(reinterpret_cast<const char*>(a.in + a.in_choff) + lin0 * pix_b);
+    const i32x4 rsrcA = make_rsrc(reinterpret_cast<const char*>(a.in + a.in_choff) + lin0 * pix_b);
     const int p_q = (lane & 3) ^ (((lane >> 4) & 1) << 1);
     const unsigned p_piece = (unsigned)((p_q >> 1) * 64 + (p_q & 1) * 16);
     unsigned voA, vbits = 0;
@@ -296,9 +290,9 @@ __global__ void __launch_bounds__(256 * WR, 2) conv_h2s3_kernel(const ConvArgs a
         const int m = m0 + wave * 16 + (lane >> 2);
         const bool mv = m < a.M;
         const int mc = mv ? m : m0;
-        const int n = fastdiv3(mc, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(mc, a.howo_magic, a.howo_shift);
         const int rem = mc - n * HoWo;
-        const int oy = fastdiv3(rem, a.wo_magic, a.wo_shift), ox = rem - oy * a.Wo;
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift), ox = rem - oy * a.Wo;
         const int iy0 = 2 * oy - 1, ix0 = 2 * ox - 1;
         const long long lin = ((long long)n * a.H + iy0) * a.W + ix0;
         voA = (unsigned)((lin - lin0) * pix_b) + p_piece;
@@ -323,8 +317,8 @@ __global__ void __launch_bounds__(256 * WR, 2) conv_h2s3_kernel(const ConvArgs a
         const unsigned lb_ = lpw + (unsigned)(SB_);                                                               \
         i32x4 rs_ = rsrcA;                                                                                        \
         if ((int)(CH_) >= nch) rs_[2] = 0;                                                                        \
-        const unsigned vo_ = (vbits & need_) == need_ ? voA : kOOR3;                                              \
-        dma3<0>(vo_, rs_, so_, lb_); dma3<kSPlaneB>(vo_, rs_, so_ + 32u, lb_);                                    \
+        const unsigned vo_ = (vbits & need_) == need_ ? voA : kOOR;                                               \
+        lds_dma<0>(vo_, rs_, so_, lb_); lds_dma<kSPlaneB>(vo_, rs_, so_ + 32u, lb_);                              \
     } while (0)
 
     // ---- weights: a.wr = [fragment][k-step][h | m][lane][16 bytes], k-step = chunk * 9 + tap
@@ -334,9 +328,9 @@ __global__ void __launch_bounds__(256 * WR, 2) conv_h2s3_kernel(const ConvArgs a
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
         const int frag = min(f0 + NF * wc + j, a.n16 - 1);
-        rsrcW[j] = make_rsrc3(reinterpret_cast<const char*>(a.wr) + (long long)frag * fragb);
+        rsrcW[j] = make_rsrc(reinterpret_cast<const char*>(a.wr) + (long long)frag * fragb);
     }
-    hs_i32x4 w[3][NF];
+    i32x4 w[3][NF];
     unsigned s_kw = 0;                            // byte offset of the current chunk's first k-step inside a fragment
 #define PADEL_HS3_LOADW(SET_, TT_)                                                                                \
     do {                                                                                                          \
@@ -347,7 +341,7 @@ __global__ void __launch_bounds__(256 * WR, 2) conv_h2s3_kernel(const ConvArgs a
 #define PADEL_HS3_WAITW(SET_, N_)                                                                                 \
     asm volatile("s_waitcnt vmcnt(%3)" : "+v"(w[SET_][0]), "+v"(w[SET_][1]), "+v"(w[SET_][2]) : "n"(N_) : "memory")
 
-    const unsigned abase = hs_off(64 * wr + lr, lq);
+    const unsigned abase = swz_off(64 * wr + lr, lq);
     f32x4 acc[MF][NF], part[MF][NF], cross[MF][NF];
 #pragma unroll
     for (int f = 0; f < MF; ++f)

@@ -14,55 +14,30 @@
 // 32-channel tail block of 9 k-steps when cin % 64 == 32), fp32 accumulation, same epilogue (fp16 or fp32 output).
 // LDS: 2 x 12 KB patch + 2 x 3 x BN x 64 B: 48 KB for BN = 64 -> 3 workgroups per CU; 60 KB for BN = 96 -> 2.
 #include "kernels.h"
+#include "conv_prims.h"
 #include "act_fast.h"
 #include "f16_epilogue.h"
 #include <cmath>
-#include <cstdint>
 
 namespace padel {
 
 namespace {
 
-typedef float p16_f32x4 __attribute__((ext_vector_type(4)));
-typedef int p16_i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 p16_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 p16_h4 __attribute__((ext_vector_type(4)));
-
-constexpr int kPW16 = 18, kNPix16 = 180;
-constexpr int kPieces16 = kNPix16 * 4;          // 16-byte pieces of a 32-channel fp16 patch
+constexpr int kPieces16 = kPatchPix * 4;          // 16-byte pieces of a 32-channel fp16 patch
 constexpr int kPatch16B = 768 * 16;             // 3 passes of 256 lanes (the last 48 pieces are padding)
-constexpr unsigned kOOR16 = 0xFFFFFFF0u;
 
-__device__ __forceinline__ p16_i32x4 p16_rsrc(const void* base) {
-    const unsigned long long b = (unsigned long long)(uintptr_t)base;
-    p16_i32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    r[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xFFFFu));
-    r[2] = (int)0x80000000u;
-    r[3] = 0x00020000;
-    return r;
-}
-template <int LDS_IMM>
-__device__ __forceinline__ void p16_dma(unsigned voff, p16_i32x4 rsrc, unsigned soff, unsigned lds_wave) {
-    asm volatile("s_add_u32 m0, %[lb], %[imm]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[vo], %[rs], %[so] offen lds"
-                 :
-                 : [lb] "s"(lds_wave), [imm] "n"(LDS_IMM), [vo] "v"(voff), [rs] "s"(rsrc), [so] "s"(soff)
-                 : "memory", "scc");
-}
 // request k of a wave of the quad kernel: LDS span (wave + 3 k) -> immediate 3072 k on top of the wave's base
 template <int NF>
-__device__ __forceinline__ void q16_dma_k(int k, unsigned voff, p16_i32x4 rsrc, unsigned soff, unsigned lds_wave) {
+__device__ __forceinline__ void q16_dma_k(int k, unsigned voff, i32x4 rsrc, unsigned soff, unsigned lds_wave) {
     switch (k) {
-        case 0: p16_dma<0>(voff, rsrc, soff, lds_wave); break;
-        case 1: p16_dma<3072>(voff, rsrc, soff, lds_wave); break;
-        case 2: p16_dma<6144>(voff, rsrc, soff, lds_wave); break;
-        case 3: p16_dma<9216>(voff, rsrc, soff, lds_wave); break;
-        case 4: p16_dma<12288>(voff, rsrc, soff, lds_wave); break;
-        case 5: p16_dma<15360>(voff, rsrc, soff, lds_wave); break;
+        case 0: lds_dma<0>(voff, rsrc, soff, lds_wave); break;
+        case 1: lds_dma<3072>(voff, rsrc, soff, lds_wave); break;
+        case 2: lds_dma<6144>(voff, rsrc, soff, lds_wave); break;
+        case 3: lds_dma<9216>(voff, rsrc, soff, lds_wave); break;
+        case 4: lds_dma<12288>(voff, rsrc, soff, lds_wave); break;
+        case 5: lds_dma<15360>(voff, rsrc, soff, lds_wave); break;
     }
 }
-__device__ __forceinline__ void p16_wait_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ unsigned p16_off(int p, int q) { return (unsigned)(p * 64 + ((q ^ (((p >> 2) & 1) << 1)) << 4)); }
 // epilogue: f16_epilogue.h (shared with conv_tap16.hip)
 
 }  // namespace
@@ -82,18 +57,14 @@ __global__ void __launch_bounds__(256, NF <= 4 ? 3 : 2) conv_p16_kernel(const Co
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lq = lane >> 4;
 
-    // XCD-aware 1-D tile map (conv_patch_bx3.hip)
+    // XCD-aware 1-D tile map (conv_index.h)
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;
     const int bid = blockIdx.x;
-    const int q8 = nmt >> 3, r8 = nmt & 7, xcd = bid & 7, idx = bid >> 3;
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;
-    if (mloc >= q8 + (xcd < r8 ? 1 : 0)) return;
-    const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
-    const int txN = (a.Wo + 15) >> 4, tyN = (a.Ho + 7) >> 3;
-    const int tpi = tyN * txN;
-    const int n = mt / tpi, rt = mt - n * tpi;
-    const int ty = rt / txN, tx = rt - ty * txN;
-    const int y0 = ty * 8, x0 = tx * 16;
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);
+    if (xcd_slot_padding(slot)) return;
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;
+    const TileOrigin org = tile_origin<3, 4>(a.Ho, a.Wo, mt);
+    const int n = org.n, y0 = org.y0, x0 = org.x0;
     const int f0 = nt * NF;
 
     // ---- patch requests: piece i * 256 + tid fills physical slot (piece & 3) of patch pixel piece >> 2
@@ -103,12 +74,12 @@ __global__ void __launch_bounds__(256, NF <= 4 ? 3 : 2) conv_p16_kernel(const Co
         const int piece = i * 256 + tid;
         const int pp = piece >> 2;
         const int qq = (piece & 3) ^ (((pp >> 2) & 1) << 1);
-        const int py = pp / kPW16, px = pp - py * kPW16;
+        const int py = pp / kPatchW, px = pp - py * kPatchW;
         const bool ok = piece < kPieces16 && (unsigned)(y0 - 1 + py) < (unsigned)a.H && (unsigned)(x0 - 1 + px) < (unsigned)a.W;
-        voffP[i] = ok ? (unsigned)(((py * a.W + px) * a.in_cs + qq * 8) * 2) : kOOR16;
+        voffP[i] = ok ? (unsigned)(((py * a.W + px) * a.in_cs + qq * 8) * 2) : kOOR;
     }
     const _Float16* const in16 = reinterpret_cast<const _Float16*>(a.in);
-    const p16_i32x4 rsrcP = p16_rsrc(in16 + (((long long)n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * a.in_cs + a.in_choff);
+    const i32x4 rsrcP = make_rsrc(in16 + (((long long)n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * a.in_cs + a.in_choff);
 
     // ---- weights: fp16 rows of Ktot = 9 cin halves; k-step (32 channels of one tap) = 64 bytes
     const int nch = a.cin >> 5;                    // 32-channel chunks
@@ -123,7 +94,7 @@ __global__ void __launch_bounds__(256, NF <= 4 ? 3 : 2) conv_p16_kernel(const Co
         const int frag = min(f0 + (rr >> 4), a.n16 - 1);
         voffB[p] = (unsigned)(((frag - f0) * 16 + (rr & 15)) * rowb + sc * 16);
     }
-    const p16_i32x4 rsrcB = p16_rsrc(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
+    const i32x4 rsrcB = make_rsrc(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
     const bool b_last = BP > BFULL && (BFULL * 64 + wave * 16 < BN);
 
     const unsigned lds0 = (unsigned)(uintptr_t)lds + wave * 1024u;
@@ -134,21 +105,21 @@ __global__ void __launch_bounds__(256, NF <= 4 ? 3 : 2) conv_p16_kernel(const Co
     const int ld_off = lr * 16 + ((lq ^ ((4 - ((lr >> 2) & 3)) & 3)) << 2);
     const float* b_rd0 = lds + (2 * kPatch16B) / 4 + ld_off;
     const float* b_rd1 = b_rd0 + BSTAGE_B / 4;
-    const int rd_pix = 2 * wave * kPW16 + lr;
+    const int rd_pix = 2 * wave * kPatchW + lr;
 
-    p16_f32x4 acc[MF][NF];
+    f32x4 acc[MF][NF];
 #pragma unroll
     for (int f = 0; f < MF; ++f)
 #pragma unroll
-        for (int j = 0; j < NF; ++j) acc[f][j] = (p16_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NF; ++j) acc[f][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     // byte offset of k-step (chunk C_, tap T_) inside a weight row
 #define PADEL_P16_KS(C_, T_) ((unsigned)(((C_) >> 1) < nfull64 ? ((C_) >> 1) * 18 + (T_) * 2 + ((C_) & 1) : nfull64 * 18 + (T_)) * 64u)
 #define PADEL_P16_DMAB_TAP(LW_, TI_, SOFF_)                                                                       \
     do {                                                                                                          \
         const unsigned so_ = (SOFF_);                                                                             \
-        if constexpr (BFULL >= 1) p16_dma<(TI_) * BTAP_B>(voffB[0], rsrcB, so_, (LW_));                           \
-        if constexpr (BP > BFULL) { if (b_last) p16_dma<(TI_) * BTAP_B + BFULL * 4096>(voffB[BP - 1], rsrcB, so_, (LW_)); } \
+        if constexpr (BFULL >= 1) lds_dma<(TI_) * BTAP_B>(voffB[0], rsrcB, so_, (LW_));                           \
+        if constexpr (BP > BFULL) { if (b_last) lds_dma<(TI_) * BTAP_B + BFULL * 4096>(voffB[BP - 1], rsrcB, so_, (LW_)); } \
     } while (0)
     // weight stage S_ = kernel COLUMN S_ (taps (ky, kx) = (0..2, S_): rows of the weight matrix keep the row-major tap order of
     // the tap kernels, the walk is column-major like the quad kernel's below) of chunk C_ into ring stage LW_
@@ -161,15 +132,15 @@ __global__ void __launch_bounds__(256, NF <= 4 ? 3 : 2) conv_p16_kernel(const Co
 #define PADEL_P16_DMAP(LW_, C_)                                                                                   \
     do {                                                                                                          \
         const unsigned so_ = (unsigned)(C_) * 64u;                                                                \
-        p16_dma<0>(voffP[0], rsrcP, so_, (LW_));                                                                  \
-        p16_dma<4096>(voffP[1], rsrcP, so_, (LW_));                                                               \
-        p16_dma<8192>(voffP[2], rsrcP, so_, (LW_));                                                               \
+        lds_dma<0>(voffP[0], rsrcP, so_, (LW_));                                                                  \
+        lds_dma<4096>(voffP[1], rsrcP, so_, (LW_));                                                               \
+        lds_dma<8192>(voffP[2], rsrcP, so_, (LW_));                                                               \
     } while (0)
     // stage S_ of the current chunk: everything requested one stage earlier has landed for every wave after the barrier,
     // which also releases the other weight stage and (at S_ == 0) the other patch image
 #define PADEL_P16_STAGE(S_)                                                                                       \
     do {                                                                                                          \
-        p16_wait_all();                                                                                           \
+        wait_vm<0>();                                                                                             \
         __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
         const unsigned lwn_ = ((S_) & 1) ? lwB0 : lwB1;                                                           \
@@ -178,12 +149,12 @@ __global__ void __launch_bounds__(256, NF <= 4 ? 3 : 2) conv_p16_kernel(const Co
         if constexpr ((S_) == 0) { if (c + 1 < nch) PADEL_P16_DMAP(lwP1, c + 1); }                                \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         const float* const br_ = ((S_) & 1) ? b_rd1 : b_rd0;                                                      \
-        p16_h8 av[3][MF], bv[3][NF];                                                                              \
+        h16x8 av[3][MF], bv[3][NF];                                                                               \
         _Pragma("unroll") for (int t = 0; t < 3; ++t) {                                                           \
             _Pragma("unroll") for (int f = 0; f < MF; ++f)                                                        \
-                av[t][f] = *reinterpret_cast<const p16_h8*>(pA0 + p16_off(rd_pix + (f + t) * kPW16 + (S_), lq));  \
+                av[t][f] = *reinterpret_cast<const h16x8*>(pA0 + swz_off(rd_pix + (f + t) * kPatchW + (S_), lq)); \
             _Pragma("unroll") for (int j = 0; j < NF; ++j)                                                        \
-                bv[t][j] = __builtin_bit_cast(p16_h8, *reinterpret_cast<const p16_f32x4*>(br_ + t * (BTAP_B / 4) + j * 256)); \
+                bv[t][j] = __builtin_bit_cast(h16x8, *reinterpret_cast<const f32x4*>(br_ + t * (BTAP_B / 4) + j * 256)); \
         }                                                                                                         \
         __builtin_amdgcn_s_setprio(1);                                                                            \
         _Pragma("unroll") for (int t = 0; t < 3; ++t)                                                             \
@@ -202,7 +173,7 @@ __global__ void __launch_bounds__(256, NF <= 4 ? 3 : 2) conv_p16_kernel(const Co
         { const float* t_ = b_rd0; b_rd0 = b_rd1; b_rd1 = t_; unsigned u_ = lwB0; lwB0 = lwB1; lwB1 = u_;
           const char* p_ = pA0; pA0 = pA1; pA1 = p_; u_ = lwP0; lwP0 = lwP1; lwP1 = u_; }
     }
-    p16_wait_all();
+    wait_vm<0>();
 #undef PADEL_P16_STAGE
 #undef PADEL_P16_DMAP
 #undef PADEL_P16_DMAB
@@ -228,8 +199,7 @@ __global__ void __launch_bounds__(256, NF <= 4 ? 3 : 2) conv_p16_kernel(const Co
 // 18 x 18 patch is requested by wave 3 (a third per stage), the weights by waves 0..2: vmcnt is in-order per wave, so no
 // weight wait ever waits for patch data.  Same K walk (32-channel chunk, column, row) as the kernel above: bitwise equal.
 // LDS: 2 x 21 KB patch (324 pixels, padded to 21 spans of 16) + 2 stages x 3 taps x BN x 64 B: 78 KB for BN = 96.
-constexpr int kQ16PW = 18, kQ16NPix = 18 * 18;
-constexpr int kQ16Spans = (kQ16NPix + 15) / 16;          // 21
+constexpr int kQ16Spans = (kPatchSqPix + 15) / 16;          // 21
 constexpr int kQ16PatchB = kQ16Spans * 1024;
 
 template <int NF>
@@ -247,33 +217,29 @@ __global__ void __launch_bounds__(256, 2) conv_p16q_kernel(const ConvArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lq = lane >> 4;
 
-    // XCD-aware 1-D tile map (conv_patch_bx3.hip)
+    // XCD-aware 1-D tile map (conv_index.h)
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;
     const int bid = blockIdx.x;
-    const int q8 = nmt >> 3, r8 = nmt & 7, xcd = bid & 7, idx = bid >> 3;
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;
-    if (mloc >= q8 + (xcd < r8 ? 1 : 0)) return;
-    const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
-    const int txN = (a.Wo + 15) >> 4, tyN = (a.Ho + 15) >> 4;
-    const int tpi = tyN * txN;
-    const int n = mt / tpi, rt = mt - n * tpi;
-    const int ty = rt / txN, tx = rt - ty * txN;
-    const int y0 = ty * 16, x0 = tx * 16;
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);
+    if (xcd_slot_padding(slot)) return;
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;
+    const TileOrigin org = tile_origin<4, 4>(a.Ho, a.Wo, mt);
+    const int n = org.n, y0 = org.y0, x0 = org.x0;
     const int f0 = nt * NF;
 
     // ---- patch (wave 3): span s = 16 pixels x 64 bytes, lane i -> pixel 16 s + i / 4, physical slot i & 3 = logical chunk
     // (i & 3) ^ 2 ((p >> 2) & 1) of that pixel's 64 bytes
     const _Float16* const in16 = reinterpret_cast<const _Float16*>(a.in);
-    const p16_i32x4 rsrcP = p16_rsrc(in16 + (((long long)n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * a.in_cs + a.in_choff);
+    const i32x4 rsrcP = make_rsrc(in16 + (((long long)n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * a.in_cs + a.in_choff);
     const int p_lane = lane >> 2;
     const unsigned p_piece = (unsigned)(((lane & 3) ^ (((lane >> 4) & 1) << 1)) * 16);
     const unsigned lp0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds);
 #define PADEL_Q16_PSPAN(S_)                                                                                       \
     do {                                                                                                          \
         const int pp_ = (S_) * 16 + pl_;                                                                          \
-        const int py_ = pp_ / kQ16PW, px_ = pp_ - py_ * kQ16PW;                                                   \
-        const bool ok_ = pp_ < kQ16NPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
-        p16_dma<(S_) * 1024>(ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 2) + p_piece : kOOR16, rsrcP, so_, lb_); \
+        const int py_ = pp_ / kPatchW, px_ = pp_ - py_ * kPatchW;                                                 \
+        const bool ok_ = pp_ < kPatchSqPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
+        lds_dma<(S_) * 1024>(ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 2) + p_piece : kOOR, rsrcP, so_, lb_); \
     } while (0)
     // spans 7 G_ .. 7 G_ + 6 (a third) of the patch of chunk CH_ into buffer BUF_
 #define PADEL_Q16_PATCH(CH_, BUF_, G_)                                                                            \
@@ -303,7 +269,7 @@ __global__ void __launch_bounds__(256, 2) conv_p16q_kernel(const ConvArgs a) {
         const int frag = min(f0 + g, a.n16 - 1);
         voffB[k] = (unsigned)(((frag - f0) * 16 + b_row) * rowb + b_sc * 16);
     }
-    const p16_i32x4 rsrcB = p16_rsrc(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
+    const i32x4 rsrcB = make_rsrc(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
     unsigned lwB0 = __builtin_amdgcn_readfirstlane(lp0 + 2u * kQ16PatchB + (unsigned)min(wave, 2) * 1024u);
     unsigned lwB1 = __builtin_amdgcn_readfirstlane(lwB0 + (unsigned)BSTAGE_B);
     // byte offset of k-step (chunk C_, tap T_) inside a weight row (taps row-major in memory: T_ = 3 ky + kx)
@@ -316,13 +282,13 @@ __global__ void __launch_bounds__(256, 2) conv_p16q_kernel(const ConvArgs a) {
     const int ld_off = lr * 16 + ((lq ^ ((4 - ((lr >> 2) & 3)) & 3)) << 2);
     const float* b_rd0 = lds + (2 * kQ16PatchB) / 4 + ld_off;
     const float* b_rd1 = b_rd0 + BSTAGE_B / 4;
-    const int rd_pix = 4 * wave * kQ16PW + lr;              // patch pixel of the wave's row 0, kx = 0
+    const int rd_pix = 4 * wave * kPatchW + lr;              // patch pixel of the wave's row 0, kx = 0
 
-    p16_f32x4 acc[MF][NF];
+    f32x4 acc[MF][NF];
 #pragma unroll
     for (int f = 0; f < MF; ++f)
 #pragma unroll
-        for (int j = 0; j < NF; ++j) acc[f][j] = (p16_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < NF; ++j) acc[f][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     // stage S_ = kernel column S_ of the current chunk: everything requested one stage earlier has landed for every wave
     // after the barrier, which also releases the other weight stage and (at S_ == 0) the other patch buffer
@@ -330,19 +296,19 @@ __global__ void __launch_bounds__(256, 2) conv_p16q_kernel(const ConvArgs a) {
     do {                                                                                                          \
         int rp_ = rd_pix;                                  /* row addresses recomputed per stage */                \
         asm volatile("" : "+v"(rp_));                                                                             \
-        p16_h8 av[6], bv[2][NF];                           /* weights of the tap in flight / of the next tap */       \
+        h16x8 av[6], bv[2][NF];                           /* weights of the tap in flight / of the next tap */    \
         if constexpr ((S_) > 0) {                          /* the patch is static inside a chunk: read under the wait */ \
             _Pragma("unroll") for (int r = 0; r < 6; ++r)                                                         \
-                av[r] = *reinterpret_cast<const p16_h8*>(pbuf + p16_off(rp_ + r * kQ16PW + (S_), lq));            \
+                av[r] = *reinterpret_cast<const h16x8*>(pbuf + swz_off(rp_ + r * kPatchW + (S_), lq));            \
         }                                                                                                         \
-        if ((S_) == 0 || wave != 3) p16_wait_all();                                                               \
+        if ((S_) == 0 || wave != 3) wait_vm<0>();                                                                 \
         __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
         const float* const br_ = ((S_) & 1) ? b_rd1 : b_rd0;                                                      \
-        _Pragma("unroll") for (int j = 0; j < NF; ++j) bv[0][j] = __builtin_bit_cast(p16_h8, *reinterpret_cast<const p16_f32x4*>(br_ + j * 256)); \
+        _Pragma("unroll") for (int j = 0; j < NF; ++j) bv[0][j] = __builtin_bit_cast(h16x8, *reinterpret_cast<const f32x4*>(br_ + j * 256)); \
         if constexpr ((S_) == 0) {                                                                                \
             _Pragma("unroll") for (int r = 0; r < 6; ++r)                                                         \
-                av[r] = *reinterpret_cast<const p16_h8*>(pbuf + p16_off(rp_ + r * kQ16PW, lq));                   \
+                av[r] = *reinterpret_cast<const h16x8*>(pbuf + swz_off(rp_ + r * kPatchW, lq));                   \
         }                                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         const unsigned lwn_ = ((S_) & 1) ? lwB0 : lwB1;                                                           \
@@ -357,7 +323,7 @@ __global__ void __launch_bounds__(256, 2) conv_p16q_kernel(const ConvArgs a) {
         _Pragma("unroll") for (int t = 0; t < 3; ++t) {                                                           \
             if (t < 2) {                                   /* next tap's weights under this tap's MFMAs */           \
                 _Pragma("unroll") for (int j = 0; j < NF; ++j)                                                    \
-                    bv[(t + 1) & 1][j] = __builtin_bit_cast(p16_h8, *reinterpret_cast<const p16_f32x4*>(br_ + (t + 1) * (BTAP_B / 4) + j * 256)); \
+                    bv[(t + 1) & 1][j] = __builtin_bit_cast(h16x8, *reinterpret_cast<const f32x4*>(br_ + (t + 1) * (BTAP_B / 4) + j * 256)); \
             }                                                                                                     \
             _Pragma("unroll") for (int f = 0; f < MF; ++f)                                                        \
                 _Pragma("unroll") for (int j = 0; j < NF; ++j)                                                    \
@@ -375,7 +341,7 @@ __global__ void __launch_bounds__(256, 2) conv_p16q_kernel(const ConvArgs a) {
         // 3 stages per chunk: the weight stages swap roles
         { const float* t_ = b_rd0; b_rd0 = b_rd1; b_rd1 = t_; const unsigned u_ = lwB0; lwB0 = lwB1; lwB1 = u_; }
     }
-    p16_wait_all();
+    wait_vm<0>();
 #undef PADEL_Q16_STAGE
 #undef PADEL_Q16_DMAB
 #undef PADEL_Q16_KS

@@ -25,18 +25,9 @@ namespace padel {
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kPW = 18;                       // patch width in pixels (16 + halo)
-constexpr int kNPix = 180;                    // 10 x 18
-constexpr int kPlaneB = kNPix * 64;           // one bf16 plane of a 32-channel chunk
-constexpr int kPatchB = 3 * kPlaneB;
-constexpr int kItems = kNPix * 8;             // 16-byte (4-channel) pieces of the fp32 patch
+constexpr int kPatchB = 3 * kPatchPlaneB;
+constexpr int kItems = kPatchPix * 8;             // 16-byte (4-channel) pieces of the fp32 patch
 constexpr int kPasses = (kItems + 255) / 256; // 6
-
-// byte offset, inside a plane, of logical 16-byte chunk q (K slots 8q..8q+7) of patch pixel p
-__device__ __forceinline__ unsigned patch_off(int p, int q) { return (unsigned)(p * 64 + ((q ^ (((p >> 2) & 1) << 1)) << 4)); }
 
 // 4 fp32 -> exact bf16 triples, 2 per dword (same arithmetic as split8)
 __device__ __forceinline__ void split4(const u32x4 x, u32x2& hi, u32x2& mid, u32x2& lo) {
@@ -53,11 +44,9 @@ __device__ __forceinline__ void split4(const u32x4 x, u32x2& hi, u32x2& mid, u32
     }
 }
 
-// tail planes: 32 bytes per pixel, 8-byte slot q (4 channels)
-__device__ __forceinline__ unsigned tail_off(int p, int q) { return (unsigned)(p * 32 + ((q ^ (((p >> 3) & 1) << 1)) << 3)); }
-constexpr int kTailPasses = (kNPix * 4 + 255) / 256;     // 3
-
-__device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// tail planes: 32 bytes per pixel, 8-byte slot q (4 channels) — four 8-byte slots, not the two 16-byte ones of swz_tail_off (conv_index.h)
+__device__ __forceinline__ unsigned bx3_tail_off(int p, int q) { return (unsigned)(p * 32 + ((q ^ (((p >> 3) & 1) << 1)) << 3)); }
+constexpr int kTailPasses = (kPatchPix * 4 + 255) / 256;     // 3
 
 }  // namespace
 
@@ -81,18 +70,14 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lq = lane >> 4;
 
-    // XCD-aware 1-D tile map (see PADEL_BX3_GEOMETRY): the channel tiles of one pixel patch are neighbours on one XCD
+    // XCD-aware 1-D tile map (conv_index.h): the channel tiles of one pixel patch are neighbours on one XCD
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;
     const int bid = blockIdx.x;
-    const int q8 = nmt >> 3, r8 = nmt & 7, xcd = bid & 7, idx = bid >> 3;
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;
-    if (mloc >= q8 + (xcd < r8 ? 1 : 0)) return;
-    const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
-    const int txN = (a.Wo + 15) >> 4, tyN = (a.Ho + 7) >> 3;
-    const int tpi = tyN * txN;
-    const int n = mt / tpi, rt = mt - n * tpi;
-    const int ty = rt / txN, tx = rt - ty * txN;
-    const int y0 = ty * 8, x0 = tx * 16;
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);
+    if (xcd_slot_padding(slot)) return;
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;
+    const TileOrigin org = tile_origin<3, 4>(a.Ho, a.Wo, mt);
+    const int n = org.n, y0 = org.y0, x0 = org.x0;
     const int f0 = nt * NF;
 
     // ---- the fp32 patch: piece i * 256 + tid = (pixel, 4-channel group); lane offsets are chunk-independent
@@ -101,19 +86,19 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
     for (int i = 0; i < kPasses; ++i) {
         const int item = i * 256 + tid;
         const int pp = item >> 3, c4 = item & 7;
-        const int py = pp / kPW, px = pp - py * kPW;
+        const int py = pp / kPatchW, px = pp - py * kPatchW;
         const int iy = y0 - 1 + py, ix = x0 - 1 + px;
         const bool ok = item < kItems && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        voffP[i] = ok ? (unsigned)(((py * a.W + px) * a.in_cs + c4 * 4) * 4) : kOOR3;
-        wrP[i] = patch_off(pp, c4 & 3) + (unsigned)((c4 >> 2) * 8);       // channels [0,16) of the chunk: K slots 0-3 of a lane, [16,32): 4-7
+        voffP[i] = ok ? (unsigned)(((py * a.W + px) * a.in_cs + c4 * 4) * 4) : kOOR;
+        wrP[i] = swz_off(pp, c4 & 3) + (unsigned)((c4 >> 2) * 8);       // channels [0,16) of the chunk: K slots 0-3 of a lane, [16,32): 4-7
     }
     const float* const in0 = a.in + (((long long)n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * a.in_cs + a.in_choff;
-    const __amdgpu_buffer_rsrc_t rsrcP = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in0), 0, (int)0x80000000u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcP = make_buffer_rsrc(in0);
     // coarse map of an absorbed upsample: descriptor based at the coarse pixel of the patch's top-left halo pixel
     const int H2 = a.H >> 1, W2 = a.W >> 1;
     const int cy0 = (y0 - 1) >> 1, cx0 = (x0 - 1) >> 1;                 // arithmetic shifts: -1 for the halo above / left of the image
     const float* const inU = UP ? a.in2 + (((long long)n * H2 + cy0) * W2 + cx0) * a.in2_cs + a.in2_choff : in0;
-    const __amdgpu_buffer_rsrc_t rsrcU = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(inU), 0, (int)0x80000000u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcU = make_buffer_rsrc(inU);
     const int nup = UP ? a.up_c >> 5 : 0;
     (void)H2; (void)W2; (void)cy0; (void)cx0; (void)rsrcU; (void)nup;
 
@@ -129,14 +114,14 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
         const int frag = min(f0 + (rr >> 4), a.n16 - 1);
         voffB[p] = (unsigned)(((frag - f0) * 16 + (rr & 15)) * rowb + sc * 16);
     }
-    const i32x4 rsrcB = make_rsrc3(reinterpret_cast<const char*>(a.w3) + (long long)f0 * 16 * rowb);
+    const i32x4 rsrcB = make_rsrc(reinterpret_cast<const char*>(a.w3) + (long long)f0 * 16 * rowb);
     const bool b_last = BP > BFULL && (BFULL * 64 + wave * 16 < BN);
     unsigned lw0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds + (unsigned)kPatchB + wave * 1024u);
     unsigned lw1 = __builtin_amdgcn_readfirstlane(lw0 + (unsigned)BSTAGE_B);
     const int ld_off = lr * 16 + ((lq ^ ((4 - ((lr >> 2) & 3)) & 3)) << 2);
     const float* b_rd0 = lds + kPatchB / 4 + ld_off;
     const float* b_rd1 = b_rd0 + BSTAGE_B / 4;
-    const int rd_pix = 2 * wave * kPW + lr;                 // patch pixel of fragment 0, tap (0, 0)
+    const int rd_pix = 2 * wave * kPatchW + lr;                 // patch pixel of fragment 0, tap (0, 0)
 
     f32x4 acc[MF][NF], part[MF][NF];
 #pragma unroll
@@ -154,8 +139,8 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
     } while (0)
 #define PADEL_P_DMAB1(PL_, S_)                                                                                    \
     do {                                                                                                          \
-        if constexpr (BFULL >= 1) dma3<(PL_) * BN * 64>(voffB[0], rsrcB, (S_), lw_);                              \
-        if constexpr (BP > BFULL) { if (b_last) dma3<(PL_) * BN * 64 + BFULL * 4096>(voffB[BP - 1], rsrcB, (S_), lw_); } \
+        if constexpr (BFULL >= 1) lds_dma<(PL_) * BN * 64>(voffB[0], rsrcB, (S_), lw_);                           \
+        if constexpr (BP > BFULL) { if (b_last) lds_dma<(PL_) * BN * 64 + BFULL * 4096>(voffB[BP - 1], rsrcB, (S_), lw_); } \
     } while (0)
 #define PADEL_P_LOAD(CH_)                                                                                         \
     do {                                                                                                          \
@@ -164,10 +149,10 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
             _Pragma("unroll") for (int i = 0; i < kPasses; ++i) {                                                 \
                 const int item = i * 256 + tid;                                                                   \
                 const int pp = item >> 3, c4 = item & 7;                                                          \
-                const int py = pp / kPW, px = pp - py * kPW;                                                      \
+                const int py = pp / kPatchW, px = pp - py * kPatchW;                                              \
                 const int iy = y0 - 1 + py, ix = x0 - 1 + px;                                                     \
                 const bool ok = item < kItems && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;   \
-                const unsigned vo_ = ok ? (unsigned)(((((iy >> 1) - cy0) * W2 + ((ix >> 1) - cx0)) * a.in2_cs + c4 * 4) * 4) : kOOR3; \
+                const unsigned vo_ = ok ? (unsigned)(((((iy >> 1) - cy0) * W2 + ((ix >> 1) - cx0)) * a.in2_cs + c4 * 4) * 4) : kOOR; \
                 pre[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrcU, vo_, so_, 0);                               \
             }                                                                                                     \
         } else {                                                                                                  \
@@ -177,10 +162,10 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
 #define PADEL_P_READA(T_)                                                                                         \
     do {                                                                                                          \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
-            const char* p_ = ldsb + patch_off(rd_pix + (f + (T_) / 3) * kPW + (T_) % 3, lq);                      \
+            const char* p_ = ldsb + swz_off(rd_pix + (f + (T_) / 3) * kPatchW + (T_) % 3, lq);                    \
             ah[f] = *reinterpret_cast<const bf8*>(p_);                                                            \
-            am[f] = *reinterpret_cast<const bf8*>(p_ + kPlaneB);                                                  \
-            al[f] = *reinterpret_cast<const bf8*>(p_ + 2 * kPlaneB);                                              \
+            am[f] = *reinterpret_cast<const bf8*>(p_ + kPatchPlaneB);                                             \
+            al[f] = *reinterpret_cast<const bf8*>(p_ + 2 * kPatchPlaneB);                                         \
         }                                                                                                         \
     } while (0)
     // tail step JT: taps 2 JT and 2 JT + 1 (the 10th "tap" has zero weights: any finite data, tap 8 again)
@@ -188,14 +173,14 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
     do {                                                                                                          \
         constexpr int ta_ = 2 * (JT_), tb_ = 2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8;                               \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
-            const char* pa_ = ldsb + tail_off(rd_pix + (f + ta_ / 3) * kPW + ta_ % 3, lq);                        \
-            const char* pb_ = ldsb + tail_off(rd_pix + (f + tb_ / 3) * kPW + tb_ % 3, lq);                        \
+            const char* pa_ = ldsb + bx3_tail_off(rd_pix + (f + ta_ / 3) * kPatchW + ta_ % 3, lq);                \
+            const char* pb_ = ldsb + bx3_tail_off(rd_pix + (f + tb_ / 3) * kPatchW + tb_ % 3, lq);                \
             u32x4 v_;                                                                                             \
             { const u32x2 x_ = *reinterpret_cast<const u32x2*>(pa_), y_ = *reinterpret_cast<const u32x2*>(pb_);    \
               v_ = (u32x4){x_[0], x_[1], y_[0], y_[1]}; ah[f] = __builtin_bit_cast(bf8, v_); }                    \
-            { const u32x2 x_ = *reinterpret_cast<const u32x2*>(pa_ + kPlaneB), y_ = *reinterpret_cast<const u32x2*>(pb_ + kPlaneB); \
+            { const u32x2 x_ = *reinterpret_cast<const u32x2*>(pa_ + kPatchPlaneB), y_ = *reinterpret_cast<const u32x2*>(pb_ + kPatchPlaneB); \
               v_ = (u32x4){x_[0], x_[1], y_[0], y_[1]}; am[f] = __builtin_bit_cast(bf8, v_); }                    \
-            { const u32x2 x_ = *reinterpret_cast<const u32x2*>(pa_ + 2 * kPlaneB), y_ = *reinterpret_cast<const u32x2*>(pb_ + 2 * kPlaneB); \
+            { const u32x2 x_ = *reinterpret_cast<const u32x2*>(pa_ + 2 * kPatchPlaneB), y_ = *reinterpret_cast<const u32x2*>(pb_ + 2 * kPatchPlaneB); \
               v_ = (u32x4){x_[0], x_[1], y_[0], y_[1]}; al[f] = __builtin_bit_cast(bf8, v_); }                    \
         }                                                                                                         \
     } while (0)
@@ -235,7 +220,7 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
            the barrier (their LDS latency runs under the wait), and the weight operands before the next step's      \
            LDS-DMA requests are issued: +1..2.5 % (profiles/conv_bx3_sweep_r2r_read_order.txt) */                 \
         if constexpr ((T_) > 0) PADEL_P_READA(T_);                                                                \
-        wait_vm3<0>();                                                                                            \
+        wait_vm<0>();                                                                                             \
         if constexpr ((T_) == 0) lds_fence();          /* this wave's plane writes have reached the LDS */         \
         __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
@@ -256,16 +241,16 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
         _Pragma("unroll") for (int i = 0; i < kTailPasses; ++i) {                                                 \
             const int item = i * 256 + tid;                                                                       \
             const int pp = item >> 2, c4 = item & 3;                                                              \
-            const int py = pp / kPW, px = pp - py * kPW;                                                          \
-            const bool ok = item < kNPix * 4 && (unsigned)(y0 - 1 + py) < (unsigned)a.H && (unsigned)(x0 - 1 + px) < (unsigned)a.W; \
-            pre[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrcP, ok ? (unsigned)(((py * a.W + px) * a.in_cs + c4 * 4) * 4) : kOOR3, \
+            const int py = pp / kPatchW, px = pp - py * kPatchW;                                                  \
+            const bool ok = item < kPatchPix * 4 && (unsigned)(y0 - 1 + py) < (unsigned)a.H && (unsigned)(x0 - 1 + px) < (unsigned)a.W; \
+            pre[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrcP, ok ? (unsigned)(((py * a.W + px) * a.in_cs + c4 * 4) * 4) : kOOR, \
                                                            (unsigned)nch * 128u, 0);                              \
         }                                                                                                         \
     } while (0)
 #define PADEL_P_TSTEP(JT_)                                                                                        \
     do {                                                                                                          \
         bf8 ah[MF], am[MF], al[MF], wh[NF], wm[NF], wl[NF];                                                       \
-        wait_vm3<0>();                                                                                            \
+        wait_vm<0>();                                                                                             \
         lds_fence();                                                                                              \
         __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
@@ -292,8 +277,8 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
             split4(pre[i], h, m, l);
             if (i * 256 + 255 < kItems || i * 256 + tid < kItems) {
                 *reinterpret_cast<u32x2*>(ldsb + wrP[i]) = h;
-                *reinterpret_cast<u32x2*>(ldsb + kPlaneB + wrP[i]) = m;
-                *reinterpret_cast<u32x2*>(ldsb + 2 * kPlaneB + wrP[i]) = l;
+                *reinterpret_cast<u32x2*>(ldsb + kPatchPlaneB + wrP[i]) = m;
+                *reinterpret_cast<u32x2*>(ldsb + 2 * kPatchPlaneB + wrP[i]) = l;
             }
         }
         PADEL_P_STEP(0); PADEL_P_STEP(1); PADEL_P_STEP(2); PADEL_P_STEP(3); PADEL_P_STEP(4);
@@ -316,11 +301,11 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
             const int pp = item >> 2, c4 = item & 3;
             u32x2 h, m, l;
             split4(pre[i], h, m, l);
-            if (item < kNPix * 4) {
-                char* const w_ = ldsb + tail_off(pp, c4);
+            if (item < kPatchPix * 4) {
+                char* const w_ = ldsb + bx3_tail_off(pp, c4);
                 *reinterpret_cast<u32x2*>(w_) = h;
-                *reinterpret_cast<u32x2*>(w_ + kPlaneB) = m;
-                *reinterpret_cast<u32x2*>(w_ + 2 * kPlaneB) = l;
+                *reinterpret_cast<u32x2*>(w_ + kPatchPlaneB) = m;
+                *reinterpret_cast<u32x2*>(w_ + 2 * kPatchPlaneB) = l;
             }
         }
         PADEL_P_TSTEP(0); PADEL_P_TSTEP(1); PADEL_P_TSTEP(2); PADEL_P_TSTEP(3); PADEL_P_TSTEP(4);
@@ -329,7 +314,7 @@ __global__ void __launch_bounds__(256, NF <= 3 ? 3 : 2) conv_bx3p_kernel(const C
 #pragma unroll
             for (int j = 0; j < NF; ++j) acc[f][j] += part[f][j];
     }
-    wait_vm3<0>();
+    wait_vm<0>();
 #undef PADEL_P_TSTEP
 #undef PADEL_P_TLOAD
 #undef PADEL_P_TREADA

@@ -24,21 +24,10 @@ namespace padel {
 
 namespace {
 
-typedef unsigned hp_u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kHPW = 18;                        // patch width in pixels (16 + halo)
-constexpr int kHNPix = 180;                     // 10 x 18
-constexpr int kHPlaneB = kHNPix * 64;           // one fp16 plane of a 32-channel chunk
-constexpr int kHPatchB = 2 * kHPlaneB;
-constexpr int kHItems = kHNPix * 8;             // 16-byte pieces of the 128-byte-per-pixel patch
+constexpr int kHPatchB = 2 * kPatchPlaneB;
+constexpr int kHItems = kPatchPix * 8;             // 16-byte pieces of the 128-byte-per-pixel patch
 constexpr int kHPasses = (kHItems + 255) / 256; // 6
-constexpr int kHTailPasses = (kHNPix * 4 + 255) / 256;     // 3
-
-// byte offset, inside a plane, of logical 16-byte chunk q (K slots 8q..8q+7) of patch pixel p
-__device__ __forceinline__ unsigned hp_off(int p, int q) { return (unsigned)(p * 64 + ((q ^ (((p >> 2) & 1) << 1)) << 4)); }
-// tail planes: 32 bytes per pixel, 16-byte slot s (channels 8s..8s+7)
-__device__ __forceinline__ unsigned hp_tail_off(int p, int s) { return (unsigned)(p * 32 + ((s ^ ((p >> 3) & 1)) << 4)); }
-__device__ __forceinline__ void hp_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+constexpr int kHTailPasses = (kPatchPix * 4 + 255) / 256;     // 3
 
 }  // namespace
 
@@ -71,15 +60,13 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
     // XCD-aware 1-D tile map: the channel tiles of one pixel patch are neighbours on one XCD
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;
     const int bid = blockIdx.x;
+    // (xcd_slot / xcd_slot_padding / xcd_slot_mtile of conv_index.h, written out: through the functions the NF = 4 two-product kernels allocate their registers differently)
     const int q8 = nmt >> 3, r8 = nmt & 7, xcd = bid & 7, idx = bid >> 3;
     const int mloc = idx / nnt, nt = idx - mloc * nnt;
     if (mloc >= q8 + (xcd < r8 ? 1 : 0)) return;
     const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
-    const int txN = (a.Wo + 15) >> 4, tyN = (a.Ho + 7) >> 3;
-    const int tpi = tyN * txN;
-    const int n = mt / tpi, rt = mt - n * tpi;
-    const int ty = rt / txN, tx = rt - ty * txN;
-    const int y0 = ty * 8, x0 = tx * 16;
+    const TileOrigin org = tile_origin<3, 4>(a.Ho, a.Wo, mt);
+    const int n = org.n, y0 = org.y0, x0 = org.x0;
     const int f0 = nt * NF;
 
     // ---- the patch: piece i * 256 + tid = (pixel, 16-byte piece 0..7 of its 128-byte chunk: group g = piece >> 2,
@@ -89,21 +76,21 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
     for (int i = 0; i < kHPasses; ++i) {
         const int item = i * 256 + tid;
         const int pp = item >> 3, pc = item & 7;
-        const int py = pp / kHPW, px = pp - py * kHPW;
+        const int py = pp / kPatchW, px = pp - py * kPatchW;
         const int iy = y0 - 1 + py, ix = x0 - 1 + px;
         const bool ok = item < kHItems && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-        voffP[i] = ok ? (unsigned)((py * a.W + px) * a.in_cs * 4 + pc * 16) : kOOR3;
+        voffP[i] = ok ? (unsigned)((py * a.W + px) * a.in_cs * 4 + pc * 16) : kOOR;
     }
     // LDS place of piece (pixel pp = i * 32 + tid / 8, piece pc = tid & 7): plane (pc >> 1) & 1, logical chunk (pc >> 2) * 2 + (pc & 1)
-    const unsigned wr0 = (unsigned)((((tid & 7) >> 1) & 1) * kHPlaneB);
+    const unsigned wr0 = (unsigned)((((tid & 7) >> 1) & 1) * kPatchPlaneB);
     const int wr_q = ((tid & 7) >> 2) * 2 + (tid & 1);
     const float* const in0 = a.in + (((long long)n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * a.in_cs + a.in_choff;
-    const __amdgpu_buffer_rsrc_t rsrcP = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(in0), 0, (int)0x80000000u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcP = make_buffer_rsrc(in0);
     // coarse map of an absorbed upsample: descriptor based at the coarse pixel of the patch's top-left halo pixel
     const int H2 = a.H >> 1, W2 = a.W >> 1;
     const int cy0 = (y0 - 1) >> 1, cx0 = (x0 - 1) >> 1;                 // arithmetic shifts: -1 for the halo above / left of the image
     const float* const inU = UP ? a.in2 + (((long long)n * H2 + cy0) * W2 + cx0) * a.in2_cs + a.in2_choff : in0;
-    const __amdgpu_buffer_rsrc_t rsrcU = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(inU), 0, (int)0x80000000u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrcU = make_buffer_rsrc(inU);
     const int nup = UP ? a.up_c >> 5 : 0;
     (void)H2; (void)W2; (void)cy0; (void)cx0; (void)rsrcU; (void)nup;
 
@@ -119,14 +106,14 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
         const int frag = min(f0 + (rr >> 4), a.n16 - 1);
         voffB[p] = (unsigned)(((frag - f0) * 16 + (rr & 15)) * rowb + sc * 16);
     }
-    const i32x4 rsrcB = make_rsrc3(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
+    const i32x4 rsrcB = make_rsrc(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
     const bool b_last = BP > BFULL && (BFULL * 64 + wave * 16 < BN);
     unsigned lw0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds + (unsigned)kHPatchB + wave * 1024u);
     unsigned lw1 = __builtin_amdgcn_readfirstlane(lw0 + (unsigned)BSTAGE_B);
     const int ld_off = lr * 16 + ((lq ^ ((4 - ((lr >> 2) & 3)) & 3)) << 2);
     const float* b_rd0 = lds + kHPatchB / 4 + ld_off;
     const float* b_rd1 = b_rd0 + BSTAGE_B / 4;
-    const int rd_pix = 2 * wave * kHPW + lr;                // patch pixel of fragment 0, tap (0, 0)
+    const int rd_pix = 2 * wave * kPatchW + lr;                // patch pixel of fragment 0, tap (0, 0)
 
     f32x4 acc[MF][NF], part[MF][NF], cross[MF][NF];
 #pragma unroll
@@ -144,8 +131,8 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
     } while (0)
 #define PADEL_HP_DMAB1(PL_, S_)                                                                                   \
     do {                                                                                                          \
-        if constexpr (BFULL >= 1) dma3<(PL_) * BN * 64>(voffB[0], rsrcB, (S_), lw_);                              \
-        if constexpr (BP > BFULL) { if (b_last) dma3<(PL_) * BN * 64 + BFULL * 4096>(voffB[BP - 1], rsrcB, (S_), lw_); } \
+        if constexpr (BFULL >= 1) lds_dma<(PL_) * BN * 64>(voffB[0], rsrcB, (S_), lw_);                           \
+        if constexpr (BP > BFULL) { if (b_last) lds_dma<(PL_) * BN * 64 + BFULL * 4096>(voffB[BP - 1], rsrcB, (S_), lw_); } \
     } while (0)
 #define PADEL_HP_LOAD(CH_)                                                                                        \
     do {                                                                                                          \
@@ -154,10 +141,10 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
             _Pragma("unroll") for (int i = 0; i < kHPasses; ++i) {                                                \
                 const int item = i * 256 + tid;                                                                   \
                 const int pp = item >> 3, pc = item & 7;                                                          \
-                const int py = pp / kHPW, px = pp - py * kHPW;                                                    \
+                const int py = pp / kPatchW, px = pp - py * kPatchW;                                              \
                 const int iy = y0 - 1 + py, ix = x0 - 1 + px;                                                     \
                 const bool ok = item < kHItems && (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;  \
-                const unsigned vo_ = ok ? (unsigned)((((iy >> 1) - cy0) * W2 + ((ix >> 1) - cx0)) * a.in2_cs * 4 + pc * 16) : kOOR3; \
+                const unsigned vo_ = ok ? (unsigned)((((iy >> 1) - cy0) * W2 + ((ix >> 1) - cx0)) * a.in2_cs * 4 + pc * 16) : kOOR; \
                 pre[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrcU, vo_, so_, 0);                               \
             }                                                                                                     \
         } else {                                                                                                  \
@@ -167,9 +154,9 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
 #define PADEL_HP_READA(T_)                                                                                        \
     do {                                                                                                          \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
-            const char* p_ = ldsb + hp_off(rd_pix + (f + h2_tap_ky(T_)) * kHPW + h2_tap_kx(T_), lq);                        \
+            const char* p_ = ldsb + swz_off(rd_pix + (f + h2_tap_ky(T_)) * kPatchW + h2_tap_kx(T_), lq);          \
             ah[f] = *reinterpret_cast<const h16x8*>(p_);                                                          \
-            am[f] = *reinterpret_cast<const h16x8*>(p_ + kHPlaneB);                                               \
+            am[f] = *reinterpret_cast<const h16x8*>(p_ + kPatchPlaneB);                                           \
         }                                                                                                         \
     } while (0)
     // tail step JT: lane group q reads the 8 channels 8 (q & 1).. of tap 2 JT + (q >> 1) (the 10th "tap" has zero weights:
@@ -178,10 +165,10 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
     do {                                                                                                          \
         constexpr int ta_ = 2 * (JT_), tb_ = 2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8;                               \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
-            const int pa_ = rd_pix + (f + h2_tap_ky(ta_)) * kHPW + h2_tap_kx(ta_), pb_ = rd_pix + (f + h2_tap_ky(tb_)) * kHPW + h2_tap_kx(tb_); \
-            const char* p_ = ldsb + hp_tail_off((lq >> 1) ? pb_ : pa_, lq & 1);                                   \
+            const int pa_ = rd_pix + (f + h2_tap_ky(ta_)) * kPatchW + h2_tap_kx(ta_), pb_ = rd_pix + (f + h2_tap_ky(tb_)) * kPatchW + h2_tap_kx(tb_); \
+            const char* p_ = ldsb + swz_tail_off((lq >> 1) ? pb_ : pa_, lq & 1);                                  \
             ah[f] = *reinterpret_cast<const h16x8*>(p_);                                                          \
-            am[f] = *reinterpret_cast<const h16x8*>(p_ + kHPlaneB);                                               \
+            am[f] = *reinterpret_cast<const h16x8*>(p_ + kPatchPlaneB);                                           \
         }                                                                                                         \
     } while (0)
 #define PADEL_HP_READB(T_)                                                                                        \
@@ -209,19 +196,19 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
 #define PADEL_HP_READA2(T_, S_)                                                                                   \
     do {                                                                                                          \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
-            const char* p_ = ldsb + hp_off(rd_pix + (f + h2_tap_ky(T_)) * kHPW + h2_tap_kx(T_), lq);                        \
+            const char* p_ = ldsb + swz_off(rd_pix + (f + h2_tap_ky(T_)) * kPatchW + h2_tap_kx(T_), lq);          \
             ah2[S_][f] = *reinterpret_cast<const h16x8*>(p_);                                                     \
-            am2[S_][f] = *reinterpret_cast<const h16x8*>(p_ + kHPlaneB);                                          \
+            am2[S_][f] = *reinterpret_cast<const h16x8*>(p_ + kPatchPlaneB);                                      \
         }                                                                                                         \
     } while (0)
 #define PADEL_HP_TREADA2(JT_, S_)                                                                                 \
     do {                                                                                                          \
         constexpr int ta_ = 2 * (JT_), tb_ = 2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8;                               \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
-            const int pa_ = rd_pix + (f + h2_tap_ky(ta_)) * kHPW + h2_tap_kx(ta_), pb_ = rd_pix + (f + h2_tap_ky(tb_)) * kHPW + h2_tap_kx(tb_); \
-            const char* p_ = ldsb + hp_tail_off((lq >> 1) ? pb_ : pa_, lq & 1);                                   \
+            const int pa_ = rd_pix + (f + h2_tap_ky(ta_)) * kPatchW + h2_tap_kx(ta_), pb_ = rd_pix + (f + h2_tap_ky(tb_)) * kPatchW + h2_tap_kx(tb_); \
+            const char* p_ = ldsb + swz_tail_off((lq >> 1) ? pb_ : pa_, lq & 1);                                  \
             ah2[S_][f] = *reinterpret_cast<const h16x8*>(p_);                                                     \
-            am2[S_][f] = *reinterpret_cast<const h16x8*>(p_ + kHPlaneB);                                          \
+            am2[S_][f] = *reinterpret_cast<const h16x8*>(p_ + kPatchPlaneB);                                      \
         }                                                                                                         \
     } while (0)
 #define PADEL_HP_READB2(T_, S_)                                                                                   \
@@ -256,8 +243,8 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
     // block's last step, i.e. before every wave reached this barrier)
 #define PADEL_HP_PENTRY(READA0_)                                                                                  \
     do {                                                                                                          \
-        wait_vm3<0>();                                                                                            \
-        hp_lds_fence();                                                                                           \
+        wait_vm<0>();                                                                                             \
+        lds_fence();                                                                                              \
         __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
         PADEL_HP_READB2(0, 0);                                                                                    \
@@ -275,7 +262,7 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
         PADEL_HP_MFMA_CROSS((T_) & 1);                                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         if constexpr ((T_) + 1 < (NT_)) {                                                                         \
-            wait_vm3<0>();                                                                                        \
+            wait_vm<0>();                                                                                         \
             __builtin_amdgcn_s_barrier();                                                                         \
             asm volatile("" ::: "memory");                                                                        \
             PADEL_HP_READB2((T_) + 1, ((T_) + 1) & 1);                                                            \
@@ -295,8 +282,8 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
     do {                                                                                                          \
         constexpr bool first_ = (T_) == 0;                                                                        \
         if constexpr (!first_ && !(PROBE & 8)) PADEL_HP_READA(T_);   /* the planes are static inside a chunk: read under the wait */ \
-        if constexpr (first_ || !(PROBE & 4)) wait_vm3<0>();                                                      \
-        if constexpr (first_) hp_lds_fence();           /* this wave's plane writes have reached the LDS */         \
+        if constexpr (first_ || !(PROBE & 4)) wait_vm<0>();                                                       \
+        if constexpr (first_) lds_fence();           /* this wave's plane writes have reached the LDS */          \
         if constexpr (first_ || !(PROBE & 1)) __builtin_amdgcn_s_barrier();                                       \
         asm volatile("" ::: "memory");                                                                            \
         if constexpr (first_ || !(PROBE & 2)) PADEL_HP_READB(T_);                                                 \
@@ -318,16 +305,16 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
         _Pragma("unroll") for (int i = 0; i < kHTailPasses; ++i) {                                                \
             const int item = i * 256 + tid;                                                                       \
             const int pp = item >> 2, pc = item & 3;                                                              \
-            const int py = pp / kHPW, px = pp - py * kHPW;                                                        \
-            const bool ok = item < kHNPix * 4 && (unsigned)(y0 - 1 + py) < (unsigned)a.H && (unsigned)(x0 - 1 + px) < (unsigned)a.W; \
-            pre[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrcP, ok ? (unsigned)((py * a.W + px) * a.in_cs * 4 + pc * 16) : kOOR3, \
+            const int py = pp / kPatchW, px = pp - py * kPatchW;                                                  \
+            const bool ok = item < kPatchPix * 4 && (unsigned)(y0 - 1 + py) < (unsigned)a.H && (unsigned)(x0 - 1 + px) < (unsigned)a.W; \
+            pre[i] = __builtin_amdgcn_raw_buffer_load_b128(rsrcP, ok ? (unsigned)((py * a.W + px) * a.in_cs * 4 + pc * 16) : kOOR, \
                                                            (unsigned)nch * 128u, 0);                              \
         }                                                                                                         \
     } while (0)
 #define PADEL_HP_TSTEP(JT_)                                                                                       \
     do {                                                                                                          \
-        wait_vm3<0>();                                                                                            \
-        hp_lds_fence();                                                                                           \
+        wait_vm<0>();                                                                                             \
+        lds_fence();                                                                                              \
         __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
         if constexpr ((JT_) < 4) PADEL_HP_DMAB((JT_) + 1, s_kb + ((JT_) + 1) * 128u);                             \
@@ -338,7 +325,7 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
         __builtin_amdgcn_sched_barrier(0);                                                                        \
     } while (0)
 
-    hp_u32x4 pre[kHPasses];
+    u32x4 pre[kHPasses];
     unsigned s_kb = 0;
     if (!TAIL || nch > 0) PADEL_HP_LOAD(0); else PADEL_HP_TLOAD();
     PADEL_HP_DMAB(0, 0u);
@@ -352,7 +339,7 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
 #pragma unroll
             for (int i = 0; i < kHPasses; ++i)
                 if (i * 256 + 255 < kHItems || i * 256 + tid < kHItems)
-                    *reinterpret_cast<hp_u32x4*>(ldsb + wr0 + hp_off(i * 32 + (tid >> 3), wr_q)) = pre[i];
+                    *reinterpret_cast<u32x4*>(ldsb + wr0 + swz_off(i * 32 + (tid >> 3), wr_q)) = pre[i];
             const bool more = c + 1 < nch || TAIL;
             PADEL_HP_PENTRY(PADEL_HP_READA2(0, 0));
 #define PADEL_HP_PREFETCH() do { if (c + 1 < nch) PADEL_HP_LOAD(c + 1); if constexpr (TAIL) { if (c + 1 == nch) PADEL_HP_TLOAD(); } } while (0)
@@ -384,7 +371,7 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
             for (int i = 0; i < kHTailPasses; ++i) {
                 const int item = i * 256 + tid;
                 const int pp = item >> 2, pc = item & 3;
-                if (item < kHNPix * 4) *reinterpret_cast<hp_u32x4*>(ldsb + (pc >> 1) * kHPlaneB + hp_tail_off(pp, pc & 1)) = pre[i];
+                if (item < kPatchPix * 4) *reinterpret_cast<u32x4*>(ldsb + (pc >> 1) * kPatchPlaneB + swz_tail_off(pp, pc & 1)) = pre[i];
             }
             PADEL_HP_PENTRY(PADEL_HP_TREADA2(0, 0));
             PADEL_HP_PSTEP(0, 5, PADEL_HP_TREADA2(1, 1), false, (void)0);
@@ -409,7 +396,7 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
 #pragma unroll
         for (int i = 0; i < kHPasses; ++i)
             if (i * 256 + 255 < kHItems || i * 256 + tid < kHItems)
-                *reinterpret_cast<hp_u32x4*>(ldsb + wr0 + hp_off(i * 32 + (tid >> 3), wr_q)) = pre[i];
+                *reinterpret_cast<u32x4*>(ldsb + wr0 + swz_off(i * 32 + (tid >> 3), wr_q)) = pre[i];
         PADEL_HP_STEP(0); PADEL_HP_STEP(1); PADEL_HP_STEP(2); PADEL_HP_STEP(3); PADEL_HP_STEP(4);
         PADEL_HP_STEP(5); PADEL_HP_STEP(6); PADEL_HP_STEP(7); PADEL_HP_STEP(8);
         if constexpr (TWOL) {
@@ -430,7 +417,7 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
         for (int i = 0; i < kHTailPasses; ++i) {
             const int item = i * 256 + tid;
             const int pp = item >> 2, pc = item & 3;
-            if (item < kHNPix * 4) *reinterpret_cast<hp_u32x4*>(ldsb + (pc >> 1) * kHPlaneB + hp_tail_off(pp, pc & 1)) = pre[i];
+            if (item < kPatchPix * 4) *reinterpret_cast<u32x4*>(ldsb + (pc >> 1) * kPatchPlaneB + swz_tail_off(pp, pc & 1)) = pre[i];
         }
         PADEL_HP_TSTEP(0); PADEL_HP_TSTEP(1); PADEL_HP_TSTEP(2); PADEL_HP_TSTEP(3); PADEL_HP_TSTEP(4);
         if constexpr (TWOL) {
@@ -441,7 +428,7 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
         }
     }
     }
-    wait_vm3<0>();
+    wait_vm<0>();
 #undef PADEL_HP_TSTEP
 #undef PADEL_HP_PSTEP
 #undef PADEL_HP_PENTRY

@@ -50,13 +50,7 @@ namespace padel {
 
 namespace {
 
-constexpr int kQPW = 18;                        // patch width in pixels (16 + halo)
-constexpr int kQNPix = 180;                     // 10 x 18
-constexpr int kQPlaneB = 192 * 64;              // one fp16 plane of a 32-channel chunk, padded to 12 spans of 16 pixels
-constexpr int kQPatchB = 2 * kQPlaneB;
-
-// byte offset, inside a plane, of logical 16-byte chunk q (K slots 8q..8q+7) of patch pixel p (conv_patch_h2.hip:hp_off)
-__device__ __forceinline__ unsigned hq_off(int p, int q) { return (unsigned)(p * 64 + ((q ^ (((p >> 2) & 1) << 1)) << 4)); }
+constexpr int kQPatchB = 2 * kPatchPadPlaneB;
 
 // DBG (tuning only, builds with -DPADEL_H2P_PROBES, pa_engine_set_tuning "timeline"): every wave stamps s_memtime at 5
 // points of every tap step (step top / own requests landed / barrier passed / operands in registers / last MFMA issued)
@@ -106,22 +100,18 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
     // XCD-aware 1-D tile map: the channel tiles of one pixel patch are neighbours on one XCD
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;
     const int bid = blockIdx.x;
-    const int q8 = nmt >> 3, r8 = nmt & 7, xcd = bid & 7, idx = bid >> 3;
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;
-    if (mloc >= q8 + (xcd < r8 ? 1 : 0)) return;
-    const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
-    const int txN = (a.Wo + 15) >> 4, tyN = (a.Ho + 7) >> 3;
-    const int tpi = tyN * txN;
-    const int n = mt / tpi, rt = mt - n * tpi;
-    const int ty = rt / txN, tx = rt - ty * txN;
-    const int y0 = ty * 8, x0 = tx * 16;
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);
+    if (xcd_slot_padding(slot)) return;
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;
+    const TileOrigin org = tile_origin<3, 4>(a.Ho, a.Wo, mt);
+    const int n = org.n, y0 = org.y0, x0 = org.x0;
     const int f0 = nt * 2 * NF;
 
     // ---- the patch (wave 3): span s of a plane = 16 pixels x 64 bytes, lane i -> pixel 16 s + i / 4, physical 16-byte slot
-    // i & 3 = logical chunk q of that pixel (hq_off), which is piece (q & 1) of group (q >> 1) of the pixel's 128 bytes
+    // i & 3 = logical chunk q of that pixel (swz_off), which is piece (q & 1) of group (q >> 1) of the pixel's 128 bytes
     // [h0 m0 h1 m1] in HBM; the plane's 32 bytes go in through the scalar offset
     const float* const in0 = a.in + (((long long)n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * a.in_cs + a.in_choff;
-    const i32x4 rsrcP = make_rsrc3(in0);
+    const i32x4 rsrcP = make_rsrc(in0);
     const int p_lane = lane >> 2;
     const int p_q = (lane & 3) ^ (((lane >> 4) & 1) << 1);
     const unsigned p_piece = (unsigned)((p_q >> 1) * 64 + (p_q & 1) * 16);
@@ -138,11 +128,11 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
 #define PADEL_HQ_PSPAN(S_)                                                                                        \
     do {                                                                                                          \
         const int pp_ = (S_) * 16 + pl_;                                                                          \
-        const int py_ = pp_ / kQPW, px_ = pp_ - py_ * kQPW;                                                       \
-        const bool ok_ = pp_ < kQNPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
-        const unsigned vo_ = ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 4) + p_piece : kOOR3;                 \
-        dma3<(S_) * 1024>(vo_, rsrcP, so_, lb_);                                                                  \
-        dma3<kQPlaneB + (S_) * 1024>(vo_, rsrcP, so_ + 32u, lb_);                                                 \
+        const int py_ = pp_ / kPatchW, px_ = pp_ - py_ * kPatchW;                                                 \
+        const bool ok_ = pp_ < kPatchPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
+        const unsigned vo_ = ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 4) + p_piece : kOOR;                  \
+        lds_dma<(S_) * 1024>(vo_, rsrcP, so_, lb_);                                                               \
+        lds_dma<kPatchPadPlaneB + (S_) * 1024>(vo_, rsrcP, so_ + 32u, lb_);                                       \
     } while (0)
 
     // ---- weights (waves 0..2): rows of (cin / 32) * 9 k-steps x 128 bytes (h | m); wave w requests the spans 2 w, 2 w + 1
@@ -158,24 +148,24 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
         const int frag = min(f0 + g, a.n16 - 1);            // fragments beyond the matrix: any valid rows (never stored)
         voffB[k] = (unsigned)(((frag - f0) * 16 + b_row) * rowb + b_sc * 16);
     }
-    const i32x4 rsrcB = make_rsrc3(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
+    const i32x4 rsrcB = make_rsrc(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
     unsigned lw0 = __builtin_amdgcn_readfirstlane(lp0 + (unsigned)(2 * kQPatchB) + (unsigned)wave * 2048u);
     unsigned lw1 = __builtin_amdgcn_readfirstlane(lw0 + (unsigned)BSTAGE_B);
 #define PADEL_HQ_DMAB(SR_, SB_)                                                                                   \
     do {                                                                                                          \
         const unsigned lw_ = ((SR_) & 1) ? lw1 : lw0;                                                             \
         const unsigned sb_ = (SB_);                                                                               \
-        dma3<0>(voffB[0], rsrcB, sb_, lw_);                                                                       \
-        dma3<1024>(voffB[1], rsrcB, sb_, lw_);                                                                    \
+        lds_dma<0>(voffB[0], rsrcB, sb_, lw_);                                                                    \
+        lds_dma<1024>(voffB[1], rsrcB, sb_, lw_);                                                                 \
         if constexpr (!WS) {                                                                                      \
-            dma3<BPLANE_B>(voffB[0], rsrcB, sb_ + 64u, lw_);                                                      \
-            dma3<BPLANE_B + 1024>(voffB[1], rsrcB, sb_ + 64u, lw_);                                               \
+            lds_dma<BPLANE_B>(voffB[0], rsrcB, sb_ + 64u, lw_);                                                   \
+            lds_dma<BPLANE_B + 1024>(voffB[1], rsrcB, sb_ + 64u, lw_);                                            \
         }                                                                                                         \
     } while (0)
     const int ld_off = (3 * wc) * 256 + lr * 16 + ((lq ^ ((4 - ((lr >> 2) & 3)) & 3)) << 2);      // floats
     const float* b_rd0 = lds + (2 * kQPatchB) / 4 + ld_off;
     const float* b_rd1 = b_rd0 + BSTAGE_B / 4;
-    const int rd_pix = 4 * wr * kQPW + lr;                 // patch pixel of the wave's row 0, kx = 0
+    const int rd_pix = 4 * wr * kPatchW + lr;                 // patch pixel of the wave's row 0, kx = 0
 
     f32x4 acc[MF][NF], part[MF][NF], cross[MF][NF];
 #pragma unroll
@@ -186,9 +176,9 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
     // input row R_ (0..5 of the wave's window) at column shift KX_ into its slot
 #define PADEL_HQ_READROW(R_, KX_)                                                                                 \
     do {                                                                                                          \
-        const char* p_ = pbuf + hq_off(rp_ + (R_) * kQPW + (KX_), lq);                                            \
+        const char* p_ = pbuf + swz_off(rp_ + (R_) * kPatchW + (KX_), lq);                                        \
         ah[(R_) & 3] = *reinterpret_cast<const h16x8*>(p_);                                                       \
-        am[(R_) & 3] = *reinterpret_cast<const h16x8*>(p_ + kQPlaneB);                                            \
+        am[(R_) & 3] = *reinterpret_cast<const h16x8*>(p_ + kPatchPadPlaneB);                                     \
     } while (0)
 #define PADEL_HQ_READB(T_)                                                                                        \
     do {                                                                                                          \
@@ -227,7 +217,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
             if constexpr (ky_ == 0) { PADEL_HQ_READROW(0, kx_); PADEL_HQ_READROW(1, kx_); PADEL_HQ_READROW(2, kx_); PADEL_HQ_READROW(3, kx_); } \
             else PADEL_HQ_READROW(3 + ky_, kx_);                                                                  \
         }                                                                                                         \
-        if ((T_) == 0 || wave != 3) wait_vm3<0>();                                                                \
+        if ((T_) == 0 || wave != 3) wait_vm<0>();                                                                 \
         PADEL_HQ_STAMP(T_, 1);                                                                                    \
         __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
@@ -235,7 +225,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
         PADEL_HQ_READB(T_);                                                                                       \
         if constexpr ((T_) == 0) { PADEL_HQ_READROW(0, 0); PADEL_HQ_READROW(1, 0); PADEL_HQ_READROW(2, 0); PADEL_HQ_READROW(3, 0); } \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        if constexpr (DBG) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); PADEL_HQ_STAMP(T_, 3); }          \
+        if constexpr (DBG) { lds_fence(); PADEL_HQ_STAMP(T_, 3); }                                                \
         __builtin_amdgcn_s_setprio(1);                                                                            \
         PADEL_HQ_MFMA_ROW(0, ky_);                                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -270,7 +260,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
         s_kb += 9u * 128u;
         dbg_k += 9;
     }
-    wait_vm3<0>();
+    wait_vm<0>();
 #undef PADEL_HQ_STEP
 #undef PADEL_HQ_MFMA_ROW
 #undef PADEL_HQ_READB

@@ -34,16 +34,8 @@ namespace padel {
 
 namespace {
 
-constexpr int kRPW = 18;                        // patch width in pixels (16 + halo)
-constexpr int kRNPix = 180;                     // 10 x 18
-constexpr int kRPlaneB = 192 * 64;              // one fp16 plane of a 32-channel chunk, padded to 12 spans of 16 pixels
-constexpr int kRPatchB = 2 * kRPlaneB;
+constexpr int kRPatchB = 2 * kPatchPadPlaneB;
 constexpr int kRBufStride = 32768;              // the two patch buffers sit 32 KB apart: switching buffers is one XOR per read address
-
-// byte offset, inside a plane, of logical 16-byte chunk q (K slots 8q..8q+7) of patch pixel p (conv_patch_h2.hip:hp_off)
-__device__ __forceinline__ unsigned hr_off(int p, int q) { return (unsigned)(p * 64 + ((q ^ (((p >> 2) & 1) << 1)) << 4)); }
-
-typedef int hr_i32x4 __attribute__((ext_vector_type(4)));
 
 // DBG (tuning only, builds with -DPADEL_H2P_PROBES, pa_engine_set_tuning "timeline"): the record format of conv_patch_h2q.hip — every
 // wave stamps s_memtime at 5 points of every tap step into an LDS ring of 32 steps (tools/timeline_probe.py --kernel h2r):
@@ -62,17 +54,11 @@ struct HrTile { int n, y0, x0, f0; bool valid; };
 __device__ __forceinline__ HrTile hr_tile(const ConvArgs& a, int v, int vmax, int frags_per_tile) {
     HrTile t;
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;
-    const int q8 = nmt >> 3, r8 = nmt & 7, xcd = v & 7, idx = v >> 3;
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;
-    t.valid = v < vmax && mloc < q8 + (xcd < r8 ? 1 : 0);
-    const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
-    const int txN = (a.Wo + 15) >> 4, tyN = (a.Ho + 7) >> 3;
-    const int tpi = tyN * txN;
-    t.n = mt / tpi;
-    const int rt = mt - t.n * tpi;
-    const int ty = rt / txN, tx = rt - ty * txN;
-    t.y0 = ty * 8; t.x0 = tx * 16;
-    t.f0 = nt * frags_per_tile;
+    const XcdSlot slot = xcd_slot(nmt, nnt, v);
+    t.valid = v < vmax && !xcd_slot_padding(slot);
+    const TileOrigin org = tile_origin<3, 4>(a.Ho, a.Wo, xcd_slot_mtile(slot));
+    t.n = org.n; t.y0 = org.y0; t.x0 = org.x0;
+    t.f0 = slot.nt * frags_per_tile;
     return t;
 }
 
@@ -144,7 +130,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
     HrTile cur = hr_tile(a, v, vmax, 2 * NF);
     if (!cur.valid) return;
     // ---- the patch: span s of a plane = 16 pixels x 64 bytes, lane i -> pixel 16 s + i / 4, physical 16-byte slot i & 3 =
-    // logical chunk q of that pixel (hr_off), which is piece (q & 1) of group (q >> 1) of the pixel's 128 bytes [h0 m0 h1 m1]
+    // logical chunk q of that pixel (swz_off), which is piece (q & 1) of group (q >> 1) of the pixel's 128 bytes [h0 m0 h1 m1]
     // in HBM; the plane's 32 bytes go in through the scalar offset.  Wave w requests spans 3 w .. 3 w + 2 of both planes.
     // The lane offsets of the wave's three spans do not depend on the chunk (it enters through the scalar offset): 3 VGPRs per tile.
     // A tile that does not exist gets a descriptor of zero records: every lane out of range, zeros into a free buffer — the request
@@ -160,16 +146,16 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
 #define PADEL_HR_PARAMS(T_, RS_, SET_)                                                                            \
     do {                                                                                                          \
         const float* const in0_ = a.in + (((long long)(T_).n * a.H + ((T_).y0 - 1)) * a.W + ((T_).x0 - 1)) * a.in_cs + a.in_choff; \
-        RS_ = make_rsrc3(in0_);                                                                                   \
+        RS_ = make_rsrc(in0_);                                                                                    \
         RS_[2] = (T_).valid ? (int)0x80000000u : 0;                                                               \
         const int pl_ = lane >> 2;                                                                                \
         const int pq_ = (lane & 3) ^ (((lane >> 4) & 1) << 1);                                                    \
         const unsigned piece_ = (unsigned)((pq_ >> 1) * 64 + (pq_ & 1) * 16);                                     \
         _Pragma("unroll") for (int k = 0; k < 3; ++k) {                                                           \
             const int pp = (3 * wave + k) * 16 + pl_;                                                             \
-            const int py = pp / kRPW, px = pp - py * kRPW;                                                        \
-            const bool ok = pp < kRNPix && (unsigned)((T_).y0 - 1 + py) < (unsigned)a.H && (unsigned)((T_).x0 - 1 + px) < (unsigned)a.W; \
-            pvo[((SET_) * 3 + k) * 256] = ok ? (unsigned)((py * a.W + px) * a.in_cs * 4) + piece_ : kOOR3;        \
+            const int py = pp / kPatchW, px = pp - py * kPatchW;                                                  \
+            const bool ok = pp < kPatchPix && (unsigned)((T_).y0 - 1 + py) < (unsigned)a.H && (unsigned)((T_).x0 - 1 + px) < (unsigned)a.W; \
+            pvo[((SET_) * 3 + k) * 256] = ok ? (unsigned)((py * a.W + px) * a.in_cs * 4) + piece_ : kOOR;         \
         }                                                                                                         \
     } while (0)
     // the wave's requests of span K_ (both planes) of the chunk at scalar offset SO_ of the tile RS_ / parameter set SET_ describe,
@@ -178,7 +164,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
     do {                                                                                                          \
         const unsigned lb_ = lpw + (unsigned)(BUF_) * (unsigned)kRBufStride;                                      \
         const unsigned vo_ = pvo[((SET_) * 3 + (K_)) * 256];                                                      \
-        dma3<(K_) * 1024>(vo_, RS_, (SO_), lb_); dma3<kRPlaneB + (K_) * 1024>(vo_, RS_, (SO_) + 32u, lb_);        \
+        lds_dma<(K_) * 1024>(vo_, RS_, (SO_), lb_); lds_dma<kPatchPadPlaneB + (K_) * 1024>(vo_, RS_, (SO_) + 32u, lb_); \
     } while (0)
 #define PADEL_HR_PATCH(CH_, BUF_, RS_, SET_)                                                                      \
     do {                                                                                                          \
@@ -191,7 +177,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
 #define PADEL_HR_PSPAN8(K_)                                                                                       \
     do {                                                                                                          \
         const unsigned lb_ = lpw + (unsigned)gpar * (unsigned)kRBufStride;                                        \
-        dma3<(K_) * 1024>(vo8[K_], rs8, so8, lb_); dma3<kRPlaneB + (K_) * 1024>(vo8[K_], rs8, so8 + 32u, lb_);    \
+        lds_dma<(K_) * 1024>(vo8[K_], rs8, so8, lb_); lds_dma<kPatchPadPlaneB + (K_) * 1024>(vo8[K_], rs8, so8 + 32u, lb_); \
     } while (0)
 
     // ---- weights: a.wr = [fragment][k-step][h | m][lane][16 bytes]: lane l of fragment j reads bytes [16 l, 16 l + 16) of the
@@ -200,7 +186,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
     const unsigned fragb = (unsigned)(nch * 9) * 2048u;
     const unsigned voffW = (unsigned)lane * 16u;
     i32x4 rsrcW[NF];
-    hr_i32x4 w[3][NF], wm[3][WS ? 1 : NF];        // (wm: the correction plane's operands; unused with WS)
+    i32x4 w[3][NF], wm[3][WS ? 1 : NF];        // (wm: the correction plane's operands; unused with WS)
     unsigned s_kb = 0;                            // byte offset of the current chunk's first k-step inside a fragment
     // tap TT_ (0..10, relative to the current chunk: 9 and 10 are the next chunk's first two) into register set SET_; the reads of
     // the last chunk's 9 / 10 run up to 4 KB past a fragment (into the next fragment, or the slack behind the copy)
@@ -228,7 +214,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
                          : "n"((BASE_) + kWQ * NW) : "memory");                                                   \
     } while (0)
 
-    // ---- row reads: patch pixel p = p0 + d with p0 = 72 wr + lr (the wave's row 0 at kx = 0) and d = 18 R + KX; hr_off's swizzle
+    // ---- row reads: patch pixel p = p0 + d with p0 = 72 wr + lr (the wave's row 0 at kx = 0) and d = 18 R + KX; swz_off's swizzle
     // term depends on bit 2 of p only, i.e. on d & 7 (adding a multiple of 8 leaves bit 2 alone): eight lane addresses, everything
     // else of a read is an immediate (64 d, + the m plane).  The two patch buffers sit 32 KB apart, so that the chunk hand-over is
     // one XOR per address; a read costs no VALU at all (the first version recomputed ~8 VALU per read: the ky = 2 taps, four
@@ -240,10 +226,10 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
     // input row R_ (0..5 of the wave's window) at column shift KX_ of the buffer rbase points into, into slot R_ & 3
 #define PADEL_HR_READROW(R_, KX_)                                                                                 \
     do {                                                                                                          \
-        constexpr int d_ = (R_) * kRPW + (KX_);                                                                   \
+        constexpr int d_ = (R_) * kPatchW + (KX_);                                                                \
         const char* p_ = ldsb + rbase[d_ & 7];                                                                    \
         ah[(R_) & 3] = *reinterpret_cast<const h16x8*>(p_ + d_ * 64);                                             \
-        am[(R_) & 3] = *reinterpret_cast<const h16x8*>(p_ + d_ * 64 + kRPlaneB);                                  \
+        am[(R_) & 3] = *reinterpret_cast<const h16x8*>(p_ + d_ * 64 + kPatchPadPlaneB);                           \
     } while (0)
     // the 6 products of output row F_ at tap row KY_ (its input row F_ + KY_ sits in slot (F_ + KY_) & 3) with weight set SET_;
     // FIRST_: tap 0 starts the chunk's main chain from the MFMA's constant-0 C operand (bitwise 0 + x)
@@ -324,7 +310,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
             if constexpr (kLateW && PADEL_HR_ON(256)) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);                   \
             /* every read of this chunk's patch has returned (row 5 was read under tap 7; lgkmcnt(0) costs nothing here), */ \
             /* and the wave's own requests of the next chunk's patch landed long ago (in order in front of W(8)) */ \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                    \
+            lds_fence();                                                                                          \
             if constexpr (PADEL_HR_ON(64)) __builtin_amdgcn_s_barrier();                                          \
             asm volatile("" ::: "memory");                                                                        \
             PADEL_HR_STAMP(T_, 2); PADEL_HR_STAMP(T_, 3);                                                         \
@@ -372,7 +358,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
 #pragma unroll
         for (int j = 0; j < NF; ++j) {
             const int frag = min(cur.f0 + NF * wc + j, a.n16 - 1);   // fragments beyond the matrix: any valid rows (never stored)
-            rsrcW[j] = make_rsrc3(reinterpret_cast<const char*>(a.wr) + (long long)frag * fragb);
+            rsrcW[j] = make_rsrc(reinterpret_cast<const char*>(a.wr) + (long long)frag * fragb);
         }
         s_kb = 0;
         // W(0), W(1), P(1): the order the steady state leaves behind tap 8 (P(0): before the loop / tap 8 of the previous tile's
@@ -382,16 +368,16 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
         PADEL_HR_PATCH(1, gpar ^ 1, rsrcP, tpar);
         const HrTile nxt = hr_tile(a, v + G, vmax, 2 * NF);        // (the tile arithmetic runs under the latency of the requests above)
         PADEL_HR_PARAMS(nxt, rsrcPn, tpar ^ 1);
-        if constexpr ((ABL & 256) != 0) { wait_vm3<0>(); for (int j = 0; j < NF; ++j) { w[2][j] = w[0][j]; if constexpr (!WS) wm[2][j] = wm[0][j]; } }      // (probe: no weight requests inside the loop)
+        if constexpr ((ABL & 256) != 0) { wait_vm<0>(); for (int j = 0; j < NF; ++j) { w[2][j] = w[0][j]; if constexpr (!WS) wm[2][j] = wm[0][j]; } }      // (probe: no weight requests inside the loop)
         if (first) {
-            wait_vm3<2 * NW + 6>();               // P(0) landed (W(0), W(1), P(1) may be in flight)
+            wait_vm<2 * NW + 6>();               // P(0) landed (W(0), W(1), P(1) may be in flight)
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
         {
             int lr_ = lr;
             asm volatile("" : "+v"(lr_));
-            const int p0 = 4 * wr * kRPW + lr_;
+            const int p0 = 4 * wr * kPatchW + lr_;
 #pragma unroll
             for (int r = 0; r < 8; ++r)
                 rbase[r] = (unsigned)(p0 * 64 + ((lq ^ ((((p0 + r) >> 2) & 1) << 1)) << 4)) ^ (gpar ? (unsigned)kRBufStride : 0u);
@@ -442,7 +428,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
         tpar ^= 1;
         first = false;
     }
-    wait_vm3<0>();                                // the tail's requests (zeros into a free buffer, weights nobody uses) before the LDS is released
+    wait_vm<0>();                                // the tail's requests (zeros into a free buffer, weights nobody uses) before the LDS is released
 #undef PADEL_HR_STEP
 #undef PADEL_HR_MFMA_ROW
 #undef PADEL_HR_READROW
@@ -480,8 +466,8 @@ __global__ void __launch_bounds__(256) h2r_repack_kernel(const char* __restrict_
     const int l = (int)(i & 63), pl = (int)((i >> 6) & 1);
     const long long ft = i >> 7;
     const int t = (int)(ft % ksteps), f = (int)(ft / ksteps);
-    const h2_u32x4 v = *reinterpret_cast<const h2_u32x4*>(w + ((long long)(f * 16 + (l & 15)) * ksteps + t) * 128 + pl * 64 + (l >> 4) * 16);
-    *reinterpret_cast<h2_u32x4*>(wr + i * 16) = v;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(w + ((long long)(f * 16 + (l & 15)) * ksteps + t) * 128 + pl * 64 + (l >> 4) * 16);
+    *reinterpret_cast<u32x4*>(wr + i * 16) = v;
 }
 
 // PA_CONV_W_SINGLE is a promise of the CALLER's (public C-ABI): the m plane of the packed weights is all zero.  Checked once per
@@ -489,7 +475,7 @@ __global__ void __launch_bounds__(256) h2r_repack_kernel(const char* __restrict_
 __global__ void __launch_bounds__(256) h2_mplane_check_kernel(const unsigned* __restrict__ w, long long n_steps, unsigned* flag) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;          // one thread per 16 bytes of an m half (64 B = 4 threads)
     if (i >= n_steps * 4) return;
-    const h2_u32x4 v = *reinterpret_cast<const h2_u32x4*>(w + (i >> 2) * 32 + 16 + (i & 3) * 4);
+    const u32x4 v = *reinterpret_cast<const u32x4*>(w + (i >> 2) * 32 + 16 + (i & 3) * 4);
     if (((v[0] | v[1] | v[2] | v[3]) & 0x7FFF7FFFu) != 0u) atomicOr(flag, 1u);
 }
 

@@ -18,15 +18,10 @@ namespace padel {
 
 namespace {
 
-constexpr int kVPW = 18, kVNPix = 18 * 18;            // 16 x 16 output pixels + halo
-constexpr int kVSpans = (kVNPix + 15) / 16;            // 21 spans of 16 pixels x 64 B per chunk plane
+constexpr int kVSpans = (kPatchSqPix + 15) / 16;            // 21 spans of 16 pixels x 64 B per chunk plane
 constexpr int kVPlaneB = kVSpans * 1024;
-constexpr int kVTSpans = (kVNPix + 31) / 32;           // 11 spans of 32 pixels x 32 B per tail plane
+constexpr int kVTSpans = (kPatchSqPix + 31) / 32;           // 11 spans of 32 pixels x 32 B per tail plane
 constexpr int kVTPlaneB = kVTSpans * 1024;
-
-__device__ __forceinline__ unsigned hv_tail_off(int p, int s) { return (unsigned)(p * 32 + ((s ^ ((p >> 3) & 1)) << 4)); }
-
-typedef int hv_i32x4 __attribute__((ext_vector_type(4)));
 
 }  // namespace
 
@@ -50,19 +45,15 @@ __global__ void __launch_bounds__(256, 2) conv_h2v_kernel(const ConvArgs a) {
     // XCD-aware 1-D tile map: the channel tiles of one pixel patch are neighbours on one XCD
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;
     const int bid = blockIdx.x;
-    const int q8 = nmt >> 3, r8 = nmt & 7, xcd = bid & 7, idx = bid >> 3;
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;
-    if (mloc >= q8 + (xcd < r8 ? 1 : 0)) return;
-    const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
-    const int txN = (a.Wo + 15) >> 4, tyN = (a.Ho + 15) >> 4;
-    const int tpi = tyN * txN;
-    const int n = mt / tpi, rt = mt - n * tpi;
-    const int ty = rt / txN, tx = rt - ty * txN;
-    const int y0 = ty * 16, x0 = tx * 16;
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);
+    if (xcd_slot_padding(slot)) return;
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;
+    const TileOrigin org = tile_origin<4, 4>(a.Ho, a.Wo, mt);
+    const int n = org.n, y0 = org.y0, x0 = org.x0;
     const int f0 = nt * NF;
 
     const float* const in0 = a.in + (((long long)n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * a.in_cs + a.in_choff;
-    const i32x4 rsrcP = make_rsrc3(in0);
+    const i32x4 rsrcP = make_rsrc(in0);
     const unsigned lp0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds);
 
     // ---- the whole input, requested up front (spans round-robin over the 4 waves; conv_patch_h2w.hip)
@@ -73,11 +64,11 @@ __global__ void __launch_bounds__(256, 2) conv_h2v_kernel(const ConvArgs a) {
 #define PADEL_HV_PSPAN(S_)                                                                                        \
         if (((S_) & 3) == wave) {                                                                                 \
             const int pp_ = (S_) * 16 + p_lane;                                                                   \
-            const int py_ = pp_ / kVPW, px_ = pp_ - py_ * kVPW;                                                   \
-            const bool ok_ = pp_ < kVNPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
-            const unsigned vo_ = ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 4) + p_piece : kOOR3;             \
-            dma3<(S_) * 1024>(vo_, rsrcP, 0u, lp0);                                                               \
-            dma3<kVPlaneB + (S_) * 1024>(vo_, rsrcP, 32u, lp0);                                                   \
+            const int py_ = pp_ / kPatchW, px_ = pp_ - py_ * kPatchW;                                             \
+            const bool ok_ = pp_ < kPatchSqPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
+            const unsigned vo_ = ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 4) + p_piece : kOOR;              \
+            lds_dma<(S_) * 1024>(vo_, rsrcP, 0u, lp0);                                                            \
+            lds_dma<kVPlaneB + (S_) * 1024>(vo_, rsrcP, 32u, lp0);                                                \
         }
         PADEL_HV_PSPAN(0) PADEL_HV_PSPAN(1) PADEL_HV_PSPAN(2) PADEL_HV_PSPAN(3) PADEL_HV_PSPAN(4) PADEL_HV_PSPAN(5) PADEL_HV_PSPAN(6)
         PADEL_HV_PSPAN(7) PADEL_HV_PSPAN(8) PADEL_HV_PSPAN(9) PADEL_HV_PSPAN(10) PADEL_HV_PSPAN(11) PADEL_HV_PSPAN(12) PADEL_HV_PSPAN(13)
@@ -91,11 +82,11 @@ __global__ void __launch_bounds__(256, 2) conv_h2v_kernel(const ConvArgs a) {
 #define PADEL_HV_TSPAN(S_)                                                                                        \
         if (((S_) & 3) == ((wave + 1) & 3)) {                                                                     \
             const int pp_ = (S_) * 32 + t_lane;                                                                   \
-            const int py_ = pp_ / kVPW, px_ = pp_ - py_ * kVPW;                                                   \
-            const bool ok_ = pp_ < kVNPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
-            const unsigned vo_ = ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 4) + t_piece : kOOR3;             \
-            dma3<PATCH_B + (S_) * 1024>(vo_, rsrcP, t_so, lp0);                                                   \
-            dma3<PATCH_B + kVTPlaneB + (S_) * 1024>(vo_, rsrcP, t_so + 32u, lp0);                                 \
+            const int py_ = pp_ / kPatchW, px_ = pp_ - py_ * kPatchW;                                             \
+            const bool ok_ = pp_ < kPatchSqPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
+            const unsigned vo_ = ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 4) + t_piece : kOOR;              \
+            lds_dma<PATCH_B + (S_) * 1024>(vo_, rsrcP, t_so, lp0);                                                \
+            lds_dma<PATCH_B + kVTPlaneB + (S_) * 1024>(vo_, rsrcP, t_so + 32u, lp0);                              \
         }
         PADEL_HV_TSPAN(0) PADEL_HV_TSPAN(1) PADEL_HV_TSPAN(2) PADEL_HV_TSPAN(3) PADEL_HV_TSPAN(4) PADEL_HV_TSPAN(5)
         PADEL_HV_TSPAN(6) PADEL_HV_TSPAN(7) PADEL_HV_TSPAN(8) PADEL_HV_TSPAN(9) PADEL_HV_TSPAN(10)
@@ -109,9 +100,9 @@ __global__ void __launch_bounds__(256, 2) conv_h2v_kernel(const ConvArgs a) {
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
         const int frag = min(f0 + j, a.n16 - 1);     // fragments beyond the matrix: any valid rows (never stored)
-        rsrcW[j] = make_rsrc3(reinterpret_cast<const char*>(a.wr) + (long long)frag * fragb);
+        rsrcW[j] = make_rsrc(reinterpret_cast<const char*>(a.wr) + (long long)frag * fragb);
     }
-    hv_i32x4 w[3][NF], wm[3][WS ? 1 : NF];
+    i32x4 w[3][NF], wm[3][WS ? 1 : NF];
 #define PADEL_HV_LOADW(ST_)                                                                                       \
     do {                                                                                                          \
         const unsigned so_ = (unsigned)((ST_) * 2048);                                                            \
@@ -144,11 +135,11 @@ __global__ void __launch_bounds__(256, 2) conv_h2v_kernel(const ConvArgs a) {
     if constexpr (CHUNK) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const int p0 = 4 * wave * kVPW + lr;
+            const int p0 = 4 * wave * kPatchW + lr;
             rbase[r] = (unsigned)(p0 * 64 + ((lq ^ ((((p0 + r) >> 2) & 1) << 1)) << 4));
         }
     }
-    const int rd_pix = 4 * wave * kVPW + lr;
+    const int rd_pix = 4 * wave * kPatchW + lr;
 
     f32x4 acc[MF][NF], part[MF][NF], cross[MF][NF];
 #pragma unroll
@@ -158,7 +149,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2v_kernel(const ConvArgs a) {
     h16x8 ah[4], am[4];
 #define PADEL_HV_READROW(R_, KX_)                                                                                 \
     do {                                                                                                          \
-        constexpr int d_ = (R_) * kVPW + (KX_);                                                                   \
+        constexpr int d_ = (R_) * kPatchW + (KX_);                                                                \
         const char* p_ = ldsb + rbase[d_ & 7];                                                                    \
         ah[(R_) & 3] = *reinterpret_cast<const h16x8*>(p_ + d_ * 64);                                             \
         am[(R_) & 3] = *reinterpret_cast<const h16x8*>(p_ + d_ * 64 + kVPlaneB);                                  \
@@ -222,8 +213,8 @@ __global__ void __launch_bounds__(256, 2) conv_h2v_kernel(const ConvArgs a) {
         int rp_ = rd_pix;                                                                                         \
         asm volatile("" : "+v"(rp_));                                                                             \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
-            const int pa_ = rp_ + (f + h2_tap_ky(ta_)) * kVPW + h2_tap_kx(ta_), pb_ = rp_ + (f + h2_tap_ky(tb_)) * kVPW + h2_tap_kx(tb_); \
-            const char* p_ = ldsb + PATCH_B + hv_tail_off((lq >> 1) ? pb_ : pa_, lq & 1);                         \
+            const int pa_ = rp_ + (f + h2_tap_ky(ta_)) * kPatchW + h2_tap_kx(ta_), pb_ = rp_ + (f + h2_tap_ky(tb_)) * kPatchW + h2_tap_kx(tb_); \
+            const char* p_ = ldsb + PATCH_B + swz_tail_off((lq >> 1) ? pb_ : pa_, lq & 1);                        \
             ah[f] = *reinterpret_cast<const h16x8*>(p_);                                                          \
             am[f] = *reinterpret_cast<const h16x8*>(p_ + kVTPlaneB);                                              \
         }                                                                                                         \
@@ -241,7 +232,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2v_kernel(const ConvArgs a) {
     // requests: with W(0), W(1) allowed in flight)
     PADEL_HV_LOADW(0);
     if constexpr (NSTEPS > 1) PADEL_HV_LOADW(1);
-    wait_vm3<NW * (NSTEPS > 1 ? 2 : 1)>();
+    wait_vm<NW * (NSTEPS > 1 ? 2 : 1)>();
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if constexpr (CHUNK) {

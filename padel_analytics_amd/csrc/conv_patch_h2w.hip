@@ -20,14 +20,10 @@ namespace padel {
 
 namespace {
 
-constexpr int kWPW = 18, kWNPix = 18 * 18;            // 16 x 16 output pixels + halo
-constexpr int kWSpans = (kWNPix + 15) / 16;            // 21 spans of 16 pixels x 64 B per chunk plane
+constexpr int kWSpans = (kPatchSqPix + 15) / 16;            // 21 spans of 16 pixels x 64 B per chunk plane
 constexpr int kWPlaneB = kWSpans * 1024;
-constexpr int kWTSpans = (kWNPix + 31) / 32;           // 11 spans of 32 pixels x 32 B per tail plane
+constexpr int kWTSpans = (kPatchSqPix + 31) / 32;           // 11 spans of 32 pixels x 32 B per tail plane
 constexpr int kWTPlaneB = kWTSpans * 1024;
-
-__device__ __forceinline__ unsigned hw_off(int p, int q) { return (unsigned)(p * 64 + ((q ^ (((p >> 2) & 1) << 1)) << 4)); }
-__device__ __forceinline__ unsigned hw_tail_off(int p, int s) { return (unsigned)(p * 32 + ((s ^ ((p >> 3) & 1)) << 4)); }
 
 }  // namespace
 
@@ -53,24 +49,20 @@ __global__ void __launch_bounds__(256, 2) conv_h2w_kernel(const ConvArgs a) {
     // XCD-aware 1-D tile map: the channel tiles of one pixel patch are neighbours on one XCD
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;
     const int bid = blockIdx.x;
-    const int q8 = nmt >> 3, r8 = nmt & 7, xcd = bid & 7, idx = bid >> 3;
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;
-    if (mloc >= q8 + (xcd < r8 ? 1 : 0)) return;
-    const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
-    const int txN = (a.Wo + 15) >> 4, tyN = (a.Ho + 15) >> 4;
-    const int tpi = tyN * txN;
-    const int n = mt / tpi, rt = mt - n * tpi;
-    const int ty = rt / txN, tx = rt - ty * txN;
-    const int y0 = ty * 16, x0 = tx * 16;
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);
+    if (xcd_slot_padding(slot)) return;
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;
+    const TileOrigin org = tile_origin<4, 4>(a.Ho, a.Wo, mt);
+    const int n = org.n, y0 = org.y0, x0 = org.x0;
     const int f0 = nt * NF;
 
     const float* const in0 = a.in + (((long long)n * a.H + (y0 - 1)) * a.W + (x0 - 1)) * a.in_cs + a.in_choff;
-    const i32x4 rsrcP = make_rsrc3(in0);
+    const i32x4 rsrcP = make_rsrc(in0);
     const unsigned lp0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds);
 
     // ---- the whole input, requested up front (spans round-robin over the 4 waves).
     // chunk plane span s: 16 pixels x 64 bytes, lane i -> pixel 16 s + i / 4, physical 16-byte slot i & 3 = logical chunk q of
-    // that pixel (hw_off), piece (q & 1) of group (q >> 1) of the pixel's 128 bytes [h0 m0 h1 m1]; + 32 bytes for the m plane
+    // that pixel (swz_off), piece (q & 1) of group (q >> 1) of the pixel's 128 bytes [h0 m0 h1 m1]; + 32 bytes for the m plane
     if constexpr (CHUNK) {
         const int p_lane = lane >> 2;
         const int p_q = (lane & 3) ^ (((lane >> 4) & 1) << 1);
@@ -78,11 +70,11 @@ __global__ void __launch_bounds__(256, 2) conv_h2w_kernel(const ConvArgs a) {
 #define PADEL_HW_PSPAN(S_)                                                                                        \
         if (((S_) & 3) == wave) {                                                                                 \
             const int pp_ = (S_) * 16 + p_lane;                                                                   \
-            const int py_ = pp_ / kWPW, px_ = pp_ - py_ * kWPW;                                                   \
-            const bool ok_ = pp_ < kWNPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
-            const unsigned vo_ = ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 4) + p_piece : kOOR3;             \
-            dma3<(S_) * 1024>(vo_, rsrcP, 0u, lp0);                                                               \
-            dma3<kWPlaneB + (S_) * 1024>(vo_, rsrcP, 32u, lp0);                                                   \
+            const int py_ = pp_ / kPatchW, px_ = pp_ - py_ * kPatchW;                                             \
+            const bool ok_ = pp_ < kPatchSqPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
+            const unsigned vo_ = ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 4) + p_piece : kOOR;              \
+            lds_dma<(S_) * 1024>(vo_, rsrcP, 0u, lp0);                                                            \
+            lds_dma<kWPlaneB + (S_) * 1024>(vo_, rsrcP, 32u, lp0);                                                \
         }
         PADEL_HW_PSPAN(0) PADEL_HW_PSPAN(1) PADEL_HW_PSPAN(2) PADEL_HW_PSPAN(3) PADEL_HW_PSPAN(4) PADEL_HW_PSPAN(5) PADEL_HW_PSPAN(6)
         PADEL_HW_PSPAN(7) PADEL_HW_PSPAN(8) PADEL_HW_PSPAN(9) PADEL_HW_PSPAN(10) PADEL_HW_PSPAN(11) PADEL_HW_PSPAN(12) PADEL_HW_PSPAN(13)
@@ -98,11 +90,11 @@ __global__ void __launch_bounds__(256, 2) conv_h2w_kernel(const ConvArgs a) {
 #define PADEL_HW_TSPAN(S_)                                                                                        \
         if (((S_) & 3) == ((wave + 1) & 3)) {                                                                     \
             const int pp_ = (S_) * 32 + t_lane;                                                                   \
-            const int py_ = pp_ / kWPW, px_ = pp_ - py_ * kWPW;                                                   \
-            const bool ok_ = pp_ < kWNPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
-            const unsigned vo_ = ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 4) + t_piece : kOOR3;             \
-            dma3<PATCH_B + (S_) * 1024>(vo_, rsrcP, t_so, lp0);                                                   \
-            dma3<PATCH_B + kWTPlaneB + (S_) * 1024>(vo_, rsrcP, t_so + 32u, lp0);                                 \
+            const int py_ = pp_ / kPatchW, px_ = pp_ - py_ * kPatchW;                                             \
+            const bool ok_ = pp_ < kPatchSqPix && (unsigned)(y0 - 1 + py_) < (unsigned)a.H && (unsigned)(x0 - 1 + px_) < (unsigned)a.W; \
+            const unsigned vo_ = ok_ ? (unsigned)((py_ * a.W + px_) * a.in_cs * 4) + t_piece : kOOR;              \
+            lds_dma<PATCH_B + (S_) * 1024>(vo_, rsrcP, t_so, lp0);                                                \
+            lds_dma<PATCH_B + kWTPlaneB + (S_) * 1024>(vo_, rsrcP, t_so + 32u, lp0);                              \
         }
         PADEL_HW_TSPAN(0) PADEL_HW_TSPAN(1) PADEL_HW_TSPAN(2) PADEL_HW_TSPAN(3) PADEL_HW_TSPAN(4) PADEL_HW_TSPAN(5)
         PADEL_HW_TSPAN(6) PADEL_HW_TSPAN(7) PADEL_HW_TSPAN(8) PADEL_HW_TSPAN(9) PADEL_HW_TSPAN(10)
@@ -124,19 +116,19 @@ __global__ void __launch_bounds__(256, 2) conv_h2w_kernel(const ConvArgs a) {
         const int frag = min(f0 + min(g, NF - 1), a.n16 - 1);
         voffB[k] = (unsigned)(((frag - f0) * 16 + b_row) * rowb + pl * 64 + b_sc * 16);
     }
-    const i32x4 rsrcB = make_rsrc3(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
+    const i32x4 rsrcB = make_rsrc(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
     const unsigned lw0 = __builtin_amdgcn_readfirstlane(lp0 + (unsigned)(PATCH_B + TPATCH_B) + (unsigned)wave * 1024u);
     const unsigned lw1 = __builtin_amdgcn_readfirstlane(lw0 + (unsigned)BSTAGE_B);
 #define PADEL_HW_DMAB(ST_)                                                                                        \
     do {                                                                                                          \
         const unsigned lw_ = ((ST_) & 1) ? lw1 : lw0;                                                             \
-        if (haveB[0]) dma3<0>(voffB[0], rsrcB, (unsigned)(ST_) * 128u, lw_);                                      \
-        if (haveB[1]) dma3<4096>(voffB[1], rsrcB, (unsigned)(ST_) * 128u, lw_);                                   \
+        if (haveB[0]) lds_dma<0>(voffB[0], rsrcB, (unsigned)(ST_) * 128u, lw_);                                   \
+        if (haveB[1]) lds_dma<4096>(voffB[1], rsrcB, (unsigned)(ST_) * 128u, lw_);                                \
     } while (0)
     const int ld_off = lr * 16 + ((lq ^ ((4 - ((lr >> 2) & 3)) & 3)) << 2);      // floats
     const float* const b_rd0 = lds + (PATCH_B + TPATCH_B) / 4 + ld_off;
     const float* const b_rd1 = b_rd0 + BSTAGE_B / 4;
-    const int rd_pix = 4 * wave * kWPW + lr;               // patch pixel of the wave's row 0, kx = 0
+    const int rd_pix = 4 * wave * kPatchW + lr;               // patch pixel of the wave's row 0, kx = 0
 
     f32x4 acc[MF][NF], part[MF][NF], cross[MF][NF];
 #pragma unroll
@@ -146,7 +138,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2w_kernel(const ConvArgs a) {
     h16x8 ah[4], am[4], wh[NF], wm[NF];       // full chunk: input rows in 4 sliding slots (row r of the current kx in slot r & 3)
 #define PADEL_HW_READROW(R_, KX_)                                                                                 \
     do {                                                                                                          \
-        const char* p_ = ldsb + hw_off(rp_ + (R_) * kWPW + (KX_), lq);                                            \
+        const char* p_ = ldsb + swz_off(rp_ + (R_) * kPatchW + (KX_), lq);                                        \
         ah[(R_) & 3] = *reinterpret_cast<const h16x8*>(p_);                                                       \
         am[(R_) & 3] = *reinterpret_cast<const h16x8*>(p_ + kWPlaneB);                                            \
     } while (0)
@@ -175,7 +167,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2w_kernel(const ConvArgs a) {
     // publishes the patches
 #define PADEL_HW_SYNC(ST_)                                                                                        \
     do {                                                                                                          \
-        wait_vm3<0>();                                                                                            \
+        wait_vm<0>();                                                                                             \
         __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
         PADEL_HW_READB(ST_);                                                                                      \
@@ -211,8 +203,8 @@ __global__ void __launch_bounds__(256, 2) conv_h2w_kernel(const ConvArgs a) {
         asm volatile("" : "+v"(rp_));                                                                             \
         if constexpr ((ST_) > 0) {                                                                                \
             _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                      \
-                const int pa_ = rp_ + (f + h2_tap_ky(ta_)) * kWPW + h2_tap_kx(ta_), pb_ = rp_ + (f + h2_tap_ky(tb_)) * kWPW + h2_tap_kx(tb_); \
-                const char* p_ = ldsb + PATCH_B + hw_tail_off((lq >> 1) ? pb_ : pa_, lq & 1);                     \
+                const int pa_ = rp_ + (f + h2_tap_ky(ta_)) * kPatchW + h2_tap_kx(ta_), pb_ = rp_ + (f + h2_tap_ky(tb_)) * kPatchW + h2_tap_kx(tb_); \
+                const char* p_ = ldsb + PATCH_B + swz_tail_off((lq >> 1) ? pb_ : pa_, lq & 1);                    \
                 ah[f] = *reinterpret_cast<const h16x8*>(p_);                                                      \
                 am[f] = *reinterpret_cast<const h16x8*>(p_ + kWTPlaneB);                                          \
             }                                                                                                     \
@@ -220,8 +212,8 @@ __global__ void __launch_bounds__(256, 2) conv_h2w_kernel(const ConvArgs a) {
         PADEL_HW_SYNC(ST_);                                                                                       \
         if constexpr ((ST_) == 0) {                                                                               \
             _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                      \
-                const int pa_ = rp_ + (f + h2_tap_ky(ta_)) * kWPW + h2_tap_kx(ta_), pb_ = rp_ + (f + h2_tap_ky(tb_)) * kWPW + h2_tap_kx(tb_); \
-                const char* p_ = ldsb + PATCH_B + hw_tail_off((lq >> 1) ? pb_ : pa_, lq & 1);                     \
+                const int pa_ = rp_ + (f + h2_tap_ky(ta_)) * kPatchW + h2_tap_kx(ta_), pb_ = rp_ + (f + h2_tap_ky(tb_)) * kPatchW + h2_tap_kx(tb_); \
+                const char* p_ = ldsb + PATCH_B + swz_tail_off((lq >> 1) ? pb_ : pa_, lq & 1);                    \
                 ah[f] = *reinterpret_cast<const h16x8*>(p_);                                                      \
                 am[f] = *reinterpret_cast<const h16x8*>(p_ + kWTPlaneB);                                          \
             }                                                                                                     \
@@ -253,7 +245,7 @@ __global__ void __launch_bounds__(256, 2) conv_h2w_kernel(const ConvArgs a) {
         PADEL_HW_TSTEP(0, S0); PADEL_HW_TSTEP(1, S0 + 1); PADEL_HW_TSTEP(2, S0 + 2); PADEL_HW_TSTEP(3, S0 + 3); PADEL_HW_TSTEP(4, S0 + 4);
         PADEL_HW_FLUSH();
     }
-    wait_vm3<0>();
+    wait_vm<0>();
 #undef PADEL_HW_FLUSH
 #undef PADEL_HW_TSTEP
 #undef PADEL_HW_STEP

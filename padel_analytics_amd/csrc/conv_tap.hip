@@ -26,15 +26,12 @@
 // block has 16 steps; 16 % 4 == 0 keeps the stage a compile-time constant) and a per-step `J < steps` guard for
 // the last, shorter block.
 #include "kernels.h"
+#include "conv_prims.h"
 #include <cmath>
-#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 
 namespace padel {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float act_apply5(float v, int act) {
     if (act == ACT_SILU) return v / (1.0f + expf(-v));
@@ -42,37 +39,6 @@ __device__ __forceinline__ float act_apply5(float v, int act) {
     if (act == ACT_SIGMOID) return 1.0f / (1.0f + expf(-v));
     if (act == ACT_LEAKY) return v >= 0.0f ? v : 0.01f * v;
     return v;
-}
-
-// raw buffer descriptor (gfx9 family): base, stride 0, num_records = 2 GiB, 32-bit data format
-__device__ __forceinline__ i32x4 make_rsrc(const float* base) {
-    const unsigned long long b = (unsigned long long)(uintptr_t)base;
-    i32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    r[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xFFFFu));
-    r[2] = (int)0x80000000u;
-    r[3] = 0x00020000;
-    return r;
-}
-constexpr unsigned kOutOfRange = 0xFFFFFFF0u;      // >= num_records: the load returns zeros
-
-// 64 lanes x 16 bytes, buffer (rsrc base + soff + per-lane voff) -> LDS (lds_wave + LDS_IMM + 16 * lane)
-template <int LDS_IMM>
-__device__ __forceinline__ void dma16(unsigned voff, i32x4 rsrc, unsigned soff, unsigned lds_wave) {
-    asm volatile("s_add_u32 m0, %[lb], %[imm]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[vo], %[rs], %[so] offen lds"
-                 :
-                 : [lb] "s"(lds_wave), [imm] "n"(LDS_IMM), [vo] "v"(voff), [rs] "s"(rsrc), [so] "s"(soff)
-                 : "memory", "scc");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// n / d for 0 <= n < 2^31 with the (magic, shift) pair of fill_fastdiv (kernels.h): 3 instructions instead of ~35
-__device__ __forceinline__ int fastdiv(int n, unsigned magic, unsigned shift) {
-    return (int)((__umulhi((unsigned)n, magic) + (unsigned)n) >> shift);
 }
 
 constexpr int tap_min_waves(int nw, int frags) {
@@ -86,11 +52,11 @@ constexpr int tap_min_waves(int nw, int frags) {
 #define PADEL_TAP_DMA(SR_, SA_, SB_, VA0_, VA1_)                                                                  \
     do {                                                                                                          \
         const unsigned sa_ = (SA_), sb_ = (SB_);                                                                  \
-        dma16<(SR_) * STAGE_B>((VA0_), rsrcA, sa_, lds_wave);                                                     \
-        if constexpr (AP >= 2) dma16<(SR_) * STAGE_B + RP * 64>((VA1_), rsrcA, sa_, lds_wave);                    \
-        if constexpr (BFULL >= 1) dma16<(SR_) * STAGE_B + BM * 64>(voffB[0], rsrcB, sb_, lds_wave);               \
-        if constexpr (BFULL >= 2) dma16<(SR_) * STAGE_B + BM * 64 + RP * 64>(voffB[1], rsrcB, sb_, lds_wave);     \
-        if constexpr (BP > BFULL) { if (b_last) dma16<(SR_) * STAGE_B + BM * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, sb_, lds_wave); } \
+        lds_dma<(SR_) * STAGE_B>((VA0_), rsrcA, sa_, lds_wave);                                                   \
+        if constexpr (AP >= 2) lds_dma<(SR_) * STAGE_B + RP * 64>((VA1_), rsrcA, sa_, lds_wave);                  \
+        if constexpr (BFULL >= 1) lds_dma<(SR_) * STAGE_B + BM * 64>(voffB[0], rsrcB, sb_, lds_wave);             \
+        if constexpr (BFULL >= 2) lds_dma<(SR_) * STAGE_B + BM * 64 + RP * 64>(voffB[1], rsrcB, sb_, lds_wave);   \
+        if constexpr (BP > BFULL) { if (b_last) lds_dma<(SR_) * STAGE_B + BM * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, sb_, lds_wave); } \
     } while (0)
 
 // fragments of ring stage ST_ -> MF * NF * 4 MFMAs on `part`
@@ -199,8 +165,7 @@ __device__ __forceinline__ void tap_epilogue(const ConvArgs& a, const f32x4 (&ac
     const int wm = wave / WN, wn = wave % WN;                                                                     \
     const int nmt = a.n_mtiles;                                                                                   \
     const int bid = blockIdx.x;                                                                                   \
-    const int q = nmt >> 3, r = nmt & 7, xcd = bid & 7, idx = bid >> 3;                                           \
-    const int mt = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;                                 \
+    const int mt = xcd_slot_mtile(xcd_slot(nmt, 1, bid));    /* 2-D grid: x walks the pixel tiles XCD by XCD, no padding ids */ \
     const int m0 = mt * BM;                                                                                       \
     const int f0 = blockIdx.y * (WN * NF);   /* first 16-channel fragment of this workgroup */                    \
     const int HoWo = a.Ho * a.Wo;                                                                                 \
@@ -272,7 +237,7 @@ __global__ void __launch_bounds__(64 * WM * WN, tap_min_waves(WM * WN, MF * NF))
             vx[d] = (unsigned)(ox * a.stride - 1 + d) < (unsigned)a.W;
         }
 #pragma unroll
-        for (int t = 0; t < 9; ++t) voffA[p][t] = (vy[t / 3] && vx[t % 3]) ? off : kOutOfRange;
+        for (int t = 0; t < 9; ++t) voffA[p][t] = (vy[t / 3] && vx[t % 3]) ? off : kOOR;
     }
     // base of the A descriptor: channel slice of the tap-(0,0) pixel of row m0 (may lie below a.in: never dereferenced there)
     const i32x4 rsrcA = make_rsrc(a.in + ((lin0 - (a.W + 1)) * a.in_cs + a.in_choff));
@@ -312,7 +277,7 @@ __global__ void __launch_bounds__(64 * WM * WN, tap_min_waves(WM * WN, MF * NF))
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         if constexpr (DBG) {                                                                                      \
             PADEL_TAP_FRAGS_DBG((J) % 3)                                                                          \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                    \
+            lds_fence();                                                                                          \
             PADEL_TAP_STAMP(J, 3);                                                                                \
             PADEL_TAP_MFMAS_DBG();                                                                                \
             PADEL_TAP_STAMP(J, 4);                                                                                \
@@ -401,7 +366,7 @@ __global__ void __launch_bounds__(64 * WM * WN, tap1_min_waves(WM * WN, MF * NF,
         const int oy = fastdiv(rem, a.wo_magic, a.wo_shift);
         const int ox = rem - oy * a.Wo;
         const long long lin = ((long long)n * a.H + oy * a.stride) * a.W + ox * a.stride;
-        voffA[p] = rv ? (unsigned)(((lin - lin0) * a.in_cs + sc * 4) * 4) : kOutOfRange;
+        voffA[p] = rv ? (unsigned)(((lin - lin0) * a.in_cs + sc * 4) * 4) : kOOR;
     }
     const i32x4 rsrcA = make_rsrc(a.in + (lin0 * a.in_cs + a.in_choff));
     PADEL_TAP_WEIGHTS()

@@ -20,47 +20,14 @@
 //   * convs that feed the Detect/Pose decode write fp32 (ConvArgs::out_f32): the head maps stay fp32, so DFL
 //     softmax / box decode / NMS are the same kernels and the same arithmetic as on the fp32 path.
 #include "kernels.h"
+#include "conv_prims.h"
 #include "act_fast.h"
 #include "f16_epilogue.h"
 #include <cmath>
-#include <cstdint>
 
 namespace padel {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-__device__ __forceinline__ i32x4 make_rsrc16(const void* base) {
-    const unsigned long long b = (unsigned long long)(uintptr_t)base;
-    i32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    r[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xFFFFu));
-    r[2] = (int)0x80000000u;
-    r[3] = 0x00020000;
-    return r;
-}
-constexpr unsigned kOutOfRange16 = 0xFFFFFFF0u;
-
-template <int LDS_IMM>
-__device__ __forceinline__ void dma16h(unsigned voff, i32x4 rsrc, unsigned soff, unsigned lds_wave) {
-    asm volatile("s_add_u32 m0, %[lb], %[imm]\n\ts_nop 0\n\tbuffer_load_dwordx4 %[vo], %[rs], %[so] offen lds"
-                 :
-                 : [lb] "s"(lds_wave), [imm] "n"(LDS_IMM), [vo] "v"(voff), [rs] "s"(rsrc), [so] "s"(soff)
-                 : "memory", "scc");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm16() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-__device__ __forceinline__ int fastdiv16(int n, unsigned magic, unsigned shift) {
-    return (int)((__umulhi((unsigned)n, magic) + (unsigned)n) >> shift);
-}
 
 constexpr int min_waves16(int nw, int frags) { return nw == 4 ? (frags <= 6 ? 4 : (frags <= 8 ? 3 : 2)) : 2; }
 
@@ -69,11 +36,11 @@ constexpr int min_waves16(int nw, int frags) { return nw == 4 ? (frags <= 6 ? 4 
 #define PADEL_T16_DMA(SR_, SA_, SB_, VA0_, VA1_)                                                                  \
     do {                                                                                                          \
         const unsigned sa_ = (SA_), sb_ = (SB_);                                                                  \
-        dma16h<(SR_) * STAGE_B>((VA0_), rsrcA, sa_, lds_wave);                                                    \
-        if constexpr (AP >= 2) dma16h<(SR_) * STAGE_B + RP * 64>((VA1_), rsrcA, sa_, lds_wave);                   \
-        if constexpr (BFULL >= 1) dma16h<(SR_) * STAGE_B + BM * 64>(voffB[0], rsrcB, sb_, lds_wave);              \
-        if constexpr (BFULL >= 2) dma16h<(SR_) * STAGE_B + BM * 64 + RP * 64>(voffB[1], rsrcB, sb_, lds_wave);    \
-        if constexpr (BP > BFULL) { if (b_last) dma16h<(SR_) * STAGE_B + BM * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, sb_, lds_wave); } \
+        lds_dma<(SR_) * STAGE_B>((VA0_), rsrcA, sa_, lds_wave);                                                   \
+        if constexpr (AP >= 2) lds_dma<(SR_) * STAGE_B + RP * 64>((VA1_), rsrcA, sa_, lds_wave);                  \
+        if constexpr (BFULL >= 1) lds_dma<(SR_) * STAGE_B + BM * 64>(voffB[0], rsrcB, sb_, lds_wave);             \
+        if constexpr (BFULL >= 2) lds_dma<(SR_) * STAGE_B + BM * 64 + RP * 64>(voffB[1], rsrcB, sb_, lds_wave);   \
+        if constexpr (BP > BFULL) { if (b_last) lds_dma<(SR_) * STAGE_B + BM * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, sb_, lds_wave); } \
     } while (0)
 
 // fragments of ring stage ST_ -> MF * NF MFMAs (weights as the A operand: D rows = channels, D columns = pixels)
@@ -85,7 +52,7 @@ constexpr int min_waves16(int nw, int frags) { return nw == 4 ? (frags <= 6 ? 4 
         __builtin_amdgcn_s_setprio(1);                                                                            \
         _Pragma("unroll") for (int f = 0; f < MF; ++f)                                                            \
             _Pragma("unroll") for (int j = 0; j < NF; ++j)                                                        \
-                acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, B_[j]), __builtin_bit_cast(h8, A_[f]), acc[f][j], 0, 0, 0); \
+                acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, B_[j]), __builtin_bit_cast(h16x8, A_[f]), acc[f][j], 0, 0, 0); \
         __builtin_amdgcn_s_setprio(0);                                                                            \
     } while (0)
 
@@ -109,20 +76,16 @@ constexpr int min_waves16(int nw, int frags) { return nw == 4 ? (frags <= 6 ? 4 
     const int wm = wave / WN, wn = wave % WN;                                                                     \
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;                                                                 \
     const int bid = blockIdx.x;                                                                                   \
-    /* XCD-aware 1-D tile map: XCD x (= bid % 8, how the hardware deals out workgroups) owns a contiguous range of  \
-       pixel tiles, and inside an XCD consecutive workgroups are the CHANNEL tiles of one pixel tile — they run    \
-       concurrently on that XCD, so the input tile is fetched from HBM once and re-read from its L2 */             \
-    const int q = nmt >> 3, r = nmt & 7, xcd = bid & 7, idx = bid >> 3;                                           \
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;                                                            \
-    if (mloc >= q + (xcd < r ? 1 : 0)) return;       /* grid is padded to 8 x max tiles per XCD */                \
-    const int mt = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + mloc;                                \
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);     /* XCD-aware 1-D tile map (conv_index.h) */                 \
+    if (xcd_slot_padding(slot)) return;               /* the grid is padded to 8 x max tiles per XCD */           \
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;                                                            \
     const int m0 = mt * BM;                                                                                       \
     const int f0 = nt * (WN * NF);                                                                                \
     const int HoWo = a.Ho * a.Wo;                                                                                 \
     const int srow = tid >> 2;                                                                                    \
     const int sc = (tid & 3) ^ ((4 - ((srow >> 2) & 3)) & 3);                                                     \
-    const int n0 = fastdiv16(m0, a.howo_magic, a.howo_shift), rem0 = m0 - n0 * HoWo;                              \
-    const int oy0 = fastdiv16(rem0, a.wo_magic, a.wo_shift), ox0 = rem0 - oy0 * a.Wo;                             \
+    const int n0 = fastdiv(m0, a.howo_magic, a.howo_shift), rem0 = m0 - n0 * HoWo;                                \
+    const int oy0 = fastdiv(rem0, a.wo_magic, a.wo_shift), ox0 = rem0 - oy0 * a.Wo;                               \
     const long long lin0 = ((long long)n0 * a.H + oy0 * a.stride) * a.W + ox0 * a.stride;                         \
     const unsigned lds_wave = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds + wave * 1024u);            \
     const int ld_off = lr * 16 + ((lq ^ ((4 - ((lr >> 2) & 3)) & 3)) << 2);                                       \
@@ -142,7 +105,7 @@ constexpr int min_waves16(int nw, int frags) { return nw == 4 ? (frags <= 6 ? 4 
         const int frag = min(f0 + (rr >> 4), a.n16 - 1);                                                          \
         voffB[p] = (unsigned)((((frag - f0) * 16 + (rr & 15)) * Ktot) * 2 + sc * 16);                             \
     }                                                                                                             \
-    const i32x4 rsrcB = make_rsrc16(w16 + (long long)f0 * 16 * Ktot);
+    const i32x4 rsrcB = make_rsrc(w16 + (long long)f0 * 16 * Ktot);
 
 #define PADEL_T16_FINISH()                                                                                        \
     const bool fast_ = m0 + BM <= a.M && (f0 + WN * NF) * 16 <= a.cout && ((a.out_choff & 3) == 0) &&             \
@@ -165,9 +128,9 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16(WM * WN, MF * NF)) c
         int m = m0 + srow + RP * p;
         const bool rv = m < a.M;
         if (!rv) m = m0;
-        const int n = fastdiv16(m, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(m, a.howo_magic, a.howo_shift);
         const int rem = m - n * HoWo;
-        const int oy = fastdiv16(rem, a.wo_magic, a.wo_shift);
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift);
         const int ox = rem - oy * a.Wo;
         const long long lin = ((long long)n * a.H + oy * a.stride) * a.W + ox * a.stride;
         const unsigned off = (unsigned)((lin - lin0) * a.in_cs * 2 + sc * 16);
@@ -178,9 +141,9 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16(WM * WN, MF * NF)) c
             vx[d] = (unsigned)(ox * a.stride - 1 + d) < (unsigned)a.W;
         }
 #pragma unroll
-        for (int t = 0; t < 9; ++t) voffA[p][t] = (vy[t / 3] && vx[t % 3]) ? off : kOutOfRange16;
+        for (int t = 0; t < 9; ++t) voffA[p][t] = (vy[t / 3] && vx[t % 3]) ? off : kOOR;
     }
-    const i32x4 rsrcA = make_rsrc16(in16 + ((lin0 - (a.W + 1)) * a.in_cs + a.in_choff));
+    const i32x4 rsrcA = make_rsrc(in16 + ((lin0 - (a.W + 1)) * a.in_cs + a.in_choff));
     unsigned tapoff[18];
 #pragma unroll
     for (int j = 0; j < 18; ++j) {
@@ -198,7 +161,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16(WM * WN, MF * NF)) c
 
 #define PADEL_T16_STEP(J)                                                                                         \
     do {                                                                                                          \
-        wait_vm16<AP + BFULL>();                                                                                  \
+        wait_vm<AP + BFULL>();                                                                                    \
         __builtin_amdgcn_s_barrier();                                                                             \
         if constexpr ((J) + 2 < 18)                                                                               \
             PADEL_T16_DMA(((J) + 2) % 3, s_chunk + tapoff[((J) + 2) % 18], s_kb + ((J) + 2) * 64u,                \
@@ -213,7 +176,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16(WM * WN, MF * NF)) c
     } while (0)
 #define PADEL_T16_TSTEP(J)                                                                                        \
     do {                                                                                                          \
-        if constexpr ((J) == 8) wait_vm16<0>(); else wait_vm16<AP + BFULL>();                                     \
+        if constexpr ((J) == 8) wait_vm<0>(); else wait_vm<AP + BFULL>();                                         \
         __builtin_amdgcn_s_barrier();                                                                             \
         if constexpr ((J) + 2 < 9)                                                                                \
             PADEL_T16_DMA(((J) + 2) % 3, s_chunk + tapoff[2 * ((J) + 2 < 9 ? (J) + 2 : 0)], s_kb + ((J) + 2) * 64u, \
@@ -240,7 +203,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16(WM * WN, MF * NF)) c
         PADEL_T16_TSTEP(0); PADEL_T16_TSTEP(1); PADEL_T16_TSTEP(2); PADEL_T16_TSTEP(3); PADEL_T16_TSTEP(4);
         PADEL_T16_TSTEP(5); PADEL_T16_TSTEP(6); PADEL_T16_TSTEP(7); PADEL_T16_TSTEP(8);
     } else {
-        wait_vm16<0>();
+        wait_vm<0>();
     }
     PADEL_T16_FINISH()
 #undef PADEL_T16_STEP
@@ -266,21 +229,21 @@ __global__ void __launch_bounds__(64 * WM * WN, tap16_1_min_waves(WM * WN, MF * 
         int m = m0 + srow + RP * p;
         const bool rv = m < a.M;
         if (!rv) m = m0;
-        const int n = fastdiv16(m, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(m, a.howo_magic, a.howo_shift);
         const int rem = m - n * HoWo;
-        const int oy = fastdiv16(rem, a.wo_magic, a.wo_shift);
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift);
         const int ox = rem - oy * a.Wo;
         const long long lin = ((long long)n * a.H + oy * a.stride) * a.W + ox * a.stride;
-        voffA[p] = rv ? (unsigned)((lin - lin0) * a.in_cs * 2 + sc * 16) : kOutOfRange16;
+        voffA[p] = rv ? (unsigned)((lin - lin0) * a.in_cs * 2 + sc * 16) : kOOR;
     }
-    const i32x4 rsrcA = make_rsrc16(in16 + (lin0 * a.in_cs + a.in_choff));
+    const i32x4 rsrcA = make_rsrc(in16 + (lin0 * a.in_cs + a.in_choff));
     PADEL_T16_WEIGHTS()
 
     unsigned s_k = 0;
     constexpr int PD = 3;                     // whole 4-stage ring in flight: the matrix pipe is no cover here
 #define PADEL_T16_1STEP(J)                                                                                        \
     if ((J) < nb) {                                                                                               \
-        wait_vm16<(PD - 1) * (AP + BFULL)>();                                                                     \
+        wait_vm<(PD - 1) * (AP + BFULL)>();                                                                       \
         __builtin_amdgcn_s_barrier();                                                                             \
         PADEL_T16_DMA(((J) + PD) % 4, s_k + ((J) + PD) * 64u, s_k + ((J) + PD) * 64u, voffA[0], voffA[AP - 1]);   \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -298,7 +261,7 @@ __global__ void __launch_bounds__(64 * WM * WN, tap16_1_min_waves(WM * WN, MF * 
         PADEL_T16_1STEP(12) PADEL_T16_1STEP(13) PADEL_T16_1STEP(14) PADEL_T16_1STEP(15)
         s_k += 16u * 64u;
     }
-    wait_vm16<0>();
+    wait_vm<0>();
     PADEL_T16_FINISH()
 #undef PADEL_T16_1STEP
 }
@@ -314,16 +277,16 @@ __global__ void __launch_bounds__(64 * WM * WN, tap16_1_min_waves(WM * WN, MF * 
 #define PADEL_T16D_DMA(SR_, SA0_, SA1_, SB0_, SB1_, VA00_, VA01_, VA10_, VA11_, VBX_)                             \
     do {                                                                                                          \
         const unsigned sa0_ = (SA0_), sa1_ = (SA1_), sb0_ = (SB0_), sb1_ = (SB1_);                                \
-        dma16h<(SR_) * STAGE_B>((VA00_), rsrcA, sa0_, lds_wave);                                                  \
-        if constexpr (AP >= 2) dma16h<(SR_) * STAGE_B + RP * 64>((VA01_), rsrcA, sa0_, lds_wave);                 \
-        dma16h<(SR_) * STAGE_B + BM * 64>((VA10_), rsrcA, sa1_, lds_wave);                                        \
-        if constexpr (AP >= 2) dma16h<(SR_) * STAGE_B + BM * 64 + RP * 64>((VA11_), rsrcA, sa1_, lds_wave);       \
-        if constexpr (BFULL >= 1) dma16h<(SR_) * STAGE_B + 2 * BM * 64>(voffB[0], rsrcB, sb0_, lds_wave);         \
-        if constexpr (BFULL >= 2) dma16h<(SR_) * STAGE_B + 2 * BM * 64 + RP * 64>(voffB[1], rsrcB, sb0_, lds_wave); \
-        if constexpr (BP > BFULL) { if (b_last) dma16h<(SR_) * STAGE_B + 2 * BM * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, sb0_, lds_wave); } \
-        if constexpr (BFULL >= 1) dma16h<(SR_) * STAGE_B + (2 * BM + BN) * 64>((VBX_) ? kOutOfRange16 : voffB[0], rsrcB, sb1_, lds_wave); \
-        if constexpr (BFULL >= 2) dma16h<(SR_) * STAGE_B + (2 * BM + BN) * 64 + RP * 64>((VBX_) ? kOutOfRange16 : voffB[1], rsrcB, sb1_, lds_wave); \
-        if constexpr (BP > BFULL) { if (b_last) dma16h<(SR_) * STAGE_B + (2 * BM + BN) * 64 + BFULL * RP * 64>((VBX_) ? kOutOfRange16 : voffB[BP - 1], rsrcB, sb1_, lds_wave); } \
+        lds_dma<(SR_) * STAGE_B>((VA00_), rsrcA, sa0_, lds_wave);                                                 \
+        if constexpr (AP >= 2) lds_dma<(SR_) * STAGE_B + RP * 64>((VA01_), rsrcA, sa0_, lds_wave);                \
+        lds_dma<(SR_) * STAGE_B + BM * 64>((VA10_), rsrcA, sa1_, lds_wave);                                       \
+        if constexpr (AP >= 2) lds_dma<(SR_) * STAGE_B + BM * 64 + RP * 64>((VA11_), rsrcA, sa1_, lds_wave);      \
+        if constexpr (BFULL >= 1) lds_dma<(SR_) * STAGE_B + 2 * BM * 64>(voffB[0], rsrcB, sb0_, lds_wave);        \
+        if constexpr (BFULL >= 2) lds_dma<(SR_) * STAGE_B + 2 * BM * 64 + RP * 64>(voffB[1], rsrcB, sb0_, lds_wave); \
+        if constexpr (BP > BFULL) { if (b_last) lds_dma<(SR_) * STAGE_B + 2 * BM * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, sb0_, lds_wave); } \
+        if constexpr (BFULL >= 1) lds_dma<(SR_) * STAGE_B + (2 * BM + BN) * 64>((VBX_) ? kOOR : voffB[0], rsrcB, sb1_, lds_wave); \
+        if constexpr (BFULL >= 2) lds_dma<(SR_) * STAGE_B + (2 * BM + BN) * 64 + RP * 64>((VBX_) ? kOOR : voffB[1], rsrcB, sb1_, lds_wave); \
+        if constexpr (BP > BFULL) { if (b_last) lds_dma<(SR_) * STAGE_B + (2 * BM + BN) * 64 + BFULL * RP * 64>((VBX_) ? kOOR : voffB[BP - 1], rsrcB, sb1_, lds_wave); } \
     } while (0)
 
 #define PADEL_T16D_COMPUTE(ST_)                                                                                   \
@@ -335,7 +298,7 @@ __global__ void __launch_bounds__(64 * WM * WN, tap16_1_min_waves(WM * WN, MF * 
             _Pragma("unroll") for (int j = 0; j < NF; ++j) B_[j] = *reinterpret_cast<const f32x4*>(b_rd + (ST_) * STAGE + sub * BN * 16 + j * 256); \
             _Pragma("unroll") for (int f = 0; f < MF; ++f)                                                        \
                 _Pragma("unroll") for (int j = 0; j < NF; ++j)                                                    \
-                    acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, B_[j]), __builtin_bit_cast(h8, A_[f]), acc[f][j], 0, 0, 0); \
+                    acc[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, B_[j]), __builtin_bit_cast(h16x8, A_[f]), acc[f][j], 0, 0, 0); \
         }                                                                                                         \
         __builtin_amdgcn_s_setprio(0);                                                                            \
     } while (0)
@@ -359,20 +322,16 @@ __global__ void __launch_bounds__(64 * WM * WN, tap16_1_min_waves(WM * WN, MF * 
     const int wm = wave / WN, wn = wave % WN;                                                                     \
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;                                                                 \
     const int bid = blockIdx.x;                                                                                   \
-    /* XCD-aware 1-D tile map: XCD x (= bid % 8, how the hardware deals out workgroups) owns a contiguous range of  \
-       pixel tiles, and inside an XCD consecutive workgroups are the CHANNEL tiles of one pixel tile — they run    \
-       concurrently on that XCD, so the input tile is fetched from HBM once and re-read from its L2 */             \
-    const int q = nmt >> 3, r = nmt & 7, xcd = bid & 7, idx = bid >> 3;                                           \
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;                                                            \
-    if (mloc >= q + (xcd < r ? 1 : 0)) return;       /* grid is padded to 8 x max tiles per XCD */                \
-    const int mt = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + mloc;                                \
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);     /* XCD-aware 1-D tile map (conv_index.h) */                 \
+    if (xcd_slot_padding(slot)) return;               /* the grid is padded to 8 x max tiles per XCD */           \
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;                                                            \
     const int m0 = mt * BM;                                                                                       \
     const int f0 = nt * (WN * NF);                                                                                \
     const int HoWo = a.Ho * a.Wo;                                                                                 \
     const int srow = tid >> 2;                                                                                    \
     const int sc = (tid & 3) ^ ((4 - ((srow >> 2) & 3)) & 3);                                                     \
-    const int n0 = fastdiv16(m0, a.howo_magic, a.howo_shift), rem0 = m0 - n0 * HoWo;                              \
-    const int oy0 = fastdiv16(rem0, a.wo_magic, a.wo_shift), ox0 = rem0 - oy0 * a.Wo;                             \
+    const int n0 = fastdiv(m0, a.howo_magic, a.howo_shift), rem0 = m0 - n0 * HoWo;                                \
+    const int oy0 = fastdiv(rem0, a.wo_magic, a.wo_shift), ox0 = rem0 - oy0 * a.Wo;                               \
     const long long lin0 = ((long long)n0 * a.H + oy0 * a.stride) * a.W + ox0 * a.stride;                         \
     const unsigned lds_wave = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds + wave * 1024u);            \
     const int ld_off = lr * 16 + ((lq ^ ((4 - ((lr >> 2) & 3)) & 3)) << 2);                                       \
@@ -400,9 +359,9 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16d(WM * WN, MF * NF)) 
         int m = m0 + srow + RP * p;
         const bool rv = m < a.M;
         if (!rv) m = m0;
-        const int n = fastdiv16(m, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(m, a.howo_magic, a.howo_shift);
         const int rem = m - n * HoWo;
-        const int oy = fastdiv16(rem, a.wo_magic, a.wo_shift);
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift);
         const int ox = rem - oy * a.Wo;
         const long long lin = ((long long)n * a.H + oy * a.stride) * a.W + ox * a.stride;
         const unsigned off = (unsigned)((lin - lin0) * a.in_cs * 2 + sc * 16);
@@ -413,9 +372,9 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16d(WM * WN, MF * NF)) 
             vx[d] = (unsigned)(ox * a.stride - 1 + d) < (unsigned)a.W;
         }
 #pragma unroll
-        for (int t = 0; t < 9; ++t) voffA[p][t] = (vy[t / 3] && vx[t % 3]) ? off : kOutOfRange16;
+        for (int t = 0; t < 9; ++t) voffA[p][t] = (vy[t / 3] && vx[t % 3]) ? off : kOOR;
     }
-    const i32x4 rsrcA = make_rsrc16(in16 + ((lin0 - (a.W + 1)) * a.in_cs + a.in_choff));
+    const i32x4 rsrcA = make_rsrc(in16 + ((lin0 - (a.W + 1)) * a.in_cs + a.in_choff));
     unsigned tapoff[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) tapoff[t] = __builtin_amdgcn_readfirstlane((unsigned)(((t / 3) * a.W + (t % 3)) * a.in_cs * 2));
@@ -428,13 +387,13 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16d(WM * WN, MF * NF)) 
 #define PADEL_T16D_REQ_TAIL(SR_, CH_, KB_, JT_)                                                                   \
     PADEL_T16D_DMA(SR_, (CH_) + tapoff[2 * (JT_)], (CH_) + tapoff[2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8], KB_, (KB_) + 64u, \
                    voffA[0][2 * (JT_)], voffA[AP - 1][2 * (JT_)],                                                 \
-                   2 * (JT_) + 1 < 9 ? voffA[0][2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8] : kOutOfRange16,           \
-                   2 * (JT_) + 1 < 9 ? voffA[AP - 1][2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8] : kOutOfRange16,      \
+                   2 * (JT_) + 1 < 9 ? voffA[0][2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8] : kOOR,                    \
+                   2 * (JT_) + 1 < 9 ? voffA[AP - 1][2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8] : kOOR,               \
                    2 * (JT_) + 1 >= 9)
     bool nxt_tail = false;
 #define PADEL_T16D_STEP(J)                                                                                        \
     do {                                                                                                          \
-        wait_vm16<NREQ>();                                                                                        \
+        wait_vm<NREQ>();                                                                                          \
         __builtin_amdgcn_s_barrier();                                                                             \
         if constexpr ((J) + 2 < 9) {                                                                              \
             PADEL_T16D_REQ_FULL(((J) + 2) % 3, s_chunk, s_kb + ((J) + 2) * 128u, (J) + 2 < 9 ? (J) + 2 : 0);      \
@@ -448,7 +407,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16d(WM * WN, MF * NF)) 
     } while (0)
 #define PADEL_T16D_TSTEP(JT)                                                                                      \
     do {                                                                                                          \
-        if constexpr ((JT) == 4) wait_vm16<0>(); else wait_vm16<NREQ>();                                          \
+        if constexpr ((JT) == 4) wait_vm<0>(); else wait_vm<NREQ>();                                              \
         __builtin_amdgcn_s_barrier();                                                                             \
         if constexpr ((JT) + 2 < 5) { PADEL_T16D_REQ_TAIL(((JT) + 2) % 3, s_chunk, s_kb + ((JT) + 2) * 128u, (JT) + 2 < 5 ? (JT) + 2 : 0); } \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -473,7 +432,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16d(WM * WN, MF * NF)) 
     if (has_tail) {
         PADEL_T16D_TSTEP(0); PADEL_T16D_TSTEP(1); PADEL_T16D_TSTEP(2); PADEL_T16D_TSTEP(3); PADEL_T16D_TSTEP(4);
     } else {
-        wait_vm16<0>();
+        wait_vm<0>();
     }
     PADEL_T16_FINISH()
 #undef PADEL_T16D_STEP
@@ -495,24 +454,24 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16d(WM * WN, MF * NF)) 
         int m = m0 + srow + RP * p;
         const bool rv = m < a.M;
         if (!rv) m = m0;
-        const int n = fastdiv16(m, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(m, a.howo_magic, a.howo_shift);
         const int rem = m - n * HoWo;
-        const int oy = fastdiv16(rem, a.wo_magic, a.wo_shift);
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift);
         const int ox = rem - oy * a.Wo;
         const long long lin = ((long long)n * a.H + oy * a.stride) * a.W + ox * a.stride;
-        voffA[p] = rv ? (unsigned)((lin - lin0) * a.in_cs * 2 + sc * 16) : kOutOfRange16;
+        voffA[p] = rv ? (unsigned)((lin - lin0) * a.in_cs * 2 + sc * 16) : kOOR;
     }
-    const i32x4 rsrcA = make_rsrc16(in16 + (lin0 * a.in_cs + a.in_choff));
+    const i32x4 rsrcA = make_rsrc(in16 + (lin0 * a.in_cs + a.in_choff));
     PADEL_T16_WEIGHTS()
 
     unsigned s_k = 0;
 #define PADEL_T16D_OFF1(K_) (half_tail && (int)(K_) >= nks - 1)
 #define PADEL_T16D_REQ1(SR_, K_)                                                                                  \
     PADEL_T16D_DMA(SR_, (K_) * 128u, (K_) * 128u + 64u, (K_) * 128u, (K_) * 128u + 64u, voffA[0], voffA[AP - 1],  \
-                   PADEL_T16D_OFF1(K_) ? kOutOfRange16 : voffA[0], PADEL_T16D_OFF1(K_) ? kOutOfRange16 : voffA[AP - 1], PADEL_T16D_OFF1(K_))
+                   PADEL_T16D_OFF1(K_) ? kOOR : voffA[0], PADEL_T16D_OFF1(K_) ? kOOR : voffA[AP - 1], PADEL_T16D_OFF1(K_))
 #define PADEL_T16D_1STEP(J)                                                                                       \
     if ((J) < nb) {                                                                                               \
-        wait_vm16<NREQ>();                                                                                        \
+        wait_vm<NREQ>();                                                                                          \
         __builtin_amdgcn_s_barrier();                                                                             \
         PADEL_T16D_REQ1(((J) + 2) % 3, s_k + (J) + 2);                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -527,7 +486,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves16d(WM * WN, MF * NF)) 
         PADEL_T16D_1STEP(5) PADEL_T16D_1STEP(6) PADEL_T16D_1STEP(7) PADEL_T16D_1STEP(8)
         s_k += 9u;
     }
-    wait_vm16<0>();
+    wait_vm<0>();
     PADEL_T16_FINISH()
 #undef PADEL_T16D_1STEP
 #undef PADEL_T16D_REQ1

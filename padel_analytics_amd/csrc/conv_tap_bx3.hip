@@ -96,10 +96,10 @@ namespace padel {
     do {                                                                                                          \
         const unsigned sa0_ = (SA0_), sa1_ = (SA1_), sb_ = (SB_);                                                 \
         if constexpr (!(DBG & 4)) {        /* probe bit 4: no activation requests */                              \
-        dma3<PADEL_BX3_IMM(SR_)>((VA0_), rsrcA, sa0_, PADEL_BX3_LW(SR_));                                                     \
-        if constexpr (AP >= 2) dma3<PADEL_BX3_IMM(SR_) + RP * 64>((VA1_), rsrcA, sa0_, PADEL_BX3_LW(SR_));                    \
-        dma3<PADEL_BX3_IMM(SR_) + BM * 64>((VB0_), rsrcA, sa1_, PADEL_BX3_LW(SR_));                                           \
-        if constexpr (AP >= 2) dma3<PADEL_BX3_IMM(SR_) + BM * 64 + RP * 64>((VB1_), rsrcA, sa1_, PADEL_BX3_LW(SR_));          \
+        lds_dma<PADEL_BX3_IMM(SR_)>((VA0_), rsrcA, sa0_, PADEL_BX3_LW(SR_));                                      \
+        if constexpr (AP >= 2) lds_dma<PADEL_BX3_IMM(SR_) + RP * 64>((VA1_), rsrcA, sa0_, PADEL_BX3_LW(SR_));     \
+        lds_dma<PADEL_BX3_IMM(SR_) + BM * 64>((VB0_), rsrcA, sa1_, PADEL_BX3_LW(SR_));                            \
+        if constexpr (AP >= 2) lds_dma<PADEL_BX3_IMM(SR_) + BM * 64 + RP * 64>((VB1_), rsrcA, sa1_, PADEL_BX3_LW(SR_)); \
         }                                                                                                         \
         if constexpr (!(DBG & 8)) {        /* probe bit 8: no weight requests */                                  \
         PADEL_BX3_DMAB(SR_, 0, sb_);                                                                              \
@@ -109,9 +109,9 @@ namespace padel {
     } while (0)
 #define PADEL_BX3_DMAB(SR_, PL_, SB_)                                                                             \
     do {                                                                                                          \
-        if constexpr (BFULL >= 1) dma3<PADEL_BX3_IMM(SR_) + 2 * BM * 64 + (PL_) * BN * 64>(voffB[0], rsrcB, (SB_), PADEL_BX3_LW(SR_)); \
-        if constexpr (BFULL >= 2) dma3<PADEL_BX3_IMM(SR_) + 2 * BM * 64 + (PL_) * BN * 64 + RP * 64>(voffB[1], rsrcB, (SB_), PADEL_BX3_LW(SR_)); \
-        if constexpr (BP > BFULL) { if (b_last) dma3<PADEL_BX3_IMM(SR_) + 2 * BM * 64 + (PL_) * BN * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, (SB_), PADEL_BX3_LW(SR_)); } \
+        if constexpr (BFULL >= 1) lds_dma<PADEL_BX3_IMM(SR_) + 2 * BM * 64 + (PL_) * BN * 64>(voffB[0], rsrcB, (SB_), PADEL_BX3_LW(SR_)); \
+        if constexpr (BFULL >= 2) lds_dma<PADEL_BX3_IMM(SR_) + 2 * BM * 64 + (PL_) * BN * 64 + RP * 64>(voffB[1], rsrcB, (SB_), PADEL_BX3_LW(SR_)); \
+        if constexpr (BP > BFULL) { if (b_last) lds_dma<PADEL_BX3_IMM(SR_) + 2 * BM * 64 + (PL_) * BN * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, (SB_), PADEL_BX3_LW(SR_)); } \
     } while (0)
 
 
@@ -134,9 +134,8 @@ namespace padel {
     const int wm = wave / WN, wn = wave % WN;                                                                     \
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;                                                                 \
     const int bid = blockIdx.x;                                                                                   \
-    /* XCD-aware 1-D tile map: XCD x (= bid % 8, how the hardware deals out workgroups) owns a contiguous range of  \
-       pixel tiles, and inside an XCD consecutive workgroups are the CHANNEL tiles of one pixel tile — they run    \
-       concurrently on that XCD, so the input tile is fetched from HBM once and re-read from its L2 */             \
+    /* XCD-aware 1-D tile map: xcd_slot / xcd_slot_padding / xcd_slot_mtile of conv_index.h, written out (through \
+       the functions one -DPADEL_BX3_PROBES instantiation allocates its scalar registers differently) */          \
     const int q = nmt >> 3, r = nmt & 7, xcd = bid & 7, idx = bid >> 3;                                           \
     const int mloc = idx / nnt, nt = idx - mloc * nnt;                                                            \
     if (mloc >= q + (xcd < r ? 1 : 0)) return;       /* grid is padded to 8 x max tiles per XCD */                \
@@ -146,8 +145,8 @@ namespace padel {
     const int HoWo = a.Ho * a.Wo;                                                                                 \
     const int srow = tid >> 2;                                                                                    \
     const int sc = (tid & 3) ^ ((4 - ((srow >> 2) & 3)) & 3);                                                     \
-    const int n0 = fastdiv3(m0, a.howo_magic, a.howo_shift), rem0 = m0 - n0 * HoWo;                               \
-    const int oy0 = fastdiv3(rem0, a.wo_magic, a.wo_shift), ox0 = rem0 - oy0 * a.Wo;                              \
+    const int n0 = fastdiv(m0, a.howo_magic, a.howo_shift), rem0 = m0 - n0 * HoWo;                                \
+    const int oy0 = fastdiv(rem0, a.wo_magic, a.wo_shift), ox0 = rem0 - oy0 * a.Wo;                               \
     const long long lin0 = ((long long)n0 * a.H + oy0 * a.stride) * a.W + ox0 * a.stride;                         \
     const unsigned lds_wave = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds + wave * 1024u);            \
     const int ld_off = lr * 16 + ((lq ^ ((4 - ((lr >> 2) & 3)) & 3)) << 2);                                       \
@@ -172,7 +171,7 @@ namespace padel {
         const int frag = min(f0 + (rr >> 4), a.n16 - 1);                                                          \
         voffB[p] = (unsigned)(((frag - f0) * 16 + (rr & 15)) * rowb + sc * 16);                                   \
     }                                                                                                             \
-    const i32x4 rsrcB = make_rsrc3(reinterpret_cast<const char*>(a.w3) + (long long)f0 * 16 * rowb);
+    const i32x4 rsrcB = make_rsrc(reinterpret_cast<const char*>(a.w3) + (long long)f0 * 16 * rowb);
 
 #define PADEL_BX3_FINISH()                                                                                        \
     const bool fast_ = m0 + BM <= a.M && (f0 + WN * NF) * 16 <= a.cout && (((a.out_choff | a.out_cs) & 3) == 0) && \
@@ -191,9 +190,9 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
         int m = m0 + srow + RP * p;
         const bool rv = m < a.M;
         if (!rv) m = m0;
-        const int n = fastdiv3(m, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(m, a.howo_magic, a.howo_shift);
         const int rem = m - n * HoWo;
-        const int oy = fastdiv3(rem, a.wo_magic, a.wo_shift);
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift);
         const int ox = rem - oy * a.Wo;
         const long long lin = ((long long)n * a.H + oy * a.stride) * a.W + ox * a.stride;
         const unsigned off = (unsigned)(((lin - lin0) * a.in_cs + sc * 4) * 4);
@@ -204,9 +203,9 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
             vx[d] = (unsigned)(ox * a.stride - 1 + d) < (unsigned)a.W;
         }
 #pragma unroll
-        for (int t = 0; t < 9; ++t) voffA[p][t] = (vy[t / 3] && vx[t % 3]) ? off : kOOR3;
+        for (int t = 0; t < 9; ++t) voffA[p][t] = (vy[t / 3] && vx[t % 3]) ? off : kOOR;
     }
-    const i32x4 rsrcA = make_rsrc3(a.in + ((lin0 - (a.W + 1)) * a.in_cs + a.in_choff));
+    const i32x4 rsrcA = make_rsrc(a.in + ((lin0 - (a.W + 1)) * a.in_cs + a.in_choff));
     unsigned tapoff[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) tapoff[t] = __builtin_amdgcn_readfirstlane((unsigned)((((t / 3) * a.W + (t % 3)) * a.in_cs) * 4));
@@ -222,13 +221,13 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
 #define PADEL_BX3_REQ_TAIL(SR_, CH_, KB_, JT_)                                                                     \
     PADEL_BX3_DMA(SR_, (CH_) + tapoff[2 * (JT_)], (CH_) + tapoff[2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8], KB_,    \
                   voffA[0][2 * (JT_)], voffA[AP - 1][2 * (JT_)],                                                  \
-                  2 * (JT_) + 1 < 9 ? voffA[0][2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8] : kOOR3,                    \
-                  2 * (JT_) + 1 < 9 ? voffA[AP - 1][2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8] : kOOR3)
+                  2 * (JT_) + 1 < 9 ? voffA[0][2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8] : kOOR,                     \
+                  2 * (JT_) + 1 < 9 ? voffA[AP - 1][2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8] : kOOR)
     bool nxt_tail = false;       // the block after the current full chunk is the tail block
 
 #define PADEL_BX3_STEP(J)                                                                                         \
     do {                                                                                                          \
-        wait_vm3<NREQ>();                                                                                         \
+        wait_vm<NREQ>();                                                                                          \
         __builtin_amdgcn_s_barrier();                                                                             \
         if constexpr ((J) + 2 < 9) {                                                                              \
             PADEL_BX3_REQ_FULL(((J) + 2) % 3, s_chunk, s_kb + ((J) + 2) * 192u, (J) + 2 < 9 ? (J) + 2 : 0);      \
@@ -243,7 +242,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
     // tail step JT (0..4): nothing is requested past step 4, so step 4 drains the queue
 #define PADEL_BX3_TSTEP(JT)                                                                                       \
     do {                                                                                                          \
-        if constexpr ((JT) == 4) wait_vm3<0>(); else wait_vm3<NREQ>();                                            \
+        if constexpr ((JT) == 4) wait_vm<0>(); else wait_vm<NREQ>();                                              \
         __builtin_amdgcn_s_barrier();                                                                             \
         if constexpr ((JT) + 2 < 5) { PADEL_BX3_REQ_TAIL(((JT) + 2) % 3, s_chunk, s_kb + ((JT) + 2) * 192u, (JT) + 2 < 5 ? (JT) + 2 : 0); } \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -271,7 +270,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
             PADEL_BX3_TSTEP(0); PADEL_BX3_TSTEP(1); PADEL_BX3_TSTEP(2); PADEL_BX3_TSTEP(3); PADEL_BX3_TSTEP(4);
             PADEL_BX3_FLUSH();
         } else {
-            wait_vm3<0>();      // the two trailing requests (past the last chunk: slack bytes) must land before LDS is released
+            wait_vm<0>();      // the two trailing requests (past the last chunk: slack bytes) must land before LDS is released
         }
     } else {
         // ---- 2-stage ring: step J waits for ITS requests (issued one step earlier), passes the barrier, requests
@@ -282,7 +281,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
              const unsigned u_ = lw0; lw0 = lw1; lw1 = u_; } while (0)
 #define PADEL_BX3_STEP2(J)                                                                                        \
         do {                                                                                                      \
-            wait_vm3<0>();                                                                                        \
+            wait_vm<0>();                                                                                         \
             __builtin_amdgcn_s_barrier();                                                                         \
             if constexpr ((J) + 1 < 9) {                                                                          \
                 PADEL_BX3_REQ_FULL((J) + 1, s_chunk, s_kb + ((J) + 1) * 192u, (J) + 1 < 9 ? (J) + 1 : 0);         \
@@ -296,7 +295,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
         } while (0)
 #define PADEL_BX3_TSTEP2(JT)                                                                                      \
         do {                                                                                                      \
-            wait_vm3<0>();                                                                                        \
+            wait_vm<0>();                                                                                         \
             __builtin_amdgcn_s_barrier();                                                                         \
             if constexpr ((JT) + 1 < 5) { PADEL_BX3_REQ_TAIL((JT) + 1, s_chunk, s_kb + ((JT) + 1) * 192u, (JT) + 1 < 5 ? (JT) + 1 : 0); } \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
@@ -317,7 +316,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
             PADEL_BX3_TSTEP2(0); PADEL_BX3_TSTEP2(1); PADEL_BX3_TSTEP2(2); PADEL_BX3_TSTEP2(3); PADEL_BX3_TSTEP2(4);
             PADEL_BX3_FLUSH();
         }
-        wait_vm3<0>();
+        wait_vm<0>();
 #undef PADEL_BX3_STEP2
 #undef PADEL_BX3_TSTEP2
 #undef PADEL_BX3_SWAP
@@ -345,20 +344,20 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
         int m = m0 + srow + RP * p;
         const bool rv = m < a.M;
         if (!rv) m = m0;
-        const int n = fastdiv3(m, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(m, a.howo_magic, a.howo_shift);
         const int rem = m - n * HoWo;
-        const int oy = fastdiv3(rem, a.wo_magic, a.wo_shift);
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift);
         const int ox = rem - oy * a.Wo;
         const long long lin = ((long long)n * a.H + oy * a.stride) * a.W + ox * a.stride;
-        voffA[p] = rv ? (unsigned)(((lin - lin0) * a.in_cs + sc * 4) * 4) : kOOR3;
+        voffA[p] = rv ? (unsigned)(((lin - lin0) * a.in_cs + sc * 4) * 4) : kOOR;
         if constexpr (UP) {
             const long long linU = ((long long)n * H2 + (oy >> 1)) * W2 + (ox >> 1);
-            voffU[p] = rv ? (unsigned)(((linU - linU0) * a.in2_cs + sc * 4) * 4) : kOOR3;
+            voffU[p] = rv ? (unsigned)(((linU - linU0) * a.in2_cs + sc * 4) * 4) : kOOR;
         }
     }
     (void)voffU; (void)linU0;
-    const i32x4 rsrcA = make_rsrc3(a.in + (lin0 * a.in_cs + a.in_choff));
-    const i32x4 rsrcU = make_rsrc3(UP ? a.in2 + (linU0 * a.in2_cs + a.in2_choff) : a.in);
+    const i32x4 rsrcA = make_rsrc(a.in + (lin0 * a.in_cs + a.in_choff));
+    const i32x4 rsrcU = make_rsrc(UP ? a.in2 + (linU0 * a.in2_cs + a.in2_choff) : a.in);
     const unsigned nup = UP ? (unsigned)(a.up_c >> 5) : 0u;
     (void)rsrcU; (void)nup;
     PADEL_BX3_WEIGHTS(nch)
@@ -375,10 +374,10 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
 
     unsigned s_k = 0;                         // index of the first k-step of the current 9-step accumulation block
     // step J of a block: chunk s_k + J; its A1 exists unless it is the half-empty last chunk
-#define PADEL_BX3_A1(K_, P_) ((half_tail && (int)(K_) >= nch - 1) ? kOOR3 : voffA[P_])
+#define PADEL_BX3_A1(K_, P_) ((half_tail && (int)(K_) >= nch - 1) ? kOOR : voffA[P_])
 #define PADEL_BX3_1STEP(J)                                                                                        \
     if ((J) < nb) {                                                                                               \
-        wait_vm3<NREQ>();                                                                                         \
+        wait_vm<NREQ>();                                                                                          \
         __builtin_amdgcn_s_barrier();                                                                             \
         PADEL_BX3_1REQ(((J) + 2) % 3, s_k + (J) + 2);                                                             \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -388,7 +387,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
     // 2-stage ring (see the 3x3 kernel): stage = parity of the step inside the 9-step block, pointers swapped per block
 #define PADEL_BX3_1STEP2(J)                                                                                       \
     if ((J) < nb) {                                                                                               \
-        wait_vm3<0>();                                                                                            \
+        wait_vm<0>();                                                                                             \
         __builtin_amdgcn_s_barrier();                                                                             \
         PADEL_BX3_1REQ((J) + 1, s_k + (J) + 1);                                                                   \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -416,7 +415,7 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
             s_k += 9u;
         }
     }
-    wait_vm3<0>();
+    wait_vm<0>();
     PADEL_BX3_FINISH()
 #undef PADEL_BX3_1STEP
 #undef PADEL_BX3_1STEP2

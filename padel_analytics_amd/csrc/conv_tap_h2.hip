@@ -26,9 +26,9 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_ke
         int m = m0 + srow + RP * p;
         const bool rv = m < a.M;
         if (!rv) m = m0;
-        const int n = fastdiv3(m, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(m, a.howo_magic, a.howo_shift);
         const int rem = m - n * HoWo;
-        const int oy = fastdiv3(rem, a.wo_magic, a.wo_shift);
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift);
         const int ox = rem - oy * a.Wo;
         const long long lin = ((long long)n * a.H + oy * a.stride) * a.W + ox * a.stride;
         const unsigned off = (unsigned)((lin - lin0) * a.in_cs * 4) + slot_b;
@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_ke
 #pragma unroll
         for (int t = 0; t < 9; ++t) voffA[p][t] = (vy[h2_tap_ky(t)] && vx[h2_tap_kx(t)]) ? off : kOORh;
     }
-    const i32x4 rsrcA = make_rsrc3(a.in + ((lin0 - (a.W + 1)) * a.in_cs + a.in_choff));
+    const i32x4 rsrcA = make_rsrc(a.in + ((lin0 - (a.W + 1)) * a.in_cs + a.in_choff));
     unsigned tapoff[9];
 #pragma unroll
     for (int t = 0; t < 9; ++t) tapoff[t] = __builtin_amdgcn_readfirstlane((unsigned)(((h2_tap_ky(t) * a.W + h2_tap_kx(t)) * a.in_cs) * 4));
@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_ke
     // (9 / 5), so the two stages swap roles after every block.
 #define PADEL_H2T_STEP2(J)                                                                                        \
     do {                                                                                                          \
-        wait_vm3<0>();                                                                                            \
+        wait_vm<0>();                                                                                             \
         __builtin_amdgcn_s_barrier();                                                                             \
         if constexpr ((J) + 1 < 9) {                                                                              \
             PADEL_H2T_REQ_FULL((J) + 1, s_chunk, s_kb + ((J) + 1) * 128u, (J) + 1 < 9 ? (J) + 1 : 0);             \
@@ -87,7 +87,7 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_ke
     } while (0)
 #define PADEL_H2T_TSTEP2(JT)                                                                                      \
     do {                                                                                                          \
-        wait_vm3<0>();                                                                                            \
+        wait_vm<0>();                                                                                             \
         __builtin_amdgcn_s_barrier();                                                                             \
         if constexpr ((JT) + 1 < 5) { PADEL_H2T_REQ_TAIL((JT) + 1, s_chunk, s_kb + ((JT) + 1) * 128u, (JT) + 1 < 5 ? (JT) + 1 : 0); } \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -108,7 +108,7 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_ke
         PADEL_H2T_TSTEP2(0); PADEL_H2T_TSTEP2(1); PADEL_H2T_TSTEP2(2); PADEL_H2T_TSTEP2(3); PADEL_H2T_TSTEP2(4);
         PADEL_H2T_FLUSH();
     }
-    wait_vm3<0>();
+    wait_vm<0>();
     PADEL_H2T_FINISH()
 #undef PADEL_H2T_STEP2
 #undef PADEL_H2T_TSTEP2
@@ -133,9 +133,9 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_1_
         int m = m0 + srow + RP * p;
         const bool rv = m < a.M;
         if (!rv) m = m0;
-        const int n = fastdiv3(m, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(m, a.howo_magic, a.howo_shift);
         const int rem = m - n * HoWo;
-        const int oy = fastdiv3(rem, a.wo_magic, a.wo_shift);
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift);
         const int ox = rem - oy * a.Wo;
         const long long lin = ((long long)n * a.H + oy * a.stride) * a.W + ox * a.stride;
         voffA[p] = rv ? (unsigned)((lin - lin0) * a.in_cs * 4) + slot_b : kOORh;
@@ -146,8 +146,8 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_1_
         }
     }
     (void)voffU; (void)linU0;
-    const i32x4 rsrcA = make_rsrc3(a.in + (lin0 * a.in_cs + a.in_choff));
-    const i32x4 rsrcU = make_rsrc3(UP ? a.in2 + (linU0 * a.in2_cs + a.in2_choff) : a.in);
+    const i32x4 rsrcA = make_rsrc(a.in + (lin0 * a.in_cs + a.in_choff));
+    const i32x4 rsrcU = make_rsrc(UP ? a.in2 + (linU0 * a.in2_cs + a.in2_choff) : a.in);
     const unsigned nup = UP ? (unsigned)(a.up_c >> 5) : 0u;
     (void)rsrcU; (void)nup;
     PADEL_H2T_WEIGHTS(nch)
@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_1_
     unsigned s_k = 0;                         // index of the first k-step of the current 9-step accumulation block
 #define PADEL_H2T_1STEP2(J)                                                                                       \
     if ((J) < nb) {                                                                                               \
-        wait_vm3<0>();                                                                                            \
+        wait_vm<0>();                                                                                             \
         __builtin_amdgcn_s_barrier();                                                                             \
         if ((int)(s_k + (J) + 1) < nch) PADEL_H2T_1REQ((J) + 1, s_k + (J) + 1);                                   \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -183,7 +183,7 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_1_
         PADEL_H2T_SWAP();
         s_k += 9u;
     }
-    wait_vm3<0>();
+    wait_vm<0>();
     PADEL_H2T_FINISH()
 #undef PADEL_H2T_1STEP2
 #undef PADEL_H2T_1REQ

@@ -8,16 +8,16 @@ namespace padel {
 #define PADEL_H2P_A(rsrc_, AS_, SA_, V0_, V1_)                                                                    \
     do {                                                                                                          \
         const unsigned sa_ = (SA_);                                                                               \
-        dma3<(AS_) * ASTG_B>((V0_), rsrc_, sa_, lds_wave);                                                        \
-        if constexpr (AP >= 2) dma3<(AS_) * ASTG_B + RP * 64>((V1_), rsrc_, sa_, lds_wave);                       \
-        dma3<(AS_) * ASTG_B + BM * 64>((V0_), rsrc_, sa_ + 32u, lds_wave);                                        \
-        if constexpr (AP >= 2) dma3<(AS_) * ASTG_B + BM * 64 + RP * 64>((V1_), rsrc_, sa_ + 32u, lds_wave);       \
+        lds_dma<(AS_) * ASTG_B>((V0_), rsrc_, sa_, lds_wave);                                                     \
+        if constexpr (AP >= 2) lds_dma<(AS_) * ASTG_B + RP * 64>((V1_), rsrc_, sa_, lds_wave);                    \
+        lds_dma<(AS_) * ASTG_B + BM * 64>((V0_), rsrc_, sa_ + 32u, lds_wave);                                     \
+        if constexpr (AP >= 2) lds_dma<(AS_) * ASTG_B + BM * 64 + RP * 64>((V1_), rsrc_, sa_ + 32u, lds_wave);    \
     } while (0)
 #define PADEL_H2P_WPL(LW_, PL_, SB_)                                                                              \
     do {                                                                                                          \
-        if constexpr (BFULL >= 1) dma3<(PL_) * BN * 64>(voffB[0], rsrcB, (SB_), LW_);                             \
-        if constexpr (BFULL >= 2) dma3<(PL_) * BN * 64 + RP * 64>(voffB[1], rsrcB, (SB_), LW_);                   \
-        if constexpr (BP > BFULL) { if (b_last) dma3<(PL_) * BN * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, (SB_), LW_); } \
+        if constexpr (BFULL >= 1) lds_dma<(PL_) * BN * 64>(voffB[0], rsrcB, (SB_), LW_);                          \
+        if constexpr (BFULL >= 2) lds_dma<(PL_) * BN * 64 + RP * 64>(voffB[1], rsrcB, (SB_), LW_);                \
+        if constexpr (BP > BFULL) { if (b_last) lds_dma<(PL_) * BN * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, (SB_), LW_); } \
     } while (0)
 // the two weight planes of the k-step at byte offset KB_ of a weight row into the weight stage of parity WS_
 #define PADEL_H2P_W(WS_, KB_)                                                                                     \
@@ -52,9 +52,9 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_1p
         int m = m0 + srow + RP * p;
         const bool rv = m < a.M;
         if (!rv) m = m0;
-        const int n = fastdiv3(m, a.howo_magic, a.howo_shift);
+        const int n = fastdiv(m, a.howo_magic, a.howo_shift);
         const int rem = m - n * HoWo;
-        const int oy = fastdiv3(rem, a.wo_magic, a.wo_shift);
+        const int oy = fastdiv(rem, a.wo_magic, a.wo_shift);
         const int ox = rem - oy * a.Wo;
         const long long lin = ((long long)n * a.H + oy * a.stride) * a.W + ox * a.stride;
         voffA[p] = rv ? (unsigned)((lin - lin0) * a.in_cs * 4) + slot_b : kOORh;
@@ -65,8 +65,8 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_1p
         }
     }
     (void)voffU; (void)linU0;
-    const i32x4 rsrcA = make_rsrc3(a.in + (lin0 * a.in_cs + a.in_choff));
-    const i32x4 rsrcU = make_rsrc3(UP ? a.in2 + (linU0 * a.in2_cs + a.in2_choff) : a.in);
+    const i32x4 rsrcA = make_rsrc(a.in + (lin0 * a.in_cs + a.in_choff));
+    const i32x4 rsrcU = make_rsrc(UP ? a.in2 + (linU0 * a.in2_cs + a.in2_choff) : a.in);
     const unsigned nup = UP ? (unsigned)(a.up_c >> 5) : 0u;
     (void)rsrcU; (void)nup;
     PADEL_H2T_WEIGHTS(nch)
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_1p
     // step J of a block (activation stage J % 3: blocks are 9 steps long; weight stage parity J & 1, swapped per block)
 #define PADEL_H2P_STEP(J)                                                                                         \
     if ((J) < nb) {                                                                                               \
-        if ((int)(s_k + (J) + 1) < nch) wait_vm3<2 * AP>(); else wait_vm3<0>();                                   \
+        if ((int)(s_k + (J) + 1) < nch) wait_vm<2 * AP>(); else wait_vm<0>();                                     \
         __builtin_amdgcn_s_barrier();                                                                             \
         if ((int)(s_k + (J) + 1) < nch) PADEL_H2P_REQW((J) + 1, s_k + (J) + 1);                                   \
         if ((int)(s_k + (J) + 2) < nch) PADEL_H2P_REQA(((J) + 2) % 3, s_k + (J) + 2);                             \
@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(64 * WM * WN, MF * NF <= 6 ? 3 : 2) conv_h2_1p
         { const float* t_ = b_rs0; b_rs0 = b_rs1; b_rs1 = t_; const unsigned u_ = lwb0; lwb0 = lwb1; lwb1 = u_; }
         s_k += 9u;
     }
-    wait_vm3<0>();
+    wait_vm<0>();
     PADEL_H2T_FINISH()
 #undef PADEL_H2P_STEP
 #undef PADEL_H2P_REQW

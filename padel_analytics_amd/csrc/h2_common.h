@@ -23,13 +23,12 @@
 // m of channels 0..15].  The PRODUCER encodes once in its epilogue; consumers fetch ready-made MFMA operands
 // (LDS-DMA straight into the operand planes, no VALU in the K loop).
 #pragma once
-#include "bx3_common.h"
+#include "kernels.h"
+#include "conv_prims.h"
+#include <cmath>
 #include "act_fast.h"
 
 namespace padel {
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -37,17 +36,9 @@ constexpr float kH2Max = 65504.0f;
 constexpr float kH2Scale = 2048.0f, kH2InvScale = 1.0f / 2048.0f;
 constexpr unsigned kOORh = 0x80000000u;      // out-of-range lane offset that stays out of range under small positive additions
 
-// 3x3 taps are walked COLUMN-major by every h2 kernel and in the packed weights (graph.py:pack_conv_weight_h2): k-step t
-// of a channel chunk is tap (ky, kx) = (t % 3, t / 3).  The quad patch kernel (conv_patch_h2q.hip) keeps the input rows of
-// one kx in registers across its three ky; one order for all kernels keeps their results bitwise identical.
-__host__ __device__ constexpr int h2_tap_ky(int t) { return t % 3; }
-__host__ __device__ constexpr int h2_tap_kx(int t) { return t / 3; }
-
+// (the column-major tap order of the h2 kernels, h2_tap_ky / h2_tap_kx: conv_index.h)
 // byte offset, inside a pixel, of the h part of channels [c, c + 4) (c % 4 == 0); the m part sits 32 bytes further
 __device__ __forceinline__ long long h2_chan_off(int c) { return (long long)(c >> 4) * 64 + (c & 15) * 2; }
-
-typedef float h2_f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h2_h16x2 __attribute__((ext_vector_type(2)));
 
 // 4 fp32 -> their h and m parts; `bad` collects "does not fit fp16" (|v| > 65504 or NaN).  Pairs go through the packed
 // round-to-nearest conversion (v_cvt_pk_f16_f32): 6 VALU per value
@@ -55,10 +46,10 @@ __device__ __forceinline__ void h2_encode4(const f32x4 v, h16x4& h, h16x4& m, bo
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         bad = bad || !(fabsf(v[2 * p]) <= kH2Max) || !(fabsf(v[2 * p + 1]) <= kH2Max);
-        const h2_f32x2 x = {__builtin_amdgcn_fmed3f(v[2 * p], -kH2Max, kH2Max), __builtin_amdgcn_fmed3f(v[2 * p + 1], -kH2Max, kH2Max)};
-        const h2_h16x2 hh = __builtin_convertvector(x, h2_h16x2);
-        const h2_f32x2 rr = {(x[0] - (float)hh[0]) * kH2Scale, (x[1] - (float)hh[1]) * kH2Scale};
-        const h2_h16x2 mm = __builtin_convertvector(rr, h2_h16x2);
+        const f32x2 x = {__builtin_amdgcn_fmed3f(v[2 * p], -kH2Max, kH2Max), __builtin_amdgcn_fmed3f(v[2 * p + 1], -kH2Max, kH2Max)};
+        const h16x2 hh = __builtin_convertvector(x, h16x2);
+        const f32x2 rr = {(x[0] - (float)hh[0]) * kH2Scale, (x[1] - (float)hh[1]) * kH2Scale};
+        const h16x2 mm = __builtin_convertvector(rr, h16x2);
         h[2 * p] = hh[0]; h[2 * p + 1] = hh[1];
         m[2 * p] = mm[0]; m[2 * p + 1] = mm[1];
     }
@@ -79,8 +70,6 @@ __device__ __forceinline__ void h2_raise(unsigned* flag, bool bad) {
 
 }  // namespace
 
-typedef unsigned h2_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned h2_u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short h2_u16x2 __attribute__((ext_vector_type(2)));
 
 // The fast epilogue of every h2 kernel.  acc = main + cross / 2048 per fragment; then * 1 / row scale + bias, activation,
@@ -112,10 +101,10 @@ __device__ __forceinline__ float h2_conv_value(float cross, float mainacc, float
     return fmaf(fmaf(cross, kH2InvScale, mainacc), sc, b);
 }
 // a 16-byte residual piece as the pair path loads it -> this lane's four values (the inverse of the store's two swaps, then decode)
-__device__ __forceinline__ f32x4 h2_residual4(const h2_u32x4 rr) {
-    const h2_u32x2 s0 = __builtin_amdgcn_permlane16_swap(rr[0], rr[2], false, false);
-    const h2_u32x2 s1 = __builtin_amdgcn_permlane16_swap(rr[1], rr[3], false, false);
-    const h2_u32x2 hd = {s0[0], s1[0]}, md = {s0[1], s1[1]};
+__device__ __forceinline__ f32x4 h2_residual4(const u32x4 rr) {
+    const u32x2 s0 = __builtin_amdgcn_permlane16_swap(rr[0], rr[2], false, false);
+    const u32x2 s1 = __builtin_amdgcn_permlane16_swap(rr[1], rr[3], false, false);
+    const u32x2 hd = {s0[0], s1[0]}, md = {s0[1], s1[1]};
     return h2_decode4(__builtin_bit_cast(h16x4, hd), __builtin_bit_cast(h16x4, md));
 }
 
@@ -146,14 +135,14 @@ __device__ __forceinline__ void h2_epilogue_fast(const ConvArgs& a, const f32x4 
     } else {
         const int piece = ((lq & 1) << 5) | ((lq >> 1) << 4);
         char* op[MF];
-        h2_u32x4 rr[MF][NF];
+        u32x4 rr[MF][NF];
 #pragma unroll
         for (int f = 0; f < MF; ++f) {
             op[f] = reinterpret_cast<char*>(a.out) + (long long)mpix[f] * a.out_cs * 4 + ((((a.out_choff >> 4) + fw) << 6) + piece);
             if constexpr (RES) {
                 const char* rp = reinterpret_cast<const char*>(a.res) + (long long)mpix[f] * a.res_cs * 4 + ((((a.res_choff >> 4) + fw) << 6) + piece);
 #pragma unroll
-                for (int j = 0; j < NF; ++j) rr[f][j] = *reinterpret_cast<const h2_u32x4*>(rp + j * 64);
+                for (int j = 0; j < NF; ++j) rr[f][j] = *reinterpret_cast<const u32x4*>(rp + j * 64);
             }
         }
         h2_u16x2 top = {0, 0};
@@ -177,21 +166,21 @@ __device__ __forceinline__ void h2_epilogue_fast(const ConvArgs& a, const f32x4 
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = h2_act<ACT>(v[r]);
                 }
-                h2_u32x2 hd, md;
+                u32x2 hd, md;
 #pragma unroll
                 for (int p = 0; p < 2; ++p) {
-                    const h2_f32x2 x = {__builtin_amdgcn_fmed3f(v[2 * p], -kH2Max, kH2Max), __builtin_amdgcn_fmed3f(v[2 * p + 1], -kH2Max, kH2Max)};
-                    const h2_h16x2 hh = __builtin_convertvector(x, h2_h16x2);
-                    const h2_f32x2 res = {(x[0] - (float)hh[0]) * kH2Scale, (x[1] - (float)hh[1]) * kH2Scale};
-                    const h2_h16x2 mm = __builtin_convertvector(res, h2_h16x2);
+                    const f32x2 x = {__builtin_amdgcn_fmed3f(v[2 * p], -kH2Max, kH2Max), __builtin_amdgcn_fmed3f(v[2 * p + 1], -kH2Max, kH2Max)};
+                    const h16x2 hh = __builtin_convertvector(x, h16x2);
+                    const f32x2 res = {(x[0] - (float)hh[0]) * kH2Scale, (x[1] - (float)hh[1]) * kH2Scale};
+                    const h16x2 mm = __builtin_convertvector(res, h16x2);
                     hd[p] = __builtin_bit_cast(unsigned, hh);
                     md[p] = __builtin_bit_cast(unsigned, mm);
                     top = __builtin_elementwise_max(top, __builtin_bit_cast(h2_u16x2, hd[p] & 0x7FFF7FFFu));
                 }
-                const h2_u32x2 s0 = __builtin_amdgcn_permlane16_swap(hd[0], md[0], false, false);
-                const h2_u32x2 s1 = __builtin_amdgcn_permlane16_swap(hd[1], md[1], false, false);
-                const h2_u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
-                *reinterpret_cast<h2_u32x4*>(op[f] + j * 64) = o;
+                const u32x2 s0 = __builtin_amdgcn_permlane16_swap(hd[0], md[0], false, false);
+                const u32x2 s1 = __builtin_amdgcn_permlane16_swap(hd[1], md[1], false, false);
+                const u32x4 o = {s0[0], s1[0], s0[1], s1[1]};
+                *reinterpret_cast<u32x4*>(op[f] + j * 64) = o;
             }
         bad = bad || top[0] >= 0x7BFFu || top[1] >= 0x7BFFu;
     }

@@ -51,18 +51,18 @@
 #define PADEL_H2T_DMA_R(rsrcA, SR_, SA_, SB_, V0_, V1_)                                                           \
     do {                                                                                                          \
         const unsigned sa_ = (SA_), sb_ = (SB_);                                                                  \
-        dma3<0>((V0_), rsrcA, sa_, PADEL_H2T_LW(SR_));                                                            \
-        if constexpr (AP >= 2) dma3<RP * 64>((V1_), rsrcA, sa_, PADEL_H2T_LW(SR_));                               \
-        dma3<BM * 64>((V0_), rsrcA, sa_ + 32u, PADEL_H2T_LW(SR_));                                                \
-        if constexpr (AP >= 2) dma3<BM * 64 + RP * 64>((V1_), rsrcA, sa_ + 32u, PADEL_H2T_LW(SR_));               \
+        lds_dma<0>((V0_), rsrcA, sa_, PADEL_H2T_LW(SR_));                                                         \
+        if constexpr (AP >= 2) lds_dma<RP * 64>((V1_), rsrcA, sa_, PADEL_H2T_LW(SR_));                            \
+        lds_dma<BM * 64>((V0_), rsrcA, sa_ + 32u, PADEL_H2T_LW(SR_));                                             \
+        if constexpr (AP >= 2) lds_dma<BM * 64 + RP * 64>((V1_), rsrcA, sa_ + 32u, PADEL_H2T_LW(SR_));            \
         PADEL_H2T_DMAB(SR_, 0, sb_);                                                                              \
         if constexpr (!WS) PADEL_H2T_DMAB(SR_, 1, sb_ + 64u);                                                     \
     } while (0)
 #define PADEL_H2T_DMAB(SR_, PL_, SB_)                                                                             \
     do {                                                                                                          \
-        if constexpr (BFULL >= 1) dma3<2 * BM * 64 + (PL_) * BN * 64>(voffB[0], rsrcB, (SB_), PADEL_H2T_LW(SR_)); \
-        if constexpr (BFULL >= 2) dma3<2 * BM * 64 + (PL_) * BN * 64 + RP * 64>(voffB[1], rsrcB, (SB_), PADEL_H2T_LW(SR_)); \
-        if constexpr (BP > BFULL) { if (b_last) dma3<2 * BM * 64 + (PL_) * BN * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, (SB_), PADEL_H2T_LW(SR_)); } \
+        if constexpr (BFULL >= 1) lds_dma<2 * BM * 64 + (PL_) * BN * 64>(voffB[0], rsrcB, (SB_), PADEL_H2T_LW(SR_)); \
+        if constexpr (BFULL >= 2) lds_dma<2 * BM * 64 + (PL_) * BN * 64 + RP * 64>(voffB[1], rsrcB, (SB_), PADEL_H2T_LW(SR_)); \
+        if constexpr (BP > BFULL) { if (b_last) lds_dma<2 * BM * 64 + (PL_) * BN * 64 + BFULL * RP * 64>(voffB[BP - 1], rsrcB, (SB_), PADEL_H2T_LW(SR_)); } \
     } while (0)
 
 #define PADEL_H2T_GEOMETRY() PADEL_H2T_GEOMETRY_(2 * STAGE)
@@ -84,11 +84,9 @@
     const int wm_ = wave / WN, wn_ = wave % WN;                                                                   \
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;                                                                 \
     const int bid = blockIdx.x;                                                                                   \
-    /* XCD-aware 1-D tile map (conv_tap_bx3.hip): the channel tiles of one pixel tile are neighbours on one XCD */ \
-    const int q = nmt >> 3, r = nmt & 7, xcd = bid & 7, idx = bid >> 3;                                           \
-    const int mloc = idx / nnt, nt = idx - mloc * nnt;                                                            \
-    if (mloc >= q + (xcd < r ? 1 : 0)) return;                                                                    \
-    const int mt = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + mloc;                                \
+    const XcdSlot slot = xcd_slot(nmt, nnt, bid);     /* XCD-aware 1-D tile map (conv_index.h) */                 \
+    if (xcd_slot_padding(slot)) return;               /* the grid is padded to 8 x max tiles per XCD */           \
+    const int mt = xcd_slot_mtile(slot), nt = slot.nt;                                                            \
     const int m0 = mt * BM;                                                                                       \
     const int f0 = nt * (WN * NF);                                                                                \
     const int HoWo = a.Ho * a.Wo;                                                                                 \
@@ -96,8 +94,8 @@
     const int sc = (tid & 3) ^ ((4 - ((srow >> 2) & 3)) & 3);      /* logical 16-byte slot this lane fetches */      \
     const bool sc_hi = (sc >> 1) != 0;                                                                            \
     const unsigned slot_b = (unsigned)((sc >> 1) * 64 + (sc & 1) * 16);   /* its place in a 128-byte h2 chunk (h plane) */ \
-    const int n0 = fastdiv3(m0, a.howo_magic, a.howo_shift), rem0 = m0 - n0 * HoWo;                               \
-    const int oy0 = fastdiv3(rem0, a.wo_magic, a.wo_shift), ox0 = rem0 - oy0 * a.Wo;                              \
+    const int n0 = fastdiv(m0, a.howo_magic, a.howo_shift), rem0 = m0 - n0 * HoWo;                                \
+    const int oy0 = fastdiv(rem0, a.wo_magic, a.wo_shift), ox0 = rem0 - oy0 * a.Wo;                               \
     const long long lin0 = ((long long)n0 * a.H + oy0 * a.stride) * a.W + ox0 * a.stride;                         \
     const unsigned lds_wave = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds + wave * 1024u);            \
     const int ld_off = lr * 16 + ((lq ^ ((4 - ((lr >> 2) & 3)) & 3)) << 2);                                       \
@@ -121,7 +119,7 @@
         const int frag = min(f0 + (rr >> 4), a.n16 - 1);                                                          \
         voffB[p] = (unsigned)(((frag - f0) * 16 + (rr & 15)) * rowb + sc * 16);                                   \
     }                                                                                                             \
-    const i32x4 rsrcB = make_rsrc3(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
+    const i32x4 rsrcB = make_rsrc(reinterpret_cast<const char*>(a.w) + (long long)f0 * 16 * rowb);
 
 #define PADEL_H2T_FINISH()                                                                                        \
     const bool fast_ = m0 + BM <= a.M && (f0 + WN * NF) * 16 <= a.cout && (((a.out_choff | a.out_cs) & 3) == 0) && \

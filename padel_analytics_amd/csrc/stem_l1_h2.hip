@@ -31,8 +31,6 @@ constexpr int kFPerWave = (kFFrags + 3) / 4;                        // 5
 constexpr int kFEntries = 320;                                      // 9 rows x 2 parities x 17 = 306 entries, padded
 constexpr int kFPlaneB = kFEntries * 64, kFTPlaneB = kFEntries * 32;
 
-__device__ __forceinline__ unsigned fs_off(int p, int q) { return (unsigned)(p * 64 + ((q ^ (((p >> 2) & 1) << 1)) << 4)); }
-__device__ __forceinline__ unsigned fs_tail_off(int p, int s) { return (unsigned)(p * 32 + ((s ^ ((p >> 3) & 1)) << 4)); }
 __device__ __forceinline__ int fs_entry(int srow, int scol) { return (srow * 2 + (scol & 1)) * 17 + (scol >> 1); }
 
 }  // namespace
@@ -72,14 +70,10 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
     // XCD-aware 1-D tile map (one channel tile)
     const int nmt = a.n_mtiles;
     const int bid = blockIdx.x;
-    const int q8 = nmt >> 3, r8 = nmt & 7, xcd = bid & 7, mloc = bid >> 3;
-    if (mloc >= q8 + (xcd < r8 ? 1 : 0)) return;
-    const int mt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + mloc;
-    const int txN = (a.Wo + 15) >> 4, tyN = (a.Ho + 3) >> 2;
-    const int tpi = tyN * txN;
-    const int n = mt / tpi, rt = mt - n * tpi;
-    const int ty = rt / txN, tx = rt - ty * txN;
-    const int oy0 = ty * 4, ox0 = tx * 16;
+    const XcdSlot slot = xcd_slot(nmt, 1, bid);
+    if (xcd_slot_padding(slot)) return;
+    const TileOrigin org = tile_origin<2, 4>(a.Ho, a.Wo, xcd_slot_mtile(slot));
+    const int n = org.n, oy0 = org.y0, ox0 = org.x0;
 
     // ---- layer-1 weights: rows of NSTEPS k-steps x 128 bytes (h | m).  A stage = 2 planes x 2 NF spans of 16 rows x 64 bytes;
     // wave w requests the spans w, w + 4, w + 8 (span = plane * 2 NF + row group): lane i -> row i / 4, physical slot i & 3
@@ -95,27 +89,26 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
         const int frag = min(g, a.n16 - 1);
         voffB[k] = (unsigned)((frag * 16 + b_row) * rowb + pl * 64 + b_sc * 16);
     }
-    const i32x4 rsrcB = make_rsrc3(a.w);
+    const i32x4 rsrcB = make_rsrc(a.w);
     const unsigned lw0 = __builtin_amdgcn_readfirstlane(lp0 + (unsigned)S_B + (unsigned)wave * 1024u);
     const unsigned lw1 = __builtin_amdgcn_readfirstlane(lw0 + (unsigned)BSTAGE_B);
     const unsigned lw2 = __builtin_amdgcn_readfirstlane(lw1 + (unsigned)BSTAGE_B);
 #define PADEL_FS_DMAB(ST_)                                                                                        \
     do {                                                                                                          \
         const unsigned lw_ = ((ST_) % 3) == 0 ? lw0 : ((ST_) % 3) == 1 ? lw1 : lw2;                               \
-        dma3<0>(voffB[0], rsrcB, (unsigned)(ST_) * 128u, lw_);                                                    \
-        if constexpr (NF >= 2) dma3<4096>(voffB[NF >= 2 ? 1 : 0], rsrcB, (unsigned)(ST_) * 128u, lw_);            \
-        if constexpr (NF >= 3) dma3<8192>(voffB[NF >= 3 ? 2 : 0], rsrcB, (unsigned)(ST_) * 128u, lw_);            \
+        lds_dma<0>(voffB[0], rsrcB, (unsigned)(ST_) * 128u, lw_);                                                 \
+        if constexpr (NF >= 2) lds_dma<4096>(voffB[NF >= 2 ? 1 : 0], rsrcB, (unsigned)(ST_) * 128u, lw_);         \
+        if constexpr (NF >= 3) lds_dma<8192>(voffB[NF >= 3 ? 2 : 0], rsrcB, (unsigned)(ST_) * 128u, lw_);         \
     } while (0)
     // register weights: fragment wc NF + j of layer 1 (its 2 NF fragments, NSTEPS k-steps of 2 KB each: [h | m][lane][16 B])
-    typedef int fs_i32x4 __attribute__((ext_vector_type(4)));
     const unsigned voffW = (unsigned)lane * 16u;
     i32x4 rsrcW[NF];
-    fs_i32x4 wreg[3][NF];
+    i32x4 wreg[3][NF];
     (void)voffW; (void)rsrcW; (void)wreg;
     if constexpr (WR) {
 #pragma unroll
         for (int j = 0; j < NF; ++j)
-            rsrcW[j] = make_rsrc3(reinterpret_cast<const char*>(a.wr) + (long long)(wc * NF + j) * (NSTEPS * 2048));
+            rsrcW[j] = make_rsrc(reinterpret_cast<const char*>(a.wr) + (long long)(wc * NF + j) * (NSTEPS * 2048));
     }
 #define PADEL_FS_LOADW(ST_)                                                                                       \
     do {                                                                                                          \
@@ -239,8 +232,8 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
                     h16x4 hv, mv;                                                                                 \
                     h2_encode4(v, hv, mv, bad);                                                                   \
                     char* op;                                                                                     \
-                    if (TL_) op = ldsb + fs_tail_off(s_ent[i], lq >> 1) + (lq & 1) * 8;                           \
-                    else op = ldsb + fs_off(s_ent[i], 2 * j + (lq >> 1)) + (lq & 1) * 8;                          \
+                    if (TL_) op = ldsb + swz_tail_off(s_ent[i], lq >> 1) + (lq & 1) * 8;                          \
+                    else op = ldsb + swz_off(s_ent[i], 2 * j + (lq >> 1)) + (lq & 1) * 8;                         \
                     *reinterpret_cast<h16x4*>(op) = hv;                                                           \
                     *reinterpret_cast<h16x4*>(op + ((TL_) ? kFTPlaneB : kFPlaneB)) = mv;                          \
                 }                                                                                                 \
@@ -289,7 +282,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
     // is free for the request of step ST_ + 2
 #define PADEL_FS_SYNC(ST_)                                                                                        \
     do {                                                                                                          \
-        if constexpr ((ST_) + 1 < NSTEPS) wait_vm3<NF>(); else wait_vm3<0>();                                     \
+        if constexpr ((ST_) + 1 < NSTEPS) wait_vm<NF>(); else wait_vm<0>();                                       \
         __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
         PADEL_FS_READB(ST_);                                                                                      \
@@ -300,7 +293,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
 #define PADEL_FS_READA(T_)                                                                                        \
     do {                                                                                                          \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
-            const char* p_ = ldsb + fs_off(PADEL_FS_ENT(f, T_), lq);                                              \
+            const char* p_ = ldsb + swz_off(PADEL_FS_ENT(f, T_), lq);                                             \
             ah[f] = *reinterpret_cast<const h16x8*>(p_);                                                          \
             am[f] = *reinterpret_cast<const h16x8*>(p_ + kFPlaneB);                                               \
         }                                                                                                         \
@@ -320,7 +313,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
         constexpr int ta_ = 2 * (JT_), tb_ = 2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8;                               \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
             const int ea_ = PADEL_FS_ENT(f, ta_), eb_ = PADEL_FS_ENT(f, tb_);                                     \
-            const char* p_ = ldsb + fs_tail_off((lq >> 1) ? eb_ : ea_, lq & 1);                                   \
+            const char* p_ = ldsb + swz_tail_off((lq >> 1) ? eb_ : ea_, lq & 1);                                  \
             ah[f] = *reinterpret_cast<const h16x8*>(p_);                                                          \
             am[f] = *reinterpret_cast<const h16x8*>(p_ + kFTPlaneB);                                              \
         }                                                                                                         \
@@ -343,7 +336,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
 #define PADEL_FS_READA2(SET_, T_)                                                                                 \
     do {                                                                                                          \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
-            const char* p_ = ldsb + fs_off(PADEL_FS_ENT(f, T_), lq);                                              \
+            const char* p_ = ldsb + swz_off(PADEL_FS_ENT(f, T_), lq);                                             \
             ah2[SET_][f] = *reinterpret_cast<const h16x8*>(p_);                                                   \
             am2[SET_][f] = *reinterpret_cast<const h16x8*>(p_ + kFPlaneB);                                        \
         }                                                                                                         \
@@ -353,7 +346,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
         constexpr int ta_ = 2 * (JT_), tb_ = 2 * (JT_) + 1 < 9 ? 2 * (JT_) + 1 : 8;                               \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
             const int ea_ = PADEL_FS_ENT(f, ta_), eb_ = PADEL_FS_ENT(f, tb_);                                     \
-            const char* p_ = ldsb + fs_tail_off((lq >> 1) ? eb_ : ea_, lq & 1);                                   \
+            const char* p_ = ldsb + swz_tail_off((lq >> 1) ? eb_ : ea_, lq & 1);                                  \
             ah2[SET_][f] = *reinterpret_cast<const h16x8*>(p_);                                                   \
             am2[SET_][f] = *reinterpret_cast<const h16x8*>(p_ + kFTPlaneB);                                       \
         }                                                                                                         \
@@ -380,7 +373,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
     if constexpr (WR) {
         if constexpr (CHUNK) {
             PADEL_FS_STEM(0, 2, false);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's plane writes have reached the LDS
+            lds_fence();   // this wave's plane writes have reached the LDS
             __builtin_amdgcn_s_barrier();                        // ... and every wave's: the planes are published
             asm volatile("" ::: "memory");
             PADEL_FS_READA2(0, 0);
@@ -392,12 +385,12 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
         if constexpr (TAIL) {
             constexpr int S0 = CHUNK ? 9 : 0;
             if constexpr (CHUNK) {                   // every wave is done with the chunk planes: the tail planes take their place
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                lds_fence();
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
             PADEL_FS_STEM(NCF, 1, true);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            lds_fence();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             PADEL_FS_TREADA2(S0 & 1, 0);
@@ -409,7 +402,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
     } else {
     if constexpr (CHUNK) {
         PADEL_FS_STEM(0, 2, false);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // this wave's plane writes have reached the LDS
+        lds_fence();       // this wave's plane writes have reached the LDS
         // (the barrier of step 0 publishes the planes)
         PADEL_FS_STEP(0); PADEL_FS_STEP(1); PADEL_FS_STEP(2); PADEL_FS_STEP(3); PADEL_FS_STEP(4);
         PADEL_FS_STEP(5); PADEL_FS_STEP(6); PADEL_FS_STEP(7); PADEL_FS_STEP(8);
@@ -421,13 +414,13 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
             asm volatile("" ::: "memory");
         }
         PADEL_FS_STEM(NCF, 1, true);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        lds_fence();
         constexpr int S0 = CHUNK ? 9 : 0;
         PADEL_FS_TSTEP(0, S0); PADEL_FS_TSTEP(1, S0 + 1); PADEL_FS_TSTEP(2, S0 + 2); PADEL_FS_TSTEP(3, S0 + 3); PADEL_FS_TSTEP(4, S0 + 4);
         PADEL_FS_FLUSH();
     }
     }
-    wait_vm3<0>();
+    wait_vm<0>();
 #undef PADEL_FS_STEP2
 #undef PADEL_FS_MFMA2
 #undef PADEL_FS_TREADA2
