@@ -4,7 +4,7 @@ the host op at ``players_keypoints_tracker.py:264-266`` and ``ball_tracker/itera
 
 PINNED: tests/test_preprocess_ref.py checks it bit-exactly against Pillow itself (importable here) on the
 sizes the reference uses (720x1280 -> 1280x1280, 1080x1920 -> 1280x1280, -> 512x288).  The engine's device
-kernel (csrc/kernels_misc.hip:resample_pass_kernel, tables from engine.cpp:pil_coeffs) follows the same
+kernel (csrc/kernels_misc.hip:resample_pass_kernel, tables from graph_plan.cpp:pil_coeffs) follows the same
 arithmetic and is checked against Pillow on the GPU (tests/test_gpu_preprocess.py)."""
 from __future__ import annotations
 

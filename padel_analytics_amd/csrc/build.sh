@@ -13,22 +13,25 @@ mkdir -p "$BUILD"
 pids=()
 # PADEL_ONLY="a.hip b.hip": recompile only these translation units and relink with the objects already in $BUILD (iteration)
 ALL="conv_tap.hip conv_tap16.hip conv_tap_bx3.hip conv_patch_bx3.hip conv_tap_h2.hip conv_tap_h2p.hip conv_1x1_h2s.hip conv_patch_h2.hip conv_patch_h2q.hip conv_patch_h2r.hip conv_patch_h2v.hip conv_patch_h2w.hip conv_patch16.hip kernels_misc.hip resnet_ops.hip yolo11_ops.hip stem_l1_h2.hip postproc.hip tracknet_post.hip yuv_convert.hip"
-for f in ${PADEL_ONLY:-$ALL}; do
+# the engine (host code that calls the HIP runtime), one translation unit per concern: engine_internal.h
+ENGINE="engine.cpp engine_pre.cpp engine_yolo.cpp engine_tracknet.cpp engine_resnet.cpp engine_comm.cpp"
+for f in ${PADEL_ONLY:-$ALL $ENGINE}; do
   [ -f "$f" ] || continue
-  [ "$f" = engine.cpp ] && continue
-  hipcc $FLAGS -c "$f" -o "$BUILD/${f%.hip}.o" &
+  case "$f" in
+    *.cpp) hipcc $FLAGS -x hip -c "$f" -o "$BUILD/${f%.cpp}.o" & ;;
+    *) hipcc $FLAGS -c "$f" -o "$BUILD/${f%.hip}.o" & ;;
+  esac
   pids+=($!)
 done
-if [ -z "${PADEL_ONLY:-}" ] || [[ " $PADEL_ONLY " == *" engine.cpp "* ]]; then
-hipcc $FLAGS -x hip -c engine.cpp -o "$BUILD/engine.o" &
-pids+=($!)
-fi
 # host code; -ffp-contract=off: the tracker's doubles are pinned against the Python twin (no fused multiply-adds)
 if [ -z "${PADEL_ONLY:-}" ]; then
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c bytetrack.cpp -o "$BUILD/bytetrack.o" &
 pids+=($!)
 # which kernel runs a conv (tile table, resolver, choosers): no HIP runtime call, only the types of kernels.h
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include ${PADEL_EXTRA_FLAGS:-} -c conv_select.cpp -o "$BUILD/conv_select.o" &
+pids+=($!)
+# what is decided about a graph before anything runs (refusals, upsample folds, memory plan, resize tables): no HIP runtime call either
+g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include ${PADEL_EXTRA_FLAGS:-} -c graph_plan.cpp -o "$BUILD/graph_plan.o" &
 pids+=($!)
 fi
 for p in "${pids[@]}"; do wait "$p"; done

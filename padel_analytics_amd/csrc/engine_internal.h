@@ -1,0 +1,169 @@
+// Shared by the engine's translation units (engine*.cpp); not part of the C-ABI (include/padel_hip.h).
+//   engine.cpp           engine and model lifecycle, tuning, memory and timer calls, the arena, run_ops / run_graph, profile text
+//   engine_pre.cpp       preprocessing shared by the model families: frame staging, the Pillow resample, YUV -> BGR
+//   engine_yolo.cpp      YOLO plan, prepare, enqueue, post-processing, tickets, read-backs
+//   engine_tracknet.cpp  pa_tracknet_infer and the ball session
+//   engine_resnet.cpp    the ResNet-50 court-keypoint regressor
+//   engine_comm.cpp      RCCL
+// What is decided about a graph on the host alone lives in graph_plan.cpp, which kernel runs a conv in conv_select.cpp.
+#pragma once
+#include "../../include/padel_hip.h"
+#include "graph_plan.h"
+#include "kernels.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <string>
+#include <vector>
+
+using namespace padel;
+
+// Tuning knobs: read from the environment ONCE at pa_engine_create (PADEL_CONV_IMPL=tap|bx3, PADEL_CONV_VARIANT,
+// PADEL_CONV_TUNE, PADEL_CONV_TAP_PD, PADEL_GRAPH, PADEL_ALIAS), changed afterwards only through
+// pa_engine_set_tuning — the replay loop never touches getenv.
+struct Tuning {
+    int impl = 2;        // 2 (default): bf16x3 kernels — fp32 values split exactly into 3 bf16, 6 products on the bf16
+                         // pipe, fp32 accumulate (admitted by the same parity criteria as the fp32-MFMA kernels);
+                         // 0: tap-unrolled LDS-DMA fp32-MFMA kernels, 1: LDS kernel (their bitwise cross-check)
+    int variant = -1;    // forced tile id (tests / tools), -1: per-layer heuristic
+    int tune = 1;        // bit 0: s_setprio around MFMA clusters
+    int tap_pd = 2;      // prefetch distance of the 1x1 tap kernel
+    int graph = 0;       // 1: replay the op list of a (model, batch) from a captured hipGraph
+    int timeline = 0;    // 1: 3x3 tap launches of the 64x96 tile run the s_memtime-instrumented instantiation
+    int alias = 1;       // 1: activation buffers share one arena by liveness, 0: disjoint ranges
+    int fuse_stem = 1;   // 1: h2 YOLOv8 graphs run model.0 (stem) + model.1 (3x3 stride 2) as ONE kernel (stem_l1_h2.hip; default since round 4, 0 = two kernels)
+    int w_single = 1;    // 1 (default): h2 convs whose packed weights have an all-zero m plane (PA_CONV_W_SINGLE) skip the wm x ah product;
+                         // 0 (tests): all three products everywhere — bitwise the same results
+    int fuse_sppf = 1;   // 1: h2 graphs run the three chained 5x5 max-pools of SPPF as ONE kernel (sppf_h2_kernel: keys in LDS, separable passes); 0 = three launches.  Bitwise the same maps
+    int fold_up = 1;     // 1: an nn.Upsample(2) whose only reader is a bf16x3 1x1 conv is never materialised (the conv
+                         // fetches those channels at [y >> 1][x >> 1] of the coarse map), 0: run the upsample kernel
+};
+
+struct pa_comm;
+
+struct pa_engine {
+    int dev = 0;
+    hipStream_t stream = nullptr;
+    hipStream_t copy_stream = nullptr;   // uploads that must not queue behind compute (pa_upload)
+    std::string err;
+    bool profiling = false;
+    float* zeros = nullptr;   // 256 B of zeros: source of padded conv taps
+    Tuning t;
+    int tuning_epoch = 0;     // bumped by pa_engine_set_tuning: captured graphs of an older epoch are discarded
+    std::string timeline_path;
+    pa_comm* comm = nullptr;  // RCCL communicator (pa_engine_comm_init), optional
+    uint8_t* yuv_stage = nullptr; size_t yuv_stage_cap = 0;   // pa_yuv420_to_bgr: raw YUV bytes of a host source, filled and read on `stream` only
+    int yuv_last_path = 0;    // 1 vector, 2 byte: what the last pa_yuv420_to_bgr launched (pa_yuv_last_path)
+    hipEvent_t timer_ev[2]{};  // pa_engine_timer_start / _stop, created on first use
+};
+
+extern thread_local std::string g_err;      // errors of calls that have no engine yet (pa_last_error(NULL))
+
+#define PA_FAIL(eng, ...)                                        \
+    do {                                                         \
+        char _b[512];                                            \
+        snprintf(_b, sizeof(_b), __VA_ARGS__);                   \
+        if (eng) (eng)->err = _b; else g_err = _b;               \
+        return 1;                                                \
+    } while (0)
+
+#define PA_HIP(eng, call)                                                                  \
+    do {                                                                                   \
+        hipError_t _e = (call);                                                            \
+        if (_e != hipSuccess) {                                                            \
+            (void)hipGetLastError();   /* reported here: must not surface again at the next launch's hipGetLastError() */ \
+            PA_FAIL(eng, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
+        }                                                                                  \
+    } while (0)
+
+struct ProfRec { int kind; int ksize; double flops; hipEvent_t e0, e1; float ms; int M, cout, cin, stride, mf, nf, res; int tile; const char* family; };      // tile, family: what the conv dispatcher launched (ConvLaunched; -1 / "" for other ops)
+enum { PROF_PRE = 100, PROF_DECODE = 101, PROF_NMS = 102 };      // `kind` of the profile rows that are not ops of the graph
+
+// The two-pass Pillow resample of u8 HWC frames (sh x sw x 3 -> dh x dw): its tables on the device and the temporary between
+// the passes (engine_pre.cpp).  No table for an axis that already has the target size, d_tmp only when both axes change.
+struct ResamplePlan {
+    int sh = 0, sw = 0, dh = 0, dw = 0;
+    int32_t *d_hb = nullptr, *d_hk = nullptr, *d_vb = nullptr, *d_vk = nullptr;
+    int hks = 0, vks = 0;
+    uint8_t* d_tmp = nullptr;
+};
+
+struct pa_model {
+    pa_engine* e = nullptr;
+    pa_model_desc d{};
+    std::vector<pa_buf_desc> bufs;
+    std::vector<pa_op_desc> ops;
+    std::vector<int> fold_src;             // conv op i -> index of the upsample op it can absorb (-1: none), find_upsample_folds
+    std::vector<int> fold_dst;             // upsample op j -> its absorbing conv (-1: none)
+    std::vector<char> stem_fuse;           // op i -> stem_fusable (the stem and the stride-2 3x3 behind it can run as one kernel)
+    float* d_w = nullptr;
+    size_t n_w = 0;
+    // h2 models: the h planes of the two-product stride-1 3x3 convs once more in MFMA operand order (conv_patch_h2r.hip), built on
+    // the device from d_w before the first replay and again after a weight broadcast (ensure_operand_copies)
+    char* d_wr = nullptr;
+    std::vector<long long> wr_off;         // op -> byte offset into d_wr, -1: no copy
+    bool wr_valid = false;
+    unsigned* d_ovf = nullptr;             // h2 models: sticky "a value did not fit fp16" flag (pa_model_take_overflow)
+    float* d_stage = nullptr; size_t stage_cap = 0;   // h2 generic graphs: fp32 input staged here before it is encoded
+    float* d_fc = nullptr;                 // graphs with a PA_OP_GAP_FC op: [max_batch][kGapFcMaxOut] logits, then as many probabilities (plan_buffers)
+    int fc_nout = 0;                       // outputs of that op (0: the graph has none)
+    int max_batch = 64;
+
+    // plan
+    bool planned = false;
+    int p_h0 = 0, p_w0 = 0, p_imgsz = 0, p_pre = 0, p_auto = 0, p_batch = 0;
+    int net_h = 0, net_w = 0;
+    int rw = 0, rh = 0, top = 0, left = 0, lb_mode = 0;
+    std::vector<float*> bptr;
+    void* arena = nullptr;                 // what bptr points into
+    size_t arena_bytes = 0, logical_bytes = 0;   // bytes of the plan with / without liveness aliasing
+    unsigned h_ovf = 0;                    // overflow flag as read back by the last pa_yolo_infer calls (h2 models)
+    bool ovf_cached = false;               // h_ovf is current: no kernel of this model has run since it was read
+    // pa_yolo_submit / pa_yolo_wait: tickets in flight.  slot = ticket % PA_MAX_INFLIGHT; h_pin[slot]: the overflow flag as the
+    // stream read it back after that ticket's kernels (page-locked: a pageable destination would make the copy block the host)
+    unsigned* h_pin = nullptr;
+    hipEvent_t tk_ev[PA_MAX_INFLIGHT]{};
+    bool tk_busy[PA_MAX_INFLIGHT]{};
+    int next_ticket = 0, n_inflight = 0;
+    std::vector<int32_t> classes_host;     // what d_classes holds (set_classes: uploaded again only when the caller's list changes)
+    std::map<int, hipGraphExec_t> graphs;  // op-list replay per batch size (tuning "graph")
+    int graph_epoch = -1;                  // engine tuning epoch the graphs were captured under
+    uint8_t* d_frames = nullptr; size_t frames_cap = 0;
+    uint8_t* d_netin = nullptr;
+    int32_t *d_xtab = nullptr, *d_ytab = nullptr;                 // cv2 bilinear tables
+    ResamplePlan rs;                                              // PIL tables
+    // post
+    int A = 0, P2 = 0;
+    HeadLevel lv[3]{};
+    float* d_cand = nullptr; int32_t* d_cidx = nullptr; int32_t* d_ccnt = nullptr;
+    uint64_t* d_keys = nullptr; int32_t* d_order = nullptr; uint8_t* d_supp = nullptr;
+    float* d_oboxes = nullptr; float* d_okpts = nullptr; int32_t* d_ocnt = nullptr;
+    int32_t* d_classes = nullptr; int classes_cap = 0;
+    int last_n = 0;
+    std::vector<ProfRec> prof;
+    size_t n_prof = 0;
+};
+
+// ---- engine.cpp
+ProfRec* prof_begin(pa_model* m, size_t idx, int kind, int ksize, double flops);
+inline void prof_end(pa_model* m, ProfRec* r) { if (r) hipEventRecord(r->e1, m->e->stream); }
+int finish_profile(pa_model* m, size_t n_rec);
+void free_plan(pa_model* m);                         // the caller has synchronised the stream
+int plan_buffers(pa_model* m, int batch);            // the arena of a model whose net_h x net_w is set: allocation, memsets, bptr, d_fc
+// run_ops, or (tuning "graph", not while profiling) the replay of its capture for this batch size
+int run_graph(pa_model* m, int n, size_t* pi);
+
+// ---- engine_pre.cpp
+hipError_t upload_table(pa_engine* e, int32_t** dptr, const std::vector<int32_t>& v);
+// grow d_frames to max_batch frames if need be and copy nb host frames into it (on the stream); *src then names the device copy
+int stage_frames(pa_model* m, const uint8_t** src, int nb, size_t frame_bytes);
+// tables + temporary for sh x sw -> dh x dw over at most max_batch frames; identity_pass: a source that already has the target
+// size still gets a 1-tap vertical table (the ball session: its pass also reorders channels into 3-byte pixels)
+int resample_plan(pa_engine* e, ResamplePlan* rs, int sh, int sw, int dh, int dw, int filter, int max_batch, bool identity_pass = false);
+void resample_free(ResamplePlan* rs);
+// the one or two passes (horizontal first) of n frames into dst with out_c (3 | 4) bytes per pixel; the last pass reverses channels
+hipError_t resample_enqueue(const ResamplePlan& rs, const uint8_t* src, uint8_t* dst, int n, int out_c, int reverse, hipStream_t s);

@@ -748,7 +748,7 @@ class Model:
             self._free_rings()
 
 
-# ``kind`` of the profile rows that are not ops of the graph (csrc/engine.cpp: PROF_PRE, PROF_DECODE, PROF_NMS)
+# ``kind`` of the profile rows that are not ops of the graph (csrc/engine_internal.h: PROF_PRE, PROF_DECODE, PROF_NMS)
 PROF_PRE, PROF_DECODE, PROF_NMS = 100, 101, 102
 
 

@@ -15,7 +15,7 @@
 //     copy       conv_wants_operand_copy;  absorbed: the upsample is read through in2 (the engine's rule: attach, resolve, detach if nothing reads it)
 //
 // -DCONV_SELECT_PARENT: the same main against a commit that predates conv_select.cpp (its conv .hip objects + libamdhip64): only
-// the four choosers exist there, `copy` is that commit's own condition (engine.cpp: ensure_operand_copies), the other columns print
+// the four choosers exist there, `copy` is that commit's own condition (its engine.cpp: ensure_operand_copies; the engine has since been split, csrc/engine_internal.h), the other columns print
 // as "-".  This is how tests/golden/conv_tile_choices.json was recorded.
 #include "kernels.h"
 

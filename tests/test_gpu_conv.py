@@ -282,7 +282,7 @@ def test_conv_slices(gpu_engine, path, base):
 def test_upsample_absorbed(gpu_engine, shape):
     """Upsample(2) + cat in front of a stride-1 conv is never materialised — the bf16x3 1x1 kernel (YOLOv8's
     FPN joins) and the 3x3 patch kernel (TrackNet's decoder blocks) read the first channels at [y >> 1][x >> 1] of the
-    coarse map (csrc/engine.cpp:find_upsample_folds).  Same arithmetic on the same values: bitwise equal to running the
+    coarse map (csrc/graph_plan.cpp:find_upsample_folds).  Same arithmetic on the same values: bitwise equal to running the
     upsample kernel, for every tile that has the absorbing instantiation; tiles without it keep the upsample kernel."""
     B, H, W, c_up, c_skip, cout, k = shape
     rng = np.random.default_rng(c_up * 7 + c_skip + k)

@@ -39,7 +39,7 @@ from tests.test_gpu_conv import slice_sentinel
 
 pytestmark = pytest.mark.gpu
 
-VEC = {"f32": 4, "f16": 8, "h2": 16}                       # channel granularity of a helper op's slices (engine.cpp: validate_desc)
+VEC = {"f32": 4, "f16": 8, "h2": 16}                       # channel granularity of a helper op's slices (graph_plan.cpp: validate_desc)
 DTYPE = {"f32": G.DTYPE_F32, "f16": G.DTYPE_F16, "h2": G.DTYPE_H2}
 CONTENTS = ("negative", "ties", "ramp", "wide")
 

@@ -54,3 +54,26 @@ def test_pose_known_answers(gpu_engine):
     k = kpts[0, 0].reshape(13, 3)
     assert np.array_equal(k[:, :2], ek[:, :2].astype(np.float32)), k[:3]
     assert np.allclose(k[:, 2], ek[:, 2], atol=3e-7)
+
+
+def test_class_filter_of_postprocess_does_not_leak_into_infer(gpu_engine):
+    """One class list on the device, one host copy of it: ``yolo_postprocess(classes=[1])`` between two
+    ``yolo_infer(classes=[0])`` calls must not leave filter [1] behind for the second (the engine compares the caller's list
+    with the host copy to skip the upload; a path that replaced the device list alone made the third call filter by class 1).
+    64 x 64 frames at imgsz 64: the smallest size at which the calibrated synthetic YOLOv8n returns a class-0 detection."""
+    from tests import synth
+    from tests.helpers import calibrated_state_dict
+    S = 64
+    frames = synth.synthetic_frames(2, S, S, seed=3)
+    sd = calibrated_state_dict("n", 80, None, [f[..., ::-1] for f in frames], S, 0.5, seed=5)
+    m = E.Model(gpu_engine, G.build_yolov8(sd, 80, None, dtype=E.graph_dtype()))
+    m.set_max_batch(2)
+    kw = dict(imgsz=S, conf=0.5, iou=0.7)
+    boxes0, _, counts0 = m.yolo_infer(frames, 2, S, S, classes=[0], **kw)
+    assert int(counts0.sum()) >= 1 and (boxes0[0, :counts0[0], 5] == 0).all() and (boxes0[1, :counts0[1], 5] == 0).all(), counts0
+    heads = [m.read_head(l, 2) for l in range(3)]
+    _, _, counts_other = m.yolo_postprocess(heads, S, S, classes=[1], **kw)
+    boxes1, _, counts1 = m.yolo_infer(frames, 2, S, S, classes=[0], **kw)
+    m.close()
+    assert not np.array_equal(counts_other, counts0), "the class-1 filter keeps other rows than the class-0 one"
+    assert np.array_equal(counts1, counts0) and boxes1.tobytes() == boxes0.tobytes(), (counts0, counts1)

@@ -1,4 +1,4 @@
-"""CPU twins of two claims the fused SPPF kernels and the fp16 helper kernels rest on (csrc/kernels_misc.hip, csrc/engine.cpp).
+"""CPU twins of two claims the fused SPPF kernels and the fp16 helper kernels rest on (csrc/kernels_misc.hip, csrc/graph_plan.cpp).
 
 1. ``sppf_h2_kernel`` / ``sppf_f16_kernel`` compute the row of pixel p without an integer division:
    ``y = (int)(((float)p + 0.5f) * (1.0f / (float)W))``.  The same float32 operations in numpy, for every map width and every pixel
@@ -43,7 +43,7 @@ def _fp16_graphs():
 
 
 def test_fp16_graphs_keep_helper_buffers_a_multiple_of_8_wide():
-    """What validate_desc (csrc/engine.cpp) refuses for fp16 graphs, checked on every graph the builders make.  (Only build_yolov8
+    """What validate_desc (csrc/graph_plan.cpp) refuses for fp16 graphs, checked on every graph the builders make.  (Only build_yolov8
     has an fp16 form: build_tracknet and build_inpaintnet make fp32 / h2 graphs.)"""
     seen = 0
     for name, g in _fp16_graphs():
