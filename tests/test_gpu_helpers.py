@@ -24,9 +24,8 @@ B. The activation epilogues over their whole argument range: an identity 1 x 1 c
    figures are printed and, where the environment names a directory in ``PADEL_REPORT_DIR``, appended to ``act_ulp_sweep.txt`` there
    (profiles/act_ulp_sweep.txt is a copy of one such run).
 
-Out of scope by decision: the stem kernels (``stem_mfma_kernel``, ``stem_l1_h2``).  Their output cannot be read back through the
-C-ABI without a level-3 head behind it; they are covered by whole-graph parity on the n / s / m scales (widths 64 and 80,
-yolov8 l / x, are instantiated and never run: a follow-up)."""
+The stem kernels (``stem_mfma_kernel``, ``stem_l1_h2``) have their own file, tests/test_gpu_stem.py: their output is read back
+through a level-3 head that changes nothing (one-hot unshuffle convs, tests/stem_probe.py), at every width from 16 to 80."""
 import os
 
 import numpy as np
