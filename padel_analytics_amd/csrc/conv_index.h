@@ -1,6 +1,7 @@
 // Index arithmetic shared by the convolution kernels: which tile a workgroup owns, where a tile sits in the image, where a
 // 16-byte operand slot sits in a swizzled LDS plane, division by a launch-time constant.  Integers only and no HIP type, so a
-// plain C++ compiler can include it (tests/conv_index_main.cpp checks every function here on the CPU).
+// plain C++ compiler can include it (tests/conv_index_main.cpp and, for the stem patch, tests/stem_index_main.cpp check every
+// function here on the CPU).
 #pragma once
 
 #if defined(__HIPCC__)
@@ -63,5 +64,41 @@ PADEL_IDX int fastdiv(int n, unsigned magic, unsigned shift) {
 // one kx in registers across its three ky; one order for all kernels keeps their results bitwise identical.
 PADEL_IDX int h2_tap_ky(int t) { return t % 3; }
 PADEL_IDX int h2_tap_kx(int t) { return t / 3; }
+
+// ---- the u8 input patch of the fused stem + layer-1 kernel (stem_l1_h2.hip, register-weights instantiations).  A workgroup owns
+// 4 x 16 pixels of layer 1 at (oy0, ox0): 9 x 33 stem positions p = 33 srow + scol, stem pixel (2 oy0 - 1 + srow, 2 ox0 - 1 + scol),
+// whose tap (dy, dx) is input pixel (4 oy0 - 3 + 2 srow + dy, 4 ox0 - 3 + 2 scol + dx): 19 rows x 67 pixels of the NHWC4 input.
+// The patch in LDS starts one pixel further left (4 ox0 - 4: 16-byte aligned in a row of W % 4 == 0 pixels) and holds 72 words
+// (pixels) per row = 18 chunks of 16 bytes; chunk c = 18 row + ch lies at byte 16 c.  A chunk is wholly inside the image or
+// wholly outside (zeros: the conv's padding, and never a row of the neighbouring frame).
+constexpr int kStemPatchRows = 19, kStemPatchRowW = 72;
+constexpr int kStemPatchChunks = kStemPatchRows * kStemPatchRowW / 4;       // 342
+constexpr int kStemPatchB = kStemPatchRows * kStemPatchRowW * 4;            // 5472
+PADEL_IDX int stem_patch_y0(int oy0) { return 4 * oy0 - 3; }
+PADEL_IDX int stem_patch_x0(int ox0) { return 4 * ox0 - 4; }
+PADEL_IDX int stem_patch_chunk_row(int c) { return c / (kStemPatchRowW / 4); }
+PADEL_IDX int stem_patch_chunk_col(int c) { return 4 * (c % (kStemPatchRowW / 4)); }      // first pixel of the chunk within the patch row
+PADEL_IDX bool stem_patch_chunk_inside(int H, int W, int iy, int ix0) { return (unsigned)iy < (unsigned)H && ix0 >= 0 && ix0 + 4 <= W; }
+// patch word of tap (dy, dx) of stem position p < 297
+PADEL_IDX int stem_patch_tap_word(int p, int dy, int dx) {
+    const int srow = p / 33, scol = p - srow * 33;
+    return (2 * srow + dy) * kStemPatchRowW + 1 + 2 * scol + dx;
+}
+// K slot kk of lane group lq is k = 8 lq + kk = 3 tap + colour (k >= 27: zero).  The 8 slots of a group span the taps
+// 8 lq / 3 .. min(8 lq + 7, 26) / 3 — 3, 4, 3, 1 words; word i of the group is that tap's pixel (i past the span: the last one again,
+// read and not used).
+PADEL_IDX int stem_lq_tap0(int lq) { return 8 * lq / 3; }
+PADEL_IDX int stem_lq_words(int lq) { return (8 * lq + 7 < 26 ? 8 * lq + 7 : 26) / 3 - stem_lq_tap0(lq) + 1; }
+PADEL_IDX int stem_lq_word_tap(int lq, int i) { return stem_lq_tap0(lq) + (i < stem_lq_words(lq) ? i : stem_lq_words(lq) - 1); }
+// Slots 2 j and 2 j + 1 of every group lie in the words lo, lo + 1 with lo = stem_pair_word(j).  Byte selector of v_perm_b32 with
+// S1 = word lo, S0 = word lo + 1: result bytes (slot 2 j, 0, slot 2 j + 1, 0); selector value 4 w + colour, 0x0c: a zero byte.
+PADEL_IDX int stem_pair_word(int j) { return j == 0 ? 0 : j - 1; }
+PADEL_IDX unsigned stem_slot_selector(int lq, int kk) {
+    const int k = 8 * lq + kk;
+    return k >= 27 ? 0x0cu : (unsigned)(4 * (k / 3 - stem_lq_tap0(lq) - stem_pair_word(kk >> 1)) + k % 3);
+}
+PADEL_IDX unsigned stem_pair_selector(int lq, int j) {
+    return stem_slot_selector(lq, 2 * j) | (stem_slot_selector(lq, 2 * j + 1) << 16) | 0x0c000c00u;
+}
 
 }  // namespace padel

@@ -405,6 +405,7 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
             a.H = m->net_h; a.W = m->net_w; a.Ho = Ho; a.Wo = Wo; a.cout = o.cout; a.B = n;
             a.out_f16 = m->d.dtype == PA_DTYPE_F16 ? 1 : m->d.dtype == PA_DTYPE_H2 ? 2 : 0;
             a.ovf_flag = m->d_ovf;
+            a.opw = (m->wr_valid && i < m->wr_off.size() && m->wr_off[i] >= 0) ? (const void*)(m->d_wr + m->wr_off[i]) : nullptr;
             pr = prof_begin(m, (*pi)++, o.kind, 3, 2.0 * n * Ho * Wo * (double)o.cout * 27);
             // tuning "fuse_stem": the stem and the stride-2 3x3 behind it (its only reader) as one kernel; the conv's own
             // turn in this loop is skipped (the profile shows both under the stem's record)
@@ -493,7 +494,8 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
     return 0;
 }
 
-// the operand-order weight copies of conv_patch_h2r.hip: allocated once, (re)built from the blob whenever it changed
+// the operand-order weight copies of conv_patch_h2r.hip and the stem operand block of stem_l1_h2.hip: allocated once, (re)built
+// from the blob whenever it changed
 static int ensure_operand_copies(pa_model* m) {
     if (m->wr_valid || m->d.dtype != PA_DTYPE_H2) return 0;
     pa_engine* e = m->e;
@@ -521,6 +523,11 @@ static int ensure_operand_copies(pa_model* m) {
         size_t total = 0;
         for (size_t i = 0; i < m->ops.size(); ++i) {
             const pa_op_desc& o = m->ops[i];
+            if (o.kind == PA_OP_STEM && m->stem_fuse[i] && (o.cout == 16 || o.cout == 32 || o.cout == 48)) {
+                off[i] = (long long)total;             // the fused stem + layer-1 kernel's stem operand block
+                total += (stem_l1_operand_bytes(o.cout) + 2047) / 2048 * 2048;
+                continue;
+            }
             if (o.kind != PA_OP_CONV || !conv_wants_operand_copy(o.ksize, o.stride, o.cin, (o.flags & PA_CONV_W_SINGLE) != 0)) continue;
             off[i] = (long long)total;
             total += conv_h2r_copy_bytes(o.npad / 16, o.cin, o.ksize);
@@ -534,6 +541,10 @@ static int ensure_operand_copies(pa_model* m) {
     for (size_t i = 0; i < m->ops.size(); ++i) {
         if (m->wr_off[i] < 0) continue;
         const pa_op_desc& o = m->ops[i];
+        if (o.kind == PA_OP_STEM) {
+            PA_HIP(e, launch_stem_l1_operands(m->d_w + o.w_off, o.cout, m->d_wr + m->wr_off[i], e->stream));
+            continue;
+        }
         PA_HIP(e, launch_h2r_repack(m->d_w + o.w_off, m->d_wr + m->wr_off[i], o.npad / 16, o.cin, o.ksize, e->stream));
     }
     m->wr_valid = true;

@@ -134,11 +134,16 @@ struct StemArgs {
     int out_f16;          // 1: `out` is a _Float16 buffer (fp16 models; the stem itself computes in fp32); 2: h2 pairs
     unsigned* ovf_flag;   // out_f16 == 2: raised when a value does not fit the fp16 range
     unsigned howo_magic, howo_shift, wo_magic, wo_shift;   // filled by launch_stem (fill_fastdiv): pixel index -> (n, oy, ox)
+    const void* opw;      // stem_l1_h2.hip: the stem's weights as MFMA operands + inverse row scales (launch_stem_l1_operands; nullptr: none)
 };
 hipError_t launch_stem(const StemArgs& a, hipStream_t s);
 struct ConvArgs;
 bool stem_l1_h2_supported(const StemArgs& st, const ConvArgs& cv);        // stem_l1_h2.hip: stem + the 3x3 stride-2 conv behind it, one kernel
 hipError_t launch_stem_l1_h2(const StemArgs& st, const ConvArgs& cv, hipStream_t s);
+// the stem operand block of its register-weights instantiations (cout = 16 / 32 / 48): per 16-channel fragment 2 KB [h | m][lane][16 B]
+// of w / 255 row-scaled and split into fp16 pairs, then the cout inverse row scales.  Built from the blob's [cout][27] stem weights
+size_t stem_l1_operand_bytes(int cout);
+hipError_t launch_stem_l1_operands(const float* w, int cout, void* blk, hipStream_t s);
 
 // SPPF: three chained MaxPool2d(5,1,2) of slice [choff, choff+c) written to the next three slices
 // (f16 == 1 in these three: the buffers hold _Float16 elements; cs / choff / c count elements, c % 8 == 0;

@@ -12,7 +12,15 @@
 //            v_mfma_f32_16x16x4_f32 (32 cycles each) of the stand-alone stem kernel: 32 instead of 256 matrix-pipe cycles
 //            per fragment, 3 600 of a wave's ~15 700 busy cycles per tile.  sum w (v / 255) becomes sum (w / 255) v: the same
 //            value to fp32 rounding (the stand-alone stem kernel keeps the literal order; tests/test_gpu_h2.py compares the
-//            two to 2e-5 of the head maps).  Then bias, fast SiLU, pair encoding) go to LDS — zeros where layer 1 sees its padding — in COLUMN-PARITY planes:
+//            two to 2e-5 of the head maps).  Where the operands come from depends on the instantiation.  Register weights (WR,
+//            what the engine runs by default): the weight operands and inverse row scales are read ready-made from the stem
+//            operand block that stem_l1_operands_kernel builds once per weight blob (engine.cpp:ensure_operand_copies), and
+//            the tile's u8 input patch — 19 rows x 72 pixels, 5.5 KB, zeros outside the frame — is staged in LDS once per
+//            workgroup with 16-byte loads; a lane then reads the at most four pixel words its 8 K slots lie in and turns
+//            bytes into fp16 with one byte permute, an OR and a packed subtract per slot pair (conv_index.h: stem_patch_*,
+//            checked on the CPU by tests/stem_index_main.cpp).  Weight ring and three products: the split runs in the
+//            prologue of every wave and every K slot is one dword load with its own clamp and border predicate — the
+//            bitwise yardstick of the other path (tests/test_gpu_stem_paths.py).  Then bias, fast SiLU, pair encoding) go to LDS — zeros where layer 1 sees its padding — in COLUMN-PARITY planes:
 //            entry ((row * 2 + (col & 1)) * 17 + col / 2), so that the stride-2 window of a tap (cols 2 ox + kx) is 16
 //            CONSECUTIVE entries, read as MFMA operands exactly like the stride-1 patch kernels read theirs;
 //   phase 2: layer 1 from those planes: waves as 2 row pairs x 2 channel halves (2 x NF fragments each), weights through the
@@ -32,6 +40,45 @@ constexpr int kFEntries = 320;                                      // 9 rows x 
 constexpr int kFPlaneB = kFEntries * 64, kFTPlaneB = kFEntries * 32;
 
 __device__ __forceinline__ int fs_entry(int srow, int scol) { return (srow * 2 + (scol & 1)) * 17 + (scol >> 1); }
+
+// Stem weight rows 16 j .. 16 j + 15 as MFMA operands: lane (lr, lq) holds the K slots k = 8 lq .. 8 lq + 7 of row 16 j + lr (k >= 27:
+// zero).  w / 255, scaled by the power of two that puts the row's largest magnitude into [2^12, 2^13) (graph.py:h2_row_scale), split
+// into an fp16 pair like the packed weights of every other h2 layer.  Returns 1 / scale.  Whole waves only (the row maximum goes
+// through shuffles: the 27 weights of a row sit in the 4 lanes lr + 16 q).
+__device__ __forceinline__ float stem_split_rows(const float* __restrict__ w, int j, int lr, int lq, h16x8& wh, h16x8& wm) {
+    float wv[8], mx = 0.0f;
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+        wv[kk] = 8 * lq + kk < 27 ? w[(j * 16 + lr) * 27 + 8 * lq + kk] / 255.0f : 0.0f;
+        mx = fmaxf(mx, fabsf(wv[kk]));
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));              // the row's largest |w / 255|
+    const int ex = (int)((__float_as_uint(mx) >> 23) & 255u);          // biased exponent: floor(log2 mx) + 127
+    const int e = ex == 0 ? 0 : min(max(139 - ex, -100), 100);         // 12 - floor(log2 mx); denormal / all-zero rows: scale 1
+    const float sc = __uint_as_float((unsigned)(e + 127) << 23), isc = __uint_as_float((unsigned)(127 - e) << 23);
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+        const float x = wv[kk] * sc;
+        const _Float16 hh = (_Float16)x;
+        wh[kk] = hh;
+        wm[kk] = (_Float16)((x - (float)hh) * kH2Scale);
+    }
+    return isc;
+}
+
+// The stem operand block of the register-weights instantiations, built once per weight blob (engine.cpp:ensure_operand_copies):
+// per channel fragment j 2 KB [h | m][lane][16 B], then the cout inverse row scales.  One wave.
+__global__ void __launch_bounds__(64) stem_l1_operands_kernel(const float* __restrict__ w, int nf, char* __restrict__ blk) {
+    const int lane = threadIdx.x & 63, lr = lane & 15, lq = lane >> 4;
+    for (int j = 0; j < nf; ++j) {
+        h16x8 wh, wm;
+        const float isc = stem_split_rows(w, j, lr, lq, wh, wm);
+        *reinterpret_cast<h16x8*>(blk + j * 2048 + lane * 16) = wh;
+        *reinterpret_cast<h16x8*>(blk + j * 2048 + 1024 + lane * 16) = wm;
+        if (lq == 0) reinterpret_cast<float*>(blk + nf * 2048)[j * 16 + lr] = isc;
+    }
+}
 
 }  // namespace
 
@@ -58,9 +105,11 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
                                                      // is 18 MFMAs per wave: with a 2-stage ring every step waited out a DMA round trip)
     static_assert(S_B + NSTG * BSTAGE_B + 1024 <= 80 * 1024, "2 workgroups per CU");
     constexpr int WSTG_B = WR ? 0 : NSTG * BSTAGE_B;               // (register weights: no weight stages)
-    __shared__ __attribute__((aligned(16))) float lds[(S_B + WSTG_B + 1024) / 4];
+    constexpr int XTRA_B = WR ? (kStemPatchB + 15) / 16 * 16 : 1024;    // register weights: the input patch; else the inverse row scales
+    __shared__ __attribute__((aligned(16))) float lds[(S_B + WSTG_B + XTRA_B) / 4];
     char* const ldsb = reinterpret_cast<char*>(lds);
-    float* const s_osc = lds + (S_B + WSTG_B) / 4;                  // 1 / row scale of the stem's weight rows (NF x 16 floats)
+    float* const s_osc = lds + (S_B + WSTG_B) / 4;                  // 1 / row scale of the stem's weight rows (NF x 16 floats; not WR)
+    (void)s_osc;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -131,12 +180,82 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
         PADEL_FS_DMAB(1);
     }
 
-    // ---- phase 1 operands.  K slot kk of lane group lq is k = 8 lq + kk -> tap (dy, dx) = (k / 9, k / 3 % 3), colour byte k % 3
-    // (k >= 27: zero weights AND zero data).  Weights of row lr = channel 16 j + lr: w / 255, scaled by the power of two that
-    // puts the row's largest magnitude into [2^12, 2^13) (graph.py:h2_row_scale), split into fp16 pairs like the packed weights
-    // of every other h2 layer; every wave computes all NF rows sets (24 values per lane), wave 0 publishes the inverse scales.
+    // ---- phase 1 operands: the stem's weight rows (wfh, wfm: stem_split_rows), bias and inverse row scales; per owned fragment of
+    // 16 positions the input bytes as fp16
     h16x8 wfh[NF], wfm[NF];
     f32x4 bias4[NF], osc4[NF];
+    const uint32_t* const img = reinterpret_cast<const uint32_t*>(st.in) + (long long)n * st.H * st.W;
+    h16x8 apx[kFPerWave];                            // per owned position fragment: the 8 K slots of this lane as fp16 (exact bytes)
+    int s_ent[kFPerWave];                            // LDS entry of the fragment's position of this lane, -1: no such position
+    bool s_in[kFPerWave];                            // the position lies inside the stem map (else layer 1 sees its zero padding)
+    if constexpr (WR) {
+        // register weights: the weight operands come ready from the block built once per model (stem_l1_operands_kernel), and the
+        // tile's 19 x 72-pixel input patch goes through LDS once per workgroup: chunk c (16 bytes) of the patch by thread c, c + 256
+        const int py0 = stem_patch_y0(oy0), px0 = stem_patch_x0(ox0);
+        u32x4 pch[2];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int c = tid + 256 * r;
+            const int iy = py0 + stem_patch_chunk_row(c), ix0 = px0 + stem_patch_chunk_col(c);
+            pch[r] = (u32x4){0u, 0u, 0u, 0u};
+#if defined(PADEL_STEM_PROBE) && (PADEL_STEM_PROBE == 2 || PADEL_STEM_PROBE == 5)
+            pch[r] = (u32x4){(unsigned)c, (unsigned)c * 3u, (unsigned)c * 7u, (unsigned)c * 11u};      // probe: no input loads
+#else
+            if (c < kStemPatchChunks && stem_patch_chunk_inside(st.H, st.W, iy, ix0))
+                pch[r] = *reinterpret_cast<const u32x4*>(img + (long long)iy * st.W + ix0);
+#endif
+        }
+        const char* const blk = reinterpret_cast<const char*>(st.opw);
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+            wfh[j] = *reinterpret_cast<const h16x8*>(blk + j * 2048 + lane * 16);
+            wfm[j] = *reinterpret_cast<const h16x8*>(blk + j * 2048 + 1024 + lane * 16);
+            osc4[j] = *reinterpret_cast<const f32x4*>(blk + NF * 2048 + (j * 16 + lq * 4) * 4);
+            bias4[j] = *reinterpret_cast<const f32x4*>(st.bias + j * 16 + lq * 4);
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int c = tid + 256 * r;
+            if (c < kStemPatchChunks) *reinterpret_cast<u32x4*>(ldsb + S_B + c * 16) = pch[r];
+        }
+        // apx from the patch: this lane's (at most four) words relative to a position's tap (0, 0), one byte permute per slot pair;
+        // bytes -> fp16: 0x6400 | b is 1024 + b, minus 1024 (exact).  A position outside the stem map keeps its operands: its result
+        // is replaced by 0 in PADEL_FS_STEM
+        const uint32_t* const s_patch = reinterpret_cast<const uint32_t*>(ldsb + S_B);
+        int woff[4];
+        unsigned psel[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int t = stem_lq_word_tap(lq, i);
+            woff[i] = (t / 3) * kStemPatchRowW + t % 3;
+            psel[i] = stem_pair_selector(lq, i);
+        }
+        __syncthreads();                             // the patch
+#pragma unroll
+        for (int i = 0; i < kFPerWave; ++i) {
+            const int p = (wave + 4 * i) * 16 + lr;
+            const bool pv = (wave + 4 * i) < kFFrags && p < kFPos;
+            const int pc = pv ? p : 0;
+            const int srow = pc / kFCols, scol = pc - srow * kFCols;
+            const int sy = 2 * oy0 - 1 + srow, sx = 2 * ox0 - 1 + scol;
+            s_ent[i] = pv ? fs_entry(srow, scol) : -1;
+            s_in[i] = pv && (unsigned)sy < (unsigned)st.Ho && (unsigned)sx < (unsigned)st.Wo;
+            const uint32_t* const pw = s_patch + stem_patch_tap_word(pc, 0, 0);
+            uint32_t wd[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) wd[k] = pw[woff[k]];
+            u32x4 ap;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t two = __builtin_amdgcn_perm(wd[stem_pair_word(k) + 1], wd[stem_pair_word(k)], psel[k]) | 0x64006400u;
+                ap[k] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(h16x2, two) - (h16x2){(_Float16)1024.0f, (_Float16)1024.0f});
+            }
+            apx[i] = __builtin_bit_cast(h16x8, ap);
+        }
+    } else {
+    // ---- phase 1 operands.  K slot kk of lane group lq is k = 8 lq + kk -> tap (dy, dx) = (k / 9, k / 3 % 3), colour byte k % 3
+    // (k >= 27: zero weights AND zero data).  Weights of row lr = channel 16 j + lr: stem_split_rows; every wave computes all NF row
+    // sets (24 values per lane), wave 0 publishes the inverse scales.
     int kdy[8], kdx[8], ksh[8];
     bool kval[8];
 #pragma unroll
@@ -150,34 +269,13 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
     }
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
-        float wv[8], mx = 0.0f;
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            wv[kk] = kval[kk] ? st.w[(j * 16 + lr) * 27 + 8 * lq + kk] / 255.0f : 0.0f;
-            mx = fmaxf(mx, fabsf(wv[kk]));
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));              // the row's largest |w / 255| (its 27 weights sit in the 4 lanes lr + 16 q)
-        const int ex = (int)((__float_as_uint(mx) >> 23) & 255u);          // biased exponent: floor(log2 mx) + 127
-        const int e = ex == 0 ? 0 : min(max(139 - ex, -100), 100);         // 12 - floor(log2 mx); denormal / all-zero rows: scale 1
-        const float sc = __uint_as_float((unsigned)(e + 127) << 23), isc = __uint_as_float((unsigned)(127 - e) << 23);
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            const float x = wv[kk] * sc;
-            const _Float16 hh = (_Float16)x;
-            wfh[j][kk] = hh;
-            wfm[j][kk] = (_Float16)((x - (float)hh) * kH2Scale);
-        }
+        const float isc = stem_split_rows(st.w, j, lr, lq, wfh[j], wfm[j]);
         if (wave == 0 && lq == 0) s_osc[j * 16 + lr] = isc;
         bias4[j] = *reinterpret_cast<const f32x4*>(st.bias + j * 16 + lq * 4);
     }
     __syncthreads();                                 // the inverse scales
 #pragma unroll
     for (int j = 0; j < NF; ++j) osc4[j] = *reinterpret_cast<const f32x4*>(s_osc + j * 16 + lq * 4);
-    const uint32_t* const img = reinterpret_cast<const uint32_t*>(st.in) + (long long)n * st.H * st.W;
-    h16x8 apx[kFPerWave];                            // per owned position fragment: the 8 K slots of this lane as fp16 (exact bytes)
-    int s_ent[kFPerWave];                            // LDS entry of the fragment's position of this lane, -1: no such position
-    bool s_in[kFPerWave];                            // the position lies inside the stem map (else layer 1 sees its zero padding)
 #pragma unroll
     for (int i = 0; i < kFPerWave; ++i) {
         const int p = (wave + 4 * i) * 16 + lr;
@@ -205,6 +303,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
             const int v = okk[kk] ? (int)((pxw[kk] >> ksh[kk]) & 255u) : 0;
             apx[i][kk] = (_Float16)v;
         }
+    }
     }
     bool bad = false;
 #if defined(PADEL_STEM_PROBE) && (PADEL_STEM_PROBE == 1 || PADEL_STEM_PROBE == 5)
@@ -466,6 +565,14 @@ bool stem_l1_h2_supported(const StemArgs& st, const ConvArgs& a) {
            a.ovf_flag && !a.in2 && !a.res && (st.Ho & 1) == 0 && (st.Wo & 1) == 0;
 }
 
+size_t stem_l1_operand_bytes(int cout) { return (size_t)(cout / 16) * 2048 + (size_t)cout * sizeof(float); }
+
+hipError_t launch_stem_l1_operands(const float* w, int cout, void* blk, hipStream_t s) {
+    if (cout != 16 && cout != 32 && cout != 48) return hipErrorNotSupported;
+    hipLaunchKernelGGL(stem_l1_operands_kernel, dim3(1), dim3(64), 0, s, w, cout / 16, reinterpret_cast<char*>(blk));
+    return hipGetLastError();
+}
+
 hipError_t launch_stem_l1_h2(const StemArgs& st, const ConvArgs& a_in, hipStream_t s) {
     if (!stem_l1_h2_supported(st, a_in)) return hipErrorNotSupported;
     ConvArgs a = a_in;
@@ -473,11 +580,14 @@ hipError_t launch_stem_l1_h2(const StemArgs& st, const ConvArgs& a_in, hipStream
     a.n_mtiles = batch * ((a.Ho + 3) / 4) * ((a.Wo + 15) / 16);
     a.n_ntiles = 1;
     dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8), 1, 1);
-    if (a.w_single && a.wr && !(a.tune & 8)) {           // register weights (tuning bit 3: the round-5 weight ring)
+    // register weights (tuning bit 3: the round-5 weight ring).  They read the stem operand block and stage the input in 16-byte
+    // chunks of 4 pixels: W % 4 == 0
+    if (a.w_single && a.wr && st.opw && (st.W & 3) == 0 && !(a.tune & 8)) {
         switch (st.cout / 16) {
             case 1: hipLaunchKernelGGL((stem_l1_h2_kernel<1, true, true>), grid, dim3(256), 0, s, st, a); return hipGetLastError();
             case 2: hipLaunchKernelGGL((stem_l1_h2_kernel<2, true, true>), grid, dim3(256), 0, s, st, a); return hipGetLastError();
-            // (3 workgroups per CU — the LDS would allow them now — need 168 VGPRs: 11 spilled, 3.42 instead of 3.32 ms on the pose graph)
+            // (3 workgroups per CU — the LDS would allow them: 3 x 46 KB — need 168 VGPRs; the kernel takes 182, and under
+            // __launch_bounds__(256, 3) it spills 14 of them to scratch: not built.  profiles/stem_l1_operands_ab.txt)
             case 3: hipLaunchKernelGGL((stem_l1_h2_kernel<3, true, true>), grid, dim3(256), 0, s, st, a); return hipGetLastError();
             default: return hipErrorNotSupported;
         }
