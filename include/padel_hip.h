@@ -306,7 +306,10 @@ int pa_pil_coeffs(int in_size, int out_size, int filter, int32_t* bounds, int32_
  * (iterable.py:188), windows of 8 consecutive frames + the background are run through the TrackNet
  * model, the 8 overlapping window outputs of each frame are ensembled (ball_tracker.py:449-509) and
  * thresholded at 0.5 (predict.py:184).  The caller gets one 288x512 uint8 mask (255/0) per frame, in
- * frame order, and turns it into coordinates (predict.py:7-39) on the host.                          */
+ * frame order, and turns it into coordinates (predict.py:7-39) on the host.
+ * The TrackNet model may have any storage type: fp32, h2 pairs, or PA_DTYPE_F16 (fp16 activations and
+ * weights, fp32 accumulation; window assembly writes halves, the sigmoid head map stays fp32, so the
+ * ensemble, threshold and locate steps are the same for all three).                                  */
 typedef struct pa_ball pa_ball;
 int pa_ball_create(pa_model* tracknet, int src_h, int src_w, pa_ball** out);
 void pa_ball_destroy(pa_ball* b);

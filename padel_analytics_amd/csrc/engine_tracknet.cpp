@@ -85,8 +85,7 @@ void pa_ball_destroy(pa_ball* b);
 int pa_ball_create(pa_model* m, int src_h, int src_w, pa_ball** out) {
     if (!m || !out) return 1;
     pa_engine* e = m->e;
-    if (m->d.task != PA_TASK_TRACKNET || (m->d.dtype != PA_DTYPE_F32 && m->d.dtype != PA_DTYPE_H2))
-        PA_FAIL(e, "pa_ball_create: not an fp32 / h2 TrackNet model");
+    if (m->d.task != PA_TASK_TRACKNET) PA_FAIL(e, "pa_ball_create: not a TrackNet model");
     if (m->bufs[0].channels != 32) PA_FAIL(e, "pa_ball_create: TrackNet input buffer must have 32 channels (27 + pad)");
     PA_HIP(e, hipSetDevice(e->dev));
     if (src_h <= 0 || src_w <= 0) PA_FAIL(e, "pa_ball_create: unsupported source size %dx%d", src_w, src_h);
@@ -221,7 +220,7 @@ int pa_ball_feed(pa_ball* b, const uint8_t* frames, int n, int on_device, int fl
             BallAssembleArgs aa{};
             aa.median = b->d_med; aa.frames = b->d_small; aa.lut = b->d_lut; aa.out = m->bptr[0];
             aa.B = nw; aa.H = BALL_H; aa.W = BALL_W; aa.ring = b->ring; aa.first_slot = (int)(g_lo % b->ring);
-            aa.out_h2 = m->d.dtype == PA_DTYPE_H2;
+            aa.out_f16 = m->d.dtype == PA_DTYPE_F16 ? 1 : m->d.dtype == PA_DTYPE_H2 ? 2 : 0;
             hipError_t r = launch_ball_assemble(aa, s);
             if (r != hipSuccess) PA_FAIL(e, "ball assemble launch failed: %s", hipGetErrorString(r));
             if (run_graph(m, nw, &prof_n)) return 1;

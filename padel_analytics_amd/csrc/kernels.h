@@ -301,9 +301,10 @@ struct BallAssembleArgs {
     const uint8_t* median;   // [H][W][3] RGB, resized background
     const uint8_t* frames;   // ring [ring][H][W][3] RGB, resized frames
     const float* lut;        // [256] u8 -> float(double(u)/255)
-    float* out;              // [B][H][W][32] fp32 (or h2 pairs: out_h2)
+    float* out;              // [B][H][W][32] fp32, 16-byte aligned (or fp16 / h2 pairs: out_f16)
     int B, H, W, ring, first_slot;
-    int out_h2;              // 1: the TrackNet graph is an h2 graph (h2_common.h)
+    int out_f16;             // 0: fp32; 1: `out` is a _Float16 buffer (fp16 graphs), pad channels 27..31 written as zero;
+                             // 2: the TrackNet graph is an h2 graph (h2_common.h)
 };
 hipError_t launch_ball_assemble(const BallAssembleArgs& a, hipStream_t s);
 

@@ -1,5 +1,5 @@
 // K10 — TrackNet pre/post kernels of the ball path (gfx950), HBM-bound.
-//   ball_assemble_kernel : builds the (27 -> 32 channel) fp32 NHWC network input of a batch of 8-frame
+//   ball_assemble_kernel : builds the (27 -> 32 channel) NHWC network input (fp32, fp16 or h2 pairs) of a batch of 8-frame
 //                          windows from the resized background + resized frames kept as uint8 in HBM
 //                          (reference: ball_tracker/iterable.py:167-199 process_chunck, bg_mode "concat").
 //                          u8 -> float goes through a 256-entry table built on the host as
@@ -32,7 +32,20 @@ __global__ void __launch_bounds__(256) ball_assemble_kernel(const BallAssembleAr
     }
 #pragma unroll
     for (int c = 27; c < 32; ++c) v[c] = 0.0f;
-    if (a.out_h2) {                      // h2 graph: two 16-channel groups of fp16 pairs (values in [0, 1]: always in range)
+    if (a.out_f16 == 1) {                // fp16 graph: 32 halves = 64 bytes per pixel, four 16-byte stores; (_Float16) rounds the table
+                                         // value to nearest even.  The five pad channels are written too: their weights are zero, but
+                                         // 0 x (a stale NaN of the arena) is NaN
+        h16x8* o = reinterpret_cast<h16x8*>(reinterpret_cast<_Float16*>(a.out) + i * 32);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            h16x8 hv;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) hv[r] = (_Float16)v[8 * c + r];
+            o[c] = hv;
+        }
+        return;
+    }
+    if (a.out_f16 == 2) {                // h2 graph: two 16-channel groups of fp16 pairs (values in [0, 1]: always in range)
         bool bad = false;
         char* ob = reinterpret_cast<char*>(a.out + i * 32);
 #pragma unroll
@@ -51,6 +64,7 @@ __global__ void __launch_bounds__(256) ball_assemble_kernel(const BallAssembleAr
 }
 
 hipError_t launch_ball_assemble(const BallAssembleArgs& a, hipStream_t s) {
+    if (a.out_f16 < 0 || a.out_f16 > 2 || (reinterpret_cast<uintptr_t>(a.out) & 15)) return hipErrorInvalidValue;      // 16-byte vector stores
     const long long total = (long long)a.B * a.H * a.W;
     hipLaunchKernelGGL(ball_assemble_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
     return hipGetLastError();

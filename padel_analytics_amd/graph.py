@@ -760,13 +760,16 @@ TRACKNET_BN_EPS = 1e-5      # nn.BatchNorm2d default (reference models.py:9)
 def build_tracknet(sd, dtype: str = "f32") -> Graph:
     """TrackNetV3 U-Net (reference ``trackers/ball_tracker/models.py:45-74``) over the engine's op set.
 
-    Buffer 0 is the fp32 NHWC input with the 27 channels (background + 8 frames x RGB) zero-padded to 32.
+    Buffer 0 is the NHWC input with the 27 channels (background + 8 frames x RGB) zero-padded to 32.
     ``torch.cat([Upsample(x), skip])`` (:66,:68,:70) is a concat buffer whose first slice is written by the
-    upsample op and whose second slice is written directly by the encoder block that produces the skip."""
-    g = Graph(task=TASK_TRACKNET, dtype={"f32": DTYPE_F32, "h2": DTYPE_H2}[dtype])
+    upsample op and whose second slice is written directly by the encoder block that produces the skip.
+
+    ``dtype="f16"``: the same op list, buffers and slices with fp16 activations and weights (every slice is a whole number
+    of 32-channel k-steps already); the sigmoid head buffer stays fp32."""
+    g = Graph(task=TASK_TRACKNET, dtype={"f32": DTYPE_F32, "f16": DTYPE_F16, "h2": DTYPE_H2}[dtype])
     in_dim = int(np.asarray(sd["down_block_1.conv_1.conv.weight"]).shape[1])
     out_dim = int(np.asarray(sd["predictor.weight"]).shape[0])
-    cin0 = pad16(in_dim)
+    cin0 = g.padk(in_dim)
     g.in_channels = cin0
 
     def block(prefix, src, dst):

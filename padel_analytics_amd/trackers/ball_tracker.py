@@ -71,7 +71,14 @@ class BallTracker(Tracker):
 
     def __init__(self, tracking_model_path: str, inpainting_model_path: Optional[str], batch_size: int,
                  median_max_sample_num: int = 1800, median: Optional[np.ndarray] = None,
-                 load_path: Optional[str | Path] = None, save_path: Optional[str | Path] = None):
+                 load_path: Optional[str | Path] = None, save_path: Optional[str | Path] = None, half: bool = False):
+        """``half=True`` runs the TrackNet stage like ``YOLO(half=True)``: fp16 activations and weights, fp32 accumulation, an
+        fp32 sigmoid head map (BASELINE configs[4]).  Everything behind the head map — ensemble, threshold, locate — and the
+        InpaintNet (always on its fp32-equivalent path) are the same as with ``half=False``, the default, which alone meets
+        the parity bar.  As with ``YOLO(half=True)`` there is no range guard: an activation beyond 65504 is stored as the
+        largest fp16 number by the conv epilogues and a weight beyond it becomes inf; the h2 path raises an overflow flag and
+        repeats on bf16x3, this one does not.  ``use_full_range()`` is the way back: it rebuilds the tracker on the default
+        fp32-equivalent path."""
         super().__init__(load_path=load_path, save_path=save_path)
         ck = checkpoint.load_checkpoint(tracking_model_path)
         if ck.task != "tracknet":
@@ -82,7 +89,8 @@ class BallTracker(Tracker):
         assert self.bg_mode == "concat", "only bg_mode='concat' (27 input channels) is wired, like the reference (:402,:443)"
         self._state_dict = ck.state_dict
         self.fp32_mode = E.fp32_mode()           # "h2" (fp16 pairs, 3 products) or "bx3"; see yolo.YOLO
-        self.graph = G.build_tracknet(ck.state_dict, dtype="h2" if self.fp32_mode == "h2" else "f32")
+        self.half = bool(half)
+        self.graph = G.build_tracknet(ck.state_dict, dtype="f16" if self.half else E.graph_dtype(self.fp32_mode))
         self.inpaintnet = None
         if inpainting_model_path:
             ick = checkpoint.load_checkpoint(inpainting_model_path)
@@ -116,12 +124,14 @@ class BallTracker(Tracker):
         return self.graph.dtype != G.DTYPE_H2
 
     def use_full_range(self) -> None:
-        if self.graph.dtype == G.DTYPE_H2:
+        """h2 -> bf16x3 (after an overflow); a ``half=True`` tracker goes back to the default fp32-equivalent path."""
+        if self.half or self.graph.dtype == G.DTYPE_H2:
             if self._model is not None:
                 self._model.close()
                 self._model = None
-            self.fp32_mode = "bx3"
-            self.graph = G.build_tracknet(self._state_dict, dtype="f32")
+            self.fp32_mode = E.fp32_mode() if self.half else "bx3"
+            self.half = False
+            self.graph = G.build_tracknet(self._state_dict, dtype=E.graph_dtype(self.fp32_mode))
 
     def to(self, device: str) -> None:
         if str(device).startswith("cuda"):
