@@ -284,6 +284,32 @@ def bound(t: str, K: int, v: np.ndarray, S: np.ndarray) -> np.ndarray:
     return 1.1 * K * U * S + SILU_ULPS * ulp32(v) + store_term(t, v)
 
 
+# ---- the fp16 conv kernels (tests/test_gpu_f16_epilogue.py): one fp32 accumulation over K exact products, bias, activation -----
+ACT_ULPS = {G.ACT_NONE: 0.0, G.ACT_RELU: 0.0, G.ACT_LEAKY: 1.0, G.ACT_SILU: SILU_ULPS, G.ACT_SIGMOID: SILU_ULPS}
+F16_MAX = 65504.0
+
+
+def ulp16(v: np.ndarray) -> np.ndarray:
+    """Spacing of the fp16 numbers at |v|: 2^(e - 11) for 2^(e - 1) <= |v| < 2^e, 2^-24 below 2^-14 (gradual underflow)."""
+    _, e = np.frexp(np.maximum(np.abs(v), 2.0 ** -14))
+    return np.ldexp(1.0, e - 11)
+
+
+def conv16_bound(K: int, act: int, v: np.ndarray, S: np.ndarray) -> np.ndarray:
+    """fp32-head output of an fp16 conv: |y32 - v| <= 1.1 K u S + ACT_ULPS ulp32(v).  Products of two halves are exact in fp32, so
+    the K = cin k k + 1 roundings are those of the additions (bias included); 1.1 bounds the slope of every activation."""
+    return 1.1 * K * U * S + ACT_ULPS[act] * ulp32(v)
+
+
+def conv16_bound_f16(K: int, act: int, v: np.ndarray, S: np.ndarray, res=None) -> np.ndarray:
+    """The same result stored as a half: ``v`` already includes the residual ``res`` (the stored halves, exact), whose fp32
+    addition costs one more ulp32; then half a unit of the fp16 spacing at the largest value the store may have seen."""
+    b = conv16_bound(K, act, v if res is None else v - res, S)
+    if res is not None:
+        b = b + ulp32(v)
+    return b + 0.5 * ulp16(np.abs(v) + b)
+
+
 def storable(t: str, got: np.ndarray) -> bool:
     """``got`` holds only values the storage type can hold."""
     if t == "f16":

@@ -7,13 +7,15 @@
   not have (the K loop of the wide patch kernels) is absent from the table's ``required_classes``.
 * The pair-store test (tests/test_gpu_h2_epilogue.py) reaches the three pair paths of h2_epilogue on every tile id.
 * The premise of that test: an identity 1x1 reads a pair back exactly, on the CPU twin of the arithmetic.
+* The fp16 store test (tests/test_gpu_f16_epilogue.py) reaches, on every fp16 tile id, every store path of f16_epilogue its
+  fragment count allows, through both heads; its clamp cases reach a 16-byte and an element-wise path on every id.
 * ``parse_profile_text`` reads 10-, 11-, 12- and 13-column lines."""
 import numpy as np
 import pytest
 
 from padel_analytics_amd import engine as E, graph as G
 from tests import tile_support as TS
-from tests import test_gpu_conv as TC, test_gpu_fp16 as TF, test_gpu_h2 as TH, test_gpu_h2_epilogue as TE
+from tests import test_gpu_conv as TC, test_gpu_fp16 as TF, test_gpu_h2 as TH, test_gpu_h2_epilogue as TE, test_gpu_f16_epilogue as T16
 
 SWEEPS = {
     "h2": (TH.H2_TILES, [(c, False) for c in TH.H2_CASES] + [(c, ws) for c in TH.W_SINGLE_CASES for ws in (True, False)]),
@@ -80,6 +82,73 @@ def test_pair_store_cases_reach_every_path_on_every_tile():
         for t, ws in TE.native_runs(case):
             paths.setdefault(t, set()).update(p[:4] for p in TS.h2_store_paths(TS.expected("h2", t, case, ws)[0], t, case))
     assert all(paths.get(t) == {"fast", "slow"} for t in TH.H2_TILES), paths
+
+
+def test_f16_store_paths_by_hand():
+    """Rows a reader can check against csrc/f16_epilogue.h and the launcher tables by eye."""
+    full, part = T16.CASES[0], T16.CASES[3]
+    res = T16.CASES[1]
+    assert TS.f16_store_paths("tap16", 6, full, "f16") == {"pair16"}                       # NF 4: two pairs
+    assert TS.f16_store_paths("tap16", 7, full, "f16") == {"pair16", "tail8"}              # NF 3: a pair and the 8-byte leftover
+    assert TS.f16_store_paths("tap16", 12, full, "f16") == {"tail8"}                       # NF 1: the leftover alone
+    assert TS.f16_store_paths("p16q", 323, res, "f16") == {"pair16_res", "tail8_res"}
+    assert TS.f16_store_paths("p16", 306, res, "f16") == {"pair16_res"}                    # NF 6
+    assert TS.f16_store_paths("tap16d", 47, full, "f32") == {"f32"}
+    assert TS.f16_store_paths("tap16d", 47, res, "f32") == {"slow_f32"}                    # an fp32 head with a residual is never ``wide``
+    assert TS.f16_store_paths("tap16", 7, part, "f16") == {"slow"} and TS.f16_store_paths("tap16", 7, part, "f32") == {"slow_f32"}
+    assert {t for t, nf in TS.F16_NF.items() if nf & 1} == {7, 12, 20, 31, 47, 60, 71, 303, 323}
+
+
+def _f16_paths(cases, tiles_of=T16.native_tiles):
+    seen = {}
+    for case in cases:
+        for t in tiles_of(case):
+            for head, c in T16.head_runs(case):
+                fam = TS.expected("f16", t, c)[0]
+                seen.setdefault(t, set()).update(TS.f16_store_paths(fam, t, c, head))
+    return seen
+
+
+def test_f16_store_cases_reach_every_path_on_every_tile():
+    """f16_epilogue: 16-byte pair stores, the 8-byte leftover of an odd NF, both with the residual loads, 16-byte fp32 stores and the
+    two element-wise forms — each on every tile id whose NF has it, natively, over the cases of tests/test_gpu_f16_epilogue.py."""
+    assert set(T16.TILES) == set(TS.SHAPES["f16"]) == set(TS.F16_NF)
+    seen = _f16_paths(T16.CASES)
+    missing = {t: TS.f16_paths_of_tile(t) - seen.get(t, set()) for t in T16.TILES if TS.f16_paths_of_tile(t) - seen.get(t, set())}
+    assert not missing, missing
+    assert all(seen[t] == TS.f16_paths_of_tile(t) for t in T16.TILES), "a path the tile's NF does not have"
+    assert "pair16" not in seen[12] and all("tail8" not in seen[t] for t in T16.TILES if TS.F16_NF[t] % 2 == 0)
+    # each kernel group (stride-1 3x3 with the patch kernels, 1x1, stride-2 3x3) has whole and partial tiles, a partial fragment, and
+    # every fp16 family sees every activation but through the epilogue they share
+    for k, s in ((3, 1), (1, 1), (3, 2)):
+        grp = [c for c in T16.CASES if (c[5], c[6]) == (k, s)]
+        for t in T16.TILES:
+            if not any(TS.native("f16", t, c) for c in grp):
+                assert t >= 300 and (k, s) != (3, 1)
+                continue
+            cls = set().union(*(TS.classes("f16", TS.expected("f16", t, c)[0], t, c) for c in grp if TS.native("f16", t, c)))
+            assert {"full", "n_tail16", "res", "nores"} <= cls and cls & {"m_tail", "patch_y"}, (k, s, t, cls)
+    assert {c[7] for c in T16.CASES} == set(TS.ACTS)
+    # the clamp: no sigmoid; a 16-byte and an element-wise path on every id; the negative value behind ACT_NONE on both
+    clamp = [T16.CASES[i] for i in T16.CLAMP_CASES]
+    assert all(c[7] != G.ACT_SIGMOID for c in clamp)
+    for cases in (clamp, [c for c in clamp if c[7] == G.ACT_NONE]):
+        got = {}
+        for case in cases:
+            for t in T16.native_tiles(case):
+                got.setdefault(t, set()).update("slow" if p == "slow" else "fast" for p in TS.f16_store_paths(TS.expected("f16", t, case)[0], t, case, "f16"))
+        if cases is clamp:
+            assert all(got.get(t) == {"fast", "slow"} for t in T16.TILES), got
+        else:
+            assert {"fast", "slow"} <= set().union(*got.values())
+    # small magnitudes: per family one whole-tile and one partial-tile run, each with a packed and a scalar conversion
+    fams = {}
+    for i, tiles in T16.SMALL_RUNS:
+        for t in tiles:
+            assert TS.native("f16", t, T16.CASES[i])
+            fam = TS.expected("f16", t, T16.CASES[i])[0]
+            fams.setdefault(fam, set()).update(TS.f16_store_paths(fam, t, T16.CASES[i], "f16"))
+    assert set(fams) == set(T16.FAMILIES) and all(v & {"slow"} and v - {"slow"} for v in fams.values()), fams
 
 
 @pytest.mark.parametrize("corner", [False, True], ids=["mid", "corner"])

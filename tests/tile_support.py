@@ -39,6 +39,13 @@ SHAPES = {
             323: ("patch", 16, 16, 48), 324: ("patch", 16, 16, 64), 326: ("patch", 16, 16, 96)},
 }
 
+# channel fragments (16 channels) per WAVE of every fp16 tile, from the launcher tables of csrc/conv_tap16.hip (launch_conv_t16) and
+# csrc/conv_patch16.hip (launch_conv_p16): f16_epilogue stores fragment pairs with 16 bytes and an odd last fragment with 8
+F16_NF = {6: 4, 7: 3, 9: 4, 11: 2, 12: 1, 20: 3, 30: 4, 31: 3, 32: 2,
+          46: 4, 47: 3, 49: 4, 51: 2, 60: 3, 70: 4, 71: 3, 72: 2,
+          303: 3, 304: 4, 306: 6, 323: 3, 324: 4, 326: 6}
+assert set(F16_NF) == set(SHAPES["f16"])
+
 PATCH_FAMILIES = ("h2p", "h2q", "h2r", "h2v", "h2w", "bx3p", "p16", "p16q")
 NO_K_LOOP = ("h2v", "h2w")          # the wide patch kernels hold the whole K extent (cin <= 48) in LDS: no K loop to exercise
 
@@ -172,6 +179,39 @@ def h2_store_paths(family, tile, case):
     if "full" in cls:
         return {"fast_res" if case[8] else "fast"}
     return {"slow"}          # (its interior workgroups still take the fast path)
+
+
+F16_STORE_PATHS = ("pair16", "tail8", "pair16_res", "tail8_res", "f32", "slow", "slow_f32")
+
+
+def f16_store_paths(family, tile, case, head):
+    """Store paths of csrc/f16_epilogue.h a native fp16 run takes at 8-aligned slices.  ``head``: "f16" (the conv writes halves) or
+    "f32" (it writes the fp32 head buffer itself).  The kernels' ``fast`` predicates (conv_tap16.hip: PADEL_T16_FINISH,
+    conv_patch16.hip) hold for a workgroup whose pixels and channel fragments all exist, i.e. for every workgroup of a ``full``
+    case; ``f16_epilogue`` then takes
+
+      pair16 / pair16_res   one 16-byte store per fragment pair (NF >= 2), with a residual also one 16-byte load
+      tail8 / tail8_res     the 8-byte store (and residual load) of fragment NF - 1 of an odd NF
+      f32                   16-byte fp32 stores — an fp32 head without residual (``wide`` is false for out_f32 with a residual)
+
+    and everything else the element-wise path, ``slow`` or ``slow_f32`` (its interior workgroups still take the fast paths: the
+    rule of ``h2_store_paths``)."""
+    assert head in ("f16", "f32"), head
+    cls = classes("f16", family, tile, case)
+    res = bool(case[8])
+    if head == "f32":
+        return {"f32"} if "full" in cls and not res else {"slow_f32"}
+    if "full" not in cls:
+        return {"slow"}
+    nf, sfx = F16_NF[tile], "_res" if res else ""
+    return ({"pair16" + sfx} if nf >= 2 else set()) | ({"tail8" + sfx} if nf & 1 else set())
+
+
+def f16_paths_of_tile(tile):
+    """Every path of ``f16_store_paths`` the tile's NF allows (both heads, with and without residual)."""
+    nf = F16_NF[tile]
+    fast = ({"pair16", "pair16_res"} if nf >= 2 else set()) | ({"tail8", "tail8_res"} if nf & 1 else set())
+    return fast | {"f32", "slow", "slow_f32"}
 
 
 def native(path, tile, case, w_single=False):
