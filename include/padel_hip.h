@@ -13,7 +13,7 @@
  *
  * Conventions: plain pointers and sizes only; the caller owns every buffer and the
  * library never keeps a caller pointer past return; every call is synchronous at this boundary (the
- * exceptions: the pa_yolo_submit / pa_yolo_wait pair and the stream-ordered pa_yuv420_to_bgr below); one
+ * exceptions: the pa_yolo_submit / pa_yolo_wait pair and the stream-ordered pa_yuv420_to_bgr / pa_render below); one
  * engine per GPU, not thread-safe; return 0 on success, non-zero on failure with the message in
  * pa_last_error().  The Python binding (`padel_analytics_amd/engine.py`, ctypes) is the only caller.
  */
@@ -185,6 +185,67 @@ int pa_yuv420_to_bgr(pa_engine* eng, const uint8_t* src, int src_on_device, int 
 /* tests / tools: which instantiation the last successful pa_yuv420_to_bgr of this engine launched — 1 vector path, 2 byte path,
  * 0 none yet                                                                                                          */
 int pa_yuv_last_path(pa_engine* eng);
+
+/* ---- frames to an encoder: marks drawn on packed BGR frames in HBM, written as BGR or as 8-bit YUV 4:2:0 (csrc/render.hip) ----
+ * One pass: source BGR -> marks applied in registers, in list order -> BGR or NV12 / I420.  Parity with cv2 / supervision drawing
+ * is NOT pinned (neither is installed); the integer rules below are the specification.  Their code is csrc/render_marks.h (host and
+ * device), their readable twin padel_analytics_amd/render.py (render_host).
+ *
+ * A mark is opaque; marks apply in list order, a later one overwrites an earlier one.  Coordinates are integers in [-8192, 8191] and
+ * may lie outside the frame; frames are at most 8192 x 8192, so every product below fits int64.  Pixel (x, y) is covered by
+ *   PA_MARK_DISC     (x - x0)^2 + (y - y0)^2 <= r^2 + r,  r = size in 0..255  (r = 0, 1, 2, 6: 1, 9, 21, 137 pixels)
+ *   PA_MARK_SEGMENT  thickness t = size in 1..255, round caps.  d = P1 - P0, L2 = |d|^2, p = P - P0, s = p . d:
+ *                      L2 = 0 or s <= 0:  4 |p|^2 <= t^2;    s >= L2:  4 |P - P1|^2 <= t^2;
+ *                      otherwise:         4 (p.x d.y - p.y d.x)^2 <= t^2 L2
+ *   PA_MARK_FILL     min(x0, x1) <= x <= max(x0, x1) and the same in y (inclusive)
+ *   PA_MARK_BOX      inside the FILL rectangle and not inside that rectangle shrunk by t = size (1..255) on every side
+ *                    (the border grows inwards)
+ *   PA_MARK_GLYPH    character `arg` of the built-in 5 x 7 font at scale k = size in 1..16, the cell's top-left at (x0, y0): font bit
+ *                    (i, j) covers the k x k block at (x0 + i k, y0 + j k).  Codes: 0-9 A-Z space : . -   x1, y1 must be 0.       */
+enum pa_mark_kind { PA_MARK_DISC = 1, PA_MARK_SEGMENT = 2, PA_MARK_FILL = 3, PA_MARK_BOX = 4, PA_MARK_GLYPH = 5 };
+typedef struct pa_mark {
+    int32_t kind;                 /* enum pa_mark_kind                                  */
+    int32_t x0, y0, x1, y1;
+    int32_t size;                 /* radius, thickness or scale, by kind                */
+    uint32_t bgr;                 /* B | G << 8 | R << 16                                */
+    int32_t arg;                  /* PA_MARK_GLYPH: character code; otherwise 0         */
+} pa_mark;
+/* BGR -> YUV 4:2:0, the inverse of pa_yuv420_to_bgr.  All int32, >> arithmetic:
+ *     Y = clamp(((yr R + yg G + yb B + (1 << 19)) >> 20) + y_off, 0, 255)                        per pixel
+ *     U = clamp(((ur Rs + ug Gs + ub Bs + (1 << 21)) >> 22) + 128, 0, 255)     Rs, Gs, Bs: sums over the 2 x 2 block;  V likewise
+ * The named tables are video.YUV_ENC_COEFFS: round(c * 2^20) of the standard matrices (their chroma rows sum to 0: grey gives
+ * U = V = 128 exactly).  Geometry of the output (layout, pitches, plane offsets, frame stride) is a pa_yuv_desc whose six decode
+ * coefficients are ignored.                                                                                                 */
+typedef struct pa_yuv_enc {
+    int32_t y_off;
+    int32_t yr, yg, yb, ur, ug, ub, vr, vg, vb;
+} pa_yuv_enc;
+enum pa_render_out { PA_RENDER_BGR = 0, PA_RENDER_YUV420 = 1 };
+/* n frames of h x w packed BGR at src_bgr_dev (HBM, frame i at src + i * h * w * 3); frame i carries marks_host[first_host[i] ..
+ * first_host[i + 1]) (first_host: n + 1 entries, first[0] = 0, non-decreasing).  out = PA_RENDER_BGR: n packed frames at dst_dev
+ * (geom, enc ignored; dst_dev == src_bgr_dev renders in place: every thread reads its own pixels before it writes them, and a
+ * tile no mark meets writes nothing); any other overlap of dst and src is the caller's error.  out = PA_RENDER_YUV420: frame i at
+ * dst_dev + i * geom->frame_stride as geom lays it out; w, h even.  The source is never written unless dst == src in BGR mode.
+ * Refused, nothing launched, the reason in pa_last_error: an unknown kind, a coordinate / size / code out of range, a bad first[],
+ * n < 1, w or h over 8192, YUV output with odd or too small w / h, a pitch smaller than its row, planes reaching into the next
+ * frame, NV12 with off_v != off_u + 1, coefficients that could leave int32.  pa_render_check gives the same answers on the host
+ * alone (no engine, no GPU): 0, or 1 with the reason in why[0 .. cap).
+ * ASYNCHRONOUS on the engine's compute stream, like pa_yuv420_to_bgr.  The marks and first[] are copied to an engine-owned staging
+ * buffer (grown on demand, freed with the engine) before the call returns: the caller may reuse its arrays at once.
+ * INVARIANT, as for pa_yuv420_to_bgr: whatever later reads or overwrites dst, overwrites src, or reuses the staging buffer (the
+ * next pa_render) is ordered behind this call by that one stream; work on another stream (pa_upload's copy stream, another
+ * engine) is NOT ordered: pa_engine_synchronize first.
+ * Two store paths, chosen per call from its pointers, pitches, offsets, stride and w % 4: dword loads / stores (16-bit stores for
+ * I420's chroma planes) or bytes, which also cover the tail of widths that are no multiple of 4.                          */
+int pa_render(pa_engine* eng, const uint8_t* src_bgr_dev, int n, int h, int w, const pa_mark* marks_host, const int32_t* first_host,
+              int out, const pa_yuv_desc* geom, const pa_yuv_enc* enc, uint8_t* dst_dev);
+int pa_render_check(int n, int h, int w, const pa_mark* marks_host, const int32_t* first_host, int out, const pa_yuv_desc* geom,
+                    const pa_yuv_enc* enc, char* why, size_t cap);
+/* which instantiation the last successful pa_render of this engine launched — 1 vector path, 2 byte path, 0 none yet */
+int pa_render_last_path(pa_engine* eng);
+/* host only: the 7 rows (top first) of one glyph of the built-in font, column i (0 = leftmost) in bit i of a row; non-zero for a
+ * code outside the font                                                                                                   */
+int pa_glyph_rows(int code, uint8_t rows[7]);
 
 /* tools: device time of whatever is queued on the engine's compute stream between the two calls, from a pair of HIP events
  * recorded on that stream (tools/yuv_bench.py times the asynchronous pa_yuv420_to_bgr with it).  pa_engine_timer_stop waits for

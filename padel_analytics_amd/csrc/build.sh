@@ -4,7 +4,8 @@ set -e
 cd "$(dirname "$0")"
 # PADEL_EXTRA_FLAGS=-DPADEL_BX3_PROBES adds the (wrong-result) ceiling-probe tiles 420 / 520 of conv_tap_bx3.hip,
 # -DPADEL_H2P_PROBES the ablation tiles 332.. of conv_patch_h2.hip, -DPADEL_STEM_PROBE=1|2|4|5 the ablations of stem_l1_h2.hip
-# (profiles/r5m_stem_ablation.txt); PADEL_OUT / PADEL_BUILD_DIR keep such a build apart
+# (profiles/r5m_stem_ablation.txt), -DPADEL_RENDER_PROBE clocks render.hip's cull and apply phases inside the kernel and reports them
+# per call on stderr (profiles/render_bench.txt); PADEL_OUT / PADEL_BUILD_DIR keep such a build apart
 # from the product library (tools only)
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -Wno-unused-value ${PADEL_EXTRA_FLAGS:-}"
 BUILD="${PADEL_BUILD_DIR:-build}"
@@ -12,9 +13,9 @@ OUT="${PADEL_OUT:-../libpadel_hip.so}"
 mkdir -p "$BUILD"
 pids=()
 # PADEL_ONLY="a.hip b.hip": recompile only these translation units and relink with the objects already in $BUILD (iteration)
-ALL="conv_tap.hip conv_tap16.hip conv_tap_bx3.hip conv_patch_bx3.hip conv_tap_h2.hip conv_tap_h2p.hip conv_1x1_h2s.hip conv_patch_h2.hip conv_patch_h2q.hip conv_patch_h2r.hip conv_patch_h2v.hip conv_patch_h2w.hip conv_patch16.hip kernels_misc.hip resnet_ops.hip yolo11_ops.hip stem_l1_h2.hip postproc.hip tracknet_post.hip yuv_convert.hip"
+ALL="conv_tap.hip conv_tap16.hip conv_tap_bx3.hip conv_patch_bx3.hip conv_tap_h2.hip conv_tap_h2p.hip conv_1x1_h2s.hip conv_patch_h2.hip conv_patch_h2q.hip conv_patch_h2r.hip conv_patch_h2v.hip conv_patch_h2w.hip conv_patch16.hip kernels_misc.hip resnet_ops.hip yolo11_ops.hip stem_l1_h2.hip postproc.hip tracknet_post.hip yuv_convert.hip render.hip"
 # the engine (host code that calls the HIP runtime), one translation unit per concern: engine_internal.h
-ENGINE="engine.cpp engine_pre.cpp engine_yolo.cpp engine_tracknet.cpp engine_resnet.cpp engine_comm.cpp"
+ENGINE="engine.cpp engine_pre.cpp engine_yolo.cpp engine_tracknet.cpp engine_resnet.cpp engine_comm.cpp engine_render.cpp"
 for f in ${PADEL_ONLY:-$ALL $ENGINE}; do
   [ -f "$f" ] || continue
   case "$f" in
@@ -32,6 +33,9 @@ g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I/opt/r
 pids+=($!)
 # what is decided about a graph before anything runs (refusals, upsample folds, memory plan, resize tables): no HIP runtime call either
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include ${PADEL_EXTRA_FLAGS:-} -c graph_plan.cpp -o "$BUILD/graph_plan.o" &
+pids+=($!)
+# what pa_render refuses, and the font: no HIP at all (the same file builds into tests/render_marks_main.cpp's program)
+g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c render_check.cpp -o "$BUILD/render_check.o" &
 pids+=($!)
 fi
 for p in "${pids[@]}"; do wait "$p"; done

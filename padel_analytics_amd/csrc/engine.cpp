@@ -88,6 +88,7 @@ void pa_engine_destroy(pa_engine* e) {
     pa_engine_comm_destroy(e);
     if (e->zeros) hipFree(e->zeros);
     if (e->yuv_stage) { if (e->stream) hipStreamSynchronize(e->stream); hipFree(e->yuv_stage); }
+    if (e->render_stage) { if (e->stream) hipStreamSynchronize(e->stream); hipFree(e->render_stage); }
     for (hipEvent_t ev : e->timer_ev) if (ev) hipEventDestroy(ev);
     if (e->stream) hipStreamDestroy(e->stream);
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);

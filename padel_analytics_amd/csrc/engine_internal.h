@@ -4,6 +4,7 @@
 //   engine_yolo.cpp      YOLO plan, prepare, enqueue, post-processing, tickets, read-backs
 //   engine_tracknet.cpp  pa_tracknet_infer and the ball session
 //   engine_resnet.cpp    the ResNet-50 court-keypoint regressor
+//   engine_render.cpp    pa_render: marks on BGR frames -> BGR / YUV 4:2:0 (the refusals and the font: render_check.cpp, host only)
 //   engine_comm.cpp      RCCL
 // What is decided about a graph on the host alone lives in graph_plan.cpp, which kernel runs a conv in conv_select.cpp.
 #pragma once
@@ -59,6 +60,8 @@ struct pa_engine {
     uint8_t* yuv_stage = nullptr; size_t yuv_stage_cap = 0;   // pa_yuv420_to_bgr: raw YUV bytes of a host source, filled and read on `stream` only
     int yuv_last_path = 0;    // 1 vector, 2 byte: what the last pa_yuv420_to_bgr launched (pa_yuv_last_path)
     hipEvent_t timer_ev[2]{};  // pa_engine_timer_start / _stop, created on first use
+    uint8_t* render_stage = nullptr; size_t render_stage_cap = 0;   // pa_render: the resolved marks and first[] of the call in flight, filled and read on `stream` only
+    int render_last_path = 0; // 1 vector, 2 byte: what the last pa_render launched (pa_render_last_path)
 };
 
 extern thread_local std::string g_err;      // errors of calls that have no engine yet (pa_last_error(NULL))

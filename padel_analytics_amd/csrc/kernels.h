@@ -248,6 +248,27 @@ struct YuvArgs {
 bool yuv_vector_path_ok(const YuvArgs& a);              // every address of this launch allows dword / 16-bit accesses
 hipError_t launch_yuv420_to_bgr(const YuvArgs& a, hipStream_t s, int* vec_out = nullptr);      // *vec_out: 1 vector path, 0 byte path
 
+// Marks on packed BGR frames, written as BGR or YUV 4:2:0 (render.hip).  The caller (pa_render) has checked the marks and the
+// geometry (render_check.cpp) and staged the RESOLVED mark list (render_marks.h) and first[] in HBM.
+struct RenderArgs {
+    const uint8_t* src;   // n packed BGR frames
+    uint8_t* dst;
+    const void* marks;    // pa_mark[first[n]], resolved
+    const void* boxes;    // int16 x0, y0, x1, y1 per mark: mark_bbox of each, what the tiles cull by (8 bytes instead of 32)
+    const int32_t* first; // [n + 1]
+    int n, h, w;
+    int out;              // 0 BGR, 1 NV12, 2 I420
+    int in_place;         // BGR output with dst == src: a tile no mark meets stores nothing
+    int pitch_y, pitch_c, off_u, off_v;
+    long long frame_stride;
+    int y_off, yr, yg, yb, ur, ug, ub, vr, vg, vb;
+#ifdef PADEL_RENDER_PROBE
+    unsigned long long* probe;   // tools: {cull, apply, whole kernel} shader-clock cycles summed over the workgroups, and their count
+#endif
+};
+bool render_vector_path_ok(const RenderArgs& a);        // every address of this launch allows dword / 16-bit accesses
+hipError_t launch_render(const RenderArgs& a, hipStream_t s, int* vec_out = nullptr);          // *vec_out: 1 vector path, 0 byte path
+
 // Pillow-style separable resample pass over u8 images (coefficients precomputed on host):
 // out[b][y][x][c] = clip8((sum_k coef[o][k] * in[...lo[o]+k...] + (1<<21)) >> 22)
 struct ResamplePassArgs {

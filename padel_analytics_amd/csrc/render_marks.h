@@ -1,0 +1,85 @@
+// The coverage rules of the renderer's marks (include/padel_hip.h, pa_mark) and each mark's bounding box, for host and device:
+// render.hip applies them to pixel registers, render_check.cpp and tests/render_marks_main.cpp run the same code on the CPU.
+// No HIP runtime call, no table: a glyph mark reaches this code RESOLVED (render_resolve_marks, render_check.cpp: the font lives
+// there, once) — its 35 font bits, bit j * 5 + i for column i of row j, sit in x1 (bits 0..31) and y1 (bits 32..34).
+#pragma once
+#include "../../include/padel_hip.h"
+
+#if defined(__HIPCC__)
+#define PA_HD __host__ __device__ __forceinline__
+#else
+#define PA_HD inline
+#endif
+
+namespace padel {
+
+constexpr int kMarkCoordMin = -8192, kMarkCoordMax = 8191, kRenderMaxSide = 8192;
+constexpr int kGlyphW = 5, kGlyphH = 7, kGlyphMaxScale = 16;
+
+struct MarkBox { int x0, y0, x1, y1; };      // inclusive on every side; every covered pixel lies inside
+
+PA_HD int mark_min(int a, int b) { return a < b ? a : b; }
+PA_HD int mark_max(int a, int b) { return a > b ? a : b; }
+
+PA_HD MarkBox mark_bbox(const pa_mark& m) {
+    switch (m.kind) {
+    case PA_MARK_DISC:                       // dx^2 <= r^2 + r < (r + 1)^2
+        return {m.x0 - m.size, m.y0 - m.size, m.x0 + m.size, m.y0 + m.size};
+    case PA_MARK_SEGMENT: {                  // every covered pixel is within t / 2 of the segment: floor(t / 2) in whole pixels
+        const int e = m.size >> 1;
+        return {mark_min(m.x0, m.x1) - e, mark_min(m.y0, m.y1) - e, mark_max(m.x0, m.x1) + e, mark_max(m.y0, m.y1) + e};
+    }
+    case PA_MARK_FILL:
+    case PA_MARK_BOX:
+        return {mark_min(m.x0, m.x1), mark_min(m.y0, m.y1), mark_max(m.x0, m.x1), mark_max(m.y0, m.y1)};
+    case PA_MARK_GLYPH:
+        return {m.x0, m.y0, m.x0 + kGlyphW * m.size - 1, m.y0 + kGlyphH * m.size - 1};
+    default:
+        return {0, 0, -1, -1};
+    }
+}
+
+PA_HD bool mark_box_meets(const MarkBox& b, int x0, int y0, int x1, int y1) {
+    return b.x0 <= x1 && b.x1 >= x0 && b.y0 <= y1 && b.y1 >= y0;
+}
+
+// Is pixel (x, y), 0 <= x, y < 8192, covered?  The caller has checked the mark (render_validate): with its bounds the int32
+// terms below stay under 2^31 and the int64 ones under 2^62.
+PA_HD bool mark_covers(const pa_mark& m, int x, int y) {
+    switch (m.kind) {
+    case PA_MARK_DISC: {
+        const int dx = x - m.x0, dy = y - m.y0, r = m.size;            // |dx|, |dy| <= 16383: the sum is below 2^30
+        return dx * dx + dy * dy <= r * r + r;
+    }
+    case PA_MARK_SEGMENT: {
+        const int dx = m.x1 - m.x0, dy = m.y1 - m.y0, px = x - m.x0, py = y - m.y0;
+        const long long t2 = (long long)m.size * m.size;
+        const long long L2 = (long long)dx * dx + (long long)dy * dy;
+        const long long s = (long long)px * dx + (long long)py * dy;
+        if (L2 == 0 || s <= 0) return 4 * ((long long)px * px + (long long)py * py) <= t2;
+        if (s >= L2) {
+            const long long qx = x - m.x1, qy = y - m.y1;
+            return 4 * (qx * qx + qy * qy) <= t2;
+        }
+        const long long cross = (long long)px * dy - (long long)py * dx;
+        return 4 * cross * cross <= t2 * L2;
+    }
+    case PA_MARK_FILL:
+        return x >= mark_min(m.x0, m.x1) && x <= mark_max(m.x0, m.x1) && y >= mark_min(m.y0, m.y1) && y <= mark_max(m.y0, m.y1);
+    case PA_MARK_BOX: {
+        const int ax = mark_min(m.x0, m.x1), bx = mark_max(m.x0, m.x1), ay = mark_min(m.y0, m.y1), by = mark_max(m.y0, m.y1), t = m.size;
+        if (x < ax || x > bx || y < ay || y > by) return false;
+        return !(x >= ax + t && x <= bx - t && y >= ay + t && y <= by - t);
+    }
+    case PA_MARK_GLYPH: {
+        const int k = m.size, ex = x - m.x0, ey = y - m.y0;
+        if (ex < 0 || ey < 0 || ex >= kGlyphW * k || ey >= kGlyphH * k) return false;
+        const int bit = (ey / k) * kGlyphW + ex / k;
+        return bit < 32 ? ((unsigned)m.x1 >> bit) & 1u : ((unsigned)m.y1 >> (bit - 32)) & 1u;
+    }
+    default:
+        return false;
+    }
+}
+
+}  // namespace padel

@@ -76,6 +76,24 @@ class pa_yuv_desc(C.Structure):
                 ("cub", C.c_int32)]
 
 
+class pa_mark(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32),
+                ("size", C.c_int32), ("bgr", C.c_uint32), ("arg", C.c_int32)]
+
+
+class pa_yuv_enc(C.Structure):
+    _fields_ = [("y_off", C.c_int32), ("yr", C.c_int32), ("yg", C.c_int32), ("yb", C.c_int32), ("ur", C.c_int32), ("ug", C.c_int32),
+                ("ub", C.c_int32), ("vr", C.c_int32), ("vg", C.c_int32), ("vb", C.c_int32)]
+
+
+#: numpy view of ``pa_mark`` (32 bytes): what ``render.pack`` returns and ``Engine.render`` takes
+MARK_DTYPE = np.dtype([("kind", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("size", "<i4"), ("bgr", "<u4"),
+                       ("arg", "<i4")])
+MARK_DISC, MARK_SEGMENT, MARK_FILL, MARK_BOX, MARK_GLYPH = 1, 2, 3, 4, 5
+RENDER_BGR, RENDER_YUV420 = 0, 1
+#: ``Engine.render_last_path()``
+RENDER_PATH_VECTOR, RENDER_PATH_BYTE = 1, 2
+
 PRE_LETTERBOX, PRE_PIL_STRETCH = 0, 1
 YUV_NV12, YUV_I420 = 0, 1
 #: ``Engine.yuv_last_path()``: which instantiation of the conversion kernel the launcher chose
@@ -98,6 +116,7 @@ ABI_SYMBOLS = [
     "pa_engine_bcast_weights_from", "pa_model_fill_arena", "pa_yolo_submit", "pa_yolo_wait",
     "pa_resnet_infer", "pa_resnet_read_netin", "pa_resnet_read_fc", "pa_resnet_read_head", "pa_pil_coeffs",
     "pa_yuv420_to_bgr", "pa_yuv_last_path", "pa_engine_timer_start", "pa_engine_timer_stop",
+    "pa_render", "pa_render_check", "pa_render_last_path", "pa_glyph_rows",
 ]
 
 
@@ -183,6 +202,10 @@ def load_library():
     lib.pa_yolo_postprocess.argtypes = [vp, C.POINTER(vp), i32, i32, i32, C.POINTER(pa_yolo_params), vp, vp, vp]
     lib.pa_yuv420_to_bgr.argtypes = [vp, vp, i32, i32, i32, i32, C.POINTER(pa_yuv_desc), vp]
     lib.pa_yuv_last_path.argtypes = [vp]
+    lib.pa_render.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, C.POINTER(pa_yuv_desc), C.POINTER(pa_yuv_enc), vp]
+    lib.pa_render_check.argtypes = [i32, i32, i32, vp, vp, i32, C.POINTER(pa_yuv_desc), C.POINTER(pa_yuv_enc), C.c_char_p, sz]
+    lib.pa_render_last_path.argtypes = [vp]
+    lib.pa_glyph_rows.argtypes = [i32, vp]
     lib.pa_engine_timer_start.argtypes = [vp]
     lib.pa_engine_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
     if lib.pa_abi_version() != 5:
@@ -226,6 +249,37 @@ def yuv_span_bytes(n: int, h: int, w: int, d: "pa_yuv_desc") -> Optional[int]:
     if d.frame_stride < extent:
         return None
     return (n - 1) * d.frame_stride + extent
+
+
+def glyph_rows(code) -> Optional[np.ndarray]:
+    """The 7 rows (top first; column i in bit i, 0 = leftmost) of one glyph of the renderer's 5 x 7 font, None for a character
+    the font does not have (``pa_glyph_rows``: host code, no GPU needed)."""
+    rows = np.zeros(7, np.uint8)
+    code = ord(code) if isinstance(code, str) else int(code)
+    return rows if load_library().pa_glyph_rows(code, rows.ctypes.data) == 0 else None
+
+
+def _render_args(marks, first, geom, enc):
+    marks = np.ascontiguousarray(marks, MARK_DTYPE).reshape(-1)
+    first = np.ascontiguousarray(first, np.int32).reshape(-1)
+    if geom is not None and not isinstance(geom, pa_yuv_desc):
+        geom = pa_yuv_desc(**{k: int(v) for k, v in geom.items()})
+    if enc is not None and not isinstance(enc, pa_yuv_enc):
+        enc = pa_yuv_enc(*(int(c) for c in enc))
+    return marks, first, geom, enc
+
+
+def render_check(n: int, h: int, w: int, marks, first, out: int = RENDER_BGR, geom=None, enc=None) -> Optional[str]:
+    """None if ``pa_render`` would accept the call, else its reason for refusing it (``pa_render_check``: host code, no GPU)."""
+    marks, first, geom, enc = _render_args(marks, first, geom, enc)
+    if first.size != max(int(n), 0) + 1:
+        return f"pa_render: first has {first.size} entries, n + 1 = {int(n) + 1} are needed"
+    if marks.size < int(first[-1]):
+        return f"pa_render: first[] announces {int(first[-1])} marks, marks holds {marks.size}"
+    why = C.create_string_buffer(512)
+    rc = load_library().pa_render_check(int(n), int(h), int(w), marks.ctypes.data if marks.size else None, first.ctypes.data, int(out),
+                                        C.byref(geom) if geom is not None else None, C.byref(enc) if enc is not None else None, why, 512)
+    return why.value.decode() if rc else None
 
 
 class DeviceBuffer:
@@ -324,6 +378,36 @@ class Engine:
     def yuv_last_path(self) -> int:
         """YUV_PATH_VECTOR / YUV_PATH_BYTE: what the last successful ``yuv420_to_bgr`` launched (0: none yet)."""
         return int(self.lib.pa_yuv_last_path(self.handle))
+
+    def render(self, src: DeviceBuffer, n: int, h: int, w: int, marks, first, dst: DeviceBuffer, out: int = RENDER_BGR, geom=None,
+               enc=None) -> None:
+        """Draw ``marks`` on ``n`` packed BGR frames of ``h`` x ``w`` in ``src`` and write them to ``dst`` as packed BGR or, with
+        ``out=RENDER_YUV420``, as 8-bit YUV 4:2:0 laid out by ``geom`` (a ``pa_yuv_desc`` or a dict of its fields: ``video.yuv_desc``)
+        with the encode table ``enc`` (``pa_yuv_enc`` or its ten integers: ``video.YUV_ENC_COEFFS``) — ``pa_render``.  ``marks``: an
+        array of ``MARK_DTYPE`` records, frame i owning ``marks[first[i]:first[i + 1]]`` (``render.pack`` builds both).  ``dst`` may be
+        ``src`` itself for BGR output (in place).  Asynchronous: ordered with every later call of this engine by its one compute
+        stream; the mark arrays are consumed before the call returns.  What the kernel cannot run is an ``EngineError``, nothing is
+        launched."""
+        marks, first, geom, enc = _render_args(marks, first, geom, enc)
+        if first.size != max(int(n), 0) + 1:
+            raise EngineError(f"render: first has {first.size} entries, n + 1 = {int(n) + 1} are needed")
+        if marks.size < int(first[-1]):
+            raise EngineError(f"render: first[] announces {int(first[-1])} marks, marks holds {marks.size}")
+        if n >= 1 and h >= 1 and w >= 1 and src.nbytes < n * h * w * 3:
+            raise EngineError(f"render: src holds {src.nbytes} bytes, {n} BGR frames need {n * h * w * 3}")
+        if out == RENDER_YUV420 and geom is not None:
+            need = yuv_span_bytes(n, h, w, geom)
+        else:
+            need = n * h * w * 3 if (n >= 1 and h >= 1 and w >= 1) else None
+        if need is not None and dst.nbytes < need:     # (geometry that has no span is refused by the library, with its reason)
+            raise EngineError(f"render: {n} frames as described span {need} bytes, dst holds {dst.nbytes}")
+        self._check(self.lib.pa_render(self.handle, src.ptr, int(n), int(h), int(w), marks.ctypes.data if marks.size else None,
+                                       first.ctypes.data, int(out), C.byref(geom) if geom is not None else None,
+                                       C.byref(enc) if enc is not None else None, dst.ptr))
+
+    def render_last_path(self) -> int:
+        """RENDER_PATH_VECTOR / RENDER_PATH_BYTE: what the last successful ``render`` launched (0: none yet)."""
+        return int(self.lib.pa_render_last_path(self.handle))
 
     def timer_start(self) -> None:
         """Tools: mark the compute stream with a HIP event; ``timer_stop`` -> milliseconds of device time queued since."""

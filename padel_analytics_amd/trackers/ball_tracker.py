@@ -44,6 +44,13 @@ class Ball(Object):
 
     def asint(self) -> tuple: return tuple(int(v) for v in self.xy)
 
+    def marks(self, **kwargs) -> list:
+        """Reference :180-193: a filled circle of radius 6 in RGB (0, 255, 0) at the ball's position (drawn whatever the
+        visibility, as there)."""
+        from .. import render
+        x, y = self.asint()
+        return [render.disc(x, y, 6, (0, 255, 0))]
+
 
 def predict_location(mask_u8: np.ndarray) -> tuple:
     """predict.py:7-39: bounding rectangle of maximal w*h among the 8-connected foreground components; on ties

@@ -35,6 +35,13 @@ class Keypoint:
 
     def asint(self) -> tuple: return tuple(int(v) for v in self.xy)
 
+    def marks(self) -> list:
+        """Reference :45-70: ``str(id + 1)`` in white with its bottom-left at (x + 5, y - 5) — here the renderer's 5 x 7 font at
+        scale 1 — then a filled circle of radius 6 in RGB (255, 0, 0)."""
+        from .. import render
+        x, y = self.asint()
+        return render.text(str(self.id + 1), x + 5, y - 5 - (render.GLYPH_H - 1), 1, (255, 255, 255)) + [render.disc(x, y, 6, (0, 0, 255))]
+
 
 class Keypoints(Object):
     def __init__(self, keypoints: list):
@@ -53,6 +60,9 @@ class Keypoints(Object):
     def __iter__(self): return iter(self.keypoints)
 
     def __getitem__(self, id: int) -> Keypoint: return self.keypoints_by_id[id]
+
+    def marks(self, **kwargs) -> list:
+        return [m for k in self.keypoints for m in k.marks()]
 
 
 class KeypointsTracker(Tracker):

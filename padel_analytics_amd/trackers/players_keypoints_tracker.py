@@ -34,6 +34,12 @@ class PlayerKeypoint:
 
     def serialize(self) -> dict: return {"id": self.id, "name": self.name, "xy": self.xy}
 
+    def marks(self) -> list:
+        """Reference :44-56: a filled circle of radius 2 in RGB (255, 0, 0)."""
+        from .. import render
+        x, y = self.asint()
+        return [render.disc(x, y, 2, (0, 0, 255))]
+
 
 class PlayerKeypoints:
     """The 13 keypoints of one person (reference :59-162): ``player_keypoints`` (list of ``PlayerKeypoint``),
@@ -97,6 +103,14 @@ class PlayerKeypoints:
 
     def draw(self, frame: np.ndarray) -> np.ndarray: return frame
 
+    def marks(self) -> list:
+        """Reference :137-162: the 13 ``CONNECTIONS`` as lines of thickness 2 in RGB (255, 0, 0); nothing without keypoints."""
+        from .. import render
+        pts = {k.name: k.asint() for k in self.player_keypoints}
+        if not pts:
+            return []
+        return [render.segment(*pts[a], *pts[b], 2, (0, 0, 255)) for a, b in self.CONNECTIONS]
+
 
 class PlayersKeypoints(Object):
     """All players' keypoints of one frame (reference :165-197).  Built from ``PlayerKeypoints`` objects (reference
@@ -141,6 +155,9 @@ class PlayersKeypoints(Object):
     def __iter__(self): return iter(self.players_keypoints)
 
     def __getitem__(self, i: int) -> PlayerKeypoints: return self.players_keypoints[i]
+
+    def marks(self, **kwargs) -> list:
+        return [m for p in self.players_keypoints for m in p.marks()]
 
 
 class PlayerKeypointsTracker(Tracker):

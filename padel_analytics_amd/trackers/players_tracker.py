@@ -83,6 +83,24 @@ class Player:
     def feet(self) -> tuple:
         return int(self.top_left[0] + self.width / 2), int(self.bottom_right[1])
 
+    def marks(self, video_info=None, annotator: str = "rectangle_bounding_box", show_confidence: bool = True) -> list:
+        """Reference :100-169 (supervision's BoxAnnotator + LabelAnnotator in Color.BLUE): the box outline in RGB (0, 0, 255),
+        thickness 2 below 1080 lines and 4 from 1080 up, growing inwards, and the label ``f"{id}: {confidence:.2f}"`` (``f"{id}"``
+        without ``show_confidence``) in white on a filled plate of the box's colour, centred above the box's top edge, font
+        scale 2.  The thickness rule is supervision's ``calculate_optimal_line_thickness`` AS RECALLED, the plate's geometry is
+        this project's: parity with supervision is unpinned (it is not installed).  Every ``annotator`` draws the
+        rectangle."""
+        from .. import render
+        x0, y0 = self.top_left
+        x1, y1 = self.bottom_right
+        lines = video_info.height if video_info is not None else 0
+        t, k, blue = (2 if lines < 1080 else 4), 2, (255, 0, 0)
+        label = f"{self.id}: {self.confidence:.2f}" if show_confidence else f"{self.id}"
+        tw = render.text_width(label, k)
+        tx, ty = (x0 + x1) // 2 - tw // 2, y0 - (render.GLYPH_H + 1) * k
+        return ([render.box(x0, y0, x1, y1, t, blue), render.fill(tx - k, ty - k, tx + tw - 1 + k, y0 - 1, blue)]
+                + render.text(label, tx, ty, k, (255, 255, 255)))
+
     @classmethod
     def from_json(cls, x: dict) -> "Player":
         det = Detections(xyxy=np.array([x["xyxy"]]), confidence=np.array([x["confidence"]]),
@@ -142,6 +160,9 @@ class Players(Object):
     def __iter__(self): return iter(self.players)
 
     def __getitem__(self, i: int) -> Player: return self.players[i]
+
+    def marks(self, **kwargs) -> list:
+        return [m for p in self.players for m in p.marks(**kwargs)]
 
 
 class PlayerTracker(Tracker):

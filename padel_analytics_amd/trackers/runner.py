@@ -17,7 +17,10 @@ Additions (all off by default, the reference's sequential semantics stay the def
   batch trackers consume the same device-resident frames; stream trackers (TrackNet) get the same handles.  The
   reference decodes and uploads the clip once per tracker (:215-220).
 
-``draw_and_collect_data`` (video encode, homography, analytics: SURVEY.md §1 L3') is out of scope."""
+* ``render=`` a ``.y4m`` path or a ``video.FrameSink``: ``draw_and_collect_data`` (reference :91-173) reads the clip again and writes it
+  with every tracker's results drawn on it — on the GPU (csrc/render.hip: marks applied to the BGR frames in HBM and converted to
+  YUV 4:2:0 in one pass), one download and one write per batch.  Without it (the default) the step prints that it is skipped.
+  The 2-D court inset, the homography and ``DataAnalytics`` (SURVEY.md §1 L3') stay out of scope."""
 from __future__ import annotations
 
 import threading
@@ -35,7 +38,7 @@ from .tracker import NoPredictFrames, Tracker, _sampler
 class TrackingRunner:
     def __init__(self, trackers: list, video_path: str | Path, inference_path: str | Path, start: int = 0,
                  end: Optional[int] = None, collect_data: bool = False, *, distributed: bool = False,
-                 fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None) -> None:
+                 fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None, render=None) -> None:
         self.video_path = video_path
         self.inference_path = inference_path
         self.start = start
@@ -61,13 +64,74 @@ class TrackingRunner:
         # queued when its device loop ends drains beside the NEXT tracker's device work (1: the loop waits for its own tail)
         self.host_queue_depth = int(os.environ.get("PADEL_HOST_QUEUE_DEPTH", 8)) if host_queue_depth is None else host_queue_depth
         self._tails: list = []
+        self.render = render               # None | path of the .y4m to write | video.FrameSink
 
     def restart(self) -> None:
         for tracker in self.trackers.values():
             tracker.restart()
 
+    #: frames per Engine.render call / download / write of the render step
+    RENDER_BATCH = 64
+
     def draw_and_collect_data(self) -> None:
-        print("runner: drawing / data collection is outside the hot path of this build (skipped)")
+        if self.render is None:
+            print("runner: drawing / data collection is outside the hot path of this build (skipped)")
+            return
+        if self.distributed and D.rank() != 0:     # the results live on rank 0
+            return
+        self._render_clip()
+
+    def frame_marks(self, i: int) -> list:
+        """The marks of frame ``i`` (counted from ``start``): ``FRAME: i + 1`` (reference :118-127, there cv2's Hershey font in RGB
+        (255, 255, 0) with its bottom-left at (20, 50); here the renderer's font at scale 3), then every tracker's
+        ``results[i].marks(**tracker.draw_kwargs())`` in tracker order."""
+        from .. import render as R
+        k = 3
+        marks = R.text(f"FRAME: {i + 1}", 20, 50 - (R.GLYPH_H * k - 1), k, (0, 255, 255))
+        for tracker in self.trackers.values():
+            if i < len(tracker.results):
+                marks += tracker.results[i].marks(**tracker.draw_kwargs())
+        return marks
+
+    def _render_clip(self) -> None:
+        """The clip once more, ``RENDER_BATCH`` frames at a time: BGR in HBM (``video.device_batch``; host frames through one staging
+        clip), one ``Engine.render`` to YUV 4:2:0 in the sink's geometry, one download, one write."""
+        from .. import engine as E, render as R
+        eng = self.engine or E.default_engine()
+        w, h = self.video_info.width, self.video_info.height
+        own = not isinstance(self.render, video.FrameSink)
+        sink = video.Y4mSink(self.render, w, h, fps=self.video_info.fps) if own else self.render
+        print(f"runner: Writing results into {getattr(sink, 'path', sink)}")
+        bs, fb = self.RENDER_BATCH, h * w * 3
+        dst = eng.alloc(video.yuv_span(bs, h, w, sink.desc))
+        stage = None
+        t0 = timeit.default_timer()
+        done = 0
+        try:
+            for sample in _sampler(self._frames(), bs):
+                n = len(sample)
+                dev = video.device_batch(sample)
+                if dev is None:
+                    if stage is None:
+                        stage = video.DeviceClip(eng, shape=(bs, h, w, 3))
+                    stage.upload(video.host_batch(sample), copy_stream=False)      # synchronous: the render behind it sees the frames
+                    src = stage.buffer.view(0, n * fb)
+                else:
+                    src = dev[0]
+                marks, first = R.pack([self.frame_marks(done + k) for k in range(n)])
+                eng.render(src, n, h, w, marks, first, dst, out=E.RENDER_YUV420, geom=sink.desc, enc=sink.enc)
+                sink.write_device(dst.view(0, video.yuv_span(n, h, w, sink.desc)), n)
+                done += n
+        finally:
+            eng.synchronize()
+            dst.free()
+            if stage is not None:
+                stage.free()
+            if own:
+                sink.close()
+        t1 = timeit.default_timer()
+        self.timings["__render__"] = {"seconds": t1 - t0, "frames": done}
+        print(f"runner: rendered {done} frames in {t1 - t0:.3f} s ({done / max(t1 - t0, 1e-9):.1f} frames/s: render + download + write)")
 
     def _frames(self, lo: int = 0, hi: Optional[int] = None):
         """Frames [start + lo, start + hi) of the clip (hi None: to self.end)."""

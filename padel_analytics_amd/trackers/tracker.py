@@ -57,6 +57,11 @@ class Object(ABC):
         """Annotation is outside the hot path (SURVEY.md §2 #3/#4: OUT OF SCOPE); frames pass through."""
         return frame
 
+    def marks(self, **kwargs) -> list:
+        """What the reference's ``draw`` paints, as marks for the GPU renderer (``padel_analytics_amd.render``; the same keyword
+        arguments, from ``Tracker.draw_kwargs``).  ``TrackingRunner(render=...)`` draws them; the default is nothing."""
+        return []
+
 
 @dataclass
 class TrackingResults:

@@ -199,6 +199,16 @@ YUV_COEFFS = {
     "bt709_full": (0, 1048576, 1651297, -196423, -490863, 1945737),
 }
 YUV_LAYOUTS = {"nv12": 0, "i420": 1}          # enum pa_yuv_layout
+# The other direction (include/padel_hip.h, pa_yuv_enc; csrc/render.hip): name -> (y_off, YR, YG, YB, UR, UG, UB, VR, VG, VB), each
+# round(c * 2^20) of the standard matrix for (Kr, Kb) = (0.299, 0.114) / (0.2126, 0.0722): Y = Kr R + Kg G + Kb B,
+# U = (B - Y) / (2 (1 - Kb)), V = (R - Y) / (2 (1 - Kr)); limited range scales luma by 219 / 255 and chroma by 224 / 255.  The U
+# row and the V row each sum to 0 — grey encodes to U = V = 128 exactly.
+YUV_ENC_COEFFS = {
+    "bt601_limited": (16, 269262, 528618, 102662, -155423, -305128, 460551, 460551, -385654, -74897),
+    "bt709_limited": (16, 191455, 644067, 65019, -105533, -355018, 460551, 460551, -418321, -42230),
+    "bt601_full": (0, 313524, 615514, 119538, -176932, -347356, 524288, 524288, -439026, -85262),
+    "bt709_full": (0, 222927, 749942, 75707, -120138, -404150, 524288, 524288, -476214, -48074),
+}
 _DESC_FIELDS = ("layout", "pitch_y", "pitch_c", "off_u", "off_v", "frame_stride", "y_off", "cy", "cvr", "cug", "cvg", "cub")
 
 
@@ -279,6 +289,36 @@ def yuv420_to_bgr_host(raw, n: int, h: int, w: int, desc) -> np.ndarray:
         out[i, ..., 2] = np.clip((y + np.int32(d["cvr"]) * v) >> 20, 0, 255)
         out[i, ..., 1] = np.clip((y + np.int32(d["cug"]) * u + np.int32(d["cvg"]) * v) >> 20, 0, 255)
         out[i, ..., 0] = np.clip((y + np.int32(d["cub"]) * u) >> 20, 0, 255)
+    return out
+
+
+def bgr_to_yuv420_host(frames: np.ndarray, desc, enc, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """``frames`` (n, h, w, 3) uint8 BGR -> the 1-D byte array of ``n`` frames of 8-bit YUV 4:2:0 laid out by ``desc`` (bytes between
+    the planes and rows stay as ``out`` has them, zero without ``out``), coefficients ``enc`` = (y_off, yr, yg, yb, ur, ug, ub, vr, vg,
+    vb).  The readable twin of the encode half of csrc/render.hip — the same integers (include/padel_hip.h, pa_yuv_enc): int32,
+    ``>>`` arithmetic, chroma from the sums over each 2 x 2 block."""
+    d = _desc_dict(desc)
+    frames = np.asarray(frames)
+    n, h, w = frames.shape[:3]
+    span = yuv_span(n, h, w, d)
+    if out is None:
+        out = np.zeros(span, np.uint8)
+    if out.dtype != np.uint8 or out.ndim != 1 or out.size < span:
+        raise ValueError(f"{n} frames as described span {span} bytes")
+    y_off, yr, yg, yb, ur, ug, ub, vr, vg, vb = (np.int32(c) for c in enc)
+    nv12 = d["layout"] == YUV_LAYOUTS["nv12"]
+    strided = np.lib.stride_tricks.as_strided
+    cs = 2 if nv12 else 1
+    for i in range(n):
+        f = out[i * d["frame_stride"]:]
+        B, G, R = (frames[i, ..., c].astype(np.int32) for c in range(3))
+        Y = np.clip(((yr * R + yg * G + yb * B + np.int32(1 << 19)) >> 20) + y_off, 0, 255)
+        Bs, Gs, Rs = (p[0::2, 0::2] + p[0::2, 1::2] + p[1::2, 0::2] + p[1::2, 1::2] for p in (B, G, R))      # sums over each 2 x 2 block
+        U = np.clip(((ur * Rs + ug * Gs + ub * Bs + np.int32(1 << 21)) >> 22) + 128, 0, 255)
+        V = np.clip(((vr * Rs + vg * Gs + vb * Bs + np.int32(1 << 21)) >> 22) + 128, 0, 255)
+        strided(f, (h, w), (d["pitch_y"], 1))[...] = Y
+        strided(f[d["off_u"]:], (h // 2, w // 2), (d["pitch_c"], cs))[...] = U
+        strided(f[d["off_v"]:], (h // 2, w // 2), (d["pitch_c"], cs))[...] = V
     return out
 
 
@@ -545,6 +585,76 @@ class DeviceYuvClip(_YuvSource):
         if self._owns and self.buffer is not None:
             self.buffer.free()
         self.buffer = None
+
+
+# ---------------------------------------------------------------------------------------------- sinks for rendered frames
+class FrameSink:
+    """Where rendered frames go (``TrackingRunner(render=...)``).  A sink states the form it takes them in — ``w``, ``h``, ``desc``
+    (the ``pa_yuv_desc`` fields the renderer writes by: ``yuv_desc``) and ``enc`` (the ten integers of ``pa_yuv_enc``) — and receives
+    them ``n`` at a time as one ``DeviceBuffer`` of YUV 4:2:0 bytes in HBM.  ``Y4mSink`` downloads and writes them to a file; a
+    hardware encoder's input surfaces would be another sink."""
+    w: int
+    h: int
+    desc: dict
+    enc: tuple
+
+    def write_device(self, buffer, n: int) -> None:
+        raise NotImplementedError
+
+    def close(self) -> None:
+        pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
+class Y4mSink(FrameSink):
+    """Writes a ``.y4m`` file: the header ``YuvClip.from_y4m`` reads back (its colour-range tag included), then ``FRAME\\n`` plus the
+    Y, U and V planes for every frame.  ``layout`` / ``pitch`` / ``pitch_c`` describe the frames it is HANDED (``desc``: tightly
+    packed by default; NV12's interleaved chroma is split into the file's planes on the host); ``matrix`` and ``range`` pick the
+    encode table ``YUV_ENC_COEFFS`` (.y4m has no tag for the matrix: bt601 is what ``from_y4m`` assumes)."""
+
+    def __init__(self, path, w: int, h: int, fps: int = 30, layout: str = "i420", matrix: str = "bt601", range: str = "limited",
+                 pitch: Optional[int] = None, pitch_c: Optional[int] = None):
+        name = f"{matrix}_{range}"
+        if name not in YUV_ENC_COEFFS:
+            raise ValueError(f"no YUV encode table {name!r} (video.YUV_ENC_COEFFS: {', '.join(YUV_ENC_COEFFS)})")
+        self.path, self.w, self.h, self.fps, self.layout = str(path), int(w), int(h), int(fps), layout
+        self.desc = yuv_desc(w, h, layout, matrix, range, pitch, pitch_c)
+        self.enc = YUV_ENC_COEFFS[name]
+        self.extent = yuv_span(1, self.h, self.w, self.desc)
+        self.frames_written = 0
+        self._host = None
+        self._fh = open(self.path, "wb")
+        self._fh.write(f"YUV4MPEG2 W{self.w} H{self.h} F{self.fps}:1 Ip A1:1 C420jpeg XCOLORRANGE={range.upper()}\n".encode("ascii"))
+
+    def write_host(self, raw: np.ndarray, n: int) -> None:
+        """``n`` frames in the 1-D byte array ``raw``, laid out by ``desc``."""
+        d, h, w = self.desc, self.h, self.w
+        strided = np.lib.stride_tricks.as_strided
+        cs = 2 if self.layout == "nv12" else 1
+        for i in range(n):
+            f = raw[i * d["frame_stride"]:]
+            self._fh.write(b"FRAME\n")
+            self._fh.write(np.ascontiguousarray(strided(f, (h, w), (d["pitch_y"], 1))).tobytes())
+            self._fh.write(np.ascontiguousarray(strided(f[d["off_u"]:], (h // 2, w // 2), (d["pitch_c"], cs))).tobytes())
+            self._fh.write(np.ascontiguousarray(strided(f[d["off_v"]:], (h // 2, w // 2), (d["pitch_c"], cs))).tobytes())
+        self.frames_written += n
+
+    def write_device(self, buffer, n: int) -> None:
+        span = yuv_span(n, self.h, self.w, self.desc)
+        if self._host is None or self._host.size < span:
+            self._host = np.empty(span, np.uint8)
+        buffer.download(self._host[:span])             # (synchronous: the render queued before it has finished)
+        self.write_host(self._host, n)
+
+    def close(self) -> None:
+        if self._fh is not None:
+            self._fh.close()
+            self._fh = None
 
 
 # .y4m files opened by path: one clip per file as it is on disk now (every read of the path — VideoInfo, each tracker's pass — shares

@@ -1,0 +1,161 @@
+#!/usr/bin/env python
+"""What drawing the annotated clip costs (csrc/render.hip), alone and as the runner's render step.  GPU only.
+
+(a) the kernel on 64 frames of 1280 x 720 resident in HBM, for a scene of four players with labels and skeletons, a ball, 22 court
+    keypoints and the frame text (the mark count is printed) and for no marks at all, to NV12, I420 and BGR: warm-up calls, then
+    --reps calls between one pair of HIP events on the engine's stream (``pa_engine_timer_start / _stop``).  Reported: microseconds per
+    call, frames/s, GB/s of the 4.5 bytes per pixel a YUV pass must move (3 read, 1.5 written; 6 for BGR) and that as a share of the
+    HBM peak.  The calls rotate over three source / destination sets so that a repetition does not find its bytes in the 256 MB
+    last-level cache.  Every call also copies its marks to the device first (on the same stream), which the event pair includes.
+(b) ``TrackingRunner``'s render step on the same clip and marks, end to end — render + download + write of the ``.y4m`` — with a
+    host clock; the frames come from a ``DeviceClip``.
+
+    python tools/render_bench.py [--frames 64] [--reps 50] [--warmup 5] [--passes 3] [--skip-runner] [--kernel-only]
+
+``--kernel-only`` runs (a) with few repetitions and nothing else: the run to put under ``rocprofv3 --kernel-trace --stats``.
+"""
+import argparse, json, statistics, sys, tempfile, time
+from pathlib import Path
+import numpy as np
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+HBM_PEAK = 8.0e12          # bytes/s, the MI355X's HBM3E specification
+
+
+def scene(i: int, w: int, h: int):
+    """The result objects of frame ``i``: (Players, PlayersKeypoints, Ball, Keypoints) of a plausible padel frame."""
+    from padel_analytics_amd.trackers.ball_tracker import Ball
+    from padel_analytics_amd.trackers.keypoints_tracker import Keypoint, Keypoints
+    from padel_analytics_amd.trackers.players_keypoints_tracker import PlayerKeypoint, PlayerKeypoints, PlayersKeypoints
+    from padel_analytics_amd.trackers.players_tracker import Player, Players
+    rng = np.random.default_rng(1000 + i)
+    players, skeletons = [], []
+    for k in range(4):
+        cx, cy = w * (0.2 + 0.2 * k) + rng.integers(-20, 20), h * (0.35 + 0.1 * (k % 2)) + rng.integers(-10, 10)
+        bw, bh = 70 + 10 * k, 170 + 15 * k
+        players.append(Player.from_row(np.array([cx - bw / 2, cy - bh / 2, cx + bw / 2, cy + bh / 2], np.float32), 0.8 + 0.04 * k, 0, k + 1))
+        names = PlayerKeypoints.KEYPOINTS_NAMES
+        skeletons.append(PlayerKeypoints([PlayerKeypoint(j, n, (cx + rng.integers(-bw // 2, bw // 2), cy + rng.integers(-bh // 2, bh // 2)))
+                                          for j, n in enumerate(names)]))
+    court = Keypoints([Keypoint(j, (w * (0.1 + 0.8 * (j % 6) / 5), h * (0.3 + 0.6 * (j // 6) / 3))) for j in range(22)])
+    return Players(players), PlayersKeypoints(skeletons), Ball(i, (w * 0.5 + 5 * i, h * 0.4 + 2 * i), 1), court
+
+
+class Stored:
+    """A tracker that only holds results (what ``TrackingRunner`` finds after its trackers ran, or loaded their caches)."""
+
+    def __init__(self, name, results, kwargs=None):
+        from padel_analytics_amd.trackers.tracker import TrackingResults
+        self.name, self.kwargs = name, kwargs or {}
+        self.results = TrackingResults()
+        self.results.predictions = results
+
+    def video_info_post_init(self, video_info):
+        if "video_info" in self.kwargs:
+            self.kwargs["video_info"] = video_info
+        return self
+
+    def draw_kwargs(self): return self.kwargs
+    def __len__(self): return len(self.results)
+    def __str__(self): return self.name
+    def restart(self): pass
+
+
+class Joints:
+    """The 13 joints of every skeleton as discs (``PlayerKeypoint.marks``): the reference's own ``PlayersKeypoints.draw`` paints the
+    lines only, a user who wants the joints adds them like this."""
+
+    def __init__(self, pk): self.pk = pk
+    def marks(self, **kw): return [m for p in self.pk for k in p for m in k.marks()]
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--height", type=int, default=720)
+    ap.add_argument("--width", type=int, default=1280)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--passes", type=int, default=3, help="(b): timed passes over the clip")
+    ap.add_argument("--skip-runner", action="store_true")
+    ap.add_argument("--kernel-only", action="store_true")
+    a = ap.parse_args()
+    from padel_analytics_amd import engine as E, render as R, video
+    from padel_analytics_amd.trackers import TrackingRunner
+    from tests import synth                                     # seeded frames (setup only)
+    eng = E.default_engine(0)
+    n, h, w = a.frames, a.height, a.width
+    if a.kernel_only:
+        a.reps, a.skip_runner = min(a.reps, 10), True
+    print("# " + " ".join(["python", "tools/render_bench.py"] + sys.argv[1:]))
+    bgr = synth.synthetic_frames(n, h, w, seed=1000)
+    info = video.VideoInfo(w, h, 30, n)
+    scenes = [scene(i, w, h) for i in range(n)]
+    trackers = [Stored("players_tracker", [s[0] for s in scenes], {"video_info": info, "annotator": "rectangle_bounding_box", "show_confidence": True}),
+                Stored("players_keypoints_tracker", [s[1] for s in scenes]), Stored("joints", [Joints(s[1]) for s in scenes]),
+                Stored("ball_tracker", [s[2] for s in scenes]), Stored("keypoints_tracker", [s[3] for s in scenes])]
+    clip = video.DeviceClip(eng, bgr)
+    tmp = Path(tempfile.mkdtemp(prefix="render_bench_"))
+    runner = TrackingRunner(trackers, clip, tmp / "out.mp4", render=tmp / "out.y4m", engine=eng)
+    per_frame = [runner.frame_marks(i) for i in range(n)]
+    full = R.pack(per_frame)
+    none = R.pack([[] for _ in range(n)])
+    kinds = {k: int((full[0]["kind"] == k).sum()) // n for k in range(1, 6)}
+    print(json.dumps({"what": "scene", "marks_per_frame": len(per_frame[0]), "by_kind_disc_segment_fill_box_glyph": list(kinds.values())}))
+
+    # ---- (a) the kernel
+    SETS = 3
+    enc = video.YUV_ENC_COEFFS["bt601_limited"]
+    src = [clip.buffer] + [eng.alloc(bgr.nbytes).upload(bgr) for _ in range(SETS - 1)]
+    for out_name in ("nv12", "i420", "bgr"):
+        yuv = out_name != "bgr"
+        geom = video.yuv_desc(w, h, out_name) if yuv else None
+        span = video.yuv_span(n, h, w, geom) if yuv else bgr.nbytes
+        dst = [eng.alloc(span) for _ in range(SETS)]
+        moved = n * h * w * (4.5 if yuv else 6.0)
+        for label, (marks, first) in (("scene", full), ("no marks", none)):
+            call = lambda i: eng.render(src[i % SETS], n, h, w, marks, first, dst[i % SETS], out=E.RENDER_YUV420 if yuv else E.RENDER_BGR,
+                                        geom=geom, enc=enc if yuv else None)
+            for i in range(a.warmup):
+                call(i)
+            eng.synchronize()
+            assert eng.render_last_path() == E.RENDER_PATH_VECTOR
+            eng.timer_start()
+            for i in range(a.reps):
+                call(i)
+            ms = eng.timer_stop() / a.reps
+            each = []
+            for i in range(min(a.reps, 20)):
+                eng.timer_start()
+                call(i)
+                each.append(eng.timer_stop())
+            print(json.dumps({"what": "render, HIP events around %d calls" % a.reps, "out": out_name, "marks": label, "frames": n, "h": h, "w": w,
+                              "us_per_call": round(1e3 * ms, 1), "us_single_call_median_min_max": [round(1e3 * statistics.median(each), 1),
+                                                                                                    round(1e3 * min(each), 1), round(1e3 * max(each), 1)],
+                              "frames_per_s": round(n / (ms * 1e-3)), "bytes_moved": int(moved),
+                              "GB_per_s_algorithmic": round(moved / (ms * 1e-3) / 1e9, 1),
+                              "share_of_HBM_peak_8TBps": round(moved / (ms * 1e-3) / HBM_PEAK, 3)}))
+        for b in dst:
+            b.free()
+    for b in src[1:]:
+        b.free()
+
+    # ---- (b) the runner's render step: render + download + write
+    if not a.skip_runner:
+        import contextlib
+        secs = []
+        with contextlib.redirect_stdout(sys.stderr):
+            for k in range(a.passes + 1):                       # one untimed pass first
+                eng.synchronize()
+                t0 = time.perf_counter()
+                runner.draw_and_collect_data()
+                secs.append(time.perf_counter() - t0)
+        secs = secs[1:]
+        med = statistics.median(secs)
+        size = (tmp / "out.y4m").stat().st_size
+        print(json.dumps({"what": "TrackingRunner render step: render + download + write of the .y4m (host clock)", "frames": n, "h": h, "w": w,
+                          "marks_per_frame": len(per_frame[0]), "seconds_median": round(med, 4), "seconds_passes": [round(s, 4) for s in secs],
+                          "frames_per_s": round(n / med, 1), "file_bytes": size, "MB_per_s_written": round(size / med / 1e6, 1)}))
+        (tmp / "out.y4m").unlink()
+    clip.free()
