@@ -191,7 +191,7 @@ int pa_yuv_last_path(pa_engine* eng);
  * is NOT pinned (neither is installed); the integer rules below are the specification.  Their code is csrc/render_marks.h (host and
  * device), their readable twin padel_analytics_amd/render.py (render_host).
  *
- * A mark is opaque; marks apply in list order, a later one overwrites an earlier one.  Coordinates are integers in [-8192, 8191] and
+ * A mark is opaque (PA_MARK_BLEND apart); marks apply in list order, a later one overwrites an earlier one.  Coordinates are integers in [-8192, 8191] and
  * may lie outside the frame; frames are at most 8192 x 8192, so every product below fits int64.  Pixel (x, y) is covered by
  *   PA_MARK_DISC     (x - x0)^2 + (y - y0)^2 <= r^2 + r,  r = size in 0..255  (r = 0, 1, 2, 6: 1, 9, 21, 137 pixels)
  *   PA_MARK_SEGMENT  thickness t = size in 1..255, round caps.  d = P1 - P0, L2 = |d|^2, p = P - P0, s = p . d:
@@ -201,14 +201,19 @@ int pa_yuv_last_path(pa_engine* eng);
  *   PA_MARK_BOX      inside the FILL rectangle and not inside that rectangle shrunk by t = size (1..255) on every side
  *                    (the border grows inwards)
  *   PA_MARK_GLYPH    character `arg` of the built-in 5 x 7 font at scale k = size in 1..16, the cell's top-left at (x0, y0): font bit
- *                    (i, j) covers the k x k block at (x0 + i k, y0 + j k).  Codes: 0-9 A-Z space : . -   x1, y1 must be 0.       */
-enum pa_mark_kind { PA_MARK_DISC = 1, PA_MARK_SEGMENT = 2, PA_MARK_FILL = 3, PA_MARK_BOX = 4, PA_MARK_GLYPH = 5 };
+ *                    (i, j) covers the k x k block at (x0 + i k, y0 + j k).  Codes: 0-9 A-Z space : . -   x1, y1 must be 0.
+ *   PA_MARK_BLEND    the FILL rectangle (size 0..255 accepted and ignored, as for a fill).  The one kind that is NOT opaque: `arg`
+ *                    is the weight a of the mark's colour, in 1..255, and a covered pixel becomes, per channel,
+ *                        (p * (256 - a) + c * a + 128) >> 8
+ *                    p the channel as the marks BEFORE this one in the list left it, c the mark's channel.  A later mark sees the
+ *                    blended value.  (a = 128 over c = 0xffffff: half way to white; p = c stays p for every a.)                   */
+enum pa_mark_kind { PA_MARK_DISC = 1, PA_MARK_SEGMENT = 2, PA_MARK_FILL = 3, PA_MARK_BOX = 4, PA_MARK_GLYPH = 5, PA_MARK_BLEND = 6 };
 typedef struct pa_mark {
     int32_t kind;                 /* enum pa_mark_kind                                  */
     int32_t x0, y0, x1, y1;
     int32_t size;                 /* radius, thickness or scale, by kind                */
     uint32_t bgr;                 /* B | G << 8 | R << 16                                */
-    int32_t arg;                  /* PA_MARK_GLYPH: character code; otherwise 0         */
+    int32_t arg;                  /* PA_MARK_GLYPH: character code; PA_MARK_BLEND: weight 1..255; otherwise 0 */
 } pa_mark;
 /* BGR -> YUV 4:2:0, the inverse of pa_yuv420_to_bgr.  All int32, >> arithmetic:
  *     Y = clamp(((yr R + yg G + yb B + (1 << 19)) >> 20) + y_off, 0, 255)                        per pixel
@@ -226,7 +231,7 @@ enum pa_render_out { PA_RENDER_BGR = 0, PA_RENDER_YUV420 = 1 };
  * (geom, enc ignored; dst_dev == src_bgr_dev renders in place: every thread reads its own pixels before it writes them, and a
  * tile no mark meets writes nothing); any other overlap of dst and src is the caller's error.  out = PA_RENDER_YUV420: frame i at
  * dst_dev + i * geom->frame_stride as geom lays it out; w, h even.  The source is never written unless dst == src in BGR mode.
- * Refused, nothing launched, the reason in pa_last_error: an unknown kind, a coordinate / size / code out of range, a bad first[],
+ * Refused, nothing launched, the reason in pa_last_error: an unknown kind, a coordinate / size / code / weight out of range, a bad first[],
  * n < 1, w or h over 8192, YUV output with odd or too small w / h, a pitch smaller than its row, planes reaching into the next
  * frame, NV12 with off_v != off_u + 1, coefficients that could leave int32.  pa_render_check gives the same answers on the host
  * alone (no engine, no GPU): 0, or 1 with the reason in why[0 .. cap).

@@ -1,0 +1,1 @@
+from .analytics import DataAnalytics, DataPoint, InvalidDataPoint, PlayerPosition  # noqa: F401

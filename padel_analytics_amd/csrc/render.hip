@@ -6,10 +6,13 @@
 // computed once on the host with the same mark_bbox) against the tile, the survivors — only they are read in full — are compacted
 // into LDS IN LIST ORDER (ballot + popcount inside a wave, the four waves' counts in LDS: a
 // thread's slot = survivors before it in the chunk) and applied to the pixel registers before the next chunk is looked at — so a
-// later mark always overwrites an earlier one, within a chunk and across chunks.  A chunk can keep at most kCullChunk marks: the
+// later mark always applies to what the earlier ones left (mark_apply: overwrites it, or PA_MARK_BLEND blends into it), within a chunk
+// and across chunks.  A chunk can keep at most kCullChunk marks: the
 // LDS list cannot overflow.
 // kVec: three dword loads per 4-pixel row, dword stores of Y, of BGR and of NV12's UV, 16-bit stores for I420's planes — only when
 // the launcher has checked every address of THIS launch; otherwise bytes, which also cover widths that are no multiple of 4.
+#include <type_traits>
+
 #include "kernels.h"
 #include "render_marks.h"
 
@@ -136,11 +139,29 @@ __global__ void __launch_bounds__(256) render_kernel(const RenderArgs a) {
                 const uint4 l = s_marks[k * 2], u = s_marks[k * 2 + 1];
                 pa_mark m;
                 m.kind = (int)l.x; m.x0 = (int)l.y; m.y0 = (int)l.z; m.x1 = (int)l.w; m.y1 = (int)u.x; m.size = (int)u.y; m.bgr = u.z; m.arg = (int)u.w;
+                // One switch per mark, not one per pixel: the record is the same for every lane (the compiler keeps it in scalar
+                // registers), so this is a scalar branch, and inside an arm the kind is a constant — mark_covers is that kind's rule
+                // alone and mark_apply the colour, or for PA_MARK_BLEND the weighted sum: an opaque mark pays nothing for the kind
+                // that blends.  (One loop over the pixels with the kind tested inside it cost the 206-mark scene 13-24 % once there
+                // were six kinds: profiles/render_blend.txt)
+                const auto apply = [&](auto kind) {
+                    pa_mark mk = m;
+                    mk.kind = decltype(kind)::value;
 #pragma unroll
-                for (int r = 0; r < 2; ++r)
+                    for (int r = 0; r < 2; ++r)
 #pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (mark_covers(m, px + c, py + r)) pix[r][c] = m.bgr;
+                        for (int c = 0; c < 4; ++c)
+                            if (mark_covers(mk, px + c, py + r)) pix[r][c] = mark_apply(mk, pix[r][c]);
+                };
+                switch (m.kind) {
+                case PA_MARK_DISC: apply(std::integral_constant<int, PA_MARK_DISC>()); break;
+                case PA_MARK_SEGMENT: apply(std::integral_constant<int, PA_MARK_SEGMENT>()); break;
+                case PA_MARK_FILL: apply(std::integral_constant<int, PA_MARK_FILL>()); break;
+                case PA_MARK_BOX: apply(std::integral_constant<int, PA_MARK_BOX>()); break;
+                case PA_MARK_GLYPH: apply(std::integral_constant<int, PA_MARK_GLYPH>()); break;
+                case PA_MARK_BLEND: apply(std::integral_constant<int, PA_MARK_BLEND>()); break;
+                default: break;                              // (render_validate lets no other kind through)
+                }
             }
         }
         __syncthreads();                                 // everyone is done with the list and the counts before the next chunk rewrites them

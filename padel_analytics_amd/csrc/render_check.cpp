@@ -103,17 +103,19 @@ int render_validate(int n, int h, int w, const pa_mark* marks, const int32_t* fi
     if (total > 0 && !marks) FAIL("pa_render: %d marks announced by first[], marks is NULL", total);
     for (int k = 0; k < total; ++k) {
         const pa_mark& m = marks[k];
-        if (m.kind < PA_MARK_DISC || m.kind > PA_MARK_GLYPH) FAIL("pa_render: mark %d has unknown kind %d", k, m.kind);
+        if (m.kind < PA_MARK_DISC || m.kind > PA_MARK_BLEND) FAIL("pa_render: mark %d has unknown kind %d", k, m.kind);
         if (!coord_ok(m.x0) || !coord_ok(m.y0) || !coord_ok(m.x1) || !coord_ok(m.y1))
             FAIL("pa_render: mark %d has a coordinate outside [%d, %d] (%d, %d, %d, %d)", k, kMarkCoordMin, kMarkCoordMax, m.x0, m.y0, m.x1, m.y1);
-        // (a fill has no size: 0..255 are accepted and ignored)
-        const int lo = (m.kind == PA_MARK_DISC || m.kind == PA_MARK_FILL) ? 0 : 1, hi = m.kind == PA_MARK_GLYPH ? kGlyphMaxScale : 255;
+        // (a fill and a blend have no size: 0..255 are accepted and ignored)
+        const int lo = (m.kind == PA_MARK_DISC || m.kind == PA_MARK_FILL || m.kind == PA_MARK_BLEND) ? 0 : 1, hi = m.kind == PA_MARK_GLYPH ? kGlyphMaxScale : 255;
         if (m.size < lo || m.size > hi) FAIL("pa_render: mark %d (kind %d) has size %d outside [%d, %d]", k, m.kind, m.size, lo, hi);
         if (m.bgr > 0xffffffu) FAIL("pa_render: mark %d has colour 0x%x beyond 24 bits", k, m.bgr);
         uint8_t rows[kGlyphH];
         if (m.kind == PA_MARK_GLYPH) {
             if (glyph_rows(m.arg, rows)) FAIL("pa_render: mark %d names character code %d, which the font does not have", k, m.arg);
             if (m.x1 != 0 || m.y1 != 0) FAIL("pa_render: glyph mark %d has x1, y1 = %d, %d, must be 0", k, m.x1, m.y1);
+        } else if (m.kind == PA_MARK_BLEND) {
+            if (m.arg < 1 || m.arg > 255) FAIL("pa_render: blend mark %d has weight %d outside [1, 255]", k, m.arg);
         } else if (m.arg != 0) FAIL("pa_render: mark %d (kind %d) has arg %d, must be 0", k, m.kind, m.arg);
     }
     if (out == PA_RENDER_BGR) {

@@ -1,4 +1,5 @@
-// The coverage rules of the renderer's marks (include/padel_hip.h, pa_mark) and each mark's bounding box, for host and device:
+// The coverage rules of the renderer's marks (include/padel_hip.h, pa_mark), each mark's bounding box and what a covered pixel becomes
+// (mark_apply: the colour, or PA_MARK_BLEND's weighted sum), for host and device:
 // render.hip applies them to pixel registers, render_check.cpp and tests/render_marks_main.cpp run the same code on the CPU.
 // No HIP runtime call, no table: a glyph mark reaches this code RESOLVED (render_resolve_marks, render_check.cpp: the font lives
 // there, once) — its 35 font bits, bit j * 5 + i for column i of row j, sit in x1 (bits 0..31) and y1 (bits 32..34).
@@ -31,6 +32,7 @@ PA_HD MarkBox mark_bbox(const pa_mark& m) {
     }
     case PA_MARK_FILL:
     case PA_MARK_BOX:
+    case PA_MARK_BLEND:
         return {mark_min(m.x0, m.x1), mark_min(m.y0, m.y1), mark_max(m.x0, m.x1), mark_max(m.y0, m.y1)};
     case PA_MARK_GLYPH:
         return {m.x0, m.y0, m.x0 + kGlyphW * m.size - 1, m.y0 + kGlyphH * m.size - 1};
@@ -65,6 +67,7 @@ PA_HD bool mark_covers(const pa_mark& m, int x, int y) {
         return 4 * cross * cross <= t2 * L2;
     }
     case PA_MARK_FILL:
+    case PA_MARK_BLEND:
         return x >= mark_min(m.x0, m.x1) && x <= mark_max(m.x0, m.x1) && y >= mark_min(m.y0, m.y1) && y <= mark_max(m.y0, m.y1);
     case PA_MARK_BOX: {
         const int ax = mark_min(m.x0, m.x1), bx = mark_max(m.x0, m.x1), ay = mark_min(m.y0, m.y1), by = mark_max(m.y0, m.y1), t = m.size;
@@ -80,6 +83,17 @@ PA_HD bool mark_covers(const pa_mark& m, int x, int y) {
     default:
         return false;
     }
+}
+
+// What a COVERED pixel p (B | G << 8 | R << 16) becomes under mark m: the mark's colour, or for PA_MARK_BLEND with weight a = arg in
+// 1..255 (render_validate) per channel (p * (256 - a) + c * a + 128) >> 8 — at most 255 * 256 + 128 < 2^16, so B and R are blended
+// together in one multiply (bits 0..15 and 16..31 of a 32-bit word, the sum of the two weights being 256: no carry between them)
+PA_HD unsigned mark_apply(const pa_mark& m, unsigned p) {
+    if (m.kind != PA_MARK_BLEND) return m.bgr;
+    const unsigned a = (unsigned)m.arg, b = 256u - a, c = m.bgr;
+    const unsigned rb = ((p & 0xff00ffu) * b + (c & 0xff00ffu) * a + 0x800080u) >> 8;
+    const unsigned g = ((p & 0xff00u) * b + (c & 0xff00u) * a + 0x8000u) >> 8;
+    return (rb & 0xff00ffu) | (g & 0xff00u);
 }
 
 }  // namespace padel

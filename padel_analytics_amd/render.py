@@ -1,9 +1,10 @@
 """Marks for the renderer (``Engine.render`` / ``pa_render``, csrc/render.hip) and its numpy twin.
 
 A mark is one record of ``engine.MARK_DTYPE`` — kind, x0, y0, x1, y1, size, bgr, arg — built here by ``disc``, ``segment``,
-``box``, ``fill`` and ``text``; ``pack`` turns one list of marks per frame into the (``marks``, ``first``) pair the engine takes.
+``box``, ``fill``, ``blend`` and ``text``; ``pack`` turns one list of marks per frame into the (``marks``, ``first``) pair the engine takes.
 ``render_host`` applies them with numpy: the CPU path, and the readable statement of the integer coverage rules that
-include/padel_hip.h specifies (``pa_mark``) — opaque marks, applied in list order, a later mark overwriting an earlier one.
+include/padel_hip.h specifies (``pa_mark``) — marks applied in list order, a later mark overwriting an earlier one, or, for the
+one kind that is not opaque (``blend``), mixing its colour into what the earlier ones left.
 Parity with cv2 / supervision drawing is not pinned (neither is installed); these rules are the specification."""
 from __future__ import annotations
 
@@ -41,6 +42,12 @@ def segment(x0, y0, x1, y1, t: int, bgr) -> tuple:
 
 def fill(x0, y0, x1, y1, bgr) -> tuple:
     return (E.MARK_FILL, _c(x0), _c(y0), _c(x1), _c(y1), 0, _bgr(bgr), 0)
+
+
+def blend(x0, y0, x1, y1, bgr, weight: int) -> tuple:
+    """The rectangle of ``fill`` with ``bgr`` mixed in at ``weight`` / 256, ``weight`` in 1..255 (128 over white: cv2's ``addWeighted``
+    at 0.5): per channel ``(p * (256 - weight) + c * weight + 128) >> 8``."""
+    return (E.MARK_BLEND, _c(x0), _c(y0), _c(x1), _c(y1), 0, _bgr(bgr), int(weight))
 
 
 def box(x0, y0, x1, y1, t: int, bgr) -> tuple:
@@ -101,7 +108,7 @@ def coverage(mark, h: int, w: int) -> tuple:
     elif kind == E.MARK_SEGMENT:
         e = size // 2
         bb = (min(x0, x1) - e, min(y0, y1) - e, max(x0, x1) + e, max(y0, y1) + e)
-    elif kind in (E.MARK_FILL, E.MARK_BOX):
+    elif kind in (E.MARK_FILL, E.MARK_BOX, E.MARK_BLEND):
         bb = (min(x0, x1), min(y0, y1), max(x0, x1), max(y0, y1))
     elif kind == E.MARK_GLYPH:
         bb = (x0, y0, x0 + GLYPH_W * size - 1, y0 + GLYPH_H * size - 1)
@@ -122,7 +129,7 @@ def coverage(mark, h: int, w: int) -> tuple:
         near1 = 4 * ((x - x1) ** 2 + (y - y1) ** 2) <= t2
         cross = px * dy - py * dx
         m = np.where((L2 == 0) | (s <= 0), near0, np.where(s >= L2, near1, 4 * cross * cross <= t2 * L2))
-    elif kind == E.MARK_FILL:
+    elif kind in (E.MARK_FILL, E.MARK_BLEND):
         m = np.ones((by - ay + 1, bx - ax + 1), bool)
     elif kind == E.MARK_BOX:
         inner = (x >= bb[0] + size) & (x <= bb[2] - size) & (y >= bb[1] + size) & (y <= bb[3] - size)
@@ -141,7 +148,13 @@ def draw_host(frame: np.ndarray, marks) -> np.ndarray:
             continue
         y0, x0, m = c
         bgr = int(mk[6])
-        frame[y0:y0 + m.shape[0], x0:x0 + m.shape[1]][m] = (bgr & 0xff, (bgr >> 8) & 0xff, (bgr >> 16) & 0xff)
+        c = np.array([bgr & 0xff, (bgr >> 8) & 0xff, (bgr >> 16) & 0xff], np.int64)
+        region = frame[y0:y0 + m.shape[0], x0:x0 + m.shape[1]]
+        if int(mk[0]) == E.MARK_BLEND:
+            a = int(mk[7])
+            region[m] = ((region[m].astype(np.int64) * (256 - a) + c * a + 128) >> 8).astype(np.uint8)
+        else:
+            region[m] = c.astype(np.uint8)
     return frame
 
 

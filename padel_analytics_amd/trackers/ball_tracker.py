@@ -51,6 +51,13 @@ class Ball(Object):
         x, y = self.asint()
         return [render.disc(x, y, 6, (0, 255, 0))]
 
+    def projection_marks(self) -> list:
+        """Reference :195-205, the ball in the court inset: a filled circle of radius 6 in RGB (255, 255, 0) at ``projection``."""
+        if not self.projection:
+            return []
+        from .. import render
+        return [render.disc(self.projection[0], self.projection[1], 6, (0, 255, 255))]
+
 
 def predict_location(mask_u8: np.ndarray) -> tuple:
     """predict.py:7-39: bounding rectangle of maximal w*h among the 8-connected foreground components; on ties

@@ -101,6 +101,17 @@ class Player:
         return ([render.box(x0, y0, x1, y1, t, blue), render.fill(tx - k, ty - k, tx + tw - 1 + k, y0 - 1, blue)]
                 + render.text(label, tx, ty, k, (255, 255, 255)))
 
+    def projection_marks(self) -> list:
+        """Reference :171-192, the player in the court inset: a filled circle of radius 8 in RGB (0, 0, 255) at ``projection`` and
+        the id in the same colour with its bottom-left at (x, y - 10) — here the renderer's font at the labels' scale 2.  Nothing
+        without a projection."""
+        if not self.projection:
+            return []
+        from .. import render
+        x, y = self.projection
+        k, blue = 2, (255, 0, 0)
+        return [render.disc(x, y, 8, blue)] + render.text(str(self.id), x, y - 10 - (render.GLYPH_H * k - 1), k, blue)
+
     @classmethod
     def from_json(cls, x: dict) -> "Player":
         det = Detections(xyxy=np.array([x["xyxy"]]), confidence=np.array([x["confidence"]]),
@@ -163,6 +174,9 @@ class Players(Object):
 
     def marks(self, **kwargs) -> list:
         return [m for p in self.players for m in p.marks(**kwargs)]
+
+    def projection_marks(self) -> list:
+        return [m for p in self.players for m in p.projection_marks()]
 
 
 class PlayerTracker(Tracker):

@@ -19,8 +19,15 @@ Additions (all off by default, the reference's sequential semantics stay the def
 
 * ``render=`` a ``.y4m`` path or a ``video.FrameSink``: ``draw_and_collect_data`` (reference :91-173) reads the clip again and writes it
   with every tracker's results drawn on it — on the GPU (csrc/render.hip: marks applied to the BGR frames in HBM and converted to
-  YUV 4:2:0 in one pass), one download and one write per batch.  Without it (the default) the step prints that it is skipped.
-  The 2-D court inset, the homography and ``DataAnalytics`` (SURVEY.md §1 L3') stay out of scope."""
+  YUV 4:2:0 in one pass), one download and one write per batch.  Without it (the default) the step prints that it is skipped;
+* ``collect_data=True`` (the reference's own switch, :74-79): the step also projects every frame's players and ball into the 2-D
+  court (``projected_court.ProjectedCourt.project_batch``: the reference's homography state machine :633-647, the frames of a batch
+  that need a homography solved together) and fills ``self.data_analytics`` (``analytics.DataAnalytics``) with the players' positions
+  in metres, frame by frame in the reference's order (:139-167) — the hand-over of its ``main.py``,
+  ``runner.data_analytics.into_dataframe(fps)``.  With ``render`` the court inset is drawn too (``court_inset``: None = "iff
+  ``collect_data``"): the translucent panel — the renderer's one blending mark — the court, and the projected players and ball.
+  Without ``render`` the data are collected from the stored results alone: no frame is read, no GPU touched.  ``timings["__collect__"]``
+  is the host time of projection and collection.  Under ``distributed`` all of it is rank 0's."""
 from __future__ import annotations
 
 import threading
@@ -38,7 +45,8 @@ from .tracker import NoPredictFrames, Tracker, _sampler
 class TrackingRunner:
     def __init__(self, trackers: list, video_path: str | Path, inference_path: str | Path, start: int = 0,
                  end: Optional[int] = None, collect_data: bool = False, *, distributed: bool = False,
-                 fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None, render=None) -> None:
+                 fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None, render=None,
+                 court_inset: Optional[bool] = None) -> None:
         self.video_path = video_path
         self.inference_path = inference_path
         self.start = start
@@ -54,8 +62,22 @@ class TrackingRunner:
         self.trackers = {}
         for tracker in trackers:
             self.trackers[str(tracker)] = tracker.video_info_post_init(self.video_info)
+        # reference :59-79: fixed keypoints keep the first homography for the whole clip
+        from ..projected_court import ProjectedCourt
+        from ..analytics import DataAnalytics
+        self.is_fixed_keypoints = False
+        for tracker in trackers:
+            if self._object_name(tracker) == "Keypoints":
+                self.is_fixed_keypoints = getattr(tracker, "fixed_keypoints_detection", None) is not None
+        self.projected_court = ProjectedCourt(self.video_info)
         self.collect_data = collect_data
-        self.data_analytics = None
+        self.data_analytics = DataAnalytics() if collect_data else None
+        self.court_inset = bool(collect_data) if court_inset is None else bool(court_inset)   # None: on iff collect_data
+        self._projected: list = []         # FrameProjection of frames [0, len): filled in frame order, the homography carrying over
+        self._collect_seconds = 0.0
+        self._told: set = set()            # what was said once about missing data
+        if collect_data:
+            print("runner: Ready for data collection" + (" (fixed court keypoints)" if self.is_fixed_keypoints else ""))
         self.timings: dict = {}
         self.distributed = distributed
         self.fanout = fanout
@@ -69,33 +91,121 @@ class TrackingRunner:
     def restart(self) -> None:
         for tracker in self.trackers.values():
             tracker.restart()
+        self._restart_collection()
+
+    def _restart_collection(self) -> None:
+        """Forget the projections and what was collected: the homography is a state machine over the frames from the first one on."""
+        if self.data_analytics is not None:        # (not its truth value: that is len(), 0 after a clip of no frames)
+            self.data_analytics.restart()
+        self._projected, self.projected_court.H = [], None
 
     #: frames per Engine.render call / download / write of the render step
     RENDER_BATCH = 64
 
     def draw_and_collect_data(self) -> None:
-        if self.render is None:
+        if self.render is None and self.data_analytics is None:
             print("runner: drawing / data collection is outside the hot path of this build (skipped)")
             return
         if self.distributed and D.rank() != 0:     # the results live on rank 0
             return
-        self._render_clip()
+        projecting = self.court_inset or self.data_analytics is not None
+        # every pass starts over: a second call does not append the clip's datapoints again, and projections that frame_marks /
+        # inset_marks cached before the trackers had stored their results do not stay
+        self._restart_collection()
+        self._collect_seconds = 0.0
+        if self.render is None:                    # the stored results alone: no frame is read, no GPU touched
+            done = 0
+            while done < self.n_available:
+                n = min(self.RENDER_BATCH, self.n_available - done)
+                self._collect(done, n)
+                done += n
+        else:
+            done = self._render_clip()
+        if self.data_analytics is not None:
+            self.data_analytics.frames = self.data_analytics.frames[:-1]          # reference :167: remove the extra frame
+            print(f"runner: collected the players' positions of {done} frames ({len(self.data_analytics)} in data_analytics)")
+        if projecting:
+            self.timings["__collect__"] = {"seconds": self._collect_seconds, "frames": done}
+
+    @staticmethod
+    def _object_name(tracker) -> Optional[str]:
+        """The name of the tracker's result type (``Players`` / ``Ball`` / ``Keypoints`` are what the projection looks for); None
+        for a holder of results that states none."""
+        obj = getattr(tracker, "object", None)
+        return getattr(obj(), "__name__", None) if callable(obj) else None
+
+    def _tell_once(self, what: str) -> None:
+        if what not in self._told:
+            self._told.add(what)
+            print(f"runner: {what}")
+
+    def _project_through(self, hi: int) -> None:
+        """Projections of frames [len(self._projected), hi), ``RENDER_BATCH`` at a time, in frame order (the homography is a state
+        machine over the frames): each frame's Players / Ball / Keypoints are the stored results of the tracker of that type (the
+        last one, if several: reference :141-146)."""
+        t0 = timeit.default_timer()
+        while len(self._projected) < hi:
+            lo = len(self._projected)
+            n = min(self.RENDER_BATCH, hi - lo)
+            per = {"Keypoints": [None] * n, "Players": [None] * n, "Ball": [None] * n}
+            for tracker in self.trackers.values():
+                name = self._object_name(tracker)
+                if name in per:
+                    per[name] = [tracker.results[i] if i < len(tracker.results) else None for i in range(lo, lo + n)]
+            self._projected += self.projected_court.project_batch(per["Keypoints"], per["Players"], per["Ball"], self.is_fixed_keypoints)
+        self._collect_seconds += timeit.default_timer() - t0
+
+    def _collect(self, lo: int, n: int) -> None:
+        """Frames [lo, lo + n): project them, and put every projected player's position, in metres from the court centre, into
+        ``data_analytics`` (reference :541-567), one ``step`` per frame (:159-160).  Where the reference prints, frame after frame,
+        that data are missing, this says so once."""
+        self._project_through(lo + n)
+        t0 = timeit.default_timer()
+        shift = self.projected_court.court_keypoints.shift_point_origin
+        for fp in self._projected[lo:lo + n]:
+            if fp.H is None:
+                self._tell_once("no homography for some frames (no court keypoints): nothing is projected there")
+            elif fp.players is None:
+                self._tell_once("Missing data for players projection in some frames")
+            if self.data_analytics is not None:
+                for player in fp.players or ():
+                    self.data_analytics.add_player_position(
+                        id=player.id, position=shift(tuple(float(v) for v in player.projection), "meters"))
+                self.data_analytics.step(1)
+        self._collect_seconds += timeit.default_timer() - t0
+
+    def inset_marks(self, i: int) -> list:
+        """The court inset of frame ``i``, in the reference's order (:630-668): the panel and the court, the projected players,
+        the projected ball."""
+        self._project_through(i + 1)
+        fp = self._projected[i]
+        marks = self.projected_court.inset_marks()
+        if fp.players is not None:
+            marks += fp.players.projection_marks()
+        if fp.ball is not None:
+            marks += fp.ball.projection_marks()
+        return marks
 
     def frame_marks(self, i: int) -> list:
         """The marks of frame ``i`` (counted from ``start``): ``FRAME: i + 1`` (reference :118-127, there cv2's Hershey font in RGB
         (255, 255, 0) with its bottom-left at (20, 50); here the renderer's font at scale 3), then every tracker's
-        ``results[i].marks(**tracker.draw_kwargs())`` in tracker order."""
+        ``results[i].marks(**tracker.draw_kwargs())`` in tracker order, then — with ``court_inset`` — ``inset_marks(i)``.  The
+        projections behind the inset are computed once, in frame order, from the results stored at that moment and kept until the next
+        ``draw_and_collect_data`` or ``restart``, which start over."""
         from .. import render as R
         k = 3
         marks = R.text(f"FRAME: {i + 1}", 20, 50 - (R.GLYPH_H * k - 1), k, (0, 255, 255))
         for tracker in self.trackers.values():
             if i < len(tracker.results):
                 marks += tracker.results[i].marks(**tracker.draw_kwargs())
+        if self.court_inset:
+            marks += self.inset_marks(i)
         return marks
 
-    def _render_clip(self) -> None:
+    def _render_clip(self) -> int:
         """The clip once more, ``RENDER_BATCH`` frames at a time: BGR in HBM (``video.device_batch``; host frames through one staging
-        clip), one ``Engine.render`` to YUV 4:2:0 in the sink's geometry, one download, one write."""
+        clip), one ``Engine.render`` to YUV 4:2:0 in the sink's geometry, one download, one write.  With the inset or the collection
+        on, each batch is projected (and collected) first.  -> the number of frames."""
         from .. import engine as E, render as R
         eng = self.engine or E.default_engine()
         w, h = self.video_info.width, self.video_info.height
@@ -118,6 +228,8 @@ class TrackingRunner:
                     src = stage.buffer.view(0, n * fb)
                 else:
                     src = dev[0]
+                if self.court_inset or self.data_analytics is not None:
+                    self._collect(done, n)
                 marks, first = R.pack([self.frame_marks(done + k) for k in range(n)])
                 eng.render(src, n, h, w, marks, first, dst, out=E.RENDER_YUV420, geom=sink.desc, enc=sink.enc)
                 sink.write_device(dst.view(0, video.yuv_span(n, h, w, sink.desc)), n)
@@ -132,6 +244,7 @@ class TrackingRunner:
         t1 = timeit.default_timer()
         self.timings["__render__"] = {"seconds": t1 - t0, "frames": done}
         print(f"runner: rendered {done} frames in {t1 - t0:.3f} s ({done / max(t1 - t0, 1e-9):.1f} frames/s: render + download + write)")
+        return done
 
     def _frames(self, lo: int = 0, hi: Optional[int] = None):
         """Frames [start + lo, start + hi) of the clip (hi None: to self.end)."""

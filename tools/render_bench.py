@@ -7,14 +7,17 @@
     call, frames/s, GB/s of the 4.5 bytes per pixel a YUV pass must move (3 read, 1.5 written; 6 for BGR) and that as a share of the
     HBM peak.  The calls rotate over three source / destination sets so that a repetition does not find its bytes in the 256 MB
     last-level cache.  Every call also copies its marks to the device first (on the same stream), which the event pair includes.
+    A third scene adds the court inset (``TrackingRunner(collect_data=True)``: the blending panel, the drawn court, the projected
+    players and ball) to the first; a library that refuses the blending mark skips it and says so.
 (b) ``TrackingRunner``'s render step on the same clip and marks, end to end — render + download + write of the ``.y4m`` — with a
-    host clock; the frames come from a ``DeviceClip``.
+    host clock; the frames come from a ``DeviceClip``.  Then the same with ``collect_data=True`` — projection, collection and the inset
+    on top — once with fixed court keypoints (one homography per clip) and once with keypoints that differ per frame (one per frame).
 
     python tools/render_bench.py [--frames 64] [--reps 50] [--warmup 5] [--passes 3] [--skip-runner] [--kernel-only]
 
 ``--kernel-only`` runs (a) with few repetitions and nothing else: the run to put under ``rocprofv3 --kernel-trace --stats``.
 """
-import argparse, json, statistics, sys, tempfile, time
+import argparse, contextlib, json, statistics, sys, tempfile, time
 from pathlib import Path
 import numpy as np
 ROOT = Path(__file__).resolve().parents[1]
@@ -45,11 +48,14 @@ def scene(i: int, w: int, h: int):
 class Stored:
     """A tracker that only holds results (what ``TrackingRunner`` finds after its trackers ran, or loaded their caches)."""
 
-    def __init__(self, name, results, kwargs=None):
+    def __init__(self, name, results, kwargs=None, kind=None, fixed_keypoints_detection=None):
         from padel_analytics_amd.trackers.tracker import TrackingResults
-        self.name, self.kwargs = name, kwargs or {}
+        self.name, self.kwargs, self.kind = name, kwargs or {}, kind
         self.results = TrackingResults()
         self.results.predictions = results
+        self.fixed_keypoints_detection = fixed_keypoints_detection
+
+    def object(self): return self.kind
 
     def video_info_post_init(self, video_info):
         if "video_info" in self.kwargs:
@@ -60,6 +66,22 @@ class Stored:
     def __len__(self): return len(self.results)
     def __str__(self): return self.name
     def restart(self): pass
+
+
+def court_view(i: int, w: int, h: int, court):
+    """22 court keypoints as a camera behind the baseline sees them in frame ``i`` (the drawn court's corners as a trapezoid that
+    sways a little from frame to frame, half a pixel of detector noise): what ``project_batch`` solves a homography from."""
+    from padel_analytics_amd import projected_court as PC
+    from padel_analytics_amd.trackers.keypoints_tracker import Keypoint, Keypoints
+    rng = np.random.default_rng(5000 + i)
+    ck = court.court_keypoints
+    corners = np.array([ck.k1, ck.k2, ck.k11, ck.k12], np.float64)
+    seen = np.array([[0.14, 0.92], [0.86, 0.9], [0.33, 0.32], [0.67, 0.33]]) * (w, h) + rng.normal(0, 2.0, (4, 2))
+    back = np.linalg.inv(PC.find_homography(seen, corners))
+    dst = np.array([k.xy for k in ck.keypoints(number_keypoints=22)])
+    q = np.c_[dst, np.ones(22)] @ back.T
+    xy = q[:, :2] / q[:, 2:] + rng.normal(0, 0.5, (22, 2))
+    return Keypoints([Keypoint(j, (float(x), float(y))) for j, (x, y) in enumerate(xy)])
 
 
 class Joints:
@@ -92,9 +114,12 @@ if __name__ == "__main__":
     bgr = synth.synthetic_frames(n, h, w, seed=1000)
     info = video.VideoInfo(w, h, 30, n)
     scenes = [scene(i, w, h) for i in range(n)]
-    trackers = [Stored("players_tracker", [s[0] for s in scenes], {"video_info": info, "annotator": "rectangle_bounding_box", "show_confidence": True}),
+    from padel_analytics_amd.trackers.ball_tracker import Ball
+    from padel_analytics_amd.trackers.keypoints_tracker import Keypoints
+    from padel_analytics_amd.trackers.players_tracker import Players
+    trackers = [Stored("players_tracker", [s[0] for s in scenes], {"video_info": info, "annotator": "rectangle_bounding_box", "show_confidence": True}, Players),
                 Stored("players_keypoints_tracker", [s[1] for s in scenes]), Stored("joints", [Joints(s[1]) for s in scenes]),
-                Stored("ball_tracker", [s[2] for s in scenes]), Stored("keypoints_tracker", [s[3] for s in scenes])]
+                Stored("ball_tracker", [s[2] for s in scenes], kind=Ball), Stored("keypoints_tracker", [s[3] for s in scenes], kind=Keypoints)]
     clip = video.DeviceClip(eng, bgr)
     tmp = Path(tempfile.mkdtemp(prefix="render_bench_"))
     runner = TrackingRunner(trackers, clip, tmp / "out.mp4", render=tmp / "out.y4m", engine=eng)
@@ -103,6 +128,23 @@ if __name__ == "__main__":
     none = R.pack([[] for _ in range(n)])
     kinds = {k: int((full[0]["kind"] == k).sum()) // n for k in range(1, 6)}
     print(json.dumps({"what": "scene", "marks_per_frame": len(per_frame[0]), "by_kind_disc_segment_fill_box_glyph": list(kinds.values())}))
+
+    # the same scene seen by a camera (keypoints a homography can be solved from), for the court inset and the collection
+    def collecting_runner(fixed: bool):
+        views = [court_view(0 if fixed else i, w, h, runner.projected_court) for i in range(n)]
+        ts = trackers[:-1] + [Stored("keypoints_tracker", views, kind=Keypoints, fixed_keypoints_detection=views[0] if fixed else None)]
+        with contextlib.redirect_stdout(sys.stderr):                # (the runner says that it is ready: not a line of this tool's JSON)
+            return TrackingRunner(ts, clip, tmp / "out.mp4", render=tmp / "out.y4m", engine=eng, collect_data=True)
+    scenes_timed = [("scene", full), ("no marks", none)]
+    inset_runner = collecting_runner(False)
+    with_inset = [inset_runner.frame_marks(i) for i in range(n)]
+    inset = R.pack(with_inset)
+    refused = E.render_check(n, h, w, inset[0], inset[1])
+    if refused is None:
+        scenes_timed.append(("scene + court inset", inset))
+        print(json.dumps({"what": "scene + court inset", "marks_per_frame": len(with_inset[0]), "of_them_blending": int((inset[0]["kind"] == 6).sum()) // n}))
+    else:
+        print(json.dumps({"what": "scene + court inset", "skipped": "this library refuses it: " + refused}))
 
     # ---- (a) the kernel
     SETS = 3
@@ -114,7 +156,7 @@ if __name__ == "__main__":
         span = video.yuv_span(n, h, w, geom) if yuv else bgr.nbytes
         dst = [eng.alloc(span) for _ in range(SETS)]
         moved = n * h * w * (4.5 if yuv else 6.0)
-        for label, (marks, first) in (("scene", full), ("no marks", none)):
+        for label, (marks, first) in scenes_timed:
             call = lambda i: eng.render(src[i % SETS], n, h, w, marks, first, dst[i % SETS], out=E.RENDER_YUV420 if yuv else E.RENDER_BGR,
                                         geom=geom, enc=enc if yuv else None)
             for i in range(a.warmup):
@@ -141,21 +183,30 @@ if __name__ == "__main__":
     for b in src[1:]:
         b.free()
 
-    # ---- (b) the runner's render step: render + download + write
+    # ---- (b) the runner's render step: render + download + write; then with projection, collection and the inset
     if not a.skip_runner:
-        import contextlib
-        secs = []
-        with contextlib.redirect_stdout(sys.stderr):
-            for k in range(a.passes + 1):                       # one untimed pass first
-                eng.synchronize()
-                t0 = time.perf_counter()
-                runner.draw_and_collect_data()
-                secs.append(time.perf_counter() - t0)
-        secs = secs[1:]
-        med = statistics.median(secs)
-        size = (tmp / "out.y4m").stat().st_size
-        print(json.dumps({"what": "TrackingRunner render step: render + download + write of the .y4m (host clock)", "frames": n, "h": h, "w": w,
-                          "marks_per_frame": len(per_frame[0]), "seconds_median": round(med, 4), "seconds_passes": [round(s, 4) for s in secs],
-                          "frames_per_s": round(n / med, 1), "file_bytes": size, "MB_per_s_written": round(size / med / 1e6, 1)}))
-        (tmp / "out.y4m").unlink()
+        runs = [("render + download + write of the .y4m", runner)]
+        if refused is None:
+            runs += [("the same with collect_data=True, fixed court keypoints", collecting_runner(True)),
+                     ("the same with collect_data=True, court keypoints per frame", collecting_runner(False))]
+        for what, r in runs:
+            secs, collect = [], []
+            with contextlib.redirect_stdout(sys.stderr):
+                for k in range(a.passes + 1):                       # one untimed pass first
+                    eng.synchronize()
+                    t0 = time.perf_counter()
+                    r.draw_and_collect_data()
+                    secs.append(time.perf_counter() - t0)
+                    collect.append(r.timings.get("__collect__", {}).get("seconds"))
+            secs = secs[1:]
+            med = statistics.median(secs)
+            size = (tmp / "out.y4m").stat().st_size
+            marks_per_frame = len(r.frame_marks(0))
+            row = {"what": "TrackingRunner render step: " + what + " (host clock)", "frames": n, "h": h, "w": w,
+                   "marks_per_frame": marks_per_frame, "seconds_median": round(med, 4), "seconds_passes": [round(s, 4) for s in secs],
+                   "frames_per_s": round(n / med, 1), "file_bytes": size, "MB_per_s_written": round(size / med / 1e6, 1)}
+            if collect[-1] is not None:
+                row["collect_seconds_passes"] = [round(c, 4) for c in collect[1:]]
+            print(json.dumps(row))
+            (tmp / "out.y4m").unlink()
     clip.free()
