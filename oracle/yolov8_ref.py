@@ -19,7 +19,6 @@ Nothing in the product package imports this module.
 """
 from __future__ import annotations
 
-import math
 from typing import Optional, Sequence
 
 import numpy as np
@@ -177,12 +176,39 @@ class YoloV8Ref:
 
 # --------------------------------------------------------------------------- preprocessing
 
+def cv2_linear_coeffs(src: int, dst: int):
+    """Source index and the two 11-bit weights of every output of one axis of ``cv2.resize(..., INTER_LINEAR)`` on u8:
+    -> (idx, c0, c1), int64 arrays of length ``dst``.
+
+    SINGLE precision, like OpenCV's generic resize path (modules/imgproc/src/resize.cpp), which declares ``float fx`` and does
+    ``fx = (float)((dx + 0.5) * scale_x - 0.5); sx = cvFloor(fx); fx -= sx; cbuf[0] = 1.f - fx; cbuf[1] = fx;`` and then
+    ``saturate_cast<short>(cbuf[k] * INTER_RESIZE_COEF_SCALE)`` (2048; cvRound: half to even): the product ``(dx + 0.5) * scale``
+    is a double, everything after the cast — the fraction, ``1 - fx``, the scaling — is float32.  This function computed all of
+    it in float64 before; the two differ by one unit of a weight wherever the float32 fraction sits on the other side of a
+    rounding boundary (725 -> 362, output 71: 620 / 1428 in float32, 619 / 1429 in float64), on none of the resizes of a 16:9
+    source to 640 and on a few outputs of most odd pairs.  The decision for single precision rests on reading OpenCV's source:
+    there is no OpenCV on the machines this project is developed and tested on, so it has NOT been checked against a run of
+    ``cv2`` itself.  The engine's table (csrc/graph_plan.cpp:cv2_linear_table) is a separate statement of the same arithmetic in
+    C++; tests/test_letterbox_geometry_host.py compares the two number for number."""
+    scale = src / dst
+    f = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f)
+    f = f - s                                                                    # float32 - float32
+    lo, hi = s < 0, s >= src - 1
+    idx = np.where(lo, 0, np.where(hi, src - 1, s)).astype(np.int64)
+    f = np.where(lo | hi, np.float32(0), f)
+    assert f.dtype == np.float32
+    c0 = np.rint((np.float32(1) - f) * np.float32(2048)).astype(np.int64)        # np.rint: half to even, like cvRound
+    c1 = np.rint(f * np.float32(2048)).astype(np.int64)
+    return idx, c0, c1
+
+
 def cv2_resize_linear_u8(img: np.ndarray, dst_w: int, dst_h: int) -> np.ndarray:
     """Restatement of ``cv2.resize(img, (dst_w, dst_h), interpolation=cv2.INTER_LINEAR)`` on u8.
 
     * exact 2x2 decimation takes OpenCV's area-fast path: ``(a+b+c+d+2)>>2``;
-    * otherwise 11-bit fixed-point separable bilinear (INTER_RESIZE_COEF_BITS = 11):
-      horizontal pass in int32, vertical pass
+    * otherwise 11-bit fixed-point separable bilinear (INTER_RESIZE_COEF_BITS = 11), weights from ``cv2_linear_coeffs``
+      (single precision, see there): horizontal pass in int32, vertical pass
       ``(((b0*(S0>>4))>>16) + ((b1*(S1>>4))>>16) + 2) >> 2``.
     """
     sh, sw = img.shape[:2]
@@ -193,27 +219,8 @@ def cv2_resize_linear_u8(img: np.ndarray, dst_w: int, dst_h: int) -> np.ndarray:
         s = a[0::2, 0::2] + a[0::2, 1::2] + a[1::2, 0::2] + a[1::2, 1::2] + 2
         return (s >> 2).astype(np.uint8)
 
-    def coeffs(src, dst):
-        scale = src / dst
-        idx = np.empty(dst, np.int64)
-        c0 = np.empty(dst, np.int64)
-        c1 = np.empty(dst, np.int64)
-        for d in range(dst):
-            f = (d + 0.5) * scale - 0.5
-            s = int(math.floor(f))
-            f -= s
-            if s < 0:
-                s, f = 0, 0.0
-            if s >= src - 1:
-                s, f = src - 1, 0.0
-            idx[d] = s
-            # saturate_cast<short>(x * 2048) with round-half-to-even (cvRound)
-            c0[d] = int(np.rint((1.0 - f) * 2048.0))
-            c1[d] = int(np.rint(f * 2048.0))
-        return idx, c0, c1
-
-    xi, xa0, xa1 = coeffs(sw, dst_w)
-    yi, yb0, yb1 = coeffs(sh, dst_h)
+    xi, xa0, xa1 = cv2_linear_coeffs(sw, dst_w)
+    yi, yb0, yb1 = cv2_linear_coeffs(sh, dst_h)
     a = img.astype(np.int64)
     x1 = np.minimum(xi + 1, sw - 1)
     rows = a[:, xi] * xa0[None, :, None] + a[:, x1] * xa1[None, :, None]          # (sh, dw, C)

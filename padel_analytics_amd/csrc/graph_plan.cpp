@@ -315,7 +315,13 @@ int yolo_geometry(int h0, int w0, int imgsz, int pre_mode, int letterbox_auto, Y
 }
 
 // ---- host-side coefficient tables --------------------------------------------------------------
-// cv2.resize INTER_LINEAR u8 (see oracle/yolov8_ref.py:cv2_resize_linear_u8)
+// cv2.resize INTER_LINEAR u8: source index and the two 11-bit weights per output (oracle/yolov8_ref.py:cv2_linear_coeffs is the
+// numpy statement of the same arithmetic; tests/test_letterbox_geometry_host.py compares them number for number).
+// The fraction is SINGLE precision on purpose: OpenCV's generic resize path declares `float fx` and does
+// `fx = (float)((dx + 0.5) * scale_x - 0.5); sx = cvFloor(fx); fx -= sx; cbuf[0] = 1.f - fx; cbuf[1] = fx;`, then
+// `saturate_cast<short>(cbuf[k] * 2048)` (half to even).  Double precision here gives another weight, by one unit, on a few outputs
+// of most odd size pairs (725 -> 362, output 71: 620 / 1428 in float, 619 / 1429 in double) and on none of a 16:9 source to 640.
+// This rests on reading OpenCV's source; it has not been checked against a run of cv2 (none is installed where this is tested).
 void cv2_linear_table(int src, int dst, std::vector<int32_t>& tab) {
     tab.resize((size_t)dst * 3);
     const double scale = (double)src / dst;

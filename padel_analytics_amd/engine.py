@@ -691,9 +691,9 @@ class Model:
         self.engine._check(self.engine.lib.pa_yolo_wait(self.handle, t, C.byref(ovf)))
         return boxes, kpts, counts, bool(ovf.value)
 
-    def head_shapes(self, h: int, w: int, imgsz: int, pre_mode: int = PRE_LETTERBOX) -> list:
+    def head_shapes(self, h: int, w: int, imgsz: int, pre_mode: int = PRE_LETTERBOX, letterbox_auto: bool = True) -> list:
         """[(H_l, W_l, c)] of the three head maps for source size h x w (host arithmetic of the planner)."""
-        if pre_mode == PRE_PIL_STRETCH:
+        if pre_mode == PRE_PIL_STRETCH or not letterbox_auto:
             nh = nw = imgsz
         else:
             r = min(imgsz / h, imgsz / w)
