@@ -511,6 +511,24 @@ def _round_up(x: int, a: int) -> int:
     return (int(x) + a - 1) // a * a
 
 
+def _frames_arg(frames, n: Optional[int], h: int, w: int):
+    """frames: (n, h, w, 3) uint8 ndarray (``n`` None: as many as it holds), or a DeviceBuffer holding ``n`` such frames
+    -> (what the pointer points into, pointer, n, on_device); the caller holds on to the first over the native call."""
+    if isinstance(frames, DeviceBuffer):
+        assert n is not None and frames.nbytes >= n * h * w * 3
+        return frames, frames.ptr, n, True
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n = len(frames) if n is None else n
+    assert frames.shape == (n, h, w, 3), frames.shape
+    return frames, frames.ctypes.data, n, False
+
+
+def _yolo_params(classes: Optional[Sequence[int]], **fields):
+    """-> (pa_yolo_params, the ctypes array its ``classes`` points to | None); the caller holds on to both over the native call."""
+    cls_arr = (C.c_int32 * len(classes))(*[int(c) for c in classes]) if classes is not None and len(classes) else None
+    return pa_yolo_params(n_classes=0 if cls_arr is None else len(cls_arr), classes=cls_arr, **fields), cls_arr
+
+
 class _PinnedBlock:
     """Whole pages of host memory, page-locked for one engine (hipHostRegister locks pages: small arrays that share a page
     cannot be registered / unregistered independently).  Unregistered by ``release()`` or when the object dies — always
@@ -563,7 +581,7 @@ class Model:
                 setattr(ops[i], k, int(v))
         d = pa_model_desc(task=graph.task, nc=graph.nc, nk=graph.nk, kpt_dim=graph.kpt_dim, n_bufs=len(graph.bufs),
                           bufs=bufs, n_ops=len(graph.ops), ops=ops, in_channels=graph.in_channels,
-                          dtype=getattr(graph, "dtype", 0))
+                          dtype=graph.dtype)
         for i in range(3):
             d.head_buf[i] = graph.head_buf[i] if i < len(graph.head_buf) else -1
         h = C.c_void_p()
@@ -600,6 +618,11 @@ class Model:
         ring[1] = (i + 1) % self.OUT_RING
         return sets[i][:3]
 
+    def _fresh_outputs(self, n: int, max_det: int):
+        nk = self.graph.nk
+        return (np.zeros((n, max_det, 6), np.float32), np.zeros((n, max_det, nk), np.float32) if nk else None,
+                np.zeros((n,), np.int32))
+
     def _free_rings(self):
         for sets, _ in self._out_ring.values():
             for arrs in sets:
@@ -634,29 +657,11 @@ class Model:
         ``reuse_outputs=True`` (the trackers' batch loops): the arrays are one of ``OUT_RING`` page-locked sets this model
         keeps per (n, max_det) — the device copies its results straight into them (no staging copy, no 3.5 MB of fresh
         zeros per pose batch) — and are overwritten by the ``OUT_RING``-th next such call; copy what must live longer."""
-        on_dev = isinstance(frames, DeviceBuffer)
-        if on_dev:
-            ptr = frames.ptr
-            assert frames.nbytes >= n * h * w * 3
-        else:
-            frames = np.ascontiguousarray(frames, np.uint8)
-            assert frames.shape == (n, h, w, 3), frames.shape
-            ptr = frames.ctypes.data
-        cls_arr = None
-        p = pa_yolo_params(imgsz=imgsz, pre_mode=pre_mode, channel_reverse=int(channel_reverse),
-                           letterbox_auto=int(letterbox_auto), conf=conf, iou=iou, max_det=max_det,
-                           n_classes=0, classes=None, frames_on_device=int(on_dev))
-        if classes is not None and len(classes):
-            cls_arr = (C.c_int32 * len(classes))(*[int(c) for c in classes])
-            p.n_classes = len(classes)
-            p.classes = cls_arr
-        if reuse_outputs:
-            boxes, kpts, counts = self._ring_outputs(n, max_det)
-        else:
-            boxes = np.zeros((n, max_det, 6), np.float32)
-            counts = np.zeros((n,), np.int32)
-            nk = self.graph.nk
-            kpts = np.zeros((n, max_det, nk), np.float32) if nk else None
+        frames, ptr, n, on_dev = _frames_arg(frames, n, h, w)
+        p, cls_arr = _yolo_params(classes, imgsz=imgsz, pre_mode=pre_mode, channel_reverse=int(channel_reverse),
+                                  letterbox_auto=int(letterbox_auto), conf=conf, iou=iou, max_det=max_det,
+                                  frames_on_device=int(on_dev))
+        boxes, kpts, counts = self._ring_outputs(n, max_det) if reuse_outputs else self._fresh_outputs(n, max_det)
         self.engine._check(self.engine.lib.pa_yolo_infer(
             self.handle, ptr, n, h, w, C.byref(p), boxes.ctypes.data,
             kpts.ctypes.data if kpts is not None else None, counts.ctypes.data))
@@ -670,14 +675,8 @@ class Model:
         HBM; the results land in one of the model's recycled page-locked sets (``reuse_outputs`` rules).  Submit batch k + 1
         before waiting for batch k and the GPU never waits for the host between batches."""
         assert isinstance(frames, DeviceBuffer) and frames.nbytes >= n * h * w * 3
-        cls_arr = None
-        p = pa_yolo_params(imgsz=imgsz, pre_mode=pre_mode, channel_reverse=int(channel_reverse),
-                           letterbox_auto=int(letterbox_auto), conf=conf, iou=iou, max_det=max_det,
-                           n_classes=0, classes=None, frames_on_device=1)
-        if classes is not None and len(classes):
-            cls_arr = (C.c_int32 * len(classes))(*[int(c) for c in classes])
-            p.n_classes = len(classes)
-            p.classes = cls_arr
+        p, cls_arr = _yolo_params(classes, imgsz=imgsz, pre_mode=pre_mode, channel_reverse=int(channel_reverse),
+                                  letterbox_auto=int(letterbox_auto), conf=conf, iou=iou, max_det=max_det, frames_on_device=1)
         boxes, kpts, counts = self._ring_outputs(n, max_det)
         t = C.c_int(-1)
         self.engine._check(self.engine.lib.pa_yolo_submit(
@@ -709,18 +708,10 @@ class Model:
         heads = [np.ascontiguousarray(x, np.float32) for x in heads]
         n = heads[0].shape[0]
         assert [x.shape[1:] for x in heads] == [tuple(s) for s in self.head_shapes(h, w, imgsz, pre_mode)], [x.shape for x in heads]
-        p = pa_yolo_params(imgsz=imgsz, pre_mode=pre_mode, channel_reverse=0, letterbox_auto=1, conf=conf, iou=iou,
-                           max_det=max_det, n_classes=0, classes=None, frames_on_device=0)
-        cls_arr = None
-        if classes is not None and len(classes):
-            cls_arr = (C.c_int32 * len(classes))(*[int(c) for c in classes])
-            p.n_classes = len(classes)
-            p.classes = cls_arr
+        p, cls_arr = _yolo_params(classes, imgsz=imgsz, pre_mode=pre_mode, channel_reverse=0, letterbox_auto=1, conf=conf, iou=iou,
+                                  max_det=max_det, frames_on_device=0)
         ptrs = (C.c_void_p * 3)(*[x.ctypes.data for x in heads])
-        boxes = np.zeros((n, max_det, 6), np.float32)
-        counts = np.zeros((n,), np.int32)
-        nk = self.graph.nk
-        kpts = np.zeros((n, max_det, nk), np.float32) if nk else None
+        boxes, kpts, counts = self._fresh_outputs(n, max_det)
         self.engine._check(self.engine.lib.pa_yolo_postprocess(self.handle, ptrs, n, h, w, C.byref(p), boxes.ctypes.data,
                                                                kpts.ctypes.data if kpts is not None else None, counts.ctypes.data))
         return boxes, kpts, counts
@@ -758,7 +749,7 @@ class Model:
 
     def tracknet_infer(self, x: np.ndarray) -> np.ndarray:
         """x: (n, H, W, C_in) NHWC (fp32; fp16 for a graph with dtype f16) -> (n, H, W, C_out) fp32."""
-        x = np.ascontiguousarray(x, np.float16 if getattr(self.graph, "dtype", 0) == G.DTYPE_F16 else np.float32)
+        x = np.ascontiguousarray(x, np.float16 if self.graph.dtype == G.DTYPE_F16 else np.float32)
         n, h, w, c = x.shape
         assert c == self.graph.bufs[0][1], (c, self.graph.bufs[0])
         lvl, cout = self.graph.bufs[self.graph.head_buf[0]]
@@ -771,14 +762,7 @@ class Model:
         """frames: (n, h, w, 3) uint8 BGR ndarray, or a DeviceBuffer holding the same bytes -> (xy (n, c) fp32 sigmoid outputs,
         logits (n, c) | None); c = outputs of the graph's pooled linear head (24).  A graph without one (unit tests) gives
         (None, None): read its head buffer with ``resnet_read_head``."""
-        on_dev = isinstance(frames, DeviceBuffer)
-        if on_dev:
-            ptr = frames.ptr
-            assert frames.nbytes >= n * h * w * 3
-        else:
-            frames = np.ascontiguousarray(frames, np.uint8)
-            assert frames.shape == (n, h, w, 3), frames.shape
-            ptr = frames.ctypes.data
+        frames, ptr, n, on_dev = _frames_arg(frames, n, h, w)
         c = next((o["cout"] for o in self.graph.ops if o["kind"] == G.OP_GAP_FC), 0)
         xy = np.zeros((n, c), np.float32) if c else None
         logits = np.zeros((n, c), np.float32) if (c and want_logits) else None
@@ -924,14 +908,7 @@ class BallSession:
         """Median background of (n, h, w, 3) uint8 BGR frames on the device (np.median + uint8 truncation).
         ``frames_bgr``: ndarray, or a DeviceBuffer holding ``n`` frames."""
         on_dev = isinstance(frames_bgr, DeviceBuffer)
-        if on_dev:
-            ptr = frames_bgr.ptr
-            assert n is not None and frames_bgr.nbytes >= n * self.src_h * self.src_w * 3
-        else:
-            f = np.ascontiguousarray(frames_bgr, np.uint8)
-            n = len(f)
-            assert f.shape == (n, self.src_h, self.src_w, 3)
-            ptr = f.ctypes.data
+        frames_bgr, ptr, n, _ = _frames_arg(frames_bgr, n if on_dev else None, self.src_h, self.src_w)
         med = np.empty((self.src_h, self.src_w, 3), np.uint8) if want_median else None
         self.model.engine._check(self.model.engine.lib.pa_ball_background_from_frames(
             self.handle, ptr, n, int(on_dev), med.ctypes.data if want_median else None))
@@ -944,15 +921,11 @@ class BallSession:
         outputs for the next k frames in order; rects = predict_location of each mask computed on the device."""
         on_dev = isinstance(frames_bgr, DeviceBuffer)
         ptr = None
-        if on_dev:
-            assert n is not None and 0 < n <= self.max_feed and frames_bgr.nbytes >= n * self.src_h * self.src_w * 3
-            ptr = frames_bgr.ptr
-        else:
+        if not on_dev:
             n = 0 if frames_bgr is None else len(frames_bgr)
-            if n:
-                frames_bgr = np.ascontiguousarray(frames_bgr, np.uint8)
-                assert frames_bgr.shape == (n, self.src_h, self.src_w, 3) and n <= self.max_feed
-                ptr = frames_bgr.ctypes.data
+        if on_dev or n:
+            frames_bgr, ptr, n, _ = _frames_arg(frames_bgr, n, self.src_h, self.src_w)
+            assert 0 < n <= self.max_feed
         masks = np.empty((n + 7, self.H, self.W), np.uint8) if (want_masks or not want_rects) else None
         heat = np.empty((n + 7, self.H, self.W), np.float32) if want_heat else None
         rects = np.empty((n + 7, 4), np.int32) if want_rects else None

@@ -31,6 +31,9 @@ OP_DWCONV3, OP_PSA_ATTN = 9, 10                         # YOLO11: depthwise 3x3,
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_SIGMOID, ACT_LEAKY = 0, 1, 2, 3, 4
 TASK_DETECT, TASK_POSE, TASK_TRACKNET, TASK_RESNET = 0, 1, 2, 3
 DTYPE_F32, DTYPE_F16, DTYPE_H2 = 0, 1, 2
+# the fields of pa_op_desc: every op of a Graph carries all of them
+OP_FIELDS = ("kind", "in_buf", "in_choff", "cin", "out_buf", "out_choff", "cout", "ksize", "stride", "act", "res_buf", "res_choff",
+             "npad", "reserved", "w_off", "b_off", "flags")
 
 
 def pad16(c: int) -> int:
@@ -199,17 +202,24 @@ def h2_weights_single(planes: np.ndarray) -> bool:
     return not bool((planes[:, :, 1, :] & 0x7FFF).any())
 
 
-def fold_bn_split(sd, prefix: str, eps: float):
-    """The pieces of ``fold_bn`` kept apart: (raw conv weight, per-channel BatchNorm scale, folded bias) — the same fp32
-    operations in the same order for scale and bias; ``fold_bn``'s weight is ``raw * scale`` rounded to fp32."""
-    w = np.asarray(sd[f"{prefix}.conv.weight"], np.float32)
-    g = np.asarray(sd[f"{prefix}.bn.weight"], np.float32)
-    beta = np.asarray(sd[f"{prefix}.bn.bias"], np.float32)
-    mu = np.asarray(sd[f"{prefix}.bn.running_mean"], np.float32)
-    var = np.asarray(sd[f"{prefix}.bn.running_var"], np.float32)
+def _bn_split(sd, wkey: str, bn: str, eps: float, perm=None):
+    """(raw conv weight ``sd[wkey]``, per-channel scale, bias) of the conv behind the BatchNorm ``sd[bn + ".*"]``, all fp32, same
+    operation order as ultralytics' fuse_conv_and_bn; ``perm``: output-channel order (rows of the weight and of BatchNorm)."""
+    load = lambda k: np.asarray(sd[k], np.float32) if perm is None else np.asarray(sd[k], np.float32)[perm]
+    w, g, beta, mu, var = (load(k) for k in (wkey, f"{bn}.weight", f"{bn}.bias", f"{bn}.running_mean", f"{bn}.running_var"))
     scale = (g / np.sqrt(np.float32(eps) + var)).astype(np.float32)
     bf = (beta - (g * mu) / np.sqrt(var + np.float32(eps))).astype(np.float32)
     return w, scale, bf
+
+
+def _scale_rows(w: np.ndarray, scale: np.ndarray) -> np.ndarray:
+    return (w.reshape(w.shape[0], -1) * scale[:, None]).reshape(w.shape).astype(np.float32)
+
+
+def fold_bn_split(sd, prefix: str, eps: float):
+    """The pieces of ``fold_bn`` kept apart: (raw conv weight, per-channel BatchNorm scale, folded bias); ``fold_bn``'s weight
+    is ``raw * scale`` rounded to fp32."""
+    return _bn_split(sd, f"{prefix}.conv.weight", f"{prefix}.bn", eps)
 
 
 def fp16_exact(w: np.ndarray) -> bool:
@@ -219,15 +229,8 @@ def fp16_exact(w: np.ndarray) -> bool:
 
 def fold_bn(sd, prefix: str, eps: float):
     """Conv+BN fold in fp32, same operation order as ultralytics' fuse_conv_and_bn."""
-    w = np.asarray(sd[f"{prefix}.conv.weight"], np.float32)
-    g = np.asarray(sd[f"{prefix}.bn.weight"], np.float32)
-    beta = np.asarray(sd[f"{prefix}.bn.bias"], np.float32)
-    mu = np.asarray(sd[f"{prefix}.bn.running_mean"], np.float32)
-    var = np.asarray(sd[f"{prefix}.bn.running_var"], np.float32)
-    scale = g / np.sqrt(np.float32(eps) + var)
-    wf = (w.reshape(w.shape[0], -1) * scale[:, None]).reshape(w.shape).astype(np.float32)
-    bf = (beta - (g * mu) / np.sqrt(var + np.float32(eps))).astype(np.float32)
-    return wf, bf
+    w, scale, bf = fold_bn_split(sd, prefix, eps)
+    return _scale_rows(w, scale), bf
 
 
 @dataclass
@@ -268,6 +271,16 @@ class Graph:
             self.chunks.append(np.zeros(padn, np.float32))
         self.n_floats += arr.size + padn
         return off
+
+    def _op(self, kind, src, dst, res=None, **fields):
+        """Append one op reading ``src = (buf, choff, channels)`` and writing ``dst = (buf, choff)``, with ``res = (buf, choff)``
+        as its residual slice.  ``cout`` is the channels read unless given; every other field of pa_op_desc is 0 unless given."""
+        assert set(fields) <= set(OP_FIELDS), fields
+        op = dict.fromkeys(OP_FIELDS, 0)
+        op.update(kind=kind, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=dst[0], out_choff=dst[1], cout=src[2],
+                  res_buf=-1 if res is None else res[0], res_choff=0 if res is None else res[1])
+        op.update(fields)
+        self.ops.append(op)
 
     def conv(self, src, dst, w, b, k, s, act, res=None, out_width=None, out_scale=None, res_preact=False):
         """src = (buf, choff, width read), dst = (buf, choff).  ``w`` is (cout, cin, k, k) with the
@@ -315,10 +328,36 @@ class Graph:
         if res_preact:
             assert res is not None and self.dtype != DTYPE_F16, "res_preact: a residual, h2 / fp32 graphs only"
             flags |= FLAG_RES_PREACT
-        self.ops.append(dict(kind=OP_CONV, in_buf=sb, in_choff=so, cin=sw, out_buf=dst[0], out_choff=dst[1],
-                             cout=ow, ksize=k, stride=s, act=act, res_buf=-1 if res is None else res[0],
-                             res_choff=0 if res is None else res[1], npad=npad, w_off=w_off, b_off=b_off, reserved=w3_off,
-                             flags=flags))
+        self._op(OP_CONV, (sb, so, sw), dst, res, cout=ow, ksize=k, stride=s, act=act, npad=npad, w_off=w_off, b_off=b_off,
+                 reserved=w3_off, flags=flags)
+
+    # ---- the ops of the YOLO and TrackNet graphs that are not Graph.conv
+    def stem(self, w, b, dst, out_width=None):
+        """Conv 3x3 stride 2 pad 1, 3 -> cout (``w`` (cout, 3, 3, 3), BatchNorm folded) + bias + SiLU from the u8 network input
+        into ``dst = (buf, choff)`` at level 1.  The blob gets the weights as [out_width][27] ((ky, kx, colour) order) and the bias;
+        the rows up to ``out_width`` are zero, so those channels hold SiLU(0) = 0."""
+        w = np.asarray(w, np.float32)
+        cout = w.shape[0]
+        ow = cout if out_width is None else out_width
+        wp = np.zeros((ow, 27), np.float32)
+        wp[:cout] = np.ascontiguousarray(w.transpose(0, 2, 3, 1)).reshape(cout, 27)
+        bp = np.zeros(ow, np.float32)
+        bp[:cout] = b
+        w_off, b_off = self._add(wp), self._add(bp)
+        self._op(OP_STEM, (0, 0, 3), dst, cout=ow, ksize=3, stride=2, act=ACT_SILU, npad=ow, w_off=w_off, b_off=b_off)
+
+    def upsample2x(self, src, dst):
+        """Nearest-neighbour x2 of ``src = (buf, choff, channels)`` into ``dst = (buf, choff)`` one level finer."""
+        self._op(OP_UPSAMPLE2X, src, dst)
+
+    def maxpool2(self, src, dst):
+        """MaxPool2d(2, 2) of ``src = (buf, choff, channels)`` into ``dst = (buf, choff)`` one level coarser."""
+        self._op(OP_MAXPOOL2, src, dst, ksize=2, stride=2)
+
+    def sppf_pool(self, buf, ch, choff=0):
+        """SPPF's three chained MaxPool2d(5, 1, 2): reads channels [0, ch) of ``buf`` and writes [ch, 4 * ch) of the same buffer
+        (both counted from ``choff``)."""
+        self._op(OP_SPPF_POOL, (buf, choff, ch), (buf, choff + ch), cout=3 * ch, ksize=5, stride=1)
 
     # ---- the three ops of the ResNet-50 graph (csrc/resnet_ops.hip)
     def stem7(self, w, b, dst, act=ACT_RELU):
@@ -330,13 +369,11 @@ class Graph:
         wp = np.zeros((148, 64), np.float32)
         wp[:147] = np.ascontiguousarray(w.transpose(2, 3, 1, 0)).reshape(147, 64)
         w_off, b_off, lut_off = self._add(wp), self._add(np.asarray(b, np.float32)), self._add(resnet_norm_table())
-        self.ops.append(dict(kind=OP_STEM7, in_buf=0, in_choff=0, cin=3, out_buf=dst[0], out_choff=dst[1], cout=64, ksize=7, stride=2,
-                             act=act, res_buf=-1, res_choff=0, npad=64, w_off=w_off, b_off=b_off, reserved=lut_off))
+        self._op(OP_STEM7, (0, 0, 3), dst, cout=64, ksize=7, stride=2, act=act, npad=64, w_off=w_off, b_off=b_off, reserved=lut_off)
 
     def maxpool3s2(self, src, dst):
         """MaxPool2d(3, 2, 1) of ``src = (buf, choff, channels)`` into ``dst = (buf, choff)`` one level coarser."""
-        self.ops.append(dict(kind=OP_MAXPOOL3S2, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=dst[0], out_choff=dst[1], cout=src[2],
-                             ksize=3, stride=2, act=0, res_buf=-1, res_choff=0, npad=0, w_off=0, b_off=0))
+        self._op(OP_MAXPOOL3S2, src, dst, ksize=3, stride=2)
 
     def gap_fc(self, src, w, b):
         """Mean over the map of ``src = (buf, choff, channels)``, linear layer ``w`` (nout, channels) + ``b``, sigmoid; the results
@@ -344,8 +381,7 @@ class Graph:
         w = np.asarray(w, np.float32)
         assert w.shape[1] == src[2] and len(b) == w.shape[0], (w.shape, src)
         w_off, b_off = self._add(w), self._add(np.asarray(b, np.float32))
-        self.ops.append(dict(kind=OP_GAP_FC, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=src[0], out_choff=0, cout=w.shape[0],
-                             ksize=0, stride=0, act=ACT_SIGMOID, res_buf=-1, res_choff=0, npad=0, w_off=w_off, b_off=b_off))
+        self._op(OP_GAP_FC, src, (src[0], 0), cout=w.shape[0], act=ACT_SIGMOID, w_off=w_off, b_off=b_off)
 
     # ---- the two ops YOLO11 adds (csrc/yolo11_ops.hip)
     def dwconv3(self, src, dst, w, b, act, res=None):
@@ -353,7 +389,7 @@ class Graph:
         (c, 1, 3, 3) with BatchNorm folded and c <= width: the channels up to ``width`` get zero weights and a zero bias (they read
         the zeros a padded producer wrote there and write act(0) = 0).  The blob gets the weights as [9][width] (tap ky * 3 + kx).
         ``res = (buf, choff)``: a slice added after the activation."""
-        sb, so, sw = src
+        sw = src[2]
         w = np.asarray(w, np.float32)
         c = w.shape[0]
         assert w.shape == (c, 1, 3, 3) and c <= sw and sw % 4 == 0 and act in (ACT_NONE, ACT_SILU), (w.shape, sw, act)
@@ -363,16 +399,13 @@ class Graph:
         bp = np.zeros(sw, np.float32)
         bp[:c] = b
         w_off, b_off = self._add(wp), self._add(bp)
-        self.ops.append(dict(kind=OP_DWCONV3, in_buf=sb, in_choff=so, cin=sw, out_buf=dst[0], out_choff=dst[1], cout=sw, ksize=3, stride=1,
-                             act=act, res_buf=-1 if res is None else res[0], res_choff=0 if res is None else res[1], npad=sw,
-                             w_off=w_off, b_off=b_off))
+        self._op(OP_DWCONV3, src, dst, res, ksize=3, stride=1, act=act, npad=sw, w_off=w_off, b_off=b_off)
 
     def psa_attn(self, src, dst, heads: int, kd: int = yolo_arch.PSA_KEY_DIM, hd: int = yolo_arch.PSA_HEAD_DIM):
         """C2PSA's attention: ``src = (buf, choff)`` holds [q of all heads | k of all heads | v of all heads] (heads * (2 kd + hd)
         channels), ``dst = (buf, choff)`` receives heads * hd channels: softmax over the keys of (q^T k) * kd^-1/2, applied to v."""
         assert self.dtype != DTYPE_F16, "PSA attention: fp32 and h2 graphs only"
-        self.ops.append(dict(kind=OP_PSA_ATTN, in_buf=src[0], in_choff=src[1], cin=heads * (2 * kd + hd), out_buf=dst[0], out_choff=dst[1],
-                             cout=heads * hd, ksize=kd, stride=heads, act=ACT_NONE, res_buf=-1, res_choff=0, npad=hd, w_off=0, b_off=0))
+        self._op(OP_PSA_ATTN, (src[0], src[1], heads * (2 * kd + hd)), dst, cout=heads * hd, ksize=kd, stride=heads, npad=hd)
 
     def blob(self) -> np.ndarray:
         return np.concatenate(self.chunks) if self.chunks else np.zeros(0, np.float32)
@@ -399,6 +432,63 @@ UNFOLDED_BN: bool = os.environ.get("PADEL_UNFOLDED_BN", "1") != "0"
 HEAD_SPLIT: Optional[bool] = {"0": False, "1": True}.get(os.environ.get("PADEL_HEAD_SPLIT", ""))
 
 
+def bn_parts(g: Graph, sd, wkey: str, bn: str, eps: float, perm=None):
+    """-> (weights to pack, bias, out_scale | None) for ``Graph.conv``: the conv ``sd[wkey]`` behind the BatchNorm ``sd[bn + ".*"]``,
+    rows in the order ``perm`` if given.
+
+    h2 graphs: a checkpoint whose conv weights are fp16 numbers (Ultralytics stores ``model.half()``) keeps them that way —
+    BatchNorm's scale goes into the conv's per-channel output scale instead of into the weights, the correction plane of
+    the packed weights is zero and the kernels run two products per operand pair instead of three (PA_CONV_W_SINGLE).
+    sum(w a) * scale + shift instead of sum(fl32(w * scale) a) + shift: the same value to fp32 rounding (the head maps move
+    by 0.12-0.18 x the fp32 oracle's own distance from its fp64 evaluation: DESIGN.md 3.5).  Any other weights, any other
+    storage type: folded."""
+    w, scale, b = _bn_split(sd, wkey, bn, eps, perm)
+    if g.dtype == DTYPE_H2 and UNFOLDED_BN and fp16_exact(w):
+        return w, b, scale
+    return _scale_rows(w, scale), b, None
+
+
+def _yolo_parts(g: Graph, sd, prefix: str, perm=None):
+    """``bn_parts`` of an Ultralytics ``Conv`` module (``prefix.conv`` + ``prefix.bn``, eps 1e-3)."""
+    return bn_parts(g, sd, f"{prefix}.conv.weight", f"{prefix}.bn", yolo_arch.BN_EPS, perm)
+
+
+def _conv2d(g: Graph, sd, name: str, src, dst, act=ACT_NONE):
+    """A 1x1 nn.Conv2d with its own bias and no BatchNorm (the last conv of a head branch, TrackNet's predictor)."""
+    g.conv(src, dst, np.asarray(sd[f"{name}.weight"], np.float32), np.asarray(sd[f"{name}.bias"], np.float32), 1, 1, act)
+
+
+def _yolo_graph(info: dict, d, nc: int, kpt_shape: Optional[tuple], dtype: str):
+    """What both YOLO builders start from -> (empty Graph, (box, class, keypoint) hidden widths of the head, nk)."""
+    assert info["nc"] == nc, (info, nc)
+    c2h, c3h, c4h, nk = yolo_arch.head_dims(d, nc, kpt_shape)
+    assert nk == info["nk"], (nk, info)
+    g = Graph(task=TASK_POSE if kpt_shape else TASK_DETECT, nc=nc, nk=nk, kpt_dim=int(kpt_shape[1]) if kpt_shape else 0,
+              dtype={"f32": DTYPE_F32, "f16": DTYPE_F16, "h2": DTYPE_H2}[dtype])
+    return g, (c2h, c3h, c4h), nk
+
+
+def _yolo_stem(g: Graph, sd, c1: int):
+    """model.0 straight from the u8 network input, written at k-step width (zero rows -> SiLU(0) = 0 in the pad channels)
+    -> the slice (buf, 0, width) the next conv reads."""
+    c1p = g.padk(c1)
+    b0 = g.buf(1, c1p)
+    g.stem(*fold_bn(sd, "model.0", yolo_arch.BN_EPS), (b0, 0), out_width=c1p)
+    return b0, 0, c1p
+
+
+def _yolo_sppf(g: Graph, cbs, src, c5: int, dst=None):
+    """model.9 = SPPF: cv1 into the first quarter of its concat buffer, the pool op, cv2 into ``dst`` (None: a buffer of its own,
+    made after the concat buffer) -> dst."""
+    ch = c5 // 2
+    cat = g.buf(5, 4 * ch)
+    cbs("model.9.cv1", src, (cat, 0), 1, 1)
+    g.sppf_pool(cat, ch)
+    dst = (g.buf(5, c5), 0) if dst is None else dst
+    cbs("model.9.cv2", (cat, 0, 4 * ch), dst, 1, 1)
+    return dst
+
+
 def build_yolov8(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f32") -> Graph:
     """YOLOv8 detect / pose graph (SURVEY.md Appendix A layer table) over the engine's op set.
 
@@ -407,32 +497,10 @@ def build_yolov8(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
     fp16 once — what ``model.half()`` after ``fuse()`` does upstream."""
     info = yolo_arch.infer_arch_from_state_dict(sd)
     d = yolo_arch.arch_dims(info["scale"])
-    assert info["nc"] == nc, (info, nc)
-    c2h, c3h, c4h, nk = yolo_arch.head_dims(d, nc, kpt_shape)
-    assert nk == info["nk"], (nk, info)
-    g = Graph(task=TASK_POSE if kpt_shape else TASK_DETECT, nc=nc, nk=nk, kpt_dim=int(kpt_shape[1]) if kpt_shape else 0,
-              dtype={"f32": DTYPE_F32, "f16": DTYPE_F16, "h2": DTYPE_H2}[dtype])
-    eps = yolo_arch.BN_EPS
-    fuse = lambda p: fold_bn(sd, p, eps)
-
-    # h2 graphs: a checkpoint whose conv weights are fp16 numbers (Ultralytics stores `model.half()`) keeps them that way —
-    # BatchNorm's scale goes into the conv's per-channel output scale instead of into the weights, the correction plane of
-    # the packed weights is zero and the kernels run two products per operand pair instead of three (PA_CONV_W_SINGLE).
-    # sum(w a) * scale + shift instead of sum(fl32(w * scale) a) + shift: the same value to fp32 rounding (the head maps move
-    # by 0.12-0.18 x the fp32 oracle's own distance from its fp64 evaluation: DESIGN.md 3.5).  Any other weights: folded as before.
-    split_bn = g.dtype == DTYPE_H2 and UNFOLDED_BN
-
-    def parts(prefix):
-        """-> (weights to pack, bias, out_scale | None)"""
-        if split_bn:
-            w, sc, b = fold_bn_split(sd, prefix, eps)
-            if fp16_exact(w):
-                return w, b, sc
-        w, b = fuse(prefix)
-        return w, b, None
+    g, (c2h, c3h, c4h), nk = _yolo_graph(info, d, nc, kpt_shape, dtype)
 
     def cbs(prefix, src, dst, k, s, res=None, out_width=None):
-        w, b, sc = parts(prefix)
+        w, b, sc = _yolo_parts(g, sd, prefix)
         g.conv(src, dst, w, b, k, s, ACT_SILU, res, out_width, out_scale=sc)
 
     def nblocks(i):
@@ -456,20 +524,9 @@ def build_yolov8(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
         cbs(f"model.{i}.cv2", (cat, 0, (2 + n) * c), dst, 1, 1)
 
     c1, c2, c3, c4, c5 = d.c1, d.c2, d.c3, d.c4, d.c5
-    # stem: straight from the u8 network input
-    c1p = g.padk(c1)               # stem output at k-step width: zero rows -> SiLU(0) = 0 in the pad channels
-    b0 = g.buf(1, c1p)
-    w0, bias0 = fuse("model.0")
-    w0p = np.zeros((c1p, 27), np.float32)
-    w0p[:c1] = np.ascontiguousarray(w0.transpose(0, 2, 3, 1)).reshape(c1, 27)          # [cout][ky][kx][c]
-    b0p = np.zeros(c1p, np.float32)
-    b0p[:c1] = bias0
-    w_off = g._add(w0p)
-    b_off = g._add(b0p)
-    g.ops.append(dict(kind=OP_STEM, in_buf=0, in_choff=0, cin=3, out_buf=b0, out_choff=0, cout=c1p, ksize=3, stride=2,
-                      act=ACT_SILU, res_buf=-1, res_choff=0, npad=c1p, w_off=w_off, b_off=b_off))
+    x0 = _yolo_stem(g, sd, c1)
     b1 = g.buf(2, c2)
-    cbs("model.1", (b0, 0, c1p), (b1, 0), 3, 2)
+    cbs("model.1", x0, (b1, 0), 3, 2)
     b2 = g.buf(2, c2)
     c2f(2, (b1, 0, c2), c2, True, 2, (b2, 0))
     b3 = g.buf(3, c3)
@@ -485,22 +542,11 @@ def build_yolov8(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
     b8 = g.buf(5, c5)
     c2f(8, (b7, 0, c5), c5, True, 5, (b8, 0))
     cat20 = g.buf(5, c4 + c5)      # [model.19 | model.9]
-    ch = c5 // 2
-    cat9 = g.buf(5, 4 * ch)
-    cbs("model.9.cv1", (b8, 0, c5), (cat9, 0), 1, 1)
-    g.ops.append(dict(kind=OP_SPPF_POOL, in_buf=cat9, in_choff=0, cin=ch, out_buf=cat9, out_choff=ch, cout=3 * ch,
-                      ksize=5, stride=1, act=0, res_buf=-1, res_choff=0, npad=0, w_off=0, b_off=0))
-    cbs("model.9.cv2", (cat9, 0, 4 * ch), (cat20, c4), 1, 1)
-
-    def upsample(src, dst):
-        g.ops.append(dict(kind=OP_UPSAMPLE2X, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=dst[0],
-                          out_choff=dst[1], cout=src[2], ksize=0, stride=0, act=0, res_buf=-1, res_choff=0, npad=0,
-                          w_off=0, b_off=0))
-
-    upsample((cat20, c4, c5), (cat11, 0))
+    _yolo_sppf(g, cbs, (b8, 0, c5), c5, (cat20, c4))
+    g.upsample2x((cat20, c4, c5), (cat11, 0))
     cat17 = g.buf(4, c3 + c4)      # [model.16 | model.12]
     c2f(12, (cat11, 0, c5 + c4), c4, False, 4, (cat17, c3))
-    upsample((cat17, c3, c4), (cat14, 0))
+    g.upsample2x((cat17, c3, c4), (cat14, 0))
     b15 = g.buf(3, c3)
     c2f(15, (cat14, 0, c4 + c3), c3, False, 3, (b15, 0))
     cbs("model.16", (b15, 0, c3), (cat17, 0), 3, 2)
@@ -536,9 +582,9 @@ def build_yolov8(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
         scat = np.ones(tot, np.float32)
         offs = []
         o = 0
-        br_parts = [parts(f"model.22.{br}.{l}.0") for (br, _, _, _) in branches]
+        br_parts = [_yolo_parts(g, sd, f"model.22.{br}.{l}.0") for (br, _, _, _) in branches]
         if any(p[2] is None for p in br_parts):           # one branch has to be folded: fold them all (one conv, one rule)
-            br_parts = [fuse(f"model.22.{br}.{l}.0") + (None,) for (br, _, _, _) in branches]
+            br_parts = [fold_bn(sd, f"model.22.{br}.{l}.0", yolo_arch.BN_EPS) + (None,) for (br, _, _, _) in branches]
         for (br, wd, _, _), pw, (w, b, sc) in zip(branches, widths, br_parts):
             wcat[o:o + wd] = w
             bcat[o:o + wd] = b
@@ -558,9 +604,7 @@ def build_yolov8(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
         for (br, wd, nout, hoff), pw, o in zip(branches, widths, offs):
             h1 = g.buf(lvl, pw)
             cbs(f"model.22.{br}.{l}.1", (h0, o, pw), (h1, 0), 3, 1, out_width=pw)
-            w = np.asarray(sd[f"model.22.{br}.{l}.2.weight"], np.float32)
-            b = np.asarray(sd[f"model.22.{br}.{l}.2.bias"], np.float32)
-            g.conv((h1, 0, pw), (hd, hoff), w, b, 1, 1, ACT_NONE)
+            _conv2d(g, sd, f"model.22.{br}.{l}.2", (h1, 0, pw), (hd, hoff))
         heads.append(hd)
     g.head_buf = tuple(heads)
     return g
@@ -580,34 +624,14 @@ def build_yolo11(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
         raise ValueError("YOLO11 graphs: fp16 storage (half=True) is not implemented for the depthwise conv and the PSA attention")
     info = yolo_arch.infer_arch11_from_state_dict(sd)
     d = yolo_arch.arch11_dims(info["scale"])
-    assert info["nc"] == nc, (info, nc)
-    c2h, c3h, c4h, nk = yolo_arch.head_dims(d, nc, kpt_shape)
-    assert nk == info["nk"], (nk, info)
-    g = Graph(task=TASK_POSE if kpt_shape else TASK_DETECT, nc=nc, nk=nk, kpt_dim=int(kpt_shape[1]) if kpt_shape else 0,
-              dtype={"f32": DTYPE_F32, "h2": DTYPE_H2}[dtype])
-    eps = yolo_arch.BN_EPS
-    split_bn = g.dtype == DTYPE_H2 and UNFOLDED_BN
-
-    def parts(prefix, perm=None):
-        """-> (weights to pack, bias, out_scale | None); ``perm``: output-channel order (rows of the weights and of BatchNorm)"""
-        view, p = sd, prefix
-        if perm is not None:
-            view = {"x.conv.weight": np.asarray(sd[f"{prefix}.conv.weight"])[perm]}
-            view.update({f"x.bn.{k}": np.asarray(sd[f"{prefix}.bn.{k}"])[perm] for k in ("weight", "bias", "running_mean", "running_var")})
-            p = "x"
-        if split_bn:
-            w, sc, b = fold_bn_split(view, p, eps)
-            if fp16_exact(w):
-                return w, b, sc
-        w, b = fold_bn(view, p, eps)
-        return w, b, None
+    g, (c2h, c3h, c4h), nk = _yolo_graph(info, d, nc, kpt_shape, dtype)
 
     def cb(prefix, src, dst, k, s, act=ACT_SILU, res=None, out_width=None, perm=None):
-        w, b, sc = parts(prefix, perm)
+        w, b, sc = _yolo_parts(g, sd, prefix, perm)         # perm: output-channel order (rows of the weights and of BatchNorm)
         g.conv(src, dst, w, b, k, s, act, res, out_width, out_scale=sc)
 
     def dw(prefix, src, dst, act, res=None):
-        w, b = fold_bn(sd, prefix, eps)
+        w, b = fold_bn(sd, prefix, yolo_arch.BN_EPS)
         g.dwconv3(src, dst, w, b, act, res)
 
     def c3k2(i, src, cout, c3k, e, level, dst):
@@ -637,28 +661,11 @@ def build_yolo11(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
                 cb(f"{p}.m.{j}.cv2", (t, 0, ht), y, 3, 1, res=(x[0], x[1]))
         cb(f"{p}.cv2", (cat, 0, (2 + n) * c), dst, 1, 1)
 
-    def upsample(src, dst):
-        g.ops.append(dict(kind=OP_UPSAMPLE2X, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=dst[0],
-                          out_choff=dst[1], cout=src[2], ksize=0, stride=0, act=0, res_buf=-1, res_choff=0, npad=0,
-                          w_off=0, b_off=0))
-
     blk = {i: (cout, c3k, e) for i, _, cout, c3k, e in yolo_arch.c3k2_layers(d)}
     c1, c2, c3, c4, c5 = d.c1, d.c2, d.c3, d.c4, d.c5
-    fuse = lambda p: fold_bn(sd, p, eps)
-    # stem: straight from the u8 network input
-    c1p = g.padk(c1)
-    b0 = g.buf(1, c1p)
-    w0, bias0 = fuse("model.0")
-    w0p = np.zeros((c1p, 27), np.float32)
-    w0p[:c1] = np.ascontiguousarray(w0.transpose(0, 2, 3, 1)).reshape(c1, 27)          # [cout][ky][kx][c]
-    b0p = np.zeros(c1p, np.float32)
-    b0p[:c1] = bias0
-    w_off = g._add(w0p)
-    b_off = g._add(b0p)
-    g.ops.append(dict(kind=OP_STEM, in_buf=0, in_choff=0, cin=3, out_buf=b0, out_choff=0, cout=c1p, ksize=3, stride=2,
-                      act=ACT_SILU, res_buf=-1, res_choff=0, npad=c1p, w_off=w_off, b_off=b_off))
+    x0 = _yolo_stem(g, sd, c1)
     b1 = g.buf(2, c2)
-    cb("model.1", (b0, 0, c1p), (b1, 0), 3, 2)
+    cb("model.1", x0, (b1, 0), 3, 2)
     b2 = g.buf(2, c3)
     c3k2(2, (b1, 0, c2), *blk[2], 2, (b2, 0))
     b3 = g.buf(3, c3)
@@ -673,13 +680,7 @@ def build_yolo11(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
     cb("model.7", (cat12, c5, c4), (b7, 0), 3, 2)
     b8 = g.buf(5, c5)
     c3k2(8, (b7, 0, c5), *blk[8], 5, (b8, 0))
-    ch = c5 // 2
-    cat9 = g.buf(5, 4 * ch)
-    cb("model.9.cv1", (b8, 0, c5), (cat9, 0), 1, 1)
-    g.ops.append(dict(kind=OP_SPPF_POOL, in_buf=cat9, in_choff=0, cin=ch, out_buf=cat9, out_choff=ch, cout=3 * ch,
-                      ksize=5, stride=1, act=0, res_buf=-1, res_choff=0, npad=0, w_off=0, b_off=0))
-    b9 = g.buf(5, c5)
-    cb("model.9.cv2", (cat9, 0, 4 * ch), (b9, 0), 1, 1)
+    b9, _ = _yolo_sppf(g, cb, (b8, 0, c5), c5)
 
     # C2PSA: a, b = split(cv1(x)); b = PSABlock^n(b); cv2(cat(a, b))
     cat21 = g.buf(5, c4 + c5)      # [model.20 | model.10]
@@ -705,10 +706,10 @@ def build_yolo11(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
         x = y
     cb("model.10.cv2", (catp, 0, 2 * c), (cat21, c4), 1, 1)
 
-    upsample((cat21, c4, c5), (cat12, 0))
+    g.upsample2x((cat21, c4, c5), (cat12, 0))
     cat18 = g.buf(4, c3 + c4)      # [model.17 | model.13]
     c3k2(13, (cat12, 0, c5 + c4), *blk[13], 4, (cat18, c3))
-    upsample((cat18, c3, c4), (cat15, 0))
+    g.upsample2x((cat18, c3, c4), (cat15, 0))
     b16 = g.buf(3, c3)
     c3k2(16, (cat15, 0, c4 + c4), *blk[16], 3, (b16, 0))
     cb("model.17", (b16, 0, c3), (cat18, 0), 3, 2)
@@ -729,16 +730,14 @@ def build_yolo11(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
             h0, h1 = g.buf(lvl, pw), g.buf(lvl, pw)
             cb(f"model.23.{br}.{l}.0", (feat, 0, chn), (h0, 0), 3, 1, out_width=pw)
             cb(f"model.23.{br}.{l}.1", (h0, 0, pw), (h1, 0), 3, 1, out_width=pw)
-            g.conv((h1, 0, pw), (hdb, hoff), np.asarray(sd[f"model.23.{br}.{l}.2.weight"], np.float32),
-                   np.asarray(sd[f"model.23.{br}.{l}.2.bias"], np.float32), 1, 1, ACT_NONE)
+            _conv2d(g, sd, f"model.23.{br}.{l}.2", (h1, 0, pw), (hdb, hoff))
         pw = g.padk(c3h)
         d0, p0, d1, p1 = g.buf(lvl, chn), g.buf(lvl, pw), g.buf(lvl, pw), g.buf(lvl, pw)
         dw(f"model.23.cv3.{l}.0.0", (feat, 0, chn), (d0, 0), ACT_SILU)
         cb(f"model.23.cv3.{l}.0.1", (d0, 0, chn), (p0, 0), 1, 1, out_width=pw)
         dw(f"model.23.cv3.{l}.1.0", (p0, 0, pw), (d1, 0), ACT_SILU)
         cb(f"model.23.cv3.{l}.1.1", (d1, 0, pw), (p1, 0), 1, 1, out_width=pw)
-        g.conv((p1, 0, pw), (hdb, 64), np.asarray(sd[f"model.23.cv3.{l}.2.weight"], np.float32),
-               np.asarray(sd[f"model.23.cv3.{l}.2.bias"], np.float32), 1, 1, ACT_NONE)
+        _conv2d(g, sd, f"model.23.cv3.{l}.2", (p1, 0, pw), (hdb, 64))
         heads_out.append(hdb)
     g.head_buf = tuple(heads_out)
     return g
@@ -776,15 +775,7 @@ def build_tracknet(sd, dtype: str = "f32") -> Graph:
         w, b = fold_bn(sd, prefix, TRACKNET_BN_EPS)
         g.conv(src, dst, w, b, 3, 1, ACT_RELU)
 
-    def pool(src, dst):
-        g.ops.append(dict(kind=OP_MAXPOOL2, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=dst[0], out_choff=dst[1],
-                          cout=src[2], ksize=2, stride=2, act=0, res_buf=-1, res_choff=0, npad=0, w_off=0, b_off=0))
-
-    def up(src, dst):
-        g.ops.append(dict(kind=OP_UPSAMPLE2X, in_buf=src[0], in_choff=src[1], cin=src[2], out_buf=dst[0],
-                          out_choff=dst[1], cout=src[2], ksize=0, stride=0, act=0, res_buf=-1, res_choff=0, npad=0,
-                          w_off=0, b_off=0))
-
+    pool, up = g.maxpool2, g.upsample2x
     x0 = g.buf(0, cin0)
     cat3 = g.buf(0, 128 + 64)        # [up(up_block_2) | x1]
     cat2 = g.buf(1, 256 + 128)       # [up(up_block_1) | x2]
@@ -825,8 +816,7 @@ def build_tracknet(sd, dtype: str = "f32") -> Graph:
     block("up_block_3.conv_1", (cat3, 0, 192), (t, 0))
     block("up_block_3.conv_2", (t, 0, 64), (u3, 0))
     out = g.buf(0, out_dim if out_dim % 4 == 0 else pad16(out_dim))
-    g.conv((u3, 0, 64), (out, 0), np.asarray(sd["predictor.weight"], np.float32),
-           np.asarray(sd["predictor.bias"], np.float32), 1, 1, ACT_SIGMOID)
+    _conv2d(g, sd, "predictor", (u3, 0, 64), (out, 0), ACT_SIGMOID)
     g.head_buf = (out, -1, -1)
     g.out_channels = out_dim
     return g
@@ -941,28 +931,15 @@ def build_resnet50(sd, dtype: str = "f32") -> Graph:
     h2 graph runs three products per operand pair, as TrackNetV3 does."""
     check_resnet50_state_dict(sd)
     g = Graph(task=TASK_RESNET, dtype={"f32": DTYPE_F32, "h2": DTYPE_H2}[dtype])
-    split_bn = g.dtype == DTYPE_H2 and UNFOLDED_BN
-
-    def parts(conv, bn):
-        """-> (weights to pack, bias, out_scale | None): fold_bn / fold_bn_split over this conv's and BatchNorm's tensors"""
-        view = {"x.conv.weight": sd[f"{conv}.weight"]}
-        view.update({f"x.bn.{k}": sd[f"{bn}.{k}"] for k in ("weight", "bias", "running_mean", "running_var")})
-        if split_bn:
-            w, sc, b = fold_bn_split(view, "x", RESNET_BN_EPS)
-            if fp16_exact(w):
-                return w, b, sc
-        w, b = fold_bn(view, "x", RESNET_BN_EPS)
-        return w, b, None
 
     def cb(conv, bn, src, dst, k, s, act, res=None, res_preact=False):
-        w, b, sc = parts(conv, bn)
+        w, b, sc = bn_parts(g, sd, f"{conv}.weight", bn, RESNET_BN_EPS)
         g.conv(src, dst, w, b, k, s, act, res, out_scale=sc, res_preact=res_preact)
 
     # conv1 + bn1 + relu from the u8 network input: [148][64] weights (row (ky * 7 + kx) * 3 + c), bias, normalisation table
-    w0, b0 = fold_bn({"x.conv.weight": sd["conv1.weight"], **{f"x.bn.{k}": sd[f"bn1.{k}"] for k in
-                                                               ("weight", "bias", "running_mean", "running_var")}}, "x", RESNET_BN_EPS)
+    w0, scale0, b0 = _bn_split(sd, "conv1.weight", "bn1", RESNET_BN_EPS)
     stem = g.buf(1, 64)
-    g.stem7(w0, b0, (stem, 0))
+    g.stem7(_scale_rows(w0, scale0), b0, (stem, 0))
     x = g.buf(2, 64)
     g.maxpool3s2((stem, 0, 64), (x, 0))
     cin, level = 64, 2

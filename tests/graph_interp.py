@@ -72,8 +72,8 @@ def run(graph: G.Graph, net_in: torch.Tensor = None, buf0: torch.Tensor = None, 
     blob = graph.blob()
     ref = net_in if net_in is not None else buf0
     B, _, H, W = ref.shape
-    f16 = getattr(graph, "dtype", 0) == G.DTYPE_F16
-    h2 = getattr(graph, "dtype", 0) == G.DTYPE_H2
+    f16 = graph.dtype == G.DTYPE_F16
+    h2 = graph.dtype == G.DTYPE_H2
     heads = set(graph.head_buf)
     # fp16 graphs: what is written to a non-head buffer is rounded to fp16 (storage), arithmetic stays fp32 —
     # the engine's fp16 path up to the order of the fp32 accumulation.  `stale` fills the buffers first, to prove

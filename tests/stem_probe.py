@@ -60,12 +60,9 @@ def unshuffle_weight(cin: int) -> np.ndarray:
 
 
 def append_stem(g: G.Graph, w: np.ndarray, b: np.ndarray, dst) -> None:
-    """The OP_STEM op exactly as ``graph.build_yolov8`` appends it: weights [cout][27] in (ky, kx, colour) order, bias, SiLU."""
-    c = w.shape[0]
-    w_off = g._add(np.ascontiguousarray(w, np.float32).reshape(c, 27))
-    b_off = g._add(np.asarray(b, np.float32))
-    g.ops.append(dict(kind=G.OP_STEM, in_buf=0, in_choff=0, cin=3, out_buf=dst[0], out_choff=dst[1], cout=c, ksize=3, stride=2,
-                      act=G.ACT_SILU, res_buf=-1, res_choff=0, npad=c, w_off=w_off, b_off=b_off))
+    """The OP_STEM op exactly as ``graph.build_yolov8`` appends it: weights [cout][27] in (ky, kx, colour) order, bias, SiLU.
+    ``w`` is [cout][ky][kx][colour] already; ``Graph.stem`` takes the checkpoint's [cout][colour][ky][kx]."""
+    g.stem(np.asarray(w).transpose(0, 3, 1, 2), b, dst)
 
 
 def _finish_heads(g: G.Graph, src, head3: int, width: int) -> None:

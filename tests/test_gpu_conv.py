@@ -300,8 +300,7 @@ def test_upsample_absorbed(gpu_engine, shape):
         cat = g.buf(0, c_up + c_skip)
         out = g.buf(0, G.pad16(cout))
         g.conv((b0, 0, cin0), (coarse, 0), w_dn, np.zeros(c_up, np.float32), 3, 2, G.ACT_SILU)
-        g.ops.append(dict(kind=G.OP_UPSAMPLE2X, in_buf=coarse, in_choff=0, cin=c_up, out_buf=cat, out_choff=0, cout=c_up,
-                          ksize=0, stride=0, act=0, res_buf=-1, res_choff=0, npad=0, w_off=0, b_off=0))
+        g.upsample2x((coarse, 0, c_up), (cat, 0))
         g.conv((b0, 0, cin0), (cat, c_up), w_sk, np.zeros(c_skip, np.float32), 1, 1, G.ACT_NONE)
         g.conv((cat, 0, c_up + c_skip), (out, 0), w, b, k, 1, G.ACT_SILU)
         g.head_buf = (out, -1, -1)

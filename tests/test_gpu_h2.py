@@ -313,8 +313,7 @@ def test_h2_upsample_absorbed(gpu_engine, shape):
         cat = g.buf(0, c_up + c_skip)
         out = g.buf(0, G.pad16(cout))
         g.conv((b0, 0, cin0), (coarse, 0), w_dn, np.zeros(c_up, np.float32), 3, 2, G.ACT_SILU)
-        g.ops.append(dict(kind=G.OP_UPSAMPLE2X, in_buf=coarse, in_choff=0, cin=c_up, out_buf=cat, out_choff=0, cout=c_up,
-                          ksize=0, stride=0, act=0, res_buf=-1, res_choff=0, npad=0, w_off=0, b_off=0))
+        g.upsample2x((coarse, 0, c_up), (cat, 0))
         g.conv((b0, 0, cin0), (cat, c_up), w_sk, np.zeros(c_skip, np.float32), 1, 1, G.ACT_NONE)
         g.conv((cat, 0, c_up + c_skip), (out, 0), w, b, k, 1, G.ACT_SILU)
         g.head_buf = (out, -1, -1)
@@ -367,11 +366,9 @@ def test_h2_helper_kernels(gpu_engine):
     b0 = g.buf(0, c)
     small = g.buf(1, c)
     cat = g.buf(0, 4 * c)
-    op = lambda kind, src, dst, cin, cout, k, s: dict(kind=kind, in_buf=src[0], in_choff=src[1], cin=cin, out_buf=dst[0], out_choff=dst[1],
-                                                      cout=cout, ksize=k, stride=s, act=0, res_buf=-1, res_choff=0, npad=0, w_off=0, b_off=0)
-    g.ops.append(op(G.OP_MAXPOOL2, (b0, 0), (small, 0), c, c, 2, 2))
-    g.ops.append(op(G.OP_UPSAMPLE2X, (small, 0), (cat, 0), c, c, 0, 0))          # its reader is a pool: never absorbed
-    g.ops.append(op(G.OP_SPPF_POOL, (cat, 0), (cat, c), c, 3 * c, 5, 1))
+    g.maxpool2((b0, 0, c), (small, 0))
+    g.upsample2x((small, 0, c), (cat, 0))          # its reader is a pool: never absorbed
+    g.sppf_pool(cat, c)
     g.head_buf = (cat, -1, -1)                                        # read back raw: the pools wrote PAIRS into it
     m = E.Model(gpu_engine, g)
     m.set_max_batch(B)

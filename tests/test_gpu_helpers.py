@@ -43,11 +43,6 @@ DTYPE = {"f32": G.DTYPE_F32, "f16": G.DTYPE_F16, "h2": G.DTYPE_H2}
 CONTENTS = ("negative", "ties", "ramp", "wide")
 
 
-def _op(kind, src, dst, cin, cout, k, s):
-    return dict(kind=kind, in_buf=src[0], in_choff=src[1], cin=cin, out_buf=dst[0], out_choff=dst[1], cout=cout, ksize=k, stride=s,
-                act=0, res_buf=-1, res_choff=0, npad=0, w_off=0, b_off=0)
-
-
 # ---- storage types: what a buffer holds for a given fp32 array, as bits and as values ---------------------------------------
 def to_input(t, x):
     """The array handed to tracknet_infer (fp16 graphs take halves; h2 graphs take fp32 and encode on the device)."""
@@ -165,7 +160,7 @@ def test_sppf(gpu_engine, case):
     width = off + 4 * c + VEC[t]                                   # wider than the concat: channels right of it must survive
     g = G.Graph(task=G.TASK_TRACKNET, dtype=DTYPE[t])
     b0 = g.buf(0, width)
-    g.ops.append(_op(G.OP_SPPF_POOL, (b0, off), (b0, off + c), c, 3 * c, 5, 1))
+    g.sppf_pool(b0, c, off)
     g.head_buf = (b0, -1, -1)
     m = E.Model(gpu_engine, g)
     m.set_max_batch(B)
@@ -222,12 +217,12 @@ def pool_graph(t, c, in_off, off1, off0, upsample):
     b0 = g.buf(0, W_IN)
     s1 = g.buf(1, W_SMALL)
     g.conv((b0, 0, 32), (s1, 0), z(W_SMALL, 32, 1, 1), slice_sentinel(W_SMALL), 1, 2, G.ACT_NONE)
-    g.ops.append(_op(G.OP_MAXPOOL2, (b0, in_off), (s1, off1), c, c, 2, 2))
+    g.maxpool2((b0, in_off, c), (s1, off1))
     last, lvl, width = s1, 1, W_SMALL
     if upsample:
         s0 = g.buf(0, W_BIG)
         g.conv((b0, 0, 32), (s0, 0), z(W_BIG, 32, 1, 1), slice_sentinel(W_BIG), 1, 1, G.ACT_NONE)
-        g.ops.append(_op(G.OP_UPSAMPLE2X, (s1, off1), (s0, off0), c, c, 0, 0))
+        g.upsample2x((s1, off1, c), (s0, off0))
         last, lvl, width = s0, 0, W_BIG
     if t == "f16":
         hd = g.buf(lvl, width)
@@ -300,7 +295,7 @@ def encoder_specials():
 def encoder_run(gpu_engine, x):
     g = G.Graph(task=G.TASK_TRACKNET, dtype=G.DTYPE_H2)
     b0 = g.buf(0, ENC_SHAPE[-1])
-    g.ops.append(_op(G.OP_SPPF_POOL, (b0, 0), (b0, 16), 16, 48, 5, 1))
+    g.sppf_pool(b0, 16)
     g.head_buf = (b0, -1, -1)
     m = E.Model(gpu_engine, g)
     m.set_max_batch(1)
@@ -365,16 +360,16 @@ def test_fp16_helper_on_a_buffer_that_is_not_a_multiple_of_8_wide_is_refused(gpu
     g = G.Graph(task=G.TASK_TRACKNET, dtype=G.DTYPE_F16)
     if kind == "sppf":
         b0 = g.buf(0, 36)
-        g.ops.append(_op(G.OP_SPPF_POOL, (b0, 0), (b0, 8), 8, 24, 5, 1))
+        g.sppf_pool(b0, 8)
         g.head_buf = (b0, -1, -1)
     elif kind == "maxpool":
         b0, b1 = g.buf(0, 32), g.buf(1, 36)
-        g.ops.append(_op(G.OP_MAXPOOL2, (b0, 0), (b1, 8), 8, 8, 2, 2))
+        g.maxpool2((b0, 0, 8), (b1, 8))
         g.head_buf = (b1, -1, -1)
     else:
         b0, b1, b2 = g.buf(0, 32), g.buf(1, 32), g.buf(0, 44)
-        g.ops.append(_op(G.OP_MAXPOOL2, (b0, 0), (b1, 8), 8, 8, 2, 2))
-        g.ops.append(_op(G.OP_UPSAMPLE2X, (b1, 8), (b2, 16), 8, 8, 0, 0))
+        g.maxpool2((b0, 0, 8), (b1, 8))
+        g.upsample2x((b1, 8, 8), (b2, 16))
         g.head_buf = (b2, -1, -1)
     with pytest.raises(E.EngineError, match="multiple of 8"):
         E.Model(gpu_engine, g)
