@@ -285,7 +285,8 @@ int pa_model_plan_bytes(pa_model* m, size_t* arena_bytes, size_t* logical_bytes)
 
 /* tests: overwrite every byte of the planned activation arena (0xFF = NaN patterns in fp32 and fp16).  A following
  * inference must be unaffected: no kernel may read a byte nobody wrote since (h2 / fp32 graphs; fp16 graphs rely on
- * zero-initialised pad channels and are excluded)                                                            */
+ * zero-initialised pad channels and are excluded).  The u8 network input of a YOLO / ResNet plan is overwritten as well:
+ * the preprocessing of the next call writes all four bytes of every pixel                                     */
 int pa_model_fill_arena(pa_model* m, int byte_value);
 
 enum pa_pre_mode {
@@ -398,6 +399,11 @@ int pa_ball_feed(pa_ball* b, const uint8_t* frames_bgr, int n, int frames_on_dev
 
 /* predict_location on caller-supplied masks (n x 288 x 512 uint8, n <= max_batch + 7) -> n x 4 {x, y, w, h} */
 int pa_ball_locate(pa_ball* b, const uint8_t* masks, int n, int32_t* out_rects);
+
+/* tests: one image of the session's Pillow-bicubic resize, 288 x 512 x 3 bytes RGB — byte-exact check of that preprocessing.
+ * frame < 0: the resized background of the last pa_ball_set_background / pa_ball_background_from_frames; otherwise frame `frame`
+ * (counted from 0 since the background was set) of the ring, which keeps the last max_batch + 7 frames fed */
+int pa_ball_read_resized(pa_ball* b, long long frame, uint8_t* out);
 
 /* ---- multi-GPU: one process per GPU, frames shard by batch, the ONLY collective is the one-time broadcast
  * of the packed weight blob from the rank that loaded the checkpoint; RCCL over xGMI,

@@ -603,6 +603,8 @@ int pa_model_fill_arena(pa_model* m, int byte_value) {
     if (!m->planned || !m->arena) PA_FAIL(e, "pa_model_fill_arena: no plan yet");
     PA_HIP(e, hipSetDevice(e->dev));
     PA_HIP(e, hipMemsetAsync(m->arena, byte_value & 0xFF, m->arena_bytes, e->stream));
+    // (the u8 network input as well: the preprocessing of the next call writes all four bytes of every pixel)
+    if (m->d_netin) PA_HIP(e, hipMemsetAsync(m->d_netin, byte_value & 0xFF, (size_t)m->p_batch * m->net_h * m->net_w * 4, e->stream));
     PA_HIP(e, hipStreamSynchronize(e->stream));
     return 0;
 }

@@ -46,6 +46,9 @@ void resample_free(ResamplePlan* rs) {
 }
 
 hipError_t resample_enqueue(const ResamplePlan& rs, const uint8_t* src, uint8_t* dst, int n, int out_c, int reverse, hipStream_t s) {
+    // a source of the target size has no pass to run unless the plan built the 1-tap one (the ball session's): the YOLO and ResNet
+    // paths copy such frames with the letterbox kernel and never get here; launching nothing would leave dst as it was
+    if (rs.sw == rs.dw && rs.sh == rs.dh && !rs.d_vb) return hipErrorInvalidValue;
     const uint8_t* cur = src;
     int cw = rs.sw;
     hipError_t r = hipSuccess;

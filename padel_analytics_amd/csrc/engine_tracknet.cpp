@@ -279,6 +279,20 @@ int pa_ball_feed(pa_ball* b, const uint8_t* frames, int n, int on_device, int fl
     return 0;
 }
 
+int pa_ball_read_resized(pa_ball* b, long long frame, uint8_t* out) {
+    if (!b || !out) return 1;
+    pa_engine* e = b->m->e;
+    if (!b->have_bg) PA_FAIL(e, "pa_ball_read_resized: no background set");
+    if (frame >= b->fed || (frame >= 0 && frame + b->ring < b->fed))
+        PA_FAIL(e, "pa_ball_read_resized: frame %lld is not among the last %d of %lld fed", frame, b->ring, b->fed);
+    PA_HIP(e, hipSetDevice(e->dev));
+    const size_t bytes = (size_t)BALL_H * BALL_W * 3;
+    const uint8_t* src = frame < 0 ? b->d_med : b->d_small + (size_t)(frame % b->ring) * bytes;
+    PA_HIP(e, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, e->stream));
+    PA_HIP(e, hipStreamSynchronize(e->stream));
+    return 0;
+}
+
 int pa_ball_locate(pa_ball* b, const uint8_t* masks, int n, int32_t* out_rects) {
     if (!b || !masks || !out_rects) return 1;
     pa_engine* e = b->m->e;

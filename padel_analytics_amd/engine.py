@@ -116,7 +116,7 @@ ABI_SYMBOLS = [
     "pa_engine_bcast_weights_from", "pa_model_fill_arena", "pa_yolo_submit", "pa_yolo_wait",
     "pa_resnet_infer", "pa_resnet_read_netin", "pa_resnet_read_fc", "pa_resnet_read_head", "pa_pil_coeffs",
     "pa_yuv420_to_bgr", "pa_yuv_last_path", "pa_engine_timer_start", "pa_engine_timer_stop",
-    "pa_render", "pa_render_check", "pa_render_last_path", "pa_glyph_rows",
+    "pa_render", "pa_render_check", "pa_render_last_path", "pa_glyph_rows", "pa_ball_read_resized",
 ]
 
 
@@ -173,6 +173,7 @@ def load_library():
     lib.pa_ball_feed.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, C.POINTER(i32)]
     lib.pa_ball_locate.argtypes = [vp, vp, i32, vp]
     lib.pa_ball_background_from_frames.argtypes = [vp, vp, i32, i32, vp]
+    lib.pa_ball_read_resized.argtypes = [vp, C.c_longlong, vp]
     lib.pa_upload.argtypes = [vp, vp, vp, sz]
     lib.pa_engine_set_tuning.argtypes = [vp, C.c_char_p, i32]
     lib.pa_engine_set_timeline_path.argtypes = [vp, C.c_char_p]
@@ -717,7 +718,8 @@ class Model:
         return boxes, kpts, counts
 
     def fill_arena(self, byte_value: int = 0xFF) -> None:
-        """Tests: overwrite the planned activation arena (0xFF = NaN patterns): a following inference must not notice."""
+        """Tests: overwrite the planned activation arena (0xFF = NaN patterns) and the u8 network input: a following inference
+        must not notice."""
         self.engine._check(self.engine.lib.pa_model_fill_arena(self.handle, int(byte_value)))
 
     def take_overflow(self) -> bool:
@@ -945,6 +947,14 @@ class BallSession:
         rects = np.empty((n, 4), np.int32)
         self.model.engine._check(self.model.engine.lib.pa_ball_locate(self.handle, masks.ctypes.data, n, rects.ctypes.data))
         return rects
+
+    def read_resized(self, frame: Optional[int] = None) -> np.ndarray:
+        """Tests: the (288, 512, 3) uint8 RGB image the session's Pillow resize made of the background (``frame`` None) or of
+        frame ``frame`` (counted from 0 since the background was set; the ring keeps the last max_feed + 7 frames fed)."""
+        out = np.empty((self.H, self.W, 3), np.uint8)
+        self.model.engine._check(self.model.engine.lib.pa_ball_read_resized(self.handle, -1 if frame is None else int(frame),
+                                                                            out.ctypes.data))
+        return out
 
     def close(self):
         if self.handle:
