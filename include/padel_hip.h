@@ -252,6 +252,49 @@ int pa_render_last_path(pa_engine* eng);
  * code outside the font                                                                                                   */
 int pa_glyph_rows(int code, uint8_t rows[7]);
 
+/* ---- frames to a file: the YUV 4:2:0 bytes pa_render writes -> one baseline JPEG per frame (Motion-JPEG; csrc/jpeg_encode.hip) ----
+ * The bit stream is specified here; its constants are csrc/jpeg_tables.h (host and device), its readable twin
+ * padel_analytics_amd/mjpeg.py (encode_host), which produces the same bytes.
+ *
+ * One frame = one baseline sequential JPEG (ITU-T T.81): 8-bit, three components, Y sampled 2 x 2, Cb and Cr 1 x 1 (4:2:0, MCUs of
+ * 16 x 16 pixels: Y00 Y01 Y10 Y11 Cb Cr).  Segments, in this order, 613 bytes up to the scan:
+ *     SOI | APP0 "JFIF" 1.01, no units, 1:1, no thumbnail | DQT, one segment, tables 0 (luma) and 1 (chroma), 8-bit, zig-zag order |
+ *     SOF0 with the true h and w, Y table 0, Cb / Cr table 1 | DHT, one segment: DC 0, AC 0, DC 1, AC 1, the Annex K tables, in every
+ *     frame | DRI ceil(w / 16): a restart interval is one MCU row | SOS | the scan, RSTm (m = interval index mod 8) between the
+ *     intervals | EOI
+ * Input: frames as a pa_yuv_desc lays them out (either layout, any pitch, plane offsets, frame stride; its decode coefficients are
+ * not used); JFIF decoders assume the full-range BT.601 matrix — video.YUV_ENC_COEFFS["bt601_full"] on the rendering side.  w and h
+ * even, >= 2; where they are no multiples of 16 a block is completed by repeating the last column and the last row.
+ * Arithmetic, all int32, >> arithmetic, descale(x, s) = (x + (1 << (s - 1))) >> s:
+ *   samples       x - 128
+ *   forward DCT   Loeffler-Ligtenberg-Moshovitz with 13-bit constants (libjpeg's "islow": jpeg_tables.h, fdct8), rows first, then
+ *                 columns.  Row pass: outputs 0 and 4 are the sums shifted left by 2 (exact), the six others descale(.., 11): results
+ *                 scaled by 4.  Column pass: outputs 0 and 4 descale(.., 2), the others descale(.., 15): results scaled by 8 in all.
+ *   quantisation  sign(c) * ((|c| + 4 q) / (8 q)), integer division
+ *   tables        q = clamp((base * s + 50) / 100, 1, 255), base the Annex K luminance / chrominance entry, s = 5000 / Q for
+ *                 Q < 50, else 200 - 2 Q; Q = quality in 1..100
+ * Entropy coding: zig-zag order; DC as the difference to the previous block of the same component in the same restart interval (0
+ * at its start), category + bits; AC as run / size symbols with ZRL for 16 zeros and EOB; the Annex K Huffman codes; the last byte
+ * of an interval padded with 1-bits; every 0xFF byte of entropy-coded data followed by 0x00.
+ *
+ * n frames of h x w at src_yuv_dev (HBM) -> the JPEGs back to back in dst_host[0 .. offsets_host[n]); frame i occupies
+ * [offsets_host[i], offsets_host[i + 1]) (offsets_host: n + 1 entries, [0] = 0).  0 on success.  If the frames take more than
+ * cap bytes, nothing is written to dst_host, offsets_host[n] is the size needed (offsets_host[0] = 0, the others untouched)
+ * and the call fails.  Refused, nothing launched, the reason in pa_last_error: n < 1, odd or too small w / h, w > PA_JPEG_MAX_WIDTH
+ * (one workgroup stages an MCU row in LDS), quality outside 1..100, a pitch smaller than its row, planes reaching into the next
+ * frame, NV12 with off_v != off_u + 1.  pa_jpeg_check gives the same answers on the host alone (no engine, no GPU).
+ * SYNCHRONOUS, but ordered on the engine's compute stream: the pa_render that produced src is ahead of it in that stream, nothing
+ * runs on another stream.  Scratch (the restart intervals' slots, the gathered frames) belongs to the engine, grows on demand and
+ * is freed with it.  A slot holds the worst case of its interval — pa_jpeg_interval_bytes(w): every block 22 + 63 x 26 bits, every
+ * byte stuffed — so no input writes outside its slot; slots of at most 256 MiB are in use at a time (larger calls are encoded
+ * in sub-batches inside the call).                                                                                          */
+#define PA_JPEG_MAX_WIDTH 2560
+int pa_jpeg_encode(pa_engine* eng, const uint8_t* src_yuv_dev, int n, int h, int w, const pa_yuv_desc* geom, int quality,
+                   uint8_t* dst_host, size_t cap, int64_t* offsets_host);
+int pa_jpeg_check(int n, int h, int w, const pa_yuv_desc* geom, int quality, char* why, size_t cap);
+/* host only: the most bytes one restart interval of a frame of width w can take, its closing marker included: a slot's capacity */
+size_t pa_jpeg_interval_bytes(int w);
+
 /* tools: device time of whatever is queued on the engine's compute stream between the two calls, from a pair of HIP events
  * recorded on that stream (tools/yuv_bench.py times the asynchronous pa_yuv420_to_bgr with it).  pa_engine_timer_stop waits for
  * its event and returns the milliseconds between the two.                                                              */

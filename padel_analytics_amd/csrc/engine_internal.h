@@ -5,6 +5,7 @@
 //   engine_tracknet.cpp  pa_tracknet_infer and the ball session
 //   engine_resnet.cpp    the ResNet-50 court-keypoint regressor
 //   engine_render.cpp    pa_render: marks on BGR frames -> BGR / YUV 4:2:0 (the refusals and the font: render_check.cpp, host only)
+//   engine_jpeg.cpp      pa_jpeg_encode: YUV 4:2:0 frames in HBM -> baseline JPEGs in host memory (the refusals, tables and header: jpeg_check.cpp, host only)
 //   engine_comm.cpp      RCCL
 // What is decided about a graph on the host alone lives in graph_plan.cpp, which kernel runs a conv in conv_select.cpp.
 #pragma once
@@ -45,6 +46,7 @@ struct Tuning {
 };
 
 struct pa_comm;
+struct JpegScratch;
 
 struct pa_engine {
     int dev = 0;
@@ -62,6 +64,7 @@ struct pa_engine {
     hipEvent_t timer_ev[2]{};  // pa_engine_timer_start / _stop, created on first use
     uint8_t* render_stage = nullptr; size_t render_stage_cap = 0;   // pa_render: the resolved marks and first[] of the call in flight, filled and read on `stream` only
     int render_last_path = 0; // 1 vector, 2 byte: what the last pa_render launched (pa_render_last_path)
+    JpegScratch* jpeg = nullptr;   // pa_jpeg_encode: slots, tables and the gathered frames, grown on demand, used on `stream` only (engine_jpeg.cpp)
 };
 
 extern thread_local std::string g_err;      // errors of calls that have no engine yet (pa_last_error(NULL))
@@ -159,6 +162,9 @@ void free_plan(pa_model* m);                         // the caller has synchroni
 int plan_buffers(pa_model* m, int batch);            // the arena of a model whose net_h x net_w is set: allocation, memsets, bptr, d_fc
 // run_ops, or (tuning "graph", not while profiling) the replay of its capture for this batch size
 int run_graph(pa_model* m, int n, size_t* pi);
+
+// ---- engine_jpeg.cpp
+void jpeg_scratch_free(pa_engine* e);                 // waits for the stream first
 
 // ---- engine_pre.cpp
 hipError_t upload_table(pa_engine* e, int32_t** dptr, const std::vector<int32_t>& v);

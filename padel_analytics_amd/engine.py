@@ -117,6 +117,7 @@ ABI_SYMBOLS = [
     "pa_resnet_infer", "pa_resnet_read_netin", "pa_resnet_read_fc", "pa_resnet_read_head", "pa_pil_coeffs",
     "pa_yuv420_to_bgr", "pa_yuv_last_path", "pa_engine_timer_start", "pa_engine_timer_stop",
     "pa_render", "pa_render_check", "pa_render_last_path", "pa_glyph_rows", "pa_ball_read_resized",
+    "pa_jpeg_encode", "pa_jpeg_check", "pa_jpeg_interval_bytes",
 ]
 
 
@@ -207,6 +208,10 @@ def load_library():
     lib.pa_render_check.argtypes = [i32, i32, i32, vp, vp, i32, C.POINTER(pa_yuv_desc), C.POINTER(pa_yuv_enc), C.c_char_p, sz]
     lib.pa_render_last_path.argtypes = [vp]
     lib.pa_glyph_rows.argtypes = [i32, vp]
+    lib.pa_jpeg_encode.argtypes = [vp, vp, i32, i32, i32, C.POINTER(pa_yuv_desc), i32, vp, sz, vp]
+    lib.pa_jpeg_check.argtypes = [i32, i32, i32, C.POINTER(pa_yuv_desc), i32, C.c_char_p, sz]
+    lib.pa_jpeg_interval_bytes.argtypes = [i32]
+    lib.pa_jpeg_interval_bytes.restype = sz
     lib.pa_engine_timer_start.argtypes = [vp]
     lib.pa_engine_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
     if lib.pa_abi_version() != 5:
@@ -281,6 +286,28 @@ def render_check(n: int, h: int, w: int, marks, first, out: int = RENDER_BGR, ge
     rc = load_library().pa_render_check(int(n), int(h), int(w), marks.ctypes.data if marks.size else None, first.ctypes.data, int(out),
                                         C.byref(geom) if geom is not None else None, C.byref(enc) if enc is not None else None, why, 512)
     return why.value.decode() if rc else None
+
+
+#: ``pa_jpeg_encode`` refuses wider frames (PA_JPEG_MAX_WIDTH)
+JPEG_MAX_WIDTH = 2560
+
+
+def _yuv_desc_arg(desc):
+    return desc if desc is None or isinstance(desc, pa_yuv_desc) else pa_yuv_desc(**{k: int(v) for k, v in desc.items()})
+
+
+def jpeg_check(n: int, h: int, w: int, desc, quality: int = 90) -> Optional[str]:
+    """None if ``pa_jpeg_encode`` would accept the call, else its reason for refusing it (``pa_jpeg_check``: host code, no GPU)."""
+    desc = _yuv_desc_arg(desc)
+    why = C.create_string_buffer(512)
+    rc = load_library().pa_jpeg_check(int(n), int(h), int(w), C.byref(desc) if desc is not None else None, int(quality), why, 512)
+    return why.value.decode() if rc else None
+
+
+def jpeg_interval_bytes(w: int) -> int:
+    """The most bytes one restart interval (one MCU row) of a JPEG of width ``w`` can take — the capacity of the slot the encode
+    kernel writes it to (``pa_jpeg_interval_bytes``: host code, no GPU)."""
+    return int(load_library().pa_jpeg_interval_bytes(int(w)))
 
 
 class DeviceBuffer:
@@ -409,6 +436,36 @@ class Engine:
     def render_last_path(self) -> int:
         """RENDER_PATH_VECTOR / RENDER_PATH_BYTE: what the last successful ``render`` launched (0: none yet)."""
         return int(self.lib.pa_render_last_path(self.handle))
+
+    def jpeg_encode(self, buffer: DeviceBuffer, n: int, h: int, w: int, desc, quality: int = 90, out: Optional[np.ndarray] = None):
+        """``n`` frames of 8-bit YUV 4:2:0 in ``buffer``, laid out by ``desc`` (a ``pa_yuv_desc`` or a dict of its fields; what
+        ``render`` wrote with ``out=RENDER_YUV420``, ``enc`` = ``video.YUV_ENC_COEFFS["bt601_full"]``), -> (the baseline JPEGs back to
+        back as a uint8 array, offsets (n + 1,) int64: frame i is ``bytes[offsets[i]:offsets[i + 1]]``) — ``pa_jpeg_encode``, the same
+        bytes as ``mjpeg.encode_host``.  Ordered behind the ``render`` that produced ``buffer`` by the engine's compute stream;
+        returns when the bytes are on the host.  ``out``: a 1-D uint8 array to write into (the result is a view of it); if it is too
+        small nothing is written and the ``EngineError`` carries the size in ``.needed``.  Without ``out`` the array is sized by a
+        guess and, if that was too small, the call is repeated once with the size it asked for."""
+        desc = _yuv_desc_arg(desc)
+        need = yuv_span_bytes(n, h, w, desc)
+        if need is not None and buffer.nbytes < need:   # (geometry that has no span is refused by the library, with its reason)
+            raise EngineError(f"jpeg_encode: {n} frames as described span {need} bytes, the buffer holds {buffer.nbytes}")
+        offsets = np.zeros(max(int(n), 0) + 1, np.int64)
+        own = out is None
+        if own:
+            out = np.empty(max(int(n), 1) * (max(int(h), 1) * max(int(w), 1) // 4 + 4096), np.uint8)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.ndim == 1 and out.flags.c_contiguous):
+            raise TypeError("jpeg_encode: out must be a contiguous 1-D uint8 array")
+        for attempt in (0, 1):
+            rc = self.lib.pa_jpeg_encode(self.handle, buffer.ptr, int(n), int(h), int(w), C.byref(desc), int(quality), out.ctypes.data,
+                                         out.size, offsets.ctypes.data)
+            if rc == 0:
+                return out[:int(offsets[-1])], offsets
+            needed = int(offsets[-1])
+            if needed <= out.size or not own or attempt:
+                err = EngineError(self.lib.pa_last_error(self.handle).decode())
+                err.needed = needed if needed > out.size else None
+                raise err
+            out = np.empty(needed, np.uint8)
 
     def timer_start(self) -> None:
         """Tools: mark the compute stream with a HIP event; ``timer_stop`` -> milliseconds of device time queued since."""

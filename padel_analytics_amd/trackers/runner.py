@@ -17,7 +17,8 @@ Additions (all off by default, the reference's sequential semantics stay the def
   batch trackers consume the same device-resident frames; stream trackers (TrackNet) get the same handles.  The
   reference decodes and uploads the clip once per tracker (:215-220).
 
-* ``render=`` a ``.y4m`` path or a ``video.FrameSink``: ``draw_and_collect_data`` (reference :91-173) reads the clip again and writes it
+* ``render=`` a path or a ``video.FrameSink`` (``.avi`` / ``.mjpeg`` / ``.mjpg``: Motion-JPEG of ``render_quality``, encoded on the GPU
+  — ``video.MjpegSink``; any other path: ``.y4m``): ``draw_and_collect_data`` (reference :91-173) reads the clip again and writes it
   with every tracker's results drawn on it — on the GPU (csrc/render.hip: marks applied to the BGR frames in HBM and converted to
   YUV 4:2:0 in one pass), one download and one write per batch.  Without it (the default) the step prints that it is skipped;
 * ``collect_data=True`` (the reference's own switch, :74-79): the step also projects every frame's players and ball into the 2-D
@@ -46,7 +47,7 @@ class TrackingRunner:
     def __init__(self, trackers: list, video_path: str | Path, inference_path: str | Path, start: int = 0,
                  end: Optional[int] = None, collect_data: bool = False, *, distributed: bool = False,
                  fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None, render=None,
-                 court_inset: Optional[bool] = None) -> None:
+                 court_inset: Optional[bool] = None, render_quality: int = 90) -> None:
         self.video_path = video_path
         self.inference_path = inference_path
         self.start = start
@@ -86,7 +87,8 @@ class TrackingRunner:
         # queued when its device loop ends drains beside the NEXT tracker's device work (1: the loop waits for its own tail)
         self.host_queue_depth = int(os.environ.get("PADEL_HOST_QUEUE_DEPTH", 8)) if host_queue_depth is None else host_queue_depth
         self._tails: list = []
-        self.render = render               # None | path of the .y4m to write | video.FrameSink
+        self.render = render               # None | path of the file to write (.avi / .mjpeg / .mjpg: Motion-JPEG; anything else: .y4m) | video.FrameSink
+        self.render_quality = int(render_quality)   # JPEG quality of a Motion-JPEG file (1..100)
 
     def restart(self) -> None:
         for tracker in self.trackers.values():
@@ -202,6 +204,16 @@ class TrackingRunner:
             marks += self.inset_marks(i)
         return marks
 
+    def _make_sink(self):
+        """(the sink the rendered frames go to, whether the runner owns — and closes — it).  A path ending in ``.avi``, ``.mjpeg`` or
+        ``.mjpg`` gives a ``video.MjpegSink`` of ``render_quality``, any other path a ``video.Y4mSink``."""
+        if isinstance(self.render, video.FrameSink):
+            return self.render, False
+        w, h = self.video_info.width, self.video_info.height
+        if os.path.splitext(str(self.render))[1].lower() in (".avi", ".mjpeg", ".mjpg"):
+            return video.MjpegSink(self.render, w, h, fps=self.video_info.fps, quality=self.render_quality), True
+        return video.Y4mSink(self.render, w, h, fps=self.video_info.fps), True
+
     def _render_clip(self) -> int:
         """The clip once more, ``RENDER_BATCH`` frames at a time: BGR in HBM (``video.device_batch``; host frames through one staging
         clip), one ``Engine.render`` to YUV 4:2:0 in the sink's geometry, one download, one write.  With the inset or the collection
@@ -209,8 +221,7 @@ class TrackingRunner:
         from .. import engine as E, render as R
         eng = self.engine or E.default_engine()
         w, h = self.video_info.width, self.video_info.height
-        own = not isinstance(self.render, video.FrameSink)
-        sink = video.Y4mSink(self.render, w, h, fps=self.video_info.fps) if own else self.render
+        sink, own = self._make_sink()
         print(f"runner: Writing results into {getattr(sink, 'path', sink)}")
         bs, fb = self.RENDER_BATCH, h * w * 3
         dst = eng.alloc(video.yuv_span(bs, h, w, sink.desc))
@@ -242,7 +253,10 @@ class TrackingRunner:
             if own:
                 sink.close()
         t1 = timeit.default_timer()
-        self.timings["__render__"] = {"seconds": t1 - t0, "frames": done}
+        written = getattr(sink, "bytes_written", None)
+        if written is None and own:
+            written = os.path.getsize(sink.path)
+        self.timings["__render__"] = {"seconds": t1 - t0, "frames": done, "bytes": written}
         print(f"runner: rendered {done} frames in {t1 - t0:.3f} s ({done / max(t1 - t0, 1e-9):.1f} frames/s: render + download + write)")
         return done
 

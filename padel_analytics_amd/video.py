@@ -657,6 +657,138 @@ class Y4mSink(FrameSink):
             self._fh = None
 
 
+class MjpegSink(FrameSink):
+    """Writes the frames as Motion-JPEG: every frame one baseline JPEG (``include/padel_hip.h``, ``pa_jpeg_encode``), encoded on the GPU
+    from the renderer's output (``Engine.jpeg_encode``) — only the compressed bytes cross to the host — or, with ``on_device=False``,
+    by the numpy twin ``mjpeg.encode_host``.  The renderer is asked for full-range BT.601 (``enc``), the matrix JFIF decoders assume.
+    The suffix of ``path`` picks the container:
+
+    * ``.mjpeg`` / ``.mjpg``: the JPEGs back to back (``ffmpeg -f mjpeg`` reads that); unbounded.
+    * ``.avi``: AVI 1.0 — ``RIFF 'AVI '``, ``hdrl`` (``avih``, one ``strl`` with ``strh`` ``vids`` / ``MJPG`` and ``strf``, a
+      BITMAPINFOHEADER with ``biCompression = 'MJPG'``), a ``movi`` list of ``00dc`` chunks padded to even length, ``idx1``; the frame
+      count and the sizes are patched in ``close()``.  AVI 1.0 ends at 2 GiB: when the next frame would take the RIFF past
+      ``max_riff_bytes`` the file is finished and the clip continues in ``<stem>.part002.avi``, ``.part003.avi``, ...
+
+    ``paths`` lists the files written.  ``layout`` / ``pitch`` / ``pitch_c`` describe the frames the sink is HANDED, as for
+    ``Y4mSink``."""
+    _MOVI_AT = 220                                     # offset of the 'movi' fourcc: 12 + 12 + 64 + 12 + 64 + 48 + 8
+
+    def __init__(self, path, w: int, h: int, fps: int = 30, quality: int = 90, layout: str = "i420", pitch: Optional[int] = None,
+                 pitch_c: Optional[int] = None, max_riff_bytes: int = 2 ** 31 - 2 ** 24, on_device: bool = True):
+        from . import mjpeg
+        self.path, self.w, self.h, self.fps, self.layout = str(path), int(w), int(h), int(fps), layout
+        self.quality, self.on_device = int(quality), bool(on_device)
+        suffix = os.path.splitext(self.path)[1].lower()
+        if suffix not in (".avi", ".mjpeg", ".mjpg"):
+            raise ValueError(f"MjpegSink: {self.path!r}: the suffix must be .avi, .mjpeg or .mjpg")
+        self.avi = suffix == ".avi"
+        self.desc = yuv_desc(w, h, layout, "bt601", "full", pitch, pitch_c)
+        self.enc = YUV_ENC_COEFFS["bt601_full"]
+        mjpeg.check(1, self.h, self.w, self.desc, self.quality)
+        self.max_riff_bytes = int(max_riff_bytes)
+        self.frames_written = 0
+        self._closed_bytes = 0                         # of the files finished so far
+        self.paths: list = []
+        self._host = None
+        self._fh = None
+        self._open(self.path)
+
+    @property
+    def bytes_written(self) -> int:
+        """Bytes of every file written so far (the open one: up to its last frame)."""
+        return self._closed_bytes + (self._pos if self._fh is not None else 0)
+
+    # ---- the container
+    def _open(self, path: str) -> None:
+        import struct
+        self._fh = open(path, "wb")
+        self.paths.append(path)
+        self._index: list = []                         # (offset of the chunk from the 'movi' fourcc, size of its data)
+        if self.avi:
+            w, h = self.w, self.h
+            avih = struct.pack("<14I", 1000000 // max(self.fps, 1), 0, 0, 0x10, 0, 0, 1, 0, w, h, 0, 0, 0, 0)
+            strh = struct.pack("<4s4sIHHIIIIIIII4h", b"vids", b"MJPG", 0, 0, 0, 0, 1, self.fps, 0, 0, 0, 0xffffffff, 0, 0, 0, w, h)
+            strf = struct.pack("<IiiHH4sIiiII", 40, w, h, 1, 24, b"MJPG", w * h * 3, 0, 0, 0, 0)
+            strl = b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh + b"strf" + struct.pack("<I", len(strf)) + strf
+            hdrl = b"hdrl" + b"avih" + struct.pack("<I", len(avih)) + avih + b"LIST" + struct.pack("<I", len(strl)) + strl
+            head = b"RIFF" + struct.pack("<I", 0) + b"AVI " + b"LIST" + struct.pack("<I", len(hdrl)) + hdrl
+            head += b"LIST" + struct.pack("<I", 0) + b"movi"
+            assert len(head) == self._MOVI_AT + 4
+            self._fh.write(head)
+        self._pos = self._fh.tell()
+
+    def _finish(self) -> None:
+        """The index and the patched sizes of the open file; closes it."""
+        import struct
+        fh = self._fh
+        if self.avi:
+            n = len(self._index)
+            movi_end = self._pos
+            fh.write(b"idx1" + struct.pack("<I", 16 * n))
+            fh.write(b"".join(b"00dc" + struct.pack("<III", 0x10, off, size) for off, size in self._index))
+            end = fh.tell()
+            biggest = max((size for _, size in self._index), default=0)
+            for at, value in ((4, end - 8), (self._MOVI_AT - 4, movi_end - self._MOVI_AT),
+                              (32 + 16, n), (32 + 28, biggest),         # avih: dwTotalFrames, dwSuggestedBufferSize (data at 32)
+                              (108 + 32, n), (108 + 36, biggest)):      # strh: dwLength, dwSuggestedBufferSize (data at 108)
+                fh.seek(at)
+                fh.write(struct.pack("<I", value))
+            self._pos = end
+        fh.close()
+        self._fh = None
+        self._closed_bytes += self._pos
+
+    def _part_path(self, k: int) -> str:
+        stem, suffix = os.path.splitext(self.path)
+        return f"{stem}.part{k:03d}{suffix}"
+
+    def write_jpegs(self, data: np.ndarray, offsets) -> None:
+        """Append the JPEGs ``data[offsets[i]:offsets[i + 1]]``."""
+        import struct
+        for i in range(len(offsets) - 1):
+            jpg = data[int(offsets[i]):int(offsets[i + 1])].tobytes()
+            if not self.avi:
+                self._fh.write(jpg)
+                self._pos += len(jpg)
+            else:
+                chunk = 8 + len(jpg) + (len(jpg) & 1)
+                if self._index and self._pos + chunk + 8 + 16 * (len(self._index) + 1) > self.max_riff_bytes:
+                    self._finish()
+                    self._open(self._part_path(len(self.paths) + 1))
+                self._index.append((self._pos - self._MOVI_AT, len(jpg)))
+                self._fh.write(b"00dc" + struct.pack("<I", len(jpg)) + jpg + (b"\0" if len(jpg) & 1 else b""))
+                self._pos += chunk
+            self.frames_written += 1
+
+    def write_host(self, raw: np.ndarray, n: int) -> None:
+        """``n`` frames in the 1-D byte array ``raw``, laid out by ``desc``: encoded on the host."""
+        from . import mjpeg
+        self.write_jpegs(*mjpeg.encode_host(raw, n, self.h, self.w, self.desc, self.quality))
+
+    def write_device(self, buffer, n: int) -> None:
+        if not self.on_device:
+            span = yuv_span(n, self.h, self.w, self.desc)
+            if self._host is None or self._host.size < span:
+                self._host = np.empty(span, np.uint8)
+            buffer.download(self._host[:span])
+            return self.write_host(self._host[:span], n)
+        if self._host is None:                         # the compressed frames of a batch: grown when a batch needs more
+            self._host = np.empty(n * (self.w * self.h // 4 + 4096), np.uint8)
+        from .engine import EngineError
+        try:
+            data, offsets = buffer.engine.jpeg_encode(buffer, n, self.h, self.w, self.desc, self.quality, out=self._host)
+        except EngineError as e:
+            if getattr(e, "needed", None) is None:
+                raise
+            self._host = np.empty(e.needed * 2, np.uint8)
+            data, offsets = buffer.engine.jpeg_encode(buffer, n, self.h, self.w, self.desc, self.quality, out=self._host)
+        self.write_jpegs(data, offsets)
+
+    def close(self) -> None:
+        if self._fh is not None:
+            self._finish()
+
+
 # .y4m files opened by path: one clip per file as it is on disk now (every read of the path — VideoInfo, each tracker's pass — shares
 # the mapping, the BGR staging and its memory of what it holds); a file that changed is opened afresh
 _Y4M_OPEN: dict = {}
