@@ -31,16 +31,28 @@ Additions (all off by default, the reference's sequential semantics stay the def
   is the host time of projection and collection.  Under ``distributed`` all of it is rank 0's."""
 from __future__ import annotations
 
-import threading
 import os
 import timeit
+from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass
 from pathlib import Path
-from typing import Optional
+from typing import Callable, Optional
 
 import numpy as np
 
 from .. import dist as D, video
-from .tracker import NoPredictFrames, Tracker, _sampler
+from .tracker import NoPredictFrames, Tracker, _sampler, host_stages, relaxed_gc
+
+
+@dataclass(eq=False)
+class _Deferred:
+    """What ``run()`` owes a tracker from the start of its loop on: the wait for its work that finishes later, the report, the save."""
+    tracker: Tracker
+    wait: Optional[Callable] = None    # None: nothing is outstanding; else -> None, or the (start, end) span of the work
+    t0: Optional[float] = None         # the tracker's loop as run() times it (t1 None: the loop did not end)
+    t1: Optional[float] = None
+    merge: bool = False                # rank 0's sequential stage on the merge thread (else: the queued host stages of a batch loop)
+    overlapped: bool = False           # another tracker's loop ran after this was registered
 
 
 class TrackingRunner:
@@ -86,7 +98,8 @@ class TrackingRunner:
         # host stages (zone, ByteTrack, result objects) a batch tracker may have queued behind its device stage; what is still
         # queued when its device loop ends drains beside the NEXT tracker's device work (1: the loop waits for its own tail)
         self.host_queue_depth = int(os.environ.get("PADEL_HOST_QUEUE_DEPTH", 8)) if host_queue_depth is None else host_queue_depth
-        self._tails: list = []
+        self._deferred: list = []          # _Deferred, in tracker order: what run() has not reported and saved yet
+        self._merge_pool = None            # sharded mode, rank 0: the thread of the sequential stages (created with the first one)
         self.render = render               # None | path of the file to write (.avi / .mjpeg / .mjpg: Motion-JPEG; anything else: .y4m) | video.FrameSink
         self.render_quality = int(render_quality)   # JPEG quality of a Motion-JPEG file (1..100)
 
@@ -267,7 +280,6 @@ class TrackingRunner:
 
     def run(self) -> None:
         print(f"runner: Running {self.total_frames} frames")
-        self._merges = []                  # sharded mode, rank 0: sequential stages still running behind the next tracker's shard
         try:
             if self.fanout:
                 self._run_fanout()
@@ -281,39 +293,33 @@ class TrackingRunner:
                         continue
                     tracker.to(tracker.DEVICE)
                     print(f"{str(tracker)}: Running on {tracker.DEVICE} ...")
-                    t0 = timeit.default_timer()
-                    tail: list = []
+                    # registered before its loop and before anything is joined: neither an earlier tracker's error nor its own
+                    # leaves what this tracker has queued uncollected
+                    mine = _Deferred(tracker, t0=timeit.default_timer())
+                    self._deferred.append(mine)
                     if self.distributed:
-                        self._predict_sharded(tracker)
+                        self._predict_sharded(tracker, mine)
                     else:
                         tracker.host_queue_depth = max(1, int(self.host_queue_depth))
+                        tail: list = []
                         self._predict(tracker, defer=tail)
-                    t1 = timeit.default_timer()
+                        mine.wait = tail[0] if tail else None
+                    mine.t1 = timeit.default_timer()
                     tracker.to("cpu")
-                    if self._merges and self._merges[-1][0] is tracker:
-                        self._merges[-1] += (t0, t1)      # reported when the merge is done: shard time and the merge's own span apart
-                        continue
                     # the trackers before this one had this tracker's whole device loop to finish their queued host stages
-                    self._join_tails()
-                    if tail:
-                        self._tails.append((tracker, tail, t0, t1))
-                        continue
-                    self._report(tracker, t0, t1)
-                    if not self.distributed or D.rank() == 0:
-                        tracker.save_predictions()
+                    for d in self._deferred:
+                        d.overlapped = d is not mine
+                    self._join(merges=False, alone=False)
         finally:
-            #  a tracker that raises must not leave finished merges unsaved or the worker pool alive; a merge's own
-            # exception surfaces here, after the merges before it were saved
-            try:
-                self._join_tails()
-            finally:
-                self._join_merges()
+            #  a tracker that raises must not leave finished work unsaved or a worker pool alive; a deferred stage's
+            # own exception surfaces here, after the ones before it were saved
+            self._join()
         self.draw_and_collect_data()
 
     def _predict(self, tracker: Tracker, defer: Optional[list] = None) -> None:
         """One tracker over the whole clip.  A stream tracker on the h2 arithmetic whose activations left the fp16
         range has switched itself to the full-range path and asks to be run again (engine.RangeOverflow); batch
-        trackers repeat the offending batch themselves (yolo.YOLO.infer_frames).  ``defer``: Tracker._predict_batches."""
+        trackers repeat the offending batch themselves (yolo.YOLO.infer_frames).  ``defer``: Tracker.predict_and_update."""
         from .. import engine as E
         try:
             tracker.predict_and_update(self._frames(), defer=defer, total_frames=self.total_frames)
@@ -323,23 +329,47 @@ class TrackingRunner:
             tracker.to(tracker.DEVICE)
             tracker.predict_and_update(self._frames(), defer=defer, total_frames=self.total_frames)
 
-    def _join_tails(self) -> None:
-        """Collect the host stages that were still queued when their trackers' device loops ended.  ``timings``: "seconds" is the
-        device loop's span, "host_tail_seconds" what was left to wait for here — after the next tracker's loop, normally nothing."""
-        tails, self._tails = self._tails, []
+    def _join(self, merges: bool = True, alone: bool = True) -> None:
+        """Wait for deferred work, report and save (rank 0), in tracker order, host tails before merges.  ``merges`` False:
+        only host tails; ``alone`` False: only those that had another tracker's loop to drain beside (or have nothing
+        outstanding).  Every entry is collected even when one raises (the ones behind it are finished work too); the first error
+        is raised afterwards.  With ``merges`` the merge thread ends.
+
+        ``timings``: "seconds" is the tracker's own loop (sharded: device stage + gather).  "host_tail_seconds" is what was left
+        to wait for of its queued host stages — after the next tracker's loop ("host_tail_overlapped"), normally nothing; a tail
+        that drained with no loop beside it is part of "seconds".  "merge_seconds" is the merge's own span, which ran BESIDE the
+        next tracker's shard ("merge_overlapped") — the two are not added: the next tracker's "seconds" already covers that wall
+        time (no double counting)."""
+        take = [d for d in self._deferred if (merges or not d.merge) and (alone or d.overlapped or d.wait is None)]
+        self._deferred = [d for d in self._deferred if d not in take]
         first_error = None
-        for tracker, fins, t0, t1 in tails:
-            ts = timeit.default_timer()
-            try:
-                for f in fins:
-                    f()
-            except BaseException as exc:           # keep collecting: the tails behind this one are finished work too
-                first_error = first_error or exc
-                continue
-            self._report(tracker, t0, t1)
-            self.timings[str(tracker)].update(host_tail_seconds=timeit.default_timer() - ts, host_tail_overlapped=True)
-            if not self.distributed or D.rank() == 0:
-                tracker.save_predictions()
+        try:
+            for d in sorted(take, key=lambda d: d.merge):
+                ts = timeit.default_timer()
+                try:
+                    span = d.wait() if d.wait is not None else None
+                except BaseException as exc:
+                    first_error = first_error or exc
+                    continue
+                waited = timeit.default_timer() - ts
+                if d.t1 is None:                    # its loop did not end: nothing to report
+                    continue
+                if d.merge:
+                    self._report(d.tracker, d.t0, d.t1)
+                    self.timings[str(d.tracker)].update(merge_seconds=span[1] - span[0], merge_overlapped=True)
+                elif d.wait is None or d.overlapped:
+                    self._report(d.tracker, d.t0, d.t1)
+                    if d.wait is not None:
+                        self.timings[str(d.tracker)].update(host_tail_seconds=waited, host_tail_overlapped=True)
+                else:                               # a tail that drained with nothing beside it
+                    self._report(d.tracker, d.t0, d.t1 + waited)
+                    self.timings[str(d.tracker)].update(host_tail_seconds=waited)
+                if not self.distributed or D.rank() == 0:
+                    d.tracker.save_predictions()
+        finally:
+            if merges and self._merge_pool is not None:
+                self._merge_pool.shutdown()
+                self._merge_pool = None
         if first_error is not None:
             raise first_error
 
@@ -351,7 +381,8 @@ class TrackingRunner:
             print(f"{str(tracker)}: {n / (t1 - t0):.1f} frames/s")
 
     # ------------------------------------------------------------------ sharded over GPUs
-    def _predict_sharded(self, tracker: Tracker) -> None:
+    def _predict_sharded(self, tracker: Tracker, mine: _Deferred) -> None:
+        """``mine``: the tracker's entry in ``run()``'s deferred list — a merge that goes to the merge thread is noted there."""
         rank, world = D.rank(), D.world_size()
         n = self.n_available
         lo, hi = D.shard_range(n, rank, world)
@@ -393,7 +424,6 @@ class TrackingRunner:
             allp = D.gather_results(partial, dst=0)
         if rank == 0:
             def merge():
-                from .tracker import relaxed_gc
                 ts = timeit.default_timer()
                 with relaxed_gc():
                     tracker.results.predictions = tracker.merge_partials(allp)
@@ -403,39 +433,11 @@ class TrackingRunner:
             # alone.  Where it touches no GPU it runs on a worker thread while rank 0's GPU starts on the next tracker's shard —
             # otherwise the other ranks would wait for it at the next gather; run() joins before it returns
             if tracker.merge_is_host_only and world > 1:
-                if getattr(self, "_merge_pool", None) is None:
-                    from concurrent.futures import ThreadPoolExecutor
+                if self._merge_pool is None:
                     self._merge_pool = ThreadPoolExecutor(max_workers=1)
-                self._merges.append((tracker, self._merge_pool.submit(merge)))
+                mine.wait, mine.merge = self._merge_pool.submit(merge).result, True
             else:
                 merge()
-
-    def _join_merges(self) -> None:
-        """Collect rank 0's deferred sequential stages.  ``timings``: "seconds" is the tracker's own shard (device stage + gather),
-        "merge_seconds" the merge's own span, which ran BESIDE the next tracker's shard ("merge_overlapped") — the two are not
-        added: the next tracker's "seconds" already covers that wall time (no double counting)."""
-        merges, self._merges = getattr(self, "_merges", []), []
-        pool, self._merge_pool = getattr(self, "_merge_pool", None), None
-        first_error = None
-        try:
-            for item in merges:
-                tracker, fut = item[0], item[1]
-                try:
-                    ts, te = fut.result()
-                except BaseException as exc:       # keep collecting: the merges behind this one are finished work
-                    first_error = first_error or exc
-                    continue
-                if len(item) >= 4:
-                    self._report(tracker, item[2], item[3])
-                    self.timings[str(tracker)].update(merge_seconds=te - ts, merge_overlapped=True)
-                else:                               # the tracker loop was left before its bookkeeping: report the merge alone
-                    self._report(tracker, ts, te)
-                tracker.save_predictions()
-        finally:
-            if pool is not None:
-                pool.shutdown()
-        if first_error is not None:
-            raise first_error
 
     def _share_background(self, tracker) -> None:
         """TrackNet's background median (iterable.py:59-81) is a property of the clip's first frames: rank 0
@@ -463,7 +465,6 @@ class TrackingRunner:
             t.to(t.DEVICE)
             print(f"{str(t)}: Running on {t.DEVICE} (fan-out, {bs} frames per upload) ...")
         t0 = timeit.default_timer()
-        from concurrent.futures import ThreadPoolExecutor
 
         def batches():
             """Batches of frames resident in HBM: device clips and YUV clips pass through; host frames are uploaded once per
@@ -510,28 +511,17 @@ class TrackingRunner:
             for c in clips:
                 c.free()
 
-        import sys
-        interval = sys.getswitchinterval()                 # see Tracker._predict_batches: the device stage must get the GIL back quickly
-        sys.setswitchinterval(min(interval, 2e-4))
-        from .tracker import relaxed_gc
-        try:
-            with relaxed_gc(), ThreadPoolExecutor(max_workers=1) as post:
-                pending = []
-                for sample in batches():
-                    for t in batch:
-                        for sub in _sampler(iter(sample), t.batch_size):
-                            if t._has_stages():
-                                raw = t.infer_sample(sub)
-                                pending.append((t, post.submit(t.post_sample, raw)))
-                            else:
-                                t.results.update(t.predict_sample(sub))
-                    while len(pending) > len(batch):           # host stages trail the device stages by one batch
-                        t, f = pending.pop(0)
-                        t.results.update(f.result())
-                for t, f in pending:
-                    t.results.update(f.result())
-        finally:
-            sys.setswitchinterval(interval)
+        # the host stages of all batch trackers share one queue (no copies: the device stages hand out their own arrays here) and
+        # trail the device stages by one stage per tracker; a tracker without stages is updated in line
+        with host_stages(len(batch)) as queue:
+            for sample in batches():
+                for t in batch:
+                    for sub in _sampler(iter(sample), t.batch_size):
+                        if t._has_stages():
+                            queue.put(t.post_sample, t.infer_sample(sub), t.results.update)
+                        else:
+                            t.results.update(t.predict_sample(sub))
+            queue.finish()
         # stream trackers (TrackNet needs the clip's background median before its first window): their own pass —
         # over the same HBM-resident handles when the clip lives in HBM, else a second read of the source
         for t in stream:

@@ -22,10 +22,10 @@ Written from scratch; host logic only (the numeric engines live behind ``padel_a
 """
 from __future__ import annotations
 
+import contextlib
+import json
 import sys
 import threading
-
-import json
 from abc import ABC, abstractmethod
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass, field
@@ -149,6 +149,60 @@ def _own_arrays(raw):
     return raw
 
 
+class HostStageQueue:
+    """The host stages behind a device loop: one worker thread, at most ``depth`` of them queued, every result delivered to
+    its own ``update`` in the order queued — on the thread that calls ``put`` / ``finish``.  ``own_arrays``: what is queued is
+    a copy (a queue deeper than the engine's recycled result sets must not hold the sets themselves)."""
+
+    def __init__(self, depth: int, own_arrays: bool = False) -> None:
+        self.depth, self.own_arrays = depth, own_arrays
+        self.pool = ThreadPoolExecutor(max_workers=1)
+        self.pending: list = []                              # (future, update), oldest first
+
+    def put(self, fn, raw, update) -> None:
+        if self.own_arrays:
+            raw = _own_arrays(raw)
+        self.pending.append((self.pool.submit(fn, raw), update))
+        while len(self.pending) > self.depth:               # keep `depth` host stages queued behind the device stage
+            self._deliver()
+
+    def _deliver(self) -> None:
+        future, update = self.pending.pop(0)
+        update(future.result())
+
+    def finish(self) -> None:
+        """Deliver what is still queued, then end the worker."""
+        try:
+            with relaxed_gc():
+                while self.pending:
+                    self._deliver()
+        finally:
+            self.close()
+
+    def close(self) -> None:
+        """End the worker without delivering (the error path): what has not started is cancelled."""
+        self.pool.shutdown(wait=True, cancel_futures=True)
+
+
+@contextlib.contextmanager
+def host_stages(depth: int, own_arrays: bool = False):
+    """A ``HostStageQueue`` for the device loop in the block (an exception closes it; otherwise the block finishes it or hands
+    its ``finish`` on), under ``relaxed_gc`` and a short switch interval: the device stage blocks inside the C library with the
+    GIL released; when it returns, its thread has to take the GIL back from the worker, which hands it over only every
+    sys.getswitchinterval() (5 ms by default — the length of a whole device stage of the small models)."""
+    queue = HostStageQueue(depth, own_arrays)
+    interval = sys.getswitchinterval()
+    sys.setswitchinterval(min(interval, 2e-4))
+    try:
+        with relaxed_gc():
+            yield queue
+    except BaseException:
+        queue.close()
+        raise
+    finally:
+        sys.setswitchinterval(interval)
+
+
 def pack_ragged(items: list) -> Optional[list]:
     """[ndarray (k_i, ...)] with one dtype / trailing shape -> [counts (n,) int32, rows (sum k_i, ...)]; None if the items
     are anything else."""
@@ -171,7 +225,7 @@ def unpack_ragged(arrays: list) -> list:
 
 class Tracker(ABC):
     batch_size: int
-    #: True while a loop that bounds the number of live result sets runs (``_predict_batches``): ``infer_sample`` may then ask
+    #: True while a loop that bounds the number of live result sets runs (``_raw_batches``): ``infer_sample`` may then ask
     #: the engine for its recycled output arrays
     _reuse_outputs: bool = False
     #: frames of temporal context a shard needs before / after its own frames (TrackNet windows: 7 / 7)
@@ -285,82 +339,38 @@ class Tracker(ABC):
     #: detector with many tracks is slower than its device stage, and what queues up drains beside the NEXT tracker's device work)
     host_queue_depth = 1
 
-    def _predict_batches(self, frame_generator, update, defer: Optional[list] = None, **kwargs) -> None:
+    def _predict_batches(self, frame_generator, update, defer: Optional[list] = None, **kwargs):
         """Batch loop of reference tracker.py:319-326.  With the two-stage form, post_sample(batch k) runs on one
-        worker thread (in batch order) while infer_sample(batch k+1) occupies the GPU.
+        worker thread (in batch order: ``HostStageQueue``) while the device stage of batch k+1 occupies the GPU (``_raw_batches``).
 
-        ``defer`` (a list): host stages still queued when the device loop ends are not waited for here — a ``finish()`` callable
-        that collects them (in order, through ``update``) is appended instead, for the caller to run once the next tracker's
-        device work is under way.  Results are identical either way: one worker, batch order."""
+        ``defer`` not None: host stages still queued when the device loop ends are not waited for here — the callable that
+        collects them (in order, through ``update``) is returned instead, for the caller to run once the next tracker's device
+        work is under way (None: nothing is left to collect).  Results are identical either way: one worker, batch order."""
         if not self._has_stages():
             for sample in _sampler(frame_generator, self.batch_size):
                 update(self.predict_sample(sample, **kwargs))
-            return
-        # The device stage blocks inside the C library with the GIL released; when it returns, this thread has to take the
-        # GIL back from the worker, which hands it over only every sys.getswitchinterval() (5 ms by default — the length of
-        # a whole device stage of the small models): a short interval for the duration of the loop
-        interval = sys.getswitchinterval()
-        sys.setswitchinterval(min(interval, 2e-4))
+            return None
         # at most three result sets are alive here (the batch in the host stage, the submitted batch being collected, the batch
         # submitted behind it): the device stage may hand out the model's recycled page-locked arrays (engine.Model.OUT_RING).
         # A deeper host queue owns copies of what it holds.
-        self._reuse_outputs = True
         depth = max(1, int(self.host_queue_depth))
-        submitted = None                                    # the token of the batch that is queued on the GPU and not collected yet
-        pool = ThreadPoolExecutor(max_workers=1)
-        pending = []
-        handed_over = False
-        try:
-            with relaxed_gc():
-                def host_stage(raw):
-                    if depth > 1:
-                        raw = _own_arrays(raw)
-                    pending.append(pool.submit(self.post_sample, raw, **kwargs))
-                    while len(pending) > depth:             # keep `depth` host stages queued behind the device stage
-                        update(pending.pop(0).result())
-
-                # Trackers with the two-call device stage (submit_sample / collect_sample: pa_yolo_submit / pa_yolo_wait) have
-                # batch k + 1 queued on the GPU before batch k is collected; the others run one synchronous call per batch.
-                for sample in _sampler(frame_generator, self.batch_size):
-                    token = self.submit_sample(sample, **kwargs)
-                    if submitted is not None:
-                        done, submitted = submitted, token       # (what is in flight is always in `submitted`: the finally drains it)
-                        host_stage(self.collect_sample(done))
-                        if token is None:
-                            host_stage(self.infer_sample(sample, **kwargs))
-                        continue
-                    if token is None:
-                        host_stage(self.infer_sample(sample, **kwargs))
-                    else:
-                        submitted = token
-                if submitted is not None:
-                    token, submitted = submitted, None
-                    host_stage(self.collect_sample(token))
-
-                def finish():
-                    try:
-                        with relaxed_gc():
-                            while pending:
-                                update(pending.pop(0).result())
-                    finally:
-                        pool.shutdown(wait=True, cancel_futures=True)
-
-                if defer is not None and depth > 1 and pending:
-                    defer.append(finish)
-                    handed_over = True
-                else:
-                    finish()
-        finally:
-            self._reuse_outputs = False
-            sys.setswitchinterval(interval)
-            self._drain(submitted)
-            if not handed_over:
-                pool.shutdown(wait=True, cancel_futures=True)
+        post = lambda raw: self.post_sample(raw, **kwargs)
+        with host_stages(depth, own_arrays=depth > 1) as queue:
+            # closed here, not when the generator is collected: a host stage that raises must find the batch in flight
+            # released (``_drain``) before its exception leaves this frame
+            with contextlib.closing(self._raw_batches(frame_generator, **kwargs)) as raws:
+                for raw in raws:
+                    queue.put(post, raw, update)
+            if defer is not None and depth > 1 and queue.pending:
+                return queue.finish
+            queue.finish()
 
     def _raw_batches(self, frame_generator, **kwargs):
         """Yield ``infer_sample``'s result for every batch of the stream, in order — with the next batch already submitted
-        (``submit_sample``) where the tracker has the two-call device stage.  For loops that finish with a batch's arrays
-        before asking for the next one (sharded ``predict_partial``): at most two result sets are alive."""
+        (``submit_sample``: pa_yolo_submit / pa_yolo_wait) where the tracker has the two-call device stage; a batch it declines
+        runs as one synchronous call, in place.  ``_predict_batches`` queues a host stage per result; the sharded ``predict_partial``
+        loops finish with a batch's arrays before asking for the next one: at most two result sets are alive there.  Closing
+        the generator releases the batch in flight (``_drain``)."""
         self._reuse_outputs = True
         submitted = None
         try:
@@ -394,17 +404,17 @@ class Tracker(ABC):
                 print(f"{self.__str__()}: could not release the batch still in flight ({exc!r})")
 
     def predict_and_update(self, frame_generator: Iterable[np.ndarray], defer: Optional[list] = None, **kwargs) -> TrackingResults:
-        """``defer``: see ``_predict_batches`` — the results are complete once every callable appended to it has run."""
-        tail = [] if defer is not None else None
+        """``defer`` (a list): a batch loop that ends with host stages still queued (``_predict_batches``) appends ONE callable to
+        it instead of waiting for them — the results are complete once that callable has run."""
+        tail = None
         try:
             predictions = self.predict_frames(frame_generator, **kwargs)
             self.results.predictions = predictions
         except NoPredictFrames:
-            self._predict_batches(frame_generator, self.results.update, defer=tail, **kwargs)
-        if tail:
+            tail = self._predict_batches(frame_generator, self.results.update, defer=defer, **kwargs)
+        if tail is not None:
             def finish():
-                for f in tail:
-                    f()
+                tail()
                 print(f"{self.__str__()}: {len(self.results)} predictions.")
             defer.append(finish)
         else:

@@ -1,7 +1,15 @@
 """Tracker._predict_batches (host logic, no GPU): the device stage in two halves — batch k + 1 submitted before batch k is
 collected — keeps batch order, bounds the number of live result sets, mixes with batches that have to take the synchronous
 call, and a tracker without the two-call form runs as before."""
+import itertools
+import json
+import os
+import threading
+import timeit
+from pathlib import Path
+
 import numpy as np
+import pytest
 
 from padel_analytics_amd.trackers.tracker import NoPredictFrames, Tracker
 
@@ -276,3 +284,190 @@ def test_runner_collects_a_tracker_tail_after_the_next_tracker_loop(tmp_path):
     r1 = TrackingRunner([a1, b1], "ints://clip", tmp_path / "out.mp4", host_queue_depth=1)
     r1.run()
     assert a1.results.predictions == a.results.predictions and "host_tail_overlapped" not in r1.timings["a"]
+
+
+# ---------------------------------------------------------------------------------------------- call sequences, pinned
+# What the batch loops call, and in which order, is recorded in tests/golden/batch_loop_calls.json.
+# ``PADEL_RECORD_BATCH_LOOP_CALLS=1 pytest tests/test_batch_loop.py`` rewrites the fixture instead of comparing — to be run on
+# the commit whose behaviour is the reference, never to make a failing comparison pass.
+CALLS_FIXTURE = Path(__file__).parent / "golden" / "batch_loop_calls.json"
+RECORD_CALLS = os.environ.get("PADEL_RECORD_BATCH_LOOP_CALLS") == "1"
+_recorded: dict = {}
+
+
+def _check_calls(case: str, have: dict) -> None:
+    have = json.loads(json.dumps(have))                        # (tuples -> lists, as the fixture holds them)
+    if RECORD_CALLS:
+        _recorded[case] = have
+        return
+    assert have == json.loads(CALLS_FIXTURE.read_text())[case], case
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _write_recorded_calls():
+    yield
+    if RECORD_CALLS:
+        CALLS_FIXTURE.write_text(json.dumps(dict(sorted(_recorded.items())), separators=(",", ":")) + "\n")
+
+
+class _N(int):
+    def serialize(self): return int(self)
+
+
+class _Logged(Tracker):
+    """Frames are integers (or handles with an ``index``); ``calls`` is the device thread's log of (call, batch index).
+    ``form``: the two-call device stage is accepted ``always``, declined every ``third`` batch, or ``absent``.  The host stage
+    of batch ``fail`` raises."""
+    streams = False
+
+    def __init__(self, form="always", batch_size=4, name="toy", fail=None, staged=True, delay=0.0):
+        self.form, self.batch_size, self.name, self.fail, self.staged, self.delay = form, batch_size, name, fail, staged, delay
+        self.calls, self.stamps = [], []
+        super().__init__()
+
+    def video_info_post_init(self, video_info): return self
+    def object(self): return _N
+    def draw_kwargs(self): return {}
+    def __str__(self): return self.name
+    def restart(self): self.results.restart()
+    def predict_frames(self, frame_generator, **kw): raise NoPredictFrames()
+
+    def _has_stages(self): return self.staged
+
+    def _frames(self, sample): return [getattr(f, "index", f) for f in sample]
+
+    def _log(self, what, frames):
+        self.calls.append((what, frames[0] // self.batch_size))
+        self.stamps.append(timeit.default_timer())
+
+    def predict_sample(self, sample, **kw):
+        self._log("predict", self._frames(sample))
+        return [_N(f * 10) for f in self._frames(sample)]
+
+    def infer_sample(self, sample, **kw):
+        self._log("infer", self._frames(sample))
+        return self._frames(sample)
+
+    def submit_sample(self, sample, **kw):
+        frames = self._frames(sample)
+        if self.form == "absent" or (self.form == "third" and frames[0] // self.batch_size % 3 == 2):
+            return None
+        self._log("submit", frames)
+        return {"frames": frames}
+
+    def collect_sample(self, token):
+        self._log("collect", token["frames"])
+        return token["frames"]
+
+    def discard_sample(self, token):
+        self._log("discard", token["frames"])
+
+    def post_sample(self, raw, **kw):
+        if self.delay:
+            import time
+            time.sleep(self.delay)
+        if self.fail is not None and raw[0] // self.batch_size == self.fail:
+            raise RuntimeError("host stage failed")
+        return [_N(f * 10) for f in raw]
+
+
+def _loop_record(t, n, defer):
+    """The device-thread log, the order in which ``update`` received the results, and how much of it arrived before
+    ``predict_and_update`` returned (the rest is the tail that was handed over)."""
+    tail = [] if defer else None
+    error = None
+    try:
+        t.predict_and_update(iter(range(n)), defer=tail)
+    except RuntimeError as ex:
+        error = str(ex)
+    at_return = len(t.results.predictions)
+    for f in tail or ():
+        f()
+    assert not t._reuse_outputs
+    return {"device": t.calls, "updates": [int(p) for p in t.results.predictions], "delivered_at_return": at_return,
+            "deferred": len(tail or ()), "error": error}
+
+
+@pytest.mark.parametrize("form,depth,n,defer", list(itertools.product(("always", "third", "absent"), (1, 6), (0, 1, 4, 5, 14), (True, False))))
+def test_call_sequence_of_the_batch_loop_is_the_recorded_one(form, depth, n, defer):
+    t = _Logged(form)
+    t.host_queue_depth = depth
+    have = _loop_record(t, n, defer)
+    assert have["updates"] == [f * 10 for f in range(n)] and have["error"] is None
+    _check_calls(f"loop-{form}-depth{depth}-n{n}-{'defer' if defer else 'own'}", have)
+
+
+@pytest.mark.parametrize("form,depth", list(itertools.product(("always", "third"), (1, 6))))
+def test_call_sequence_when_a_host_stage_raises_is_the_recorded_one(form, depth):
+    """10 batches, the host stage of batch 1 raises: the error surfaces where the queue delivers that batch, and the batch in
+    flight at that moment is discarded."""
+    t = _Logged(form, fail=1)
+    t.host_queue_depth = depth
+    have = _loop_record(t, 38, False)
+    assert have["error"] == "host stage failed" and have["updates"] == [0, 10, 20, 30]
+    assert sum(c[0] == "submit" for c in t.calls) == sum(c[0] in ("collect", "discard") for c in t.calls)
+    _check_calls(f"raise-{form}-depth{depth}", have)
+
+
+def _int_clip(scheme, n, handles=False):
+    from padel_analytics_amd import video
+    frame = (lambda i: video.DeviceFrame(None, i)) if handles else (lambda i: i)
+    video.register_source(scheme, lambda p: video.VideoInfo(8, 8, 30, n),
+                          lambda p, start, end, stride: (frame(i) for i in range(start, n if end is None else min(end, n), stride)))
+    return f"{scheme}://clip"
+
+
+def test_call_sequence_of_the_fanout_loop_is_the_recorded_one(tmp_path):
+    """Two staged trackers with different batch sizes and one without stages over one pass of 26 device-resident frames (uploads
+    of 6): each tracker's own ``infer_sample`` / ``predict_sample`` sequence, and its final results."""
+    from padel_analytics_amd.trackers.runner import TrackingRunner
+    n = 26
+    trackers = [_Logged(batch_size=4, name="x"), _Logged(batch_size=6, name="y"), _Logged(batch_size=3, name="z", staged=False)]
+    TrackingRunner(trackers, _int_clip("handles", n, handles=True), tmp_path / "out.mp4", fanout=True).run()
+    for t in trackers:
+        assert t.results.predictions == [f * 10 for f in range(n)]
+    _check_calls("fanout", {t.name: {"device": t.calls, "updates": [int(p) for p in t.results.predictions]} for t in trackers})
+
+
+def test_a_failing_tail_does_not_orphan_the_next_trackers_tail(tmp_path):
+    """The last host stage of the first tracker raises — inside its tail, which the runner collects after the second tracker's
+    device loop.  ``run()`` raises that error; the second tracker's tail is collected all the same: its results are complete
+    and saved, and neither tracker's worker thread is left alive.  (Before the runner registered a tracker's tail ahead of
+    joining the earlier ones, this failed: the second tracker's queued host stages were never collected.)"""
+    from padel_analytics_amd.trackers.runner import TrackingRunner
+    n = 30                                                      # 8 batches at depth 6: 6 host stages are queued when a loop ends
+    before = set(threading.enumerate())
+    a, b = _Logged(name="a", fail=7, delay=0.002), _Logged(name="b", delay=0.002)
+    b.save_path = tmp_path / "b.json"
+    r = TrackingRunner([a, b], _int_clip("ints", n), tmp_path / "out.mp4", host_queue_depth=6)
+    with pytest.raises(RuntimeError, match="host stage failed"):
+        r.run()
+    assert len(a.results.predictions) == 28                     # (everything before the batch that failed)
+    assert b.results.predictions == [f * 10 for f in range(n)]
+    assert json.loads(b.save_path.read_text()) == [f * 10 for f in range(n)]
+    assert r.timings["b"]["frames"] == n and "host_tail_seconds" in r.timings["b"]
+    assert not [t for t in set(threading.enumerate()) - before if t.is_alive()]
+
+
+def test_only_a_tail_that_drained_beside_another_loop_is_labelled_overlapped(tmp_path):
+    """Two staged trackers at depth 6: the first one's tail drains beside the second one's device loop
+    (``host_tail_overlapped``); the second one's drains alone, so the wait for it belongs to its ``seconds``."""
+    from padel_analytics_amd.trackers.runner import TrackingRunner
+    n = 30
+    a, b = _Logged(name="a"), _Logged(name="b", delay=0.02)
+    r = TrackingRunner([a, b], _int_clip("ints", n), tmp_path / "out.mp4", host_queue_depth=6)
+    r.run()
+    ta, tb = r.timings["a"], r.timings["b"]
+    assert ta.get("host_tail_overlapped") is True and "host_tail_seconds" in ta
+    assert tb.get("host_tail_overlapped") is not True
+    # 6 host stages of 20 ms are queued when b's loop ends, at most one of them already running, and a's tail takes no time:
+    # 100 ms are left to wait for; half of that is asserted
+    assert tb["host_tail_seconds"] >= 0.05
+    device_loop = b.stamps[-1] - b.stamps[0]                    # first submit to last collect: inside what the runner times
+    assert tb["seconds"] >= device_loop + tb["host_tail_seconds"]
+    # depth 1: every loop collects its own host stages; neither key appears
+    a1, b1 = _Logged(name="a"), _Logged(name="b")
+    r1 = TrackingRunner([a1, b1], _int_clip("ints", n), tmp_path / "out.mp4", host_queue_depth=1)
+    r1.run()
+    for name in ("a", "b"):
+        assert "host_tail_overlapped" not in r1.timings[name] and "host_tail_seconds" not in r1.timings[name]
