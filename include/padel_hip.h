@@ -295,6 +295,88 @@ int pa_jpeg_check(int n, int h, int w, const pa_yuv_desc* geom, int quality, cha
 /* host only: the most bytes one restart interval of a frame of width w can take, its closing marker included: a slot's capacity */
 size_t pa_jpeg_interval_bytes(int w);
 
+/* ---- frames from a file: baseline JPEGs (Motion-JPEG: .avi 'MJPG', .mjpeg) in host memory -> packed BGR in HBM (csrc/jpeg_decode.hip) ----
+ * The decoded pixels are specified here: those of libjpeg's default decoder (JDCT_ISLOW, fancy upsampling, JFIF YCbCr -> RGB).  The
+ * readable twin is padel_analytics_amd/mjpeg.py (parse_frame, decode_host), which produces the same bytes; the markers are read by
+ * host-only code (csrc/jpeg_parse.cpp), the entropy decoder is one header for host and device (csrc/jpeg_entropy.h), the arithmetic
+ * another (csrc/jpeg_idct.h).
+ *
+ * Accepted: one SOF0 frame, 8-bit, three components, the first sampled 2 x 2 and the two others 1 x 1; 8-bit DQT; one interleaved scan
+ * over the three components (Ss = 0, Se = 63, Ah = Al = 0); any Huffman tables (ids 0 and 1) in DHT, and WITHOUT any DHT the Annex K
+ * tables (the AVI 'MJPG' convention); DRI of any value, intervals that are not whole MCU rows and RSTm wrapping past 7 included; any
+ * 1 <= w, h <= PA_JPEG_DEC_MAX_DIM in at most PA_JPEG_DEC_MAX_BYTES; APPn / COM and other segments with a length are skipped by it.
+ * Refused, each with its reason:
+ * progressive / extended / lossless / arithmetic SOF, 12- or 16-bit data, another sampling, more than one scan, a truncated header,
+ * a table the scan names but no segment defined, and (pa_jpeg_decode) frame sizes that differ within a call.
+ * A restart interval is found by a scan of the entropy-coded data for FF D0..D7; interval k covers MCUs [k Ri, min((k + 1) Ri, MCUs));
+ * a stream without DRI is one interval.  Intervals the data does not hold are empty; more markers than intervals set PA_JPEG_ST_MARKERS.
+ * Entropy decoding of one interval: bits MSB first, FF 00 is the byte FF, any other FF xx ends the data; bits past the end read as 0.
+ * DC: category (<= 11) + bits, added to the previous block of the component in this interval (0 at its start); AC: run / size symbols
+ * (size <= 10), 00 = end of block, F0 = 16 zeros.  A block that cannot be decoded — a bit pattern no code matches, a category beyond
+ * those limits, a coefficient index past 63, more bits taken than the interval holds — ends its interval: that block and the rest
+ * of the interval's are zero, the reason goes into the frame's status word (PA_JPEG_ST_*), and nothing is read or written out of
+ * bounds: a corrupt frame is reported, never a fault.
+ * Per block, all int32 with wrap-around, >> arithmetic: coefficient k of the zig-zag times the component's quantiser entry k; then
+ * the inverse DCT, one pass over 8 values d0..d7 with descale shift s:
+ *     z1 = (d2 + d6) * 4433; t2 = z1 - d6 * 15137; t3 = z1 + d2 * 6270; t0 = (d0 + d4) << 13; t1 = (d0 - d4) << 13
+ *     t10 = t0 + t3; t13 = t0 - t3; t11 = t1 + t2; t12 = t1 - t2
+ *     a0 = d7; a1 = d5; a2 = d3; a3 = d1; z1 = a0 + a3; z2 = a1 + a2; z3 = a0 + a2; z4 = a1 + a3; z5 = (z3 + z4) * 9633
+ *     a0 *= 2446; a1 *= 16819; a2 *= 25172; a3 *= 12299; z1 *= -7373; z2 *= -20995; z3 = z3 * -16069 + z5; z4 = z4 * -3196 + z5
+ *     a0 += z1 + z3; a1 += z2 + z4; a2 += z2 + z3; a3 += z1 + z4
+ *     out = (t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3), each (x + (1 << (s - 1))) >> s
+ * over the columns first (s = 11), then over the rows (s = 18); the sample is clamp(x + 128, 0, 255).  (libjpeg's table wraps instead
+ * of clamping once |x| >= 384; below that the two agree.)
+ * Chroma ("h2v2 fancy"), on the plane of its real size ceil(h / 2) x ceil(w / 2), indices clamped to it: for output row 2 r + v,
+ * s[c] = 3 C[r][c] + C[r'][c], r' = r - 1 (v = 0) or r + 1 (v = 1); out[2 c] = (3 s[c] + s[c - 1] + 8) >> 4,
+ * out[2 c + 1] = (3 s[c] + s[c + 1] + 7) >> 4; cropped to h x w.
+ * Colour, cb -= 128, cr -= 128: R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ * G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), each clamped to 0..255, stored B, G, R.                                       */
+#define PA_JPEG_DEC_MAX_DIM 4096
+#define PA_JPEG_DEC_MAX_BYTES (1 << 27)   /* of one frame */
+enum { PA_JPEG_ST_CODE = 1, PA_JPEG_ST_INDEX = 2, PA_JPEG_ST_SIZE = 4, PA_JPEG_ST_DATA = 8, PA_JPEG_ST_MARKERS = 16 };
+typedef struct pa_jpeg_huff {
+    uint8_t bits[16];       /* codes per length 1..16 */
+    uint8_t vals[256];      /* symbols in code order */
+    int32_t nvals;
+} pa_jpeg_huff;
+typedef struct pa_jpeg_interval {
+    int64_t begin, end;     /* entropy-coded bytes [begin, end) from the start of the frame, markers excluded */
+    int32_t first_mcu, mcus;
+} pa_jpeg_interval;
+typedef struct pa_jpeg_frame_info {
+    int32_t w, h, mcus_x, mcus_y;
+    int32_t restart_interval;   /* DRI, 0: none */
+    int32_t n_intervals;
+    int32_t default_huffman;    /* 1: the frame has no DHT, the Annex K tables stand in */
+    int32_t status;             /* 0 or PA_JPEG_ST_MARKERS */
+    int64_t scan_begin, scan_end;   /* the entropy-coded data: behind SOS .. the marker that ends it (or the end of the bytes) */
+    uint8_t quant[3][64];       /* per component, zig-zag order */
+    uint8_t comp_dc[3], comp_ac[3], pad_[2];   /* per component: index into dc[] / ac[] */
+    pa_jpeg_huff dc[2], ac[2];
+} pa_jpeg_frame_info;
+/* host only (no engine, no GPU): the markers of one frame -> its description and the first ivl_cap entries of its interval table
+ * (info->n_intervals says how many there are).  Non-zero: refused, the reason in why[0 .. cap).                              */
+int pa_jpeg_parse(const uint8_t* jpeg, size_t len, pa_jpeg_frame_info* info, pa_jpeg_interval* ivls, size_t ivl_cap, char* why,
+                  size_t cap);
+/* n JPEGs, frame i at jpegs_host[offsets[i] .. offsets[i + 1]) (offsets: n + 1 entries), all h x w -> packed BGR frames at
+ * dst_bgr_dev (HBM, n * h * w * 3 bytes, any alignment), status_host[i] = 0 or the PA_JPEG_ST_* bits of frame i.  0 on success — a
+ * frame with a non-zero status is still a success of the call.  Refused, nothing launched, the reason in pa_last_error: what
+ * pa_jpeg_parse refuses (with the frame's index) and a frame whose size is not h x w.  SYNCHRONOUS, on the engine's compute stream
+ * (a reader of dst queued earlier is ahead of it, nothing runs on another stream).  Three kernels: one wave per restart interval
+ * decodes it to int16 coefficients, one thread per block dequantises and inverts the DCT into padded planes, a third pass
+ * upsamples and converts.  The scratch (compressed bytes, coefficients, planes: 4.5 bytes per pixel of the padded frame) belongs
+ * to the engine, grows on demand and is freed with it; at most 64 frames or 256 MiB of it are in use at a time (larger calls are
+ * decoded in sub-batches inside the call).  A stream without restart markers is one interval: one wave per frame.            */
+int pa_jpeg_decode(pa_engine* eng, const uint8_t* jpegs_host, const int64_t* offsets, int n, int h, int w, uint8_t* dst_bgr_dev,
+                   int32_t* status_host);
+/* tests: 1 if the last successful pa_jpeg_decode wrote its pixels with 16-byte stores (w a multiple of 16 and dst 16-byte aligned),
+ * 2 if with byte stores, 0: none yet                                                                                          */
+int pa_jpeg_decode_last_path(pa_engine* eng);
+/* tools: while profiling is on (pa_engine_set_profiling) a pa_jpeg_decode also times its stages; ms[0 .. 5) of the last such call:
+ * reading the markers of all frames (host clock), the upload of the compressed bytes and tables, the entropy pass, the IDCT pass,
+ * the colour pass (HIP events on the compute stream, summed over the call's sub-batches)                                     */
+int pa_jpeg_decode_last_times(pa_engine* eng, double ms[5]);
+
 /* tools: device time of whatever is queued on the engine's compute stream between the two calls, from a pair of HIP events
  * recorded on that stream (tools/yuv_bench.py times the asynchronous pa_yuv420_to_bgr with it).  pa_engine_timer_stop waits for
  * its event and returns the milliseconds between the two.                                                              */

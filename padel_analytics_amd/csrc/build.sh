@@ -13,9 +13,9 @@ OUT="${PADEL_OUT:-../libpadel_hip.so}"
 mkdir -p "$BUILD"
 pids=()
 # PADEL_ONLY="a.hip b.hip": recompile only these translation units and relink with the objects already in $BUILD (iteration)
-ALL="conv_tap.hip conv_tap16.hip conv_tap_bx3.hip conv_patch_bx3.hip conv_tap_h2.hip conv_tap_h2p.hip conv_1x1_h2s.hip conv_patch_h2.hip conv_patch_h2q.hip conv_patch_h2r.hip conv_patch_h2v.hip conv_patch_h2w.hip conv_patch16.hip kernels_misc.hip resnet_ops.hip yolo11_ops.hip stem_l1_h2.hip postproc.hip tracknet_post.hip yuv_convert.hip render.hip jpeg_encode.hip"
+ALL="conv_tap.hip conv_tap16.hip conv_tap_bx3.hip conv_patch_bx3.hip conv_tap_h2.hip conv_tap_h2p.hip conv_1x1_h2s.hip conv_patch_h2.hip conv_patch_h2q.hip conv_patch_h2r.hip conv_patch_h2v.hip conv_patch_h2w.hip conv_patch16.hip kernels_misc.hip resnet_ops.hip yolo11_ops.hip stem_l1_h2.hip postproc.hip tracknet_post.hip yuv_convert.hip render.hip jpeg_encode.hip jpeg_decode.hip"
 # the engine (host code that calls the HIP runtime), one translation unit per concern: engine_internal.h
-ENGINE="engine.cpp engine_pre.cpp engine_yolo.cpp engine_tracknet.cpp engine_resnet.cpp engine_comm.cpp engine_render.cpp engine_jpeg.cpp"
+ENGINE="engine.cpp engine_pre.cpp engine_yolo.cpp engine_tracknet.cpp engine_resnet.cpp engine_comm.cpp engine_render.cpp engine_jpeg.cpp engine_jpeg_decode.cpp"
 for f in ${PADEL_ONLY:-$ALL $ENGINE}; do
   [ -f "$f" ] || continue
   case "$f" in
@@ -39,6 +39,9 @@ g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c render_check.cpp -o "$BUILD/
 pids+=($!)
 # what pa_jpeg_encode refuses, its tables, header and sizes: no HIP either (jpeg_tables.h also builds into tests/jpeg_tables_main.cpp's program)
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c jpeg_check.cpp -o "$BUILD/jpeg_check.o" &
+pids+=($!)
+# the markers of a JPEG that pa_jpeg_decode reads, and pa_jpeg_parse: no HIP either (the same file builds into tests/jpeg_decode_main.cpp's program)
+g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c jpeg_parse.cpp -o "$BUILD/jpeg_parse.o" &
 pids+=($!)
 fi
 for p in "${pids[@]}"; do wait "$p"; done

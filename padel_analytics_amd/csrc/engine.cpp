@@ -90,6 +90,7 @@ void pa_engine_destroy(pa_engine* e) {
     if (e->yuv_stage) { if (e->stream) hipStreamSynchronize(e->stream); hipFree(e->yuv_stage); }
     if (e->render_stage) { if (e->stream) hipStreamSynchronize(e->stream); hipFree(e->render_stage); }
     jpeg_scratch_free(e);
+    jpeg_dec_scratch_free(e);
     for (hipEvent_t ev : e->timer_ev) if (ev) hipEventDestroy(ev);
     if (e->stream) hipStreamDestroy(e->stream);
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);

@@ -6,6 +6,7 @@
 //   engine_resnet.cpp    the ResNet-50 court-keypoint regressor
 //   engine_render.cpp    pa_render: marks on BGR frames -> BGR / YUV 4:2:0 (the refusals and the font: render_check.cpp, host only)
 //   engine_jpeg.cpp      pa_jpeg_encode: YUV 4:2:0 frames in HBM -> baseline JPEGs in host memory (the refusals, tables and header: jpeg_check.cpp, host only)
+//   engine_jpeg_decode.cpp  pa_jpeg_decode: baseline JPEGs in host memory -> BGR frames in HBM (the markers: jpeg_parse.cpp, host only)
 //   engine_comm.cpp      RCCL
 // What is decided about a graph on the host alone lives in graph_plan.cpp, which kernel runs a conv in conv_select.cpp.
 #pragma once
@@ -47,6 +48,7 @@ struct Tuning {
 
 struct pa_comm;
 struct JpegScratch;
+struct JpegDecScratch;
 
 struct pa_engine {
     int dev = 0;
@@ -65,6 +67,8 @@ struct pa_engine {
     uint8_t* render_stage = nullptr; size_t render_stage_cap = 0;   // pa_render: the resolved marks and first[] of the call in flight, filled and read on `stream` only
     int render_last_path = 0; // 1 vector, 2 byte: what the last pa_render launched (pa_render_last_path)
     JpegScratch* jpeg = nullptr;   // pa_jpeg_encode: slots, tables and the gathered frames, grown on demand, used on `stream` only (engine_jpeg.cpp)
+    JpegDecScratch* jpeg_dec = nullptr;   // pa_jpeg_decode: compressed bytes, tables, coefficients and planes, likewise (engine_jpeg_decode.cpp)
+    int jpeg_dec_last_path = 0;    // 1 vector, 2 byte: what the last pa_jpeg_decode launched for its colour pass (pa_jpeg_decode_last_path)
 };
 
 extern thread_local std::string g_err;      // errors of calls that have no engine yet (pa_last_error(NULL))
@@ -165,6 +169,9 @@ int run_graph(pa_model* m, int n, size_t* pi);
 
 // ---- engine_jpeg.cpp
 void jpeg_scratch_free(pa_engine* e);                 // waits for the stream first
+
+// ---- engine_jpeg_decode.cpp
+void jpeg_dec_scratch_free(pa_engine* e);             // waits for the stream first
 
 // ---- engine_pre.cpp
 hipError_t upload_table(pa_engine* e, int32_t** dptr, const std::vector<int32_t>& v);

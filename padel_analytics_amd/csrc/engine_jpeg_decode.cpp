@@ -1,0 +1,157 @@
+// pa_jpeg_decode: baseline JPEGs in host memory -> packed BGR frames in HBM (jpeg_decode.hip).  The markers are read by host-only
+// code (jpeg_parse.cpp); what reaches the device is the compressed bytes as they are, one table block per frame and the interval table.
+#include "engine_internal.h"
+#include "jpeg_decode.h"
+#include "jpeg_parse.h"
+
+#include <chrono>
+
+// Scratch of the call in flight, grown on demand, freed with the engine; filled and read on the compute stream only.
+struct JpegDecScratch {
+    uint8_t* data = nullptr; size_t data_cap = 0;                // compressed bytes of a sub-batch
+    JpegDecFrame* frames = nullptr; size_t frames_cap = 0;       // bytes
+    JpegDecInterval* ivls = nullptr; size_t ivls_cap = 0;        // bytes
+    int32_t* status = nullptr; size_t status_cap = 0;            // bytes: one word per interval
+    int16_t* coef = nullptr; size_t coef_cap = 0;                // bytes
+    uint8_t* planes = nullptr; size_t planes_cap = 0;
+    hipEvent_t ev[5]{};                                          // profiling: in front of the upload, of (a), (b), (c), behind (c)
+    double ms[5]{};                                              // of the last call while profiling: parse (host clock), upload, (a), (b), (c)
+};
+
+// coefficients and planes of one sub-batch stay under this many bytes (one frame's where a single frame needs more), and a sub-batch
+// has at most this many frames
+static const size_t kDecBudget = (size_t)256 << 20;
+static const int kDecMaxSub = 64;
+
+void jpeg_dec_scratch_free(pa_engine* e) {
+    if (!e->jpeg_dec) return;
+    if (e->stream) hipStreamSynchronize(e->stream);
+    JpegDecScratch* s = e->jpeg_dec;
+    if (s->data) hipFree(s->data);
+    if (s->frames) hipFree(s->frames);
+    if (s->ivls) hipFree(s->ivls);
+    if (s->status) hipFree(s->status);
+    if (s->coef) hipFree(s->coef);
+    if (s->planes) hipFree(s->planes);
+    for (hipEvent_t ev : s->ev) if (ev) hipEventDestroy(ev);
+    delete s;
+    e->jpeg_dec = nullptr;
+}
+
+// *p holds at least `need` bytes afterwards; its contents are not kept (the stream is idle: the caller has synchronised)
+template <class T> static int fit(pa_engine* e, T** p, size_t* cap, size_t need) {
+    if (*cap >= need) return 0;
+    if (*p) hipFree(*p);
+    *p = nullptr; *cap = 0;
+    need += need / 4;
+    PA_HIP(e, hipMalloc((void**)p, need));
+    *cap = need;
+    return 0;
+}
+
+int pa_jpeg_decode(pa_engine* e, const uint8_t* jpegs, const int64_t* offsets, int n, int h, int w, uint8_t* dst, int32_t* status_host) {
+    if (!e) return 1;
+    if (!jpegs || !offsets || !dst || !status_host) PA_FAIL(e, "pa_jpeg_decode: jpegs_host, offsets, dst_bgr_dev or status_host is NULL");
+    if (n < 1) PA_FAIL(e, "pa_jpeg_decode: n = %d frames", n);
+    if (w < 1 || h < 1 || w > PA_JPEG_DEC_MAX_DIM || h > PA_JPEG_DEC_MAX_DIM)
+        PA_FAIL(e, "pa_jpeg_decode: %d x %d frames outside 1 .. %d pixels a side", w, h, PA_JPEG_DEC_MAX_DIM);
+    for (int i = 0; i < n; ++i)
+        if (offsets[i] < 0 || offsets[i + 1] < offsets[i]) PA_FAIL(e, "pa_jpeg_decode: offsets[%d .. %d] = %lld, %lld do not ascend", i, i + 1, (long long)offsets[i], (long long)offsets[i + 1]);
+    // every frame is parsed before anything is launched: a refusal leaves dst untouched
+    std::vector<pa_jpeg_frame_info> infos((size_t)n);
+    std::vector<std::vector<pa_jpeg_interval>> tables((size_t)n);
+    std::string why;
+    const auto parse_t0 = std::chrono::steady_clock::now();
+    for (int i = 0; i < n; ++i) {
+        if (jpeg_parse_frame(jpegs + offsets[i], (size_t)(offsets[i + 1] - offsets[i]), &infos[(size_t)i], tables[(size_t)i], why))
+            PA_FAIL(e, "pa_jpeg_decode: frame %d: %s", i, why.c_str());
+        if (infos[(size_t)i].w != w || infos[(size_t)i].h != h)
+            PA_FAIL(e, "pa_jpeg_decode: frame %d is %d x %d, the call says %d x %d: frame sizes differ within the clip", i, infos[(size_t)i].w, infos[(size_t)i].h, w, h);
+    }
+    const double parse_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - parse_t0).count();
+    PA_HIP(e, hipSetDevice(e->dev));
+    if (!e->jpeg_dec) e->jpeg_dec = new JpegDecScratch();
+    JpegDecScratch* s = e->jpeg_dec;
+    const bool timed = e->profiling;
+    if (timed) {
+        for (hipEvent_t& ev : s->ev)
+            if (!ev) PA_HIP(e, hipEventCreate(&ev));
+        for (double& v : s->ms) v = 0;
+        s->ms[0] = parse_ms;
+    }
+    const int mcus_x = jpeg::mcus_per_row(w), mcus_y = jpeg::mcu_rows(h);
+    const size_t mcus = (size_t)mcus_x * mcus_y;
+    const size_t coef_frame = mcus * jpeg::kBlocksPerMcu * 64 * sizeof(int16_t), planes_frame = mcus * 384;
+    const int sub = (int)std::max<size_t>(1, std::min<size_t>(std::min(n, kDecMaxSub), kDecBudget / (coef_frame + planes_frame)));
+
+    std::vector<JpegDecFrame> frames;
+    std::vector<JpegDecInterval> ivls;
+    std::vector<int32_t> ivl_status;
+    for (int f0 = 0; f0 < n; f0 += sub) {
+        const int nf = std::min(sub, n - f0);
+        const int64_t base = offsets[f0];
+        const size_t bytes = (size_t)(offsets[f0 + nf] - base);
+        frames.assign((size_t)nf, JpegDecFrame{});
+        ivls.clear();
+        for (int i = 0; i < nf; ++i) {
+            const pa_jpeg_frame_info& in = infos[(size_t)(f0 + i)];
+            JpegDecFrame& fr = frames[(size_t)i];
+            for (int t = 0; t < 2; ++t) {
+                jpeg::huff_dec_build(in.dc[t].bits, in.dc[t].vals, in.dc[t].nvals, &fr.dc[t]);
+                jpeg::huff_dec_build(in.ac[t].bits, in.ac[t].vals, in.ac[t].nvals, &fr.ac[t]);
+            }
+            for (int c = 0; c < 3; ++c) {
+                for (int k = 0; k < 64; ++k) fr.quant[c][k] = in.quant[c][k];
+                fr.comp_dc[c] = in.comp_dc[c];
+                fr.comp_ac[c] = in.comp_ac[c];
+            }
+            const int64_t at = offsets[f0 + i] - base;
+            for (const pa_jpeg_interval& v : tables[(size_t)(f0 + i)])
+                ivls.push_back({(long long)(at + v.begin), (long long)(at + v.end), i, v.first_mcu, v.mcus, 0});
+        }
+        const size_t need_f = frames.size() * sizeof(JpegDecFrame), need_i = ivls.size() * sizeof(JpegDecInterval);
+        const size_t need_s = ivls.size() * sizeof(int32_t);
+        if (s->data_cap < bytes + 16 || s->frames_cap < need_f || s->ivls_cap < need_i || s->status_cap < need_s ||
+            s->coef_cap < coef_frame * nf || s->planes_cap < planes_frame * nf) {
+            PA_HIP(e, hipStreamSynchronize(e->stream));          // a decode still queued uses what is about to go
+            if (fit(e, &s->data, &s->data_cap, bytes + 16) || fit(e, &s->frames, &s->frames_cap, need_f) ||
+                fit(e, &s->ivls, &s->ivls_cap, need_i) || fit(e, &s->status, &s->status_cap, need_s) ||
+                fit(e, &s->coef, &s->coef_cap, coef_frame * nf) || fit(e, &s->planes, &s->planes_cap, planes_frame * nf))
+                return 1;
+        }
+        // (pageable sources: the runtime has consumed them when hipMemcpyAsync returns; an earlier sub-batch's kernels are ahead in the stream)
+        if (timed) PA_HIP(e, hipEventRecord(s->ev[0], e->stream));
+        if (bytes) PA_HIP(e, hipMemcpyAsync(s->data, jpegs + base, bytes, hipMemcpyHostToDevice, e->stream));
+        PA_HIP(e, hipMemcpyAsync(s->frames, frames.data(), need_f, hipMemcpyHostToDevice, e->stream));
+        PA_HIP(e, hipMemcpyAsync(s->ivls, ivls.data(), need_i, hipMemcpyHostToDevice, e->stream));
+        JpegDecArgs a{};
+        a.data = s->data; a.ivls = s->ivls; a.frames = s->frames; a.coef = s->coef; a.ivl_status = s->status; a.planes = s->planes;
+        a.dst = dst + (size_t)f0 * h * w * 3;
+        a.n = nf; a.n_ivls = (int)ivls.size(); a.h = h; a.w = w; a.mcus_x = mcus_x; a.mcus_y = mcus_y;
+        int path = 0;
+        const hipError_t r = launch_jpeg_decode(a, &path, e->stream, timed ? s->ev + 1 : nullptr);
+        if (r != hipSuccess) PA_FAIL(e, "jpeg decode launch failed: %s", hipGetErrorString(r));
+        e->jpeg_dec_last_path = path;
+        ivl_status.resize(ivls.size());
+        PA_HIP(e, hipMemcpyAsync(ivl_status.data(), s->status, need_s, hipMemcpyDeviceToHost, e->stream));
+        PA_HIP(e, hipStreamSynchronize(e->stream));
+        if (timed)
+            for (int k = 0; k < 4; ++k) {
+                float ms = 0;
+                PA_HIP(e, hipEventElapsedTime(&ms, s->ev[k], s->ev[k + 1]));
+                s->ms[k + 1] += ms;
+            }
+        for (int i = 0; i < nf; ++i) status_host[f0 + i] = infos[(size_t)(f0 + i)].status;
+        for (size_t k = 0; k < ivls.size(); ++k) status_host[f0 + ivls[k].frame] |= ivl_status[k];
+    }
+    return 0;
+}
+
+int pa_jpeg_decode_last_path(pa_engine* e) { return e ? e->jpeg_dec_last_path : 0; }
+
+int pa_jpeg_decode_last_times(pa_engine* e, double ms[5]) {
+    if (!e) return 1;
+    if (!e->jpeg_dec || !ms) PA_FAIL(e, "pa_jpeg_decode_last_times: no pa_jpeg_decode has run on this engine");
+    for (int k = 0; k < 5; ++k) ms[k] = e->jpeg_dec->ms[k];
+    return 0;
+}

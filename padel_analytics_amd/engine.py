@@ -118,6 +118,7 @@ ABI_SYMBOLS = [
     "pa_yuv420_to_bgr", "pa_yuv_last_path", "pa_engine_timer_start", "pa_engine_timer_stop",
     "pa_render", "pa_render_check", "pa_render_last_path", "pa_glyph_rows", "pa_ball_read_resized",
     "pa_jpeg_encode", "pa_jpeg_check", "pa_jpeg_interval_bytes",
+    "pa_jpeg_parse", "pa_jpeg_decode", "pa_jpeg_decode_last_path", "pa_jpeg_decode_last_times",
 ]
 
 
@@ -212,6 +213,10 @@ def load_library():
     lib.pa_jpeg_check.argtypes = [i32, i32, i32, C.POINTER(pa_yuv_desc), i32, C.c_char_p, sz]
     lib.pa_jpeg_interval_bytes.argtypes = [i32]
     lib.pa_jpeg_interval_bytes.restype = sz
+    lib.pa_jpeg_parse.argtypes = [vp, sz, C.POINTER(pa_jpeg_frame_info), vp, sz, C.c_char_p, sz]
+    lib.pa_jpeg_decode.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.pa_jpeg_decode_last_path.argtypes = [vp]
+    lib.pa_jpeg_decode_last_times.argtypes = [vp, vp]
     lib.pa_engine_timer_start.argtypes = [vp]
     lib.pa_engine_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
     if lib.pa_abi_version() != 5:
@@ -308,6 +313,46 @@ def jpeg_interval_bytes(w: int) -> int:
     """The most bytes one restart interval (one MCU row) of a JPEG of width ``w`` can take — the capacity of the slot the encode
     kernel writes it to (``pa_jpeg_interval_bytes``: host code, no GPU)."""
     return int(load_library().pa_jpeg_interval_bytes(int(w)))
+
+
+#: ``pa_jpeg_parse`` / ``pa_jpeg_decode`` refuse larger frames (PA_JPEG_DEC_MAX_DIM)
+JPEG_DEC_MAX_DIM = 4096
+#: ``Engine.jpeg_decode_last_path()``: how the colour pass of the last decode stored its pixels
+JPEG_DEC_PATH_VECTOR, JPEG_DEC_PATH_BYTE = 1, 2
+
+
+class pa_jpeg_huff(C.Structure):
+    _fields_ = [("bits", C.c_uint8 * 16), ("vals", C.c_uint8 * 256), ("nvals", C.c_int32)]
+
+
+class pa_jpeg_interval(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("first_mcu", C.c_int32), ("mcus", C.c_int32)]
+
+
+class pa_jpeg_frame_info(C.Structure):
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("restart_interval", C.c_int32),
+                ("n_intervals", C.c_int32), ("default_huffman", C.c_int32), ("status", C.c_int32), ("scan_begin", C.c_int64),
+                ("scan_end", C.c_int64), ("quant", (C.c_uint8 * 64) * 3), ("comp_dc", C.c_uint8 * 3), ("comp_ac", C.c_uint8 * 3),
+                ("pad_", C.c_uint8 * 2), ("dc", pa_jpeg_huff * 2), ("ac", pa_jpeg_huff * 2)]
+
+
+def jpeg_parse(jpeg) -> dict:
+    """The description ``pa_jpeg_parse`` gives of one baseline JPEG (host code, no GPU), in the form of ``mjpeg.parse_frame``;
+    ``ValueError`` with the library's reason for what it refuses."""
+    raw = np.frombuffer(bytes(jpeg), np.uint8)
+    info, why = pa_jpeg_frame_info(), C.create_string_buffer(512)
+    lib = load_library()
+    if lib.pa_jpeg_parse(raw.ctypes.data, raw.size, C.byref(info), None, 0, why, 512):
+        raise ValueError(why.value.decode())
+    ivls = (pa_jpeg_interval * max(info.n_intervals, 1))()
+    if lib.pa_jpeg_parse(raw.ctypes.data, raw.size, C.byref(info), ivls, info.n_intervals, why, 512):
+        raise ValueError(why.value.decode())
+    table = lambda t: (list(t.bits), list(t.vals)[:t.nvals])
+    return dict(w=info.w, h=info.h, mcus_x=info.mcus_x, mcus_y=info.mcus_y, restart_interval=info.restart_interval,
+                n_intervals=info.n_intervals, default_huffman=info.default_huffman, status=info.status, scan_begin=info.scan_begin,
+                scan_end=info.scan_end, quant=np.array([list(q) for q in info.quant], np.uint8), comp_dc=list(info.comp_dc),
+                comp_ac=list(info.comp_ac), dc=[table(t) for t in info.dc], ac=[table(t) for t in info.ac],
+                intervals=[(v.begin, v.end, v.first_mcu, v.mcus) for v in ivls[:info.n_intervals]])
 
 
 class DeviceBuffer:
@@ -466,6 +511,44 @@ class Engine:
                 err.needed = needed if needed > out.size else None
                 raise err
             out = np.empty(needed, np.uint8)
+
+    def jpeg_decode(self, data, offsets, dst: DeviceBuffer, h: Optional[int] = None, w: Optional[int] = None) -> np.ndarray:
+        """The baseline JPEGs ``data[offsets[i]:offsets[i + 1]]`` (``data``: a 1-D uint8 array or bytes in host memory; all frames of one
+        size, 4:2:0) -> packed BGR frames in ``dst``, decoded on the GPU (``pa_jpeg_decode``; the same bytes as ``mjpeg.decode_host``).
+        Returns the status words (n,) int32: 0, or the ``mjpeg.ST_*`` bits of a frame whose entropy-coded data is damaged — such a
+        frame is reported, its undecodable intervals are grey, and the call succeeds.  The frame size is read from the first JPEG
+        unless ``h`` and ``w`` say what it has to be (a clip that knows its size).
+        Synchronous, on the engine's compute stream.  What the library refuses is an ``EngineError``, nothing is launched."""
+        data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data
+        if not (isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.ndim == 1 and data.flags.c_contiguous):
+            raise TypeError("jpeg_decode: data must be bytes or a contiguous 1-D uint8 array")
+        offsets = np.ascontiguousarray(offsets, np.int64)
+        n = offsets.size - 1
+        if n < 1 or offsets[0] < 0 or np.any(np.diff(offsets) < 0) or offsets[-1] > data.size:
+            raise EngineError(f"jpeg_decode: offsets must be n + 1 >= 2 ascending positions inside the {data.size} bytes of data")
+        if h is None or w is None:
+            try:
+                info = jpeg_parse(data[int(offsets[0]):int(offsets[1])].tobytes())
+            except ValueError as e:
+                raise EngineError(f"jpeg_decode: frame 0: {e}") from None
+            h, w = info["h"], info["w"]
+        h, w = int(h), int(w)
+        if dst.nbytes < n * h * w * 3:
+            raise EngineError(f"jpeg_decode: dst holds {dst.nbytes} bytes, {n} BGR frames of {w} x {h} need {n * h * w * 3}")
+        status = np.zeros(n, np.int32)
+        self._check(self.lib.pa_jpeg_decode(self.handle, data.ctypes.data, offsets.ctypes.data, n, h, w, dst.ptr, status.ctypes.data))
+        return status
+
+    def jpeg_decode_last_path(self) -> int:
+        """JPEG_DEC_PATH_VECTOR / JPEG_DEC_PATH_BYTE: how the last successful ``jpeg_decode`` stored its pixels (0: none yet)."""
+        return int(self.lib.pa_jpeg_decode_last_path(self.handle))
+
+    def jpeg_decode_last_times(self) -> dict:
+        """Tools: milliseconds the stages of the last ``jpeg_decode`` took while ``set_profiling(True)`` was on — ``parse`` (host clock),
+        ``upload``, ``entropy``, ``idct``, ``colour`` (HIP events)."""
+        ms = (C.c_double * 5)()
+        self._check(self.lib.pa_jpeg_decode_last_times(self.handle, ms))
+        return dict(zip(("parse", "upload", "entropy", "idct", "colour"), (float(v) for v in ms)))
 
     def timer_start(self) -> None:
         """Tools: mark the compute stream with a HIP event; ``timer_stop`` -> milliseconds of device time queued since."""

@@ -467,7 +467,8 @@ class TrackingRunner:
         t0 = timeit.default_timer()
 
         def batches():
-            """Batches of frames resident in HBM: device clips and YUV clips pass through; host frames are uploaded once per
+            """Batches of frames resident in HBM: device clips, YUV clips and Motion-JPEG clips (their ``MjpegFrame`` handles are
+            ``YuvFrame``s) pass through; host frames are uploaded once per
             batch into one of two staging clips, the next upload overlapping this batch's compute."""
             gen = self._frames()
             first = next(gen, None)
@@ -478,7 +479,7 @@ class TrackingRunner:
                     yield first
                     yield from gen
                 for sample in _sampler(chain(), bs):
-                    # YUV clips: one conversion per batch into the clip's own BGR staging (no host_batch, no second staging
+                    # YUV / Motion-JPEG clips: one conversion or decode per batch into the clip's own BGR staging (no host_batch, no second staging
                     # clip) — every tracker's device_batch over this batch or a part of it then finds the frames converted
                     if isinstance(first, video.YuvFrame):
                         video.device_batch(sample)

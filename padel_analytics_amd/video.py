@@ -10,7 +10,10 @@ what decoders, capture cards and ``ffmpeg -f rawvideo`` actually emit, 1.5 bytes
 memory, any pitch / padded plane height / gap between frames), ``DeviceYuvClip`` (the same bytes resident in HBM: a hardware
 decoder's surfaces) and ``.y4m`` files by path (``YuvClip.from_y4m``: the one self-describing raw format, no codec).  Their
 frames are ``YuvFrame`` handles; ``device_batch`` converts a batch to BGR on the GPU (csrc/yuv_convert.hip), ``host_batch`` /
-``np.asarray(frame)`` on the host with the same integer formula (``yuv420_to_bgr_host``).
+``np.asarray(frame)`` on the host with the same integer formula (``yuv420_to_bgr_host``), (f) Motion-JPEG — ``.avi`` files with an
+``MJPG`` stream, raw ``.mjpeg`` / ``.mjpg`` files, by path or as ``MjpegClip``: what ``MjpegSink`` writes, ``ffmpeg -c:v mjpeg``
+produces from anything and capture cards emit.  Only the compressed bytes are uploaded; the frames are decoded to BGR on the GPU
+(csrc/jpeg_decode.hip) into the clip's staging buffer, or on the host by the numpy twin ``mjpeg.decode_host``.
 Frames are HWC uint8 **BGR**, exactly what supervision yields."""
 from __future__ import annotations
 
@@ -53,7 +56,7 @@ class VideoInfo:
 
     @classmethod
     def from_video_path(cls, video_path) -> "VideoInfo":
-        if isinstance(video_path, (DeviceClip, ArrayClip, _YuvSource)):
+        if isinstance(video_path, (DeviceClip, ArrayClip, _StagedSource)):
             return cls(video_path.w, video_path.h, video_path.fps, video_path.total_frames)
         p = str(video_path)
         src = _scheme(p)
@@ -65,6 +68,9 @@ class VideoInfo:
         if p.endswith(".npy"):
             a = np.load(p, mmap_mode="r")
             return cls(int(a.shape[2]), int(a.shape[1]), 30, int(a.shape[0]))
+        c = _open_mjpeg(p)
+        if c is not None:
+            return cls(c.w, c.h, c.fps, c.total_frames)
         cv2 = _cv2()
         cap = cv2.VideoCapture(p)
         if not cap.isOpened():
@@ -80,7 +86,8 @@ def _cv2():
         import cv2
         return cv2
     except ImportError as e:
-        raise RuntimeError("reading encoded video needs opencv-python, which is not installed; use a .npy frame "
+        raise RuntimeError("reading encoded video needs opencv-python, which is not installed; use a Motion-JPEG file (.avi with an "
+                           "'MJPG' stream, .mjpeg, .mjpg: `ffmpeg -i in.mp4 -c:v mjpeg -q:v 3 out.avi`), a .y4m file, a .npy frame "
                            "stack or a registered frame source") from e
 
 
@@ -323,11 +330,12 @@ def bgr_to_yuv420_host(frames: np.ndarray, desc, enc, out: Optional[np.ndarray] 
 
 
 class YuvFrame:
-    """Handle of one frame of a YUV clip (stored frame ``index`` of ``clip``).  ``.shape`` is the BGR frame's; ``np.asarray(f)`` /
+    """Handle of one frame of a YUV clip — or of any clip whose frames become BGR on their way to the trackers (``MjpegClip`` hands
+    out its subclass ``MjpegFrame``) — stored frame ``index`` of ``clip``.  ``.shape`` is the BGR frame's; ``np.asarray(f)`` /
     ``f.bgr()`` convert it on the host; a batch of them goes through ``device_batch`` / ``host_batch``."""
     __slots__ = ("clip", "index")
 
-    def __init__(self, clip: "_YuvSource", index: int):
+    def __init__(self, clip: "_StagedSource", index: int):
         self.clip, self.index = clip, index
 
     @property
@@ -342,48 +350,32 @@ class YuvFrame:
         return a if dtype is None else a.astype(dtype)
 
 
-class _YuvSource:
-    """What ``YuvClip`` and ``DeviceYuvClip`` share: the geometry, the frame handles, the BGR staging buffer in HBM and the
-    memory of which stored range it holds."""
+class _StagedSource:
+    """A clip of ``n`` stored frames (presented ``repeat`` times over) that reach the trackers as BGR through one staging buffer in
+    HBM: the frame handles, the staging buffer and the memory of which stored range it holds.  A subclass says how a range gets
+    there (``_to_device``, through the engine method named ``_engine_call``) and what it is on the host (``host_bgr``)."""
+    _engine_call = "yuv420_to_bgr"
+    _frame_type = YuvFrame
 
-    def _init_geometry(self, nbytes: int, w, h, layout, matrix, range, pitch, pitch_c, off_u, off_v, frame_stride, header_bytes, n,
-                       fps, repeat, coeffs=None) -> None:
-        self.w, self.h = int(w), int(h)
-        self.layout = layout
-        self.desc = yuv_desc(w, h, layout, matrix, range, pitch, pitch_c, off_u, off_v, frame_stride, coeffs)
-        self.header_bytes = int(header_bytes)
-        self.frame_stride = self.desc["frame_stride"]
-        self.extent = yuv_span(1, self.h, self.w, self.desc)
-        fit = (nbytes - self.header_bytes - self.extent) // self.frame_stride + 1 if nbytes - self.header_bytes >= self.extent else 0
-        self.n = fit if n is None else int(n)
-        if self.n < 1 or self.n > fit:
-            raise ValueError(f"{nbytes} bytes hold {fit} frame(s) of this geometry behind a {self.header_bytes}-byte header; n = {self.n}")
+    def _init_staging(self, fps, repeat) -> None:
         self.fps, self.repeat = int(fps), int(repeat)
         self.frame_bytes = self.h * self.w * 3
-        self._bgr = None                 # DeviceBuffer: converted frames of the stored range _bgr_range = (first, count)
+        self._bgr = None                 # DeviceBuffer: BGR frames of the stored range _bgr_range = (first, count)
         self._bgr_range = None
-        self._marker = None              # .y4m: the bytes every frame record starts with, checked when the frame is yielded
 
     @property
     def total_frames(self) -> int:
         return self.n * self.repeat
-
-    def _offset(self, i: int) -> int:
-        return self.header_bytes + i * self.frame_stride
 
     def frames(self, start: int = 0, end: Optional[int] = None, stride: int = 1) -> Iterator[YuvFrame]:
         stop = self.total_frames if end is None else min(end, self.total_frames)
         for i in range(start, stop, stride):
             k = i % self.n
             self._check_marker(k)
-            yield YuvFrame(self, k)
+            yield self._frame_type(self, k)
 
     def _check_marker(self, k: int) -> None:
         pass
-
-    def host_bgr(self, first: int, count: int) -> np.ndarray:
-        """(count, h, w, 3) uint8 BGR of stored frames [first, first + count), converted on the host."""
-        return yuv420_to_bgr_host(self._host_bytes(first, count), count, self.h, self.w, self.desc)
 
     def _engine_or_default(self):
         if self.engine is None:
@@ -402,7 +394,7 @@ class _YuvSource:
         pa_yuv420_to_bgr).  A range the staging already holds converts nothing (fan-out: every tracker asks for the same batch)."""
         assert 0 <= first and count >= 1 and first + count <= self.n, (first, count, self.n)
         eng = self._engine_or_default()
-        if not hasattr(eng, "yuv420_to_bgr"):        # a stand-in engine without kernels (tests/fake_engine.py): host path
+        if not hasattr(eng, self._engine_call):      # a stand-in engine without kernels (tests/fake_engine.py): host path
             return None
         held = self._bgr_range
         if held is None or first < held[0] or first + count > held[0] + held[1]:
@@ -414,7 +406,7 @@ class _YuvSource:
                 self._bgr_range = None
                 self._bgr = eng.alloc(need)
             self._bgr_range = None
-            eng.yuv420_to_bgr(self._device_source(first, count), count, self.h, self.w, self.desc, self._bgr)
+            self._to_device(eng, first, count)
             held = self._bgr_range = (first, count)
         return self._bgr.view((first - held[0]) * self.frame_bytes, count * self.frame_bytes), count, self.h, self.w
 
@@ -425,6 +417,35 @@ class _YuvSource:
                 self.engine.synchronize()
             self._bgr.free()
         self._bgr, self._bgr_range = None, None
+
+
+class _YuvSource(_StagedSource):
+    """What ``YuvClip`` and ``DeviceYuvClip`` share: the geometry of the raw bytes and their conversion."""
+
+    def _init_geometry(self, nbytes: int, w, h, layout, matrix, range, pitch, pitch_c, off_u, off_v, frame_stride, header_bytes, n,
+                       fps, repeat, coeffs=None) -> None:
+        self.w, self.h = int(w), int(h)
+        self.layout = layout
+        self.desc = yuv_desc(w, h, layout, matrix, range, pitch, pitch_c, off_u, off_v, frame_stride, coeffs)
+        self.header_bytes = int(header_bytes)
+        self.frame_stride = self.desc["frame_stride"]
+        self.extent = yuv_span(1, self.h, self.w, self.desc)
+        fit = (nbytes - self.header_bytes - self.extent) // self.frame_stride + 1 if nbytes - self.header_bytes >= self.extent else 0
+        self.n = fit if n is None else int(n)
+        if self.n < 1 or self.n > fit:
+            raise ValueError(f"{nbytes} bytes hold {fit} frame(s) of this geometry behind a {self.header_bytes}-byte header; n = {self.n}")
+        self._init_staging(fps, repeat)
+        self._marker = None              # .y4m: the bytes every frame record starts with, checked when the frame is yielded
+
+    def _offset(self, i: int) -> int:
+        return self.header_bytes + i * self.frame_stride
+
+    def host_bgr(self, first: int, count: int) -> np.ndarray:
+        """(count, h, w, 3) uint8 BGR of stored frames [first, first + count), converted on the host."""
+        return yuv420_to_bgr_host(self._host_bytes(first, count), count, self.h, self.w, self.desc)
+
+    def _to_device(self, eng, first: int, count: int) -> None:
+        eng.yuv420_to_bgr(self._device_source(first, count), count, self.h, self.w, self.desc, self._bgr)
 
 
 class YuvClip(_YuvSource):
@@ -585,6 +606,72 @@ class DeviceYuvClip(_YuvSource):
         if self._owns and self.buffer is not None:
             self.buffer.free()
         self.buffer = None
+
+
+# ---------------------------------------------------------------------------------------------- Motion-JPEG sources
+class MjpegFrame(YuvFrame):
+    """Handle of one frame of an ``MjpegClip``: everything a ``YuvFrame`` is (``device_batch`` / ``host_batch`` / ``np.asarray``)."""
+    __slots__ = ()
+
+
+class MjpegClip(_StagedSource):
+    """A Motion-JPEG clip: ``path_or_bytes`` is the path of a ``.avi`` (AVI 1.0, ``MJPG`` stream; ``MjpegSink``'s ``.partNNN`` files are
+    followed) or ``.mjpeg`` / ``.mjpg`` file, or the JPEGs back to back as ``bytes`` / a 1-D uint8 array.  Baseline JPEG, 4:2:0, all
+    frames of one size (``mjpeg.parse_frame`` says what else is refused).  Presented as ``n * repeat`` frames.  ``on_device=True``:
+    a batch's compressed bytes are uploaded and decoded on the GPU of ``engine`` (default: the default engine) into one BGR staging
+    buffer — ``Engine.jpeg_decode``; ``on_device=False``: decoded on the host by ``mjpeg.decode_host``, the same bytes (boxes
+    without a GPU).  ``corrupt`` collects {stored frame: status word} of frames whose entropy-coded data was damaged: they are
+    reported (a warning, once per frame) and decoded as far as they go, never an error."""
+    _engine_call = "jpeg_decode"
+    _frame_type = MjpegFrame
+
+    def __init__(self, path_or_bytes, on_device: bool = True, engine=None, repeat: int = 1, fps: Optional[int] = None):
+        from . import mjpeg
+        if isinstance(path_or_bytes, (bytes, bytearray, np.ndarray)):
+            raw = np.frombuffer(path_or_bytes, np.uint8) if not isinstance(path_or_bytes, np.ndarray) else path_or_bytes
+            if raw.dtype != np.uint8 or raw.ndim != 1:
+                raise ValueError("MjpegClip: the bytes must be a 1-D uint8 array")
+            buf = raw.tobytes()
+            self.index = mjpeg.MjpegIndex(["<bytes>"], [(0, off, n) for off, n in mjpeg.split_mjpeg(buf)], 30, [raw])
+            self.path = None
+        else:
+            self.path = str(path_or_bytes)
+            self.index = mjpeg.index_file(self.path)
+        self.w, self.h, self.n = self.index.w, self.index.h, len(self.index)
+        self.on_device, self.engine = bool(on_device), engine
+        self.corrupt: dict = {}
+        self.decodes = 0                     # batches decoded so far (a range the staging already held is not one)
+        self._init_staging(self.index.fps if fps is None else fps, repeat)
+
+    def _report(self, first: int, status) -> None:
+        import warnings
+        for k in np.nonzero(status)[0]:
+            if first + int(k) not in self.corrupt:
+                self.corrupt[first + int(k)] = int(status[k])
+                warnings.warn(f"{self.path or 'MjpegClip'}: frame {first + int(k)} is damaged (status 0x{int(status[k]):x}: mjpeg.ST_*); "
+                              f"what could not be decoded is grey", RuntimeWarning, stacklevel=3)
+
+    def host_bgr(self, first: int, count: int) -> np.ndarray:
+        """(count, h, w, 3) uint8 BGR of stored frames [first, first + count), decoded on the host."""
+        from . import mjpeg
+        frames, status = mjpeg.decode_host_status(*self.index.batch(first, count))
+        if frames.shape[1:3] != (self.h, self.w):
+            raise ValueError(f"{self.path or 'MjpegClip'}: frames {first}.. are {frames.shape[2]} x {frames.shape[1]}, the clip is "
+                             f"{self.w} x {self.h}: frame sizes differ within the clip")
+        self.decodes += 1
+        self._report(first, status)
+        return frames
+
+    def _to_device(self, eng, first: int, count: int) -> None:
+        data, offsets = self.index.batch(first, count)
+        self.decodes += 1
+        self._report(first, eng.jpeg_decode(data, offsets, self._bgr, h=self.h, w=self.w))
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 # ---------------------------------------------------------------------------------------------- sinks for rendered frames
@@ -805,6 +892,29 @@ def _open_y4m(p: str) -> YuvClip:
     return hit[1]
 
 
+# Motion-JPEG files opened by path, kept like _Y4M_OPEN; None for what is no Motion-JPEG file (the caller goes on to cv2)
+_MJPEG_OPEN: dict = {}
+MJPEG_SUFFIXES = (".avi", ".mjpeg", ".mjpg")
+
+
+def _open_mjpeg(p: str) -> Optional["MjpegClip"]:
+    from . import mjpeg
+    if not p.lower().endswith(MJPEG_SUFFIXES) or not os.path.exists(p):
+        return None
+    st = os.stat(p)
+    key = (os.path.abspath(p), st.st_mtime_ns, st.st_size)
+    hit = _MJPEG_OPEN.get(key[0])
+    if hit is None or hit[0] != key:
+        if hit is not None:
+            hit[1].free()
+        try:
+            clip = MjpegClip(p)
+        except mjpeg.NotMjpeg:
+            return None
+        hit = _MJPEG_OPEN[key[0]] = (key, clip)
+    return hit[1]
+
+
 def device_batch(sample):
     """If ``sample`` is a list of DeviceFrame handles of ONE clip with consecutive stored indices, return
     (DeviceBuffer view over exactly those frames, n, h, w); None for host frames.  Anything else is an error: a
@@ -854,7 +964,7 @@ def host_batch(sample) -> np.ndarray:
 
 
 def get_video_frames_generator(source_path, stride: int = 1, start: int = 0, end: Optional[int] = None) -> Iterator[np.ndarray]:
-    if isinstance(source_path, (DeviceClip, ArrayClip, _YuvSource)):
+    if isinstance(source_path, (DeviceClip, ArrayClip, _StagedSource)):
         yield from source_path.frames(start, end, stride)
         return
     p = str(source_path)
@@ -870,6 +980,10 @@ def get_video_frames_generator(source_path, stride: int = 1, start: int = 0, end
         stop = a.shape[0] if end is None else min(end, a.shape[0])
         for i in range(start, stop, stride):
             yield np.ascontiguousarray(a[i])
+        return
+    c = _open_mjpeg(p)
+    if c is not None:
+        yield from c.frames(start, end, stride)
         return
     cv2 = _cv2()
     cap = cv2.VideoCapture(p)
