@@ -460,9 +460,15 @@ int pa_yolo_postprocess(pa_model* m, const float* const* heads, int n, int h, in
                         float* out_boxes, float* out_kpts, int32_t* out_counts);
 
 /* raw head maps of the last pa_yolo_infer call (level 0..2): n x H_l x W_l x c fp32 (c from
- * pa_yolo_head_shape; channels [0,64) box DFL logits, [64,64+nc) class logits, then nk keypoint values) */
+ * pa_yolo_head_shape; channels [0,64) box DFL logits, [64,64+nc) class logits, then nk keypoint values).
+ * h2 models whose heads end in the usual 1x1 convs do not write these maps in a plain call (tuning fuse_head: the convs and the
+ * decode run as one kernel): pa_yolo_read_head then computes them on demand, for the images of the last call, from the convs'
+ * inputs, which the plan keeps until the next call; further reads copy what the first one computed */
 int pa_yolo_head_shape(pa_model* m, int level, int* h, int* w, int* c);
 int pa_yolo_read_head(pa_model* m, int level, int n, float* out);
+/* which post-processing the model's last pa_yolo_infer / pa_yolo_submit / pa_yolo_postprocess took: 0 decode_kernel over head
+ * maps, 1 the fused head tail (the heads' last convs and the decode in one kernel, no head map)                            */
+int pa_yolo_last_post_path(pa_model* m);
 
 /* the u8 network input (NHWC4: R,G,B,0 as the network sees them) the last pa_yolo_infer call built from its
  * first n frames — byte-exact check of the letterbox (cv2 INTER_LINEAR) / Pillow-bicubic preprocessing */

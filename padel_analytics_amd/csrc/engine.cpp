@@ -22,6 +22,7 @@ static const struct Knob { const char* key; const char* env; int Tuning::*field;
     {"fold_up", "PADEL_FOLD_UP", &Tuning::fold_up, knob_flag},
     {"fuse_stem", "PADEL_FUSE_STEM", &Tuning::fuse_stem, knob_raw},
     {"fuse_sppf", "PADEL_FUSE_SPPF", &Tuning::fuse_sppf, knob_raw},
+    {"fuse_head", "PADEL_FUSE_HEAD", &Tuning::fuse_head, knob_flag},
     {"w_single", nullptr, &Tuning::w_single, knob_flag},
 };
 
@@ -51,6 +52,7 @@ int pa_engine_create(int device_id, pa_engine** out) {
     if (r == hipSuccess) r = hipMemset(e->zeros, 0, 256);
     if (r != hipSuccess) { delete e; PA_FAIL((pa_engine*)nullptr, "zero page: %s", hipGetErrorString(r)); }
     r = padel::init_misc_kernels();
+    if (r == hipSuccess) r = padel::init_head_tail_kernels();
     if (r != hipSuccess) { delete e; PA_FAIL((pa_engine*)nullptr, "kernel attributes: %s", hipGetErrorString(r)); }
     if (const char* v = getenv("PADEL_CONV_IMPL")) {       // tap | bx3 ("lds", the kernel retired in round 5, is refused — it used to select tap silently)
         if (v[0] == 'l') { delete e; PA_FAIL((pa_engine*)nullptr, "PADEL_CONV_IMPL=%s: the LDS kernel was retired in round 5; tap or bx3", v); }
@@ -178,6 +180,12 @@ int pa_model_create(pa_engine* e, const pa_model_desc* desc, const float* weight
     find_upsample_folds(m->d, m->fold_src, m->fold_dst);
     m->stem_fuse.resize(m->ops.size());
     for (size_t i = 0; i < m->ops.size(); ++i) m->stem_fuse[i] = stem_fusable(m->d, i);
+    m->tail = find_head_tail(m->d, m->fold_src);
+    m->tail_op.assign(m->ops.size(), 0);
+    if (m->tail.found)
+        for (int l = 0; l < 3; ++l)
+            for (int c = 0; c < 3; ++c)
+                if (m->tail.op[l][c] >= 0) m->tail_op[m->tail.op[l][c]] = 1;
     m->n_w = n_floats;
     hipError_t r = hipMalloc((void**)&m->d_w, n_floats * sizeof(float) + kConvReadSlack);
     if (r == hipSuccess)
@@ -215,6 +223,7 @@ void free_plan(pa_model* m) {
     m->d_cand = nullptr; m->d_cidx = m->d_ccnt = nullptr; m->d_keys = nullptr; m->d_order = nullptr; m->d_supp = nullptr;
     m->d_oboxes = m->d_okpts = nullptr; m->d_ocnt = nullptr;
     m->planned = false;
+    m->heads_stale = false;
 }
 
 void pa_model_destroy(pa_model* m) {
@@ -269,7 +278,7 @@ int plan_buffers(pa_model* m, int batch) {
     pa_engine* e = m->e;
     BufferPlan bp;
     std::string why;
-    if (plan_activations(m->d, m->fold_src, m->net_h, m->net_w, batch, e->t.alias != 0, bp, why)) PA_FAIL(e, "%s", why.c_str());
+    if (plan_activations(m->d, m->fold_src, m->net_h, m->net_w, batch, e->t.alias != 0, bp, why, &m->tail)) PA_FAIL(e, "%s", why.c_str());
     m->fc_nout = 0;
     for (const auto& o : m->ops) if (o.kind == PA_OP_GAP_FC) m->fc_nout = o.cout;
     if (m->fc_nout) {
@@ -354,12 +363,55 @@ static int conv_launch_args(const pa_model* m, size_t i, int n, ConvArgs& a, int
     return lv;
 }
 
+void head_tail_convs(const pa_model* m, HeadTailArgs& a) {
+    bool single = m->e->t.w_single != 0;
+    for (int l = 0; l < 3; ++l)
+        for (int c = 0; c < 3; ++c) {
+            HeadTailConv& v = a.cv[l][c];
+            v = HeadTailConv{};
+            const int i = m->tail.op[l][c];
+            if (i < 0) continue;
+            const pa_op_desc& o = m->ops[i];
+            v.in = m->bptr[o.in_buf]; v.in_cs = m->bufs[o.in_buf].channels; v.in_choff = o.in_choff;
+            v.w = m->d_w + o.w_off; v.bias = m->d_w + o.b_off; v.oscale = m->d_w + o.reserved;
+            v.cin = o.cin; v.n16 = o.npad / 16;
+            single = single && (o.flags & PA_CONV_W_SINGLE);
+        }
+    a.w_single = single ? 1 : 0;      // one form for the three convs: the three-product form is bitwise the two-product one on a zero m plane
+}
+
+bool head_fused(const pa_model* m) {
+    const pa_engine* e = m->e;
+    if (!e->t.fuse_head || m->d.dtype != PA_DTYPE_H2 || !m->tail.found || e->profiling || e->t.timeline || !m->planned) return false;
+    HeadTailArgs a{};
+    a.d.cs = m->bufs[m->d.head_buf[0]].channels; a.d.nc = m->d.nc; a.d.nk = m->d.nk;
+    head_tail_convs(m, a);
+    return head_tail_h2_supported(a);
+}
+
+int run_tail_ops(pa_model* m, int n) {
+    pa_engine* e = m->e;
+    for (int l = 0; l < 3; ++l)
+        for (int c = 0; c < 3; ++c) {
+            const int i = m->tail.op[l][c];
+            if (i < 0) continue;
+            ConvArgs a{};
+            int path = CONV_PATH_TAP;
+            const int lv = conv_launch_args(m, (size_t)i, n, a, &path);
+            const hipError_t r = launch_conv(path, a, lv, e->stream);
+            if (r != hipSuccess) PA_FAIL(e, "op %d (head tail) launch failed: %s", i, hipGetErrorString(r));
+        }
+    return 0;
+}
+
 // replay the op list for `n` images (prof records appended starting at *pi)
 static int run_ops(pa_model* m, int n, size_t* pi) {
     pa_engine* e = m->e;
     hipStream_t s = e->stream;
+    const bool skip_tail = head_fused(m);          // the heads' last convs run inside the fused head tail (run_post)
     for (size_t i = 0; i < m->ops.size(); ++i) {
         const pa_op_desc& o = m->ops[i];
+        if (skip_tail && m->tail_op[i]) continue;
         const pa_buf_desc& ob = m->bufs[o.out_buf];
         const int Ho = m->net_h >> ob.level, Wo = m->net_w >> ob.level;
         hipError_t r = hipSuccess;

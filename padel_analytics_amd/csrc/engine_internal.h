@@ -42,6 +42,9 @@ struct Tuning {
     int w_single = 1;    // 1 (default): h2 convs whose packed weights have an all-zero m plane (PA_CONV_W_SINGLE) skip the wm x ah product;
                          // 0 (tests): all three products everywhere — bitwise the same results
     int fuse_sppf = 1;   // 1: h2 graphs run the three chained 5x5 max-pools of SPPF as ONE kernel (sppf_h2_kernel: keys in LDS, separable passes); 0 = three launches.  Bitwise the same maps
+    int fuse_head = 1;   // 1: h2 Detect / Pose models whose plan found the head tail (graph_plan.h: HeadTail) run the heads' last 1x1 convs and the
+                         // decode as ONE kernel (head_tail_h2.hip) and never write the head maps; 0: the convs, then decode_kernel.  Bitwise the same
+                         // detections; off while profiling or collecting a timeline (the profile keeps its rows)
     int fold_up = 1;     // 1: an nn.Upsample(2) whose only reader is a bf16x3 1x1 conv is never materialised (the conv
                          // fetches those channels at [y >> 1][x >> 1] of the coarse map), 0: run the upsample kernel
 };
@@ -110,6 +113,8 @@ struct pa_model {
     std::vector<int> fold_src;             // conv op i -> index of the upsample op it can absorb (-1: none), find_upsample_folds
     std::vector<int> fold_dst;             // upsample op j -> its absorbing conv (-1: none)
     std::vector<char> stem_fuse;           // op i -> stem_fusable (the stem and the stride-2 3x3 behind it can run as one kernel)
+    HeadTail tail;                         // the heads' last 1x1 convs, if the graph ends the way find_head_tail wants it
+    std::vector<char> tail_op;             // op i is one of them
     float* d_w = nullptr;
     size_t n_w = 0;
     // h2 models: the h planes of the two-product stride-1 3x3 convs once more in MFMA operand order (conv_patch_h2r.hip), built on
@@ -154,6 +159,8 @@ struct pa_model {
     float* d_oboxes = nullptr; float* d_okpts = nullptr; int32_t* d_ocnt = nullptr;
     int32_t* d_classes = nullptr; int classes_cap = 0;
     int last_n = 0;
+    int last_post_path = 0;                // pa_yolo_last_post_path: 0 decode_kernel on head maps, 1 the fused head tail
+    bool heads_stale = false;              // the last call ran the fused head tail: the head maps are not there (pa_yolo_read_head computes them)
     std::vector<ProfRec> prof;
     size_t n_prof = 0;
 };
@@ -166,6 +173,11 @@ void free_plan(pa_model* m);                         // the caller has synchroni
 int plan_buffers(pa_model* m, int batch);            // the arena of a model whose net_h x net_w is set: allocation, memsets, bptr, d_fc
 // run_ops, or (tuning "graph", not while profiling) the replay of its capture for this batch size
 int run_graph(pa_model* m, int n, size_t* pi);
+// The fused head tail applies to the next replay of a planned model: tuning fuse_head, an h2 model whose plan found the tail, a
+// shape head_tail_h2.hip has, no profiling, no timeline.  run_ops then skips the tail convs and run_post launches the fused kernel.
+bool head_fused(const pa_model* m);
+void head_tail_convs(const pa_model* m, HeadTailArgs& a);      // a.cv and a.w_single of a planned model (a.d: the caller's)
+int run_tail_ops(pa_model* m, int n);                // the tail convs alone, from their inputs (still live): the head maps of the last call
 
 // ---- engine_jpeg.cpp
 void jpeg_scratch_free(pa_engine* e);                 // waits for the stream first

@@ -43,9 +43,10 @@ static int plan_yolo(pa_model* m, int h0, int w0, const pa_yolo_params* p) {
 
 // decode + NMS + scale_boxes / scale_coords of the head maps in m->lv[] for nb images of a planned model, results copied to
 // the caller's arrays (rows beyond max_det are never written on device).  oh x ow: the size upstream treats as the source
-// (the PIL-resized image on the stretch path).
+// (the PIL-resized image on the stretch path).  fused: the op list skipped the heads' last convs (head_fused): the fused head tail
+// computes them and the candidate list in place of decode_kernel; the head maps then hold only the keypoint rows NMS reads.
 static int run_post(pa_model* m, const pa_yolo_params* p, int nb, int oh, int ow, size_t* ppi, float* out_boxes, float* out_kpts,
-                int32_t* out_counts, int ovf_slot) {
+                int32_t* out_counts, int ovf_slot, bool fused) {
     pa_engine* e = m->e;
     hipStream_t s = e->stream;
     size_t& pi = *ppi;
@@ -60,9 +61,18 @@ static int run_post(pa_model* m, const pa_yolo_params* p, int nb, int oh, int ow
     da.A = m->A; da.B = nb; da.conf = p->conf; da.classes = m->d_classes; da.n_classes = p->n_classes;
     da.cand = m->d_cand; da.cand_idx = m->d_cidx; da.cand_cnt = m->d_ccnt;
     pr = prof_begin(m, pi++, PROF_DECODE, 0, 0.0);
-    r = launch_decode(da, s);
+    if (fused) {
+        HeadTailArgs ha{};
+        ha.d = da;
+        head_tail_convs(m, ha);
+        r = launch_head_tail_h2(ha, s);
+    } else {
+        r = launch_decode(da, s);
+    }
     prof_end(m, pr);
-    if (r != hipSuccess) PA_FAIL(e, "decode launch failed: %s", hipGetErrorString(r));
+    if (r != hipSuccess) PA_FAIL(e, "%s launch failed: %s", fused ? "fused head tail" : "decode", hipGetErrorString(r));
+    m->last_post_path = fused ? 1 : 0;
+    m->heads_stale = fused;
     NmsArgs na{};
     na.cand = m->d_cand; na.cand_idx = m->d_cidx; na.cand_cnt = m->d_ccnt; na.keys = m->d_keys;
     na.order = m->d_order; na.supp = m->d_supp;
@@ -156,10 +166,11 @@ static int yolo_enqueue(pa_model* m, const uint8_t* src, int nb, int h, int w, c
     }
     prof_end(m, pr);
     if (r != hipSuccess) PA_FAIL(e, "preprocess launch failed: %s", hipGetErrorString(r));
-    // ---- network
+    // ---- network (without the heads' last convs when the fused head tail runs them: the same decision in run_ops)
+    const bool fused = head_fused(m);
     if (run_graph(m, nb, &pi)) return 1;
     // ---- decode + NMS + results back to the caller's arrays
-    return run_post(m, p, nb, oh, ow, &pi, out_boxes, m->d.nk ? out_kpts : nullptr, out_counts, ovf_slot);
+    return run_post(m, p, nb, oh, ow, &pi, out_boxes, m->d.nk ? out_kpts : nullptr, out_counts, ovf_slot, fused);
 }
 
 int pa_yolo_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, const pa_yolo_params* p,
@@ -244,7 +255,7 @@ int pa_yolo_postprocess(pa_model* m, const float* const* heads, int n, int h, in
     const int S = p->imgsz;
     const int oh = p->pre_mode == PA_PRE_PIL_STRETCH ? S : h, ow = p->pre_mode == PA_PRE_PIL_STRETCH ? S : w;
     size_t pi = 0;
-    if (run_post(m, p, n, oh, ow, &pi, out_boxes, out_kpts, out_counts, PA_MAX_INFLIGHT)) return 1;
+    if (run_post(m, p, n, oh, ow, &pi, out_boxes, out_kpts, out_counts, PA_MAX_INFLIGHT, false)) return 1;
     PA_HIP(e, hipStreamSynchronize(s));
     m->last_n = n;
     finish_profile(m, pi);
@@ -261,11 +272,17 @@ int pa_yolo_read_head(pa_model* m, int level, int n, float* out) {
     pa_engine* e = m->e;
     if (!m->planned || level < 0 || level > 2 || n > m->last_n) PA_FAIL(e, "pa_yolo_read_head: no plan / bad level / n");
     PA_HIP(e, hipSetDevice(e->dev));
+    if (m->heads_stale) {          // the last call ran the fused head tail: the maps of its last_n images from the tail convs' inputs, once
+        if (run_tail_ops(m, m->last_n)) return 1;
+        m->heads_stale = false;
+    }
     const size_t bytes = (size_t)n * m->lv[level].H * m->lv[level].W * m->bufs[m->d.head_buf[0]].channels * sizeof(float);
     PA_HIP(e, hipMemcpyAsync(out, m->lv[level].buf, bytes, hipMemcpyDeviceToHost, e->stream));
     PA_HIP(e, hipStreamSynchronize(e->stream));
     return 0;
 }
+
+int pa_yolo_last_post_path(pa_model* m) { return m ? m->last_post_path : 0; }
 
 int pa_yolo_netin_shape(pa_model* m, int* h, int* w) {
     if (!m->planned || m->d.task == PA_TASK_TRACKNET) PA_FAIL(m->e, "pa_yolo_netin_shape: no YOLO plan");

@@ -208,15 +208,46 @@ bool stem_fusable(const pa_model_desc& d, size_t i) {
     return true;
 }
 
+HeadTail find_head_tail(const pa_model_desc& d, const std::vector<int>& fold_src) {
+    HeadTail none, t;
+    if ((d.task != PA_TASK_DETECT && d.task != PA_TASK_POSE) || d.dtype != PA_DTYPE_H2 || d.nc < 1 || d.nk < 0) return none;
+    for (int l = 0; l < 3; ++l)
+        if (d.head_buf[l] < 0 || d.head_buf[l] >= d.n_bufs) return none;
+    const int want = d.nk > 0 ? 3 : 2;
+    for (int i = 0; i < d.n_ops; ++i) {
+        const pa_op_desc& o = d.ops[i];
+        const bool reads_in = o.kind != PA_OP_STEM && o.kind != PA_OP_STEM7;
+        if (reads_in && is_head_buf(d, o.in_buf)) return none;                       // somebody reads a head map
+        if ((o.kind == PA_OP_CONV || o.kind == PA_OP_DWCONV3) && o.res_buf >= 0 && is_head_buf(d, o.res_buf)) return none;
+        if (o.kind == PA_OP_GAP_FC || !is_head_buf(d, o.out_buf)) continue;          // (the pooled linear head writes no buffer)
+        int l = 0;
+        while (d.head_buf[l] != o.out_buf) ++l;
+        if (d.head_buf[(l + 1) % 3] == o.out_buf || d.head_buf[(l + 2) % 3] == o.out_buf) return none;      // one buffer for two levels
+        if (o.kind != PA_OP_CONV || o.ksize != 1 || o.stride != 1 || o.act != PA_ACT_NONE || o.res_buf >= 0) return none;
+        if (i < (int)fold_src.size() && fold_src[i] >= 0) return none;
+        const int c = o.out_choff == 0 ? 0 : o.out_choff == 64 ? 1 : (d.nk > 0 && o.out_choff == 64 + d.nc) ? 2 : -1;
+        if (c < 0 || o.cout != (c == 0 ? 64 : c == 1 ? d.nc : d.nk) || t.op[l][c] >= 0) return none;
+        for (int k = i + 1; k < d.n_ops; ++k)                                        // its input must still be there after the op list
+            if (d.ops[k].kind != PA_OP_GAP_FC && d.ops[k].out_buf == o.in_buf) return none;
+        t.op[l][c] = i;
+    }
+    for (int l = 0; l < 3; ++l)
+        for (int c = 0; c < want; ++c)
+            if (t.op[l][c] < 0) return none;
+    t.found = true;
+    return t;
+}
+
 // ------------------------------------------------------------------------------- activation memory plan
 // Every logical buffer of the graph needs batch * H * W * channels floats, but most
 // are dead most of the time (a C2f's scratch dies with the C2f): buffers whose live ranges on the op list do not
 // overlap share bytes of ONE arena (first-fit by offset over the buffers ordered by first use).  A buffer is
 // live from the first op that touches it to the last one; the network input of a TrackNet graph (buffer 0) is
-// live from before op 0, head buffers stay live past the last op (decode / NMS / pa_yolo_read_head read them).
+// live from before op 0, head buffers stay live past the last op (decode / NMS / pa_yolo_read_head read them), and so do the
+// inputs of a head tail the caller passes (find_head_tail).
 // Aliased bytes always hold finite fp32 activations, so a zero-weighted pad channel still contributes exactly 0.
 int plan_activations(const pa_model_desc& d, const std::vector<int>& fold_src, int net_h, int net_w, int batch, bool alias,
-                     BufferPlan& out, std::string& err) {
+                     BufferPlan& out, std::string& err, const HeadTail* tail) {
     int maxl = 0;
     for (int i = 0; i < d.n_bufs; ++i) maxl = std::max(maxl, d.bufs[i].level);
     const int mask = (1 << maxl) - 1;
@@ -234,6 +265,10 @@ int plan_activations(const pa_model_desc& d, const std::vector<int>& fold_src, i
     if (d.task == PA_TASK_TRACKNET) touch(0, -1);
     const bool f16 = d.dtype == PA_DTYPE_F16;
     for (int l = 0; l < 3; ++l) touch(d.head_buf[l], nops + 1);
+    if (tail && tail->found)          // the fused head tail reads its convs' inputs after the op list
+        for (int l = 0; l < 3; ++l)
+            for (int c = 0; c < 3; ++c)
+                if (tail->op[l][c] >= 0) touch(d.ops[tail->op[l][c]].in_buf, nops + 1);
     // fp16 models: the head maps are the only fp32 buffers; they never share bytes with fp16 buffers, so a pad
     // channel that is read under a zero weight always holds a finite fp16 value, never reinterpreted fp32 bits
     if (f16) for (int l = 0; l < 3; ++l) touch(d.head_buf[l], -1);

@@ -20,12 +20,26 @@ void find_upsample_folds(const pa_model_desc& d, std::vector<int>& fold_src, std
 // op i is the stem, op i + 1 a 3x3 stride-2 conv over exactly the stem's channels, and nothing else reads the stem's output
 bool stem_fusable(const pa_model_desc& d, size_t i);
 
+// The tail of a Detect / Pose head of an h2 model: on every level the ops that write head_buf[l] are exactly a 1x1, stride-1 conv
+// without activation or residual for the 64 box logits (channel 0), one for the nc class logits (channel 64) and, iff nk > 0, one
+// for the nk keypoint values (channel 64 + nc); each reads a non-head buffer that no later op writes, absorbs no upsample, and
+// nothing reads the head maps.  op[l][0 | 1 | 2]: the box / class / keypoint conv of level l (-1: no keypoint conv).  Anything else
+// — a partial match, a test graph with one conv into a head buffer, another dtype or task — is `found == false`.  The engine may
+// then run the three convs and the decode as one kernel (head_tail_h2.hip) and never write the maps.
+struct HeadTail {
+    bool found = false;
+    int op[3][3] = {{-1, -1, -1}, {-1, -1, -1}, {-1, -1, -1}};
+};
+HeadTail find_head_tail(const pa_model_desc& d, const std::vector<int>& fold_src);
+
 struct BufferPlan {
     std::vector<size_t> off, bytes;            // per logical buffer: byte offset into the arena, bytes (slack included, multiple of 256)
     size_t arena_bytes = 0, logical_bytes = 0; // bytes of the plan with / without liveness aliasing
 };
+// tail (optional, found): the inputs of its convs stay live past the last op, like the head maps — the fused kernel reads them
+// after the op list, and pa_yolo_read_head computes the maps from them on demand
 int plan_activations(const pa_model_desc& d, const std::vector<int>& fold_src, int net_h, int net_w, int batch, bool alias,
-                     BufferPlan& out, std::string& err);
+                     BufferPlan& out, std::string& err, const HeadTail* tail = nullptr);
 
 struct YoloGeometry {
     int rw = 0, rh = 0, top = 0, left = 0, net_h = 0, net_w = 0, lb_mode = 0;   // lb_mode 0 copy, 1 exact 2x2 area, 2 cv2 bilinear tables

@@ -299,6 +299,27 @@ struct DecodeArgs {
 };
 hipError_t launch_decode(const DecodeArgs& a, hipStream_t s);
 
+// The fused head tail of h2 Detect / Pose models (head_tail_h2.hip): per level the last 1x1 convs of the box / class / keypoint
+// branches (graph_plan.h: HeadTail) and the decode in ONE launch.  The head maps are not written, except the nk keypoint values of
+// the anchors that pass, at their place in the map (where nms_kernel reads them).  Candidates are bitwise those of the convs
+// followed by decode_kernel.
+struct HeadTailConv {
+    const float* in;      // h2 pairs, pixel stride in_cs channels, slice at in_choff
+    const float* w;       // packed planes [npad][k-step][h | m][32 fp16]
+    const float* bias;    // [npad]
+    const float* oscale;  // [npad]
+    int in_cs, in_choff, cin, n16;
+};
+struct HeadTailArgs {
+    DecodeArgs d;         // lv[l].buf: the head map of level l (keypoint rows of passing anchors only)
+    HeadTailConv cv[3][3];   // [level][box 64, class nc, keypoint nk]; cv[l][2].in == nullptr: detect
+    int w_single;         // every conv's m plane is all zero (ConvArgs::w_single): two products per operand pair
+    int wg_end[3];        // filled by the launcher: workgroups [wg_end[l - 1], wg_end[l]) walk level l
+};
+bool head_tail_h2_supported(const HeadTailArgs& a);      // the k-step counts have an instantiation, the weights fit the LDS
+hipError_t init_head_tail_kernels();                     // per engine: the kernels' dynamic-LDS limit on the current device
+hipError_t launch_head_tail_h2(const HeadTailArgs& a, hipStream_t s);
+
 struct NmsArgs {
     const float* cand; const int32_t* cand_idx; const int32_t* cand_cnt;
     uint64_t* keys;       // [B][P2] sort scratch (P2 = pow2 >= A)

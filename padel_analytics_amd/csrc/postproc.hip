@@ -18,10 +18,9 @@
 //                 same decisions as the sequential loop, which stays as the path for longer lists; then
 //                 the kept boxes / keypoints are rescaled to source-frame pixels and written in rank order.
 #include "kernels.h"
+#include "decode_math.h"
 
 namespace padel {
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 __global__ void __launch_bounds__(256) decode_kernel(const DecodeArgs a) {
     const int b = blockIdx.y;
@@ -57,30 +56,16 @@ __global__ void __launch_bounds__(256) decode_kernel(const DecodeArgs a) {
     }
     float bx[4] = {0.f, 0.f, 0.f, 0.f};
     if (pass) {
-        // DFL: softmax over 16 bins, expectation with arange(16)
+        // DFL + dist2bbox: decode_math.h
         float d[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             float v[16];
-            float m = h[s * 16];
 #pragma unroll
-            for (int i = 0; i < 16; ++i) { v[i] = h[s * 16 + i]; m = fmaxf(m, v[i]); }
-            float sum = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { v[i] = expf(v[i] - m); sum += v[i]; }
-            float e = 0.0f;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) e += (v[i] / sum) * (float)i;
-            d[s] = e;
+            for (int i = 0; i < 16; ++i) v[i] = h[s * 16 + i];
+            d[s] = dfl_expect(v);
         }
-        const float ax = (float)(pix % lv.W) + 0.5f, ay = (float)(pix / lv.W) + 0.5f;
-        const float st = (float)lv.stride;
-        // dist2bbox(xywh=True) * stride, then xywh2xyxy (same op order as upstream)
-        const float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
-        const float cx = ((x1 + x2) / 2.0f) * st, cy = ((y1 + y2) / 2.0f) * st;
-        const float w = (x2 - x1) * st, hh = (y2 - y1) * st;
-        const float hw = w / 2.0f, hhh = hh / 2.0f;
-        bx[0] = cx - hw; bx[1] = cy - hhh; bx[2] = cx + hw; bx[3] = cy + hhh;
+        dfl_box(d, pix, lv.W, lv.stride, bx);
     }
     // stream compaction: survivors of a wave take consecutive slots behind ONE atomic (their order inside the list does
     // not matter: nms_kernel's sort key carries the anchor index)

@@ -96,6 +96,8 @@ RENDER_PATH_VECTOR, RENDER_PATH_BYTE = 1, 2
 
 PRE_LETTERBOX, PRE_PIL_STRETCH = 0, 1
 YUV_NV12, YUV_I420 = 0, 1
+#: ``Model.last_post_path()``: decode_kernel over head maps, or the heads' last convs + decode as one kernel
+POST_PATH_DECODE, POST_PATH_FUSED = 0, 1
 #: ``Engine.yuv_last_path()``: which instantiation of the conversion kernel the launcher chose
 YUV_PATH_VECTOR, YUV_PATH_BYTE = 1, 2
 
@@ -119,6 +121,7 @@ ABI_SYMBOLS = [
     "pa_render", "pa_render_check", "pa_render_last_path", "pa_glyph_rows", "pa_ball_read_resized",
     "pa_jpeg_encode", "pa_jpeg_check", "pa_jpeg_interval_bytes",
     "pa_jpeg_parse", "pa_jpeg_decode", "pa_jpeg_decode_last_path", "pa_jpeg_decode_last_times",
+    "pa_yolo_last_post_path",
 ]
 
 
@@ -159,6 +162,7 @@ def load_library():
     lib.pa_yolo_wait.argtypes = [vp, i32, C.POINTER(C.c_int)]
     lib.pa_yolo_head_shape.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.pa_yolo_read_head.argtypes = [vp, i32, i32, vp]
+    lib.pa_yolo_last_post_path.argtypes = [vp]
     lib.pa_tracknet_infer.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
     lib.pa_resnet_infer.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
     lib.pa_resnet_read_netin.argtypes = [vp, i32, vp]
@@ -560,7 +564,7 @@ class Engine:
         return float(ms.value)
 
     def set_tuning(self, **kv):
-        """Tests / tools only: impl (2 bx3, 0 tap; 1 — the retired LDS kernel — is refused), variant (tile id, -1 auto), tune, tap_pd, graph, alias, fold_up, timeline."""
+        """Tests / tools only: impl (2 bx3, 0 tap; 1 — the retired LDS kernel — is refused), variant (tile id, -1 auto), tune, tap_pd, graph, alias, fold_up, timeline, fuse_stem, fuse_sppf, fuse_head."""
         for k, v in kv.items():
             self._check(self.lib.pa_engine_set_tuning(self.handle, k.encode(), int(v)))
             if k == "timeline":
@@ -874,6 +878,11 @@ class Model:
         out = np.empty((n, hh.value, ww.value, cc.value), np.float32)
         self.engine._check(self.engine.lib.pa_yolo_read_head(self.handle, level, n, out.ctypes.data))
         return out
+
+    def last_post_path(self) -> int:
+        """POST_PATH_DECODE / POST_PATH_FUSED: what the last ``yolo_infer`` / ``yolo_submit`` / ``postprocess`` of this model ran
+        after the network — ``decode_kernel`` over head maps, or the fused head tail (tuning ``fuse_head``)."""
+        return int(self.engine.lib.pa_yolo_last_post_path(self.handle))
 
     def read_netin(self, n: int) -> np.ndarray:
         """u8 NHWC4 network input of the first n frames of the last yolo_infer call."""
