@@ -366,9 +366,29 @@ int pa_jpeg_parse(const uint8_t* jpeg, size_t len, pa_jpeg_frame_info* info, pa_
  * decodes it to int16 coefficients, one thread per block dequantises and inverts the DCT into padded planes, a third pass
  * upsamples and converts.  The scratch (compressed bytes, coefficients, planes: 4.5 bytes per pixel of the padded frame) belongs
  * to the engine, grows on demand and is freed with it; at most 64 frames or 256 MiB of it are in use at a time (larger calls are
- * decoded in sub-batches inside the call).  A stream without restart markers is one interval: one wave per frame.            */
+ * decoded in sub-batches inside the call).
+ * The split path: an interval of at least min_bytes bytes (pa_jpeg_decode_set_split; a stream without restart markers is one interval,
+ * the whole frame) is decoded by one workgroup instead of one wave (csrc/jpeg_entropy_split.h).  Its bytes are cut into subsequences
+ * of sub_bytes raw bytes (more where 4096 of them would not cover it), one lane each.  A lane decodes its subsequence from the state
+ * (bit position, block in MCU, coefficient index) the subsequence before it ended in, in the first round from the guess "a block
+ * starts at my first bit"; a state no symbol could be decoded from is replaced by that guess.  Rounds repeat until no exit state
+ * changes, at most one per subsequence, after which every state is the serial decoder's; then each subsequence is decoded once more
+ * and stores its coefficients at their blocks, DC as differences that one scan per component sums.  Pixels and status words are
+ * those specified above bit for bit, damaged intervals included; how many rounds it took depends on the data only.  Shorter
+ * intervals keep the one-wave kernel, so a stream without restart markers is one workgroup per frame, one with them one wave per
+ * interval.                                                                                                                      */
 int pa_jpeg_decode(pa_engine* eng, const uint8_t* jpegs_host, const int64_t* offsets, int n, int h, int w, uint8_t* dst_bgr_dev,
                    int32_t* status_host);
+/* Which intervals of later pa_jpeg_decode calls take the split path.  min_bytes: 0 the default, -1 never (every interval on the
+ * one-wave kernel), else the length in bytes from which an interval is split.  sub_bytes: 0 the default, else a multiple of 4 in
+ * [4, 32768].  Anything else is refused with its reason (pa_last_error(eng); of a NULL engine: pa_last_error(NULL)).  The defaults
+ * are measured (profiles/mjpeg_split_bench.txt).                                                                               */
+#define PA_JPEG_DEC_SPLIT_MIN_BYTES 7168
+#define PA_JPEG_DEC_SPLIT_SUB_BYTES 128
+int pa_jpeg_decode_set_split(pa_engine* eng, int64_t min_bytes, int32_t sub_bytes);
+/* tests, tools: of the last successful pa_jpeg_decode: out[0] intervals on the split path, out[1] their subsequences, out[2] the
+ * largest number of rounds any of them took (the kernel writes it beside the status word), out[3] intervals on the one-wave kernel */
+int pa_jpeg_decode_last_split(pa_engine* eng, int64_t out[4]);
 /* tests: 1 if the last successful pa_jpeg_decode wrote its pixels with 16-byte stores (w a multiple of 16 and dst 16-byte aligned),
  * 2 if with byte stores, 0: none yet                                                                                          */
 int pa_jpeg_decode_last_path(pa_engine* eng);

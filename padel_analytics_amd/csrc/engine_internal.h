@@ -72,6 +72,9 @@ struct pa_engine {
     JpegScratch* jpeg = nullptr;   // pa_jpeg_encode: slots, tables and the gathered frames, grown on demand, used on `stream` only (engine_jpeg.cpp)
     JpegDecScratch* jpeg_dec = nullptr;   // pa_jpeg_decode: compressed bytes, tables, coefficients and planes, likewise (engine_jpeg_decode.cpp)
     int jpeg_dec_last_path = 0;    // 1 vector, 2 byte: what the last pa_jpeg_decode launched for its colour pass (pa_jpeg_decode_last_path)
+    long long jpeg_dec_split_min = 0;   // pa_jpeg_decode_set_split as given: 0 the default, -1 never; an interval of at least this many bytes is split
+    int jpeg_dec_split_sub = 0;         // ... its subsequences' bytes, 0 the default
+    long long jpeg_dec_last_split[4] = {0, 0, 0, 0};   // pa_jpeg_decode_last_split
 };
 
 extern thread_local std::string g_err;      // errors of calls that have no engine yet (pa_last_error(NULL))

@@ -11,7 +11,8 @@ struct JpegDecScratch {
     uint8_t* data = nullptr; size_t data_cap = 0;                // compressed bytes of a sub-batch
     JpegDecFrame* frames = nullptr; size_t frames_cap = 0;       // bytes
     JpegDecInterval* ivls = nullptr; size_t ivls_cap = 0;        // bytes
-    int32_t* status = nullptr; size_t status_cap = 0;            // bytes: one word per interval
+    int32_t* status = nullptr; size_t status_cap = 0;            // bytes: per interval one status word, then one word of rounds
+    int32_t* order = nullptr; size_t order_cap = 0;              // bytes: the intervals of the serial kernel, then those of the split kernel
     int16_t* coef = nullptr; size_t coef_cap = 0;                // bytes
     uint8_t* planes = nullptr; size_t planes_cap = 0;
     hipEvent_t ev[5]{};                                          // profiling: in front of the upload, of (a), (b), (c), behind (c)
@@ -31,6 +32,7 @@ void jpeg_dec_scratch_free(pa_engine* e) {
     if (s->frames) hipFree(s->frames);
     if (s->ivls) hipFree(s->ivls);
     if (s->status) hipFree(s->status);
+    if (s->order) hipFree(s->order);
     if (s->coef) hipFree(s->coef);
     if (s->planes) hipFree(s->planes);
     for (hipEvent_t ev : s->ev) if (ev) hipEventDestroy(ev);
@@ -86,7 +88,10 @@ int pa_jpeg_decode(pa_engine* e, const uint8_t* jpegs, const int64_t* offsets, i
 
     std::vector<JpegDecFrame> frames;
     std::vector<JpegDecInterval> ivls;
-    std::vector<int32_t> ivl_status;
+    std::vector<int32_t> ivl_status, order, split;
+    const long long split_min = e->jpeg_dec_split_min == 0 ? PA_JPEG_DEC_SPLIT_MIN_BYTES : e->jpeg_dec_split_min;      // < 0: never
+    const int split_sub = e->jpeg_dec_split_sub == 0 ? PA_JPEG_DEC_SPLIT_SUB_BYTES : e->jpeg_dec_split_sub;
+    long long last_split[4] = {0, 0, 0, 0};
     for (int f0 = 0; f0 < n; f0 += sub) {
         const int nf = std::min(sub, n - f0);
         const int64_t base = offsets[f0];
@@ -110,12 +115,32 @@ int pa_jpeg_decode(pa_engine* e, const uint8_t* jpegs, const int64_t* offsets, i
                 ivls.push_back({(long long)(at + v.begin), (long long)(at + v.end), i, v.first_mcu, v.mcus, 0});
         }
         const size_t need_f = frames.size() * sizeof(JpegDecFrame), need_i = ivls.size() * sizeof(JpegDecInterval);
-        const size_t need_s = ivls.size() * sizeof(int32_t);
-        if (s->data_cap < bytes + 16 || s->frames_cap < need_f || s->ivls_cap < need_i || s->status_cap < need_s ||
+        // which kernel decodes an interval: its length decides (an empty one has nothing to split)
+        order.clear();
+        split.clear();
+        int most_sub = 1;
+        for (size_t k = 0; k < ivls.size(); ++k) {
+            const long long len = ivls[k].end - ivls[k].begin;
+            if (split_min >= 0 && len > 0 && len >= split_min && ivls[k].mcus > 0) {
+                split.push_back((int32_t)k);
+                const uint32_t l = jpeg::split_len(ivls[k].begin, ivls[k].end);
+                const int subs = jpeg::split_count(l, jpeg::split_sub_bytes(l, split_sub));
+                most_sub = std::max(most_sub, subs);
+                last_split[1] += subs;
+            } else {
+                order.push_back((int32_t)k);
+            }
+        }
+        const int n_serial = (int)order.size(), n_split = (int)split.size();
+        order.insert(order.end(), split.begin(), split.end());
+        last_split[0] += n_split;
+        last_split[3] += n_serial;
+        const size_t need_s = 2 * ivls.size() * sizeof(int32_t), need_o = ivls.size() * sizeof(int32_t);
+        if (s->data_cap < bytes + 16 || s->frames_cap < need_f || s->ivls_cap < need_i || s->status_cap < need_s || s->order_cap < need_o ||
             s->coef_cap < coef_frame * nf || s->planes_cap < planes_frame * nf) {
             PA_HIP(e, hipStreamSynchronize(e->stream));          // a decode still queued uses what is about to go
             if (fit(e, &s->data, &s->data_cap, bytes + 16) || fit(e, &s->frames, &s->frames_cap, need_f) ||
-                fit(e, &s->ivls, &s->ivls_cap, need_i) || fit(e, &s->status, &s->status_cap, need_s) ||
+                fit(e, &s->ivls, &s->ivls_cap, need_i) || fit(e, &s->status, &s->status_cap, need_s) || fit(e, &s->order, &s->order_cap, need_o) ||
                 fit(e, &s->coef, &s->coef_cap, coef_frame * nf) || fit(e, &s->planes, &s->planes_cap, planes_frame * nf))
                 return 1;
         }
@@ -124,15 +149,18 @@ int pa_jpeg_decode(pa_engine* e, const uint8_t* jpegs, const int64_t* offsets, i
         if (bytes) PA_HIP(e, hipMemcpyAsync(s->data, jpegs + base, bytes, hipMemcpyHostToDevice, e->stream));
         PA_HIP(e, hipMemcpyAsync(s->frames, frames.data(), need_f, hipMemcpyHostToDevice, e->stream));
         PA_HIP(e, hipMemcpyAsync(s->ivls, ivls.data(), need_i, hipMemcpyHostToDevice, e->stream));
+        PA_HIP(e, hipMemcpyAsync(s->order, order.data(), need_o, hipMemcpyHostToDevice, e->stream));
         JpegDecArgs a{};
         a.data = s->data; a.ivls = s->ivls; a.frames = s->frames; a.coef = s->coef; a.ivl_status = s->status; a.planes = s->planes;
         a.dst = dst + (size_t)f0 * h * w * 3;
         a.n = nf; a.n_ivls = (int)ivls.size(); a.h = h; a.w = w; a.mcus_x = mcus_x; a.mcus_y = mcus_y;
+        a.order = s->order; a.n_serial = n_serial; a.n_split = n_split; a.sub_bytes = split_sub;
+        a.split_threads = std::min(kSplitMaxThreads, (most_sub + 63) / 64 * 64);
         int path = 0;
         const hipError_t r = launch_jpeg_decode(a, &path, e->stream, timed ? s->ev + 1 : nullptr);
         if (r != hipSuccess) PA_FAIL(e, "jpeg decode launch failed: %s", hipGetErrorString(r));
         e->jpeg_dec_last_path = path;
-        ivl_status.resize(ivls.size());
+        ivl_status.resize(2 * ivls.size());
         PA_HIP(e, hipMemcpyAsync(ivl_status.data(), s->status, need_s, hipMemcpyDeviceToHost, e->stream));
         PA_HIP(e, hipStreamSynchronize(e->stream));
         if (timed)
@@ -143,7 +171,28 @@ int pa_jpeg_decode(pa_engine* e, const uint8_t* jpegs, const int64_t* offsets, i
             }
         for (int i = 0; i < nf; ++i) status_host[f0 + i] = infos[(size_t)(f0 + i)].status;
         for (size_t k = 0; k < ivls.size(); ++k) status_host[f0 + ivls[k].frame] |= ivl_status[k];
+        for (int k = n_serial; k < n_serial + n_split; ++k)
+            last_split[2] = std::max<long long>(last_split[2], ivl_status[ivls.size() + (size_t)order[(size_t)k]]);
     }
+    for (int k = 0; k < 4; ++k) e->jpeg_dec_last_split[k] = last_split[k];
+    return 0;
+}
+
+int pa_jpeg_decode_set_split(pa_engine* e, int64_t min_bytes, int32_t sub_bytes) {
+    if (min_bytes < -1) PA_FAIL(e, "pa_jpeg_decode_set_split: min_bytes = %lld: 0 (the default), -1 (never split) or a length in bytes", (long long)min_bytes);
+    if (sub_bytes != 0 && (sub_bytes < jpeg::kSplitMinSubBytes || sub_bytes > jpeg::kSplitMaxSubBytes))
+        PA_FAIL(e, "pa_jpeg_decode_set_split: sub_bytes = %d outside %d .. %d (0: the default)", (int)sub_bytes, jpeg::kSplitMinSubBytes, jpeg::kSplitMaxSubBytes);
+    if (sub_bytes % 4) PA_FAIL(e, "pa_jpeg_decode_set_split: sub_bytes = %d is not a multiple of 4", (int)sub_bytes);
+    if (!e) PA_FAIL(e, "pa_jpeg_decode_set_split: the engine is NULL");
+    e->jpeg_dec_split_min = min_bytes;
+    e->jpeg_dec_split_sub = sub_bytes;
+    return 0;
+}
+
+int pa_jpeg_decode_last_split(pa_engine* e, int64_t out[4]) {
+    if (!out) PA_FAIL(e, "pa_jpeg_decode_last_split: out is NULL");
+    if (!e) PA_FAIL(e, "pa_jpeg_decode_last_split: the engine is NULL");
+    for (int k = 0; k < 4; ++k) out[k] = e->jpeg_dec_last_split[k];
     return 0;
 }
 

@@ -121,7 +121,7 @@ ABI_SYMBOLS = [
     "pa_render", "pa_render_check", "pa_render_last_path", "pa_glyph_rows", "pa_ball_read_resized",
     "pa_jpeg_encode", "pa_jpeg_check", "pa_jpeg_interval_bytes",
     "pa_jpeg_parse", "pa_jpeg_decode", "pa_jpeg_decode_last_path", "pa_jpeg_decode_last_times",
-    "pa_yolo_last_post_path",
+    "pa_yolo_last_post_path", "pa_jpeg_decode_set_split", "pa_jpeg_decode_last_split",
 ]
 
 
@@ -221,6 +221,8 @@ def load_library():
     lib.pa_jpeg_decode.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     lib.pa_jpeg_decode_last_path.argtypes = [vp]
     lib.pa_jpeg_decode_last_times.argtypes = [vp, vp]
+    lib.pa_jpeg_decode_set_split.argtypes = [vp, C.c_int64, i32]
+    lib.pa_jpeg_decode_last_split.argtypes = [vp, vp]
     lib.pa_engine_timer_start.argtypes = [vp]
     lib.pa_engine_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
     if lib.pa_abi_version() != 5:
@@ -323,6 +325,8 @@ def jpeg_interval_bytes(w: int) -> int:
 JPEG_DEC_MAX_DIM = 4096
 #: ``Engine.jpeg_decode_last_path()``: how the colour pass of the last decode stored its pixels
 JPEG_DEC_PATH_VECTOR, JPEG_DEC_PATH_BYTE = 1, 2
+#: the defaults of ``Engine.jpeg_decode_set_split`` (PA_JPEG_DEC_SPLIT_MIN_BYTES, PA_JPEG_DEC_SPLIT_SUB_BYTES)
+JPEG_DEC_SPLIT_MIN_BYTES, JPEG_DEC_SPLIT_SUB_BYTES = 7168, 128
 
 
 class pa_jpeg_huff(C.Structure):
@@ -553,6 +557,20 @@ class Engine:
         ms = (C.c_double * 5)()
         self._check(self.lib.pa_jpeg_decode_last_times(self.handle, ms))
         return dict(zip(("parse", "upload", "entropy", "idct", "colour"), (float(v) for v in ms)))
+
+    def jpeg_decode_set_split(self, min_bytes: int = 0, sub_bytes: int = 0) -> None:
+        """Which restart intervals of later ``jpeg_decode`` calls are split among the lanes of a workgroup
+        (``pa_jpeg_decode_set_split``): those of at least ``min_bytes`` bytes (0: the default, -1: none, today's one wave per interval
+        for all), in subsequences of ``sub_bytes`` bytes (0: the default, else a multiple of 4 in 4 .. 32768).  The pixels do not
+        depend on either."""
+        self._check(self.lib.pa_jpeg_decode_set_split(self.handle, int(min_bytes), int(sub_bytes)))
+
+    def jpeg_decode_last_split(self) -> dict:
+        """Of the last ``jpeg_decode``: ``split`` intervals on the split path, their ``subsequences``, the most ``rounds`` any of
+        them took, ``serial`` intervals on the one-wave kernel."""
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.pa_jpeg_decode_last_split(self.handle, out))
+        return dict(zip(("split", "subsequences", "rounds", "serial"), (int(v) for v in out)))
 
     def timer_start(self) -> None:
         """Tools: mark the compute stream with a HIP event; ``timer_stop`` -> milliseconds of device time queued since."""
