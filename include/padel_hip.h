@@ -408,7 +408,8 @@ int pa_engine_timer_stop(pa_engine* eng, float* ms);
  * keys: "impl" (2 bf16x3 kernels = default, 0 fp32-MFMA tap kernels, 1 fp32-MFMA LDS cross-check kernel),
  * "variant" (forced tile id, -1 auto), "tune",
  * "tap_pd" (2|3), "graph" (hipGraph replay of the op list), "alias" (liveness-shared activation arena),
- * "timeline" (s_memtime-instrumented 3x3 kernel, dump to pa_engine_set_timeline_path)                 */
+ * "timeline" (s_memtime-instrumented 3x3 kernel, dump to pa_engine_set_timeline_path),
+ * "lanes" (2 = default: a YOLO model may run alternate in-flight tickets on a second lane, 1: one lane; PADEL_LANES) */
 int pa_engine_set_tuning(pa_engine* eng, const char* key, int value);
 int pa_engine_set_timeline_path(pa_engine* eng, const char* path);
 
@@ -457,16 +458,28 @@ int pa_yolo_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, const
                   float* out_boxes, float* out_kpts, int32_t* out_counts);
 
 /* The same call in two halves, for pipelined batch loops (round 4): pa_yolo_submit enqueues everything pa_yolo_infer does
- * — preprocessing, network, decode, NMS, the result copies — behind whatever the engine's stream still holds and returns a
+ * — preprocessing, network, decode, NMS, the result copies — behind whatever the engine's stream holds at the call and returns a
  * ticket WITHOUT waiting; pa_yolo_wait blocks until that ticket's results are in the caller's arrays.  Submitting batch
  * k + 1 before waiting for batch k keeps the GPU busy while the host collects results and prepares the next call (the
  * reference's `predict` is synchronous per batch, players_tracker.py:351-359: its GPU idles there).
+ * LANES.  A ticket runs on one of the model's (at most two) lanes: a stream of its own with its own network input, activation
+ * arena and post-processing buffers.  A submit that finds the model's previous ticket still in flight (not waited for) goes to
+ * the other lane — allocated then, if the memory is there; otherwise the model stays on one lane — so that the workgroups of two
+ * batches share the chip (tuning "lanes", PADEL_LANES = 1 | 2).  Every ticket's results are bitwise what pa_yolo_infer gives.
+ * ORDERING, as observed by the caller, is still that of ONE stream: a ticket runs behind everything enqueued on the engine's
+ * stream before its submit (a conversion, a decode, a render: it sees their frames), and everything enqueued on the engine's
+ * stream after the submit — the next conversion into the same frame buffer, a render, a read-back, pa_engine_synchronize,
+ * pa_model_take_overflow — runs behind the ticket.  Two tickets with nothing between their submits but waits may run at the same
+ * time; work put on the engine's stream between two submits orders the second ticket behind the first, as before lanes.
+ * Tickets need NOT complete in submission order: pa_yolo_wait may be called in any order and returns when its own ticket is
+ * done.  pa_yolo_infer and pa_yolo_postprocess run on lane 0 and return with every outstanding ticket of either lane complete.
  * Requirements: frames in HBM (frames_on_device = 1), n <= max_batch, no profiling; out_* must be page-locked
  * (pa_host_register) and must not be touched between submit and wait — the ONE place where the library keeps caller
- * pointers past return.  At most PA_MAX_INFLIGHT tickets per model; tickets complete in submission order; the plan
+ * pointers past return.  At most PA_MAX_INFLIGHT tickets per model; the plan
  * (source size, imgsz, batch) must not change while tickets are in flight.  `overflow` (may be NULL): 1 if an activation of
- * an h2 model has left the fp16 range by the time this ticket finished (sticky until pa_model_take_overflow): the
- * results of this and of later tickets are then not to be used (see PA_DTYPE_H2).                                   */
+ * an h2 model has left the fp16 range by the time this ticket finished (sticky until pa_model_take_overflow, and shared by the
+ * lanes: a ticket always sees its own overflow, and may see its neighbour's): the results of this and of later tickets are then
+ * not to be used (see PA_DTYPE_H2).                                                                                  */
 #define PA_MAX_INFLIGHT 4
 int pa_yolo_submit(pa_model* m, const uint8_t* frames, int n, int h, int w, const pa_yolo_params* p,
                    float* out_boxes, float* out_kpts, int32_t* out_counts, int* ticket);
@@ -489,6 +502,14 @@ int pa_yolo_read_head(pa_model* m, int level, int n, float* out);
 /* which post-processing the model's last pa_yolo_infer / pa_yolo_submit / pa_yolo_postprocess took: 0 decode_kernel over head
  * maps, 1 the fused head tail (the heads' last convs and the decode in one kernel, no head map)                            */
 int pa_yolo_last_post_path(pa_model* m);
+/* lanes (pa_yolo_submit): how many the model's current plan has allocated (0 before a plan, 1, 2), and the lane (0 | 1) its last
+ * pa_yolo_infer / pa_yolo_submit / pa_yolo_postprocess ran on.  pa_yolo_read_head, pa_yolo_read_netin and
+ * pa_yolo_last_post_path refer to that lane.  pa_model_plan_bytes reports ONE lane's plan                              */
+int pa_model_lanes_allocated(pa_model* m);
+/* tests: passes of the Pillow resample of the model's current plan — 0 (no plan, letterbox, or a source of the target size), 1 (one
+ * axis changes), 2 (both: the horizontal pass writes a temporary that the vertical pass reads; every lane has its own)       */
+int pa_yolo_resample_passes(pa_model* m);
+int pa_model_last_lane(pa_model* m);
 
 /* the u8 network input (NHWC4: R,G,B,0 as the network sees them) the last pa_yolo_infer call built from its
  * first n frames — byte-exact check of the letterbox (cv2 INTER_LINEAR) / Pillow-bicubic preprocessing */

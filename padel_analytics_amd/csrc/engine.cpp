@@ -1,5 +1,5 @@
-// libpadel_hip.so — engine: owns one HIP stream per GPU, the packed weights and every activation
-// buffer in HBM, plans a graph for a (source size, imgsz, batch) and replays it per batch.
+// libpadel_hip.so — engine: owns the streams of one GPU (the main stream that orders its work, two lane streams for in-flight
+// YOLO batches, a copy stream), the packed weights and every activation buffer in HBM, plans a graph for a (source size, imgsz, batch) and replays it per batch.
 // C-ABI declared in include/padel_hip.h.  This file: engine and model lifecycle, tuning, memory and timer calls, the arena,
 // the op-list replay (run_ops / run_graph) and the profile text; engine_internal.h names the other files.
 #include "engine_internal.h"
@@ -12,6 +12,7 @@ thread_local std::string g_err;
 static int knob_raw(int v) { return v; }
 static int knob_flag(int v) { return v ? 1 : 0; }
 static int knob_tap_pd(int v) { return v == 3 ? 3 : 2; }
+static int knob_lanes(int v) { return v >= 2 ? 2 : 1; }
 static const struct Knob { const char* key; const char* env; int Tuning::*field; int (*norm)(int); } kKnobs[] = {
     {"variant", "PADEL_CONV_VARIANT", &Tuning::variant, knob_raw},
     {"tune", "PADEL_CONV_TUNE", &Tuning::tune, knob_raw},
@@ -20,6 +21,7 @@ static const struct Knob { const char* key; const char* env; int Tuning::*field;
     {"timeline", nullptr, &Tuning::timeline, knob_flag},
     {"alias", "PADEL_ALIAS", &Tuning::alias, knob_flag},
     {"fold_up", "PADEL_FOLD_UP", &Tuning::fold_up, knob_flag},
+    {"lanes", "PADEL_LANES", &Tuning::lanes, knob_lanes},
     {"fuse_stem", "PADEL_FUSE_STEM", &Tuning::fuse_stem, knob_raw},
     {"fuse_sppf", "PADEL_FUSE_SPPF", &Tuning::fuse_sppf, knob_raw},
     {"fuse_head", "PADEL_FUSE_HEAD", &Tuning::fuse_head, knob_flag},
@@ -44,10 +46,9 @@ int pa_engine_create(int device_id, pa_engine** out) {
     PA_HIP((pa_engine*)nullptr, hipSetDevice(device_id));
     pa_engine* e = new pa_engine();
     e->dev = device_id;
-    hipError_t r = hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking);
-    if (r != hipSuccess) { delete e; PA_FAIL((pa_engine*)nullptr, "hipStreamCreate: %s", hipGetErrorString(r)); }
+    hipError_t r = e->create_streams();
     if (r == hipSuccess) r = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking);
-    if (r != hipSuccess) { delete e; PA_FAIL((pa_engine*)nullptr, "hipStreamCreate: %s", hipGetErrorString(r)); }
+    if (r != hipSuccess) { pa_engine_destroy(e); PA_FAIL((pa_engine*)nullptr, "hipStreamCreate: %s", hipGetErrorString(r)); }
     r = hipMalloc((void**)&e->zeros, 256);
     if (r == hipSuccess) r = hipMemset(e->zeros, 0, 256);
     if (r != hipSuccess) { delete e; PA_FAIL((pa_engine*)nullptr, "zero page: %s", hipGetErrorString(r)); }
@@ -62,6 +63,39 @@ int pa_engine_create(int device_id, pa_engine** out) {
         if (const char* v = k.env ? getenv(k.env) : nullptr) e->t.*k.field = k.norm(atoi(v));
     *out = e;
     return 0;
+}
+
+hipError_t pa_engine::create_streams() {
+    hipError_t r = hipStreamCreateWithFlags(&main_, hipStreamNonBlocking);
+    for (int i = 0; i < kMaxLanes && r == hipSuccess; ++i) {
+        r = hipStreamCreateWithFlags(&lane_stream[i], hipStreamNonBlocking);
+        if (r == hipSuccess) r = hipEventCreateWithFlags(&fork_ev_[i], hipEventDisableTiming);
+    }
+    return r;
+}
+
+void pa_engine::destroy_streams() {
+    for (int i = 0; i < kMaxLanes; ++i) {
+        if (lane_stream[i]) { hipStreamSynchronize(lane_stream[i]); hipStreamDestroy(lane_stream[i]); }
+        if (fork_ev_[i]) hipEventDestroy(fork_ev_[i]);
+        lane_stream[i] = nullptr; fork_ev_[i] = nullptr;
+    }
+    if (main_) hipStreamDestroy(main_);
+    main_ = nullptr;
+}
+
+hipError_t pa_engine::fork_lane(int i) {
+    if (forked_seq_[i] == main_seq_) return hipSuccess;      // only joins since: waiting would put this lane behind the other one's ticket
+    hipError_t r = hipEventRecord(fork_ev_[i], main_);
+    if (r == hipSuccess) r = hipStreamWaitEvent(lane_stream[i], fork_ev_[i], 0);
+    if (r == hipSuccess) forked_seq_[i] = main_seq_;
+    return r;
+}
+
+hipError_t pa_engine::sync_lanes() {
+    for (hipStream_t s : lane_stream)
+        if (s) { const hipError_t r = hipStreamSynchronize(s); if (r != hipSuccess) return r; }
+    return hipSuccess;
 }
 
 int pa_engine_set_tuning(pa_engine* e, const char* key, int value) {
@@ -89,19 +123,20 @@ void pa_engine_destroy(pa_engine* e) {
     hipSetDevice(e->dev);
     pa_engine_comm_destroy(e);
     if (e->zeros) hipFree(e->zeros);
-    if (e->yuv_stage) { if (e->stream) hipStreamSynchronize(e->stream); hipFree(e->yuv_stage); }
-    if (e->render_stage) { if (e->stream) hipStreamSynchronize(e->stream); hipFree(e->render_stage); }
+    if (e->main_stream_wait_only()) hipStreamSynchronize(e->main_stream_wait_only());
+    if (e->yuv_stage) hipFree(e->yuv_stage);
+    if (e->render_stage) hipFree(e->render_stage);
     jpeg_scratch_free(e);
     jpeg_dec_scratch_free(e);
     for (hipEvent_t ev : e->timer_ev) if (ev) hipEventDestroy(ev);
-    if (e->stream) hipStreamDestroy(e->stream);
+    e->destroy_streams();
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);
     delete e;
 }
 
 int pa_engine_synchronize(pa_engine* e) {
     PA_HIP(e, hipSetDevice(e->dev));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     return 0;
 }
 
@@ -119,8 +154,8 @@ int pa_device_free(pa_engine* e, void* p) {
 }
 int pa_memcpy_h2d(pa_engine* e, void* dst, const void* src, size_t n) {
     PA_HIP(e, hipSetDevice(e->dev));
-    PA_HIP(e, hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, e->stream));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, e->main_stream()));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     return 0;
 }
 int pa_upload(pa_engine* e, void* dst, const void* src, size_t n) {
@@ -141,8 +176,8 @@ int pa_host_unregister(pa_engine* e, void* ptr) {
 }
 int pa_memcpy_d2h(pa_engine* e, void* dst, const void* src, size_t n) {
     PA_HIP(e, hipSetDevice(e->dev));
-    PA_HIP(e, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, e->stream));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, e->main_stream()));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     return 0;
 }
 
@@ -150,14 +185,14 @@ int pa_engine_timer_start(pa_engine* e) {
     if (!e) return 1;
     PA_HIP(e, hipSetDevice(e->dev));
     for (hipEvent_t& ev : e->timer_ev) if (!ev) PA_HIP(e, hipEventCreate(&ev));
-    PA_HIP(e, hipEventRecord(e->timer_ev[0], e->stream));
+    PA_HIP(e, hipEventRecord(e->timer_ev[0], e->main_stream()));
     return 0;
 }
 int pa_engine_timer_stop(pa_engine* e, float* ms) {
     if (!e || !ms) return 1;
     if (!e->timer_ev[0] || !e->timer_ev[1]) PA_FAIL(e, "pa_engine_timer_stop without pa_engine_timer_start");
     PA_HIP(e, hipSetDevice(e->dev));
-    PA_HIP(e, hipEventRecord(e->timer_ev[1], e->stream));
+    PA_HIP(e, hipEventRecord(e->timer_ev[1], e->main_stream()));
     PA_HIP(e, hipEventSynchronize(e->timer_ev[1]));
     PA_HIP(e, hipEventElapsedTime(ms, e->timer_ev[0], e->timer_ev[1]));
     return 0;
@@ -187,41 +222,51 @@ int pa_model_create(pa_engine* e, const pa_model_desc* desc, const float* weight
             for (int c = 0; c < 3; ++c)
                 if (m->tail.op[l][c] >= 0) m->tail_op[m->tail.op[l][c]] = 1;
     m->n_w = n_floats;
+    if (desc->task == PA_TASK_DETECT || desc->task == PA_TASK_POSE)
+        for (int i = 0; i < kMaxLanes; ++i) m->ln[i].stream = e->lane_stream[i];
     hipError_t r = hipMalloc((void**)&m->d_w, n_floats * sizeof(float) + kConvReadSlack);
     if (r == hipSuccess)
-        r = weights ? hipMemcpyAsync(m->d_w, weights, n_floats * sizeof(float), hipMemcpyHostToDevice, e->stream)
-                    : hipMemsetAsync(m->d_w, 0, n_floats * sizeof(float), e->stream);
-    if (r == hipSuccess) r = hipMemsetAsync(m->d_w + n_floats, 0, kConvReadSlack, e->stream);
+        r = weights ? hipMemcpyAsync(m->d_w, weights, n_floats * sizeof(float), hipMemcpyHostToDevice, e->main_stream())
+                    : hipMemsetAsync(m->d_w, 0, n_floats * sizeof(float), e->main_stream());
+    if (r == hipSuccess) r = hipMemsetAsync(m->d_w + n_floats, 0, kConvReadSlack, e->main_stream());
     if (r == hipSuccess) r = hipMalloc((void**)&m->d_ovf, 256);
-    if (r == hipSuccess) r = hipMemsetAsync(m->d_ovf, 0, 256, e->stream);
+    if (r == hipSuccess) r = hipMemsetAsync(m->d_ovf, 0, 256, e->main_stream());
     if (r == hipSuccess) r = hipHostMalloc((void**)&m->h_pin, 64 * sizeof(unsigned), hipHostMallocDefault);
     if (r == hipSuccess) memset(m->h_pin, 0, 64 * sizeof(unsigned));
     for (int k = 0; k < PA_MAX_INFLIGHT && r == hipSuccess; ++k) r = hipEventCreateWithFlags(&m->tk_ev[k], hipEventDisableTiming);
-    if (r == hipSuccess) r = hipStreamSynchronize(e->stream);
+    if (r == hipSuccess) r = hipStreamSynchronize(e->main_stream_wait_only());
     if (r != hipSuccess) { delete m; PA_FAIL(e, "weights upload: %s", hipGetErrorString(r)); }
     *out = m;
     return 0;
 }
 
 static void destroy_graphs(pa_model* m) {
-    for (auto& g : m->graphs) hipGraphExecDestroy(g.second);
-    m->graphs.clear();
+    for (Lane& L : m->ln) {
+        for (auto& g : L.graphs) hipGraphExecDestroy(g.second);
+        L.graphs.clear();
+    }
+}
+
+void free_lane(Lane& L) {
+    for (auto& g : L.graphs) hipGraphExecDestroy(g.second);
+    L.graphs.clear();
+    void* ptrs[] = {L.arena, L.d_fc, L.d_stage, L.d_netin, L.d_rs_tmp, L.d_cand, L.d_cidx, L.d_ccnt, L.d_keys, L.d_order, L.d_supp,
+                    L.d_oboxes, L.d_okpts, L.d_ocnt};
+    for (void* p : ptrs) if (p) hipFree(p);
+    const hipStream_t s = L.stream;
+    L = Lane{};
+    L.stream = s;
 }
 
 void free_plan(pa_model* m) {
-    destroy_graphs(m);
-    if (m->arena) hipFree(m->arena);
-    m->arena = nullptr;
-    m->bptr.clear();
-    void* ptrs[] = {m->d_netin, m->d_xtab, m->d_ytab, m->d_cand,
-                    m->d_cidx, m->d_ccnt, m->d_keys, m->d_order, m->d_supp, m->d_oboxes, m->d_okpts, m->d_ocnt, m->d_fc};
-    for (void* p : ptrs) if (p) hipFree(p);
-    resample_free(&m->rs);
-    m->d_fc = nullptr;
-    m->d_netin = nullptr;
+    (void)m->e->sync_lanes();
+    for (Lane& L : m->ln) free_lane(L);
+    if (m->d_xtab) hipFree(m->d_xtab);
+    if (m->d_ytab) hipFree(m->d_ytab);
     m->d_xtab = m->d_ytab = nullptr;
-    m->d_cand = nullptr; m->d_cidx = m->d_ccnt = nullptr; m->d_keys = nullptr; m->d_order = nullptr; m->d_supp = nullptr;
-    m->d_oboxes = m->d_okpts = nullptr; m->d_ocnt = nullptr;
+    resample_free(&m->rs);
+    m->lane1_refused = false;
+    m->last_lane = 0;
     m->planned = false;
     m->heads_stale = false;
 }
@@ -229,7 +274,7 @@ void free_plan(pa_model* m) {
 void pa_model_destroy(pa_model* m) {
     if (!m) return;
     hipSetDevice(m->e->dev);
-    hipStreamSynchronize(m->e->stream);
+    hipStreamSynchronize(m->e->main_stream_wait_only());      // (behind every ticket's join; free_plan drains the lanes themselves)
     free_plan(m);
     for (auto& r : m->prof) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
     if (m->d_frames) hipFree(m->d_frames);
@@ -237,7 +282,6 @@ void pa_model_destroy(pa_model* m) {
     if (m->d_w) hipFree(m->d_w);
     if (m->d_wr) hipFree(m->d_wr);
     if (m->d_ovf) hipFree(m->d_ovf);
-    if (m->d_stage) hipFree(m->d_stage);
     if (m->h_pin) hipHostFree(m->h_pin);
     for (int k = 0; k < PA_MAX_INFLIGHT; ++k) if (m->tk_ev[k]) hipEventDestroy(m->tk_ev[k]);
     delete m;
@@ -253,14 +297,14 @@ int pa_model_take_overflow(pa_model* m, int* out) {
     if (m->ovf_cached) {                 // pa_yolo_infer read the flag back with its results (nothing has run on the model since)
         v = m->h_ovf;
     } else {
-        PA_HIP(e, hipMemcpyAsync(&v, m->d_ovf, sizeof(v), hipMemcpyDeviceToHost, e->stream));
-        PA_HIP(e, hipStreamSynchronize(e->stream));
+        PA_HIP(e, hipMemcpyAsync(&v, m->d_ovf, sizeof(v), hipMemcpyDeviceToHost, e->main_stream()));
+        PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     }
     m->ovf_cached = false;
     m->h_ovf = 0;
     if (v) {
-        PA_HIP(e, hipMemsetAsync(m->d_ovf, 0, sizeof(v), e->stream));
-        PA_HIP(e, hipStreamSynchronize(e->stream));
+        PA_HIP(e, hipMemsetAsync(m->d_ovf, 0, sizeof(v), e->main_stream()));
+        PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     }
     *out = v ? 1 : 0;
     return 0;
@@ -268,34 +312,42 @@ int pa_model_take_overflow(pa_model* m, int* out) {
 
 int pa_model_set_max_batch(pa_model* m, int max_batch) {
     if (max_batch < 1) PA_FAIL(m->e, "max_batch %d", max_batch);
-    if (max_batch != m->max_batch) { hipSetDevice(m->e->dev); hipStreamSynchronize(m->e->stream); free_plan(m); m->max_batch = max_batch; }
+    if (max_batch != m->max_batch) { hipSetDevice(m->e->dev); hipStreamSynchronize(m->e->main_stream_wait_only()); free_plan(m); m->max_batch = max_batch; }
     return 0;
 }
 
 // The activation arena of a model whose network input size is set: graph_plan.cpp decides which buffers share bytes
 // (plan_activations), this allocates and zeroes what it asks for.
-int plan_buffers(pa_model* m, int batch) {
+int plan_buffers(pa_model* m, Lane& L, int batch, hipStream_t s) {
     pa_engine* e = m->e;
     BufferPlan bp;
     std::string why;
     if (plan_activations(m->d, m->fold_src, m->net_h, m->net_w, batch, e->t.alias != 0, bp, why, &m->tail)) PA_FAIL(e, "%s", why.c_str());
     m->fc_nout = 0;
-    for (const auto& o : m->ops) if (o.kind == PA_OP_GAP_FC) m->fc_nout = o.cout;
-    if (m->fc_nout) {
-        PA_HIP(e, hipMalloc((void**)&m->d_fc, (size_t)batch * 2 * kGapFcMaxOut * sizeof(float)));
-        PA_HIP(e, hipMemsetAsync(m->d_fc, 0, (size_t)batch * 2 * kGapFcMaxOut * sizeof(float), e->stream));
+    m->conv_flops = 0;
+    for (const auto& o : m->ops) {
+        if (o.kind == PA_OP_GAP_FC) m->fc_nout = o.cout;
+        if (o.kind == PA_OP_CONV) {
+            const int lvl = m->bufs[o.out_buf].level;
+            m->conv_flops += 2.0 * batch * (double)(m->net_h >> lvl) * (m->net_w >> lvl) * o.cout * o.cin * o.ksize * o.ksize;
+        }
     }
-    PA_HIP(e, hipMalloc(&m->arena, bp.arena_bytes + kConvReadSlack));
-    PA_HIP(e, hipMemsetAsync(m->arena, 0, bp.arena_bytes + kConvReadSlack, e->stream));
-    m->bptr.assign(m->bufs.size(), nullptr);
-    for (size_t i = 0; i < m->bufs.size(); ++i) m->bptr[i] = reinterpret_cast<float*>(static_cast<char*>(m->arena) + bp.off[i]);
+    if (m->fc_nout) {
+        PA_HIP(e, hipMalloc((void**)&L.d_fc, (size_t)batch * 2 * kGapFcMaxOut * sizeof(float)));
+        PA_HIP(e, hipMemsetAsync(L.d_fc, 0, (size_t)batch * 2 * kGapFcMaxOut * sizeof(float), s));
+    }
+    PA_HIP(e, hipMalloc(&L.arena, bp.arena_bytes + kConvReadSlack));
+    PA_HIP(e, hipMemsetAsync(L.arena, 0, bp.arena_bytes + kConvReadSlack, s));
+    L.bptr.assign(m->bufs.size(), nullptr);
+    for (size_t i = 0; i < m->bufs.size(); ++i) L.bptr[i] = reinterpret_cast<float*>(static_cast<char*>(L.arena) + bp.off[i]);
+    L.allocated = true;
     m->arena_bytes = bp.arena_bytes;
     m->logical_bytes = bp.logical_bytes;
     m->p_batch = batch;
     return 0;
 }
 
-ProfRec* prof_begin(pa_model* m, size_t idx, int kind, int ksize, double flops) {
+ProfRec* prof_begin(pa_model* m, hipStream_t s, size_t idx, int kind, int ksize, double flops) {
     if (!m->e->profiling) return nullptr;
     if (m->prof.size() <= idx) {
         m->prof.resize(idx + 1);
@@ -306,7 +358,7 @@ ProfRec* prof_begin(pa_model* m, size_t idx, int kind, int ksize, double flops) 
     r->kind = kind; r->ksize = ksize; r->flops = flops; r->ms = 0.f;
     r->M = r->cout = r->cin = r->stride = r->mf = r->nf = r->res = 0;
     r->tile = -1; r->family = "";
-    hipEventRecord(r->e0, m->e->stream);
+    hipEventRecord(r->e0, s);
     return r;
 }
 
@@ -319,15 +371,15 @@ static bool fold_active(const pa_model* m, int conv_op) {
 // models) and the tile id it will be requested with (a forced variant picks the tile of whichever path is selected).  An absorbed
 // upsample (find_upsample_folds) is attached here, where the requested tile resolves to a kernel that reads it: the 1x1 tap
 // tiles, and for a 3x3 consumer the patch kernel.
-static int conv_launch_args(const pa_model* m, size_t i, int n, ConvArgs& a, int* path_out = nullptr) {
+static int conv_launch_args(const pa_model* m, const Lane& L, size_t i, int n, ConvArgs& a, int* path_out = nullptr) {
     const pa_engine* e = m->e;
     const pa_op_desc& o = m->ops[i];
     const pa_buf_desc& ob = m->bufs[o.out_buf];
     const pa_buf_desc& ib = m->bufs[o.in_buf];
     const int Ho = m->net_h >> ob.level, Wo = m->net_w >> ob.level;
-    a.in = m->bptr[o.in_buf]; a.in_cs = ib.channels; a.in_choff = o.in_choff;
-    a.out = m->bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
-    a.res = o.res_buf >= 0 ? m->bptr[o.res_buf] : nullptr;
+    a.in = L.bptr[o.in_buf]; a.in_cs = ib.channels; a.in_choff = o.in_choff;
+    a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
+    a.res = o.res_buf >= 0 ? L.bptr[o.res_buf] : nullptr;
     a.res_cs = o.res_buf >= 0 ? m->bufs[o.res_buf].channels : 0; a.res_choff = o.res_choff;
     a.res_pre = (o.res_buf >= 0 && (o.flags & PA_CONV_RES_PREACT)) ? 1 : 0;
     a.zeros = e->zeros;
@@ -357,13 +409,13 @@ static int conv_launch_args(const pa_model* m, size_t i, int n, ConvArgs& a, int
                          : choose_conv_tap_variant(a.M, a.n16);
     if ((h2 || use_bx3) && fold_active(m, (int)i)) {
         const pa_op_desc& u = m->ops[m->fold_src[i]];       // the first up_c channels come from the coarse map
-        a.in2 = m->bptr[u.in_buf]; a.in2_cs = m->bufs[u.in_buf].channels; a.in2_choff = u.in_choff; a.up_c = u.cin;
+        a.in2 = L.bptr[u.in_buf]; a.in2_cs = m->bufs[u.in_buf].channels; a.in2_choff = u.in_choff; a.up_c = u.cin;
         if (!resolve_conv(path, a, lv, nullptr)) { a.in2 = nullptr; a.in2_cs = a.in2_choff = a.up_c = 0; }      // no kernel of this tile's chain reads it: the upsample runs
     }
     return lv;
 }
 
-void head_tail_convs(const pa_model* m, HeadTailArgs& a) {
+void head_tail_convs(const pa_model* m, const Lane& L, HeadTailArgs& a) {
     bool single = m->e->t.w_single != 0;
     for (int l = 0; l < 3; ++l)
         for (int c = 0; c < 3; ++c) {
@@ -372,7 +424,7 @@ void head_tail_convs(const pa_model* m, HeadTailArgs& a) {
             const int i = m->tail.op[l][c];
             if (i < 0) continue;
             const pa_op_desc& o = m->ops[i];
-            v.in = m->bptr[o.in_buf]; v.in_cs = m->bufs[o.in_buf].channels; v.in_choff = o.in_choff;
+            v.in = L.bptr[o.in_buf]; v.in_cs = m->bufs[o.in_buf].channels; v.in_choff = o.in_choff;
             v.w = m->d_w + o.w_off; v.bias = m->d_w + o.b_off; v.oscale = m->d_w + o.reserved;
             v.cin = o.cin; v.n16 = o.npad / 16;
             single = single && (o.flags & PA_CONV_W_SINGLE);
@@ -385,11 +437,11 @@ bool head_fused(const pa_model* m) {
     if (!e->t.fuse_head || m->d.dtype != PA_DTYPE_H2 || !m->tail.found || e->profiling || e->t.timeline || !m->planned) return false;
     HeadTailArgs a{};
     a.d.cs = m->bufs[m->d.head_buf[0]].channels; a.d.nc = m->d.nc; a.d.nk = m->d.nk;
-    head_tail_convs(m, a);
+    head_tail_convs(m, m->ln[0], a);          // (what it asks does not depend on the lane)
     return head_tail_h2_supported(a);
 }
 
-int run_tail_ops(pa_model* m, int n) {
+int run_tail_ops(pa_model* m, Lane& L, hipStream_t s, int n) {
     pa_engine* e = m->e;
     for (int l = 0; l < 3; ++l)
         for (int c = 0; c < 3; ++c) {
@@ -397,17 +449,16 @@ int run_tail_ops(pa_model* m, int n) {
             if (i < 0) continue;
             ConvArgs a{};
             int path = CONV_PATH_TAP;
-            const int lv = conv_launch_args(m, (size_t)i, n, a, &path);
-            const hipError_t r = launch_conv(path, a, lv, e->stream);
+            const int lv = conv_launch_args(m, L, (size_t)i, n, a, &path);
+            const hipError_t r = launch_conv(path, a, lv, s);
             if (r != hipSuccess) PA_FAIL(e, "op %d (head tail) launch failed: %s", i, hipGetErrorString(r));
         }
     return 0;
 }
 
 // replay the op list for `n` images (prof records appended starting at *pi)
-static int run_ops(pa_model* m, int n, size_t* pi) {
+static int run_ops(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
     pa_engine* e = m->e;
-    hipStream_t s = e->stream;
     const bool skip_tail = head_fused(m);          // the heads' last convs run inside the fused head tail (run_post)
     for (size_t i = 0; i < m->ops.size(); ++i) {
         const pa_op_desc& o = m->ops[i];
@@ -419,11 +470,11 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
         if (o.kind == PA_OP_CONV) {
             ConvArgs a{};
             int path = CONV_PATH_TAP;
-            const int lv = conv_launch_args(m, i, n, a, &path);
+            const int lv = conv_launch_args(m, L, i, n, a, &path);
             const bool f16 = path == CONV_PATH_F16, h2 = path == CONV_PATH_H2, use_bx3 = path == CONV_PATH_BX3;
             int bm = 0, bn = 0;
             conv_tile_shape(path, lv, &bm, &bn);            // profile rows carry BM, BN of the REQUESTED workgroup tile
-            pr = prof_begin(m, (*pi)++, o.kind, o.ksize, 2.0 * a.M * (double)o.cout * o.cin * o.ksize * o.ksize);
+            pr = prof_begin(m, s, (*pi)++, o.kind, o.ksize, 2.0 * a.M * (double)o.cout * o.cin * o.ksize * o.ksize);
             if (pr) { pr->M = a.M; pr->cout = o.cout; pr->cin = o.cin; pr->stride = o.stride; pr->mf = bm; pr->nf = bn; pr->res = a.res != nullptr; }
             // tuning only ("timeline"): collect the s_memtime timeline of this launch into timeline_path
             unsigned long long* dbg_dev = nullptr;
@@ -455,21 +506,21 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
             }
         } else if (o.kind == PA_OP_STEM) {
             StemArgs a{};
-            a.in = m->d_netin; a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off;
-            a.out = m->bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
+            a.in = L.d_netin; a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off;
+            a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
             a.H = m->net_h; a.W = m->net_w; a.Ho = Ho; a.Wo = Wo; a.cout = o.cout; a.B = n;
             a.out_f16 = m->d.dtype == PA_DTYPE_F16 ? 1 : m->d.dtype == PA_DTYPE_H2 ? 2 : 0;
             a.ovf_flag = m->d_ovf;
             a.opw = (m->wr_valid && i < m->wr_off.size() && m->wr_off[i] >= 0) ? (const void*)(m->d_wr + m->wr_off[i]) : nullptr;
-            pr = prof_begin(m, (*pi)++, o.kind, 3, 2.0 * n * Ho * Wo * (double)o.cout * 27);
+            pr = prof_begin(m, s, (*pi)++, o.kind, 3, 2.0 * n * Ho * Wo * (double)o.cout * 27);
             // tuning "fuse_stem": the stem and the stride-2 3x3 behind it (its only reader) as one kernel; the conv's own
             // turn in this loop is skipped (the profile shows both under the stem's record)
             if (e->t.fuse_stem && m->d.dtype == PA_DTYPE_H2 && m->stem_fuse[i]) {
                 ConvArgs ca{};
-                conv_launch_args(m, i + 1, n, ca);
+                conv_launch_args(m, L, i + 1, n, ca);
                 if (stem_l1_h2_supported(a, ca)) {
                     r = launch_stem_l1_h2(a, ca, s);
-                    prof_end(m, pr);
+                    prof_end(s, pr);
                     if (r != hipSuccess) PA_FAIL(e, "fused stem + layer 1 launch failed: %s", hipGetErrorString(r));
                     ++i;
                     continue;
@@ -477,56 +528,56 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
             }
             r = launch_stem(a, s);
         } else if (o.kind == PA_OP_SPPF_POOL) {
-            pr = prof_begin(m, (*pi)++, o.kind, 5, 0.0);
-            r = launch_sppf_pool(m->bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, o.cin, n, Ho, Wo, s, (int)m->d.dtype, e->t.fuse_sppf);
+            pr = prof_begin(m, s, (*pi)++, o.kind, 5, 0.0);
+            r = launch_sppf_pool(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, o.cin, n, Ho, Wo, s, (int)m->d.dtype, e->t.fuse_sppf);
         } else if (o.kind == PA_OP_UPSAMPLE2X) {
             if (m->fold_dst[i] >= 0) {                   // absorbed by its consumer conv?  (same decision as at that conv)
                 ConvArgs ca{};
-                conv_launch_args(m, (size_t)m->fold_dst[i], n, ca);
+                conv_launch_args(m, L, (size_t)m->fold_dst[i], n, ca);
                 if (ca.in2) continue;
             }
-            pr = prof_begin(m, (*pi)++, o.kind, 0, 0.0);
-            r = launch_upsample2x(m->bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, m->bptr[o.out_buf],
+            pr = prof_begin(m, s, (*pi)++, o.kind, 0, 0.0);
+            r = launch_upsample2x(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, L.bptr[o.out_buf],
                                   ob.channels, o.out_choff, o.cin, n, Ho / 2, Wo / 2, s, (int)m->d.dtype);
         } else if (o.kind == PA_OP_MAXPOOL2) {
-            pr = prof_begin(m, (*pi)++, o.kind, 2, 0.0);
-            r = launch_maxpool2(m->bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, m->bptr[o.out_buf],
+            pr = prof_begin(m, s, (*pi)++, o.kind, 2, 0.0);
+            r = launch_maxpool2(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, L.bptr[o.out_buf],
                                 ob.channels, o.out_choff, o.cin, n, Ho * 2, Wo * 2, s, (int)m->d.dtype);
         } else if (o.kind == PA_OP_MAXPOOL3S2) {
             const int lin = m->bufs[o.in_buf].level;
-            pr = prof_begin(m, (*pi)++, o.kind, 3, 0.0);
-            r = launch_maxpool3s2(m->bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, m->bptr[o.out_buf], ob.channels, o.out_choff,
+            pr = prof_begin(m, s, (*pi)++, o.kind, 3, 0.0);
+            r = launch_maxpool3s2(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, L.bptr[o.out_buf], ob.channels, o.out_choff,
                                   o.cin, n, m->net_h >> lin, m->net_w >> lin, Ho, Wo, s, m->d.dtype == PA_DTYPE_H2 ? 1 : 0);
         } else if (o.kind == PA_OP_STEM7) {
-            if (!m->d_netin) PA_FAIL(e, "op %zu: the 7x7 stem reads the u8 network input of pa_resnet_infer", i);
+            if (!L.d_netin) PA_FAIL(e, "op %zu: the 7x7 stem reads the u8 network input of pa_resnet_infer", i);
             const bool head = is_head_buf(m->d, o.out_buf);
             Stem7Args a{};
-            a.in = m->d_netin; a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off; a.lut = m->d_w + o.reserved;
-            a.out = m->bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
+            a.in = L.d_netin; a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off; a.lut = m->d_w + o.reserved;
+            a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
             a.H = m->net_h; a.W = m->net_w; a.Ho = Ho; a.Wo = Wo; a.B = n; a.act = o.act;
             a.out_h2 = (m->d.dtype == PA_DTYPE_H2 && !head) ? 1 : 0;
             a.ovf_flag = m->d_ovf;
-            pr = prof_begin(m, (*pi)++, o.kind, 7, 2.0 * n * Ho * Wo * 64.0 * 147.0);
+            pr = prof_begin(m, s, (*pi)++, o.kind, 7, 2.0 * n * Ho * Wo * 64.0 * 147.0);
             if (pr) { pr->M = n * Ho * Wo; pr->cout = 64; pr->cin = 3; pr->stride = 2; }
             r = launch_stem7(a, s);
         } else if (o.kind == PA_OP_GAP_FC) {
             const int lin = m->bufs[o.in_buf].level;
             const int hw = (m->net_h >> lin) * (m->net_w >> lin);
-            pr = prof_begin(m, (*pi)++, o.kind, 0, 2.0 * n * (double)o.cout * o.cin);
+            pr = prof_begin(m, s, (*pi)++, o.kind, 0, 2.0 * n * (double)o.cout * o.cin);
             if (pr) { pr->M = n; pr->cout = o.cout; pr->cin = o.cin; }
-            r = launch_gap_fc(m->bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, o.cin, n, hw, m->d_w + o.w_off, m->d_w + o.b_off,
-                              o.cout, m->d_fc, m->d_fc + (size_t)m->p_batch * kGapFcMaxOut, s, m->d.dtype == PA_DTYPE_H2 ? 1 : 0);
+            r = launch_gap_fc(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, o.cin, n, hw, m->d_w + o.w_off, m->d_w + o.b_off,
+                              o.cout, L.d_fc, L.d_fc + (size_t)m->p_batch * kGapFcMaxOut, s, m->d.dtype == PA_DTYPE_H2 ? 1 : 0);
         } else if (o.kind == PA_OP_DWCONV3) {
             const bool h2 = m->d.dtype == PA_DTYPE_H2;
             const bool head = is_head_buf(m->d, o.out_buf);
             DwConvArgs a{};
-            a.in = m->bptr[o.in_buf]; a.in_cs = m->bufs[o.in_buf].channels; a.in_choff = o.in_choff;
+            a.in = L.bptr[o.in_buf]; a.in_cs = m->bufs[o.in_buf].channels; a.in_choff = o.in_choff;
             a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off;
-            a.out = m->bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
-            if (o.res_buf >= 0) { a.res = m->bptr[o.res_buf]; a.res_cs = m->bufs[o.res_buf].channels; a.res_choff = o.res_choff; }
+            a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
+            if (o.res_buf >= 0) { a.res = L.bptr[o.res_buf]; a.res_cs = m->bufs[o.res_buf].channels; a.res_choff = o.res_choff; }
             a.C = o.cin; a.B = n; a.H = Ho; a.W = Wo; a.act = o.act;
             a.h2 = h2 ? 1 : 0; a.out_f32 = (h2 && head) ? 1 : 0; a.ovf_flag = m->d_ovf;
-            pr = prof_begin(m, (*pi)++, o.kind, 3, 2.0 * n * Ho * Wo * (double)o.cin * 9.0);
+            pr = prof_begin(m, s, (*pi)++, o.kind, 3, 2.0 * n * Ho * Wo * (double)o.cin * 9.0);
             if (pr) { pr->M = n * Ho * Wo; pr->cout = o.cout; pr->cin = o.cin; pr->stride = 1; pr->res = o.res_buf >= 0; }
             r = launch_dwconv3(a, s);
         } else if (o.kind == PA_OP_PSA_ATTN) {
@@ -534,16 +585,16 @@ static int run_ops(pa_model* m, int n, size_t* pi) {
             const bool head = is_head_buf(m->d, o.out_buf);
             AttnArgs a{};
             a.heads = o.stride; a.kd = o.ksize; a.hd = o.npad;
-            a.qkv = m->bptr[o.in_buf]; a.cs = m->bufs[o.in_buf].channels;
+            a.qkv = L.bptr[o.in_buf]; a.cs = m->bufs[o.in_buf].channels;
             a.q_choff = o.in_choff; a.k_choff = o.in_choff + a.heads * a.kd; a.v_choff = o.in_choff + 2 * a.heads * a.kd;
-            a.out = m->bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
+            a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
             a.N = Ho * Wo; a.B = n; a.scale = (float)(1.0 / std::sqrt((double)a.kd));
             a.h2 = h2 ? 1 : 0; a.out_f32 = (h2 && head) ? 1 : 0; a.ovf_flag = m->d_ovf;
-            pr = prof_begin(m, (*pi)++, o.kind, 0, 2.0 * n * (double)a.heads * a.N * (double)a.N * (a.kd + a.hd));
+            pr = prof_begin(m, s, (*pi)++, o.kind, 0, 2.0 * n * (double)a.heads * a.N * (double)a.N * (a.kd + a.hd));
             if (pr) { pr->M = n * a.N; pr->cout = o.cout; pr->cin = o.cin; pr->stride = a.heads; }
             r = launch_psa_attn(a, s);
         }
-        prof_end(m, pr);
+        prof_end(s, pr);
         if (r != hipSuccess) PA_FAIL(e, "op %zu (kind %d) launch failed: %s", i, o.kind, hipGetErrorString(r));
     }
     return 0;
@@ -559,17 +610,17 @@ static int ensure_operand_copies(pa_model* m) {
     // promise does not hold fails the call instead of computing silently wrong results
     {
         bool any = false;
-        PA_HIP(e, hipMemsetAsync(m->d_ovf + 32, 0, sizeof(unsigned) * 8, e->stream));        // scratch words of the 256-byte flag block
+        PA_HIP(e, hipMemsetAsync(m->d_ovf + 32, 0, sizeof(unsigned) * 8, e->main_stream()));        // scratch words of the 256-byte flag block
         for (size_t i = 0; i < m->ops.size(); ++i) {
             const pa_op_desc& o = m->ops[i];
             if (o.kind != PA_OP_CONV || !(o.flags & PA_CONV_W_SINGLE)) continue;
-            PA_HIP(e, launch_h2_mplane_check(m->d_w + o.w_off, (long long)o.npad * h2_ksteps(o.cin, o.ksize), m->d_ovf + 32, e->stream));
+            PA_HIP(e, launch_h2_mplane_check(m->d_w + o.w_off, (long long)o.npad * h2_ksteps(o.cin, o.ksize), m->d_ovf + 32, e->main_stream()));
             any = true;
         }
         if (any) {
             unsigned bad = 0;
-            PA_HIP(e, hipMemcpyAsync(&bad, m->d_ovf + 32, sizeof(bad), hipMemcpyDeviceToHost, e->stream));
-            PA_HIP(e, hipStreamSynchronize(e->stream));
+            PA_HIP(e, hipMemcpyAsync(&bad, m->d_ovf + 32, sizeof(bad), hipMemcpyDeviceToHost, e->main_stream()));
+            PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
             if (bad) PA_FAIL(e, "a conv flagged PA_CONV_W_SINGLE has a non-zero m plane in the weight blob (pack it without the flag, or with fp16-number weights)");
         }
     }
@@ -589,7 +640,7 @@ static int ensure_operand_copies(pa_model* m) {
         }
         if (total) {
             PA_HIP(e, hipMalloc((void**)&m->d_wr, total + 8192));          // the last chunk's look-ahead reads run 4 KB past a fragment
-            PA_HIP(e, hipMemsetAsync(m->d_wr + total, 0, 8192, e->stream));
+            PA_HIP(e, hipMemsetAsync(m->d_wr + total, 0, 8192, e->main_stream()));
         }
         m->wr_off = std::move(off);        // only once the allocation stands: a failed call leaves no offsets into a null d_wr
     }
@@ -597,42 +648,45 @@ static int ensure_operand_copies(pa_model* m) {
         if (m->wr_off[i] < 0) continue;
         const pa_op_desc& o = m->ops[i];
         if (o.kind == PA_OP_STEM) {
-            PA_HIP(e, launch_stem_l1_operands(m->d_w + o.w_off, o.cout, m->d_wr + m->wr_off[i], e->stream));
+            PA_HIP(e, launch_stem_l1_operands(m->d_w + o.w_off, o.cout, m->d_wr + m->wr_off[i], e->main_stream()));
             continue;
         }
-        PA_HIP(e, launch_h2r_repack(m->d_w + o.w_off, m->d_wr + m->wr_off[i], o.npad / 16, o.cin, o.ksize, e->stream));
+        PA_HIP(e, launch_h2r_repack(m->d_w + o.w_off, m->d_wr + m->wr_off[i], o.npad / 16, o.cin, o.ksize, e->main_stream()));
     }
+    // (built on the main stream, read on the lanes: the lanes do not fork for it, the host waits once per model instead)
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     m->wr_valid = true;
     return 0;
 }
 
 // run_ops, or (tuning "graph", not while profiling) the replay of its capture for this batch size: the op list of
 // an n-scale graph is ~100 launches of 10-40 us each, where per-launch host work shows
-int run_graph(pa_model* m, int n, size_t* pi) {
+int run_graph(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
     pa_engine* e = m->e;
     if (ensure_operand_copies(m)) return 1;
-    if (!e->t.graph || e->profiling || e->t.timeline) return run_ops(m, n, pi);
+    if (!e->t.graph || e->profiling || e->t.timeline) return run_ops(m, L, s, n, pi);
     if (m->graph_epoch != e->tuning_epoch) {            // kernel choice may have changed since the capture
-        PA_HIP(e, hipStreamSynchronize(e->stream));
+        PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
+        PA_HIP(e, e->sync_lanes());
         destroy_graphs(m);
         m->graph_epoch = e->tuning_epoch;
     }
-    auto it = m->graphs.find(n);
-    if (it == m->graphs.end()) {
+    auto it = L.graphs.find(n);
+    if (it == L.graphs.end()) {
         hipGraph_t g = nullptr;
         hipGraphExec_t ge = nullptr;
-        PA_HIP(e, hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+        PA_HIP(e, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         size_t dummy = 0;
-        const int rc = run_ops(m, n, &dummy);
-        const hipError_t r = hipStreamEndCapture(e->stream, &g);
+        const int rc = run_ops(m, L, s, n, &dummy);
+        const hipError_t r = hipStreamEndCapture(s, &g);
         if (rc) { if (g) hipGraphDestroy(g); return 1; }
         if (r != hipSuccess) PA_FAIL(e, "hipStreamEndCapture: %s", hipGetErrorString(r));
         const hipError_t ri = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
         hipGraphDestroy(g);
         if (ri != hipSuccess) PA_FAIL(e, "hipGraphInstantiate: %s", hipGetErrorString(ri));
-        it = m->graphs.emplace(n, ge).first;
+        it = L.graphs.emplace(n, ge).first;
     }
-    PA_HIP(e, hipGraphLaunch(it->second, e->stream));
+    PA_HIP(e, hipGraphLaunch(it->second, s));
     return 0;
 }
 
@@ -654,14 +708,26 @@ int pa_model_plan_bytes(pa_model* m, size_t* arena_bytes, size_t* logical_bytes)
 int pa_model_fill_arena(pa_model* m, int byte_value) {
     if (!m) return 1;
     pa_engine* e = m->e;
-    if (!m->planned || !m->arena) PA_FAIL(e, "pa_model_fill_arena: no plan yet");
+    if (!m->planned || !m->ln[0].arena) PA_FAIL(e, "pa_model_fill_arena: no plan yet");
     PA_HIP(e, hipSetDevice(e->dev));
-    PA_HIP(e, hipMemsetAsync(m->arena, byte_value & 0xFF, m->arena_bytes, e->stream));
-    // (the u8 network input as well: the preprocessing of the next call writes all four bytes of every pixel)
-    if (m->d_netin) PA_HIP(e, hipMemsetAsync(m->d_netin, byte_value & 0xFF, (size_t)m->p_batch * m->net_h * m->net_w * 4, e->stream));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    for (Lane& L : m->ln) {          // every lane the model has, each on the stream its batches run on
+        if (!L.allocated) continue;
+        const hipStream_t s = L.stream ? L.stream : e->main_stream();
+        PA_HIP(e, hipMemsetAsync(L.arena, byte_value & 0xFF, m->arena_bytes, s));
+        // (the u8 network input as well: the preprocessing of the next call writes all four bytes of every pixel)
+        if (L.d_netin) PA_HIP(e, hipMemsetAsync(L.d_netin, byte_value & 0xFF, (size_t)m->p_batch * m->net_h * m->net_w * 4, s));
+        PA_HIP(e, hipStreamSynchronize(s));
+    }
     return 0;
 }
+
+int pa_model_lanes_allocated(pa_model* m) {
+    int n = 0;
+    if (m) for (const Lane& L : m->ln) n += L.allocated ? 1 : 0;
+    return n;
+}
+
+int pa_model_last_lane(pa_model* m) { return m ? m->last_lane : 0; }
 
 int pa_model_profile_text(pa_model* m, char* buf, size_t cap) {
     size_t off = 0;

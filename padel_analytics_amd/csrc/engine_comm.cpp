@@ -83,7 +83,7 @@ int pa_engine_comm_init(pa_engine* e, const void* unique_id, size_t id_bytes, in
 void pa_engine_comm_destroy(pa_engine* e) {
     if (!e || !e->comm) return;
     hipSetDevice(e->dev);
-    hipStreamSynchronize(e->stream);
+    hipStreamSynchronize(e->main_stream_wait_only());
     if (e->comm->comm) e->comm->CommDestroy(e->comm->comm);
     delete e->comm;
     e->comm = nullptr;
@@ -94,9 +94,9 @@ int pa_engine_bcast(pa_engine* e, void* dev_ptr, size_t nbytes, int root) {
     if (!e || !dev_ptr) return 1;
     if (!e->comm) PA_FAIL(e, "pa_engine_bcast: call pa_engine_comm_init first");
     PA_HIP(e, hipSetDevice(e->dev));
-    const ncclResult_t r = e->comm->Broadcast(dev_ptr, dev_ptr, nbytes, ncclUint8, root, e->comm->comm, e->stream);
+    const ncclResult_t r = e->comm->Broadcast(dev_ptr, dev_ptr, nbytes, ncclUint8, root, e->comm->comm, e->main_stream());
     if (r != ncclSuccess) PA_FAIL(e, "ncclBroadcast: %s", e->comm->GetErrorString(r));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     return 0;
 }
 
@@ -118,9 +118,9 @@ int pa_engine_bcast_weights_from(pa_engine* e, pa_model* src, pa_model* dst, int
     PA_HIP(e, hipSetDevice(e->dev));
     dst->wr_valid = false;
     const void* send = src ? src->d_w : dst->d_w;
-    const ncclResult_t r = e->comm->Broadcast(send, dst->d_w, dst->n_w * sizeof(float), ncclUint8, root, e->comm->comm, e->stream);
+    const ncclResult_t r = e->comm->Broadcast(send, dst->d_w, dst->n_w * sizeof(float), ncclUint8, root, e->comm->comm, e->main_stream());
     if (r != ncclSuccess) PA_FAIL(e, "ncclBroadcast: %s", e->comm->GetErrorString(r));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     return 0;
 }
 
@@ -136,12 +136,12 @@ int pa_engine_gather_sizes(pa_engine* e, size_t nbytes, uint64_t* sizes) {
     unsigned long long* d_sizes = nullptr;
     PA_HIP(e, hipMalloc((void**)&d_sizes, (size_t)(nranks + 1) * sizeof(unsigned long long)));
     const unsigned long long mine = nbytes;
-    hipError_t h = hipMemcpyAsync(d_sizes + nranks, &mine, sizeof(mine), hipMemcpyHostToDevice, e->stream);
+    hipError_t h = hipMemcpyAsync(d_sizes + nranks, &mine, sizeof(mine), hipMemcpyHostToDevice, e->main_stream());
     ncclResult_t r = ncclSuccess;
-    if (h == hipSuccess) r = c->AllGather(d_sizes + nranks, d_sizes, 1, ncclUint64, c->comm, e->stream);
+    if (h == hipSuccess) r = c->AllGather(d_sizes + nranks, d_sizes, 1, ncclUint64, c->comm, e->main_stream());
     std::vector<unsigned long long> hs((size_t)nranks);
-    if (h == hipSuccess && r == ncclSuccess) h = hipMemcpyAsync(hs.data(), d_sizes, (size_t)nranks * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream);
-    if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
+    if (h == hipSuccess && r == ncclSuccess) h = hipMemcpyAsync(hs.data(), d_sizes, (size_t)nranks * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->main_stream());
+    if (h == hipSuccess) h = hipStreamSynchronize(e->main_stream_wait_only());
     hipFree(d_sizes);
     if (r != ncclSuccess) PA_FAIL(e, "ncclAllGather: %s", c->GetErrorString(r));
     if (h != hipSuccess) PA_FAIL(e, "pa_engine_gather_sizes: %s", hipGetErrorString(h));
@@ -171,7 +171,7 @@ int pa_engine_gather(pa_engine* e, const void* send, size_t nbytes, void* recv, 
     ncclResult_t r = ncclSuccess;
     if (me != root && nbytes) {
         h = hipMalloc((void**)&d_send, nbytes);
-        if (h == hipSuccess) h = hipMemcpyAsync(d_send, send, nbytes, hipMemcpyHostToDevice, e->stream);
+        if (h == hipSuccess) h = hipMemcpyAsync(d_send, send, nbytes, hipMemcpyHostToDevice, e->main_stream());
     }
     if (me == root && total) h = hipMalloc((void**)&d_recv, total);
     // (an allocation failure still enters the group with nothing posted: the peers' sends then fail inside RCCL instead of hanging)
@@ -180,11 +180,11 @@ int pa_engine_gather(pa_engine* e, const void* send, size_t nbytes, void* recv, 
         if (me == root) {
             size_t off = 0;
             for (int k = 0; k < nranks && r == ncclSuccess; ++k) {
-                if (k != root && sizes[k]) r = c->Recv(d_recv + off, (size_t)sizes[k], ncclUint8, k, c->comm, e->stream);
+                if (k != root && sizes[k]) r = c->Recv(d_recv + off, (size_t)sizes[k], ncclUint8, k, c->comm, e->main_stream());
                 off += (size_t)sizes[k];
             }
         } else if (nbytes) {
-            r = c->Send(d_send, nbytes, ncclUint8, root, c->comm, e->stream);
+            r = c->Send(d_send, nbytes, ncclUint8, root, c->comm, e->main_stream());
         }
     }
     const ncclResult_t r2 = c->GroupEnd();
@@ -194,11 +194,11 @@ int pa_engine_gather(pa_engine* e, const void* send, size_t nbytes, void* recv, 
         for (int k = 0; k < nranks && h == hipSuccess; ++k) {
             const size_t nb = (size_t)sizes[k];
             if (k == root) { if (nb) memcpy((char*)recv + off, send, nb); }
-            else if (nb) h = hipMemcpyAsync((char*)recv + off, d_recv + off, nb, hipMemcpyDeviceToHost, e->stream);
+            else if (nb) h = hipMemcpyAsync((char*)recv + off, d_recv + off, nb, hipMemcpyDeviceToHost, e->main_stream());
             off += nb;
         }
     }
-    if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
+    if (h == hipSuccess) h = hipStreamSynchronize(e->main_stream_wait_only());
     if (d_send) hipFree(d_send);
     if (d_recv) hipFree(d_recv);
     if (r != ncclSuccess) PA_FAIL(e, "ncclSend/Recv: %s", c->GetErrorString(r));
@@ -213,11 +213,11 @@ int pa_engine_allreduce_max(pa_engine* e, double* value) {
     PA_HIP(e, hipSetDevice(e->dev));
     double* d = nullptr;
     PA_HIP(e, hipMalloc((void**)&d, sizeof(double)));
-    hipError_t h = hipMemcpyAsync(d, value, sizeof(double), hipMemcpyHostToDevice, e->stream);
+    hipError_t h = hipMemcpyAsync(d, value, sizeof(double), hipMemcpyHostToDevice, e->main_stream());
     ncclResult_t r = ncclSuccess;
-    if (h == hipSuccess) r = e->comm->AllReduce(d, d, 1, ncclDouble, ncclMax, e->comm->comm, e->stream);
-    if (h == hipSuccess && r == ncclSuccess) h = hipMemcpyAsync(value, d, sizeof(double), hipMemcpyDeviceToHost, e->stream);
-    if (h == hipSuccess) h = hipStreamSynchronize(e->stream);
+    if (h == hipSuccess) r = e->comm->AllReduce(d, d, 1, ncclDouble, ncclMax, e->comm->comm, e->main_stream());
+    if (h == hipSuccess && r == ncclSuccess) h = hipMemcpyAsync(value, d, sizeof(double), hipMemcpyDeviceToHost, e->main_stream());
+    if (h == hipSuccess) h = hipStreamSynchronize(e->main_stream_wait_only());
     hipFree(d);
     if (r != ncclSuccess) PA_FAIL(e, "ncclAllReduce: %s", e->comm->GetErrorString(r));
     if (h != hipSuccess) PA_FAIL(e, "pa_engine_allreduce_max: %s", hipGetErrorString(h));

@@ -1,7 +1,7 @@
 // Shared by the engine's translation units (engine*.cpp); not part of the C-ABI (include/padel_hip.h).
 //   engine.cpp           engine and model lifecycle, tuning, memory and timer calls, the arena, run_ops / run_graph, profile text
 //   engine_pre.cpp       preprocessing shared by the model families: frame staging, the Pillow resample, YUV -> BGR
-//   engine_yolo.cpp      YOLO plan, prepare, enqueue, post-processing, tickets, read-backs
+//   engine_yolo.cpp      YOLO plan (per lane), prepare, enqueue, post-processing, tickets and their lanes, read-backs
 //   engine_tracknet.cpp  pa_tracknet_infer and the ball session
 //   engine_resnet.cpp    the ResNet-50 court-keypoint regressor
 //   engine_render.cpp    pa_render: marks on BGR frames -> BGR / YUV 4:2:0 (the refusals and the font: render_check.cpp, host only)
@@ -12,6 +12,7 @@
 #pragma once
 #include "../../include/padel_hip.h"
 #include "graph_plan.h"
+#include "lane_plan.h"
 #include "kernels.h"
 
 #include <algorithm>
@@ -26,7 +27,7 @@
 using namespace padel;
 
 // Tuning knobs: read from the environment ONCE at pa_engine_create (PADEL_CONV_IMPL=tap|bx3, PADEL_CONV_VARIANT,
-// PADEL_CONV_TUNE, PADEL_CONV_TAP_PD, PADEL_GRAPH, PADEL_ALIAS), changed afterwards only through
+// PADEL_CONV_TUNE, PADEL_CONV_TAP_PD, PADEL_GRAPH, PADEL_ALIAS, PADEL_LANES), changed afterwards only through
 // pa_engine_set_tuning — the replay loop never touches getenv.
 struct Tuning {
     int impl = 2;        // 2 (default): bf16x3 kernels — fp32 values split exactly into 3 bf16, 6 products on the bf16
@@ -45,6 +46,8 @@ struct Tuning {
     int fuse_head = 1;   // 1: h2 Detect / Pose models whose plan found the head tail (graph_plan.h: HeadTail) run the heads' last 1x1 convs and the
                          // decode as ONE kernel (head_tail_h2.hip) and never write the head maps; 0: the convs, then decode_kernel.  Bitwise the same
                          // detections; off while profiling or collecting a timeline (the profile keeps its rows)
+    int lanes = 2;       // 2: a YOLO model whose submit finds its last ticket still in flight gets a second lane (struct Lane) and alternate
+                         // tickets run on two streams; 1: everything on lane 0.  Bitwise the same results
     int fold_up = 1;     // 1: an nn.Upsample(2) whose only reader is a bf16x3 1x1 conv is never materialised (the conv
                          // fetches those channels at [y >> 1][x >> 1] of the coarse map), 0: run the upsample kernel
 };
@@ -55,7 +58,26 @@ struct JpegDecScratch;
 
 struct pa_engine {
     int dev = 0;
-    hipStream_t stream = nullptr;
+    // The main stream: everything but the YOLO lanes runs on it, and it is what orders the engine's work (padel_hip.h).  It is
+    // handed out by main_stream() alone, which counts the hand-outs: a lane forks from the main stream (fork_lane) only when
+    // something other than a ticket's join was put on it since that lane last forked, so a user that did not go through the
+    // accessor would be work a lane does not wait for.  The member is private: such a use does not compile.
+    hipStream_t main_stream() { ++main_seq_; return main_; }
+    // ... and for a host-side wait alone (hipStreamSynchronize, a null test): nothing is enqueued, so nothing is counted — a wait
+    // between two submits must not put the second ticket's lane behind the first ticket's join.  What the host does after such a
+    // wait is complete before the next submit is made, so no lane has to fork for it.  Never hand this to a call that enqueues.
+    hipStream_t main_stream_wait_only() const { return main_; }
+    hipError_t create_streams();                 // engine.cpp
+    void destroy_streams();
+    // lane_stream[i] waits for what the main stream holds (nothing to do when only joins were enqueued since its last fork)
+    hipError_t fork_lane(int i);
+    // the main stream waits for ev, recorded on a lane stream: what is enqueued on the main stream later runs behind that ticket
+    hipError_t join_lane(hipEvent_t ev) { return hipStreamWaitEvent(main_, ev, 0); }
+    hipError_t sync_lanes();                     // both lane streams drained (the main stream is the caller's business)
+    // The lanes' streams belong to the engine, not to the model: the runner walks its trackers one after the other, and the
+    // runtime maps streams onto a handful of hardware queues (two streams on one queue do not overlap), so three models bring
+    // no six streams.  A model's Lane carries the stream it runs on.
+    hipStream_t lane_stream[kMaxLanes] = {nullptr, nullptr};
     hipStream_t copy_stream = nullptr;   // uploads that must not queue behind compute (pa_upload)
     std::string err;
     bool profiling = false;
@@ -64,17 +86,22 @@ struct pa_engine {
     int tuning_epoch = 0;     // bumped by pa_engine_set_tuning: captured graphs of an older epoch are discarded
     std::string timeline_path;
     pa_comm* comm = nullptr;  // RCCL communicator (pa_engine_comm_init), optional
-    uint8_t* yuv_stage = nullptr; size_t yuv_stage_cap = 0;   // pa_yuv420_to_bgr: raw YUV bytes of a host source, filled and read on `stream` only
+    uint8_t* yuv_stage = nullptr; size_t yuv_stage_cap = 0;   // pa_yuv420_to_bgr: raw YUV bytes of a host source, filled and read on the main stream only
     int yuv_last_path = 0;    // 1 vector, 2 byte: what the last pa_yuv420_to_bgr launched (pa_yuv_last_path)
     hipEvent_t timer_ev[2]{};  // pa_engine_timer_start / _stop, created on first use
-    uint8_t* render_stage = nullptr; size_t render_stage_cap = 0;   // pa_render: the resolved marks and first[] of the call in flight, filled and read on `stream` only
+    uint8_t* render_stage = nullptr; size_t render_stage_cap = 0;   // pa_render: the resolved marks and first[] of the call in flight, filled and read on the main stream only
     int render_last_path = 0; // 1 vector, 2 byte: what the last pa_render launched (pa_render_last_path)
-    JpegScratch* jpeg = nullptr;   // pa_jpeg_encode: slots, tables and the gathered frames, grown on demand, used on `stream` only (engine_jpeg.cpp)
+    JpegScratch* jpeg = nullptr;   // pa_jpeg_encode: slots, tables and the gathered frames, grown on demand, used on the main stream only (engine_jpeg.cpp)
     JpegDecScratch* jpeg_dec = nullptr;   // pa_jpeg_decode: compressed bytes, tables, coefficients and planes, likewise (engine_jpeg_decode.cpp)
     int jpeg_dec_last_path = 0;    // 1 vector, 2 byte: what the last pa_jpeg_decode launched for its colour pass (pa_jpeg_decode_last_path)
     long long jpeg_dec_split_min = 0;   // pa_jpeg_decode_set_split as given: 0 the default, -1 never; an interval of at least this many bytes is split
     int jpeg_dec_split_sub = 0;         // ... its subsequences' bytes, 0 the default
     long long jpeg_dec_last_split[4] = {0, 0, 0, 0};   // pa_jpeg_decode_last_split
+private:
+    hipStream_t main_ = nullptr;
+    unsigned long long main_seq_ = 1;                  // hand-outs of main_
+    unsigned long long forked_seq_[kMaxLanes] = {0, 0};   // main_seq_ at the lane's last fork
+    hipEvent_t fork_ev_[kMaxLanes] = {nullptr, nullptr};
 };
 
 extern thread_local std::string g_err;      // errors of calls that have no engine yet (pa_last_error(NULL))
@@ -105,7 +132,38 @@ struct ResamplePlan {
     int sh = 0, sw = 0, dh = 0, dw = 0;
     int32_t *d_hb = nullptr, *d_hk = nullptr, *d_vb = nullptr, *d_vk = nullptr;
     int hks = 0, vks = 0;
-    uint8_t* d_tmp = nullptr;
+    uint8_t* d_tmp = nullptr; size_t tmp_bytes = 0;   // the temporary between the passes and its size (a second lane allocates as much)
+};
+
+// A lane: everything ONE in-flight YOLO batch writes on the device, so that two batches of a model can run at the same time on two
+// streams.  Lane 0 is the plan's (every model has it; TrackNet / ResNet models use nothing else and run it on the main stream);
+// lane 1 of a YOLO model is allocated by the first pa_yolo_submit that finds lane 0's ticket still in flight (lane_plan.h).
+// Audit of every device pointer plan_yolo, plan_buffers, run_ops, run_post, head_tail_convs and run_tail_ops hand to a kernel:
+//   per lane (written per batch): arena / bptr (every activation, in / in2 / out / res of the convs, the head-tail convs' inputs,
+//     lv[].buf), d_fc, d_stage, d_netin, the Pillow resample temporary (lane 0: ResamplePlan::d_tmp, lane 1: d_rs_tmp), d_cand,
+//     d_cidx, d_ccnt, d_keys, d_order, d_supp, d_oboxes, d_okpts, d_ocnt, the timeline scratch (allocated per launch), and the
+//     captured graphs, which hold these pointers;
+//   shared, read-only while tickets run: d_w (w, bias, oscale, w3, lut), d_wr (wr, opw; rebuilt on the main stream, then a host
+//     wait), d_xtab / d_ytab, the resample tables d_hb / d_hk / d_vb / d_vk, d_classes (replaced only after a main-stream wait,
+//     which the joins make a wait for every ticket), e->zeros, the caller's frames;
+//   shared, sticky by design: d_ovf (kernels only ever set it; a ticket reads it back after its own kernels, so it sees its own
+//     overflow; a neighbour's can only make it report 1 early, which callers treat as "recompute").  d_frames is pa_yolo_infer's
+//     alone (host frames; a submit refuses them).
+struct Lane {
+    bool allocated = false;
+    hipStream_t stream = nullptr;          // e->lane_stream[i] (YOLO models; not owned), nullptr: the model runs on the main stream
+    void* arena = nullptr;                 // what bptr points into
+    std::vector<float*> bptr;
+    float* d_fc = nullptr;                 // graphs with a PA_OP_GAP_FC op: [max_batch][kGapFcMaxOut] logits, then as many probabilities (plan_buffers)
+    float* d_stage = nullptr; size_t stage_cap = 0;   // h2 generic graphs: fp32 input staged here before it is encoded
+    uint8_t* d_netin = nullptr;
+    HeadLevel lv[3]{};
+    float* d_cand = nullptr; int32_t* d_cidx = nullptr; int32_t* d_ccnt = nullptr;
+    uint64_t* d_keys = nullptr; int32_t* d_order = nullptr; uint8_t* d_supp = nullptr;
+    float* d_oboxes = nullptr; float* d_okpts = nullptr; int32_t* d_ocnt = nullptr;
+    std::map<int, hipGraphExec_t> graphs;  // op-list replay per batch size (tuning "graph")
+    uint8_t* d_rs_tmp = nullptr;           // lane 1: its own temporary between the resample passes (lane 0 uses the plan's)
+    LaneState st;                          // pick_lane's view
 };
 
 struct pa_model {
@@ -126,18 +184,19 @@ struct pa_model {
     std::vector<long long> wr_off;         // op -> byte offset into d_wr, -1: no copy
     bool wr_valid = false;
     unsigned* d_ovf = nullptr;             // h2 models: sticky "a value did not fit fp16" flag (pa_model_take_overflow)
-    float* d_stage = nullptr; size_t stage_cap = 0;   // h2 generic graphs: fp32 input staged here before it is encoded
-    float* d_fc = nullptr;                 // graphs with a PA_OP_GAP_FC op: [max_batch][kGapFcMaxOut] logits, then as many probabilities (plan_buffers)
     int fc_nout = 0;                       // outputs of that op (0: the graph has none)
     int max_batch = 64;
+    Lane ln[kMaxLanes];                    // ln[0]: the plan's; ln[1]: lazily, YOLO models only
+    int last_lane = 0;                     // the lane of the model's last call (pa_yolo_read_head, pa_yolo_read_netin, pa_model_last_lane)
+    bool lane1_refused = false;            // the second lane did not fit this plan (second_lane_fits, or a failed allocation): not tried again
+    double conv_flops = 0;                 // conv FLOPs of one replay at max_batch (second_lane_wanted)
+    size_t lane_bytes = 0;                 // device bytes of one lane of this plan
 
     // plan
     bool planned = false;
     int p_h0 = 0, p_w0 = 0, p_imgsz = 0, p_pre = 0, p_auto = 0, p_batch = 0;
     int net_h = 0, net_w = 0;
     int rw = 0, rh = 0, top = 0, left = 0, lb_mode = 0;
-    std::vector<float*> bptr;
-    void* arena = nullptr;                 // what bptr points into
     size_t arena_bytes = 0, logical_bytes = 0;   // bytes of the plan with / without liveness aliasing
     unsigned h_ovf = 0;                    // overflow flag as read back by the last pa_yolo_infer calls (h2 models)
     bool ovf_cached = false;               // h_ovf is current: no kernel of this model has run since it was read
@@ -146,20 +205,16 @@ struct pa_model {
     unsigned* h_pin = nullptr;
     hipEvent_t tk_ev[PA_MAX_INFLIGHT]{};
     bool tk_busy[PA_MAX_INFLIGHT]{};
+    int tk_lane[PA_MAX_INFLIGHT]{};        // the lane a ticket in flight runs on
     int next_ticket = 0, n_inflight = 0;
     std::vector<int32_t> classes_host;     // what d_classes holds (set_classes: uploaded again only when the caller's list changes)
-    std::map<int, hipGraphExec_t> graphs;  // op-list replay per batch size (tuning "graph")
     int graph_epoch = -1;                  // engine tuning epoch the graphs were captured under
     uint8_t* d_frames = nullptr; size_t frames_cap = 0;
-    uint8_t* d_netin = nullptr;
     int32_t *d_xtab = nullptr, *d_ytab = nullptr;                 // cv2 bilinear tables
     ResamplePlan rs;                                              // PIL tables
     // post
     int A = 0, P2 = 0;
-    HeadLevel lv[3]{};
-    float* d_cand = nullptr; int32_t* d_cidx = nullptr; int32_t* d_ccnt = nullptr;
-    uint64_t* d_keys = nullptr; int32_t* d_order = nullptr; uint8_t* d_supp = nullptr;
-    float* d_oboxes = nullptr; float* d_okpts = nullptr; int32_t* d_ocnt = nullptr;
+    YoloGeometry geom;                     // of the plan (a second lane is planned from it)
     int32_t* d_classes = nullptr; int classes_cap = 0;
     int last_n = 0;
     int last_post_path = 0;                // pa_yolo_last_post_path: 0 decode_kernel on head maps, 1 the fused head tail
@@ -169,18 +224,21 @@ struct pa_model {
 };
 
 // ---- engine.cpp
-ProfRec* prof_begin(pa_model* m, size_t idx, int kind, int ksize, double flops);
-inline void prof_end(pa_model* m, ProfRec* r) { if (r) hipEventRecord(r->e1, m->e->stream); }
+// (the profile's events go onto the stream the profiled kernels run on)
+ProfRec* prof_begin(pa_model* m, hipStream_t s, size_t idx, int kind, int ksize, double flops);
+inline void prof_end(hipStream_t s, ProfRec* r) { if (r) hipEventRecord(r->e1, s); }
 int finish_profile(pa_model* m, size_t n_rec);
-void free_plan(pa_model* m);                         // the caller has synchronised the stream
-int plan_buffers(pa_model* m, int batch);            // the arena of a model whose net_h x net_w is set: allocation, memsets, bptr, d_fc
-// run_ops, or (tuning "graph", not while profiling) the replay of its capture for this batch size
-int run_graph(pa_model* m, int n, size_t* pi);
+void free_plan(pa_model* m);                         // both lanes; the caller has synchronised the main stream, the lanes are drained here
+// the arena of one lane of a model whose net_h x net_w is set: allocation, memsets (on s), bptr, d_fc
+int plan_buffers(pa_model* m, Lane& L, int batch, hipStream_t s);
+void free_lane(Lane& L);                             // what plan_buffers and the YOLO plan gave a lane; drains nothing: the CALLER has waited for the lane's stream
+// run_ops on lane L and stream s, or (tuning "graph", not while profiling) the replay of its capture for this batch size
+int run_graph(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi);
 // The fused head tail applies to the next replay of a planned model: tuning fuse_head, an h2 model whose plan found the tail, a
 // shape head_tail_h2.hip has, no profiling, no timeline.  run_ops then skips the tail convs and run_post launches the fused kernel.
 bool head_fused(const pa_model* m);
-void head_tail_convs(const pa_model* m, HeadTailArgs& a);      // a.cv and a.w_single of a planned model (a.d: the caller's)
-int run_tail_ops(pa_model* m, int n);                // the tail convs alone, from their inputs (still live): the head maps of the last call
+void head_tail_convs(const pa_model* m, const Lane& L, HeadTailArgs& a);      // a.cv and a.w_single of a planned model (a.d: the caller's)
+int run_tail_ops(pa_model* m, Lane& L, hipStream_t s, int n);   // the tail convs alone, from their inputs (still live): the head maps of the lane's last call
 
 // ---- engine_jpeg.cpp
 void jpeg_scratch_free(pa_engine* e);                 // waits for the stream first
@@ -191,10 +249,11 @@ void jpeg_dec_scratch_free(pa_engine* e);             // waits for the stream fi
 // ---- engine_pre.cpp
 hipError_t upload_table(pa_engine* e, int32_t** dptr, const std::vector<int32_t>& v);
 // grow d_frames to max_batch frames if need be and copy nb host frames into it (on the stream); *src then names the device copy
-int stage_frames(pa_model* m, const uint8_t** src, int nb, size_t frame_bytes);
+int stage_frames(pa_model* m, const uint8_t** src, int nb, size_t frame_bytes, hipStream_t s);
 // tables + temporary for sh x sw -> dh x dw over at most max_batch frames; identity_pass: a source that already has the target
 // size still gets a 1-tap vertical table (the ball session: its pass also reorders channels into 3-byte pixels)
 int resample_plan(pa_engine* e, ResamplePlan* rs, int sh, int sw, int dh, int dw, int filter, int max_batch, bool identity_pass = false);
 void resample_free(ResamplePlan* rs);
-// the one or two passes (horizontal first) of n frames into dst with out_c (3 | 4) bytes per pixel; the last pass reverses channels
-hipError_t resample_enqueue(const ResamplePlan& rs, const uint8_t* src, uint8_t* dst, int n, int out_c, int reverse, hipStream_t s);
+// the one or two passes (horizontal first) of n frames into dst with out_c (3 | 4) bytes per pixel; the last pass reverses channels.
+// tmp: the temporary between the passes in place of the plan's (a second lane's own, as large as the plan's)
+hipError_t resample_enqueue(const ResamplePlan& rs, const uint8_t* src, uint8_t* dst, int n, int out_c, int reverse, hipStream_t s, uint8_t* tmp = nullptr);

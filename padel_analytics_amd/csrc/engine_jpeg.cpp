@@ -16,7 +16,7 @@ static const size_t kSlotBudget = (size_t)256 << 20;
 
 void jpeg_scratch_free(pa_engine* e) {
     if (!e->jpeg) return;
-    if (e->stream) hipStreamSynchronize(e->stream);
+    if (e->main_stream_wait_only()) hipStreamSynchronize(e->main_stream_wait_only());
     JpegScratch* s = e->jpeg;
     if (s->slots) hipFree(s->slots);
     if (s->lens) hipFree(s->lens);
@@ -56,7 +56,7 @@ int pa_jpeg_encode(pa_engine* e, const uint8_t* src, int n, int h, int w, const 
     const int sub = (int)std::max<size_t>(1, std::min<size_t>(std::min(n, 256), kSlotBudget / per_frame));
     const size_t ivls = (size_t)sub * rows;
     if (s->slots_cap < per_frame * sub || s->ivl_cap < ivls || !s->tab) {
-        PA_HIP(e, hipStreamSynchronize(e->stream));              // an encode still queued uses what is about to go
+        PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));              // an encode still queued uses what is about to go
         if (grow(e, &s->slots, &s->slots_cap, per_frame * sub, 0)) return 1;
         if (s->ivl_cap < ivls) {
             if (s->lens) hipFree(s->lens);
@@ -71,7 +71,7 @@ int pa_jpeg_encode(pa_engine* e, const uint8_t* src, int n, int h, int w, const 
     JpegDevTables tab;
     jpeg_fill_tables(h, w, quality, &tab);
     // (pageable source: the runtime has consumed it when hipMemcpyAsync returns; an earlier call's kernels are ahead of it in the stream)
-    PA_HIP(e, hipMemcpyAsync(s->tab, &tab, sizeof(tab), hipMemcpyHostToDevice, e->stream));
+    PA_HIP(e, hipMemcpyAsync(s->tab, &tab, sizeof(tab), hipMemcpyHostToDevice, e->main_stream()));
 
     std::vector<int64_t> offsets((size_t)n + 1, 0);
     std::vector<long long> frame_off(257);
@@ -83,30 +83,30 @@ int pa_jpeg_encode(pa_engine* e, const uint8_t* src, int n, int h, int w, const 
         a.n = nf; a.h = h; a.w = w; a.mcus = mcus; a.rows = rows; a.nv12 = geom->layout == PA_YUV_NV12;
         a.pitch_y = geom->pitch_y; a.pitch_c = geom->pitch_c; a.off_u = geom->off_u; a.off_v = geom->off_v;
         a.frame_stride = geom->frame_stride; a.slot_cap = slot_cap;
-        hipError_t r = launch_jpeg_encode(a, e->stream);
+        hipError_t r = launch_jpeg_encode(a, e->main_stream());
         if (r != hipSuccess) PA_FAIL(e, "jpeg encode launch failed: %s", hipGetErrorString(r));
         long long* d_frame_off = s->offs;
         long long* d_ivl_off = s->offs + 257;
-        r = launch_jpeg_offsets(s->lens, nf, rows, d_frame_off, d_ivl_off, e->stream);
+        r = launch_jpeg_offsets(s->lens, nf, rows, d_frame_off, d_ivl_off, e->main_stream());
         if (r != hipSuccess) PA_FAIL(e, "jpeg offsets launch failed: %s", hipGetErrorString(r));
         // the sizes come back before the gather: `out` is then known to hold this sub-batch (no size is guessed)
-        PA_HIP(e, hipMemcpyAsync(frame_off.data(), d_frame_off, (size_t)(nf + 1) * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
-        PA_HIP(e, hipStreamSynchronize(e->stream));
+        PA_HIP(e, hipMemcpyAsync(frame_off.data(), d_frame_off, (size_t)(nf + 1) * sizeof(long long), hipMemcpyDeviceToHost, e->main_stream()));
+        PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
         const size_t bytes = (size_t)frame_off[nf];
         if (s->out_cap < total + bytes && grow(e, &s->out, &s->out_cap, std::max((total + bytes) * 2, (size_t)1 << 20), total)) return 1;
-        r = launch_jpeg_gather(s->slots, slot_cap, s->lens, d_frame_off, d_ivl_off, s->tab, s->out + total, nf, rows, e->stream);
+        r = launch_jpeg_gather(s->slots, slot_cap, s->lens, d_frame_off, d_ivl_off, s->tab, s->out + total, nf, rows, e->main_stream());
         if (r != hipSuccess) PA_FAIL(e, "jpeg gather launch failed: %s", hipGetErrorString(r));
         for (int i = 0; i <= nf; ++i) offsets[(size_t)f0 + i] = (int64_t)(total + (size_t)frame_off[i]);
         total += bytes;
     }
     if (total > cap) {
-        PA_HIP(e, hipStreamSynchronize(e->stream));
+        PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
         offsets_host[0] = 0;
         offsets_host[n] = (int64_t)total;
         PA_FAIL(e, "pa_jpeg_encode: the %d frames take %zu bytes, dst_host holds %zu", n, total, cap);
     }
-    PA_HIP(e, hipMemcpyAsync(dst_host, s->out, total, hipMemcpyDeviceToHost, e->stream));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipMemcpyAsync(dst_host, s->out, total, hipMemcpyDeviceToHost, e->main_stream()));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     memcpy(offsets_host, offsets.data(), ((size_t)n + 1) * sizeof(int64_t));
     return 0;
 }

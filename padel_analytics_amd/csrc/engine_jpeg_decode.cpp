@@ -26,7 +26,7 @@ static const int kDecMaxSub = 64;
 
 void jpeg_dec_scratch_free(pa_engine* e) {
     if (!e->jpeg_dec) return;
-    if (e->stream) hipStreamSynchronize(e->stream);
+    if (e->main_stream_wait_only()) hipStreamSynchronize(e->main_stream_wait_only());
     JpegDecScratch* s = e->jpeg_dec;
     if (s->data) hipFree(s->data);
     if (s->frames) hipFree(s->frames);
@@ -138,18 +138,18 @@ int pa_jpeg_decode(pa_engine* e, const uint8_t* jpegs, const int64_t* offsets, i
         const size_t need_s = 2 * ivls.size() * sizeof(int32_t), need_o = ivls.size() * sizeof(int32_t);
         if (s->data_cap < bytes + 16 || s->frames_cap < need_f || s->ivls_cap < need_i || s->status_cap < need_s || s->order_cap < need_o ||
             s->coef_cap < coef_frame * nf || s->planes_cap < planes_frame * nf) {
-            PA_HIP(e, hipStreamSynchronize(e->stream));          // a decode still queued uses what is about to go
+            PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));          // a decode still queued uses what is about to go
             if (fit(e, &s->data, &s->data_cap, bytes + 16) || fit(e, &s->frames, &s->frames_cap, need_f) ||
                 fit(e, &s->ivls, &s->ivls_cap, need_i) || fit(e, &s->status, &s->status_cap, need_s) || fit(e, &s->order, &s->order_cap, need_o) ||
                 fit(e, &s->coef, &s->coef_cap, coef_frame * nf) || fit(e, &s->planes, &s->planes_cap, planes_frame * nf))
                 return 1;
         }
         // (pageable sources: the runtime has consumed them when hipMemcpyAsync returns; an earlier sub-batch's kernels are ahead in the stream)
-        if (timed) PA_HIP(e, hipEventRecord(s->ev[0], e->stream));
-        if (bytes) PA_HIP(e, hipMemcpyAsync(s->data, jpegs + base, bytes, hipMemcpyHostToDevice, e->stream));
-        PA_HIP(e, hipMemcpyAsync(s->frames, frames.data(), need_f, hipMemcpyHostToDevice, e->stream));
-        PA_HIP(e, hipMemcpyAsync(s->ivls, ivls.data(), need_i, hipMemcpyHostToDevice, e->stream));
-        PA_HIP(e, hipMemcpyAsync(s->order, order.data(), need_o, hipMemcpyHostToDevice, e->stream));
+        if (timed) PA_HIP(e, hipEventRecord(s->ev[0], e->main_stream()));
+        if (bytes) PA_HIP(e, hipMemcpyAsync(s->data, jpegs + base, bytes, hipMemcpyHostToDevice, e->main_stream()));
+        PA_HIP(e, hipMemcpyAsync(s->frames, frames.data(), need_f, hipMemcpyHostToDevice, e->main_stream()));
+        PA_HIP(e, hipMemcpyAsync(s->ivls, ivls.data(), need_i, hipMemcpyHostToDevice, e->main_stream()));
+        PA_HIP(e, hipMemcpyAsync(s->order, order.data(), need_o, hipMemcpyHostToDevice, e->main_stream()));
         JpegDecArgs a{};
         a.data = s->data; a.ivls = s->ivls; a.frames = s->frames; a.coef = s->coef; a.ivl_status = s->status; a.planes = s->planes;
         a.dst = dst + (size_t)f0 * h * w * 3;
@@ -157,12 +157,12 @@ int pa_jpeg_decode(pa_engine* e, const uint8_t* jpegs, const int64_t* offsets, i
         a.order = s->order; a.n_serial = n_serial; a.n_split = n_split; a.sub_bytes = split_sub;
         a.split_threads = std::min(kSplitMaxThreads, (most_sub + 63) / 64 * 64);
         int path = 0;
-        const hipError_t r = launch_jpeg_decode(a, &path, e->stream, timed ? s->ev + 1 : nullptr);
+        const hipError_t r = launch_jpeg_decode(a, &path, e->main_stream(), timed ? s->ev + 1 : nullptr);
         if (r != hipSuccess) PA_FAIL(e, "jpeg decode launch failed: %s", hipGetErrorString(r));
         e->jpeg_dec_last_path = path;
         ivl_status.resize(2 * ivls.size());
-        PA_HIP(e, hipMemcpyAsync(ivl_status.data(), s->status, need_s, hipMemcpyDeviceToHost, e->stream));
-        PA_HIP(e, hipStreamSynchronize(e->stream));
+        PA_HIP(e, hipMemcpyAsync(ivl_status.data(), s->status, need_s, hipMemcpyDeviceToHost, e->main_stream()));
+        PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
         if (timed)
             for (int k = 0; k < 4; ++k) {
                 float ms = 0;

@@ -5,19 +5,19 @@
 hipError_t upload_table(pa_engine* e, int32_t** dptr, const std::vector<int32_t>& v) {
     hipError_t r = hipMalloc((void**)dptr, v.size() * sizeof(int32_t));
     if (r != hipSuccess) return r;
-    r = hipMemcpyAsync(*dptr, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->stream);
+    r = hipMemcpyAsync(*dptr, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->main_stream());
     if (r != hipSuccess) return r;
-    return hipStreamSynchronize(e->stream);
+    return hipStreamSynchronize(e->main_stream_wait_only());
 }
 
-int stage_frames(pa_model* m, const uint8_t** src, int nb, size_t frame_bytes) {
+int stage_frames(pa_model* m, const uint8_t** src, int nb, size_t frame_bytes, hipStream_t s) {
     pa_engine* e = m->e;
     if (m->frames_cap < (size_t)nb * frame_bytes) {
         if (m->d_frames) hipFree(m->d_frames);
         m->frames_cap = (size_t)m->max_batch * frame_bytes;
         PA_HIP(e, hipMalloc((void**)&m->d_frames, m->frames_cap));
     }
-    PA_HIP(e, hipMemcpyAsync(m->d_frames, *src, (size_t)nb * frame_bytes, hipMemcpyHostToDevice, e->stream));
+    PA_HIP(e, hipMemcpyAsync(m->d_frames, *src, (size_t)nb * frame_bytes, hipMemcpyHostToDevice, s));
     *src = m->d_frames;
     return 0;
 }
@@ -27,7 +27,10 @@ int resample_plan(pa_engine* e, ResamplePlan* rs, int sh, int sw, int dh, int dw
     std::vector<int32_t> b, k;
     if (sw != dw) { rs->hks = pil_coeffs(sw, dw, b, k, filter); PA_HIP(e, upload_table(e, &rs->d_hb, b)); PA_HIP(e, upload_table(e, &rs->d_hk, k)); }
     if (sh != dh) { rs->vks = pil_coeffs(sh, dh, b, k, filter); PA_HIP(e, upload_table(e, &rs->d_vb, b)); PA_HIP(e, upload_table(e, &rs->d_vk, k)); }
-    if (sw != dw && sh != dh) PA_HIP(e, hipMalloc((void**)&rs->d_tmp, (size_t)max_batch * sh * dw * 3));
+    if (sw != dw && sh != dh) {
+        rs->tmp_bytes = (size_t)max_batch * sh * dw * 3;
+        PA_HIP(e, hipMalloc((void**)&rs->d_tmp, rs->tmp_bytes));
+    }
     if (identity_pass && sh == dh && sw == dw) {
         // identity "resample": one tap of weight 1.0 (1 << 22) per output row
         rs->vks = 1;
@@ -45,21 +48,22 @@ void resample_free(ResamplePlan* rs) {
     *rs = ResamplePlan{};
 }
 
-hipError_t resample_enqueue(const ResamplePlan& rs, const uint8_t* src, uint8_t* dst, int n, int out_c, int reverse, hipStream_t s) {
+hipError_t resample_enqueue(const ResamplePlan& rs, const uint8_t* src, uint8_t* dst, int n, int out_c, int reverse, hipStream_t s, uint8_t* tmp) {
     // a source of the target size has no pass to run unless the plan built the 1-tap one (the ball session's): the YOLO and ResNet
     // paths copy such frames with the letterbox kernel and never get here; launching nothing would leave dst as it was
     if (rs.sw == rs.dw && rs.sh == rs.dh && !rs.d_vb) return hipErrorInvalidValue;
+    if (!tmp) tmp = rs.d_tmp;
     const uint8_t* cur = src;
     int cw = rs.sw;
     hipError_t r = hipSuccess;
     if (rs.sw != rs.dw) {
         ResamplePassArgs a{};
         const bool last = (rs.sh == rs.dh);
-        a.in = cur; a.out = last ? dst : rs.d_tmp; a.B = n; a.in_h = rs.sh; a.in_w = rs.sw; a.in_c = 3;
+        a.in = cur; a.out = last ? dst : tmp; a.B = n; a.in_h = rs.sh; a.in_w = rs.sw; a.in_c = 3;
         a.out_h = rs.sh; a.out_w = rs.dw; a.out_c = last ? out_c : 3; a.vertical = 0; a.bounds = rs.d_hb; a.coefs = rs.d_hk;
         a.ksize = rs.hks; a.reverse = last ? reverse : 0;
         r = launch_resample_pass(a, s);
-        cur = rs.d_tmp; cw = rs.dw;
+        cur = tmp; cw = rs.dw;
     }
     // (a source that already has the target size runs the 1-tap pass where the plan built one: only the channel order
     // may change; the letterbox kernel in copy mode writes 4-byte pixels)
@@ -84,13 +88,13 @@ int pa_yuv420_to_bgr(pa_engine* e, const uint8_t* src, int src_on_device, int n,
     PA_HIP(e, hipSetDevice(e->dev));
     if (!src_on_device) {
         if (e->yuv_stage_cap < span) {
-            PA_HIP(e, hipStreamSynchronize(e->stream));          // a conversion still queued reads the buffer about to go
+            PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));          // a conversion still queued reads the buffer about to go
             if (e->yuv_stage) hipFree(e->yuv_stage);
             e->yuv_stage = nullptr; e->yuv_stage_cap = 0;
             PA_HIP(e, hipMalloc((void**)&e->yuv_stage, span));
             e->yuv_stage_cap = span;
         }
-        PA_HIP(e, hipMemcpyAsync(e->yuv_stage, src, span, hipMemcpyHostToDevice, e->stream));
+        PA_HIP(e, hipMemcpyAsync(e->yuv_stage, src, span, hipMemcpyHostToDevice, e->main_stream()));
         src = e->yuv_stage;
     }
     YuvArgs a{};
@@ -98,7 +102,7 @@ int pa_yuv420_to_bgr(pa_engine* e, const uint8_t* src, int src_on_device, int n,
     a.pitch_y = d->pitch_y; a.pitch_c = d->pitch_c; a.off_u = d->off_u; a.off_v = d->off_v; a.frame_stride = d->frame_stride;
     a.y_off = d->y_off; a.cy = d->cy; a.cvr = d->cvr; a.cug = d->cug; a.cvg = d->cvg; a.cub = d->cub;
     int vec = 0;
-    const hipError_t r = launch_yuv420_to_bgr(a, e->stream, &vec);
+    const hipError_t r = launch_yuv420_to_bgr(a, e->main_stream(), &vec);
     if (r != hipSuccess) PA_FAIL(e, "yuv420_to_bgr launch failed: %s", hipGetErrorString(r));
     e->yuv_last_path = vec ? 1 : 2;
     return 0;

@@ -28,14 +28,14 @@ int pa_render(pa_engine* e, const uint8_t* src, int n, int h, int w, const pa_ma
     }
     memcpy(reinterpret_cast<char*>(host.data()) + first_off, first, (size_t)(n + 1) * sizeof(int32_t));
     if (e->render_stage_cap < bytes) {
-        PA_HIP(e, hipStreamSynchronize(e->stream));              // a render still queued reads the buffer about to go
+        PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));              // a render still queued reads the buffer about to go
         if (e->render_stage) hipFree(e->render_stage);
         e->render_stage = nullptr; e->render_stage_cap = 0;
         const size_t cap = std::max(bytes * 2, (size_t)65536);
         PA_HIP(e, hipMalloc((void**)&e->render_stage, cap));
         e->render_stage_cap = cap;
     }
-    PA_HIP(e, hipMemcpyAsync(e->render_stage, host.data(), bytes, hipMemcpyHostToDevice, e->stream));
+    PA_HIP(e, hipMemcpyAsync(e->render_stage, host.data(), bytes, hipMemcpyHostToDevice, e->main_stream()));
     RenderArgs a{};
     a.src = src; a.dst = dst; a.marks = e->render_stage; a.boxes = e->render_stage + box_off;
     a.first = reinterpret_cast<const int32_t*>(e->render_stage + first_off);
@@ -49,16 +49,16 @@ int pa_render(pa_engine* e, const uint8_t* src, int n, int h, int w, const pa_ma
 #ifdef PADEL_RENDER_PROBE
     static unsigned long long* d_probe = nullptr;                // tools build only (build.sh, PADEL_EXTRA_FLAGS): see the report below
     if (!d_probe) PA_HIP(e, hipMalloc((void**)&d_probe, 4 * sizeof(unsigned long long)));
-    PA_HIP(e, hipMemsetAsync(d_probe, 0, 4 * sizeof(unsigned long long), e->stream));
+    PA_HIP(e, hipMemsetAsync(d_probe, 0, 4 * sizeof(unsigned long long), e->main_stream()));
     a.probe = d_probe;
 #endif
     int vec = 0;
-    const hipError_t r = launch_render(a, e->stream, &vec);
+    const hipError_t r = launch_render(a, e->main_stream(), &vec);
     if (r != hipSuccess) PA_FAIL(e, "render launch failed: %s", hipGetErrorString(r));
 #ifdef PADEL_RENDER_PROBE
     unsigned long long p[4] = {};
-    PA_HIP(e, hipMemcpyAsync(p, d_probe, sizeof(p), hipMemcpyDeviceToHost, e->stream));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipMemcpyAsync(p, d_probe, sizeof(p), hipMemcpyDeviceToHost, e->main_stream()));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     if (p[3]) fprintf(stderr, "render probe: %llu marks, %llu workgroups, shader-clock cycles per workgroup up to its stores %.0f, of which cull %.0f, apply %.0f\n",
                       (unsigned long long)total, p[3], (double)p[2] / p[3], (double)p[0] / p[3], (double)p[1] / p[3]);
 #endif

@@ -5,10 +5,10 @@
 static int ensure_tracknet_plan(pa_model* m, int h, int w) {
     pa_engine* e = m->e;
     if (m->planned && m->net_h == h && m->net_w == w && m->p_batch == m->max_batch) return 0;
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     free_plan(m);
     m->net_h = h; m->net_w = w;
-    if (plan_buffers(m, m->max_batch)) return 1;
+    if (plan_buffers(m, m->ln[0], m->max_batch, e->main_stream())) return 1;
     m->planned = true;
     return 0;
 }
@@ -21,7 +21,7 @@ int pa_tracknet_infer(pa_model* m, const float* x, int n, int h, int w, int x_on
     PA_HIP(e, hipSetDevice(e->dev));
     m->ovf_cached = false;               // this call's kernels may raise the flag: the host copy is stale
     if (ensure_tracknet_plan(m, h, w)) return 1;
-    hipStream_t s = e->stream;
+    hipStream_t s = e->main_stream();
     const int cin = m->bufs[0].channels;
     const int ob = m->d.head_buf[0];
     const int cout = m->bufs[ob].channels;
@@ -36,23 +36,23 @@ int pa_tracknet_infer(pa_model* m, const float* x, int n, int h, int w, int x_on
         if (h2) {
             const float* src = reinterpret_cast<const float*>(xs);
             if (!x_on_device) {
-                if (m->stage_cap < in_bytes) {
-                    if (m->d_stage) hipFree(m->d_stage);
-                    m->stage_cap = (size_t)m->max_batch * h * w * cin * 4;
-                    PA_HIP(e, hipMalloc((void**)&m->d_stage, m->stage_cap));
+                if (m->ln[0].stage_cap < in_bytes) {
+                    if (m->ln[0].d_stage) hipFree(m->ln[0].d_stage);
+                    m->ln[0].stage_cap = (size_t)m->max_batch * h * w * cin * 4;
+                    PA_HIP(e, hipMalloc((void**)&m->ln[0].d_stage, m->ln[0].stage_cap));
                 }
-                PA_HIP(e, hipMemcpyAsync(m->d_stage, xs, in_bytes, hipMemcpyHostToDevice, s));
-                src = m->d_stage;
+                PA_HIP(e, hipMemcpyAsync(m->ln[0].d_stage, xs, in_bytes, hipMemcpyHostToDevice, s));
+                src = m->ln[0].d_stage;
             }
-            const hipError_t er = launch_h2_encode(src, m->bptr[0], (long long)(in_bytes / 4), m->d_ovf, s);
+            const hipError_t er = launch_h2_encode(src, m->ln[0].bptr[0], (long long)(in_bytes / 4), m->d_ovf, s);
             if (er != hipSuccess) PA_FAIL(e, "h2 encode launch failed: %s", hipGetErrorString(er));
         } else
-        PA_HIP(e, hipMemcpyAsync(m->bptr[0], xs, in_bytes,
+        PA_HIP(e, hipMemcpyAsync(m->ln[0].bptr[0], xs, in_bytes,
                                  x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        if (run_graph(m, nb, &pi)) return 1;
+        if (run_graph(m, m->ln[0], s, nb, &pi)) return 1;
         const size_t ohw = (size_t)(h >> m->bufs[ob].level) * (w >> m->bufs[ob].level);
         const size_t out_bytes = (size_t)nb * ohw * cout * sizeof(float);
-        PA_HIP(e, hipMemcpyAsync(out + (size_t)c0 * ohw * cout, m->bptr[ob], out_bytes,
+        PA_HIP(e, hipMemcpyAsync(out + (size_t)c0 * ohw * cout, m->ln[0].bptr[ob], out_bytes,
                                  out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
         PA_HIP(e, hipStreamSynchronize(s));
     }
@@ -112,8 +112,8 @@ int pa_ball_create(pa_model* m, int src_h, int src_w, pa_ball** out) {
     std::vector<float> lut(256);
     for (int i = 0; i < 256; ++i) lut[i] = (float)((double)i / 255.0);     // float64 division, then .float()
     PA_HIP(e, hipMalloc((void**)&b->d_lut, 256 * sizeof(float)));
-    PA_HIP(e, hipMemcpyAsync(b->d_lut, lut.data(), 256 * sizeof(float), hipMemcpyHostToDevice, e->stream));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipMemcpyAsync(b->d_lut, lut.data(), 256 * sizeof(float), hipMemcpyHostToDevice, e->main_stream()));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     if (resample_plan(e, &b->rs, src_h, src_w, BALL_H, BALL_W, PIL_BICUBIC, b->B, true)) return 1;
     guard.ok = true;
     *out = b;
@@ -123,7 +123,7 @@ int pa_ball_create(pa_model* m, int src_h, int src_w, pa_ball** out) {
 void pa_ball_destroy(pa_ball* b) {
     if (!b) return;
     hipSetDevice(b->m->e->dev);
-    hipStreamSynchronize(b->m->e->stream);
+    hipStreamSynchronize(b->m->e->main_stream_wait_only());
     resample_free(&b->rs);
     void* ptrs[] = {b->d_src, b->d_small, b->d_med_src, b->d_med, b->d_mask, b->d_heat, b->d_Y, b->d_lut, b->d_row0, b->d_mode, b->d_div, b->d_label, b->d_bbox, b->d_rect};
     for (void* p : ptrs) if (p) hipFree(p);
@@ -133,7 +133,7 @@ void pa_ball_destroy(pa_ball* b) {
 // Pillow bicubic resize of n u8 HWC images (h x w x 3) to 288 x 512 x 3, optional channel reversal
 static int ball_resize(pa_ball* b, const uint8_t* src, int n, uint8_t* dst, int reverse) {
     pa_engine* e = b->m->e;
-    const hipError_t r = resample_enqueue(b->rs, src, dst, n, 3, reverse, e->stream);
+    const hipError_t r = resample_enqueue(b->rs, src, dst, n, 3, reverse, e->main_stream());
     if (r != hipSuccess) PA_FAIL(e, "ball resize launch failed: %s", hipGetErrorString(r));
     return 0;
 }
@@ -144,15 +144,15 @@ int pa_ball_set_background(pa_ball* b, const uint8_t* median_rgb) {
     if (!b || !median_rgb) return 1;
     pa_engine* e = b->m->e;
     PA_HIP(e, hipSetDevice(e->dev));
-    PA_HIP(e, hipMemcpyAsync(b->d_med_src, median_rgb, (size_t)b->h * b->w * 3, hipMemcpyHostToDevice, e->stream));
+    PA_HIP(e, hipMemcpyAsync(b->d_med_src, median_rgb, (size_t)b->h * b->w * 3, hipMemcpyHostToDevice, e->main_stream()));
     return ball_finish_background(b);
 }
 
 static int ball_finish_background(pa_ball* b) {
     pa_engine* e = b->m->e;
     if (ball_resize(b, b->d_med_src, 1, b->d_med, 0)) return 1;
-    PA_HIP(e, hipMemsetAsync(b->d_Y, 0, (size_t)(b->B + 14) * BALL_H * BALL_W * b->cs * sizeof(float), e->stream));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipMemsetAsync(b->d_Y, 0, (size_t)(b->B + 14) * BALL_H * BALL_W * b->cs * sizeof(float), e->main_stream()));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     b->fed = 0;
     b->have_bg = true;
     return 0;
@@ -163,7 +163,7 @@ int pa_ball_background_from_frames(pa_ball* b, const uint8_t* frames_bgr, int n,
     pa_engine* e = b->m->e;
     if (n < 1 || n > 65535) PA_FAIL(e, "pa_ball_background_from_frames: n = %d", n);
     PA_HIP(e, hipSetDevice(e->dev));
-    hipStream_t s = e->stream;
+    hipStream_t s = e->main_stream();
     const long long fb = (long long)b->h * b->w * 3;
     const uint8_t* src = frames_bgr;
     uint8_t* tmp = nullptr;
@@ -193,7 +193,7 @@ int pa_ball_feed(pa_ball* b, const uint8_t* frames, int n, int on_device, int fl
     if (n < 0 || n > b->B || (n > 0 && !frames)) PA_FAIL(e, "pa_ball_feed: n = %d (max %d)", n, b->B);
     PA_HIP(e, hipSetDevice(e->dev));
     m->ovf_cached = false;               // this call's kernels may raise the flag: the host copy is stale
-    hipStream_t s = e->stream;
+    hipStream_t s = e->main_stream();
     const size_t HW = (size_t)BALL_H * BALL_W;
     if (ensure_tracknet_plan(m, BALL_H, BALL_W)) return 1;
     int nout = 0;
@@ -218,13 +218,13 @@ int pa_ball_feed(pa_ball* b, const uint8_t* frames, int n, int on_device, int fl
         nw = g_hi >= g_lo ? (int)(g_hi - g_lo + 1) : 0;
         if (nw > 0) {
             BallAssembleArgs aa{};
-            aa.median = b->d_med; aa.frames = b->d_small; aa.lut = b->d_lut; aa.out = m->bptr[0];
+            aa.median = b->d_med; aa.frames = b->d_small; aa.lut = b->d_lut; aa.out = m->ln[0].bptr[0];
             aa.B = nw; aa.H = BALL_H; aa.W = BALL_W; aa.ring = b->ring; aa.first_slot = (int)(g_lo % b->ring);
             aa.out_f16 = m->d.dtype == PA_DTYPE_F16 ? 1 : m->d.dtype == PA_DTYPE_H2 ? 2 : 0;
             hipError_t r = launch_ball_assemble(aa, s);
             if (r != hipSuccess) PA_FAIL(e, "ball assemble launch failed: %s", hipGetErrorString(r));
-            if (run_graph(m, nw, &prof_n)) return 1;
-            PA_HIP(e, hipMemcpyAsync(b->d_Y + (size_t)7 * HW * b->cs, m->bptr[m->d.head_buf[0]],
+            if (run_graph(m, m->ln[0], s, nw, &prof_n)) return 1;
+            PA_HIP(e, hipMemcpyAsync(b->d_Y + (size_t)7 * HW * b->cs, m->ln[0].bptr[m->d.head_buf[0]],
                                      (size_t)nw * HW * b->cs * sizeof(float), hipMemcpyDeviceToDevice, s));
             for (int i = 0; i < nw; ++i) {             // frame g = g_lo + i: rows i .. i+7 (row r <-> window g_lo - 7 + r)
                 const long long g = g_lo + i;
@@ -288,8 +288,8 @@ int pa_ball_read_resized(pa_ball* b, long long frame, uint8_t* out) {
     PA_HIP(e, hipSetDevice(e->dev));
     const size_t bytes = (size_t)BALL_H * BALL_W * 3;
     const uint8_t* src = frame < 0 ? b->d_med : b->d_small + (size_t)(frame % b->ring) * bytes;
-    PA_HIP(e, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, e->stream));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, e->main_stream()));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     return 0;
 }
 
@@ -298,7 +298,7 @@ int pa_ball_locate(pa_ball* b, const uint8_t* masks, int n, int32_t* out_rects) 
     pa_engine* e = b->m->e;
     if (n < 1 || n > b->B + 7) PA_FAIL(e, "pa_ball_locate: n = %d (max %d)", n, b->B + 7);
     PA_HIP(e, hipSetDevice(e->dev));
-    hipStream_t s = e->stream;
+    hipStream_t s = e->main_stream();
     const size_t HW = (size_t)BALL_H * BALL_W;
     PA_HIP(e, hipMemcpyAsync(b->d_mask, masks, (size_t)n * HW, hipMemcpyHostToDevice, s));
     BallLocateArgs la{};

@@ -2,9 +2,38 @@
 // (pa_yolo_submit / pa_yolo_wait) and the read-backs of the tests.
 #include "engine_internal.h"
 
+// What one lane of a YOLO plan owns (struct Lane): network input, activation arena, head-level pointers, post-processing buffers
+// and, on a second lane of a two-pass Pillow plan, its own temporary between the passes.  The memsets go onto the lane's stream.
+// Notes the bytes of one lane in m->lane_bytes.
+static int plan_lane(pa_model* m, Lane& L, const YoloGeometry& g, bool own_tmp) {
+    pa_engine* e = m->e;
+    const size_t B = (size_t)m->max_batch;
+    const size_t A = (size_t)g.A;
+    size_t total = 0;
+    auto dmalloc = [&](void** p, size_t bytes) { total += bytes; return hipMalloc(p, bytes); };
+    PA_HIP(e, dmalloc((void**)&L.d_netin, B * m->net_h * m->net_w * 4));
+    if (plan_buffers(m, L, (int)B, L.stream)) return 1;
+    total += m->arena_bytes + kConvReadSlack;
+    for (int l = 0; l < 3; ++l) L.lv[l] = HeadLevel{L.bptr[m->d.head_buf[l]], g.lv[l].H, g.lv[l].W, g.lv[l].stride, g.lv[l].anchor0};
+    PA_HIP(e, dmalloc((void**)&L.d_cand, B * A * 6 * sizeof(float)));
+    PA_HIP(e, dmalloc((void**)&L.d_cidx, B * A * sizeof(int32_t)));
+    PA_HIP(e, dmalloc((void**)&L.d_ccnt, B * sizeof(int32_t)));
+    PA_HIP(e, dmalloc((void**)&L.d_keys, B * g.P2 * sizeof(uint64_t)));
+    PA_HIP(e, dmalloc((void**)&L.d_order, B * A * sizeof(int32_t)));
+    PA_HIP(e, dmalloc((void**)&L.d_supp, B * A));
+    PA_HIP(e, dmalloc((void**)&L.d_oboxes, B * 300 * 6 * sizeof(float)));
+    PA_HIP(e, dmalloc((void**)&L.d_ocnt, B * sizeof(int32_t)));
+    if (m->d.nk) PA_HIP(e, dmalloc((void**)&L.d_okpts, B * 300 * m->d.nk * sizeof(float)));
+    if (m->rs.d_tmp) {
+        if (own_tmp) PA_HIP(e, dmalloc((void**)&L.d_rs_tmp, m->rs.tmp_bytes)); else total += m->rs.tmp_bytes;
+    }
+    m->lane_bytes = total;
+    return 0;
+}
+
 static int plan_yolo(pa_model* m, int h0, int w0, const pa_yolo_params* p) {
     pa_engine* e = m->e;
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     free_plan(m);
     const int S = p->imgsz;
     YoloGeometry g;
@@ -20,35 +49,54 @@ static int plan_yolo(pa_model* m, int h0, int w0, const pa_yolo_params* p) {
         PA_HIP(e, upload_table(e, &m->d_ytab, yt));
     }
     if (p->pre_mode == PA_PRE_PIL_STRETCH && resample_plan(e, &m->rs, h0, w0, S, S, PIL_BICUBIC, m->max_batch)) return 1;
-    const int B = m->max_batch;
-    PA_HIP(e, hipMalloc((void**)&m->d_netin, (size_t)B * m->net_h * m->net_w * 4));
-    if (plan_buffers(m, B)) return 1;
-    for (int l = 0; l < 3; ++l) m->lv[l] = HeadLevel{m->bptr[m->d.head_buf[l]], g.lv[l].H, g.lv[l].W, g.lv[l].stride, g.lv[l].anchor0};
     m->A = g.A;
     m->P2 = g.P2;
-    PA_HIP(e, hipMalloc((void**)&m->d_cand, (size_t)B * m->A * 6 * sizeof(float)));
-    PA_HIP(e, hipMalloc((void**)&m->d_cidx, (size_t)B * m->A * sizeof(int32_t)));
-    PA_HIP(e, hipMalloc((void**)&m->d_ccnt, (size_t)B * sizeof(int32_t)));
-    PA_HIP(e, hipMalloc((void**)&m->d_keys, (size_t)B * m->P2 * sizeof(uint64_t)));
-    PA_HIP(e, hipMalloc((void**)&m->d_order, (size_t)B * m->A * sizeof(int32_t)));
-    PA_HIP(e, hipMalloc((void**)&m->d_supp, (size_t)B * m->A));
-    PA_HIP(e, hipMalloc((void**)&m->d_oboxes, (size_t)B * 300 * 6 * sizeof(float)));
-    PA_HIP(e, hipMalloc((void**)&m->d_ocnt, (size_t)B * sizeof(int32_t)));
-    if (m->d.nk) PA_HIP(e, hipMalloc((void**)&m->d_okpts, (size_t)B * 300 * m->d.nk * sizeof(float)));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    m->geom = g;
+    if (plan_lane(m, m->ln[0], g, false)) return 1;
+    PA_HIP(e, hipStreamSynchronize(m->ln[0].stream));
     m->p_h0 = h0; m->p_w0 = w0; m->p_imgsz = S; m->p_pre = p->pre_mode; m->p_auto = p->letterbox_auto;
     m->planned = true;
     return 0;
 }
 
-// decode + NMS + scale_boxes / scale_coords of the head maps in m->lv[] for nb images of a planned model, results copied to
+// May the next ticket go to lane 1?  It exists, or it may be allocated now: the knob and the size gate (second_lane_wanted), and
+// no earlier refusal for this plan.
+static bool second_lane_ok(const pa_model* m) {
+    if (!second_lane_wanted(m->e->t.lanes, m->conv_flops, kLaneGateFlops)) return false;
+    return m->ln[1].allocated || !m->lane1_refused;
+}
+
+// Lane 1 of a planned model, at the first submit that wants it.  A lane that does not fit (second_lane_fits) or whose allocation
+// fails is given up for this plan: the model stays on lane 0, silently and correctly.
+static bool alloc_second_lane(pa_model* m) {
+    pa_engine* e = m->e;
+    Lane& L = m->ln[1];
+    size_t free_b = 0, total_b = 0;
+    bool ok = hipMemGetInfo(&free_b, &total_b) == hipSuccess && second_lane_fits(free_b, m->lane_bytes, m->arena_bytes);
+    if (ok) {
+        const std::string err = e->err;
+        const size_t arena = m->arena_bytes, logical = m->logical_bytes, lane_bytes = m->lane_bytes;
+        ok = plan_lane(m, L, m->geom, true) == 0;
+        m->arena_bytes = arena; m->logical_bytes = logical; m->lane_bytes = lane_bytes;      // (pa_model_plan_bytes: one lane's plan)
+        if (!ok) {
+            (void)hipGetLastError();
+            (void)hipStreamSynchronize(L.stream);
+            free_lane(L);
+            e->err = err;
+        }
+    }
+    if (!ok) m->lane1_refused = true;
+    return ok;
+}
+
+// decode + NMS + scale_boxes / scale_coords of the head maps in L.lv[] for nb images of a planned model, results copied to
 // the caller's arrays (rows beyond max_det are never written on device).  oh x ow: the size upstream treats as the source
 // (the PIL-resized image on the stretch path).  fused: the op list skipped the heads' last convs (head_fused): the fused head tail
 // computes them and the candidate list in place of decode_kernel; the head maps then hold only the keypoint rows NMS reads.
-static int run_post(pa_model* m, const pa_yolo_params* p, int nb, int oh, int ow, size_t* ppi, float* out_boxes, float* out_kpts,
+static int run_post(pa_model* m, Lane& L, const pa_yolo_params* p, int nb, int oh, int ow, size_t* ppi, float* out_boxes, float* out_kpts,
                 int32_t* out_counts, int ovf_slot, bool fused) {
     pa_engine* e = m->e;
-    hipStream_t s = e->stream;
+    hipStream_t s = L.stream;
     size_t& pi = *ppi;
     ProfRec* pr = nullptr;
     hipError_t r = hipSuccess;
@@ -56,46 +104,46 @@ static int run_post(pa_model* m, const pa_yolo_params* p, int nb, int oh, int ow
     const double kpx = (m->net_w - ow * gain) / 2, kpy = (m->net_h - oh * gain) / 2;
     // ---- decode + NMS
     DecodeArgs da{};
-    for (int l = 0; l < 3; ++l) da.lv[l] = m->lv[l];
+    for (int l = 0; l < 3; ++l) da.lv[l] = L.lv[l];
     da.cs = m->bufs[m->d.head_buf[0]].channels; da.nc = m->d.nc; da.nk = m->d.nk; da.kdim = m->d.kpt_dim;
     da.A = m->A; da.B = nb; da.conf = p->conf; da.classes = m->d_classes; da.n_classes = p->n_classes;
-    da.cand = m->d_cand; da.cand_idx = m->d_cidx; da.cand_cnt = m->d_ccnt;
-    pr = prof_begin(m, pi++, PROF_DECODE, 0, 0.0);
+    da.cand = L.d_cand; da.cand_idx = L.d_cidx; da.cand_cnt = L.d_ccnt;
+    pr = prof_begin(m, s, pi++, PROF_DECODE, 0, 0.0);
     if (fused) {
         HeadTailArgs ha{};
         ha.d = da;
-        head_tail_convs(m, ha);
+        head_tail_convs(m, L, ha);
         r = launch_head_tail_h2(ha, s);
     } else {
         r = launch_decode(da, s);
     }
-    prof_end(m, pr);
+    prof_end(s, pr);
     if (r != hipSuccess) PA_FAIL(e, "%s launch failed: %s", fused ? "fused head tail" : "decode", hipGetErrorString(r));
     m->last_post_path = fused ? 1 : 0;
     m->heads_stale = fused;
     NmsArgs na{};
-    na.cand = m->d_cand; na.cand_idx = m->d_cidx; na.cand_cnt = m->d_ccnt; na.keys = m->d_keys;
-    na.order = m->d_order; na.supp = m->d_supp;
-    for (int l = 0; l < 3; ++l) na.lv[l] = m->lv[l];
+    na.cand = L.d_cand; na.cand_idx = L.d_cidx; na.cand_cnt = L.d_ccnt; na.keys = L.d_keys;
+    na.order = L.d_order; na.supp = L.d_supp;
+    for (int l = 0; l < 3; ++l) na.lv[l] = L.lv[l];
     na.cs = da.cs; na.nc = m->d.nc; na.nk = m->d.nk; na.kdim = m->d.kpt_dim; na.A = m->A; na.B = nb; na.P2 = m->P2;
     na.iou = p->iou; na.max_det = p->max_det; na.max_nms = 30000;
     na.gain = (float)gain;
     na.pad_x = (float)std::nearbyint(kpx - 0.1); na.pad_y = (float)std::nearbyint(kpy - 0.1);
     na.kpad_x = (float)kpx; na.kpad_y = (float)kpy;
     na.w0 = (float)ow; na.h0 = (float)oh;
-    na.out_boxes = m->d_oboxes; na.out_kpts = m->d_okpts; na.out_cnt = m->d_ocnt;
-    pr = prof_begin(m, pi++, PROF_NMS, 0, 0.0);
+    na.out_boxes = L.d_oboxes; na.out_kpts = L.d_okpts; na.out_cnt = L.d_ocnt;
+    pr = prof_begin(m, s, pi++, PROF_NMS, 0, 0.0);
     r = launch_nms(na, s);
-    prof_end(m, pr);
+    prof_end(s, pr);
     if (r != hipSuccess) PA_FAIL(e, "nms launch failed: %s", hipGetErrorString(r));
     // ---- results back to the caller's arrays (rows beyond max_det are never written on device)
     if (m->d.dtype == PA_DTYPE_H2)      // the overflow flag travels with the results: pa_model_take_overflow needs no device round trip
         PA_HIP(e, hipMemcpyAsync(m->h_pin + ovf_slot, m->d_ovf, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    PA_HIP(e, hipMemcpyAsync(out_counts, m->d_ocnt, nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    PA_HIP(e, hipMemcpyAsync(out_boxes, m->d_oboxes,
+    PA_HIP(e, hipMemcpyAsync(out_counts, L.d_ocnt, nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    PA_HIP(e, hipMemcpyAsync(out_boxes, L.d_oboxes,
                              (size_t)nb * p->max_det * 6 * sizeof(float), hipMemcpyDeviceToHost, s));
     if (m->d.nk)
-        PA_HIP(e, hipMemcpyAsync(out_kpts, m->d_okpts,
+        PA_HIP(e, hipMemcpyAsync(out_kpts, L.d_okpts,
                                  (size_t)nb * p->max_det * m->d.nk * sizeof(float), hipMemcpyDeviceToHost, s));
     return 0;
 }
@@ -112,7 +160,8 @@ static int set_classes(pa_model* m, const pa_yolo_params* p) {
     if (p->n_classes <= 0) return 0;
     if ((int)m->classes_host.size() == p->n_classes && !memcmp(m->classes_host.data(), p->classes, p->n_classes * sizeof(int32_t))) return 0;
     // (the device list is read by queued decode kernels: replace it only once they are done)
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));        // (behind every ticket's join)
+    PA_HIP(e, e->sync_lanes());
     if (p->n_classes > m->classes_cap) {
         if (m->d_classes) hipFree(m->d_classes);
         m->d_classes = nullptr; m->classes_cap = 0; m->classes_host.clear();
@@ -140,37 +189,41 @@ static int yolo_prepare(pa_model* m, const uint8_t* frames, int n, int h, int w,
     return set_classes(m, p);
 }
 
-// everything one batch of nb <= max_batch frames needs, enqueued on the engine's stream: upload (host frames), preprocessing,
-// network, decode, NMS, result copies (the overflow flag of h2 models into h_pin[ovf_slot]).  Does not wait.
-static int yolo_enqueue(pa_model* m, const uint8_t* src, int nb, int h, int w, const pa_yolo_params* p, float* out_boxes,
+// everything one batch of nb <= max_batch frames needs, enqueued on lane li's stream behind what the main stream held at the call
+// (fork_lane): upload (host frames), preprocessing, network, decode, NMS, result copies (the overflow flag of h2 models into
+// h_pin[ovf_slot]).  Does not wait.
+static int yolo_enqueue(pa_model* m, int li, const uint8_t* src, int nb, int h, int w, const pa_yolo_params* p, float* out_boxes,
                         float* out_kpts, int32_t* out_counts, int ovf_slot, size_t* ppi) {
     pa_engine* e = m->e;
-    hipStream_t s = e->stream;
+    Lane& L = m->ln[li];
+    hipStream_t s = L.stream;
+    PA_HIP(e, e->fork_lane(li));
+    m->last_lane = li;
     size_t& pi = *ppi;
     const size_t frame_bytes = (size_t)h * w * 3;
     const int S = p->imgsz;
     // scale_boxes / scale_coords parameters (upstream treats the PIL-resized image as the source)
     const int oh = p->pre_mode == PA_PRE_PIL_STRETCH ? S : h, ow = p->pre_mode == PA_PRE_PIL_STRETCH ? S : w;
-    if (!p->frames_on_device && stage_frames(m, &src, nb, frame_bytes)) return 1;
+    if (!p->frames_on_device && stage_frames(m, &src, nb, frame_bytes, s)) return 1;
     // ---- preprocessing -> u8 NHWC4 network input
-    ProfRec* pr = prof_begin(m, pi++, PROF_PRE, 0, 0.0);
+    ProfRec* pr = prof_begin(m, s, pi++, PROF_PRE, 0, 0.0);
     hipError_t r = hipSuccess;
     if (p->pre_mode == PA_PRE_LETTERBOX || (h == S && w == S)) {
         LetterboxArgs a{};
-        a.src = src; a.dst = m->d_netin; a.B = nb; a.h0 = h; a.w0 = w; a.rw = m->rw; a.rh = m->rh;
+        a.src = src; a.dst = L.d_netin; a.B = nb; a.h0 = h; a.w0 = w; a.rw = m->rw; a.rh = m->rh;
         a.top = m->top; a.left = m->left; a.nh = m->net_h; a.nw = m->net_w; a.mode = m->lb_mode;
         a.reverse = p->channel_reverse; a.xtab = m->d_xtab; a.ytab = m->d_ytab;
         r = launch_letterbox(a, s);
     } else {
-        r = resample_enqueue(m->rs, src, m->d_netin, nb, 4, p->channel_reverse, s);
+        r = resample_enqueue(m->rs, src, L.d_netin, nb, 4, p->channel_reverse, s, L.d_rs_tmp);
     }
-    prof_end(m, pr);
+    prof_end(s, pr);
     if (r != hipSuccess) PA_FAIL(e, "preprocess launch failed: %s", hipGetErrorString(r));
     // ---- network (without the heads' last convs when the fused head tail runs them: the same decision in run_ops)
     const bool fused = head_fused(m);
-    if (run_graph(m, nb, &pi)) return 1;
+    if (run_graph(m, L, s, nb, &pi)) return 1;
     // ---- decode + NMS + results back to the caller's arrays
-    return run_post(m, p, nb, oh, ow, &pi, out_boxes, m->d.nk ? out_kpts : nullptr, out_counts, ovf_slot, fused);
+    return run_post(m, L, p, nb, oh, ow, &pi, out_boxes, m->d.nk ? out_kpts : nullptr, out_counts, ovf_slot, fused);
 }
 
 int pa_yolo_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, const pa_yolo_params* p,
@@ -178,18 +231,19 @@ int pa_yolo_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, const
     if (!m || !p) return 1;
     pa_engine* e = m->e;
     if (yolo_prepare(m, frames, n, h, w, p, out_boxes, out_kpts, out_counts, "pa_yolo_infer")) return 1;
-    hipStream_t s = e->stream;
+    hipStream_t s = m->ln[0].stream;          // synchronous calls run on lane 0
     const size_t frame_bytes = (size_t)h * w * 3;
     size_t pi = 0;
     for (int c0 = 0; c0 < n; c0 += m->max_batch) {
         const int nb = std::min(m->max_batch, n - c0);
-        if (yolo_enqueue(m, frames + (size_t)c0 * frame_bytes, nb, h, w, p, out_boxes + (size_t)c0 * p->max_det * 6,
+        if (yolo_enqueue(m, 0, frames + (size_t)c0 * frame_bytes, nb, h, w, p, out_boxes + (size_t)c0 * p->max_det * 6,
                          m->d.nk ? out_kpts + (size_t)c0 * p->max_det * m->d.nk : nullptr, out_counts + c0, PA_MAX_INFLIGHT, &pi))
             return 1;
-        PA_HIP(e, hipStreamSynchronize(s));          // (also completes every ticket still in flight; their waits return at once)
+        PA_HIP(e, hipStreamSynchronize(s));
         m->last_n = nb;
         if (m->d.dtype == PA_DTYPE_H2) { m->h_ovf |= m->h_pin[PA_MAX_INFLIGHT]; m->ovf_cached = true; }
     }
+    PA_HIP(e, e->sync_lanes());          // a synchronous call completes every ticket still in flight, on either lane: their waits return at once
     finish_profile(m, pi);
     return 0;
 }
@@ -204,14 +258,23 @@ int pa_yolo_submit(pa_model* m, const uint8_t* frames, int n, int h, int w, cons
     const int slot = m->next_ticket % PA_MAX_INFLIGHT;
     if (m->tk_busy[slot]) PA_FAIL(e, "pa_yolo_submit: %d tickets in flight (PA_MAX_INFLIGHT)", PA_MAX_INFLIGHT);
     if (yolo_prepare(m, frames, n, h, w, p, out_boxes, out_kpts, out_counts, "pa_yolo_submit")) return 1;
+    const LaneState st[kMaxLanes] = {m->ln[0].st, m->ln[1].st};
+    int li = pick_lane(st, second_lane_ok(m));
+    if (li == 1 && !m->ln[1].allocated && !alloc_second_lane(m)) li = 0;
+    Lane& L = m->ln[li];
     size_t pi = 0;
-    if (yolo_enqueue(m, frames, n, h, w, p, out_boxes, out_kpts, out_counts, slot, &pi)) {
+    if (yolo_enqueue(m, li, frames, n, h, w, p, out_boxes, out_kpts, out_counts, slot, &pi)) {
         // part of the call may be queued already (preprocessing, some layers) and would write into the caller's arrays with
         // no ticket to wait on: drain before reporting the failure
-        (void)hipStreamSynchronize(e->stream);
+        (void)hipStreamSynchronize(L.stream);
         return 1;
     }
-    PA_HIP(e, hipEventRecord(m->tk_ev[slot], e->stream));
+    PA_HIP(e, hipEventRecord(m->tk_ev[slot], L.stream));
+    // join: whatever goes onto the main stream from here on runs behind this ticket, as when the ticket itself ran there
+    PA_HIP(e, e->join_lane(m->tk_ev[slot]));
+    L.st.busy = true;
+    L.st.last_ticket = m->next_ticket;
+    m->tk_lane[slot] = li;
     m->tk_busy[slot] = true;
     ++m->n_inflight;
     m->last_n = n;
@@ -231,6 +294,8 @@ int pa_yolo_wait(pa_model* m, int ticket, int* overflow) {
     PA_HIP(e, hipEventSynchronize(m->tk_ev[slot]));
     m->tk_busy[slot] = false;
     --m->n_inflight;
+    Lane& L = m->ln[m->tk_lane[slot]];
+    if (L.st.last_ticket == ticket) L.st.busy = false;
     if (overflow) *overflow = (m->d.dtype == PA_DTYPE_H2 && m->h_pin[slot]) ? 1 : 0;
     return 0;
 }
@@ -245,18 +310,21 @@ int pa_yolo_postprocess(pa_model* m, const float* const* heads, int n, int h, in
     PA_HIP(e, hipSetDevice(e->dev));
     if (!yolo_plan_current(m, h, w, p) && plan_yolo(m, h, w, p)) return 1;
     if (set_classes(m, p)) return 1;
-    hipStream_t s = e->stream;
+    Lane& L = m->ln[0];
+    hipStream_t s = L.stream;
+    PA_HIP(e, e->fork_lane(0));
+    m->last_lane = 0;
     const int cs = m->bufs[m->d.head_buf[0]].channels;
     for (int l = 0; l < 3; ++l) {
         if (!heads[l]) PA_FAIL(e, "pa_yolo_postprocess: heads[%d] is NULL", l);
-        PA_HIP(e, hipMemcpyAsync(const_cast<float*>(m->lv[l].buf), heads[l], (size_t)n * m->lv[l].H * m->lv[l].W * cs * sizeof(float),
+        PA_HIP(e, hipMemcpyAsync(const_cast<float*>(L.lv[l].buf), heads[l], (size_t)n * L.lv[l].H * L.lv[l].W * cs * sizeof(float),
                                  hipMemcpyHostToDevice, s));
     }
     const int S = p->imgsz;
     const int oh = p->pre_mode == PA_PRE_PIL_STRETCH ? S : h, ow = p->pre_mode == PA_PRE_PIL_STRETCH ? S : w;
     size_t pi = 0;
-    if (run_post(m, p, n, oh, ow, &pi, out_boxes, out_kpts, out_counts, PA_MAX_INFLIGHT, false)) return 1;
-    PA_HIP(e, hipStreamSynchronize(s));
+    if (run_post(m, L, p, n, oh, ow, &pi, out_boxes, out_kpts, out_counts, PA_MAX_INFLIGHT, false)) return 1;
+    PA_HIP(e, e->sync_lanes());
     m->last_n = n;
     finish_profile(m, pi);
     return 0;
@@ -264,22 +332,32 @@ int pa_yolo_postprocess(pa_model* m, const float* const* heads, int n, int h, in
 
 int pa_yolo_head_shape(pa_model* m, int level, int* h, int* w, int* c) {
     if (!m->planned || level < 0 || level > 2) PA_FAIL(m->e, "pa_yolo_head_shape: no plan / bad level");
-    *h = m->lv[level].H; *w = m->lv[level].W; *c = m->bufs[m->d.head_buf[0]].channels;
+    *h = m->ln[0].lv[level].H; *w = m->ln[0].lv[level].W; *c = m->bufs[m->d.head_buf[0]].channels;
     return 0;
 }
 
 int pa_yolo_read_head(pa_model* m, int level, int n, float* out) {
     pa_engine* e = m->e;
+    if (m->d.task != PA_TASK_DETECT && m->d.task != PA_TASK_POSE) PA_FAIL(e, "pa_yolo_read_head on a non-YOLO model");
     if (!m->planned || level < 0 || level > 2 || n > m->last_n) PA_FAIL(e, "pa_yolo_read_head: no plan / bad level / n");
     PA_HIP(e, hipSetDevice(e->dev));
+    Lane& L = m->ln[m->last_lane];          // the lane of the model's last call
+    hipStream_t s = L.stream;
     if (m->heads_stale) {          // the last call ran the fused head tail: the maps of its last_n images from the tail convs' inputs, once
-        if (run_tail_ops(m, m->last_n)) return 1;
+        if (run_tail_ops(m, L, s, m->last_n)) return 1;
         m->heads_stale = false;
     }
-    const size_t bytes = (size_t)n * m->lv[level].H * m->lv[level].W * m->bufs[m->d.head_buf[0]].channels * sizeof(float);
-    PA_HIP(e, hipMemcpyAsync(out, m->lv[level].buf, bytes, hipMemcpyDeviceToHost, e->stream));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    const size_t bytes = (size_t)n * L.lv[level].H * L.lv[level].W * m->bufs[m->d.head_buf[0]].channels * sizeof(float);
+    PA_HIP(e, hipMemcpyAsync(out, L.lv[level].buf, bytes, hipMemcpyDeviceToHost, s));
+    PA_HIP(e, hipStreamSynchronize(s));
     return 0;
+}
+
+int pa_yolo_resample_passes(pa_model* m) {
+    if (!m || !m->planned) return 0;
+    const ResamplePlan& r = m->rs;
+    const int passes = (r.sw != r.dw ? 1 : 0) + (r.sh != r.dh ? 1 : 0);
+    return passes == 2 && !r.d_tmp ? -1 : passes;          // (two passes always have their temporary)
 }
 
 int pa_yolo_last_post_path(pa_model* m) { return m ? m->last_post_path : 0; }
@@ -292,9 +370,11 @@ int pa_yolo_netin_shape(pa_model* m, int* h, int* w) {
 
 int pa_yolo_read_netin(pa_model* m, int n, uint8_t* out) {
     pa_engine* e = m->e;
-    if (!m->planned || !m->d_netin || n < 1 || n > m->last_n || !out) PA_FAIL(e, "pa_yolo_read_netin: no plan / bad n");
+    if (!m->planned || !m->ln[0].d_netin || n < 1 || n > m->last_n || !out) PA_FAIL(e, "pa_yolo_read_netin: no plan / bad n");
     PA_HIP(e, hipSetDevice(e->dev));
-    PA_HIP(e, hipMemcpyAsync(out, m->d_netin, (size_t)n * m->net_h * m->net_w * 4, hipMemcpyDeviceToHost, e->stream));
-    PA_HIP(e, hipStreamSynchronize(e->stream));
+    Lane& L = m->ln[m->last_lane];
+    const hipStream_t s = L.stream ? L.stream : e->main_stream();          // (a ResNet plan has a network input too: it runs on the main stream)
+    PA_HIP(e, hipMemcpyAsync(out, L.d_netin, (size_t)n * m->net_h * m->net_w * 4, hipMemcpyDeviceToHost, s));
+    PA_HIP(e, hipStreamSynchronize(s));
     return 0;
 }

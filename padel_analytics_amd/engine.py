@@ -122,6 +122,7 @@ ABI_SYMBOLS = [
     "pa_jpeg_encode", "pa_jpeg_check", "pa_jpeg_interval_bytes",
     "pa_jpeg_parse", "pa_jpeg_decode", "pa_jpeg_decode_last_path", "pa_jpeg_decode_last_times",
     "pa_yolo_last_post_path", "pa_jpeg_decode_set_split", "pa_jpeg_decode_last_split",
+    "pa_model_lanes_allocated", "pa_model_last_lane", "pa_yolo_resample_passes",
 ]
 
 
@@ -163,6 +164,9 @@ def load_library():
     lib.pa_yolo_head_shape.argtypes = [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     lib.pa_yolo_read_head.argtypes = [vp, i32, i32, vp]
     lib.pa_yolo_last_post_path.argtypes = [vp]
+    lib.pa_model_lanes_allocated.argtypes = [vp]
+    lib.pa_model_last_lane.argtypes = [vp]
+    lib.pa_yolo_resample_passes.argtypes = [vp]
     lib.pa_tracknet_infer.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
     lib.pa_resnet_infer.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
     lib.pa_resnet_read_netin.argtypes = [vp, i32, vp]
@@ -582,7 +586,8 @@ class Engine:
         return float(ms.value)
 
     def set_tuning(self, **kv):
-        """Tests / tools only: impl (2 bx3, 0 tap; 1 — the retired LDS kernel — is refused), variant (tile id, -1 auto), tune, tap_pd, graph, alias, fold_up, timeline, fuse_stem, fuse_sppf, fuse_head."""
+        """Tests / tools only: impl (2 bx3, 0 tap; 1 — the retired LDS kernel — is refused), variant (tile id, -1 auto), tune, tap_pd, graph, alias, fold_up, timeline, fuse_stem, fuse_sppf, fuse_head,
+        lanes (2: alternate in-flight YOLO tickets run on two streams with their own activation memory, 1: one lane; same results)."""
         for k, v in kv.items():
             self._check(self.lib.pa_engine_set_tuning(self.handle, k.encode(), int(v)))
             if k == "timeline":
@@ -901,6 +906,19 @@ class Model:
         """POST_PATH_DECODE / POST_PATH_FUSED: what the last ``yolo_infer`` / ``yolo_submit`` / ``postprocess`` of this model ran
         after the network — ``decode_kernel`` over head maps, or the fused head tail (tuning ``fuse_head``)."""
         return int(self.engine.lib.pa_yolo_last_post_path(self.handle))
+
+    def lanes_allocated(self) -> int:
+        """How many lanes (sets of per-batch device memory) the current plan has: 0 before a plan, 1, or 2 once a ``yolo_submit``
+        found the previous ticket still in flight (tuning ``lanes``)."""
+        return int(self.engine.lib.pa_model_lanes_allocated(self.handle))
+
+    def resample_passes(self) -> int:
+        """Tests: passes of the Pillow resample of the current plan (0 none, 1 one axis, 2 both axes through a temporary)."""
+        return int(self.engine.lib.pa_yolo_resample_passes(self.handle))
+
+    def last_lane(self) -> int:
+        """The lane (0 | 1) the model's last ``yolo_infer`` / ``yolo_submit`` / ``postprocess`` ran on."""
+        return int(self.engine.lib.pa_model_last_lane(self.handle))
 
     def read_netin(self, n: int) -> np.ndarray:
         """u8 NHWC4 network input of the first n frames of the last yolo_infer call."""
