@@ -136,6 +136,11 @@ int pa_engine_synchronize(pa_engine* eng);
 /* raw device memory helpers (bench keeps frames resident in HBM with these) */
 int pa_device_malloc(pa_engine* eng, size_t nbytes, void** out_dev);
 int pa_device_free(pa_engine* eng, void* dev);
+/* Device bytes the library itself holds in this process at the moment, over all engines: weights, plans, lanes, ball sessions
+ * and the scratch buffers of the conversion, render and JPEG calls.  Memory handed out by pa_device_malloc is the caller's and
+ * is not counted, nor is page-locked host memory.  Read-only; a value that returns to where it was after a model, a session or
+ * an engine is destroyed says that everything it owned was released. */
+size_t pa_device_bytes_live(void);
 int pa_memcpy_h2d(pa_engine* eng, void* dst_dev, const void* src_host, size_t nbytes);
 int pa_memcpy_d2h(pa_engine* eng, void* dst_host, const void* src_dev, size_t nbytes);
 /* host -> HBM on the engine's copy stream: does not queue behind inference launched from another host

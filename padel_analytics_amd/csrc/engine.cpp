@@ -4,7 +4,18 @@
 // the op-list replay (run_ops / run_graph) and the profile text; engine_internal.h names the other files.
 #include "engine_internal.h"
 
+#include <atomic>
+
 thread_local std::string g_err;
+
+// device_mem.h's hooks: every allocation a DevMem / PinMem of the engine owns is made and released here, and the device bytes
+// they hold are counted for the whole process (pa_device_bytes_live: a release that was forgotten shows as a number)
+static std::atomic<size_t> g_live_bytes{0};
+int dev_alloc(void** p, size_t bytes) { const hipError_t r = hipMalloc(p, bytes); if (r == hipSuccess) g_live_bytes += bytes; return (int)r; }
+void dev_free(void* p, size_t bytes) { (void)hipFree(p); g_live_bytes -= bytes; }
+int pin_alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+void pin_free(void* p, size_t) { (void)hipHostFree(p); }
+size_t pa_device_bytes_live(void) { return g_live_bytes.load(); }
 
 // Every tuning knob but `impl` (whose environment value is a word): pa_engine_set_tuning key, environment variable read once at
 // pa_engine_create (none: set_tuning only), field, and how a value is normalised on both ways in.  A flag is only ever tested
@@ -49,8 +60,8 @@ int pa_engine_create(int device_id, pa_engine** out) {
     hipError_t r = e->create_streams();
     if (r == hipSuccess) r = hipStreamCreateWithFlags(&e->copy_stream, hipStreamNonBlocking);
     if (r != hipSuccess) { pa_engine_destroy(e); PA_FAIL((pa_engine*)nullptr, "hipStreamCreate: %s", hipGetErrorString(r)); }
-    r = hipMalloc((void**)&e->zeros, 256);
-    if (r == hipSuccess) r = hipMemset(e->zeros, 0, 256);
+    r = (hipError_t)e->zeros.alloc(256);
+    if (r == hipSuccess) r = hipMemset(e->zeros.get(), 0, 256);
     if (r != hipSuccess) { delete e; PA_FAIL((pa_engine*)nullptr, "zero page: %s", hipGetErrorString(r)); }
     r = padel::init_misc_kernels();
     if (r == hipSuccess) r = padel::init_head_tail_kernels();
@@ -122,16 +133,13 @@ void pa_engine_destroy(pa_engine* e) {
     if (!e) return;
     hipSetDevice(e->dev);
     pa_engine_comm_destroy(e);
-    if (e->zeros) hipFree(e->zeros);
     if (e->main_stream_wait_only()) hipStreamSynchronize(e->main_stream_wait_only());
-    if (e->yuv_stage) hipFree(e->yuv_stage);
-    if (e->render_stage) hipFree(e->render_stage);
     jpeg_scratch_free(e);
     jpeg_dec_scratch_free(e);
     for (hipEvent_t ev : e->timer_ev) if (ev) hipEventDestroy(ev);
     e->destroy_streams();
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);
-    delete e;
+    delete e;          // zeros, yuv_stage, render_stage: idle since the wait above
 }
 
 int pa_engine_synchronize(pa_engine* e) {
@@ -224,15 +232,15 @@ int pa_model_create(pa_engine* e, const pa_model_desc* desc, const float* weight
     m->n_w = n_floats;
     if (desc->task == PA_TASK_DETECT || desc->task == PA_TASK_POSE)
         for (int i = 0; i < kMaxLanes; ++i) m->ln[i].stream = e->lane_stream[i];
-    hipError_t r = hipMalloc((void**)&m->d_w, n_floats * sizeof(float) + kConvReadSlack);
+    hipError_t r = (hipError_t)m->d_w.alloc(n_floats * sizeof(float) + kConvReadSlack);
     if (r == hipSuccess)
-        r = weights ? hipMemcpyAsync(m->d_w, weights, n_floats * sizeof(float), hipMemcpyHostToDevice, e->main_stream())
-                    : hipMemsetAsync(m->d_w, 0, n_floats * sizeof(float), e->main_stream());
-    if (r == hipSuccess) r = hipMemsetAsync(m->d_w + n_floats, 0, kConvReadSlack, e->main_stream());
-    if (r == hipSuccess) r = hipMalloc((void**)&m->d_ovf, 256);
-    if (r == hipSuccess) r = hipMemsetAsync(m->d_ovf, 0, 256, e->main_stream());
-    if (r == hipSuccess) r = hipHostMalloc((void**)&m->h_pin, 64 * sizeof(unsigned), hipHostMallocDefault);
-    if (r == hipSuccess) memset(m->h_pin, 0, 64 * sizeof(unsigned));
+        r = weights ? hipMemcpyAsync(m->d_w.get(), weights, n_floats * sizeof(float), hipMemcpyHostToDevice, e->main_stream())
+                    : hipMemsetAsync(m->d_w.get(), 0, n_floats * sizeof(float), e->main_stream());
+    if (r == hipSuccess) r = hipMemsetAsync(m->d_w.get() + n_floats, 0, kConvReadSlack, e->main_stream());
+    if (r == hipSuccess) r = (hipError_t)m->d_ovf.alloc(256);
+    if (r == hipSuccess) r = hipMemsetAsync(m->d_ovf.get(), 0, 256, e->main_stream());
+    if (r == hipSuccess) r = (hipError_t)m->h_pin.alloc(64 * sizeof(unsigned));
+    if (r == hipSuccess) memset(m->h_pin.get(), 0, 64 * sizeof(unsigned));
     for (int k = 0; k < PA_MAX_INFLIGHT && r == hipSuccess; ++k) r = hipEventCreateWithFlags(&m->tk_ev[k], hipEventDisableTiming);
     if (r == hipSuccess) r = hipStreamSynchronize(e->main_stream_wait_only());
     if (r != hipSuccess) { delete m; PA_FAIL(e, "weights upload: %s", hipGetErrorString(r)); }
@@ -250,9 +258,6 @@ static void destroy_graphs(pa_model* m) {
 void free_lane(Lane& L) {
     for (auto& g : L.graphs) hipGraphExecDestroy(g.second);
     L.graphs.clear();
-    void* ptrs[] = {L.arena, L.d_fc, L.d_stage, L.d_netin, L.d_rs_tmp, L.d_cand, L.d_cidx, L.d_ccnt, L.d_keys, L.d_order, L.d_supp,
-                    L.d_oboxes, L.d_okpts, L.d_ocnt};
-    for (void* p : ptrs) if (p) hipFree(p);
     const hipStream_t s = L.stream;
     L = Lane{};
     L.stream = s;
@@ -261,10 +266,9 @@ void free_lane(Lane& L) {
 void free_plan(pa_model* m) {
     (void)m->e->sync_lanes();
     for (Lane& L : m->ln) free_lane(L);
-    if (m->d_xtab) hipFree(m->d_xtab);
-    if (m->d_ytab) hipFree(m->d_ytab);
-    m->d_xtab = m->d_ytab = nullptr;
-    resample_free(&m->rs);
+    m->d_xtab.reset();
+    m->d_ytab.reset();
+    m->rs = ResamplePlan{};
     m->lane1_refused = false;
     m->last_lane = 0;
     m->planned = false;
@@ -277,14 +281,8 @@ void pa_model_destroy(pa_model* m) {
     hipStreamSynchronize(m->e->main_stream_wait_only());      // (behind every ticket's join; free_plan drains the lanes themselves)
     free_plan(m);
     for (auto& r : m->prof) { hipEventDestroy(r.e0); hipEventDestroy(r.e1); }
-    if (m->d_frames) hipFree(m->d_frames);
-    if (m->d_classes) hipFree(m->d_classes);
-    if (m->d_w) hipFree(m->d_w);
-    if (m->d_wr) hipFree(m->d_wr);
-    if (m->d_ovf) hipFree(m->d_ovf);
-    if (m->h_pin) hipHostFree(m->h_pin);
     for (int k = 0; k < PA_MAX_INFLIGHT; ++k) if (m->tk_ev[k]) hipEventDestroy(m->tk_ev[k]);
-    delete m;
+    delete m;          // weights, operand copies, flags, staging: idle since the wait above
 }
 
 int pa_model_take_overflow(pa_model* m, int* out) {
@@ -297,13 +295,13 @@ int pa_model_take_overflow(pa_model* m, int* out) {
     if (m->ovf_cached) {                 // pa_yolo_infer read the flag back with its results (nothing has run on the model since)
         v = m->h_ovf;
     } else {
-        PA_HIP(e, hipMemcpyAsync(&v, m->d_ovf, sizeof(v), hipMemcpyDeviceToHost, e->main_stream()));
+        PA_HIP(e, hipMemcpyAsync(&v, m->d_ovf.get(), sizeof(v), hipMemcpyDeviceToHost, e->main_stream()));
         PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     }
     m->ovf_cached = false;
     m->h_ovf = 0;
     if (v) {
-        PA_HIP(e, hipMemsetAsync(m->d_ovf, 0, sizeof(v), e->main_stream()));
+        PA_HIP(e, hipMemsetAsync(m->d_ovf.get(), 0, sizeof(v), e->main_stream()));
         PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     }
     *out = v ? 1 : 0;
@@ -333,13 +331,13 @@ int plan_buffers(pa_model* m, Lane& L, int batch, hipStream_t s) {
         }
     }
     if (m->fc_nout) {
-        PA_HIP(e, hipMalloc((void**)&L.d_fc, (size_t)batch * 2 * kGapFcMaxOut * sizeof(float)));
-        PA_HIP(e, hipMemsetAsync(L.d_fc, 0, (size_t)batch * 2 * kGapFcMaxOut * sizeof(float), s));
+        PA_HIP(e, L.d_fc.alloc((size_t)batch * 2 * kGapFcMaxOut * sizeof(float)));
+        PA_HIP(e, hipMemsetAsync(L.d_fc.get(), 0, (size_t)batch * 2 * kGapFcMaxOut * sizeof(float), s));
     }
-    PA_HIP(e, hipMalloc(&L.arena, bp.arena_bytes + kConvReadSlack));
-    PA_HIP(e, hipMemsetAsync(L.arena, 0, bp.arena_bytes + kConvReadSlack, s));
+    PA_HIP(e, L.arena.alloc(bp.arena_bytes + kConvReadSlack));
+    PA_HIP(e, hipMemsetAsync(L.arena.get(), 0, bp.arena_bytes + kConvReadSlack, s));
     L.bptr.assign(m->bufs.size(), nullptr);
-    for (size_t i = 0; i < m->bufs.size(); ++i) L.bptr[i] = reinterpret_cast<float*>(static_cast<char*>(L.arena) + bp.off[i]);
+    for (size_t i = 0; i < m->bufs.size(); ++i) L.bptr[i] = reinterpret_cast<float*>(L.arena.get() + bp.off[i]);
     L.allocated = true;
     m->arena_bytes = bp.arena_bytes;
     m->logical_bytes = bp.logical_bytes;
@@ -382,8 +380,8 @@ static int conv_launch_args(const pa_model* m, const Lane& L, size_t i, int n, C
     a.res = o.res_buf >= 0 ? L.bptr[o.res_buf] : nullptr;
     a.res_cs = o.res_buf >= 0 ? m->bufs[o.res_buf].channels : 0; a.res_choff = o.res_choff;
     a.res_pre = (o.res_buf >= 0 && (o.flags & PA_CONV_RES_PREACT)) ? 1 : 0;
-    a.zeros = e->zeros;
-    a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off;
+    a.zeros = e->zeros.get();
+    a.w = m->d_w.get() + o.w_off; a.bias = m->d_w.get() + o.b_off;
     a.H = m->net_h >> ib.level; a.W = m->net_w >> ib.level; a.Ho = Ho; a.Wo = Wo;
     a.cin = o.cin; a.cout = o.cout; a.n16 = o.npad / 16; a.ksize = o.ksize; a.stride = o.stride; a.act = o.act;
     a.M = n * Ho * Wo;
@@ -392,15 +390,15 @@ static int conv_launch_args(const pa_model* m, const Lane& L, size_t i, int n, C
     a.tune = e->t.tune; a.tap_pd = e->t.tap_pd;
     const bool f16 = m->d.dtype == PA_DTYPE_F16, h2 = m->d.dtype == PA_DTYPE_H2;
     const bool use_bx3 = !f16 && !h2 && e->t.impl == 2 && o.reserved > 0;
-    a.w3 = use_bx3 ? (const void*)(m->d_w + o.reserved) : nullptr;
+    a.w3 = use_bx3 ? (const void*)(m->d_w.get() + o.reserved) : nullptr;
     a.out_f32 = (f16 || h2) && is_head_buf(m->d, o.out_buf);
     const int path = h2 ? CONV_PATH_H2 : f16 ? CONV_PATH_F16 : use_bx3 ? CONV_PATH_BX3 : CONV_PATH_TAP;
     if (path_out) *path_out = path;
     if (h2) {
-        a.oscale = m->d_w + o.reserved;
-        a.ovf_flag = m->d_ovf;
+        a.oscale = m->d_w.get() + o.reserved;
+        a.ovf_flag = m->d_ovf.get();
         a.w_single = (o.flags & PA_CONV_W_SINGLE) && e->t.w_single ? 1 : 0;
-        a.wr = (m->wr_valid && i < m->wr_off.size() && m->wr_off[i] >= 0) ? (const void*)(m->d_wr + m->wr_off[i]) : nullptr;
+        a.wr = (m->wr_valid && i < m->wr_off.size() && m->wr_off[i] >= 0) ? (const void*)(m->d_wr.get() + m->wr_off[i]) : nullptr;
     }
     const int lv = e->t.variant >= 0 ? e->t.variant
                    : h2 ? choose_conv_h2_variant(a)
@@ -425,7 +423,7 @@ void head_tail_convs(const pa_model* m, const Lane& L, HeadTailArgs& a) {
             if (i < 0) continue;
             const pa_op_desc& o = m->ops[i];
             v.in = L.bptr[o.in_buf]; v.in_cs = m->bufs[o.in_buf].channels; v.in_choff = o.in_choff;
-            v.w = m->d_w + o.w_off; v.bias = m->d_w + o.b_off; v.oscale = m->d_w + o.reserved;
+            v.w = m->d_w.get() + o.w_off; v.bias = m->d_w.get() + o.b_off; v.oscale = m->d_w.get() + o.reserved;
             v.cin = o.cin; v.n16 = o.npad / 16;
             single = single && (o.flags & PA_CONV_W_SINGLE);
         }
@@ -477,7 +475,7 @@ static int run_ops(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
             pr = prof_begin(m, s, (*pi)++, o.kind, o.ksize, 2.0 * a.M * (double)o.cout * o.cin * o.ksize * o.ksize);
             if (pr) { pr->M = a.M; pr->cout = o.cout; pr->cin = o.cin; pr->stride = o.stride; pr->mf = bm; pr->nf = bn; pr->res = a.res != nullptr; }
             // tuning only ("timeline"): collect the s_memtime timeline of this launch into timeline_path
-            unsigned long long* dbg_dev = nullptr;
+            DevMem<unsigned long long> dbg_dev;          // per launch: released where this op's turn ends, behind the wait below
             size_t dbg_bytes = 0;
             ConvLaunched will{-1, ""};
             if (e->t.timeline && !e->timeline_path.empty() && resolve_conv(path, a, lv, &will) && will.tile == lv) {
@@ -486,9 +484,8 @@ static int run_ops(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
                 dbg_bytes = records * conv_timeline_words(will, o.ksize) * 8;          // 0: this kernel has no timeline instantiation
             }
             if (dbg_bytes) {
-                if (hipMalloc(&dbg_dev, dbg_bytes) == hipSuccess) (void)hipMemsetAsync(dbg_dev, 0, dbg_bytes, s);
-                else dbg_dev = nullptr;
-                a.dbg = dbg_dev;
+                if (dbg_dev.alloc(dbg_bytes) == 0) (void)hipMemsetAsync(dbg_dev.get(), 0, dbg_bytes, s);
+                a.dbg = dbg_dev.get();
             }
             ConvLaunched ran{-1, ""};
             // act(conv + bias + residual) exists in the h2 and bf16x3 epilogues; the other families refuse instead of applying the other order
@@ -500,18 +497,17 @@ static int run_ops(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
             if (dbg_dev) {
                 (void)hipStreamSynchronize(s);
                 std::vector<unsigned long long> host(dbg_bytes / 8);
-                (void)hipMemcpy(host.data(), dbg_dev, dbg_bytes, hipMemcpyDeviceToHost);
+                (void)hipMemcpy(host.data(), dbg_dev.get(), dbg_bytes, hipMemcpyDeviceToHost);
                 if (FILE* f = fopen(e->timeline_path.c_str(), "wb")) { fwrite(host.data(), 1, dbg_bytes, f); fclose(f); }
-                (void)hipFree(dbg_dev);
             }
         } else if (o.kind == PA_OP_STEM) {
             StemArgs a{};
-            a.in = L.d_netin; a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off;
+            a.in = L.d_netin.get(); a.w = m->d_w.get() + o.w_off; a.bias = m->d_w.get() + o.b_off;
             a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
             a.H = m->net_h; a.W = m->net_w; a.Ho = Ho; a.Wo = Wo; a.cout = o.cout; a.B = n;
             a.out_f16 = m->d.dtype == PA_DTYPE_F16 ? 1 : m->d.dtype == PA_DTYPE_H2 ? 2 : 0;
-            a.ovf_flag = m->d_ovf;
-            a.opw = (m->wr_valid && i < m->wr_off.size() && m->wr_off[i] >= 0) ? (const void*)(m->d_wr + m->wr_off[i]) : nullptr;
+            a.ovf_flag = m->d_ovf.get();
+            a.opw = (m->wr_valid && i < m->wr_off.size() && m->wr_off[i] >= 0) ? (const void*)(m->d_wr.get() + m->wr_off[i]) : nullptr;
             pr = prof_begin(m, s, (*pi)++, o.kind, 3, 2.0 * n * Ho * Wo * (double)o.cout * 27);
             // tuning "fuse_stem": the stem and the stride-2 3x3 behind it (its only reader) as one kernel; the conv's own
             // turn in this loop is skipped (the profile shows both under the stem's record)
@@ -552,11 +548,11 @@ static int run_ops(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
             if (!L.d_netin) PA_FAIL(e, "op %zu: the 7x7 stem reads the u8 network input of pa_resnet_infer", i);
             const bool head = is_head_buf(m->d, o.out_buf);
             Stem7Args a{};
-            a.in = L.d_netin; a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off; a.lut = m->d_w + o.reserved;
+            a.in = L.d_netin.get(); a.w = m->d_w.get() + o.w_off; a.bias = m->d_w.get() + o.b_off; a.lut = m->d_w.get() + o.reserved;
             a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
             a.H = m->net_h; a.W = m->net_w; a.Ho = Ho; a.Wo = Wo; a.B = n; a.act = o.act;
             a.out_h2 = (m->d.dtype == PA_DTYPE_H2 && !head) ? 1 : 0;
-            a.ovf_flag = m->d_ovf;
+            a.ovf_flag = m->d_ovf.get();
             pr = prof_begin(m, s, (*pi)++, o.kind, 7, 2.0 * n * Ho * Wo * 64.0 * 147.0);
             if (pr) { pr->M = n * Ho * Wo; pr->cout = 64; pr->cin = 3; pr->stride = 2; }
             r = launch_stem7(a, s);
@@ -565,18 +561,18 @@ static int run_ops(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
             const int hw = (m->net_h >> lin) * (m->net_w >> lin);
             pr = prof_begin(m, s, (*pi)++, o.kind, 0, 2.0 * n * (double)o.cout * o.cin);
             if (pr) { pr->M = n; pr->cout = o.cout; pr->cin = o.cin; }
-            r = launch_gap_fc(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, o.cin, n, hw, m->d_w + o.w_off, m->d_w + o.b_off,
-                              o.cout, L.d_fc, L.d_fc + (size_t)m->p_batch * kGapFcMaxOut, s, m->d.dtype == PA_DTYPE_H2 ? 1 : 0);
+            r = launch_gap_fc(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, o.cin, n, hw, m->d_w.get() + o.w_off, m->d_w.get() + o.b_off,
+                              o.cout, L.d_fc.get(), L.d_fc.get() + (size_t)m->p_batch * kGapFcMaxOut, s, m->d.dtype == PA_DTYPE_H2 ? 1 : 0);
         } else if (o.kind == PA_OP_DWCONV3) {
             const bool h2 = m->d.dtype == PA_DTYPE_H2;
             const bool head = is_head_buf(m->d, o.out_buf);
             DwConvArgs a{};
             a.in = L.bptr[o.in_buf]; a.in_cs = m->bufs[o.in_buf].channels; a.in_choff = o.in_choff;
-            a.w = m->d_w + o.w_off; a.bias = m->d_w + o.b_off;
+            a.w = m->d_w.get() + o.w_off; a.bias = m->d_w.get() + o.b_off;
             a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
             if (o.res_buf >= 0) { a.res = L.bptr[o.res_buf]; a.res_cs = m->bufs[o.res_buf].channels; a.res_choff = o.res_choff; }
             a.C = o.cin; a.B = n; a.H = Ho; a.W = Wo; a.act = o.act;
-            a.h2 = h2 ? 1 : 0; a.out_f32 = (h2 && head) ? 1 : 0; a.ovf_flag = m->d_ovf;
+            a.h2 = h2 ? 1 : 0; a.out_f32 = (h2 && head) ? 1 : 0; a.ovf_flag = m->d_ovf.get();
             pr = prof_begin(m, s, (*pi)++, o.kind, 3, 2.0 * n * Ho * Wo * (double)o.cin * 9.0);
             if (pr) { pr->M = n * Ho * Wo; pr->cout = o.cout; pr->cin = o.cin; pr->stride = 1; pr->res = o.res_buf >= 0; }
             r = launch_dwconv3(a, s);
@@ -589,7 +585,7 @@ static int run_ops(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
             a.q_choff = o.in_choff; a.k_choff = o.in_choff + a.heads * a.kd; a.v_choff = o.in_choff + 2 * a.heads * a.kd;
             a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
             a.N = Ho * Wo; a.B = n; a.scale = (float)(1.0 / std::sqrt((double)a.kd));
-            a.h2 = h2 ? 1 : 0; a.out_f32 = (h2 && head) ? 1 : 0; a.ovf_flag = m->d_ovf;
+            a.h2 = h2 ? 1 : 0; a.out_f32 = (h2 && head) ? 1 : 0; a.ovf_flag = m->d_ovf.get();
             pr = prof_begin(m, s, (*pi)++, o.kind, 0, 2.0 * n * (double)a.heads * a.N * (double)a.N * (a.kd + a.hd));
             if (pr) { pr->M = n * a.N; pr->cout = o.cout; pr->cin = o.cin; pr->stride = a.heads; }
             r = launch_psa_attn(a, s);
@@ -610,16 +606,16 @@ static int ensure_operand_copies(pa_model* m) {
     // promise does not hold fails the call instead of computing silently wrong results
     {
         bool any = false;
-        PA_HIP(e, hipMemsetAsync(m->d_ovf + 32, 0, sizeof(unsigned) * 8, e->main_stream()));        // scratch words of the 256-byte flag block
+        PA_HIP(e, hipMemsetAsync(m->d_ovf.get() + 32, 0, sizeof(unsigned) * 8, e->main_stream()));        // scratch words of the 256-byte flag block
         for (size_t i = 0; i < m->ops.size(); ++i) {
             const pa_op_desc& o = m->ops[i];
             if (o.kind != PA_OP_CONV || !(o.flags & PA_CONV_W_SINGLE)) continue;
-            PA_HIP(e, launch_h2_mplane_check(m->d_w + o.w_off, (long long)o.npad * h2_ksteps(o.cin, o.ksize), m->d_ovf + 32, e->main_stream()));
+            PA_HIP(e, launch_h2_mplane_check(m->d_w.get() + o.w_off, (long long)o.npad * h2_ksteps(o.cin, o.ksize), m->d_ovf.get() + 32, e->main_stream()));
             any = true;
         }
         if (any) {
             unsigned bad = 0;
-            PA_HIP(e, hipMemcpyAsync(&bad, m->d_ovf + 32, sizeof(bad), hipMemcpyDeviceToHost, e->main_stream()));
+            PA_HIP(e, hipMemcpyAsync(&bad, m->d_ovf.get() + 32, sizeof(bad), hipMemcpyDeviceToHost, e->main_stream()));
             PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
             if (bad) PA_FAIL(e, "a conv flagged PA_CONV_W_SINGLE has a non-zero m plane in the weight blob (pack it without the flag, or with fp16-number weights)");
         }
@@ -639,8 +635,8 @@ static int ensure_operand_copies(pa_model* m) {
             total += conv_h2r_copy_bytes(o.npad / 16, o.cin, o.ksize);
         }
         if (total) {
-            PA_HIP(e, hipMalloc((void**)&m->d_wr, total + 8192));          // the last chunk's look-ahead reads run 4 KB past a fragment
-            PA_HIP(e, hipMemsetAsync(m->d_wr + total, 0, 8192, e->main_stream()));
+            PA_HIP(e, m->d_wr.fit(total + 8192, total + 8192));          // the last chunk's look-ahead reads run 4 KB past a fragment
+            PA_HIP(e, hipMemsetAsync(m->d_wr.get() + total, 0, 8192, e->main_stream()));
         }
         m->wr_off = std::move(off);        // only once the allocation stands: a failed call leaves no offsets into a null d_wr
     }
@@ -648,10 +644,10 @@ static int ensure_operand_copies(pa_model* m) {
         if (m->wr_off[i] < 0) continue;
         const pa_op_desc& o = m->ops[i];
         if (o.kind == PA_OP_STEM) {
-            PA_HIP(e, launch_stem_l1_operands(m->d_w + o.w_off, o.cout, m->d_wr + m->wr_off[i], e->main_stream()));
+            PA_HIP(e, launch_stem_l1_operands(m->d_w.get() + o.w_off, o.cout, m->d_wr.get() + m->wr_off[i], e->main_stream()));
             continue;
         }
-        PA_HIP(e, launch_h2r_repack(m->d_w + o.w_off, m->d_wr + m->wr_off[i], o.npad / 16, o.cin, o.ksize, e->main_stream()));
+        PA_HIP(e, launch_h2r_repack(m->d_w.get() + o.w_off, m->d_wr.get() + m->wr_off[i], o.npad / 16, o.cin, o.ksize, e->main_stream()));
     }
     // (built on the main stream, read on the lanes: the lanes do not fork for it, the host waits once per model instead)
     PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
@@ -713,9 +709,9 @@ int pa_model_fill_arena(pa_model* m, int byte_value) {
     for (Lane& L : m->ln) {          // every lane the model has, each on the stream its batches run on
         if (!L.allocated) continue;
         const hipStream_t s = L.stream ? L.stream : e->main_stream();
-        PA_HIP(e, hipMemsetAsync(L.arena, byte_value & 0xFF, m->arena_bytes, s));
+        PA_HIP(e, hipMemsetAsync(L.arena.get(), byte_value & 0xFF, m->arena_bytes, s));
         // (the u8 network input as well: the preprocessing of the next call writes all four bytes of every pixel)
-        if (L.d_netin) PA_HIP(e, hipMemsetAsync(L.d_netin, byte_value & 0xFF, (size_t)m->p_batch * m->net_h * m->net_w * 4, s));
+        if (L.d_netin) PA_HIP(e, hipMemsetAsync(L.d_netin.get(), byte_value & 0xFF, (size_t)m->p_batch * m->net_h * m->net_w * 4, s));
         PA_HIP(e, hipStreamSynchronize(s));
     }
     return 0;

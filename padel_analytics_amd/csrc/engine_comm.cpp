@@ -105,7 +105,7 @@ int pa_engine_bcast(pa_engine* e, void* dev_ptr, size_t nbytes, int root) {
 int pa_engine_bcast_weights(pa_engine* e, pa_model* m, int root) {
     if (!e || !m || m->e != e) return 1;
     m->wr_valid = false;
-    return pa_engine_bcast(e, m->d_w, m->n_w * sizeof(float), root);
+    return pa_engine_bcast(e, m->d_w.get(), m->n_w * sizeof(float), root);
 }
 
 // The same broadcast with a separate SOURCE on the root: the root rank sends `src`'s blob (the model it loaded), every rank —
@@ -117,8 +117,8 @@ int pa_engine_bcast_weights_from(pa_engine* e, pa_model* src, pa_model* dst, int
     if (!e->comm) PA_FAIL(e, "pa_engine_bcast_weights_from: call pa_engine_comm_init first");
     PA_HIP(e, hipSetDevice(e->dev));
     dst->wr_valid = false;
-    const void* send = src ? src->d_w : dst->d_w;
-    const ncclResult_t r = e->comm->Broadcast(send, dst->d_w, dst->n_w * sizeof(float), ncclUint8, root, e->comm->comm, e->main_stream());
+    const void* send = src ? src->d_w.get() : dst->d_w.get();
+    const ncclResult_t r = e->comm->Broadcast(send, dst->d_w.get(), dst->n_w * sizeof(float), ncclUint8, root, e->comm->comm, e->main_stream());
     if (r != ncclSuccess) PA_FAIL(e, "ncclBroadcast: %s", e->comm->GetErrorString(r));
     PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     return 0;
@@ -133,8 +133,9 @@ int pa_engine_gather_sizes(pa_engine* e, size_t nbytes, uint64_t* sizes) {
     if (nranks == 1) { sizes[0] = nbytes; return 0; }
     PA_HIP(e, hipSetDevice(e->dev));
     pa_comm* c = e->comm;
-    unsigned long long* d_sizes = nullptr;
-    PA_HIP(e, hipMalloc((void**)&d_sizes, (size_t)(nranks + 1) * sizeof(unsigned long long)));
+    DevMem<unsigned long long> sizes_dev;          // (the stream is waited for below, before any return)
+    PA_HIP(e, sizes_dev.alloc((size_t)(nranks + 1) * sizeof(unsigned long long)));
+    unsigned long long* const d_sizes = sizes_dev.get();
     const unsigned long long mine = nbytes;
     hipError_t h = hipMemcpyAsync(d_sizes + nranks, &mine, sizeof(mine), hipMemcpyHostToDevice, e->main_stream());
     ncclResult_t r = ncclSuccess;
@@ -142,7 +143,6 @@ int pa_engine_gather_sizes(pa_engine* e, size_t nbytes, uint64_t* sizes) {
     std::vector<unsigned long long> hs((size_t)nranks);
     if (h == hipSuccess && r == ncclSuccess) h = hipMemcpyAsync(hs.data(), d_sizes, (size_t)nranks * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->main_stream());
     if (h == hipSuccess) h = hipStreamSynchronize(e->main_stream_wait_only());
-    hipFree(d_sizes);
     if (r != ncclSuccess) PA_FAIL(e, "ncclAllGather: %s", c->GetErrorString(r));
     if (h != hipSuccess) PA_FAIL(e, "pa_engine_gather_sizes: %s", hipGetErrorString(h));
     for (int k = 0; k < nranks; ++k) sizes[k] = hs[(size_t)k];
@@ -165,26 +165,25 @@ int pa_engine_gather(pa_engine* e, const void* send, size_t nbytes, void* recv, 
     }
     PA_HIP(e, hipSetDevice(e->dev));
     pa_comm* c = e->comm;
-    char* d_send = nullptr;
-    char* d_recv = nullptr;
+    DevMem<char> d_send, d_recv;          // (likewise)
     hipError_t h = hipSuccess;
     ncclResult_t r = ncclSuccess;
     if (me != root && nbytes) {
-        h = hipMalloc((void**)&d_send, nbytes);
-        if (h == hipSuccess) h = hipMemcpyAsync(d_send, send, nbytes, hipMemcpyHostToDevice, e->main_stream());
+        h = (hipError_t)d_send.alloc(nbytes);
+        if (h == hipSuccess) h = hipMemcpyAsync(d_send.get(), send, nbytes, hipMemcpyHostToDevice, e->main_stream());
     }
-    if (me == root && total) h = hipMalloc((void**)&d_recv, total);
+    if (me == root && total) h = (hipError_t)d_recv.alloc(total);
     // (an allocation failure still enters the group with nothing posted: the peers' sends then fail inside RCCL instead of hanging)
     r = c->GroupStart();
     if (h == hipSuccess && r == ncclSuccess) {
         if (me == root) {
             size_t off = 0;
             for (int k = 0; k < nranks && r == ncclSuccess; ++k) {
-                if (k != root && sizes[k]) r = c->Recv(d_recv + off, (size_t)sizes[k], ncclUint8, k, c->comm, e->main_stream());
+                if (k != root && sizes[k]) r = c->Recv(d_recv.get() + off, (size_t)sizes[k], ncclUint8, k, c->comm, e->main_stream());
                 off += (size_t)sizes[k];
             }
         } else if (nbytes) {
-            r = c->Send(d_send, nbytes, ncclUint8, root, c->comm, e->main_stream());
+            r = c->Send(d_send.get(), nbytes, ncclUint8, root, c->comm, e->main_stream());
         }
     }
     const ncclResult_t r2 = c->GroupEnd();
@@ -194,13 +193,11 @@ int pa_engine_gather(pa_engine* e, const void* send, size_t nbytes, void* recv, 
         for (int k = 0; k < nranks && h == hipSuccess; ++k) {
             const size_t nb = (size_t)sizes[k];
             if (k == root) { if (nb) memcpy((char*)recv + off, send, nb); }
-            else if (nb) h = hipMemcpyAsync((char*)recv + off, d_recv + off, nb, hipMemcpyDeviceToHost, e->main_stream());
+            else if (nb) h = hipMemcpyAsync((char*)recv + off, d_recv.get() + off, nb, hipMemcpyDeviceToHost, e->main_stream());
             off += nb;
         }
     }
     if (h == hipSuccess) h = hipStreamSynchronize(e->main_stream_wait_only());
-    if (d_send) hipFree(d_send);
-    if (d_recv) hipFree(d_recv);
     if (r != ncclSuccess) PA_FAIL(e, "ncclSend/Recv: %s", c->GetErrorString(r));
     if (h != hipSuccess) PA_FAIL(e, "pa_engine_gather: %s", hipGetErrorString(h));
     return 0;
@@ -211,14 +208,14 @@ int pa_engine_allreduce_max(pa_engine* e, double* value) {
     if (!e || !value) return 1;
     if (!e->comm) PA_FAIL(e, "pa_engine_allreduce_max: call pa_engine_comm_init first");
     PA_HIP(e, hipSetDevice(e->dev));
-    double* d = nullptr;
-    PA_HIP(e, hipMalloc((void**)&d, sizeof(double)));
+    DevMem<double> d_val;
+    PA_HIP(e, d_val.alloc(sizeof(double)));
+    double* const d = d_val.get();
     hipError_t h = hipMemcpyAsync(d, value, sizeof(double), hipMemcpyHostToDevice, e->main_stream());
     ncclResult_t r = ncclSuccess;
     if (h == hipSuccess) r = e->comm->AllReduce(d, d, 1, ncclDouble, ncclMax, e->comm->comm, e->main_stream());
     if (h == hipSuccess && r == ncclSuccess) h = hipMemcpyAsync(value, d, sizeof(double), hipMemcpyDeviceToHost, e->main_stream());
     if (h == hipSuccess) h = hipStreamSynchronize(e->main_stream_wait_only());
-    hipFree(d);
     if (r != ncclSuccess) PA_FAIL(e, "ncclAllReduce: %s", e->comm->GetErrorString(r));
     if (h != hipSuccess) PA_FAIL(e, "pa_engine_allreduce_max: %s", hipGetErrorString(h));
     return 0;

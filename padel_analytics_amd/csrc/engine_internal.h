@@ -8,11 +8,14 @@
 //   engine_jpeg.cpp      pa_jpeg_encode: YUV 4:2:0 frames in HBM -> baseline JPEGs in host memory (the refusals, tables and header: jpeg_check.cpp, host only)
 //   engine_jpeg_decode.cpp  pa_jpeg_decode: baseline JPEGs in host memory -> BGR frames in HBM (the markers: jpeg_parse.cpp, host only)
 //   engine_comm.cpp      RCCL
+//   device_mem.h         DevMem<T> / PinMem<T>: the owner of every device (page-locked host) allocation of these files; the
+//                        hooks it allocates through, and the count of live bytes, are engine.cpp's
 // What is decided about a graph on the host alone lives in graph_plan.cpp, which kernel runs a conv in conv_select.cpp.
 #pragma once
 #include "../../include/padel_hip.h"
 #include "graph_plan.h"
 #include "lane_plan.h"
+#include "device_mem.h"
 #include "kernels.h"
 
 #include <algorithm>
@@ -21,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -81,15 +85,15 @@ struct pa_engine {
     hipStream_t copy_stream = nullptr;   // uploads that must not queue behind compute (pa_upload)
     std::string err;
     bool profiling = false;
-    float* zeros = nullptr;   // 256 B of zeros: source of padded conv taps
+    DevMem<float> zeros;      // 256 B of zeros: source of padded conv taps
     Tuning t;
     int tuning_epoch = 0;     // bumped by pa_engine_set_tuning: captured graphs of an older epoch are discarded
     std::string timeline_path;
     pa_comm* comm = nullptr;  // RCCL communicator (pa_engine_comm_init), optional
-    uint8_t* yuv_stage = nullptr; size_t yuv_stage_cap = 0;   // pa_yuv420_to_bgr: raw YUV bytes of a host source, filled and read on the main stream only
+    DevMem<uint8_t> yuv_stage;   // pa_yuv420_to_bgr: raw YUV bytes of a host source, filled and read on the main stream only
     int yuv_last_path = 0;    // 1 vector, 2 byte: what the last pa_yuv420_to_bgr launched (pa_yuv_last_path)
     hipEvent_t timer_ev[2]{};  // pa_engine_timer_start / _stop, created on first use
-    uint8_t* render_stage = nullptr; size_t render_stage_cap = 0;   // pa_render: the resolved marks and first[] of the call in flight, filled and read on the main stream only
+    DevMem<uint8_t> render_stage;   // pa_render: the resolved marks and first[] of the call in flight, filled and read on the main stream only
     int render_last_path = 0; // 1 vector, 2 byte: what the last pa_render launched (pa_render_last_path)
     JpegScratch* jpeg = nullptr;   // pa_jpeg_encode: slots, tables and the gathered frames, grown on demand, used on the main stream only (engine_jpeg.cpp)
     JpegDecScratch* jpeg_dec = nullptr;   // pa_jpeg_decode: compressed bytes, tables, coefficients and planes, likewise (engine_jpeg_decode.cpp)
@@ -116,7 +120,7 @@ extern thread_local std::string g_err;      // errors of calls that have no engi
 
 #define PA_HIP(eng, call)                                                                  \
     do {                                                                                   \
-        hipError_t _e = (call);                                                            \
+        const hipError_t _e = static_cast<hipError_t>(call);   /* (a DevMem reports the runtime's code as int) */ \
         if (_e != hipSuccess) {                                                            \
             (void)hipGetLastError();   /* reported here: must not surface again at the next launch's hipGetLastError() */ \
             PA_FAIL(eng, "%s failed: %s (%s:%d)", #call, hipGetErrorString(_e), __FILE__, __LINE__); \
@@ -130,9 +134,9 @@ enum { PROF_PRE = 100, PROF_DECODE = 101, PROF_NMS = 102 };      // `kind` of th
 // the passes (engine_pre.cpp).  No table for an axis that already has the target size, d_tmp only when both axes change.
 struct ResamplePlan {
     int sh = 0, sw = 0, dh = 0, dw = 0;
-    int32_t *d_hb = nullptr, *d_hk = nullptr, *d_vb = nullptr, *d_vk = nullptr;
+    DevMem<int32_t> d_hb, d_hk, d_vb, d_vk;
     int hks = 0, vks = 0;
-    uint8_t* d_tmp = nullptr; size_t tmp_bytes = 0;   // the temporary between the passes and its size (a second lane allocates as much)
+    DevMem<uint8_t> d_tmp;   // the temporary between the passes (a second lane allocates as much)
 };
 
 // A lane: everything ONE in-flight YOLO batch writes on the device, so that two batches of a model can run at the same time on two
@@ -149,21 +153,27 @@ struct ResamplePlan {
 //   shared, sticky by design: d_ovf (kernels only ever set it; a ticket reads it back after its own kernels, so it sees its own
 //     overflow; a neighbour's can only make it report 1 early, which callers treat as "recompute").  d_frames is pa_yolo_infer's
 //     alone (host frames; a submit refuses them).
+// Freed by: the type.  Every member that owns device memory is a DevMem, so `L = Lane{}` (free_lane) and the model's destructor
+// release a lane whole; the graphs are destroyed by free_lane, the stream is the engine's.
 struct Lane {
     bool allocated = false;
     hipStream_t stream = nullptr;          // e->lane_stream[i] (YOLO models; not owned), nullptr: the model runs on the main stream
-    void* arena = nullptr;                 // what bptr points into
+    DevMem<char> arena;                    // what bptr points into
     std::vector<float*> bptr;
-    float* d_fc = nullptr;                 // graphs with a PA_OP_GAP_FC op: [max_batch][kGapFcMaxOut] logits, then as many probabilities (plan_buffers)
-    float* d_stage = nullptr; size_t stage_cap = 0;   // h2 generic graphs: fp32 input staged here before it is encoded
-    uint8_t* d_netin = nullptr;
+    DevMem<float> d_fc;                    // graphs with a PA_OP_GAP_FC op: [max_batch][kGapFcMaxOut] logits, then as many probabilities (plan_buffers)
+    DevMem<float> d_stage;                 // h2 generic graphs: fp32 input staged here before it is encoded
+    DevMem<uint8_t> d_netin;
     HeadLevel lv[3]{};
-    float* d_cand = nullptr; int32_t* d_cidx = nullptr; int32_t* d_ccnt = nullptr;
-    uint64_t* d_keys = nullptr; int32_t* d_order = nullptr; uint8_t* d_supp = nullptr;
-    float* d_oboxes = nullptr; float* d_okpts = nullptr; int32_t* d_ocnt = nullptr;
+    DevMem<float> d_cand; DevMem<int32_t> d_cidx, d_ccnt;
+    DevMem<uint64_t> d_keys; DevMem<int32_t> d_order; DevMem<uint8_t> d_supp;
+    DevMem<float> d_oboxes, d_okpts; DevMem<int32_t> d_ocnt;
     std::map<int, hipGraphExec_t> graphs;  // op-list replay per batch size (tuning "graph")
-    uint8_t* d_rs_tmp = nullptr;           // lane 1: its own temporary between the resample passes (lane 0 uses the plan's)
+    DevMem<uint8_t> d_rs_tmp;              // lane 1: its own temporary between the resample passes (lane 0 uses the plan's)
     LaneState st;                          // pick_lane's view
+    size_t device_bytes() const {          // what the lane holds on the device (pa_model::lane_bytes)
+        return arena.bytes() + d_fc.bytes() + d_stage.bytes() + d_netin.bytes() + d_cand.bytes() + d_cidx.bytes() + d_ccnt.bytes() + d_keys.bytes() +
+               d_order.bytes() + d_supp.bytes() + d_oboxes.bytes() + d_okpts.bytes() + d_ocnt.bytes() + d_rs_tmp.bytes();
+    }
 };
 
 struct pa_model {
@@ -176,14 +186,14 @@ struct pa_model {
     std::vector<char> stem_fuse;           // op i -> stem_fusable (the stem and the stride-2 3x3 behind it can run as one kernel)
     HeadTail tail;                         // the heads' last 1x1 convs, if the graph ends the way find_head_tail wants it
     std::vector<char> tail_op;             // op i is one of them
-    float* d_w = nullptr;
+    DevMem<float> d_w;
     size_t n_w = 0;
     // h2 models: the h planes of the two-product stride-1 3x3 convs once more in MFMA operand order (conv_patch_h2r.hip), built on
     // the device from d_w before the first replay and again after a weight broadcast (ensure_operand_copies)
-    char* d_wr = nullptr;
+    DevMem<char> d_wr;
     std::vector<long long> wr_off;         // op -> byte offset into d_wr, -1: no copy
     bool wr_valid = false;
-    unsigned* d_ovf = nullptr;             // h2 models: sticky "a value did not fit fp16" flag (pa_model_take_overflow)
+    DevMem<unsigned> d_ovf;                // h2 models: sticky "a value did not fit fp16" flag (pa_model_take_overflow)
     int fc_nout = 0;                       // outputs of that op (0: the graph has none)
     int max_batch = 64;
     Lane ln[kMaxLanes];                    // ln[0]: the plan's; ln[1]: lazily, YOLO models only
@@ -202,20 +212,20 @@ struct pa_model {
     bool ovf_cached = false;               // h_ovf is current: no kernel of this model has run since it was read
     // pa_yolo_submit / pa_yolo_wait: tickets in flight.  slot = ticket % PA_MAX_INFLIGHT; h_pin[slot]: the overflow flag as the
     // stream read it back after that ticket's kernels (page-locked: a pageable destination would make the copy block the host)
-    unsigned* h_pin = nullptr;
+    PinMem<unsigned> h_pin;
     hipEvent_t tk_ev[PA_MAX_INFLIGHT]{};
     bool tk_busy[PA_MAX_INFLIGHT]{};
     int tk_lane[PA_MAX_INFLIGHT]{};        // the lane a ticket in flight runs on
     int next_ticket = 0, n_inflight = 0;
     std::vector<int32_t> classes_host;     // what d_classes holds (set_classes: uploaded again only when the caller's list changes)
     int graph_epoch = -1;                  // engine tuning epoch the graphs were captured under
-    uint8_t* d_frames = nullptr; size_t frames_cap = 0;
-    int32_t *d_xtab = nullptr, *d_ytab = nullptr;                 // cv2 bilinear tables
+    DevMem<uint8_t> d_frames;
+    DevMem<int32_t> d_xtab, d_ytab;                               // cv2 bilinear tables
     ResamplePlan rs;                                              // PIL tables
     // post
     int A = 0, P2 = 0;
     YoloGeometry geom;                     // of the plan (a second lane is planned from it)
-    int32_t* d_classes = nullptr; int classes_cap = 0;
+    DevMem<int32_t> d_classes;
     int last_n = 0;
     int last_post_path = 0;                // pa_yolo_last_post_path: 0 decode_kernel on head maps, 1 the fused head tail
     bool heads_stale = false;              // the last call ran the fused head tail: the head maps are not there (pa_yolo_read_head computes them)
@@ -231,7 +241,7 @@ int finish_profile(pa_model* m, size_t n_rec);
 void free_plan(pa_model* m);                         // both lanes; the caller has synchronised the main stream, the lanes are drained here
 // the arena of one lane of a model whose net_h x net_w is set: allocation, memsets (on s), bptr, d_fc
 int plan_buffers(pa_model* m, Lane& L, int batch, hipStream_t s);
-void free_lane(Lane& L);                             // what plan_buffers and the YOLO plan gave a lane; drains nothing: the CALLER has waited for the lane's stream
+void free_lane(Lane& L);                             // the graphs, then `L = Lane{}` with the stream kept; drains nothing: the CALLER has waited for the lane's stream
 // run_ops on lane L and stream s, or (tuning "graph", not while profiling) the replay of its capture for this batch size
 int run_graph(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi);
 // The fused head tail applies to the next replay of a planned model: tuning fuse_head, an h2 model whose plan found the tail, a
@@ -241,19 +251,18 @@ void head_tail_convs(const pa_model* m, const Lane& L, HeadTailArgs& a);      //
 int run_tail_ops(pa_model* m, Lane& L, hipStream_t s, int n);   // the tail convs alone, from their inputs (still live): the head maps of the lane's last call
 
 // ---- engine_jpeg.cpp
-void jpeg_scratch_free(pa_engine* e);                 // waits for the stream first
+void jpeg_scratch_free(pa_engine* e);                 // waits for the stream first, then deletes the scratch
 
 // ---- engine_jpeg_decode.cpp
-void jpeg_dec_scratch_free(pa_engine* e);             // waits for the stream first
+void jpeg_dec_scratch_free(pa_engine* e);             // waits for the stream first, destroys the events, deletes the scratch
 
 // ---- engine_pre.cpp
-hipError_t upload_table(pa_engine* e, int32_t** dptr, const std::vector<int32_t>& v);
+hipError_t upload_table(pa_engine* e, DevMem<int32_t>& d, const std::vector<int32_t>& v);
 // grow d_frames to max_batch frames if need be and copy nb host frames into it (on the stream); *src then names the device copy
 int stage_frames(pa_model* m, const uint8_t** src, int nb, size_t frame_bytes, hipStream_t s);
 // tables + temporary for sh x sw -> dh x dw over at most max_batch frames; identity_pass: a source that already has the target
 // size still gets a 1-tap vertical table (the ball session: its pass also reorders channels into 3-byte pixels)
 int resample_plan(pa_engine* e, ResamplePlan* rs, int sh, int sw, int dh, int dw, int filter, int max_batch, bool identity_pass = false);
-void resample_free(ResamplePlan* rs);
 // the one or two passes (horizontal first) of n frames into dst with out_c (3 | 4) bytes per pixel; the last pass reverses channels.
 // tmp: the temporary between the passes in place of the plan's (a second lane's own, as large as the plan's)
 hipError_t resample_enqueue(const ResamplePlan& rs, const uint8_t* src, uint8_t* dst, int n, int out_c, int reverse, hipStream_t s, uint8_t* tmp = nullptr);

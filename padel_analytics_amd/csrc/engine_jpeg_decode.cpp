@@ -8,13 +8,13 @@
 
 // Scratch of the call in flight, grown on demand, freed with the engine; filled and read on the compute stream only.
 struct JpegDecScratch {
-    uint8_t* data = nullptr; size_t data_cap = 0;                // compressed bytes of a sub-batch
-    JpegDecFrame* frames = nullptr; size_t frames_cap = 0;       // bytes
-    JpegDecInterval* ivls = nullptr; size_t ivls_cap = 0;        // bytes
-    int32_t* status = nullptr; size_t status_cap = 0;            // bytes: per interval one status word, then one word of rounds
-    int32_t* order = nullptr; size_t order_cap = 0;              // bytes: the intervals of the serial kernel, then those of the split kernel
-    int16_t* coef = nullptr; size_t coef_cap = 0;                // bytes
-    uint8_t* planes = nullptr; size_t planes_cap = 0;
+    DevMem<uint8_t> data;                                        // compressed bytes of a sub-batch
+    DevMem<JpegDecFrame> frames;
+    DevMem<JpegDecInterval> ivls;
+    DevMem<int32_t> status;                                      // per interval one status word, then one word of rounds
+    DevMem<int32_t> order;                                       // the intervals of the serial kernel, then those of the split kernel
+    DevMem<int16_t> coef;
+    DevMem<uint8_t> planes;
     hipEvent_t ev[5]{};                                          // profiling: in front of the upload, of (a), (b), (c), behind (c)
     double ms[5]{};                                              // of the last call while profiling: parse (host clock), upload, (a), (b), (c)
 };
@@ -27,28 +27,9 @@ static const int kDecMaxSub = 64;
 void jpeg_dec_scratch_free(pa_engine* e) {
     if (!e->jpeg_dec) return;
     if (e->main_stream_wait_only()) hipStreamSynchronize(e->main_stream_wait_only());
-    JpegDecScratch* s = e->jpeg_dec;
-    if (s->data) hipFree(s->data);
-    if (s->frames) hipFree(s->frames);
-    if (s->ivls) hipFree(s->ivls);
-    if (s->status) hipFree(s->status);
-    if (s->order) hipFree(s->order);
-    if (s->coef) hipFree(s->coef);
-    if (s->planes) hipFree(s->planes);
-    for (hipEvent_t ev : s->ev) if (ev) hipEventDestroy(ev);
-    delete s;
+    for (hipEvent_t ev : e->jpeg_dec->ev) if (ev) hipEventDestroy(ev);
+    delete e->jpeg_dec;
     e->jpeg_dec = nullptr;
-}
-
-// *p holds at least `need` bytes afterwards; its contents are not kept (the stream is idle: the caller has synchronised)
-template <class T> static int fit(pa_engine* e, T** p, size_t* cap, size_t need) {
-    if (*cap >= need) return 0;
-    if (*p) hipFree(*p);
-    *p = nullptr; *cap = 0;
-    need += need / 4;
-    PA_HIP(e, hipMalloc((void**)p, need));
-    *cap = need;
-    return 0;
 }
 
 int pa_jpeg_decode(pa_engine* e, const uint8_t* jpegs, const int64_t* offsets, int n, int h, int w, uint8_t* dst, int32_t* status_host) {
@@ -136,32 +117,36 @@ int pa_jpeg_decode(pa_engine* e, const uint8_t* jpegs, const int64_t* offsets, i
         last_split[0] += n_split;
         last_split[3] += n_serial;
         const size_t need_s = 2 * ivls.size() * sizeof(int32_t), need_o = ivls.size() * sizeof(int32_t);
-        if (s->data_cap < bytes + 16 || s->frames_cap < need_f || s->ivls_cap < need_i || s->status_cap < need_s || s->order_cap < need_o ||
-            s->coef_cap < coef_frame * nf || s->planes_cap < planes_frame * nf) {
+        if (s->data.bytes() < bytes + 16 || s->frames.bytes() < need_f || s->ivls.bytes() < need_i || s->status.bytes() < need_s ||
+            s->order.bytes() < need_o || s->coef.bytes() < coef_frame * nf || s->planes.bytes() < planes_frame * nf) {
             PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));          // a decode still queued uses what is about to go
-            if (fit(e, &s->data, &s->data_cap, bytes + 16) || fit(e, &s->frames, &s->frames_cap, need_f) ||
-                fit(e, &s->ivls, &s->ivls_cap, need_i) || fit(e, &s->status, &s->status_cap, need_s) || fit(e, &s->order, &s->order_cap, need_o) ||
-                fit(e, &s->coef, &s->coef_cap, coef_frame * nf) || fit(e, &s->planes, &s->planes_cap, planes_frame * nf))
-                return 1;
+            const auto roomy = [](size_t need) { return need + need / 4; };       // what a buffer that has to grow is given
+            PA_HIP(e, s->data.fit(bytes + 16, roomy(bytes + 16)));
+            PA_HIP(e, s->frames.fit(need_f, roomy(need_f)));
+            PA_HIP(e, s->ivls.fit(need_i, roomy(need_i)));
+            PA_HIP(e, s->status.fit(need_s, roomy(need_s)));
+            PA_HIP(e, s->order.fit(need_o, roomy(need_o)));
+            PA_HIP(e, s->coef.fit(coef_frame * nf, roomy(coef_frame * nf)));
+            PA_HIP(e, s->planes.fit(planes_frame * nf, roomy(planes_frame * nf)));
         }
         // (pageable sources: the runtime has consumed them when hipMemcpyAsync returns; an earlier sub-batch's kernels are ahead in the stream)
         if (timed) PA_HIP(e, hipEventRecord(s->ev[0], e->main_stream()));
-        if (bytes) PA_HIP(e, hipMemcpyAsync(s->data, jpegs + base, bytes, hipMemcpyHostToDevice, e->main_stream()));
-        PA_HIP(e, hipMemcpyAsync(s->frames, frames.data(), need_f, hipMemcpyHostToDevice, e->main_stream()));
-        PA_HIP(e, hipMemcpyAsync(s->ivls, ivls.data(), need_i, hipMemcpyHostToDevice, e->main_stream()));
-        PA_HIP(e, hipMemcpyAsync(s->order, order.data(), need_o, hipMemcpyHostToDevice, e->main_stream()));
+        if (bytes) PA_HIP(e, hipMemcpyAsync(s->data.get(), jpegs + base, bytes, hipMemcpyHostToDevice, e->main_stream()));
+        PA_HIP(e, hipMemcpyAsync(s->frames.get(), frames.data(), need_f, hipMemcpyHostToDevice, e->main_stream()));
+        PA_HIP(e, hipMemcpyAsync(s->ivls.get(), ivls.data(), need_i, hipMemcpyHostToDevice, e->main_stream()));
+        PA_HIP(e, hipMemcpyAsync(s->order.get(), order.data(), need_o, hipMemcpyHostToDevice, e->main_stream()));
         JpegDecArgs a{};
-        a.data = s->data; a.ivls = s->ivls; a.frames = s->frames; a.coef = s->coef; a.ivl_status = s->status; a.planes = s->planes;
+        a.data = s->data.get(); a.ivls = s->ivls.get(); a.frames = s->frames.get(); a.coef = s->coef.get(); a.ivl_status = s->status.get(); a.planes = s->planes.get();
         a.dst = dst + (size_t)f0 * h * w * 3;
         a.n = nf; a.n_ivls = (int)ivls.size(); a.h = h; a.w = w; a.mcus_x = mcus_x; a.mcus_y = mcus_y;
-        a.order = s->order; a.n_serial = n_serial; a.n_split = n_split; a.sub_bytes = split_sub;
+        a.order = s->order.get(); a.n_serial = n_serial; a.n_split = n_split; a.sub_bytes = split_sub;
         a.split_threads = std::min(kSplitMaxThreads, (most_sub + 63) / 64 * 64);
         int path = 0;
         const hipError_t r = launch_jpeg_decode(a, &path, e->main_stream(), timed ? s->ev + 1 : nullptr);
         if (r != hipSuccess) PA_FAIL(e, "jpeg decode launch failed: %s", hipGetErrorString(r));
         e->jpeg_dec_last_path = path;
         ivl_status.resize(2 * ivls.size());
-        PA_HIP(e, hipMemcpyAsync(ivl_status.data(), s->status, need_s, hipMemcpyDeviceToHost, e->main_stream()));
+        PA_HIP(e, hipMemcpyAsync(ivl_status.data(), s->status.get(), need_s, hipMemcpyDeviceToHost, e->main_stream()));
         PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
         if (timed)
             for (int k = 0; k < 4; ++k) {

@@ -2,57 +2,44 @@
 // launches) and YUV 4:2:0 -> BGR.  The arithmetic of the tables is host-only code in graph_plan.cpp.
 #include "engine_internal.h"
 
-hipError_t upload_table(pa_engine* e, int32_t** dptr, const std::vector<int32_t>& v) {
-    hipError_t r = hipMalloc((void**)dptr, v.size() * sizeof(int32_t));
+hipError_t upload_table(pa_engine* e, DevMem<int32_t>& d, const std::vector<int32_t>& v) {
+    hipError_t r = (hipError_t)d.alloc(v.size() * sizeof(int32_t));
     if (r != hipSuccess) return r;
-    r = hipMemcpyAsync(*dptr, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->main_stream());
+    r = hipMemcpyAsync(d.get(), v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice, e->main_stream());
     if (r != hipSuccess) return r;
     return hipStreamSynchronize(e->main_stream_wait_only());
 }
 
 int stage_frames(pa_model* m, const uint8_t** src, int nb, size_t frame_bytes, hipStream_t s) {
     pa_engine* e = m->e;
-    if (m->frames_cap < (size_t)nb * frame_bytes) {
-        if (m->d_frames) hipFree(m->d_frames);
-        m->frames_cap = (size_t)m->max_batch * frame_bytes;
-        PA_HIP(e, hipMalloc((void**)&m->d_frames, m->frames_cap));
-    }
-    PA_HIP(e, hipMemcpyAsync(m->d_frames, *src, (size_t)nb * frame_bytes, hipMemcpyHostToDevice, s));
-    *src = m->d_frames;
+    PA_HIP(e, m->d_frames.fit((size_t)nb * frame_bytes, (size_t)m->max_batch * frame_bytes));
+    PA_HIP(e, hipMemcpyAsync(m->d_frames.get(), *src, (size_t)nb * frame_bytes, hipMemcpyHostToDevice, s));
+    *src = m->d_frames.get();
     return 0;
 }
 
 int resample_plan(pa_engine* e, ResamplePlan* rs, int sh, int sw, int dh, int dw, int filter, int max_batch, bool identity_pass) {
     rs->sh = sh; rs->sw = sw; rs->dh = dh; rs->dw = dw;
     std::vector<int32_t> b, k;
-    if (sw != dw) { rs->hks = pil_coeffs(sw, dw, b, k, filter); PA_HIP(e, upload_table(e, &rs->d_hb, b)); PA_HIP(e, upload_table(e, &rs->d_hk, k)); }
-    if (sh != dh) { rs->vks = pil_coeffs(sh, dh, b, k, filter); PA_HIP(e, upload_table(e, &rs->d_vb, b)); PA_HIP(e, upload_table(e, &rs->d_vk, k)); }
-    if (sw != dw && sh != dh) {
-        rs->tmp_bytes = (size_t)max_batch * sh * dw * 3;
-        PA_HIP(e, hipMalloc((void**)&rs->d_tmp, rs->tmp_bytes));
-    }
+    if (sw != dw) { rs->hks = pil_coeffs(sw, dw, b, k, filter); PA_HIP(e, upload_table(e, rs->d_hb, b)); PA_HIP(e, upload_table(e, rs->d_hk, k)); }
+    if (sh != dh) { rs->vks = pil_coeffs(sh, dh, b, k, filter); PA_HIP(e, upload_table(e, rs->d_vb, b)); PA_HIP(e, upload_table(e, rs->d_vk, k)); }
+    if (sw != dw && sh != dh) PA_HIP(e, rs->d_tmp.alloc((size_t)max_batch * sh * dw * 3));
     if (identity_pass && sh == dh && sw == dw) {
         // identity "resample": one tap of weight 1.0 (1 << 22) per output row
         rs->vks = 1;
         b.assign((size_t)dh * 2, 0);
         k.assign((size_t)dh, 1 << 22);
         for (int y = 0; y < dh; ++y) { b[2 * y] = y; b[2 * y + 1] = 1; }
-        PA_HIP(e, upload_table(e, &rs->d_vb, b)); PA_HIP(e, upload_table(e, &rs->d_vk, k));
+        PA_HIP(e, upload_table(e, rs->d_vb, b)); PA_HIP(e, upload_table(e, rs->d_vk, k));
     }
     return 0;
-}
-
-void resample_free(ResamplePlan* rs) {
-    void* ptrs[] = {rs->d_hb, rs->d_hk, rs->d_vb, rs->d_vk, rs->d_tmp};
-    for (void* p : ptrs) if (p) hipFree(p);
-    *rs = ResamplePlan{};
 }
 
 hipError_t resample_enqueue(const ResamplePlan& rs, const uint8_t* src, uint8_t* dst, int n, int out_c, int reverse, hipStream_t s, uint8_t* tmp) {
     // a source of the target size has no pass to run unless the plan built the 1-tap one (the ball session's): the YOLO and ResNet
     // paths copy such frames with the letterbox kernel and never get here; launching nothing would leave dst as it was
     if (rs.sw == rs.dw && rs.sh == rs.dh && !rs.d_vb) return hipErrorInvalidValue;
-    if (!tmp) tmp = rs.d_tmp;
+    if (!tmp) tmp = rs.d_tmp.get();
     const uint8_t* cur = src;
     int cw = rs.sw;
     hipError_t r = hipSuccess;
@@ -60,7 +47,7 @@ hipError_t resample_enqueue(const ResamplePlan& rs, const uint8_t* src, uint8_t*
         ResamplePassArgs a{};
         const bool last = (rs.sh == rs.dh);
         a.in = cur; a.out = last ? dst : tmp; a.B = n; a.in_h = rs.sh; a.in_w = rs.sw; a.in_c = 3;
-        a.out_h = rs.sh; a.out_w = rs.dw; a.out_c = last ? out_c : 3; a.vertical = 0; a.bounds = rs.d_hb; a.coefs = rs.d_hk;
+        a.out_h = rs.sh; a.out_w = rs.dw; a.out_c = last ? out_c : 3; a.vertical = 0; a.bounds = rs.d_hb.get(); a.coefs = rs.d_hk.get();
         a.ksize = rs.hks; a.reverse = last ? reverse : 0;
         r = launch_resample_pass(a, s);
         cur = tmp; cw = rs.dw;
@@ -70,7 +57,7 @@ hipError_t resample_enqueue(const ResamplePlan& rs, const uint8_t* src, uint8_t*
     if (r == hipSuccess && (rs.sh != rs.dh || (rs.sw == rs.dw && rs.d_vb))) {
         ResamplePassArgs a{};
         a.in = cur; a.out = dst; a.B = n; a.in_h = rs.sh; a.in_w = cw; a.in_c = 3;
-        a.out_h = rs.dh; a.out_w = cw; a.out_c = out_c; a.vertical = 1; a.bounds = rs.d_vb; a.coefs = rs.d_vk;
+        a.out_h = rs.dh; a.out_w = cw; a.out_c = out_c; a.vertical = 1; a.bounds = rs.d_vb.get(); a.coefs = rs.d_vk.get();
         a.ksize = rs.vks; a.reverse = reverse;
         r = launch_resample_pass(a, s);
     }
@@ -87,15 +74,12 @@ int pa_yuv420_to_bgr(pa_engine* e, const uint8_t* src, int src_on_device, int n,
     if (yuv_validate(n, h, w, d, &span, why)) PA_FAIL(e, "%s", why.c_str());
     PA_HIP(e, hipSetDevice(e->dev));
     if (!src_on_device) {
-        if (e->yuv_stage_cap < span) {
+        if (e->yuv_stage.bytes() < span) {
             PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));          // a conversion still queued reads the buffer about to go
-            if (e->yuv_stage) hipFree(e->yuv_stage);
-            e->yuv_stage = nullptr; e->yuv_stage_cap = 0;
-            PA_HIP(e, hipMalloc((void**)&e->yuv_stage, span));
-            e->yuv_stage_cap = span;
+            PA_HIP(e, e->yuv_stage.fit(span, span));
         }
-        PA_HIP(e, hipMemcpyAsync(e->yuv_stage, src, span, hipMemcpyHostToDevice, e->main_stream()));
-        src = e->yuv_stage;
+        PA_HIP(e, hipMemcpyAsync(e->yuv_stage.get(), src, span, hipMemcpyHostToDevice, e->main_stream()));
+        src = e->yuv_stage.get();
     }
     YuvArgs a{};
     a.src = src; a.dst = dst; a.n = n; a.h = h; a.w = w; a.nv12 = d->layout == PA_YUV_NV12;

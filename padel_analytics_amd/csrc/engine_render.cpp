@@ -27,18 +27,15 @@ int pa_render(pa_engine* e, const uint8_t* src, int n, int h, int w, const pa_ma
         hb[4 * k] = (int16_t)b.x0; hb[4 * k + 1] = (int16_t)b.y0; hb[4 * k + 2] = (int16_t)b.x1; hb[4 * k + 3] = (int16_t)b.y1;
     }
     memcpy(reinterpret_cast<char*>(host.data()) + first_off, first, (size_t)(n + 1) * sizeof(int32_t));
-    if (e->render_stage_cap < bytes) {
+    if (e->render_stage.bytes() < bytes) {
         PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));              // a render still queued reads the buffer about to go
-        if (e->render_stage) hipFree(e->render_stage);
-        e->render_stage = nullptr; e->render_stage_cap = 0;
-        const size_t cap = std::max(bytes * 2, (size_t)65536);
-        PA_HIP(e, hipMalloc((void**)&e->render_stage, cap));
-        e->render_stage_cap = cap;
+        PA_HIP(e, e->render_stage.fit(bytes, std::max(bytes * 2, (size_t)65536)));
     }
-    PA_HIP(e, hipMemcpyAsync(e->render_stage, host.data(), bytes, hipMemcpyHostToDevice, e->main_stream()));
+    uint8_t* const stage = e->render_stage.get();
+    PA_HIP(e, hipMemcpyAsync(stage, host.data(), bytes, hipMemcpyHostToDevice, e->main_stream()));
     RenderArgs a{};
-    a.src = src; a.dst = dst; a.marks = e->render_stage; a.boxes = e->render_stage + box_off;
-    a.first = reinterpret_cast<const int32_t*>(e->render_stage + first_off);
+    a.src = src; a.dst = dst; a.marks = stage; a.boxes = stage + box_off;
+    a.first = reinterpret_cast<const int32_t*>(stage + first_off);
     a.n = n; a.h = h; a.w = w; a.in_place = same ? 1 : 0;
     if (out == PA_RENDER_YUV420) {
         a.out = geom->layout == PA_YUV_NV12 ? 1 : 2;

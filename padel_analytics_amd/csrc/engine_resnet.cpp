@@ -13,7 +13,7 @@ static int plan_resnet(pa_model* m, int h0, int w0) {
     m->net_h = m->net_w = S;
     m->rw = m->rh = S; m->top = m->left = 0; m->lb_mode = 0;
     if (resample_plan(e, &m->rs, h0, w0, S, S, PIL_BILINEAR, m->max_batch)) return 1;
-    PA_HIP(e, hipMalloc((void**)&m->ln[0].d_netin, (size_t)m->max_batch * S * S * 4));
+    PA_HIP(e, m->ln[0].d_netin.alloc((size_t)m->max_batch * S * S * 4));
     if (plan_buffers(m, m->ln[0], m->max_batch, e->main_stream())) return 1;
     PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     m->p_h0 = h0; m->p_w0 = w0; m->p_imgsz = S; m->p_pre = PA_PRE_PIL_STRETCH; m->p_auto = 0;
@@ -45,18 +45,18 @@ int pa_resnet_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, int
         hipError_t r = hipSuccess;
         if (h == S && w == S) {
             LetterboxArgs a{};
-            a.src = src; a.dst = m->ln[0].d_netin; a.B = nb; a.h0 = h; a.w0 = w; a.rw = S; a.rh = S; a.nh = S; a.nw = S; a.mode = 0; a.reverse = 1;
+            a.src = src; a.dst = m->ln[0].d_netin.get(); a.B = nb; a.h0 = h; a.w0 = w; a.rw = S; a.rh = S; a.nh = S; a.nw = S; a.mode = 0; a.reverse = 1;
             r = launch_letterbox(a, s);
         } else {
-            r = resample_enqueue(m->rs, src, m->ln[0].d_netin, nb, 4, 1, s);
+            r = resample_enqueue(m->rs, src, m->ln[0].d_netin.get(), nb, 4, 1, s);
         }
         prof_end(s, pr);
         if (r != hipSuccess) PA_FAIL(e, "preprocess launch failed: %s", hipGetErrorString(r));
         if (run_graph(m, m->ln[0], s, nb, &pi)) return 1;
         if (m->fc_nout) {
             const size_t row = (size_t)m->fc_nout * sizeof(float);
-            PA_HIP(e, hipMemcpyAsync(out_xy + (size_t)c0 * m->fc_nout, m->ln[0].d_fc + (size_t)m->p_batch * kGapFcMaxOut, nb * row, hipMemcpyDeviceToHost, s));
-            if (out_logits) PA_HIP(e, hipMemcpyAsync(out_logits + (size_t)c0 * m->fc_nout, m->ln[0].d_fc, nb * row, hipMemcpyDeviceToHost, s));
+            PA_HIP(e, hipMemcpyAsync(out_xy + (size_t)c0 * m->fc_nout, m->ln[0].d_fc.get() + (size_t)m->p_batch * kGapFcMaxOut, nb * row, hipMemcpyDeviceToHost, s));
+            if (out_logits) PA_HIP(e, hipMemcpyAsync(out_logits + (size_t)c0 * m->fc_nout, m->ln[0].d_fc.get(), nb * row, hipMemcpyDeviceToHost, s));
         }
         PA_HIP(e, hipStreamSynchronize(s));
         m->last_n = nb;
@@ -68,9 +68,9 @@ int pa_resnet_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, int
 int pa_resnet_read_netin(pa_model* m, int n, uint8_t* out) {
     if (!m) return 1;
     pa_engine* e = m->e;
-    if (m->d.task != PA_TASK_RESNET || !m->planned || !m->ln[0].d_netin || n < 1 || n > m->last_n || !out) PA_FAIL(e, "pa_resnet_read_netin: no plan / bad n");
+    if (m->d.task != PA_TASK_RESNET || !m->planned || !m->ln[0].d_netin.get() || n < 1 || n > m->last_n || !out) PA_FAIL(e, "pa_resnet_read_netin: no plan / bad n");
     PA_HIP(e, hipSetDevice(e->dev));
-    PA_HIP(e, hipMemcpyAsync(out, m->ln[0].d_netin, (size_t)n * RESNET_S * RESNET_S * 4, hipMemcpyDeviceToHost, e->main_stream()));
+    PA_HIP(e, hipMemcpyAsync(out, m->ln[0].d_netin.get(), (size_t)n * RESNET_S * RESNET_S * 4, hipMemcpyDeviceToHost, e->main_stream()));
     PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     return 0;
 }
@@ -78,11 +78,11 @@ int pa_resnet_read_netin(pa_model* m, int n, uint8_t* out) {
 int pa_resnet_read_fc(pa_model* m, int n, float* out_xy, float* out_logits) {
     if (!m) return 1;
     pa_engine* e = m->e;
-    if (!m->planned || !m->fc_nout || !m->ln[0].d_fc || n < 1 || n > m->p_batch) PA_FAIL(e, "pa_resnet_read_fc: no plan with a pooled linear head / bad n");
+    if (!m->planned || !m->fc_nout || !m->ln[0].d_fc.get() || n < 1 || n > m->p_batch) PA_FAIL(e, "pa_resnet_read_fc: no plan with a pooled linear head / bad n");
     PA_HIP(e, hipSetDevice(e->dev));
     const size_t bytes = (size_t)n * m->fc_nout * sizeof(float);
-    if (out_xy) PA_HIP(e, hipMemcpyAsync(out_xy, m->ln[0].d_fc + (size_t)m->p_batch * kGapFcMaxOut, bytes, hipMemcpyDeviceToHost, e->main_stream()));
-    if (out_logits) PA_HIP(e, hipMemcpyAsync(out_logits, m->ln[0].d_fc, bytes, hipMemcpyDeviceToHost, e->main_stream()));
+    if (out_xy) PA_HIP(e, hipMemcpyAsync(out_xy, m->ln[0].d_fc.get() + (size_t)m->p_batch * kGapFcMaxOut, bytes, hipMemcpyDeviceToHost, e->main_stream()));
+    if (out_logits) PA_HIP(e, hipMemcpyAsync(out_logits, m->ln[0].d_fc.get(), bytes, hipMemcpyDeviceToHost, e->main_stream()));
     PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     return 0;
 }

@@ -36,15 +36,11 @@ int pa_tracknet_infer(pa_model* m, const float* x, int n, int h, int w, int x_on
         if (h2) {
             const float* src = reinterpret_cast<const float*>(xs);
             if (!x_on_device) {
-                if (m->ln[0].stage_cap < in_bytes) {
-                    if (m->ln[0].d_stage) hipFree(m->ln[0].d_stage);
-                    m->ln[0].stage_cap = (size_t)m->max_batch * h * w * cin * 4;
-                    PA_HIP(e, hipMalloc((void**)&m->ln[0].d_stage, m->ln[0].stage_cap));
-                }
-                PA_HIP(e, hipMemcpyAsync(m->ln[0].d_stage, xs, in_bytes, hipMemcpyHostToDevice, s));
-                src = m->ln[0].d_stage;
+                PA_HIP(e, m->ln[0].d_stage.fit(in_bytes, (size_t)m->max_batch * h * w * cin * 4));
+                PA_HIP(e, hipMemcpyAsync(m->ln[0].d_stage.get(), xs, in_bytes, hipMemcpyHostToDevice, s));
+                src = m->ln[0].d_stage.get();
             }
-            const hipError_t er = launch_h2_encode(src, m->ln[0].bptr[0], (long long)(in_bytes / 4), m->d_ovf, s);
+            const hipError_t er = launch_h2_encode(src, m->ln[0].bptr[0], (long long)(in_bytes / 4), m->d_ovf.get(), s);
             if (er != hipSuccess) PA_FAIL(e, "h2 encode launch failed: %s", hipGetErrorString(er));
         } else
         PA_HIP(e, hipMemcpyAsync(m->ln[0].bptr[0], xs, in_bytes,
@@ -68,13 +64,12 @@ struct pa_ball {
     int ring = 0;                // resized-frame ring slots (B + 7)
     long long fed = 0;           // frames fed since the last set_background
     bool have_bg = false;
-    uint8_t *d_src = nullptr, *d_small = nullptr, *d_med_src = nullptr, *d_med = nullptr;
-    uint8_t* d_mask = nullptr; float* d_heat = nullptr;
-    float* d_Y = nullptr;        // [7 + B + 7][288][512][cs] window outputs (7 carry rows first)
-    float* d_lut = nullptr;
+    DevMem<uint8_t> d_src, d_small, d_med_src, d_med, d_mask; DevMem<float> d_heat;
+    DevMem<float> d_Y;           // [7 + B + 7][288][512][cs] window outputs (7 carry rows first)
+    DevMem<float> d_lut;
     ResamplePlan rs;             // Pillow bicubic, source size -> 288 x 512
-    int32_t *d_row0 = nullptr, *d_mode = nullptr; float* d_div = nullptr;
-    int32_t *d_label = nullptr, *d_bbox = nullptr, *d_rect = nullptr;
+    DevMem<int32_t> d_row0, d_mode; DevMem<float> d_div;
+    DevMem<int32_t> d_label, d_bbox, d_rect;
     int cs = 0;
 };
 
@@ -91,32 +86,31 @@ int pa_ball_create(pa_model* m, int src_h, int src_w, pa_ball** out) {
     if (src_h <= 0 || src_w <= 0) PA_FAIL(e, "pa_ball_create: unsupported source size %dx%d", src_w, src_h);
     if (m->bufs[m->d.head_buf[0]].channels < 8)
         PA_FAIL(e, "pa_ball_create: TrackNet output has %d channels (< 8)", m->bufs[m->d.head_buf[0]].channels);
-    pa_ball* b = new pa_ball();
+    std::unique_ptr<pa_ball, void (*)(pa_ball*)> owner(new pa_ball(), pa_ball_destroy);      // a failure below: wait, then release
+    pa_ball* b = owner.get();
     b->m = m; b->h = src_h; b->w = src_w; b->B = m->max_batch; b->ring = b->B + 7;
     b->cs = m->bufs[m->d.head_buf[0]].channels;
     const size_t HW = (size_t)BALL_H * BALL_W;
-    struct Guard { pa_ball* b; bool ok = false; ~Guard() { if (!ok) pa_ball_destroy(b); } } guard{b};
-    PA_HIP(e, hipMalloc((void**)&b->d_src, (size_t)b->B * src_h * src_w * 3));
-    PA_HIP(e, hipMalloc((void**)&b->d_small, (size_t)b->ring * HW * 3));
-    PA_HIP(e, hipMalloc((void**)&b->d_med_src, (size_t)src_h * src_w * 3));
-    PA_HIP(e, hipMalloc((void**)&b->d_med, HW * 3));
-    PA_HIP(e, hipMalloc((void**)&b->d_mask, (size_t)(b->B + 7) * HW));
-    PA_HIP(e, hipMalloc((void**)&b->d_heat, (size_t)(b->B + 7) * HW * sizeof(float)));
-    PA_HIP(e, hipMalloc((void**)&b->d_Y, (size_t)(b->B + 14) * HW * b->cs * sizeof(float)));
-    PA_HIP(e, hipMalloc((void**)&b->d_row0, (b->B + 7) * sizeof(int32_t)));
-    PA_HIP(e, hipMalloc((void**)&b->d_mode, (b->B + 7) * sizeof(int32_t)));
-    PA_HIP(e, hipMalloc((void**)&b->d_div, (b->B + 7) * sizeof(float)));
-    PA_HIP(e, hipMalloc((void**)&b->d_label, (size_t)(b->B + 7) * HW * sizeof(int32_t)));
-    PA_HIP(e, hipMalloc((void**)&b->d_bbox, (size_t)(b->B + 7) * 4 * HW * sizeof(int32_t)));
-    PA_HIP(e, hipMalloc((void**)&b->d_rect, (size_t)(b->B + 7) * 4 * sizeof(int32_t)));
+    PA_HIP(e, b->d_src.alloc((size_t)b->B * src_h * src_w * 3));
+    PA_HIP(e, b->d_small.alloc((size_t)b->ring * HW * 3));
+    PA_HIP(e, b->d_med_src.alloc((size_t)src_h * src_w * 3));
+    PA_HIP(e, b->d_med.alloc(HW * 3));
+    PA_HIP(e, b->d_mask.alloc((size_t)(b->B + 7) * HW));
+    PA_HIP(e, b->d_heat.alloc((size_t)(b->B + 7) * HW * sizeof(float)));
+    PA_HIP(e, b->d_Y.alloc((size_t)(b->B + 14) * HW * b->cs * sizeof(float)));
+    PA_HIP(e, b->d_row0.alloc((b->B + 7) * sizeof(int32_t)));
+    PA_HIP(e, b->d_mode.alloc((b->B + 7) * sizeof(int32_t)));
+    PA_HIP(e, b->d_div.alloc((b->B + 7) * sizeof(float)));
+    PA_HIP(e, b->d_label.alloc((size_t)(b->B + 7) * HW * sizeof(int32_t)));
+    PA_HIP(e, b->d_bbox.alloc((size_t)(b->B + 7) * 4 * HW * sizeof(int32_t)));
+    PA_HIP(e, b->d_rect.alloc((size_t)(b->B + 7) * 4 * sizeof(int32_t)));
     std::vector<float> lut(256);
     for (int i = 0; i < 256; ++i) lut[i] = (float)((double)i / 255.0);     // float64 division, then .float()
-    PA_HIP(e, hipMalloc((void**)&b->d_lut, 256 * sizeof(float)));
-    PA_HIP(e, hipMemcpyAsync(b->d_lut, lut.data(), 256 * sizeof(float), hipMemcpyHostToDevice, e->main_stream()));
+    PA_HIP(e, b->d_lut.alloc(256 * sizeof(float)));
+    PA_HIP(e, hipMemcpyAsync(b->d_lut.get(), lut.data(), 256 * sizeof(float), hipMemcpyHostToDevice, e->main_stream()));
     PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     if (resample_plan(e, &b->rs, src_h, src_w, BALL_H, BALL_W, PIL_BICUBIC, b->B, true)) return 1;
-    guard.ok = true;
-    *out = b;
+    *out = owner.release();
     return 0;
 }
 
@@ -124,9 +118,6 @@ void pa_ball_destroy(pa_ball* b) {
     if (!b) return;
     hipSetDevice(b->m->e->dev);
     hipStreamSynchronize(b->m->e->main_stream_wait_only());
-    resample_free(&b->rs);
-    void* ptrs[] = {b->d_src, b->d_small, b->d_med_src, b->d_med, b->d_mask, b->d_heat, b->d_Y, b->d_lut, b->d_row0, b->d_mode, b->d_div, b->d_label, b->d_bbox, b->d_rect};
-    for (void* p : ptrs) if (p) hipFree(p);
     delete b;
 }
 
@@ -144,14 +135,14 @@ int pa_ball_set_background(pa_ball* b, const uint8_t* median_rgb) {
     if (!b || !median_rgb) return 1;
     pa_engine* e = b->m->e;
     PA_HIP(e, hipSetDevice(e->dev));
-    PA_HIP(e, hipMemcpyAsync(b->d_med_src, median_rgb, (size_t)b->h * b->w * 3, hipMemcpyHostToDevice, e->main_stream()));
+    PA_HIP(e, hipMemcpyAsync(b->d_med_src.get(), median_rgb, (size_t)b->h * b->w * 3, hipMemcpyHostToDevice, e->main_stream()));
     return ball_finish_background(b);
 }
 
 static int ball_finish_background(pa_ball* b) {
     pa_engine* e = b->m->e;
-    if (ball_resize(b, b->d_med_src, 1, b->d_med, 0)) return 1;
-    PA_HIP(e, hipMemsetAsync(b->d_Y, 0, (size_t)(b->B + 14) * BALL_H * BALL_W * b->cs * sizeof(float), e->main_stream()));
+    if (ball_resize(b, b->d_med_src.get(), 1, b->d_med.get(), 0)) return 1;
+    PA_HIP(e, hipMemsetAsync(b->d_Y.get(), 0, (size_t)(b->B + 14) * BALL_H * BALL_W * b->cs * sizeof(float), e->main_stream()));
     PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     b->fed = 0;
     b->have_bg = true;
@@ -166,17 +157,17 @@ int pa_ball_background_from_frames(pa_ball* b, const uint8_t* frames_bgr, int n,
     hipStream_t s = e->main_stream();
     const long long fb = (long long)b->h * b->w * 3;
     const uint8_t* src = frames_bgr;
-    uint8_t* tmp = nullptr;
+    DevMem<uint8_t> tmp;         // host frames: their copy on the device, for this call
     if (!on_device) {
-        PA_HIP(e, hipMalloc((void**)&tmp, (size_t)n * fb));
-        hipError_t r = hipMemcpyAsync(tmp, frames_bgr, (size_t)n * fb, hipMemcpyHostToDevice, s);
-        if (r != hipSuccess) { hipFree(tmp); PA_FAIL(e, "median upload: %s", hipGetErrorString(r)); }
-        src = tmp;
+        PA_HIP(e, tmp.alloc((size_t)n * fb));
+        hipError_t r = hipMemcpyAsync(tmp.get(), frames_bgr, (size_t)n * fb, hipMemcpyHostToDevice, s);
+        if (r != hipSuccess) PA_FAIL(e, "median upload: %s", hipGetErrorString(r));
+        src = tmp.get();
     }
-    hipError_t r = launch_median(src, n, fb, b->d_med_src, s);
-    if (r == hipSuccess && out_median_rgb) r = hipMemcpyAsync(out_median_rgb, b->d_med_src, (size_t)fb, hipMemcpyDeviceToHost, s);
+    hipError_t r = launch_median(src, n, fb, b->d_med_src.get(), s);
+    if (r == hipSuccess && out_median_rgb) r = hipMemcpyAsync(out_median_rgb, b->d_med_src.get(), (size_t)fb, hipMemcpyDeviceToHost, s);
     if (r == hipSuccess) r = hipStreamSynchronize(s);
-    if (tmp) hipFree(tmp);
+    tmp.reset();
     if (r != hipSuccess) PA_FAIL(e, "median kernel: %s", hipGetErrorString(r));
     return ball_finish_background(b);
 }
@@ -205,26 +196,26 @@ int pa_ball_feed(pa_ball* b, const uint8_t* frames, int n, int on_device, int fl
         // 1. resize the new frames (BGR -> RGB) into the ring; a feed never wraps more than once
         const uint8_t* src = frames;
         if (!on_device) {
-            PA_HIP(e, hipMemcpyAsync(b->d_src, frames, (size_t)n * b->h * b->w * 3, hipMemcpyHostToDevice, s));
-            src = b->d_src;
+            PA_HIP(e, hipMemcpyAsync(b->d_src.get(), frames, (size_t)n * b->h * b->w * 3, hipMemcpyHostToDevice, s));
+            src = b->d_src.get();
         }
         const int slot0 = (int)(b->fed % b->ring);
         const int first = std::min(n, b->ring - slot0);
-        if (ball_resize(b, src, first, b->d_small + (size_t)slot0 * HW * 3, 1)) return 1;
-        if (first < n && ball_resize(b, src + (size_t)first * b->h * b->w * 3, n - first, b->d_small, 1)) return 1;
+        if (ball_resize(b, src, first, b->d_small.get() + (size_t)slot0 * HW * 3, 1)) return 1;
+        if (first < n && ball_resize(b, src + (size_t)first * b->h * b->w * 3, n - first, b->d_small.get(), 1)) return 1;
         const long long f_old = b->fed, f_new = b->fed + n;
         // 2. new complete windows g in [g_lo, g_hi]
         const long long g_lo = std::max(0ll, f_old - 7), g_hi = f_new - 8;
         nw = g_hi >= g_lo ? (int)(g_hi - g_lo + 1) : 0;
         if (nw > 0) {
             BallAssembleArgs aa{};
-            aa.median = b->d_med; aa.frames = b->d_small; aa.lut = b->d_lut; aa.out = m->ln[0].bptr[0];
+            aa.median = b->d_med.get(); aa.frames = b->d_small.get(); aa.lut = b->d_lut.get(); aa.out = m->ln[0].bptr[0];
             aa.B = nw; aa.H = BALL_H; aa.W = BALL_W; aa.ring = b->ring; aa.first_slot = (int)(g_lo % b->ring);
             aa.out_f16 = m->d.dtype == PA_DTYPE_F16 ? 1 : m->d.dtype == PA_DTYPE_H2 ? 2 : 0;
             hipError_t r = launch_ball_assemble(aa, s);
             if (r != hipSuccess) PA_FAIL(e, "ball assemble launch failed: %s", hipGetErrorString(r));
             if (run_graph(m, m->ln[0], s, nw, &prof_n)) return 1;
-            PA_HIP(e, hipMemcpyAsync(b->d_Y + (size_t)7 * HW * b->cs, m->ln[0].bptr[m->d.head_buf[0]],
+            PA_HIP(e, hipMemcpyAsync(b->d_Y.get() + (size_t)7 * HW * b->cs, m->ln[0].bptr[m->d.head_buf[0]],
                                      (size_t)nw * HW * b->cs * sizeof(float), hipMemcpyDeviceToDevice, s));
             for (int i = 0; i < nw; ++i) {             // frame g = g_lo + i: rows i .. i+7 (row r <-> window g_lo - 7 + r)
                 const long long g = g_lo + i;
@@ -237,7 +228,7 @@ int pa_ball_feed(pa_ball* b, const uint8_t* frames, int n, int on_device, int fl
     }
     if (flush && b->fed >= 8) {
         // tail: rows after the last window are zero (ball_tracker.py:486-509)
-        PA_HIP(e, hipMemsetAsync(b->d_Y + (size_t)(7 + nw) * HW * b->cs, 0, (size_t)7 * HW * b->cs * sizeof(float), s));
+        PA_HIP(e, hipMemsetAsync(b->d_Y.get() + (size_t)(7 + nw) * HW * b->cs, 0, (size_t)7 * HW * b->cs * sizeof(float), s));
         for (int fi = 1; fi < 8; ++fi) {
             row0.push_back(nw - 1 + fi);               // window index of the last sample is row (nw - 1) + 7
             mode.push_back(1);
@@ -246,31 +237,31 @@ int pa_ball_feed(pa_ball* b, const uint8_t* frames, int n, int on_device, int fl
     }
     nout = (int)row0.size();
     if (nout > 0) {
-        PA_HIP(e, hipMemcpyAsync(b->d_row0, row0.data(), nout * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        PA_HIP(e, hipMemcpyAsync(b->d_mode, mode.data(), nout * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        PA_HIP(e, hipMemcpyAsync(b->d_div, div.data(), nout * sizeof(float), hipMemcpyHostToDevice, s));
+        PA_HIP(e, hipMemcpyAsync(b->d_row0.get(), row0.data(), nout * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        PA_HIP(e, hipMemcpyAsync(b->d_mode.get(), mode.data(), nout * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        PA_HIP(e, hipMemcpyAsync(b->d_div.get(), div.data(), nout * sizeof(float), hipMemcpyHostToDevice, s));
         BallEnsembleArgs ea{};
-        ea.Y = b->d_Y; ea.cs = b->cs; ea.H = BALL_H; ea.W = BALL_W; ea.row0 = b->d_row0; ea.mode = b->d_mode; ea.div = b->d_div;
+        ea.Y = b->d_Y.get(); ea.cs = b->cs; ea.H = BALL_H; ea.W = BALL_W; ea.row0 = b->d_row0.get(); ea.mode = b->d_mode.get(); ea.div = b->d_div.get();
         static const float w8[8] = {1.f, 2.f, 3.f, 4.f, 4.f, 3.f, 2.f, 1.f};
         for (int k = 0; k < 8; ++k) ea.w[k] = w8[k] / 20.0f;
-        ea.threshold = 0.5f; ea.heat = out_heat ? b->d_heat : nullptr; ea.mask = b->d_mask;
+        ea.threshold = 0.5f; ea.heat = out_heat ? b->d_heat.get() : nullptr; ea.mask = b->d_mask.get();
         hipError_t r = launch_ball_ensemble(ea, nout, s);
         if (r != hipSuccess) PA_FAIL(e, "ball ensemble launch failed: %s", hipGetErrorString(r));
         if (out_rects) {
             BallLocateArgs la{};
-            la.mask = b->d_mask; la.label = b->d_label; la.bbox = b->d_bbox; la.rect = b->d_rect; la.H = BALL_H; la.W = BALL_W;
+            la.mask = b->d_mask.get(); la.label = b->d_label.get(); la.bbox = b->d_bbox.get(); la.rect = b->d_rect.get(); la.H = BALL_H; la.W = BALL_W;
             r = launch_ball_locate(la, nout, s);
             if (r != hipSuccess) PA_FAIL(e, "ball locate launch failed: %s", hipGetErrorString(r));
-            PA_HIP(e, hipMemcpyAsync(out_rects, b->d_rect, (size_t)nout * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            PA_HIP(e, hipMemcpyAsync(out_rects, b->d_rect.get(), (size_t)nout * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         }
-        if (out_masks) PA_HIP(e, hipMemcpyAsync(out_masks, b->d_mask, (size_t)nout * HW, hipMemcpyDeviceToHost, s));
-        if (out_heat) PA_HIP(e, hipMemcpyAsync(out_heat, b->d_heat, (size_t)nout * HW * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (out_masks) PA_HIP(e, hipMemcpyAsync(out_masks, b->d_mask.get(), (size_t)nout * HW, hipMemcpyDeviceToHost, s));
+        if (out_heat) PA_HIP(e, hipMemcpyAsync(out_heat, b->d_heat.get(), (size_t)nout * HW * sizeof(float), hipMemcpyDeviceToHost, s));
     }
     // 3. carry the last 7 window rows to the front for the next feed: rows [nw, nw+7) -> [0, 7).  The ranges
     // overlap when nw < 7; copying row by row in ascending order is safe because dst row < src row.
     if (nw > 0) {
         for (int r7 = 0; r7 < 7; ++r7)
-            PA_HIP(e, hipMemcpyAsync(b->d_Y + (size_t)r7 * HW * b->cs, b->d_Y + (size_t)(nw + r7) * HW * b->cs,
+            PA_HIP(e, hipMemcpyAsync(b->d_Y.get() + (size_t)r7 * HW * b->cs, b->d_Y.get() + (size_t)(nw + r7) * HW * b->cs,
                                      HW * b->cs * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     PA_HIP(e, hipStreamSynchronize(s));
@@ -287,7 +278,7 @@ int pa_ball_read_resized(pa_ball* b, long long frame, uint8_t* out) {
         PA_FAIL(e, "pa_ball_read_resized: frame %lld is not among the last %d of %lld fed", frame, b->ring, b->fed);
     PA_HIP(e, hipSetDevice(e->dev));
     const size_t bytes = (size_t)BALL_H * BALL_W * 3;
-    const uint8_t* src = frame < 0 ? b->d_med : b->d_small + (size_t)(frame % b->ring) * bytes;
+    const uint8_t* src = frame < 0 ? b->d_med.get() : b->d_small.get() + (size_t)(frame % b->ring) * bytes;
     PA_HIP(e, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, e->main_stream()));
     PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
     return 0;
@@ -300,12 +291,12 @@ int pa_ball_locate(pa_ball* b, const uint8_t* masks, int n, int32_t* out_rects) 
     PA_HIP(e, hipSetDevice(e->dev));
     hipStream_t s = e->main_stream();
     const size_t HW = (size_t)BALL_H * BALL_W;
-    PA_HIP(e, hipMemcpyAsync(b->d_mask, masks, (size_t)n * HW, hipMemcpyHostToDevice, s));
+    PA_HIP(e, hipMemcpyAsync(b->d_mask.get(), masks, (size_t)n * HW, hipMemcpyHostToDevice, s));
     BallLocateArgs la{};
-    la.mask = b->d_mask; la.label = b->d_label; la.bbox = b->d_bbox; la.rect = b->d_rect; la.H = BALL_H; la.W = BALL_W;
+    la.mask = b->d_mask.get(); la.label = b->d_label.get(); la.bbox = b->d_bbox.get(); la.rect = b->d_rect.get(); la.H = BALL_H; la.W = BALL_W;
     hipError_t r = launch_ball_locate(la, n, s);
     if (r != hipSuccess) PA_FAIL(e, "ball locate launch failed: %s", hipGetErrorString(r));
-    PA_HIP(e, hipMemcpyAsync(out_rects, b->d_rect, (size_t)n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    PA_HIP(e, hipMemcpyAsync(out_rects, b->d_rect.get(), (size_t)n * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     PA_HIP(e, hipStreamSynchronize(s));
     return 0;
 }

@@ -4,30 +4,25 @@
 
 // What one lane of a YOLO plan owns (struct Lane): network input, activation arena, head-level pointers, post-processing buffers
 // and, on a second lane of a two-pass Pillow plan, its own temporary between the passes.  The memsets go onto the lane's stream.
-// Notes the bytes of one lane in m->lane_bytes.
+// Notes the bytes of one lane in m->lane_bytes: what the lane holds, and the plan's temporary where lane 0 borrows it.
 static int plan_lane(pa_model* m, Lane& L, const YoloGeometry& g, bool own_tmp) {
     pa_engine* e = m->e;
     const size_t B = (size_t)m->max_batch;
     const size_t A = (size_t)g.A;
-    size_t total = 0;
-    auto dmalloc = [&](void** p, size_t bytes) { total += bytes; return hipMalloc(p, bytes); };
-    PA_HIP(e, dmalloc((void**)&L.d_netin, B * m->net_h * m->net_w * 4));
+    PA_HIP(e, L.d_netin.alloc(B * m->net_h * m->net_w * 4));
     if (plan_buffers(m, L, (int)B, L.stream)) return 1;
-    total += m->arena_bytes + kConvReadSlack;
     for (int l = 0; l < 3; ++l) L.lv[l] = HeadLevel{L.bptr[m->d.head_buf[l]], g.lv[l].H, g.lv[l].W, g.lv[l].stride, g.lv[l].anchor0};
-    PA_HIP(e, dmalloc((void**)&L.d_cand, B * A * 6 * sizeof(float)));
-    PA_HIP(e, dmalloc((void**)&L.d_cidx, B * A * sizeof(int32_t)));
-    PA_HIP(e, dmalloc((void**)&L.d_ccnt, B * sizeof(int32_t)));
-    PA_HIP(e, dmalloc((void**)&L.d_keys, B * g.P2 * sizeof(uint64_t)));
-    PA_HIP(e, dmalloc((void**)&L.d_order, B * A * sizeof(int32_t)));
-    PA_HIP(e, dmalloc((void**)&L.d_supp, B * A));
-    PA_HIP(e, dmalloc((void**)&L.d_oboxes, B * 300 * 6 * sizeof(float)));
-    PA_HIP(e, dmalloc((void**)&L.d_ocnt, B * sizeof(int32_t)));
-    if (m->d.nk) PA_HIP(e, dmalloc((void**)&L.d_okpts, B * 300 * m->d.nk * sizeof(float)));
-    if (m->rs.d_tmp) {
-        if (own_tmp) PA_HIP(e, dmalloc((void**)&L.d_rs_tmp, m->rs.tmp_bytes)); else total += m->rs.tmp_bytes;
-    }
-    m->lane_bytes = total;
+    PA_HIP(e, L.d_cand.alloc(B * A * 6 * sizeof(float)));
+    PA_HIP(e, L.d_cidx.alloc(B * A * sizeof(int32_t)));
+    PA_HIP(e, L.d_ccnt.alloc(B * sizeof(int32_t)));
+    PA_HIP(e, L.d_keys.alloc(B * g.P2 * sizeof(uint64_t)));
+    PA_HIP(e, L.d_order.alloc(B * A * sizeof(int32_t)));
+    PA_HIP(e, L.d_supp.alloc(B * A));
+    PA_HIP(e, L.d_oboxes.alloc(B * 300 * 6 * sizeof(float)));
+    PA_HIP(e, L.d_ocnt.alloc(B * sizeof(int32_t)));
+    if (m->d.nk) PA_HIP(e, L.d_okpts.alloc(B * 300 * m->d.nk * sizeof(float)));
+    if (own_tmp && m->rs.d_tmp) PA_HIP(e, L.d_rs_tmp.alloc(m->rs.d_tmp.bytes()));
+    m->lane_bytes = L.device_bytes() + (own_tmp ? 0 : m->rs.d_tmp.bytes());
     return 0;
 }
 
@@ -45,8 +40,8 @@ static int plan_yolo(pa_model* m, int h0, int w0, const pa_yolo_params* p) {
         std::vector<int32_t> xt, yt;
         cv2_linear_table(w0, m->rw, xt);
         cv2_linear_table(h0, m->rh, yt);
-        PA_HIP(e, upload_table(e, &m->d_xtab, xt));
-        PA_HIP(e, upload_table(e, &m->d_ytab, yt));
+        PA_HIP(e, upload_table(e, m->d_xtab, xt));
+        PA_HIP(e, upload_table(e, m->d_ytab, yt));
     }
     if (p->pre_mode == PA_PRE_PIL_STRETCH && resample_plan(e, &m->rs, h0, w0, S, S, PIL_BICUBIC, m->max_batch)) return 1;
     m->A = g.A;
@@ -106,8 +101,8 @@ static int run_post(pa_model* m, Lane& L, const pa_yolo_params* p, int nb, int o
     DecodeArgs da{};
     for (int l = 0; l < 3; ++l) da.lv[l] = L.lv[l];
     da.cs = m->bufs[m->d.head_buf[0]].channels; da.nc = m->d.nc; da.nk = m->d.nk; da.kdim = m->d.kpt_dim;
-    da.A = m->A; da.B = nb; da.conf = p->conf; da.classes = m->d_classes; da.n_classes = p->n_classes;
-    da.cand = L.d_cand; da.cand_idx = L.d_cidx; da.cand_cnt = L.d_ccnt;
+    da.A = m->A; da.B = nb; da.conf = p->conf; da.classes = m->d_classes.get(); da.n_classes = p->n_classes;
+    da.cand = L.d_cand.get(); da.cand_idx = L.d_cidx.get(); da.cand_cnt = L.d_ccnt.get();
     pr = prof_begin(m, s, pi++, PROF_DECODE, 0, 0.0);
     if (fused) {
         HeadTailArgs ha{};
@@ -122,8 +117,8 @@ static int run_post(pa_model* m, Lane& L, const pa_yolo_params* p, int nb, int o
     m->last_post_path = fused ? 1 : 0;
     m->heads_stale = fused;
     NmsArgs na{};
-    na.cand = L.d_cand; na.cand_idx = L.d_cidx; na.cand_cnt = L.d_ccnt; na.keys = L.d_keys;
-    na.order = L.d_order; na.supp = L.d_supp;
+    na.cand = L.d_cand.get(); na.cand_idx = L.d_cidx.get(); na.cand_cnt = L.d_ccnt.get(); na.keys = L.d_keys.get();
+    na.order = L.d_order.get(); na.supp = L.d_supp.get();
     for (int l = 0; l < 3; ++l) na.lv[l] = L.lv[l];
     na.cs = da.cs; na.nc = m->d.nc; na.nk = m->d.nk; na.kdim = m->d.kpt_dim; na.A = m->A; na.B = nb; na.P2 = m->P2;
     na.iou = p->iou; na.max_det = p->max_det; na.max_nms = 30000;
@@ -131,19 +126,19 @@ static int run_post(pa_model* m, Lane& L, const pa_yolo_params* p, int nb, int o
     na.pad_x = (float)std::nearbyint(kpx - 0.1); na.pad_y = (float)std::nearbyint(kpy - 0.1);
     na.kpad_x = (float)kpx; na.kpad_y = (float)kpy;
     na.w0 = (float)ow; na.h0 = (float)oh;
-    na.out_boxes = L.d_oboxes; na.out_kpts = L.d_okpts; na.out_cnt = L.d_ocnt;
+    na.out_boxes = L.d_oboxes.get(); na.out_kpts = L.d_okpts.get(); na.out_cnt = L.d_ocnt.get();
     pr = prof_begin(m, s, pi++, PROF_NMS, 0, 0.0);
     r = launch_nms(na, s);
     prof_end(s, pr);
     if (r != hipSuccess) PA_FAIL(e, "nms launch failed: %s", hipGetErrorString(r));
     // ---- results back to the caller's arrays (rows beyond max_det are never written on device)
     if (m->d.dtype == PA_DTYPE_H2)      // the overflow flag travels with the results: pa_model_take_overflow needs no device round trip
-        PA_HIP(e, hipMemcpyAsync(m->h_pin + ovf_slot, m->d_ovf, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    PA_HIP(e, hipMemcpyAsync(out_counts, L.d_ocnt, nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    PA_HIP(e, hipMemcpyAsync(out_boxes, L.d_oboxes,
+        PA_HIP(e, hipMemcpyAsync(m->h_pin.get() + ovf_slot, m->d_ovf.get(), sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    PA_HIP(e, hipMemcpyAsync(out_counts, L.d_ocnt.get(), nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    PA_HIP(e, hipMemcpyAsync(out_boxes, L.d_oboxes.get(),
                              (size_t)nb * p->max_det * 6 * sizeof(float), hipMemcpyDeviceToHost, s));
     if (m->d.nk)
-        PA_HIP(e, hipMemcpyAsync(out_kpts, L.d_okpts,
+        PA_HIP(e, hipMemcpyAsync(out_kpts, L.d_okpts.get(),
                                  (size_t)nb * p->max_det * m->d.nk * sizeof(float), hipMemcpyDeviceToHost, s));
     return 0;
 }
@@ -162,14 +157,11 @@ static int set_classes(pa_model* m, const pa_yolo_params* p) {
     // (the device list is read by queued decode kernels: replace it only once they are done)
     PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));        // (behind every ticket's join)
     PA_HIP(e, e->sync_lanes());
-    if (p->n_classes > m->classes_cap) {
-        if (m->d_classes) hipFree(m->d_classes);
-        m->d_classes = nullptr; m->classes_cap = 0; m->classes_host.clear();
-        PA_HIP(e, hipMalloc((void**)&m->d_classes, p->n_classes * sizeof(int32_t)));
-        m->classes_cap = p->n_classes;
-    }
+    const size_t bytes = p->n_classes * sizeof(int32_t);
+    if (m->d_classes.bytes() < bytes) m->classes_host.clear();          // the device list is about to go
+    PA_HIP(e, m->d_classes.fit(bytes, bytes));
     m->classes_host.assign(p->classes, p->classes + p->n_classes);
-    PA_HIP(e, hipMemcpy(m->d_classes, m->classes_host.data(), p->n_classes * sizeof(int32_t), hipMemcpyHostToDevice));
+    PA_HIP(e, hipMemcpy(m->d_classes.get(), m->classes_host.data(), p->n_classes * sizeof(int32_t), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -210,12 +202,12 @@ static int yolo_enqueue(pa_model* m, int li, const uint8_t* src, int nb, int h, 
     hipError_t r = hipSuccess;
     if (p->pre_mode == PA_PRE_LETTERBOX || (h == S && w == S)) {
         LetterboxArgs a{};
-        a.src = src; a.dst = L.d_netin; a.B = nb; a.h0 = h; a.w0 = w; a.rw = m->rw; a.rh = m->rh;
+        a.src = src; a.dst = L.d_netin.get(); a.B = nb; a.h0 = h; a.w0 = w; a.rw = m->rw; a.rh = m->rh;
         a.top = m->top; a.left = m->left; a.nh = m->net_h; a.nw = m->net_w; a.mode = m->lb_mode;
-        a.reverse = p->channel_reverse; a.xtab = m->d_xtab; a.ytab = m->d_ytab;
+        a.reverse = p->channel_reverse; a.xtab = m->d_xtab.get(); a.ytab = m->d_ytab.get();
         r = launch_letterbox(a, s);
     } else {
-        r = resample_enqueue(m->rs, src, L.d_netin, nb, 4, p->channel_reverse, s, L.d_rs_tmp);
+        r = resample_enqueue(m->rs, src, L.d_netin.get(), nb, 4, p->channel_reverse, s, L.d_rs_tmp.get());
     }
     prof_end(s, pr);
     if (r != hipSuccess) PA_FAIL(e, "preprocess launch failed: %s", hipGetErrorString(r));
@@ -241,7 +233,7 @@ int pa_yolo_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, const
             return 1;
         PA_HIP(e, hipStreamSynchronize(s));
         m->last_n = nb;
-        if (m->d.dtype == PA_DTYPE_H2) { m->h_ovf |= m->h_pin[PA_MAX_INFLIGHT]; m->ovf_cached = true; }
+        if (m->d.dtype == PA_DTYPE_H2) { m->h_ovf |= m->h_pin.get()[PA_MAX_INFLIGHT]; m->ovf_cached = true; }
     }
     PA_HIP(e, e->sync_lanes());          // a synchronous call completes every ticket still in flight, on either lane: their waits return at once
     finish_profile(m, pi);
@@ -296,7 +288,7 @@ int pa_yolo_wait(pa_model* m, int ticket, int* overflow) {
     --m->n_inflight;
     Lane& L = m->ln[m->tk_lane[slot]];
     if (L.st.last_ticket == ticket) L.st.busy = false;
-    if (overflow) *overflow = (m->d.dtype == PA_DTYPE_H2 && m->h_pin[slot]) ? 1 : 0;
+    if (overflow) *overflow = (m->d.dtype == PA_DTYPE_H2 && m->h_pin.get()[slot]) ? 1 : 0;
     return 0;
 }
 
@@ -374,7 +366,7 @@ int pa_yolo_read_netin(pa_model* m, int n, uint8_t* out) {
     PA_HIP(e, hipSetDevice(e->dev));
     Lane& L = m->ln[m->last_lane];
     const hipStream_t s = L.stream ? L.stream : e->main_stream();          // (a ResNet plan has a network input too: it runs on the main stream)
-    PA_HIP(e, hipMemcpyAsync(out, L.d_netin, (size_t)n * m->net_h * m->net_w * 4, hipMemcpyDeviceToHost, s));
+    PA_HIP(e, hipMemcpyAsync(out, L.d_netin.get(), (size_t)n * m->net_h * m->net_w * 4, hipMemcpyDeviceToHost, s));
     PA_HIP(e, hipStreamSynchronize(s));
     return 0;
 }

@@ -122,7 +122,7 @@ ABI_SYMBOLS = [
     "pa_jpeg_encode", "pa_jpeg_check", "pa_jpeg_interval_bytes",
     "pa_jpeg_parse", "pa_jpeg_decode", "pa_jpeg_decode_last_path", "pa_jpeg_decode_last_times",
     "pa_yolo_last_post_path", "pa_jpeg_decode_set_split", "pa_jpeg_decode_last_split",
-    "pa_model_lanes_allocated", "pa_model_last_lane", "pa_yolo_resample_passes",
+    "pa_model_lanes_allocated", "pa_model_last_lane", "pa_yolo_resample_passes", "pa_device_bytes_live",
 ]
 
 
@@ -152,6 +152,8 @@ def load_library():
     lib.pa_engine_synchronize.argtypes = [vp]
     lib.pa_device_malloc.argtypes = [vp, sz, C.POINTER(vp)]
     lib.pa_device_free.argtypes = [vp, vp]
+    lib.pa_device_bytes_live.argtypes = []
+    lib.pa_device_bytes_live.restype = sz
     lib.pa_memcpy_h2d.argtypes = [vp, vp, vp, sz]
     lib.pa_memcpy_d2h.argtypes = [vp, vp, vp, sz]
     lib.pa_model_create.argtypes = [vp, C.POINTER(pa_model_desc), vp, sz, C.POINTER(vp)]
@@ -233,6 +235,12 @@ def load_library():
         raise EngineUnavailable("libpadel_hip.so ABI version mismatch")
     _lib = lib
     return lib
+
+
+def device_bytes_live() -> int:
+    """Device bytes the library holds in this process right now (``pa_device_bytes_live``): everything its models, sessions and
+    engines own, not the ``DeviceBuffer`` s of the caller.  It returns to its earlier value when what was created since is closed."""
+    return int(load_library().pa_device_bytes_live())
 
 
 PIL_BICUBIC, PIL_BILINEAR = 0, 1
