@@ -34,6 +34,9 @@ pids+=($!)
 # what is decided about a graph before anything runs (refusals, upsample folds, memory plan, resize tables): no HIP runtime call either
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include ${PADEL_EXTRA_FLAGS:-} -c graph_plan.cpp -o "$BUILD/graph_plan.o" &
 pids+=($!)
+# what one replay of an op list launches, and with which arguments: no HIP runtime call either
+g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include ${PADEL_EXTRA_FLAGS:-} -c launch_plan.cpp -o "$BUILD/launch_plan.o" &
+pids+=($!)
 # what pa_render refuses, and the font: no HIP at all (the same file builds into tests/render_marks_main.cpp's program)
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c render_check.cpp -o "$BUILD/render_check.o" &
 pids+=($!)

@@ -7,8 +7,8 @@
 //   * the RESOLVER: (path, layer, requested id) -> (tile, family) after every fall-through      -> resolve_conv
 //   * the four CHOOSERS over the table with one scoring helper                                  -> choose_conv_*_variant
 //
-// The .hip files keep kernels and launch_conv_<family>(a, tile, s), which launches exactly that tile; launch_conv (conv_tap.hip)
-// resolves and calls the launcher the row names.  A new tile is one table row and one launcher case.
+// The .hip files keep kernels and launch_conv_<family>(a, tile, s), which launches exactly that tile; the step builder (launch_plan.cpp)
+// resolves, launch_conv_family (conv_tap.hip) calls the launcher the row names.  A new tile is one table row and one launcher case.
 #include "kernels.h"
 
 #include <string.h>

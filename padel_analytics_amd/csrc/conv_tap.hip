@@ -439,17 +439,13 @@ hipError_t launch_conv_tapt(const ConvArgs& a, int tile, hipStream_t s) {
     return hipErrorNotSupported;
 }
 
-// The one conv entry point: which (tile, family) runs is resolve_conv's decision alone (conv_select.cpp); a launcher launches the tile it is given
-hipError_t launch_conv(int path, const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran) {
+// The one conv entry point: which (tile, family) runs is resolve_conv's decision alone (conv_select.cpp), made where the launch is
+// planned (launch_plan.cpp); a launcher launches the tile it is given
+hipError_t launch_conv_family(ConvFamily f, const ConvArgs& a, int tile, hipStream_t s) {
     static hipError_t (*const launchers[])(const ConvArgs&, int, hipStream_t) = {      // by ConvFamily
         launch_conv_tapt, launch_conv_bx3t, launch_conv_bx3p, launch_conv_h2t, launch_conv_h2d, launch_conv_h2s, launch_conv_h2s3, launch_conv_h2p,
         launch_conv_h2q,  launch_conv_h2r,  launch_conv_h2w,  launch_conv_h2v, launch_conv_t16, launch_conv_t16, launch_conv_p16,  launch_conv_p16};
-    ConvLaunched r;
-    ConvFamily f;
-    if (!resolve_conv(path, a, variant, &r, &f)) return hipErrorNotSupported;
-    const hipError_t e = launchers[f](a, r.tile, s);
-    if (ran && e == hipSuccess) *ran = r;
-    return e;
+    return launchers[f](a, tile, s);
 }
 
 }  // namespace padel

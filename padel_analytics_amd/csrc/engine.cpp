@@ -1,7 +1,8 @@
 // libpadel_hip.so — engine: owns the streams of one GPU (the main stream that orders its work, two lane streams for in-flight
 // YOLO batches, a copy stream), the packed weights and every activation buffer in HBM, plans a graph for a (source size, imgsz, batch) and replays it per batch.
 // C-ABI declared in include/padel_hip.h.  This file: engine and model lifecycle, tuning, memory and timer calls, the arena,
-// the op-list replay (run_ops / run_graph) and the profile text; engine_internal.h names the other files.
+// the op-list replay (run_ops / run_graph: the step list of launch_plan.cpp, launched step by step) and the profile text;
+// engine_internal.h names the other files.
 #include "engine_internal.h"
 
 #include <atomic>
@@ -220,15 +221,11 @@ int pa_model_create(pa_engine* e, const pa_model_desc* desc, const float* weight
     m->ops.assign(desc->ops, desc->ops + desc->n_ops);
     m->d.bufs = m->bufs.data();
     m->d.ops = m->ops.data();
-    find_upsample_folds(m->d, m->fold_src, m->fold_dst);
+    std::vector<int> fold_dst;
+    find_upsample_folds(m->d, m->fold_src, fold_dst);
     m->stem_fuse.resize(m->ops.size());
     for (size_t i = 0; i < m->ops.size(); ++i) m->stem_fuse[i] = stem_fusable(m->d, i);
     m->tail = find_head_tail(m->d, m->fold_src);
-    m->tail_op.assign(m->ops.size(), 0);
-    if (m->tail.found)
-        for (int l = 0; l < 3; ++l)
-            for (int c = 0; c < 3; ++c)
-                if (m->tail.op[l][c] >= 0) m->tail_op[m->tail.op[l][c]] = 1;
     m->n_w = n_floats;
     if (desc->task == PA_TASK_DETECT || desc->task == PA_TASK_POSE)
         for (int i = 0; i < kMaxLanes; ++i) m->ln[i].stream = e->lane_stream[i];
@@ -360,57 +357,19 @@ ProfRec* prof_begin(pa_model* m, hipStream_t s, size_t idx, int kind, int ksize,
     return r;
 }
 
-static bool fold_active(const pa_model* m, int conv_op) {
-    if (m->d.dtype == PA_DTYPE_H2) return m->e->t.fold_up && m->fold_src[conv_op] >= 0;
-    return m->e->t.fold_up && m->e->t.impl == 2 && m->d.dtype != PA_DTYPE_F16 && m->fold_src[conv_op] >= 0;
+// the base pointers of a replay on lane L (launch_plan.h; their lifetime: the audit at struct Lane)
+static PlanPointers plan_pointers(const pa_model* m, const Lane& L) {
+    return PlanPointers{L.bptr.data(), m->d_w.get(), m->d_wr.get(), m->wr_valid ? m->wr_off.data() : nullptr, m->e->zeros.get(), m->d_ovf.get(),
+                        L.d_netin.get(), L.d_fc.get(), m->p_batch};
 }
 
-// ConvArgs of conv op i for `n` images, its path (kernel choice: bf16x3 by default, tap kernels by tuning, conv_tap16 for fp16
-// models) and the tile id it will be requested with (a forced variant picks the tile of whichever path is selected).  An absorbed
-// upsample (find_upsample_folds) is attached here, where the requested tile resolves to a kernel that reads it: the 1x1 tap
-// tiles, and for a 3x3 consumer the patch kernel.
-static int conv_launch_args(const pa_model* m, const Lane& L, size_t i, int n, ConvArgs& a, int* path_out = nullptr) {
-    const pa_engine* e = m->e;
-    const pa_op_desc& o = m->ops[i];
-    const pa_buf_desc& ob = m->bufs[o.out_buf];
-    const pa_buf_desc& ib = m->bufs[o.in_buf];
-    const int Ho = m->net_h >> ob.level, Wo = m->net_w >> ob.level;
-    a.in = L.bptr[o.in_buf]; a.in_cs = ib.channels; a.in_choff = o.in_choff;
-    a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
-    a.res = o.res_buf >= 0 ? L.bptr[o.res_buf] : nullptr;
-    a.res_cs = o.res_buf >= 0 ? m->bufs[o.res_buf].channels : 0; a.res_choff = o.res_choff;
-    a.res_pre = (o.res_buf >= 0 && (o.flags & PA_CONV_RES_PREACT)) ? 1 : 0;
-    a.zeros = e->zeros.get();
-    a.w = m->d_w.get() + o.w_off; a.bias = m->d_w.get() + o.b_off;
-    a.H = m->net_h >> ib.level; a.W = m->net_w >> ib.level; a.Ho = Ho; a.Wo = Wo;
-    a.cin = o.cin; a.cout = o.cout; a.n16 = o.npad / 16; a.ksize = o.ksize; a.stride = o.stride; a.act = o.act;
-    a.M = n * Ho * Wo;
-    fill_fastdiv((unsigned)(Ho * Wo), &a.howo_magic, &a.howo_shift);
-    fill_fastdiv((unsigned)Wo, &a.wo_magic, &a.wo_shift);
-    a.tune = e->t.tune; a.tap_pd = e->t.tap_pd;
-    const bool f16 = m->d.dtype == PA_DTYPE_F16, h2 = m->d.dtype == PA_DTYPE_H2;
-    const bool use_bx3 = !f16 && !h2 && e->t.impl == 2 && o.reserved > 0;
-    a.w3 = use_bx3 ? (const void*)(m->d_w.get() + o.reserved) : nullptr;
-    a.out_f32 = (f16 || h2) && is_head_buf(m->d, o.out_buf);
-    const int path = h2 ? CONV_PATH_H2 : f16 ? CONV_PATH_F16 : use_bx3 ? CONV_PATH_BX3 : CONV_PATH_TAP;
-    if (path_out) *path_out = path;
-    if (h2) {
-        a.oscale = m->d_w.get() + o.reserved;
-        a.ovf_flag = m->d_ovf.get();
-        a.w_single = (o.flags & PA_CONV_W_SINGLE) && e->t.w_single ? 1 : 0;
-        a.wr = (m->wr_valid && i < m->wr_off.size() && m->wr_off[i] >= 0) ? (const void*)(m->d_wr.get() + m->wr_off[i]) : nullptr;
-    }
-    const int lv = e->t.variant >= 0 ? e->t.variant
-                   : h2 ? choose_conv_h2_variant(a)
-                   : f16 ? choose_conv_tap16_variant(a)
-                   : use_bx3 ? choose_conv_bx3_variant(a)
-                         : choose_conv_tap_variant(a.M, a.n16);
-    if ((h2 || use_bx3) && fold_active(m, (int)i)) {
-        const pa_op_desc& u = m->ops[m->fold_src[i]];       // the first up_c channels come from the coarse map
-        a.in2 = L.bptr[u.in_buf]; a.in2_cs = m->bufs[u.in_buf].channels; a.in2_choff = u.in_choff; a.up_c = u.cin;
-        if (!resolve_conv(path, a, lv, nullptr)) { a.in2 = nullptr; a.in2_cs = a.in2_choff = a.up_c = 0; }      // no kernel of this tile's chain reads it: the upsample runs
-    }
-    return lv;
+// the launches of one replay for n images into L.steps; a refusal leaves the list empty and nothing enqueued
+static int plan_steps(pa_model* m, Lane& L, int n) {
+    std::string why;
+    if (build_steps(m->d, m->fold_src, m->stem_fuse, m->tail, m->e->t, plan_pointers(m, L), m->net_h, m->net_w, n, L.steps, why,
+                    hipGetErrorString(hipErrorNotSupported)))
+        PA_FAIL(m->e, "%s", why.c_str());
+    return 0;
 }
 
 void head_tail_convs(const pa_model* m, const Lane& L, HeadTailArgs& a) {
@@ -439,159 +398,73 @@ bool head_fused(const pa_model* m) {
     return head_tail_h2_supported(a);
 }
 
-int run_tail_ops(pa_model* m, Lane& L, hipStream_t s, int n) {
+// the launcher of a step's kind with the step's arguments (a: its conv arguments, or the timeline's copy of them)
+static hipError_t launch_step(const Step& st, const ConvArgs& a, hipStream_t s) {
+    const SliceArgs& v = st.sl;
+    switch (st.kind) {
+        case PA_OP_CONV: return launch_conv_family(st.family, a, st.ran.tile, s);
+        case PA_OP_STEM: return st.n_ops == 2 ? launch_stem_l1_h2(st.stem, a, s) : launch_stem(st.stem, s);
+        case PA_OP_SPPF_POOL: return launch_sppf_pool(v.in, v.in_cs, v.in_choff, v.c, v.B, v.H, v.W, s, v.fmt, v.fused);
+        case PA_OP_UPSAMPLE2X: return launch_upsample2x(v.in, v.in_cs, v.in_choff, v.out, v.out_cs, v.out_choff, v.c, v.B, v.H, v.W, s, v.fmt);
+        case PA_OP_MAXPOOL2: return launch_maxpool2(v.in, v.in_cs, v.in_choff, v.out, v.out_cs, v.out_choff, v.c, v.B, v.H, v.W, s, v.fmt);
+        case PA_OP_MAXPOOL3S2: return launch_maxpool3s2(v.in, v.in_cs, v.in_choff, v.out, v.out_cs, v.out_choff, v.c, v.B, v.H, v.W, v.Ho, v.Wo, s, v.fmt);
+        case PA_OP_STEM7: return launch_stem7(st.stem7, s);
+        case PA_OP_GAP_FC: return launch_gap_fc(v.in, v.in_cs, v.in_choff, v.c, v.B, v.H, v.w, v.bias, v.nout, v.logits, v.probs, s, v.fmt);
+        case PA_OP_DWCONV3: return launch_dwconv3(st.dw, s);
+        case PA_OP_PSA_ATTN: return launch_psa_attn(st.attn, s);
+    }
+    return hipSuccess;
+}
+
+// tuning only ("timeline"): a conv step that runs the tile it asked for, with the s_memtime timeline of this launch collected into
+// timeline_path.  The buffer is per launch: released where this returns, behind the wait
+static hipError_t launch_conv_timeline(pa_model* m, const Step& st, hipStream_t s) {
     pa_engine* e = m->e;
-    for (int l = 0; l < 3; ++l)
-        for (int c = 0; c < 3; ++c) {
-            const int i = m->tail.op[l][c];
-            if (i < 0) continue;
-            ConvArgs a{};
-            int path = CONV_PATH_TAP;
-            const int lv = conv_launch_args(m, L, (size_t)i, n, a, &path);
-            const hipError_t r = launch_conv(path, a, lv, s);
-            if (r != hipSuccess) PA_FAIL(e, "op %d (head tail) launch failed: %s", i, hipGetErrorString(r));
-        }
+    ConvArgs a = st.conv;
+    const size_t patches = (size_t)(a.M / (a.Ho * a.Wo)) * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);          // patch kernels: one record per workgroup of the 1-D grid
+    const size_t records = st.path == CONV_PATH_H2 ? 8 * ((patches + 7) / 8) * (size_t)((a.n16 + 5) / 6)
+                                                   : (size_t)((a.M + 63) / 64) * ((m->ops[st.op].npad + 95) / 96);
+    const size_t dbg_bytes = records * conv_timeline_words(st.ran, a.ksize) * 8;          // 0: this kernel has no timeline instantiation
+    DevMem<unsigned long long> dbg_dev;
+    if (dbg_bytes && dbg_dev.alloc(dbg_bytes) == 0) (void)hipMemsetAsync(dbg_dev.get(), 0, dbg_bytes, s);
+    a.dbg = dbg_dev.get();
+    const hipError_t r = launch_step(st, a, s);
+    if (dbg_dev) {
+        (void)hipStreamSynchronize(s);
+        std::vector<unsigned long long> host(dbg_bytes / 8);
+        (void)hipMemcpy(host.data(), dbg_dev.get(), dbg_bytes, hipMemcpyDeviceToHost);
+        if (FILE* f = fopen(e->timeline_path.c_str(), "wb")) { fwrite(host.data(), 1, dbg_bytes, f); fclose(f); }
+    }
+    return r;
+}
+
+// the tail convs alone, for the n images of the lane's last call: the same list, the steps marked `tail`
+int run_tail_ops(pa_model* m, Lane& L, hipStream_t s, int n) {
+    if (plan_steps(m, L, n)) return 1;
+    for (const Step& st : L.steps) {
+        if (!st.tail) continue;
+        const hipError_t r = launch_step(st, st.conv, s);
+        if (r != hipSuccess) PA_FAIL(m->e, "op %d (head tail) launch failed: %s", st.op, hipGetErrorString(r));
+    }
     return 0;
 }
 
-// replay the op list for `n` images (prof records appended starting at *pi)
-static int run_ops(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
+// replay the op list for `n` images (prof records appended starting at *pi): decide every launch (launch_plan.cpp), then launch
+static int run_ops(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi, bool skip_tail) {
     pa_engine* e = m->e;
-    const bool skip_tail = head_fused(m);          // the heads' last convs run inside the fused head tail (run_post)
-    for (size_t i = 0; i < m->ops.size(); ++i) {
-        const pa_op_desc& o = m->ops[i];
-        if (skip_tail && m->tail_op[i]) continue;
-        const pa_buf_desc& ob = m->bufs[o.out_buf];
-        const int Ho = m->net_h >> ob.level, Wo = m->net_w >> ob.level;
-        hipError_t r = hipSuccess;
-        ProfRec* pr = nullptr;
-        if (o.kind == PA_OP_CONV) {
-            ConvArgs a{};
-            int path = CONV_PATH_TAP;
-            const int lv = conv_launch_args(m, L, i, n, a, &path);
-            const bool f16 = path == CONV_PATH_F16, h2 = path == CONV_PATH_H2, use_bx3 = path == CONV_PATH_BX3;
-            int bm = 0, bn = 0;
-            conv_tile_shape(path, lv, &bm, &bn);            // profile rows carry BM, BN of the REQUESTED workgroup tile
-            pr = prof_begin(m, s, (*pi)++, o.kind, o.ksize, 2.0 * a.M * (double)o.cout * o.cin * o.ksize * o.ksize);
-            if (pr) { pr->M = a.M; pr->cout = o.cout; pr->cin = o.cin; pr->stride = o.stride; pr->mf = bm; pr->nf = bn; pr->res = a.res != nullptr; }
-            // tuning only ("timeline"): collect the s_memtime timeline of this launch into timeline_path
-            DevMem<unsigned long long> dbg_dev;          // per launch: released where this op's turn ends, behind the wait below
-            size_t dbg_bytes = 0;
-            ConvLaunched will{-1, ""};
-            if (e->t.timeline && !e->timeline_path.empty() && resolve_conv(path, a, lv, &will) && will.tile == lv) {
-                const size_t patches = (size_t)n * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);          // patch kernels: one record per workgroup of the 1-D grid
-                const size_t records = h2 ? 8 * ((patches + 7) / 8) * (size_t)((a.n16 + 5) / 6) : (size_t)((a.M + 63) / 64) * ((o.npad + 95) / 96);
-                dbg_bytes = records * conv_timeline_words(will, o.ksize) * 8;          // 0: this kernel has no timeline instantiation
-            }
-            if (dbg_bytes) {
-                if (dbg_dev.alloc(dbg_bytes) == 0) (void)hipMemsetAsync(dbg_dev.get(), 0, dbg_bytes, s);
-                a.dbg = dbg_dev.get();
-            }
-            ConvLaunched ran{-1, ""};
-            // act(conv + bias + residual) exists in the h2 and bf16x3 epilogues; the other families refuse instead of applying the other order
-            if (a.res_pre && !h2 && !use_bx3)
-                PA_FAIL(e, "op %zu: PA_CONV_RES_PREACT needs the h2 or the bf16x3 kernels (tuning impl = 2, bf16x3 weights in the blob), not the %s family",
-                        i, f16 ? "fp16" : "fp32-MFMA tap");
-            r = launch_conv(path, a, lv, s, &ran);
-            if (pr) { pr->tile = ran.tile; pr->family = ran.family; }
-            if (dbg_dev) {
-                (void)hipStreamSynchronize(s);
-                std::vector<unsigned long long> host(dbg_bytes / 8);
-                (void)hipMemcpy(host.data(), dbg_dev.get(), dbg_bytes, hipMemcpyDeviceToHost);
-                if (FILE* f = fopen(e->timeline_path.c_str(), "wb")) { fwrite(host.data(), 1, dbg_bytes, f); fclose(f); }
-            }
-        } else if (o.kind == PA_OP_STEM) {
-            StemArgs a{};
-            a.in = L.d_netin.get(); a.w = m->d_w.get() + o.w_off; a.bias = m->d_w.get() + o.b_off;
-            a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
-            a.H = m->net_h; a.W = m->net_w; a.Ho = Ho; a.Wo = Wo; a.cout = o.cout; a.B = n;
-            a.out_f16 = m->d.dtype == PA_DTYPE_F16 ? 1 : m->d.dtype == PA_DTYPE_H2 ? 2 : 0;
-            a.ovf_flag = m->d_ovf.get();
-            a.opw = (m->wr_valid && i < m->wr_off.size() && m->wr_off[i] >= 0) ? (const void*)(m->d_wr.get() + m->wr_off[i]) : nullptr;
-            pr = prof_begin(m, s, (*pi)++, o.kind, 3, 2.0 * n * Ho * Wo * (double)o.cout * 27);
-            // tuning "fuse_stem": the stem and the stride-2 3x3 behind it (its only reader) as one kernel; the conv's own
-            // turn in this loop is skipped (the profile shows both under the stem's record)
-            if (e->t.fuse_stem && m->d.dtype == PA_DTYPE_H2 && m->stem_fuse[i]) {
-                ConvArgs ca{};
-                conv_launch_args(m, L, i + 1, n, ca);
-                if (stem_l1_h2_supported(a, ca)) {
-                    r = launch_stem_l1_h2(a, ca, s);
-                    prof_end(s, pr);
-                    if (r != hipSuccess) PA_FAIL(e, "fused stem + layer 1 launch failed: %s", hipGetErrorString(r));
-                    ++i;
-                    continue;
-                }
-            }
-            r = launch_stem(a, s);
-        } else if (o.kind == PA_OP_SPPF_POOL) {
-            pr = prof_begin(m, s, (*pi)++, o.kind, 5, 0.0);
-            r = launch_sppf_pool(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, o.cin, n, Ho, Wo, s, (int)m->d.dtype, e->t.fuse_sppf);
-        } else if (o.kind == PA_OP_UPSAMPLE2X) {
-            if (m->fold_dst[i] >= 0) {                   // absorbed by its consumer conv?  (same decision as at that conv)
-                ConvArgs ca{};
-                conv_launch_args(m, L, (size_t)m->fold_dst[i], n, ca);
-                if (ca.in2) continue;
-            }
-            pr = prof_begin(m, s, (*pi)++, o.kind, 0, 0.0);
-            r = launch_upsample2x(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, L.bptr[o.out_buf],
-                                  ob.channels, o.out_choff, o.cin, n, Ho / 2, Wo / 2, s, (int)m->d.dtype);
-        } else if (o.kind == PA_OP_MAXPOOL2) {
-            pr = prof_begin(m, s, (*pi)++, o.kind, 2, 0.0);
-            r = launch_maxpool2(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, L.bptr[o.out_buf],
-                                ob.channels, o.out_choff, o.cin, n, Ho * 2, Wo * 2, s, (int)m->d.dtype);
-        } else if (o.kind == PA_OP_MAXPOOL3S2) {
-            const int lin = m->bufs[o.in_buf].level;
-            pr = prof_begin(m, s, (*pi)++, o.kind, 3, 0.0);
-            r = launch_maxpool3s2(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, L.bptr[o.out_buf], ob.channels, o.out_choff,
-                                  o.cin, n, m->net_h >> lin, m->net_w >> lin, Ho, Wo, s, m->d.dtype == PA_DTYPE_H2 ? 1 : 0);
-        } else if (o.kind == PA_OP_STEM7) {
-            if (!L.d_netin) PA_FAIL(e, "op %zu: the 7x7 stem reads the u8 network input of pa_resnet_infer", i);
-            const bool head = is_head_buf(m->d, o.out_buf);
-            Stem7Args a{};
-            a.in = L.d_netin.get(); a.w = m->d_w.get() + o.w_off; a.bias = m->d_w.get() + o.b_off; a.lut = m->d_w.get() + o.reserved;
-            a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
-            a.H = m->net_h; a.W = m->net_w; a.Ho = Ho; a.Wo = Wo; a.B = n; a.act = o.act;
-            a.out_h2 = (m->d.dtype == PA_DTYPE_H2 && !head) ? 1 : 0;
-            a.ovf_flag = m->d_ovf.get();
-            pr = prof_begin(m, s, (*pi)++, o.kind, 7, 2.0 * n * Ho * Wo * 64.0 * 147.0);
-            if (pr) { pr->M = n * Ho * Wo; pr->cout = 64; pr->cin = 3; pr->stride = 2; }
-            r = launch_stem7(a, s);
-        } else if (o.kind == PA_OP_GAP_FC) {
-            const int lin = m->bufs[o.in_buf].level;
-            const int hw = (m->net_h >> lin) * (m->net_w >> lin);
-            pr = prof_begin(m, s, (*pi)++, o.kind, 0, 2.0 * n * (double)o.cout * o.cin);
-            if (pr) { pr->M = n; pr->cout = o.cout; pr->cin = o.cin; }
-            r = launch_gap_fc(L.bptr[o.in_buf], m->bufs[o.in_buf].channels, o.in_choff, o.cin, n, hw, m->d_w.get() + o.w_off, m->d_w.get() + o.b_off,
-                              o.cout, L.d_fc.get(), L.d_fc.get() + (size_t)m->p_batch * kGapFcMaxOut, s, m->d.dtype == PA_DTYPE_H2 ? 1 : 0);
-        } else if (o.kind == PA_OP_DWCONV3) {
-            const bool h2 = m->d.dtype == PA_DTYPE_H2;
-            const bool head = is_head_buf(m->d, o.out_buf);
-            DwConvArgs a{};
-            a.in = L.bptr[o.in_buf]; a.in_cs = m->bufs[o.in_buf].channels; a.in_choff = o.in_choff;
-            a.w = m->d_w.get() + o.w_off; a.bias = m->d_w.get() + o.b_off;
-            a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
-            if (o.res_buf >= 0) { a.res = L.bptr[o.res_buf]; a.res_cs = m->bufs[o.res_buf].channels; a.res_choff = o.res_choff; }
-            a.C = o.cin; a.B = n; a.H = Ho; a.W = Wo; a.act = o.act;
-            a.h2 = h2 ? 1 : 0; a.out_f32 = (h2 && head) ? 1 : 0; a.ovf_flag = m->d_ovf.get();
-            pr = prof_begin(m, s, (*pi)++, o.kind, 3, 2.0 * n * Ho * Wo * (double)o.cin * 9.0);
-            if (pr) { pr->M = n * Ho * Wo; pr->cout = o.cout; pr->cin = o.cin; pr->stride = 1; pr->res = o.res_buf >= 0; }
-            r = launch_dwconv3(a, s);
-        } else if (o.kind == PA_OP_PSA_ATTN) {
-            const bool h2 = m->d.dtype == PA_DTYPE_H2;
-            const bool head = is_head_buf(m->d, o.out_buf);
-            AttnArgs a{};
-            a.heads = o.stride; a.kd = o.ksize; a.hd = o.npad;
-            a.qkv = L.bptr[o.in_buf]; a.cs = m->bufs[o.in_buf].channels;
-            a.q_choff = o.in_choff; a.k_choff = o.in_choff + a.heads * a.kd; a.v_choff = o.in_choff + 2 * a.heads * a.kd;
-            a.out = L.bptr[o.out_buf]; a.out_cs = ob.channels; a.out_choff = o.out_choff;
-            a.N = Ho * Wo; a.B = n; a.scale = (float)(1.0 / std::sqrt((double)a.kd));
-            a.h2 = h2 ? 1 : 0; a.out_f32 = (h2 && head) ? 1 : 0; a.ovf_flag = m->d_ovf.get();
-            pr = prof_begin(m, s, (*pi)++, o.kind, 0, 2.0 * n * (double)a.heads * a.N * (double)a.N * (a.kd + a.hd));
-            if (pr) { pr->M = n * a.N; pr->cout = o.cout; pr->cin = o.cin; pr->stride = a.heads; }
-            r = launch_psa_attn(a, s);
+    if (plan_steps(m, L, n)) return 1;
+    for (const Step& st : L.steps) {
+        if (skip_tail && st.tail) continue;          // the heads' last convs run inside the fused head tail (run_post)
+        ProfRec* pr = prof_begin(m, s, (*pi)++, st.kind, st.ksize, st.flops);
+        if (pr) {
+            pr->M = st.M; pr->cout = st.cout; pr->cin = st.cin; pr->stride = st.stride; pr->mf = st.mf; pr->nf = st.nf; pr->res = st.res;
+            pr->tile = st.ran.tile; pr->family = st.ran.family;
         }
+        const bool timeline = st.kind == PA_OP_CONV && e->t.timeline && !e->timeline_path.empty() && st.ran.tile == st.requested;
+        const hipError_t r = timeline ? launch_conv_timeline(m, st, s) : launch_step(st, st.conv, s);
         prof_end(s, pr);
-        if (r != hipSuccess) PA_FAIL(e, "op %zu (kind %d) launch failed: %s", i, o.kind, hipGetErrorString(r));
+        if (r != hipSuccess && st.n_ops == 2) PA_FAIL(e, "fused stem + layer 1 launch failed: %s", hipGetErrorString(r));
+        if (r != hipSuccess) PA_FAIL(e, "op %d (kind %d) launch failed: %s", st.op, st.kind, hipGetErrorString(r));
     }
     return 0;
 }
@@ -621,19 +494,8 @@ static int ensure_operand_copies(pa_model* m) {
         }
     }
     if (m->wr_off.empty()) {
-        std::vector<long long> off(m->ops.size(), -1);
-        size_t total = 0;
-        for (size_t i = 0; i < m->ops.size(); ++i) {
-            const pa_op_desc& o = m->ops[i];
-            if (o.kind == PA_OP_STEM && m->stem_fuse[i] && (o.cout == 16 || o.cout == 32 || o.cout == 48)) {
-                off[i] = (long long)total;             // the fused stem + layer-1 kernel's stem operand block
-                total += (stem_l1_operand_bytes(o.cout) + 2047) / 2048 * 2048;
-                continue;
-            }
-            if (o.kind != PA_OP_CONV || !conv_wants_operand_copy(o.ksize, o.stride, o.cin, (o.flags & PA_CONV_W_SINGLE) != 0)) continue;
-            off[i] = (long long)total;
-            total += conv_h2r_copy_bytes(o.npad / 16, o.cin, o.ksize);
-        }
+        std::vector<long long> off;
+        const size_t total = operand_copy_offsets(m->d, m->stem_fuse, off);
         if (total) {
             PA_HIP(e, m->d_wr.fit(total + 8192, total + 8192));          // the last chunk's look-ahead reads run 4 KB past a fragment
             PA_HIP(e, hipMemsetAsync(m->d_wr.get() + total, 0, 8192, e->main_stream()));
@@ -656,11 +518,14 @@ static int ensure_operand_copies(pa_model* m) {
 }
 
 // run_ops, or (tuning "graph", not while profiling) the replay of its capture for this batch size: the op list of
-// an n-scale graph is ~100 launches of 10-40 us each, where per-launch host work shows
-int run_graph(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
+// an n-scale graph is ~100 launches of 10-40 us each, where per-launch host work shows.  A captured graph bakes the skip_tail of
+// its capture.  That is sound: skip_tail is the caller's head_fused, which for a planned model changes only with tuning fuse_head
+// (every pa_engine_set_tuning bumps the epoch, and the graphs of an older epoch are destroyed below) or with profiling / timeline,
+// under which no graph is replayed.
+int run_graph(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi, bool skip_tail) {
     pa_engine* e = m->e;
     if (ensure_operand_copies(m)) return 1;
-    if (!e->t.graph || e->profiling || e->t.timeline) return run_ops(m, L, s, n, pi);
+    if (!e->t.graph || e->profiling || e->t.timeline) return run_ops(m, L, s, n, pi, skip_tail);
     if (m->graph_epoch != e->tuning_epoch) {            // kernel choice may have changed since the capture
         PA_HIP(e, hipStreamSynchronize(e->main_stream_wait_only()));
         PA_HIP(e, e->sync_lanes());
@@ -673,7 +538,7 @@ int run_graph(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi) {
         hipGraphExec_t ge = nullptr;
         PA_HIP(e, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
         size_t dummy = 0;
-        const int rc = run_ops(m, L, s, n, &dummy);
+        const int rc = run_ops(m, L, s, n, &dummy, skip_tail);
         const hipError_t r = hipStreamEndCapture(s, &g);
         if (rc) { if (g) hipGraphDestroy(g); return 1; }
         if (r != hipSuccess) PA_FAIL(e, "hipStreamEndCapture: %s", hipGetErrorString(r));

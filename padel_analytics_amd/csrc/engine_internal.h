@@ -1,5 +1,6 @@
 // Shared by the engine's translation units (engine*.cpp); not part of the C-ABI (include/padel_hip.h).
-//   engine.cpp           engine and model lifecycle, tuning, memory and timer calls, the arena, run_ops / run_graph, profile text
+//   engine.cpp           engine and model lifecycle, tuning, memory and timer calls, the arena, the replay of a step list (run_ops /
+//                        run_graph), profile text
 //   engine_pre.cpp       preprocessing shared by the model families: frame staging, the Pillow resample, YUV -> BGR
 //   engine_yolo.cpp      YOLO plan (per lane), prepare, enqueue, post-processing, tickets and their lanes, read-backs
 //   engine_tracknet.cpp  pa_tracknet_infer and the ball session
@@ -10,10 +11,12 @@
 //   engine_comm.cpp      RCCL
 //   device_mem.h         DevMem<T> / PinMem<T>: the owner of every device (page-locked host) allocation of these files; the
 //                        hooks it allocates through, and the count of live bytes, are engine.cpp's
-// What is decided about a graph on the host alone lives in graph_plan.cpp, which kernel runs a conv in conv_select.cpp.
+// What is decided about a graph on the host alone lives in graph_plan.cpp, which kernel runs a conv in conv_select.cpp, what one
+// replay launches and with which arguments (struct Tuning, struct Step) in launch_plan.cpp.
 #pragma once
 #include "../../include/padel_hip.h"
 #include "graph_plan.h"
+#include "launch_plan.h"
 #include "lane_plan.h"
 #include "device_mem.h"
 #include "kernels.h"
@@ -29,32 +32,6 @@
 #include <vector>
 
 using namespace padel;
-
-// Tuning knobs: read from the environment ONCE at pa_engine_create (PADEL_CONV_IMPL=tap|bx3, PADEL_CONV_VARIANT,
-// PADEL_CONV_TUNE, PADEL_CONV_TAP_PD, PADEL_GRAPH, PADEL_ALIAS, PADEL_LANES), changed afterwards only through
-// pa_engine_set_tuning — the replay loop never touches getenv.
-struct Tuning {
-    int impl = 2;        // 2 (default): bf16x3 kernels — fp32 values split exactly into 3 bf16, 6 products on the bf16
-                         // pipe, fp32 accumulate (admitted by the same parity criteria as the fp32-MFMA kernels);
-                         // 0: tap-unrolled LDS-DMA fp32-MFMA kernels, 1: LDS kernel (their bitwise cross-check)
-    int variant = -1;    // forced tile id (tests / tools), -1: per-layer heuristic
-    int tune = 1;        // bit 0: s_setprio around MFMA clusters
-    int tap_pd = 2;      // prefetch distance of the 1x1 tap kernel
-    int graph = 0;       // 1: replay the op list of a (model, batch) from a captured hipGraph
-    int timeline = 0;    // 1: 3x3 tap launches of the 64x96 tile run the s_memtime-instrumented instantiation
-    int alias = 1;       // 1: activation buffers share one arena by liveness, 0: disjoint ranges
-    int fuse_stem = 1;   // 1: h2 YOLOv8 graphs run model.0 (stem) + model.1 (3x3 stride 2) as ONE kernel (stem_l1_h2.hip; default since round 4, 0 = two kernels)
-    int w_single = 1;    // 1 (default): h2 convs whose packed weights have an all-zero m plane (PA_CONV_W_SINGLE) skip the wm x ah product;
-                         // 0 (tests): all three products everywhere — bitwise the same results
-    int fuse_sppf = 1;   // 1: h2 graphs run the three chained 5x5 max-pools of SPPF as ONE kernel (sppf_h2_kernel: keys in LDS, separable passes); 0 = three launches.  Bitwise the same maps
-    int fuse_head = 1;   // 1: h2 Detect / Pose models whose plan found the head tail (graph_plan.h: HeadTail) run the heads' last 1x1 convs and the
-                         // decode as ONE kernel (head_tail_h2.hip) and never write the head maps; 0: the convs, then decode_kernel.  Bitwise the same
-                         // detections; off while profiling or collecting a timeline (the profile keeps its rows)
-    int lanes = 2;       // 2: a YOLO model whose submit finds its last ticket still in flight gets a second lane (struct Lane) and alternate
-                         // tickets run on two streams; 1: everything on lane 0.  Bitwise the same results
-    int fold_up = 1;     // 1: an nn.Upsample(2) whose only reader is a bf16x3 1x1 conv is never materialised (the conv
-                         // fetches those channels at [y >> 1][x >> 1] of the coarse map), 0: run the upsample kernel
-};
 
 struct pa_comm;
 struct JpegScratch;
@@ -142,7 +119,13 @@ struct ResamplePlan {
 // A lane: everything ONE in-flight YOLO batch writes on the device, so that two batches of a model can run at the same time on two
 // streams.  Lane 0 is the plan's (every model has it; TrackNet / ResNet models use nothing else and run it on the main stream);
 // lane 1 of a YOLO model is allocated by the first pa_yolo_submit that finds lane 0's ticket still in flight (lane_plan.h).
-// Audit of every device pointer plan_yolo, plan_buffers, run_ops, run_post, head_tail_convs and run_tail_ops hand to a kernel:
+// Audit of every device pointer plan_yolo, plan_buffers, run_ops, run_post, head_tail_convs and run_tail_ops hand to a kernel.  What
+// the op list's launches get is made from the base pointers of ONE struct, PlanPointers (launch_plan.h; plan_pointers in engine.cpp
+// fills it per replay), and every one of them stands before the first replay of a plan and until free_plan or the model's end: the
+// arena / bptr and d_fc are plan_buffers', d_netin is plan_yolo's / pa_resnet_infer's plan, released by free_lane alone; d_w and d_ovf
+// are pa_model_create's, e->zeros pa_engine_create's; d_wr is allocated once by ensure_operand_copies, which run_graph calls in front
+// of every replay.  A weight broadcast rewrites d_w and d_wr in place (wr_valid goes false, the copies are rebuilt into the same
+// block).  A step list is rebuilt per replay and kept by no one but the lane's own vector, so it holds no pointer past these.
 //   per lane (written per batch): arena / bptr (every activation, in / in2 / out / res of the convs, the head-tail convs' inputs,
 //     lv[].buf), d_fc, d_stage, d_netin, the Pillow resample temporary (lane 0: ResamplePlan::d_tmp, lane 1: d_rs_tmp), d_cand,
 //     d_cidx, d_ccnt, d_keys, d_order, d_supp, d_oboxes, d_okpts, d_ocnt, the timeline scratch (allocated per launch), and the
@@ -167,6 +150,7 @@ struct Lane {
     DevMem<float> d_cand; DevMem<int32_t> d_cidx, d_ccnt;
     DevMem<uint64_t> d_keys; DevMem<int32_t> d_order; DevMem<uint8_t> d_supp;
     DevMem<float> d_oboxes, d_okpts; DevMem<int32_t> d_ocnt;
+    std::vector<Step> steps;               // the launches of the replay being enqueued (build_steps): rebuilt per call, capacity kept
     std::map<int, hipGraphExec_t> graphs;  // op-list replay per batch size (tuning "graph")
     DevMem<uint8_t> d_rs_tmp;              // lane 1: its own temporary between the resample passes (lane 0 uses the plan's)
     LaneState st;                          // pick_lane's view
@@ -182,10 +166,8 @@ struct pa_model {
     std::vector<pa_buf_desc> bufs;
     std::vector<pa_op_desc> ops;
     std::vector<int> fold_src;             // conv op i -> index of the upsample op it can absorb (-1: none), find_upsample_folds
-    std::vector<int> fold_dst;             // upsample op j -> its absorbing conv (-1: none)
     std::vector<char> stem_fuse;           // op i -> stem_fusable (the stem and the stride-2 3x3 behind it can run as one kernel)
     HeadTail tail;                         // the heads' last 1x1 convs, if the graph ends the way find_head_tail wants it
-    std::vector<char> tail_op;             // op i is one of them
     DevMem<float> d_w;
     size_t n_w = 0;
     // h2 models: the h planes of the two-product stride-1 3x3 convs once more in MFMA operand order (conv_patch_h2r.hip), built on
@@ -242,10 +224,11 @@ void free_plan(pa_model* m);                         // both lanes; the caller h
 // the arena of one lane of a model whose net_h x net_w is set: allocation, memsets (on s), bptr, d_fc
 int plan_buffers(pa_model* m, Lane& L, int batch, hipStream_t s);
 void free_lane(Lane& L);                             // the graphs, then `L = Lane{}` with the stream kept; drains nothing: the CALLER has waited for the lane's stream
-// run_ops on lane L and stream s, or (tuning "graph", not while profiling) the replay of its capture for this batch size
-int run_graph(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi);
+// run_ops on lane L and stream s, or (tuning "graph", not while profiling) the replay of its capture for this batch size.
+// skip_tail: the steps marked `tail` are left out (the caller's head_fused: its run_post launches the fused kernel instead)
+int run_graph(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi, bool skip_tail);
 // The fused head tail applies to the next replay of a planned model: tuning fuse_head, an h2 model whose plan found the tail, a
-// shape head_tail_h2.hip has, no profiling, no timeline.  run_ops then skips the tail convs and run_post launches the fused kernel.
+// shape head_tail_h2.hip has, no profiling, no timeline.  Evaluated once per call (yolo_enqueue) and handed to run_graph and run_post.
 bool head_fused(const pa_model* m);
 void head_tail_convs(const pa_model* m, const Lane& L, HeadTailArgs& a);      // a.cv and a.w_single of a planned model (a.d: the caller's)
 int run_tail_ops(pa_model* m, Lane& L, hipStream_t s, int n);   // the tail convs alone, from their inputs (still live): the head maps of the lane's last call

@@ -52,7 +52,7 @@ int pa_resnet_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, int
         }
         prof_end(s, pr);
         if (r != hipSuccess) PA_FAIL(e, "preprocess launch failed: %s", hipGetErrorString(r));
-        if (run_graph(m, m->ln[0], s, nb, &pi)) return 1;
+        if (run_graph(m, m->ln[0], s, nb, &pi, false)) return 1;
         if (m->fc_nout) {
             const size_t row = (size_t)m->fc_nout * sizeof(float);
             PA_HIP(e, hipMemcpyAsync(out_xy + (size_t)c0 * m->fc_nout, m->ln[0].d_fc.get() + (size_t)m->p_batch * kGapFcMaxOut, nb * row, hipMemcpyDeviceToHost, s));

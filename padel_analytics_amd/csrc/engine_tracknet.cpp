@@ -45,7 +45,7 @@ int pa_tracknet_infer(pa_model* m, const float* x, int n, int h, int w, int x_on
         } else
         PA_HIP(e, hipMemcpyAsync(m->ln[0].bptr[0], xs, in_bytes,
                                  x_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-        if (run_graph(m, m->ln[0], s, nb, &pi)) return 1;
+        if (run_graph(m, m->ln[0], s, nb, &pi, false)) return 1;
         const size_t ohw = (size_t)(h >> m->bufs[ob].level) * (w >> m->bufs[ob].level);
         const size_t out_bytes = (size_t)nb * ohw * cout * sizeof(float);
         PA_HIP(e, hipMemcpyAsync(out + (size_t)c0 * ohw * cout, m->ln[0].bptr[ob], out_bytes,
@@ -214,7 +214,7 @@ int pa_ball_feed(pa_ball* b, const uint8_t* frames, int n, int on_device, int fl
             aa.out_f16 = m->d.dtype == PA_DTYPE_F16 ? 1 : m->d.dtype == PA_DTYPE_H2 ? 2 : 0;
             hipError_t r = launch_ball_assemble(aa, s);
             if (r != hipSuccess) PA_FAIL(e, "ball assemble launch failed: %s", hipGetErrorString(r));
-            if (run_graph(m, m->ln[0], s, nw, &prof_n)) return 1;
+            if (run_graph(m, m->ln[0], s, nw, &prof_n, false)) return 1;
             PA_HIP(e, hipMemcpyAsync(b->d_Y.get() + (size_t)7 * HW * b->cs, m->ln[0].bptr[m->d.head_buf[0]],
                                      (size_t)nw * HW * b->cs * sizeof(float), hipMemcpyDeviceToDevice, s));
             for (int i = 0; i < nw; ++i) {             // frame g = g_lo + i: rows i .. i+7 (row r <-> window g_lo - 7 + r)

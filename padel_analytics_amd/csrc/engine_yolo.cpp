@@ -211,9 +211,9 @@ static int yolo_enqueue(pa_model* m, int li, const uint8_t* src, int nb, int h, 
     }
     prof_end(s, pr);
     if (r != hipSuccess) PA_FAIL(e, "preprocess launch failed: %s", hipGetErrorString(r));
-    // ---- network (without the heads' last convs when the fused head tail runs them: the same decision in run_ops)
+    // ---- network (without the heads' last convs when the fused head tail runs them: decided once, here)
     const bool fused = head_fused(m);
-    if (run_graph(m, L, s, nb, &pi)) return 1;
+    if (run_graph(m, L, s, nb, &pi, fused)) return 1;
     // ---- decode + NMS + results back to the caller's arrays
     return run_post(m, L, p, nb, oh, ow, &pi, out_boxes, m->d.nk ? out_kpts : nullptr, out_counts, ovf_slot, fused);
 }

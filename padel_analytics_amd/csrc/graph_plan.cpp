@@ -142,9 +142,9 @@ int validate_desc(const pa_model_desc* d, size_t n_floats, std::string& err) {
 // (coarse slice S[so, so + c) -> fine slice X[xo, xo + c)) is absorbed by conv i when: i is a stride-1 conv of an h2 model or
 // with bf16x3 weights — 1x1 (YOLOv8's FPN joins) or 3x3 with cin % 32 == 0 (TrackNet's decoder blocks) — whose input slice
 // starts at X[xo] and covers the c channels (c % 32 == 0), nothing else reads those channels of X, and nothing overwrites the
-// source slice between j and i.  Whether the absorption is USED is decided per launch in conv_launch_args (tuning fold_up; the
-// coarse map is attached and kept where resolve_conv names a kernel that reads it — the 1x1 tap tiles, and for a 3x3
-// consumer the patch kernel); the upsample op asks the same function, so both make one decision.  The liveness plan keeps S
+// source slice between j and i.  Whether the absorption is USED is decided per replay by the step builder (launch_plan.cpp:
+// request_conv under tuning fold_up; the coarse map is attached and kept where resolve_conv names a kernel that reads it — the
+// 1x1 tap tiles, and for a 3x3 consumer the patch kernel); the upsample op is a step iff that conv did not keep it: one decision.  The liveness plan keeps S
 // alive until i either way.
 void find_upsample_folds(const pa_model_desc& d, std::vector<int>& fold_src, std::vector<int>& fold_dst) {
     const int nops = d.n_ops;

@@ -88,9 +88,8 @@ const char* conv_family_name(ConvFamily f);
 // false: the layer or the tile is not covered.  With a.in2 set (an absorbed nn.Upsample(2); h2 and bf16x3) only kernels that read it resolve.
 bool resolve_conv(int path, const ConvArgs& a, int requested, ConvLaunched* out, ConvFamily* family = nullptr);
 int conv_timeline_words(const ConvLaunched& k, int ksize);      // u64 words per record of the timeline instantiation of kernel `k` on a ksize layer; 0: it has none
-// resolve_conv, then the launcher of the family it names (conv_tap.hip); hipErrorNotSupported: not resolved.  `ran` is filled on
-// success when the caller passes one: one host-side store per launch
-hipError_t launch_conv(int path, const ConvArgs& a, int variant, hipStream_t s, ConvLaunched* ran = nullptr);
+// the launcher of the family resolve_conv named, with the tile it named (conv_tap.hip)
+hipError_t launch_conv_family(ConvFamily f, const ConvArgs& a, int tile, hipStream_t s);
 // conv_tap.hip reads up to 128 B past the last chunk of a pixel / weight row, so every buffer a conv reads is
 // allocated with kConvReadSlack extra bytes
 constexpr size_t kConvReadSlack = 512;
@@ -138,11 +137,13 @@ struct StemArgs {
 };
 hipError_t launch_stem(const StemArgs& a, hipStream_t s);
 struct ConvArgs;
-bool stem_l1_h2_supported(const StemArgs& st, const ConvArgs& cv);        // stem_l1_h2.hip: stem + the 3x3 stride-2 conv behind it, one kernel
+// stem_l1_h2.hip: stem + the 3x3 stride-2 conv behind it, one kernel.  Whether it covers a pair reads the two argument structs and
+// nothing else (launch_plan.cpp: host code, asked where the launch is planned and once more by the launcher)
+bool stem_l1_h2_supported(const StemArgs& st, const ConvArgs& cv);
 hipError_t launch_stem_l1_h2(const StemArgs& st, const ConvArgs& cv, hipStream_t s);
 // the stem operand block of its register-weights instantiations (cout = 16 / 32 / 48): per 16-channel fragment 2 KB [h | m][lane][16 B]
 // of w / 255 row-scaled and split into fp16 pairs, then the cout inverse row scales.  Built from the blob's [cout][27] stem weights
-size_t stem_l1_operand_bytes(int cout);
+size_t stem_l1_operand_bytes(int cout);                                   // launch_plan.cpp
 hipError_t launch_stem_l1_operands(const float* w, int cout, void* blk, hipStream_t s);
 
 // SPPF: three chained MaxPool2d(5,1,2) of slice [choff, choff+c) written to the next three slices

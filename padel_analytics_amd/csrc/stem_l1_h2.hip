@@ -557,16 +557,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
 #endif
 }
 
-// stem (h2 output, c = 16 / 32 / 48 channels) followed by a 3x3 stride-2 conv over exactly those channels with 2c outputs
-bool stem_l1_h2_supported(const StemArgs& st, const ConvArgs& a) {
-    const int c = st.cout;
-    return st.out_f16 == 2 && (c == 16 || c == 32 || c == 48) && a.ksize == 3 && a.stride == 2 && a.cin == c && a.n16 * 16 == 2 * c &&
-           a.cout == 2 * c && a.H == st.Ho && a.W == st.Wo && a.Ho == (st.Ho + 1) / 2 && a.Wo == (st.Wo + 1) / 2 && a.w && a.oscale &&
-           a.ovf_flag && !a.in2 && !a.res && (st.Ho & 1) == 0 && (st.Wo & 1) == 0;
-}
-
-size_t stem_l1_operand_bytes(int cout) { return (size_t)(cout / 16) * 2048 + (size_t)cout * sizeof(float); }
-
+// (what the kernel covers — stem_l1_h2_supported — and the size of its operand block are host code: launch_plan.cpp)
 hipError_t launch_stem_l1_operands(const float* w, int cout, void* blk, hipStream_t s) {
     if (cout != 16 && cout != 32 && cout != 48) return hipErrorNotSupported;
     hipLaunchKernelGGL(stem_l1_operands_kernel, dim3(1), dim3(64), 0, s, w, cout / 16, reinterpret_cast<char*>(blk));

@@ -12,12 +12,15 @@
 //     chosen     the chooser's tile (always computed, without in2 — as the engine does)
 //     resolved   the tile that runs after every fall-through, -1: not supported;  family: its tag, "-": none
 //     bm bn      conv_tile_shape of the REQUESTED tile (0 0: not a tile of the path)
-//     copy       conv_wants_operand_copy;  absorbed: the upsample is read through in2 (the engine's rule: attach, resolve, detach if nothing reads it)
+//     copy       conv_wants_operand_copy;  absorbed: the upsample is read through in2 (request_conv, the function the engine's step builder uses)
 //
 // -DCONV_SELECT_PARENT: the same main against a commit that predates conv_select.cpp (its conv .hip objects + libamdhip64): only
 // the four choosers exist there, `copy` is that commit's own condition (its engine.cpp: ensure_operand_copies; the engine has since been split, csrc/engine_internal.h), the other columns print
 // as "-".  This is how tests/golden/conv_tile_choices.json was recorded.
 #include "kernels.h"
+#ifndef CONV_SELECT_PARENT
+#include "launch_plan.h"
+#endif
 
 #include <cstdio>
 #include <cstring>
@@ -56,16 +59,11 @@ int main() {
         printf("%d - - - - %d -\n", chosen, (int)copy);
 #else
         const int p = h2 ? CONV_PATH_H2 : f16 ? CONV_PATH_F16 : bx3 ? CONV_PATH_BX3 : CONV_PATH_TAP;
-        const int lv = req >= 0 ? req : chosen;
-        if (up_c > 0 && (h2 || bx3)) {
-            a.in2 = dummy; a.in2_cs = up_c; a.up_c = up_c;
-            if (!resolve_conv(p, a, lv, nullptr)) { a.in2 = nullptr; a.in2_cs = a.up_c = 0; }
-        }
-        ConvLaunched r{-1, "-"};
-        if (!resolve_conv(p, a, lv, &r)) r = ConvLaunched{-1, "-"};
+        const ConvUp up{dummy, up_c, 0, up_c};
+        const ConvRequest r = request_conv(p, a, req, (up_c > 0 && (h2 || bx3)) ? &up : nullptr);          // the engine's own rule (launch_plan.cpp)
         int bm = 0, bn = 0;
-        conv_tile_shape(p, lv, &bm, &bn);
-        printf("%d %d %s %d %d %d %d\n", chosen, r.tile, r.family, bm, bn, (int)copy, a.in2 ? 1 : 0);
+        conv_tile_shape(p, r.tile, &bm, &bn);
+        printf("%d %d %s %d %d %d %d\n", chosen, r.ran.tile, r.resolved ? r.ran.family : "-", bm, bn, (int)copy, a.in2 ? 1 : 0);
 #endif
     }
     return 0;

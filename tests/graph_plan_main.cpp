@@ -25,6 +25,8 @@
 using namespace padel;
 #endif
 
+#include "graph_desc_read.h"
+
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -39,24 +41,7 @@ int main() {
     std::string err;
     while (scanf("%31s", cmd) == 1) {
         if (!strcmp(cmd, "graph")) {
-            int nb = 0, no = 0;
-            if (scanf("%d %d", &nb, &no) != 2 || nb < 0 || no < 0) return 2;
-            d = pa_model_desc{};
-            if (scanf("%d %d %d %d %d %d %d %d %d %lld", &d.task, &d.dtype, &d.nc, &d.nk, &d.kpt_dim, &d.head_buf[0], &d.head_buf[1], &d.head_buf[2],
-                      &d.in_channels, &n_floats) != 10)
-                return 2;
-            bufs.assign(nb, pa_buf_desc{});
-            ops.assign(no, pa_op_desc{});
-            for (auto& b : bufs) if (scanf("%d %d", &b.level, &b.channels) != 2) return 2;
-            for (auto& o : ops) {
-                long long w_off = 0, b_off = 0;
-                if (scanf("%d %d %d %d %d %d %d %d %d %d %d %d %d %d %lld %lld %d %d", &o.kind, &o.in_buf, &o.in_choff, &o.cin, &o.out_buf, &o.out_choff,
-                          &o.cout, &o.ksize, &o.stride, &o.act, &o.res_buf, &o.res_choff, &o.npad, &o.reserved, &w_off, &b_off, &o.flags, &o.pad_) != 18)
-                    return 2;
-                o.w_off = w_off; o.b_off = b_off;
-            }
-            d.n_bufs = nb; d.bufs = bufs.data();
-            d.n_ops = no; d.ops = ops.data();
+            if (!read_graph(d, bufs, ops, n_floats)) return 2;
         } else if (!strcmp(cmd, "validate")) {
             if (validate_desc(&d, (size_t)n_floats, err)) printf("refused: %s\n", err.c_str());
             else printf("ok\n");

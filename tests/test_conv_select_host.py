@@ -34,7 +34,7 @@ def harness(tmp_path_factory):
     exe = tmp_path_factory.mktemp("conv_select") / "conv_select_main"
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     subprocess.run(["g++", "-O2", "-ffp-contract=off", "-std=c++17", "-Wall", "-D__HIP_PLATFORM_AMD__", f"-I{rocm}/include", f"-I{CSRC}",
-                    str(ROOT / "tests" / "conv_select_main.cpp"), str(CSRC / "conv_select.cpp"), "-o", str(exe)], check=True)
+                    str(ROOT / "tests" / "conv_select_main.cpp"), str(CSRC / "conv_select.cpp"), str(CSRC / "launch_plan.cpp"), "-o", str(exe)], check=True)
     return exe
 
 
