@@ -257,6 +257,36 @@ int pa_render_last_path(pa_engine* eng);
  * code outside the font                                                                                                   */
 int pa_glyph_rows(int code, uint8_t rows[7]);
 
+/* ---- frame statistics: is this the court camera?  (csrc/frame_activity.hip; the readable twin is activity.frame_activity_host) ----
+ * All integer.  The luma of a BGR pixel is  Y = (29 B + 150 G + 77 R + 128) >> 8  (0 .. 255).
+ * For frames f_0 .. f_{n-1} of h x w packed BGR (frame i at frames_bgr_dev + i * h * w * 3), a reference image ref of the same size,
+ * an optional frame prev, a rectangle roi = {x0, y0, x1, y1}, half-open, 0 <= x0 < x1 <= w, 0 <= y0 < y1 <= h (NULL: the whole
+ * frame) and a threshold tau in 0 .. 255, three uint64 per frame, summed over the pixels of roi:
+ *     out[3 i + 0] = sad_ref  = sum |Y(f_i) - Y(ref)|
+ *     out[3 i + 1] = changed  = #{ |Y(f_i) - Y(ref)| > tau }          (strict)
+ *     out[3 i + 2] = sad_prev = sum |Y(f_i) - Y(f_{i-1})|             f_{-1} = prev if given, otherwise sad_prev of frame 0 is 0
+ * The numbers of a frame are exact and depend on that frame, ref and its predecessor alone: not on n, on the frame's place in the
+ * batch, on the alignment of a pointer or on how the launch is shaped (workgroups write partial sums to a slab, a second kernel adds
+ * them: no atomics).  out_u64 is HOST memory, n x 3; rows beyond n are not touched.
+ * Limits (PA_ACTIVITY_MAX_SIDE, PA_ACTIVITY_MAX_FRAMES): h and w at most 16384 — a workgroup's band of at most 16384 pixels keeps
+ * every 32-bit partial sum below 2^23 — and n at most 65535, the second grid dimension.
+ * pa_frame_activity_check: host only (no engine, no GPU): NULL if pa_frame_activity would accept these arguments, else the reason,
+ * a string of static storage in this thread, valid until its next call.  One reason each for: n out of range; h or w out of
+ * range; a roi that is empty or leaves the frame; tau outside 0 .. 255.
+ * pa_frame_activity: SYNCHRONOUS, on the engine's compute stream, so ordered behind whatever produced the frames there.  Refuses
+ * what the check refuses (and a NULL pointer), launching nothing, the reason in pa_last_error.  The slab is an engine-owned buffer
+ * grown on demand and freed with the engine.                                                                                 */
+#define PA_ACTIVITY_MAX_SIDE 16384
+#define PA_ACTIVITY_MAX_FRAMES 65535
+const char* pa_frame_activity_check(int n, int h, int w, const int32_t* roi, int tau);
+int pa_frame_activity(pa_engine* eng, const uint8_t* frames_bgr_dev, int n, int h, int w, const uint8_t* ref_bgr_dev,
+                      const uint8_t* prev_bgr_dev_or_null, const int32_t* roi_or_null, int tau, uint64_t* out_u64);
+/* the per-pixel, per-channel median of n BGR frames in HBM (np.median(frames, 0).astype(uint8): an even n gives (a + b) >> 1 of
+ * the two middle values), n <= 65535, h and w within PA_ACTIVITY_MAX_SIDE -> h x w x 3 BGR at out_bgr_dev (HBM, not overlapping
+ * the frames).  The kernel of pa_ball_background_from_frames (which writes RGB), reachable without a ball session.  SYNCHRONOUS
+ * on the compute stream.                                                                                                      */
+int pa_frames_median(pa_engine* eng, const uint8_t* frames_bgr_dev, int n, int h, int w, uint8_t* out_bgr_dev);
+
 /* ---- frames to a file: the YUV 4:2:0 bytes pa_render writes -> one baseline JPEG per frame (Motion-JPEG; csrc/jpeg_encode.hip) ----
  * The bit stream is specified here; its constants are csrc/jpeg_tables.h (host and device), its readable twin
  * padel_analytics_amd/mjpeg.py (encode_host), which produces the same bytes.

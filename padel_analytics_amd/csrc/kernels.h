@@ -372,7 +372,22 @@ struct BallLocateArgs {
     int H, W;
 };
 hipError_t launch_ball_locate(const BallLocateArgs& a, int nout, hipStream_t s);
-// K11: per-byte median over N BGR frames -> RGB background (np.median + uint8 truncation)
-hipError_t launch_median(const uint8_t* frames, int N, long long frame_bytes, uint8_t* out_rgb, hipStream_t s);
+// K11: per-byte median over N BGR frames -> RGB background (np.median + uint8 truncation); keep_bgr: the output stays BGR
+hipError_t launch_median(const uint8_t* frames, int N, long long frame_bytes, uint8_t* out_rgb, hipStream_t s, bool keep_bgr = false);
+
+// Frame statistics against a reference image and the previous frame (frame_activity.hip; the specification: include/padel_hip.h).
+// The caller (pa_frame_activity) has checked the arguments (activity_check.cpp) and chosen band_rows.
+struct ActivityArgs {
+    const uint8_t* frames;   // n packed BGR frames
+    const uint8_t* ref;      // one frame
+    const uint8_t* prev;     // the frame before frames[0], or nullptr
+    int n, h, w;
+    int x0, y0, x1, y1;      // the roi
+    int tau;
+    int band_rows, bands;    // workgroup (band, frame) takes roi rows [y0 + band * band_rows, ...): activity_check.h
+    uint32_t* slab;          // [n][bands][3] partial sums: sad_ref, changed, sad_prev
+    unsigned long long* out; // [n][3]
+};
+hipError_t launch_frame_activity(const ActivityArgs& a, hipStream_t s);
 
 }  // namespace padel

@@ -207,13 +207,14 @@ hipError_t launch_ball_locate(const BallLocateArgs& a, int nout, hipStream_t s) 
 // out [bin][thread] so that neighbouring threads touch neighbouring addresses; frames are read once,
 // coalesced (consecutive threads = consecutive bytes).  np.median semantics: odd N -> the middle element;
 // even N -> mean of the two middle elements computed in float64, and the uint8 cast truncates -> (a+b)>>1.
-// Input frames are BGR, the output is RGB (channel 2-c), like the reference's cvtColor before the median.
+// Input frames are BGR, the output is RGB (channel 2-c), like the reference's cvtColor before the median; with keep_bgr it stays
+// BGR (pa_frames_median).
 #define MED_THREADS 128
 
 namespace padel {
 
 __global__ void __launch_bounds__(MED_THREADS) median_kernel(const uint8_t* frames, int N, long long frame_bytes,
-                                                              uint8_t* out_rgb) {
+                                                              uint8_t* out_rgb, int keep_bgr) {
     __shared__ unsigned short hist[256 * MED_THREADS];
     const int t = threadIdx.x;
     const long long e = (long long)blockIdx.x * MED_THREADS + t;
@@ -232,12 +233,12 @@ __global__ void __launch_bounds__(MED_THREADS) median_kernel(const uint8_t* fram
     }
     const long long pix = e / 3;
     const int c = (int)(e - pix * 3);
-    out_rgb[pix * 3 + (2 - c)] = (uint8_t)((lo + hi) >> 1);
+    out_rgb[pix * 3 + (keep_bgr ? c : 2 - c)] = (uint8_t)((lo + hi) >> 1);
 }
 
-hipError_t launch_median(const uint8_t* frames, int N, long long frame_bytes, uint8_t* out_rgb, hipStream_t s) {
+hipError_t launch_median(const uint8_t* frames, int N, long long frame_bytes, uint8_t* out_rgb, hipStream_t s, bool keep_bgr) {
     const long long blocks = (frame_bytes + MED_THREADS - 1) / MED_THREADS;
-    hipLaunchKernelGGL(median_kernel, dim3((unsigned)blocks), dim3(MED_THREADS), 0, s, frames, N, frame_bytes, out_rgb);
+    hipLaunchKernelGGL(median_kernel, dim3((unsigned)blocks), dim3(MED_THREADS), 0, s, frames, N, frame_bytes, out_rgb, keep_bgr ? 1 : 0);
     return hipGetLastError();
 }
 

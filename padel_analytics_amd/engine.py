@@ -123,6 +123,7 @@ ABI_SYMBOLS = [
     "pa_jpeg_parse", "pa_jpeg_decode", "pa_jpeg_decode_last_path", "pa_jpeg_decode_last_times",
     "pa_yolo_last_post_path", "pa_jpeg_decode_set_split", "pa_jpeg_decode_last_split",
     "pa_model_lanes_allocated", "pa_model_last_lane", "pa_yolo_resample_passes", "pa_device_bytes_live",
+    "pa_frame_activity", "pa_frame_activity_check", "pa_frames_median",
 ]
 
 
@@ -229,6 +230,10 @@ def load_library():
     lib.pa_jpeg_decode_last_times.argtypes = [vp, vp]
     lib.pa_jpeg_decode_set_split.argtypes = [vp, C.c_int64, i32]
     lib.pa_jpeg_decode_last_split.argtypes = [vp, vp]
+    lib.pa_frame_activity_check.argtypes = [i32, i32, i32, vp, i32]
+    lib.pa_frame_activity_check.restype = C.c_char_p
+    lib.pa_frame_activity.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, vp]
+    lib.pa_frames_median.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.pa_engine_timer_start.argtypes = [vp]
     lib.pa_engine_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
     if lib.pa_abi_version() != 5:
@@ -309,6 +314,28 @@ def render_check(n: int, h: int, w: int, marks, first, out: int = RENDER_BGR, ge
     rc = load_library().pa_render_check(int(n), int(h), int(w), marks.ctypes.data if marks.size else None, first.ctypes.data, int(out),
                                         C.byref(geom) if geom is not None else None, C.byref(enc) if enc is not None else None, why, 512)
     return why.value.decode() if rc else None
+
+
+#: ``pa_frame_activity`` / ``pa_frames_median`` refuse larger frames and longer batches (PA_ACTIVITY_MAX_SIDE, PA_ACTIVITY_MAX_FRAMES)
+ACTIVITY_MAX_SIDE, ACTIVITY_MAX_FRAMES = 16384, 65535
+
+
+def _roi_arg(roi):
+    """None, or the rectangle as four int32 (x0, y0, x1, y1)."""
+    if roi is None:
+        return None
+    roi = np.ascontiguousarray(roi, np.int32).reshape(-1)
+    if roi.size != 4:
+        raise ValueError(f"roi must be (x0, y0, x1, y1), got {roi.size} numbers")
+    return roi
+
+
+def frame_activity_check(n: int, h: int, w: int, roi=None, tau: int = 24) -> Optional[str]:
+    """None if ``pa_frame_activity`` would accept these arguments, else its reason for refusing them (``pa_frame_activity_check``:
+    host code, no GPU)."""
+    roi = _roi_arg(roi)
+    why = load_library().pa_frame_activity_check(int(n), int(h), int(w), roi.ctypes.data if roi is not None else None, int(tau))
+    return why.decode() if why else None
 
 
 #: ``pa_jpeg_encode`` refuses wider frames (PA_JPEG_MAX_WIDTH)
@@ -501,6 +528,52 @@ class Engine:
     def render_last_path(self) -> int:
         """RENDER_PATH_VECTOR / RENDER_PATH_BYTE: what the last successful ``render`` launched (0: none yet)."""
         return int(self.lib.pa_render_last_path(self.handle))
+
+    def frame_activity(self, src: DeviceBuffer, n: int, h: int, w: int, ref: DeviceBuffer, prev: Optional[DeviceBuffer] = None, roi=None,
+                       tau: int = 24, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """(n, 3) uint64 — ``sad_ref``, ``changed``, ``sad_prev`` of each of the ``n`` packed BGR frames of ``h`` x ``w`` in ``src``
+        against the reference image ``ref`` and the frame before it (``prev`` for frame 0; without it ``sad_prev[0]`` is 0), over
+        the half-open rectangle ``roi = (x0, y0, x1, y1)`` (None: the whole frame) — ``pa_frame_activity``; the specification is
+        ``include/padel_hip.h``, its executable form ``activity.frame_activity_host``.  Synchronous, on the compute stream.  ``out``:
+        a C-contiguous uint64 array of at least ``n`` rows of 3 to write into (rows beyond ``n`` stay as they are).  What the
+        library refuses (``frame_activity_check``) is an ``EngineError``, nothing is launched."""
+        roi = _roi_arg(roi)
+        why = frame_activity_check(n, h, w, roi, tau)
+        if why is not None:
+            raise EngineError(why)
+        fb = h * w * 3
+        if src.nbytes < n * fb:
+            raise EngineError(f"frame_activity: src holds {src.nbytes} bytes, {n} BGR frames need {n * fb}")
+        for name, buf in (("ref", ref), ("prev", prev)):
+            if buf is not None and buf.nbytes < fb:
+                raise EngineError(f"frame_activity: {name} holds {buf.nbytes} bytes, one BGR frame needs {fb}")
+        if out is None:
+            out = np.zeros((n, 3), np.uint64)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint64 and out.flags.c_contiguous and out.ndim == 2
+                  and out.shape[1] == 3 and out.shape[0] >= n):
+            raise EngineError("frame_activity: out must be a C-contiguous uint64 array of at least n rows of 3")
+        self._check(self.lib.pa_frame_activity(self.handle, src.ptr, int(n), int(h), int(w), ref.ptr, prev.ptr if prev is not None else None,
+                                               roi.ctypes.data if roi is not None else None, int(tau), out.ctypes.data))
+        return out
+
+    def frames_median(self, src: DeviceBuffer, n: int, h: int, w: int, out: Optional[DeviceBuffer] = None) -> DeviceBuffer:
+        """The per-pixel, per-channel median of ``n`` packed BGR frames in ``src`` — ``np.median(frames, 0).astype(np.uint8)``, BGR —
+        into ``out`` (allocated if None; the caller frees it), ``pa_frames_median``.  Synchronous."""
+        fb = h * w * 3
+        if n >= 1 and h >= 1 and w >= 1 and src.nbytes < n * fb:
+            raise EngineError(f"frames_median: src holds {src.nbytes} bytes, {n} BGR frames need {n * fb}")
+        own = out is None
+        if own:
+            out = self.alloc(max(fb, 1))
+        elif out.nbytes < fb:
+            raise EngineError(f"frames_median: out holds {out.nbytes} bytes, one BGR frame needs {fb}")
+        try:
+            self._check(self.lib.pa_frames_median(self.handle, src.ptr, int(n), int(h), int(w), out.ptr))
+        except EngineError:
+            if own:
+                out.free()
+            raise
+        return out
 
     def jpeg_encode(self, buffer: DeviceBuffer, n: int, h: int, w: int, desc, quality: int = 90, out: Optional[np.ndarray] = None):
         """``n`` frames of 8-bit YUV 4:2:0 in ``buffer``, laid out by ``desc`` (a ``pa_yuv_desc`` or a dict of its fields; what

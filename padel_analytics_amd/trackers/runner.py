@@ -28,7 +28,16 @@ Additions (all off by default, the reference's sequential semantics stay the def
   ``runner.data_analytics.into_dataframe(fps)``.  With ``render`` the court inset is drawn too (``court_inset``: None = "iff
   ``collect_data``"): the translucent panel — the renderer's one blending mark — the court, and the projected players and ball.
   Without ``render`` the data are collected from the stored results alone: no frame is read, no GPU touched.  ``timings["__collect__"]``
-  is the host time of projection and collection.  Under ``distributed`` all of it is rank 0's."""
+  is the host time of projection and collection.  Under ``distributed`` all of it is rank 0's.
+
+* ``segments=`` (the reference's open item, ``main.py:122``: "FILTER FRAMES OF INTEREST"): the trackers and the render step see only
+  the frames of some half-open ranges ``(lo, hi)`` of source frame numbers — a list, or ``"court"``: ``activity.scan`` +
+  ``court_view_mask`` + ``segments`` over [start, end) before the first tracker (``segment_options``: keyword arguments for them;
+  ``timings["__segments__"]``).  ``source_index[i]`` is the source frame of kept position ``i``; ``n_available``, ``total_frames``,
+  every tracker's ``results`` and ``Ball.frame`` count kept frames.  Each tracker runs segment by segment, in order: no batch (and no
+  TrackNet window, no InpaintNet sequence) spans a cut, while ByteTrack and every other state a tracker keeps between batches carry
+  over.  A stream tracker's background is computed once, over the first kept frames.  ``DataAnalytics`` deltas across a cut are not
+  corrected.  Not with ``distributed`` or ``fanout``."""
 from __future__ import annotations
 
 import os
@@ -59,7 +68,8 @@ class TrackingRunner:
     def __init__(self, trackers: list, video_path: str | Path, inference_path: str | Path, start: int = 0,
                  end: Optional[int] = None, collect_data: bool = False, *, distributed: bool = False,
                  fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None, render=None,
-                 court_inset: Optional[bool] = None, render_quality: int = 90) -> None:
+                 court_inset: Optional[bool] = None, render_quality: int = 90, segments=None,
+                 segment_options: Optional[dict] = None) -> None:
         self.video_path = video_path
         self.inference_path = inference_path
         self.start = start
@@ -102,6 +112,81 @@ class TrackingRunner:
         self._merge_pool = None            # sharded mode, rank 0: the thread of the sequential stages (created with the first one)
         self.render = render               # None | path of the file to write (.avi / .mjpeg / .mjpg: Motion-JPEG; anything else: .y4m) | video.FrameSink
         self.render_quality = int(render_quality)   # JPEG quality of a Motion-JPEG file (1..100)
+        # kept frames: None = all of [start, start + n_available); else [(lo, hi)] source frame numbers, set by _set_segments
+        self.segments: Optional[list] = None
+        self._run_range = (self.start, self.start + self.n_available)      # the source frames this run may keep
+        self.source_index = np.arange(self.start, self.start + self.n_available, dtype=np.int64)
+        self.segment_options = dict(segment_options or {})
+        self._segments_pending = False             # "court": resolved by run() before the first tracker (resolve_segments)
+        if segments is not None:
+            if distributed or fanout:
+                raise ValueError("segments= is not available with distributed=True or fanout=True")
+            if isinstance(segments, str):
+                if segments != "court":
+                    raise ValueError(f"segments={segments!r}: a list of (lo, hi) source frame numbers or \"court\"")
+                self._segments_pending = True
+            else:
+                self._set_segments(segments)
+
+    def _set_segments(self, segments) -> None:
+        """``segments``: ascending, non-overlapping, non-empty (lo, hi) inside [start, start + n_available) — else ``ValueError``
+        naming the pair."""
+        lo_all, hi_all = self._run_range
+        segs, last = [], lo_all
+        for pair in segments:
+            lo, hi = (int(v) for v in pair)
+            if hi <= lo:
+                raise ValueError(f"segments: ({lo}, {hi}) is empty")
+            if lo < lo_all or hi > hi_all:
+                raise ValueError(f"segments: ({lo}, {hi}) leaves the frames [{lo_all}, {hi_all}) of this run")
+            if lo < last:
+                raise ValueError(f"segments: ({lo}, {hi}) starts before the end of the one in front of it ({last}): they must be "
+                                 f"ascending and must not overlap")
+            segs.append((lo, hi))
+            last = hi
+        self.segments = segs
+        self.source_index = (np.concatenate([np.arange(lo, hi, dtype=np.int64) for lo, hi in segs]) if segs
+                             else np.zeros(0, np.int64))
+        self.n_available = self.total_frames = len(self.source_index)
+
+    def resolve_segments(self) -> None:
+        """``segments="court"``: scan [start, end), decide, set the segments (``run()`` does this before the first tracker)."""
+        if not self._segments_pending:
+            return
+        from .. import activity as A
+        opt = dict(self.segment_options)
+        scan_kw = {k: opt.pop(k) for k in ("ref", "roi", "tau", "batch") if k in opt}
+        opt.setdefault("fps", self.video_info.fps)
+        t0 = timeit.default_timer()
+        n = len(self.source_index)
+        act = A.scan(self.video_path, engine=self.engine, start=self.start, end=self.start + n, **scan_kw)
+        segs = [(self.start + lo, self.start + hi) for lo, hi in A.segments(A.court_view_mask(act, **opt))]
+        self._segments_pending = False
+        self._set_segments(segs)
+        t1 = timeit.default_timer()
+        self.timings["__segments__"] = {"seconds": t1 - t0, "frames": n, "kept": self.n_available, "segments": len(segs)}
+        print(f"runner: court view in {self.n_available} of {n} frames, {len(segs)} segments ({n / max(t1 - t0, 1e-9):.1f} frames/s scanned)")
+
+    def _pieces(self, lo: int = 0, hi: Optional[int] = None):
+        """(kept position, source frame, count) of the parts of kept positions [lo, hi) that lie in one segment each."""
+        hi = self.n_available if hi is None else min(hi, self.n_available)
+        k = 0
+        for slo, shi in self.segments:
+            a, b = max(lo, k), min(hi, k + shi - slo)
+            if a < b:
+                yield a, slo + (a - k), b - a
+            k += shi - slo
+
+    def _batches(self, bs: int, lo: int = 0, hi: Optional[int] = None):
+        """Lists of at most ``bs`` frames of kept positions [lo, hi), in order; with segments none spans a cut."""
+        if self.segments is None:
+            yield from _sampler(self._frames(lo, hi), bs)
+            return
+        for _, src, n in self._pieces(lo, hi):
+            yield from _sampler(self._source_frames(src, src + n), bs)
+
+    def _source_frames(self, lo: int, hi: int):
+        return video.get_video_frames_generator(self.video_path, start=lo, stride=self.stride, end=hi)
 
     def restart(self) -> None:
         for tracker in self.trackers.values():
@@ -202,14 +287,15 @@ class TrackingRunner:
         return marks
 
     def frame_marks(self, i: int) -> list:
-        """The marks of frame ``i`` (counted from ``start``): ``FRAME: i + 1`` (reference :118-127, there cv2's Hershey font in RGB
+        """The marks of frame ``i`` (counted from ``start``; with segments: kept position ``i``, and the label shows the source frame,
+        ``source_index[i] - start + 1``): ``FRAME: i + 1`` (reference :118-127, there cv2's Hershey font in RGB
         (255, 255, 0) with its bottom-left at (20, 50); here the renderer's font at scale 3), then every tracker's
         ``results[i].marks(**tracker.draw_kwargs())`` in tracker order, then — with ``court_inset`` — ``inset_marks(i)``.  The
         projections behind the inset are computed once, in frame order, from the results stored at that moment and kept until the next
         ``draw_and_collect_data`` or ``restart``, which start over."""
         from .. import render as R
         k = 3
-        marks = R.text(f"FRAME: {i + 1}", 20, 50 - (R.GLYPH_H * k - 1), k, (0, 255, 255))
+        marks = R.text(f"FRAME: {int(self.source_index[i]) - self.start + 1 if i < len(self.source_index) else i + 1}", 20, 50 - (R.GLYPH_H * k - 1), k, (0, 255, 255))
         for tracker in self.trackers.values():
             if i < len(tracker.results):
                 marks += tracker.results[i].marks(**tracker.draw_kwargs())
@@ -242,7 +328,7 @@ class TrackingRunner:
         t0 = timeit.default_timer()
         done = 0
         try:
-            for sample in _sampler(self._frames(), bs):
+            for sample in self._batches(bs):
                 n = len(sample)
                 dev = video.device_batch(sample)
                 if dev is None:
@@ -274,11 +360,14 @@ class TrackingRunner:
         return done
 
     def _frames(self, lo: int = 0, hi: Optional[int] = None):
-        """Frames [start + lo, start + hi) of the clip (hi None: to self.end)."""
+        """Frames [start + lo, start + hi) of the clip (hi None: to self.end); with segments: kept positions [lo, hi)."""
+        if self.segments is not None:
+            return (f for _, src, n in self._pieces(lo, hi) for f in self._source_frames(src, src + n))
         end = self.end if hi is None else self.start + hi
         return video.get_video_frames_generator(self.video_path, start=self.start + lo, stride=self.stride, end=end)
 
     def run(self) -> None:
+        self.resolve_segments()
         print(f"runner: Running {self.total_frames} frames")
         try:
             if self.fanout:
@@ -321,6 +410,15 @@ class TrackingRunner:
         range has switched itself to the full-range path and asks to be run again (engine.RangeOverflow); batch
         trackers repeat the offending batch themselves (yolo.YOLO.infer_frames).  ``defer``: Tracker.predict_and_update."""
         from .. import engine as E
+        if self.segments is not None:
+            try:
+                self._predict_segments(tracker)
+            except E.RangeOverflow as ex:
+                print(f"{str(tracker)}: {ex}")
+                tracker.restart()
+                tracker.to(tracker.DEVICE)
+                self._predict_segments(tracker)
+            return
         try:
             tracker.predict_and_update(self._frames(), defer=defer, total_frames=self.total_frames)
         except E.RangeOverflow as ex:
@@ -328,6 +426,41 @@ class TrackingRunner:
             tracker.restart()
             tracker.to(tracker.DEVICE)
             tracker.predict_and_update(self._frames(), defer=defer, total_frames=self.total_frames)
+
+    def _predict_segments(self, tracker: Tracker) -> None:
+        """One tracker over the kept frames, segment by segment.  A batch tracker's loop (``Tracker._predict_batches``) runs once per
+        segment and appends to its results: what it keeps between batches (ByteTrack) carries over, its batches end at the cut.  A
+        stream tracker runs ``predict_partial`` + ``merge_partials`` per segment — its windows and sequences never span a cut — with
+        the background set beforehand; results that carry a ``frame`` number get the kept position."""
+        if self._is_batch_tracker(tracker):
+            for _, src, n in self._pieces():
+                tracker._predict_batches(self._source_frames(src, src + n), tracker.results.update, total_frames=n)
+        else:
+            self._segment_background(tracker)
+            out: list = []
+            for kept, src, n in self._pieces():
+                part = tracker.merge_partials(tracker.predict_partial(self._source_frames(src, src + n), first_frame=kept, total_frames=n))
+                assert len(part) == n, (str(tracker), len(part), n)
+                for obj in part:
+                    if kept and isinstance(getattr(obj, "frame", None), int):
+                        obj.frame += kept
+                out += part
+            tracker.results.predictions = out
+        print(f"{tracker.__str__()}: {len(tracker.results)} predictions.")
+
+    def _segment_background(self, tracker) -> None:
+        """A stream tracker's background (TrackNet's median), once, over the first ``min(median_max_sample_num, kept)`` kept frames —
+        as ``_share_background`` computes it over the head of the clip."""
+        if getattr(tracker, "median", None) is not None or not hasattr(tracker, "compute_median"):
+            return
+        nmed = min(tracker.median_max_sample_num, self.n_available)
+        if nmed < 1:
+            return
+        frames = list(self._frames(0, nmed))
+        if len(list(self._pieces(0, nmed))) > 1:       # kept frames of several segments are no contiguous range of a device clip
+            from ..activity import _host_frame
+            frames = [_host_frame(f) for f in frames]
+        tracker.median = tracker.compute_median(frames)
 
     def _join(self, merges: bool = True, alone: bool = True) -> None:
         """Wait for deferred work, report and save (rank 0), in tracker order, host tails before merges.  ``merges`` False:
