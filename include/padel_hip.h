@@ -287,6 +287,31 @@ int pa_frame_activity(pa_engine* eng, const uint8_t* frames_bgr_dev, int n, int 
  * on the compute stream.                                                                                                      */
 int pa_frames_median(pa_engine* eng, const uint8_t* frames_bgr_dev, int n, int h, int w, uint8_t* out_bgr_dev);
 
+/* ---- colour histograms of boxes: who is this player?  (csrc/box_histogram.hip; the readable twin is identity.box_histograms_host) ----
+ * All integer.  A BGR pixel falls into bin  ((B >> 5) << 6) | ((G >> 5) << 3) | (R >> 5)  (0 .. 511: three bits a channel).
+ * For frames of h x w packed BGR (frame i at frames_bgr_dev + i * h * w * 3) and k rectangles rects[5 j .. 5 j + 4] = {frame, x0,
+ * y0, x1, y1}, half-open, 0 <= frame < n, 0 <= x0 < x1 <= w, 0 <= y0 < y1 <= h, 512 uint32 per rectangle:
+ *     out[512 j + b] = #{ pixels (x, y) of frame rects[5 j], x0 <= x < x1, y0 <= y < y1, whose bin is b }
+ * The counts of a rectangle are exact and depend on that rectangle and its frame alone: not on k, on the rectangle's place in the
+ * list (a rectangle listed twice gives two equal rows), on the alignment of a pointer or on how the launch is shaped (one workgroup
+ * per rectangle adds into histograms in LDS — integer addition, exact in any order — and stores its row with plain stores: no
+ * global atomics).  rects and out_u32 are HOST memory, k x 5 and k x 512; rows beyond k are not touched.  k = 0 is accepted and
+ * launches nothing (rects may then be NULL).
+ * Limits: n, h and w as for pa_frame_activity (PA_ACTIVITY_MAX_FRAMES, PA_ACTIVITY_MAX_SIDE: a rectangle has at most 2^28 pixels, a
+ * counter cannot wrap); k at most PA_BOX_HIST_MAX_RECTS.
+ * pa_box_histograms_check: host only (no engine, no GPU): NULL if pa_box_histograms would accept these arguments, else the reason,
+ * a string of static storage in this thread, valid until its next call.  One reason each for: n out of range; h or w out of
+ * range; k out of range; a NULL pointer; a frame index outside 0 .. n - 1; a rectangle that is empty or leaves the frame (the
+ * last two name the first offending rectangle).
+ * pa_box_histograms: SYNCHRONOUS, on the engine's compute stream, so ordered behind whatever produced the frames there.  Refuses
+ * what the check refuses (and a NULL frames or out pointer, with the check's words for NULL), launching nothing, the reason in
+ * pa_last_error.  The rectangle list and the counters go through an engine-owned buffer grown on demand and freed with the engine. */
+#define PA_BOX_HIST_BINS 512
+#define PA_BOX_HIST_MAX_RECTS 16384
+const char* pa_box_histograms_check(int n, int h, int w, const int32_t* rects, int k);
+int pa_box_histograms(pa_engine* eng, const uint8_t* frames_bgr_dev, int n, int h, int w,
+                      const int32_t* rects /* host, k x 5: frame, x0, y0, x1, y1 */, int k, uint32_t* out_u32 /* host, k x 512 */);
+
 /* ---- frames to a file: the YUV 4:2:0 bytes pa_render writes -> one baseline JPEG per frame (Motion-JPEG; csrc/jpeg_encode.hip) ----
  * The bit stream is specified here; its constants are csrc/jpeg_tables.h (host and device), its readable twin
  * padel_analytics_amd/mjpeg.py (encode_host), which produces the same bytes.

@@ -13,7 +13,7 @@ OUT="${PADEL_OUT:-../libpadel_hip.so}"
 mkdir -p "$BUILD"
 pids=()
 # PADEL_ONLY="a.hip b.hip": recompile only these translation units and relink with the objects already in $BUILD (iteration)
-ALL="conv_tap.hip conv_tap16.hip conv_tap_bx3.hip conv_patch_bx3.hip conv_tap_h2.hip conv_tap_h2p.hip conv_1x1_h2s.hip conv_patch_h2.hip conv_patch_h2q.hip conv_patch_h2r.hip conv_patch_h2v.hip conv_patch_h2w.hip conv_patch16.hip kernels_misc.hip resnet_ops.hip yolo11_ops.hip stem_l1_h2.hip head_tail_h2.hip postproc.hip tracknet_post.hip yuv_convert.hip render.hip jpeg_encode.hip jpeg_decode.hip frame_activity.hip"
+ALL="conv_tap.hip conv_tap16.hip conv_tap_bx3.hip conv_patch_bx3.hip conv_tap_h2.hip conv_tap_h2p.hip conv_1x1_h2s.hip conv_patch_h2.hip conv_patch_h2q.hip conv_patch_h2r.hip conv_patch_h2v.hip conv_patch_h2w.hip conv_patch16.hip kernels_misc.hip resnet_ops.hip yolo11_ops.hip stem_l1_h2.hip head_tail_h2.hip postproc.hip tracknet_post.hip yuv_convert.hip render.hip jpeg_encode.hip jpeg_decode.hip frame_activity.hip box_histogram.hip"
 # the engine (host code that calls the HIP runtime), one translation unit per concern: engine_internal.h
 ENGINE="engine.cpp engine_pre.cpp engine_yolo.cpp engine_tracknet.cpp engine_resnet.cpp engine_comm.cpp engine_render.cpp engine_jpeg.cpp engine_jpeg_decode.cpp engine_activity.cpp"
 for f in ${PADEL_ONLY:-$ALL $ENGINE}; do
@@ -42,6 +42,9 @@ g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c render_check.cpp -o "$BUILD/
 pids+=($!)
 # what pa_frame_activity refuses, and how a launch is cut into bands: no HIP at all (the same file builds into tests/activity_check_main.cpp's program)
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c activity_check.cpp -o "$BUILD/activity_check.o" &
+pids+=($!)
+# what pa_box_histograms refuses: no HIP at all (the same file builds into tests/box_histogram_check_main.cpp's program)
+g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c box_histogram_check.cpp -o "$BUILD/box_histogram_check.o" &
 pids+=($!)
 # what pa_jpeg_encode refuses, its tables, header and sizes: no HIP either (jpeg_tables.h also builds into tests/jpeg_tables_main.cpp's program)
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c jpeg_check.cpp -o "$BUILD/jpeg_check.o" &

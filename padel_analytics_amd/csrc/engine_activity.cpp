@@ -1,7 +1,9 @@
 // pa_frame_activity: frame statistics of BGR frames in HBM against a reference image and the previous frame (frame_activity.hip);
-// pa_frames_median: the median kernel of the ball session without one.  What is refused is host-only code in activity_check.cpp.
+// pa_frames_median: the median kernel of the ball session without one; pa_box_histograms: colour histograms of rectangles of such
+// frames (box_histogram.hip).  What is refused is host-only code in activity_check.cpp and box_histogram_check.cpp.
 #include "engine_internal.h"
 #include "activity_check.h"
+#include "box_histogram_check.h"
 
 int pa_frame_activity(pa_engine* e, const uint8_t* frames, int n, int h, int w, const uint8_t* ref, const uint8_t* prev, const int32_t* roi,
                       int tau, uint64_t* out) {
@@ -41,6 +43,31 @@ int pa_frames_median(pa_engine* e, const uint8_t* frames, int n, int h, int w, u
     hipStream_t s = e->main_stream();
     const hipError_t r = launch_median(frames, n, fb, out, s, /*keep_bgr=*/true);
     if (r != hipSuccess) PA_FAIL(e, "median launch failed: %s", hipGetErrorString(r));
+    PA_HIP(e, hipStreamSynchronize(s));
+    return 0;
+}
+
+int pa_box_histograms(pa_engine* e, const uint8_t* frames, int n, int h, int w, const int32_t* rects, int k, uint32_t* out) {
+    if (!e) return 1;
+    if (!frames || !out) PA_FAIL(e, "%s", kBoxHistNull);
+    std::string why;
+    if (box_hist_validate(n, h, w, rects, k, why)) PA_FAIL(e, "%s", why.c_str());
+    if (k == 0) return 0;
+    PA_HIP(e, hipSetDevice(e->dev));
+    // [k x 512 uint32 results | k x 5 int32 rectangles] in one engine-owned block; the call is synchronous, so a block about to be
+    // replaced is idle.  The list is pageable memory: the runtime has consumed it when hipMemcpyAsync returns
+    const size_t out_bytes = (size_t)k * kBoxHistBins * sizeof(uint32_t), rect_bytes = (size_t)k * 5 * sizeof(int32_t);
+    PA_HIP(e, e->box_stage.fit(out_bytes + rect_bytes, std::max((out_bytes + rect_bytes) * 2, (size_t)65536)));
+    BoxHistArgs a{};
+    a.frames = frames; a.h = h; a.w = w; a.k = k;
+    a.out = reinterpret_cast<uint32_t*>(e->box_stage.get());
+    int32_t* const d_rects = reinterpret_cast<int32_t*>(e->box_stage.get() + out_bytes);
+    a.rects = d_rects;
+    hipStream_t s = e->main_stream();
+    PA_HIP(e, hipMemcpyAsync(d_rects, rects, rect_bytes, hipMemcpyHostToDevice, s));
+    hipError_t r = launch_box_histograms(a, s);
+    if (r != hipSuccess) PA_FAIL(e, "box histogram launch failed: %s", hipGetErrorString(r));
+    PA_HIP(e, hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, s));
     PA_HIP(e, hipStreamSynchronize(s));
     return 0;
 }

@@ -8,7 +8,8 @@
 //   engine_render.cpp    pa_render: marks on BGR frames -> BGR / YUV 4:2:0 (the refusals and the font: render_check.cpp, host only)
 //   engine_jpeg.cpp      pa_jpeg_encode: YUV 4:2:0 frames in HBM -> baseline JPEGs in host memory (the refusals, tables and header: jpeg_check.cpp, host only)
 //   engine_jpeg_decode.cpp  pa_jpeg_decode: baseline JPEGs in host memory -> BGR frames in HBM (the markers: jpeg_parse.cpp, host only)
-//   engine_activity.cpp  pa_frame_activity, pa_frames_median: frame statistics for the court-view filter (the refusals: activity_check.cpp, host only)
+//   engine_activity.cpp  pa_frame_activity, pa_frames_median: frame statistics for the court-view filter (the refusals: activity_check.cpp, host only);
+//                        pa_box_histograms: colour histograms of player boxes (the refusals: box_histogram_check.cpp, host only)
 //   engine_comm.cpp      RCCL
 //   device_mem.h         DevMem<T> / PinMem<T>: the owner of every device (page-locked host) allocation of these files; the
 //                        hooks it allocates through, and the count of live bytes, are engine.cpp's
@@ -73,6 +74,7 @@ struct pa_engine {
     hipEvent_t timer_ev[2]{};  // pa_engine_timer_start / _stop, created on first use
     DevMem<uint8_t> render_stage;   // pa_render: the resolved marks and first[] of the call in flight, filled and read on the main stream only
     DevMem<uint8_t> activity_stage; // pa_frame_activity: the results and the workgroups' partial sums of the call in flight (the call is synchronous)
+    DevMem<uint8_t> box_stage;      // pa_box_histograms: the rows of counters and the rectangle list of the call in flight (synchronous too)
     int render_last_path = 0; // 1 vector, 2 byte: what the last pa_render launched (pa_render_last_path)
     JpegScratch* jpeg = nullptr;   // pa_jpeg_encode: slots, tables and the gathered frames, grown on demand, used on the main stream only (engine_jpeg.cpp)
     JpegDecScratch* jpeg_dec = nullptr;   // pa_jpeg_decode: compressed bytes, tables, coefficients and planes, likewise (engine_jpeg_decode.cpp)

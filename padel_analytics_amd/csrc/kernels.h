@@ -390,4 +390,14 @@ struct ActivityArgs {
 };
 hipError_t launch_frame_activity(const ActivityArgs& a, hipStream_t s);
 
+// Colour histograms of rectangles of BGR frames (box_histogram.hip; the specification: include/padel_hip.h).  The caller
+// (pa_box_histograms) has checked the arguments (box_histogram_check.cpp); k >= 1.
+struct BoxHistArgs {
+    const uint8_t* frames;   // packed BGR frames of h x w
+    const int32_t* rects;    // [k][5] on the device: frame, x0, y0, x1, y1
+    uint32_t* out;           // [k][512] on the device, 8-byte aligned
+    int h, w, k;
+};
+hipError_t launch_box_histograms(const BoxHistArgs& a, hipStream_t s);
+
 }  // namespace padel

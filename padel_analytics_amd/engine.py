@@ -124,6 +124,7 @@ ABI_SYMBOLS = [
     "pa_yolo_last_post_path", "pa_jpeg_decode_set_split", "pa_jpeg_decode_last_split",
     "pa_model_lanes_allocated", "pa_model_last_lane", "pa_yolo_resample_passes", "pa_device_bytes_live",
     "pa_frame_activity", "pa_frame_activity_check", "pa_frames_median",
+    "pa_box_histograms", "pa_box_histograms_check",
 ]
 
 
@@ -234,6 +235,9 @@ def load_library():
     lib.pa_frame_activity_check.restype = C.c_char_p
     lib.pa_frame_activity.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, vp]
     lib.pa_frames_median.argtypes = [vp, vp, i32, i32, i32, vp]
+    lib.pa_box_histograms_check.argtypes = [i32, i32, i32, vp, i32]
+    lib.pa_box_histograms_check.restype = C.c_char_p
+    lib.pa_box_histograms.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp]
     lib.pa_engine_timer_start.argtypes = [vp]
     lib.pa_engine_timer_stop.argtypes = [vp, C.POINTER(C.c_float)]
     if lib.pa_abi_version() != 5:
@@ -335,6 +339,32 @@ def frame_activity_check(n: int, h: int, w: int, roi=None, tau: int = 24) -> Opt
     host code, no GPU)."""
     roi = _roi_arg(roi)
     why = load_library().pa_frame_activity_check(int(n), int(h), int(w), roi.ctypes.data if roi is not None else None, int(tau))
+    return why.decode() if why else None
+
+
+#: a row of ``pa_box_histograms`` (PA_BOX_HIST_BINS) and the rectangles one call takes at most (PA_BOX_HIST_MAX_RECTS)
+BOX_HIST_BINS, BOX_HIST_MAX_RECTS = 512, 16384
+
+
+def _rects_arg(rects) -> np.ndarray:
+    """The rectangle list as a C-contiguous (k, 5) int32 array (frame, x0, y0, x1, y1)."""
+    rects = np.ascontiguousarray(rects, np.int32)
+    if rects.size == 0:
+        return rects.reshape(0, 5)
+    if rects.ndim != 2 or rects.shape[1] != 5:
+        raise ValueError(f"rects must be (k, 5): frame, x0, y0, x1, y1; got shape {rects.shape}")
+    return rects
+
+
+def box_histograms_check(n: int, h: int, w: int, rects) -> Optional[str]:
+    """None if ``pa_box_histograms`` would accept these arguments, else its reason for refusing them (``pa_box_histograms_check``:
+    host code, no GPU).  ``rects=None`` stands for a NULL list of one rectangle."""
+    if rects is None:
+        ptr, k = None, 1
+    else:
+        rects = _rects_arg(rects)
+        ptr, k = (rects.ctypes.data if len(rects) else None), len(rects)
+    why = load_library().pa_box_histograms_check(int(n), int(h), int(w), ptr, int(k))
     return why.decode() if why else None
 
 
@@ -554,6 +584,31 @@ class Engine:
             raise EngineError("frame_activity: out must be a C-contiguous uint64 array of at least n rows of 3")
         self._check(self.lib.pa_frame_activity(self.handle, src.ptr, int(n), int(h), int(w), ref.ptr, prev.ptr if prev is not None else None,
                                                roi.ctypes.data if roi is not None else None, int(tau), out.ctypes.data))
+        return out
+
+    def box_histograms(self, src: DeviceBuffer, n: int, h: int, w: int, rects, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """(k, 512) uint32 — for each of the ``k`` rectangles ``rects[j] = (frame, x0, y0, x1, y1)``, half-open, of the ``n`` packed
+        BGR frames of ``h`` x ``w`` in ``src``, the number of its pixels per colour bin ``((B >> 5) << 6) | ((G >> 5) << 3) | (R >> 5)``
+        — ``pa_box_histograms``; the specification is ``include/padel_hip.h``, its executable form
+        ``identity.box_histograms_host``.  Synchronous, on the compute stream.  ``out``: a C-contiguous uint32 array of at least
+        ``k`` rows of 512 to write into (rows beyond ``k`` stay as they are).  What the library refuses (``box_histograms_check``)
+        is an ``EngineError``, nothing is launched."""
+        if rects is None:
+            raise EngineError(box_histograms_check(n, h, w, None))
+        rects = _rects_arg(rects)
+        k = len(rects)
+        why = box_histograms_check(n, h, w, rects)
+        if why is not None:
+            raise EngineError(why)
+        if src.nbytes < n * h * w * 3:
+            raise EngineError(f"box_histograms: src holds {src.nbytes} bytes, {n} BGR frames need {n * h * w * 3}")
+        if out is None:
+            out = np.zeros((k, BOX_HIST_BINS), np.uint32)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint32 and out.flags.c_contiguous and out.ndim == 2
+                  and out.shape[1] == BOX_HIST_BINS and out.shape[0] >= k):
+            raise EngineError("box_histograms: out must be a C-contiguous uint32 array of at least k rows of 512")
+        self._check(self.lib.pa_box_histograms(self.handle, src.ptr, int(n), int(h), int(w), rects.ctypes.data if k else None, int(k),
+                                               out.ctypes.data))
         return out
 
     def frames_median(self, src: DeviceBuffer, n: int, h: int, w: int, out: Optional[DeviceBuffer] = None) -> DeviceBuffer:

@@ -37,7 +37,17 @@ Additions (all off by default, the reference's sequential semantics stay the def
   every tracker's ``results`` and ``Ball.frame`` count kept frames.  Each tracker runs segment by segment, in order: no batch (and no
   TrackNet window, no InpaintNet sequence) spans a cut, while ByteTrack and every other state a tracker keeps between batches carry
   over.  A stream tracker's background is computed once, over the first kept frames.  ``DataAnalytics`` deltas across a cut are not
-  corrected.  Not with ``distributed`` or ``fanout``."""
+  corrected.  Not with ``distributed`` or ``fanout``.
+
+* ``identities=True``: ByteTrack never gives a lost track its old id back, so a player who was hidden for longer than its buffer
+  returns as id 5, 6, ... and ``DataAnalytics`` drops them.  After the trackers (and after their prediction caches are written:
+  the caches keep ByteTrack's ids, so a cached run gives the same answer as a fresh one) and before ``draw_and_collect_data``, the
+  stored boxes of the tracker whose ``object()`` is ``Players`` get colour histograms in a second pass over the kept frames
+  (``identity.scan``: csrc/box_histogram.hip), ``identity.assign`` maps the tracks to four identities, and that tracker's results are
+  replaced in memory by ``Players`` with the mapped ids (``identity.relabel``).  ``identity_options``: ``every``, ``batch``,
+  ``on_device`` for the scan, ``n_players``, ``max_distance`` for the assignment.  ``identity_map`` is the mapping,
+  ``identity_distances`` what it was decided by, ``timings["__identities__"]`` the pass.  The thresholds are parameters, not
+  findings.  Not with ``distributed`` or ``fanout``."""
 from __future__ import annotations
 
 import os
@@ -69,7 +79,7 @@ class TrackingRunner:
                  end: Optional[int] = None, collect_data: bool = False, *, distributed: bool = False,
                  fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None, render=None,
                  court_inset: Optional[bool] = None, render_quality: int = 90, segments=None,
-                 segment_options: Optional[dict] = None) -> None:
+                 segment_options: Optional[dict] = None, identities: bool = False, identity_options: Optional[dict] = None) -> None:
         self.video_path = video_path
         self.inference_path = inference_path
         self.start = start
@@ -127,6 +137,12 @@ class TrackingRunner:
                 self._segments_pending = True
             else:
                 self._set_segments(segments)
+        self.identities = bool(identities)
+        self.identity_options = dict(identity_options or {})
+        self.identity_map: Optional[dict] = None       # {ByteTrack id: id 1..4, or 5.. for a track nobody claimed}: repair_identities
+        self.identity_distances: Optional[dict] = None
+        if self.identities and (distributed or fanout):
+            raise ValueError("identities=True is not available with distributed=True or fanout=True")
 
     def _set_segments(self, segments) -> None:
         """``segments``: ascending, non-overlapping, non-empty (lo, hi) inside [start, start + n_available) — else ``ValueError``
@@ -166,6 +182,34 @@ class TrackingRunner:
         t1 = timeit.default_timer()
         self.timings["__segments__"] = {"seconds": t1 - t0, "frames": n, "kept": self.n_available, "segments": len(segs)}
         print(f"runner: court view in {self.n_available} of {n} frames, {len(segs)} segments ({n / max(t1 - t0, 1e-9):.1f} frames/s scanned)")
+
+    def repair_identities(self) -> None:
+        """``identities=True``: histograms of the stored player boxes over the kept frames, the assignment, and the ``Players``
+        tracker's results replaced by relabelled ones (``run()`` does this between the trackers and ``draw_and_collect_data``)."""
+        if not self.identities:
+            return
+        from .. import identity as I
+        tracker = None
+        for t in self.trackers.values():           # the last one, as the projection takes it
+            if self._object_name(t) == "Players":
+                tracker = t
+        if tracker is None:
+            print("runner: identities=True, but no tracker gives Players: nothing to relabel")
+            return
+        opt = dict(self.identity_options)
+        scan_kw = {k: opt.pop(k) for k in ("every", "batch", "on_device") if k in opt}
+        t0 = timeit.default_timer()
+        results = tracker.results.predictions
+        tracks = I.scan(self.video_path, results, engine=self.engine, positions=self.source_index[:len(results)], **scan_kw)
+        self.identity_map, self.identity_distances = I.assign(tracks, **opt)
+        tracker.results.predictions = [I.relabel(p, self.identity_map) for p in results]
+        t1 = timeit.default_timer()
+        n_players = int(opt.get("n_players", 4))
+        assigned = sum(1 for v in self.identity_map.values() if v <= n_players)
+        self.timings["__identities__"] = {"seconds": t1 - t0, "frames": len(results), "boxes": sum(t.boxes for t in tracks.values()),
+                                          "tracks": len(tracks), "assigned": assigned, "unassigned": len(tracks) - assigned}
+        print(f"runner: identities: {len(tracks)} tracks over {len(results)} frames -> {assigned} assigned, {len(tracks) - assigned} unassigned "
+              f"({len(results) / max(t1 - t0, 1e-9):.1f} frames/s scanned)")
 
     def _pieces(self, lo: int = 0, hi: Optional[int] = None):
         """(kept position, source frame, count) of the parts of kept positions [lo, hi) that lie in one segment each."""
@@ -403,6 +447,7 @@ class TrackingRunner:
             #  a tracker that raises must not leave finished work unsaved or a worker pool alive; a deferred stage's
             # own exception surfaces here, after the ones before it were saved
             self._join()
+        self.repair_identities()
         self.draw_and_collect_data()
 
     def _predict(self, tracker: Tracker, defer: Optional[list] = None) -> None:
