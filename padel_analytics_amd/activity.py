@@ -20,7 +20,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import video
+from . import engine as E, video
 
 
 def luma(bgr: np.ndarray) -> np.ndarray:
@@ -75,21 +75,6 @@ class FrameActivity:
         return len(self.changed)
 
 
-def _host_frame(f) -> np.ndarray:
-    """One frame of any source as an (h, w, 3) uint8 array on the host."""
-    if isinstance(f, video.DeviceFrame):
-        out = np.empty(f.shape, np.uint8)
-        return f.clip.buffer.view(f.index * f.clip.frame_bytes, f.clip.frame_bytes).download(out)
-    return np.ascontiguousarray(np.asarray(f), np.uint8)
-
-
-def _engine(engine):
-    if engine is not None:
-        return engine
-    from . import engine as E
-    return E.default_engine()
-
-
 def reference_frame(source, samples: int = 64, engine=None, start: int = 0, end: Optional[int] = None) -> np.ndarray:
     """(h, w, 3) uint8 BGR: the per-pixel median (``Engine.frames_median``: ``np.median(...).astype(uint8)``) of the frames at
     indices ``start + k * total // samples``, k = 0 .. samples - 1, of the ``total`` frames of ``source`` in [start, end).
@@ -105,9 +90,9 @@ def reference_frame(source, samples: int = 64, engine=None, start: int = 0, end:
     idx = sorted({int(start) + k * total // int(samples) for k in range(int(samples))})
     frames = []
     for i in idx:
-        frames += [_host_frame(f) for f in video.get_video_frames_generator(source, start=i, end=i + 1)]
+        frames += [video.host_frame(f) for f in video.get_video_frames_generator(source, start=i, end=i + 1)]
     stack = np.stack(frames)
-    eng = _engine(engine)
+    eng = engine or E.default_engine()
     n, h, w = stack.shape[:3]
     src = eng.alloc(stack.nbytes)
     med = None
@@ -123,18 +108,18 @@ def reference_frame(source, samples: int = 64, engine=None, start: int = 0, end:
 
 def _follows(a, b) -> bool:
     """Frame handle ``b`` is the stored frame behind ``a`` in the same device-resident clip."""
-    return type(a) is type(b) and isinstance(a, (video.DeviceFrame, video.YuvFrame)) and a.clip is b.clip and b.index == a.index + 1
+    return (type(a) is type(b) and isinstance(a, (video.DeviceFrame, video.YuvFrame)) and a.clip is b.clip and b.index == a.index + 1
+            and getattr(a.clip, "on_device", True))
 
 
 def scan(source, ref=None, roi=None, tau: int = 24, batch: int = 64, engine=None, start: int = 0, end: Optional[int] = None) -> FrameActivity:
     """``frame_activity`` of every frame of ``source`` in [start, end) — anything ``video.get_video_frames_generator`` accepts —
     against ``ref`` ((h, w, 3) uint8 BGR; None: ``reference_frame(source)`` over the same range), ``batch`` frames per call.
 
-    Device-resident batches (``video.device_batch``: device clips, YUV and Motion-JPEG clips) are read where they are, one frame
-    earlier than the batch so that its first frame finds its predecessor; host frames go through one staging ``DeviceClip`` whose
-    first slot keeps the last frame of the batch before.  ``sad_prev`` is therefore continuous over the clip (0 for its first
-    frame)."""
-    eng = _engine(engine)
+    The frames come through ``video.ResidentBatches``.  A batch finds its predecessor either as the stored frame in front of it —
+    then it is asked for as part of the batch — or in slot 0 of the walk's staging clip (host frames, a device clip that
+    repeats).  ``sad_prev`` is therefore continuous over the clip (0 for its first frame)."""
+    eng = engine or E.default_engine()
     info = video.VideoInfo.from_video_path(source)
     h, w = info.height, info.width
     fb = h * w * 3
@@ -145,43 +130,34 @@ def scan(source, ref=None, roi=None, tau: int = 24, batch: int = 64, engine=None
     if ref.shape != (h, w, 3):
         raise ValueError(f"ref has shape {ref.shape}, the clip's frames are {(h, w, 3)}")
     batch = max(1, int(batch))
-    rows, stage, carry = [], None, None
+    rows, laps, carry = [], [], None
+
+    def samples():
+        """The batches; one whose predecessor is the stored frame in front of it starts with that frame (``laps``: 1 for those),
+        so that a YUV or Motion-JPEG clip converts the two as one range."""
+        last = None
+        for sample in video.sampler(video.get_video_frames_generator(source, start=start, end=end), batch):
+            laps.append(int(last is not None and _follows(last, sample[0])))
+            yield [last] + sample if laps[-1] else sample
+            last = sample[-1]
+
     d_ref = eng.alloc(fb).upload(ref)
     try:
-        from .trackers.tracker import _sampler
-        for sample in _sampler(video.get_video_frames_generator(source, start=start, end=end), batch):
-            n = len(sample)
-            dev = prev = None
-            if carry is not None and _follows(carry, sample[0]):
-                dev = video.device_batch([carry] + sample)
-                if dev is not None:
-                    src, prev = dev[0].view(fb, n * fb), dev[0].view(0, fb)
-            if dev is None:
-                dev = video.device_batch(sample)
-                if dev is not None:
-                    src, prev = dev[0], None
-            if dev is None or (prev is None and carry is not None):
-                # host frames, or a device batch whose predecessor is not the stored frame in front of it (a clip that repeats):
-                # slot 0 of the staging clip holds the predecessor
-                if stage is None:
-                    stage = video.DeviceClip(eng, shape=(batch + 1, h, w, 3))
-                if carry is not None:
-                    stage.upload(_host_frame(carry)[None], first=0, copy_stream=False)
+        with video.ResidentBatches(eng, samples(), batch + 1, (h, w), lead=1) as walk:
+            for frames, host in walk:
+                lap = laps.pop()
+                n = len(frames) - lap
+                buf = video.device_batch(frames)[0]
+                prev = buf.view(0, fb) if lap else None
+                if carry is not None and not lap:        # host frames, a clip that repeats: the predecessor goes to slot 0
+                    stage = walk.staging()
+                    stage.upload(video.host_frame(carry)[None], first=0, copy_stream=False)
                     prev = stage.buffer.view(0, fb)
-                if dev is None:
-                    host = video.host_batch(sample)
-                    stage.upload(host, first=1, copy_stream=False)
-                    src = stage.buffer.view(fb, n * fb)
-                    carry_next = np.array(host[n - 1])
-            if dev is not None:
-                carry_next = sample[-1]
-            rows.append(eng.frame_activity(src, n, h, w, d_ref, prev=prev, roi=roi, tau=tau))
-            carry = carry_next
+                rows.append(eng.frame_activity(buf.view(lap * fb, n * fb), n, h, w, d_ref, prev=prev, roi=roi, tau=tau))
+                carry = frames[-1] if host is None else np.array(host[-1])
     finally:
         eng.synchronize()
         d_ref.free()
-        if stage is not None:
-            stage.free()
     a = np.concatenate(rows) if rows else np.zeros((0, 3), np.uint64)
     return FrameActivity(sad_ref=a[:, 0].copy(), changed=a[:, 1].copy(), sad_prev=a[:, 2].copy(), npix=(x1 - x0) * (y1 - y0))
 

@@ -22,7 +22,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import video
+from . import engine as E, video
 
 BINS = 512
 MAX_RECTS = 16384          # engine.BOX_HIST_MAX_RECTS: the rectangles one Engine.box_histograms call takes
@@ -100,13 +100,10 @@ def scan(source, players_results, every: int = 1, batch: int = 64, engine=None, 
     ``i``; the runner passes its ``source_index``, so that only kept frames are read).  Every box with an id counts towards its
     track's ``frames``; on every ``every``-th position its ``torso_rect`` gets a histogram, summed into the track's ``hist``.
 
-    The clip is walked in batches of ``batch`` frames, as ``activity.scan`` walks it: device-resident batches
-    (``video.device_batch``: device clips, YUV and Motion-JPEG clips) are read where they are, host frames go through one staging
-    ``DeviceClip``; a batch without a rectangle is not read at all.  One ``Engine.box_histograms`` call per batch (one per
-    ``MAX_RECTS`` rectangles of it).
+    The clip is walked in batches of ``batch`` frames; the batches that hold a rectangle — the others are never handed to the walk,
+    so they are not read, staged or converted — come through ``video.ResidentBatches``.  One ``Engine.box_histograms`` call per batch
+    (one per ``MAX_RECTS`` rectangles of it).
     ``on_device=False`` runs ``box_histograms_host`` on host frames instead (no engine, no GPU) and gives the same numbers."""
-    from .activity import _engine, _host_frame
-    from .trackers.tracker import _sampler
     results = list(players_results)
     positions = np.arange(len(results), dtype=np.int64) if positions is None else np.asarray(positions, np.int64)
     if len(positions) < len(results):
@@ -114,16 +111,15 @@ def scan(source, players_results, every: int = 1, batch: int = 64, engine=None, 
     every, batch = max(1, int(every)), max(1, int(batch))
     info = video.VideoInfo.from_video_path(source)
     h, w = info.height, info.width
-    fb = h * w * 3
     tracks: dict = {}
-    eng = stage = None
-    try:
+    todo: list = []                    # (rectangles, their tracks) of the samples handed out and not yet summed
+
+    def samples():
         for first, src, count in _runs(positions[:len(results)]):
             done = 0
-            for sample in _sampler(video.get_video_frames_generator(source, start=src, end=src + count), batch):
-                n = len(sample)
+            for sample in video.sampler(video.get_video_frames_generator(source, start=src, end=src + count), batch):
                 rects, owners = [], []
-                for k in range(n):
+                for k in range(len(sample)):
                     i = first + done + k
                     for p in results[i] or ():
                         if p.id is None:
@@ -134,34 +130,29 @@ def scan(source, players_results, every: int = 1, batch: int = 64, engine=None, 
                         if r is not None:
                             rects.append((k,) + r)
                             owners.append(t)
-                done += n
-                if not rects:
-                    continue
-                if on_device:
-                    eng = eng or _engine(engine)
-                    dev = video.device_batch(sample)
-                    if dev is None:
-                        if stage is None:
-                            stage = video.DeviceClip(eng, shape=(batch, h, w, 3))
-                        stage.upload(video.host_batch(sample), copy_stream=False)      # synchronous: the kernel behind it sees the frames
-                        buf = stage.buffer.view(0, n * fb)
-                    else:
-                        buf = dev[0]
-                    cap = MAX_RECTS                                  # what one call takes: a crowded batch goes in several
-                    hists = np.concatenate([eng.box_histograms(buf, n, h, w, rects[lo:lo + cap]) for lo in range(0, len(rects), cap)])
-                else:
-                    host = [_host_frame(f) for f in sample] if isinstance(sample[0], video.DeviceFrame) else video.host_batch(sample)
-                    hists = box_histograms_host(np.asarray(host), rects)
-                for t, row in zip(owners, hists):
-                    t.hist += row
-                    t.boxes += 1
+                done += len(sample)
+                if rects:
+                    todo.append((rects, owners))
+                    yield sample
             if done != count:
                 raise ValueError(f"scan: the source ends at frame {src + done}, the results go on to {src + count}")
-    finally:
-        if eng is not None:
-            eng.synchronize()
-        if stage is not None:
-            stage.free()
+
+    def add(hists) -> None:
+        for t, row in zip(todo.pop()[1], hists):
+            t.hist += row
+            t.boxes += 1
+
+    if not on_device:
+        for sample in samples():
+            host = [video.host_frame(f) for f in sample] if isinstance(sample[0], video.DeviceFrame) else video.host_batch(sample)
+            add(box_histograms_host(np.asarray(host), todo[-1][0]))
+        return tracks
+    cap = MAX_RECTS                                  # what one call takes: a crowded batch goes in several
+    with video.ResidentBatches(engine, samples(), batch, (h, w)) as walk:
+        for frames, _ in walk:
+            engine = engine or E.default_engine()
+            buf, rects = video.device_batch(frames)[0], todo[-1][0]
+            add(np.concatenate([engine.box_histograms(buf, len(frames), h, w, rects[lo:lo + cap]) for lo in range(0, len(rects), cap)]))
     return tracks
 
 

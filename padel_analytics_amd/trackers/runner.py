@@ -358,41 +358,31 @@ class TrackingRunner:
         return video.Y4mSink(self.render, w, h, fps=self.video_info.fps), True
 
     def _render_clip(self) -> int:
-        """The clip once more, ``RENDER_BATCH`` frames at a time: BGR in HBM (``video.device_batch``; host frames through one staging
-        clip), one ``Engine.render`` to YUV 4:2:0 in the sink's geometry, one download, one write.  With the inset or the collection
-        on, each batch is projected (and collected) first.  -> the number of frames."""
+        """The clip once more, ``RENDER_BATCH`` frames at a time: BGR in HBM (``video.ResidentBatches``), one ``Engine.render`` to YUV
+        4:2:0 in the sink's geometry, one download, one write.  With the inset or the collection on, each batch is projected (and
+        collected) first.  -> the number of frames."""
         from .. import engine as E, render as R
         eng = self.engine or E.default_engine()
         w, h = self.video_info.width, self.video_info.height
         sink, own = self._make_sink()
         print(f"runner: Writing results into {getattr(sink, 'path', sink)}")
-        bs, fb = self.RENDER_BATCH, h * w * 3
+        bs = self.RENDER_BATCH
         dst = eng.alloc(video.yuv_span(bs, h, w, sink.desc))
-        stage = None
         t0 = timeit.default_timer()
         done = 0
         try:
-            for sample in self._batches(bs):
-                n = len(sample)
-                dev = video.device_batch(sample)
-                if dev is None:
-                    if stage is None:
-                        stage = video.DeviceClip(eng, shape=(bs, h, w, 3))
-                    stage.upload(video.host_batch(sample), copy_stream=False)      # synchronous: the render behind it sees the frames
-                    src = stage.buffer.view(0, n * fb)
-                else:
-                    src = dev[0]
-                if self.court_inset or self.data_analytics is not None:
-                    self._collect(done, n)
-                marks, first = R.pack([self.frame_marks(done + k) for k in range(n)])
-                eng.render(src, n, h, w, marks, first, dst, out=E.RENDER_YUV420, geom=sink.desc, enc=sink.enc)
-                sink.write_device(dst.view(0, video.yuv_span(n, h, w, sink.desc)), n)
-                done += n
+            with video.ResidentBatches(eng, self._batches(bs), bs, (h, w)) as walk:
+                for frames, _ in walk:
+                    n = len(frames)
+                    if self.court_inset or self.data_analytics is not None:
+                        self._collect(done, n)
+                    marks, first = R.pack([self.frame_marks(done + k) for k in range(n)])
+                    eng.render(video.device_batch(frames)[0], n, h, w, marks, first, dst, out=E.RENDER_YUV420, geom=sink.desc, enc=sink.enc)
+                    sink.write_device(dst.view(0, video.yuv_span(n, h, w, sink.desc)), n)
+                    done += n
         finally:
             eng.synchronize()
             dst.free()
-            if stage is not None:
-                stage.free()
             if own:
                 sink.close()
         t1 = timeit.default_timer()
@@ -503,8 +493,7 @@ class TrackingRunner:
             return
         frames = list(self._frames(0, nmed))
         if len(list(self._pieces(0, nmed))) > 1:       # kept frames of several segments are no contiguous range of a device clip
-            from ..activity import _host_frame
-            frames = [_host_frame(f) for f in frames]
+            frames = [video.host_frame(f) for f in frames]
         tracker.median = tracker.compute_median(frames)
 
     def _join(self, merges: bool = True, alone: bool = True) -> None:
@@ -644,56 +633,12 @@ class TrackingRunner:
             print(f"{str(t)}: Running on {t.DEVICE} (fan-out, {bs} frames per upload) ...")
         t0 = timeit.default_timer()
 
-        def batches():
-            """Batches of frames resident in HBM: device clips, YUV clips and Motion-JPEG clips (their ``MjpegFrame`` handles are
-            ``YuvFrame``s) pass through; host frames are uploaded once per
-            batch into one of two staging clips, the next upload overlapping this batch's compute."""
-            gen = self._frames()
-            first = next(gen, None)
-            if first is None:
-                return
-            if isinstance(first, (video.DeviceFrame, video.YuvFrame)):
-                def chain():
-                    yield first
-                    yield from gen
-                for sample in _sampler(chain(), bs):
-                    # YUV / Motion-JPEG clips: one conversion or decode per batch into the clip's own BGR staging (no host_batch, no second staging
-                    # clip) — every tracker's device_batch over this batch or a part of it then finds the frames converted
-                    if isinstance(first, video.YuvFrame):
-                        video.device_batch(sample)
-                    yield sample
-                return
-            from .. import engine as E
-            eng = self.engine or E.default_engine()
-            h, w = first.shape[:2]
-            clips = [video.DeviceClip(eng, shape=(bs, h, w, 3)) for _ in range(2)]
-
-            def chain():
-                yield first
-                yield from gen
-
-            def stage(k, frames):
-                c = clips[k % len(clips)]
-                c.upload(video.host_batch(frames), copy_stream=True)
-                return [video.DeviceFrame(c, i) for i in range(len(frames))]
-
-            with ThreadPoolExecutor(max_workers=1) as up:
-                fut, k = None, 0
-                for frames in _sampler(chain(), bs):
-                    nxt = up.submit(stage, k, frames)
-                    k += 1
-                    if fut is not None:
-                        yield fut.result()
-                    fut = nxt
-                if fut is not None:
-                    yield fut.result()
-            for c in clips:
-                c.free()
-
         # the host stages of all batch trackers share one queue (no copies: the device stages hand out their own arrays here) and
         # trail the device stages by one stage per tracker; a tracker without stages is updated in line
-        with host_stages(len(batch)) as queue:
-            for sample in batches():
+        # (the staging of host frames is the walk's: freed after the queue has drained, whatever ends the pass)
+        with video.ResidentBatches(self.engine, _sampler(self._frames(), bs), bs, self.video_info.resolution_wh[::-1], prefetch=True) as walk, \
+                host_stages(len(batch)) as queue:
+            for sample, _ in walk:
                 for t in batch:
                     for sub in _sampler(iter(sample), t.batch_size):
                         if t._has_stages():

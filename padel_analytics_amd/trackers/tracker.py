@@ -34,6 +34,8 @@ from typing import Iterable, Iterator, Optional, Type
 
 import numpy as np
 
+from ..video import sampler as _sampler      # (one definition; the loops here and the trackers know it by this name)
+
 
 class NoPredictSample(Exception):
     """The tracker predicts from the frame generator, not from samples (reference tracker.py:15-20)."""
@@ -92,18 +94,6 @@ class TrackingResults:
 
     def __iter__(self) -> Iterator:
         return iter(self.predictions)
-
-
-def _sampler(generator: Iterable[np.ndarray], sequence_length: int) -> Iterator[list]:
-    """Chop a frame stream into lists of ``sequence_length`` frames; the last one may be short."""
-    w: list = []
-    for x in generator:
-        w.append(x)
-        if len(w) == sequence_length:
-            yield w
-            w = []
-    if w:
-        yield w
 
 
 class relaxed_gc:

@@ -18,6 +18,7 @@ Frames are HWC uint8 **BGR**, exactly what supervision yields."""
 from __future__ import annotations
 
 import os
+from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import Iterator, Optional
 
@@ -961,6 +962,103 @@ def host_batch(sample) -> np.ndarray:
                       f.ctypes.data == p0 + k * fb for k, f in enumerate(sample)):
             return np.lib.stride_tricks.as_strided(f0, shape=(len(sample),) + f0.shape, strides=(fb,) + f0.strides, writeable=False)
     return np.stack(sample)
+
+
+def host_frame(f) -> np.ndarray:
+    """One frame of any source as an (h, w, 3) uint8 array on the host."""
+    if isinstance(f, DeviceFrame):
+        out = np.empty(f.shape, np.uint8)
+        return f.clip.buffer.view(f.index * f.clip.frame_bytes, f.clip.frame_bytes).download(out)
+    return np.ascontiguousarray(np.asarray(f), np.uint8)
+
+
+def sampler(generator, sequence_length: int) -> Iterator[list]:
+    """Chop a frame stream into lists of ``sequence_length`` frames; the last one may be short."""
+    w: list = []
+    for x in generator:
+        w.append(x)
+        if len(w) == sequence_length:
+            yield w
+            w = []
+    if w:
+        yield w
+
+
+class ResidentBatches:
+    """A walk over a clip as batches resident in HBM, and the one owner of the staging memory such a walk needs:
+    ``with ResidentBatches(engine, samples, capacity, (h, w)) as walk: for frames, host in walk: ...``.  ``samples``: non-empty lists of
+    at most ``capacity`` frames (``sampler``).  ``frames`` are handles ``device_batch`` gives a view over; ``host`` is None for a sample
+    that was resident as it came, else the (n, h, w, 3) array that was uploaded.
+
+    * ``DeviceFrame`` handles pass through, not looked at.
+    * ``YuvFrame`` / ``MjpegFrame`` handles get one ``device_batch(sample)`` when it is their turn — converted or decoded into their
+      clip's own BGR staging — and pass through if that answers.
+    * Everything else is staged: ``host_batch(sample)`` goes up behind ``lead`` slots that are the caller's (``staging()`` reaches
+      them); ``frames`` are ``DeviceFrame(staging, lead + k)``.
+
+    A staging clip of ``lead + capacity`` frames is created by the first sample that needs one, on ``engine`` (None: the default
+    engine, resolved then).  ``prefetch``: two of them, filled by turns on the copy stream by a worker thread that starts with the
+    first; host frames go up before the sample in front of them is handed out, and a sample's bytes stay until the next one is asked
+    for.  A sample is made resident when it is drawn, so who reads only some (``identity.scan``) leaves the others out of ``samples``.
+    Leaving the ``with`` — at the end, by an error, by a ``break`` — joins the worker, synchronises the engine, then frees the staging."""
+
+    def __init__(self, engine, samples, capacity: int, hw: tuple, lead: int = 0, prefetch: bool = False):
+        self.engine, self._samples, self._lead, self._prefetch = engine, iter(samples), int(lead), bool(prefetch)
+        self._shape = (self._lead + int(capacity), int(hw[0]), int(hw[1]), 3)
+        self._clips, self._pool, self._uploads = [], None, 0
+
+    def __enter__(self) -> "ResidentBatches":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        if self._pool is not None:
+            self._pool.shutdown(wait=True, cancel_futures=True)
+        if self.engine is not None:
+            self.engine.synchronize()                # readers of the staging may still be queued
+        while self._clips:
+            self._clips.pop().free()
+
+    def staging(self, k: int = 0) -> DeviceClip:
+        """Staging clip ``k``, created if need be."""
+        while len(self._clips) <= k:
+            if self.engine is None:
+                from . import engine as E
+                self.engine = E.default_engine()
+            self._clips.append(DeviceClip(self.engine, shape=self._shape))
+        return self._clips[k]
+
+    def _stage(self, sample, clip: DeviceClip) -> tuple:
+        host = host_batch(sample)
+        clip.upload(host, first=self._lead, copy_stream=self._prefetch)
+        return [DeviceFrame(clip, self._lead + k) for k in range(len(sample))], host
+
+    def _submit(self, sample):
+        """The upload of ``sample`` on the worker thread, into the staging clip the upload before it did not take."""
+        if self._pool is None:
+            self._pool = ThreadPoolExecutor(max_workers=1)
+        self._uploads += 1
+        return self._pool.submit(self._stage, sample, self.staging(self._uploads % 2))
+
+    def _resident(self, sample) -> Optional[tuple]:
+        """``(sample, None)`` if its frames are in HBM as they are (after their conversion), else None."""
+        f = sample[0]
+        return (sample, None) if isinstance(f, DeviceFrame) or (isinstance(f, YuvFrame) and device_batch(sample) is not None) else None
+
+    def __iter__(self):
+        if not self._prefetch:
+            for sample in self._samples:
+                yield self._resident(sample) or self._stage(sample, self.staging())
+            return
+        # one sample ahead: `fut` is the upload of `nxt`, if `nxt` is host frames (handles are resolved at their turn: a clip's
+        # own staging holds one range)
+        ahead = lambda s: None if s is None or isinstance(s[0], (DeviceFrame, YuvFrame)) else self._submit(s)
+        nxt = next(self._samples, None)
+        fut = ahead(nxt)
+        while nxt is not None:
+            cur, cur_fut = nxt, fut
+            nxt = next(self._samples, None)
+            fut = ahead(nxt)
+            yield cur_fut.result() if cur_fut is not None else self._resident(cur) or self._submit(cur).result()
 
 
 def get_video_frames_generator(source_path, stride: int = 1, start: int = 0, end: Optional[int] = None) -> Iterator[np.ndarray]:
