@@ -100,7 +100,10 @@ enum pa_task { PA_TASK_DETECT = 0, PA_TASK_POSE = 1, PA_TASK_TRACKNET = 2, PA_TA
  * PA_DTYPE_F16 (detect / pose only; BASELINE configs[4]): activations and conv weights are fp16, accumulation fp32
  * (v_mfma_f32_16x16x32_f16), biases / stem weights / the Detect-Pose head maps (head_buf) stay fp32; conv weights sit
  * in the blob as fp16 [npad][Ktot] with K order (64-channel chunk, tap, 32-channel half), cin % 32 == 0,
- * w_off still counts 4-byte blob words.
+ * w_off still counts 4-byte blob words.  Stored halves are saturated (no infinity reaches HBM), and every kernel that turns an
+ * fp32 value x into a stored half of an activation buffer (the conv epilogues, the stem) raises the model's overflow flag iff
+ * !(|x| <= 65504), tested on x just before the clamp, behind the residual add: NaN raises, exactly +-65504 does not.  The fp32
+ * head maps store x itself and raise nothing.  The caller repeats such a call on a PA_DTYPE_H2 or PA_DTYPE_F32 model.
  * PA_DTYPE_H2 (the fast fp32-equivalent path): every activation is an fp16 PAIR (x ~ h + m / 2048, 22-23 significant
  * bits) stored in 16-channel groups of 64 bytes [h x 16 | m x 16] — 4 bytes per channel like fp32 — written once by its
  * producer; conv weights sit at w_off as pre-split planes [npad][k-step][h | m][32 fp16] of the row-scaled weights, the
@@ -480,8 +483,10 @@ int pa_engine_set_timeline_path(pa_engine* eng, const char* path);
 int pa_model_create(pa_engine* eng, const pa_model_desc* desc, const float* weights, size_t n_floats,
                     pa_model** out);
 void pa_model_destroy(pa_model* m);
-/* PA_DTYPE_H2 models: *out = 1 if any activation written since the last call did not fit the fp16 range (results of
- * those inferences are invalid: repeat them on a PA_DTYPE_F32 model), then clears the flag; always 0 for other dtypes */
+/* PA_DTYPE_H2 and PA_DTYPE_F16 models: *out = 1 if any activation written since the last call did not fit the fp16 range
+ * (h2: |x| > 65504 of a pair's value; fp16: !(|x| <= 65504) of the fp32 value about to be clamped and stored, NaN included).
+ * The results of those inferences are invalid: repeat them on a model of a wider type (fp16 -> h2 or fp32, h2 -> fp32).  Then
+ * clears the flag.  Always 0 for PA_DTYPE_F32 models                                                                   */
 int pa_model_take_overflow(pa_model* m, int* out);
 /* frames / windows processed per replay of the graph (activation buffers are sized for it); default 64 */
 int pa_model_set_max_batch(pa_model* m, int max_batch);
@@ -537,9 +542,9 @@ int pa_yolo_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, const
  * (pa_host_register) and must not be touched between submit and wait — the ONE place where the library keeps caller
  * pointers past return.  At most PA_MAX_INFLIGHT tickets per model; the plan
  * (source size, imgsz, batch) must not change while tickets are in flight.  `overflow` (may be NULL): 1 if an activation of
- * an h2 model has left the fp16 range by the time this ticket finished (sticky until pa_model_take_overflow, and shared by the
+ * an h2 or fp16 model has left the fp16 range by the time this ticket finished (sticky until pa_model_take_overflow, and shared by the
  * lanes: a ticket always sees its own overflow, and may see its neighbour's): the results of this and of later tickets are then
- * not to be used (see PA_DTYPE_H2).                                                                                  */
+ * not to be used (see pa_dtype); 0 for fp32 models.                                                                                */
 #define PA_MAX_INFLIGHT 4
 int pa_yolo_submit(pa_model* m, const uint8_t* frames, int n, int h, int w, const pa_yolo_params* p,
                    float* out_boxes, float* out_kpts, int32_t* out_counts, int* ticket);

@@ -52,6 +52,11 @@ __device__ __forceinline__ void wait_vm() {
 }
 // this wave's LDS accesses have completed
 __device__ __forceinline__ void lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// The sticky "a value did not fit fp16" flag of a model (h2 and fp16 families): each lane brings the OR of its own tests, the wave
+// does one ballot and, only when that is non-zero, one atomicOr by its first lane.  Called where the whole wave is active.
+__device__ __forceinline__ void range_raise(unsigned* flag, bool bad) {
+    if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
 
 }  // namespace
 

@@ -286,7 +286,7 @@ int pa_model_take_overflow(pa_model* m, int* out) {
     if (!m || !out) return 1;
     pa_engine* e = m->e;
     *out = 0;
-    if (m->d.dtype != PA_DTYPE_H2) return 0;
+    if (!guards_range(m)) return 0;
     PA_HIP(e, hipSetDevice(e->dev));
     unsigned v = 0;
     if (m->ovf_cached) {                 // pa_yolo_infer read the flag back with its results (nothing has run on the model since)

@@ -179,7 +179,7 @@ struct pa_model {
     DevMem<char> d_wr;
     std::vector<long long> wr_off;         // op -> byte offset into d_wr, -1: no copy
     bool wr_valid = false;
-    DevMem<unsigned> d_ovf;                // h2 models: sticky "a value did not fit fp16" flag (pa_model_take_overflow)
+    DevMem<unsigned> d_ovf;                // h2 and fp16 models: sticky "a value did not fit fp16" flag (pa_model_take_overflow)
     int fc_nout = 0;                       // outputs of that op (0: the graph has none)
     int max_batch = 64;
     Lane ln[kMaxLanes];                    // ln[0]: the plan's; ln[1]: lazily, YOLO models only
@@ -194,7 +194,7 @@ struct pa_model {
     int net_h = 0, net_w = 0;
     int rw = 0, rh = 0, top = 0, left = 0, lb_mode = 0;
     size_t arena_bytes = 0, logical_bytes = 0;   // bytes of the plan with / without liveness aliasing
-    unsigned h_ovf = 0;                    // overflow flag as read back by the last pa_yolo_infer calls (h2 models)
+    unsigned h_ovf = 0;                    // overflow flag as read back by the last pa_yolo_infer calls (h2 and fp16 models)
     bool ovf_cached = false;               // h_ovf is current: no kernel of this model has run since it was read
     // pa_yolo_submit / pa_yolo_wait: tickets in flight.  slot = ticket % PA_MAX_INFLIGHT; h_pin[slot]: the overflow flag as the
     // stream read it back after that ticket's kernels (page-locked: a pageable destination would make the copy block the host)
@@ -220,6 +220,8 @@ struct pa_model {
 };
 
 // ---- engine.cpp
+// does the model's dtype raise d_ovf (h2 pairs and the fp16 family; fp32 models never do)?
+inline bool guards_range(const pa_model* m) { return m->d.dtype == PA_DTYPE_H2 || m->d.dtype == PA_DTYPE_F16; }
 // (the profile's events go onto the stream the profiled kernels run on)
 ProfRec* prof_begin(pa_model* m, hipStream_t s, size_t idx, int kind, int ksize, double flops);
 inline void prof_end(hipStream_t s, ProfRec* r) { if (r) hipEventRecord(r->e1, s); }

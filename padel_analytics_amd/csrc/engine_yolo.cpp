@@ -132,7 +132,7 @@ static int run_post(pa_model* m, Lane& L, const pa_yolo_params* p, int nb, int o
     prof_end(s, pr);
     if (r != hipSuccess) PA_FAIL(e, "nms launch failed: %s", hipGetErrorString(r));
     // ---- results back to the caller's arrays (rows beyond max_det are never written on device)
-    if (m->d.dtype == PA_DTYPE_H2)      // the overflow flag travels with the results: pa_model_take_overflow needs no device round trip
+    if (guards_range(m))      // the overflow flag travels with the results: pa_model_take_overflow needs no device round trip
         PA_HIP(e, hipMemcpyAsync(m->h_pin.get() + ovf_slot, m->d_ovf.get(), sizeof(unsigned), hipMemcpyDeviceToHost, s));
     PA_HIP(e, hipMemcpyAsync(out_counts, L.d_ocnt.get(), nb * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     PA_HIP(e, hipMemcpyAsync(out_boxes, L.d_oboxes.get(),
@@ -182,7 +182,7 @@ static int yolo_prepare(pa_model* m, const uint8_t* frames, int n, int h, int w,
 }
 
 // everything one batch of nb <= max_batch frames needs, enqueued on lane li's stream behind what the main stream held at the call
-// (fork_lane): upload (host frames), preprocessing, network, decode, NMS, result copies (the overflow flag of h2 models into
+// (fork_lane): upload (host frames), preprocessing, network, decode, NMS, result copies (the overflow flag of h2 and fp16 models into
 // h_pin[ovf_slot]).  Does not wait.
 static int yolo_enqueue(pa_model* m, int li, const uint8_t* src, int nb, int h, int w, const pa_yolo_params* p, float* out_boxes,
                         float* out_kpts, int32_t* out_counts, int ovf_slot, size_t* ppi) {
@@ -233,7 +233,7 @@ int pa_yolo_infer(pa_model* m, const uint8_t* frames, int n, int h, int w, const
             return 1;
         PA_HIP(e, hipStreamSynchronize(s));
         m->last_n = nb;
-        if (m->d.dtype == PA_DTYPE_H2) { m->h_ovf |= m->h_pin.get()[PA_MAX_INFLIGHT]; m->ovf_cached = true; }
+        if (guards_range(m)) { m->h_ovf |= m->h_pin.get()[PA_MAX_INFLIGHT]; m->ovf_cached = true; }
     }
     PA_HIP(e, e->sync_lanes());          // a synchronous call completes every ticket still in flight, on either lane: their waits return at once
     finish_profile(m, pi);
@@ -288,7 +288,7 @@ int pa_yolo_wait(pa_model* m, int ticket, int* overflow) {
     --m->n_inflight;
     Lane& L = m->ln[m->tk_lane[slot]];
     if (L.st.last_ticket == ticket) L.st.busy = false;
-    if (overflow) *overflow = (m->d.dtype == PA_DTYPE_H2 && m->h_pin.get()[slot]) ? 1 : 0;
+    if (overflow) *overflow = (guards_range(m) && m->h_pin.get()[slot]) ? 1 : 0;
     return 0;
 }
 

@@ -10,6 +10,11 @@
 // 0 / 1 / 2 / 3 with channels [0, 8) of j / [0, 8) of j + 1 / [8, 16) of j / [8, 16) of j + 1 — one 16-byte store (and one
 // 16-byte residual load, un-swapped by the same involution) per two fragments; an odd last fragment keeps 8-byte moves.
 // Same arithmetic per value in the same order: results are bitwise those of round 3.
+//
+// Range guard: a value x that is stored as a half raises the model's sticky flag (ConvArgs::f16_flag) iff !(|x| <= 65504), tested
+// on the fp32 value the clamp sees (behind the residual add; NaN raises, exactly +-65504 does not).  A lane ORs the test over
+// every value it stores, then the wave does one ballot and, when that is non-zero, one atomicOr by one lane (range_raise, as in
+// the h2 epilogues).  The stored bits are those of the clamp alone.  The fp32 head paths store x itself and raise nothing.
 #pragma once
 #include "kernels.h"
 #include "conv_prims.h"
@@ -30,6 +35,13 @@ __device__ __forceinline__ u32x2 f16e_pack4(const f32x4 v) {
         o[p] = __builtin_bit_cast(unsigned, __builtin_convertvector(x, h16x2));
     }
     return o;
+}
+// does any of 4 values about to be clamped leave the fp16 range (or is NaN)?
+__device__ __forceinline__ bool f16e_out_of_range(const f32x4 v) {
+    bool bad = false;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bad |= !(fabsf(v[r]) <= 65504.0f);
+    return bad;
 }
 
 // whole fragments inside the tensor; fp16 out: choff % 8 == 0 and cs % 8 == 0 (16-byte pieces), fp32 out: % 4, no residual
@@ -71,6 +83,7 @@ __device__ __forceinline__ void f16_epilogue_fast(const ConvArgs& a, const f32x4
             }
         }
         (void)rp; (void)rr; (void)rl;
+        bool bad = false;
 #pragma unroll
         for (int p = 0; p < NP; ++p)
 #pragma unroll
@@ -86,6 +99,8 @@ __device__ __forceinline__ void f16_epilogue_fast(const ConvArgs& a, const f32x4
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { v0[r] += (float)r0[r]; v1[r] += (float)r1[r]; }
                 }
+                bad |= f16e_out_of_range(v0);
+                bad |= f16e_out_of_range(v1);
                 const u32x2 o0 = f16e_pack4(v0), o1 = f16e_pack4(v1);
                 const u32x2 s0 = __builtin_amdgcn_permlane16_swap(o0[0], o1[0], false, false);
                 const u32x2 s1 = __builtin_amdgcn_permlane16_swap(o0[1], o1[1], false, false);
@@ -103,9 +118,11 @@ __device__ __forceinline__ void f16_epilogue_fast(const ConvArgs& a, const f32x4
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] += (float)r0[r];
                 }
+                bad |= f16e_out_of_range(v);
                 *reinterpret_cast<u32x2*>(op[f] + (NF - 1) * 32 + lq * 8) = f16e_pack4(v);
             }
         }
+        if (a.f16_flag) range_raise(a.f16_flag, bad);
     }
 }
 
@@ -113,6 +130,9 @@ __device__ __forceinline__ void f16_epilogue_fast(const ConvArgs& a, const f32x4
 template <int MF, int NF, int ACT, bool RES>
 __device__ __forceinline__ void f16_epilogue_slow(const ConvArgs& a, const f32x4 (&acc)[MF][NF], const int (&mpix)[MF], int fw, int lq) {
     const _Float16* res = reinterpret_cast<const _Float16*>(a.res);
+    // the guard, folded: one integer max per stored value over the bits of |x| (positive floats order like unsigned integers, and
+    // the inf and NaN patterns lie above every finite one), compared once per lane: !(|x| <= 65504) <=> bits(|x|) > bits(65504)
+    unsigned mx = 0u;
 #pragma unroll
     for (int j = 0; j < NF; ++j) {
         const int co0 = (fw + j) * 16 + lq * 4;
@@ -127,10 +147,14 @@ __device__ __forceinline__ void f16_epilogue_slow(const ConvArgs& a, const f32x4
                 float x = f16e_act<ACT>(acc[f][j][r] + a.bias[min(co, a.n16 * 16 - 1)]);
                 if (RES) x += (float)res[(long long)m * a.res_cs + a.res_choff + co];
                 if (a.out_f32) a.out[(long long)m * a.out_cs + a.out_choff + co] = x;
-                else reinterpret_cast<_Float16*>(a.out)[(long long)m * a.out_cs + a.out_choff + co] = (_Float16)__builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f);
+                else {
+                    mx = max(mx, __builtin_bit_cast(unsigned, x) & 0x7FFFFFFFu);
+                    reinterpret_cast<_Float16*>(a.out)[(long long)m * a.out_cs + a.out_choff + co] = (_Float16)__builtin_amdgcn_fmed3f(x, -65504.0f, 65504.0f);
+                }
             }
         }
     }
+    if (a.f16_flag) range_raise(a.f16_flag, mx > 0x477FE000u);      // 0x477FE000: 65504.0f (every lane of the wave is back here: the loops above only skip)
 }
 
 // mpix[f] = linear output pixel of this lane's column of pixel fragment f, -1 = outside the tensor; `fast` from the kernel:

@@ -64,9 +64,7 @@ __device__ __forceinline__ f32x4 h2_decode4(const h16x4 h, const h16x4 m) {
     for (int r = 0; r < 4; ++r) v[r] = fmaf((float)m[r], kH2InvScale, (float)h[r]);
     return v;
 }
-__device__ __forceinline__ void h2_raise(unsigned* flag, bool bad) {
-    if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
-}
+__device__ __forceinline__ void h2_raise(unsigned* flag, bool bad) { range_raise(flag, bad); }      // conv_prims.h
 
 }  // namespace
 

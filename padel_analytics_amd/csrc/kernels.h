@@ -40,6 +40,8 @@ struct ConvArgs {
     int out_f32;          // fp16 / h2 kernels only: 1 = `out` is an fp32 buffer (convs that feed the Detect/Pose decode)
     const float* oscale;  // h2 kernels: [Npad] 1 / (power-of-two scale of the weight row), applied before the bias
     unsigned* ovf_flag;   // h2 kernels: set to 1 when an output value does not fit the fp16 range (h2_common.h)
+    unsigned* f16_flag;   // fp16 kernels: the same flag for the fp16 family (f16_epilogue.h), raised where a stored half was clamped or is
+                          // NaN; nullptr: no guard.  A field of its own: ovf_flag stays null in the launches of fp16 graphs
     int w_single;         // h2 kernels: 1 = the m plane of the packed weights is all zero (PA_CONV_W_SINGLE): the wm x ah product, its
                           // weight requests and operand reads are skipped — two MFMAs per operand pair (same results: the product is 0)
     const void* wr;       // h2 stride-1 3x3 layers with whole chunks: the weights once more in MFMA operand order [fragment][k-step][h | m][lane][16 B]
@@ -131,7 +133,7 @@ struct StemArgs {
     int out_cs, out_choff;
     int H, W, Ho, Wo, cout, B;
     int out_f16;          // 1: `out` is a _Float16 buffer (fp16 models; the stem itself computes in fp32); 2: h2 pairs
-    unsigned* ovf_flag;   // out_f16 == 2: raised when a value does not fit the fp16 range
+    unsigned* ovf_flag;   // out_f16 != 0: raised when a value does not fit the fp16 range (out_f16 == 1: on the value the clamp sees)
     unsigned howo_magic, howo_shift, wo_magic, wo_shift;   // filled by launch_stem (fill_fastdiv): pixel index -> (n, oy, ox)
     const void* opw;      // stem_l1_h2.hip: the stem's weights as MFMA operands + inverse row scales (launch_stem_l1_operands; nullptr: none)
 };

@@ -99,6 +99,7 @@ struct Builder {
             a.w_single = (o.flags & PA_CONV_W_SINGLE) && t.w_single ? 1 : 0;
             a.wr = operand_copy(i);
         }
+        if (f16) a.f16_flag = p.ovf;          // the fp16 family's range guard (f16_epilogue.h)
         ConvUp up{};
         const bool fold = (h2 || use_bx3) && t.fold_up && fold_src[i] >= 0;
         if (fold) {

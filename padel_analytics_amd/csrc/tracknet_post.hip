@@ -34,7 +34,8 @@ __global__ void __launch_bounds__(256) ball_assemble_kernel(const BallAssembleAr
     for (int c = 27; c < 32; ++c) v[c] = 0.0f;
     if (a.out_f16 == 1) {                // fp16 graph: 32 halves = 64 bytes per pixel, four 16-byte stores; (_Float16) rounds the table
                                          // value to nearest even.  The five pad channels are written too: their weights are zero, but
-                                         // 0 x (a stale NaN of the arena) is NaN
+                                         // 0 x (a stale NaN of the arena) is NaN.  No range test here (the fp16 family's guard,
+                                         // f16_epilogue.h): every value is a table entry u8 / 255 in [0, 1] or zero, in range by construction
         h16x8* o = reinterpret_cast<h16x8*>(reinterpret_cast<_Float16*>(a.out) + i * 32);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {

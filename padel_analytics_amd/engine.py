@@ -1026,7 +1026,8 @@ class Model:
         self.engine._check(self.engine.lib.pa_model_fill_arena(self.handle, int(byte_value)))
 
     def take_overflow(self) -> bool:
-        """h2 models: True if an activation written since the last call did not fit the fp16 range (clears the flag)."""
+        """h2 and fp16 models: True if an activation written since the last call did not fit the fp16 range (clears the flag);
+        fp16 models test the fp32 value they clamp, ``not (|x| <= 65504)``, NaN included.  Always False for fp32 models."""
         v = C.c_int(0)
         self.engine._check(self.engine.lib.pa_model_take_overflow(self.handle, C.byref(v)))
         return bool(v.value)

@@ -248,6 +248,10 @@ class Graph:
     out_channels: int = 0
     dtype: int = DTYPE_F32                        # storage type of activations / conv weights (pa_dtype)
     bx3: bool = True                              # fp32 graphs: also pack the bf16x3 (3-way split) weight planes
+    #: f16 graphs: a conv weight (BatchNorm folded) lies beyond +-65504, so the packed half is an infinity.  Such a graph must not
+    #: run: ``yolo.YOLO`` and ``BallTracker`` take the first step of their fallback ladder when they see it.  False for other dtypes.
+    f16_weight_overflow: bool = False
+    f16_overflow_layer: Optional[str] = None      # the first such conv: its ``name``, else "conv op <index>"
 
     @property
     def kalign(self) -> int:
@@ -282,13 +286,14 @@ class Graph:
         op.update(fields)
         self.ops.append(op)
 
-    def conv(self, src, dst, w, b, k, s, act, res=None, out_width=None, out_scale=None, res_preact=False):
+    def conv(self, src, dst, w, b, k, s, act, res=None, out_width=None, out_scale=None, res_preact=False, name=None):
         """src = (buf, choff, width read), dst = (buf, choff).  ``w`` is (cout, cin, k, k) with the
         real channel counts; input channels are zero-padded up to the slice width, output channels up
         to ``out_width`` (those rows are zero, so the kernel writes act(0) there).
         ``out_scale`` (h2 graphs only): per-output-channel factor applied to the accumulated sum before the bias — BatchNorm's
         scale kept out of the weights, so that a checkpoint's fp16 weights stay fp16 numbers (PA_CONV_W_SINGLE).
-        ``res_preact``: the residual is added BEFORE the activation, act(conv + bias + res) (PA_CONV_RES_PREACT)."""
+        ``res_preact``: the residual is added BEFORE the activation, act(conv + bias + res) (PA_CONV_RES_PREACT).
+        ``name``: the checkpoint's name of the layer, for messages (``f16_overflow_layer``)."""
         sb, so, sw = src
         cout, cin = w.shape[:2]
         if sw % self.kalign:
@@ -310,7 +315,11 @@ class Graph:
         flags = 0
         assert out_scale is None or self.dtype == DTYPE_H2, "out_scale: h2 graphs only"
         if self.dtype == DTYPE_F16:
-            w_off = self._add(np.ascontiguousarray(pack_conv_weight(wp, 32).astype(np.float16)).view(np.float32))
+            if not self.f16_weight_overflow and not bool((np.abs(wp) <= np.float32(65504.0)).all()):      # (NaN counts)
+                self.f16_weight_overflow = True
+                self.f16_overflow_layer = name or f"conv op {len(self.ops)}"
+            with np.errstate(over="ignore"):      # (a graph with f16_weight_overflow set is not run)
+                w_off = self._add(np.ascontiguousarray(pack_conv_weight(wp, 32).astype(np.float16)).view(np.float32))
         elif self.dtype == DTYPE_H2:
             planes, inv_scale = pack_conv_weight_h2(wp)
             if out_scale is not None:             # (1 / row scale is a power of two: the product is the scale's own bits)
@@ -455,7 +464,7 @@ def _yolo_parts(g: Graph, sd, prefix: str, perm=None):
 
 def _conv2d(g: Graph, sd, name: str, src, dst, act=ACT_NONE):
     """A 1x1 nn.Conv2d with its own bias and no BatchNorm (the last conv of a head branch, TrackNet's predictor)."""
-    g.conv(src, dst, np.asarray(sd[f"{name}.weight"], np.float32), np.asarray(sd[f"{name}.bias"], np.float32), 1, 1, act)
+    g.conv(src, dst, np.asarray(sd[f"{name}.weight"], np.float32), np.asarray(sd[f"{name}.bias"], np.float32), 1, 1, act, name=name)
 
 
 def _yolo_graph(info: dict, d, nc: int, kpt_shape: Optional[tuple], dtype: str):
@@ -501,7 +510,7 @@ def build_yolov8(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
 
     def cbs(prefix, src, dst, k, s, res=None, out_width=None):
         w, b, sc = _yolo_parts(g, sd, prefix)
-        g.conv(src, dst, w, b, k, s, ACT_SILU, res, out_width, out_scale=sc)
+        g.conv(src, dst, w, b, k, s, ACT_SILU, res, out_width, out_scale=sc, name=prefix)
 
     def nblocks(i):
         n = 0
@@ -597,9 +606,9 @@ def build_yolov8(sd, nc: int, kpt_shape: Optional[tuple] = None, dtype: str = "f
         if split_head(lvl, tot):
             for (br, wd, _, _), pw, o in zip(branches, widths, offs):
                 g.conv((feat, 0, chn), (h0, o), wcat[o:o + wd], bcat[o:o + wd], 3, 1, ACT_SILU, out_width=pw,
-                       out_scale=scat[o:o + wd] if use_sc else None)
+                       out_scale=scat[o:o + wd] if use_sc else None, name=f"model.22.{br}.{l}.0")
         else:
-            g.conv((feat, 0, chn), (h0, 0), wcat, bcat, 3, 1, ACT_SILU, out_scale=scat if use_sc else None)
+            g.conv((feat, 0, chn), (h0, 0), wcat, bcat, 3, 1, ACT_SILU, out_scale=scat if use_sc else None, name=f"model.22.*.{l}.0")
         hd = g.buf(lvl, head_cs)
         for (br, wd, nout, hoff), pw, o in zip(branches, widths, offs):
             h1 = g.buf(lvl, pw)
@@ -773,7 +782,7 @@ def build_tracknet(sd, dtype: str = "f32") -> Graph:
 
     def block(prefix, src, dst):
         w, b = fold_bn(sd, prefix, TRACKNET_BN_EPS)
-        g.conv(src, dst, w, b, 3, 1, ACT_RELU)
+        g.conv(src, dst, w, b, 3, 1, ACT_RELU, name=prefix)
 
     pool, up = g.maxpool2, g.upsample2x
     x0 = g.buf(0, cin0)

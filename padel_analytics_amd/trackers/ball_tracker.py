@@ -89,10 +89,11 @@ class BallTracker(Tracker):
         """``half=True`` runs the TrackNet stage like ``YOLO(half=True)``: fp16 activations and weights, fp32 accumulation, an
         fp32 sigmoid head map (BASELINE configs[4]).  Everything behind the head map — ensemble, threshold, locate — and the
         InpaintNet (always on its fp32-equivalent path) are the same as with ``half=False``, the default, which alone meets
-        the parity bar.  As with ``YOLO(half=True)`` there is no range guard: an activation beyond 65504 is stored as the
-        largest fp16 number by the conv epilogues and a weight beyond it becomes inf; the h2 path raises an overflow flag and
-        repeats on bf16x3, this one does not.  ``use_full_range()`` is the way back: it rebuilds the tracker on the default
-        fp32-equivalent path."""
+        the parity bar.  As with ``YOLO(half=True)`` the range is guarded: an activation that the conv epilogues have to clamp
+        to +-65504 raises the model's overflow flag, and the tracker then takes the route of the h2 path one step earlier — it
+        rebuilds itself on the default fp32-equivalent path (``use_full_range()``) and asks to be run again
+        (``engine.RangeOverflow``); should that path overflow too, the same route ends on bf16x3.  A checkpoint with a folded
+        weight beyond +-65504 takes the first step here, at construction: no model with an infinity in it is built."""
         super().__init__(load_path=load_path, save_path=save_path)
         ck = checkpoint.load_checkpoint(tracking_model_path)
         if ck.task != "tracknet":
@@ -104,7 +105,12 @@ class BallTracker(Tracker):
         self._state_dict = ck.state_dict
         self.fp32_mode = E.fp32_mode()           # "h2" (fp16 pairs, 3 products) or "bx3"; see yolo.YOLO
         self.half = bool(half)
+        self._model: Optional[E.Model] = None
         self.graph = G.build_tracknet(ck.state_dict, dtype="f16" if self.half else E.graph_dtype(self.fp32_mode))
+        if self.graph.f16_weight_overflow:
+            print(f"ball_tracker: a weight of {self.graph.f16_overflow_layer} lies beyond the fp16 range — half=True is not used for "
+                  f"this checkpoint; running on the default fp32-equivalent path")
+            self.use_full_range()
         self.inpaintnet = None
         if inpainting_model_path:
             ick = checkpoint.load_checkpoint(inpainting_model_path)
@@ -118,7 +124,6 @@ class BallTracker(Tracker):
         self.median_max_sample_num = median_max_sample_num
         self.median = median
         self.video_info = None
-        self._model: Optional[E.Model] = None
         self._engine: Optional[E.Engine] = None
 
     def video_info_post_init(self, video_info) -> "BallTracker":
@@ -137,8 +142,12 @@ class BallTracker(Tracker):
     def full_range(self) -> bool:
         return self.graph.dtype != G.DTYPE_H2
 
+    @property
+    def arithmetic(self) -> str:
+        return "f16" if self.half else "h2" if self.graph.dtype == G.DTYPE_H2 else "bx3" if self.fp32_mode == "bx3" else "f32"
+
     def use_full_range(self) -> None:
-        """h2 -> bf16x3 (after an overflow); a ``half=True`` tracker goes back to the default fp32-equivalent path."""
+        """One step of the ladder: h2 -> bf16x3; a ``half=True`` tracker goes back to the default fp32-equivalent path."""
         if self.half or self.graph.dtype == G.DTYPE_H2:
             if self._model is not None:
                 self._model.close()
@@ -260,11 +269,12 @@ class BallTracker(Tracker):
                 consume(sess.feed(video.host_batch(c), want_rects=True))
         consume(sess.feed(None, flush=True, want_rects=True))
         sess.close()
-        if self.graph.dtype == G.DTYPE_H2 and self._model.take_overflow():
+        if self.graph.dtype in (G.DTYPE_H2, G.DTYPE_F16) and self._model.take_overflow():
             # activations beyond the fp16 range: the stream has been consumed, so the caller (TrackingRunner) restarts
-            # this tracker; from now on it runs the full-range bf16x3 arithmetic
+            # this tracker; from now on it runs one step up the ladder (f16 -> the default path, h2 -> the full-range bf16x3)
             self.use_full_range()
-            raise E.RangeOverflow("TrackNet activations left the fp16 range: tracker switched to the bf16x3 path, run it again")
+            raise E.RangeOverflow(f"TrackNet activations left the fp16 range: tracker switched to the "
+                                  f"{'bf16x3' if self.arithmetic == 'bx3' else 'default fp32-equivalent'} path, run it again")
         if len(out) < n_fed:                       # fewer than 8 frames fed: no window, no detection (reference :688-696)
             out += [None] * (n_fed - len(out))
         return out[head_context:n_fed - tail_context]

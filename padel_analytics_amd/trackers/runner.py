@@ -441,26 +441,26 @@ class TrackingRunner:
         self.draw_and_collect_data()
 
     def _predict(self, tracker: Tracker, defer: Optional[list] = None) -> None:
-        """One tracker over the whole clip.  A stream tracker on the h2 arithmetic whose activations left the fp16
-        range has switched itself to the full-range path and asks to be run again (engine.RangeOverflow); batch
-        trackers repeat the offending batch themselves (yolo.YOLO.infer_frames).  ``defer``: Tracker.predict_and_update."""
+        """One tracker over the whole clip.  A stream tracker on the fp16 or the h2 arithmetic whose activations left the fp16
+        range has switched itself one step up the ladder f16 -> default -> bx3 and asks to be run again (engine.RangeOverflow):
+        at most twice; batch trackers repeat the offending batch themselves (yolo.YOLO.infer_frames).
+        ``defer``: Tracker.predict_and_update."""
         from .. import engine as E
-        if self.segments is not None:
-            try:
+
+        def once():
+            if self.segments is not None:
                 self._predict_segments(tracker)
+            else:
+                tracker.predict_and_update(self._frames(), defer=defer, total_frames=self.total_frames)
+
+        for _ in range(2):
+            try:
+                return once()
             except E.RangeOverflow as ex:
                 print(f"{str(tracker)}: {ex}")
                 tracker.restart()
                 tracker.to(tracker.DEVICE)
-                self._predict_segments(tracker)
-            return
-        try:
-            tracker.predict_and_update(self._frames(), defer=defer, total_frames=self.total_frames)
-        except E.RangeOverflow as ex:
-            print(f"{str(tracker)}: {ex}")
-            tracker.restart()
-            tracker.to(tracker.DEVICE)
-            tracker.predict_and_update(self._frames(), defer=defer, total_frames=self.total_frames)
+        once()
 
     def _predict_segments(self, tracker: Tracker) -> None:
         """One tracker over the kept frames, segment by segment.  A batch tracker's loop (``Tracker._predict_batches``) runs once per
@@ -569,17 +569,29 @@ class TrackingRunner:
                 print(f"{str(tracker)}: {ex}")
                 return None, True
 
-        was_full = tracker.full_range
+        # where the tracker stands on the ladder f16 -> default (h2) -> bx3; a tracker without the switch counts as at its end
+        def level():
+            return {"f16": 0, "h2": 1}.get(getattr(tracker, "arithmetic", None), 2)
+
+        was_full, was = tracker.full_range, level()
         partial, over = attempt()
-        # h2 -> bx3 is decided for ALL ranks at once: a rank whose shard overflowed (stream trackers raise, batch trackers
-        # switch inside the offending batch) must not leave the others waiting in the gather, and the merged result must
-        # come from one arithmetic.  Every rank enters this collective
-        if D.any_flag(over or (not was_full and tracker.full_range)):
-            print(f"{str(tracker)}: activations left the fp16 range on some rank — every rank repeats its shard on the bf16x3 path")
-            tracker.use_full_range()
+        # A step of the ladder is decided for ALL ranks at once: a rank whose shard overflowed (stream trackers raise, batch
+        # trackers switch inside the offending batch) must not leave the others waiting in the gather, and the merged result
+        # must come from one arithmetic.  Every rank enters these collectives; the ranks then stand where the furthest one
+        # stands (use_full_range is not called on a rank already there) and repeat.  At most twice: f16 -> default, default -> bx3
+        for _ in range(2):
+            if not D.any_flag(over or level() != was or (not was_full and tracker.full_range)):
+                break
+            target = 2 if D.any_flag(level() >= 2) else 1 if D.any_flag(level() >= 1) else 0
+            print(f"{str(tracker)}: activations left the fp16 range on some rank — every rank repeats its shard on the "
+                  f"{'bf16x3' if target == 2 else 'default fp32-equivalent'} path")
+            for _step in range(2):
+                if level() < target:
+                    tracker.use_full_range()
             tracker.to(tracker.DEVICE)
+            was_full, was = tracker.full_range, level()
             partial, over = attempt()
-            assert not over
+        assert not over
         assert len(partial) == hi - lo, (str(tracker), len(partial), lo, hi)
         # the partials travel as arrays (counts + rows per rank: two collectives, O(bytes)); trackers whose partials are not
         # arrays fall back to one pickled buffer per rank.  Every rank must take the same branch: agreed by a collective

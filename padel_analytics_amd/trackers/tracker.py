@@ -277,8 +277,9 @@ class Tracker(ABC):
         """Move the tracker's model(s) to ``device`` (weights go to HBM on "cuda")."""
 
     # ---- arithmetic of the fp32-equivalent path (engine.fp32_mode): the default "h2" covers |x| <= 65504 and switches a
-    # model to the full-range "bx3" kernels when an activation leaves that range.  A sharded run must take that decision
-    # for ALL ranks at once (TrackingRunner._predict_sharded), so trackers expose it
+    # model to the full-range "bx3" kernels when an activation leaves that range; a ``half=True`` model guards the same range
+    # and switches to the default path first.  One ladder: f16 -> default -> bx3.  A sharded run must take each step for ALL
+    # ranks at once (TrackingRunner._predict_sharded), so trackers expose where they stand
     @property
     def full_range(self) -> bool:
         """True when the tracker's model(s) cannot overflow any more (bx3 / fp16 models, or nothing to switch)."""
@@ -287,10 +288,26 @@ class Tracker(ABC):
             return bool(getattr(m, "half", False)) or m.fp32_mode != "h2"
         return True
 
-    def use_full_range(self) -> None:
-        """Put the tracker on the full-range arithmetic (rebuilds the packed graph; the HBM model follows on next use)."""
+    @property
+    def arithmetic(self) -> Optional[str]:
+        """What the next frame would run on: "f16" (``half=True``), "h2" (the default fp32-equivalent path), "bx3" (the full-range
+        one), "f32" (any other fp32 arithmetic), or None for a tracker without such a model."""
         m = getattr(self, "model", None)
-        if m is not None and hasattr(m, "set_fp32_mode"):
+        if m is None or not hasattr(m, "fp32_mode"):
+            return None
+        if getattr(m, "half", False):
+            return "f16"
+        return m.fp32_mode if m.fp32_mode in ("h2", "bx3") else "f32"
+
+    def use_full_range(self) -> None:
+        """One step up the ladder f16 -> default -> bx3 (rebuilds the packed graph; the HBM model follows on next use): a half model
+        goes to its ``fp32_mode``, an h2 model to the full-range arithmetic; nothing to do beyond that."""
+        m = getattr(self, "model", None)
+        if m is None:
+            return
+        if getattr(m, "half", False) and hasattr(m, "set_half"):
+            m.set_half(False)
+        elif hasattr(m, "set_fp32_mode"):
             m.set_fp32_mode("bx3")
 
     @abstractmethod

@@ -68,12 +68,16 @@ class YOLO:
     def __init__(self, model_path, engine: Optional[E.Engine] = None, half: bool = False, fp32_mode: Optional[str] = None):
         """``half=True`` is upstream's ``predict(half=True)`` / ``model.half()``: fp16 activations and weights with
         fp32 accumulation (BASELINE configs[4]).  The reference leaves it False (players_tracker.py:351-359), and
-        only the fp32 path meets the parity bar; the fp16 path reports its own error.
+        only the fp32 path meets the parity bar; the fp16 path reports its own error.  The fp16 kernels guard their range: a
+        value that has to be clamped to +-65504 (or is NaN) on its way into an activation buffer raises the model's overflow flag,
+        and this object then leaves ``half`` — it prints one line, sets ``half = False`` and ``fell_back = True``, rebuilds on
+        ``fp32_mode`` and repeats the batch there.  A checkpoint with a folded conv weight beyond +-65504 never runs in fp16: the
+        same step is taken at construction (``set_half(True)`` likewise).
 
         ``fp32_mode`` (``half=False`` only): "h2" — activations as fp16 pairs, three MFMA products per operand pair
         (default, ``engine.fp32_mode()``); "bx3" — exact bf16 triples, six products.  An h2 model whose activations
         leave the fp16 range (|x| > 65504) raises its overflow flag: the call is repeated on a bx3 model, which this
-        object then keeps using."""
+        object then keeps using.  One ladder: f16 -> ``fp32_mode`` -> bx3."""
         self.ckpt = checkpoint.load_checkpoint(model_path)
         if self.ckpt.task not in ("detect", "pose"):
             raise ValueError(f"{model_path}: not a YOLOv8 / YOLO11 detect/pose checkpoint (task {self.ckpt.task})")
@@ -82,15 +86,17 @@ class YOLO:
         self.kpt_shape = self.ckpt.kpt_shape
         self.half = bool(half)
         self.fp32_mode = fp32_mode or E.fp32_mode()
+        self.fell_back = False
+        self._no_half = False                 # this checkpoint's folded weights do not fit fp16 (found by _build)
         #: "yolov8" | "yolo11": which builder turns the state_dict into the engine's op list
         self.family = self.ckpt.family
         self.graph = self._build()
         self._engine = engine
         self._model: Optional[E.Model] = None
         self.max_batch = 64
-        #: set when an h2 model overflowed and this object rebuilt itself on the bx3 kernels (infer_frames); callers that
-        #: hold the old E.Model handle (bench, tests) or coordinate several ranks (TrackingRunner) read it
-        self.fell_back = False
+        #: set when an fp16 or h2 model overflowed and this object rebuilt itself one step up the ladder (infer_frames); callers that
+        #: hold the old E.Model handle (bench, tests) or coordinate several ranks (TrackingRunner) read it.  (Initialised above
+        #: _build: a checkpoint whose fp16 weights overflow sets it at construction.)
 
     def _graph_dtype(self) -> str:
         return "f16" if self.half else ("h2" if self.fp32_mode == "h2" else "f32")
@@ -99,14 +105,44 @@ class YOLO:
         if self.half and self.family == "yolo11":
             raise ValueError("half=True is not available for YOLO11 checkpoints: fp16 storage is not implemented for the depthwise "
                              "conv and the PSA attention (use the default fp32-equivalent path)")
-        return G.build_yolo(self.ckpt.state_dict, self.ckpt.nc, self.kpt_shape, dtype=self._graph_dtype(), family=self.family)
+        g = G.build_yolo(self.ckpt.state_dict, self.ckpt.nc, self.kpt_shape, dtype=self._graph_dtype(), family=self.family)
+        if g.f16_weight_overflow:
+            # the packed half of that weight is an infinity: this checkpoint never runs in fp16 (the first step of the ladder, now)
+            print(f"padel_analytics_amd: a weight of {g.f16_overflow_layer} lies beyond the fp16 range — half=True is not used for "
+                  f"this checkpoint; running on the {self._next_name()} path")
+            self.half = False
+            self.fell_back = True
+            self._no_half = True              # remembered: a later set_half(True) / predict(half=True) builds and prints nothing
+            g = G.build_yolo(self.ckpt.state_dict, self.ckpt.nc, self.kpt_shape, dtype=self._graph_dtype(), family=self.family)
+        return g
+
+    def _next_name(self) -> str:
+        return "bf16x3" if self.fp32_mode == "bx3" else "default fp32-equivalent (h2)"
+
+    @property
+    def arithmetic(self) -> str:
+        """What the next batch runs on: "f16" | "h2" | "bx3"."""
+        return "f16" if self.half else ("h2" if self.fp32_mode == "h2" else "bx3")
+
+    def _overflowed(self) -> None:
+        """The live model's flag was up: say so, take one step of the ladder f16 -> ``fp32_mode`` -> bx3, remember it."""
+        print(f"padel_analytics_amd: activations beyond the fp16 range — switching this model to the "
+              f"{self._next_name() if self.half else 'bf16x3'} path")
+        if self.half:
+            self.set_half(False)
+        else:
+            self.set_fp32_mode("bx3")
+        self.fell_back = True
 
     def _rebuild(self) -> None:
         self.close()
         self.graph = self._build()
 
     def set_half(self, half: bool) -> None:
-        """Switch precision (rebuilds the packed graph; the HBM-resident model is re-created on next use)."""
+        """Switch precision (rebuilds the packed graph; the HBM-resident model is re-created on next use).  On a checkpoint whose
+        folded weights do not fit fp16 ``set_half(True)`` changes nothing (it said so once, when that was found)."""
+        if half and self._no_half:
+            return
         if bool(half) != self.half:
             old, self.half = self.half, bool(half)
             try:
@@ -208,12 +244,12 @@ class YOLO:
                   pre_mode=pre_mode, channel_reverse=channel_reverse, letterbox_auto=True, reuse_outputs=reuse_outputs)
         m = self._ensure_model()
         boxes, kpts, counts = m.yolo_infer(src, n, h, w, **kw)
-        if self.graph.dtype == G.DTYPE_H2 and m.take_overflow():
-            # an activation left the fp16 range: this checkpoint needs the full-range arithmetic from now on
-            print(f"padel_analytics_amd: activations beyond the fp16 range — switching this model to the bf16x3 path")
-            self.set_fp32_mode("bx3")
-            self.fell_back = True
-            boxes, kpts, counts = self._ensure_model().yolo_infer(src, n, h, w, **kw)
+        if self.graph.dtype in (G.DTYPE_H2, G.DTYPE_F16) and m.take_overflow():
+            # an activation left the fp16 range: this checkpoint needs wider arithmetic from now on.  The batch is repeated one step
+            # up the ladder (an fp16 model lands on fp32_mode; if that is h2 and overflows too, this runs once more and ends on bx3)
+            self._overflowed()
+            return self.infer_frames(frames, conf, iou, imgsz, classes, max_det, channel_reverse=channel_reverse,
+                                     pil_stretch=pil_stretch, reuse_outputs=reuse_outputs)
         return boxes, kpts, counts, (h, w), int(imgsz), pre_mode
 
     # ---- the device stage in two halves (pa_yolo_submit / pa_yolo_wait): the trackers' batch loops submit batch k + 1 before
@@ -238,15 +274,13 @@ class YOLO:
 
     def collect_frames(self, token) -> tuple:
         """Results of a ``submit_frames`` token, in ``infer_frames``' form.  If an activation left the fp16 range (now or in
-        an earlier ticket, which replaced the model) the batch is computed again on the bf16x3 model, like ``infer_frames``."""
+        an earlier ticket, which replaced the model) the batch is computed again one step up the ladder, like ``infer_frames``."""
         m = token["model"]
         if m is not self._model:                     # the model this was submitted to is gone (overflow fallback in between)
             return self.infer_frames(token["frames"], *token["args"], reuse_outputs=True, **token["kw"])
         boxes, kpts, counts, ovf = m.yolo_wait(token["ticket"])
-        if ovf and self.graph.dtype == G.DTYPE_H2:
-            print(f"padel_analytics_amd: activations beyond the fp16 range — switching this model to the bf16x3 path")
-            self.set_fp32_mode("bx3")                # (closing the model drains its stream: later tickets die with it)
-            self.fell_back = True
+        if ovf and self.graph.dtype in (G.DTYPE_H2, G.DTYPE_F16):
+            self._overflowed()                       # (closing the model drains its stream: later tickets die with it)
             return self.infer_frames(token["frames"], *token["args"], reuse_outputs=True, **token["kw"])
         return (boxes, kpts, counts) + token["ret"]
 
