@@ -472,7 +472,10 @@ int pa_engine_timer_stop(pa_engine* eng, float* ms);
  * "variant" (forced tile id, -1 auto), "tune",
  * "tap_pd" (2|3), "graph" (hipGraph replay of the op list), "alias" (liveness-shared activation arena),
  * "timeline" (s_memtime-instrumented 3x3 kernel, dump to pa_engine_set_timeline_path),
- * "lanes" (2 = default: a YOLO model may run alternate in-flight tickets on a second lane, 1: one lane; PADEL_LANES) */
+ * "lanes" (2 = default: a YOLO model may run alternate in-flight tickets on a second lane, 1: one lane; PADEL_LANES),
+ * "fuse_stem_cv1" (1 = default: an h2 YOLOv8 graph computes model.2.cv1, the 1x1 conv behind model.1, inside the fused stem +
+ * model.1 kernel and never writes model.1's map, 0: that conv is a launch of its own; same bits; off while profiling or collecting
+ * a timeline; PADEL_FUSE_STEM_CV1; pa_model_last_stem_path tells which ran) */
 int pa_engine_set_tuning(pa_engine* eng, const char* key, int value);
 int pa_engine_set_timeline_path(pa_engine* eng, const char* path);
 
@@ -575,6 +578,9 @@ int pa_model_lanes_allocated(pa_model* m);
  * axis changes), 2 (both: the horizontal pass writes a temporary that the vertical pass reads; every lane has its own)       */
 int pa_yolo_resample_passes(pa_model* m);
 int pa_model_last_lane(pa_model* m);
+/* which form of the fused stem kernel the model's last replay of its op list launched: 1 stem + model.1 + the 1x1 conv behind it
+ * (tuning fuse_stem_cv1), 0 anything else (that conv ran as a launch of its own, or the graph has no such conv)                  */
+int pa_model_last_stem_path(pa_model* m);
 
 /* the u8 network input (NHWC4: R,G,B,0 as the network sees them) the last pa_yolo_infer call built from its
  * first n frames — byte-exact check of the letterbox (cv2 INTER_LINEAR) / Pillow-bicubic preprocessing */

@@ -37,6 +37,7 @@ static const struct Knob { const char* key; const char* env; int Tuning::*field;
     {"fuse_stem", "PADEL_FUSE_STEM", &Tuning::fuse_stem, knob_raw},
     {"fuse_sppf", "PADEL_FUSE_SPPF", &Tuning::fuse_sppf, knob_raw},
     {"fuse_head", "PADEL_FUSE_HEAD", &Tuning::fuse_head, knob_flag},
+    {"fuse_stem_cv1", "PADEL_FUSE_STEM_CV1", &Tuning::fuse_stem_cv1, knob_flag},
     {"w_single", nullptr, &Tuning::w_single, knob_flag},
 };
 
@@ -224,7 +225,7 @@ int pa_model_create(pa_engine* e, const pa_model_desc* desc, const float* weight
     std::vector<int> fold_dst;
     find_upsample_folds(m->d, m->fold_src, fold_dst);
     m->stem_fuse.resize(m->ops.size());
-    for (size_t i = 0; i < m->ops.size(); ++i) m->stem_fuse[i] = stem_fusable(m->d, i);
+    for (size_t i = 0; i < m->ops.size(); ++i) m->stem_fuse[i] = stem_cv1_fusable(m->d, i) ? 2 : stem_fusable(m->d, i) ? 1 : 0;
     m->tail = find_head_tail(m->d, m->fold_src);
     m->n_w = n_floats;
     if (desc->task == PA_TASK_DETECT || desc->task == PA_TASK_POSE)
@@ -403,7 +404,7 @@ static hipError_t launch_step(const Step& st, const ConvArgs& a, hipStream_t s) 
     const SliceArgs& v = st.sl;
     switch (st.kind) {
         case PA_OP_CONV: return launch_conv_family(st.family, a, st.ran.tile, s);
-        case PA_OP_STEM: return st.n_ops == 2 ? launch_stem_l1_h2(st.stem, a, s) : launch_stem(st.stem, s);
+        case PA_OP_STEM: return st.n_ops == 2 ? launch_stem_l1_h2(st.stem, a, nullptr, s) : launch_stem(st.stem, s);
         case PA_OP_SPPF_POOL: return launch_sppf_pool(v.in, v.in_cs, v.in_choff, v.c, v.B, v.H, v.W, s, v.fmt, v.fused);
         case PA_OP_UPSAMPLE2X: return launch_upsample2x(v.in, v.in_cs, v.in_choff, v.out, v.out_cs, v.out_choff, v.c, v.B, v.H, v.W, s, v.fmt);
         case PA_OP_MAXPOOL2: return launch_maxpool2(v.in, v.in_cs, v.in_choff, v.out, v.out_cs, v.out_choff, v.c, v.B, v.H, v.W, s, v.fmt);
@@ -453,8 +454,20 @@ int run_tail_ops(pa_model* m, Lane& L, hipStream_t s, int n) {
 static int run_ops(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi, bool skip_tail) {
     pa_engine* e = m->e;
     if (plan_steps(m, L, n)) return 1;
+    // the 1x1 behind a fused stem + layer 1 inside that kernel (tuning fuse_stem_cv1, decided per step by build_steps): not while
+    // profiling or collecting a timeline, which keep that conv's row
+    const bool cv1_fused = !e->profiling && !e->t.timeline;
+    m->last_stem_path = 0;
     for (const Step& st : L.steps) {
         if (skip_tail && st.tail) continue;          // the heads' last convs run inside the fused head tail (run_post)
+        if (cv1_fused && st.stem_cv1) continue;      // ran inside the stem's kernel
+        if (cv1_fused && st.kind == PA_OP_STEM && st.n_ops == 2 && st.has_cv1) {
+            const hipError_t r = launch_stem_l1_h2(st.stem, st.conv, &st.cv1, s);
+            if (r != hipSuccess) PA_FAIL(e, "fused stem + layer 1 + 1x1 launch failed: %s", hipGetErrorString(r));
+            m->last_stem_path = 1;
+            ++*pi;                                   // (its record stays unused: no profile is being taken)
+            continue;
+        }
         ProfRec* pr = prof_begin(m, s, (*pi)++, st.kind, st.ksize, st.flops);
         if (pr) {
             pr->M = st.M; pr->cout = st.cout; pr->cin = st.cin; pr->stride = st.stride; pr->mf = st.mf; pr->nf = st.nf; pr->res = st.res;
@@ -546,8 +559,10 @@ int run_graph(pa_model* m, Lane& L, hipStream_t s, int n, size_t* pi, bool skip_
         hipGraphDestroy(g);
         if (ri != hipSuccess) PA_FAIL(e, "hipGraphInstantiate: %s", hipGetErrorString(ri));
         it = L.graphs.emplace(n, ge).first;
+        L.graph_stem_path[n] = m->last_stem_path;          // what the capture launched is what every replay of it launches
     }
     PA_HIP(e, hipGraphLaunch(it->second, s));
+    m->last_stem_path = L.graph_stem_path[n];
     return 0;
 }
 
@@ -589,6 +604,8 @@ int pa_model_lanes_allocated(pa_model* m) {
 }
 
 int pa_model_last_lane(pa_model* m) { return m ? m->last_lane : 0; }
+
+int pa_model_last_stem_path(pa_model* m) { return m ? m->last_stem_path : 0; }
 
 int pa_model_profile_text(pa_model* m, char* buf, size_t cap) {
     size_t off = 0;

@@ -156,6 +156,7 @@ struct Lane {
     DevMem<float> d_oboxes, d_okpts; DevMem<int32_t> d_ocnt;
     std::vector<Step> steps;               // the launches of the replay being enqueued (build_steps): rebuilt per call, capacity kept
     std::map<int, hipGraphExec_t> graphs;  // op-list replay per batch size (tuning "graph")
+    std::map<int, int> graph_stem_path;    // ... and the pa_model_last_stem_path of each capture
     DevMem<uint8_t> d_rs_tmp;              // lane 1: its own temporary between the resample passes (lane 0 uses the plan's)
     LaneState st;                          // pick_lane's view
     size_t device_bytes() const {          // what the lane holds on the device (pa_model::lane_bytes)
@@ -170,7 +171,8 @@ struct pa_model {
     std::vector<pa_buf_desc> bufs;
     std::vector<pa_op_desc> ops;
     std::vector<int> fold_src;             // conv op i -> index of the upsample op it can absorb (-1: none), find_upsample_folds
-    std::vector<char> stem_fuse;           // op i -> stem_fusable (the stem and the stride-2 3x3 behind it can run as one kernel)
+    std::vector<char> stem_fuse;           // op i -> 1: stem_fusable (the stem and the stride-2 3x3 behind it can run as one kernel), 2: stem_cv1_fusable
+                                           // too (and the 1x1 behind that conv), 0: neither
     HeadTail tail;                         // the heads' last 1x1 convs, if the graph ends the way find_head_tail wants it
     DevMem<float> d_w;
     size_t n_w = 0;
@@ -214,6 +216,7 @@ struct pa_model {
     DevMem<int32_t> d_classes;
     int last_n = 0;
     int last_post_path = 0;                // pa_yolo_last_post_path: 0 decode_kernel on head maps, 1 the fused head tail
+    int last_stem_path = 0;                // pa_model_last_stem_path: 1 the last replay ran the 1x1 behind layer 1 inside the fused stem kernel
     bool heads_stale = false;              // the last call ran the fused head tail: the head maps are not there (pa_yolo_read_head computes them)
     std::vector<ProfRec> prof;
     size_t n_prof = 0;

@@ -208,6 +208,25 @@ bool stem_fusable(const pa_model_desc& d, size_t i) {
     return true;
 }
 
+bool stem_cv1_fusable(const pa_model_desc& d, size_t i) {
+    if (d.dtype != PA_DTYPE_H2 || !stem_fusable(d, i) || i + 2 >= (size_t)d.n_ops) return false;
+    const pa_op_desc& l1 = d.ops[i + 1];
+    const pa_op_desc& c = d.ops[i + 2];
+    if (l1.act != PA_ACT_SILU || !(l1.flags & PA_CONV_W_SINGLE) || is_head_buf(d, l1.out_buf)) return false;
+    if (c.kind != PA_OP_CONV || c.ksize != 1 || c.stride != 1 || c.act != PA_ACT_SILU || !(c.flags & PA_CONV_W_SINGLE) || c.res_buf >= 0) return false;
+    if (c.in_buf != l1.out_buf || c.in_choff != l1.out_choff || c.cin != l1.cout) return false;      // all of layer 1's output, nothing else
+    if (c.out_buf == l1.out_buf || c.out_buf == d.ops[i].out_buf) return false;
+    for (size_t k = 0; k < (size_t)d.n_ops; ++k) {          // layer 1's map has no other reader (any op that touches its buffer counts)
+        if (k == i + 1 || k == i + 2) continue;
+        const pa_op_desc& o = d.ops[k];
+        const bool reads_in = o.kind != PA_OP_STEM && o.kind != PA_OP_STEM7;
+        if (reads_in && o.in_buf == l1.out_buf) return false;
+        if ((o.kind == PA_OP_CONV || o.kind == PA_OP_DWCONV3) && o.res_buf == l1.out_buf) return false;
+        if (o.kind != PA_OP_GAP_FC && o.out_buf == l1.out_buf) return false;      // nor another writer: its bytes are not there
+    }
+    return true;
+}
+
 HeadTail find_head_tail(const pa_model_desc& d, const std::vector<int>& fold_src) {
     HeadTail none, t;
     if ((d.task != PA_TASK_DETECT && d.task != PA_TASK_POSE) || d.dtype != PA_DTYPE_H2 || d.nc < 1 || d.nk < 0) return none;

@@ -19,6 +19,10 @@ int validate_desc(const pa_model_desc* d, size_t n_floats, std::string& err);
 void find_upsample_folds(const pa_model_desc& d, std::vector<int>& fold_src, std::vector<int>& fold_dst);
 // op i is the stem, op i + 1 a 3x3 stride-2 conv over exactly the stem's channels, and nothing else reads the stem's output
 bool stem_fusable(const pa_model_desc& d, size_t i);
+// ... and, in an h2 graph, op i + 2 is a 1x1 stride-1 conv with SiLU and no residual that reads ALL of op i + 1's output and nothing
+// else, both convs are two-product layers (PA_CONV_W_SINGLE), op i + 1 has SiLU, and no other op reads or writes op i + 1's buffer
+// (model.2.cv1 behind model.1 of a YOLOv8 graph): the fused stem kernel may compute op i + 2 as well and never write op i + 1's map
+bool stem_cv1_fusable(const pa_model_desc& d, size_t i);
 
 // The tail of a Detect / Pose head of an h2 model: on every level the ops that write head_buf[l] are exactly a 1x1, stride-1 conv
 // without activation or residual for the 64 box logits (channel 0), one for the nc class logits (channel 64) and, iff nk > 0, one

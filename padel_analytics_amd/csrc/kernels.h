@@ -142,7 +142,11 @@ struct ConvArgs;
 // stem_l1_h2.hip: stem + the 3x3 stride-2 conv behind it, one kernel.  Whether it covers a pair reads the two argument structs and
 // nothing else (launch_plan.cpp: host code, asked where the launch is planned and once more by the launcher)
 bool stem_l1_h2_supported(const StemArgs& st, const ConvArgs& cv);
-hipError_t launch_stem_l1_h2(const StemArgs& st, const ConvArgs& cv, hipStream_t s);
+// ... and, as a third phase of the same kernel, the 1x1 stride-1 conv `cv1` that is the only reader of that conv's map (model.2.cv1
+// of a YOLOv8 graph; graph_plan.h: stem_cv1_fusable): the register-weights instantiations, two-product layers, SiLU behind layer 1,
+// cv1 over all of layer 1's 2c channels with 2c outputs and an operand-order weight copy.  Layer 1's map is not written then
+bool stem_l1_cv1_h2_supported(const StemArgs& st, const ConvArgs& cv, const ConvArgs& cv1);
+hipError_t launch_stem_l1_h2(const StemArgs& st, const ConvArgs& cv, const ConvArgs* cv1, hipStream_t s);      // cv1 == nullptr: two phases
 // the stem operand block of its register-weights instantiations (cout = 16 / 32 / 48): per 16-channel fragment 2 KB [h | m][lane][16 B]
 // of w / 255 row-scaled and split into fp16 pairs, then the cout inverse row scales.  Built from the blob's [cout][27] stem weights
 size_t stem_l1_operand_bytes(int cout);                                   // launch_plan.cpp

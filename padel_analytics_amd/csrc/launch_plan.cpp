@@ -34,6 +34,16 @@ bool stem_l1_h2_supported(const StemArgs& st, const ConvArgs& a) {
            a.ovf_flag && !a.in2 && !a.res && (st.Ho & 1) == 0 && (st.Wo & 1) == 0;
 }
 
+// ... with cv1, a 1x1 stride-1 conv over exactly that conv's 2c outputs with 2c outputs of its own, as the kernel's third phase.  The
+// first line is what launch_stem_l1_h2 asks before it picks a register-weights instantiation: the third phase exists in those only
+bool stem_l1_cv1_h2_supported(const StemArgs& st, const ConvArgs& a, const ConvArgs& b) {
+    return stem_l1_h2_supported(st, a) && a.w_single && a.wr && st.opw && (st.W & 3) == 0 && !(a.tune & 8) &&
+           a.act == ACT_SILU && !a.out_f32 && a.out &&
+           b.ksize == 1 && b.stride == 1 && b.cin == a.cout && b.cout == a.cout && b.n16 * 16 == b.cout && b.H == a.Ho && b.W == a.Wo &&
+           b.Ho == a.Ho && b.Wo == a.Wo && b.M == a.M && b.in == a.out && b.in_cs == a.out_cs && b.in_choff == a.out_choff &&
+           b.w_single && b.wr && b.w && b.bias && b.oscale && b.out && b.ovf_flag && !b.in2 && !b.res;
+}
+
 size_t stem_l1_operand_bytes(int cout) { return (size_t)(cout / 16) * 2048 + (size_t)cout * sizeof(float); }
 
 size_t operand_copy_offsets(const pa_model_desc& d, const std::vector<char>& stem_fuse, std::vector<long long>& off) {
@@ -46,7 +56,10 @@ size_t operand_copy_offsets(const pa_model_desc& d, const std::vector<char>& ste
             total += (stem_l1_operand_bytes(o.cout) + 2047) / 2048 * 2048;
             continue;
         }
-        if (o.kind != PA_OP_CONV || !conv_wants_operand_copy(o.ksize, o.stride, o.cin, (o.flags & PA_CONV_W_SINGLE) != 0)) continue;
+        // (the 1x1 behind a fused stem + layer 1 is read from a copy at every width: conv_wants_operand_copy stops at cin = 64, and
+        //  the third phase of stem_l1_h2.hip also takes the 32 -> 32 layer of a yolov8n graph)
+        const bool stem_cv1 = i >= 2 && stem_fuse[i - 2] == 2;
+        if (o.kind != PA_OP_CONV || !(stem_cv1 || conv_wants_operand_copy(o.ksize, o.stride, o.cin, (o.flags & PA_CONV_W_SINGLE) != 0))) continue;
         off[i] = (long long)total;
         total += conv_h2r_copy_bytes(o.npad / 16, o.cin, o.ksize);
     }
@@ -143,12 +156,14 @@ int build_steps(const pa_model_desc& d, const std::vector<int>& fold_src, const 
     const Builder b{d, fold_src, t, p, net_h, net_w, n};
     const bool h2 = d.dtype == PA_DTYPE_H2;
     out.clear();
+    int cv1_op = -1;          // the conv that the fused stem step in front of it also carries (Step::has_cv1)
     for (int i = 0; i < d.n_ops; ++i) {
         const pa_op_desc& o = d.ops[i];
         const pa_buf_desc& ob = d.bufs[o.out_buf];
         const int Ho = net_h >> ob.level, Wo = net_w >> ob.level;
         Step st{};
         st.op = i; st.n_ops = 1; st.kind = o.kind; st.ran = ConvLaunched{-1, ""};
+        st.stem_cv1 = i == cv1_op;
         for (int l = 0; l < 3 && tail.found; ++l)
             for (int c = 0; c < 3; ++c) st.tail = st.tail || tail.op[l][c] == i;
         if (o.kind == PA_OP_CONV) {
@@ -172,8 +187,18 @@ int build_steps(const pa_model_desc& d, const std::vector<int>& fold_src, const 
             // its own (the profile shows both under the stem's record)
             if (t.fuse_stem && h2 && stem_fuse[i]) {
                 b.conv(i + 1, st);
-                if (stem_l1_h2_supported(st.stem, st.conv)) { st.n_ops = 2; ++i; }
-                else st.conv = ConvArgs{};              // two launches: the conv has its own turn
+                if (stem_l1_h2_supported(st.stem, st.conv)) {
+                    st.n_ops = 2;
+                    // tuning "fuse_stem_cv1": the 1x1 behind layer 1 (its only reader: stem_fuse == 2) as the kernel's third phase.
+                    // That conv KEEPS its step, marked `stem_cv1`: a replay that profiles or collects a timeline runs it there
+                    if (t.fuse_stem_cv1 && stem_fuse[i] == 2) {
+                        Step c1{};
+                        if (b.conv(i + 2, c1) && stem_l1_cv1_h2_supported(st.stem, st.conv, c1.conv)) { st.cv1 = c1.conv; st.has_cv1 = true; cv1_op = i + 2; }
+                    }
+                    ++i;
+                } else {
+                    st.conv = ConvArgs{};              // two launches: the conv has its own turn
+                }
                 st.path = st.requested = 0; st.family = CONV_TAP; st.ran = ConvLaunched{-1, ""};          // (a stem's row names no conv kernel)
             }
         } else if (o.kind == PA_OP_SPPF_POOL) {

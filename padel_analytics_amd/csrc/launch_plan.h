@@ -24,6 +24,10 @@ struct Tuning {
     int timeline = 0;    // 1: 3x3 tap launches of the 64x96 tile run the s_memtime-instrumented instantiation
     int alias = 1;       // 1: activation buffers share one arena by liveness, 0: disjoint ranges
     int fuse_stem = 1;   // 1: h2 YOLOv8 graphs run model.0 (stem) + model.1 (3x3 stride 2) as ONE kernel (stem_l1_h2.hip; default since round 4, 0 = two kernels)
+    int fuse_stem_cv1 = 1;   // 1: where the op behind a fused stem + layer 1 is a 1x1 stride-1 two-product SiLU conv over all of layer 1's channels
+                         // and layer 1's only reader (model.2.cv1; graph_plan.h: stem_cv1_fusable), the kernel computes it too and layer 1's
+                         // map is never written; 0: that conv is a launch of its own.  Bitwise the same maps; off while profiling or collecting
+                         // a timeline (the profile keeps the conv's row)
     int w_single = 1;    // 1 (default): h2 convs whose packed weights have an all-zero m plane (PA_CONV_W_SINGLE) skip the wm x ah product;
                          // 0 (tests): all three products everywhere — bitwise the same results
     int fuse_sppf = 1;   // 1: h2 graphs run the three chained 5x5 max-pools of SPPF as ONE kernel (sppf_h2_kernel: keys in LDS, separable passes); 0 = three launches.  Bitwise the same maps
@@ -85,6 +89,11 @@ struct Step {
     int kind;                    // pa_op_desc::kind of `op`
     bool tail;                   // one of HeadTail::op[][]: the fused head tail runs it in place of this step
     ConvArgs conv;               // PA_OP_CONV, and layer 1 of a fused stem
+    // The 1x1 behind layer 1 inside the fused stem kernel (tuning fuse_stem_cv1; stem_l1_cv1_h2_supported).  The stem's step carries
+    // that conv's arguments (has_cv1, cv1), the conv's own step is marked stem_cv1: a plain replay launches (stem, conv, cv1) as one
+    // kernel and leaves the marked step out; a replay that profiles or collects a timeline launches both steps as they are
+    bool has_cv1, stem_cv1;
+    ConvArgs cv1;
     int path;                    // ConvPath
     int requested;               // tile id asked for
     ConvFamily family;           // what it resolved to ...

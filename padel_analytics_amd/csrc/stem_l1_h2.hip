@@ -91,9 +91,19 @@ __global__ void __launch_bounds__(64) stem_l1_operands_kernel(const float* __res
 // phase 2 has NO per-step barrier and no weight stages in LDS (a step is 2 x NF x 2 = 12 MFMAs per wave at c = 48 — 192 pipe
 // cycles that used to sit behind a barrier, a ring wait and NF weight reads each).  The barriers that remain publish the stem's
 // planes (one, two more around the c = 48 tail planes).
-template <int NF, bool WS = false, bool WR = false>
-__global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, const ConvArgs a) {
+//
+// CV1 (register weights only): `b` is the 1x1 stride-1 two-product conv that is the only reader of layer 1's map (model.2.cv1 of a
+// YOLOv8 graph: 2c -> 2c), computed here as a THIRD phase — layer 1's map is never written.  The phase-2 epilogue computes what
+// h2_epilogue computes (h2_conv_value, SiLU, clamp, pair encoding, the range check) and puts the pairs into LDS operand planes in
+// the region of the stem planes, which are dead by then: per 32-channel k-step an h and an m plane of 64 pixels x 64 bytes, slot
+// swz_off(pixel, q) as the 1x1 kernels read theirs.  Phase 3 walks the NF k-steps (2c / 32 = NF) with the accumulation order of
+// conv_h2_1_kernel — cross += wh x am per step, the main product as one block flushed into acc — on weights read global -> VGPR
+// from cv1's operand-order copy (requested before the phase-2 epilogue: they land under it), and ends in the ordinary h2_epilogue
+// on cv1's arguments.  Bitwise the two launches it replaces.
+template <int NF, bool WS = false, bool WR = false, bool CV1 = false>
+__global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, const ConvArgs a, const ConvArgs b) {
     static_assert(!WR || WS, "register weights: two-product layers");
+    static_assert(!CV1 || WR, "the third phase: register-weights instantiations only");
     constexpr bool CHUNK = NF >= 2, TAIL = (NF & 1) != 0;
     constexpr int NCF = CHUNK ? 2 : 0;               // stem fragments that form the 32-channel chunk
     constexpr int MF = 2;
@@ -104,6 +114,8 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
     constexpr int NSTG = 3;                          // weight ring: step T + 2 is requested while step T computes (a layer-1 step
                                                      // is 18 MFMAs per wave: with a 2-stage ring every step waited out a DMA round trip)
     static_assert(S_B + NSTG * BSTAGE_B + 1024 <= 80 * 1024, "2 workgroups per CU");
+    constexpr int kC1PlaneB = 64 * 64;               // CV1: one operand plane of the tile's 64 pixels (a k-step: h plane, then m plane)
+    static_assert(!CV1 || NF * 2 * kC1PlaneB <= S_B, "cv1's operand planes take the place of the stem planes");
     constexpr int WSTG_B = WR ? 0 : NSTG * BSTAGE_B;               // (register weights: no weight stages)
     constexpr int XTRA_B = WR ? (kStemPatchB + 15) / 16 * 16 : 1024;    // register weights: the input patch; else the inverse row scales
     __shared__ __attribute__((aligned(16))) float lds[(S_B + WSTG_B + XTRA_B) / 4];
@@ -548,6 +560,84 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
     const int fw = NF * wc;
     const bool fast = oy0 + 4 <= a.Ho && ox0 + 16 <= a.Wo && (fw + NF) * 16 <= a.cout && (((a.out_choff | a.out_cs) & 3) == 0) &&
                       (!a.res || (((a.res_choff | a.res_cs) & 3) == 0));
+    if constexpr (CV1) {
+        // ---- phase 3.  cv1's weights: fragment fw + j, k-step ks of its operand-order copy (h planes: two products)
+        const char* const wr3 = reinterpret_cast<const char*>(b.wr) + (long long)fw * (NF * 2048) + lane * 16;
+        i32x4 w3[NF][NF];
+#pragma unroll
+        for (int j = 0; j < NF; ++j)
+#pragma unroll
+            for (int ks = 0; ks < NF; ++ks) w3[j][ks] = *reinterpret_cast<const i32x4*>(wr3 + (j * NF + ks) * 2048);
+        f32x4 b1[NF], sc1[NF];
+#pragma unroll
+        for (int j = 0; j < NF; ++j) {
+            b1[j] = *reinterpret_cast<const f32x4*>(a.bias + (fw + j) * 16 + lq * 4);
+            sc1[j] = *reinterpret_cast<const f32x4*>(a.oscale + (fw + j) * 16 + lq * 4);
+        }
+        // the range check of the epilogue layer 1 would have taken: the pair path tests the packed h halves, the element-wise path
+        // (partial tiles, slices that are no whole groups) the values of the pixels inside the map
+        const bool wide1 = fast && (((a.out_choff | a.out_cs) & 15) == 0);
+        bool bad1 = false;
+        h2_u16x2 top = {0, 0};
+        __builtin_amdgcn_s_barrier();                // every wave has read its last stem plane operands
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int j = 0; j < NF; ++j)
+#pragma unroll
+            for (int f = 0; f < MF; ++f) {
+                f32x4 v;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = h2_act<ACT_SILU>(h2_conv_value(cross[f][j][r], acc[f][j][r], sc1[j][r], b1[j][r]));
+                h16x4 hv, mv;
+                bool oor = false;
+                h2_encode4(v, hv, mv, oor);
+                const u32x2 hd = __builtin_bit_cast(u32x2, hv);
+                top = __builtin_elementwise_max(top, __builtin_bit_cast(h2_u16x2, hd[0] & 0x7FFF7FFFu));
+                top = __builtin_elementwise_max(top, __builtin_bit_cast(h2_u16x2, hd[1] & 0x7FFF7FFFu));
+                bad1 = bad1 || (oor && mpix[f] >= 0);
+                // channel 16 (fw + j) + 4 lq + r of pixel (2 wr + f, lr): k-step (fw + j) / 2, K slots 16 ((fw + j) & 1) + 4 lq + r
+                const int fr = fw + j;
+                char* const op = ldsb + (fr >> 1) * (2 * kC1PlaneB) + swz_off((2 * wr + f) * 16 + lr, ((fr & 1) << 1) | (lq >> 1)) + (lq & 1) * 8;
+                *reinterpret_cast<h16x4*>(op) = hv;
+                *reinterpret_cast<h16x4*>(op + kC1PlaneB) = mv;
+            }
+        h2_raise(a.ovf_flag, wide1 ? (top[0] >= 0x7BFFu || top[1] >= 0x7BFFu) : bad1);
+        lds_fence();
+        __builtin_amdgcn_s_barrier();                // the planes are published
+        asm volatile("" ::: "memory");
+        f32x4 acc3[MF][NF], part3[MF][NF], cross3[MF][NF];
+#pragma unroll
+        for (int f = 0; f < MF; ++f)
+#pragma unroll
+            for (int j = 0; j < NF; ++j) { acc3[f][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; part3[f][j] = acc3[f][j]; cross3[f][j] = acc3[f][j]; }
+#pragma unroll
+        for (int ks = 0; ks < NF; ++ks) {
+            h16x8 ah3[MF], am3[MF];
+#pragma unroll
+            for (int f = 0; f < MF; ++f) {
+                const char* const p_ = ldsb + ks * (2 * kC1PlaneB) + swz_off((2 * wr + f) * 16 + lr, lq);
+                ah3[f] = *reinterpret_cast<const h16x8*>(p_);
+                am3[f] = *reinterpret_cast<const h16x8*>(p_ + kC1PlaneB);
+            }
+#pragma unroll
+            for (int f = 0; f < MF; ++f)
+#pragma unroll
+                for (int j = 0; j < NF; ++j)
+                    cross3[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, w3[j][ks]), am3[f], cross3[f][j], 0, 0, 0);
+#pragma unroll
+            for (int f = 0; f < MF; ++f)
+#pragma unroll
+                for (int j = 0; j < NF; ++j)
+                    part3[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, w3[j][ks]), ah3[f], part3[f][j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int f = 0; f < MF; ++f)
+#pragma unroll
+            for (int j = 0; j < NF; ++j) acc3[f][j] += part3[f][j];
+        // (cv1 is 1x1, stride 1: its output pixels are layer 1's)
+        const bool fast3 = oy0 + 4 <= a.Ho && ox0 + 16 <= a.Wo && (fw + NF) * 16 <= b.cout && (((b.out_choff | b.out_cs) & 3) == 0);
+        h2_epilogue<MF, NF>(b, acc3, cross3, mpix, fw, lq, fast3);
+    } else {
 #if defined(PADEL_STEM_PROBE) && (PADEL_STEM_PROBE == 4 || PADEL_STEM_PROBE == 5)
     ConvArgs a_lin = a;                              // probe: layer 1's epilogue without its SiLU (wrong results)
     a_lin.act = ACT_NONE;
@@ -555,6 +645,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
 #else
     h2_epilogue<MF, NF>(a, acc, cross, mpix, fw, lq, fast);
 #endif
+    }
 }
 
 // (what the kernel covers — stem_l1_h2_supported — and the size of its operand block are host code: launch_plan.cpp)
@@ -564,34 +655,44 @@ hipError_t launch_stem_l1_operands(const float* w, int cout, void* blk, hipStrea
     return hipGetLastError();
 }
 
-hipError_t launch_stem_l1_h2(const StemArgs& st, const ConvArgs& a_in, hipStream_t s) {
-    if (!stem_l1_h2_supported(st, a_in)) return hipErrorNotSupported;
+// cv1 (nullptr: none): the 1x1 conv behind layer 1, computed in the same kernel (stem_l1_cv1_h2_supported)
+hipError_t launch_stem_l1_h2(const StemArgs& st, const ConvArgs& a_in, const ConvArgs* cv1, hipStream_t s) {
+    if (!stem_l1_h2_supported(st, a_in) || (cv1 && !stem_l1_cv1_h2_supported(st, a_in, *cv1))) return hipErrorNotSupported;
     ConvArgs a = a_in;
+    const ConvArgs b = cv1 ? *cv1 : ConvArgs{};
     const int batch = a.M / (a.Ho * a.Wo);
     a.n_mtiles = batch * ((a.Ho + 3) / 4) * ((a.Wo + 15) / 16);
     a.n_ntiles = 1;
     dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8), 1, 1);
     // register weights (tuning bit 3: the round-5 weight ring).  They read the stem operand block and stage the input in 16-byte
     // chunks of 4 pixels: W % 4 == 0
+    if (cv1) {
+        switch (st.cout / 16) {
+            case 1: hipLaunchKernelGGL((stem_l1_h2_kernel<1, true, true, true>), grid, dim3(256), 0, s, st, a, b); return hipGetLastError();
+            case 2: hipLaunchKernelGGL((stem_l1_h2_kernel<2, true, true, true>), grid, dim3(256), 0, s, st, a, b); return hipGetLastError();
+            case 3: hipLaunchKernelGGL((stem_l1_h2_kernel<3, true, true, true>), grid, dim3(256), 0, s, st, a, b); return hipGetLastError();
+            default: return hipErrorNotSupported;
+        }
+    }
     if (a.w_single && a.wr && st.opw && (st.W & 3) == 0 && !(a.tune & 8)) {
         switch (st.cout / 16) {
-            case 1: hipLaunchKernelGGL((stem_l1_h2_kernel<1, true, true>), grid, dim3(256), 0, s, st, a); return hipGetLastError();
-            case 2: hipLaunchKernelGGL((stem_l1_h2_kernel<2, true, true>), grid, dim3(256), 0, s, st, a); return hipGetLastError();
+            case 1: hipLaunchKernelGGL((stem_l1_h2_kernel<1, true, true>), grid, dim3(256), 0, s, st, a, b); return hipGetLastError();
+            case 2: hipLaunchKernelGGL((stem_l1_h2_kernel<2, true, true>), grid, dim3(256), 0, s, st, a, b); return hipGetLastError();
             // (3 workgroups per CU — the LDS would allow them: 3 x 46 KB — need 168 VGPRs; the kernel takes 182, and under
             // __launch_bounds__(256, 3) it spills 14 of them to scratch: not built.  profiles/stem_l1_operands_ab.txt)
-            case 3: hipLaunchKernelGGL((stem_l1_h2_kernel<3, true, true>), grid, dim3(256), 0, s, st, a); return hipGetLastError();
+            case 3: hipLaunchKernelGGL((stem_l1_h2_kernel<3, true, true>), grid, dim3(256), 0, s, st, a, b); return hipGetLastError();
             default: return hipErrorNotSupported;
         }
     }
     switch (st.cout / 16) {
-        case 1: if (a.w_single) hipLaunchKernelGGL((stem_l1_h2_kernel<1, true>), grid, dim3(256), 0, s, st, a);
-                else hipLaunchKernelGGL((stem_l1_h2_kernel<1>), grid, dim3(256), 0, s, st, a);
+        case 1: if (a.w_single) hipLaunchKernelGGL((stem_l1_h2_kernel<1, true>), grid, dim3(256), 0, s, st, a, b);
+                else hipLaunchKernelGGL((stem_l1_h2_kernel<1>), grid, dim3(256), 0, s, st, a, b);
                 break;
-        case 2: if (a.w_single) hipLaunchKernelGGL((stem_l1_h2_kernel<2, true>), grid, dim3(256), 0, s, st, a);
-                else hipLaunchKernelGGL((stem_l1_h2_kernel<2>), grid, dim3(256), 0, s, st, a);
+        case 2: if (a.w_single) hipLaunchKernelGGL((stem_l1_h2_kernel<2, true>), grid, dim3(256), 0, s, st, a, b);
+                else hipLaunchKernelGGL((stem_l1_h2_kernel<2>), grid, dim3(256), 0, s, st, a, b);
                 break;
-        case 3: if (a.w_single) hipLaunchKernelGGL((stem_l1_h2_kernel<3, true>), grid, dim3(256), 0, s, st, a);
-                else hipLaunchKernelGGL((stem_l1_h2_kernel<3>), grid, dim3(256), 0, s, st, a);
+        case 3: if (a.w_single) hipLaunchKernelGGL((stem_l1_h2_kernel<3, true>), grid, dim3(256), 0, s, st, a, b);
+                else hipLaunchKernelGGL((stem_l1_h2_kernel<3>), grid, dim3(256), 0, s, st, a, b);
                 break;
         default: return hipErrorNotSupported;
     }

@@ -122,7 +122,7 @@ ABI_SYMBOLS = [
     "pa_jpeg_encode", "pa_jpeg_check", "pa_jpeg_interval_bytes",
     "pa_jpeg_parse", "pa_jpeg_decode", "pa_jpeg_decode_last_path", "pa_jpeg_decode_last_times",
     "pa_yolo_last_post_path", "pa_jpeg_decode_set_split", "pa_jpeg_decode_last_split",
-    "pa_model_lanes_allocated", "pa_model_last_lane", "pa_yolo_resample_passes", "pa_device_bytes_live",
+    "pa_model_lanes_allocated", "pa_model_last_lane", "pa_model_last_stem_path", "pa_yolo_resample_passes", "pa_device_bytes_live",
     "pa_frame_activity", "pa_frame_activity_check", "pa_frames_median",
     "pa_box_histograms", "pa_box_histograms_check",
 ]
@@ -170,6 +170,7 @@ def load_library():
     lib.pa_yolo_last_post_path.argtypes = [vp]
     lib.pa_model_lanes_allocated.argtypes = [vp]
     lib.pa_model_last_lane.argtypes = [vp]
+    lib.pa_model_last_stem_path.argtypes = [vp]
     lib.pa_yolo_resample_passes.argtypes = [vp]
     lib.pa_tracknet_infer.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
     lib.pa_resnet_infer.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
@@ -722,7 +723,7 @@ class Engine:
         return float(ms.value)
 
     def set_tuning(self, **kv):
-        """Tests / tools only: impl (2 bx3, 0 tap; 1 — the retired LDS kernel — is refused), variant (tile id, -1 auto), tune, tap_pd, graph, alias, fold_up, timeline, fuse_stem, fuse_sppf, fuse_head,
+        """Tests / tools only: impl (2 bx3, 0 tap; 1 — the retired LDS kernel — is refused), variant (tile id, -1 auto), tune, tap_pd, graph, alias, fold_up, timeline, fuse_stem, fuse_stem_cv1, fuse_sppf, fuse_head,
         lanes (2: alternate in-flight YOLO tickets run on two streams with their own activation memory, 1: one lane; same results)."""
         for k, v in kv.items():
             self._check(self.lib.pa_engine_set_tuning(self.handle, k.encode(), int(v)))
@@ -1043,6 +1044,11 @@ class Model:
         """POST_PATH_DECODE / POST_PATH_FUSED: what the last ``yolo_infer`` / ``yolo_submit`` / ``postprocess`` of this model ran
         after the network — ``decode_kernel`` over head maps, or the fused head tail (tuning ``fuse_head``)."""
         return int(self.engine.lib.pa_yolo_last_post_path(self.handle))
+
+    def last_stem_path(self) -> int:
+        """1: the last replay of this model's op list ran the 1x1 conv behind layer 1 (model.2.cv1) inside the fused stem kernel
+        (tuning ``fuse_stem_cv1``), 0: it did not (that conv was a launch of its own, or the graph has none)."""
+        return int(self.engine.lib.pa_model_last_stem_path(self.handle))
 
     def lanes_allocated(self) -> int:
         """How many lanes (sets of per-batch device memory) the current plan has: 0 before a plan, 1, or 2 once a ``yolo_submit``
