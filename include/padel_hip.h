@@ -469,7 +469,7 @@ int pa_engine_timer_stop(pa_engine* eng, float* ms);
 /* tuning knobs (tests / tools only).  Defaults come from the environment ONCE at pa_engine_create
  * (PADEL_CONV_IMPL=tap|lds, PADEL_CONV_VARIANT, PADEL_CONV_TUNE, PADEL_CONV_TAP_PD, PADEL_GRAPH, PADEL_ALIAS).
  * keys: "impl" (2 bf16x3 kernels = default, 0 fp32-MFMA tap kernels, 1 fp32-MFMA LDS cross-check kernel),
- * "variant" (forced tile id, -1 auto), "tune",
+ * "variant" (forced tile id, -1 auto), "tune" (bit word; bits 0..3 are kept, csrc/launch_plan.h names the ones that select anything),
  * "tap_pd" (2|3), "graph" (hipGraph replay of the op list), "alias" (liveness-shared activation arena),
  * "timeline" (s_memtime-instrumented 3x3 kernel, dump to pa_engine_set_timeline_path),
  * "lanes" (2 = default: a YOLO model may run alternate in-flight tickets on a second lane, 1: one lane; PADEL_LANES),

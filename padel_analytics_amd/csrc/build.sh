@@ -2,11 +2,9 @@
 # Build libpadel_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
 set -e
 cd "$(dirname "$0")"
-# PADEL_EXTRA_FLAGS=-DPADEL_BX3_PROBES adds the (wrong-result) ceiling-probe tiles 420 / 520 of conv_tap_bx3.hip,
-# -DPADEL_H2P_PROBES the ablation tiles 332.. of conv_patch_h2.hip, -DPADEL_STEM_PROBE=1|2|4|5 the ablations of stem_l1_h2.hip
-# (profiles/r5m_stem_ablation.txt), -DPADEL_RENDER_PROBE clocks render.hip's cull and apply phases inside the kernel and reports them
-# per call on stderr (profiles/render_bench.txt); PADEL_OUT / PADEL_BUILD_DIR keep such a build apart
-# from the product library (tools only)
+# PADEL_EXTRA_FLAGS=-DPADEL_RENDER_PROBE clocks render.hip's cull and apply phases inside the kernel and reports them per call on
+# stderr (profiles/render_bench.txt; right results); PADEL_OUT / PADEL_BUILD_DIR keep such a build apart from the product library
+# (tools only).  No flag builds a kernel that computes wrong results any more
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -Wno-unused-value ${PADEL_EXTRA_FLAGS:-}"
 BUILD="${PADEL_BUILD_DIR:-build}"
 OUT="${PADEL_OUT:-../libpadel_hip.so}"

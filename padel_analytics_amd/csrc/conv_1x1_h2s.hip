@@ -31,32 +31,26 @@ namespace {
 // WC = waves along the channels: 2 (128 x 96 tile, 4 waves, 2 workgroups per CU, 5-stage ring) or 4 (128 x 192 tile, 8 waves, ONE
 // workgroup per CU, 9-stage ring): what bounds a long-K 1x1 layer is the request stream of its activation tile — every 96-channel
 // tile of a pixel tile requests the same 16 KB per k-step again (7.4 TB/s of requests on 1152 -> 384) —, and with all MFMAs compiled
-// out (PROBE) the kernel is exactly as fast: 265 vs 264 / 309 vs 331 TFLOP/s (profiles/r6B_1x1_probe.txt).  Twice the channels per
+// out the kernel is exactly as fast: 265 vs 264 / 309 vs 331 TFLOP/s (profiles/r6B_1x1_probe.txt).  Twice the channels per
 // workgroup is half the requests.
-// PROBE (tuning word bit 6, WRONG results; the eight-wave tile only beyond 1): 1 = no MFMAs and no operand reads — what the two
-// request streams alone sustain; 2 (+ bit 8): the activation requests alone; 3 (+ bit 9): the weight loads alone; 4 (+ bits 8, 9):
-// activations alone as whole 128-byte records; 5 (+ bit 10): activations alone in address order; 6 (+ bit 11): activations alone as
-// plain register loads; 7 (+ bit 12): both streams, one wave of each pair answered by a zero-record descriptor
-// D = how many k-steps ahead a wave loads its weights (D + 1 register sets).  A wave's memory requests complete IN ORDER (one vmcnt
+// D = 2: how many k-steps ahead a wave loads its weights (D + 1 register sets).  A wave's memory requests complete IN ORDER (one vmcnt
 // counter): waiting for W(K), issued D steps ago, also waits for every activation request issued before it — the ring's requests
 // have min(ring depth, D + 1) steps to arrive, not the ring depth: D = 2 leaves an eight-step ring a three-step window.  Measured
 // (profiles/r6I_1x1_weight_lookahead.txt): D = 4 (five-step window, 246 VGPRs) is 0..1 % SLOWER on every long-K layer, D = 3 on the
-// 128 x 96 tile likewise — the window is not what bounds these layers; D = 2 stays, the other is tuning bit 3.
-// What does (profiles/r6J_1x1_stream_probes.txt, 1152 -> 384, TFLOP/s-equivalent of the kernel's time): whole kernel 405; both
+// 128 x 96 tile likewise — the window is not what bounds these layers; D = 2 stays.
+// What does (measured with wrong-result probe instantiations of this kernel, removed since: DESIGN.md §5;
+// profiles/r6J_1x1_stream_probes.txt, 1152 -> 384, TFLOP/s-equivalent of the kernel's time): whole kernel 405; both
 // request streams without MFMAs 472; the activation requests alone 596 — and the same 590..630 whether they ask for half lines or
 // whole 128-byte records, walk the tile in address order, or are plain register loads instead of LDS-DMA; the weight loads alone
 // 1 380; half of the weight loads answered by zero-record descriptors: 475.  1 / 596 + 1 / 1380 = 1 / 416: the two streams nearly
 // ADD, MFMAs hide under them, and neither the L2 (50 % hits, 6 TB/s of 34) nor HBM (3 + 1 TB/s read + write: activations are
 // fetched once, TCC counters) is at its roof — the per-CU vector-memory path serialises them.  The activation-only numbers do not depend
-// on how many steps the probe leaves in flight behind its wait either (2 / 4 / 7: 600 / 617 / 592; -DPADEL_HS_AWIN).
+// on how many steps the probe leaves in flight behind its wait either (2 / 4 / 7: 600 / 617 / 592).
 // WR = waves along the pixels: 2 (128-pixel tiles) or 1 (WC = 4 only: 64 x 192 tiles of FOUR waves, two workgroups per CU with
 // nine 8 KB stages each — the bytes of the 128 x 192 tile per product, but two independent barrier domains per CU)
-#ifndef PADEL_HS_AWIN
-#define PADEL_HS_AWIN D        // activation-only probes: steps that may stay in flight behind the wait (the real kernel's queue leaves D)
-#endif
-template <int WC, int PROBE = 0, int D = 2, int WR = 2>
+template <int WC, int WR = 2>
 __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArgs a) {
-    constexpr int MF = 4, NF = 3, NSET = D + 1;
+    constexpr int MF = 4, NF = 3, D = 2, NSET = D + 1;
     constexpr int kSPlaneB = 64 * WR * 64;         // one fp16 plane of a 32-channel chunk: 64 WR pixels x 64 B
     constexpr int kSStageB = 2 * kSPlaneB;         // h | m of one k-step
     constexpr int kSStages = WC == 2 ? 5 : 9;
@@ -97,34 +91,23 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
     unsigned voA[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) voA[k] = (unsigned)(((wave + 4 * k) * 16 + (lane >> 2)) * (unsigned)pix_b) + p_piece;     // (WC = 4: one span per wave)
-    unsigned voL[2];                              // PROBE 4: whole 128-byte records, 8 pixels per request (wrong LDS layout)
+    // 16-byte pieces of pixels that are whole 64-byte channel groups apart: what a dwordx4 request needs.  (A loop of its own: with
+    // it the 128 x 96 instantiation keeps the scalar register numbering it was measured with; no instruction depends on it)
 #pragma unroll
-    for (int k = 0; k < 2; ++k) voL[k] = (unsigned)((wave * 16 + 8 * k + (lane >> 3)) * (unsigned)pix_b) + (unsigned)(lane & 7) * 16u;
-    i32x4 sink[2] = {};                        // PROBE 6: the activation requests as plain register loads (no LDS-DMA)
-    unsigned voQ[2];                              // PROBE 5: the tile's bytes in address order — 16 KB contiguous per k-step (wrong data)
-#pragma unroll
-    for (int k = 0; k < 2; ++k) voQ[k] = (unsigned)(wave * 2048 + k * 1024 + lane * 16);
+    for (int k = 0; k < 2; ++k) __builtin_assume((voA[k] & 15u) == 0u);
     const unsigned lp0 = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds);
     const unsigned lpw = __builtin_amdgcn_readfirstlane(lp0 + (unsigned)wave * 1024u);
     // k-step K_ into the stage at byte offset SB_; k-steps beyond the last go through a descriptor of zero records (the request
     // count per step — and with it every counted wait — is static)
 #define PADEL_HS_REQA(SB_, K_)                                                                                    \
-    if constexpr (PROBE != 3) {                                                                                   \
+    do {                                                                                                          \
         const unsigned so_ = (unsigned)(K_) * 128u;                                                               \
         const unsigned lb_ = lpw + (unsigned)(SB_);                                                               \
         i32x4 rs_ = rsrcA;                                                                                        \
         if ((int)(K_) >= nch) rs_[2] = 0;                                                                         \
-        if constexpr (PROBE == 4) { lds_dma<0>(voL[0], rs_, so_, lb_); lds_dma<kSPlaneB>(voL[1], rs_, so_, lb_); } \
-        else if constexpr (PROBE == 6) {                                                                          \
-            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(sink[0]) : "v"(voA[0]), "s"(rs_), "s"(so_) : "memory"); \
-            asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(sink[1]) : "v"(voA[0]), "s"(rs_), "s"(so_ + 32u) : "memory"); \
-        }                                                                                                         \
-        else if constexpr (PROBE == 5) { lds_dma<0>(voQ[0], rs_, so_ * 128u, lb_); lds_dma<kSPlaneB>(voQ[1], rs_, so_ * 128u, lb_); } \
-        else {                                                                                                    \
         lds_dma<0>(voA[0], rs_, so_, lb_); if constexpr (WC == 2) lds_dma<4096>(voA[1], rs_, so_, lb_);           \
         lds_dma<kSPlaneB>(voA[0], rs_, so_ + 32u, lb_); if constexpr (WC == 2) lds_dma<kSPlaneB + 4096>(voA[1], rs_, so_ + 32u, lb_); \
-        }                                                                                                         \
-    }
+    } while (0)
 
     // ---- weights: a.wr = [fragment][k-step][h | m][lane][16 bytes]; NF requests per wave and k-step
     const unsigned fragb = (unsigned)nch * 2048u;
@@ -138,14 +121,13 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
     i32x4 w[NSET][NF];
     // (k-steps beyond the last read the next fragment's first k-steps, or the slack behind the copy — never multiplied)
 #define PADEL_HS_LOADW(SET_, K_)                                                                                  \
-    if constexpr (PROBE != 2 && PROBE < 4 || PROBE == 7) {                                                        \
+    do {                                                                                                          \
         const unsigned so_ = (unsigned)(K_) * 2048u;                                                              \
-        if (PROBE == 7 && wr == 1) rsrcW[0][2] = rsrcW[1][2] = rsrcW[2][2] = 0;     /* one wave of a pair loads */ \
         _Pragma("unroll") for (int j = 0; j < NF; ++j)                                                            \
             asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(w[SET_][j]) : "v"(voffW), "s"(rsrcW[j]), "s"(so_) : "memory"); \
-    }
+    } while (0)
 #define PADEL_HS_WAITW(SET_, N_)                                                                                  \
-    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(w[SET_][0]), "+v"(w[SET_][1]), "+v"(w[SET_][2]) : "n"(PROBE == 2 || (PROBE >= 4 && PROBE != 7) ? ((N_) == 0 ? 0 : (PADEL_HS_AWIN) * NA) : PROBE == 3 ? (N_) * NF / (NF + NA) : (N_)) : "memory")
+    asm volatile("s_waitcnt vmcnt(%3)" : "+v"(w[SET_][0]), "+v"(w[SET_][1]), "+v"(w[SET_][2]) : "n"(N_) : "memory")
 
     // ---- operand reads: pixel fragment f of the wave = pixels 64 wr + 16 f + lr: swz_off's swizzle depends on lr only, everything
     // else is the stage's offset (scalar, walks the ring) and an immediate
@@ -175,7 +157,7 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
         asm volatile("" ::: "memory");                                                                            \
         PADEL_HS_REQA(s_wr, (K_) + kSAhead);                                                                      \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        if constexpr (PROBE == 0) {                                                                               \
+        {                                                                                                         \
             const char* p_ = ldsb + abase + s_rd;                                                                 \
             _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                      \
                 ah[f] = *reinterpret_cast<const h16x8*>(p_ + f * 1024);                                           \
@@ -183,7 +165,7 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
             }                                                                                                     \
         }                                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        if constexpr (PROBE == 0) { PADEL_HS_MFMA(0, SET_); PADEL_HS_MFMA(1, SET_); PADEL_HS_MFMA(2, SET_); PADEL_HS_MFMA(3, SET_); } \
+        PADEL_HS_MFMA(0, SET_); PADEL_HS_MFMA(1, SET_); PADEL_HS_MFMA(2, SET_); PADEL_HS_MFMA(3, SET_);           \
         if (++kblk == 9) {                        /* main sums in blocks of 9 k-steps (the tap kernels' accumulation blocks) */ \
             kblk = 0;                                                                                             \
             _Pragma("unroll") for (int f = 0; f < MF; ++f)                                                        \
@@ -221,7 +203,6 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
     // before the epilogue may reuse the weight registers
 #pragma unroll
     for (int i = 0; i < NSET; ++i) PADEL_HS_WAITW(i, 0);
-    if constexpr (PROBE == 6) asm volatile("" :: "v"(sink[0]), "v"(sink[1]));
 #undef PADEL_HS_STEP
 #undef PADEL_HS_MFMA
 #undef PADEL_HS_WAITW
@@ -248,8 +229,8 @@ __global__ void __launch_bounds__(64 * WR * WC, 2) conv_h2s_kernel(const ConvArg
 // the taps column-major like every h2 kernel and the main sums flushed per chunk (= the tap kernels' blocks of 9 k-steps): bitwise
 // conv_h2_kernel.  A lane's request offset is its pixel's top-left input pixel relative to the tile's; the tap enters through the
 // scalar offset, taps outside the image through a per-lane validity mask (3 row bits + 3 column bits).
-// WR = 1: 64 x 192 tiles of four waves, two workgroups per CU (nine 8 KB stages each), as conv_h2s_kernel<4, .., 1>
-template <int PROBE = 0, int WR = 2>
+// WR = 1: 64 x 192 tiles of four waves, two workgroups per CU (nine 8 KB stages each), as conv_h2s_kernel<4, 1>
+template <int WR = 2>
 __global__ void __launch_bounds__(256 * WR, 2) conv_h2s3_kernel(const ConvArgs a) {
     constexpr int MF = 4, NF = 3, WC = 4;
     constexpr int kSPlaneB = 64 * WR * 64, kSStageB = 2 * kSPlaneB;
@@ -365,7 +346,7 @@ __global__ void __launch_bounds__(256 * WR, 2) conv_h2s3_kernel(const ConvArgs a
         asm volatile("" ::: "memory");                                                                            \
         PADEL_HS3_REQA(s_wr, c + ((T_) >= 1 ? 1 : 0), ((T_) + 8) % 9);                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        if constexpr (PROBE == 0) {                                                                               \
+        {                                                                                                         \
             const char* p_ = ldsb + abase + s_rd;                                                                 \
             _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                      \
                 ah[f] = *reinterpret_cast<const h16x8*>(p_ + f * 1024);                                           \
@@ -373,7 +354,7 @@ __global__ void __launch_bounds__(256 * WR, 2) conv_h2s3_kernel(const ConvArgs a
             }                                                                                                     \
         }                                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        if constexpr (PROBE == 0) { PADEL_HS3_MFMA(0, (T_) % 3); PADEL_HS3_MFMA(1, (T_) % 3); PADEL_HS3_MFMA(2, (T_) % 3); PADEL_HS3_MFMA(3, (T_) % 3); } \
+        PADEL_HS3_MFMA(0, (T_) % 3); PADEL_HS3_MFMA(1, (T_) % 3); PADEL_HS3_MFMA(2, (T_) % 3); PADEL_HS3_MFMA(3, (T_) % 3); \
         s_wr = s_rd;                                                                                              \
         s_rd = s_rd + (unsigned)kSStageB == (unsigned)(kSStages * kSStageB) ? 0u : s_rd + (unsigned)kSStageB;     \
     } while (0)
@@ -423,13 +404,8 @@ hipError_t launch_conv_h2s3(const ConvArgs& a_in, int tile, hipStream_t s) {
     a.n_mtiles = m64 ? (a.M + 63) / 64 : (a.M + 127) / 128;
     a.n_ntiles = (a.n16 + 11) / 12;
     dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8) * (unsigned)a.n_ntiles, 1, 1);
-    if (m64) {
-        if (a.tune & 64) hipLaunchKernelGGL((conv_h2s3_kernel<1, 1>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv_h2s3_kernel<0, 1>), grid, dim3(256), 0, s, a);
-        return hipGetLastError();
-    }
-    if (a.tune & 64) hipLaunchKernelGGL((conv_h2s3_kernel<1>), grid, dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((conv_h2s3_kernel<0>), grid, dim3(512), 0, s, a);
+    if (m64) hipLaunchKernelGGL((conv_h2s3_kernel<1>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((conv_h2s3_kernel<2>), grid, dim3(512), 0, s, a);
     return hipGetLastError();
 }
 
@@ -442,8 +418,7 @@ hipError_t launch_conv_h2s(const ConvArgs& a_in, int tile, hipStream_t s) {
         a.n_mtiles = (a.M + 63) / 64;
         a.n_ntiles = (a.n16 + 11) / 12;
         dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8) * (unsigned)a.n_ntiles, 1, 1);
-        if (a.tune & 64) hipLaunchKernelGGL((conv_h2s_kernel<4, 1, 2, 1>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((conv_h2s_kernel<4, 0, 2, 1>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL((conv_h2s_kernel<4, 1>), grid, dim3(256), 0, s, a);
         return hipGetLastError();
     }
     a.n_mtiles = (a.M + 127) / 128;
@@ -453,21 +428,11 @@ hipError_t launch_conv_h2s(const ConvArgs& a_in, int tile, hipStream_t s) {
     if (wide) {
         static bool attr = false;
         if (!attr) {                                // 144 KB of static LDS
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_h2s_kernel<4, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 0);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_h2s_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 0);
             attr = true;
         }
-        if ((a.tune & 64) && (a.tune & 4096)) hipLaunchKernelGGL((conv_h2s_kernel<4, 7>), grid, dim3(512), 0, s, a);               // both streams, one wave of a pair loads weights
-        else if ((a.tune & 64) && (a.tune & 2048)) hipLaunchKernelGGL((conv_h2s_kernel<4, 6>), grid, dim3(512), 0, s, a);               // activations alone, to registers
-        else if ((a.tune & 64) && (a.tune & 1024)) hipLaunchKernelGGL((conv_h2s_kernel<4, 5>), grid, dim3(512), 0, s, a);               // activations alone, in address order
-        else if ((a.tune & 64) && (a.tune & 256) && (a.tune & 512)) hipLaunchKernelGGL((conv_h2s_kernel<4, 4>), grid, dim3(512), 0, s, a);  // activations alone, whole records
-        else if ((a.tune & 64) && (a.tune & 256)) hipLaunchKernelGGL((conv_h2s_kernel<4, 2>), grid, dim3(512), 0, s, a);      // activations only
-        else if ((a.tune & 64) && (a.tune & 512)) hipLaunchKernelGGL((conv_h2s_kernel<4, 3>), grid, dim3(512), 0, s, a); // weights only
-        else if (a.tune & 64) hipLaunchKernelGGL((conv_h2s_kernel<4, 1>), grid, dim3(512), 0, s, a);
-        else if (a.tune & 8) hipLaunchKernelGGL((conv_h2s_kernel<4, 0, 4>), grid, dim3(512), 0, s, a);        // weights four steps ahead: a five-step window (A/B: no faster)
-        else hipLaunchKernelGGL((conv_h2s_kernel<4, 0, 2>), grid, dim3(512), 0, s, a);
-    } else if (a.tune & 64) hipLaunchKernelGGL((conv_h2s_kernel<2, 1>), grid, dim3(256), 0, s, a);
-    else if (a.tune & 8) hipLaunchKernelGGL((conv_h2s_kernel<2, 0, 3>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((conv_h2s_kernel<2, 0, 2>), grid, dim3(256), 0, s, a);
+        hipLaunchKernelGGL((conv_h2s_kernel<4>), grid, dim3(512), 0, s, a);
+    } else hipLaunchKernelGGL((conv_h2s_kernel<2>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

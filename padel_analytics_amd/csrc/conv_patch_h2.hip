@@ -38,10 +38,8 @@ constexpr int kHTailPasses = (kPatchPix * 4 + 255) / 256;     // 3
 // issues the operand reads of T + 1 into a SECOND register set, then runs the main products of step T under their
 // latency.  Costs 40 more VGPRs (2 waves per SIMD instead of 3).  Same products in the same order per accumulator:
 // bitwise equal to the plain schedule.
-// PROBE (builds with -DPADEL_H2P_PROBES only; WRONG results, ceilings for tools/conv_bench.py): bit 0 no barrier on tap
-// steps 1..8, bit 1 no weight reads there, bit 2 no weight requests there, bit 3 no patch reads there, bit 4 no MFMAs
 // WS: the packed weights' m plane is all zero (ConvArgs::w_single): no wm x ah product, no m-plane requests / reads (conv_patch_h2q.hip)
-template <int NF, bool TAIL, bool UP, bool PIPE, int PROBE = 0, bool WS = false>
+template <int NF, bool TAIL, bool UP, bool PIPE, bool WS = false>
 __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h2p_kernel(const ConvArgs a) {
     constexpr int MF = 2;
     constexpr bool TWOL = NF <= 4;               // two-level main accumulation (part -> acc once per chunk) where registers allow
@@ -281,21 +279,19 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
 #define PADEL_HP_STEP(T_)                                                                                         \
     do {                                                                                                          \
         constexpr bool first_ = (T_) == 0;                                                                        \
-        if constexpr (!first_ && !(PROBE & 8)) PADEL_HP_READA(T_);   /* the planes are static inside a chunk: read under the wait */ \
-        if constexpr (first_ || !(PROBE & 4)) wait_vm<0>();                                                       \
+        if constexpr (!first_) PADEL_HP_READA(T_);   /* the planes are static inside a chunk: read under the wait */ \
+        wait_vm<0>();                                                                                             \
         if constexpr (first_) lds_fence();           /* this wave's plane writes have reached the LDS */          \
-        if constexpr (first_ || !(PROBE & 1)) __builtin_amdgcn_s_barrier();                                       \
+        __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
-        if constexpr (first_ || !(PROBE & 2)) PADEL_HP_READB(T_);                                                 \
+        PADEL_HP_READB(T_);                                                                                       \
         if constexpr (first_) PADEL_HP_READA(T_);                                                                 \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        if constexpr (first_ || (T_) == 8 || !(PROBE & 4)) {                                                      \
-            if ((T_) < 8 || c + 1 < nch || TAIL) PADEL_HP_DMAB((T_) + 1, s_kb + ((T_) + 1) * 128u);               \
-        }                                                                                                         \
+        if ((T_) < 8 || c + 1 < nch || TAIL) PADEL_HP_DMAB((T_) + 1, s_kb + ((T_) + 1) * 128u);                   \
         if ((T_) == 0 && c + 1 < nch) PADEL_HP_LOAD(c + 1);                                                       \
         if constexpr (TAIL) { if ((T_) == 0 && c + 1 == nch) PADEL_HP_TLOAD(); }                                  \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        if constexpr (!(PROBE & 16)) PADEL_HP_MFMA();                                                             \
+        PADEL_HP_MFMA();                                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
     } while (0)
 
@@ -458,20 +454,15 @@ __global__ void __launch_bounds__(256, (NF <= 3 && !UP && !PIPE) ? 3 : 2) conv_h
     h2_epilogue<MF, NF>(a, acc, cross, mpix, f0, lq, fast);
 }
 
-template <int NF, bool TAIL, bool UP, bool PIPE, int PROBE = 0>
+template <int NF, bool TAIL, bool UP, bool PIPE>
 static hipError_t launch_hpt(const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a = a_in;
     const int batch = a.M / (a.Ho * a.Wo);
     a.n_mtiles = batch * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
     a.n_ntiles = (a.n16 + NF - 1) / NF;
     dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8) * (unsigned)a.n_ntiles, 1, 1);
-    if constexpr (PROBE == 0) {
-        if (a.w_single) {
-            hipLaunchKernelGGL((conv_h2p_kernel<NF, TAIL, UP, PIPE, 0, true>), grid, dim3(256), 0, s, a);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((conv_h2p_kernel<NF, TAIL, UP, PIPE, PROBE>), grid, dim3(256), 0, s, a);
+    if (a.w_single) hipLaunchKernelGGL((conv_h2p_kernel<NF, TAIL, UP, PIPE, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((conv_h2p_kernel<NF, TAIL, UP, PIPE>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -491,13 +482,6 @@ hipError_t launch_conv_h2p(const ConvArgs& a, int tile, hipStream_t s) {
         // (round 5 prune: the 6-fragment tile 306 — main product accumulated in ONE level for want of registers, no faster than
         //  303 and 1.3-2 x its RMS error on long K, profiles/conv_h2_sweep_r3a.txt — and the software-pipelined 64-channel tile
         //  314 — 10-15 % slower than 304, profiles/conv_h2_sweep_r3f_pipe.txt — were never chosen automatically: removed)
-#ifdef PADEL_H2P_PROBES
-#define PADEL_HP_PROBE_CASE(P_) case 32 + (P_): return launch_hpt<3, false, false, false, (P_)>(a, s);
-        PADEL_HP_PROBE_CASE(1) PADEL_HP_PROBE_CASE(2) PADEL_HP_PROBE_CASE(3) PADEL_HP_PROBE_CASE(4) PADEL_HP_PROBE_CASE(5)
-        PADEL_HP_PROBE_CASE(7) PADEL_HP_PROBE_CASE(8) PADEL_HP_PROBE_CASE(10) PADEL_HP_PROBE_CASE(15) PADEL_HP_PROBE_CASE(16)
-        PADEL_HP_PROBE_CASE(17) PADEL_HP_PROBE_CASE(31)
-#undef PADEL_HP_PROBE_CASE
-#endif
     }
     return hipErrorNotSupported;
 }

@@ -52,12 +52,6 @@ namespace {
 
 constexpr int kQPatchB = 2 * kPatchPadPlaneB;
 
-// DBG (tuning only, builds with -DPADEL_H2P_PROBES, pa_engine_set_tuning "timeline"): every wave stamps s_memtime at 5
-// points of every tap step (step top / own requests landed / barrier passed / operands in registers / last MFMA issued)
-// into an LDS ring of 32 steps, dumped to a.dbg at the end (tools/timeline_probe.py --kernel h2q)
-constexpr int kQDbgSteps = kPatchDbgSteps;      // kernels.h: the engine sizes the timeline buffer with the same constants
-constexpr int kQDbgWords = kPatchDbgWords;
-
 }  // namespace
 
 // WS (round 5): the packed weights' m plane is all zero (ConvArgs::w_single — fp16 checkpoint weights, BatchNorm's scale in the
@@ -66,31 +60,16 @@ constexpr int kQDbgWords = kPatchDbgWords;
 // weights (the skipped product is exactly zero).  192 -> 192: 408 -> 532 TFLOP/s fp32-equivalent, 96 -> 96: 350 -> 424.
 // (Tried on top, gpurun r5r: the freed m-plane stages as a THIRD h-only weight stage, weights requested two steps ahead with a
 //  counted vmcnt(2) — bitwise, but 320 / 271 TFLOP/s: slower than the two-stage ring by 40 %; reverted.)
-template <int NF, bool DBG = false, bool WS = false>
+template <int NF, bool WS = false>
 __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
     constexpr int MF = 4;
     constexpr int BN = 2 * NF * 16;              // output channels per workgroup
     constexpr int BPLANE_B = BN * 64;
     constexpr int BSTAGE_B = 2 * BPLANE_B;
     static_assert(NF == 3, "weight requests are laid out for 6 spans of 16 rows per plane: 2 per wave 0..2");
-    constexpr int DBG_B = DBG ? (4 * kQDbgSteps * 5 + 4 * 64) * 8 : 0;
-    static_assert(2 * kQPatchB + 2 * BSTAGE_B + DBG_B <= 80 * 1024, "2 workgroups per CU, instrumented too");
-    __shared__ __attribute__((aligned(16))) float lds[(2 * kQPatchB + 2 * BSTAGE_B + DBG_B) / 4];
+    static_assert(2 * kQPatchB + 2 * BSTAGE_B <= 80 * 1024, "2 workgroups per CU");
+    __shared__ __attribute__((aligned(16))) float lds[(2 * kQPatchB + 2 * BSTAGE_B) / 4];
     char* const ldsb = reinterpret_cast<char*>(lds);
-    unsigned long long* const stamps = reinterpret_cast<unsigned long long*>(ldsb + 2 * kQPatchB + 2 * BSTAGE_B);
-    unsigned long long t_begin = 0;
-    int dbg_k = 0;
-    if constexpr (DBG) t_begin = __builtin_amdgcn_s_memtime();
-    (void)stamps; (void)t_begin; (void)dbg_k;
-#define PADEL_HQ_STAMP(J, slot)                                                                                   \
-    do {                                                                                                          \
-        if constexpr (DBG) {                                                                                      \
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                           \
-            const int real_ = (wave * kQDbgSteps + ((dbg_k + (J)) & (kQDbgSteps - 1))) * 5 + (slot);              \
-            const int dummy_ = 4 * kQDbgSteps * 5 + wave * 64 + lane;                                             \
-            stamps[lane == 0 ? real_ : dummy_] = t_;                                                              \
-        }                                                                                                         \
-    } while (0)
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -212,20 +191,16 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
         constexpr int kx_ = h2_tap_kx(T_), ky_ = h2_tap_ky(T_);                                                   \
         int rp_ = rd_pix;                                  /* row addresses recomputed per tap (3 VALU each): 18 hoisted ones would spill */ \
         asm volatile("" : "+v"(rp_));                                                                             \
-        PADEL_HQ_STAMP(T_, 0);                                                                                    \
         if constexpr ((T_) > 0) {                          /* the planes are static inside a chunk: read under the wait */ \
             if constexpr (ky_ == 0) { PADEL_HQ_READROW(0, kx_); PADEL_HQ_READROW(1, kx_); PADEL_HQ_READROW(2, kx_); PADEL_HQ_READROW(3, kx_); } \
             else PADEL_HQ_READROW(3 + ky_, kx_);                                                                  \
         }                                                                                                         \
         if ((T_) == 0 || wave != 3) wait_vm<0>();                                                                 \
-        PADEL_HQ_STAMP(T_, 1);                                                                                    \
         __builtin_amdgcn_s_barrier();                                                                             \
         asm volatile("" ::: "memory");                                                                            \
-        PADEL_HQ_STAMP(T_, 2);                                                                                    \
         PADEL_HQ_READB(T_);                                                                                       \
         if constexpr ((T_) == 0) { PADEL_HQ_READROW(0, 0); PADEL_HQ_READROW(1, 0); PADEL_HQ_READROW(2, 0); PADEL_HQ_READROW(3, 0); } \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        if constexpr (DBG) { lds_fence(); PADEL_HQ_STAMP(T_, 3); }                                                \
         __builtin_amdgcn_s_setprio(1);                                                                            \
         PADEL_HQ_MFMA_ROW(0, ky_);                                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
@@ -238,7 +213,6 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
         PADEL_HQ_MFMA_ROW(1, ky_); PADEL_HQ_MFMA_ROW(2, ky_); PADEL_HQ_MFMA_ROW(3, ky_);                          \
         __builtin_amdgcn_s_setprio(0);                                                                            \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
-        PADEL_HQ_STAMP(T_, 4);                                                                                    \
     } while (0)
 
     unsigned s_kb = 0;
@@ -258,7 +232,6 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
             for (int j = 0; j < NF; ++j) { acc[f][j] += part[f][j]; part[f][j] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
         { const float* t_ = b_rd0; b_rd0 = b_rd1; b_rd1 = t_; const unsigned u_ = lw0; lw0 = lw1; lw1 = u_; }
         s_kb += 9u * 128u;
-        dbg_k += 9;
     }
     wait_vm<0>();
 #undef PADEL_HQ_STEP
@@ -279,21 +252,6 @@ __global__ void __launch_bounds__(256, 2) conv_h2q_kernel(const ConvArgs a) {
     const bool fast = y0 + 8 <= a.Ho && x0 + 16 <= a.Wo && (fw + NF) * 16 <= a.cout && (((a.out_choff | a.out_cs) & 3) == 0) &&
                       (!a.res || (((a.res_choff | a.res_cs) & 3) == 0));
     if (fw < a.n16) h2_epilogue<MF, NF>(a, acc, cross, mpix, fw, lq, fast);
-    if constexpr (DBG) {
-        if (a.dbg) {
-            const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-            __syncthreads();
-            unsigned long long* d = a.dbg + (long long)blockIdx.x * kQDbgWords;
-            for (int i = tid; i < 4 * kQDbgSteps * 5; i += 256) d[8 + i] = stamps[i];
-            if (lane == 0) {
-                const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);       // HW_REG_HW_ID
-                const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);     // HW_REG_XCC_ID
-                d[wave] = ((unsigned long long)xcc << 32) | hw;
-                if (wave == 0) { d[4] = t_begin; d[5] = t_end; d[6] = (unsigned long long)(nch * 9); d[7] = (unsigned long long)bid; }
-            }
-        }
-    }
-#undef PADEL_HQ_STAMP
 }
 
 hipError_t launch_conv_h2q(const ConvArgs& a_in, int tile, hipStream_t s) {
@@ -303,13 +261,7 @@ hipError_t launch_conv_h2q(const ConvArgs& a_in, int tile, hipStream_t s) {
     a.n_mtiles = batch * ((a.Ho + 7) / 8) * ((a.Wo + 15) / 16);
     a.n_ntiles = (a.n16 + 5) / 6;
     dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8) * (unsigned)a.n_ntiles, 1, 1);
-#ifdef PADEL_H2P_PROBES
-    if (a.dbg) {
-        hipLaunchKernelGGL((conv_h2q_kernel<3, true>), grid, dim3(256), 0, s, a);
-        return hipGetLastError();
-    }
-#endif
-    if (a.w_single) hipLaunchKernelGGL((conv_h2q_kernel<3, false, true>), grid, dim3(256), 0, s, a);
+    if (a.w_single) hipLaunchKernelGGL((conv_h2q_kernel<3, true>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((conv_h2q_kernel<3>), grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }

@@ -29,6 +29,7 @@
 //
 // LDS: 2 patch buffers x 2 planes x 192 pixels x 64 B, 32 KB apart = 57 344 B + 6 KB of request offsets; registers bound the occupancy (2 workgroups per CU).
 #include "h2_common.h"
+#include "launch_plan.h"
 
 namespace padel {
 
@@ -36,14 +37,6 @@ namespace {
 
 constexpr int kRPatchB = 2 * kPatchPadPlaneB;
 constexpr int kRBufStride = 32768;              // the two patch buffers sit 32 KB apart: switching buffers is one XOR per read address
-
-// DBG (tuning only, builds with -DPADEL_H2P_PROBES, pa_engine_set_tuning "timeline"): the record format of conv_patch_h2q.hip — every
-// wave stamps s_memtime at 5 points of every tap step into an LDS ring of 32 steps (tools/timeline_probe.py --kernel h2r):
-// 0 step top / 1 this tap's weights landed (counted wait passed) / 2 chunk barrier passed (tap 8; elsewhere = 1) / 3 the first
-// row's six products issued (its operands were in registers) / 4 last product issued
-constexpr int kRDbgSteps = kPatchDbgSteps;      // kernels.h: the engine sizes the timeline buffer with the same constants
-constexpr int kRDbgWords = kPatchDbgWords;
-constexpr int kRDbgTile = 3;                     // the tile of a persistent workgroup whose steps the ring keeps
 
 }  // namespace
 
@@ -76,10 +69,7 @@ __device__ __forceinline__ HrTile hr_tile(const ConvArgs& a, int v, int vmax, in
 // workgroup in the CU's odd thread-group slot — the tile log of the probe build shows the two workgroups of a CU are not in phase
 // anyway (the older one gets the pipe first: 64.5 k vs 83 k ticks per tile, epilogues 0.9 beside the partner's main loop), no
 // change; `nt` on the patch requests (-6 .. -8 %), `sc0` on the weight loads (0).
-#ifndef PADEL_HR_LATEW
-#define PADEL_HR_LATEW 1
-#endif
-template <int NF, bool WS, bool DBG = false, int ABL = 0, int PRIO = 0>
+template <int NF, bool WS>
 __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, const int vmax) {
     constexpr int MF = 4;
     // NF channel fragments per wave (a workgroup: 2 NF x 16 channels); WS: two products (the m plane of the weights is all zero and
@@ -92,36 +82,15 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
     // the requests of tap T + 2 go out behind tap T's first row of products (their issue time — ~110 cycles for six loads — under the
     // matrix pipe) instead of in front of its counted wait: +1.0..1.4 % on 96 -> 96, +0.2 % on 192 -> 192 with 96-channel tiles, -0.4..1.4 %
     // with 64-channel tiles (four rows of FOUR products hide less): profiles/r7a_h2r_late_weight_requests.txt
-    constexpr bool kLateW = PADEL_HR_LATEW != 0 && NF == 3;
+    constexpr bool kLateW = NF == 3;
     constexpr int kWQ = kLateW ? 1 : 2;           // taps of weight requests that are younger than W(T) when tap T waits for it
-    constexpr int DBG_B = DBG ? (4 * kRDbgSteps * 5 + 4 * 64) * 8 : 0;
     constexpr int PATCH_B = (NBUF - 1) * kRBufStride + kRPatchB;
     constexpr int PVO_B = 2 * 3 * 256 * 4;       // the lane offsets of the patch requests, two tiles' worth
-    __shared__ __attribute__((aligned(16))) float lds[(PATCH_B + PVO_B + DBG_B) / 4];
+    __shared__ __attribute__((aligned(16))) float lds[(PATCH_B + PVO_B) / 4];
     char* const ldsb = reinterpret_cast<char*>(lds);
-    unsigned long long* const stamps = reinterpret_cast<unsigned long long*>(ldsb + PATCH_B + PVO_B);
-    unsigned long long t_begin = 0, t_end_rec = 0;
-    int dbg_k = 0, dbg_tile = 0;
-    (void)stamps; (void)t_begin; (void)t_end_rec; (void)dbg_k; (void)dbg_tile;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // ablation probes (-DPADEL_H2P_PROBES instantiates ABL != 0, wrong results by construction; pa_engine_set_tuning "tune" selects
-    // one): bits switch pieces of the main loop off — 16 the patch requests, 32 the flushes, 64 the chunk barrier, 128 tap 8's row
-    // reads, 256 the weight requests, 512 the other row reads
-#define PADEL_HR_ON(BIT_) (!(ABL & (BIT_)))
-    // (PRIO = 1, tuning only: a priority ladder over the rows of a tap, so that the wave further into its burst keeps the pipe —
-    //  measured -2 % .. +0 %, profiles/r6g_prio_ladder.txt; off)
-#define PADEL_HR_PRIO(N_) do { if constexpr (PRIO == 1) __builtin_amdgcn_s_setprio(N_); } while (0)
-#define PADEL_HR_STAMP(J, slot)                                                                                   \
-    do {                                                                                                          \
-        if constexpr (DBG) {                               /* the ring records ONE tile in the middle of the launch (the fourth) */ \
-            const unsigned long long t_ = __builtin_amdgcn_s_memtime();                                           \
-            const int real_ = (wave * kRDbgSteps + ((dbg_k + (J)) & (kRDbgSteps - 1))) * 5 + (slot);              \
-            const int dummy_ = 4 * kRDbgSteps * 5 + wave * 64 + lane;                                             \
-            stamps[(lane == 0 && dbg_tile == kRDbgTile) ? real_ : dummy_] = t_;                                   \
-        }                                                                                                         \
-    } while (0)
     const int wr = wave & 1, wc = wave >> 1;      // pixel half (rows 4 wr ..), channel half (fragments 3 wc ..)
     const int lr = lane & 15, lq = lane >> 4;
     const int nch = a.cin >> 5;                   // >= 2 (launch_conv_h2r)
@@ -262,82 +231,66 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
 #define PADEL_HR_STEP(T_)                                                                                         \
     do {                                                                                                          \
         constexpr int kx_ = h2_tap_kx(T_), ky_ = h2_tap_ky(T_), set_ = (T_) % 3;                                  \
-        PADEL_HR_STAMP(T_, 0);                                                                                    \
-        PADEL_HR_PRIO(0);                                                                                         \
-        if constexpr (!kLateW && PADEL_HR_ON(256)) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);                      \
+        if constexpr (!kLateW) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);                                          \
         PADEL_HR_WAITW(set_, (T_) < 2 ? 6 : 0);                                                                   \
-        PADEL_HR_STAMP(T_, 1);                                                                                    \
-        if constexpr ((T_) != 8) PADEL_HR_STAMP(T_, 2);                                                           \
-        PADEL_HR_PRIO(1);                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                        \
         if constexpr (ky_ == 0) {                                                                                 \
-            PADEL_HR_MFMA_ROW(0, 0, set_, (T_) == 0 && !(ABL & 32));                                              \
-            if constexpr (kLateW && PADEL_HR_ON(256)) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);   /* its issue under this row's products */ \
-            PADEL_HR_STAMP(T_, 3);                                                                                \
-            if constexpr ((T_) == 0 && !(ABL & 32)) PADEL_HR_FLUSH(1);   /* the previous chunk's last row (chunk 0: + 0) */ \
-            if constexpr (PADEL_HR_ON(512)) PADEL_HR_READROW(4, kx_);   /* slot 0, first used by row 3 of ky = 1 */ \
-            PADEL_HR_PRIO(2);                                                                                     \
+            PADEL_HR_MFMA_ROW(0, 0, set_, (T_) == 0);                                                             \
+            if constexpr (kLateW) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);   /* its issue under this row's products */ \
+            if constexpr ((T_) == 0) PADEL_HR_FLUSH(1);   /* the previous chunk's last row (chunk 0: + 0) */      \
+            PADEL_HR_READROW(4, kx_);   /* slot 0, first used by row 3 of ky = 1 */                               \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
-            PADEL_HR_MFMA_ROW(1, 0, set_, (T_) == 0 && !(ABL & 32)); PADEL_HR_PRIO(3);                            \
-            PADEL_HR_MFMA_ROW(2, 0, set_, (T_) == 0 && !(ABL & 32)); PADEL_HR_MFMA_ROW(3, 0, set_, (T_) == 0 && !(ABL & 32)); \
+            PADEL_HR_MFMA_ROW(1, 0, set_, (T_) == 0);                                                             \
+            PADEL_HR_MFMA_ROW(2, 0, set_, (T_) == 0); PADEL_HR_MFMA_ROW(3, 0, set_, (T_) == 0);                   \
         } else if constexpr (ky_ == 1) {                                                                          \
             PADEL_HR_MFMA_ROW(0, 1, set_, false);                                                                 \
-            if constexpr (kLateW && PADEL_HR_ON(256)) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);   /* its issue under this row's products */ \
-            PADEL_HR_STAMP(T_, 3);                                                                                \
-            if constexpr (PADEL_HR_ON(512)) PADEL_HR_READROW(5, kx_);   /* slot 1, first used by row 3 of ky = 2 */ \
-            PADEL_HR_PRIO(2);                                                                                     \
+            if constexpr (kLateW) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);   /* its issue under this row's products */ \
+            PADEL_HR_READROW(5, kx_);   /* slot 1, first used by row 3 of ky = 2 */                               \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
-            PADEL_HR_MFMA_ROW(1, 1, set_, false); PADEL_HR_PRIO(3); PADEL_HR_MFMA_ROW(2, 1, set_, false); PADEL_HR_MFMA_ROW(3, 1, set_, false); \
+            PADEL_HR_MFMA_ROW(1, 1, set_, false); PADEL_HR_MFMA_ROW(2, 1, set_, false); PADEL_HR_MFMA_ROW(3, 1, set_, false); \
         } else if constexpr (kx_ < 2) {                    /* ky = 2: rows 2, 3, 0, 1 free slots 0, 1, 2, 3 for the next column */ \
             PADEL_HR_MFMA_ROW(2, 2, set_, false);                                                                 \
-            if constexpr (kLateW && PADEL_HR_ON(256)) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);   /* its issue under this row's products */ \
-            PADEL_HR_STAMP(T_, 3);                                                                                \
-            if constexpr (PADEL_HR_ON(512)) PADEL_HR_READROW(0, kx_ + 1);                                         \
-            PADEL_HR_PRIO(2);                                                                                     \
+            if constexpr (kLateW) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);   /* its issue under this row's products */ \
+            PADEL_HR_READROW(0, kx_ + 1);                                                                         \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
             PADEL_HR_MFMA_ROW(3, 2, set_, false);                                                                 \
-            if constexpr (PADEL_HR_ON(512)) PADEL_HR_READROW(1, kx_ + 1);                                         \
-            PADEL_HR_PRIO(3);                                                                                     \
+            PADEL_HR_READROW(1, kx_ + 1);                                                                         \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
             PADEL_HR_MFMA_ROW(0, 2, set_, false);                                                                 \
-            if constexpr (PADEL_HR_ON(512)) PADEL_HR_READROW(2, kx_ + 1);                                         \
+            PADEL_HR_READROW(2, kx_ + 1);                                                                         \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
             PADEL_HR_MFMA_ROW(1, 2, set_, false);                                                                 \
-            if constexpr (PADEL_HR_ON(512)) PADEL_HR_READROW(3, kx_ + 1);                                         \
+            PADEL_HR_READROW(3, kx_ + 1);                                                                         \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
         } else {                                           /* tap 8: the chunk barrier sits behind the first row's products */ \
             PADEL_HR_MFMA_ROW(2, 2, set_, false);                                                                 \
-            if constexpr (kLateW && PADEL_HR_ON(256)) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);                   \
+            if constexpr (kLateW) PADEL_HR_LOADW(((T_) + 2) % 3, (T_) + 2);                                       \
             /* every read of this chunk's patch has returned (row 5 was read under tap 7; lgkmcnt(0) costs nothing here), */ \
             /* and the wave's own requests of the next chunk's patch landed long ago (in order in front of W(8)) */ \
             lds_fence();                                                                                          \
-            if constexpr (PADEL_HR_ON(64)) __builtin_amdgcn_s_barrier();                                          \
+            __builtin_amdgcn_s_barrier();                                                                         \
             asm volatile("" ::: "memory");                                                                        \
-            PADEL_HR_STAMP(T_, 2); PADEL_HR_STAMP(T_, 3);                                                         \
             unsigned vo8[3];                               /* the three lane offsets: read here, used a row of MFMAs later */ \
             _Pragma("unroll") for (int k = 0; k < 3; ++k) vo8[k] = pvo[(set8 * 3 + k) * 256];                     \
             _Pragma("unroll") for (int r = 0; r < 8; ++r) rbase[r] ^= (unsigned)kRBufStride;                      \
-            if constexpr (PADEL_HR_ON(128)) PADEL_HR_READROW(0, 0);                                               \
-            PADEL_HR_PRIO(2);                                                                                     \
+            PADEL_HR_READROW(0, 0);                                                                               \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
             PADEL_HR_MFMA_ROW(3, 2, set_, false);                                                                 \
-            PADEL_HR_PRIO(3);                                                                                     \
-            if constexpr (PADEL_HR_ON(32)) PADEL_HR_FLUSH(2);                                                     \
-            if constexpr (PADEL_HR_ON(128)) PADEL_HR_READROW(1, 0);                                               \
-            if constexpr (PADEL_HR_ON(16)) PADEL_HR_PSPAN8(0);   /* into the buffer this chunk read */ \
+            PADEL_HR_FLUSH(2);                                                                                    \
+            PADEL_HR_READROW(1, 0);                                                                               \
+            PADEL_HR_PSPAN8(0);   /* into the buffer this chunk read */                                           \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
             PADEL_HR_MFMA_ROW(0, 2, set_, false);                                                                 \
-            if constexpr (PADEL_HR_ON(32)) PADEL_HR_FLUSH(3);                                                     \
-            if constexpr (PADEL_HR_ON(128)) PADEL_HR_READROW(2, 0);                                               \
-            if constexpr (PADEL_HR_ON(16)) PADEL_HR_PSPAN8(1);                     \
+            PADEL_HR_FLUSH(3);                                                                                    \
+            PADEL_HR_READROW(2, 0);                                                                               \
+            PADEL_HR_PSPAN8(1);                                                                                   \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
             PADEL_HR_MFMA_ROW(1, 2, set_, false);                                                                 \
-            if constexpr (PADEL_HR_ON(32)) PADEL_HR_FLUSH(0);                                                     \
-            if constexpr (PADEL_HR_ON(128)) PADEL_HR_READROW(3, 0);                                               \
-            if constexpr (PADEL_HR_ON(16)) PADEL_HR_PSPAN8(2);                     \
+            PADEL_HR_FLUSH(0);                                                                                    \
+            PADEL_HR_READROW(3, 0);                                                                               \
+            PADEL_HR_PSPAN8(2);                                                                                   \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
         }                                                                                                         \
-        PADEL_HR_STAMP(T_, 4);                                                                                    \
     } while (0)
 
     int gpar = 0;                                 // parity of the running chunk count = the buffer the current chunk reads
@@ -346,13 +299,6 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
     PADEL_HR_PARAMS(cur, rsrcPn, 0);
     PADEL_HR_PATCH(0, 0, rsrcPn, 0);
     for (;;) {                                    // ---- tiles
-        if constexpr (DBG) {
-            const unsigned long long tb_ = __builtin_amdgcn_s_memtime(); dbg_k = 0;
-            if (dbg_tile <= kRDbgTile) t_begin = tb_;
-            if (dbg_tile == kRDbgTile + 1) t_end_rec = tb_;
-            // the tile log (records gridDim.x + blockIdx.x of the dump, behind the per-workgroup records): tile start / epilogue start
-            if (a.dbg && tid == 0 && dbg_tile < kRDbgWords / 2) a.dbg[((long long)G + blockIdx.x) * kRDbgWords + 2 * dbg_tile] = tb_;
-        }
         // this tile's patch parameters are the ones the previous tile computed as "next"
         rsrcP = rsrcPn;
 #pragma unroll
@@ -368,7 +314,6 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
         PADEL_HR_PATCH(1, gpar ^ 1, rsrcP, tpar);
         const HrTile nxt = hr_tile(a, v + G, vmax, 2 * NF);        // (the tile arithmetic runs under the latency of the requests above)
         PADEL_HR_PARAMS(nxt, rsrcPn, tpar ^ 1);
-        if constexpr ((ABL & 256) != 0) { wait_vm<0>(); for (int j = 0; j < NF; ++j) { w[2][j] = w[0][j]; if constexpr (!WS) wm[2][j] = wm[0][j]; } }      // (probe: no weight requests inside the loop)
         if (first) {
             wait_vm<2 * NW + 6>();               // P(0) landed (W(0), W(1), P(1) may be in flight)
             __builtin_amdgcn_s_barrier();
@@ -392,26 +337,19 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
         for (int c = 0; c < nch; ++c) {
             const bool own8 = c + 2 < nch;
             i32x4 rs8 = own8 ? rsrcP : rsrcPn;
-            if (c + 1 >= nch || (ABL & 2048)) rs8[2] = 0;      // (probe 2048: every tap-8 request through the zero-record descriptor)
+            if (c + 1 >= nch) rs8[2] = 0;
             const unsigned so8 = own8 ? (unsigned)(c + 2) * 128u : 0u;
             const int set8 = own8 ? tpar : tpar ^ 1;
             PADEL_HR_STEP(0); PADEL_HR_STEP(1); PADEL_HR_STEP(2); PADEL_HR_STEP(3); PADEL_HR_STEP(4);
             PADEL_HR_STEP(5); PADEL_HR_STEP(6); PADEL_HR_STEP(7); PADEL_HR_STEP(8);
             s_kb += 9u * 2048u;
             gpar ^= 1;
-            dbg_k += 9;
         }
-        PADEL_HR_PRIO(0);
         // the look-ahead requests of the last chunk (taps 9 / 10: weights nobody uses, issued to keep the counted waits static) target
         // register sets 0 and 1: they must have landed before the epilogue may reuse those registers
         PADEL_HR_WAITW(0, -kWQ * NW); PADEL_HR_WAITW(1, -kWQ * NW);       // vmcnt(0), both sets' registers through it
         PADEL_HR_FLUSH(1);
-        if constexpr ((ABL & 32) != 0) { PADEL_HR_FLUSH(0); PADEL_HR_FLUSH(2); PADEL_HR_FLUSH(3); }      // (probe: one main chain, flushed once)
 
-        if constexpr (DBG) {
-            if (a.dbg && tid == 0 && dbg_tile < kRDbgWords / 2) a.dbg[((long long)G + blockIdx.x) * kRDbgWords + 2 * dbg_tile + 1] = __builtin_amdgcn_s_memtime();
-            ++dbg_tile;
-        }
         int mpix[MF];
 #pragma unroll
         for (int f = 0; f < MF; ++f) {
@@ -439,23 +377,6 @@ __global__ void __launch_bounds__(256, 2) conv_h2r_kernel(const ConvArgs a, cons
 #undef PADEL_HR_PSPAN8
 #undef PADEL_HR_PARAMS
 #undef PADEL_HR_FLUSH
-    if constexpr (DBG) {
-        if (a.dbg) {
-            const unsigned long long t_end = t_end_rec ? t_end_rec : __builtin_amdgcn_s_memtime();      // the recorded tile's end = the next tile's start
-            __syncthreads();
-            unsigned long long* d = a.dbg + (long long)blockIdx.x * kRDbgWords;
-            for (int i = tid; i < 4 * kRDbgSteps * 5; i += 256) d[8 + i] = stamps[i];
-            if (lane == 0) {
-                const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);       // HW_REG_HW_ID
-                const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);     // HW_REG_XCC_ID
-                d[wave] = ((unsigned long long)xcc << 32) | hw;
-                if (wave == 0) { d[4] = t_begin; d[5] = t_end; d[6] = (unsigned long long)(nch * 9); d[7] = (unsigned long long)blockIdx.x; }      // the LAST tile's life
-            }
-        }
-    }
-#undef PADEL_HR_STAMP
-#undef PADEL_HR_PRIO
-#undef PADEL_HR_ON
 }
 
 // one thread per 16 bytes of the copy: [fragment f][k-step t][plane p][lane l] <- bytes [16 (l >> 4), +16) of plane p (h | m) of k-step t
@@ -504,22 +425,8 @@ hipError_t launch_conv_h2r(const ConvArgs& a_in, int tile, hipStream_t s) {
     const int vmax = 8 * ((a.n_mtiles + 7) / 8) * a.n_ntiles;          // virtual block ids
     static int n_cu = 0;
     if (!n_cu) { int dev = 0; hipDeviceProp_t p; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n_cu = p.multiProcessorCount; if (n_cu <= 0) n_cu = 256; }
-    const int per = (a.tune & 4) ? vmax : 2 * n_cu;                     // tuning bit 2: one workgroup per tile (the non-persistent form)
+    const int per = (a.tune & kTuneTilePerWorkgroup) ? vmax : 2 * n_cu;     // one workgroup per tile (the non-persistent form)
     dim3 grid((unsigned)(vmax < per ? vmax : per), 1, 1);               // 2 workgroups per CU (registers); both multiples of 8
-#ifdef PADEL_H2P_PROBES
-    if (nf == 3) {
-        if (a.dbg) {
-            hipLaunchKernelGGL((conv_h2r_kernel<3, true, true>), grid, dim3(256), 0, s, a, vmax);
-            return hipGetLastError();
-        }
-#define PADEL_HR_ABL(N_) case N_: hipLaunchKernelGGL((conv_h2r_kernel<3, true, false, N_>), grid, dim3(256), 0, s, a, vmax); return hipGetLastError();
-        switch ((a.tune >> 5) << 4) {      // tuning word bits 5.. = ABL >> 4
-            PADEL_HR_ABL(16) PADEL_HR_ABL(240) PADEL_HR_ABL(1008) PADEL_HR_ABL(2048)
-            default: break;
-        }
-#undef PADEL_HR_ABL
-    }
-#endif
     if (nf == 3) hipLaunchKernelGGL((conv_h2r_kernel<3, true>), grid, dim3(256), 0, s, a, vmax);
     else if (a.w_single) hipLaunchKernelGGL((conv_h2r_kernel<2, true>), grid, dim3(256), 0, s, a, vmax);
     else hipLaunchKernelGGL((conv_h2r_kernel<2, false>), grid, dim3(256), 0, s, a, vmax);

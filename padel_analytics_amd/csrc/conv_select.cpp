@@ -9,7 +9,7 @@
 //
 // The .hip files keep kernels and launch_conv_<family>(a, tile, s), which launches exactly that tile; the step builder (launch_plan.cpp)
 // resolves, launch_conv_family (conv_tap.hip) calls the launcher the row names.  A new tile is one table row and one launcher case.
-#include "kernels.h"
+#include "launch_plan.h"
 
 #include <string.h>
 
@@ -54,11 +54,6 @@ static const ConvTile kBx3Tiles[] = {
     // stride-1 3x3: the patch kernel measured 1.18x (48-channel tiles, 3 workgroups per CU) / 1.15x (64-channel tiles) the best
     // tap tile on full 8 x 16 patches (profiles/conv_bx3_sweep_r2n.txt); its fill counts the pixels of partial patches
     {303, CONV_BX3P, 8, 16, 48, 1.17f, 0.f},    {304, CONV_BX3P, 8, 16, 64, 1.14f, 0.f},   {306, CONV_BX3P, 8, 16, 96, 0.f, 0.f},
-#ifdef PADEL_BX3_PROBES      // ceiling probes of tile 220 (WRONG results; tools/conv_bench.py only)
-    {420, CONV_BX3T, 0, 128, 48, 0.f, 0.f},     {520, CONV_BX3T, 0, 128, 48, 0.f, 0.f},    {620, CONV_BX3T, 0, 128, 48, 0.f, 0.f},
-    {720, CONV_BX3T, 0, 128, 48, 0.f, 0.f},     {820, CONV_BX3T, 0, 128, 48, 0.f, 0.f},    {920, CONV_BX3T, 0, 128, 48, 0.f, 0.f},
-    {1020, CONV_BX3T, 0, 128, 48, 0.f, 0.f},    {1120, CONV_BX3T, 0, 128, 48, 0.f, 0.f},
-#endif
 };
 
 // ---- h2 (conv_tap_h2.hip and the files named at the rows).  Tap-tile speeds start from the bf16x3 measurements and are
@@ -100,12 +95,6 @@ static const ConvTile kH2Tiles[] = {
     {341, CONV_H2V, 16, 16, 16, 0.f, 0.f},     {341, CONV_H2W, 16, 16, 16, 1.28f, 0.f},
     {342, CONV_H2V, 16, 16, 32, 0.f, 0.f},     {342, CONV_H2W, 16, 16, 32, 1.42f, 0.f},
     {343, CONV_H2V, 16, 16, 48, 0.f, 0.f},     {343, CONV_H2W, 16, 16, 48, 1.46f, 0.f},
-#ifdef PADEL_H2P_PROBES      // ablations of tile 303 (tools only): 332 + probe number (probe 10 = id 342 is the wide patch tile's: never reachable)
-    {333, CONV_H2P, 8, 16, 48, 0.f, 0.f},      {334, CONV_H2P, 8, 16, 48, 0.f, 0.f},     {335, CONV_H2P, 8, 16, 48, 0.f, 0.f},
-    {336, CONV_H2P, 8, 16, 48, 0.f, 0.f},      {337, CONV_H2P, 8, 16, 48, 0.f, 0.f},     {339, CONV_H2P, 8, 16, 48, 0.f, 0.f},
-    {340, CONV_H2P, 8, 16, 48, 0.f, 0.f},      {347, CONV_H2P, 8, 16, 48, 0.f, 0.f},     {348, CONV_H2P, 8, 16, 48, 0.f, 0.f},
-    {349, CONV_H2P, 8, 16, 48, 0.f, 0.f},      {363, CONV_H2P, 8, 16, 48, 0.f, 0.f},
-#endif
 };
 static const float kH2rThreeProducts = 1.22f;      // tile 325 on a three-product layer (its row holds the two-product speed)
 
@@ -159,10 +148,8 @@ bool conv_tile_shape(int path, int id, int* bm, int* bn) {
     return true;
 }
 
-// tuning "timeline": the kernels instantiated with s_memtime stamps — the h2 quad patch kernels (conv_patch_h2q.hip; conv_patch_h2r.hip
-// on 96-channel tiles) and the 3x3 of the fp32 64 x 96 tap tile
+// tuning "timeline": the one kernel instantiated with s_memtime stamps — the 3x3 of the fp32 64 x 96 tap tile
 int conv_timeline_words(const ConvLaunched& k, int ksize) {
-    if (!strcmp(k.family, "h2q") || (!strcmp(k.family, "h2r") && k.tile == 324)) return kPatchDbgWords;
     if (!strcmp(k.family, "tap") && k.tile == 7 && ksize == 3) return kConvDbgWords;
     return 0;
 }
@@ -227,16 +214,16 @@ static bool conv_p16_supported(const ConvArgs& a) { return a.ksize == 3 && a.str
 static bool family_takes(ConvFamily family, const ConvArgs& a, int id) {
     switch (family) {
         case CONV_TAP: case CONV_TAP16: case CONV_TAP16D: return true;
-        case CONV_BX3T: return id < 400 ? up_ok_1x1(a) : a.ksize == 3;      // (>= 400: the ceiling probes)
+        case CONV_BX3T: return up_ok_1x1(a);
         case CONV_BX3P: return conv_bx3p_supported(a);
         case CONV_H2T: return up_ok_1x1(a);
         case CONV_H2D: return a.ksize == 1 && up_ok_1x1(a);
         case CONV_H2S: return conv_h2s_supported(a);
         case CONV_H2S3: return conv_h2s3_supported(a);
-        case CONV_H2P: return conv_h2p_supported(a) && (id < 330 || (!a.in2 && !(a.cin & 16)));      // (>= 330: the ablation probes)
+        case CONV_H2P: return conv_h2p_supported(a);
         case CONV_H2Q: return conv_h2q_supported(a);
         case CONV_H2R: return conv_h2r_supported(a) && (id == 325 || a.w_single);      // 96-channel tiles: two-product layers only
-        case CONV_H2V: return !(a.tune & 8) && conv_h2v_supported(a) && (id < 343 || a.w_single);      // tuning bit 3: the round-3 kernel; 3 fragments: two products only
+        case CONV_H2V: return !(a.tune & kTunePrevGen) && conv_h2v_supported(a) && (id < 343 || a.w_single);      // kTunePrevGen: h2w, the round-3 kernel; 3 fragments: two products only
         case CONV_H2W: return conv_h2w_supported(a);
         case CONV_P16: case CONV_P16Q: return conv_p16_supported(a);
     }

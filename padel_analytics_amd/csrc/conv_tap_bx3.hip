@@ -29,8 +29,8 @@
 // patch kernel (conv_patch_bx3.hip: input split once per chunk instead of once per tap) does not take.  Both kernels
 // exist with a 3-stage ring (prefetch distance 2, ids 6..25) and a 2-stage ring (prefetch distance 1, ids + 200: two
 // thirds of the LDS -> 3 workgroups per CU, the default); the 1x1 kernel can absorb a preceding nn.Upsample(2)
-// (template flag UP: the first up_c channels come from the coarse map).  -DPADEL_BX3_PROBES adds instantiations of
-// tile 220 with parts of the k-step removed (wrong results; ceiling measurements, profiles/conv_bx3_probes_r2m.txt).
+// (template flag UP: the first up_c channels come from the coarse map).  (Instantiations of tile 220 with parts of the
+// k-step removed — wrong results, ceiling measurements: profiles/conv_bx3_probes_r2m.txt — are gone: DESIGN.md §5.)
 #include "bx3_common.h"
 
 namespace padel {
@@ -50,11 +50,7 @@ namespace padel {
         _Pragma("unroll") for (int f = 0; f < MF; ++f) {                                                          \
             const f32x4 x0 = *reinterpret_cast<const f32x4*>(PADEL_BX3_AR(ST_) + f * 256);                     \
             const f32x4 x1 = *reinterpret_cast<const f32x4*>(PADEL_BX3_AR(ST_) + BM * 16 + f * 256);           \
-            if constexpr (DBG & 1) {       /* ceiling probe: no split arithmetic (results are wrong) */          \
-                ah[f] = __builtin_bit_cast(bf8, x0); am[f] = __builtin_bit_cast(bf8, x1); al[f] = ah[f];          \
-            } else {                                                                                              \
-                split8(x0, x1, ah[f], am[f], al[f]);                                                              \
-            }                                                                                                     \
+            split8(x0, x1, ah[f], am[f], al[f]);                                                                  \
         }                                                                                                         \
         bf8 wh[NF], wm[NF], wl[NF];                                                                               \
         _Pragma("unroll") for (int j = 0; j < NF; ++j) {                                                          \
@@ -63,10 +59,6 @@ namespace padel {
             wl[j] = __builtin_bit_cast(bf8, *reinterpret_cast<const f32x4*>(PADEL_BX3_BR(ST_) + 2 * BN * 16 + j * 256)); \
         }                                                                                                         \
         __builtin_amdgcn_s_setprio(1);                                                                            \
-        if constexpr (DBG & 2) {           /* ceiling probe: full split, one product group instead of six */      \
-            _Pragma("unroll") for (int f = 0; f < MF; ++f) { asm volatile("" :: "v"(am[f]), "v"(al[f])); }        \
-            _Pragma("unroll") for (int j = 0; j < NF; ++j) { asm volatile("" :: "v"(wm[j]), "v"(wl[j])); }        \
-        } else {                                                                                                  \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) _Pragma("unroll") for (int j = 0; j < NF; ++j)             \
             part[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], al[f], part[f][j], 0, 0, 0);              \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) _Pragma("unroll") for (int j = 0; j < NF; ++j)             \
@@ -77,7 +69,6 @@ namespace padel {
             part[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], am[f], part[f][j], 0, 0, 0);              \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) _Pragma("unroll") for (int j = 0; j < NF; ++j)             \
             part[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm[j], ah[f], part[f][j], 0, 0, 0);              \
-        }                                                                                                         \
         _Pragma("unroll") for (int f = 0; f < MF; ++f) _Pragma("unroll") for (int j = 0; j < NF; ++j)             \
             part[f][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[j], ah[f], part[f][j], 0, 0, 0);              \
         __builtin_amdgcn_s_setprio(0);                                                                            \
@@ -95,17 +86,13 @@ namespace padel {
 #define PADEL_BX3_DMA_R(rsrcA, SR_, SA0_, SA1_, SB_, VA0_, VA1_, VB0_, VB1_)                                      \
     do {                                                                                                          \
         const unsigned sa0_ = (SA0_), sa1_ = (SA1_), sb_ = (SB_);                                                 \
-        if constexpr (!(DBG & 4)) {        /* probe bit 4: no activation requests */                              \
         lds_dma<PADEL_BX3_IMM(SR_)>((VA0_), rsrcA, sa0_, PADEL_BX3_LW(SR_));                                      \
         if constexpr (AP >= 2) lds_dma<PADEL_BX3_IMM(SR_) + RP * 64>((VA1_), rsrcA, sa0_, PADEL_BX3_LW(SR_));     \
         lds_dma<PADEL_BX3_IMM(SR_) + BM * 64>((VB0_), rsrcA, sa1_, PADEL_BX3_LW(SR_));                            \
         if constexpr (AP >= 2) lds_dma<PADEL_BX3_IMM(SR_) + BM * 64 + RP * 64>((VB1_), rsrcA, sa1_, PADEL_BX3_LW(SR_)); \
-        }                                                                                                         \
-        if constexpr (!(DBG & 8)) {        /* probe bit 8: no weight requests */                                  \
         PADEL_BX3_DMAB(SR_, 0, sb_);                                                                              \
         PADEL_BX3_DMAB(SR_, 1, sb_ + 64u);                                                                        \
         PADEL_BX3_DMAB(SR_, 2, sb_ + 128u);                                                                       \
-        }                                                                                                         \
     } while (0)
 #define PADEL_BX3_DMAB(SR_, PL_, SB_)                                                                             \
     do {                                                                                                          \
@@ -134,8 +121,7 @@ namespace padel {
     const int wm = wave / WN, wn = wave % WN;                                                                     \
     const int nmt = a.n_mtiles, nnt = a.n_ntiles;                                                                 \
     const int bid = blockIdx.x;                                                                                   \
-    /* XCD-aware 1-D tile map: xcd_slot / xcd_slot_padding / xcd_slot_mtile of conv_index.h, written out (through \
-       the functions one -DPADEL_BX3_PROBES instantiation allocates its scalar registers differently) */          \
+    /* XCD-aware 1-D tile map: xcd_slot / xcd_slot_padding / xcd_slot_mtile of conv_index.h, written out */       \
     const int q = nmt >> 3, r = nmt & 7, xcd = bid & 7, idx = bid >> 3;                                           \
     const int mloc = idx / nnt, nt = idx - mloc * nnt;                                                            \
     if (mloc >= q + (xcd < r ? 1 : 0)) return;       /* grid is padded to 8 x max tiles per XCD */                \
@@ -181,7 +167,7 @@ namespace padel {
     bx3_epilogue<MF, NF>(a, acc, mpix_, f0 + wn * NF, lq, fast_);
 
 // =====================================================================================================  3x3
-template <int WM, int WN, int MF, int NF, int NSTG, int DBG = 0>
+template <int WM, int WN, int MF, int NF, int NSTG>
 __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2 ? 1 : 0)) conv_bx3_kernel(const ConvArgs a) {
     PADEL_BX3_GEOMETRY()
     unsigned voffA[AP][9];
@@ -333,7 +319,6 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
 // [y >> 1][x >> 1] — an nn.Upsample(2) + torch.cat in front of this conv that is never materialised
 template <int WM, int WN, int MF, int NF, int NSTG, bool UP>
 __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2 ? 1 : 0)) conv_bx3_1_kernel(const ConvArgs a) {
-    constexpr int DBG = 0;
     PADEL_BX3_GEOMETRY()
     unsigned voffA[AP];
     unsigned voffU[AP];
@@ -423,14 +408,14 @@ __global__ void __launch_bounds__(64 * WM * WN, min_waves3(MF * NF) + (NSTG == 2
 #undef PADEL_BX3_A1
 }
 
-template <int WM, int WN, int MF, int NF, int NSTG = 3, int DBG = 0>
+template <int WM, int WN, int MF, int NF, int NSTG = 3>
 static hipError_t launch_b3(const ConvArgs& a_in, hipStream_t s) {
     ConvArgs a = a_in;
     constexpr int BM = WM * MF * 16;
     a.n_mtiles = (a.M + BM - 1) / BM;
     a.n_ntiles = (a.n16 + WN * NF - 1) / (WN * NF);
     dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8) * (unsigned)a.n_ntiles, 1, 1);
-    if (a.ksize == 3) hipLaunchKernelGGL((conv_bx3_kernel<WM, WN, MF, NF, NSTG, DBG>), grid, dim3(64 * WM * WN), 0, s, a);
+    if (a.ksize == 3) hipLaunchKernelGGL((conv_bx3_kernel<WM, WN, MF, NF, NSTG>), grid, dim3(64 * WM * WN), 0, s, a);
     else hipLaunchKernelGGL((conv_bx3_1_kernel<WM, WN, MF, NF, NSTG, false>), grid, dim3(64 * WM * WN), 0, s, a);
     return hipGetLastError();
 }
@@ -473,16 +458,6 @@ hipError_t launch_conv_bx3t(const ConvArgs& a, int tile, hipStream_t s) {
         case 211: return launch_b3<4, 1, 2, 2, 2>(a, s);
         case 225: return launch_b3<4, 1, 1, 5, 2>(a, s);
         case 213: return launch_b3<4, 1, 2, 6, 2>(a, s);   // 128 x 96 with 4 waves (2 x 6 fragments each), 2 workgroups per CU
-#ifdef PADEL_BX3_PROBES      // ceiling probes of tile 220 (WRONG results; tools/conv_bench.py only), DBG bits: 1 no split VALU, 2 one of the 6 MFMA groups, 4 / 8 no activation / weight requests
-        case 420: return launch_b3<4, 1, 2, 3, 2, 1>(a, s);
-        case 520: return launch_b3<4, 1, 2, 3, 2, 2>(a, s);
-        case 620: return launch_b3<4, 1, 2, 3, 2, 3>(a, s);    // no split, 1 group: data movement only
-        case 720: return launch_b3<4, 1, 2, 3, 2, 4>(a, s);    // no activation requests
-        case 820: return launch_b3<4, 1, 2, 3, 2, 8>(a, s);    // no weight requests
-        case 920: return launch_b3<4, 1, 2, 3, 2, 12>(a, s);   // no requests at all
-        case 1020: return launch_b3<4, 1, 2, 3, 2, 13>(a, s);  // LDS reads + 6 MFMA groups + barriers only
-        case 1120: return launch_b3<4, 1, 2, 3, 2, 5>(a, s);   // no split, no activation requests
-#endif
         case 25: return launch_b3<4, 1, 1, 5>(a, s);   //  64 x  80, 4 waves of 16 x 80: the 19-fragment (304-channel) fused pose heads
     }
     return hipErrorNotSupported;

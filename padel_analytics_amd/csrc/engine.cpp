@@ -22,12 +22,13 @@ size_t pa_device_bytes_live(void) { return g_live_bytes.load(); }
 // pa_engine_create (none: set_tuning only), field, and how a value is normalised on both ways in.  A flag is only ever tested
 // for truth; fuse_stem / fuse_sppf keep the raw value (fuse_sppf 2..4 force a workgroup size, kernels_misc.hip).
 static int knob_raw(int v) { return v; }
+static int knob_tune(int v) { return v & kTuneMask; }      // launch_plan.h: no other bit selects anything
 static int knob_flag(int v) { return v ? 1 : 0; }
 static int knob_tap_pd(int v) { return v == 3 ? 3 : 2; }
 static int knob_lanes(int v) { return v >= 2 ? 2 : 1; }
 static const struct Knob { const char* key; const char* env; int Tuning::*field; int (*norm)(int); } kKnobs[] = {
     {"variant", "PADEL_CONV_VARIANT", &Tuning::variant, knob_raw},
-    {"tune", "PADEL_CONV_TUNE", &Tuning::tune, knob_raw},
+    {"tune", "PADEL_CONV_TUNE", &Tuning::tune, knob_tune},
     {"tap_pd", "PADEL_CONV_TAP_PD", &Tuning::tap_pd, knob_tap_pd},
     {"graph", "PADEL_GRAPH", &Tuning::graph, knob_flag},
     {"timeline", nullptr, &Tuning::timeline, knob_flag},

@@ -35,7 +35,7 @@ struct ConvArgs {
     int M;                // batch * Ho * Wo
     int n_mtiles;         // ceil(M / BM)
     int n_ntiles;         // bx3 / fp16 kernels (1-D grid): channel tiles per pixel tile
-    int tune;             // bit 0: s_setprio(1) around MFMA clusters; bit 1: staggered workgroup start
+    int tune;             // Tuning::tune (launch_plan.h: kTuneTilePerWorkgroup, kTunePrevGen; no kernel reads another bit)
     int tap_pd;           // 1x1 tap kernel: prefetch distance 2 or 3 (pa_engine_set_tuning "tap_pd")
     int out_f32;          // fp16 / h2 kernels only: 1 = `out` is an fp32 buffer (convs that feed the Detect/Pose decode)
     const float* oscale;  // h2 kernels: [Npad] 1 / (power-of-two scale of the weight row), applied before the bias
@@ -61,8 +61,6 @@ inline void fill_fastdiv(unsigned d, unsigned* magic, unsigned* shift) {
 constexpr int conv_dbg_words(int steps) { return 8 + 4 * steps * 5; }
 constexpr int kConvDbgSteps = 64;                       // k-steps kept per wave (ring): the fp32 tap kernel (conv_tap.hip)
 constexpr int kConvDbgWords = conv_dbg_words(kConvDbgSteps);
-constexpr int kPatchDbgSteps = 32;                      // ... the h2 quad patch kernels (conv_patch_h2q.hip, conv_patch_h2r.hip)
-constexpr int kPatchDbgWords = conv_dbg_words(kPatchDbgSteps);
 
 // ---- which kernel runs a conv (conv_select.cpp: host code only) -----------------------------------------------------
 // The implicit-GEMM conv on v_mfma_f32_16x16x4_f32 (strict fp32: the cross-check / no-argument leg) is the tap-unrolled LDS-DMA

@@ -37,7 +37,7 @@ bool stem_l1_h2_supported(const StemArgs& st, const ConvArgs& a) {
 // ... with cv1, a 1x1 stride-1 conv over exactly that conv's 2c outputs with 2c outputs of its own, as the kernel's third phase.  The
 // first line is what launch_stem_l1_h2 asks before it picks a register-weights instantiation: the third phase exists in those only
 bool stem_l1_cv1_h2_supported(const StemArgs& st, const ConvArgs& a, const ConvArgs& b) {
-    return stem_l1_h2_supported(st, a) && a.w_single && a.wr && st.opw && (st.W & 3) == 0 && !(a.tune & 8) &&
+    return stem_l1_h2_supported(st, a) && a.w_single && a.wr && st.opw && (st.W & 3) == 0 && !(a.tune & kTunePrevGen) &&
            a.act == ACT_SILU && !a.out_f32 && a.out &&
            b.ksize == 1 && b.stride == 1 && b.cin == a.cout && b.cout == a.cout && b.n16 * 16 == b.cout && b.H == a.Ho && b.W == a.Wo &&
            b.Ho == a.Ho && b.Wo == a.Wo && b.M == a.M && b.in == a.out && b.in_cs == a.out_cs && b.in_choff == a.out_choff &&

@@ -18,7 +18,10 @@ struct Tuning {
                          // pipe, fp32 accumulate (admitted by the same parity criteria as the fp32-MFMA kernels);
                          // 0: tap-unrolled LDS-DMA fp32-MFMA kernels, 1: LDS kernel (their bitwise cross-check)
     int variant = -1;    // forced tile id (tests / tools), -1: per-layer heuristic
-    int tune = 1;        // bit 0: s_setprio around MFMA clusters
+    int tune = 1;        // the tuning word: kTune* below are all of its bits that anything reads.  Bits 0 and 1 (once s_setprio around MFMA
+                         // clusters and a staggered workgroup start) are read by no kernel any more; the default stays 1.  The engine
+                         // keeps bits 0..3 of what pa_engine_set_tuning "tune" / PADEL_CONV_TUNE give it (engine.cpp: knob_tune), so
+                         // every value of the word runs product kernels
     int tap_pd = 2;      // prefetch distance of the 1x1 tap kernel
     int graph = 0;       // 1: replay the op list of a (model, batch) from a captured hipGraph
     int timeline = 0;    // 1: 3x3 tap launches of the 64x96 tile run the s_memtime-instrumented instantiation
@@ -39,6 +42,11 @@ struct Tuning {
     int fold_up = 1;     // 1: an nn.Upsample(2) whose only reader is a bf16x3 1x1 conv is never materialised (the conv
                          // fetches those channels at [y >> 1][x >> 1] of the coarse map), 0: run the upsample kernel
 };
+// The bits of Tuning::tune / ConvArgs::tune.  Every kernel they select computes the same results bitwise (tests pass 5, 8 and 9)
+constexpr int kTuneTilePerWorkgroup = 4;     // bit 2: conv_patch_h2r.hip launches one workgroup per tile instead of 2 persistent ones per CU
+constexpr int kTunePrevGen = 8;              // bit 3: the previous kernel generation — h2w instead of h2v (conv_select.cpp), the weight-ring
+                                             // fused stem instead of the register-weights one (launch_plan.cpp, stem_l1_h2.hip)
+constexpr int kTuneMask = 15;                // bits 0..3: what the engine keeps of a tuning word
 
 // ---- a conv's request ------------------------------------------------------------------------------------------------
 int choose_conv_tile(int path, const ConvArgs& a);      // the path's chooser (kernels.h)

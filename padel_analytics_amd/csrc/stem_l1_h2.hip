@@ -28,6 +28,7 @@
 // c = 48 (yolov8m): the chunk planes (40 KB) and the tail planes would not fit next to the weight ring, so the tail channels
 // of the stem are computed AFTER the chunk steps into the same LDS region (their u8 operands are kept in registers).
 #include "h2_common.h"
+#include "launch_plan.h"
 
 namespace padel {
 
@@ -210,12 +211,8 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
             const int c = tid + 256 * r;
             const int iy = py0 + stem_patch_chunk_row(c), ix0 = px0 + stem_patch_chunk_col(c);
             pch[r] = (u32x4){0u, 0u, 0u, 0u};
-#if defined(PADEL_STEM_PROBE) && (PADEL_STEM_PROBE == 2 || PADEL_STEM_PROBE == 5)
-            pch[r] = (u32x4){(unsigned)c, (unsigned)c * 3u, (unsigned)c * 7u, (unsigned)c * 11u};      // probe: no input loads
-#else
             if (c < kStemPatchChunks && stem_patch_chunk_inside(st.H, st.W, iy, ix0))
                 pch[r] = *reinterpret_cast<const u32x4*>(img + (long long)iy * st.W + ix0);
-#endif
         }
         const char* const blk = reinterpret_cast<const char*>(st.opw);
 #pragma unroll
@@ -304,11 +301,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
             const int iy = sy * 2 - 1 + kdy[kk], ix = sx * 2 - 1 + kdx[kk];
             okk[kk] = s_in[i] && kval[kk] && (unsigned)iy < (unsigned)st.H && (unsigned)ix < (unsigned)st.W;
             const int iyc = min(max(iy, 0), st.H - 1), ixc = min(max(ix, 0), st.W - 1);
-#if defined(PADEL_STEM_PROBE) && (PADEL_STEM_PROBE == 2 || PADEL_STEM_PROBE == 5)
-            pxw[kk] = (uint32_t)(iyc * 3 + ixc * 7);      // probe: no input gathers
-#else
             pxw[kk] = img[(long long)iyc * st.W + ixc];
-#endif
         }
 #pragma unroll
         for (int kk = 0; kk < 8; ++kk) {
@@ -318,11 +311,6 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
     }
     }
     bool bad = false;
-#if defined(PADEL_STEM_PROBE) && (PADEL_STEM_PROBE == 1 || PADEL_STEM_PROBE == 5)
-#define PADEL_STEM_ACT(x_) (x_)                      // probe: no SiLU in the stem phase (wrong results)
-#else
-#define PADEL_STEM_ACT(x_) h2_act<ACT_SILU>(x_)
-#endif
     // stem fragments [J0_, J0_ + NJ_) of every owned position -> pairs in LDS.  TL_: they are the 16-channel tail group
     // (32 bytes per entry and plane), else halves 0 / 1 of the 32-channel chunk (64 bytes per entry and plane)
 #define PADEL_FS_STEM(J0_, NJ_, TL_)                                                                              \
@@ -337,7 +325,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
                 _Pragma("unroll") for (int j = 0; j < (NJ_); ++j) {                                               \
                     f32x4 v;                                                                                      \
                     _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                               \
-                        const float x = PADEL_STEM_ACT(fmaf(fmaf(scross[j][r], kH2InvScale, smain[j][r]), osc4[(J0_) + j][r], bias4[(J0_) + j][r])); \
+                        const float x = h2_act<ACT_SILU>(fmaf(fmaf(scross[j][r], kH2InvScale, smain[j][r]), osc4[(J0_) + j][r], bias4[(J0_) + j][r])); \
                         v[r] = s_in[i] ? x : 0.0f;                                                                \
                     }                                                                                             \
                     h16x4 hv, mv;                                                                                 \
@@ -638,13 +626,7 @@ __global__ void __launch_bounds__(256, 2) stem_l1_h2_kernel(const StemArgs st, c
         const bool fast3 = oy0 + 4 <= a.Ho && ox0 + 16 <= a.Wo && (fw + NF) * 16 <= b.cout && (((b.out_choff | b.out_cs) & 3) == 0);
         h2_epilogue<MF, NF>(b, acc3, cross3, mpix, fw, lq, fast3);
     } else {
-#if defined(PADEL_STEM_PROBE) && (PADEL_STEM_PROBE == 4 || PADEL_STEM_PROBE == 5)
-    ConvArgs a_lin = a;                              // probe: layer 1's epilogue without its SiLU (wrong results)
-    a_lin.act = ACT_NONE;
-    h2_epilogue<MF, NF>(a_lin, acc, cross, mpix, fw, lq, fast);
-#else
     h2_epilogue<MF, NF>(a, acc, cross, mpix, fw, lq, fast);
-#endif
     }
 }
 
@@ -664,7 +646,7 @@ hipError_t launch_stem_l1_h2(const StemArgs& st, const ConvArgs& a_in, const Con
     a.n_mtiles = batch * ((a.Ho + 3) / 4) * ((a.Wo + 15) / 16);
     a.n_ntiles = 1;
     dim3 grid(8u * (unsigned)((a.n_mtiles + 7) / 8), 1, 1);
-    // register weights (tuning bit 3: the round-5 weight ring).  They read the stem operand block and stage the input in 16-byte
+    // register weights (kTunePrevGen: the round-5 weight ring).  They read the stem operand block and stage the input in 16-byte
     // chunks of 4 pixels: W % 4 == 0
     if (cv1) {
         switch (st.cout / 16) {
@@ -674,7 +656,7 @@ hipError_t launch_stem_l1_h2(const StemArgs& st, const ConvArgs& a_in, const Con
             default: return hipErrorNotSupported;
         }
     }
-    if (a.w_single && a.wr && st.opw && (st.W & 3) == 0 && !(a.tune & 8)) {
+    if (a.w_single && a.wr && st.opw && (st.W & 3) == 0 && !(a.tune & kTunePrevGen)) {
         switch (st.cout / 16) {
             case 1: hipLaunchKernelGGL((stem_l1_h2_kernel<1, true, true>), grid, dim3(256), 0, s, st, a, b); return hipGetLastError();
             case 2: hipLaunchKernelGGL((stem_l1_h2_kernel<2, true, true>), grid, dim3(256), 0, s, st, a, b); return hipGetLastError();

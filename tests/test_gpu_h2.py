@@ -246,6 +246,33 @@ def test_h2_two_product_mode_on_fp16_weights(gpu_engine, case):
     assert rms(ref) <= 1.25 * rms(y32) + 1e-9, (rms(ref), rms(y32))
 
 
+_TUNE_1X1, _TUNE_S2, _TUNE_S1 = (1, 16, 16, 64, 192, 1, 1, G.ACT_SILU, False), (1, 16, 16, 64, 192, 3, 2, G.ACT_SILU, False), (1, 8, 16, 64, 96, 3, 1, G.ACT_SILU, False)
+
+
+@pytest.mark.parametrize("tile,case", [(245, _TUNE_1X1), (247, _TUNE_1X1), (246, _TUNE_S2), (248, _TUNE_S2), (324, _TUNE_S1)], ids=["245", "247", "246", "248", "324"])
+def test_every_tuning_word_runs_the_product_kernel(gpu_engine, tile, case):
+    """Bits 5..14 of the tuning word used to select ablation probes — kernels with pieces of the main loop compiled out, wrong results
+    by construction: bit 6 (+ 8..12) in conv_1x1_h2s.hip in every build, bits 5.. in conv_patch_h2r.hip in probe builds.  They are gone and
+    the engine keeps bits 0..3 of the word (csrc/launch_plan.h): the same kernel, the same bits of output, whatever else is set.  The
+    smallest two-product shapes that are native for each tile."""
+    assert TS.native("h2", tile, case, True)
+    want = TS.expected("h2", tile, case, True)
+    x, w, b, wr = _data(case)
+    w = w.astype(np.float16).astype(np.float32)                # fp16 numbers: the packed m plane is all zero
+    assert _graph(case, w, b, wr, G.DTYPE_H2).ops[-1]["flags"] & G.FLAG_W_SINGLE
+    outs, got = {}, {}
+    try:
+        for tune in (1, 1 | 0x7FE0):
+            gpu_engine.set_tuning(variant=tile, tune=tune)
+            ran = {}
+            outs[tune] = _run(gpu_engine, case, x, w, b, wr, ran=ran)
+            got[tune] = ran["launched"]
+    finally:
+        gpu_engine.set_tuning(tune=1, variant=-1)
+    assert got[1] == want and got[1 | 0x7FE0] == want, (got, want)
+    assert np.array_equal(outs[1], outs[1 | 0x7FE0]), f"tile {tile}: tuning word 0x7FE1 changes {int((outs[1] != outs[1 | 0x7FE0]).sum())} of {outs[1].size} values"
+
+
 @pytest.mark.parametrize("xs,ws", [(1e-4, 1.0), (3e-6, 1e-3), (200.0, 1e-5), (1.0, 64.0)], ids=["tiny-x", "tiny-x-w", "big-x-tiny-w", "big-w"])
 def test_h2_dynamic_range(gpu_engine, xs, ws):
     """fp16 subnormal parts (|x| < 6.1e-5: h is subnormal or 0, m carries the value) must survive the MFMA, and the

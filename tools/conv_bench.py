@@ -110,7 +110,7 @@ def main():
         for t in tiles:
             kw = dict(impl=0, variant=-1, tap_pd=2)        # "auto" / Tn / Apn: the fp32-MFMA tap kernels
             kw["tune"] = 1
-            if t.startswith("T"):                         # Tn = tile n; Tn:m = tile n with tuning word m (probe builds: ablation bits)
+            if t.startswith("T"):                         # Tn = tile n; Tn:m = tile n with tuning word m (launch_plan.h: kTune*)
                 tt = t[1:].split(":")
                 kw.update(variant=int(tt[0]))
                 if len(tt) > 1:

@@ -9,7 +9,6 @@
 #   smoke         __graft_entry__.smoke()
 #   ubench        tools/mfma_f16_ubench (16x16x32 and 32x32x16 f16 MFMA ceilings)
 #   sweep         tools/conv_bench.py --dtype h2 for every library under tools/ab/ and the product library
-#   timeline      tools/timeline_probe.py --kernel h2q with tools/ab/libpadel_hip_probes.so (192->192 and 96->96)
 #   pmc_nms       instruction mix / wait breakdown of nms_kernel and decode_kernel (tools/pmc_nms.sh)
 #   tiles         tools/conv_bench.py --dtype h2 --tiles $TILES (default auto,T323,T303) on $SWEEP_ARGS shapes
 #   tests_sel     python -m pytest $PYTEST_SEL -m gpu (any selection)
@@ -53,10 +52,6 @@ for stage in "$@"; do
         PADEL_LIB=$lib timeout 600 python tools/conv_bench.py --dtype h2 --tiles auto --reps 5 ${SWEEP_ARGS:-} > "$OUT/sweep_$name.txt" 2>&1; note "sweep:$name" $?
         echo "== $name"; cat "$OUT/sweep_$name.txt" | tail -24
       done ;;
-    timeline)
-      PADEL_LIB=tools/ab/libpadel_hip_probes.so timeout 300 python tools/timeline_probe.py --kernel h2q --out "$OUT/timeline_h2q_192.txt" > /dev/null 2>"$OUT/timeline_192.err"; note "timeline:192" $?
-      PADEL_LIB=tools/ab/libpadel_hip_probes.so timeout 300 python tools/timeline_probe.py --kernel h2q --cin 96 --cout 96 --hw 96x160 --out "$OUT/timeline_h2q_96.txt" > /dev/null 2>"$OUT/timeline_96.err"; note "timeline:96" $?
-      head -60 "$OUT/timeline_h2q_192.txt"; head -20 "$OUT/timeline_h2q_96.txt"; grep -A3 'epilogue' "$OUT/timeline_h2q_96.txt" | head -5 ;;
     bench)
       timeout 1200 python bench.py --full --dump-ops "$OUT/ops_c3.csv" > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"; note $stage $?
       python tools/bench_summary.py "$OUT/bench_c3.json" ;;
