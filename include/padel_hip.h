@@ -214,14 +214,29 @@ int pa_yuv_last_path(pa_engine* eng);
  *                    is the weight a of the mark's colour, in 1..255, and a covered pixel becomes, per channel,
  *                        (p * (256 - a) + c * a + 128) >> 8
  *                    p the channel as the marks BEFORE this one in the list left it, c the mark's channel.  A later mark sees the
- *                    blended value.  (a = 128 over c = 0xffffff: half way to white; p = c stays p for every a.)                   */
-enum pa_mark_kind { PA_MARK_DISC = 1, PA_MARK_SEGMENT = 2, PA_MARK_FILL = 3, PA_MARK_BOX = 4, PA_MARK_GLYPH = 5, PA_MARK_BLEND = 6 };
+ *                    blended value.  (a = 128 over c = 0xffffff: half way to white; p = c stays p for every a.)
+ *   PA_MARK_ARC      an axis-parallel elliptical ring cut to octants, opaque: centre (x0, y0), OUTER semi-axes a = x1, b = y1, each in
+ *                    1..4095, thickness t = size in 1..255 (the ring grows inwards, like PA_MARK_BOX), octant mask `arg` in 1..255.
+ *                    dx = x - x0, dy = y - y0;  in(X, Y, A, B):  X^2 B^2 + Y^2 A^2 <= A^2 B^2  (int64: |dx| <= 16383 and A, B <= 4095
+ *                    keep every term below 2^54).  Covered iff all three hold:
+ *                      1. in(dx, dy, a, b);
+ *                      2. the hole rule  a - t < 1 or b - t < 1 or !in(dx, dy, a - t, b - t),  or the rim rule: one of the four
+ *                         neighbours (dx +- 1, dy), (dx, dy +- 1) fails in(., ., a, b) — the 4-neighbour inner boundary of the filled
+ *                         ellipse, without which a thin ring of a flat ellipse has gaps between the axes (the two ellipses are closer
+ *                         than a pixel there); with it a full ring is 8-connected and closed;
+ *                      3. bit k of `arg` is set for the pixel's octant k, taken in the ellipse's parameter space, y pointing down:
+ *                         u = dx b, v = dy a; octant 0 is u > 0, 0 <= v < u; octant 1 is u > 0, v >= u; octants 2k and 2k + 1 are the
+ *                         same two tests after rotating (u, v) -> (v, -u) k times: octant k is the parameter angle [45 k, 45 (k + 1))
+ *                         degrees, half-open.  The centre pixel (u = v = 0) counts as octant 0.
+ *                    Every covered pixel lies in x0 - a .. x0 + a, y0 - b .. y0 + b.  Kinds 7 and 9 do not exist.                    */
+enum pa_mark_kind { PA_MARK_DISC = 1, PA_MARK_SEGMENT = 2, PA_MARK_FILL = 3, PA_MARK_BOX = 4, PA_MARK_GLYPH = 5, PA_MARK_BLEND = 6,
+                    PA_MARK_ARC = 8 };
 typedef struct pa_mark {
     int32_t kind;                 /* enum pa_mark_kind                                  */
     int32_t x0, y0, x1, y1;
     int32_t size;                 /* radius, thickness or scale, by kind                */
     uint32_t bgr;                 /* B | G << 8 | R << 16                                */
-    int32_t arg;                  /* PA_MARK_GLYPH: character code; PA_MARK_BLEND: weight 1..255; otherwise 0 */
+    int32_t arg;                  /* PA_MARK_GLYPH: character code; PA_MARK_BLEND: weight 1..255; PA_MARK_ARC: octant mask 1..255; otherwise 0 */
 } pa_mark;
 /* BGR -> YUV 4:2:0, the inverse of pa_yuv420_to_bgr.  All int32, >> arithmetic:
  *     Y = clamp(((yr R + yg G + yb B + (1 << 19)) >> 20) + y_off, 0, 255)                        per pixel
@@ -239,7 +254,7 @@ enum pa_render_out { PA_RENDER_BGR = 0, PA_RENDER_YUV420 = 1 };
  * (geom, enc ignored; dst_dev == src_bgr_dev renders in place: every thread reads its own pixels before it writes them, and a
  * tile no mark meets writes nothing); any other overlap of dst and src is the caller's error.  out = PA_RENDER_YUV420: frame i at
  * dst_dev + i * geom->frame_stride as geom lays it out; w, h even.  The source is never written unless dst == src in BGR mode.
- * Refused, nothing launched, the reason in pa_last_error: an unknown kind, a coordinate / size / code / weight out of range, a bad first[],
+ * Refused, nothing launched, the reason in pa_last_error: an unknown kind, a coordinate / size / code / weight / semi-axis / octant mask out of range, a bad first[],
  * n < 1, w or h over 8192, YUV output with odd or too small w / h, a pitch smaller than its row, planes reaching into the next
  * frame, NV12 with off_v != off_u + 1, coefficients that could leave int32.  pa_render_check gives the same answers on the host
  * alone (no engine, no GPU): 0, or 1 with the reason in why[0 .. cap).

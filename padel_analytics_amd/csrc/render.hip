@@ -44,6 +44,17 @@ __device__ __forceinline__ MarkBox unpack_box(uint2 b) {
     return {(int)(short)(b.x & 0xffff), (int)b.x >> 16, (int)(short)(b.y & 0xffff), (int)b.y >> 16};
 }
 
+// PA_MARK_ARC's coverage of a thread's 2 x 4 block, bit r * 4 + c.  One pixel at a time ON PURPOSE: the rule is 64-bit products, and
+// the eight pixels' worth of them live at once (the unrolled loop the other kinds use) took the kernel from 46-53 to 80-90 VGPRs
+// and from 8 to 5-6 waves per SIMD for every scene, arcs or none (profiles/render_arc.txt).  An arc's box is mostly hole: few
+// threads get here, and those that do pay eight short iterations
+__device__ __forceinline__ unsigned arc_block_bits(const pa_mark& m, int px, int py) {
+    unsigned bits = 0;
+#pragma unroll 1
+    for (int i = 0; i < 8; ++i) bits |= (mark_covers(m, px + (i & 3), py + (i >> 2)) ? 1u : 0u) << i;
+    return bits;
+}
+
 template <bool kVec, int kOut>
 __global__ void __launch_bounds__(256) render_kernel(const RenderArgs a) {
     __shared__ uint4 s_marks[kCullChunk * 2];            // pa_mark = 2 x uint4
@@ -147,6 +158,15 @@ __global__ void __launch_bounds__(256) render_kernel(const RenderArgs a) {
                 const auto apply = [&](auto kind) {
                     pa_mark mk = m;
                     mk.kind = decltype(kind)::value;
+                    if constexpr (decltype(kind)::value == PA_MARK_ARC) {
+                        const unsigned bits = arc_block_bits(mk, px, py);
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+#pragma unroll
+                            for (int c = 0; c < 4; ++c)
+                                if ((bits >> (r * 4 + c)) & 1u) pix[r][c] = mk.bgr;
+                        return;
+                    }
 #pragma unroll
                     for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -160,6 +180,7 @@ __global__ void __launch_bounds__(256) render_kernel(const RenderArgs a) {
                 case PA_MARK_BOX: apply(std::integral_constant<int, PA_MARK_BOX>()); break;
                 case PA_MARK_GLYPH: apply(std::integral_constant<int, PA_MARK_GLYPH>()); break;
                 case PA_MARK_BLEND: apply(std::integral_constant<int, PA_MARK_BLEND>()); break;
+                case PA_MARK_ARC: apply(std::integral_constant<int, PA_MARK_ARC>()); break;
                 default: break;                              // (render_validate lets no other kind through)
                 }
             }

@@ -103,7 +103,7 @@ int render_validate(int n, int h, int w, const pa_mark* marks, const int32_t* fi
     if (total > 0 && !marks) FAIL("pa_render: %d marks announced by first[], marks is NULL", total);
     for (int k = 0; k < total; ++k) {
         const pa_mark& m = marks[k];
-        if (m.kind < PA_MARK_DISC || m.kind > PA_MARK_BLEND) FAIL("pa_render: mark %d has unknown kind %d", k, m.kind);
+        if (m.kind < PA_MARK_DISC || (m.kind > PA_MARK_BLEND && m.kind != PA_MARK_ARC)) FAIL("pa_render: mark %d has unknown kind %d", k, m.kind);
         if (!coord_ok(m.x0) || !coord_ok(m.y0) || !coord_ok(m.x1) || !coord_ok(m.y1))
             FAIL("pa_render: mark %d has a coordinate outside [%d, %d] (%d, %d, %d, %d)", k, kMarkCoordMin, kMarkCoordMax, m.x0, m.y0, m.x1, m.y1);
         // (a fill and a blend have no size: 0..255 are accepted and ignored)
@@ -116,6 +116,10 @@ int render_validate(int n, int h, int w, const pa_mark* marks, const int32_t* fi
             if (m.x1 != 0 || m.y1 != 0) FAIL("pa_render: glyph mark %d has x1, y1 = %d, %d, must be 0", k, m.x1, m.y1);
         } else if (m.kind == PA_MARK_BLEND) {
             if (m.arg < 1 || m.arg > 255) FAIL("pa_render: blend mark %d has weight %d outside [1, 255]", k, m.arg);
+        } else if (m.kind == PA_MARK_ARC) {
+            if (m.x1 < 1 || m.x1 > kArcMaxAxis || m.y1 < 1 || m.y1 > kArcMaxAxis)
+                FAIL("pa_render: arc mark %d has a semi-axis outside [1, %d] (a = x1 = %d, b = y1 = %d)", k, kArcMaxAxis, m.x1, m.y1);
+            if (m.arg < 1 || m.arg > 255) FAIL("pa_render: arc mark %d has octant mask %d outside [1, 255]", k, m.arg);
         } else if (m.arg != 0) FAIL("pa_render: mark %d (kind %d) has arg %d, must be 0", k, m.kind, m.arg);
     }
     if (out == PA_RENDER_BGR) {

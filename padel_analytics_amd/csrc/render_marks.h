@@ -16,6 +16,7 @@ namespace padel {
 
 constexpr int kMarkCoordMin = -8192, kMarkCoordMax = 8191, kRenderMaxSide = 8192;
 constexpr int kGlyphW = 5, kGlyphH = 7, kGlyphMaxScale = 16;
+constexpr int kArcMaxAxis = 4095;           // PA_MARK_ARC: a semi-axis; with |dx| <= 16384 every term of its rule stays below 2^54
 
 struct MarkBox { int x0, y0, x1, y1; };      // inclusive on every side; every covered pixel lies inside
 
@@ -36,6 +37,8 @@ PA_HD MarkBox mark_bbox(const pa_mark& m) {
         return {mark_min(m.x0, m.x1), mark_min(m.y0, m.y1), mark_max(m.x0, m.x1), mark_max(m.y0, m.y1)};
     case PA_MARK_GLYPH:
         return {m.x0, m.y0, m.x0 + kGlyphW * m.size - 1, m.y0 + kGlyphH * m.size - 1};
+    case PA_MARK_ARC:                        // the outer ellipse's box: semi-axes x1, y1 <= 4095, so every edge fits 16 bits
+        return {m.x0 - m.x1, m.y0 - m.y1, m.x0 + m.x1, m.y0 + m.y1};
     default:
         return {0, 0, -1, -1};
     }
@@ -79,6 +82,30 @@ PA_HD bool mark_covers(const pa_mark& m, int x, int y) {
         if (ex < 0 || ey < 0 || ex >= kGlyphW * k || ey >= kGlyphH * k) return false;
         const int bit = (ey / k) * kGlyphW + ex / k;
         return bit < 32 ? ((unsigned)m.x1 >> bit) & 1u : ((unsigned)m.y1 >> (bit - 32)) & 1u;
+    }
+    case PA_MARK_ARC: {
+        // |dx|, |dy| <= 16383 + 1 and a, b <= 4095: a squared offset times a squared semi-axis is below 2^53, a sum of two below 2^54
+        const int dx = x - m.x0, dy = y - m.y0, a = m.x1, b = m.y1, t = m.size;
+        const int ex = dx < 0 ? -dx : dx, ey = dy < 0 ? -dy : dy;
+        const long long A2 = (long long)a * a, B2 = (long long)b * b, full = A2 * B2;
+        const long long X2 = (long long)ex * ex * B2, Y2 = (long long)ey * ey * A2;
+        if (X2 + Y2 > full) return false;                                  // 1. outside the outer ellipse
+        // 3. the octant, in parameter space: (uu, vv) is (u, v) rotated into u > 0, v >= 0 by k quarter turns (v, -u)
+        const int u = dx * b, v = dy * a;                                  // below 2^26
+        int k = 0, uu = 1, vv = 0;                                         // (the centre: octant 0)
+        if (u > 0 && v >= 0) { uu = u; vv = v; }
+        else if (v > 0 && u <= 0) { k = 1; uu = v; vv = -u; }
+        else if (u < 0 && v <= 0) { k = 2; uu = -u; vv = -v; }
+        else if (v < 0 && u >= 0) { k = 3; uu = -v; vv = u; }
+        if (!(((unsigned)m.arg >> (2 * k + (vv >= uu ? 1 : 0))) & 1u)) return false;
+        // 2. the hole rule ...
+        const int ai = a - t, bi = b - t;
+        if (ai < 1 || bi < 1) return true;
+        const long long Ai2 = (long long)ai * ai, Bi2 = (long long)bi * bi;
+        if ((long long)ex * ex * Bi2 + (long long)ey * ey * Ai2 > Ai2 * Bi2) return true;
+        // ... or the rim rule.  The pixel is inside the outer ellipse, so of its four neighbours only the two farther from the centre,
+        // (|dx| + 1, dy) and (dx, |dy| + 1), can be outside it: (|dx| + 1)^2 = dx^2 + 2 |dx| + 1
+        return X2 + (2 * ex + 1) * B2 + Y2 > full || X2 + Y2 + (2 * ey + 1) * A2 > full;
     }
     default:
         return false;

@@ -90,6 +90,7 @@ class pa_yuv_enc(C.Structure):
 MARK_DTYPE = np.dtype([("kind", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("size", "<i4"), ("bgr", "<u4"),
                        ("arg", "<i4")])
 MARK_DISC, MARK_SEGMENT, MARK_FILL, MARK_BOX, MARK_GLYPH, MARK_BLEND = 1, 2, 3, 4, 5, 6
+MARK_ARC = 8                                       # (7 and 9 are no kinds)
 RENDER_BGR, RENDER_YUV420 = 0, 1
 #: ``Engine.render_last_path()``
 RENDER_PATH_VECTOR, RENDER_PATH_BYTE = 1, 2

@@ -1,7 +1,7 @@
 """Marks for the renderer (``Engine.render`` / ``pa_render``, csrc/render.hip) and its numpy twin.
 
 A mark is one record of ``engine.MARK_DTYPE`` — kind, x0, y0, x1, y1, size, bgr, arg — built here by ``disc``, ``segment``,
-``box``, ``fill``, ``blend`` and ``text``; ``pack`` turns one list of marks per frame into the (``marks``, ``first``) pair the engine takes.
+``box``, ``fill``, ``blend``, ``arc`` and ``text``; ``pack`` turns one list of marks per frame into the (``marks``, ``first``) pair the engine takes.
 ``render_host`` applies them with numpy: the CPU path, and the readable statement of the integer coverage rules that
 include/padel_hip.h specifies (``pa_mark``) — marks applied in list order, a later mark overwriting an earlier one, or, for the
 one kind that is not opaque (``blend``), mixing its colour into what the earlier ones left.
@@ -16,6 +16,7 @@ from . import engine as E, video
 
 COORD_MIN, COORD_MAX = -8192, 8191
 GLYPH_W, GLYPH_H, GLYPH_ADVANCE = 5, 7, 6
+ARC_MAX_AXIS = 4095                                  # an arc's semi-axis: 1..4095
 FONT_CHARS = "0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZ :.-"
 
 
@@ -52,6 +53,13 @@ def blend(x0, y0, x1, y1, bgr, weight: int) -> tuple:
 
 def box(x0, y0, x1, y1, t: int, bgr) -> tuple:
     return (E.MARK_BOX, _c(x0), _c(y0), _c(x1), _c(y1), int(t), _bgr(bgr), 0)
+
+
+def arc(x, y, a: int, b: int, t: int, bgr, mask: int = 0xFF) -> tuple:
+    """An axis-parallel elliptical ring cut to octants: centre (x, y), OUTER semi-axes ``a``, ``b`` in 1..4095, thickness ``t`` in
+    1..255 growing inwards, opaque.  Bit k of ``mask`` (1..255) keeps octant k: the parameter angle [45 k, 45 (k + 1)) degrees, 0 at
+    +x, y pointing down (so octants 0..3 are the lower half of the ring on the screen, 0xFF the whole ring)."""
+    return (E.MARK_ARC, _c(x), _c(y), int(a), int(b), int(t), _bgr(bgr), int(mask))
 
 
 def glyph(ch: str, x, y, scale: int, bgr) -> tuple:
@@ -99,6 +107,27 @@ def _glyph_bits(code: int) -> np.ndarray:
     return _FONT_CACHE[code]
 
 
+def _arc_rule(dx, dy, a: int, b: int, t: int, mask: int):
+    """PA_MARK_ARC on int64 offsets from the centre (broadcast against each other), as include/padel_hip.h words it."""
+    def inside(X, Y, A, B):
+        return X * X * (B * B) + Y * Y * (A * A) <= A * A * B * B
+
+    outer = inside(dx, dy, a, b)
+    hole = np.full(outer.shape, True) if (a - t < 1 or b - t < 1) else ~inside(dx, dy, a - t, b - t)
+    rim = ~(inside(dx + 1, dy, a, b) & inside(dx - 1, dy, a, b) & inside(dx, dy + 1, a, b) & inside(dx, dy - 1, a, b))
+    u, v = np.broadcast_arrays(dx * b, dy * a)
+    octant = np.zeros(outer.shape, bool)
+    for k in range(4):                                   # (u, v) after k turns (u, v) -> (v, -u)
+        if mask >> (2 * k) & 1:
+            octant |= (u > 0) & (v >= 0) & (v < u)
+        if mask >> (2 * k + 1) & 1:
+            octant |= (u > 0) & (v >= u)
+        u, v = v, -u
+    if mask & 1:
+        octant |= (u == 0) & (v == 0)                    # the centre pixel counts as octant 0
+    return outer & (hole | rim) & octant
+
+
 def coverage(mark, h: int, w: int) -> tuple:
     """-> (y0, x0, mask): the pixels of an ``h`` x ``w`` frame that ``mark`` covers are ``mask`` (bool) placed at row ``y0``, column
     ``x0``; None when the mark's bounding box misses the frame.  All int64, the rules of include/padel_hip.h as they stand there."""
@@ -112,6 +141,8 @@ def coverage(mark, h: int, w: int) -> tuple:
         bb = (min(x0, x1), min(y0, y1), max(x0, x1), max(y0, y1))
     elif kind == E.MARK_GLYPH:
         bb = (x0, y0, x0 + GLYPH_W * size - 1, y0 + GLYPH_H * size - 1)
+    elif kind == E.MARK_ARC:
+        bb = (x0 - x1, y0 - y1, x0 + x1, y0 + y1)
     else:
         raise ValueError(f"unknown mark kind {kind}")
     ax, ay, bx, by = max(bb[0], 0), max(bb[1], 0), min(bb[2], w - 1), min(bb[3], h - 1)
@@ -134,6 +165,8 @@ def coverage(mark, h: int, w: int) -> tuple:
     elif kind == E.MARK_BOX:
         inner = (x >= bb[0] + size) & (x <= bb[2] - size) & (y >= bb[1] + size) & (y <= bb[3] - size)
         m = ~inner
+    elif kind == E.MARK_ARC:
+        m = _arc_rule(x - x0, y - y0, x1, y1, size, arg)
     else:
         m = _glyph_bits(arg)[(y - y0) // size, (x - x0) // size]
     return ay, ax, np.broadcast_to(m, (by - ay + 1, bx - ax + 1))

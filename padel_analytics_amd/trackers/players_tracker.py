@@ -83,13 +83,27 @@ class Player:
     def feet(self) -> tuple:
         return int(self.top_left[0] + self.width / 2), int(self.bottom_right[1])
 
+    #: the values of ``annotator`` (reference players_tracker.py:104-133, config.py:24)
+    ANNOTATORS = ("rectangle_bounding_box", "round_bounding_box", "corner_bounding_box", "ellipse")
+
     def marks(self, video_info=None, annotator: str = "rectangle_bounding_box", show_confidence: bool = True) -> list:
-        """Reference :100-169 (supervision's BoxAnnotator + LabelAnnotator in Color.BLUE): the box outline in RGB (0, 0, 255),
-        thickness 2 below 1080 lines and 4 from 1080 up, growing inwards, and the label ``f"{id}: {confidence:.2f}"`` (``f"{id}"``
-        without ``show_confidence``) in white on a filled plate of the box's colour, centred above the box's top edge, font
-        scale 2.  The thickness rule is supervision's ``calculate_optimal_line_thickness`` AS RECALLED, the plate's geometry is
-        this project's: parity with supervision is unpinned (it is not installed).  Every ``annotator`` draws the
-        rectangle."""
+        """Reference :100-169 (one of supervision's box annotators + LabelAnnotator in Color.BLUE): the player's outline in RGB
+        (0, 0, 255), thickness 2 below 1080 lines and 4 from 1080 up, growing inwards, and the label ``f"{id}: {confidence:.2f}"``
+        (``f"{id}"`` without ``show_confidence``) in white on a filled plate of the box's colour, centred above the box's top edge,
+        font scale 2 — plate and text are the same for every ``annotator``.  The outline, by ``annotator`` (``outline_marks``):
+
+        * ``rectangle_bounding_box`` (BoxAnnotator, the default): one box mark;
+        * ``round_bounding_box`` (RoundBoxAnnotator, roundness 0.6): corner radius ``r = 3 * (min(w, h) // 2) // 5``, four straight
+          edges between the corners and, for r > 0, four quarter rings of radius r;
+        * ``corner_bounding_box`` (BoxCornerAnnotator, corner length 15): at each corner two bars of length
+          ``min(15, w // 2, h // 2)``;
+        * ``ellipse`` (EllipseAnnotator): one arc under the feet, centred at the middle of the bottom edge, semi-axes ``a = w`` and
+          ``b = 7 * a // 20`` (supervision's 0.35), octants 7, 0, 1, 2, 3, 4: -45 .. 225 degrees, the top quarter open.  DECIDED
+          DEVIATION: supervision's arc ends at 235 degrees; the renderer's arcs are cut at octants.
+
+        ``ValueError`` for any other name.  The thickness rule (``calculate_optimal_line_thickness``) and the annotators' constants
+        are supervision's AS RECALLED, the plate's geometry and the integer coverage rules are this project's: parity with supervision
+        is unpinned (it is not installed)."""
         from .. import render
         x0, y0 = self.top_left
         x1, y1 = self.bottom_right
@@ -98,8 +112,42 @@ class Player:
         label = f"{self.id}: {self.confidence:.2f}" if show_confidence else f"{self.id}"
         tw = render.text_width(label, k)
         tx, ty = (x0 + x1) // 2 - tw // 2, y0 - (render.GLYPH_H + 1) * k
-        return ([render.box(x0, y0, x1, y1, t, blue), render.fill(tx - k, ty - k, tx + tw - 1 + k, y0 - 1, blue)]
+        return (self.outline_marks(annotator, x0, y0, x1, y1, t, blue) + [render.fill(tx - k, ty - k, tx + tw - 1 + k, y0 - 1, blue)]
                 + render.text(label, tx, ty, k, (255, 255, 255)))
+
+    @classmethod
+    def outline_marks(cls, annotator: str, x0: int, y0: int, x1: int, y1: int, t: int, bgr) -> list:
+        """The outline of the box ``(x0, y0)`` .. ``(x1, y1)`` (inclusive corners, x0 <= x1, y0 <= y1) under ``annotator``, thickness
+        ``t``: see ``marks``.  Bars and edges are fill marks clipped to the box, so that a thickness beyond the box's own size stays
+        inside it, as the box mark's does."""
+        from .. import render
+        if annotator == "rectangle_bounding_box":
+            return [render.box(x0, y0, x1, y1, t, bgr)]
+        if annotator not in cls.ANNOTATORS:
+            raise ValueError(f"annotator {annotator!r}: one of {', '.join(cls.ANNOTATORS)}")
+        w, h = x1 - x0, y1 - y0
+
+        def bar(ax, ay, bx, by):                         # a fill, cut to the box
+            return render.fill(max(ax, x0), max(ay, y0), min(bx, x1), min(by, y1), bgr)
+
+        if annotator == "ellipse":
+            a = min(max(w, 1), render.ARC_MAX_AXIS)
+            return [render.arc((x0 + x1) // 2, y1, a, max(1, 7 * a // 20), t, bgr, 0x9F)]
+        if annotator == "corner_bounding_box":
+            n = min(15, w // 2, h // 2)
+            if n < 1:
+                return []
+            return [bar(x0, y0, x0 + n - 1, y0 + t - 1), bar(x0, y0, x0 + t - 1, y0 + n - 1),              # top left: along x, along y
+                    bar(x1 - n + 1, y0, x1, y0 + t - 1), bar(x1 - t + 1, y0, x1, y0 + n - 1),              # top right
+                    bar(x1 - n + 1, y1 - t + 1, x1, y1), bar(x1 - t + 1, y1 - n + 1, x1, y1),              # bottom right
+                    bar(x0, y1 - t + 1, x0 + n - 1, y1), bar(x0, y1 - n + 1, x0 + t - 1, y1)]              # bottom left
+        r = min(3 * (min(w, h) // 2) // 5, render.ARC_MAX_AXIS)
+        edges = [bar(x0 + r, y0, x1 - r, y0 + t - 1), bar(x0 + r, y1 - t + 1, x1 - r, y1),                  # top, bottom
+                 bar(x0, y0 + r, x0 + t - 1, y1 - r), bar(x1 - t + 1, y0 + r, x1, y1 - r)]                  # left, right
+        if r < 1:
+            return edges
+        return edges + [render.arc(x0 + r, y0 + r, r, r, t, bgr, 0x30), render.arc(x1 - r, y0 + r, r, r, t, bgr, 0xC0),
+                        render.arc(x1 - r, y1 - r, r, r, t, bgr, 0x03), render.arc(x0 + r, y1 - r, r, r, t, bgr, 0x0C)]
 
     def projection_marks(self) -> list:
         """Reference :171-192, the player in the court inset: a filled circle of radius 8 in RGB (0, 0, 255) at ``projection`` and

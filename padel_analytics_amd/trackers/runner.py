@@ -47,7 +47,11 @@ Additions (all off by default, the reference's sequential semantics stay the def
   replaced in memory by ``Players`` with the mapped ids (``identity.relabel``).  ``identity_options``: ``every``, ``batch``,
   ``on_device`` for the scan, ``n_players``, ``max_distance`` for the assignment.  ``identity_map`` is the mapping,
   ``identity_distances`` what it was decided by, ``timings["__identities__"]`` the pass.  The thresholds are parameters, not
-  findings.  Not with ``distributed`` or ``fanout``."""
+  findings.  Not with ``distributed`` or ``fanout``.
+
+* ``ball_trail=N`` (the reference's ``draw_multiple_frames``, ``ball_tracker.py:324-347``, which its runner never calls): the render
+  step also draws where the ball was seen in the last N kept frames, the current one included (``trail_marks``); a trail does not
+  reach across a cut of ``segments``.  0, the default, draws none."""
 from __future__ import annotations
 
 import os
@@ -79,7 +83,8 @@ class TrackingRunner:
                  end: Optional[int] = None, collect_data: bool = False, *, distributed: bool = False,
                  fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None, render=None,
                  court_inset: Optional[bool] = None, render_quality: int = 90, segments=None,
-                 segment_options: Optional[dict] = None, identities: bool = False, identity_options: Optional[dict] = None) -> None:
+                 segment_options: Optional[dict] = None, identities: bool = False, identity_options: Optional[dict] = None,
+                 ball_trail: int = 0) -> None:
         self.video_path = video_path
         self.inference_path = inference_path
         self.start = start
@@ -143,6 +148,9 @@ class TrackingRunner:
         self.identity_distances: Optional[dict] = None
         if self.identities and (distributed or fanout):
             raise ValueError("identities=True is not available with distributed=True or fanout=True")
+        self.ball_trail = int(ball_trail)              # kept frames whose ball positions frame_marks draws as a trail (0: none)
+        if self.ball_trail < 0:
+            raise ValueError(f"ball_trail={ball_trail!r}: a number of frames, 0 or more")
 
     def _set_segments(self, segments) -> None:
         """``segments``: ascending, non-overlapping, non-empty (lo, hi) inside [start, start + n_available) — else ``ValueError``
@@ -330,11 +338,35 @@ class TrackingRunner:
             marks += fp.ball.projection_marks()
         return marks
 
+    def _segment_start(self, i: int) -> int:
+        """The first kept position of the segment that kept position ``i`` lies in (0 without segments)."""
+        k = 0
+        for lo, hi in self.segments or ():
+            if i < k + hi - lo:
+                return k
+            k += hi - lo
+        return 0 if self.segments is None else k
+
+    def trail_marks(self, results, i: int) -> list:
+        """The ball's trail at kept position ``i`` (reference ``ball_tracker.py:299-347``, ``draw_multiple_frames`` / ``draw_traj``:
+        a queue of the last positions, an invisible ball taking a place in it, each drawn as a white circle of radius 3 with a
+        yellow outline): the positions of the ``ball_trail`` kept frames i, i - 1, ... that lie in i's segment and hold a visible
+        ball, newest first, each a disc of radius 3 in RGB (255, 255, 0) under one of radius 2 in white."""
+        from .. import render as R
+        marks = []
+        for j in range(min(i, len(results) - 1), max(self._segment_start(i), i - self.ball_trail + 1) - 1, -1):
+            ball = results[j]
+            if ball.visibility:
+                x, y = ball.asint()
+                marks += [R.disc(x, y, 3, (0, 255, 255)), R.disc(x, y, 2, (255, 255, 255))]
+        return marks
+
     def frame_marks(self, i: int) -> list:
         """The marks of frame ``i`` (counted from ``start``; with segments: kept position ``i``, and the label shows the source frame,
         ``source_index[i] - start + 1``): ``FRAME: i + 1`` (reference :118-127, there cv2's Hershey font in RGB
         (255, 255, 0) with its bottom-left at (20, 50); here the renderer's font at scale 3), then every tracker's
-        ``results[i].marks(**tracker.draw_kwargs())`` in tracker order, then — with ``court_inset`` — ``inset_marks(i)``.  The
+        ``results[i].marks(**tracker.draw_kwargs())`` in tracker order (with ``ball_trail`` the ``Ball`` tracker's is followed by
+        ``trail_marks``), then — with ``court_inset`` — ``inset_marks(i)``.  The
         projections behind the inset are computed once, in frame order, from the results stored at that moment and kept until the next
         ``draw_and_collect_data`` or ``restart``, which start over."""
         from .. import render as R
@@ -343,6 +375,8 @@ class TrackingRunner:
         for tracker in self.trackers.values():
             if i < len(tracker.results):
                 marks += tracker.results[i].marks(**tracker.draw_kwargs())
+                if self.ball_trail > 0 and self._object_name(tracker) == "Ball":
+                    marks += self.trail_marks(tracker.results, i)
         if self.court_inset:
             marks += self.inset_marks(i)
         return marks

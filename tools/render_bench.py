@@ -8,10 +8,12 @@
     HBM peak.  The calls rotate over three source / destination sets so that a repetition does not find its bytes in the 256 MB
     last-level cache.  Every call also copies its marks to the device first (on the same stream), which the event pair includes.
     A third scene adds the court inset (``TrackingRunner(collect_data=True)``: the blending panel, the drawn court, the projected
-    players and ball) to the first; a library that refuses the blending mark skips it and says so.
+    players and ball) to the first; a library that refuses the blending mark skips it and says so.  Two more draw the first scene's
+    players with ``annotator="ellipse"`` and with ``"round_bounding_box"`` (arc marks; skipped likewise by a library without them).
 (b) ``TrackingRunner``'s render step on the same clip and marks, end to end — render + download + write of the ``.y4m`` — with a
     host clock; the frames come from a ``DeviceClip``.  Then the same with ``collect_data=True`` — projection, collection and the inset
     on top — once with fixed court keypoints (one homography per clip) and once with keypoints that differ per frame (one per frame).
+    Then the first once more with ``annotator="ellipse"``.
 
     python tools/render_bench.py [--frames 64] [--reps 50] [--warmup 5] [--passes 3] [--skip-runner] [--kernel-only]
 
@@ -146,6 +148,21 @@ if __name__ == "__main__":
     else:
         print(json.dumps({"what": "scene + court inset", "skipped": "this library refuses it: " + refused}))
 
+    # the first scene under the annotators that draw arcs
+    def annotated_runner(name: str):
+        ts = [Stored("players_tracker", [s[0] for s in scenes], {"video_info": info, "annotator": name, "show_confidence": True}, Players)] + trackers[1:]
+        return TrackingRunner(ts, clip, tmp / "out.mp4", render=tmp / "out.y4m", engine=eng)
+    arcs_refused = None
+    for name in ("ellipse", "round_bounding_box"):
+        marks_of = [annotated_runner(name).frame_marks(i) for i in range(n)]
+        packed = R.pack(marks_of)
+        arcs_refused = E.render_check(n, h, w, packed[0], packed[1])
+        if arcs_refused is None:
+            scenes_timed.append((f"scene, annotator={name}", packed))
+            print(json.dumps({"what": f"scene, annotator={name}", "marks_per_frame": len(marks_of[0]), "of_them_arcs": int((packed[0]["kind"] == 8).sum()) // n}))
+        else:
+            print(json.dumps({"what": f"scene, annotator={name}", "skipped": "this library refuses it: " + arcs_refused}))
+
     # ---- (a) the kernel
     SETS = 3
     enc = video.YUV_ENC_COEFFS["bt601_limited"]
@@ -189,6 +206,8 @@ if __name__ == "__main__":
         if refused is None:
             runs += [("the same with collect_data=True, fixed court keypoints", collecting_runner(True)),
                      ("the same with collect_data=True, court keypoints per frame", collecting_runner(False))]
+        if arcs_refused is None:
+            runs.append(("render + download + write of the .y4m, annotator=ellipse", annotated_runner("ellipse")))
         for what, r in runs:
             secs, collect = [], []
             with contextlib.redirect_stdout(sys.stderr):
