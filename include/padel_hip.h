@@ -269,7 +269,24 @@ int pa_render(pa_engine* eng, const uint8_t* src_bgr_dev, int n, int h, int w, c
               int out, const pa_yuv_desc* geom, const pa_yuv_enc* enc, uint8_t* dst_dev);
 int pa_render_check(int n, int h, int w, const pa_mark* marks_host, const int32_t* first_host, int out, const pa_yuv_desc* geom,
                     const pa_yuv_enc* enc, char* why, size_t cap);
-/* which instantiation the last successful pa_render of this engine launched — 1 vector path, 2 byte path, 0 none yet */
+/* pa_render at 1 / scale of the source's size, scale in 1..4: an anti-aliased copy that moves 1 / scale^2 of the bytes.  All integer:
+ *   F' = the h x w source frame with its marks applied exactly as pa_render applies them — at source resolution, in list order;
+ *        mark coordinates stay in SOURCE pixels.
+ *   The output frame is ho x wo = (h / scale) x (w / scale); output pixel (X, Y) is, per channel, with s = scale,
+ *        D = (sum of F'[s Y + j][s X + i] over 0 <= i, j < s  +  s^2 / 2) / s^2            integer division:
+ *        (sum + 2) >> 2,  (sum + 4) / 9,  (sum + 8) >> 4         (csrc/render_scale.h; halves round up)
+ *   out = PA_RENDER_BGR stores D (frame i at dst + i * ho * wo * 3); out = PA_RENDER_YUV420 applies pa_yuv_enc's formulas to D: Y per
+ *   output pixel, U and V from the sums over each 2 x 2 block of D.  geom describes the OUTPUT frames (ho x wo).
+ * scale = 1 is pa_render, byte for byte (in-place rendering included).  Refused, nothing launched: scale outside 1..4, w or h
+ * no multiple of scale, YUV output with odd or too small wo / ho, dst == src with scale > 1, and everything pa_render refuses, its
+ * geometry tests applied to ho x wo.  pa_render_scaled_check gives the same answers on the host alone; dst_is_src != 0 states that
+ * the caller means dst == src.  Stream order, staging and the two store paths (chosen by wo % 4 and this call's addresses) are
+ * pa_render's; one pass over HBM: the source is read once, the average is taken in registers.                                */
+int pa_render_scaled(pa_engine* eng, const uint8_t* src_bgr_dev, int n, int h, int w, const pa_mark* marks_host, const int32_t* first_host,
+                     int scale, int out, const pa_yuv_desc* geom, const pa_yuv_enc* enc, uint8_t* dst_dev);
+int pa_render_scaled_check(int n, int h, int w, const pa_mark* marks_host, const int32_t* first_host, int scale, int out,
+                           const pa_yuv_desc* geom, const pa_yuv_enc* enc, int dst_is_src, char* why, size_t cap);
+/* which instantiation the last successful pa_render / pa_render_scaled of this engine launched — 1 vector path, 2 byte path, 0 none yet */
 int pa_render_last_path(pa_engine* eng);
 /* host only: the 7 rows (top first) of one glyph of the built-in font, column i (0 = leftmost) in bit i of a row; non-zero for a
  * code outside the font                                                                                                   */

@@ -1,15 +1,16 @@
-// pa_render: marks on BGR frames in HBM -> BGR or YUV 4:2:0 (render.hip).  What is refused, and the font, are host-only code in
-// render_check.cpp.
+// pa_render / pa_render_scaled: marks on BGR frames in HBM -> BGR or YUV 4:2:0, at the source's size or at 1/2, 1/3, 1/4 of it
+// (render.hip).  What is refused, and the font, are host-only code in render_check.cpp.
 #include "engine_internal.h"
 #include "render_check.h"
 
-int pa_render(pa_engine* e, const uint8_t* src, int n, int h, int w, const pa_mark* marks, const int32_t* first, int out,
-              const pa_yuv_desc* geom, const pa_yuv_enc* enc, uint8_t* dst) {
+// pa_render (scale 1) and pa_render_scaled: one body, the launch apart
+static int render_run(pa_engine* e, const uint8_t* src, int n, int h, int w, const pa_mark* marks, const int32_t* first, int scale, int out,
+                      const pa_yuv_desc* geom, const pa_yuv_enc* enc, uint8_t* dst) {
     if (!e) return 1;
     if (!src || !dst) PA_FAIL(e, "pa_render: src or dst is NULL");
     size_t span = 0;
     std::string why;
-    if (render_validate(n, h, w, marks, first, out, geom, enc, &span, why)) PA_FAIL(e, "%s", why.c_str());
+    if (render_scaled_validate(n, h, w, marks, first, scale, out, geom, enc, dst == src ? 1 : 0, &span, why)) PA_FAIL(e, "%s", why.c_str());
     const size_t src_bytes = (size_t)n * h * w * 3;
     const bool same = dst == src;
     if (!(same && out == PA_RENDER_BGR) && src < dst + span && dst < src + src_bytes)
@@ -50,7 +51,7 @@ int pa_render(pa_engine* e, const uint8_t* src, int n, int h, int w, const pa_ma
     a.probe = d_probe;
 #endif
     int vec = 0;
-    const hipError_t r = launch_render(a, e->main_stream(), &vec);
+    const hipError_t r = scale == 1 ? launch_render(a, e->main_stream(), &vec) : launch_render_scaled(a, scale, e->main_stream(), &vec);
     if (r != hipSuccess) PA_FAIL(e, "render launch failed: %s", hipGetErrorString(r));
 #ifdef PADEL_RENDER_PROBE
     unsigned long long p[4] = {};
@@ -61,6 +62,16 @@ int pa_render(pa_engine* e, const uint8_t* src, int n, int h, int w, const pa_ma
 #endif
     e->render_last_path = vec ? 1 : 2;
     return 0;
+}
+
+int pa_render(pa_engine* e, const uint8_t* src, int n, int h, int w, const pa_mark* marks, const int32_t* first, int out,
+              const pa_yuv_desc* geom, const pa_yuv_enc* enc, uint8_t* dst) {
+    return render_run(e, src, n, h, w, marks, first, 1, out, geom, enc, dst);
+}
+
+int pa_render_scaled(pa_engine* e, const uint8_t* src, int n, int h, int w, const pa_mark* marks, const int32_t* first, int scale, int out,
+                     const pa_yuv_desc* geom, const pa_yuv_enc* enc, uint8_t* dst) {
+    return render_run(e, src, n, h, w, marks, first, scale, out, geom, enc, dst);
 }
 
 int pa_render_last_path(pa_engine* e) { return e ? e->render_last_path : 0; }

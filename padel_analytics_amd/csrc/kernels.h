@@ -273,6 +273,10 @@ struct RenderArgs {
 };
 bool render_vector_path_ok(const RenderArgs& a);        // every address of this launch allows dword / 16-bit accesses
 hipError_t launch_render(const RenderArgs& a, hipStream_t s, int* vec_out = nullptr);          // *vec_out: 1 vector path, 0 byte path
+// the same pass followed by a scale x scale box average (scale 2..4 dividing a.w and a.h): a.h x a.w is the source, the geometry
+// fields describe the (a.h / scale) x (a.w / scale) output, in_place is 0
+bool render_scaled_vector_path_ok(const RenderArgs& a, int scale);
+hipError_t launch_render_scaled(const RenderArgs& a, int scale, hipStream_t s, int* vec_out = nullptr);
 
 // Pillow-style separable resample pass over u8 images (coefficients precomputed on host):
 // out[b][y][x][c] = clip8((sum_k coef[o][k] * in[...lo[o]+k...] + (1<<21)) >> 22)

@@ -15,6 +15,7 @@
 
 #include "kernels.h"
 #include "render_marks.h"
+#include "render_scale.h"
 
 namespace padel {
 
@@ -267,6 +268,208 @@ __global__ void __launch_bounds__(256) render_kernel(const RenderArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------- pa_render_scaled, s = 2, 3, 4
+// The same pass with an s x s box average behind the marks (include/padel_hip.h): a.h x a.w is the SOURCE, the output is
+// (a.h / S) x (a.w / S) and the geometry fields describe it.  One thread owns ONE output pixel — its S x S source pixels stay in
+// registers across the chunks of marks — a workgroup of 32 x 8 threads a tile of 32 S x 8 S source pixels.  A wave is two rows of 32
+// threads, so the 2 x 2 block of output pixels that shares a chroma sample is lanes l, l ^ 1, l ^ 32, l ^ 33 of one wave: chroma,
+// and the packing of four neighbours' bytes into a dword, are cross-lane moves, no LDS.
+// The cull, the list and the per-mark switch are render_kernel's, restated for an R x C block of any size: sharing one copy with
+// render_kernel was tried and took its six instantiations from 47-53 to 59-63 VGPRs (profiles/render_scale.txt), and their
+// register count is pinned (profiles/render_arc.txt).
+template <int R, int C>
+__device__ __forceinline__ unsigned arc_bits_rc(const pa_mark& m, int px, int py) {      // arc_block_bits for an R x C block, R * C <= 32
+    unsigned bits = 0;
+#pragma unroll 1
+    for (int i = 0; i < R * C; ++i) bits |= (mark_covers(m, px + i % C, py + i / C) ? 1u : 0u) << i;
+    return bits;
+}
+
+// the first `total` marks of the LDS list applied, in list order, to a thread's R x C block of pixel registers at (px, py)
+template <int R, int C>
+__device__ __forceinline__ void apply_list(const uint4* s_marks, const uint2* s_boxes, int total, int px, int py, unsigned (&pix)[R][C]) {
+    for (int k = 0; k < total; ++k) {
+        if (!mark_box_meets(unpack_box(s_boxes[k]), px, py, px + C - 1, py + R - 1)) continue;
+        const uint4 l = s_marks[k * 2], u = s_marks[k * 2 + 1];
+        pa_mark m;
+        m.kind = (int)l.x; m.x0 = (int)l.y; m.y0 = (int)l.z; m.x1 = (int)l.w; m.y1 = (int)u.x; m.size = (int)u.y; m.bgr = u.z; m.arg = (int)u.w;
+        const auto apply = [&](auto kind) {              // (one scalar switch per mark, the kind a constant inside an arm: render_kernel)
+            pa_mark mk = m;
+            mk.kind = decltype(kind)::value;
+            if constexpr (decltype(kind)::value == PA_MARK_ARC) {
+                const unsigned bits = arc_bits_rc<R, C>(mk, px, py);
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+#pragma unroll
+                    for (int c = 0; c < C; ++c)
+                        if ((bits >> (r * C + c)) & 1u) pix[r][c] = mk.bgr;
+                return;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+                    if (mark_covers(mk, px + c, py + r)) pix[r][c] = mark_apply(mk, pix[r][c]);
+        };
+        switch (m.kind) {
+        case PA_MARK_DISC: apply(std::integral_constant<int, PA_MARK_DISC>()); break;
+        case PA_MARK_SEGMENT: apply(std::integral_constant<int, PA_MARK_SEGMENT>()); break;
+        case PA_MARK_FILL: apply(std::integral_constant<int, PA_MARK_FILL>()); break;
+        case PA_MARK_BOX: apply(std::integral_constant<int, PA_MARK_BOX>()); break;
+        case PA_MARK_GLYPH: apply(std::integral_constant<int, PA_MARK_GLYPH>()); break;
+        case PA_MARK_BLEND: apply(std::integral_constant<int, PA_MARK_BLEND>()); break;
+        case PA_MARK_ARC: apply(std::integral_constant<int, PA_MARK_ARC>()); break;
+        default: break;
+        }
+    }
+}
+
+template <int S, bool kVec, int kOut>
+__global__ void __launch_bounds__(256) render_scaled_kernel(const RenderArgs a) {
+    __shared__ uint4 s_marks[kCullChunk * 2];
+    __shared__ uint2 s_boxes[kCullChunk];
+    __shared__ int s_count[4];
+    const int tid = threadIdx.y * 32 + threadIdx.x;      // lane = (threadIdx.y & 1) * 32 + threadIdx.x
+    const int wo = a.w / S, ho = a.h / S;                // (a.w, a.h are multiples of S)
+    const int X = blockIdx.x * 32 + threadIdx.x, Y = blockIdx.y * 8 + threadIdx.y;          // this thread's output pixel
+    const int tx0 = blockIdx.x * (32 * S), ty0 = blockIdx.y * (8 * S);
+    const int px = X * S, py = Y * S;
+    const int frame = blockIdx.z;
+    const bool valid = X < wo && Y < ho;
+    const size_t row_bytes = (size_t)a.w * 3;
+
+    const pa_mark* marks = reinterpret_cast<const pa_mark*>(a.marks);
+    const uint2* boxes = reinterpret_cast<const uint2*>(a.boxes);
+    const int m_begin = a.first[frame], m_end = a.first[frame + 1];
+    const int lane = tid & 63, wave = tid >> 6;
+    uint2 bx = {0, 0};
+    if (m_begin + tid < m_end) bx = boxes[m_begin + tid];               // (asked for before the pixels: render_kernel)
+
+    // kVec: the 3 S bytes of a row of the block sit `sh` bytes into kDw aligned dwords (rows start on a dword: a.w % 4 == 0).  Every
+    // one of those dwords holds at least one byte of the block, and the frames end on a dword, so none reaches past the source
+    constexpr int kDw = S == 2 ? 2 : 3;
+    unsigned pix[S][S];                                  // B | G << 8 | R << 16
+    unsigned raw[S][kDw];
+    const int xoff = min(X, wo - 1) * (3 * S);           // (a thread outside the frame reads the last block / row instead and never stores)
+    const unsigned sh = (unsigned)xoff & 3u;
+#pragma unroll
+    for (int r = 0; r < S; ++r) {
+#pragma unroll
+        for (int c = 0; c < S; ++c) pix[r][c] = 0;
+        if (kVec) {
+            const uint8_t* q = a.src + ((size_t)frame * a.h + min(py + r, a.h - 1)) * row_bytes + (size_t)(xoff & ~3);
+            const unsigned* qd = reinterpret_cast<const unsigned*>(q);
+#pragma unroll
+            for (int i = 0; i < kDw; ++i) raw[r][i] = qd[i];
+        } else {
+#pragma unroll
+            for (int i = 0; i < kDw; ++i) raw[r][i] = 0;
+            if (!valid) continue;
+            const uint8_t* q = a.src + ((size_t)frame * a.h + py + r) * row_bytes + (size_t)px * 3;
+#pragma unroll
+            for (int c = 0; c < S; ++c) pix[r][c] = (unsigned)q[3 * c] | ((unsigned)q[3 * c + 1] << 8) | ((unsigned)q[3 * c + 2] << 16);
+        }
+    }
+
+    const auto cull = [&](int base, uint2 box) -> int {  // render_kernel's, the tile being 32 S x 8 S
+        const int mi = base + tid;
+        const bool keep = mi < m_end && mark_box_meets(unpack_box(box), tx0, ty0, tx0 + 32 * S - 1, ty0 + 8 * S - 1);
+        const unsigned long long vote = __ballot(keep);
+        if (lane == 0) s_count[wave] = __popcll(vote);
+        __syncthreads();
+        const int c0 = s_count[0], c1 = s_count[1], c2 = s_count[2], c3 = s_count[3];
+        if (keep) {
+            const int before = (wave > 0 ? c0 : 0) + (wave > 1 ? c1 : 0) + (wave > 2 ? c2 : 0) + __popcll(vote & ((1ull << lane) - 1ull));
+            const uint4* g = reinterpret_cast<const uint4*>(marks + mi);
+            s_marks[before * 2] = g[0];
+            s_marks[before * 2 + 1] = g[1];
+            s_boxes[before] = box;
+        }
+        __syncthreads();
+        return c0 + c1 + c2 + c3;
+    };
+
+    int base = m_begin, total = 0;
+    if (base < m_end) total = cull(base, bx);
+    if (kVec) {
+#pragma unroll
+        for (int r = 0; r < S; ++r) {
+            unsigned al[kDw];                            // the row's bytes from the block's first one on
+#pragma unroll
+            for (int i = 0; i < kDw; ++i) al[i] = __builtin_amdgcn_alignbyte(i + 1 < kDw ? raw[r][i + 1] : 0u, raw[r][i], sh);
+#pragma unroll
+            for (int c = 0; c < S; ++c) {
+                const int wd = (3 * c) / 4, k = (3 * c) % 4;
+                unsigned v = al[wd] >> (8 * k);
+                if (k >= 2) v |= (wd + 1 < kDw ? al[wd + 1] : 0u) << (32 - 8 * k);
+                pix[r][c] = v & 0xffffffu;
+            }
+        }
+    }
+    while (base < m_end) {
+        if (valid) apply_list<S, S>(s_marks, s_boxes, total, px, py, pix);
+        __syncthreads();                                 // everyone is done with the list and the counts before the next chunk rewrites them
+        base += kCullChunk;
+        if (base < m_end) {
+            bx = uint2{0, 0};
+            if (base + tid < m_end) bx = boxes[base + tid];
+            total = cull(base, bx);
+        }
+    }
+
+    // ---- the average: B and R summed side by side in 16-bit fields (16 x 255 < 2^16), G in its own word
+    unsigned rb = 0, gs = 0;
+#pragma unroll
+    for (int r = 0; r < S; ++r)
+#pragma unroll
+        for (int c = 0; c < S; ++c) { rb += pix[r][c] & 0xff00ffu; gs += pix[r][c] & 0xff00u; }
+    const unsigned D = scale_round<S>(rb & 0xffffu) | (scale_round<S>(gs >> 8) << 8) | (scale_round<S>(rb >> 16) << 16);
+
+    // ---- the stores.  No thread has left: every lane takes part in the cross-lane moves, `valid` guards the stores alone.  kVec: wo
+    // % 4 == 0, so the four threads of a quad (q = 0..3, X - q a multiple of 4) are all inside the frame or all outside
+    const int q = threadIdx.x & 3;
+    if (kOut == OUT_BGR) {
+        uint8_t* dp = a.dst + (((size_t)frame * ho + Y) * wo + X) * 3;
+        if (kVec) {
+            const unsigned nxt = __shfl_down(D, 1);      // the quad's 12 bytes as three dwords, one from each of its first three threads
+            if (valid && q < 3) *reinterpret_cast<unsigned*>(dp + q) = (D >> (8 * q)) | (nxt << (24 - 8 * q));
+        } else if (valid) {
+            dp[0] = (uint8_t)D; dp[1] = (uint8_t)(D >> 8); dp[2] = (uint8_t)(D >> 16);
+        }
+    } else {                                             // wo, ho even: the three other pixels of a valid pixel's 2 x 2 block are valid
+        uint8_t* f = a.dst + (size_t)frame * (size_t)a.frame_stride;
+        uint8_t* yp = f + (size_t)Y * a.pitch_y + X;
+        const size_t crow = (size_t)(Y >> 1) * a.pitch_c;
+        const unsigned y = enc_luma(a, D);
+        const unsigned uv = enc_chroma(a, D, __shfl_xor(D, 1), __shfl_xor(D, 32), __shfl_xor(D, 33));
+        const bool chroma = valid && !(threadIdx.x & 1) && !(threadIdx.y & 1);               // the block's top-left thread stores it
+        if (kVec) {
+            const unsigned y4 = y | (__shfl_down(y, 1) << 8) | (__shfl_down(y, 2) << 16) | (__shfl_down(y, 3) << 24);
+            const unsigned uv1 = __shfl_down(uv, 2);     // the next block's
+            if (valid && q == 0) *reinterpret_cast<unsigned*>(yp) = y4;
+            if (chroma && q == 0) {
+                if (kOut == OUT_NV12) {
+                    *reinterpret_cast<unsigned*>(f + a.off_u + crow + X) = uv | (uv1 << 16);  // U0 V0 U1 V1
+                } else {
+                    *reinterpret_cast<unsigned short*>(f + a.off_u + crow + (X >> 1)) = (unsigned short)((uv & 0xff) | ((uv1 & 0xff) << 8));
+                    *reinterpret_cast<unsigned short*>(f + a.off_v + crow + (X >> 1)) = (unsigned short)((uv >> 8) | (uv1 & 0xff00));
+                }
+            }
+        } else {
+            if (valid) *yp = (uint8_t)y;
+            if (chroma) {
+                if (kOut == OUT_NV12) {
+                    uint8_t* pc = f + a.off_u + crow + X;
+                    pc[0] = (uint8_t)uv; pc[1] = (uint8_t)(uv >> 8);
+                } else {
+                    f[a.off_u + crow + (X >> 1)] = (uint8_t)uv;
+                    f[a.off_v + crow + (X >> 1)] = (uint8_t)(uv >> 8);
+                }
+            }
+        }
+    }
+}
+
 bool render_vector_path_ok(const RenderArgs& a) {
     const uintptr_t s = reinterpret_cast<uintptr_t>(a.src), d = reinterpret_cast<uintptr_t>(a.dst);
     if (a.w % 4 || s % 4 || d % 4) return false;         // (rows and frames of packed BGR are then multiples of 4 bytes)
@@ -289,6 +492,40 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t s, int* vec_out) {
     const dim3 grid((unsigned)((a.w + 127) / 128), (unsigned)((a.h + 15) / 16), (unsigned)a.n), block(32, 8);
     if (vec) launch_render_out<true>(a, grid, block, s);
     else launch_render_out<false>(a, grid, block, s);
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess && vec_out) *vec_out = vec ? 1 : 0;
+    return e;
+}
+
+// the scaled pass stores what render_kernel stores, at the OUTPUT's width: the same rule with a.w / scale in the place of a.w (the
+// source rows are then multiples of 4 bytes too)
+bool render_scaled_vector_path_ok(const RenderArgs& a, int scale) {
+    RenderArgs o = a;
+    o.w = a.w / scale;
+    o.h = a.h / scale;
+    return render_vector_path_ok(o);
+}
+
+template <int S, bool kVec>
+static void launch_render_scaled_out(const RenderArgs& a, dim3 grid, dim3 block, hipStream_t s) {
+    if (a.out == OUT_BGR) hipLaunchKernelGGL((render_scaled_kernel<S, kVec, OUT_BGR>), grid, block, 0, s, a);
+    else if (a.out == OUT_NV12) hipLaunchKernelGGL((render_scaled_kernel<S, kVec, OUT_NV12>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((render_scaled_kernel<S, kVec, OUT_I420>), grid, block, 0, s, a);
+}
+
+template <int S>
+static void launch_render_scaled_vec(const RenderArgs& a, bool vec, dim3 grid, dim3 block, hipStream_t s) {
+    if (vec) launch_render_scaled_out<S, true>(a, grid, block, s);
+    else launch_render_scaled_out<S, false>(a, grid, block, s);
+}
+
+hipError_t launch_render_scaled(const RenderArgs& a, int scale, hipStream_t s, int* vec_out) {
+    if (scale < 2 || scale > kRenderMaxScale || a.w % scale || a.h % scale) return hipErrorInvalidValue;      // (pa_render_scaled has refused these)
+    const bool vec = render_scaled_vector_path_ok(a, scale);
+    const dim3 grid((unsigned)((a.w / scale + 31) / 32), (unsigned)((a.h / scale + 7) / 8), (unsigned)a.n), block(32, 8);
+    if (scale == 2) launch_render_scaled_vec<2>(a, vec, grid, block, s);
+    else if (scale == 3) launch_render_scaled_vec<3>(a, vec, grid, block, s);
+    else launch_render_scaled_vec<4>(a, vec, grid, block, s);
     const hipError_t e = hipGetLastError();
     if (e == hipSuccess && vec_out) *vec_out = vec ? 1 : 0;
     return e;

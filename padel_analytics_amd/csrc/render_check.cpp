@@ -2,6 +2,7 @@
 // g++ like graph_plan.cpp, so that the same refusals and the same glyphs are available without a GPU (pa_render_check,
 // pa_glyph_rows, tests/render_marks_main.cpp).
 #include "render_check.h"
+#include "render_scale.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -158,7 +159,32 @@ int render_validate(int n, int h, int w, const pa_mark* marks, const int32_t* fi
     return 0;
 }
 
+// ------------------------------------------------------------------------------- the refusals of pa_render_scaled
+int render_scaled_validate(int n, int h, int w, const pa_mark* marks, const int32_t* first, int scale, int out, const pa_yuv_desc* g,
+                           const pa_yuv_enc* enc, int dst_is_src, size_t* dst_span, std::string& err) {
+    if (scale == 1) return render_validate(n, h, w, marks, first, out, g, enc, dst_span, err);       // pa_render itself
+    if (scale < 1 || scale > kRenderMaxScale) FAIL("pa_render_scaled: scale %d outside [1, %d]", scale, kRenderMaxScale);
+    if (w < 1 || h < 1 || w > kRenderMaxSide || h > kRenderMaxSide)
+        FAIL("pa_render_scaled: %d x %d source frames: width and height must lie in [1, %d]", w, h, kRenderMaxSide);
+    if (w % scale || h % scale) FAIL("pa_render_scaled: %d x %d source frames are no multiple of scale %d each way", w, h, scale);
+    const int wo = w / scale, ho = h / scale;
+    if (out == PA_RENDER_YUV420 && (wo < 2 || ho < 2 || (wo & 1) || (ho & 1)))
+        FAIL("pa_render_scaled: %d x %d source frames at scale %d give %d x %d: 4:2:0 needs an even output width and height of at least 2",
+             w, h, scale, wo, ho);
+    if (dst_is_src) FAIL("pa_render_scaled: dst == src at scale %d (only scale 1 renders in place)", scale);
+    return render_validate(n, ho, wo, marks, first, out, g, enc, dst_span, err);                     // marks, first[], the output's geometry
+}
+
 }  // namespace padel
+
+extern "C" int pa_render_scaled_check(int n, int h, int w, const pa_mark* marks, const int32_t* first, int scale, int out, const pa_yuv_desc* geom,
+                                      const pa_yuv_enc* enc, int dst_is_src, char* why, size_t cap) {
+    std::string err;
+    size_t span = 0;
+    const int rc = padel::render_scaled_validate(n, h, w, marks, first, scale, out, geom, enc, dst_is_src, &span, err);
+    if (why && cap) snprintf(why, cap, "%s", rc ? err.c_str() : "");
+    return rc;
+}
 
 extern "C" int pa_glyph_rows(int code, uint8_t rows[7]) {
     if (!rows) return 1;

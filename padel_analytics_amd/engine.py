@@ -126,6 +126,7 @@ ABI_SYMBOLS = [
     "pa_model_lanes_allocated", "pa_model_last_lane", "pa_model_last_stem_path", "pa_yolo_resample_passes", "pa_device_bytes_live",
     "pa_frame_activity", "pa_frame_activity_check", "pa_frames_median",
     "pa_box_histograms", "pa_box_histograms_check",
+    "pa_render_scaled", "pa_render_scaled_check",
 ]
 
 
@@ -222,6 +223,9 @@ def load_library():
     lib.pa_render.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, C.POINTER(pa_yuv_desc), C.POINTER(pa_yuv_enc), vp]
     lib.pa_render_check.argtypes = [i32, i32, i32, vp, vp, i32, C.POINTER(pa_yuv_desc), C.POINTER(pa_yuv_enc), C.c_char_p, sz]
     lib.pa_render_last_path.argtypes = [vp]
+    if hasattr(lib, "pa_render_scaled"):           # (an older build under PADEL_LIB, for an A/B run of what it does have: asking it for a scale raises)
+        lib.pa_render_scaled.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, C.POINTER(pa_yuv_desc), C.POINTER(pa_yuv_enc), vp]
+        lib.pa_render_scaled_check.argtypes = [i32, i32, i32, vp, vp, i32, i32, C.POINTER(pa_yuv_desc), C.POINTER(pa_yuv_enc), i32, C.c_char_p, sz]
     lib.pa_glyph_rows.argtypes = [i32, vp]
     lib.pa_jpeg_encode.argtypes = [vp, vp, i32, i32, i32, C.POINTER(pa_yuv_desc), i32, vp, sz, vp]
     lib.pa_jpeg_check.argtypes = [i32, i32, i32, C.POINTER(pa_yuv_desc), i32, C.c_char_p, sz]
@@ -309,16 +313,23 @@ def _render_args(marks, first, geom, enc):
     return marks, first, geom, enc
 
 
-def render_check(n: int, h: int, w: int, marks, first, out: int = RENDER_BGR, geom=None, enc=None) -> Optional[str]:
-    """None if ``pa_render`` would accept the call, else its reason for refusing it (``pa_render_check``: host code, no GPU)."""
+def render_check(n: int, h: int, w: int, marks, first, out: int = RENDER_BGR, geom=None, enc=None, scale: int = 1,
+                 in_place: bool = False) -> Optional[str]:
+    """None if ``pa_render`` — with ``scale`` other than 1: ``pa_render_scaled``, ``h`` x ``w`` being the source and ``geom`` the
+    ``h // scale`` x ``w // scale`` output — would accept the call, else its reason for refusing it (``pa_render_check`` /
+    ``pa_render_scaled_check``: host code, no GPU).  ``in_place``: the caller means ``dst`` to be ``src``."""
     marks, first, geom, enc = _render_args(marks, first, geom, enc)
     if first.size != max(int(n), 0) + 1:
         return f"pa_render: first has {first.size} entries, n + 1 = {int(n) + 1} are needed"
     if marks.size < int(first[-1]):
         return f"pa_render: first[] announces {int(first[-1])} marks, marks holds {marks.size}"
     why = C.create_string_buffer(512)
-    rc = load_library().pa_render_check(int(n), int(h), int(w), marks.ctypes.data if marks.size else None, first.ctypes.data, int(out),
-                                        C.byref(geom) if geom is not None else None, C.byref(enc) if enc is not None else None, why, 512)
+    tail = (C.byref(geom) if geom is not None else None, C.byref(enc) if enc is not None else None)
+    head = (int(n), int(h), int(w), marks.ctypes.data if marks.size else None, first.ctypes.data)
+    if int(scale) == 1:
+        rc = load_library().pa_render_check(*head, int(out), *tail, why, 512)
+    else:
+        rc = load_library().pa_render_scaled_check(*head, int(scale), int(out), *tail, 1 if in_place else 0, why, 512)
     return why.value.decode() if rc else None
 
 
@@ -532,30 +543,39 @@ class Engine:
         return int(self.lib.pa_yuv_last_path(self.handle))
 
     def render(self, src: DeviceBuffer, n: int, h: int, w: int, marks, first, dst: DeviceBuffer, out: int = RENDER_BGR, geom=None,
-               enc=None) -> None:
+               enc=None, scale: int = 1) -> None:
         """Draw ``marks`` on ``n`` packed BGR frames of ``h`` x ``w`` in ``src`` and write them to ``dst`` as packed BGR or, with
         ``out=RENDER_YUV420``, as 8-bit YUV 4:2:0 laid out by ``geom`` (a ``pa_yuv_desc`` or a dict of its fields: ``video.yuv_desc``)
         with the encode table ``enc`` (``pa_yuv_enc`` or its ten integers: ``video.YUV_ENC_COEFFS``) — ``pa_render``.  ``marks``: an
         array of ``MARK_DTYPE`` records, frame i owning ``marks[first[i]:first[i + 1]]`` (``render.pack`` builds both).  ``dst`` may be
         ``src`` itself for BGR output (in place).  Asynchronous: ordered with every later call of this engine by its one compute
         stream; the mark arrays are consumed before the call returns.  What the kernel cannot run is an ``EngineError``, nothing is
-        launched."""
+        launched.
+        ``scale`` 2, 3 or 4 (``pa_render_scaled``): the frames come out at ``h // scale`` x ``w // scale``, every output pixel the
+        rounded mean of the ``scale`` x ``scale`` rendered source pixels under it; the marks stay in source pixels, ``geom`` and
+        ``dst`` are the output's, ``h`` and ``w`` must be multiples of ``scale``, and ``dst`` may not be ``src``."""
         marks, first, geom, enc = _render_args(marks, first, geom, enc)
+        scale = int(scale)
         if first.size != max(int(n), 0) + 1:
             raise EngineError(f"render: first has {first.size} entries, n + 1 = {int(n) + 1} are needed")
         if marks.size < int(first[-1]):
             raise EngineError(f"render: first[] announces {int(first[-1])} marks, marks holds {marks.size}")
         if n >= 1 and h >= 1 and w >= 1 and src.nbytes < n * h * w * 3:
             raise EngineError(f"render: src holds {src.nbytes} bytes, {n} BGR frames need {n * h * w * 3}")
+        # (a scale the library refuses has no output size: it says why)
+        ho, wo = (h // scale, w // scale) if 1 <= scale <= 4 and h % scale == 0 and w % scale == 0 else (0, 0)
         if out == RENDER_YUV420 and geom is not None:
-            need = yuv_span_bytes(n, h, w, geom)
+            need = yuv_span_bytes(n, ho, wo, geom)
         else:
-            need = n * h * w * 3 if (n >= 1 and h >= 1 and w >= 1) else None
+            need = n * ho * wo * 3 if (n >= 1 and ho >= 1 and wo >= 1) else None
         if need is not None and dst.nbytes < need:     # (geometry that has no span is refused by the library, with its reason)
             raise EngineError(f"render: {n} frames as described span {need} bytes, dst holds {dst.nbytes}")
-        self._check(self.lib.pa_render(self.handle, src.ptr, int(n), int(h), int(w), marks.ctypes.data if marks.size else None,
-                                       first.ctypes.data, int(out), C.byref(geom) if geom is not None else None,
-                                       C.byref(enc) if enc is not None else None, dst.ptr))
+        tail = (C.byref(geom) if geom is not None else None, C.byref(enc) if enc is not None else None, dst.ptr)
+        head = (self.handle, src.ptr, int(n), int(h), int(w), marks.ctypes.data if marks.size else None, first.ctypes.data)
+        if scale == 1:
+            self._check(self.lib.pa_render(*head, int(out), *tail))
+        else:
+            self._check(self.lib.pa_render_scaled(*head, scale, int(out), *tail))
 
     def render_last_path(self) -> int:
         """RENDER_PATH_VECTOR / RENDER_PATH_BYTE: what the last successful ``render`` launched (0: none yet)."""

@@ -4,7 +4,8 @@ A mark is one record of ``engine.MARK_DTYPE`` — kind, x0, y0, x1, y1, size, bg
 ``box``, ``fill``, ``blend``, ``arc`` and ``text``; ``pack`` turns one list of marks per frame into the (``marks``, ``first``) pair the engine takes.
 ``render_host`` applies them with numpy: the CPU path, and the readable statement of the integer coverage rules that
 include/padel_hip.h specifies (``pa_mark``) — marks applied in list order, a later mark overwriting an earlier one, or, for the
-one kind that is not opaque (``blend``), mixing its colour into what the earlier ones left.
+one kind that is not opaque (``blend``), mixing its colour into what the earlier ones left.  ``render_host(scale=2 | 3 | 4)`` and
+``downscale_host`` state the scaled pass (``pa_render_scaled``): drawn at full size, then the rounded mean of every s x s block.
 Parity with cv2 / supervision drawing is not pinned (neither is installed); these rules are the specification."""
 from __future__ import annotations
 
@@ -191,22 +192,46 @@ def draw_host(frame: np.ndarray, marks) -> np.ndarray:
     return frame
 
 
-def render_host(frames: np.ndarray, marks, first, out: int = E.RENDER_BGR, geom=None, enc=None, dst: Optional[np.ndarray] = None) -> np.ndarray:
+RENDER_SCALES = (1, 2, 3, 4)                          # what ``scale=`` may be (``pa_render_scaled``)
+
+
+def downscale_host(frames: np.ndarray, s: int) -> np.ndarray:
+    """(n, h, w, 3) uint8 -> (n, h // s, w // s, 3): every output channel the rounded mean of its ``s`` x ``s`` block,
+    ``(sum + s * s // 2) // (s * s)`` in integers (include/padel_hip.h, ``pa_render_scaled``; halves round up).  ``ValueError`` for an
+    ``s`` outside 1..4 or a size that is no multiple of it."""
+    frames = np.asarray(frames)
+    if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype != np.uint8:
+        raise ValueError("downscale_host: frames must be (n, h, w, 3) uint8")
+    s = int(s)
+    n, h, w = frames.shape[:3]
+    if s not in RENDER_SCALES:
+        raise ValueError(f"downscale_host: scale {s} outside [1, 4]")
+    if h % s or w % s:
+        raise ValueError(f"downscale_host: {w} x {h} frames are no multiple of scale {s} each way")
+    sums = frames.reshape(n, h // s, s, w // s, s, 3).astype(np.int64).sum(axis=(2, 4))
+    return ((sums + (s * s) // 2) // (s * s)).astype(np.uint8)
+
+
+def render_host(frames: np.ndarray, marks, first, out: int = E.RENDER_BGR, geom=None, enc=None, dst: Optional[np.ndarray] = None,
+                scale: int = 1) -> np.ndarray:
     """The numpy twin of ``Engine.render``: ``frames`` (n, h, w, 3) uint8 BGR with frame i's ``marks[first[i]:first[i + 1]]`` drawn on
     it -> a new (n, h, w, 3) array (``out=RENDER_BGR``) or the 1-D byte array of the frames as YUV 4:2:0 laid out by ``geom`` and
-    encoded with ``enc`` (``out=RENDER_YUV420``; bytes between planes and rows stay as ``dst`` has them).  ``ValueError`` for what the
-    engine refuses (``pa_render_check``)."""
+    encoded with ``enc`` (``out=RENDER_YUV420``; bytes between planes and rows stay as ``dst`` has them).  ``scale`` 2, 3, 4: drawn at
+    full size, then ``downscale_host``, then encoded — ``geom`` describes the ``h // scale`` x ``w // scale`` output.  ``ValueError``
+    for what the engine refuses (``pa_render_check`` / ``pa_render_scaled_check``)."""
     frames = np.asarray(frames)
     if frames.ndim != 4 or frames.shape[3] != 3 or frames.dtype != np.uint8:
         raise ValueError("render_host: frames must be (n, h, w, 3) uint8")
     n, h, w = frames.shape[:3]
-    why = E.render_check(n, h, w, marks, first, out, geom, enc)
+    why = E.render_check(n, h, w, marks, first, out, geom, enc, scale=scale)
     if why is not None:
         raise ValueError(why)
     marks = np.ascontiguousarray(marks, E.MARK_DTYPE).reshape(-1)
     drawn = frames.copy()
     for i in range(n):
         draw_host(drawn[i], marks[int(first[i]):int(first[i + 1])])
+    if int(scale) != 1:
+        drawn = downscale_host(drawn, scale)
     if out == E.RENDER_BGR:
         return drawn
     enc = tuple(int(getattr(enc, f)) for f, _ in E.pa_yuv_enc._fields_) if isinstance(enc, E.pa_yuv_enc) else tuple(int(c) for c in enc)

@@ -21,6 +21,10 @@ Additions (all off by default, the reference's sequential semantics stay the def
   — ``video.MjpegSink``; any other path: ``.y4m``): ``draw_and_collect_data`` (reference :91-173) reads the clip again and writes it
   with every tracker's results drawn on it — on the GPU (csrc/render.hip: marks applied to the BGR frames in HBM and converted to
   YUV 4:2:0 in one pass), one download and one write per batch.  Without it (the default) the step prints that it is skipped;
+  ``render_scale=`` 2, 3 or 4 writes the clip at 1 / render_scale of the source's size, every pixel the rounded mean of the rendered
+  source pixels under it, in that same pass (``pa_render_scaled``): an anti-aliased copy of 1 / render_scale² the bytes — and the way
+  to an ``.avi`` of a clip wider than the JPEG encoder's 2560.  Marks, the inset and the collected data stay in source pixels.  A
+  scale the clip's size does not allow, or a ``FrameSink`` of another size than the rendered frames, is a ``ValueError`` in ``__init__``;
 * ``collect_data=True`` (the reference's own switch, :74-79): the step also projects every frame's players and ball into the 2-D
   court (``projected_court.ProjectedCourt.project_batch``: the reference's homography state machine :633-647, the frames of a batch
   that need a homography solved together) and fills ``self.data_analytics`` (``analytics.DataAnalytics``) with the players' positions
@@ -84,7 +88,10 @@ class TrackingRunner:
                  fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None, render=None,
                  court_inset: Optional[bool] = None, render_quality: int = 90, segments=None,
                  segment_options: Optional[dict] = None, identities: bool = False, identity_options: Optional[dict] = None,
-                 ball_trail: int = 0) -> None:
+                 ball_trail: int = 0, render_scale: int = 1) -> None:
+        if isinstance(render_scale, bool) or render_scale not in (1, 2, 3, 4):
+            raise ValueError(f"render_scale={render_scale!r}: 1, 2, 3 or 4 (the rendered clip at 1 / render_scale of the source's size)")
+        self.render_scale = int(render_scale)
         self.video_path = video_path
         self.inference_path = inference_path
         self.start = start
@@ -127,6 +134,8 @@ class TrackingRunner:
         self._merge_pool = None            # sharded mode, rank 0: the thread of the sequential stages (created with the first one)
         self.render = render               # None | path of the file to write (.avi / .mjpeg / .mjpg: Motion-JPEG; anything else: .y4m) | video.FrameSink
         self.render_quality = int(render_quality)   # JPEG quality of a Motion-JPEG file (1..100)
+        if render is not None:
+            self._check_render_size()               # now: a scale or a sink that does not fit the clip costs no tracker run
         # kept frames: None = all of [start, start + n_available); else [(lo, hi)] source frame numbers, set by _set_segments
         self.segments: Optional[list] = None
         self._run_range = (self.start, self.start + self.n_available)      # the source frames this run may keep
@@ -381,12 +390,31 @@ class TrackingRunner:
             marks += self.inset_marks(i)
         return marks
 
+    def render_size(self) -> tuple:
+        """(width, height) of the rendered clip: the source's, divided by ``render_scale``."""
+        return self.video_info.width // self.render_scale, self.video_info.height // self.render_scale
+
+    def _check_render_size(self) -> None:
+        """``ValueError`` for a ``render_scale`` this clip's size does not allow — the rendered frames are YUV 4:2:0: the source must
+        be a multiple of the scale each way and the output even — naming the scales that would work, and for a caller's
+        ``FrameSink`` of another size than the rendered frames."""
+        w, h, s = self.video_info.width, self.video_info.height, self.render_scale
+        fits = [k for k in (1, 2, 3, 4) if w % k == 0 and h % k == 0 and (w // k) % 2 == 0 and (h // k) % 2 == 0 and w // k >= 2 and h // k >= 2]
+        if s != 1 and s not in fits:
+            raise ValueError(f"render_scale={s}: the {w} x {h} clip does not divide into even {s} x {s}-averaged frames "
+                             f"(render_scale that works for this clip: {', '.join(str(k) for k in fits) or 'none'})")
+        wo, ho = self.render_size()
+        if isinstance(self.render, video.FrameSink):
+            sw, sh = getattr(self.render, "w", None), getattr(self.render, "h", None)
+            if sw is not None and sh is not None and (int(sw), int(sh)) != (wo, ho):
+                raise ValueError(f"render: the sink takes {sw} x {sh} frames, the {w} x {h} clip at render_scale={s} gives {wo} x {ho}")
+
     def _make_sink(self):
         """(the sink the rendered frames go to, whether the runner owns — and closes — it).  A path ending in ``.avi``, ``.mjpeg`` or
-        ``.mjpg`` gives a ``video.MjpegSink`` of ``render_quality``, any other path a ``video.Y4mSink``."""
+        ``.mjpg`` gives a ``video.MjpegSink`` of ``render_quality``, any other path a ``video.Y4mSink``, at ``render_size()``."""
         if isinstance(self.render, video.FrameSink):
             return self.render, False
-        w, h = self.video_info.width, self.video_info.height
+        w, h = self.render_size()
         if os.path.splitext(str(self.render))[1].lower() in (".avi", ".mjpeg", ".mjpg"):
             return video.MjpegSink(self.render, w, h, fps=self.video_info.fps, quality=self.render_quality), True
         return video.Y4mSink(self.render, w, h, fps=self.video_info.fps), True
@@ -398,10 +426,13 @@ class TrackingRunner:
         from .. import engine as E, render as R
         eng = self.engine or E.default_engine()
         w, h = self.video_info.width, self.video_info.height
+        wo, ho = self.render_size()
+        # (only a scale other than 1 is passed on: an engine that has never heard of the argument still renders at full size)
+        scaled = {"scale": self.render_scale} if self.render_scale != 1 else {}
         sink, own = self._make_sink()
         print(f"runner: Writing results into {getattr(sink, 'path', sink)}")
         bs = self.RENDER_BATCH
-        dst = eng.alloc(video.yuv_span(bs, h, w, sink.desc))
+        dst = eng.alloc(video.yuv_span(bs, ho, wo, sink.desc))
         t0 = timeit.default_timer()
         done = 0
         try:
@@ -411,8 +442,9 @@ class TrackingRunner:
                     if self.court_inset or self.data_analytics is not None:
                         self._collect(done, n)
                     marks, first = R.pack([self.frame_marks(done + k) for k in range(n)])
-                    eng.render(video.device_batch(frames)[0], n, h, w, marks, first, dst, out=E.RENDER_YUV420, geom=sink.desc, enc=sink.enc)
-                    sink.write_device(dst.view(0, video.yuv_span(n, h, w, sink.desc)), n)
+                    eng.render(video.device_batch(frames)[0], n, h, w, marks, first, dst, out=E.RENDER_YUV420, geom=sink.desc, enc=sink.enc,
+                               **scaled)
+                    sink.write_device(dst.view(0, video.yuv_span(n, ho, wo, sink.desc)), n)
                     done += n
         finally:
             eng.synchronize()

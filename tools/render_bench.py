@@ -15,9 +15,11 @@
     on top — once with fixed court keypoints (one homography per clip) and once with keypoints that differ per frame (one per frame).
     Then the first once more with ``annotator="ellipse"``.
 
-    python tools/render_bench.py [--frames 64] [--reps 50] [--warmup 5] [--passes 3] [--skip-runner] [--kernel-only]
+    python tools/render_bench.py [--frames 64] [--reps 50] [--warmup 5] [--passes 3] [--skip-runner] [--kernel-only] [--scale]
 
 ``--kernel-only`` runs (a) with few repetitions and nothing else: the run to put under ``rocprofv3 --kernel-trace --stats``.
+``--scale`` runs ``scale_mode`` instead: ``Engine.render(scale=)`` and ``TrackingRunner(render_scale=)`` at scales 1, 2, 4 (1280 x 720)
+and 1, 3 (1920 x 1080) — profiles/render_scale.txt.
 """
 import argparse, contextlib, json, statistics, sys, tempfile, time
 from pathlib import Path
@@ -94,8 +96,97 @@ class Joints:
     def marks(self, **kw): return [m for p in self.pk for k in p for m in k.marks()]
 
 
+def scale_mode(a, eng) -> None:
+    """``--scale``: the scaled pass (``Engine.render(scale=)``) beside the full-size pass of the same scene, and the runner's render step
+    to ``.y4m`` and ``.avi`` at each scale.  Scales 1, 2, 4 on 1280 x 720 and 1, 3 on 1920 x 1080 (720 is no multiple of 3 that gives
+    even frames of a 1280-wide clip); scenes: no marks, the 206-mark scene, the same with ``annotator="round_bounding_box"``.
+    (a) the kernel: as in the plain run, --reps calls between one pair of HIP events over three rotating buffer sets; the algorithmic
+        bytes are 3 read per SOURCE pixel plus 1.5 (YUV) or 3 (BGR) written per OUTPUT pixel.
+    (b) ``TrackingRunner(render_scale=s)``'s render step, host clock, median of --passes passes after an untimed one, with the bytes
+        written per frame."""
+    from padel_analytics_amd import engine as E, render as R, video
+    from padel_analytics_amd.trackers import TrackingRunner
+    from padel_analytics_amd.trackers.ball_tracker import Ball
+    from padel_analytics_amd.trackers.keypoints_tracker import Keypoints
+    from padel_analytics_amd.trackers.players_tracker import Players
+    from tests import synth
+    n = a.frames
+    tmp = Path(tempfile.mkdtemp(prefix="render_bench_scale_"))
+    enc = video.YUV_ENC_COEFFS["bt601_limited"]
+    SETS = 3
+    for (w, h), scales in (((1280, 720), (1, 2, 4)), ((1920, 1080), (1, 3))):
+        bgr = synth.synthetic_frames(n, h, w, seed=1000)
+        info = video.VideoInfo(w, h, 30, n)
+        scenes = [scene(i, w, h) for i in range(n)]
+        clip = video.DeviceClip(eng, bgr)
+
+        def trackers_for(annotator):
+            return [Stored("players_tracker", [s[0] for s in scenes], {"video_info": info, "annotator": annotator, "show_confidence": True}, Players),
+                    Stored("players_keypoints_tracker", [s[1] for s in scenes]), Stored("joints", [Joints(s[1]) for s in scenes]),
+                    Stored("ball_tracker", [s[2] for s in scenes], kind=Ball), Stored("keypoints_tracker", [s[3] for s in scenes], kind=Keypoints)]
+
+        def runner_for(annotator, target, s):
+            return TrackingRunner(trackers_for(annotator), clip, tmp / "out.mp4", render=target, engine=eng, render_scale=s)
+        timed = [("no marks", R.pack([[] for _ in range(n)]))]
+        for label, annotator in (("scene", "rectangle_bounding_box"), ("scene, annotator=round_bounding_box", "round_bounding_box")):
+            r = runner_for(annotator, tmp / "out.y4m", 1)
+            timed.append((label, R.pack([r.frame_marks(i) for i in range(n)])))
+            print(json.dumps({"what": label, "h": h, "w": w, "marks_per_frame": int(timed[-1][1][1][1])}))
+        src = [clip.buffer] + [eng.alloc(bgr.nbytes).upload(bgr) for _ in range(SETS - 1)]
+        for out_name in ("i420", "nv12", "bgr"):
+            yuv = out_name != "bgr"
+            for s in scales:
+                ho, wo = h // s, w // s
+                geom = video.yuv_desc(wo, ho, out_name) if yuv else None
+                span = video.yuv_span(n, ho, wo, geom) if yuv else n * ho * wo * 3
+                dst = [eng.alloc(span) for _ in range(SETS)]
+                moved = n * (h * w * 3 + ho * wo * (1.5 if yuv else 3.0))
+                for label, (marks, first) in timed:
+                    call = lambda i: eng.render(src[i % SETS], n, h, w, marks, first, dst[i % SETS], out=E.RENDER_YUV420 if yuv else E.RENDER_BGR,
+                                                geom=geom, enc=enc if yuv else None, scale=s)
+                    for i in range(a.warmup):
+                        call(i)
+                    eng.synchronize()
+                    assert eng.render_last_path() == E.RENDER_PATH_VECTOR
+                    runs = []
+                    for _ in range(3):                          # three windows of --reps calls: their spread is printed
+                        eng.timer_start()
+                        for i in range(a.reps):
+                            call(i)
+                        runs.append(eng.timer_stop() / a.reps)
+                    ms = statistics.median(runs)
+                    print(json.dumps({"what": "render, HIP events around %d calls, 3 windows" % a.reps, "scale": s, "out": out_name, "marks": label,
+                                      "frames": n, "h": h, "w": w, "us_per_call": round(1e3 * ms, 1),
+                                      "us_windows": [round(1e3 * r, 1) for r in runs], "source_frames_per_s": round(n / (ms * 1e-3)),
+                                      "bytes_moved": int(moved), "GB_per_s_algorithmic": round(moved / (ms * 1e-3) / 1e9, 1)}))
+                for b in dst:
+                    b.free()
+        for b in src[1:]:
+            b.free()
+        if not a.skip_runner:
+            for suffix in (".y4m", ".avi"):
+                for s in scales:
+                    target = tmp / ("out" + suffix)
+                    r = runner_for("rectangle_bounding_box", target, s)
+                    secs = []
+                    with contextlib.redirect_stdout(sys.stderr):
+                        for k in range(a.passes + 1):           # one untimed pass first
+                            eng.synchronize()
+                            t0 = time.perf_counter()
+                            r.draw_and_collect_data()
+                            secs.append(time.perf_counter() - t0)
+                    med = statistics.median(secs[1:])
+                    size = target.stat().st_size
+                    print(json.dumps({"what": "TrackingRunner render step to " + suffix + " (host clock)", "render_scale": s, "frames": n, "h": h, "w": w,
+                                      "out_h": h // s, "out_w": w // s, "seconds_median": round(med, 4), "seconds_passes": [round(x, 4) for x in secs[1:]],
+                                      "frames_per_s": round(n / med, 1), "bytes_per_frame": size // n, "MB_per_s_written": round(size / med / 1e6, 1)}))
+                    target.unlink()
+        clip.free()
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
+    ap.add_argument("--scale", action="store_true", help="the scaled pass and the runner's render_scale instead of the plain run (scale_mode)")
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--width", type=int, default=1280)
@@ -113,6 +204,9 @@ if __name__ == "__main__":
     if a.kernel_only:
         a.reps, a.skip_runner = min(a.reps, 10), True
     print("# " + " ".join(["python", "tools/render_bench.py"] + sys.argv[1:]))
+    if a.scale:
+        scale_mode(a, eng)
+        sys.exit(0)
     bgr = synth.synthetic_frames(n, h, w, seed=1000)
     info = video.VideoInfo(w, h, 30, n)
     scenes = [scene(i, w, h) for i in range(n)]
