@@ -292,6 +292,40 @@ int pa_render_last_path(pa_engine* eng);
  * code outside the font                                                                                                   */
 int pa_glyph_rows(int code, uint8_t rows[7]);
 
+/* ---- frames seen from above: packed BGR frames through one homography each (csrc/warp.hip) ----
+ * n packed BGR frames of h x w at src_bgr_dev (HBM, frame i at src + i * h * w * 3) become n packed BGR frames of oh x ow at
+ * dst_bgr_dev (frame i at dst + i * oh * ow * 3).  Frame i has its own 3 x 3 matrix m = m_host[9 i .. 9 i + 9), row-major, that takes
+ * CANVAS pixels to SOURCE pixels, and a word valid_host[i].  fill_bgr is B | G << 8 | R << 16.  The arithmetic is csrc/warp_math.h
+ * (host and device), its readable twin padel_analytics_amd/topdown.py (warp_host).  Output pixel (u, v), u the column:
+ *   valid == 0: the pixel is fill.
+ *   Coordinates, in IEEE double, every operation rounded on its own (no fused multiply-add), in this order:
+ *       X = (m0 u + m1 v) + m2      Y = (m3 u + m4 v) + m5      Z = (m6 u + m7 v) + m8
+ *     not Z > 0: fill.  sx = X / Z, sy = Y / Z, the correctly rounded quotients.
+ *     not (sx > -1 && sx < w && sy > -1 && sy < h): fill.  NaN and infinities fail the comparisons.
+ *   Cell and weights, in integers:  qx = (int32) floor(sx * 32), x0 = qx >> 5 (arithmetic shift), wx = qx & 31; the same in y.
+ *     (NOT sx - floor(sx): for a tiny negative sx that difference rounds to 1.  sx = -1e-20 is cell -1 with weight 31.)
+ *   Sampling: P(x, y) is the source pixel if 0 <= x < w && 0 <= y < h, else fill.  Per channel, all int32:
+ *       top = P(x0, y0) (32 - wx) + P(x0 + 1, y0) wx        bot: the same on row y0 + 1
+ *       out = (top (32 - wy) + bot wy + 512) >> 10
+ *     i.e. float64 bilinear interpolation at the coordinates quantised to 1 / 32, rounded half up.
+ * Doubles on purpose: projected_court's project_point is float64, so marks projected on the host and the warped picture agree to
+ * far below 1 / 32 pixel.  Bilinear only: no area filter, strong minification aliases.
+ * Refused, nothing launched, the reason in pa_last_error: n < 1; h, w, oh or ow outside 1 .. PA_WARP_MAX_DIM; a NULL pointer; a
+ * non-finite matrix entry in a frame with valid != 0; dst overlapping src (the call is not in place).  pa_warp_check gives the same
+ * answers on the host alone (no engine, no GPU): 0, or 1 with the reason in why[0 .. cap); src and dst are addresses it compares
+ * and never reads through.
+ * ASYNCHRONOUS on the engine's compute stream, like pa_render, under the same invariant.  The matrices and the valid words are
+ * copied to an engine-owned staging buffer (grown on demand, freed with the engine) before the call returns.
+ * Two store paths, chosen per call: 16 bytes at a time when ow is a multiple of 16 and dst_bgr_dev is 16-byte aligned, bytes
+ * otherwise.                                                                                                                 */
+#define PA_WARP_MAX_DIM 4096
+int pa_warp_perspective(pa_engine* eng, const uint8_t* src_bgr_dev, int n, int h, int w, const double* m_host, const int32_t* valid_host,
+                        uint32_t fill_bgr, uint8_t* dst_bgr_dev, int oh, int ow);
+int pa_warp_check(int n, int h, int w, int oh, int ow, const double* m_host, const int32_t* valid_host, const void* src, const void* dst,
+                  char* why, size_t cap);
+/* which instantiation the last successful pa_warp_perspective of this engine launched — 1 16-byte stores, 2 byte stores, 0 none yet */
+int pa_warp_last_path(pa_engine* eng);
+
 /* ---- frame statistics: is this the court camera?  (csrc/frame_activity.hip; the readable twin is activity.frame_activity_host) ----
  * All integer.  The luma of a BGR pixel is  Y = (29 B + 150 G + 77 R + 128) >> 8  (0 .. 255).
  * For frames f_0 .. f_{n-1} of h x w packed BGR (frame i at frames_bgr_dev + i * h * w * 3), a reference image ref of the same size,

@@ -278,6 +278,19 @@ hipError_t launch_render(const RenderArgs& a, hipStream_t s, int* vec_out = null
 bool render_scaled_vector_path_ok(const RenderArgs& a, int scale);
 hipError_t launch_render_scaled(const RenderArgs& a, int scale, hipStream_t s, int* vec_out = nullptr);
 
+// Perspective resample of packed BGR frames (warp.hip).  The caller (pa_warp_perspective) has checked the call (warp_check.cpp) and
+// staged the matrices and the valid words in HBM; the launcher only picks the 16-byte or the byte instantiation.
+struct WarpArgs {
+    const uint8_t* src;   // n packed BGR frames of h x w
+    uint8_t* dst;         // n packed BGR frames of oh x ow, not overlapping src
+    const double* m;      // [n][9], canvas -> source
+    const int32_t* valid; // [n]
+    int n, h, w, oh, ow;
+    uint32_t fill;        // B | G << 8 | R << 16
+};
+bool warp_vector_path_ok(const WarpArgs& a);            // ow a multiple of 16 and dst 16-byte aligned
+hipError_t launch_warp(const WarpArgs& a, hipStream_t s, int* vec_out = nullptr);            // *vec_out: 1 16-byte path, 0 byte path
+
 // Pillow-style separable resample pass over u8 images (coefficients precomputed on host):
 // out[b][y][x][c] = clip8((sum_k coef[o][k] * in[...lo[o]+k...] + (1<<21)) >> 22)
 struct ResamplePassArgs {

@@ -127,6 +127,7 @@ ABI_SYMBOLS = [
     "pa_frame_activity", "pa_frame_activity_check", "pa_frames_median",
     "pa_box_histograms", "pa_box_histograms_check",
     "pa_render_scaled", "pa_render_scaled_check",
+    "pa_warp_perspective", "pa_warp_check", "pa_warp_last_path",
 ]
 
 
@@ -227,6 +228,10 @@ def load_library():
         lib.pa_render_scaled.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, C.POINTER(pa_yuv_desc), C.POINTER(pa_yuv_enc), vp]
         lib.pa_render_scaled_check.argtypes = [i32, i32, i32, vp, vp, i32, i32, C.POINTER(pa_yuv_desc), C.POINTER(pa_yuv_enc), i32, C.c_char_p, sz]
     lib.pa_glyph_rows.argtypes = [i32, vp]
+    if hasattr(lib, "pa_warp_perspective"):        # (an older build under PADEL_LIB, likewise: asking it for a warp raises)
+        lib.pa_warp_perspective.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.c_uint32, vp, i32, i32]
+        lib.pa_warp_check.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_char_p, sz]
+        lib.pa_warp_last_path.argtypes = [vp]
     lib.pa_jpeg_encode.argtypes = [vp, vp, i32, i32, i32, C.POINTER(pa_yuv_desc), i32, vp, sz, vp]
     lib.pa_jpeg_check.argtypes = [i32, i32, i32, C.POINTER(pa_yuv_desc), i32, C.c_char_p, sz]
     lib.pa_jpeg_interval_bytes.argtypes = [i32]
@@ -330,6 +335,44 @@ def render_check(n: int, h: int, w: int, marks, first, out: int = RENDER_BGR, ge
         rc = load_library().pa_render_check(*head, int(out), *tail, why, 512)
     else:
         rc = load_library().pa_render_scaled_check(*head, int(scale), int(out), *tail, 1 if in_place else 0, why, 512)
+    return why.value.decode() if rc else None
+
+
+#: ``pa_warp_perspective`` refuses larger frames and canvases (PA_WARP_MAX_DIM)
+WARP_MAX_DIM = 4096
+#: ``Engine.warp_last_path()``: how the last warp stored its pixels
+WARP_PATH_VECTOR, WARP_PATH_BYTE = 1, 2
+
+
+def _warp_args(n, matrices, valid):
+    """(matrices as (n, 9) float64 or None, valid as (n,) int32 or None); ``ValueError`` for another count than ``n`` frames' worth."""
+    if matrices is not None:
+        matrices = np.ascontiguousarray(matrices, np.float64).reshape(-1)
+        if matrices.size != 9 * max(int(n), 0):
+            raise ValueError(f"warp: matrices holds {matrices.size} numbers, {n} frames need {9 * max(int(n), 0)}")
+    if valid is not None:
+        valid = np.ascontiguousarray(valid, np.int32).reshape(-1)
+        if valid.size != max(int(n), 0):
+            raise ValueError(f"warp: valid holds {valid.size} words, {n} frames need {max(int(n), 0)}")
+    return matrices, valid
+
+
+def fill_word(fill) -> int:
+    """(B, G, R) or an integer -> B | G << 8 | R << 16."""
+    if isinstance(fill, (tuple, list, np.ndarray)):
+        b, g, r = (int(c) & 0xff for c in fill)
+        return b | g << 8 | r << 16
+    return int(fill) & 0xffffff
+
+
+def warp_check(n: int, h: int, w: int, oh: int, ow: int, matrices, valid, src: Optional[int] = 1, dst: Optional[int] = 1 << 60) -> Optional[str]:
+    """None if ``pa_warp_perspective`` would accept the call, else its reason for refusing it (``pa_warp_check``: host code, no GPU).
+    ``src``, ``dst``: the addresses of the frames and of the canvases (compared, never read through; None is NULL, as it is for
+    ``matrices`` and ``valid``); the default is a source at address 1 and a destination far behind it."""
+    matrices, valid = _warp_args(n, matrices, valid)
+    why = C.create_string_buffer(512)
+    rc = load_library().pa_warp_check(int(n), int(h), int(w), int(oh), int(ow), None if matrices is None else matrices.ctypes.data,
+                                      None if valid is None else valid.ctypes.data, src, dst, why, 512)
     return why.value.decode() if rc else None
 
 
@@ -580,6 +623,27 @@ class Engine:
     def render_last_path(self) -> int:
         """RENDER_PATH_VECTOR / RENDER_PATH_BYTE: what the last successful ``render`` launched (0: none yet)."""
         return int(self.lib.pa_render_last_path(self.handle))
+
+    def warp(self, src: DeviceBuffer, n: int, h: int, w: int, matrices, valid, dst: DeviceBuffer, oh: int, ow: int, fill=(0, 0, 0)) -> None:
+        """``n`` packed BGR frames of ``h`` x ``w`` in ``src`` -> ``n`` packed BGR frames of ``oh`` x ``ow`` in ``dst``, frame i through
+        its own 3 x 3 matrix ``matrices[i]`` that takes CANVAS pixels to SOURCE pixels (float64; bilinear with weights in 1 / 32 pixel:
+        include/padel_hip.h, ``pa_warp_perspective``; the numpy twin is ``topdown.warp_host``).  A frame with ``valid[i] == 0``, and every
+        pixel that falls outside the source or behind the horizon, is ``fill`` (B, G, R).  Not in place.  Asynchronous: ordered with
+        every later call of this engine by its one compute stream; the arrays are consumed before the call returns.  What the
+        kernel cannot run is an ``EngineError``, nothing is launched."""
+        matrices, valid = _warp_args(n, matrices, valid)
+        if n >= 1 and h >= 1 and w >= 1 and src.nbytes < n * h * w * 3:
+            raise EngineError(f"warp: src holds {src.nbytes} bytes, {n} BGR frames need {n * h * w * 3}")
+        if n >= 1 and oh >= 1 and ow >= 1 and dst.nbytes < n * oh * ow * 3:
+            raise EngineError(f"warp: dst holds {dst.nbytes} bytes, {n} BGR canvases need {n * oh * ow * 3}")
+        if not hasattr(self.lib, "pa_warp_perspective"):
+            raise EngineError("warp: this build of the library has no pa_warp_perspective")
+        self._check(self.lib.pa_warp_perspective(self.handle, src.ptr, int(n), int(h), int(w), None if matrices is None else matrices.ctypes.data,
+                                                 None if valid is None else valid.ctypes.data, fill_word(fill), dst.ptr, int(oh), int(ow)))
+
+    def warp_last_path(self) -> int:
+        """WARP_PATH_VECTOR (16 bytes at a time) / WARP_PATH_BYTE: what the last successful ``warp`` launched (0: none yet)."""
+        return int(self.lib.pa_warp_last_path(self.handle))
 
     def frame_activity(self, src: DeviceBuffer, n: int, h: int, w: int, ref: DeviceBuffer, prev: Optional[DeviceBuffer] = None, roi=None,
                        tau: int = 24, out: Optional[np.ndarray] = None) -> np.ndarray:

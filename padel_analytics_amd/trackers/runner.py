@@ -25,6 +25,15 @@ Additions (all off by default, the reference's sequential semantics stay the def
   source pixels under it, in that same pass (``pa_render_scaled``): an anti-aliased copy of 1 / render_scale² the bytes — and the way
   to an ``.avi`` of a clip wider than the JPEG encoder's 2560.  Marks, the inset and the collected data stay in source pixels.  A
   scale the clip's size does not allow, or a ``FrameSink`` of another size than the rendered frames, is a ``ValueError`` in ``__init__``;
+* ``topdown=`` a path or a ``video.FrameSink``, as for ``render=``: a second clip, every frame warped through its court homography into
+  a metric canvas of the court (``topdown.TopDownView``; ``topdown_options``: its keyword arguments ``px_per_m``, ``margin_m``, ``fill``) —
+  ``Engine.warp`` (csrc/warp.hip) into a BGR canvas in HBM, then ``Engine.render`` of that canvas with the court's lines, the players
+  and the ball as marks.  The real footage seen from above: whether the floor, rectified, looks like a padel court is the check of
+  the homography the inset cannot give.  It shares the walk over the clip with ``render=`` when both are given, follows ``segments=``
+  as ``render=`` does, is rank 0's under ``distributed``, and ignores ``render_scale``; ``render_quality`` serves both files.  A frame
+  without a homography is ``fill`` with ``NO COURT`` on it.  ``ValueError`` in ``__init__``: no tracker gives ``Keypoints``, a canvas the
+  sink refuses, a ``FrameSink`` of another size than the canvas, ``fanout=True``.  ``timings["__topdown__"]``: seconds, frames, bytes;
+
 * ``collect_data=True`` (the reference's own switch, :74-79): the step also projects every frame's players and ball into the 2-D
   court (``projected_court.ProjectedCourt.project_batch``: the reference's homography state machine :633-647, the frames of a batch
   that need a homography solved together) and fills ``self.data_analytics`` (``analytics.DataAnalytics``) with the players' positions
@@ -88,7 +97,7 @@ class TrackingRunner:
                  fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None, render=None,
                  court_inset: Optional[bool] = None, render_quality: int = 90, segments=None,
                  segment_options: Optional[dict] = None, identities: bool = False, identity_options: Optional[dict] = None,
-                 ball_trail: int = 0, render_scale: int = 1) -> None:
+                 ball_trail: int = 0, render_scale: int = 1, topdown=None, topdown_options: Optional[dict] = None) -> None:
         if isinstance(render_scale, bool) or render_scale not in (1, 2, 3, 4):
             raise ValueError(f"render_scale={render_scale!r}: 1, 2, 3 or 4 (the rendered clip at 1 / render_scale of the source's size)")
         self.render_scale = int(render_scale)
@@ -136,6 +145,10 @@ class TrackingRunner:
         self.render_quality = int(render_quality)   # JPEG quality of a Motion-JPEG file (1..100)
         if render is not None:
             self._check_render_size()               # now: a scale or a sink that does not fit the clip costs no tracker run
+        self.topdown = topdown             # None | path (suffixes as for render) | video.FrameSink: the clip seen from above
+        self.topdown_view = None           # topdown.TopDownView: the canvas
+        if topdown is not None:
+            self._init_topdown(trackers, dict(topdown_options or {}))
         # kept frames: None = all of [start, start + n_available); else [(lo, hi)] source frame numbers, set by _set_segments
         self.segments: Optional[list] = None
         self._run_range = (self.start, self.start + self.n_available)      # the source frames this run may keep
@@ -264,7 +277,7 @@ class TrackingRunner:
     RENDER_BATCH = 64
 
     def draw_and_collect_data(self) -> None:
-        if self.render is None and self.data_analytics is None:
+        if self.render is None and self.topdown is None and self.data_analytics is None:
             print("runner: drawing / data collection is outside the hot path of this build (skipped)")
             return
         if self.distributed and D.rank() != 0:     # the results live on rank 0
@@ -274,7 +287,7 @@ class TrackingRunner:
         # inset_marks cached before the trackers had stored their results do not stay
         self._restart_collection()
         self._collect_seconds = 0.0
-        if self.render is None:                    # the stored results alone: no frame is read, no GPU touched
+        if self.render is None and self.topdown is None:      # the stored results alone: no frame is read, no GPU touched
             done = 0
             while done < self.n_available:
                 n = min(self.RENDER_BATCH, self.n_available - done)
@@ -409,54 +422,135 @@ class TrackingRunner:
             if sw is not None and sh is not None and (int(sw), int(sh)) != (wo, ho):
                 raise ValueError(f"render: the sink takes {sw} x {sh} frames, the {w} x {h} clip at render_scale={s} gives {wo} x {ho}")
 
+    _MJPEG_SUFFIXES = (".avi", ".mjpeg", ".mjpg")
+
+    def _sink_for(self, target, w: int, h: int):
+        """(the sink ``target`` names, whether the runner owns — and closes — it).  A path ending in ``.avi``, ``.mjpeg`` or ``.mjpg``
+        gives a ``video.MjpegSink`` of ``render_quality``, any other path a ``video.Y4mSink``, of ``w`` x ``h`` frames."""
+        if isinstance(target, video.FrameSink):
+            return target, False
+        if os.path.splitext(str(target))[1].lower() in self._MJPEG_SUFFIXES:
+            return video.MjpegSink(target, w, h, fps=self.video_info.fps, quality=self.render_quality), True
+        return video.Y4mSink(target, w, h, fps=self.video_info.fps), True
+
     def _make_sink(self):
-        """(the sink the rendered frames go to, whether the runner owns — and closes — it).  A path ending in ``.avi``, ``.mjpeg`` or
-        ``.mjpg`` gives a ``video.MjpegSink`` of ``render_quality``, any other path a ``video.Y4mSink``, at ``render_size()``."""
-        if isinstance(self.render, video.FrameSink):
-            return self.render, False
-        w, h = self.render_size()
-        if os.path.splitext(str(self.render))[1].lower() in (".avi", ".mjpeg", ".mjpg"):
-            return video.MjpegSink(self.render, w, h, fps=self.video_info.fps, quality=self.render_quality), True
-        return video.Y4mSink(self.render, w, h, fps=self.video_info.fps), True
+        """The sink the rendered frames go to (``_sink_for``), at ``render_size()``."""
+        return self._sink_for(self.render, *self.render_size())
+
+    def _init_topdown(self, trackers, options: dict) -> None:
+        """``topdown=``: the canvas, and a ``ValueError`` now — before any tracker runs, before a file is created — for a run that
+        could not write the clip: no tracker gives ``Keypoints`` (no homography, ever), ``fanout``, a canvas the sink refuses, a
+        caller's ``FrameSink`` of another size than the canvas."""
+        from .. import mjpeg, topdown as T
+        if self.fanout:
+            raise ValueError("topdown= is not available with fanout=True")
+        if not any(self._object_name(t) == "Keypoints" for t in trackers):
+            raise ValueError("topdown=: no tracker gives Keypoints, so no frame would have a court homography to be warped through")
+        self.topdown_view = view = T.TopDownView(self.projected_court, **options)
+        w, h = view.size
+        if isinstance(self.topdown, video.FrameSink):
+            sw, sh = getattr(self.topdown, "w", None), getattr(self.topdown, "h", None)
+            if sw is not None and sh is not None and (int(sw), int(sh)) != (w, h):
+                raise ValueError(f"topdown: the sink takes {sw} x {sh} frames, the canvas is {w} x {h}")
+            return
+        try:
+            if os.path.splitext(str(self.topdown))[1].lower() in self._MJPEG_SUFFIXES:
+                mjpeg.check(1, h, w, video.yuv_desc(w, h, "i420", "bt601", "full"), self.render_quality)
+            else:
+                video.yuv_span(1, h, w, video.yuv_desc(w, h, "i420"))
+        except ValueError as exc:
+            raise ValueError(f"topdown: the {w} x {h} canvas cannot be written to {self.topdown}: {exc}") from None
+
+    def topdown_marks(self, i: int) -> list:
+        """The marks of canvas frame ``i`` (``TopDownView.marks``): the frame's projection, and the stored ``Players`` / ``Ball`` of the
+        trackers of those types (the last one, if several, as the projection takes them)."""
+        self._project_through(i + 1)
+        per = {"Players": None, "Ball": None}
+        for tracker in self.trackers.values():
+            name = self._object_name(tracker)
+            if name in per and i < len(tracker.results):
+                per[name] = tracker.results[i]
+        return self.topdown_view.marks(self._projected[i], per["Players"], per["Ball"])
 
     def _render_clip(self) -> int:
-        """The clip once more, ``RENDER_BATCH`` frames at a time: BGR in HBM (``video.ResidentBatches``), one ``Engine.render`` to YUV
-        4:2:0 in the sink's geometry, one download, one write.  With the inset or the collection on, each batch is projected (and
-        collected) first.  -> the number of frames."""
+        """The clip once more, ``RENDER_BATCH`` frames at a time: BGR in HBM (``video.ResidentBatches``); each batch is projected (and,
+        with the inset or the collection on, collected) first.  ``render=``: one ``Engine.render`` to YUV 4:2:0 in the sink's geometry,
+        one download, one write.  ``topdown=``: one ``Engine.warp`` of the batch into a BGR canvas buffer, one ``Engine.render`` of that
+        buffer with the canvas marks into the second sink's geometry, one download, one write.  ONE walk serves both.  -> the number
+        of frames."""
         from .. import engine as E, render as R
         eng = self.engine or E.default_engine()
         w, h = self.video_info.width, self.video_info.height
         wo, ho = self.render_size()
         # (only a scale other than 1 is passed on: an engine that has never heard of the argument still renders at full size)
         scaled = {"scale": self.render_scale} if self.render_scale != 1 else {}
-        sink, own = self._make_sink()
-        print(f"runner: Writing results into {getattr(sink, 'path', sink)}")
         bs = self.RENDER_BATCH
-        dst = eng.alloc(video.yuv_span(bs, ho, wo, sink.desc))
+        sink = top = dst = canvas = top_dst = None
+        own = top_own = False
+        view = self.topdown_view
+        top_seconds = 0.0
         t0 = timeit.default_timer()
         done = 0
         try:
+            if self.render is not None:
+                sink, own = self._make_sink()
+                print(f"runner: Writing results into {getattr(sink, 'path', sink)}")
+                dst = eng.alloc(video.yuv_span(bs, ho, wo, sink.desc))
+                t0 = timeit.default_timer()
+            if self.topdown is not None:
+                ts = timeit.default_timer()
+                top, top_own = self._sink_for(self.topdown, *view.size)
+                print(f"runner: Writing the top-down view into {getattr(top, 'path', top)}")
+                canvas = eng.alloc(bs * view.h * view.w * 3)
+                top_dst = eng.alloc(video.yuv_span(bs, view.h, view.w, top.desc))
+                top_seconds += timeit.default_timer() - ts
             with video.ResidentBatches(eng, self._batches(bs), bs, (h, w)) as walk:
                 for frames, _ in walk:
                     n = len(frames)
                     if self.court_inset or self.data_analytics is not None:
                         self._collect(done, n)
-                    marks, first = R.pack([self.frame_marks(done + k) for k in range(n)])
-                    eng.render(video.device_batch(frames)[0], n, h, w, marks, first, dst, out=E.RENDER_YUV420, geom=sink.desc, enc=sink.enc,
-                               **scaled)
-                    sink.write_device(dst.view(0, video.yuv_span(n, ho, wo, sink.desc)), n)
+                    elif top is not None:
+                        self._project_through(done + n)
+                    src = video.device_batch(frames)[0]
+                    if sink is not None:
+                        marks, first = R.pack([self.frame_marks(done + k) for k in range(n)])
+                        eng.render(src, n, h, w, marks, first, dst, out=E.RENDER_YUV420, geom=sink.desc, enc=sink.enc, **scaled)
+                        sink.write_device(dst.view(0, video.yuv_span(n, ho, wo, sink.desc)), n)
+                    if top is not None:
+                        ts = timeit.default_timer()
+                        matrices, valid = view.matrices(self._projected[done:done + n])
+                        eng.warp(src, n, h, w, matrices, valid, canvas, view.h, view.w, fill=view.fill)
+                        marks, first = R.pack([self.topdown_marks(done + k) for k in range(n)])
+                        eng.render(canvas, n, view.h, view.w, marks, first, top_dst, out=E.RENDER_YUV420, geom=top.desc, enc=top.enc)
+                        top.write_device(top_dst.view(0, video.yuv_span(n, view.h, view.w, top.desc)), n)
+                        top_seconds += timeit.default_timer() - ts
                     done += n
         finally:
             eng.synchronize()
-            dst.free()
+            for buf in (dst, canvas, top_dst):
+                if buf is not None:
+                    buf.free()
             if own:
                 sink.close()
+            if top_own:
+                top.close()
         t1 = timeit.default_timer()
-        written = getattr(sink, "bytes_written", None)
-        if written is None and own:
-            written = os.path.getsize(sink.path)
-        self.timings["__render__"] = {"seconds": t1 - t0, "frames": done, "bytes": written}
-        print(f"runner: rendered {done} frames in {t1 - t0:.3f} s ({done / max(t1 - t0, 1e-9):.1f} frames/s: render + download + write)")
+
+        def written(s, owned):
+            b = getattr(s, "bytes_written", None)
+            return os.path.getsize(s.path) if b is None and owned else b
+
+        if sink is not None:
+            # (with topdown= as well: the walk without the top-down view's own steps)
+            seconds = t1 - t0 - (top_seconds if top is not None else 0.0)
+            self.timings["__render__"] = {"seconds": seconds, "frames": done, "bytes": written(sink, own)}
+            print(f"runner: rendered {done} frames in {seconds:.3f} s ({done / max(seconds, 1e-9):.1f} frames/s: render + download + write)")
+        if top is not None:
+            # alone: the whole walk; beside render=: its own steps (matrices and marks, warp, render, download / encode, write)
+            seconds = top_seconds if sink is not None else t1 - t0
+            self.timings["__topdown__"] = {"seconds": seconds, "frames": done, "bytes": written(top, top_own)}
+            print(f"runner: top-down view: {done} frames of {view.w} x {view.h} in {seconds:.3f} s ({done / max(seconds, 1e-9):.1f} frames/s: "
+                  f"warp + render + download + write)")
         return done
 
     def _frames(self, lo: int = 0, hi: Optional[int] = None):
