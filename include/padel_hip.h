@@ -326,6 +326,49 @@ int pa_warp_check(int n, int h, int w, int oh, int ow, const double* m_host, con
 /* which instantiation the last successful pa_warp_perspective of this engine launched — 1 16-byte stores, 2 byte stores, 0 none yet */
 int pa_warp_last_path(pa_engine* eng);
 
+/* ---- where the players stood: density maps on the warp's canvases (csrc/heat.hip) ----
+ * All integer.  The arithmetic is csrc/heat_math.h (host and device), its readable twin padel_analytics_amd/heatmap.py
+ * (accumulate_host).
+ * State: `planes` (1 .. PA_HEAT_MAX_PLANES) maps of oh x ow uint32 at state_dev (HBM, plane p at state + p * oh * ow), the CALLER's:
+ *   zero at the start, carried from call to call.
+ * Points: frame i owns the triples pts_host[3 first_host[i] .. 3 first_host[i + 1]) = (x, y, plane): a canvas pixel (it may lie
+ *   outside the canvas), |x|, |y| <= PA_HEAT_MAX_COORD, and the map it goes to.  first_host: n + 1 entries, first[0] = 0,
+ *   non-decreasing, at most PA_HEAT_MAX_POINTS per frame.  pts_host may be NULL when first_host[n] is 0.
+ * Splat: with radius r in 1 .. PA_HEAT_MAX_RADIUS, a point adds to pixel (u, v) of its map, where d2 = (u - x)^2 + (v - y)^2 < r r,
+ *       k(d2) = (255 (r r - d2)) / (r r)            floor division: 255 at the centre, 0 on the rim and beyond
+ *   (r = 2: 255, 191 on the four neighbours, 127 on the four diagonals, 1527 in all).  Every addition saturates at 2^32 - 1.
+ * Display of frame t (canvas t of canvas_bgr_dev, n packed BGR canvases of oh x ow as pa_warp_perspective leaves them), in place:
+ *   D     = the saturating sum, over the planes whose bit is set in show_mask, of the maps AFTER the points of frames 0 .. t of this
+ *           call were added;
+ *   level = D >= full ? 255 : (D 255) / full,  full in 1 .. PA_HEAT_MAX_FULL;      a = (alpha level) >> 8,  alpha in 0 .. 256;
+ *   a > 0: per channel  p = (p (256 - a) + lut[level][c] a + 128) >> 8  — PA_MARK_BLEND's rule; lut_host is 256 x 3 bytes of BGR.
+ *   alpha = 0 changes no pixel and still updates the state.
+ * valid_host[t] == 0: canvas t is left as it is, and the frame may carry no point.
+ * Refused, nothing launched, the reason in pa_last_error — one each: n < 1; oh or ow outside 1 .. PA_WARP_MAX_DIM; planes, r, full or
+ * alpha outside its range; a show_mask without a bit or with one at or above planes; a NULL pointer; a first[] that does not start
+ * at 0 or decreases; more than PA_HEAT_MAX_POINTS points in a frame; a point beyond +/- PA_HEAT_MAX_COORD or on a plane that is
+ * not there; points in a frame with valid == 0; the state overlapping the canvases.  pa_heat_check gives the same answers on the
+ * host alone (no engine, no GPU): 0, or 1 with the reason in why[0 .. cap); canvas and state are addresses it compares and never
+ * reads through.
+ * ASYNCHRONOUS on the engine's compute stream, like pa_warp_perspective, under the same invariant (the state included: what reads
+ * it is ordered behind this call by that stream).  The host arrays are copied to an engine-owned staging buffer (grown on demand,
+ * freed with the engine) before the call returns.
+ * Two store paths, chosen per call: 16 bytes at a time when ow is a multiple of 16 and canvas_bgr_dev and state_dev are 16-byte
+ * aligned, single pixels otherwise.                                                                                          */
+#define PA_HEAT_MAX_POINTS 64
+#define PA_HEAT_MAX_PLANES 4
+#define PA_HEAT_MAX_RADIUS 255
+#define PA_HEAT_MAX_COORD 32767
+#define PA_HEAT_MAX_FULL 16777215
+int pa_heat_accumulate(pa_engine* eng, uint8_t* canvas_bgr_dev, int n, int oh, int ow, uint32_t* state_dev, int planes,
+                       const int32_t* pts_host, const int32_t* first_host, const int32_t* valid_host, int r, uint32_t full, int alpha,
+                       int show_mask, const uint8_t* lut_host);
+int pa_heat_check(int n, int oh, int ow, int planes, const int32_t* pts_host, const int32_t* first_host, const int32_t* valid_host, int r,
+                  uint32_t full, int alpha, int show_mask, const uint8_t* lut_host, const void* canvas, const void* state, char* why,
+                  size_t cap);
+/* which instantiation the last successful pa_heat_accumulate of this engine launched — 1 16-byte accesses, 2 single pixels, 0 none yet */
+int pa_heat_last_path(pa_engine* eng);
+
 /* ---- frame statistics: is this the court camera?  (csrc/frame_activity.hip; the readable twin is activity.frame_activity_host) ----
  * All integer.  The luma of a BGR pixel is  Y = (29 B + 150 G + 77 R + 128) >> 8  (0 .. 255).
  * For frames f_0 .. f_{n-1} of h x w packed BGR (frame i at frames_bgr_dev + i * h * w * 3), a reference image ref of the same size,

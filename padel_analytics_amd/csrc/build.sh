@@ -11,9 +11,9 @@ OUT="${PADEL_OUT:-../libpadel_hip.so}"
 mkdir -p "$BUILD"
 pids=()
 # PADEL_ONLY="a.hip b.hip": recompile only these translation units and relink with the objects already in $BUILD (iteration)
-ALL="conv_tap.hip conv_tap16.hip conv_tap_bx3.hip conv_patch_bx3.hip conv_tap_h2.hip conv_tap_h2p.hip conv_1x1_h2s.hip conv_patch_h2.hip conv_patch_h2q.hip conv_patch_h2r.hip conv_patch_h2v.hip conv_patch_h2w.hip conv_patch16.hip kernels_misc.hip resnet_ops.hip yolo11_ops.hip stem_l1_h2.hip head_tail_h2.hip postproc.hip tracknet_post.hip yuv_convert.hip render.hip jpeg_encode.hip jpeg_decode.hip frame_activity.hip box_histogram.hip warp.hip"
+ALL="conv_tap.hip conv_tap16.hip conv_tap_bx3.hip conv_patch_bx3.hip conv_tap_h2.hip conv_tap_h2p.hip conv_1x1_h2s.hip conv_patch_h2.hip conv_patch_h2q.hip conv_patch_h2r.hip conv_patch_h2v.hip conv_patch_h2w.hip conv_patch16.hip kernels_misc.hip resnet_ops.hip yolo11_ops.hip stem_l1_h2.hip head_tail_h2.hip postproc.hip tracknet_post.hip yuv_convert.hip render.hip jpeg_encode.hip jpeg_decode.hip frame_activity.hip box_histogram.hip warp.hip heat.hip"
 # the engine (host code that calls the HIP runtime), one translation unit per concern: engine_internal.h
-ENGINE="engine.cpp engine_pre.cpp engine_yolo.cpp engine_tracknet.cpp engine_resnet.cpp engine_comm.cpp engine_render.cpp engine_jpeg.cpp engine_jpeg_decode.cpp engine_activity.cpp engine_warp.cpp"
+ENGINE="engine.cpp engine_pre.cpp engine_yolo.cpp engine_tracknet.cpp engine_resnet.cpp engine_comm.cpp engine_render.cpp engine_jpeg.cpp engine_jpeg_decode.cpp engine_activity.cpp engine_warp.cpp engine_heat.cpp"
 for f in ${PADEL_ONLY:-$ALL $ENGINE}; do
   [ -f "$f" ] || continue
   # per-file flags.  warp.hip: its doubles are pinned bit for bit against the host (warp_math.h), and at -O3 the _rn intrinsics
@@ -46,6 +46,9 @@ g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c render_check.cpp -o "$BUILD/
 pids+=($!)
 # what pa_warp_perspective refuses: no HIP at all (the same file builds into tests/warp_main.cpp's program)
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c warp_check.cpp -o "$BUILD/warp_check.o" &
+pids+=($!)
+# what pa_heat_accumulate refuses: no HIP at all (heat_math.h also builds into tests/heat_main.cpp's program)
+g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c heat_check.cpp -o "$BUILD/heat_check.o" &
 pids+=($!)
 # what pa_frame_activity refuses, and how a launch is cut into bands: no HIP at all (the same file builds into tests/activity_check_main.cpp's program)
 g++ -O3 -ffp-contract=off -std=c++17 -fPIC -Wall -c activity_check.cpp -o "$BUILD/activity_check.o" &

@@ -142,7 +142,7 @@ void pa_engine_destroy(pa_engine* e) {
     for (hipEvent_t ev : e->timer_ev) if (ev) hipEventDestroy(ev);
     e->destroy_streams();
     if (e->copy_stream) hipStreamDestroy(e->copy_stream);
-    delete e;          // zeros, yuv_stage, render_stage, warp_stage, activity_stage, box_stage: idle since the wait above
+    delete e;          // zeros, yuv_stage, render_stage, warp_stage, heat_stage, activity_stage, box_stage: idle since the wait above
 }
 
 int pa_engine_synchronize(pa_engine* e) {

@@ -7,6 +7,7 @@
 //   engine_resnet.cpp    the ResNet-50 court-keypoint regressor
 //   engine_render.cpp    pa_render: marks on BGR frames -> BGR / YUV 4:2:0 (the refusals and the font: render_check.cpp, host only)
 //   engine_warp.cpp      pa_warp_perspective: BGR frames through a homography each (the refusals: warp_check.cpp, host only)
+//   engine_heat.cpp      pa_heat_accumulate: density maps on the top-down canvases (the refusals: heat_check.cpp, host only)
 //   engine_jpeg.cpp      pa_jpeg_encode: YUV 4:2:0 frames in HBM -> baseline JPEGs in host memory (the refusals, tables and header: jpeg_check.cpp, host only)
 //   engine_jpeg_decode.cpp  pa_jpeg_decode: baseline JPEGs in host memory -> BGR frames in HBM (the markers: jpeg_parse.cpp, host only)
 //   engine_activity.cpp  pa_frame_activity, pa_frames_median: frame statistics for the court-view filter (the refusals: activity_check.cpp, host only);
@@ -79,6 +80,8 @@ struct pa_engine {
     int render_last_path = 0; // 1 vector, 2 byte: what the last pa_render launched (pa_render_last_path)
     DevMem<uint8_t> warp_stage;     // pa_warp_perspective: the matrices and valid words of the call in flight, filled and read on the main stream only
     int warp_last_path = 0;   // 1 16-byte stores, 2 byte stores: what the last pa_warp_perspective launched (pa_warp_last_path)
+    DevMem<uint8_t> heat_stage;     // pa_heat_accumulate: lut, first, valid, boxes and points of the call in flight, filled and read on the main stream only
+    int heat_last_path = 0;   // 1 16-byte accesses, 2 byte accesses: what the last pa_heat_accumulate launched (pa_heat_last_path)
     JpegScratch* jpeg = nullptr;   // pa_jpeg_encode: slots, tables and the gathered frames, grown on demand, used on the main stream only (engine_jpeg.cpp)
     JpegDecScratch* jpeg_dec = nullptr;   // pa_jpeg_decode: compressed bytes, tables, coefficients and planes, likewise (engine_jpeg_decode.cpp)
     int jpeg_dec_last_path = 0;    // 1 vector, 2 byte: what the last pa_jpeg_decode launched for its colour pass (pa_jpeg_decode_last_path)

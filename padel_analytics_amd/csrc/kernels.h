@@ -291,6 +291,22 @@ struct WarpArgs {
 bool warp_vector_path_ok(const WarpArgs& a);            // ow a multiple of 16 and dst 16-byte aligned
 hipError_t launch_warp(const WarpArgs& a, hipStream_t s, int* vec_out = nullptr);            // *vec_out: 1 16-byte path, 0 byte path
 
+// Player density maps on the top-down canvases (heat.hip).  The caller (pa_heat_accumulate) has checked the call (heat_check.cpp) and
+// staged everything but the canvases and the state in HBM; the launcher only picks the 16-byte or the byte instantiation.
+struct HeatArgs {
+    uint8_t* canvas;        // n packed BGR canvases of oh x ow, blended in place
+    uint32_t* state;        // planes maps of oh x ow, carried from call to call; not overlapping the canvases
+    const uint32_t* lut;    // [256] B | G << 8 | R << 16 per level
+    const int32_t* first;   // [n + 1]
+    const int32_t* valid;   // [n]
+    const int32_t* box;     // [n][4] x0, y0, x1, y1, inclusive: the pixels the discs of frame i can reach (x0 > x1: none)
+    const int32_t* pts;     // [first[n]][3] x, y, plane
+    int n, oh, ow, planes, r, alpha, show_mask;
+    uint32_t full;
+};
+bool heat_vector_path_ok(const HeatArgs& a);            // ow a multiple of 16, canvases and state 16-byte aligned
+hipError_t launch_heat(const HeatArgs& a, hipStream_t s, int* vec_out = nullptr);            // *vec_out: 1 16-byte path, 0 byte path
+
 // Pillow-style separable resample pass over u8 images (coefficients precomputed on host):
 // out[b][y][x][c] = clip8((sum_k coef[o][k] * in[...lo[o]+k...] + (1<<21)) >> 22)
 struct ResamplePassArgs {

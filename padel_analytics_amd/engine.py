@@ -128,6 +128,7 @@ ABI_SYMBOLS = [
     "pa_box_histograms", "pa_box_histograms_check",
     "pa_render_scaled", "pa_render_scaled_check",
     "pa_warp_perspective", "pa_warp_check", "pa_warp_last_path",
+    "pa_heat_accumulate", "pa_heat_check", "pa_heat_last_path",
 ]
 
 
@@ -232,6 +233,10 @@ def load_library():
         lib.pa_warp_perspective.argtypes = [vp, vp, i32, i32, i32, vp, vp, C.c_uint32, vp, i32, i32]
         lib.pa_warp_check.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, C.c_char_p, sz]
         lib.pa_warp_last_path.argtypes = [vp]
+    if hasattr(lib, "pa_heat_accumulate"):         # (an older build under PADEL_LIB, likewise: asking it for a heat map raises)
+        lib.pa_heat_accumulate.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp, vp, i32, C.c_uint32, i32, i32, vp]
+        lib.pa_heat_check.argtypes = [i32, i32, i32, i32, vp, vp, vp, i32, C.c_uint32, i32, i32, vp, vp, vp, C.c_char_p, sz]
+        lib.pa_heat_last_path.argtypes = [vp]
     lib.pa_jpeg_encode.argtypes = [vp, vp, i32, i32, i32, C.POINTER(pa_yuv_desc), i32, vp, sz, vp]
     lib.pa_jpeg_check.argtypes = [i32, i32, i32, C.POINTER(pa_yuv_desc), i32, C.c_char_p, sz]
     lib.pa_jpeg_interval_bytes.argtypes = [i32]
@@ -373,6 +378,51 @@ def warp_check(n: int, h: int, w: int, oh: int, ow: int, matrices, valid, src: O
     why = C.create_string_buffer(512)
     rc = load_library().pa_warp_check(int(n), int(h), int(w), int(oh), int(ow), None if matrices is None else matrices.ctypes.data,
                                       None if valid is None else valid.ctypes.data, src, dst, why, 512)
+    return why.value.decode() if rc else None
+
+
+#: the limits of ``pa_heat_accumulate`` (PA_HEAT_MAX_POINTS per frame, PA_HEAT_MAX_PLANES, PA_HEAT_MAX_RADIUS, PA_HEAT_MAX_COORD, PA_HEAT_MAX_FULL)
+HEAT_MAX_POINTS, HEAT_MAX_PLANES, HEAT_MAX_RADIUS, HEAT_MAX_COORD, HEAT_MAX_FULL = 64, 4, 255, 32767, (1 << 24) - 1
+#: ``Engine.heat_last_path()``: how the last heat call moved its pixels
+HEAT_PATH_VECTOR, HEAT_PATH_BYTE = 1, 2
+
+
+def _heat_args(n, points, first, valid, lut):
+    """(points as (k, 3) int32 flattened or None, first as (n + 1,) int32 or None, valid as (n,) int32 or None, lut as 768 bytes or
+    None); ``ValueError`` for an array of another size than ``n`` frames, the points ``first`` announces, or 256 colours need."""
+    n = max(int(n), 0)
+    if first is not None:
+        first = np.ascontiguousarray(first, np.int32).reshape(-1)
+        if first.size != n + 1:
+            raise ValueError(f"heat: first has {first.size} entries, n + 1 = {n + 1} are needed")
+    if valid is not None:
+        valid = np.ascontiguousarray(valid, np.int32).reshape(-1)
+        if valid.size != n:
+            raise ValueError(f"heat: valid holds {valid.size} words, {n} frames need {n}")
+    if points is not None:
+        points = np.ascontiguousarray(points, np.int32).reshape(-1)
+        if points.size % 3 or (first is not None and points.size < 3 * int(first[-1])):
+            raise ValueError(f"heat: points holds {points.size} numbers: (x, y, plane) triples, as many as first[] announces, are needed")
+    if lut is not None:
+        lut = np.ascontiguousarray(lut, np.uint8).reshape(-1)
+        if lut.size != 768:
+            raise ValueError(f"heat: the lut holds {lut.size} bytes, 256 colours of B, G, R are 768")
+    return points, first, valid, lut
+
+
+def heat_check(n: int, oh: int, ow: int, planes: int, points, first, valid, r: int, full: int, alpha: int, show_mask: int, lut,
+               canvas: Optional[int] = 1, state: Optional[int] = 1 << 60) -> Optional[str]:
+    """None if ``pa_heat_accumulate`` would accept the call, else its reason for refusing it (``pa_heat_check``: host code, no GPU).
+    ``canvas``, ``state``: the addresses of the canvases and of the maps (compared, never read through; None is NULL, as it is for
+    the arrays; empty ``points`` are NULL too); the default is canvases at address 1 and a state far behind them."""
+    points, first, valid, lut = _heat_args(n, points, first, valid, lut)
+    lib = load_library()
+    if not hasattr(lib, "pa_heat_check"):
+        raise EngineError("heat_check: this build of the library has no pa_heat_check")
+    why = C.create_string_buffer(512)
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+    rc = lib.pa_heat_check(int(n), int(oh), int(ow), int(planes), ptr(points), ptr(first), ptr(valid), int(r),
+                           min(max(int(full), 0), 0xffffffff), int(alpha), int(show_mask), ptr(lut), canvas, state, why, 512)
     return why.value.decode() if rc else None
 
 
@@ -644,6 +694,32 @@ class Engine:
     def warp_last_path(self) -> int:
         """WARP_PATH_VECTOR (16 bytes at a time) / WARP_PATH_BYTE: what the last successful ``warp`` launched (0: none yet)."""
         return int(self.lib.pa_warp_last_path(self.handle))
+
+    def heat(self, canvas: DeviceBuffer, n: int, oh: int, ow: int, state: DeviceBuffer, planes: int, points, first, valid, r: int,
+             full: int, alpha: int, show_mask: int, lut) -> None:
+        """Add the ``points`` of ``n`` frames to the ``planes`` density maps of ``oh`` x ``ow`` uint32 in ``state`` and blend the maps,
+        as they stand after each frame, into that frame's packed BGR canvas in ``canvas``, in place (``pa_heat_accumulate``,
+        include/padel_hip.h; the numpy twin is ``heatmap.accumulate_host``).  ``points``: (x, y, plane) int32 triples, frame i owning
+        ``points[first[i]:first[i + 1]]``; ``valid[i] == 0`` leaves canvas i alone; ``r`` the splat's radius, ``full`` the density shown
+        at level 255, ``alpha`` 0..256 (0: the state alone), ``show_mask`` the planes summed for display, ``lut`` 256 x 3 bytes of BGR.
+        ``state`` is the caller's: zero at the start, carried from call to call.  Asynchronous: ordered with every later call of this
+        engine by its one compute stream; the arrays are consumed before the call returns.  What the kernel cannot run is an
+        ``EngineError``, nothing is launched."""
+        points, first, valid, lut = _heat_args(n, points, first, valid, lut)
+        if n >= 1 and oh >= 1 and ow >= 1 and canvas.nbytes < n * oh * ow * 3:
+            raise EngineError(f"heat: canvas holds {canvas.nbytes} bytes, {n} BGR canvases need {n * oh * ow * 3}")
+        if 1 <= planes <= HEAT_MAX_PLANES and oh >= 1 and ow >= 1 and state.nbytes < planes * oh * ow * 4:
+            raise EngineError(f"heat: state holds {state.nbytes} bytes, {planes} maps need {planes * oh * ow * 4}")
+        if not hasattr(self.lib, "pa_heat_accumulate"):
+            raise EngineError("heat: this build of the library has no pa_heat_accumulate")
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data
+        self._check(self.lib.pa_heat_accumulate(self.handle, canvas.ptr, int(n), int(oh), int(ow), state.ptr, int(planes), ptr(points),
+                                                ptr(first), ptr(valid), int(r), min(max(int(full), 0), 0xffffffff), int(alpha),
+                                                int(show_mask), ptr(lut)))
+
+    def heat_last_path(self) -> int:
+        """HEAT_PATH_VECTOR (16 bytes at a time) / HEAT_PATH_BYTE: what the last successful ``heat`` launched (0: none yet)."""
+        return int(self.lib.pa_heat_last_path(self.handle))
 
     def frame_activity(self, src: DeviceBuffer, n: int, h: int, w: int, ref: DeviceBuffer, prev: Optional[DeviceBuffer] = None, roi=None,
                        tau: int = 24, out: Optional[np.ndarray] = None) -> np.ndarray:

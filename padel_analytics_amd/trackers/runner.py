@@ -34,6 +34,18 @@ Additions (all off by default, the reference's sequential semantics stay the def
   without a homography is ``fill`` with ``NO COURT`` on it.  ``ValueError`` in ``__init__``: no tracker gives ``Keypoints``, a canvas the
   sink refuses, a ``FrameSink`` of another size than the canvas, ``fanout=True``.  ``timings["__topdown__"]``: seconds, frames, bytes;
 
+* ``heatmap=`` a path ending in ``.npy`` or ``.jpg``: where on the court each player spent the clip (``heatmap.HeatMap``; ``heatmap_options``:
+  its keyword arguments ``radius_m``, ``saturate_s``, ``alpha``, ``ids``, ``show``, and ``overlay``) — one density map per player id on the
+  top-down canvas (``topdown_options`` size it, with or without ``topdown=``), an Epanechnikov bump per frame under each player's feet.
+  ``.npy``: the final maps, (planes, h, w) uint32.  ``.jpg``: one picture, the maps blended over a ``fill`` canvas at ``full`` = their
+  largest density, the court's lines over it, made by the renderer and the JPEG encoder.  With ``topdown=`` every canvas batch gets one
+  ``Engine.heat`` (csrc/heat.hip) between the warp and the canvas render: the clip shows the map growing under the players
+  (``overlay=False``: accumulated, not shown).  Without ``topdown=`` the maps come from the stored results alone
+  (``heatmap.accumulate_host``): no frame is read for them, no GPU touched.  ``heat_state`` holds the final maps,
+  ``timings["__heatmap__"]`` the step's seconds and frames.  After ``identities=True``, so the planes are the relabelled ids; follows
+  ``segments=`` and ``distributed`` as ``topdown=`` does.  ``ValueError`` in ``__init__``: no tracker gives ``Keypoints``, none gives
+  ``Players``, ``fanout=True``, another suffix, an unknown or refused option.  The defaults are parameters, not findings;
+
 * ``collect_data=True`` (the reference's own switch, :74-79): the step also projects every frame's players and ball into the 2-D
   court (``projected_court.ProjectedCourt.project_batch``: the reference's homography state machine :633-647, the frames of a batch
   that need a homography solved together) and fills ``self.data_analytics`` (``analytics.DataAnalytics``) with the players' positions
@@ -97,7 +109,8 @@ class TrackingRunner:
                  fanout: bool = False, engine=None, host_queue_depth: Optional[int] = None, render=None,
                  court_inset: Optional[bool] = None, render_quality: int = 90, segments=None,
                  segment_options: Optional[dict] = None, identities: bool = False, identity_options: Optional[dict] = None,
-                 ball_trail: int = 0, render_scale: int = 1, topdown=None, topdown_options: Optional[dict] = None) -> None:
+                 ball_trail: int = 0, render_scale: int = 1, topdown=None, topdown_options: Optional[dict] = None,
+                 heatmap=None, heatmap_options: Optional[dict] = None) -> None:
         if isinstance(render_scale, bool) or render_scale not in (1, 2, 3, 4):
             raise ValueError(f"render_scale={render_scale!r}: 1, 2, 3 or 4 (the rendered clip at 1 / render_scale of the source's size)")
         self.render_scale = int(render_scale)
@@ -149,6 +162,12 @@ class TrackingRunner:
         self.topdown_view = None           # topdown.TopDownView: the canvas
         if topdown is not None:
             self._init_topdown(trackers, dict(topdown_options or {}))
+        self.heatmap = heatmap             # None | path ending in .npy (the final maps) or .jpg (a picture of them)
+        self.heat = None                   # heatmap.HeatMap: the parameters of the maps
+        self.heat_state: Optional[np.ndarray] = None   # the final maps, (planes, h, w) uint32: draw_and_collect_data
+        self._heat_overlay = True          # heatmap_options["overlay"]: the top-down clip shows the maps
+        if heatmap is not None:
+            self._init_heatmap(trackers, dict(heatmap_options or {}), dict(topdown_options or {}))
         # kept frames: None = all of [start, start + n_available); else [(lo, hi)] source frame numbers, set by _set_segments
         self.segments: Optional[list] = None
         self._run_range = (self.start, self.start + self.n_available)      # the source frames this run may keep
@@ -277,7 +296,7 @@ class TrackingRunner:
     RENDER_BATCH = 64
 
     def draw_and_collect_data(self) -> None:
-        if self.render is None and self.topdown is None and self.data_analytics is None:
+        if self.render is None and self.topdown is None and self.data_analytics is None and self.heatmap is None:
             print("runner: drawing / data collection is outside the hot path of this build (skipped)")
             return
         if self.distributed and D.rank() != 0:     # the results live on rank 0
@@ -287,14 +306,25 @@ class TrackingRunner:
         # inset_marks cached before the trackers had stored their results do not stay
         self._restart_collection()
         self._collect_seconds = 0.0
+        self._heat_seconds = 0.0
+        if self.heat is not None:
+            self.heat_state = self.heat.state()
         if self.render is None and self.topdown is None:      # the stored results alone: no frame is read, no GPU touched
             done = 0
             while done < self.n_available:
                 n = min(self.RENDER_BATCH, self.n_available - done)
                 self._collect(done, n)
+                if self.heat is not None:
+                    self._heat_host(done, n)
                 done += n
+            if self.heat is not None:
+                self._write_heatmap(None)
         else:
             done = self._render_clip()
+        if self.heat is not None:
+            self.timings["__heatmap__"] = {"seconds": self._heat_seconds, "frames": done}
+            print(f"runner: heat maps of {done} frames ({self.heat.planes} of {self.heat.view.w} x {self.heat.view.h}) written to {self.heatmap} "
+                  f"in {self._heat_seconds:.3f} s")
         if self.data_analytics is not None:
             self.data_analytics.frames = self.data_analytics.frames[:-1]          # reference :167: remove the extra frame
             print(f"runner: collected the players' positions of {done} frames ({len(self.data_analytics)} in data_analytics)")
@@ -461,6 +491,87 @@ class TrackingRunner:
         except ValueError as exc:
             raise ValueError(f"topdown: the {w} x {h} canvas cannot be written to {self.topdown}: {exc}") from None
 
+    _HEATMAP_OPTIONS = ("radius_m", "saturate_s", "alpha", "ids", "show", "overlay")
+
+    def _init_heatmap(self, trackers, options: dict, canvas_options: dict) -> None:
+        """``heatmap=``: the maps' parameters, and a ``ValueError`` now — before any tracker runs, before a file is created — for a
+        run that could not make them: ``fanout``, no tracker that gives ``Keypoints`` or none that gives ``Players``, a path that ends
+        in neither ``.npy`` nor ``.jpg``, an option ``HeatMap`` does not know or refuses, a canvas the JPEG encoder refuses."""
+        from .. import heatmap as HM, mjpeg, topdown as T
+        if self.fanout:
+            raise ValueError("heatmap= is not available with fanout=True")
+        for name in ("Keypoints", "Players"):
+            if not any(self._object_name(t) == name for t in trackers):
+                raise ValueError(f"heatmap=: no tracker gives {name}, so no player would ever have a place on the court")
+        suffix = os.path.splitext(str(self.heatmap))[1].lower()
+        if suffix not in (".npy", ".jpg"):
+            raise ValueError(f"heatmap={str(self.heatmap)!r}: the path must end in .npy (the maps) or .jpg (a picture of them)")
+        unknown = sorted(set(options) - set(self._HEATMAP_OPTIONS))
+        if unknown:
+            raise ValueError(f"heatmap_options: unknown {', '.join(unknown)} (known: {', '.join(self._HEATMAP_OPTIONS)})")
+        self._heat_overlay = bool(options.pop("overlay", True))
+        view = self.topdown_view if self.topdown_view is not None else T.TopDownView(self.projected_court, **canvas_options)
+        self.heat = HM.HeatMap(view, fps=self.video_info.fps, **options)
+        if suffix == ".jpg":
+            try:
+                mjpeg.check(1, view.h, view.w, video.yuv_desc(view.w, view.h, "i420", "bt601", "full"), self.render_quality)
+            except ValueError as exc:
+                raise ValueError(f"heatmap: the {view.w} x {view.h} canvas cannot be written to {self.heatmap}: {exc}") from None
+
+    def _heat_batch(self, lo: int, n: int) -> tuple:
+        """(points, first, valid) of kept frames [lo, lo + n) (``HeatMap.batch``): the frames' projections, and the stored ``Players``
+        of the tracker of that type (the last one, if several, as the projection takes them)."""
+        self._project_through(lo + n)
+        players = [None] * n
+        for tracker in self.trackers.values():
+            if self._object_name(tracker) == "Players":
+                players = [tracker.results[i] if i < len(tracker.results) else None for i in range(lo, lo + n)]
+        return self.heat.batch(self._projected[lo:lo + n], players)
+
+    def _heat_host(self, lo: int, n: int) -> None:
+        """Frames [lo, lo + n) into ``heat_state`` on the host: the state alone, nothing is shown."""
+        from .. import heatmap as HM
+        t0 = timeit.default_timer()
+        HM.accumulate_host(None, self.heat_state, *self._heat_batch(lo, n), **self.heat.call(overlay=False))
+        self._heat_seconds += timeit.default_timer() - t0
+
+    def _write_heatmap(self, eng, canvas=None, state=None) -> None:
+        """``heat_state`` into the file ``heatmap`` names.  ``.npy``: the array.  ``.jpg``: a ``fill`` canvas under the maps at ``full`` =
+        their largest density (``HeatMap.picture_full``), the court's lines on it, as full-range BT.601 YUV 4:2:0 through the JPEG
+        encoder — with ``eng`` on the device (``canvas``: a buffer of one canvas at least, ``state``: the maps there), else by the
+        numpy twins; the same bytes either way."""
+        from .. import engine as E, heatmap as HM, mjpeg, render as R
+        t0 = timeit.default_timer()
+        heat, view = self.heat, self.heat.view
+        if str(self.heatmap).lower().endswith(".npy"):
+            with open(self.heatmap, "wb") as fh:             # (a handle: np.save would add a second suffix to "MAPS.NPY")
+                np.save(fh, self.heat_state)
+        else:
+            h, w = view.h, view.w
+            desc, enc = video.yuv_desc(w, h, "i420", "bt601", "full"), video.YUV_ENC_COEFFS["bt601_full"]
+            blank = np.empty((1, h, w, 3), np.uint8)
+            blank[:] = view.fill
+            call = dict(heat.call(), full=heat.picture_full(self.heat_state))
+            nothing = (np.zeros((0, 3), np.int32), np.zeros(2, np.int32), np.ones(1, np.int32))
+            marks, first = R.pack([view.court_marks()])
+            if eng is None:
+                HM.accumulate_host(blank, self.heat_state, *nothing, **call)
+                raw = R.render_host(blank, marks, first, E.RENDER_YUV420, desc, enc).reshape(-1)
+                data, _ = mjpeg.encode_host(raw, 1, h, w, desc, self.render_quality)
+            else:
+                yuv = eng.alloc(video.yuv_span(1, h, w, desc))
+                try:
+                    canvas.upload(blank)
+                    eng.heat(canvas, 1, h, w, state, heat.planes, *nothing, **call)
+                    eng.render(canvas, 1, h, w, marks, first, yuv, out=E.RENDER_YUV420, geom=desc, enc=enc)
+                    data, _ = eng.jpeg_encode(yuv, 1, h, w, desc, self.render_quality)
+                finally:
+                    eng.synchronize()
+                    yuv.free()
+            with open(self.heatmap, "wb") as fh:
+                fh.write(np.asarray(data, np.uint8).tobytes())
+        self._heat_seconds += timeit.default_timer() - t0
+
     def topdown_marks(self, i: int) -> list:
         """The marks of canvas frame ``i`` (``TopDownView.marks``): the frame's projection, and the stored ``Players`` / ``Ball`` of the
         trackers of those types (the last one, if several, as the projection takes them)."""
@@ -485,9 +596,10 @@ class TrackingRunner:
         # (only a scale other than 1 is passed on: an engine that has never heard of the argument still renders at full size)
         scaled = {"scale": self.render_scale} if self.render_scale != 1 else {}
         bs = self.RENDER_BATCH
-        sink = top = dst = canvas = top_dst = None
+        sink = top = dst = canvas = top_dst = heat_dev = None
         own = top_own = False
         view = self.topdown_view
+        heat = self.heat
         top_seconds = 0.0
         t0 = timeit.default_timer()
         done = 0
@@ -503,6 +615,8 @@ class TrackingRunner:
                 print(f"runner: Writing the top-down view into {getattr(top, 'path', top)}")
                 canvas = eng.alloc(bs * view.h * view.w * 3)
                 top_dst = eng.alloc(video.yuv_span(bs, view.h, view.w, top.desc))
+                if heat is not None:                                  # the maps live in HBM for the walk, zero at its start
+                    heat_dev = eng.alloc(self.heat_state.nbytes).upload(self.heat_state)
                 top_seconds += timeit.default_timer() - ts
             with video.ResidentBatches(eng, self._batches(bs), bs, (h, w)) as walk:
                 for frames, _ in walk:
@@ -520,14 +634,26 @@ class TrackingRunner:
                         ts = timeit.default_timer()
                         matrices, valid = view.matrices(self._projected[done:done + n])
                         eng.warp(src, n, h, w, matrices, valid, canvas, view.h, view.w, fill=view.fill)
+                        if heat_dev is not None:
+                            th = timeit.default_timer()
+                            eng.heat(canvas, n, view.h, view.w, heat_dev, heat.planes, *self._heat_batch(done, n), **heat.call(self._heat_overlay))
+                            self._heat_seconds += timeit.default_timer() - th
                         marks, first = R.pack([self.topdown_marks(done + k) for k in range(n)])
                         eng.render(canvas, n, view.h, view.w, marks, first, top_dst, out=E.RENDER_YUV420, geom=top.desc, enc=top.enc)
                         top.write_device(top_dst.view(0, video.yuv_span(n, view.h, view.w, top.desc)), n)
                         top_seconds += timeit.default_timer() - ts
+                    elif heat is not None:                            # no canvas to show them on: the stored results alone, on the host
+                        self._heat_host(done, n)
                     done += n
+            if heat_dev is not None:
+                th = timeit.default_timer()
+                heat_dev.download(self.heat_state)
+                self._heat_seconds += timeit.default_timer() - th
+            if heat is not None:
+                self._write_heatmap(eng if heat_dev is not None else None, canvas, heat_dev)
         finally:
             eng.synchronize()
-            for buf in (dst, canvas, top_dst):
+            for buf in (dst, canvas, top_dst, heat_dev):
                 if buf is not None:
                     buf.free()
             if own:
