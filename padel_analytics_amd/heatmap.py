@@ -185,3 +185,38 @@ class HeatMap:
         """``full`` of the still picture: the largest shown density of ``state``, 1 for maps that are zero throughout, and at most
         ``engine.HEAT_MAX_FULL`` (a pixel beyond that — a player who did not move for half an hour — shows level 255 like it)."""
         return int(min(max(int(shown_density(state, self.show_mask).max()), 1), E.HEAT_MAX_FULL))
+
+    def save(self, path, state: np.ndarray, quality: int = 90, eng=None, canvas=None, state_dev=None) -> None:
+        """``state`` into the file ``path`` names.  ``.npy``: the array.  ``.jpg``: a ``fill`` canvas under the maps at ``full`` = their
+        largest density (``picture_full``), the court's lines on it, as full-range BT.601 YUV 4:2:0 through the JPEG encoder — with
+        ``eng`` on the device (``canvas``: a buffer of one canvas at least, ``state_dev``: the maps there), else by the numpy twins;
+        the same bytes either way."""
+        from . import mjpeg, render as R, video
+        view = self.view
+        if str(path).lower().endswith(".npy"):
+            with open(path, "wb") as fh:                     # (a handle: np.save would add a second suffix to "MAPS.NPY")
+                np.save(fh, state)
+            return
+        h, w = view.h, view.w
+        desc, enc = video.yuv_desc(w, h, "i420", "bt601", "full"), video.YUV_ENC_COEFFS["bt601_full"]
+        blank = np.empty((1, h, w, 3), np.uint8)
+        blank[:] = view.fill
+        call = dict(self.call(), full=self.picture_full(state))
+        nothing = (np.zeros((0, 3), np.int32), np.zeros(2, np.int32), np.ones(1, np.int32))
+        marks, first = R.pack([view.court_marks()])
+        if eng is None:
+            accumulate_host(blank, state, *nothing, **call)
+            raw = R.render_host(blank, marks, first, E.RENDER_YUV420, desc, enc).reshape(-1)
+            data, _ = mjpeg.encode_host(raw, 1, h, w, desc, quality)
+        else:
+            yuv = eng.alloc(video.yuv_span(1, h, w, desc))
+            try:
+                canvas.upload(blank)
+                eng.heat(canvas, 1, h, w, state_dev, self.planes, *nothing, **call)
+                eng.render(canvas, 1, h, w, marks, first, yuv, out=E.RENDER_YUV420, geom=desc, enc=enc)
+                data, _ = eng.jpeg_encode(yuv, 1, h, w, desc, quality)
+            finally:
+                eng.synchronize()
+                yuv.free()
+        with open(path, "wb") as fh:
+            fh.write(np.asarray(data, np.uint8).tobytes())

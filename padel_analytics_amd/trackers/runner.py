@@ -89,6 +89,7 @@ from typing import Callable, Optional
 import numpy as np
 
 from .. import dist as D, video
+from . import outputs as O
 from .tracker import NoPredictFrames, Tracker, _sampler, host_stages, relaxed_gc
 
 
@@ -132,17 +133,11 @@ class TrackingRunner:
         # reference :59-79: fixed keypoints keep the first homography for the whole clip
         from ..projected_court import ProjectedCourt
         from ..analytics import DataAnalytics
-        self.is_fixed_keypoints = False
-        for tracker in trackers:
-            if self._object_name(tracker) == "Keypoints":
-                self.is_fixed_keypoints = getattr(tracker, "fixed_keypoints_detection", None) is not None
+        self.is_fixed_keypoints = getattr(O.tracker_of(trackers, "Keypoints"), "fixed_keypoints_detection", None) is not None
         self.projected_court = ProjectedCourt(self.video_info)
         self.collect_data = collect_data
         self.data_analytics = DataAnalytics() if collect_data else None
         self.court_inset = bool(collect_data) if court_inset is None else bool(court_inset)   # None: on iff collect_data
-        self._projected: list = []         # FrameProjection of frames [0, len): filled in frame order, the homography carrying over
-        self._collect_seconds = 0.0
-        self._told: set = set()            # what was said once about missing data
         if collect_data:
             print("runner: Ready for data collection" + (" (fixed court keypoints)" if self.is_fixed_keypoints else ""))
         self.timings: dict = {}
@@ -156,18 +151,13 @@ class TrackingRunner:
         self._merge_pool = None            # sharded mode, rank 0: the thread of the sequential stages (created with the first one)
         self.render = render               # None | path of the file to write (.avi / .mjpeg / .mjpg: Motion-JPEG; anything else: .y4m) | video.FrameSink
         self.render_quality = int(render_quality)   # JPEG quality of a Motion-JPEG file (1..100)
-        if render is not None:
-            self._check_render_size()               # now: a scale or a sink that does not fit the clip costs no tracker run
         self.topdown = topdown             # None | path (suffixes as for render) | video.FrameSink: the clip seen from above
-        self.topdown_view = None           # topdown.TopDownView: the canvas
-        if topdown is not None:
-            self._init_topdown(trackers, dict(topdown_options or {}))
         self.heatmap = heatmap             # None | path ending in .npy (the final maps) or .jpg (a picture of them)
-        self.heat = None                   # heatmap.HeatMap: the parameters of the maps
         self.heat_state: Optional[np.ndarray] = None   # the final maps, (planes, h, w) uint32: draw_and_collect_data
-        self._heat_overlay = True          # heatmap_options["overlay"]: the top-down clip shows the maps
-        if heatmap is not None:
-            self._init_heatmap(trackers, dict(heatmap_options or {}), dict(topdown_options or {}))
+        # the outputs check themselves now: a ValueError costs no tracker run and leaves no file
+        self._outputs = out = O.OutputStep(self, trackers, topdown_options, heatmap_options)
+        self.topdown_view = out.top.view if out.top is not None else None        # topdown.TopDownView: the canvas
+        self.heat = out.maps.heat if out.maps is not None else None              # heatmap.HeatMap: the parameters of the maps
         # kept frames: None = all of [start, start + n_available); else [(lo, hi)] source frame numbers, set by _set_segments
         self.segments: Optional[list] = None
         self._run_range = (self.start, self.start + self.n_available)      # the source frames this run may keep
@@ -238,10 +228,7 @@ class TrackingRunner:
         if not self.identities:
             return
         from .. import identity as I
-        tracker = None
-        for t in self.trackers.values():           # the last one, as the projection takes it
-            if self._object_name(t) == "Players":
-                tracker = t
+        tracker = O.tracker_of(self.trackers.values(), "Players")      # the last one, as the projection takes it
         if tracker is None:
             print("runner: identities=True, but no tracker gives Players: nothing to relabel")
             return
@@ -281,114 +268,39 @@ class TrackingRunner:
     def _source_frames(self, lo: int, hi: int):
         return video.get_video_frames_generator(self.video_path, start=lo, stride=self.stride, end=hi)
 
+    # ------------------------------------------------------------------ the output step (outputs.py)
+    #: frames per Engine.render call / download / write of the output step
+    RENDER_BATCH = 64
+
+    @property
+    def _projected(self) -> list:
+        """``FrameProjection`` of frames [0, len): filled in frame order, the homography carrying over."""
+        return self._outputs.proj.frames
+
     def restart(self) -> None:
         for tracker in self.trackers.values():
             tracker.restart()
-        self._restart_collection()
-
-    def _restart_collection(self) -> None:
-        """Forget the projections and what was collected: the homography is a state machine over the frames from the first one on."""
-        if self.data_analytics is not None:        # (not its truth value: that is len(), 0 after a clip of no frames)
-            self.data_analytics.restart()
-        self._projected, self.projected_court.H = [], None
-
-    #: frames per Engine.render call / download / write of the render step
-    RENDER_BATCH = 64
+        self._outputs.proj.restart()
 
     def draw_and_collect_data(self) -> None:
-        if self.render is None and self.topdown is None and self.data_analytics is None and self.heatmap is None:
-            print("runner: drawing / data collection is outside the hot path of this build (skipped)")
-            return
-        if self.distributed and D.rank() != 0:     # the results live on rank 0
-            return
-        projecting = self.court_inset or self.data_analytics is not None
-        # every pass starts over: a second call does not append the clip's datapoints again, and projections that frame_marks /
-        # inset_marks cached before the trackers had stored their results do not stay
-        self._restart_collection()
-        self._collect_seconds = 0.0
-        self._heat_seconds = 0.0
-        if self.heat is not None:
-            self.heat_state = self.heat.state()
-        if self.render is None and self.topdown is None:      # the stored results alone: no frame is read, no GPU touched
-            done = 0
-            while done < self.n_available:
-                n = min(self.RENDER_BATCH, self.n_available - done)
-                self._collect(done, n)
-                if self.heat is not None:
-                    self._heat_host(done, n)
-                done += n
-            if self.heat is not None:
-                self._write_heatmap(None)
-        else:
-            done = self._render_clip()
-        if self.heat is not None:
-            self.timings["__heatmap__"] = {"seconds": self._heat_seconds, "frames": done}
-            print(f"runner: heat maps of {done} frames ({self.heat.planes} of {self.heat.view.w} x {self.heat.view.h}) written to {self.heatmap} "
-                  f"in {self._heat_seconds:.3f} s")
-        if self.data_analytics is not None:
-            self.data_analytics.frames = self.data_analytics.frames[:-1]          # reference :167: remove the extra frame
-            print(f"runner: collected the players' positions of {done} frames ({len(self.data_analytics)} in data_analytics)")
-        if projecting:
-            self.timings["__collect__"] = {"seconds": self._collect_seconds, "frames": done}
+        self._outputs.draw_and_collect_data()
 
-    @staticmethod
-    def _object_name(tracker) -> Optional[str]:
-        """The name of the tracker's result type (``Players`` / ``Ball`` / ``Keypoints`` are what the projection looks for); None
-        for a holder of results that states none."""
-        obj = getattr(tracker, "object", None)
-        return getattr(obj(), "__name__", None) if callable(obj) else None
+    def render_size(self) -> tuple:
+        """(width, height) of the rendered clip: the source's, divided by ``render_scale``."""
+        return self.video_info.width // self.render_scale, self.video_info.height // self.render_scale
 
-    def _tell_once(self, what: str) -> None:
-        if what not in self._told:
-            self._told.add(what)
-            print(f"runner: {what}")
-
-    def _project_through(self, hi: int) -> None:
-        """Projections of frames [len(self._projected), hi), ``RENDER_BATCH`` at a time, in frame order (the homography is a state
-        machine over the frames): each frame's Players / Ball / Keypoints are the stored results of the tracker of that type (the
-        last one, if several: reference :141-146)."""
-        t0 = timeit.default_timer()
-        while len(self._projected) < hi:
-            lo = len(self._projected)
-            n = min(self.RENDER_BATCH, hi - lo)
-            per = {"Keypoints": [None] * n, "Players": [None] * n, "Ball": [None] * n}
-            for tracker in self.trackers.values():
-                name = self._object_name(tracker)
-                if name in per:
-                    per[name] = [tracker.results[i] if i < len(tracker.results) else None for i in range(lo, lo + n)]
-            self._projected += self.projected_court.project_batch(per["Keypoints"], per["Players"], per["Ball"], self.is_fixed_keypoints)
-        self._collect_seconds += timeit.default_timer() - t0
-
-    def _collect(self, lo: int, n: int) -> None:
-        """Frames [lo, lo + n): project them, and put every projected player's position, in metres from the court centre, into
-        ``data_analytics`` (reference :541-567), one ``step`` per frame (:159-160).  Where the reference prints, frame after frame,
-        that data are missing, this says so once."""
-        self._project_through(lo + n)
-        t0 = timeit.default_timer()
-        shift = self.projected_court.court_keypoints.shift_point_origin
-        for fp in self._projected[lo:lo + n]:
-            if fp.H is None:
-                self._tell_once("no homography for some frames (no court keypoints): nothing is projected there")
-            elif fp.players is None:
-                self._tell_once("Missing data for players projection in some frames")
-            if self.data_analytics is not None:
-                for player in fp.players or ():
-                    self.data_analytics.add_player_position(
-                        id=player.id, position=shift(tuple(float(v) for v in player.projection), "meters"))
-                self.data_analytics.step(1)
-        self._collect_seconds += timeit.default_timer() - t0
+    def frame_marks(self, i: int) -> list:
+        """The marks of frame ``i`` of the annotated clip (``OutputStep.frame_marks``)."""
+        return self._outputs.frame_marks(i)
 
     def inset_marks(self, i: int) -> list:
-        """The court inset of frame ``i``, in the reference's order (:630-668): the panel and the court, the projected players,
-        the projected ball."""
-        self._project_through(i + 1)
-        fp = self._projected[i]
-        marks = self.projected_court.inset_marks()
-        if fp.players is not None:
-            marks += fp.players.projection_marks()
-        if fp.ball is not None:
-            marks += fp.ball.projection_marks()
-        return marks
+        return self._outputs.inset_marks(i)
+
+    def trail_marks(self, results, i: int) -> list:
+        return self._outputs.trail_marks(results, i)
+
+    def topdown_marks(self, i: int) -> list:
+        return self._outputs.topdown_marks(i)
 
     def _segment_start(self, i: int) -> int:
         """The first kept position of the segment that kept position ``i`` lies in (0 without segments)."""
@@ -398,286 +310,6 @@ class TrackingRunner:
                 return k
             k += hi - lo
         return 0 if self.segments is None else k
-
-    def trail_marks(self, results, i: int) -> list:
-        """The ball's trail at kept position ``i`` (reference ``ball_tracker.py:299-347``, ``draw_multiple_frames`` / ``draw_traj``:
-        a queue of the last positions, an invisible ball taking a place in it, each drawn as a white circle of radius 3 with a
-        yellow outline): the positions of the ``ball_trail`` kept frames i, i - 1, ... that lie in i's segment and hold a visible
-        ball, newest first, each a disc of radius 3 in RGB (255, 255, 0) under one of radius 2 in white."""
-        from .. import render as R
-        marks = []
-        for j in range(min(i, len(results) - 1), max(self._segment_start(i), i - self.ball_trail + 1) - 1, -1):
-            ball = results[j]
-            if ball.visibility:
-                x, y = ball.asint()
-                marks += [R.disc(x, y, 3, (0, 255, 255)), R.disc(x, y, 2, (255, 255, 255))]
-        return marks
-
-    def frame_marks(self, i: int) -> list:
-        """The marks of frame ``i`` (counted from ``start``; with segments: kept position ``i``, and the label shows the source frame,
-        ``source_index[i] - start + 1``): ``FRAME: i + 1`` (reference :118-127, there cv2's Hershey font in RGB
-        (255, 255, 0) with its bottom-left at (20, 50); here the renderer's font at scale 3), then every tracker's
-        ``results[i].marks(**tracker.draw_kwargs())`` in tracker order (with ``ball_trail`` the ``Ball`` tracker's is followed by
-        ``trail_marks``), then — with ``court_inset`` — ``inset_marks(i)``.  The
-        projections behind the inset are computed once, in frame order, from the results stored at that moment and kept until the next
-        ``draw_and_collect_data`` or ``restart``, which start over."""
-        from .. import render as R
-        k = 3
-        marks = R.text(f"FRAME: {int(self.source_index[i]) - self.start + 1 if i < len(self.source_index) else i + 1}", 20, 50 - (R.GLYPH_H * k - 1), k, (0, 255, 255))
-        for tracker in self.trackers.values():
-            if i < len(tracker.results):
-                marks += tracker.results[i].marks(**tracker.draw_kwargs())
-                if self.ball_trail > 0 and self._object_name(tracker) == "Ball":
-                    marks += self.trail_marks(tracker.results, i)
-        if self.court_inset:
-            marks += self.inset_marks(i)
-        return marks
-
-    def render_size(self) -> tuple:
-        """(width, height) of the rendered clip: the source's, divided by ``render_scale``."""
-        return self.video_info.width // self.render_scale, self.video_info.height // self.render_scale
-
-    def _check_render_size(self) -> None:
-        """``ValueError`` for a ``render_scale`` this clip's size does not allow — the rendered frames are YUV 4:2:0: the source must
-        be a multiple of the scale each way and the output even — naming the scales that would work, and for a caller's
-        ``FrameSink`` of another size than the rendered frames."""
-        w, h, s = self.video_info.width, self.video_info.height, self.render_scale
-        fits = [k for k in (1, 2, 3, 4) if w % k == 0 and h % k == 0 and (w // k) % 2 == 0 and (h // k) % 2 == 0 and w // k >= 2 and h // k >= 2]
-        if s != 1 and s not in fits:
-            raise ValueError(f"render_scale={s}: the {w} x {h} clip does not divide into even {s} x {s}-averaged frames "
-                             f"(render_scale that works for this clip: {', '.join(str(k) for k in fits) or 'none'})")
-        wo, ho = self.render_size()
-        if isinstance(self.render, video.FrameSink):
-            sw, sh = getattr(self.render, "w", None), getattr(self.render, "h", None)
-            if sw is not None and sh is not None and (int(sw), int(sh)) != (wo, ho):
-                raise ValueError(f"render: the sink takes {sw} x {sh} frames, the {w} x {h} clip at render_scale={s} gives {wo} x {ho}")
-
-    _MJPEG_SUFFIXES = (".avi", ".mjpeg", ".mjpg")
-
-    def _sink_for(self, target, w: int, h: int):
-        """(the sink ``target`` names, whether the runner owns — and closes — it).  A path ending in ``.avi``, ``.mjpeg`` or ``.mjpg``
-        gives a ``video.MjpegSink`` of ``render_quality``, any other path a ``video.Y4mSink``, of ``w`` x ``h`` frames."""
-        if isinstance(target, video.FrameSink):
-            return target, False
-        if os.path.splitext(str(target))[1].lower() in self._MJPEG_SUFFIXES:
-            return video.MjpegSink(target, w, h, fps=self.video_info.fps, quality=self.render_quality), True
-        return video.Y4mSink(target, w, h, fps=self.video_info.fps), True
-
-    def _make_sink(self):
-        """The sink the rendered frames go to (``_sink_for``), at ``render_size()``."""
-        return self._sink_for(self.render, *self.render_size())
-
-    def _init_topdown(self, trackers, options: dict) -> None:
-        """``topdown=``: the canvas, and a ``ValueError`` now — before any tracker runs, before a file is created — for a run that
-        could not write the clip: no tracker gives ``Keypoints`` (no homography, ever), ``fanout``, a canvas the sink refuses, a
-        caller's ``FrameSink`` of another size than the canvas."""
-        from .. import mjpeg, topdown as T
-        if self.fanout:
-            raise ValueError("topdown= is not available with fanout=True")
-        if not any(self._object_name(t) == "Keypoints" for t in trackers):
-            raise ValueError("topdown=: no tracker gives Keypoints, so no frame would have a court homography to be warped through")
-        self.topdown_view = view = T.TopDownView(self.projected_court, **options)
-        w, h = view.size
-        if isinstance(self.topdown, video.FrameSink):
-            sw, sh = getattr(self.topdown, "w", None), getattr(self.topdown, "h", None)
-            if sw is not None and sh is not None and (int(sw), int(sh)) != (w, h):
-                raise ValueError(f"topdown: the sink takes {sw} x {sh} frames, the canvas is {w} x {h}")
-            return
-        try:
-            if os.path.splitext(str(self.topdown))[1].lower() in self._MJPEG_SUFFIXES:
-                mjpeg.check(1, h, w, video.yuv_desc(w, h, "i420", "bt601", "full"), self.render_quality)
-            else:
-                video.yuv_span(1, h, w, video.yuv_desc(w, h, "i420"))
-        except ValueError as exc:
-            raise ValueError(f"topdown: the {w} x {h} canvas cannot be written to {self.topdown}: {exc}") from None
-
-    _HEATMAP_OPTIONS = ("radius_m", "saturate_s", "alpha", "ids", "show", "overlay")
-
-    def _init_heatmap(self, trackers, options: dict, canvas_options: dict) -> None:
-        """``heatmap=``: the maps' parameters, and a ``ValueError`` now — before any tracker runs, before a file is created — for a
-        run that could not make them: ``fanout``, no tracker that gives ``Keypoints`` or none that gives ``Players``, a path that ends
-        in neither ``.npy`` nor ``.jpg``, an option ``HeatMap`` does not know or refuses, a canvas the JPEG encoder refuses."""
-        from .. import heatmap as HM, mjpeg, topdown as T
-        if self.fanout:
-            raise ValueError("heatmap= is not available with fanout=True")
-        for name in ("Keypoints", "Players"):
-            if not any(self._object_name(t) == name for t in trackers):
-                raise ValueError(f"heatmap=: no tracker gives {name}, so no player would ever have a place on the court")
-        suffix = os.path.splitext(str(self.heatmap))[1].lower()
-        if suffix not in (".npy", ".jpg"):
-            raise ValueError(f"heatmap={str(self.heatmap)!r}: the path must end in .npy (the maps) or .jpg (a picture of them)")
-        unknown = sorted(set(options) - set(self._HEATMAP_OPTIONS))
-        if unknown:
-            raise ValueError(f"heatmap_options: unknown {', '.join(unknown)} (known: {', '.join(self._HEATMAP_OPTIONS)})")
-        self._heat_overlay = bool(options.pop("overlay", True))
-        view = self.topdown_view if self.topdown_view is not None else T.TopDownView(self.projected_court, **canvas_options)
-        self.heat = HM.HeatMap(view, fps=self.video_info.fps, **options)
-        if suffix == ".jpg":
-            try:
-                mjpeg.check(1, view.h, view.w, video.yuv_desc(view.w, view.h, "i420", "bt601", "full"), self.render_quality)
-            except ValueError as exc:
-                raise ValueError(f"heatmap: the {view.w} x {view.h} canvas cannot be written to {self.heatmap}: {exc}") from None
-
-    def _heat_batch(self, lo: int, n: int) -> tuple:
-        """(points, first, valid) of kept frames [lo, lo + n) (``HeatMap.batch``): the frames' projections, and the stored ``Players``
-        of the tracker of that type (the last one, if several, as the projection takes them)."""
-        self._project_through(lo + n)
-        players = [None] * n
-        for tracker in self.trackers.values():
-            if self._object_name(tracker) == "Players":
-                players = [tracker.results[i] if i < len(tracker.results) else None for i in range(lo, lo + n)]
-        return self.heat.batch(self._projected[lo:lo + n], players)
-
-    def _heat_host(self, lo: int, n: int) -> None:
-        """Frames [lo, lo + n) into ``heat_state`` on the host: the state alone, nothing is shown."""
-        from .. import heatmap as HM
-        t0 = timeit.default_timer()
-        HM.accumulate_host(None, self.heat_state, *self._heat_batch(lo, n), **self.heat.call(overlay=False))
-        self._heat_seconds += timeit.default_timer() - t0
-
-    def _write_heatmap(self, eng, canvas=None, state=None) -> None:
-        """``heat_state`` into the file ``heatmap`` names.  ``.npy``: the array.  ``.jpg``: a ``fill`` canvas under the maps at ``full`` =
-        their largest density (``HeatMap.picture_full``), the court's lines on it, as full-range BT.601 YUV 4:2:0 through the JPEG
-        encoder — with ``eng`` on the device (``canvas``: a buffer of one canvas at least, ``state``: the maps there), else by the
-        numpy twins; the same bytes either way."""
-        from .. import engine as E, heatmap as HM, mjpeg, render as R
-        t0 = timeit.default_timer()
-        heat, view = self.heat, self.heat.view
-        if str(self.heatmap).lower().endswith(".npy"):
-            with open(self.heatmap, "wb") as fh:             # (a handle: np.save would add a second suffix to "MAPS.NPY")
-                np.save(fh, self.heat_state)
-        else:
-            h, w = view.h, view.w
-            desc, enc = video.yuv_desc(w, h, "i420", "bt601", "full"), video.YUV_ENC_COEFFS["bt601_full"]
-            blank = np.empty((1, h, w, 3), np.uint8)
-            blank[:] = view.fill
-            call = dict(heat.call(), full=heat.picture_full(self.heat_state))
-            nothing = (np.zeros((0, 3), np.int32), np.zeros(2, np.int32), np.ones(1, np.int32))
-            marks, first = R.pack([view.court_marks()])
-            if eng is None:
-                HM.accumulate_host(blank, self.heat_state, *nothing, **call)
-                raw = R.render_host(blank, marks, first, E.RENDER_YUV420, desc, enc).reshape(-1)
-                data, _ = mjpeg.encode_host(raw, 1, h, w, desc, self.render_quality)
-            else:
-                yuv = eng.alloc(video.yuv_span(1, h, w, desc))
-                try:
-                    canvas.upload(blank)
-                    eng.heat(canvas, 1, h, w, state, heat.planes, *nothing, **call)
-                    eng.render(canvas, 1, h, w, marks, first, yuv, out=E.RENDER_YUV420, geom=desc, enc=enc)
-                    data, _ = eng.jpeg_encode(yuv, 1, h, w, desc, self.render_quality)
-                finally:
-                    eng.synchronize()
-                    yuv.free()
-            with open(self.heatmap, "wb") as fh:
-                fh.write(np.asarray(data, np.uint8).tobytes())
-        self._heat_seconds += timeit.default_timer() - t0
-
-    def topdown_marks(self, i: int) -> list:
-        """The marks of canvas frame ``i`` (``TopDownView.marks``): the frame's projection, and the stored ``Players`` / ``Ball`` of the
-        trackers of those types (the last one, if several, as the projection takes them)."""
-        self._project_through(i + 1)
-        per = {"Players": None, "Ball": None}
-        for tracker in self.trackers.values():
-            name = self._object_name(tracker)
-            if name in per and i < len(tracker.results):
-                per[name] = tracker.results[i]
-        return self.topdown_view.marks(self._projected[i], per["Players"], per["Ball"])
-
-    def _render_clip(self) -> int:
-        """The clip once more, ``RENDER_BATCH`` frames at a time: BGR in HBM (``video.ResidentBatches``); each batch is projected (and,
-        with the inset or the collection on, collected) first.  ``render=``: one ``Engine.render`` to YUV 4:2:0 in the sink's geometry,
-        one download, one write.  ``topdown=``: one ``Engine.warp`` of the batch into a BGR canvas buffer, one ``Engine.render`` of that
-        buffer with the canvas marks into the second sink's geometry, one download, one write.  ONE walk serves both.  -> the number
-        of frames."""
-        from .. import engine as E, render as R
-        eng = self.engine or E.default_engine()
-        w, h = self.video_info.width, self.video_info.height
-        wo, ho = self.render_size()
-        # (only a scale other than 1 is passed on: an engine that has never heard of the argument still renders at full size)
-        scaled = {"scale": self.render_scale} if self.render_scale != 1 else {}
-        bs = self.RENDER_BATCH
-        sink = top = dst = canvas = top_dst = heat_dev = None
-        own = top_own = False
-        view = self.topdown_view
-        heat = self.heat
-        top_seconds = 0.0
-        t0 = timeit.default_timer()
-        done = 0
-        try:
-            if self.render is not None:
-                sink, own = self._make_sink()
-                print(f"runner: Writing results into {getattr(sink, 'path', sink)}")
-                dst = eng.alloc(video.yuv_span(bs, ho, wo, sink.desc))
-                t0 = timeit.default_timer()
-            if self.topdown is not None:
-                ts = timeit.default_timer()
-                top, top_own = self._sink_for(self.topdown, *view.size)
-                print(f"runner: Writing the top-down view into {getattr(top, 'path', top)}")
-                canvas = eng.alloc(bs * view.h * view.w * 3)
-                top_dst = eng.alloc(video.yuv_span(bs, view.h, view.w, top.desc))
-                if heat is not None:                                  # the maps live in HBM for the walk, zero at its start
-                    heat_dev = eng.alloc(self.heat_state.nbytes).upload(self.heat_state)
-                top_seconds += timeit.default_timer() - ts
-            with video.ResidentBatches(eng, self._batches(bs), bs, (h, w)) as walk:
-                for frames, _ in walk:
-                    n = len(frames)
-                    if self.court_inset or self.data_analytics is not None:
-                        self._collect(done, n)
-                    elif top is not None:
-                        self._project_through(done + n)
-                    src = video.device_batch(frames)[0]
-                    if sink is not None:
-                        marks, first = R.pack([self.frame_marks(done + k) for k in range(n)])
-                        eng.render(src, n, h, w, marks, first, dst, out=E.RENDER_YUV420, geom=sink.desc, enc=sink.enc, **scaled)
-                        sink.write_device(dst.view(0, video.yuv_span(n, ho, wo, sink.desc)), n)
-                    if top is not None:
-                        ts = timeit.default_timer()
-                        matrices, valid = view.matrices(self._projected[done:done + n])
-                        eng.warp(src, n, h, w, matrices, valid, canvas, view.h, view.w, fill=view.fill)
-                        if heat_dev is not None:
-                            th = timeit.default_timer()
-                            eng.heat(canvas, n, view.h, view.w, heat_dev, heat.planes, *self._heat_batch(done, n), **heat.call(self._heat_overlay))
-                            self._heat_seconds += timeit.default_timer() - th
-                        marks, first = R.pack([self.topdown_marks(done + k) for k in range(n)])
-                        eng.render(canvas, n, view.h, view.w, marks, first, top_dst, out=E.RENDER_YUV420, geom=top.desc, enc=top.enc)
-                        top.write_device(top_dst.view(0, video.yuv_span(n, view.h, view.w, top.desc)), n)
-                        top_seconds += timeit.default_timer() - ts
-                    elif heat is not None:                            # no canvas to show them on: the stored results alone, on the host
-                        self._heat_host(done, n)
-                    done += n
-            if heat_dev is not None:
-                th = timeit.default_timer()
-                heat_dev.download(self.heat_state)
-                self._heat_seconds += timeit.default_timer() - th
-            if heat is not None:
-                self._write_heatmap(eng if heat_dev is not None else None, canvas, heat_dev)
-        finally:
-            eng.synchronize()
-            for buf in (dst, canvas, top_dst, heat_dev):
-                if buf is not None:
-                    buf.free()
-            if own:
-                sink.close()
-            if top_own:
-                top.close()
-        t1 = timeit.default_timer()
-
-        def written(s, owned):
-            b = getattr(s, "bytes_written", None)
-            return os.path.getsize(s.path) if b is None and owned else b
-
-        if sink is not None:
-            # (with topdown= as well: the walk without the top-down view's own steps)
-            seconds = t1 - t0 - (top_seconds if top is not None else 0.0)
-            self.timings["__render__"] = {"seconds": seconds, "frames": done, "bytes": written(sink, own)}
-            print(f"runner: rendered {done} frames in {seconds:.3f} s ({done / max(seconds, 1e-9):.1f} frames/s: render + download + write)")
-        if top is not None:
-            # alone: the whole walk; beside render=: its own steps (matrices and marks, warp, render, download / encode, write)
-            seconds = top_seconds if sink is not None else t1 - t0
-            self.timings["__topdown__"] = {"seconds": seconds, "frames": done, "bytes": written(top, top_own)}
-            print(f"runner: top-down view: {done} frames of {view.w} x {view.h} in {seconds:.3f} s ({done / max(seconds, 1e-9):.1f} frames/s: "
-                  f"warp + render + download + write)")
-        return done
 
     def _frames(self, lo: int = 0, hi: Optional[int] = None):
         """Frames [start + lo, start + hi) of the clip (hi None: to self.end); with segments: kept positions [lo, hi)."""

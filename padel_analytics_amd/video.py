@@ -676,6 +676,19 @@ class MjpegClip(_StagedSource):
 
 
 # ---------------------------------------------------------------------------------------------- sinks for rendered frames
+#: the suffixes of Motion-JPEG files, to write (``MjpegSink``, ``open_sink``) and to read (``_open_mjpeg``); any other path is a ``.y4m``
+MJPEG_SUFFIXES = (".avi", ".mjpeg", ".mjpg")
+
+
+def jpeg_desc(w: int, h: int, quality: int = 90, layout: str = "i420", pitch: Optional[int] = None, pitch_c: Optional[int] = None) -> dict:
+    """``yuv_desc`` of the full-range BT.601 frames the JPEG encoder is handed; ``ValueError`` with the encoder's words for frames or a
+    ``quality`` it refuses (``mjpeg.check``)."""
+    from . import mjpeg
+    desc = yuv_desc(w, h, layout, "bt601", "full", pitch, pitch_c)
+    mjpeg.check(1, int(h), int(w), desc, int(quality))
+    return desc
+
+
 class FrameSink:
     """Where rendered frames go (``TrackingRunner(render=...)``).  A sink states the form it takes them in — ``w``, ``h``, ``desc``
     (the ``pa_yuv_desc`` fields the renderer writes by: ``yuv_desc``) and ``enc`` (the ten integers of ``pa_yuv_enc``) — and receives
@@ -763,16 +776,14 @@ class MjpegSink(FrameSink):
 
     def __init__(self, path, w: int, h: int, fps: int = 30, quality: int = 90, layout: str = "i420", pitch: Optional[int] = None,
                  pitch_c: Optional[int] = None, max_riff_bytes: int = 2 ** 31 - 2 ** 24, on_device: bool = True):
-        from . import mjpeg
         self.path, self.w, self.h, self.fps, self.layout = str(path), int(w), int(h), int(fps), layout
         self.quality, self.on_device = int(quality), bool(on_device)
         suffix = os.path.splitext(self.path)[1].lower()
-        if suffix not in (".avi", ".mjpeg", ".mjpg"):
+        if suffix not in MJPEG_SUFFIXES:
             raise ValueError(f"MjpegSink: {self.path!r}: the suffix must be .avi, .mjpeg or .mjpg")
         self.avi = suffix == ".avi"
-        self.desc = yuv_desc(w, h, layout, "bt601", "full", pitch, pitch_c)
+        self.desc = jpeg_desc(w, h, quality, layout, pitch, pitch_c)
         self.enc = YUV_ENC_COEFFS["bt601_full"]
-        mjpeg.check(1, self.h, self.w, self.desc, self.quality)
         self.max_riff_bytes = int(max_riff_bytes)
         self.frames_written = 0
         self._closed_bytes = 0                         # of the files finished so far
@@ -877,6 +888,31 @@ class MjpegSink(FrameSink):
             self._finish()
 
 
+def _is_mjpeg(target) -> bool:
+    return os.path.splitext(str(target))[1].lower() in MJPEG_SUFFIXES
+
+
+def open_sink(target, w: int, h: int, fps: int = 30, quality: int = 90) -> tuple:
+    """(the sink ``target`` names, whether the caller owns — and closes — it).  A ``FrameSink`` is the caller's own.  A path ending in
+    ``.avi``, ``.mjpeg`` or ``.mjpg`` gives a ``MjpegSink`` of ``quality``, any other path a ``Y4mSink``, of ``w`` x ``h`` frames."""
+    if isinstance(target, FrameSink):
+        return target, False
+    return (MjpegSink(target, w, h, fps=fps, quality=quality) if _is_mjpeg(target) else Y4mSink(target, w, h, fps=fps)), True
+
+
+def check_sink(target, w: int, h: int, quality: int = 90) -> None:
+    """The ``ValueError`` ``open_sink`` would give for the path ``target`` — frames the file's format cannot hold —, without creating
+    the file; for a ``FrameSink`` that states another size than ``w`` x ``h``: "the sink takes ... frames"."""
+    if isinstance(target, FrameSink):
+        sw, sh = getattr(target, "w", None), getattr(target, "h", None)
+        if sw is not None and sh is not None and (int(sw), int(sh)) != (int(w), int(h)):
+            raise ValueError(f"the sink takes {sw} x {sh} frames")
+    elif _is_mjpeg(target):
+        jpeg_desc(w, h, quality)
+    else:
+        yuv_span(1, int(h), int(w), yuv_desc(w, h, "i420"))
+
+
 # .y4m files opened by path: one clip per file as it is on disk now (every read of the path — VideoInfo, each tracker's pass — shares
 # the mapping, the BGR staging and its memory of what it holds); a file that changed is opened afresh
 _Y4M_OPEN: dict = {}
@@ -895,7 +931,6 @@ def _open_y4m(p: str) -> YuvClip:
 
 # Motion-JPEG files opened by path, kept like _Y4M_OPEN; None for what is no Motion-JPEG file (the caller goes on to cv2)
 _MJPEG_OPEN: dict = {}
-MJPEG_SUFFIXES = (".avi", ".mjpeg", ".mjpg")
 
 
 def _open_mjpeg(p: str) -> Optional["MjpegClip"]:

@@ -387,12 +387,12 @@ def test_the_runner_picks_the_sink_by_suffix(tmp_path):
     for name, kind in (("x.avi", video.MjpegSink), ("x.mjpeg", video.MjpegSink), ("x.MJPG", video.MjpegSink), ("x.y4m", video.Y4mSink),
                        ("x.bin", video.Y4mSink)):
         runner = TrackingRunner(stub_trackers([], [], []), src, tmp_path / "out.mp4", render=tmp_path / name, render_quality=77)
-        sink, own = runner._make_sink()
+        sink, own = video.open_sink(runner.render, *runner.render_size(), runner.video_info.fps, runner.render_quality)
         assert type(sink) is kind and own and (sink.w, sink.h, sink.fps) == (64, 48, 24)
         if kind is video.MjpegSink:
             assert sink.quality == 77 and sink.enc == video.YUV_ENC_COEFFS["bt601_full"]
         sink.close()
     mine = video.MjpegSink(tmp_path / "mine.avi", 64, 48, on_device=False)
     runner = TrackingRunner(stub_trackers([], [], []), src, tmp_path / "out.mp4", render=mine)
-    assert runner._make_sink() == (mine, False) and runner.render_quality == 90
+    assert video.open_sink(runner.render, *runner.render_size()) == (mine, False) and runner.render_quality == 90
     mine.close()

@@ -13,6 +13,7 @@ from padel_analytics_amd import engine as E, render as R, video
 from padel_analytics_amd.trackers import TrackingRunner
 from tests import synth  # noqa: F401  (registers the synthetic:// frame source)
 from tests.court_script import stub_trackers
+from tests.twin_engine import StandInEngine
 
 ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "padel_analytics_amd" / "csrc"
@@ -181,14 +182,12 @@ def test_what_is_accepted():
 
 
 # ---------------------------------------------------------------------------------------------- the runner
-class StandInEngine:
-    """An engine that must not be asked for anything: what is checked here is decided before the render step touches one."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"the engine was asked for {name}")
-
-
 SRC_720P = "synthetic://?n=3&h=720&w=1280&fps=25&seed=1"
+
+
+def make_sink(runner):
+    """The sink the rendered frames go to, as the render step opens it: at ``render_size()``."""
+    return video.open_sink(runner.render, *runner.render_size(), runner.video_info.fps, runner.render_quality)
 
 
 def make_runner(tmp_path, src=SRC_720P, **kw):
@@ -200,7 +199,7 @@ def test_the_runner_builds_its_sink_at_the_scaled_size(tmp_path, s, size):
     for name, kind in (("x.y4m", video.Y4mSink), ("x.avi", video.MjpegSink)):
         runner = make_runner(tmp_path, render=tmp_path / name, render_scale=s)
         assert runner.render_scale == s and runner.render_size() == size
-        sink, own = runner._make_sink()
+        sink, own = make_sink(runner)
         assert type(sink) is kind and own and (sink.w, sink.h, sink.fps) == (*size, 25)
         assert sink.desc == video.yuv_desc(*size, "i420", "bt601", "full" if kind is video.MjpegSink else "limited")
         sink.close()
@@ -209,8 +208,8 @@ def test_the_runner_builds_its_sink_at_the_scaled_size(tmp_path, s, size):
 def test_a_4k_clip_gets_its_avi_at_half_size(tmp_path):
     src = "synthetic://?n=1&h=2160&w=3840&fps=30&seed=1"
     with pytest.raises(ValueError, match="2560"):                              # today's rule: the JPEG encoder's width limit
-        make_runner(tmp_path, src, render=tmp_path / "full.avi")._make_sink()
-    sink, _ = make_runner(tmp_path, src, render=tmp_path / "half.avi", render_scale=2)._make_sink()
+        make_sink(make_runner(tmp_path, src, render=tmp_path / "full.avi"))
+    sink, _ = make_sink(make_runner(tmp_path, src, render=tmp_path / "half.avi", render_scale=2))
     assert (sink.w, sink.h) == (1920, 1080)
     sink.close()
 
@@ -233,5 +232,5 @@ def test_a_sink_of_another_size_is_refused(tmp_path):
             make_runner(tmp_path, render=full, render_scale=2)
         with pytest.raises(ValueError, match=r"sink takes 640 x 360.*render_scale=1 gives 1280 x 720"):
             make_runner(tmp_path, render=half)
-        assert make_runner(tmp_path, render=half, render_scale=2)._make_sink() == (half, False)
-        assert make_runner(tmp_path, render=full)._make_sink() == (full, False)
+        assert make_sink(make_runner(tmp_path, render=half, render_scale=2)) == (half, False)
+        assert make_sink(make_runner(tmp_path, render=full)) == (full, False)

@@ -12,7 +12,7 @@ from padel_analytics_amd.trackers.ball_tracker import Ball
 from padel_analytics_amd.trackers.players_tracker import Players
 from tests import identity_script as S, synth  # noqa: F401  (synth registers the synthetic:// frame source)
 from tests.court_script import Stored, court_for, project, stub_trackers
-from tests.fake_engine import FakeEngine
+from tests.twin_engine import FlatTwinEngine as TwinEngine, StandInEngine
 
 BLACK, BLUE, YELLOW, WHITE = (0, 0, 0), (255, 0, 0), (0, 255, 255), (255, 255, 255)
 
@@ -119,13 +119,6 @@ def test_marks_of_a_frame_without_a_homography():
 
 
 # ---------------------------------------------------------------------------------------------- the runner, before anything runs
-class StandInEngine:
-    """An engine that must not be asked for anything: what is checked here is decided before the render step touches one."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"the engine was asked for {name}")
-
-
 SRC_720P = "synthetic://?n=3&h=720&w=1280&fps=25&seed=1"
 
 
@@ -139,7 +132,7 @@ def test_the_runner_sets_up_the_canvas(tmp_path):
     runner = make_runner(tmp_path, topdown=tmp_path / "top.y4m", topdown_options=dict(px_per_m=20, margin_m=1, fill=(1, 2, 3)), render_scale=2)
     assert runner.topdown_view.size == (240, 440) and runner.topdown_view.fill == (1, 2, 3)      # render_scale does not apply
     for name, kind in (("t.y4m", video.Y4mSink), ("t.avi", video.MjpegSink)):
-        sink, own = runner._sink_for(tmp_path / name, *runner.topdown_view.size)
+        sink, own = video.open_sink(tmp_path / name, *runner.topdown_view.size, runner.video_info.fps, runner.render_quality)
         assert type(sink) is kind and own and (sink.w, sink.h, sink.fps) == (240, 440, 25)
         sink.close()
     assert make_runner(tmp_path).topdown is None and make_runner(tmp_path).topdown_view is None
@@ -170,25 +163,6 @@ def test_what_the_runner_refuses_before_any_tracker_runs(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------- the runner over a recording engine
-class TwinEngine(FakeEngine):
-    """``FakeEngine`` plus ``warp`` and ``render`` answered by the numpy twins on the stand-in buffers; every call is recorded."""
-
-    def __init__(self):
-        super().__init__(0)
-        self.calls = []
-
-    def warp(self, src, n, h, w, matrices, valid, dst, oh, ow, fill=(0, 0, 0)):
-        self.calls.append(("warp", n, h, w, oh, ow, tuple(fill)))
-        frames = src.arr[:n * h * w * 3].reshape(n, h, w, 3)
-        dst.arr[:n * oh * ow * 3] = T.warp_host(frames, matrices, valid, oh, ow, fill).reshape(-1)
-
-    def render(self, src, n, h, w, marks, first, dst, out=E.RENDER_BGR, geom=None, enc=None, scale=1):
-        self.calls.append(("render", n, h, w))
-        frames = src.arr[:n * h * w * 3].reshape(n, h, w, 3)
-        got = R.render_host(frames, marks, first, out, geom, enc, scale=scale).reshape(-1)
-        dst.arr[:got.size] = got
-
-
 N, H, W = 5, 96, 160
 SRC = f"synthetic://?n={N}&h={H}&w={W}&fps=30&seed=4"
 OPTIONS = dict(px_per_m=6, margin_m=1, fill=(9, 8, 7))        # a 72 x 132 canvas
